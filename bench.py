@@ -10,7 +10,12 @@ level's segment behind the C ABI, gf_dist_*, overlapped with the rest of the rev
 before the timed region, reported as prep_s); `end_to_end` in the same line is the training-loop figure -- a NEW batch
 every step (host graph preparation + upload overlapped on a second handle) + forward + backward + Adam.
 `--workload cfg2` / `cfg5` run BASELINE configs[1] / configs[4] (RisiContraction_18 N=32 C=64, RisiContraction_50 N=24
-C=32, batch 256) as the headline; the default line carries both under `extra`, 20 steps each, with their own rooflines.
+C=32, batch 256) as the headline; the --full line carries both under `extra`, 20 steps each, with their own rooflines.
+
+A plain run sets up, runs --warmup untimed steps, times exactly --steps steps (one timed region unless --repeats says
+otherwise), writes the last step's outputs when --dump-outputs DIR is given, and prints the line.  Everything else -- the
+per-kernel pass and roofline, the timed region's spread over five repeats, end_to_end, the `extra` workloads, the HBM copy
+probes, the CPU baselines and prep_s -- runs only with --full, and takes runs of its own.
 
 Multi-GPU: `python bench.py --gpus N` spawns N ranks itself (torch.distributed.run on 127.0.0.1) unless it already runs
 under a launcher (WORLD_SIZE set, which must equal N).  Molecules / graphs are independent, so ranks shard them (weak
@@ -141,6 +146,24 @@ def timed_run(torch, ctx, step, steps, warmup, fence, notiming=False, repeats=1,
     return elapsed, timers
 
 
+DUMP_SAMPLE = 1 << 21   # elements kept of an output larger than this (8 MiB of fp32): the whole dump stays below 64 MB
+
+
+def dump_outputs(torch, out_dir, arrays):
+    """--dump-outputs: {name: device tensor} of the last timed step -> out_dir/<name>.npy in float32.  An output of more than
+    DUMP_SAMPLE elements is written as the same seeded sample of its flattened elements in every run, so that two builds compare
+    element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, t in arrays.items():
+        x = t.detach()
+        if x.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(0).integers(0, x.numel(), DUMP_SAMPLE))
+            x = x.reshape(-1)[torch.as_tensor(idx, device=x.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), x.to(torch.float32).cpu().numpy())
+
+
 def median(xs):
     xs = sorted(xs)
     return xs[len(xs) // 2] if len(xs) % 2 else 0.5 * (xs[len(xs) // 2 - 1] + xs[len(xs) // 2])
@@ -221,7 +244,7 @@ def setup_contraction(workload, args, torch, gf, dev, world, rank, ctx):
             "config": {"workload": "%s: RisiContraction_%d fwd+bwd, N=%d, C=%d, batch=%d graphs/GPU, device-resident"
                                    % (workload, K, N, C, B),
                        "parallelism": "graph-sharded x%d, no collective" % world}}
-    return step, finish, cpu, meta, None
+    return step, finish, cpu, meta, None, lambda: {"out": Out, "dP": dP}
 
 
 # ---- cfg3: the batched SMP_omega step --------------------------------------------------------------------------------------
@@ -243,9 +266,11 @@ def setup_smp(args, torch, gf, dev, world, rank, ctx):
     t0 = time.perf_counter()
     net.prepare(mols)
     prep_first_s = time.perf_counter() - t0   # includes the one-time device allocations (pooled afterwards)
-    t0 = time.perf_counter()
-    net.prepare(mols)
-    prep_s = time.perf_counter() - t0         # steady state: what a training loop pays per new batch
+    prep_s = None
+    if args.full:
+        t0 = time.perf_counter()
+        net.prepare(mols)
+        prep_s = time.perf_counter() - t0     # steady state: what a training loop pays per new batch
     if nK == 18:
         params = torch.as_tensor(smp_params(C, F, D, L, 1).astype(np.float32)).to(dev)
     else:
@@ -518,8 +543,9 @@ def setup_smp(args, torch, gf, dev, world, rank, ctx):
                        "parallelism": ("molecule-sharded x%d, RCCL all-reduce of the %d gradient floats inside gf_smp_backward (per-level segments, overlapped)"
                                        % (world, net.n_params)) if world > 1 else "single GPU",
                        "timed_region": "device step (index tables resident); see end_to_end for the loop with a new batch every step",
-                       "prep_s": round(prep_s, 3), "prep_first_s": round(prep_first_s, 3), "work": work}}
-    return step, finish, cpu, meta, (net, end_to_end)
+                       "prep_s": None if prep_s is None else round(prep_s, 3), "prep_first_s": round(prep_first_s, 3), "work": work}}
+    # what a caller of the step receives: forward's prediction, loss and feature vectors, backward's parameter gradient
+    return step, finish, cpu, meta, (net, end_to_end), lambda: {"predict": net.predict, "loss": net.loss, "feature": net.feature, "grads": grads}
 
 
 # ---- launcher ---------------------------------------------------------------------------------------------------------------
@@ -586,19 +612,27 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; the line reports the median and the spread")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; the line reports the median and the spread (default 1, with --full 5)")
     ap.add_argument("--workload", default="cfg3", choices=["cfg2", "cfg3", "cfg5"])
     ap.add_argument("--batch", type=int, default=0, help="graphs / molecules per GPU (default 256 for cfg2/cfg5, 1024 for cfg3)")
     ap.add_argument("--N", type=int, default=32)
     ap.add_argument("--C", type=int, default=64)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the cfg2 / cfg5 / end_to_end sections of the default line")
+    ap.add_argument("--no-extra", action="store_true", help="skip the cfg2 / cfg5 / end_to_end sections of the --full line")
     ap.add_argument("--unfused", action="store_true", help="cfg3: op-by-op level pipeline instead of the fused level kernels")
     ap.add_argument("--plumbing", action="store_true", help="CPU-only check of the multi-rank plumbing (gloo); measures nothing")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel pass and roofline, end_to_end, the extra workloads, the HBM copy probes and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed to DIR/<name>.npy (float32; outputs above %d elements as a "
+                         "fixed seeded sample)" % DUMP_SAMPLE)
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --batch (default 1024 molecules / 256 graphs) PER GPU; strong: --batch (default 8192 / 2048) in TOTAL, split "
                          "evenly over the ranks (SURVEY 8d cfg4 asks for both)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_spawn(args)
@@ -638,17 +672,19 @@ def main():
         torch.cuda.synchronize()
 
     if args.workload in ("cfg2", "cfg5"):
-        step, finish, cpu, meta, keep = setup_contraction(args.workload, args, torch, gf, dev, world, rank, ctx)
+        step, finish, cpu, meta, keep, outputs = setup_contraction(args.workload, args, torch, gf, dev, world, rank, ctx)
     else:
-        step, finish, cpu, meta, keep = setup_smp(args, torch, gf, dev, world, rank, ctx)
+        step, finish, cpu, meta, keep, outputs = setup_smp(args, torch, gf, dev, world, rank, ctx)
 
-    notiming = bool(os.environ.get("GF_BENCH_NOTIMING"))
+    notiming = bool(os.environ.get("GF_BENCH_NOTIMING")) or not args.full   # the per-kernel pass is a --full measurement
     quiesce = ctx.dist_quiesce if (world > 1 or force) else None   # bounded wait for the collectives ahead of every blocking synchronize
     reps, timers = timed_run(torch, ctx, step, args.steps, args.warmup, fence, notiming, repeats=args.repeats, quiesce=quiesce)
     # every repeat is the contract's timed region (exactly --steps steps between barrier + synchronize): MAX over ranks per repeat, the
     # line's value is the MEDIAN repeat, the spread rides beside it
     reps = [gd.max_over_ranks(e, dist, side) for e in reps]
     elapsed = median(reps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, outputs())
 
     line = None
     if rank == 0:
@@ -657,7 +693,8 @@ def main():
         line = {"metric": meta["metric"], "value": round(value, 1), "unit": meta["unit"], "n_gpus": world,
                 "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
                 "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": meta.get("dtype", "f32"), "data": "synthetic",
-                "config": meta["config"], "roofline": finish(timers, ms_per_step, args.steps)}
+                "config": meta["config"],
+                "roofline": finish(timers, ms_per_step, args.steps) if args.full else {"note": "per-kernel figures: run with --full"}}
         line["timed_region"] = {"repeats": len(reps), "steps_each": args.steps, "reported": "median",
                                 "ms_per_step_min": round(1e3 * min(reps) / args.steps, 4), "ms_per_step_median": round(ms_per_step, 4),
                                 "ms_per_step_max": round(1e3 * max(reps) / args.steps, 4)}
@@ -673,11 +710,12 @@ def main():
                                   "allreduce_ms_per_step": round(ar[0] / args.steps, 4) if ar else None,
                                   "watchdog_s": float(os.environ.get("GF_DIST_TIMEOUT_S", "1800")),
                                   "note": "HIP events around each ncclAllReduce on the communicator's stream (rank 0), live inside the timed region"}
-        line["roofline"]["timing"] = ("HIP events on the kernels' stream: the dominant kernel live inside the timed region, "
-                                      "the other kernels in an identical pass of the same steps just before it")
+        if args.full:
+            line["roofline"]["timing"] = ("HIP events on the kernels' stream: the dominant kernel live inside the timed region, "
+                                          "the other kernels in an identical pass of the same steps just before it")
     # the sections below run on every rank that takes part in them, outside the timed region
     e2e = None
-    if keep is not None and not args.no_extra:
+    if keep is not None and args.full and not args.no_extra:
         net, end_to_end = keep
         if rank == 0:
             line["config"]["device_GB"] = round(net.device_bytes()[0] / 1e9, 2)   # HBM held by the batch's buffers (lazy ones included)
@@ -689,7 +727,7 @@ def main():
                 dt = gd.max_over_ranks(e2e["ms_per_step"], dist, side)
                 e2e.update(ms_per_step=round(dt, 3), value=round(world * meta["units_per_step"] / (dt * 1e-3), 1), unit="molecules/s, all %d GPUs" % world,
                            host_threads_per_rank=os.environ.get("GF_PREP_THREADS"))
-    if rank == 0:
+    if rank == 0 and args.full:
         if e2e:
             line["end_to_end"] = e2e
         if world == 1 and not args.no_extra and args.workload == "cfg3" and not args.unfused:
@@ -721,7 +759,7 @@ def main():
                         a32 = copy.copy(args)
                         a32.C = Cx
                         c32 = gf.Context(dev.index)
-                        s32, _, _, m32, k32 = setup_smp(a32, torch, gf, dev, 1, 0, c32)
+                        s32, _, _, m32, k32, _ = setup_smp(a32, torch, gf, dev, 1, 0, c32)
                         els, _ = timed_run(torch, c32, s32, 20, 3, torch.cuda.synchronize, True, repeats=3)
                         el = median(els)
                         extra["cfg3_C%d" % Cx] = {"metric": m32["metric"], "value": round(m32["units_per_step"] * 20 / el, 1), "unit": m32["unit"],
@@ -738,7 +776,7 @@ def main():
                         a7 = copy.copy(args)
                         a7.C, a7.nK = 10, nK
                         c7 = gf.Context(dev.index)
-                        s7, _, _, m7, k7 = setup_smp(a7, torch, gf, dev, 1, 0, c7)
+                        s7, _, _, m7, k7, _ = setup_smp(a7, torch, gf, dev, 1, 0, c7)
                         els, _ = timed_run(torch, c7, s7, 20, 3, torch.cuda.synchronize, True, repeats=3)
                         el = median(els)
                         extra[name] = {"metric": "molecules/sec fwd+bwd, SMP_2D_ver%d wiring (RisiContraction_%d per node)" % (6 if nK == 10 else 7, nK),
@@ -790,7 +828,7 @@ def main():
             for wl in ("cfg2", "cfg5"):
                 try:
                     ectx = gf.Context(dev.index)
-                    estep, efinish, ecpu, emeta, _ = setup_contraction(wl, args, torch, gf, dev, 1, 0, ectx)
+                    estep, efinish, ecpu, emeta, _, _ = setup_contraction(wl, args, torch, gf, dev, 1, 0, ectx)
                     els, et = timed_run(torch, ectx, estep, 20, 3, torch.cuda.synchronize, notiming, repeats=3)
                     el = median(els)
                     ems = 1e3 * el / 20

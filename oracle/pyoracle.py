@@ -23,11 +23,19 @@ def build(force=False):
     if force or not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(x) for x in srcs):
         subprocess.check_call(["make", "-C", _HERE, "libgf_oracle.so"])
     ref_root = os.environ.get("GF_REFERENCE", "/root/reference")
-    ref_so = os.path.join(_HERE, "_ref", "libgf_ref.so")
-    shim = os.path.join(_HERE, "ref_shim.cpp")
+    outs = [os.path.join(_HERE, "_ref", f) for f in ("libgf_ref.so", "dropin_reference_check")]
+    deps = [os.path.join(_HERE, "ref_shim.cpp")] + dropin_sources()
     if os.path.isdir(os.path.join(ref_root, "GraphFlow")):
-        if force or not os.path.exists(ref_so) or os.path.getmtime(ref_so) < os.path.getmtime(shim):
+        if force or not all(map(os.path.exists, outs)) or min(map(os.path.getmtime, outs)) < max(map(os.path.getmtime, deps)):
             subprocess.check_call(["make", "-C", _HERE, "ref", "GF_REFERENCE=" + ref_root])
+
+
+def dropin_sources():
+    """What oracle/_ref/dropin_reference_check (the op headers compiled against the reference's own containers) is built from."""
+    root = os.path.dirname(_HERE)
+    host = os.path.join(root, "graphflow_amd", "host")
+    return ([os.path.join(root, "tests", "cpp", "dropin_reference_check.cpp"), os.path.join(root, "include", "gf_hip.h")]
+            + [os.path.join(host, f) for f in sorted(os.listdir(host)) if f.endswith(".h")])
 
 
 def _load(path):

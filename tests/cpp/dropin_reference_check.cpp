@@ -1,7 +1,7 @@
 // dropin_reference_check.cpp -- compile-only proof that the HIP op classes drop into the REAL reference tree:
 // the reference's own containers are included first (-I<reference>/GraphFlow), then our op header, and the op is
 // used exactly like GraphFlow_gpu/SMP_omega_gpu.h uses RisiContraction_18_gpu.  Built only where the reference
-// is mounted (tests/test_host_cpp.py); nothing from the reference is copied.
+// is mounted (oracle/Makefile `ref`, run by build()); nothing from the reference is copied.
 #include "Matrix.h"
 #include "Tensor3D.h"
 #include "Tensor4D.h"

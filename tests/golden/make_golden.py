@@ -520,6 +520,36 @@ def checkpoint_fixture():
                                           feat.shape[1], D, cap, maxV)
 
 
+def reference_check_fixtures(ref):
+    """The real reference's outputs on the inputs of the oracle-versus-reference checks (tests/test_oracle_golden.py,
+    tests/test_smp_cpu.py), so that those checks run where the reference is not mounted: contractions on the seed-99
+    stream, SMP_omega on three random molecules and on the edge molecules (phi as JSON text)."""
+    from inputs import edge_molecules
+    out = {}
+    rng = np.random.default_rng(99)
+    for K in (4, 10, 18, 50):
+        for (N, Cc) in ((2, 1), (4, 3), (7, 2)):
+            P = rng.uniform(-1, 1, (N, N, N, Cc))
+            A = rng.uniform(-1, 1, (N, N))
+            G = rng.uniform(-1, 1, (N, N, K, Cc))
+            d0 = rng.uniform(-1, 1, (N, N, N, Cc))
+            tag = "r%d_%dx%d" % (K, N, Cc)
+            out[tag + "__fwd"] = ref.contract_forward(K, P, A)
+            out[tag + "__bwd"] = ref.contract_backward(K, G, A, d0)
+
+    def smp(tag, r):
+        out[tag + "__phi"] = np.array(json.dumps([[list(map(int, f)) for f in lv] for lv in r["phi"]]))
+        out[tag + "__predict"] = np.array([r["predict"]])
+        out[tag + "__grads"] = r["grads"]
+
+    for seed in (11, 12, 13):
+        adj, feat, tgt = synthetic_molecule(seed, nV=5 + seed % 7)
+        smp("random%d" % seed, pyoracle.reference_smp_omega(adj, feat, tgt, smp_params(4, 5, 2, 2, seed), 2, 4, 2, 8))
+    for name, adj, feat, tgt in edge_molecules():
+        smp("edge_" + name, pyoracle.reference_smp_omega(adj, feat, tgt, smp_params(4, 5, 2, 3, 21), 3, 4, 2, 6, max_nVertices=12))
+    return out
+
+
 def main():
     pyoracle.build()
     ref = pyoracle.reference()
@@ -531,6 +561,7 @@ def main():
     np.savez_compressed(os.path.join(HERE, "contractions_16x8.npz"), **contraction_16x8_fixtures(ref))
     np.savez_compressed(os.path.join(HERE, "stack.npz"), **stack_fixtures(ref))
     np.savez_compressed(os.path.join(HERE, "dropout.npz"), **dropout_fixtures(ref))
+    np.savez_compressed(os.path.join(HERE, "reference_checks.npz"), **reference_check_fixtures(ref))
     np.savez_compressed(os.path.join(HERE, "smp.npz"), **smp_fixtures())
     np.savez_compressed(os.path.join(HERE, "smp_big.npz"), **big_field_fixtures())
     checkpoint_fixture()
@@ -540,7 +571,7 @@ def main():
     headline_fixture()
     with open(os.path.join(HERE, "structural_50.json"), "w") as fh:
         json.dump(structural_50(), fh, indent=1)
-    for f in ("contractions.npz", "contractions_wide.npz", "mixers.npz", "smp.npz", "structural_50.json", "smp_syn12_checkpoint.txt", "dropout.npz", "smp_train.npz", "smp_headline.npz", "smp_physics.npz"):
+    for f in ("contractions.npz", "contractions_wide.npz", "mixers.npz", "reference_checks.npz", "smp.npz", "structural_50.json", "smp_syn12_checkpoint.txt", "dropout.npz", "smp_train.npz", "smp_headline.npz", "smp_physics.npz"):
         print(f, os.path.getsize(os.path.join(HERE, f)), "bytes")
 
 
@@ -561,6 +592,10 @@ if __name__ == "__main__":
         pyoracle.build()
         np.savez_compressed(os.path.join(HERE, "contractions_wide.npz"), **wide_contraction_fixtures(pyoracle.reference()))
         print("contractions_wide.npz", os.path.getsize(os.path.join(HERE, "contractions_wide.npz")), "bytes")
+    elif len(sys.argv) > 1 and sys.argv[1] == "checks":   # only the outputs behind the oracle-versus-reference checks
+        pyoracle.build()
+        np.savez_compressed(os.path.join(HERE, "reference_checks.npz"), **reference_check_fixtures(pyoracle.reference()))
+        print("reference_checks.npz", os.path.getsize(os.path.join(HERE, "reference_checks.npz")), "bytes")
     elif len(sys.argv) > 1 and sys.argv[1] == "headline":   # only the (slow) headline fixture
         pyoracle.build()
         headline_fixture()

@@ -410,7 +410,7 @@ def test_bench_entry_point_with_two_ranks_on_one_gpu(gf, scaling):
     env = dict(os.environ, GF_BENCH_ONE_GPU="1", GF_RCCL_LIBRARY=MOCK_RCCL, GF_DIST_TIMEOUT_S="120", MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--repeats", "2", "--batch",
-                        "96" if scaling == "weak" else "192", "--scaling", scaling, "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
+                        "96" if scaling == "weak" else "192", "--scaling", scaling, "--no-cpu-baseline", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -11,7 +11,7 @@ for arm in sys.argv[1:] or [""]:
     for kv in arm.split():
         k, v = kv.split("=", 1)
         env[k] = v
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-extra"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-extra"],
                          capture_output=True, text=True, env=env)
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     if not line:

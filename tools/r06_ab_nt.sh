@@ -4,7 +4,7 @@ cd $R
 for i in 1 2; do
 for lib in "" nt0 nt1 nt2 nt3 nt4 nt8 nt16 nt24 nt32 nt64; do
   p=""; [ -n "$lib" ] && p=$R/graphflow_amd/csrc/libgf_hip_$lib.so
-  GF_HIP_LIBRARY=$p python bench.py --steps 30 --warmup 5 --repeats 3 --no-cpu-baseline --no-extra 2>/dev/null | python -c "
+  GF_HIP_LIBRARY=$p python bench.py --steps 30 --warmup 5 --repeats 3 --full --no-cpu-baseline --no-extra 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 k=d['roofline']['kernel_ms_per_step']
