@@ -535,9 +535,8 @@ __global__ __launch_bounds__(MAXT) void r10_bwd_graph(const float *__restrict__ 
 // the per-graph kernels serve: C % 4 == 0 with C / 4 a power of two <= 32, N <= 32 with at most four position slots per lane, aligned
 // buffers, a workgroup's LDS within the CU's, and batches that give most CUs a graph (GF_FAM10_GRAPH=0: the table kernels)
 static bool r10_graph_ok(int N, int C, int batch, const void *p0, const void *p1, const void *p2) {
-    const char *e = std::getenv("GF_FAM10_GRAPH");   // 0: the table kernels; 2: any batch size (tests)
-    if (e && e[0] == '0') return false;
-    if (C % 4 != 0 || C < 4 || N < 1 || N > 32 || (batch < 96 && !(e && e[0] == '2'))) return false;
+    if (env_is("GF_FAM10_GRAPH", '0')) return false;   // 0: the table kernels; 2: any batch size (tests)
+    if (C % 4 != 0 || C < 4 || N < 1 || N > 32 || (batch < 96 && !env_is("GF_FAM10_GRAPH", '2'))) return false;
     const int lpc = C / 4;
     if (lpc > 32 || (lpc & (lpc - 1)) != 0) return false;
     const int ppw = 64 / lpc, slots = (N + ppw - 1) / ppw, nw = (N + 1) / 2;
@@ -1557,9 +1556,8 @@ gf_status fam_forward_launch(gf_ctx *ctx, const float *P, const float *A, float 
     if constexpr (K == 50) {
         // all fifty slices of a row from one wave, the adjacency products on the matrix pipe (GF_FAM_FWD_MFMA=0: the table kernels below,
         // which serve every other shape and _10 -- the parity tests hold the two against each other)
-        const char *e = std::getenv("GF_FAM_FWD_MFMA");
         mfma_out = vec && C % 32 == 0 && N <= 32 && (size_t)batch * N * (C / 32) < 0x7fffffffu && (size_t)N * N * N * C < (1u << 29) &&
-                   !(e && e[0] == '0');   // (buffer descriptors of a graph's P and tables stay under 2 GB)
+                   !env_is("GF_FAM_FWD_MFMA", '0');   // (buffer descriptors of a graph's P and tables stay under 2 GB)
     }
     if (mfma_out) {
         if constexpr (K == 50) {
@@ -1628,9 +1626,8 @@ gf_status fam_backward_launch(gf_ctx *ctx, const float *G, const float *A, float
     if constexpr (K == 50) {
         // matrix-pipe tables (every G row read once, no LDS): C in whole 32-channel windows, N <= 32.  GF_FAM_BWD_MFMA=0: the
         // thread-per-(i, columns, f) kernel below (every other shape, _10; the parity tests hold the two against each other)
-        const char *e = std::getenv("GF_FAM_BWD_MFMA");
         mfma_tables = C % 32 == 0 && N <= 32 && (size_t)batch * N * (C / 32) < 0x7fffffffu && (size_t)N * N * K * C < (1u << 28) &&
-                      !(e && e[0] == '0');
+                      !env_is("GF_FAM_BWD_MFMA", '0');
     }
     if constexpr (K == 50) {
         if (mfma_tables) {

@@ -41,10 +41,7 @@ static const char *error_snapshot(gf_ctx *ctx) {
 // filled with 0xff bytes (NaN as floats, -1 as indices) first, so a kernel that reads what nobody wrote shows up in the parity
 // tests instead of depending on what the allocation happened to hold.  Debug aid; off by default.
 bool poison_buffers() {
-    static const bool on = [] {
-        const char *e = std::getenv("GF_POISON");
-        return e && e[0] == '1';
-    }();
+    static const bool on = env_is("GF_POISON", '1');
     return on;
 }
 

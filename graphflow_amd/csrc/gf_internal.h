@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
+#include <cstdlib>
 #include <unordered_map>
 #include <vector>
 
@@ -50,6 +51,11 @@ struct gf_ctx {
 namespace gf {
 
 gf_status fail(gf_ctx *ctx, gf_status st, const char *fmt, ...);
+// environment switch `name` set to a value starting with `v` (read at every call: callers decide when to read)
+inline bool env_is(const char *name, char v) {
+    const char *e = std::getenv(name);
+    return e && e[0] == v;
+}
 bool poison_buffers();  // GF_POISON=1 (gf_capi.hip)
 gf_status ensure_ws(gf_ctx *ctx, size_t bytes);
 gf_status ensure_stage(gf_ctx *ctx, size_t bytes);

@@ -1026,13 +1026,13 @@ void gf::smp_derive_plan(gf_smp *s, bool allow_embed) {
     s->dup_channels = 0;
     s->n_extra = 0;
     {
-        const char *e = std::getenv("GF_SMP_PAD_CHANNELS");
+        const bool no_pad = gf::env_is("GF_SMP_PAD_CHANNELS", '0');
         const int C = s->cfg.nChanels;
         int Cc = C;
-        if ((pad_channels || (e && e[0] == '2')) && !(e && e[0] == '0') && s->cfg.nContractions == 18 && s->cfg.nLevels < gf::kPadMaxLevels) {   // (2: tests)
+        if ((pad_channels || gf::env_is("GF_SMP_PAD_CHANNELS", '2')) && !no_pad && s->cfg.nContractions == 18 && s->cfg.nLevels < gf::kPadMaxLevels) {   // (2: tests)
             // (round 5: a 16-channel build of the row-panel family -- the reference's own models have nChanels = 10; min_pad = 32 keeps a
             //  tower that will run under slice dropout on the 32-channel kernels, the only ones with per-product row factors)
-            if (C <= 16 && min_pad <= 16 && !(e && e[0] == '3')) Cc = 16;   // GF_SMP_PAD_CHANNELS=3: pad to 32 as rounds 1-4 did (tests)
+            if (C <= 16 && min_pad <= 16) Cc = 16;
             else if (C <= 32) Cc = 32;
             else if (C <= 64) Cc = 64;
             else Cc = (C + 3) & ~3;
@@ -1043,13 +1043,11 @@ void gf::smp_derive_plan(gf_smp *s, bool allow_embed) {
         // SMP_2D_ver6 (RisiContraction_10) embedded in the 18-slice fused level (see gf_smp::dup_channels): 2 C channels padded to 16 / 32 / 64.
         // GF_SMP_VER6_FUSED=0: the `_10` contraction op by op.  gf_smp_prepare switches to that plan by itself for a batch with an asymmetric adjacency.
         // (only where every field fits the fused level -- max_receptive_field <= 64 (32 until round 6): on an op-by-op level the 18-slice model at 2 C padded
-        //  channels moves more than the `_10` / `_50` contraction at C; GF_SMP_VER6_FUSED=2 / GF_SMP_VER7_FUSED=2 embed at any cap)
-        auto embed = [&](const char *name) {
-            const char *v = std::getenv(name);
-            if (!allow_embed || (v && v[0] == '0')) return false;
-            return s->cfg.max_receptive_field <= gf::kFusedMaxField || (v && v[0] == '2');   // (64 since round 6: fields of 33 .. 64 positions stay fused)
+        //  channels moves more than the `_10` / `_50` contraction at C)
+        auto embed = [&](const char *name) {   // (kFusedMaxField: 64 since round 6, fields of 33 .. 64 positions stay fused)
+            return allow_embed && !gf::env_is(name, '0') && s->cfg.max_receptive_field <= gf::kFusedMaxField;
         };
-        if (pad_channels && !(e && e[0] == '0') && s->cfg.nContractions == 10 && 2 * C <= 64 && s->cfg.nLevels < gf::kPadMaxLevels && !s->cfg.physics &&
+        if (pad_channels && !no_pad && s->cfg.nContractions == 10 && 2 * C <= 64 && s->cfg.nLevels < gf::kPadMaxLevels && !s->cfg.physics &&
             embed("GF_SMP_VER6_FUSED")) {
             s->dup_channels = C;
             s->cfg.nContractions = 18;
@@ -1057,7 +1055,7 @@ void gf::smp_derive_plan(gf_smp *s, bool allow_embed) {
             Cc = 2 * C <= 16 ? 16 : 2 * C <= 32 ? 32 : 64;
         }
         // SMP_2D_ver7 (RisiContraction_50) the same way, with three extra products per level (gf_smp::n_extra).  GF_SMP_VER7_FUSED=0: op by op.
-        if (pad_channels && !(e && e[0] == '0') && s->cfg.nContractions == 50 && 2 * C <= 64 && s->cfg.nLevels < gf::kPadMaxLevels && !s->cfg.physics &&
+        if (pad_channels && !no_pad && s->cfg.nContractions == 50 && 2 * C <= 64 && s->cfg.nLevels < gf::kPadMaxLevels && !s->cfg.physics &&
             embed("GF_SMP_VER7_FUSED")) {
             s->dup_channels = C;
             s->n_extra = 3;
@@ -1067,11 +1065,8 @@ void gf::smp_derive_plan(gf_smp *s, bool allow_embed) {
         }
         // the `_10` / `_50` wirings (SMP_2D_ver6 / ver7: op-by-op levels): a channel count that is not a multiple of 4 runs the contraction
         // kernels at one channel per lane; padded to the next multiple (10 -> 12) they take the float4 / one-stream-per-graph kernels
-        if (pad_channels && !(e && e[0] == '0') && s->cfg.nContractions != 18 && !s->dup_channels && s->cfg.nLevels < gf::kPadMaxLevels && !s->cfg.physics) {
-            const char *m = std::getenv("GF_SMP_PAD_FAMILY");   // experiment: 0 = off, 4 / 8 / 16 = pad to that multiple
-            const int mult = m ? std::atoi(m) : 4;
-            if (mult > 0) Cc = (C + mult - 1) / mult * mult;
-        }
+        if (pad_channels && !no_pad && s->cfg.nContractions != 18 && !s->dup_channels && s->cfg.nLevels < gf::kPadMaxLevels && !s->cfg.physics)
+            Cc = (C + 3) & ~3;
         s->cfg.nChanels = Cc;
     }
 }
@@ -1109,10 +1104,7 @@ gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channel
         delete s;
         return fail(ctx, GF_ERR_INVALID, "gf_smp_create: nContractions = %d (expected 10, 18 or 50)", bad);
     }
-    {
-        const char *e = std::getenv("GF_SMP_BWD_GATHER");  // 0: keep the two-kernel tables-backward + consumer gather
-        s->bwd_gather = (e && e[0] == '0') ? 0 : 1;
-    }
+    s->bwd_gather = gf::env_is("GF_SMP_BWD_GATHER", '0') ? 0 : 1;   // 0: keep the two-kernel tables-backward + consumer gather
     *out = s;
     return GF_OK;
 }
@@ -1405,10 +1397,9 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
     const auto tp0 = std::chrono::steady_clock::now();
     if (!s->upload) {
         // the batch's uploads and table-building kernels run at the LOWEST stream priority: in the loop with a new batch every step they
-        // share the device with the running step of another handle, which is what the loop waits for (GF_PREP_PRIORITY=0: default priority)
+        // share the device with the running step of another handle, which is what the loop waits for
         int least = 0, greatest = 0;
-        const char *pe = std::getenv("GF_PREP_PRIORITY");
-        if (!(pe && pe[0] == '0') && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
+        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
             if (hipStreamCreateWithPriority(&s->upload, hipStreamNonBlocking, least) != hipSuccess) s->upload = nullptr;
         } else if (hipStreamCreateWithFlags(&s->upload, hipStreamNonBlocking) != hipSuccess) {
             s->upload = nullptr;
@@ -1424,8 +1415,7 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
     // rows-sized level tables on the device (GF_PREP_DEVICE_TABLES=0: on the host, as rounds 1-2 built them; the parity tests hold
     // the two against each other bit for bit)
     {
-        const char *e = std::getenv("GF_PREP_DEVICE_TABLES");
-        s->lay.device_tables = !(e && e[0] == '0');
+        s->lay.device_tables = !gf::env_is("GF_PREP_DEVICE_TABLES", '0');
         // build_level_rows keeps three ints per field position and four shorts per vertex of its molecule in LDS: beyond the
         // default 32 KiB window (a molecule of ~4,000 vertices) the tables are built on the host, as rounds 1-2 built all of them
         // (decided BEFORE build_batch lays the batch out for one builder or the other; round-3 advice)
@@ -1700,7 +1690,7 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
         st = gf::upload(s, &s->wbound, nullptr, gf::smp_wgrad_bound_words() * (size_t)(L + 1));
         if (st != GF_OK) return st;
     } else if (s->cfg.square() && (C == 32 || C == 16)) {   // scratch words of the C = 32 / 16 weight-gradient kernel's column bounds
-        st = gf::upload(s, &s->wbound, nullptr, gf::smp_wgrad_direct_words_c32() * (size_t)(L + 1));
+        st = gf::upload(s, &s->wbound, nullptr, gf::smp_wgrad_all_words() * (size_t)(L + 1));
         if (st != GF_OK) return st;
     }
     st = gf::upload(s, &s->sh, nullptr, (size_t)top.nNodes * C);

@@ -28,11 +28,6 @@ using namespace gf::dev;
 namespace gf {
 namespace {
 
-bool env_is(const char *name, char v) {
-    const char *e = std::getenv(name);
-    return e && e[0] == v;
-}
-
 // Totals of two tables over the four c-groups (16-lane rows) of a wave in ONE butterfly: v_permlane16_swap of (u, v) leaves
 // {u.r0, v.r0, u.r2, v.r2} and {u.r1, v.r1, u.r3, v.r3}, whose sum pairs rows 0+1 and 2+3 of u in the even rows and of v in
 // the odd rows; the xor-32 step finishes both.  Even c-groups end up with the total of u, odd ones with the total of v:
@@ -639,7 +634,7 @@ __global__ __launch_bounds__(256) void tables_zero_fill(float *__restrict__ T, c
 // ---- slice dropout on the fused level (round 5; RisiContraction_18_dropout, GraphFlow/RisiContraction_18_dropout.h:106-132, 465-471) ----
 // The reference zeroes (train) or scales by nKept / 18 (test) single slices k of a node's contraction output.  The factorised level never
 // forms a slice, but every slice is one block product K^(k) applied to one table, so a node's slice factor m_k is a per-node factor on that
-// product: the eight row products take it through an eight-column row-factor table (smp_rowpanel_split / smp_wgrad_direct, NF = 8), the
+// product: the eight row products take it through an eight-column row-factor table (smp_rowpanel_split / smp_wgrad_all, NF = 8), the
 // vector / scalar products through their operands (Vt, St and their gradients are scaled block by block), the two compact diagonal
 // products where the consumer gathers them (combine-forward, diag_gather_bwd).
 //   nodefac[n][k] = bit k of keep[n] ? scale : 0        rowfac8[row] = (tot m0, tot m2, tr m6, m5, m9, m8, m12, m11) of the row's node
@@ -1172,9 +1167,9 @@ static bool smp_half_window(int C) { return C % 32 == 0 && C % 64 != 0; }
 // ... and whole 16-channel windows only (C = 16, 48, ...): four lanes per position in tables-forward (round 5: the 16-channel kernel family)
 static bool smp_quarter_window(int C) { return C == 16; }
 
-// tables-forward keeps smp_vectors' sums itself (C % 64 == 0; GF_SMP_TF_VEC=0: the separate pass)
+// tables-forward keeps smp_vectors' sums itself (C % 64 == 0, and the 32- / 16-channel windows; other channel counts: the separate pass)
 static bool smp_tables_fold_vectors(const gf_smp *s) {
-    return ((s->cfg.nChanels & 63) == 0 || smp_half_window(s->cfg.nChanels) || smp_quarter_window(s->cfg.nChanels)) && !env_is("GF_SMP_TF_VEC", '0');
+    return (s->cfg.nChanels & 63) == 0 || smp_half_window(s->cfg.nChanels) || smp_quarter_window(s->cfg.nChanels);
 }
 
 // the eight-lanes-per-position classes (C % 32 == 0, C % 64 != 0): a wave load covers eight positions, NI = 1, 2, 4 for s <= 8, 16, 32
@@ -1227,11 +1222,7 @@ gf_status launch_tables_fwd_w(gf_smp *s, int l, const SizeClass &c) {
         GF_LAUNCH(ctx, tables_fwd_name<NI>(), (smp_tables_fwd_w<NI, true, true>), dim3((unsigned)((n_hi - n_lo) * nwin)), dim3((NI >= GF_TF_WIDE ? 2 : 1) * kThreads), lds_v,
                   s->lv[l - 1].f, d.rsum, d.Q, d.Vt, d.scal, d.pair_src_row, d.pair_src_s, d.pi, d.tf_recs + 2 * (size_t)n_lo, C, nwin,
                   flags, flags ? d.rowflag : (const unsigned char *)nullptr, d.St);
-    } else if ((C & 63) == 0)
-        GF_LAUNCH(ctx, tables_fwd_name<NI>(), (smp_tables_fwd_w<NI, true>), dim3((unsigned)((n_hi - n_lo) * nwin)), dim3((NI >= GF_TF_WIDE ? 2 : 1) * kThreads), lds,
-                  s->lv[l - 1].f, d.rsum, d.Q, d.Vt, d.scal, d.pair_src_row, d.pair_src_s, d.pi, d.tf_recs + 2 * (size_t)n_lo, C, nwin,
-                  flags, flags ? d.rowflag : (const unsigned char *)nullptr, (float *)nullptr);
-    else
+    } else
         GF_LAUNCH(ctx, tables_fwd_name<NI>(), (smp_tables_fwd_w<NI, false>), dim3((unsigned)((n_hi - n_lo) * nwin)), dim3((NI >= GF_TF_WIDE ? 2 : 1) * kThreads), lds,
                   s->lv[l - 1].f, d.rsum, d.Q, d.Vt, d.scal, d.pair_src_row, d.pair_src_s, d.pi, d.tf_recs + 2 * (size_t)n_lo, C, nwin,
                   flags, (const unsigned char *)nullptr, (float *)nullptr);
@@ -1514,7 +1505,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // the dedicated C = 64 kernels of the block products (weights resident in LDS, rows in registers; output-stationary weight gradients).
 // GF_SMP_ROWPANEL=0 (read per call: the parity tests switch it) selects the grouped tiled GEMM launches every other channel count uses.
 // Round 4: the split-operand row-panel products also run at C = 32 (32 x 32 blocks: one column half, two k-chunks per lane; weight
-// gradients on smp_wgrad_direct<32>); the fp32-pipe variants, the panel combine and the small-product kernels stay C = 64 only.
+// gradients on smp_wgrad_all<32>); the fp32-pipe variants, the panel combine and the small-product kernels stay C = 64 only.
 static bool smp_c64_kernels(const gf_smp *s) {
     if (env_is("GF_SMP_ROWPANEL", '0')) return false;
     return s->cfg.nChanels == 64 || ((s->cfg.nChanels == 32 || s->cfg.nChanels == 16) && smp_split_products(s->ctx) && s->wbound != nullptr);
@@ -1526,7 +1517,7 @@ bool smp_compact_o(const gf_smp *s) { return smp_c64_kernels(s); }
 static bool smp_extras_in_kernel(const gf_smp *s, int l) {
     const int C = s->cfg.nChanels;
     return s->n_extra && (C == 32 || C == 16) && smp_c64_kernels(s) && s->lv[l].wimg_ready && s->lv[l].wimg && !s->drop_on && smp_split_products(s->ctx) &&
-           s->lv[l].trow && !env_is("GF_SMP_EXTRAS_IN_KERNEL", '0');
+           s->lv[l].trow;
 }
 gf_status smp_fused_backward_level_grouped(gf_smp *s, int l, float *dKl, float *dbl);
 
@@ -1870,16 +1861,17 @@ gf_status smp_fused_backward_level_grouped(gf_smp *s, int l, float *dKl, float *
     size_t ws_floats = ctx->ws_bytes / sizeof(float), used = 0;
     FoldGroup rowg;
     const bool stationary = d.fwd_c64;
-    if (stationary && (C == 32 || C == 16)) {   // smp_wgrad_direct<32 | 16>: one partial image of the eight products per workgroup
-        const int splits = smp_wgrad_direct_splits(ctx, rows);
+    if (stationary && (C == 32 || C == 16)) {   // smp_wgrad_all<32 | 16>: one partial image of the eight products per workgroup
+        const int splits = smp_wgrad_all_splits(ctx, rows);
         if ((size_t)splits * 8 * CC > ws_floats) return fail(ctx, GF_ERR_NOMEM, "fused level: workspace too small for %d weight-gradient images", splits);
         // SMP_2D_ver7 on the 18-slice level: its three extra products ride in the same kernel (their operands are fragments it already
-        // holds); three more images per workgroup behind the eight, folded straight into dX below
+        // holds); three more images per workgroup behind the eight, folded straight into dX below (not under slice dropout: the extra
+        // products take the plain (tot, tr) row factors)
         float *xpart = nullptr;
-        if (s->n_extra && s->extra_g && !drop && smp_wgrad_extra_supported(2) &&
+        if (s->n_extra && s->extra_g && !drop &&
             (size_t)splits * 8 * CC + ((size_t)splits + (splits + 31) / 32) * 3 * CC <= ws_floats)
             xpart = ws + (size_t)splits * 8 * CC;
-        unsigned *words = s->wbound + (size_t)l * smp_wgrad_direct_words_c32();   // (the same scratch layout at 16 channels)
+        unsigned *words = s->wbound + (size_t)l * smp_wgrad_all_words();   // (the same scratch layout at 16 channels)
         const unsigned *chan = nullptr;
         if (d.dzmax && d.row_max) {   // per-channel maxima of f_{l-1} and of this level's dz (combine-backward's per-workgroup maxima)
             GF_HIP_TRY(ctx, hipMemsetAsync(words, 0, sizeof(unsigned) * 64, ctx->stream));
@@ -1900,8 +1892,8 @@ gf_status smp_fused_backward_level_grouped(gf_smp *s, int l, float *dKl, float *
             st = smp_fused_ensure_zero_fill(s, l);
             if (st != GF_OK) return st;
         }
-        st = smp_wgrad_partials_direct_c32(ctx, T, dO, drop ? d.rowfac8 : d.rowscale, rows, splits, ws, d.trow, d.trowf, words, chan,
-                                           (float)h.buckets.back().s, d.row_max, drop ? 8 : 2, C, xpart);
+        st = smp_wgrad_partials_all(ctx, T, dO, drop ? d.rowfac8 : d.rowscale, rows, splits, ws, d.trow, d.trowf, words, chan,
+                                    (float)h.buckets.back().s, d.row_max, drop ? 8 : 2, C, xpart);
         if (st != GF_OK) return st;
         if (xpart) {
             st = splitk_fold(ctx, xpart, s->extra_g + (size_t)(l - 1) * 3 * CC, 3 * CC, splits, 0);
@@ -2097,9 +2089,9 @@ gf_status smp_fused_backward_level(gf_smp *s, int l, const float *Kl, float *dKl
         return fail(ctx, GF_ERR_INVALID, "gf_smp_backward: the product kernels' option (GF_OPT_SMP_FP32_PRODUCTS / GF_SMP_SPLIT / GF_SMP_ROWPANEL) "
                                          "changed since the forward pass of level %d", l);
     float *dzmax = (s->wbound && d.dzmax && d.fwd_c64) ? d.dzmax : (float *)nullptr;
-    // round 5: on the forward's row panels where they exist (one wave per panel, every request up front; GF_SMP_COMBINE_BWD_PANELS=0: the
-    // workgroup-per-(node, four x) kernel below, which also serves every other channel count)
-    if (d.fwd_c64 && d.fwd_pan && smp_panel_channels(C) && (long long)h.rows * 512 < 0x3fffffffll && !env_is("GF_SMP_COMBINE_BWD_PANELS", '0')) {
+    // round 5: on the forward's row panels where they exist (one wave per panel, every request up front; else the workgroup-per-(node,
+    // four x) kernel below, which serves the big nodes and every other channel count)
+    if (d.fwd_c64 && d.fwd_pan && smp_panel_channels(C) && (long long)h.rows * 512 < 0x3fffffffll) {
         st = smp_combine_bwd_panels_c64(s, l, dfrows, node_df, dO, dzmax);
         if (st != GF_OK) return st;
         s->lv[l].dz_rows = d.fwd_npanels;

@@ -51,16 +51,14 @@ gf_status smp_rowpanel_split_c64(gf_ctx *ctx, bool forward, const float *A, cons
 // the split kernels' weight images of a level (both directions), built once per forward pass (smp_level_c64_split.hip)
 size_t smp_split_image_bytes();
 gf_status smp_split_build_images(gf_ctx *ctx, const float *const *Wst, void *const *img, int n, int C = 64, const float *const *X = nullptr);
-// weight gradients of a fused level at C = 32 (smp_wgrad_direct<32>): partial images of 8 x 32 x 32 floats per workgroup
-gf_status smp_wgrad_partials_direct_c32(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int splits, float *part,
-                                        const int *trow, const int *trowf, unsigned *words, const unsigned *chan = nullptr, float smax = 0.f,
-                                        const unsigned *row_max = nullptr, int nf = 2, int C = 32, float *xpart = nullptr);
-// C = 32 or (round 5) 16
-bool smp_wgrad_extra_supported(int nf);
+// weight gradients of a fused level at C = 32 or (round 5) 16 (smp_wgrad_all<C>): partial images of 8 x C x C floats per workgroup
+gf_status smp_wgrad_partials_all(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int splits, float *part,
+                                 const int *trow, const int *trowf, unsigned *words, const unsigned *chan = nullptr, float smax = 0.f,
+                                 const unsigned *row_max = nullptr, int nf = 2, int C = 32, float *xpart = nullptr);
 gf_status smp_wgrad_channel_maxima_ld(gf_ctx *ctx, const float *fprev, long long prev_rows, int ld0, const float *dsrc, long long drows, int ld1, int C,
                                       unsigned *words);
-size_t smp_wgrad_direct_words_c32();
-int smp_wgrad_direct_splits(gf_ctx *ctx, long long rows);
+size_t smp_wgrad_all_words();
+int smp_wgrad_all_splits(gf_ctx *ctx, long long rows);
 gf_status smp_small_split_c64(gf_ctx *ctx, bool transposed, int n, const int *prog, const float *const *In, float *const *Out, const int *rows,
                               const int *pos0, const void *wimg, const char *name, int C = 64);
 // where the split-operand weight gradients take their per-column exponents from (smp_level_c64_split.hip: smp_wgrad_split): either

@@ -216,7 +216,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
 //               one more MFMA chain: output row (type t, group g) of a 32 x 32 tile takes weight  [row e in group g] * {r[y_e], A+[x_g, y_e], 1};
 //               the three weights of an input row are what ITS lane holds for the forward pass (r[y], A+[x, y]), read with v_readlane
 // and the per-column maxima of |dz| over the panel (the weight gradients' column exponents).  Same sums per output element as
-// smp_combine_bwd (fixed order: the MFMA's k order), held to it by the parity tests (GF_SMP_COMBINE_BWD_PANELS=0 selects it).
+// smp_combine_bwd (fixed order: the MFMA's k order), held to it by the parity tests (GF_SMP_ROWPANEL=0 runs smp_combine_bwd).
 // ---------------------------------------------------------------------------------------------------------------
 template <int CB>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) void smp_combine_bwd_panels(

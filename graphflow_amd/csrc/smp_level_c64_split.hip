@@ -993,250 +993,26 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
 
 
 // ---------------------------------------------------------------------------------------------------------------
-// The same eight products with the operands loaded STRAIGHT into MFMA layout (round 4): the weight gradients of the OTHER channel
-// count the row-panel kernels serve (CB = 32; at CB = 64 the staged kernel above is faster: 0.92 against 1.13 ms per cfg3 step --
-// every wave re-reads and re-splits the operands it shares with other products, 2.5 x the staged kernel's L1 / L2 traffic).
-// Both operands of  dW = A^T B  reduce over the ROWS, and v_mfma_f32_32x32x16_f16 wants from lane (c = lane & 31, g = lane >> 5)
-// the eight reduction indices k = 8 g .. 8 g + 7 of column c -- eight ROWS of one column.  One dword load per row hands the wave two
-// fully used 128-byte row segments, the lane splits its eight values in registers (a column's power-of-two scale is one register per
-// lane and tile), and the fragments go to the pipe: no transposed LDS image, no barrier per 16-row slice.  Wave w keeps product w.
+// The same eight products at the other channel counts the row-panel kernels serve (CB = 32 / 16; round 5), with ONE wave doing all
+// eight for its slices and the operands loaded STRAIGHT into MFMA layout.  Both operands of  dW = A^T B  reduce over the ROWS, and
+// v_mfma_f32_32x32x16_f16 wants from lane (c = lane & 31, g = lane >> 5) the eight reduction indices k = 8 g .. 8 g + 7 of column c --
+// eight ROWS of one column: one dword load per row hands the wave fully used row segments, the lane splits its eight values in
+// registers, and the fragments go to the pipe (no transposed LDS image, no barrier per slice).  A wave keeps the eight accumulators
+// (128 registers; one wave per SIMD, four per workgroup), requests the seven blocks of its slice once, splits nine operands (four of
+// T; L, tot L, tr L, dU, dU[trow] -- or eight factor-scaled ones under slice dropout, NF = 8) and runs the 24 MFMAs.  (A wave per
+// product, round 4, requested and split every shared block up to five times and was VALU-bound: NOTES.md.)
 //   * Buffer addressing with the descriptor REBASED per slice (wave-uniform scalar arithmetic): lane offsets are constants, the row
 //     of a request rides in its scalar offset, rows past the end of the level are out of range (they load zeros), and a row whose
 //     block is structurally zero (packed table, see smp_rowpanel_split) gets an out-of-range offset.  The gathered rows dU[trow] lie
 //     inside the row's own node (< s^2 <= 4096 rows away, kTrowWindow: 1024 until round 6, when nodes of up to 64 positions joined the
-//     fused level -- the gradient of K11 lost their far rows): their descriptor starts that many rows below the slice.  Any level size.
-//   * Two slices in flight per wave behind the one being multiplied; the slice's packed table entries and row factors are
-//     requested a slice earlier than its operands, BEFORE the previous slice's operand requests, so that waiting for them does not
-//     wait for those (loads return in order).  The fragments are pinned (an empty asm) ahead of the requests: left alone the split
-//     drifts below them, the raw registers are still live when the next requests want them, and every value loaded in the loop is
-//     copied into place behind a drained queue at the loop's end.
-//   * Same partial images (8 x CB x CB floats per workgroup), same fold as the staged kernel.
+//     fused level): their descriptor starts that many rows below the slice.  Any level size.
+//   * CB = 16: a 32 x 32 tile has room for TWO 16-column operands, so a slice is 32 rows there and the lanes of columns 16..31 carry
+//     the operands of its second sixteen rows: the tile's diagonal quadrants are the two half-slices' products (the off-diagonal ones
+//     mix the halves and are ignored) and are added at the end -- half the instructions per row of a half-empty tile.
+//   * The four waves of a workgroup take its slices in turn; their images are added in wave order through LDS: the same partial
+//     images (8 x CB x CB floats per workgroup), same fold as the staged kernel, and the result does not depend on timing.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr long long kTrowWindow = (long long)kFusedMaxField * kFusedMaxField;   // rows a transposed row (e, x) lies from its row (x, e) at most
-constexpr int kWdThreads = 512;
-template <int CB>
-__global__ __launch_bounds__(kWdThreads, 1) void smp_wgrad_direct(const float *__restrict__ T, const float *__restrict__ dO,
-                                                                   const float *__restrict__ rs, int rows, float *__restrict__ part,
-                                                                   const int *__restrict__ trow, const unsigned *__restrict__ cmax,   // [9 CB] column bounds, or null:
-                                                                   const unsigned *__restrict__ chan,   // [2 CB] max |f_{l-1}| | max |dz_l| per channel (see smp_wgrad_split)
-                                                                   float smax, const unsigned *__restrict__ row_max,   // {max |tot|, max |tr|} (float bits)
-                                                                   int packed,
-                                                                   int nf) {  // 2: rs = [rows][2] (tot, tr); 8: rs = [rows][8], product w's own factor
-                                                                   // per row (slice dropout: see smp_rowpanel_split) -- every wave scales its B operand
-    // CB = 16 (round 5): a 32 x 32 tile has room for TWO 16-column operands, so a slice is 32 rows there and the lanes of columns 16..31 carry
-    // the operands of its second sixteen rows: the tile's diagonal quadrants are the two half-slices' products (the off-diagonal ones mix
-    // the halves and are ignored) and are added at the end -- half the instructions per row of a half-empty tile.
-    constexpr int NT = CB >= 32 ? CB / 32 : 1, ACOLS = 4 * CB, BCOLS = 5 * CB;
-    constexpr int SL = CB == 16 ? 2 * kWsSlice : kWsSlice;   // rows of a slice
-    constexpr int TROW = 16 * CB, DROW = 8 * CB;   // bytes of a row of T, of dO
-    __shared__ float sScale[ACOLS + BCOLS], sInv[ACOLS + BCOLS];
-    const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lg = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int hi = (CB == 16 && li >= 16) ? 1 : 0;   // the lane works on the slice's second sixteen rows
-    const int lc = CB == 16 ? (li & 15) : li;         // ... on operand column lc
-    const int rb = 8 * lg + 16 * hi;                  // first of the lane's eight rows inside the slice
-    if (cmax) {
-        for (int c = tid; c < ACOLS + BCOLS; c += kWdThreads) pow2_scale_col(cmax[c], &sScale[c], &sInv[c]);
-    } else {   // (the bounds of smp_wgrad_split, from the level's per-channel maxima)
-        const float max_tot = __uint_as_float(row_max[0]), max_tr = __uint_as_float(row_max[1]);
-        for (int c = tid; c < ACOLS + BCOLS; c += kWdThreads) {
-            const bool isa = c < ACOLS;
-            const int blk = (isa ? c : c - ACOLS) / CB, ch = c % CB;
-            const float m = __uint_as_float(chan[(isa ? 0 : CB) + ch]);
-            const float fa = blk < 2 ? smax : max_tot;
-            const float fb = blk == 0 ? 1.f : blk == 2 ? max_tr : max_tot;
-            pow2_scale_col(__float_as_uint(m * (isa ? fa : fb)), &sScale[c], &sInv[c]);
-        }
-    }
-    __syncthreads();
-
-    const int ablk = c_ws_ablk[wave], bblk = c_ws_bblk[wave];   // (uniform)
-    const bool gathered = bblk == 4;
-    const int fsel = nf == 8 ? wave : bblk == 2 ? 1 : 0;        // the row factor a scaled copy of L takes: tot | tr  (nf == 8: the product's own)
-    const bool scaled = nf == 8 || bblk == 1 || bblk == 2;
-    const int abit = (ablk == 0 || ablk == 2) ? 31 : 29;        // presence bit of the wave's T block: S_ab / T6 | S_bc / T10
-    float sa[NT], sb[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        sa[t] = sScale[CB * ablk + 32 * t + lc];
-        sb[t] = sScale[ACOLS + CB * bblk + 32 * t + lc];
-    }
-    constexpr int kOut = 0x40000000;   // an offset no descriptor of this kernel reaches
-    const int offA = rb * TROW + (CB * ablk + lc) * 4;
-    const int offB = rb * DROW + ((bblk >= 3 ? CB : 0) + lc) * 4;
-    const int offG = (CB + lc) * 4;   // (gathered: the row comes from the table)
-    const long long nsl = ((long long)rows + SL - 1) / SL;
-    auto slice_of = [&](int n) { return (long long)blockIdx.x + (long long)n * gridDim.x; };
-
-    struct Idx {      // a slice's table entries for the lane's eight rows
-        int t[8];
-    };
-    struct Fac {      // ... and its row factors
-        float f[8];
-    };
-    struct Raw {
-        float a[NT][8], b[NT][8];
-    };
-    // (entries of rows past the end of the level read as 0 through the descriptors: no flag, factor 0 -- their operand rows are
-    //  out of range anyway)
-    const __amdgpu_buffer_rsrc_t rTr = __builtin_amdgcn_make_buffer_rsrc(const_cast<int *>(trow), 0, (unsigned)rows * 4u, 0x00020000);
-    const int rsb = 4 * nf;   // bytes of a row of rs
-    const __amdgpu_buffer_rsrc_t rRs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(rs), 0, (unsigned)rows * (unsigned)rsb, 0x00020000);
-    const int offF = scaled ? rsb * rb + 4 * fsel : kOut;   // (the other waves' requests return at once)
-    auto ld1 = [](__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-    };
-    auto load_idx = [&](Idx &I, int n) {
-        const long long k0 = slice_of(n) * SL;
-        const int ks = k0 < rows ? (int)k0 : rows;   // (past the end: every entry out of range)
-        typedef int i4v __attribute__((ext_vector_type(4)));
-        const i4v t0 = __builtin_bit_cast(i4v, __builtin_amdgcn_raw_buffer_load_b128(rTr, 4 * rb, ks * 4, 0));
-        const i4v t1 = __builtin_bit_cast(i4v, __builtin_amdgcn_raw_buffer_load_b128(rTr, 4 * rb + 16, ks * 4, 0));
-        I.t[0] = t0[0], I.t[1] = t0[1], I.t[2] = t0[2], I.t[3] = t0[3], I.t[4] = t1[0], I.t[5] = t1[1], I.t[6] = t1[2], I.t[7] = t1[3];
-    };
-    auto load_fac = [&](Fac &F, int n) {
-        const long long k0 = slice_of(n) * SL;
-        const int ks = k0 < rows ? (int)k0 : rows;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) F.f[j] = ld1(rRs, offF, (ks + j) * rsb);   // (the row in the scalar offset: one lane constant)
-    };
-    auto load_raw = [&](Raw &R, const Idx &I, int n) {
-        const long long k0 = slice_of(n) * SL;
-        const bool live = k0 < rows;
-        // descriptors of this slice: T rows [k0, k0 + SL); dO rows [g0, min(rows, k0 + SL + kTrowWindow)) with g0 = max(0, k0 - kTrowWindow)
-        long long left = (long long)rows - k0;
-        left = left < 0 ? 0 : left > SL ? SL : left;
-        const long long k0c = live ? k0 : 0;
-        const __amdgpu_buffer_rsrc_t rT = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(T + (size_t)k0c * ACOLS), 0, (unsigned)(left * TROW), 0x00020000);
-        const long long g0 = k0c > kTrowWindow ? k0c - kTrowWindow : 0;
-        long long g1 = k0c + SL + kTrowWindow;
-        g1 = g1 > rows ? rows : g1;
-        const __amdgpu_buffer_rsrc_t rD = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(dO + (size_t)g0 * 2 * CB), 0, live ? (unsigned)((g1 - g0) * DROW) : 0u, 0x00020000);
-        const int own = (int)(k0c - g0) * DROW;   // the slice's first row inside the dO window
-        const int ig0 = (int)g0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int t = I.t[j];
-            const bool pa = !packed || ((t >> abit) & 1);
-            const int va = pa ? offA : kOut;
-            // B: the slice's own rows, or (product 7) row trow of dU -- which only meets S_ab of ITS row: skipped where that is absent
-            const int tr = packed ? (t & 0x1fffffff) : t;
-            const bool pg = !packed || t < 0;
-            const int vg = pg ? (tr - ig0) * DROW + offG : kOut;
-            const int vb = gathered ? vg : offB;
-            const int sbo = gathered ? 0 : own + j * DROW;
-#pragma unroll
-            for (int u = 0; u < NT; ++u) {
-                R.a[u][j] = ld1(rT, va + 128 * u, j * TROW);
-                R.b[u][j] = ld1(rD, vb + 128 * u, sbo);
-            }
-        }
-    };
-    f16v acc[NT][NT];
-#pragma unroll
-    for (int mt = 0; mt < NT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
-    auto frag = [&](const float (&v)[8], float sc, const float *f, h8 *H, h8 *L) {
-        unsigned hw[4], lw[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            h2 h, l;
-            split_plain2(v[2 * i], v[2 * i + 1], f ? sc * f[2 * i] : sc, f ? sc * f[2 * i + 1] : sc, &h, &l);
-            hw[i] = __builtin_bit_cast(unsigned, h);
-            lw[i] = __builtin_bit_cast(unsigned, l);
-        }
-        *H = __builtin_bit_cast(h8, make_uint4(hw[0], hw[1], hw[2], hw[3]));
-        *L = __builtin_bit_cast(h8, make_uint4(lw[0], lw[1], lw[2], lw[3]));
-    };
-    if (slice_of(0) < nsl) {
-        const int mine = (int)((nsl - slice_of(0) + gridDim.x - 1) / gridDim.x);   // slices of this workgroup
-        Idx I0, I1;
-        Fac F0, F1;
-        Raw R0, R1;
-        load_idx(I0, 0);
-        load_idx(I1, 1);
-        load_fac(F0, 0);
-        load_raw(R0, I0, 0);
-        load_idx(I0, 2);
-        load_fac(F1, 1);
-        load_raw(R1, I1, 1);
-        // Step n: slice n's operands are in R and its factors in Fcur; slice n + 1's operands are in flight; slice n + 2's table
-        // entries (Inext2) and slice n + 1's factors were requested BEFORE those.  Nothing in the loop is conditional: slices past the
-        // end load zeros (descriptors of zero bytes) and add nothing, so an odd tail runs a whole pair of steps as well.
-        auto step = [&](Raw &R, Fac &Fcur, Idx &Inext2, Idx &Inext3, int n) {
-            h8 ah[NT], al[NT], bh[NT], bl[NT];
-            float fac[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) fac[j] = scaled ? Fcur.f[j] : 1.f;
-#pragma unroll
-            for (int u = 0; u < NT; ++u) {
-                frag(R.a[u], sa[u], nullptr, &ah[u], &al[u]);
-                frag(R.b[u], sb[u], fac, &bh[u], &bl[u]);
-            }
-            if constexpr (NT == 1)
-                asm volatile("" : "+v"(ah[0]), "+v"(al[0]), "+v"(bh[0]), "+v"(bl[0]));
-            else
-                asm volatile("" : "+v"(ah[0]), "+v"(al[0]), "+v"(ah[1]), "+v"(al[1]), "+v"(bh[0]), "+v"(bl[0]), "+v"(bh[1]), "+v"(bl[1]));
-            __builtin_amdgcn_sched_barrier(0);
-            load_idx(Inext3, n + 3);
-            load_fac(Fcur, n + 2);
-            load_raw(R, Inext2, n + 2);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int mt = 0; mt < NT; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-                }
-        };
-        for (int n = 0; n < mine; n += 2) {
-            step(R0, F0, I0, I1, n);       // (I0 = entries of slice n + 2, I1 <- slice n + 3)
-            step(R1, F1, I1, I0, n + 1);   // (I1 = entries of slice n + 3, I0 <- slice n + 4)
-        }
-    }
-    // back to fp32 units: row k of the product is column k of its A block, column n column n of its B block
-    float *out = part + ((size_t)blockIdx.x * 8 + wave) * (CB * CB) + lc;
-    const float *ia = sInv + ablk * CB, *ib = sInv + ACOLS + bblk * CB;
-    if constexpr (CB == 16) {
-        // the two half-slices' products: tile rows / columns [0, 16) and [16, 32) -- register r + 8 of lane ^ 16 joins register r
-        const float ub = ib[lc];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * lg;   // 0 .. 15
-            const float second = acc[0][0][r + 8];
-            const float v = acc[0][0][r] + __shfl_xor(second, 16);
-            if (li < 16) out[row * CB] = v * (ia[row] * ub);
-        }
-    } else {
-#pragma unroll
-        for (int mt = 0; mt < NT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const float ub = ib[32 * nt + li];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * lg;
-                    out[row * CB + 32 * nt] = acc[mt][nt][r] * (ia[row] * ub);
-                }
-            }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Round 5: the same products with ONE wave doing all eight for its slices (CB = 32 / 16).  smp_wgrad_direct gives every product a wave
-// of its own, so a slice's S_ab block is requested and split by four waves, L by five, S_bc and dU by two: sixteen block requests and
-// sixteen splits per slice for seven distinct blocks -- and the kernel is VALU-bound at these channel counts (SQ counters at C = 32:
-// 56 % of the SIMDs' issue slots are split instructions, half of the wave cycles wait for an issue slot).  Here a wave keeps the
-// eight accumulators (128 registers; one wave per SIMD, four per workgroup), requests the seven blocks of its slice once, splits nine
-// operands (four of T; L, tot L, tr L, dU, dU[trow] -- or eight factor-scaled ones under slice dropout, NF = 8) and runs the 24 MFMAs.
-// The four waves of a workgroup take its slices in turn; their images are added in wave order through LDS, so the partial-image
-// contract (one set of eight per workgroup, folded by smp_fold_level) is unchanged and the result does not depend on timing.
-// ---------------------------------------------------------------------------------------------------------------
 constexpr int kW8Threads = 256;
 // NX = 3 (SMP_2D_ver7 on the 18-slice level, gf_smp::n_extra): three more products on operands the slice already holds as fragments --
 // S_ab^T L, S_bc^T L, S_bc^T (tr L) -- whose images go to `xpart` (three per workgroup), folded by the caller into dX.
@@ -1250,7 +1026,7 @@ __global__ __launch_bounds__(kW8Threads, 1) void smp_wgrad_all(const float *__re
     static_assert(NX == 0 || (NX == 3 && NF == 2), "the extra products take the plain (tot, tr) row factors");
     constexpr int NP = 8 + NX;
     constexpr int ACOLS = 4 * CB, BCOLS = 5 * CB;
-    constexpr int SL = CB == 16 ? 2 * kWsSlice : kWsSlice;   // rows of a slice (CB = 16: two half-slices per tile, see smp_wgrad_direct)
+    constexpr int SL = CB == 16 ? 2 * kWsSlice : kWsSlice;   // rows of a slice (CB = 16: two half-slices per tile, see above)
     constexpr int TROW = 16 * CB, DROW = 8 * CB;             // bytes of a row of T, of dO
     constexpr int NBF = NF == 8 ? 8 : 5;                     // B fragments per slice
     __shared__ float sScale[ACOLS + BCOLS], sInv[ACOLS + BCOLS];
@@ -1479,7 +1255,7 @@ __global__ __launch_bounds__(kW8Threads, 1) void smp_wgrad_all(const float *__re
     }
 }
 
-// exact column bounds of the nine operand blocks of smp_wgrad_direct<CB> from the column maxima of T [rows][4 CB] (mt) and of
+// exact column bounds of the nine operand blocks of smp_wgrad_all<CB, 2> from the column maxima of T [rows][4 CB] (mt) and of
 // dO [rows][2 CB] (mo) and the largest |tot|, |tr| (mx): cmax [9 CB]
 __global__ void wgrad_bounds_exact_cb(const unsigned *__restrict__ mt, const unsigned *__restrict__ mo, const unsigned *__restrict__ mx,
                                       unsigned *__restrict__ cmax, int CB) {
@@ -1598,11 +1374,23 @@ __global__ void wgrad_bounds_exact(const unsigned *__restrict__ mt, const unsign
 
 bool smp_split_products(const gf_ctx *ctx) {  // (read per call: the parity tests switch it)
     if (ctx && ctx->fp32_products) return false;  // GF_OPT_SMP_FP32_PRODUCTS
-    const char *e = std::getenv("GF_SMP_SPLIT");
-    return !(e && e[0] == '0');
+    return !env_is("GF_SMP_SPLIT", '0');
+}
+
+// the level's packed transposed-row table with the presence bits (see smp_rowpanel_split) in place of the plain one: for levels of
+// fewer than `row_limit` rows, unless GF_SMP_MASK_ZEROS=0 (read per call: the parity tests switch it)
+static bool packed_rows(const int *trowf, int rows, int row_limit) {
+    return trowf && rows < row_limit && !env_is("GF_SMP_MASK_ZEROS", '0');
 }
 
 size_t smp_split_image_bytes() { return 2 * (size_t)kSpImgStride * sizeof(uint4); }
+template <int C>
+static gf_status launch_small_split(gf_ctx *ctx, const char *name, int total, size_t lds, const SmallJobs &jb, const uint4 *img) {
+    gf_status st = opt_in_lds(ctx, smp_small_split<C>, lds);
+    if (st != GF_OK) return st;
+    GF_LAUNCH(ctx, name, smp_small_split<C>, dim3((unsigned)total), dim3(kSmThreads), lds, jb, img);
+    return GF_OK;
+}
 // the small products of a level in one launch (see smp_small_split): n <= 3 jobs of prog 0 / 1 / 2 on `rows[j]` rows with the weight
 // images from stacked position pos0[j] on; `transposed` picks the backward images; wimg = the level's prebuilt images
 gf_status smp_small_split_c64(gf_ctx *ctx, bool transposed, int n, const int *prog, const float *const *In, float *const *Out, const int *rows,
@@ -1622,22 +1410,12 @@ gf_status smp_small_split_c64(gf_ctx *ctx, bool transposed, int n, const int *pr
     }
     if (total == 0) return GF_OK;
     const size_t lds = 2 * (size_t)4 * (C >= 32 ? C / 32 : 1) * (C / 16) * 64 * 16 + 16 * sizeof(float) + (kSmThreads / 64) * 32 * sizeof(float);
-    if (C == 16) {
-        gf_status st = opt_in_lds(ctx, smp_small_split<16>, lds);
-        if (st != GF_OK) return st;
-        GF_LAUNCH(ctx, name, smp_small_split<16>, dim3((unsigned)total), dim3(kSmThreads), lds, jb, img);
-    } else if (C == 64) {
-        gf_status st = opt_in_lds(ctx, smp_small_split<64>, lds);
-        if (st != GF_OK) return st;
-        GF_LAUNCH(ctx, name, smp_small_split<64>, dim3((unsigned)total), dim3(kSmThreads), lds, jb, img);
-    } else if (C == 32) {
-        gf_status st = opt_in_lds(ctx, smp_small_split<32>, lds);
-        if (st != GF_OK) return st;
-        GF_LAUNCH(ctx, name, smp_small_split<32>, dim3((unsigned)total), dim3(kSmThreads), lds, jb, img);
-    } else {
-        return fail(ctx, GF_ERR_UNSUPPORTED, "smp_small_split: %d channels", C);
+    switch (C) {
+    case 16: return launch_small_split<16>(ctx, name, total, lds, jb, img);
+    case 32: return launch_small_split<32>(ctx, name, total, lds, jb, img);
+    case 64: return launch_small_split<64>(ctx, name, total, lds, jb, img);
     }
-    return GF_OK;
+    return fail(ctx, GF_ERR_UNSUPPORTED, "smp_small_split: %d channels", C);
 }
 
 // the split weight images (both directions) of n levels' stacked weights in one launch; img[i]: smp_split_image_bytes() each
@@ -1655,6 +1433,31 @@ gf_status smp_split_build_images(gf_ctx *ctx, const float *const *Wst, void *con
     return GF_OK;
 }
 
+// the kernel arguments of smp_rowpanel_split that do not select an instantiation
+struct RowpanelArgs {
+    int grid;
+    const float *A, *rowscale, *Wst;
+    float *Out;
+    int rows;
+    const int *trow;   // the plain or (mask) the packed table
+    int store_mask;
+    const uint4 *img;   // this direction's weight images, or null
+};
+template <bool F, bool M, int CB, int NF, int NX>
+static gf_status launch_rowpanel_split(gf_ctx *ctx, const RowpanelArgs &a) {
+    const size_t lds = 2 * (size_t)(8 + NX) * (CB >= 32 ? CB / 32 : 1) * (CB / 16) * 64 * 16 + 32 * sizeof(float) + (kSpThreads / 64) * 32 * sizeof(float);
+    gf_status st = opt_in_lds(ctx, smp_rowpanel_split<F, M, CB, NF, NX>, lds);
+    if (st != GF_OK) return st;
+    GF_LAUNCH(ctx, F ? "smpf_products_fwd" : "smpf_products_bwd", (smp_rowpanel_split<F, M, CB, NF, NX>), dim3((unsigned)a.grid), dim3(kSpThreads),
+              lds, a.A, a.rowscale, a.Wst, a.Out, a.rows, a.trow, a.store_mask, a.img);
+    return GF_OK;
+}
+template <int CB, int NF, int NX = 0>
+static gf_status launch_rowpanel_split(gf_ctx *ctx, bool forward, bool mask, const RowpanelArgs &a) {
+    if (forward) return mask ? launch_rowpanel_split<true, true, CB, NF, NX>(ctx, a) : launch_rowpanel_split<true, false, CB, NF, NX>(ctx, a);
+    return mask ? launch_rowpanel_split<false, true, CB, NF, NX>(ctx, a) : launch_rowpanel_split<false, false, CB, NF, NX>(ctx, a);
+}
+
 // Row-panel products of a fused SMP level at C = 64, compact layout (O = [O_loc | U]; trow = the transposed-row table of the
 // level): forward O from T = [S_ab|S_bc|T6|T10], or backward dT from dO.  Every output element is produced by one wave in a
 // fixed order: results do not depend on the grid size.
@@ -1667,89 +1470,23 @@ gf_status smp_rowpanel_split_c64(gf_ctx *ctx, bool forward, const float *A, cons
     const int slots = C == 64 ? cus : 2 * cus;   // (C = 32 / 16: one or two per CU measured equal)
     const int grid = want < slots ? want : slots;
     if (C != 64 && !wimg) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_rowpanel_split: %d channels need the level's prebuilt weight images", C);
-    // packed table with the presence bits (see the kernel)
-    const bool mask = trowf && rows < (1 << 29) && !(std::getenv("GF_SMP_MASK_ZEROS") && std::getenv("GF_SMP_MASK_ZEROS")[0] == '0');
-#define GF_SP_LAUNCH_NX(F, M, CBv, NFv, NXv, name)                                                                                 \
-    do {                                                                                                                           \
-        const size_t lds__ = 2 * (size_t)(8 + NXv) * (CBv >= 32 ? CBv / 32 : 1) * (CBv / 16) * 64 * 16 + 32 * sizeof(float) + (kSpThreads / 64) * 32 * sizeof(float); \
-        gf_status st = opt_in_lds(ctx, smp_rowpanel_split<F, M, CBv, NFv, NXv>, lds__);                                            \
-        if (st != GF_OK) return st;                                                                                                \
-        GF_LAUNCH(ctx, name, (smp_rowpanel_split<F, M, CBv, NFv, NXv>), dim3((unsigned)grid), dim3(kSpThreads), lds__, A, rowscale, Wst, Out, rows, \
-                  M ? trowf : trow, skip_zero_grads ? 1 : 0,                                                                       \
-                  wimg ? static_cast<const uint4 *>(wimg) + (F ? 0 : kSpImgStride) : (const uint4 *)nullptr);                      \
-    } while (0)
-#define GF_SP_LAUNCH_NF(F, M, CBv, NFv, name) GF_SP_LAUNCH_NX(F, M, CBv, NFv, 0, name)
-#define GF_SP_LAUNCH(F, M, CBv, name) GF_SP_LAUNCH_NF(F, M, CBv, 2, name)
+    const bool mask = packed_rows(trowf, rows, 1 << 29);
+    const RowpanelArgs a = {grid, A, rowscale, Wst, Out, rows, mask ? trowf : trow, skip_zero_grads ? 1 : 0,
+                            wimg ? static_cast<const uint4 *>(wimg) + (forward ? 0 : kSpImgStride) : nullptr};
     if (nx != 0) {   // the extra products of SMP_2D_ver7 on the 18-slice level (see the kernel)
         if (nx != 3 || nf != 2 || !(C == 32 || C == 16) || !wimg)
             return fail(ctx, GF_ERR_UNSUPPORTED, "smp_rowpanel_split: %d extra products at %d channels / %d row factors", nx, C, nf);
-        if (C == 32) {
-            if (forward) {
-                if (mask) GF_SP_LAUNCH_NX(true, true, 32, 2, 3, "smpf_products_fwd");
-                else GF_SP_LAUNCH_NX(true, false, 32, 2, 3, "smpf_products_fwd");
-            } else {
-                if (mask) GF_SP_LAUNCH_NX(false, true, 32, 2, 3, "smpf_products_bwd");
-                else GF_SP_LAUNCH_NX(false, false, 32, 2, 3, "smpf_products_bwd");
-            }
-        } else {
-            if (forward) {
-                if (mask) GF_SP_LAUNCH_NX(true, true, 16, 2, 3, "smpf_products_fwd");
-                else GF_SP_LAUNCH_NX(true, false, 16, 2, 3, "smpf_products_fwd");
-            } else {
-                if (mask) GF_SP_LAUNCH_NX(false, true, 16, 2, 3, "smpf_products_bwd");
-                else GF_SP_LAUNCH_NX(false, false, 16, 2, 3, "smpf_products_bwd");
-            }
-        }
-        return GF_OK;
+        return C == 32 ? launch_rowpanel_split<32, 2, 3>(ctx, forward, mask, a) : launch_rowpanel_split<16, 2, 3>(ctx, forward, mask, a);
     }
     if (nf != 2 && !(nf == 8 && (C == 32 || C == 16))) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_rowpanel_split: %d row factors at %d channels", nf, C);
-    if (nf == 8 && C == 32) {   // (per-product row factors: the slice-dropout towers, computed at 32 or 16 channels)
-        if (forward) {
-            if (mask) GF_SP_LAUNCH_NF(true, true, 32, 8, "smpf_products_fwd");
-            else GF_SP_LAUNCH_NF(true, false, 32, 8, "smpf_products_fwd");
-        } else {
-            if (mask) GF_SP_LAUNCH_NF(false, true, 32, 8, "smpf_products_bwd");
-            else GF_SP_LAUNCH_NF(false, false, 32, 8, "smpf_products_bwd");
-        }
-    } else if (nf == 8) {
-        if (forward) {
-            if (mask) GF_SP_LAUNCH_NF(true, true, 16, 8, "smpf_products_fwd");
-            else GF_SP_LAUNCH_NF(true, false, 16, 8, "smpf_products_fwd");
-        } else {
-            if (mask) GF_SP_LAUNCH_NF(false, true, 16, 8, "smpf_products_bwd");
-            else GF_SP_LAUNCH_NF(false, false, 16, 8, "smpf_products_bwd");
-        }
-    } else if (C == 64) {
-        if (forward) {
-            if (mask) GF_SP_LAUNCH(true, true, 64, "smpf_products_fwd");
-            else GF_SP_LAUNCH(true, false, 64, "smpf_products_fwd");
-        } else {
-            if (mask) GF_SP_LAUNCH(false, true, 64, "smpf_products_bwd");
-            else GF_SP_LAUNCH(false, false, 64, "smpf_products_bwd");
-        }
-    } else if (C == 32) {
-        if (forward) {
-            if (mask) GF_SP_LAUNCH(true, true, 32, "smpf_products_fwd");
-            else GF_SP_LAUNCH(true, false, 32, "smpf_products_fwd");
-        } else {
-            if (mask) GF_SP_LAUNCH(false, true, 32, "smpf_products_bwd");
-            else GF_SP_LAUNCH(false, false, 32, "smpf_products_bwd");
-        }
-    } else if (C == 16) {
-        if (forward) {
-            if (mask) GF_SP_LAUNCH(true, true, 16, "smpf_products_fwd");
-            else GF_SP_LAUNCH(true, false, 16, "smpf_products_fwd");
-        } else {
-            if (mask) GF_SP_LAUNCH(false, true, 16, "smpf_products_bwd");
-            else GF_SP_LAUNCH(false, false, 16, "smpf_products_bwd");
-        }
-    } else {
-        return fail(ctx, GF_ERR_UNSUPPORTED, "smp_rowpanel_split: %d channels", C);
+    if (nf == 8)   // (per-product row factors: the slice-dropout towers, computed at 32 or 16 channels)
+        return C == 32 ? launch_rowpanel_split<32, 8>(ctx, forward, mask, a) : launch_rowpanel_split<16, 8>(ctx, forward, mask, a);
+    switch (C) {
+    case 64: return launch_rowpanel_split<64, 2>(ctx, forward, mask, a);
+    case 32: return launch_rowpanel_split<32, 2>(ctx, forward, mask, a);
+    case 16: return launch_rowpanel_split<16, 2>(ctx, forward, mask, a);
     }
-#undef GF_SP_LAUNCH
-#undef GF_SP_LAUNCH_NF
-#undef GF_SP_LAUNCH_NX
-    return GF_OK;
+    return fail(ctx, GF_ERR_UNSUPPORTED, "smp_rowpanel_split: %d channels", C);
 }
 
 // The eight row block products of a fused level at C = 64 (compact layout) as partial images, split operands: the contract of
@@ -1759,32 +1496,22 @@ gf_status smp_wgrad_partials_split_c64(gf_ctx *ctx, const float *T, const float 
                                        int splits, float *part, const int *trow, const WgradScales &ws, const int *trowf) {
     gf_status st = opt_in_lds(ctx, smp_wgrad_split, kWsLds);
     if (st != GF_OK) return st;
-    const bool mask = trowf && rows < (1 << 29) && !(std::getenv("GF_SMP_MASK_ZEROS") && std::getenv("GF_SMP_MASK_ZEROS")[0] == '0');
+    const bool mask = packed_rows(trowf, rows, 1 << 29);
     GF_LAUNCH(ctx, "smpf_wgrad", smp_wgrad_split, dim3((unsigned)splits), dim3(kWsThreads), kWsLds, T, dO, rowscale, rows, kchunk, part,
               mask ? trowf : trow, ws.cmax, ws.chan, ws.smax, ws.max_tot, ws.max_tr, ws.row_max, mask ? 1 : 0);
     return GF_OK;
 }
 
 
-// The eight row block products of a fused level at C = 32 (compact layout) as partial images of 8 x 32 x 32 floats: smp_wgrad_direct<32>.
-// Column exponents from the level's per-channel maxima (chan: [64] words, smax, row_max: see smp_wgrad_split), or -- chan null -- exact
-// column bounds taken from the operands themselves (one extra pass over T and dO; `words`: 512 + 9 * 32 scratch words).
-// one launch of the C = 32 / 16 weight-gradient kernel: smp_wgrad_all (a wave per slice, all eight products; round 5) unless
-// GF_SMP_WGRAD_ALL=0 selects smp_wgrad_direct (a wave per product)
+// one launch of smp_wgrad_all: nf row factors per row of rowscale; xpart: with the three extra products of SMP_2D_ver7
 template <int CB>
-static gf_status launch_wgrad_direct(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int splits, float *part,
-                                     const int *tr, const unsigned *cmax, const unsigned *chan, float smax, const unsigned *row_max, int packed, int nf,
-                                     float *xpart = nullptr) {
-    const char *e = std::getenv("GF_SMP_WGRAD_ALL");
-    if (xpart) {   // with the three extra products of SMP_2D_ver7 (callers check smp_wgrad_extra_supported first)
-        if (nf != 2 || (e && e[0] == '0')) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_wgrad_all: extra products with %d row factors / GF_SMP_WGRAD_ALL=0", nf);
+static gf_status launch_wgrad_all(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int splits, float *part,
+                                  const int *tr, const unsigned *cmax, const unsigned *chan, float smax, const unsigned *row_max, int packed, int nf,
+                                  float *xpart = nullptr) {
+    if (xpart) {
+        if (nf != 2) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_wgrad_all: extra products with %d row factors", nf);
         GF_LAUNCH(ctx, "smpf_wgrad", (smp_wgrad_all<CB, 2, 3>), dim3((unsigned)splits), dim3(kW8Threads), 0, T, dO, rowscale, rows, part, tr, cmax, chan, smax,
                   row_max, packed, xpart);
-        return GF_OK;
-    }
-    if (e && e[0] == '0') {
-        GF_LAUNCH(ctx, "smpf_wgrad", smp_wgrad_direct<CB>, dim3((unsigned)splits), dim3(kWdThreads), 0, T, dO, rowscale, rows, part, tr, cmax, chan, smax,
-                  row_max, packed, nf);
     } else if (nf == 8) {
         GF_LAUNCH(ctx, "smpf_wgrad", (smp_wgrad_all<CB, 8>), dim3((unsigned)splits), dim3(kW8Threads), 0, T, dO, rowscale, rows, part, tr, cmax, chan, smax,
                   row_max, packed);
@@ -1794,22 +1521,20 @@ static gf_status launch_wgrad_direct(gf_ctx *ctx, const float *T, const float *d
     }
     return GF_OK;
 }
-bool smp_wgrad_extra_supported(int nf) {
-    const char *e = std::getenv("GF_SMP_WGRAD_ALL");
-    return nf == 2 && !(e && e[0] == '0');
-}
-gf_status smp_wgrad_partials_direct_c32(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int splits, float *part,
-                                        const int *trow, const int *trowf, unsigned *words, const unsigned *chan, float smax,
-                                        const unsigned *row_max, int nf, int C, float *xpart) {
-    const bool mask = trowf && rows < (1 << 28) && !(std::getenv("GF_SMP_MASK_ZEROS") && std::getenv("GF_SMP_MASK_ZEROS")[0] == '0');
+// The eight row block products of a fused level at C = 32 / 16 (compact layout) as partial images of 8 x C x C floats: smp_wgrad_all<C>.
+// Column exponents from the level's per-channel maxima (chan: [2 C] words, smax, row_max: see smp_wgrad_split), or -- chan null -- exact
+// column bounds taken from the operands themselves (one extra pass over T and dO; `words`: smp_wgrad_all_words() scratch words).
+gf_status smp_wgrad_partials_all(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int splits, float *part,
+                                  const int *trow, const int *trowf, unsigned *words, const unsigned *chan, float smax,
+                                  const unsigned *row_max, int nf, int C, float *xpart) {
+    const bool mask = packed_rows(trowf, rows, 1 << 28);
+    const int *tr = mask ? trowf : trow;
     if (C == 16) {   // (round 5)
-        if (chan && row_max) {
-            if (gf_status st_ = launch_wgrad_direct<16>(ctx, T, dO, rowscale, rows, splits, part, mask ? trowf : trow, (const unsigned *)nullptr, chan, smax, row_max, mask ? 1 : 0, nf, xpart); st_ != GF_OK) return st_;
-            return GF_OK;
-        }
+        if (chan && row_max)
+            return launch_wgrad_all<16>(ctx, T, dO, rowscale, rows, splits, part, tr, (const unsigned *)nullptr, chan, smax, row_max, mask ? 1 : 0, nf, xpart);
         // host-built level tables: exact column bounds from the operands themselves -- T [rows][64] and dO [rows][32] are one
         // "channel maxima" pass each (words [0, 64) and [256, 288)), then the nine blocks' bounds (words [512, 512 + 144))
-        if (nf != 2) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_wgrad_direct: exact column bounds with per-product row factors");
+        if (nf != 2) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_wgrad_all: exact column bounds with per-product row factors");
         GF_HIP_TRY(ctx, hipMemsetAsync(words, 0, sizeof(unsigned) * 512, ctx->stream));
         const long long g0 = ((long long)rows + 63) / 64;
         const unsigned g = (unsigned)(g0 < 1 ? 1 : g0 > 256 ? 256 : g0);
@@ -1817,39 +1542,34 @@ gf_status smp_wgrad_partials_direct_c32(gf_ctx *ctx, const float *T, const float
         GF_LAUNCH(ctx, "smpf_colmax", level_channel_maxima_ld, dim3(g, 1), dim3(256), 0, dO, (long long)rows, 32, (const float *)nullptr, 0ll, 0, 32, words + 256);
         GF_LAUNCH(ctx, "smpf_colmax", rowscale_absmax, dim3(64), dim3(256), 0, rowscale, rows, words + 384);
         GF_LAUNCH(ctx, "smpf_colmax", wgrad_bounds_exact_cb, dim3(1), dim3(64), 0, words, words + 256, words + 384, words + 512, 16);
-        if (gf_status st_ = launch_wgrad_direct<16>(ctx, T, dO, rowscale, rows, splits, part, mask ? trowf : trow, words + 512, (const unsigned *)nullptr, 0.f, (const unsigned *)nullptr, mask ? 1 : 0, nf, xpart); st_ != GF_OK) return st_;
-        return GF_OK;
+        return launch_wgrad_all<16>(ctx, T, dO, rowscale, rows, splits, part, tr, words + 512, (const unsigned *)nullptr, 0.f, (const unsigned *)nullptr, mask ? 1 : 0, nf, xpart);
     }
-    if (C != 32) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_wgrad_direct: %d channels", C);
+    if (C != 32) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_wgrad_all: %d channels", C);
     constexpr int CB = 32;
-    if (chan && row_max) {
-        if (gf_status st_ = launch_wgrad_direct<CB>(ctx, T, dO, rowscale, rows, splits, part, mask ? trowf : trow, (const unsigned *)nullptr, chan, smax, row_max, mask ? 1 : 0, nf, xpart); st_ != GF_OK) return st_;
-        return GF_OK;
-    }
+    if (chan && row_max)
+        return launch_wgrad_all<CB>(ctx, T, dO, rowscale, rows, splits, part, tr, (const unsigned *)nullptr, chan, smax, row_max, mask ? 1 : 0, nf, xpart);
     GF_HIP_TRY(ctx, hipMemsetAsync(words, 0, sizeof(unsigned) * 512, ctx->stream));
     const long long g0 = ((long long)rows + 15) / 16;
     const unsigned g = (unsigned)(g0 < 1 ? 1 : g0 > 1024 ? 1024 : g0);
     // column maxima in chunks of 64 columns: T [rows][128] -> words [0, 128), dO [rows][64] -> words [256, 320)
     for (int k = 0; k < 4 * CB / 64; ++k) GF_LAUNCH(ctx, "smpf_colmax", col_absmax64, dim3(g), dim3(256), 0, T + 64 * k, (long long)rows, 4 * CB, words + 64 * k);
     for (int k = 0; k < 2 * CB / 64; ++k) GF_LAUNCH(ctx, "smpf_colmax", col_absmax64, dim3(g), dim3(256), 0, dO + 64 * k, (long long)rows, 2 * CB, words + 256 + 64 * k);
-    if (nf != 2) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_wgrad_direct: exact column bounds with per-product row factors");
+    if (nf != 2) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_wgrad_all: exact column bounds with per-product row factors");
     GF_LAUNCH(ctx, "smpf_colmax", rowscale_absmax, dim3(64), dim3(256), 0, rowscale, rows, words + 384);
     GF_LAUNCH(ctx, "smpf_colmax", wgrad_bounds_exact_cb, dim3(1), dim3(64), 0, words, words + 256, words + 384, words + 512, CB);
-    if (gf_status st_ = launch_wgrad_direct<CB>(ctx, T, dO, rowscale, rows, splits, part, mask ? trowf : trow, words + 512, (const unsigned *)nullptr, 0.f, (const unsigned *)nullptr, mask ? 1 : 0, nf, xpart); st_ != GF_OK) return st_;
-    return GF_OK;
+    return launch_wgrad_all<CB>(ctx, T, dO, rowscale, rows, splits, part, tr, words + 512, (const unsigned *)nullptr, 0.f, (const unsigned *)nullptr, mask ? 1 : 0, nf, xpart);
 }
-size_t smp_wgrad_direct_words_c32() { return 512 + 9 * 32; }
+size_t smp_wgrad_all_words() { return 512 + 9 * 32; }
 // workgroups (= partial image sets) of the C = 32 / 16 weight-gradient launch for a level of `rows` rows.  smp_wgrad_all keeps one wave
 // per SIMD (its eight accumulators): ONE workgroup per CU -- measured at C = 32, cfg3: 0.44 ms with 256 workgroups, 0.53 with 512 (the
-// second half waits for whole CUs), 0.72 with 1024; smp_wgrad_direct (116 registers) ran two per CU.
-int smp_wgrad_direct_splits(gf_ctx *ctx, long long rows) {
+// second half waits for whole CUs), 0.72 with 1024.
+int smp_wgrad_all_splits(gf_ctx *ctx, long long rows) {
     static int cu_count[64] = {};
     const int di = ctx->device & 63;
     if (!cu_count[di]) {
         if (hipDeviceGetAttribute(&cu_count[di], hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cu_count[di] < 1) cu_count[di] = 256;
     }
-    const char *e = std::getenv("GF_SMP_WGRAD_ALL");
-    const long long cap = (e && e[0] == '0') ? 512 : cu_count[di];
+    const long long cap = cu_count[di];
     const long long slices = (rows + 15) / 16, want = slices / 8;
     return (int)(want < 1 ? 1 : want > cap ? cap : want);
 }

@@ -5,6 +5,7 @@ TEST INFRASTRUCTURE ONLY -- importable from tests/, __graft_entry__.smoke() and 
 The product package (graphflow_amd) never imports this module.
 """
 import ctypes as C
+import hashlib
 import os
 import subprocess
 
@@ -24,10 +25,12 @@ def build(force=False):
         subprocess.check_call(["make", "-C", _HERE, "libgf_oracle.so"])
     ref_root = os.environ.get("GF_REFERENCE", "/root/reference")
     outs = [os.path.join(_HERE, "_ref", f) for f in ("libgf_ref.so", "dropin_reference_check")]
-    deps = [os.path.join(_HERE, "ref_shim.cpp")] + dropin_sources()
     if os.path.isdir(os.path.join(ref_root, "GraphFlow")):
-        if force or not all(map(os.path.exists, outs)) or min(map(os.path.getmtime, outs)) < max(map(os.path.getmtime, deps)):
+        # (stale by content, not by file times: a checkout that rewrites a source unchanged does not make the programs stale)
+        if force or not all(map(os.path.exists, outs)) or ref_built_from() != ref_digest():
             subprocess.check_call(["make", "-C", _HERE, "ref", "GF_REFERENCE=" + ref_root])
+            with open(REF_STAMP, "w") as f:
+                f.write(ref_digest())
 
 
 def dropin_sources():
@@ -36,6 +39,28 @@ def dropin_sources():
     host = os.path.join(root, "graphflow_amd", "host")
     return ([os.path.join(root, "tests", "cpp", "dropin_reference_check.cpp"), os.path.join(root, "include", "gf_hip.h")]
             + [os.path.join(host, f) for f in sorted(os.listdir(host)) if f.endswith(".h")])
+
+
+# build() records here the digest of the sources the programs under oracle/_ref were built from
+REF_STAMP = os.path.join(_HERE, "_ref", "sources.sha256")
+
+
+def ref_digest():
+    """sha256 over the names and contents of the sources of oracle/_ref: ref_shim.cpp and dropin_sources()."""
+    root = os.path.dirname(_HERE)
+    h = hashlib.sha256()
+    for path in [os.path.join(_HERE, "ref_shim.cpp")] + dropin_sources():
+        with open(path, "rb") as f:
+            h.update(os.path.relpath(path, root).encode() + b"\0" + f.read() + b"\0")
+    return h.hexdigest()
+
+
+def ref_built_from():
+    """The digest build() recorded when it last built oracle/_ref, or None."""
+    if not os.path.exists(REF_STAMP):
+        return None
+    with open(REF_STAMP) as f:
+        return f.read().strip()
 
 
 def _load(path):

@@ -15,14 +15,15 @@ def bins(gf, oracle):
     return os.path.join(CPP, "bin")
 
 
-def test_op_headers_drop_into_the_real_reference_tree():
+def test_op_headers_drop_into_the_real_reference_tree_from_the_current_sources():
     """Our op classes compiled + linked against the reference's OWN containers: build() does it (oracle/Makefile `ref`) where the
-    reference is mounted; the program must be there and newer than every source it is built from."""
+    reference is mounted; the program must be there and built from the sources as they are now (the digest of their contents
+    build() recorded, not file times: a checkout may rewrite a source unchanged after the build)."""
     from oracle import pyoracle
     exe = os.path.join(ROOT, "oracle", "_ref", "dropin_reference_check")
     if not os.path.exists(exe):
         pytest.skip("oracle/_ref/dropin_reference_check not built (reference not mounted when building)")
-    assert os.path.getmtime(exe) >= max(os.path.getmtime(f) for f in pyoracle.dropin_sources())
+    assert pyoracle.ref_built_from() == pyoracle.ref_digest(), "oracle/_ref was built from other sources: run build()"
 
 
 def test_inline_rand_stream_is_glibcs_rand_stream(bins):

@@ -444,7 +444,7 @@ def test_c64_level_kernels_equal_the_tiled_gemm_path(gf, monkeypatch):
 def test_c32_row_panel_kernels_equal_the_tiled_gemm_path(gf, monkeypatch):
     """Round 4: at C = 32 the block products of a fused level run on the same split-operand row-panel kernels as at C = 64 (32 x 32
     blocks: one column half, two k-chunks per lane; compact two-block projection with the transposed-row gather; structural zeros
-    read from the zero page) and the weight gradients on smp_wgrad_direct<32> (operands loaded straight into MFMA layout, exact
+    read from the zero page) and the weight gradients on smp_wgrad_all<32> (operands loaded straight into MFMA layout, exact
     column bounds).  GF_SMP_ROWPANEL=0 selects the grouped tiled fp32 GEMMs with the three-block projection that the other channel
     counts run.  29-atom molecules: ragged last panels and slices, rows without data in every block."""
     F, D, C, L, cap = 5, 5, 32, 3, 29
@@ -1553,7 +1553,7 @@ def test_device_level_tables_equal_the_host_built_ones(gf, monkeypatch, C, fused
     assert all(np.array_equal(x, y) for x, y in zip(a[3], b[3]))
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
     if fused and C <= 32:
-        # computed at 32 channels (padded, gf_smp_create): smp_wgrad_direct<32> takes its column exponents from the device-built
+        # computed at 32 channels (padded, gf_smp_create): smp_wgrad_all<32> takes its column exponents from the device-built
         # statistics words (largest |tot|, |tr|) when the tables were built there and from the operands' exact column maxima
         # otherwise -- two valid power-of-two scalings of the same split, equal to the last bits only
         assert rel_err(a[2].astype(np.float64), b[2].astype(np.float64)) <= 2e-7

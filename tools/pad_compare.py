@@ -1,4 +1,4 @@
-"""Gradients of one SMP_omega step at C channels, computed at 16 and at 32 padded channels: per parameter block, max |diff| / max |g|.
+"""Gradients of one SMP_omega step at C channels, computed at 16 padded channels and unpadded: per parameter block, max |diff| / max |g|.
 usage: python tools/pad_compare.py [C] [batch] [scale]"""
 import os, sys, subprocess, json
 import numpy as np
@@ -24,7 +24,7 @@ Cn = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 scale = float(sys.argv[3]) if len(sys.argv) > 3 else 0.1
 res = {}
-for tag, env in (("p16", {}), ("p32", {"GF_SMP_PAD_CHANNELS": "3"}), ("p16_old", {"GF_SMP_WGRAD_ALL": "0"}), ("unfused", {"GF_SMP_PAD_CHANNELS": "0"})):
+for tag, env in (("p16", {}), ("unfused", {"GF_SMP_PAD_CHANNELS": "0"})):
     out = "/tmp/g_%s.npy" % tag
     subprocess.run([sys.executable, __file__, "--child", str(Cn), str(B), str(scale), out], env=dict(os.environ, **env), check=True)
     res[tag] = np.load(out).astype(np.float64)
@@ -41,8 +41,7 @@ for l in range(1, L + 1):
     blocks.append(("b%d" % l, o, o + Cn)); o += Cn
 blocks.append(("W", o, o + Cn))
 ref = res["unfused"]
-print("block            max|g|      p16-unf    p32-unf    p16old-unf   (relative to the block's max)")
+print("block            max|g|      p16-unf   (relative to the block's max)")
 for name, a, b in blocks:
     m = np.abs(ref[a:b]).max() + 1e-300
-    print("%-12s %10.3e  %10.2e %10.2e %10.2e" % (name, m, np.abs(res["p16"][a:b] - ref[a:b]).max() / m, np.abs(res["p32"][a:b] - ref[a:b]).max() / m,
-                                                 np.abs(res["p16_old"][a:b] - ref[a:b]).max() / m))
+    print("%-12s %10.3e  %10.2e" % (name, m, np.abs(res["p16"][a:b] - ref[a:b]).max() / m))
