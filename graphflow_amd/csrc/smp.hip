@@ -1095,14 +1095,20 @@ gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channel
     s->req_pad_channels = pad_channels;
     s->req_min_pad = min_pad;
     gf::smp_derive_plan(s, /*allow_embed=*/true);
+    if (s->cfg.nContractions == 4 && (s->cfg.physics || s->cfg.custom_matmul)) {   // SMP_gamma: Reshape2D + MatMul on [4 C][C], one model body
+        const bool phys = s->cfg.physics != 0;
+        delete s;
+        return fail(ctx, GF_ERR_INVALID, phys ? "gf_smp_create: nContractions = 4 (SMP_gamma) has no physics tower: set physics = 0"
+                                              : "gf_smp_create: nContractions = 4 (SMP_gamma) applies K_l [4 C][C] by Reshape2D + MatMul: set custom_matmul = 0");
+    }
     if (s->cfg.physics && (s->cfg.nDepth != 0 || s->cfg.nContractions != 18 || s->cfg.custom_matmul)) {
         delete s;
         return fail(ctx, GF_ERR_INVALID, "gf_smp_create: a physics tower has nDepth 0 (raw features), RisiContraction_18 and [18 C', C] weights");
     }
-    if (s->cfg.nContractions != 10 && s->cfg.nContractions != 18 && s->cfg.nContractions != 50) {
+    if (s->cfg.nContractions != 4 && s->cfg.nContractions != 10 && s->cfg.nContractions != 18 && s->cfg.nContractions != 50) {
         const int bad = cfg->nContractions;
         delete s;
-        return fail(ctx, GF_ERR_INVALID, "gf_smp_create: nContractions = %d (expected 10, 18 or 50)", bad);
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_create: nContractions = %d (expected 4, 10, 18 or 50)", bad);
     }
     s->bwd_gather = gf::env_is("GF_SMP_BWD_GATHER", '0') ? 0 : 1;   // 0: keep the two-kernel tables-backward + consumer gather
     *out = s;
@@ -1517,7 +1523,8 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
         if (st != GF_OK) return st;
         st = gf::upload(s, &d.cons_pair, h.cons_pair.empty() ? nullptr : &h.cons_pair[0], h.cons_pair.size());
         if (st != GF_OK) return st;
-        {
+        const bool gamma = s->cfg.nContractions == 4;   // SMP_gamma: none of the 18-slice level's scratch (smp_level_gamma.hip)
+        if (!gamma) {
             float **cb[] = {&d.Fdc, &d.Gc, &d.dGc, &d.dFdc};
             for (int q = 0; q < 4; ++q) {
                 st = gf::upload(s, cb[q], nullptr, (size_t)B.level[l - 1].pairs * 2 * C);
@@ -1590,9 +1597,15 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
                 if (st != GF_OK) return st;
             }
         }
-        st = gf::upload(s, &d.Q, nullptr, (size_t)h.rows * std::max(18, s->cfg.nContractions) * Cp);
+        // (a `_4` level: T [rows][4C] op by op, G / dG [rows of level l - 1][4C] on the gamma level)
+        const size_t qrows = gamma ? (size_t)std::max<int64_t>(h.rows, B.level[l - 1].rows) : (size_t)h.rows;
+        st = gf::upload(s, &d.Q, nullptr, qrows * (gamma ? 4 : std::max(18, s->cfg.nContractions)) * Cp);
         if (st != GF_OK) return st;
-        if (s->cfg.square()) {
+        if (gamma && s->cfg.square()) {   // the gamma level's weight views [8 C^2] and its weight-gradient image [4 C^2]
+            st = gf::upload(s, &d.Wst, nullptr, (size_t)8 * C * C);
+            if (st == GF_OK) st = gf::upload(s, &d.dWst, nullptr, (size_t)4 * C * C);
+            if (st != GF_OK) return st;
+        } else if (s->cfg.square()) {
             float **bufs[] = {&d.Vt, &d.dVt, &d.St, &d.dSt, &d.scal, &d.Vout, &d.dVout, &d.Sout, &d.dSout, &d.dSpart, &d.dbpart, &d.Wst, &d.dWst};
             const size_t sizes[] = {(size_t)h.pairs * 4 * C, (size_t)h.pairs * 4 * C, (size_t)h.nNodes * 4 * C, (size_t)h.nNodes * 4 * C,
                                     (size_t)h.pairs * 4 * C, (size_t)h.pairs * C, (size_t)h.pairs * C, (size_t)h.nNodes * C,
@@ -2123,6 +2136,11 @@ static gf_status smp_forward_impl(gf_smp *s, const float *params, const float *t
             if (st != GF_OK) return st;
             continue;
         }
+        if (gf::smp_gamma_fused(s, l)) {   // SMP_gamma: products on the rows of level l - 1, one gather into f_l (smp_level_gamma.hip)
+            st = gf::smp_gamma_forward_level(s, l, K[l], b[l]);
+            if (st != GF_OK) return st;
+            continue;
+        }
         s->lv[l].t_zeros = s->lv[l].t_filled = false;  // (the op-by-op level uses all of Q: the zeros kept in the fused level's T region are gone)
         st = gf::ensure_P(s);
         if (st != GF_OK) return st;
@@ -2417,6 +2435,11 @@ static gf_status smp_backward_impl(gf_smp *s, const float *params, float *grads,
             GF_LAUNCH(ctx, "smp_lrelu_bwd", gf::lrelu_backward_colsum, dim3(nb), dim3(256), 0, d.f, d.df, s->colpart, Cc,
                       (long long)h.rows, rpb);
             GF_LAUNCH(ctx, "smp_colsum", gf::colsum_finish, dim3(1), dim3(256), 0, s->colpart, db[l], Cc, nb);
+            if (gf::smp_gamma_fused(s, l)) {   // SMP_gamma: dG gathered from dz, dK_l and df_{l-1} on the rows of level l - 1
+                st = gf::smp_gamma_backward_level(s, l, K[l], dK[l], gf::smp_dp_level_done);
+                if (st != GF_OK) return st;
+                continue;   // (no physics tower has `_4` levels: level l - 1 is not read out)
+            }
             // dK_l += Q^T dZ   (MatMul::backward second operand), then dQ = dZ K_l^T overwrites Q (first operand)
             const int KC = s->cfg.nContractions * Cq;
             st = gf::extra_products_wgrad(s, l);

@@ -257,6 +257,12 @@ gf_status smp_fused_ensure_zero_fill(gf_smp *s, int l);
 // node_df != nullptr (top level): df_l is the same C-vector at every position of a node, given as [nodes][C]
 gf_status smp_fused_backward_level(gf_smp *s, int l, const float *Kl, float *dKl, float *dbl, const float *node_df, bool rows_too = false);
 gf_status smp_fused_gather_backward(gf_smp *s, int l);
+// SMP_gamma levels (RisiContraction_4, smp_level_gamma.hip): G = f_{l-1} [K0 | K1 | K2 | K3] on the rows of level l - 1 into Q, then one gather
+// with bias + LeakyReLU into f_l; backward the consumer gather of dG from dz, dK_l and df_{l-1} as products on the rows of level l - 1.
+// Scratch: Wst [8 C^2] (the weight views), dWst [4 C^2]; Q at least [rows of level l - 1][4C].
+bool smp_gamma_fused(const gf_smp *s, int l);
+gf_status smp_gamma_forward_level(gf_smp *s, int l, const float *Kl, const float *bl);
+gf_status smp_gamma_backward_level(gf_smp *s, int l, const float *Kl, float *dKl, gf_status (*wgrad_done)(gf_smp *, int));
 bool smp_fused_gather_enabled(const gf_smp *s, int l);
 gf_status smp_fused_stack_all(gf_smp *s, const std::vector<const float *> &K);
 gf_status smp_build_gather_records(gf_smp *s, int l, hipStream_t stream);

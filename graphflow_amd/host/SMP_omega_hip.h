@@ -55,6 +55,16 @@ protected:
         init(has_WL_ordering);
     }
 
+    // SMP_gamma (below): RisiContraction_4 with [4 C][C] weights (Reshape2D + MatMul), no receptive-field cap, Adam
+    struct gamma_wiring {};
+    SMP_omega_hip(gamma_wiring, bool use_coulomb, int max_nVertices, int nLevels, int nChanels, int nFeatures, int nDepth,
+                  bool has_WL_ordering)
+        : max_nVertices(max_nVertices), max_receptive_field(max_nVertices), nLevels(nLevels), nChanels(nChanels),
+          nFeatures(nFeatures), nDepth(nDepth), use_coulomb(use_coulomb), net(NULL) {
+        wiring_contractions = 4;
+        init(has_WL_ordering);
+    }
+
 private:
     int wiring_contractions = 0, wiring_custom = 0;
     double momentum = 0.0;
@@ -224,6 +234,16 @@ public:
     SMP_2D_ver8_hip(int max_nVertices, int nLevels, int nChanels, int nFeatures, int nDepth, double momentum_param,
                     bool has_WL_ordering = true)
         : SMP_omega_hip(max_nVertices, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering, 18, momentum_param) {}
+};
+
+// SMP_gamma (GraphFlow/SMP_gamma.h:29-1190): the SMP_omega DAG with RisiContraction_4, no receptive-field cap and no reduced
+// adjacency (the use_coulomb constructors are accepted; RisiContraction_4 reads no adjacency).  Constructors of :31, :48, :65, :82.
+class SMP_gamma_hip : public SMP_omega_hip {
+public:
+    SMP_gamma_hip(int max_nVertices, int nLevels, int nChanels, int nFeatures, int nDepth, bool has_WL_ordering = true)
+        : SMP_omega_hip(gamma_wiring(), false, max_nVertices, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering) {}
+    SMP_gamma_hip(bool use_coulomb, int max_nVertices, int nLevels, int nChanels, int nFeatures, int nDepth, bool has_WL_ordering = true)
+        : SMP_omega_hip(gamma_wiring(), use_coulomb, max_nVertices, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering) {}
 };
 
 #endif

@@ -209,6 +209,14 @@ class SMPOmega:
             pass
 
 
+class SMPGamma(SMPOmega):
+    """Batched SMP_gamma (GraphFlow/SMP_gamma.h): the SMP_omega DAG with RisiContraction_4, no receptive-field cap and no
+    reduced adjacency.  Parameters in registration order: H[C, F(D+1)], (K_l[4C, C], b_l[C]) for l = 1..L, W[C]."""
+
+    def __init__(self, nLevels, nChanels, nFeatures, nDepth, max_nVertices, has_WL_ordering=True, ctx=None):
+        super().__init__(nLevels, nChanels, nFeatures, nDepth, max_nVertices, has_WL_ordering, ctx=ctx, nContractions=4)
+
+
 class SMPModelConfig(C.Structure):
     _fields_ = [("nTowers", C.c_int), ("nLevels", C.c_int), ("nChanels", C.c_int), ("max_receptive_field", C.c_int),
                 ("nFeatures", C.c_int * 2), ("nKept", C.c_int)]

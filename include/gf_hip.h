@@ -237,7 +237,13 @@ typedef struct {
      * three extra products for `_50`); the parameter / gradient layout at this interface stays the caller's.  A batch the embedding cannot
      * take -- an asymmetric or negative adjacency, a `_50` Coulomb batch, a `_10` Coulomb batch with an entry <= 0 -- is computed on the
      * op-by-op `_10` / `_50` levels instead: gf_smp_prepare picks the plan per batch (round 6; it used to refuse with GF_ERR_UNSUPPORTED),
-     * nothing changes at this interface.  GF_SMP_VER6_FUSED=0 / GF_SMP_VER7_FUSED=0 at create time select the op-by-op levels for every batch. */
+     * nothing changes at this interface.  GF_SMP_VER6_FUSED=0 / GF_SMP_VER7_FUSED=0 at create time select the op-by-op levels for every batch.
+     * nContractions = 4 with custom_matmul = 0 is SMP_gamma (GraphFlow/SMP_gamma.h): RisiContraction_4, K_l = [4C][C] by Reshape2D + MatMul,
+     * no receptive-field cap (pass max_receptive_field = max_nVertices), no reduced adjacency (gf_smp_prepare_coulomb gives the results of
+     * gf_smp_prepare).  Refused with physics = 1 or custom_matmul = 1.  A level runs the fused gamma level (smp_level_gamma.hip) when the
+     * channel count the device computes with is a multiple of 4 and at most 64 (gf_smp_create pads any nChanels to a multiple of 4 -- unless
+     * GF_SMP_PAD_CHANNELS=0 or nLevels is beyond the padding's limit, where e.g. 5 or 10 channels stay unpadded) and its fields hold at
+     * most 64 positions; otherwise, and under gf_smp_set_fused(0), promotion + the batched `_4` kernels run.  Same results either way. */
     int nContractions, custom_matmul;
     /* physics = 1: one TOWER of the `_physics` / `_pairgraphs` models (GraphFlow/SMP_omega_physics.h:29-170, :480-606;
      * SMP_omega_pairgraphs.h builds two of them): raw vertex features (nDepth must be 0; no WL histogram or ordering, the
