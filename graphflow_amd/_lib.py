@@ -127,6 +127,7 @@ PROTOTYPES.update({
     "gf_smp_model_destroy": (_i, [_vp]),
     "gf_smp_model_param_count": (C.c_size_t, [_vp]),
     "gf_smp_model_set_mode": (_i, [_vp, _i]),
+    "gf_smp_model_set_fused": (_i, [_vp, _i]),
     "gf_smp_model_prepare": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gf_smp_model_forward": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "gf_smp_model_backward": (_i, [_vp, _vp, _vp, _i]),

@@ -1003,7 +1003,13 @@ using gf::fail;
 
 extern "C" {
 
-gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out) { return gf::smp_create(ctx, cfg, /*pad_channels=*/true, out); }
+// (a gamma physics tower is built by gf_smp_model_create only: the single-model handle keeps refusing it)
+gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out) {
+    if (cfg && cfg->physics && cfg->nContractions == 4)
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_create: nContractions = 4 (SMP_gamma) has no single-handle physics tower: set physics = 0, or build "
+                                         "SMP_gamma_physics / SMP_gamma_pairgraphs with gf_smp_model_create (nContractions = 4)");
+    return gf::smp_create(ctx, cfg, /*pad_channels=*/true, out);
+}
 
 }  // extern "C"
 
@@ -1095,15 +1101,15 @@ gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channel
     s->req_pad_channels = pad_channels;
     s->req_min_pad = min_pad;
     gf::smp_derive_plan(s, /*allow_embed=*/true);
-    if (s->cfg.nContractions == 4 && (s->cfg.physics || s->cfg.custom_matmul)) {   // SMP_gamma: Reshape2D + MatMul on [4 C][C], one model body
-        const bool phys = s->cfg.physics != 0;
+    if (s->cfg.nContractions == 4 && s->cfg.custom_matmul) {   // SMP_gamma: Reshape2D + MatMul on [4 C][C]
         delete s;
-        return fail(ctx, GF_ERR_INVALID, phys ? "gf_smp_create: nContractions = 4 (SMP_gamma) has no physics tower: set physics = 0"
-                                              : "gf_smp_create: nContractions = 4 (SMP_gamma) applies K_l [4 C][C] by Reshape2D + MatMul: set custom_matmul = 0");
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_create: nContractions = 4 (SMP_gamma) applies K_l [4 C][C] by Reshape2D + MatMul: set custom_matmul = 0");
     }
-    if (s->cfg.physics && (s->cfg.nDepth != 0 || s->cfg.nContractions != 18 || s->cfg.custom_matmul)) {
+    // (a tower of SMP_gamma_physics / SMP_gamma_pairgraphs: RisiContraction_4, K_l [4 C_{l-1}][C_l], computed at its own halving widths --
+    //  smp_derive_plan pads only `_18` towers; the gamma tower level is smp_level_gamma.hip's rectangular one)
+    if (s->cfg.physics && (s->cfg.nDepth != 0 || (s->cfg.nContractions != 18 && s->cfg.nContractions != 4) || s->cfg.custom_matmul)) {
         delete s;
-        return fail(ctx, GF_ERR_INVALID, "gf_smp_create: a physics tower has nDepth 0 (raw features), RisiContraction_18 and [18 C', C] weights");
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_create: a physics tower has nDepth 0 (raw features), RisiContraction_18 or _4 and [nK C', C] weights");
     }
     if (s->cfg.nContractions != 4 && s->cfg.nContractions != 10 && s->cfg.nContractions != 18 && s->cfg.nContractions != 50) {
         const int bad = cfg->nContractions;
@@ -1597,13 +1603,13 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
                 if (st != GF_OK) return st;
             }
         }
-        // (a `_4` level: T [rows][4C] op by op, G / dG [rows of level l - 1][4C] on the gamma level)
+        // (a `_4` level: T [rows][4 Cp] op by op, G / dG [rows of level l - 1][4 Cc] on the gamma level; Cc <= Cp)
         const size_t qrows = gamma ? (size_t)std::max<int64_t>(h.rows, B.level[l - 1].rows) : (size_t)h.rows;
         st = gf::upload(s, &d.Q, nullptr, qrows * (gamma ? 4 : std::max(18, s->cfg.nContractions)) * Cp);
         if (st != GF_OK) return st;
-        if (gamma && s->cfg.square()) {   // the gamma level's weight views [8 C^2] and its weight-gradient image [4 C^2]
-            st = gf::upload(s, &d.Wst, nullptr, (size_t)8 * C * C);
-            if (st == GF_OK) st = gf::upload(s, &d.dWst, nullptr, (size_t)4 * C * C);
+        if (gamma) {   // the gamma level's weight views [8 Cp Cc] and its weight-gradient image [4 Cp Cc] (Cp = Cc = C unless a tower)
+            st = gf::upload(s, &d.Wst, nullptr, (size_t)8 * Cp * Cl);
+            if (st == GF_OK) st = gf::upload(s, &d.dWst, nullptr, (size_t)4 * Cp * Cl);
             if (st != GF_OK) return st;
         } else if (s->cfg.square()) {
             float **bufs[] = {&d.Vt, &d.dVt, &d.St, &d.dSt, &d.scal, &d.Vout, &d.dVout, &d.Sout, &d.dSout, &d.dSpart, &d.dbpart, &d.Wst, &d.dWst};
@@ -2438,7 +2444,11 @@ static gf_status smp_backward_impl(gf_smp *s, const float *params, float *grads,
             if (gf::smp_gamma_fused(s, l)) {   // SMP_gamma: dG gathered from dz, dK_l and df_{l-1} on the rows of level l - 1
                 st = gf::smp_gamma_backward_level(s, l, K[l], dK[l], gf::smp_dp_level_done);
                 if (st != GF_OK) return st;
-                continue;   // (no physics tower has `_4` levels: level l - 1 is not read out)
+                if (dfeat) {   // (a gamma tower: level l - 1 is read out too; its read-out gradient joins the df_{l-1} the GEMM wrote)
+                    st = feature_backward(l - 1, 1);
+                    if (st != GF_OK) return st;
+                }
+                continue;
             }
             // dK_l += Q^T dZ   (MatMul::backward second operand), then dQ = dZ K_l^T overwrites Q (first operand)
             const int KC = s->cfg.nContractions * Cq;

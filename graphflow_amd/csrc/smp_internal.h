@@ -259,7 +259,8 @@ gf_status smp_fused_backward_level(gf_smp *s, int l, const float *Kl, float *dKl
 gf_status smp_fused_gather_backward(gf_smp *s, int l);
 // SMP_gamma levels (RisiContraction_4, smp_level_gamma.hip): G = f_{l-1} [K0 | K1 | K2 | K3] on the rows of level l - 1 into Q, then one gather
 // with bias + LeakyReLU into f_l; backward the consumer gather of dG from dz, dK_l and df_{l-1} as products on the rows of level l - 1.
-// Scratch: Wst [8 C^2] (the weight views), dWst [4 C^2]; Q at least [rows of level l - 1][4C].
+// Scratch: Wst [8 Cp Cc] (the weight views), dWst [4 Cp Cc]; Q at least [rows of level l - 1][4 Cc].  Cp = C_{l-1}, Cc = C_l: equal
+// (C) for SMP_gamma, halving in a tower of SMP_gamma_physics / _pairgraphs (packed gathers gamma_tower_fwd / _bwd).
 bool smp_gamma_fused(const gf_smp *s, int l);
 gf_status smp_gamma_forward_level(gf_smp *s, int l, const float *Kl, const float *bl);
 gf_status smp_gamma_backward_level(gf_smp *s, int l, const float *Kl, float *dKl, gf_status (*wgrad_done)(gf_smp *, int));

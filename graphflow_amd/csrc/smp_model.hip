@@ -3,6 +3,7 @@
 //   SMP_omega_pairgraphs / SMP_beta_pairgraphs      two towers (a graph and its partner, e.g. the line graph) + a two-hidden-layer
 //                                                   head                                    (GraphFlow/SMP_omega_pairgraphs.h:81-730)
 //   SMP_sigma_pairgraphs                            the same with RisiContraction_18_dropout   (GraphFlow/SMP_sigma_pairgraphs.h)
+//   SMP_gamma_physics / SMP_gamma_pairgraphs        the same with RisiContraction_4, K_l [4 C_{l-1}][C_l] (nContractions = 4)
 // A tower is a gf_smp handle with cfg.physics = 1 (smp.hip): raw features, channels halving per level, every level read out.
 // The model's parameter / gradient vectors are flat device buffers in the REFERENCE's registration order:
 //   physics     H, (K_l, b_l) l = 1..L, W1, W2                                                 (SMP_omega_physics.h:254-262)
@@ -110,9 +111,16 @@ gf_status gf_smp_model_create(gf_ctx *ctx, const gf_smp_model_config *cfg, gf_sm
     if (cfg->nTowers < 1 || cfg->nTowers > 2 || cfg->nLevels < 1 || cfg->nChanels < 1 || cfg->max_receptive_field < 1 || cfg->nKept < 0 ||
         cfg->nKept > 18)
         return fail(ctx, GF_ERR_INVALID, "gf_smp_model_create: bad configuration");
+    const int nK = cfg->nContractions ? cfg->nContractions : 18;
+    if (nK != 18 && nK != 4)
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_model_create: nContractions = %d (expected 0 or 18: RisiContraction_18, 4: RisiContraction_4)",
+                    cfg->nContractions);
+    if (nK == 4 && cfg->nKept > 0)
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_model_create: nKept > 0 (RisiContraction_18_dropout) with nContractions = 4: no such model");
     gf_smp_model *m = new gf_smp_model();
     m->ctx = ctx;
     m->cfg = *cfg;
+    m->cfg.nContractions = nK;
     m->nTowers = cfg->nTowers;
     m->L = cfg->nLevels;
     for (int l = 0; l <= m->L; ++l) {
@@ -124,7 +132,7 @@ gf_status gf_smp_model_create(gf_ctx *ctx, const gf_smp_model_config *cfg, gf_sm
     // the H matrices come first (one per tower), then the levels, towers interleaved inside a level
     size_t toff[2] = {0, 0};
     for (int t = 0; t < m->nTowers; ++t) {
-        gf_smp_config tc = {cfg->nLevels, cfg->nChanels, cfg->nFeatures[t], 0, cfg->max_receptive_field, 0, 18, 0, 1};
+        gf_smp_config tc = {cfg->nLevels, cfg->nChanels, cfg->nFeatures[t], 0, cfg->max_receptive_field, 0, nK, 0, 1};
         // (nKept > 0, RisiContraction_18_dropout: towers of up to 32 channels run the fused levels with per-product slice factors since
         //  round 5 -- padded like the others; wider ones keep their levels op by op, at their own halving widths)
         gf_status st = gf::smp_create(ctx, &tc, /*pad_channels=*/cfg->nKept <= 0 || cfg->nChanels <= 32, &m->tower[t]);
@@ -140,7 +148,7 @@ gf_status gf_smp_model_create(gf_ctx *ctx, const gf_smp_model_config *cfg, gf_sm
     }
     for (int l = 1; l <= m->L; ++l)
         for (int t = 0; t < m->nTowers; ++t) {
-            const size_t n = (size_t)18 * m->lvlC[l - 1] * m->lvlC[l] + m->lvlC[l];
+            const size_t n = (size_t)nK * m->lvlC[l - 1] * m->lvlC[l] + m->lvlC[l];
             m->segs[t].push_back({off, toff[t], n});
             off += n;
             toff[t] += n;
@@ -202,6 +210,16 @@ size_t gf_smp_model_param_count(const gf_smp_model *m) { return m ? m->n_params 
 gf_status gf_smp_model_set_mode(gf_smp_model *m, int train) {
     if (!m) return fail(nullptr, GF_ERR_INVALID, "null model");
     m->train = train != 0;
+    return GF_OK;
+}
+
+gf_status gf_smp_model_set_fused(gf_smp_model *m, int on) {
+    if (!m) return fail(nullptr, GF_ERR_INVALID, "null model");
+    for (int t = 0; t < m->nTowers; ++t) {
+        const gf_status st = gf_smp_set_fused(m->tower[t], on);   // (drops the towers' forward state: a new forward comes first)
+        if (st != GF_OK) return st;
+    }
+    m->forwarded = false;
     return GF_OK;
 }
 
@@ -353,7 +371,7 @@ gf_status gf_smp_model_uniform_init_host(const gf_smp_model *m, float *params) {
     for (int t = 0; t < m->nTowers; ++t) sizes.push_back((size_t)C * m->cfg.nFeatures[t]);
     for (int l = 1; l <= m->L; ++l)
         for (int t = 0; t < m->nTowers; ++t) {
-            sizes.push_back((size_t)18 * m->lvlC[l - 1] * m->lvlC[l]);
+            sizes.push_back((size_t)m->cfg.nContractions * m->lvlC[l - 1] * m->lvlC[l]);
             sizes.push_back((size_t)m->lvlC[l]);
         }
     for (int i = 1; i <= m->nLayers; ++i) sizes.push_back((size_t)m->widths[i] * m->widths[i - 1]);

@@ -5,6 +5,9 @@
 //   SMP_omega_pairgraphs_hip(max_nV_1, max_nV_2, max_rf, nLevels, nChanels, nFeatures_1, _2)       GraphFlow/SMP_omega_pairgraphs.h:81
 //   SMP_beta_pairgraphs_hip(max_nV_1, max_nV_2, nLevels, nChanels, nFeatures_1, _2)                GraphFlow/SMP_beta_pairgraphs.h:81
 //   SMP_sigma_pairgraphs_hip(..., nKept) + setMode / setTrainMode / setTestMode                    GraphFlow/SMP_sigma_pairgraphs.h:81,139
+//   SMP_gamma_physics_hip([use_coulomb,] max_nVertices, max_receptive_field, nLevels, nChanels, nFeatures)
+//                                                                                                  GraphFlow/SMP_gamma_physics.h:31,47
+//   SMP_gamma_pairgraphs_hip(max_nV_1, max_nV_2, max_rf, nLevels, nChanels, nFeatures_1, _2)       GraphFlow/SMP_gamma_pairgraphs.h
 // with the reference's public training / inference methods: BatchLearn, Threaded_BatchLearn, getLoss, Predict,
 // Threaded_Predict, init_multi_threads (accepted, nothing to do: a batch is one device pass), save_model / load_model (the
 // text format of SMP_omega_physics.h:927-949: every parameter value in registration order).  The constructors draw the initial
@@ -24,13 +27,14 @@
 
 class SMP_model_hip {
 protected:
-    SMP_model_hip(int nTowers, int maxV1, int maxV2, int max_rf, int nLevels, int nChanels, int F1, int F2, int nKept)
+    // nContractions: 18 (RisiContraction_18 / _18_dropout towers) or 4 (the `_gamma` models: RisiContraction_4, K_l [4 C_{l-1}][C_l])
+    SMP_model_hip(int nTowers, int maxV1, int maxV2, int max_rf, int nLevels, int nChanels, int F1, int F2, int nKept, int nContractions = 18)
         : net(NULL), towers(nTowers) {
         maxV[0] = maxV1;
         maxV[1] = maxV2;
         nF[0] = F1;
         nF[1] = F2;
-        gf_smp_model_config cfg = {nTowers, nLevels, nChanels, max_rf, {F1, F2}, nKept};
+        gf_smp_model_config cfg = {nTowers, nLevels, nChanels, max_rf, {F1, F2}, nKept, nContractions};
         must(gf_smp_model_create(gfhost::default_context(), &cfg, &net), "gf_smp_model_create");
         std::vector<float> w(gf_smp_model_param_count(net));
         must(gf_smp_model_uniform_init_host(net, &w[0]), "gf_smp_model_uniform_init_host");  // weights_initialization()
@@ -130,6 +134,13 @@ class SMP_omega_physics_hip : public SMP_model_hip {
 public:
     SMP_omega_physics_hip(int max_nVertices, int max_receptive_field, int nLevels, int nChanels, int nFeatures)
         : SMP_model_hip(1, max_nVertices, 0, max_receptive_field, nLevels, nChanels, nFeatures, 0, 0) {}
+
+protected:
+    struct gamma_wiring {};
+    SMP_omega_physics_hip(gamma_wiring, int max_nVertices, int max_receptive_field, int nLevels, int nChanels, int nFeatures)
+        : SMP_model_hip(1, max_nVertices, 0, max_receptive_field, nLevels, nChanels, nFeatures, 0, 0, 4) {}
+
+public:
     template <class Graph>
     double getLoss(int nBatch, Graph **molecule, double *target) {
         pack(0, nBatch, molecule);
@@ -174,6 +185,14 @@ public:
     SMP_omega_pairgraphs_hip(int max_nVertices_1, int max_nVertices_2, int max_receptive_field, int nLevels, int nChanels,
                              int nFeatures_1, int nFeatures_2, int nKept = 0)
         : SMP_model_hip(2, max_nVertices_1, max_nVertices_2, max_receptive_field, nLevels, nChanels, nFeatures_1, nFeatures_2, nKept) {}
+
+protected:
+    struct gamma_wiring {};
+    SMP_omega_pairgraphs_hip(gamma_wiring, int max_nVertices_1, int max_nVertices_2, int max_receptive_field, int nLevels, int nChanels,
+                             int nFeatures_1, int nFeatures_2)
+        : SMP_model_hip(2, max_nVertices_1, max_nVertices_2, max_receptive_field, nLevels, nChanels, nFeatures_1, nFeatures_2, 0, 4) {}
+
+public:
     template <class Graph>
     double getLoss(int nBatch, Graph **molecule_1, Graph **molecule_2, double *target) {
         bind(nBatch, molecule_1, molecule_2);
@@ -223,6 +242,27 @@ public:
     SMP_sigma_pairgraphs_hip(int max_nVertices_1, int max_nVertices_2, int max_receptive_field, int nLevels, int nChanels,
                              int nFeatures_1, int nFeatures_2, int nKept)
         : SMP_omega_pairgraphs_hip(max_nVertices_1, max_nVertices_2, max_receptive_field, nLevels, nChanels, nFeatures_1, nFeatures_2, nKept) {}
+};
+
+// SMP_gamma_physics (GraphFlow/SMP_gamma_physics.h): SMP_omega_physics with RisiContraction_4 and K_l [4 C_{l-1}][C_l], no reduced
+// adjacency.  The use_coulomb constructor builds the same model: the reference stores the flag and never reads it.
+class SMP_gamma_physics_hip : public SMP_omega_physics_hip {
+public:
+    SMP_gamma_physics_hip(int max_nVertices, int max_receptive_field, int nLevels, int nChanels, int nFeatures)
+        : SMP_omega_physics_hip(gamma_wiring(), max_nVertices, max_receptive_field, nLevels, nChanels, nFeatures) {}
+    SMP_gamma_physics_hip(bool use_coulomb, int max_nVertices, int max_receptive_field, int nLevels, int nChanels, int nFeatures)
+        : SMP_omega_physics_hip(gamma_wiring(), max_nVertices, max_receptive_field, nLevels, nChanels, nFeatures) {
+        (void)use_coulomb;
+    }
+};
+
+// SMP_gamma_pairgraphs (GraphFlow/SMP_gamma_pairgraphs.h): SMP_omega_pairgraphs with RisiContraction_4 towers
+class SMP_gamma_pairgraphs_hip : public SMP_omega_pairgraphs_hip {
+public:
+    SMP_gamma_pairgraphs_hip(int max_nVertices_1, int max_nVertices_2, int max_receptive_field, int nLevels, int nChanels, int nFeatures_1,
+                             int nFeatures_2)
+        : SMP_omega_pairgraphs_hip(gamma_wiring(), max_nVertices_1, max_nVertices_2, max_receptive_field, nLevels, nChanels, nFeatures_1,
+                                   nFeatures_2) {}
 };
 
 #endif

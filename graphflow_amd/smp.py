@@ -219,18 +219,20 @@ class SMPGamma(SMPOmega):
 
 class SMPModelConfig(C.Structure):
     _fields_ = [("nTowers", C.c_int), ("nLevels", C.c_int), ("nChanels", C.c_int), ("max_receptive_field", C.c_int),
-                ("nFeatures", C.c_int * 2), ("nKept", C.c_int)]
+                ("nFeatures", C.c_int * 2), ("nKept", C.c_int), ("nContractions", C.c_int)]
 
 
 class SMPModel:
     """The _physics (one tower) / _pairgraphs (two towers, nKept > 0: SMP_sigma_pairgraphs) models of GraphFlow through
-    gf_smp_model_*.  Parameters / gradients: one flat fp32 tensor in the class's registration order."""
+    gf_smp_model_*.  nContractions = 4: SMP_gamma_physics / SMP_gamma_pairgraphs (RisiContraction_4, K_l[4 C_{l-1}, C_l]).
+    Parameters / gradients: one flat fp32 tensor in the class's registration order."""
 
-    def __init__(self, nLevels, nChanels, max_receptive_field, nFeatures, nKept=0, ctx=None):
+    def __init__(self, nLevels, nChanels, max_receptive_field, nFeatures, nKept=0, ctx=None, nContractions=18):
         feats = list(nFeatures) if isinstance(nFeatures, (list, tuple)) else [nFeatures]
         self.ctx = ctx or default_context()
         self.lib = self.ctx.lib
-        self.cfg = SMPModelConfig(len(feats), nLevels, nChanels, max_receptive_field, (C.c_int * 2)(*(feats + [0])[:2]), nKept)
+        self.cfg = SMPModelConfig(len(feats), nLevels, nChanels, max_receptive_field, (C.c_int * 2)(*(feats + [0])[:2]), nKept,
+                                  nContractions)
         h = C.c_void_p()
         self.ctx.check(self.lib.gf_smp_model_create(self.ctx.handle, C.byref(self.cfg), C.byref(h)))
         self.handle = h
@@ -256,6 +258,16 @@ class SMPModel:
 
     def set_mode(self, train=True):
         self.ctx.check(self.lib.gf_smp_model_set_mode(self.handle, 1 if train else 0))
+
+    def set_fused(self, on=True):
+        """False: every tower level op by op (promotion + contraction kernels + K-projection), the parity yardstick."""
+        self.ctx.check(self.lib.gf_smp_model_set_fused(self.handle, 1 if on else 0))
+
+    def uniform_init_host(self):
+        """weights_initialization(): the initial weights the reference class draws from rand() (call srand first)."""
+        out = np.empty(self.n_params, dtype=np.float32)
+        self.ctx.check(self.lib.gf_smp_model_uniform_init_host(self.handle, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
 
     def forward(self, params, targets=None):
         t = C.c_void_p(targets.data_ptr()) if targets is not None else None

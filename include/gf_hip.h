@@ -240,7 +240,8 @@ typedef struct {
      * nothing changes at this interface.  GF_SMP_VER6_FUSED=0 / GF_SMP_VER7_FUSED=0 at create time select the op-by-op levels for every batch.
      * nContractions = 4 with custom_matmul = 0 is SMP_gamma (GraphFlow/SMP_gamma.h): RisiContraction_4, K_l = [4C][C] by Reshape2D + MatMul,
      * no receptive-field cap (pass max_receptive_field = max_nVertices), no reduced adjacency (gf_smp_prepare_coulomb gives the results of
-     * gf_smp_prepare).  Refused with physics = 1 or custom_matmul = 1.  A level runs the fused gamma level (smp_level_gamma.hip) when the
+     * gf_smp_prepare).  Refused with custom_matmul = 1, and by gf_smp_create with physics = 1 (a gamma tower is built by
+     * gf_smp_model_create, gf_smp_model_config.nContractions = 4).  A level runs the fused gamma level (smp_level_gamma.hip) when the
      * channel count the device computes with is a multiple of 4 and at most 64 (gf_smp_create pads any nChanels to a multiple of 4 -- unless
      * GF_SMP_PAD_CHANNELS=0 or nLevels is beyond the padding's limit, where e.g. 5 or 10 channels stay unpadded) and its fields hold at
      * most 64 positions; otherwise, and under gf_smp_set_fused(0), promotion + the batched `_4` kernels run.  Same results either way. */
@@ -251,7 +252,8 @@ typedef struct {
      * K_l = [18 C_{l-1}][C_l], :141-156), and EVERY level is read out (:572-588).  Parameters: H[C][F], (K_l, b_l) l = 1..L -- no
      * readout vector.  gf_smp_forward then only fills graph_feature = [nMol][gf_smp_feature_width] (the ConcatVectors row, :590;
      * targets / predict / loss must be NULL) and the reverse sweep starts from gf_smp_backward_features.  The fully-connected
-     * head on top is gf_head_*.  SMP_beta_physics / _pairgraphs = the same with max_receptive_field = max_nVertices. */
+     * head on top is gf_head_*.  SMP_beta_physics / _pairgraphs = the same with max_receptive_field = max_nVertices.
+     * nContractions 18 (or 0); 4 (the towers of SMP_gamma_physics / _pairgraphs, K_l = [4 C_{l-1}][C_l]) only through gf_smp_model_create. */
     int physics;
 } gf_smp_config;
 gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out);
@@ -377,17 +379,26 @@ gf_status gf_adam_step_f32(gf_ctx *ctx, float *params, const float *grads, float
  *            slices; masks drawn with rand() in the reference's order in train mode, all slices x nKept / 18 in test mode).
  * params / grads: flat device buffers in the class's registration order -- physics H, (K_l, b_l)..., W1, W2 (:254-262);
  * pairgraphs H_1, H_2, (K1_l, b1_l, K2_l, b2_l)..., W1, W2, W3 (SMP_omega_pairgraphs.h:361-375).  grads = the batch SUM.
- * prepare: host pointers as gf_smp_prepare, one set per tower (the second set NULL for nTowers 1).                             */
+ * prepare: host pointers as gf_smp_prepare, one set per tower (the second set NULL for nTowers 1).
+ * nContractions = 4: SMP_gamma_physics / SMP_gamma_pairgraphs (GraphFlow/SMP_gamma_physics.h, SMP_gamma_pairgraphs.h): the same
+ *            models with RisiContraction_4 and K_l = [4 C_{l-1}][C_l]; receptive fields, halving channels, read-out of every level,
+ *            heads, registration order and weights_initialization unchanged (use_coulomb is inert in the reference: nothing to pass).
+ *            The towers compute at their own widths, on the rectangular gamma level of smp_level_gamma.hip where every width is at
+ *            most 64 channels and every field at most 64 positions (otherwise, and under gf_smp_model_set_fused(0), op by op).
+ *            0 (or an aggregate initialiser that stops before the field) means 18; other values, and nKept > 0 with 4, are refused. */
 typedef struct gf_smp_model gf_smp_model;
 typedef struct {
     int nTowers, nLevels, nChanels, max_receptive_field;
     int nFeatures[2];
     int nKept;   /* 0: RisiContraction_18; 1..18: RisiContraction_18_dropout */
+    int nContractions;   /* 0 or 18: the `_omega` / `_beta` / `_sigma` models; 4: the `_gamma` ones */
 } gf_smp_model_config;
 gf_status gf_smp_model_create(gf_ctx *ctx, const gf_smp_model_config *cfg, gf_smp_model **out);
 gf_status gf_smp_model_destroy(gf_smp_model *model);
 size_t    gf_smp_model_param_count(const gf_smp_model *model);
 gf_status gf_smp_model_set_mode(gf_smp_model *model, int train);   /* SMP_sigma_pairgraphs::setMode (:139-149); default train */
+/* gf_smp_set_fused on every tower (1, the default: the fused levels where the shape allows; 0: op by op) */
+gf_status gf_smp_model_set_fused(gf_smp_model *model, int on);
 gf_status gf_smp_model_prepare(gf_smp_model *model, int nMol, const int *nVertices1, const int *adj1, const double *feature1,
                                const int *nVertices2, const int *adj2, const double *feature2);
 gf_status gf_smp_model_forward(gf_smp_model *model, const float *params, const float *targets, float *predict, float *loss);
