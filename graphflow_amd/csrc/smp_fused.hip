@@ -1528,7 +1528,7 @@ gf_status smp_fused_stack_all(gf_smp *s, const std::vector<const float *> &K) {
         StackAll a;
         a.n = 0;
         for (int l = l0; l <= L && a.n < kStackLevels; ++l) {
-            if (!(s->fused && smp_fused_supported(s, l))) continue;
+            if (smp_level_kind(s, l) != LevelKind::Fused18) continue;
             a.K[a.n] = K[l];
             a.stacked[a.n] = s->lv[l].Wst;
             ++a.n;
@@ -1542,7 +1542,7 @@ gf_status smp_fused_stack_all(gf_smp *s, const std::vector<const float *> &K) {
         std::vector<const float *> w, x;
         std::vector<void *> im;
         for (int l = 1; l <= L; ++l)
-            if (s->fused && smp_fused_supported(s, l) && s->lv[l].wimg) {
+            if (smp_level_kind(s, l) == LevelKind::Fused18 && s->lv[l].wimg) {
                 w.push_back(s->lv[l].Wst);
                 x.push_back((s->n_extra && s->extra_w) ? s->extra_w + (size_t)(l - 1) * 3 * C * C : nullptr);   // (images 18 .. 20: SMP_2D_ver7's extra products)
                 im.push_back(s->lv[l].wimg);

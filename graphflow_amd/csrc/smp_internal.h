@@ -1,4 +1,6 @@
-// smp_internal.h -- state of one gf_smp handle, shared by smp.hip (op-by-op level pipeline) and smp_fused.hip.
+// smp_internal.h -- state of one gf_smp handle and what its translation units share: smp.hip (create / plan, the forward and reverse
+// sweeps, op-by-op levels), smp_prepare.hip (buffer pool, device-built tables, gf_smp_prepare), smp_pad.hip (channel padding, the ver6 / ver7
+// embedding), smp_optim.hip (host-pointer mode, optimisers, checkpoints), smp_fused.hip + smp_level_*.hip (fused levels), smp_model.hip.
 #ifndef GF_SMP_INTERNAL_H_INCLUDED
 #define GF_SMP_INTERNAL_H_INCLUDED
 
@@ -99,7 +101,7 @@ struct gf_smp {
     float *pad_p = nullptr, *pad_g = nullptr, *pad_feat = nullptr;   // padded copies (cfg.nChanels != ucfg.nChanels)
     // Round 5, SMP_2D_ver6 (RisiContraction_10) on the fused RisiContraction_18 level: != 0 = the caller's channel count C.  With a symmetric
     // reduced adjacency every one of the ten "1+1+1" slices is a slice of RisiContraction_18 applied to f_{l-1} or to its per-node
-    // TRANSPOSE (smp.hip: v6_slot), so the device computes an 18-slice model on [f | f^T | 0] channels: channels [C, 2C) of every level's
+    // TRANSPOSE (smp_pad.hip: v6_slot), so the device computes an 18-slice model on [f | f^T | 0] channels: channels [C, 2C) of every level's
     // activations hold the transposed matrices (dup_transposed_channels after each level, fold_transposed_channels in the reverse sweep)
     int dup_channels = 0;
     // ... and SMP_2D_ver7 (RisiContraction_50) likewise: 46 of its 50 slices are slices of RisiContraction_18 on f or f^T; the other four
@@ -150,7 +152,7 @@ struct gf_smp {
         // fused forward level at C = 64 (smp_level_c64_fwd.hip): row panels of whole (node, x) groups, per-row gather indices
         int4 *fwd_pan = nullptr;
         int *cons_of_pair = nullptr;       // [pairs] index of a pair in its source's consumer list (build_node_tables)
-        bool node_tables_merged = false;   // this batch's rows-sized tables of the level came from build_node_tables (smp.hip)
+        bool node_tables_merged = false;   // this batch's rows-sized tables of the level came from build_node_tables (smp_prepare.hip)
         int *fwd_pan_node = nullptr, *node_panel = nullptr;
         int2 *fwd_goff = nullptr;
         int fwd_npanels = 0;
@@ -188,7 +190,7 @@ struct gf_smp {
         float *sh = nullptr, *vf = nullptr;
         int *node_of_vertex = nullptr, *node_mol = nullptr;
         int *node_present = nullptr;  // [nodes] rows with data of the node (device-built tables)
-        int *field = nullptr;  // [pairs] receptive fields back to back (device-built level tables: smp.hip build_level_rows)
+        int *field = nullptr;  // [pairs] receptive fields back to back (device-built level tables: smp_prepare.hip build_level_rows)
         unsigned *keep_mask = nullptr;  // [nodes] slice masks of RisiContraction_18_dropout for this forward (gf_smp_dropout_masks)
         float *nodefac = nullptr, *rowfac8 = nullptr;  // fused levels under slice dropout: [nodes][18] slice factors, [rows][8] per-product row factors
         // fused level (smp_fused.hip): small per-(node,x) / per-node tables and stacked weights
@@ -250,6 +252,11 @@ inline bool smp_panel_channels(int C) { return C == 64 || C == 32 || C == 16; }
 // nodes of a level (a 48-atom molecule's level-3 fields reach 35) run tables-forward and the two combine steps on workgroup kernels,
 // everything else is row-based and does not care (smp_fused.hip: big_part)
 constexpr int kFusedMaxField = 64;
+// What runs level l >= 1 of a pass: the fused 18-slice level (smp_fused.hip) where gf_smp_set_fused allows and smp_fused_supported takes the
+// shape, else the SMP_gamma level where smp_gamma_fused does, else the op-by-op pipeline (smp.hip); nobody else asks the two predicates.
+// Constant for the length of a pass, NOT between passes (gf_smp_set_fused, gf_smp_dropout_masks): a sweep asks at its start, keeps nothing.
+enum class LevelKind { OpByOp, Fused18, Gamma };
+LevelKind smp_level_kind(const gf_smp *s, int l);
 bool smp_fused_supported(const gf_smp *s, int l);
 gf_status smp_backward_admissible(const gf_smp *s);   // smp.hip: refusals of a reverse sweep that must come before any work is issued
 gf_status smp_fused_forward_level(gf_smp *s, int l, const float *Kl, const float *bl);
@@ -273,9 +280,64 @@ gf_status smp_combine_fwd_panels_c64(gf_smp *s, int l, const float *O, const flo
                                      const float *nodefac = nullptr);
 // combine-backward on the forward's row panels (C = 64 / 32, compact dO): dzmax = [fwd_npanels][C] per-panel column maxima of |dz| or null
 gf_status smp_combine_bwd_panels_c64(gf_smp *s, int l, const float *dfrows, const float *node_df, float *dO, float *dzmax);
-gf_status ensure_P(gf_smp *s);
-size_t feature_width(const gfsmp::Config &c);  // physics tower: sum over the levels of their channel counts
 // level l's K_l / b_l gradients are complete on the context's CURRENT stream (l == 0: H): start their all-reduce
 gf_status smp_dp_level_done(gf_smp *s, int l);
+
+// ---- the parameter layout: H, (K_1, b_1), ..., (K_L, b_L), W -- the registration order of SMP_omega.h:289-295 (= save_model order) ----
+inline size_t param_count(const gfsmp::Config &c) {
+    size_t n = (size_t)c.nChanels * c.fdim();
+    for (int l = 1; l <= c.nLevels; ++l)
+        n += (size_t)c.nContractions * c.level_channels(l - 1) * c.level_channels(l) + c.level_channels(l);
+    return n + (c.physics ? 0 : c.nChanels);  // a physics tower ends in its level features: the head's weights are the caller's
+}
+template <typename P>
+void view_params(const gfsmp::Config &c, P *base, P **H, std::vector<P *> *K, std::vector<P *> *b, P **W) {
+    P *p = base;
+    *H = p;
+    p += (size_t)c.nChanels * c.fdim();
+    K->assign(c.nLevels + 1, nullptr);
+    b->assign(c.nLevels + 1, nullptr);
+    for (int l = 1; l <= c.nLevels; ++l) {
+        (*K)[l] = p;
+        p += (size_t)c.nContractions * c.level_channels(l - 1) * c.level_channels(l);
+        (*b)[l] = p;
+        p += c.level_channels(l);
+    }
+    *W = p;
+}
+inline size_t feature_width(const gfsmp::Config &c) {  // physics tower: sum over the levels of their channel counts
+    size_t w = 0;
+    for (int l = 0; l <= c.nLevels; ++l) w += (size_t)c.level_channels(l);
+    return w;
+}
+
+// ---- smp_prepare.hip: the handle's pool of device blocks and the page-locked allocator of the per-batch host tables ----
+// A buffer of `count` elements of `elem` bytes (at least one) from the pool -- the best-fitting idle block, else a new hipMalloc --
+// filled from `src` on the handle's upload stream when given
+gf_status upload_bytes(gf_smp *s, void **dst, const void *src, size_t elem, size_t count);
+template <typename T>
+inline gf_status upload(gf_smp *s, T **dst, const void *src, size_t count) {
+    void *p = nullptr;
+    const gf_status st = upload_bytes(s, &p, src, sizeof(T), count);
+    *dst = static_cast<T *>(p);
+    return st;
+}
+gf_status ensure_P(gf_smp *s);
+void mark_used(gf_smp *s);      // the handle's buffers were last touched by the launches before this mark
+void release(gf_smp *s);        // end of a batch: its buffers go back to the pool
+void release_pool(gf_smp *s);
+void *pinned_table_alloc(size_t bytes);
+void pinned_table_free(void *p);
+gf_status own_model(gf_smp *s);   // smp_optim.hip: the handle-owned parameter / gradient buffers (host-pointer mode), created on first use
+// ---- smp_pad.hip: the caller's layout against the device's (channel padding, SMP_2D_ver6 / ver7 on the 18-slice level) ----
+gf_status pad_params_now(gf_smp *s, const float *params);           // caller's parameters -> s->pad_p
+gf_status crop_grads_now(gf_smp *s, float *grads, int accumulate);  // s->pad_g -> caller's gradients
+gf_status pad_feature_buffer(gf_smp *s);                            // s->pad_feat: [nMol][feature width of cfg]
+gf_status copy_feature_blocks(gf_smp *s, float *user, float *padded, bool to_user);
+gf_status dup_level(gf_smp *s, int l);    // no-ops unless gf_smp::dup_channels
+gf_status fold_level(gf_smp *s, int l);
+gf_status extra_products_forward(gf_smp *s, int l);   // no-ops unless gf_smp::n_extra
+gf_status extra_products_wgrad(gf_smp *s, int l);
+gf_status extra_products_backward(gf_smp *s, int l);
 }
 #endif

@@ -382,7 +382,7 @@ __global__ void build_fwd_goff(const int *__restrict__ node_s, const long long *
 
 }  // namespace
 
-// gather_offsets = false: goff is in place already (build_node_tables, smp.hip)
+// gather_offsets = false: goff is in place already (build_node_tables, smp_prepare.hip)
 gf_status smp_fwd_fused_build_tables(gf_smp *s, int l, hipStream_t stream, bool gather_offsets) {
     gf_smp::DevLevel &d = s->lv[l];
     const gfsmp::LevelLayout &h = s->lay.level[l];

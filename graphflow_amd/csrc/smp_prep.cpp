@@ -497,7 +497,7 @@ void build_batch(const Config &cfg, int nMol, const int *nVertices, const int *a
         tvec<int64_t> &cons_pair = lv.cons_pair;
         cons_pair.assign((size_t)lv.pairs, 0);
         for (int64_t e = 0; e < lv.pairs; ++e) cons_pair[(size_t)cursor[(size_t)pair_src_node[(size_t)e]]++] = e;
-        if (out->device_tables) {   // (the device derives the per-consumer entries from cons_pair: smp.hip, build_consumer_entries)
+        if (out->device_tables) {   // (the device derives the per-consumer entries from cons_pair: smp_prepare.hip, build_consumer_entries)
             lv.cons_slab.clear();
             lv.cons_s.clear();
             lv.cons_row.clear();

@@ -85,7 +85,7 @@ struct LevelLayout {
     tvec<int> node_s, node_mol, node_vertex;
     tvec<int64_t> node_row, node_p, node_pair;
     // The rows-sized tables (adj, pi, inv) and what is summed from adj (rsum, rowscale) are built on the DEVICE when
-    // BatchLayout::device_tables is set (smp.hip: build_level_rows / build_level_inv, from `field`, the pair tables and the
+    // BatchLayout::device_tables is set (smp_prepare.hip: build_level_rows / build_level_inv, from `field`, the pair tables and the
     // molecules' adjacency matrices); the host then leaves them empty.
     tvec<int> node_panel;  // [nNodes] first row panel of the node (combine-forward on row panels, smp_level_c64_fwd.hip)
     int npanels = 0;       //   a node of size s has ceil(s / gpp) panels of gpp = max(1, min(8, 32 / s)) row groups

@@ -1,0 +1,819 @@
+// smp_prepare.hip -- a batch of molecules onto the device: the handle's pool of device blocks, the page-locked allocator of the host tables, the
+// kernels that build the rows-sized level tables, gf_smp_prepare as a sequence of steps.  The host side of the preparation is smp_prep.cpp.
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+
+#include "smp_internal.h"
+
+namespace gf {
+// page-locked host memory for the per-batch tables (smp_prep.h: table_alloc): their uploads then run on the DMA engines beside
+// the step that is executing, instead of blit kernels queued behind its compute kernels.  16-byte header: how it was obtained.
+void *pinned_table_alloc(size_t bytes) {
+    void *p = nullptr;
+    const size_t total = bytes + 16;
+    unsigned kind = 1;
+    // (portable: the preparation's worker threads never call hipSetDevice, and a table pinned against device 0 only would be
+    //  pageable memory to the uploads of every other rank's device)
+    if (hipHostMalloc(&p, total, hipHostMallocPortable) != hipSuccess) p = nullptr;
+    if (!p) {
+        (void)hipGetLastError();
+        p = std::malloc(total);
+        kind = 0;
+        if (!p) return nullptr;
+    }
+    *static_cast<unsigned *>(p) = kind;
+    return static_cast<char *>(p) + 16;
+}
+void pinned_table_free(void *q) {
+    if (!q) return;
+    void *p = static_cast<char *>(q) - 16;
+    if (*static_cast<unsigned *>(p) == 1)
+        (void)hipHostFree(p);
+    else
+        std::free(p);
+}
+
+gf_status upload_bytes(gf_smp *s, void **dst, const void *src, size_t elem, size_t count) {
+    *dst = nullptr;
+    const size_t bytes = elem * (count ? count : 1);
+    // best fit among the idle blocks of the pool (no block more than twice the request: keeps big blocks for big buffers)
+    int best = -1;
+    for (size_t i = 0; i < s->pool.size(); ++i) {
+        const gf_smp::Block &b = s->pool[i];
+        if (!b.used && b.bytes >= bytes && b.bytes <= 2 * bytes + 4096 && (best < 0 || b.bytes < s->pool[best].bytes)) best = (int)i;
+    }
+    void *p = nullptr;
+    if (best >= 0) {
+        s->pool[best].used = true;
+        s->pool[best].idle = 0;
+        p = s->pool[best].p;
+    } else {
+        const size_t cap = bytes + bytes / 8 + 256;  // slack: the next batch is about, not exactly, this size
+        hipError_t e = hipMalloc(&p, cap);
+        if (e != hipSuccess) return fail(s->ctx, GF_ERR_NOMEM, "smp: hipMalloc(%zu) failed: %s", cap, hipGetErrorString(e));
+        gf_smp::Block b = {p, cap, true, 0};
+        s->pool.push_back(b);
+    }
+    if (src && count)
+        GF_HIP_TRY(s->ctx, hipMemcpyAsync(p, src, elem * count, hipMemcpyHostToDevice, s->upload ? s->upload : s->ctx->stream));
+    else if (gf::poison_buffers()) {  // GF_POISON=1 (debug): a buffer handed out without contents is filled with NaN bit patterns, so a
+        hipStream_t st = s->upload ? s->upload : s->ctx->stream;                    // read-before-write shows
+        GF_HIP_TRY(s->ctx, hipMemsetAsync(p, 0xff, bytes, st));
+        // (finished before anything else is launched: buffers are also taken from the pool in the middle of a pass -- the promoted
+        //  stack of the op-by-op levels -- where the upload stream is not ordered against the pass)
+        GF_HIP_TRY(s->ctx, hipStreamSynchronize(st));
+    }
+    *dst = p;
+    return GF_OK;
+}
+gf_status ensure_P(gf_smp *s) { return s->P ? GF_OK : upload(s, &s->P, nullptr, s->P_count); }
+
+// End of a batch: its buffers go back to the pool (blocks idle for three batches in a row are returned to the device).
+// the handle's buffers were last touched by the launches before this mark
+void mark_used(gf_smp *s) {
+    if (s->ev_last && hipEventRecord(s->ev_last, s->ctx->stream) == hipSuccess) s->used = true;
+}
+
+void release(gf_smp *s) {
+    if (s->ctx) {
+        // wait for this handle's own work only: another handle of the context may be in the middle of its step
+        if (s->ev_last) {
+            if (s->used) (void)hipEventSynchronize(s->ev_last);
+        } else {
+            (void)hipStreamSynchronize(s->ctx->stream);
+        }
+        s->used = false;
+    }
+    std::vector<gf_smp::Block> keep;
+    for (gf_smp::Block &b : s->pool) {
+        if (!b.used && ++b.idle >= 3) {
+            (void)hipFree(b.p);
+            continue;
+        }
+        b.used = false;
+        keep.push_back(b);
+    }
+    s->pool.swap(keep);
+    s->lv.clear();
+    s->own_t = s->own_y = s->own_loss = s->own_feat = nullptr;
+    s->prepared = s->forwarded = false;
+}
+
+void release_pool(gf_smp *s) {
+    for (gf_smp::Block &b : s->pool) (void)hipFree(b.p);
+    s->pool.clear();
+}
+
+namespace {
+// rowscale[row] = (tot, tr) of the row's node (the per-row factors of the level's block products), from the per-node pairs
+__global__ void expand_rowscale(float2 *__restrict__ rowscale, const float2 *__restrict__ node_scale, const int *__restrict__ node_s,
+                                const long long *__restrict__ node_row) {
+    const int n = blockIdx.x, s = node_s[n];
+    const long long r0 = node_row[n];
+    const float2 v = node_scale[n];
+    for (int i = threadIdx.x; i < s * s; i += blockDim.x) rowscale[r0 + i] = v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Level tables on the device (round 3; BatchLayout::device_tables).  What gfsmp::build_batch writes per node in its phase B --
+// the reduced adjacency (SMP_omega.h:556-581: 1 on the diagonal and adj[v1][v2] elsewhere, or the Coulomb entries), its gated row
+// sums and (tot, tr), the selection maps pi (:461-474) -- and per consumer entry in phase D (the inverse maps) are rows-sized:
+// 2.2 of the 6.2 ms of host graph preparation on 32 threads (8 of 14 ms on 8) and 17 MB of the upload per 1024 molecules.  The
+// kernels below build them from the receptive fields (sum-s ints per level), the pair tables and the molecules' adjacency
+// matrices, with the host's summation orders (bit-identical tables: tests/test_smp_gpu.py::test_device_level_tables...).
+// Workgroup per node; wave w builds the maps of the neighbours a = w, w + 4, ...
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void build_level_rows(const int *__restrict__ node_s, const int *__restrict__ node_mol,
+                                                        const long long *__restrict__ node_row, const long long *__restrict__ node_pair,
+                                                        const int *__restrict__ field, const int *__restrict__ prev_field,
+                                                        const long long *__restrict__ pair_src_pair, const int *__restrict__ pair_src_s,
+                                                        const int *__restrict__ mol_nv, const long long *__restrict__ mol_adj_off,
+                                                        const int *__restrict__ mol_adj, const double *__restrict__ mol_coul,
+                                                        float *__restrict__ adj, float *__restrict__ rsum, float *__restrict__ node_scale,
+                                                        short *__restrict__ pi, int *__restrict__ node_present, int vmax) {
+    extern __shared__ int lr_smem[];
+    const int n = blockIdx.x, s = node_s[n], m = node_mol[n], V = mol_nv[m];
+    const long long r0 = node_row[n], p0 = node_pair[n];
+    int *f = lr_smem;                                             // [s] the node's field
+    float *rs = reinterpret_cast<float *>(lr_smem + s);           // [s] gated row sums
+    float *dg = rs + s;                                           // [s] gated diagonal
+    short *pos = reinterpret_cast<short *>(dg + s);               // [4][vmax] position inside the source's field, -1 outside
+    const int *madj = mol_adj + mol_adj_off[m];
+    const double *mc = mol_coul ? mol_coul + mol_adj_off[m] : nullptr;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    for (int i = tid; i < s; i += blockDim.x) f[i] = field[p0 + i];
+    for (int i = tid; i < 4 * vmax; i += blockDim.x) pos[i] = -1;
+    __syncthreads();
+    auto entry = [&](int i, int j) {
+        return mc ? (float)mc[(size_t)f[i] * V + f[j]] : ((f[i] == f[j]) ? 1.f : (float)madj[(size_t)f[i] * V + f[j]]);
+    };
+    for (int idx = tid; idx < s * s; idx += blockDim.x) adj[r0 + idx] = entry(idx / s, idx % s);
+    for (int i = tid; i < s; i += blockDim.x) {  // (entries with A <= 0 are skipped: RisiContraction_18.h:90; j in order, as the host sums)
+        float acc = 0.f;
+        for (int j = 0; j < s; ++j) {
+            const float av = entry(i, j);
+            if (av > 0.f) acc += av;
+        }
+        rs[i] = acc;
+        rsum[p0 + i] = acc;
+        const float d = entry(i, i);
+        dg[i] = d > 0.f ? d : 0.f;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float tot = 0.f, tr = 0.f;
+        for (int i = 0; i < s; ++i) {
+            tot += rs[i];
+            tr += dg[i];
+        }
+        node_scale[2 * (size_t)n] = tot;
+        node_scale[2 * (size_t)n + 1] = tr;
+    }
+    short *mypos = pos + wave * vmax;
+    unsigned cnt = 0;
+    for (int a0 = 0; a0 < s; a0 += 4) {
+        const int a = a0 + wave;
+        const int *wf = nullptr;
+        int sw = 0;
+        if (a < s) {
+            wf = prev_field + pair_src_pair[p0 + a];
+            sw = pair_src_s[p0 + a];
+            for (int k = lane; k < sw; k += 64) mypos[wf[k]] = (short)k;
+        }
+        __syncthreads();
+        if (a < s)
+            for (int p = lane; p < s; p += 64) {
+                const short k = mypos[f[p]];
+                pi[r0 + (long long)a * s + p] = k;
+                cnt += k >= 0;
+            }
+        __syncthreads();
+        if (a < s)
+            for (int k = lane; k < sw; k += 64) mypos[wf[k]] = -1;
+    }
+    // rows with data of the node (level_table_stats sums them: one hot word for 17,000 workgroups' atomics cost 1 ms per level)
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    __syncthreads();
+    int *wcnt = reinterpret_cast<int *>(pos);
+    if (lane == 0) wcnt[wave] = (int)cnt;
+    __syncthreads();
+    if (tid == 0) node_present[n] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+}
+
+// Round 4: ONE workgroup per node builds every rows-sized table of the node (receptive fields of at most 32 vertices): what
+// build_level_rows, build_level_inv, expand_rowscale, build_trow and build_fwd_goff built in five launches that each re-read the
+// selection maps -- 1.0 of the 1.45 ms of table-building kernels per prepared 1024-molecule batch, which run beside the step of
+// another handle in the loop with a new batch every step.  The source fields of the node's neighbours are staged in LDS once and the
+// map of a (neighbour, position) pair is a scan of at most 32 entries by its own thread (no per-neighbour barriers); the maps stay
+// in LDS for the presence masks, the transposed-row table and the gather offsets of combine-forward.
+// cons_of_pair[e] = index of pair e in its source's consumer list (the inverse of cons_pair: invert_cons_pair).
+// The per-consumer entries of a level's consumer lists from the list itself (round 4, second session; the host wrote them in a pass of
+// its own -- phase D of gfsmp::build_batch, 2 ms of a 1024-molecule prepare -- and uploaded 24 bytes per pair): consumer c is the pair
+// e = cons_pair[c] = (node n, index a); its slab of the promoted tensor, its size, its first row and a.
+__global__ void build_consumer_entries(const long long *__restrict__ cons_pair, const int *__restrict__ pair_node, const int *__restrict__ node_s,
+                                       const long long *__restrict__ node_pair, const long long *__restrict__ node_row,
+                                       const long long *__restrict__ node_p, long long *__restrict__ cons_slab, int *__restrict__ cons_s,
+                                       long long *__restrict__ cons_row, int *__restrict__ cons_a, long long pairs) {
+    const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= pairs) return;
+    const long long e = cons_pair[c];
+    const int n = pair_node[e], sz = node_s[n], a = (int)(e - node_pair[n]);
+    cons_slab[c] = node_p[n] + (long long)a * sz * sz;
+    cons_s[c] = sz;
+    cons_row[c] = node_row[n];
+    cons_a[c] = a;
+}
+__global__ void invert_cons_pair(const long long *__restrict__ cons_pair, int *__restrict__ cons_of_pair, long long pairs) {
+    const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < pairs) cons_of_pair[cons_pair[c]] = (int)c;
+}
+__global__ __launch_bounds__(128) void build_node_tables(
+    const int *__restrict__ node_s, const int *__restrict__ node_mol, const long long *__restrict__ node_row,
+    const long long *__restrict__ node_pair, const int *__restrict__ field, const int *__restrict__ prev_field,
+    const long long *__restrict__ pair_src_pair, const int *__restrict__ pair_src_s, const int *__restrict__ mol_nv,
+    const long long *__restrict__ mol_adj_off, const int *__restrict__ mol_adj, const double *__restrict__ mol_coul,
+    float *__restrict__ adj, float *__restrict__ rsum, float *__restrict__ node_scale, short *__restrict__ pi,
+    int *__restrict__ node_present, int swp,                                     // swp: largest field of the level below
+    const int *__restrict__ cons_of_pair, const long long *__restrict__ cons_inv_off, short *__restrict__ inv,   // or null (no consumers' maps)
+    float2 *__restrict__ rowscale,                                               // or null
+    int *__restrict__ trow, unsigned char *__restrict__ rowflag, int *__restrict__ trowf,   // trow null: none of the three
+    int2 *__restrict__ goff) {                                                   // or null
+    extern __shared__ int nt_smem[];
+    const int n = blockIdx.x, s = node_s[n], m = node_mol[n], V = mol_nv[m];
+    const long long r0 = node_row[n], p0 = node_pair[n];
+    int *f = nt_smem;                                             // [s] the node's field
+    float *rs = reinterpret_cast<float *>(f + s);                 // [s] gated row sums
+    float *dg = rs + s;                                           // [s] gated diagonal
+    unsigned *mask = reinterpret_cast<unsigned *>(dg + s);        // [s] bit p: neighbour a's source holds the vertex of position p
+    int *sf = reinterpret_cast<int *>(mask + s);                  // [s][swp] the neighbours' source fields, -1 padded
+    short *spi = reinterpret_cast<short *>(sf + s * swp);         // [s][s] the maps
+    const int *madj = mol_adj + mol_adj_off[m];
+    const double *mc = mol_coul ? mol_coul + mol_adj_off[m] : nullptr;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    for (int i = tid; i < s; i += nt) f[i] = field[p0 + i];
+    for (int i = tid; i < s * swp; i += nt) {
+        const int a = i / swp, k = i - a * swp;
+        sf[i] = k < pair_src_s[p0 + a] ? prev_field[pair_src_pair[p0 + a] + k] : -1;
+    }
+    __syncthreads();
+    auto entry = [&](int i, int j) {
+        return mc ? (float)mc[(size_t)f[i] * V + f[j]] : ((f[i] == f[j]) ? 1.f : (float)madj[(size_t)f[i] * V + f[j]]);
+    };
+    for (int idx = tid; idx < s * s; idx += nt) adj[r0 + idx] = entry(idx / s, idx % s);
+    for (int i = tid; i < s; i += nt) {  // (entries with A <= 0 are skipped: RisiContraction_18.h:90; j in order, as the host sums)
+        float acc = 0.f;
+        for (int j = 0; j < s; ++j) {
+            const float av = entry(i, j);
+            if (av > 0.f) acc += av;
+        }
+        rs[i] = acc;
+        rsum[p0 + i] = acc;
+        const float d = entry(i, i);
+        dg[i] = d > 0.f ? d : 0.f;
+    }
+    // the maps: pi[a][p] = position of the vertex of position p inside the field of neighbour a's source, -1 outside (:461-474)
+    for (int i = tid; i < s * s; i += nt) {
+        const int a = i / s, p = i - a * s, v = f[p];
+        const int *row = sf + a * swp;
+        int k = -1;
+        for (int kk = 0; kk < swp; ++kk) k = row[kk] == v ? kk : k;   // (a field holds a vertex once)
+        pi[r0 + i] = (short)k;
+        spi[i] = (short)k;
+        if (inv && k >= 0) inv[cons_inv_off[cons_of_pair[p0 + a]] + k] = (short)p;
+    }
+    __syncthreads();
+    float tot = 0.f, tr = 0.f;   // (every thread forms them, in the host's order: the row factors below need them)
+    for (int i = 0; i < s; ++i) {
+        tot += rs[i];
+        tr += dg[i];
+    }
+    if (tid == 0) {
+        node_scale[2 * (size_t)n] = tot;
+        node_scale[2 * (size_t)n + 1] = tr;
+    }
+    for (int a = tid; a < s; a += nt) {
+        unsigned mk = 0u;
+        for (int p = 0; p < s; ++p) mk |= (spi[a * s + p] >= 0 ? 1u : 0u) << p;
+        mask[a] = mk;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int cnt = 0;
+        for (int a = 0; a < s; ++a) cnt += __popc(mask[a]);
+        node_present[n] = cnt;
+    }
+    for (int i = tid; i < s * s; i += nt) {
+        const int x = i / s, e = i - x * s, it = e * s + x;
+        if (rowscale) rowscale[r0 + i] = make_float2(tot, tr);
+        const short pxe = spi[i], pex = spi[it];
+        if (goff) goff[r0 + i] = make_int2(pxe >= 0 ? (int)(pair_src_pair[p0 + x] + pxe) : -1, pex >= 0 ? (int)(pair_src_pair[p0 + e] + pex) : -1);
+        if (trow) {
+            const long long t = r0 + it;
+            trow[r0 + i] = (int)t;
+            const bool own = pxe >= 0, trp = pex >= 0;
+            // row (b, c) = (x, e) of the S_bc / T10 blocks has data when SOME neighbour's source holds both b and c
+            unsigned both = 0u;
+            for (int a = 0; a < s; ++a) both |= (mask[a] >> x) & (mask[a] >> e);
+            const bool bc = (both & 1u) != 0;
+            rowflag[r0 + i] = (own ? 1 : 0) | (bc ? 2 : 0);
+            if (trowf)
+                trowf[r0 + i] = (t < (1ll << 29)) ? (int)((unsigned)t | (own ? 0x80000000u : 0u) | (trp ? 0x40000000u : 0u) | (bc ? 0x20000000u : 0u)) : -1;
+        }
+    }
+}
+
+// stats = {max |tot| (float bits), max |tr|, rows with data (two words)} of a level; one workgroup, fixed order
+__global__ __launch_bounds__(1024) void level_table_stats(const float *__restrict__ node_scale, const int *__restrict__ node_present,
+                                                          int nodes, unsigned *__restrict__ stats) {
+    __shared__ float mt[1024], mr[1024];
+    __shared__ unsigned long long sc[1024];
+    float a = 0.f, b = 0.f;
+    unsigned long long c = 0;
+    for (int n = threadIdx.x; n < nodes; n += 1024) {
+        a = fmaxf(a, fabsf(node_scale[2 * (size_t)n]));
+        b = fmaxf(b, fabsf(node_scale[2 * (size_t)n + 1]));
+        c += (unsigned long long)node_present[n];
+    }
+    mt[threadIdx.x] = a, mr[threadIdx.x] = b, sc[threadIdx.x] = c;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            mt[threadIdx.x] = fmaxf(mt[threadIdx.x], mt[threadIdx.x + o]);
+            mr[threadIdx.x] = fmaxf(mr[threadIdx.x], mr[threadIdx.x + o]);
+            sc[threadIdx.x] += sc[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        stats[0] = __float_as_uint(mt[0]);
+        stats[1] = __float_as_uint(mr[0]);
+        stats[2] = (unsigned)(sc[0] & 0xffffffffull);
+        stats[3] = (unsigned)(sc[0] >> 32);
+    }
+}
+
+// inv[cons_inv_off[c] + k] = p  where source position k is the image of the consumer's position p (inv prefilled with -1)
+__global__ __launch_bounds__(256) void build_level_inv(const long long *__restrict__ cons_pair, const int *__restrict__ pair_node,
+                                                       const int *__restrict__ node_s, const long long *__restrict__ node_row,
+                                                       const long long *__restrict__ node_pair, const long long *__restrict__ cons_inv_off,
+                                                       const short *__restrict__ pi, short *__restrict__ inv, long long pairs) {
+    const long long c = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= pairs) return;
+    const int lane = threadIdx.x & 63;
+    const long long e = cons_pair[c];
+    const int n = pair_node[e], s = node_s[n], a = (int)(e - node_pair[n]);
+    const short *row = pi + node_row[n] + (long long)a * s;
+    short *iv = inv + cons_inv_off[c];
+    for (int p = lane; p < s; p += 64) {
+        const short k = row[p];
+        if (k >= 0) iv[k] = (short)p;
+    }
+}
+
+// trow[row of (x, e)] = row of (e, x) inside the same node (compact O layout of the fused C = 64 level, smp_level_c64.hip)
+__global__ void build_trow(int *__restrict__ trow, const int *__restrict__ node_s, const long long *__restrict__ node_row,
+                           const short *__restrict__ pi, unsigned char *__restrict__ rowflag, int *__restrict__ trowf) {
+    const int n = blockIdx.x, s = node_s[n];
+    const long long r0 = node_row[n];
+    for (int i = threadIdx.x; i < s * s; i += blockDim.x) {
+        const int it = (i % s) * s + i / s;
+        const long long t = r0 + it;
+        trow[r0 + i] = (int)t;
+        const bool own = pi[r0 + i] >= 0, tr = pi[r0 + it] >= 0;
+        // row (b, c) of the S_bc / T10 blocks (sums over a of P[a,b,c]) has data when SOME source a holds both b and c: 92 % of the
+        // rows at level 3 of QM9-size molecules, 71 % at level 2, 29 % at level 1 (only b == c: a level-0 field is one vertex)
+        bool bc = false;
+        {
+            const int b = i / s, c = i % s;
+            for (int a = 0; a < s && !bc; ++a) bc = pi[r0 + a * s + b] >= 0 && pi[r0 + a * s + c] >= 0;
+        }
+        rowflag[r0 + i] = (own ? 1 : 0) | (bc ? 2 : 0);  // bit 0: the S_ab / T6 blocks of the row are written by tables-forward
+                                                          // (DevLevel::t_zeros), bit 1: its S_bc / T10 blocks are
+        if (trowf)
+            trowf[r0 + i] = (t < (1ll << 29)) ? (int)((unsigned)t | (own ? 0x80000000u : 0u) | (tr ? 0x40000000u : 0u) | (bc ? 0x20000000u : 0u)) : -1;
+    }
+}
+
+// ---- gf_smp_prepare: the steps ------------------------------------------------------------------------------------
+// The ONE way a batch's buffers are taken from the pool: the first failure is kept and every later request does nothing, so a step asks
+// for its buffers in order and checks `st` at its end (and before it launches anything on them).  The ORDER of the requests is behaviour:
+// upload_bytes picks the best-fitting idle block, so it decides which block backs which buffer and how far the pool grows.
+struct Taker {
+    gf_smp *s;
+    gf_status st = GF_OK;
+    template <typename T>
+    void alloc(T **p, size_t count) {   // room for `count` elements, contents undefined
+        if (st == GF_OK) st = upload(s, p, nullptr, count);
+    }
+    template <typename T, typename V>
+    void put(T **p, const V &v) {   // a host table, copied on the handle's upload stream
+        if (st == GF_OK) st = upload(s, p, v.empty() ? nullptr : &v[0], v.size());
+    }
+    template <typename T, typename V>
+    void table(T **p, const V &v, size_t count) {   // a rows-sized table: the host's, or room for the one the device builds
+        s->lay.device_tables ? alloc(p, count) : put(p, v);
+    }
+};
+using Level = const gfsmp::LevelLayout;
+using DevLevel = gf_smp::DevLevel;
+
+// SMP_2D_ver6 / ver7 on the 18-slice level: the identities behind the embedding need a symmetric, non-negative adjacency (row sums =
+// column sums), for `_50` the unit diagonal of a reduced adjacency (cases 25, 41, 42, 45: no Coulomb mode), and in Coulomb mode
+// positive entries (RisiContraction_18 drops A <= 0 -- its `if (adj_value > 0)` -- and RisiContraction_10 does not).  A batch that
+// does not qualify runs on the op-by-op `_10` / `_50` levels, which take anything the reference takes; the plan is per batch.
+gf_status choose_plan(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *coulomb) {
+    if (!s->dup_channels && !s->embed_auto_off) return GF_OK;
+    const bool is50 = s->ucfg.nContractions == 50;
+    bool embeddable = !(is50 && coulomb);
+    const int *a = adj;
+    const double *cm = coulomb;
+    for (int m = 0; m < nMol && embeddable; ++m) {
+        const int V = nVertices[m];
+        if (cm)
+            for (int i = 0; i < V * V && embeddable; ++i) embeddable = cm[i] > 0.0;
+        for (int i = 0; i < V && embeddable; ++i)
+            for (int j = i + 1; j < V; ++j)
+                if (a[i * V + j] < 0 || a[i * V + j] != a[j * V + i] || (cm && cm[i * V + j] != cm[j * V + i])) {
+                    embeddable = false;
+                    break;
+                }
+        a += (size_t)V * V;
+        if (cm) cm += (size_t)V * V;
+    }
+    return embeddable != (s->dup_channels != 0) ? smp_switch_plan(s, embeddable) : GF_OK;
+}
+
+// the batch's uploads and table-building kernels run at the LOWEST stream priority: in the loop with a new batch every step they
+// share the device with the running step of another handle, which is what the loop waits for
+void ensure_upload_stream(gf_smp *s) {
+    if (s->upload) return;
+    int least = 0, greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
+        if (hipStreamCreateWithPriority(&s->upload, hipStreamNonBlocking, least) != hipSuccess) s->upload = nullptr;
+    } else if (hipStreamCreateWithFlags(&s->upload, hipStreamNonBlocking) != hipSuccess) {
+        s->upload = nullptr;
+    }
+    if (s->upload && hipEventCreateWithFlags(&s->ev_last, hipEventDisableTiming) != hipSuccess) {
+        (void)hipStreamDestroy(s->upload);
+        s->upload = nullptr;
+        s->ev_last = nullptr;
+    }
+}
+hipStream_t upload_stream(const gf_smp *s) { return s->upload ? s->upload : s->ctx->stream; }
+
+// rows-sized level tables on the device (GF_PREP_DEVICE_TABLES=0: on the host, as rounds 1-2 built them; the parity tests hold
+// the two against each other bit for bit)
+void choose_table_builder(gf_smp *s, int nMol, const int *nVertices) {
+    s->lay.device_tables = !env_is("GF_PREP_DEVICE_TABLES", '0');
+    // build_level_rows keeps three ints per field position and four shorts per vertex of its molecule in LDS: beyond the
+    // default 32 KiB window (a molecule of ~4,000 vertices) the tables are built on the host, as rounds 1-2 built all of them
+    // (decided BEFORE build_batch lays the batch out for one builder or the other; round-3 advice)
+    int vmax = 0;
+    for (int m = 0; m < nMol; ++m) vmax = nVertices[m] > vmax ? nVertices[m] : vmax;
+    const int smax = s->cfg.max_receptive_field > 0 && s->cfg.max_receptive_field < vmax ? s->cfg.max_receptive_field : vmax;
+    if (sizeof(int) * (size_t)smax * 3 + sizeof(short) * 4 * (size_t)vmax + 16 > 32 * 1024) s->lay.device_tables = false;
+}
+
+// every level: node bookkeeping, the activations and their gradient; a tower reads every level out
+void alloc_level_state(Taker &t, Level &h, DevLevel &d, int l) {
+    const gfsmp::Config &cfg = t.s->cfg;
+    const int Cl = cfg.level_channels(l);
+    t.put(&d.node_s, h.node_s);
+    t.put(&d.node_center, h.node_center);
+    t.put(&d.mol_order, h.mol_order);
+    t.put(&d.gather_items, h.gather_items);
+    if (t.s->lay.device_tables) {
+        t.put(&d.field, h.field);
+        if (!cfg.physics) t.put(&d.node_mol, h.node_mol);   // (the towers upload it below)
+    }
+    if (l >= 1 && cfg.square()) t.alloc(&d.tf_recs, (size_t)h.nNodes * 2);
+    t.put(&d.node_row, h.node_row);
+    t.put(&d.node_pair, h.node_pair);
+    t.alloc(&d.f, (size_t)h.rows * Cl);
+    t.alloc(&d.df, (size_t)h.rows * Cl);
+    if (!cfg.physics) return;
+    t.alloc(&d.sh, (size_t)h.nNodes * Cl);   // per-node sums, their activation and gradient, the vertex -> node map
+    t.alloc(&d.vf, (size_t)h.nNodes * Cl);
+    t.alloc(&d.dshl, (size_t)h.nNodes * Cl);
+    t.put(&d.node_of_vertex, t.s->lay.node_of_vertex[l]);
+    t.put(&d.node_mol, h.node_mol);
+    t.alloc(&d.keep_mask, (size_t)h.nNodes);
+}
+
+// levels >= 1, every kind: the promotion's pair tables, the consumer lists of the reverse gather, the selection maps.  The rows-sized
+// ones are the host's or are built on the device (build_consumer_entries here, the node tables in build_device_tables).
+gf_status alloc_level_topology(Taker &t, Level &h, DevLevel &d, int l) {
+    gf_smp *s = t.s;
+    const bool dev = s->lay.device_tables;
+    t.put(&d.node_p, h.node_p);
+    d.max_tot = d.max_tr = 0.f;
+    t.table(&d.adj, h.adj, (size_t)h.rows);
+    t.table(&d.rsum, h.rsum, (size_t)h.pairs);
+    t.table(&d.node_scale, h.rowscale, (size_t)h.nNodes * 2);
+    if (dev) t.alloc(&d.node_present, (size_t)h.nNodes);
+    for (size_t i = 0; !dev && i + 1 < h.rowscale.size(); i += 2) {
+        d.max_tot = std::max(d.max_tot, std::fabs(h.rowscale[i]));
+        d.max_tr = std::max(d.max_tr, std::fabs(h.rowscale[i + 1]));
+    }
+    t.alloc(&d.rowscale, (size_t)h.rows * 2);
+    t.put(&d.quad_node, h.quad_node);
+    t.put(&d.quad_b0, h.quad_b0);
+    t.put(&d.quad_order, h.quad_order);
+    t.put(&d.pair_node, h.pair_node);
+    t.put(&d.pair_src_s, h.pair_src_s);
+    t.table(&d.cons_s, h.cons_s, (size_t)h.pairs);
+    t.table(&d.cons_a, h.cons_a, (size_t)h.pairs);
+    t.put(&d.pair_src_pair, h.pair_src_pair);
+    t.table(&d.cons_row, h.cons_row, (size_t)h.pairs);
+    t.put(&d.cons_pair, h.cons_pair);
+    if (s->cfg.nContractions != 4)   // the compact diagonal path of the 18-slice level (SMP_gamma has none of its scratch)
+        for (float **p : {&d.Fdc, &d.Gc, &d.dGc, &d.dFdc}) t.alloc(p, (size_t)s->lay.level[l - 1].pairs * 2 * s->cfg.nChanels);
+    t.put(&d.pair_src_row, h.pair_src_row);
+    t.put(&d.cons_ptr, h.cons_ptr);
+    t.table(&d.cons_slab, h.cons_slab, (size_t)h.pairs);
+    if (t.st != GF_OK) return t.st;
+    if (dev && h.pairs) {
+        hipLaunchKernelGGL(build_consumer_entries, dim3((unsigned)((h.pairs + 255) / 256)), dim3(256), 0, upload_stream(s), d.cons_pair, d.pair_node,
+                           d.node_s, d.node_pair, d.node_row, d.node_p, d.cons_slab, d.cons_s, d.cons_row, d.cons_a, (long long)h.pairs);
+        GF_LAUNCH_CHECK(s->ctx, "build_consumer_entries");
+    }
+    t.put(&d.cons_inv_off, h.cons_inv_off);
+    t.table(&d.pi, h.pi, (size_t)h.rows);
+    t.table(&d.inv, h.inv, (size_t)h.inv_count);
+    return t.st;
+}
+
+// fused 18-slice levels with the folded backward gather: its header and record tables (smp_fused.hip: build_gather_records)
+void alloc_level_gather(Taker &t, Level &h, DevLevel &d) {
+    const gfsmp::Config &cfg = t.s->cfg;
+    if (!(cfg.square() && cfg.nContractions == 18 && cfg.nChanels % 4 == 0 && t.s->bwd_gather)) return;
+    t.alloc(&d.cons_hdr, (size_t)h.pairs * 2);
+    t.alloc(&d.cons_qrec, (size_t)h.qrec_total);
+    t.put(&d.cons_qbase, h.cons_qbase);
+}
+
+// the row-panel kernel family (C = 64; 32: the split row-panel products, round 4; 16: round 5): transposed-row tables and weight images,
+// and for an 18-slice level the row panels of the fused forward (smp_level_c64_fwd.hip) with their partial sums and maxima
+void alloc_level_panels(Taker &t, Level &h, DevLevel &d, int l) {
+    const gfsmp::Config &cfg = t.s->cfg;
+    const int L = cfg.nLevels, C = cfg.nChanels;
+    if (!(cfg.square() && smp_panel_channels(C) && h.rows < 0x7fffffffll)) return;
+    t.alloc(&d.trow, (size_t)h.rows);
+    t.alloc(&d.trowf, (size_t)h.rows);
+    unsigned char *img = nullptr;
+    t.alloc(&img, smp_split_image_bytes());
+    d.wimg = img;
+    t.alloc(&d.rowflag, (size_t)h.rows);
+    if (!(cfg.nContractions == 18 && h.rows * 256 < 0x3fffffffll && !h.buckets.empty() && h.buckets.back().s <= kFusedMaxField)) return;
+    // a node of size s has ceil(s / max(1, 32 / s)) panels
+    const int np = h.npanels;   // (page-locked table of the layout: no wait for the copy)
+    const size_t np1 = (size_t)(np > 0 ? np : 1);   // (a level whose nodes are ALL above 32 positions has no panel: the tables exist all the same)
+    d.fwd_npanels = np;
+    t.put(&d.node_panel, h.node_panel);
+    t.alloc(&d.fwd_pan, np1);
+    if (l == L || cfg.physics) t.alloc(&d.psum, np1 * C);   // (the top level -- every level of a tower: the readout's partial sums)
+    if (l < L) t.alloc(&d.pmax, np1 * C);   // (below the top level: the per-panel channel maxima the level above scales its weight-gradient operands with)
+    t.alloc(&d.dzmax, (h.quad_node.size() + np1) * 64);   // (panels, then the workgroups of the nodes above 32 positions)
+    t.alloc(&d.fwd_pan_node, np1);
+    t.alloc(&d.fwd_goff, (size_t)h.rows);
+}
+
+// the contraction's output and what the level's kind works in beside it
+void alloc_level_scratch(Taker &t, Level &h, DevLevel &d, int l) {
+    const gfsmp::Config &cfg = t.s->cfg;
+    const size_t C = cfg.nChanels, Cl = cfg.level_channels(l), Cp = cfg.level_channels(l - 1), pairs = h.pairs, nodes = h.nNodes;
+    if (cfg.nContractions == 4) {
+        // a `_4` level: T [rows][4 Cp] op by op, G / dG [rows of level l - 1][4 Cc] on the gamma level (Cc <= Cp); then the gamma level's
+        // weight views [8 Cp Cc] and its weight-gradient image [4 Cp Cc] (Cp = Cc = C unless a tower)
+        t.alloc(&d.Q, (size_t)std::max<int64_t>(h.rows, t.s->lay.level[l - 1].rows) * 4 * Cp);
+        t.alloc(&d.Wst, 8 * Cp * Cl);
+        t.alloc(&d.dWst, 4 * Cp * Cl);
+        return;
+    }
+    t.alloc(&d.Q, (size_t)h.rows * std::max(18, cfg.nContractions) * Cp);
+    if (!cfg.square()) return;
+    // fused level (smp_fused.hip): small per-(node, x) / per-node tables and the stacked weights
+    const struct { float **p; size_t n; } bufs[] = {
+        {&d.Vt, pairs * 4 * C}, {&d.dVt, pairs * 4 * C}, {&d.St, nodes * 4 * C}, {&d.dSt, nodes * 4 * C}, {&d.scal, pairs * 4 * C},
+        {&d.Vout, pairs * C}, {&d.dVout, pairs * C}, {&d.Sout, nodes * C}, {&d.dSout, nodes * C}, {&d.dSpart, pairs * C},
+        {&d.dbpart, pairs * C}, {&d.Wst, 18 * C * C}, {&d.dWst, 18 * C * C}};
+    for (const auto &b : bufs) t.alloc(b.p, b.n);
+}
+
+// all the device buffers of level l; *maxp, *contract_ws: the promoted stack and the contraction workspace the level would need
+gf_status alloc_level(gf_smp *s, int l, long long *maxp, size_t *contract_ws) {
+    Taker t = {s};
+    Level &h = s->lay.level[l];
+    DevLevel &d = s->lv[l];
+    alloc_level_state(t, h, d, l);
+    if (l == 0) return t.st;
+    const gf_status st = alloc_level_topology(t, h, d, l);   // (its own status: a failed launch check is not in t.st)
+    if (st != GF_OK) return st;
+    alloc_level_gather(t, h, d);
+    alloc_level_panels(t, h, d, l);
+    alloc_level_scratch(t, h, d, l);
+    const int Cp = s->cfg.level_channels(l - 1);
+    *maxp = std::max<long long>(*maxp, h.ppos * Cp);
+    for (const gfsmp::Bucket &bk : h.buckets) *contract_ws = std::max(*contract_ws, gf_contract_workspace_bytes(s->cfg.nContractions, bk.s, Cp, bk.count));
+    *contract_ws = std::max(*contract_ws, r18_ragged_workspace_bytes((long long)h.rows, (long long)h.pairs, Cp));
+    return t.st;
+}
+
+// device-built tables: the molecules' adjacency matrices go up, then the rows-sized tables of every level (kernels above)
+gf_status build_device_tables(gf_smp *s, bool coulomb) {
+    gf_ctx *ctx = s->ctx;
+    const gfsmp::BatchLayout &B = s->lay;
+    const int L = s->cfg.nLevels, vmax = B.max_vertices;
+    hipStream_t up = upload_stream(s);
+    Taker t = {s};
+    t.put(&s->mol_nv, B.mol_nv);
+    t.put(&s->mol_adj, B.mol_adj);
+    t.put(&s->mol_adj_off, B.mol_adj_off);
+    s->mol_coul = nullptr;
+    if (coulomb) t.put(&s->mol_coul, B.mol_coul);
+    t.alloc(&s->tab_stats, (size_t)4 * (L + 1));  // per level: max |tot|, max |tr| (float bits), rows with data (64 bit)
+    if (t.st != GF_OK) return t.st;
+    GF_HIP_TRY(ctx, hipMemsetAsync(s->tab_stats, 0, sizeof(unsigned) * 4 * (L + 1), up));
+    for (int l = 1; l <= L; ++l) {
+        const gfsmp::LevelLayout &h = B.level[l];
+        gf_smp::DevLevel &d = s->lv[l];
+        const int smax = h.buckets.empty() ? 1 : h.buckets.back().s;
+        const size_t lds = sizeof(int) * (size_t)smax * 3 + sizeof(short) * 4 * (size_t)vmax + 16;
+        if (lds > 32 * 1024)   // (cannot happen: choose_table_builder chose the host builder for such a batch)
+            return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare: a receptive field of %d vertices in a molecule of %d", smax, vmax);
+        // (the split-operand weight gradients read the level's largest |tot|, |tr| from its statistics words: no read-back, the preparing
+        //  thread does not wait for its uploads)
+        unsigned *stats = s->tab_stats + 4 * l;
+        d.row_max = stats;
+        if (h.inv_count) GF_HIP_TRY(ctx, hipMemsetAsync(d.inv, 0xff, sizeof(short) * (size_t)h.inv_count, up));
+        // one kernel for all the node's tables where the fields fit its LDS image and its 32-bit presence masks (build_node_tables)
+        const int swp = B.level[l - 1].buckets.empty() ? 1 : B.level[l - 1].buckets.back().s;
+        const size_t lds_nt = sizeof(int) * (size_t)smax * (4 + (size_t)swp) + sizeof(short) * (size_t)smax * smax + 16;
+        d.node_tables_merged = smax <= 32 && lds_nt <= 32 * 1024 && h.pairs > 0 && h.pairs < 0x7fffffffll;
+        if (d.node_tables_merged) {
+            t.alloc(&d.cons_of_pair, (size_t)h.pairs);
+            if (t.st != GF_OK) return t.st;
+            hipLaunchKernelGGL(invert_cons_pair, dim3((unsigned)((h.pairs + 255) / 256)), dim3(256), 0, up, d.cons_pair, d.cons_of_pair,
+                               (long long)h.pairs);
+            GF_LAUNCH_CHECK(ctx, "invert_cons_pair");
+            hipLaunchKernelGGL(build_node_tables, dim3(h.nNodes), dim3(128), lds_nt, up, d.node_s, d.node_mol, d.node_row, d.node_pair,
+                               d.field, s->lv[l - 1].field, d.pair_src_pair, d.pair_src_s, s->mol_nv, s->mol_adj_off, s->mol_adj, s->mol_coul,
+                               d.adj, d.rsum, d.node_scale, d.pi, d.node_present, swp, d.cons_of_pair, d.cons_inv_off, d.inv,
+                               reinterpret_cast<float2 *>(d.rowscale), d.trow, d.rowflag, d.trowf, d.fwd_goff);
+            GF_LAUNCH_CHECK(ctx, "build_node_tables");
+        } else {
+            hipLaunchKernelGGL(build_level_rows, dim3(h.nNodes), dim3(256), lds, up, d.node_s, d.node_mol, d.node_row, d.node_pair, d.field,
+                               s->lv[l - 1].field, d.pair_src_pair, d.pair_src_s, s->mol_nv, s->mol_adj_off, s->mol_adj, s->mol_coul, d.adj,
+                               d.rsum, d.node_scale, d.pi, d.node_present, vmax);
+            GF_LAUNCH_CHECK(ctx, "build_level_rows");
+            if (h.pairs) {
+                hipLaunchKernelGGL(build_level_inv, dim3((unsigned)((h.pairs + 3) / 4)), dim3(256), 0, up, d.cons_pair, d.pair_node, d.node_s,
+                                   d.node_row, d.node_pair, d.cons_inv_off, d.pi, d.inv, (long long)h.pairs);
+                GF_LAUNCH_CHECK(ctx, "build_level_inv");
+            }
+        }
+        hipLaunchKernelGGL(level_table_stats, dim3(1), dim3(1024), 0, up, d.node_scale, d.node_present, h.nNodes, stats);
+        GF_LAUNCH_CHECK(ctx, "level_table_stats");
+    }
+    return GF_OK;
+}
+
+// (the node tables went up on the handle's upload stream: the row factors, the fused levels' records and the transposed-row tables are built
+//  there too, behind them)
+gf_status build_row_tables(gf_smp *s) {
+    hipStream_t up = upload_stream(s);
+    for (int l = 1; l <= s->cfg.nLevels; ++l) {
+        const gf_smp::DevLevel &d = s->lv[l];
+        const int nNodes = s->lay.level[l].nNodes;
+        const bool merged = d.node_tables_merged;   // (row factors, transposed-row tables and gather offsets are in place)
+        if (!merged)
+            hipLaunchKernelGGL(expand_rowscale, dim3(nNodes), dim3(64), 0, up, reinterpret_cast<float2 *>(d.rowscale),
+                               reinterpret_cast<const float2 *>(d.node_scale), d.node_s, d.node_row);
+        gf_status st = smp_build_gather_records(s, l, up);
+        if (st == GF_OK) st = smp_build_tf_records(s, l, up);
+        if (st == GF_OK) st = smp_fwd_fused_build_tables(s, l, up, !merged);
+        if (st != GF_OK) return st;
+        if (d.trow && !merged) hipLaunchKernelGGL(build_trow, dim3(nNodes), dim3(64), 0, up, d.trow, d.node_s, d.node_row, d.pi, d.rowflag, d.trowf);
+    }
+    return GF_OK;
+}
+
+// the level-0 input, the read-out and the per-molecule buffers
+gf_status alloc_readout(gf_smp *s, int nMol) {
+    const gfsmp::BatchLayout &B = s->lay;
+    const int L = s->cfg.nLevels, C = s->cfg.nChanels;
+    const gfsmp::LevelLayout &top = B.level[L];
+    Taker t = {s};
+    t.put(&s->x, B.x);
+    s->wbound = nullptr;
+    if (s->cfg.square() && C == 64) t.alloc(&s->wbound, smp_wgrad_bound_words() * (size_t)(L + 1));
+    else if (s->cfg.square() && (C == 32 || C == 16))   // scratch words of the C = 32 / 16 weight-gradient kernel's column bounds
+        t.alloc(&s->wbound, smp_wgrad_all_words() * (size_t)(L + 1));
+    t.alloc(&s->sh, (size_t)top.nNodes * C);
+    t.alloc(&s->vf, (size_t)top.nNodes * C);
+    t.alloc(&s->dsh, (size_t)top.nNodes * C);
+    t.alloc(&s->g, (size_t)nMol * (s->cfg.physics ? feature_width(s->cfg) : (size_t)C));
+    t.alloc(&s->yhat, (size_t)nMol);
+    t.alloc(&s->dy, (size_t)nMol);
+    t.put(&s->top_node_mol, top.node_mol);
+    t.put(&s->mol_ptr, B.mol_first_vertex);      // [nMol + 1]: the vertices of a molecule are contiguous
+    t.put(&s->mol_nodes, B.top_node_of_vertex);  // [vertices = nodes of level L]
+    long long maxrows = 0, maxpairs = 0;
+    for (int l = 0; l <= L; ++l) {
+        maxrows = std::max(maxrows, (long long)B.level[l].rows);
+        maxpairs = std::max(maxpairs, (long long)B.level[l].pairs);
+    }
+    s->colpart_rows = (size_t)((maxrows + 1023) / 1024 + (maxpairs + 255) / 256 + 2);
+    s->colpart_rows = std::max(s->colpart_rows, (size_t)256 * (L + 1));  // fused levels: up to 256 column partials per level
+    t.alloc(&s->colpart, s->colpart_rows * C);
+    return t.st;
+}
+
+}  // namespace
+}  // namespace gf
+
+using gf::fail;
+
+extern "C" {
+
+gf_status gf_smp_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature) {
+    return gf_smp_prepare_coulomb(s, nMol, nVertices, adj, feature, nullptr);
+}
+
+gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature,
+                                 const double *coulomb) {
+    if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
+    gf_ctx *ctx = s->ctx;
+    if (nMol <= 0 || !nVertices || !adj || !feature) return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare: bad argument");
+    for (int m = 0; m < nMol; ++m)
+        if (nVertices[m] <= 0 || nVertices[m] > 4096) return fail(ctx, GF_ERR_INVALID, "molecule %d has %d vertices", m, nVertices[m]);
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    gf_status st = gf::choose_plan(s, nMol, nVertices, adj, coulomb);
+    if (st != GF_OK) return st;
+    const bool prep_timing = std::getenv("GF_PREP_TIMING") != nullptr;
+    const auto tp0 = std::chrono::steady_clock::now();
+    gf::ensure_upload_stream(s);
+    gf::release(s);
+    const auto tp1 = std::chrono::steady_clock::now();
+    gf::choose_table_builder(s, nMol, nVertices);
+    s->tab_stats = nullptr;
+    s->h_tab_stats.clear();
+    s->h_covered.clear();
+    gfsmp::build_batch(s->cfg, nMol, nVertices, adj, feature, coulomb, &s->lay);
+    const auto tp2 = std::chrono::steady_clock::now();
+    static_assert(sizeof(long long) == sizeof(int64_t), "int64 layout");
+    const int L = s->cfg.nLevels, C = s->cfg.nChanels;
+    s->lv.assign(L + 1, gf_smp::DevLevel());
+    long long maxp = 0;
+    size_t contract_ws = 0;
+    for (int l = 0; l <= L && st == GF_OK; ++l) st = gf::alloc_level(s, l, &maxp, &contract_ws);
+    if (st == GF_OK && s->lay.device_tables) st = gf::build_device_tables(s, coulomb != nullptr);
+    if (st == GF_OK) st = gf::build_row_tables(s);
+    s->P = nullptr;  // [max ppos][C]: by far the largest buffer of the op-by-op path, taken from the pool only when a level needs it
+    s->P_count = (size_t)maxp;  // (positions x channels of the level below, maximised over the levels)
+    if (st == GF_OK) st = gf::alloc_readout(s, nMol);
+    if (st != GF_OK) return st;
+    // split-K partials of the weight gradients also live in the context workspace
+    const size_t gemm_ws = sizeof(float) * 4400 * (size_t)4 * C * C + sizeof(float) * 4400 * (size_t)C * s->cfg.fdim() + (1 << 20);
+    s->ws_need = std::max(contract_ws, gemm_ws);  // grown by forward / backward on the compute thread (smp_internal.h)
+    // the tables are on the device when this returns (the host vectors are reused by the next batch); the context's stream
+    // is NOT waited for: it may be running another handle's step
+    GF_HIP_TRY(ctx, hipStreamSynchronize(gf::upload_stream(s)));
+    if (prep_timing) {
+        const auto tp3 = std::chrono::steady_clock::now();
+        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+            return std::chrono::duration<double, std::milli>(b - a).count();
+        };
+        std::fprintf(stderr, "gf_smp_prepare: release %.1f ms, host graph preparation %.1f ms, device allocation + upload %.1f ms\n",
+                     ms(tp0, tp1), ms(tp1, tp2), ms(tp2, tp3));
+    }
+    s->prepared = true;
+    return GF_OK;
+}
+
+/* Host-only graph preparation of ONE molecule (no device needed): receptive fields phi[l][v] as
+ * [L+1][V][cap+1] ints (slot 0 = size) and, optionally, the WL features [V][F(D+1)].  Lets the host logic be tested
+ * on a CPU-only box and inspected by callers. */
+gf_status gf_smp_prepare_molecule_host(const gf_smp_config *cfg, int V, const int *adj, const double *feature,
+                                       int *phi_out, double *wl_out) {
+    if (!cfg || V <= 0 || !adj || !feature || !phi_out) return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: bad argument");
+    gfsmp::Config c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, cfg->has_WL_ordering};
+    c.physics = cfg->physics ? 1 : 0;
+    gfsmp::Molecule m;
+    gfsmp::prepare_molecule(c, V, adj, feature, &m);
+    const int cap = c.max_receptive_field;
+    for (int l = 0; l <= c.nLevels; ++l)
+        for (int v = 0; v < V; ++v) {
+            int *p = phi_out + ((size_t)l * V + v) * (cap + 1);
+            const std::vector<int> &f = m.phi[l][v];
+            p[0] = (int)f.size();
+            for (int i = 0; i < cap; ++i) p[1 + i] = i < (int)f.size() ? f[i] : -1;
+        }
+    if (wl_out)
+        for (size_t i = 0; i < m.wl.size(); ++i) wl_out[i] = m.wl[i];
+    return GF_OK;
+}
+
+}  // extern "C"

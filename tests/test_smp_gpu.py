@@ -1520,7 +1520,7 @@ def test_smp_2d_ver6_on_the_fused_level_equals_the_op_by_op_level(gf, monkeypatc
 @pytest.mark.parametrize("C,fused,cap,coul", [(64, True, 29, False), (8, False, 6, False), (16, True, 12, True)])
 def test_device_level_tables_equal_the_host_built_ones(gf, monkeypatch, C, fused, cap, coul):
     """The rows-sized level tables (reduced adjacency, gated row sums, (tot, tr), selection maps, inverse maps) are built on the
-    device from the receptive fields (smp.hip: build_level_rows / build_level_inv; GF_PREP_DEVICE_TABLES=0: by the host, as
+    device from the receptive fields (smp_prepare.hip: build_level_rows / build_level_inv; GF_PREP_DEVICE_TABLES=0: by the host, as
     gfsmp::build_batch's phases B and D write them, SMP_omega.h:461-474, 556-581).  Same batch both ways: reduced adjacencies of
     every node, the count of rows with data, and -- every kernel being deterministic -- predictions, losses and gradients must
     be IDENTICAL bit for bit."""
