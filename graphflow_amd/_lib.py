@@ -83,6 +83,10 @@ PROTOTYPES.update({
     "gf_smp_create": (_i, [_vp, _vp, C.POINTER(_vp)]),
     "gf_smp_destroy": (_i, [_vp]),
     "gf_smp_param_count": (C.c_size_t, [_vp]),
+    "gf_smp_create_classifier": (_i, [_vp, _vp, _i, C.POINTER(_vp)]),
+    "gf_smp_classes": (_i, [_vp]),
+    "gf_smp_class_scores": (_i, [_vp, _vp, _vp]),
+    "gf_smp_classifier_uniform_init_host": (_i, [_vp, _i, _fp]),
     "gf_smp_prepare": (_i, [_vp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp]),
     "gf_smp_prepare_coulomb": (_i, [_vp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, _dp]),
     "gf_smp_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),

@@ -520,7 +520,7 @@ gf_status smp_dp_level_done(gf_smp *s, int l) {
     size_t n = nH;
     if (l >= 1) {
         seg += nH + (size_t)(l - 1) * per;
-        n = per + (l == c.nLevels ? C : 0);
+        n = per + (l == c.nLevels ? (size_t)c.readout_rows() * C : 0);
     }
     hipStream_t comm = dist_stream(ctx);
     GF_HIP_TRY(ctx, hipEventRecord(s->ev_grad, ctx->stream));
@@ -616,7 +616,7 @@ void gf::smp_derive_plan(gf_smp *s, bool allow_embed) {
 
 // pad_channels = false: compute at the configuration's own channel counts (the towers of a model with RisiContraction_18_dropout --
 // SMP_sigma_pairgraphs -- whose levels run op by op, where a padded width only costs)
-gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channels, gf_smp **out, int min_pad) {
+gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channels, gf_smp **out, int min_pad, int nClass) {
     if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
     if (!cfg || !out) return fail(ctx, GF_ERR_INVALID, "gf_smp_create: null argument");
     if (cfg->nLevels < 1 || cfg->nChanels < 1 || cfg->nFeatures < 1 || cfg->nDepth < 0 || cfg->max_receptive_field < 1)
@@ -629,6 +629,7 @@ gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channel
     s->cfg.nContractions = cfg->nContractions ? cfg->nContractions : 18;
     s->cfg.custom_matmul = cfg->custom_matmul ? 1 : 0;
     s->cfg.physics = cfg->physics ? 1 : 0;
+    s->cfg.nClass = nClass;
     s->ucfg = s->cfg;
     s->req_pad_channels = pad_channels;
     s->req_min_pad = min_pad;
@@ -702,6 +703,29 @@ gf_status gf_smp_destroy(gf_smp *s) {
 }
 
 size_t gf_smp_param_count(const gf_smp *s) { return s ? gf::param_count(s->ucfg) : 0; }
+
+// The `_classification` models (smp_readout_classes.hip): the levels of gf_smp_create, W [nClass][C] read out by MatVecMul + LogLoss
+gf_status gf_smp_create_classifier(gf_ctx *ctx, const gf_smp_config *cfg, int nClass, gf_smp **out) {
+    if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
+    if (!cfg || !out) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: null argument");
+    if (cfg->physics) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: a physics tower has no read-out of its own (physics = 0)");
+    if (nClass < 2) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: nClass = %d (at least 2)", nClass);
+    return gf::smp_create(ctx, cfg, /*pad_channels=*/true, out, /*min_pad=*/0, nClass);
+}
+
+int gf_smp_classes(const gf_smp *s) { return s ? s->ucfg.nClass : 0; }
+
+// scores = predict->value (MatVecMul), probability = LogLoss::probability of the last forward; device pointers, either may be NULL
+gf_status gf_smp_class_scores(gf_smp *s, float *scores, float *probability) {
+    if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
+    gf_ctx *ctx = s->ctx;
+    if (!s->ucfg.nClass) return fail(ctx, GF_ERR_INVALID, "gf_smp_class_scores: not a classifier handle (gf_smp_create_classifier)");
+    if (!s->forwarded) return fail(ctx, GF_ERR_INVALID, "gf_smp_class_scores before gf_smp_forward");
+    const size_t bytes = sizeof(float) * (size_t)s->lay.nMol * s->ucfg.nClass;
+    if (scores) GF_HIP_TRY(ctx, hipMemcpyAsync(scores, s->cls_scores, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    if (probability) GF_HIP_TRY(ctx, hipMemcpyAsync(probability, s->cls_prob, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return GF_OK;
+}
 
 }  // extern "C"
 
@@ -831,9 +855,14 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
     } else {
         st = readout_level(s, L, s->sh, s->vf, s->lv[L].psum_ready);
         if (st != GF_OK) return st;
-        GF_LAUNCH(ctx, "smp_readout_mol", readout_molecules, dim3(B.nMol), dim3(256), 0, s->vf, s->mol_ptr, s->mol_nodes, W, targets, s->g, s->yhat,
-                  loss, s->dy, C);
-        if (predict) GF_HIP_TRY(ctx, hipMemcpyAsync(predict, s->yhat, sizeof(float) * B.nMol, hipMemcpyDeviceToDevice, ctx->stream));
+        if (s->cfg.nClass) {   // (a classifier: logits, softmax, arg-max label into predict, log p[label] into loss)
+            st = readout_classes_forward(s, W, targets, predict, loss);
+            if (st != GF_OK) return st;
+        } else {
+            GF_LAUNCH(ctx, "smp_readout_mol", readout_molecules, dim3(B.nMol), dim3(256), 0, s->vf, s->mol_ptr, s->mol_nodes, W, targets, s->g, s->yhat,
+                      loss, s->dy, C);
+            if (predict) GF_HIP_TRY(ctx, hipMemcpyAsync(predict, s->yhat, sizeof(float) * B.nMol, hipMemcpyDeviceToDevice, ctx->stream));
+        }
     }
     const size_t gwidth = s->cfg.physics ? feature_width(s->cfg) : (size_t)C;
     if (graph_feature) GF_HIP_TRY(ctx, hipMemcpyAsync(graph_feature, s->g, sizeof(float) * B.nMol * gwidth, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1003,9 +1032,14 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
     // the read-out's gradient into the top level: a fused level reads it as one vector per node, the others at every (i, j)
     const gfsmp::LevelLayout &top = B.level[L];
     const bool top_fused = !dfeat && kind[L] == LevelKind::Fused18;
-    if (!dfeat) GF_LAUNCH(ctx, "smp_readout_dW", readout_dW, dim3(1), dim3(1024), 0, s->dy, s->g, dW, C, B.nMol);
+    const bool classes = !dfeat && s->cfg.nClass;   // (a classifier: dg [nMol][C] goes down instead of dy[mol] * W)
+    if (!dfeat && !classes) GF_LAUNCH(ctx, "smp_readout_dW", readout_dW, dim3(1), dim3(1024), 0, s->dy, s->g, dW, C, B.nMol);
     if (dfeat) {
         if (kind[L] != LevelKind::Fused18) st = feature_backward(s, dfeat, L, 0);
+        if (st != GF_OK) return st;
+    } else if (classes) {
+        st = readout_classes_dW(s, dW);
+        if (st == GF_OK) st = readout_classes_backward(s, /*per_node=*/top_fused);
         if (st != GF_OK) return st;
     } else if (top_fused) {
         GF_LAUNCH(ctx, "smp_readout_bwd", readout_backward_nodevec, dim3(grid_for((size_t)top.nNodes * C)), dim3(256), 0, s->dy, W, s->sh,

@@ -88,7 +88,7 @@ gf_status smp_wgrad_partials_c64(gf_ctx *ctx, const float *T, const float *dO, c
 
 namespace gf {
 // min_pad: the smallest padded width the handle may compute at (32 for the towers of a slice-dropout model)
-gf_status smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channels, gf_smp **out, int min_pad = 0);   // gf_smp_create = (.., true, ..)
+gf_status smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channels, gf_smp **out, int min_pad = 0, int nClass = 0);   // gf_smp_create = (.., true, ..)
 void smp_derive_plan(gf_smp *s, bool allow_embed);
 gf_status smp_switch_plan(gf_smp *s, bool embed);
 constexpr int kPadMaxLevels = 15;   // levels a padded model's layout map holds (gf_smp_create: deeper models compute at nChanels)
@@ -220,6 +220,8 @@ struct gf_smp {
     float *dsh = nullptr;                // [nNodes][C] gradient of sh (the fused top level reads it per node)
     float *g = nullptr;      // [nMol][C] graph features
     float *yhat = nullptr, *dy = nullptr;  // [nMol]
+    // classifier handles (cfg.nClass >= 2, smp_readout_classes.hip): logits, softmax, dz = p - onehot [nMol][nClass]; dg = W^T dz [nMol][C]
+    float *cls_scores = nullptr, *cls_prob = nullptr, *cls_dz = nullptr, *cls_dg = nullptr;
     float *colpart = nullptr;  // partial column sums for bias gradients, [colpart_rows][C]
     size_t colpart_rows = 0;
     int *top_node_mol = nullptr, *mol_ptr = nullptr, *mol_nodes = nullptr;
@@ -284,11 +286,12 @@ gf_status smp_combine_bwd_panels_c64(gf_smp *s, int l, const float *dfrows, cons
 gf_status smp_dp_level_done(gf_smp *s, int l);
 
 // ---- the parameter layout: H, (K_1, b_1), ..., (K_L, b_L), W -- the registration order of SMP_omega.h:289-295 (= save_model order) ----
+// (W is [readout_rows()][C]: one row for the regression models, nClass rows for a classifier, SMP_2D_ver6_classification.h:211-217)
 inline size_t param_count(const gfsmp::Config &c) {
     size_t n = (size_t)c.nChanels * c.fdim();
     for (int l = 1; l <= c.nLevels; ++l)
         n += (size_t)c.nContractions * c.level_channels(l - 1) * c.level_channels(l) + c.level_channels(l);
-    return n + (c.physics ? 0 : c.nChanels);  // a physics tower ends in its level features: the head's weights are the caller's
+    return n + (c.physics ? 0 : (size_t)c.readout_rows() * c.nChanels);  // a physics tower ends in its level features: the head's weights are the caller's
 }
 template <typename P>
 void view_params(const gfsmp::Config &c, P *base, P **H, std::vector<P *> *K, std::vector<P *> *b, P **W) {
@@ -339,5 +342,9 @@ gf_status fold_level(gf_smp *s, int l);
 gf_status extra_products_forward(gf_smp *s, int l);   // no-ops unless gf_smp::n_extra
 gf_status extra_products_wgrad(gf_smp *s, int l);
 gf_status extra_products_backward(gf_smp *s, int l);
+// ---- smp_readout_classes.hip: the read-out of a classifier handle (cfg.nClass >= 2); W [nClass][cfg.nChanels] ----
+gf_status readout_classes_forward(gf_smp *s, const float *W, const float *targets, float *predict, float *loss);
+gf_status readout_classes_dW(gf_smp *s, float *dW);
+gf_status readout_classes_backward(gf_smp *s, bool per_node);   // per_node: gf_smp::dsh for a fused top level, else df_L row by row
 }
 #endif

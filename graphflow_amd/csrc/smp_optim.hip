@@ -187,7 +187,7 @@ gf_status gf_smp_adam_reset(gf_smp *s) {
 // SMP_omega::weights_initialization (SMP_omega.h:334-338) = GraphFlow::uniform_init (GraphFlow.h:1297-1306) over the
 // parameters in registration order, drawn from the C library's rand() exactly as the reference draws them: after the
 // same srand() a model built here starts from the same weights as one built by the reference.  Host buffer.
-gf_status gf_smp_uniform_init_host(const gf_smp_config *cfg, float *params) {
+static gf_status uniform_init_host(const gf_smp_config *cfg, int nClass, float *params) {
     if (!cfg || !params) return GF_ERR_INVALID;
     gfsmp::Config c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, cfg->has_WL_ordering};
     c.nContractions = cfg->nContractions ? cfg->nContractions : 18;
@@ -199,7 +199,7 @@ gf_status gf_smp_uniform_init_host(const gf_smp_config *cfg, float *params) {
         sizes.push_back((size_t)c.nContractions * c.level_channels(l - 1) * c.level_channels(l));
         sizes.push_back((size_t)c.level_channels(l));
     }
-    if (!c.physics) sizes.push_back(C);
+    if (!c.physics) sizes.push_back((size_t)(nClass > 1 ? nClass : 1) * C);
     size_t off = 0;
     for (size_t v = 0; v < sizes.size(); ++v)
         for (size_t i = 0; i < sizes[v]; ++i) {
@@ -208,6 +208,13 @@ gf_status gf_smp_uniform_init_host(const gf_smp_config *cfg, float *params) {
             params[off++] = (float)x;
         }
     return GF_OK;
+}
+gf_status gf_smp_uniform_init_host(const gf_smp_config *cfg, float *params) { return uniform_init_host(cfg, 0, params); }
+// ... of the `_classification` models (SMP_2D_ver6_classification.h:256-259): sgd->params holds Vector*, so W [nClass][C] is drawn by
+// uniform_init(Vector*) like the rest, with the divisor 10 * nClass * C
+gf_status gf_smp_classifier_uniform_init_host(const gf_smp_config *cfg, int nClass, float *params) {
+    if (!cfg || cfg->physics || nClass < 2) return GF_ERR_INVALID;
+    return uniform_init_host(cfg, nClass, params);
 }
 
 // Text checkpoints in the reference's format (SMP_omega.h:1033-1042 / :1044-1055): every parameter value in

@@ -3,17 +3,17 @@
 #include "smp_internal.h"
 
 namespace gf {
-// The two parameter layouts.  Order H [C_0][FD], (K_l, b_l)..., W [C] (no W in a physics tower); K_l is [18][C_{l-1}][C_l] as (k, ci, co)
+// The two parameter layouts.  Order H [C_0][FD], (K_l, b_l)..., W [C] ([nClass][C] on a classifier handle; no W in a physics tower); K_l is [18][C_{l-1}][C_l] as (k, ci, co)
 // (SMP_omega.h:289-295; C_l = C, or halving per level in a tower) or, custom_matmul, [C][18 C] as (co, k, ci) (CustomMatMulTensor,
 // SMP_2D_ver8).  The padded layout has Cc channels at every level.
 struct PadMap {
-    int L, nK, custom, FD, Cc, hasW;
+    int L, nK, custom, FD, Cc, hasW, nW;   // nW: rows of W (Config::readout_rows)
     int cu[kPadMaxLevels + 1];          // the caller's channels of level l
     long long uoff[kPadMaxLevels + 2];  // the caller's offset of H (0), K_1, ..., K_L, W
 };
 static PadMap pad_map(const gfsmp::Config &u, const gfsmp::Config &c) {
     PadMap m = {};
-    m.L = u.nLevels, m.nK = u.nContractions, m.custom = u.custom_matmul, m.FD = u.fdim(), m.Cc = c.nChanels, m.hasW = u.physics ? 0 : 1;
+    m.L = u.nLevels, m.nK = u.nContractions, m.custom = u.custom_matmul, m.FD = u.fdim(), m.Cc = c.nChanels, m.hasW = u.physics ? 0 : 1, m.nW = u.readout_rows();
     for (int l = 0; l <= m.L; ++l) m.cu[l] = u.level_channels(l);
     m.uoff[0] = 0;
     m.uoff[1] = (long long)m.cu[0] * m.FD;
@@ -50,8 +50,9 @@ __device__ __forceinline__ long long padded_to_user(long long i, const PadMap &m
         ci = (int)(r / Cc), co = (int)(r % Cc);
         return (ci < Ci && co < Co) ? base + ((long long)k * Ci + ci) * Co + co : -1;
     }
-    const long long c = i - (long long)m.L * lvl_pad;   // W
-    return (m.hasW && c < m.cu[m.L]) ? m.uoff[m.L + 1] + c : -1;
+    const long long c = i - (long long)m.L * lvl_pad;   // W [nW][Cc]
+    const long long r = c / Cc, f = c % Cc;
+    return (m.hasW && r < m.nW && f < m.cu[m.L]) ? m.uoff[m.L + 1] + r * m.cu[m.L] + f : -1;
 }
 __global__ void pad_parameters(const float *__restrict__ user, float *__restrict__ padded, long long n_padded, PadMap m) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -88,7 +89,7 @@ __device__ __forceinline__ void v7_slot(int k, int *slot, int *grp) {
     *slot = sl[k];
     *grp = gr[k];
 }
-// the caller's parameter u -> its (only) place in the padded [H | (K_l [18 Cc][Cc], b_l [Cc]) x L | W | X_1 .. X_L] vector
+// the caller's parameter u -> its (only) place in the padded [H | (K_l [18 Cc][Cc], b_l [Cc]) x L | W [nW][Cc] | X_1 .. X_L] vector
 __device__ __forceinline__ long long v6_user_to_padded(long long u, const PadMap &m) {
     const int C = m.cu[0], Cc = m.Cc, nK = m.nK;
     if (u < m.uoff[1]) return u;   // H: rows c < C first in both layouts
@@ -111,10 +112,11 @@ __device__ __forceinline__ long long v6_user_to_padded(long long u, const PadMap
         if (nK == 10) v6_slot(k, &slot, &grp);
         else v7_slot(k, &slot, &grp);
         if (slot >= 18)   // an extra product's block
-            return hpad + m.L * lvl_pad + Cc + ((long long)(l - 1) * 3 + (slot - 18)) * Cc * Cc + (long long)(grp * C + ci) * Cc + co;
+            return hpad + m.L * lvl_pad + (long long)m.nW * Cc + ((long long)(l - 1) * 3 + (slot - 18)) * Cc * Cc + (long long)(grp * C + ci) * Cc + co;
         return base + ((long long)slot * Cc + grp * C + ci) * Cc + co;
     }
-    return hpad + m.L * lvl_pad + (u - m.uoff[m.L + 1]);   // W
+    const long long w = u - m.uoff[m.L + 1];   // W [nW][C] -> [nW][Cc]
+    return hpad + m.L * lvl_pad + (w / C) * Cc + w % C;
 }
 __global__ void v6_pad_parameters(const float *__restrict__ user, float *__restrict__ padded, long long n_user, PadMap m) {
     const long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;

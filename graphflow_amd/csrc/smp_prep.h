@@ -47,6 +47,10 @@ struct Config {
     // 1 (a physics tower's DEVICE configuration, gf_smp_create): every level is computed at nChanels -- the halving channel counts
     // zero-padded to one width -- so the tower's levels run the fused level kernels
     int uniform = 0;
+    // >= 2: the `_classification` models (gf_smp_create_classifier): the read-out weights are W [nClass][nChanels] (MatVecMul + LogLoss
+    // instead of InnerProduct + SquaredLoss); 0: regression, W [nChanels] -- one row
+    int nClass = 0;
+    int readout_rows() const { return nClass > 1 ? nClass : 1; }   // rows of W: [1][C] is the regression's [C]
     bool square() const { return !physics || uniform; }   // K_l is [nContractions C][C] at every level
     int level_channels(int l) const {
         if (square()) return nChanels;

@@ -717,6 +717,13 @@ gf_status alloc_readout(gf_smp *s, int nMol) {
     t.alloc(&s->g, (size_t)nMol * (s->cfg.physics ? feature_width(s->cfg) : (size_t)C));
     t.alloc(&s->yhat, (size_t)nMol);
     t.alloc(&s->dy, (size_t)nMol);
+    s->cls_scores = s->cls_prob = s->cls_dz = s->cls_dg = nullptr;
+    if (s->cfg.nClass) {   // classifier read-out (smp_readout_classes.hip)
+        t.alloc(&s->cls_scores, (size_t)nMol * s->cfg.nClass);
+        t.alloc(&s->cls_prob, (size_t)nMol * s->cfg.nClass);
+        t.alloc(&s->cls_dz, (size_t)nMol * s->cfg.nClass);
+        t.alloc(&s->cls_dg, (size_t)nMol * C);
+    }
     t.put(&s->top_node_mol, top.node_mol);
     t.put(&s->mol_ptr, B.mol_first_vertex);      // [nMol + 1]: the vertices of a molecule are contiguous
     t.put(&s->mol_nodes, B.top_node_of_vertex);  // [vertices = nodes of level L]

@@ -217,6 +217,43 @@ class SMPGamma(SMPOmega):
         super().__init__(nLevels, nChanels, nFeatures, nDepth, max_nVertices, has_WL_ordering, ctx=ctx, nContractions=4)
 
 
+class SMPClassifier(SMPOmega):
+    """The classification models of GraphFlow (SMP_2D_ver6_classification: nContractions=10, custom_matmul=True;
+    SMP_2D_ver7_classification: 50, True) through gf_smp_create_classifier: the levels of the regression model, read out by
+    MatVecMul(W[nClass, C]) + LogLoss.  Parameters in registration order: H, (K_l, b_l) for l = 1..L, W[nClass, C].
+    forward(params, targets) takes the labels as floats and returns (predict = arg-max label as a float, loss = log p[label],
+    at most 0 -- the reference's sign -- and graph_feature); scores() gives the logits and probabilities of that forward."""
+
+    def __init__(self, nClass, nLevels, nChanels, nFeatures, nDepth, max_receptive_field, has_WL_ordering=True, ctx=None,
+                 nContractions=10, custom_matmul=True):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.nClass = int(nClass)
+        self.cfg = SMPConfig(nLevels, nChanels, nFeatures, nDepth, max_receptive_field, 1 if has_WL_ordering else 0,
+                             nContractions, 1 if custom_matmul else 0, 0)
+        h = C.c_void_p()
+        self.ctx.check(self.lib.gf_smp_create_classifier(self.ctx.handle, C.byref(self.cfg), self.nClass, C.byref(h)))
+        self.handle = h
+        self.n_params = self.lib.gf_smp_param_count(h)
+        self.n_mol = 0
+
+    def scores(self):
+        """(scores, probability) of the last forward: predict->value and LogLoss::probability, [nMol, nClass] each."""
+        dev = self.ctx.device
+        z = torch.empty((self.n_mol, self.nClass), dtype=torch.float32, device=dev)
+        p = torch.empty((self.n_mol, self.nClass), dtype=torch.float32, device=dev)
+        self.ctx.check(self.lib.gf_smp_class_scores(self.handle, C.c_void_p(z.data_ptr()), C.c_void_p(p.data_ptr())))
+        return z, p
+
+    def uniform_init(self):
+        """Initial weights exactly as the reference classifier's constructor draws them from rand() (call srand first)."""
+        out = np.zeros(self.n_params, dtype=np.float32)
+        st = self.lib.gf_smp_classifier_uniform_init_host(C.byref(self.cfg), self.nClass, out.ctypes.data_as(C.POINTER(C.c_float)))
+        if st != 0:
+            raise RuntimeError("gf_smp_classifier_uniform_init_host failed")
+        return out
+
+
 class SMPModelConfig(C.Structure):
     _fields_ = [("nTowers", C.c_int), ("nLevels", C.c_int), ("nChanels", C.c_int), ("max_receptive_field", C.c_int),
                 ("nFeatures", C.c_int * 2), ("nKept", C.c_int), ("nContractions", C.c_int)]

@@ -259,6 +259,26 @@ typedef struct {
 gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out);
 gf_status gf_smp_destroy(gf_smp *smp);
 size_t    gf_smp_param_count(const gf_smp *smp);
+/* The `_classification` models: SMP_2D_ver6_classification (nContractions 10, custom_matmul 1) and SMP_2D_ver7_classification (50, 1) of
+ * the reference (GraphFlow/SMP_2D_ver6_classification.h:189-200, :560-563, :699-713), and the same read-out on every other non-physics
+ * wiring gf_smp_create takes (18, 4).  The levels, their weights, their plans (fused embedding, op-by-op fallback per batch, channel
+ * padding) and the Momentum optimiser are those of the regression handle; only the read-out above graph_feature differs:
+ *   scores z = MatVecMul(W[nClass][C], graph_feature), probability = softmax(z), loss = LogLoss (GraphFlow/LogLoss.h:37-76).
+ * Parameter order: H, (K_l, b_l) for l = 1..L, W[nClass][C] row-major -- the reference's registration and save_model order.  Everything
+ * that works through gf_smp_param_count (save / load, the optimisers, parameters_upload / download, forward_host) works on such a handle.
+ * gf_smp_forward on a classifier handle:
+ *   targets[m]  the label as a float (the reference's (int)target); a label outside [0, nClass) -- undefined behaviour in the reference --
+ *               gives loss NaN and contributes no gradient;
+ *   predict[m]  the arg-max label as a float, the lowest index on a tie (Predict's strict `>` loop, :706-712);
+ *   loss[m]     LogLoss::value = log probability[label], AT MOST 0 (the reference's sign: its BatchLearn returns sums of these; the
+ *               quantity the gradient descends is its negative), computed as (z_label - max z) - log sum exp(z - max z) so that it stays
+ *               finite where an fp32 probability underflows, and LOG_ZERO = -256 exactly where the reference's fp64 exp underflows;
+ *   targets == NULL: scores, probabilities and predict only.
+ * nClass >= 2; physics = 1 is refused (GF_ERR_INVALID).  gf_smp_backward is unchanged; gf_smp_backward_features stays refused. */
+gf_status gf_smp_create_classifier(gf_ctx *ctx, const gf_smp_config *cfg, int nClass, gf_smp **out);
+int       gf_smp_classes(const gf_smp *smp);   /* nClass of a classifier handle, 0 for a regression handle */
+/* Of the last gf_smp_forward: predict->value[c] and LogLoss::probability[c], device pointers [nMol][nClass], either may be NULL. */
+gf_status gf_smp_class_scores(gf_smp *smp, float *scores, float *probability);
 /* Host pointers: nVertices[nMol]; adj = the molecules' V x V int adjacency matrices back to back (DenseGraph::adj);
  * feature = their V x nFeatures matrices back to back (DenseGraph::feature).  Blocking (uploads index tables).
  * Thread safety: DIFFERENT handles of one context may be prepared at the same time from different host threads (each calling
@@ -333,6 +353,9 @@ gf_status gf_smp_momentum_step(gf_smp *smp, float *params, const float *grads, d
 /* SMP_omega::weights_initialization (SMP_omega.h:334-338; GraphFlow.h:1297-1306) into a HOST buffer of
  * gf_smp_param_count floats, drawing from rand() in the reference's order: same srand() -> same initial weights. */
 gf_status gf_smp_uniform_init_host(const gf_smp_config *cfg, float *params);
+/* ... of a classifier (SMP_2D_ver6_classification.h:256-259): sgd->params holds Vector*, so W[nClass][C] is drawn by
+ * uniform_init(Vector*) with the divisor 10 * nClass * C.  Host only. */
+gf_status gf_smp_classifier_uniform_init_host(const gf_smp_config *cfg, int nClass, float *params);
 /* Text checkpoints interchangeable with SMP_omega::save_model / load_model (GraphFlow/SMP_omega.h:1033-1055):
  * whitespace-separated values in the flat parameter order above.  `params` is a device pointer.  Blocking. */
 gf_status gf_smp_save_model(const gf_smp *smp, const float *params, const char *path);
