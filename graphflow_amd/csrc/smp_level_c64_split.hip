@@ -370,10 +370,13 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
                 if constexpr (NH == 2) gf_st_s<2>(out + (size_t)rr * LDOUT + 32, acc1[r]);
             }
         } else {
+            // (the partial panel skips the rows without data as the full ones do: until the stand-alone operator's test looked, it
+            //  stored them -- numbers no consumer reads, but "not written" then held for every row except the level's last few)
+            const unsigned mine = (MASK && !FWD) ? rowbits >> (4 * lh) : 0xffffffffu;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int rr = (r & 3) + 8 * (r >> 2);
-                if (r0 + 4 * lh + rr < rows && li < CB) {
+                if (r0 + 4 * lh + rr < rows && li < CB && ((mine >> rr) & 1u)) {
                     gf_st_s<2>(out + (size_t)rr * LDOUT, acc0[r]);
                     if constexpr (NH == 2) gf_st_s<2>(out + (size_t)rr * LDOUT + 32, acc1[r]);
                 }

@@ -1,15 +1,78 @@
-// smp_level_ops.hip -- the block products of the fused SMP level at C = 64 as stand-alone operators of the C ABI
-// (gf_smp_level_products_f32 / gf_smp_level_wgrad_f32, include/gf_hip.h): the same kernels gf_smp_forward / gf_smp_backward launch
+// smp_level_ops.hip -- the block products of the fused SMP level as stand-alone operators of the C ABI
+// (gf_smp_level_products_f32 / gf_smp_level_wgrad_f32 at C = 64, gf_smp_level_products_ex_f32 / gf_smp_level_wgrad_ex_f32 for every
+// variant the level has, include/gf_hip.h): the same kernels gf_smp_forward / gf_smp_backward launch
 // on a level's rows (smp_level_c64.hip on the fp32 matrix pipe, smp_level_c64_split.hip on the f16 pipe with two-half operands),
 // on caller-supplied matrices.  They replace, for the rows of one level, the K-projection MatMul of the reference
 // (GraphFlow/SMP_omega.h:654-657 forward, MatMul.h:69-82 backward) in its regrouped form (smp_fused.hip header) -- and they are
 // what the parity suite uses to hold the split-operand arithmetic to the fp64 product per output ROW and per weight-gradient ROW,
-// on operands whose dynamic range the whole-network tests cannot steer (tests/test_level_ops_gpu.py).
+// on operands whose dynamic range the whole-network tests cannot steer (tests/test_level_ops_gpu.py), and with rows placed on the
+// panel, slice and gather-window edges (tests/test_level_ops_ex_gpu.py).
 #include <cstring>
+#include <vector>
 
 #include "smp_internal.h"
 
 using gf::fail;
+
+namespace gf {
+namespace {
+
+// out[0] = max(1, largest per-product factor of a product that is bounded through `tot` (0, 1, 5, 6, 7)), out[1] = largest factor of
+// product 2 (bounded through `tr`), out[2] = max(1, largest factor of products 3, 4 -- they have no row factor in the level's bounds,
+// scale_words widens the channel maxima by it): float bits, atomicMax on words the caller zeroed.  rf [rows][8]
+__global__ __launch_bounds__(256) void rowfac8_absmax(const float *__restrict__ rf, int rows, unsigned *__restrict__ out) {
+    float a = 1.f, b = 0.f, c = 1.f;
+    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += gridDim.x * blockDim.x) {
+        const float *f = rf + 8 * (size_t)r;
+        a = fmaxf(a, fmaxf(fmaxf(fabsf(f[0]), fabsf(f[1])), fmaxf(fabsf(f[5]), fmaxf(fabsf(f[6]), fabsf(f[7])))));
+        b = fmaxf(b, fabsf(f[2]));
+        c = fmaxf(c, fmaxf(fabsf(f[3]), fabsf(f[4])));
+    }
+    atomicMax(&out[0], __float_as_uint(a));
+    atomicMax(&out[1], __float_as_uint(b));
+    atomicMax(&out[2], __float_as_uint(c));
+}
+__global__ void scale_words(unsigned *__restrict__ w, int n, const unsigned *__restrict__ by) {   // w[i] (float bits) *= by[0]
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) w[i] = __float_as_uint(__uint_as_float(w[i]) * __uint_as_float(by[0]));
+}
+
+// rows the gathered operand dU[trow] of smp_wgrad_all may lie from its own row (kTrowWindow of smp_level_c64_split.hip)
+constexpr long long kGatherWindow = (long long)kFusedMaxField * kFusedMaxField;
+
+// The tables of a stand-alone call, checked on the host (one blocking copy each: these are test operators): every trow inside the
+// matrix and, `window` > 0, within that many rows of its own row; the low 29 bits of a packed entry equal to the plain one.
+gf_status check_tables(gf_ctx *ctx, const char *who, int rows, const int *trow, const int *trowf, long long window) {
+    std::vector<int> t((size_t)rows), f;
+    GF_HIP_TRY(ctx, hipMemcpyAsync(t.data(), trow, sizeof(int) * (size_t)rows, hipMemcpyDeviceToHost, ctx->stream));
+    if (trowf) {
+        f.resize((size_t)rows);
+        GF_HIP_TRY(ctx, hipMemcpyAsync(f.data(), trowf, sizeof(int) * (size_t)rows, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    GF_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int r = 0; r < rows; ++r) {
+        if (t[r] < 0 || t[r] >= rows) return fail(ctx, GF_ERR_INVALID, "%s: trow[%d] = %d outside the %d rows", who, r, t[r], rows);
+        const long long d = (long long)t[r] - r;
+        if (window > 0 && (d > window || -d > window))
+            return fail(ctx, GF_ERR_INVALID, "%s: trow[%d] = %d lies more than %lld rows from its row (the gather window of the level)", who, r, t[r], window);
+        if (trowf && (f[r] & 0x1fffffff) != t[r])
+            return fail(ctx, GF_ERR_INVALID, "%s: trowf[%d] holds row %d, trow[%d] = %d", who, r, f[r] & 0x1fffffff, r, t[r]);
+    }
+    return GF_OK;
+}
+
+// the variants the level's kernels have (before any launch): 0, or the status with the reason recorded
+gf_status check_variant(gf_ctx *ctx, const char *who, int C, int nf, int nx, bool products) {
+    if (!(C == 16 || C == 32 || (C == 64 && products))) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d channels", who, C);
+    if ((nf != 2 && nf != 8) || (nx != 0 && nx != 3)) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d row factors / %d extra products", who, nf, nx);
+    if (nx == 3 && nf == 8) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: the extra products take the plain (tot, tr) row factors", who);
+    if (C == 64 && (nx != 0 || nf != 2)) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d row factors / %d extra products at 64 channels", who, nf, nx);
+    if (C != 64 && !smp_split_products(ctx)) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d channels on the fp32 matrix pipe", who, C);
+    return GF_OK;
+}
+
+}  // namespace
+}  // namespace gf
 
 extern "C" {
 
@@ -42,6 +105,78 @@ gf_status gf_smp_level_wgrad_f32(gf_ctx *ctx, int rows, const float *T, const fl
     st = gf::smp_wgrad_partials_c64(ctx, T, dO, rowscale, rows, ws, (size_t)264 * total, &fg, trow, sc);
     if (st != GF_OK) return st;
     return gf::splitk_fold(ctx, fg.part, dWst, total, fg.splits, 0);
+}
+
+gf_status gf_smp_level_products_ex_f32(gf_ctx *ctx, int backward, int C, int nf, int nx, int rows, const float *A, const float *rowfac,
+                                       const float *Wst, const float *X, const int *trow, const int *trowf, int skip_zero_grads, float *Out) {
+    static const char *who = "gf_smp_level_products_ex_f32";
+    if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
+    if (rows < 0 || (rows > 0 && (!A || !rowfac || !Wst || !trow || !Out))) return fail(ctx, GF_ERR_INVALID, "%s: null argument", who);
+    if (nx == 3 && !X) return fail(ctx, GF_ERR_INVALID, "%s: three extra products without their weight blocks", who);
+    gf_status st = gf::check_variant(ctx, who, C, nf, nx, true);
+    if (st != GF_OK) return st;
+    if (rows == 0) return GF_OK;
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = gf::check_tables(ctx, who, rows, trow, trowf, 0);
+    if (st != GF_OK) return st;
+    void *img = nullptr;
+    if (gf::smp_split_products(ctx)) {
+        // the level's prebuilt weight images (both directions).  The builder reads the level's EIGHTEEN stacked blocks: the eight row
+        // products' first, the other ten as zeros
+        const size_t CC = (size_t)C * C, img_bytes = gf::align_up(gf::smp_split_image_bytes(), 256);
+        st = gf::ensure_ws(ctx, img_bytes + sizeof(float) * 18 * CC + 256);
+        if (st != GF_OK) return st;
+        img = ctx->ws;
+        float *w18 = reinterpret_cast<float *>(static_cast<char *>(ctx->ws) + img_bytes);
+        GF_HIP_TRY(ctx, hipMemcpyAsync(w18, Wst, sizeof(float) * 8 * CC, hipMemcpyDeviceToDevice, ctx->stream));
+        GF_HIP_TRY(ctx, hipMemsetAsync(w18 + 8 * CC, 0, sizeof(float) * 10 * CC, ctx->stream));
+        const float *wp = w18, *xp = nx == 3 ? X : nullptr;
+        st = gf::smp_split_build_images(ctx, &wp, &img, 1, C, &xp);
+        if (st != GF_OK) return st;
+    }
+    return gf::smp_rowpanel_products_c64(ctx, backward == 0, A, rowfac, Wst, Out, rows, trow, trowf, skip_zero_grads != 0, img, C, nf, nx);
+}
+
+gf_status gf_smp_level_wgrad_ex_f32(gf_ctx *ctx, int C, int nf, int nx, int rows, const float *T, const float *dO, const float *rowfac,
+                                    const int *trow, const int *trowf, float *dWst, float *dX) {
+    static const char *who = "gf_smp_level_wgrad_ex_f32";
+    if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
+    if (rows < 1 || !T || !dO || !rowfac || !trow || !dWst) return fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
+    if (nx == 3 && !dX) return fail(ctx, GF_ERR_INVALID, "%s: three extra products without a place for their gradients", who);
+    gf_status st = gf::check_variant(ctx, who, C, nf, nx, false);
+    if (st != GF_OK) return st;
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = gf::check_tables(ctx, who, rows, trow, trowf, gf::kGatherWindow);
+    if (st != GF_OK) return st;
+    // workspace: the eight products' partial images (one set per workgroup, and the fold's second stage), the extra products', the
+    // scratch words of the column bounds, three words of row-factor maxima
+    const size_t CC = (size_t)C * C;
+    const int splits = gf::smp_wgrad_all_splits(ctx, rows);
+    const size_t images = (size_t)splits + (splits + 31) / 32, words = gf::smp_wgrad_all_words();
+    st = gf::ensure_ws(ctx, sizeof(float) * (images * 11 * CC + words + 4) + 256);
+    if (st != GF_OK) return st;
+    float *part = static_cast<float *>(ctx->ws), *xpart = part + images * 8 * CC;
+    unsigned *bw = reinterpret_cast<unsigned *>(xpart + images * 3 * CC), *rmax = bw + words;
+    const unsigned *chan = nullptr;
+    if (nf == 8) {
+        // per-product row factors: the kernel takes the level's bounds, not exact ones.  Any upper bound will do: chan = the largest
+        // magnitude of every channel over the four blocks of T | over the two of dO (widened by the factors of products 3 and 4),
+        // smax = 1, row_max = the largest factors that ride on tot / on tr
+        GF_HIP_TRY(ctx, hipMemsetAsync(bw, 0, sizeof(unsigned) * (words + 4), ctx->stream));
+        for (int k = 0; k < 4; ++k) {
+            st = gf::smp_wgrad_channel_maxima_ld(ctx, T + k * C, rows, 4 * C, dO + (k & 1) * C, k < 2 ? rows : 0, 2 * C, C, bw);
+            if (st != GF_OK) return st;
+        }
+        GF_LAUNCH(ctx, "smpf_colmax", gf::rowfac8_absmax, dim3(64), dim3(256), 0, rowfac, rows, rmax);
+        GF_LAUNCH(ctx, "smpf_colmax", gf::scale_words, dim3(1), dim3(64), 0, bw + C, C, rmax + 2);
+        chan = bw;
+    }
+    st = gf::smp_wgrad_partials_all(ctx, T, dO, rowfac, rows, splits, part, trow, trowf, bw, chan, 1.f, chan ? rmax : nullptr, nf, C,
+                                    nx == 3 ? xpart : nullptr);
+    if (st != GF_OK) return st;
+    st = gf::splitk_fold(ctx, part, dWst, 8 * CC, splits, 0);
+    if (st != GF_OK || nx != 3) return st;
+    return gf::splitk_fold(ctx, xpart, dX, 3 * CC, splits, 0);
 }
 
 }  // extern "C"

@@ -331,6 +331,34 @@ gf_status gf_smp_level_products_f32(gf_ctx *ctx, int backward, int rows, const f
                                     const int *trow, float *Out);
 gf_status gf_smp_level_wgrad_f32(gf_ctx *ctx, int rows, const float *T, const float *dO, const float *rowscale, const int *trow,
                                  float *dWst);
+/* The same products in every variant the fused level has: C = 64, 32 or 16 channels (blocks of C columns: T [rows][4 C], O / dO
+ * [rows][2 C], Wst [8][C][C]; forward A = T -> Out = O, backward A = dO -> Out = dT), with
+ *   nf = 2: rowfac [rows][2] = (tot, tr) as above;   nf = 8 (C = 32, 16): rowfac [rows][8] = one factor per stacked product 0..7 --
+ *           the plain (tot, tot, tr, 1, 1, 1, 1, 1) times the node's slice-dropout factors -- in place of tot / tr / 1 above.  The factors
+ *           of a row and of its transposed row must agree in product 7 (they belong to one node);
+ *   nx = 3 (C = 32, 16, nf = 2): three extra products with X [3][C][C] = (X_a, X_b, X_c), SMP_2D_ver7's:
+ *           O_loc += S_ab X_a + S_bc X_b + tr S_bc X_c,  dS_ab += L X_a^T,  dS_bc += L X_b^T + tr L X_c^T,
+ *           dX = (S_ab^T L, S_bc^T L, S_bc^T (tr L));   nx = 0: X / dX may be NULL;
+ *   trowf (or NULL): the level's PACKED table.  The low 29 bits of an entry are trow; bit 31 = the row's S_ab / T6 blocks hold data,
+ *           bit 30 = the S_ab block of the TRANSPOSED row does (= that row's bit 31), bit 29 = the row's S_bc / T10 blocks hold data.
+ *           A block whose bit is clear is never read and counts as zero.  The product kernels take the table for levels of fewer
+ *           than 2^29 rows, the weight gradients for fewer than 2^28, and neither with GF_SMP_MASK_ZEROS=0;
+ *   skip_zero_grads (backward, with trowf): the dS_ab / dT6 blocks of rows without bit 31 are NOT written (gradients of structural
+ *           zeros), and dO of a row without bit 29 (no source covers it: nothing to back-propagate) counts as zero.  This relies
+ *           on the level's structure: bit 31 implies bit 29, and bit 29 is the same for a row and its transposed row.
+ * The weight gradients exist at C = 32 and 16 (gf_smp_level_wgrad_f32 is the C = 64 kernel); with nf = 2 the operand columns take
+ * their exponents from exact column maxima, with nf = 8 from per-channel upper bounds the operator derives from the operands.
+ * Their gathered operand dU[trow] is fetched through a window of 64 x 64 rows on either side of the row's 16-row slice -- in a
+ * level a transposed row lies inside its own node, at most (s - 1)^2 rows away -- and a row further off would silently load zeros:
+ * that is a property of the level, so this operator checks trow on the host (one blocking copy of the tables per call; both
+ * operators also refuse a trow outside the matrix, and a trowf whose low bits differ from trow) and answers GF_ERR_INVALID.
+ * Combinations the kernels do not have are GF_ERR_UNSUPPORTED before anything is launched: nx = 3 with nf = 8, nx = 3 or nf = 8
+ * at C = 64, and C != 64 on the fp32 pipe (GF_SMP_SPLIT=0 / GF_OPT_SMP_FP32_PRODUCTS).  The context stays usable after a refusal. */
+gf_status gf_smp_level_products_ex_f32(gf_ctx *ctx, int backward, int C, int nf, int nx, int rows, const float *A, const float *rowfac,
+                                       const float *Wst, const float *X, const int *trow, const int *trowf, int skip_zero_grads,
+                                       float *Out);
+gf_status gf_smp_level_wgrad_ex_f32(gf_ctx *ctx, int C, int nf, int nx, int rows, const float *T, const float *dO, const float *rowfac,
+                                    const int *trow, const int *trowf, float *dWst, float *dX);
 /* Device memory of the handle's buffer pool: bytes held by the current batch, and bytes the pool keeps in total (idle
  * blocks included).  Sizing aid for batch selection (GraphFlow has no counterpart: its tensors live in host `new[]`). */
 gf_status gf_smp_device_bytes(const gf_smp *smp, size_t *in_use, size_t *reserved);

@@ -19,7 +19,22 @@ output columns (so those outputs are made of the small entries alone), all with 
     2^24 : 1           <= 1e-5  (asserted)            <= 1e-5  (asserted)
 
 The fp32 pipe (GF_SMP_SPLIT=0 / gf_ctx_set_option(GF_OPT_SMP_FP32_PRODUCTS), same entry points, timed beside the split step by
-bench.py) is held to the same bounds.  DESIGN.md section 5 states the same."""
+bench.py) is held to the same bounds.  DESIGN.md section 5 states the same.
+
+The other variants of the same kernels (gf_smp_level_products_ex_f32 / gf_smp_level_wgrad_ex_f32) are held to the same 1e-5 by
+tests/test_level_ops_ex_gpu.py, per (row, block of C columns) and per (weight-gradient block, row), against tests/level_ref.py.
+Measured worst errors (plain and packed tables, a level of nodes with 1 .. 64 positions in both node orders):
+
+    variant                 forward    backward   (skip_zero_grads)   weight gradients   dX
+    C = 64, nf = 2          3.2e-7     3.7e-7     3.1e-7              --                 --       (fp32 pipe: 1.6e-6 / 1.7e-6)
+    C = 32, nf = 2          3.2e-7     3.9e-7     3.9e-7              5.5e-7             --
+    C = 32, nf = 8          2.8e-7     3.0e-7     2.6e-7              4.5e-7             --
+    C = 32, nf = 2, nx = 3  3.9e-7     3.5e-7     3.5e-7              4.5e-7             4.7e-7
+    C = 16, nf = 2          4.3e-7     5.0e-7     5.0e-7              5.6e-7             --
+    C = 16, nf = 8          4.1e-7     4.0e-7     3.6e-7              4.5e-7             --
+    C = 16, nf = 2, nx = 3  3.8e-7     4.0e-7     3.5e-7              5.2e-7             5.9e-7
+    ragged rows 1 .. 80     <= 3.1e-7  <= 3.1e-7  <= 3.0e-7           <= 6.0e-7          <= 4.1e-7
+    1e6 : 1 in a block      4.5e-7     4.0e-7     --                  C = 32: 4.4e-7, C = 16: 5.1e-7 (one molecule 1e6 : 1)"""
 import ctypes as C
 
 import numpy as np
