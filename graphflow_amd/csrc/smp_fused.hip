@@ -1720,7 +1720,7 @@ gf_status smp_fused_forward_level(gf_smp *s, int l, const float *Kl, const float
         };
         if (smp_c64_kernels(s)) {
             st = smp_rowpanel_products_c64(ctx, true, T, drop ? d.rowfac8 : d.rowscale, d.Wst, O, rows, d.trow, d.trowf, false,
-                                           d.wimg_ready ? d.wimg : nullptr, C, drop ? 8 : 2, smp_extras_in_kernel(s, l) ? 3 : 0);  // weights in LDS
+                                           d.wimg_ready ? d.wimg : nullptr, C, drop ? 8 : 2, smp_extras_in_kernel(s, l) ? 3 : 0, d.rowcls);  // weights in LDS
             if (st != GF_OK) return st;
         } else if (gemm_grouped_supported(sp, 3, false, false)) {
             st = gemm_grouped_rows(ctx, false, false, sp, 3, rows);
@@ -1991,7 +1991,7 @@ gf_status smp_fused_backward_level_grouped(gf_smp *s, int l, float *dKl, float *
         // (with the consumer gather reading dT, the gradients of the structurally-zero S_ab / T6 rows have no reader: not written)
         st = smp_rowpanel_products_c64(ctx, false, dO, drop ? d.rowfac8 : d.rowscale, d.Wst, dT, rows, ocols == 2 ? d.trow : nullptr, d.trowf,
                                        smp_fused_gather_enabled(s, l), d.wimg_ready ? d.wimg : nullptr, C, drop ? 8 : 2,
-                                       (ocols == 2 && smp_extras_in_kernel(s, l)) ? 3 : 0);
+                                       (ocols == 2 && smp_extras_in_kernel(s, l)) ? 3 : 0, d.rowcls);
         x_bwd_done = ocols == 2 && smp_extras_in_kernel(s, l);
         if (st != GF_OK) return st;
     } else {

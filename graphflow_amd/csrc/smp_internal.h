@@ -44,12 +44,16 @@ gf_status gemm_grouped_splitk(gf_ctx *ctx, const GemmSpec *specs, int n, int row
 gf_status smp_rowpanel_products_c64(gf_ctx *ctx, bool forward, const float *A, const float *rowscale, const float *Wst, float *Out,
                                     int rows, const int *trow, const int *trowf = nullptr, bool skip_zero_grads = false,
                                     const void *wimg = nullptr, int C = 64,   // C = 32 (round 4): split products with prebuilt images only
-                                    int nf = 2, int nx = 0);   // row factors per row of `rowscale`: 2 = (tot, tr); 8 = one per product (slice dropout, C = 32)
+                                    int nf = 2, int nx = 0,   // row factors per row of `rowscale`: 2 = (tot, tr); 8 = one per product (slice dropout, C = 32)
+                                    const int *rowcls = nullptr);   // the table's row classes (C = 64 with trowf: panels of one class, see smp_rowpanel_split)
 // the compact-layout products on the f16 matrix pipe with two-half fp32 operands (smp_level_c64_split.hip; GF_SMP_SPLIT=0: fp32 MFMA)
 bool smp_split_products(const gf_ctx *ctx);
 gf_status smp_rowpanel_split_c64(gf_ctx *ctx, bool forward, const float *A, const float *rowscale, const float *Wst, float *Out,
                                  int rows, const int *trow, int cus, const int *trowf = nullptr, bool skip_zero_grads = false,
-                                 const void *wimg = nullptr, int C = 64, int nf = 2, int nx = 0);
+                                 const void *wimg = nullptr, int C = 64, int nf = 2, int nx = 0, const int *rowcls = nullptr);
+// the row classes of a level's packed table (smp_prepare.hip: row_class_count): buffer size in ints, and the builder
+size_t smp_row_class_ints(int rows);
+gf_status smp_build_row_classes(gf_ctx *ctx, hipStream_t stream, const int *trowf, int rows, int *buf);
 // the split kernels' weight images of a level (both directions), built once per forward pass (smp_level_c64_split.hip)
 size_t smp_split_image_bytes();
 gf_status smp_split_build_images(gf_ctx *ctx, const float *const *Wst, void *const *img, int n, int C = 64, const float *const *X = nullptr);
@@ -180,6 +184,7 @@ struct gf_smp {
         bool wimg_ready = false;
         bool fwd_c64 = false;  // the last forward ran this level's products on the dedicated row-panel kernels (compact O = [O_loc | U])
         int *trowf = nullptr;  // [rows] trow | bit 31: rowflag of the row | bit 30: rowflag of the transposed row (smp_rowpanel_split)
+        int *rowcls = nullptr;  // C = 64: the rows with and without S_ab / T6 data as two padded lists (smp_prepare.hip: row_class_count)
         float max_tot = 0.f, max_tr = 0.f;  // largest |tot|, |tr| of the level's row factors (split-operand weight gradients' column bounds)
         const unsigned *row_max = nullptr;  // the same two as float bits in device memory when the tables are built there
         long long *pair_src_pair = nullptr, *cons_row = nullptr, *cons_pair = nullptr;  // compact diagonal path (smp_prep.h)

@@ -171,12 +171,20 @@ __global__ __launch_bounds__(kSpThreads) void smp_split_weight_images(SplitImage
 #endif
 // NX = 3 (CB <= 32, NF = 2): the extra products of SMP_2D_ver7 on the 18-slice level ride on the panel's fragments -- forward O_loc +=
 // S_ab X_a + S_bc X_b + tr S_bc X_c, backward dS_ab += L X_a^T, dS_bc += L X_b^T + tr L X_c^T -- with the images of positions 18 .. 20
-template <bool FWD, bool MASK, int CB = 64, int NF = 2, int NX = 0>
+// CLS (the backward products with CB = 64, NF = 2, NX = 0, MASK and store_mask): panels of ONE row class.  `rcls` is the level's row-class
+// buffer (smp_prepare.hip: row_class_count) -- the rows with S_ab / T6 data and the rows without as two padded lists of (row, packed
+// word) -- and a wave's panel is 32 list entries: own-class panels run the full program and store every block, absent-class panels run
+// products 4 and 1 + 6 of the eight (no dT6 / dS_ab product, no transposed dU, no store into the scratch rows).  A row's arithmetic
+// does not depend on its panel: the results are the unclassed kernel's bit for bit.  Rows of a panel are no longer adjacent, so the
+// stores take each row's address from the wave's LDS slot.  (The forward products lost on the same lists, 0.78 -> 0.99 ms: NOTES.md.)
+template <bool FWD, bool MASK, int CB = 64, int NF = 2, int NX = 0, bool CLS = false>
 __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float *__restrict__ A, const float *__restrict__ rs,
                                                                      const float *__restrict__ Wst, float *__restrict__ Out, int rows,
                                                                      const int *__restrict__ trow, int store_mask,
-                                                                     const uint4 *__restrict__ wimg) {  // or null: this direction's
+                                                                     const uint4 *__restrict__ wimg,    // or null: this direction's
                                                                      // images, built by smp_split_weight_images
+                                                                     const int *__restrict__ rcls) {    // CLS: the row classes
+    static_assert(!CLS || (!FWD && MASK && CB == 64 && NF == 2 && NX == 0), "row classes: the masked backward products at 64 channels");
     constexpr int LDA = FWD ? 4 * CB : 2 * CB, LDOUT = FWD ? 2 * CB : 4 * CB;
     // values per lane and block, k-chunks, column halves, fragment entries per block.  CB = 16 (round 5: models of up to 16 channels, the
     // reference's own nChanels = 10): one k-chunk, one column half whose columns 16..31 are zero weights and are never stored
@@ -194,6 +202,8 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
     float *facs = winv + 32;                                        // [waves][32]: row factors on their way to the C layout
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
     const int wave = tid >> 6;
+    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+    unsigned long long *rowp = reinterpret_cast<unsigned long long *>(facs + (kSpThreads / 64) * 32);   // CLS: [waves][32] where the rows of the wave's panel are stored
 
     // ---- weight images (see build_weight_images): copied from the pass's prebuilt ones, or built here
     if (wimg) {
@@ -387,7 +397,7 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
     // One panel.  On entry Ra and Rb hold (requests for) the panel's first two blocks; every other block is requested as soon as
     // a raw buffer has been split, one to three products (0.4 - 1 us) ahead of its use, and the first two blocks of the wave's
     // next panel go out behind the panel's last ones.
-    int tnext = fetch_trow(blockIdx.x * (kSpThreads / 64) + wave);
+    int tnext = CLS ? 0 : fetch_trow(blockIdx.x * (kSpThreads / 64) + wave);   // (CLS: the class lists carry the packed words)
     auto panel = [&](int p, Raw &Ra, Raw &Rb, auto full) {
         const int pn = p + nwaves;
         const int tcur = tnext;   // the transposed rows of this panel's rows (requested during the previous panel)
@@ -464,6 +474,107 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
             store_out(p, 0, acc0, acc1, full, rowbits);
         }
     };
+    if constexpr (CLS) {
+        const int n_own_p = (rcls[0] + 31) >> 5, n_tot_p = n_own_p + ((rcls[1] + 31) >> 5), n_ent = 32 * n_tot_p;
+        const int2 *ent = reinterpret_cast<const int2 *>(rcls + 4);
+        unsigned long long *myrow = rowp + wave * 32;
+        // the lane's entry of panel q (panels past the end read the last entry: requests made for them are never used): the packed
+        // word, and through *rw the row with bit 31 set on a padding entry.  Fetched a panel ahead, like fetch_trow -- and the row with it,
+        // so no block request waits for an index.
+        auto fetch_entry = [&](int q, int *rw) {
+            const int i = q * 32 + li;
+            const int2 e = ent[i < n_ent ? i : n_ent - 1];
+            *rw = e.x;
+            return e.y;
+        };
+        auto e_row = [](int rw) { return rw & 0x1fffffff; };
+        auto scale_at = [&](int row) {
+            const float2 t = *reinterpret_cast<const float2 *>(rs + (size_t)row * 2);
+            RowFac r;
+            r.f[0] = r.f[1] = t.x, r.f[2] = t.y;
+            r.f[3] = r.f[4] = r.f[5] = r.f[6] = r.f[7] = 1.f;
+            return r;
+        };
+        // where the lane's row is stored (a padding entry: one of the scratch rows), on its way to the C/D layout like the row factors
+        auto post_rows = [&](int rw) {
+            __builtin_amdgcn_wave_barrier();
+            myrow[li] = reinterpret_cast<unsigned long long>(rw < 0 ? sp_dump + li * 64 : Out + (size_t)e_row(rw) * LDOUT);
+            __builtin_amdgcn_wave_barrier();
+        };
+        auto store_rows = [&](int o, const f16v &acc0, const f16v &acc1) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const u64x2 a = *reinterpret_cast<const u64x2 *>(myrow + 8 * g + 4 * lh), b = *reinterpret_cast<const u64x2 *>(myrow + 8 * g + 4 * lh + 2);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float *dst = reinterpret_cast<float *>(j < 2 ? a[j & 1] : b[j & 1]) + o * CB + li;
+                    gf_st_s<2>(dst, acc0[4 * g + j]);
+                    gf_st_s<2>(dst + 32, acc1[4 * g + j]);
+                }
+            }
+        };
+        int p = blockIdx.x * (kSpThreads / 64) + wave;
+        int rnext, tn = fetch_entry(p, &rnext);
+        Raw Ra, Rb;   // on entry of a panel: Ra = L, Rb = dU (of a row no source covers: zeros, see `panel`)
+        load_raw_at(Rb, e_row(rnext), 1, t_bc(tn));
+        load_raw_at(Ra, e_row(rnext), 0, t_bc(tn));
+        auto panel_own = [&](int q) {   // the program of `panel` below, its rows taken from the list; every row stores all four blocks
+            const int qn = q + nwaves, rcur = rnext, tcur = tn;
+            tn = fetch_entry(qn, &rnext);
+            const RowFac sc = scale_at(e_row(rcur));
+            post_rows(rcur);
+            f16v acc0, acc1;
+            Spl X, Y, Z;
+            float iX, iY, iZ;
+            split_blk(Ra, X, iX);
+            split_blk(Rb, Y, iY);
+            clear(acc0, acc1);
+            prod(X, iX * sc.f[3], 3, acc0, acc1);
+            store_rows(2, acc0, acc1);
+            clear(acc0, acc1);
+            prod(X, iX * sc.f[4], 4, acc0, acc1);
+            store_rows(3, acc0, acc1);
+            clear(acc0, acc1);
+            prod(X, iX * sc.f[1], 1, acc0, acc1);
+            prod(Y, iY * sc.f[6], 6, acc0, acc1);
+            store_rows(1, acc0, acc1);
+            load_raw_at(Ra, t_row(tcur), 1, t_own(tcur));  // dU at the transposed rows
+            load_raw_at(Rb, e_row(rnext), 1, t_bc(tn));    // dU of the next panel
+            clear(acc0, acc1);
+            prod(X, iX * sc.f[0], 0, acc0, acc1);
+            prod(X, iX * sc.f[2], 2, acc0, acc1);
+            prod(Y, iY * sc.f[5], 5, acc0, acc1);
+            split_blk(Ra, Z, iZ);
+            load_raw_at(Ra, e_row(rnext), 0, t_bc(tn));    // L of the next panel
+            prod(Z, iZ * sc.f[7], 7, acc0, acc1);
+            store_rows(0, acc0, acc1);
+        };
+        auto panel_absent = [&](int q) {   // rows whose S_ab / T6 blocks are structural zeros: dT10 = 4 and dS_bc = 1 + 6 are all they store
+            const int qn = q + nwaves, rcur = rnext;
+            tn = fetch_entry(qn, &rnext);
+            const RowFac sc = scale_at(e_row(rcur));
+            post_rows(rcur);
+            f16v acc0, acc1;
+            Spl X, Y;
+            float iX, iY;
+            split_blk(Ra, X, iX);
+            split_blk(Rb, Y, iY);
+            load_raw_at(Rb, e_row(rnext), 1, t_bc(tn));
+            load_raw_at(Ra, e_row(rnext), 0, t_bc(tn));
+            clear(acc0, acc1);
+            prod(X, iX * sc.f[4], 4, acc0, acc1);
+            store_rows(3, acc0, acc1);
+            clear(acc0, acc1);
+            prod(X, iX * sc.f[1], 1, acc0, acc1);
+            prod(Y, iY * sc.f[6], 6, acc0, acc1);
+            store_rows(1, acc0, acc1);
+        };
+        // own panels first, absent panels (three products of eight, two stores of four) behind them, dealt from one range: the
+        // workgroups stay balanced
+        for (; p < n_own_p; p += nwaves) panel_own(p);
+        for (; p < n_tot_p; p += nwaves) panel_absent(p);
+        return;
+    }
     if constexpr (CB <= GF_SP_WHOLE_PANEL) {
         // Sixteen channels (round 5): an operand block is 2 KB per wave and eight registers per lane, so two blocks in flight per wave
         // (what the schedule above keeps at 64 channels, where a block is 8 KB) leave the memory system idle -- 3 TB/s.  Here ALL of
@@ -1446,13 +1557,14 @@ struct RowpanelArgs {
     int store_mask;
     const uint4 *img;   // this direction's weight images, or null
 };
-template <bool F, bool M, int CB, int NF, int NX>
-static gf_status launch_rowpanel_split(gf_ctx *ctx, const RowpanelArgs &a) {
-    const size_t lds = 2 * (size_t)(8 + NX) * (CB >= 32 ? CB / 32 : 1) * (CB / 16) * 64 * 16 + 32 * sizeof(float) + (kSpThreads / 64) * 32 * sizeof(float);
-    gf_status st = opt_in_lds(ctx, smp_rowpanel_split<F, M, CB, NF, NX>, lds);
+template <bool F, bool M, int CB, int NF, int NX, bool CLS = false>
+static gf_status launch_rowpanel_split(gf_ctx *ctx, const RowpanelArgs &a, const int *rcls = nullptr) {
+    const size_t lds = 2 * (size_t)(8 + NX) * (CB >= 32 ? CB / 32 : 1) * (CB / 16) * 64 * 16 + 32 * sizeof(float) + (kSpThreads / 64) * 32 * sizeof(float) +
+                       (CLS ? (kSpThreads / 64) * 32 * sizeof(float *) : 0);
+    gf_status st = opt_in_lds(ctx, smp_rowpanel_split<F, M, CB, NF, NX, CLS>, lds);
     if (st != GF_OK) return st;
-    GF_LAUNCH(ctx, F ? "smpf_products_fwd" : "smpf_products_bwd", (smp_rowpanel_split<F, M, CB, NF, NX>), dim3((unsigned)a.grid), dim3(kSpThreads),
-              lds, a.A, a.rowscale, a.Wst, a.Out, a.rows, a.trow, a.store_mask, a.img);
+    GF_LAUNCH(ctx, F ? "smpf_products_fwd" : "smpf_products_bwd", (smp_rowpanel_split<F, M, CB, NF, NX, CLS>), dim3((unsigned)a.grid), dim3(kSpThreads),
+              lds, a.A, a.rowscale, a.Wst, a.Out, a.rows, a.trow, a.store_mask, a.img, rcls);
     return GF_OK;
 }
 template <int CB, int NF, int NX = 0>
@@ -1465,9 +1577,15 @@ static gf_status launch_rowpanel_split(gf_ctx *ctx, bool forward, bool mask, con
 // level): forward O from T = [S_ab|S_bc|T6|T10], or backward dT from dO.  Every output element is produced by one wave in a
 // fixed order: results do not depend on the grid size.
 gf_status smp_rowpanel_split_c64(gf_ctx *ctx, bool forward, const float *A, const float *rowscale, const float *Wst, float *Out,
-                                 int rows, const int *trow, int cus, const int *trowf, bool skip_zero_grads, const void *wimg, int C, int nf, int nx) {
+                                 int rows, const int *trow, int cus, const int *trowf, bool skip_zero_grads, const void *wimg, int C, int nf, int nx,
+                                 const int *rowcls) {
     const int per = kSpThreads / 64;
-    const int npanels = (rows + 31) / 32;
+    // Panels of one row class (see the kernel): the masked backward products at C = 64 with the level's class lists, when the gradients
+    // of structural zeros are skipped -- otherwise every row runs the full program and writes all four blocks, and the classes buy
+    // nothing.  GF_SMP_ROW_CLASSES=0 (read per call): the unclassed kernel.
+    const bool classed = rowcls && !forward && skip_zero_grads && C == 64 && nf == 2 && nx == 0 && packed_rows(trowf, rows, 1 << 29) &&
+                         !env_is("GF_SMP_ROW_CLASSES", '0');
+    const int npanels = (rows + 31) / 32 + (classed ? 1 : 0);   // (two padded lists: one panel more at the most)
     const int want = (npanels + per - 1) / per;
     // C = 64: one persistent workgroup per CU (the weight images take 128 KB of LDS); C = 32 (32 KB of images): two
     const int slots = C == 64 ? cus : 2 * cus;   // (C = 32 / 16: one or two per CU measured equal)
@@ -1485,7 +1603,9 @@ gf_status smp_rowpanel_split_c64(gf_ctx *ctx, bool forward, const float *A, cons
     if (nf == 8)   // (per-product row factors: the slice-dropout towers, computed at 32 or 16 channels)
         return C == 32 ? launch_rowpanel_split<32, 8>(ctx, forward, mask, a) : launch_rowpanel_split<16, 8>(ctx, forward, mask, a);
     switch (C) {
-    case 64: return launch_rowpanel_split<64, 2>(ctx, forward, mask, a);
+    case 64:
+        if (classed) return launch_rowpanel_split<false, true, 64, 2, 0, true>(ctx, a, rowcls);
+        return launch_rowpanel_split<64, 2>(ctx, forward, mask, a);
     case 32: return launch_rowpanel_split<32, 2>(ctx, forward, mask, a);
     case 16: return launch_rowpanel_split<16, 2>(ctx, forward, mask, a);
     }

@@ -120,12 +120,22 @@ gf_status gf_smp_level_products_ex_f32(gf_ctx *ctx, int backward, int C, int nf,
     st = gf::check_tables(ctx, who, rows, trow, trowf, 0);
     if (st != GF_OK) return st;
     void *img = nullptr;
+    const int *rowcls = nullptr;
     if (gf::smp_split_products(ctx)) {
         // the level's prebuilt weight images (both directions).  The builder reads the level's EIGHTEEN stacked blocks: the eight row
         // products' first, the other ten as zeros
         const size_t CC = (size_t)C * C, img_bytes = gf::align_up(gf::smp_split_image_bytes(), 256);
-        st = gf::ensure_ws(ctx, img_bytes + sizeof(float) * 18 * CC + 256);
+        // ... and, for a packed table at C = 64, the table's row classes behind them (the level builds them once per batch)
+        const size_t w_bytes = gf::align_up(sizeof(float) * 18 * CC, 256);
+        const bool classes = trowf && C == 64 && rows < (1 << 29);
+        st = gf::ensure_ws(ctx, img_bytes + w_bytes + (classes ? sizeof(int) * gf::smp_row_class_ints(rows) : 0) + 256);
         if (st != GF_OK) return st;
+        if (classes) {
+            int *buf = reinterpret_cast<int *>(static_cast<char *>(ctx->ws) + img_bytes + w_bytes);
+            st = gf::smp_build_row_classes(ctx, ctx->stream, trowf, rows, buf);
+            if (st != GF_OK) return st;
+            rowcls = buf;
+        }
         img = ctx->ws;
         float *w18 = reinterpret_cast<float *>(static_cast<char *>(ctx->ws) + img_bytes);
         GF_HIP_TRY(ctx, hipMemcpyAsync(w18, Wst, sizeof(float) * 8 * CC, hipMemcpyDeviceToDevice, ctx->stream));
@@ -134,7 +144,14 @@ gf_status gf_smp_level_products_ex_f32(gf_ctx *ctx, int backward, int C, int nf,
         st = gf::smp_split_build_images(ctx, &wp, &img, 1, C, &xp);
         if (st != GF_OK) return st;
     }
-    return gf::smp_rowpanel_products_c64(ctx, backward == 0, A, rowfac, Wst, Out, rows, trow, trowf, skip_zero_grads != 0, img, C, nf, nx);
+    return gf::smp_rowpanel_products_c64(ctx, backward == 0, A, rowfac, Wst, Out, rows, trow, trowf, skip_zero_grads != 0, img, C, nf, nx, rowcls);
+}
+
+gf_status gf_smp_level_row_classes(gf_ctx *ctx, int rows, const int *trowf, int *lists) {
+    if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
+    if (rows < 1 || rows >= (1 << 29) || !trowf || !lists) return fail(ctx, GF_ERR_INVALID, "gf_smp_level_row_classes: bad argument");
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return gf::smp_build_row_classes(ctx, ctx->stream, trowf, rows, lists);
 }
 
 gf_status gf_smp_level_wgrad_ex_f32(gf_ctx *ctx, int C, int nf, int nx, int rows, const float *T, const float *dO, const float *rowfac,

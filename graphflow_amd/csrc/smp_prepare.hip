@@ -396,6 +396,64 @@ __global__ void build_trow(int *__restrict__ trow, const int *__restrict__ node_
     }
 }
 
+// ---- row classes of a level (smp_rowpanel_split, CLS): the rows whose S_ab / T6 blocks hold data (bit 31 of the packed table) and the
+// rows where they are structural zeros, as two lists in ascending row order, each padded to a multiple of 32 entries so that a 32-row
+// panel of the product kernels holds rows of ONE class.  Buffer (ints): [0] own rows, [1] absent rows, [2..3] unused; from int 4 on the
+// entries (row, the row's packed word) -- the own list, its padding, the absent list, its padding; behind room for rows + 64 entries
+// the scratch words of the scan.  A padding entry repeats the last entry of its class with bit 31 of the row set: the kernel loads
+// that row and stores into its scratch rows.  A stable partition in three launches: own rows per 1,024-row block, an exclusive scan of
+// the block counts, the scatter.
+constexpr int kRcBlock = 1024;
+__global__ __launch_bounds__(kRcBlock) void row_class_count(const int *__restrict__ trowf, int rows, int *__restrict__ blockcnt) {
+    const int r = blockIdx.x * kRcBlock + threadIdx.x;
+    const int n = __syncthreads_count(r < rows && trowf[r] < 0);
+    if (threadIdx.x == 0) blockcnt[blockIdx.x] = n;
+}
+__global__ __launch_bounds__(kRcBlock) void row_class_scan(int *__restrict__ blockcnt, int nb, int rows, int *__restrict__ hdr) {
+    __shared__ int part[kRcBlock];
+    const int tid = threadIdx.x, per = (nb + kRcBlock - 1) / kRcBlock;
+    const int i0 = tid * per < nb ? tid * per : nb, i1 = i0 + per < nb ? i0 + per : nb;
+    int sum = 0;
+    for (int i = i0; i < i1; ++i) sum += blockcnt[i];
+    part[tid] = sum;
+    __syncthreads();
+    for (int d = 1; d < kRcBlock; d <<= 1) {
+        const int v = tid >= d ? part[tid - d] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    int run = part[tid] - sum;
+    for (int i = i0; i < i1; ++i) {
+        const int c = blockcnt[i];
+        blockcnt[i] = run;
+        run += c;
+    }
+    if (tid == kRcBlock - 1) hdr[0] = part[tid], hdr[1] = rows - part[tid], hdr[2] = hdr[3] = 0;
+}
+__global__ __launch_bounds__(kRcBlock) void row_class_fill(const int *__restrict__ trowf, int rows, const int *__restrict__ blockoff,
+                                                           const int *__restrict__ hdr, int2 *__restrict__ ent) {
+    __shared__ int wcnt[kRcBlock / 64];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int r = blockIdx.x * kRcBlock + tid;
+    const int t = r < rows ? trowf[r] : 0;
+    const bool own = t < 0;
+    const unsigned long long b = __ballot(own);
+    if (lane == 0) wcnt[w] = __popcll(b);
+    __syncthreads();
+    int before = blockoff[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));   // own rows in front of row r
+    for (int i = 0; i < w; ++i) before += wcnt[i];
+    if (r >= rows) return;
+    const int n_own = hdr[0], n_abs = hdr[1], own_pad = (n_own + 31) & ~31;
+    const int k = own ? before : r - before;   // the row's rank in its class
+    const int at = own ? k : own_pad + k;
+    ent[at] = make_int2(r, t);
+    if (k == (own ? n_own : n_abs) - 1) {   // the last row of a class fills the class's padding
+        const int end = own ? own_pad : own_pad + ((n_abs + 31) & ~31);
+        for (int i = at + 1; i < end; ++i) ent[i] = make_int2((int)((unsigned)r | 0x80000000u), t);
+    }
+}
+
 // ---- gf_smp_prepare: the steps ------------------------------------------------------------------------------------
 // The ONE way a batch's buffers are taken from the pool: the first failure is kept and every later request does nothing, so a step asks
 // for its buffers in order and checks `st` at its end (and before it launches anything on them).  The ORDER of the requests is behaviour:
@@ -562,6 +620,7 @@ void alloc_level_panels(Taker &t, Level &h, DevLevel &d, int l) {
     if (!(cfg.square() && smp_panel_channels(C) && h.rows < 0x7fffffffll)) return;
     t.alloc(&d.trow, (size_t)h.rows);
     t.alloc(&d.trowf, (size_t)h.rows);
+    if (C == 64 && cfg.nContractions == 18 && h.rows < (1ll << 29)) t.alloc(&d.rowcls, smp_row_class_ints((int)h.rows));   // (row classes of the masked products)
     unsigned char *img = nullptr;
     t.alloc(&img, smp_split_image_bytes());
     d.wimg = img;
@@ -696,6 +755,8 @@ gf_status build_row_tables(gf_smp *s) {
         if (st == GF_OK) st = smp_fwd_fused_build_tables(s, l, up, !merged);
         if (st != GF_OK) return st;
         if (d.trow && !merged) hipLaunchKernelGGL(build_trow, dim3(nNodes), dim3(64), 0, up, d.trow, d.node_s, d.node_row, d.pi, d.rowflag, d.trowf);
+        if (d.rowcls) st = smp_build_row_classes(s->ctx, up, d.trowf, (int)s->lay.level[l].rows, d.rowcls);
+        if (st != GF_OK) return st;
     }
     return GF_OK;
 }
@@ -739,6 +800,19 @@ gf_status alloc_readout(gf_smp *s, int nMol) {
 }
 
 }  // namespace
+
+// ints of a level's row-class buffer (see row_class_count), and its builder: three launches on `stream` behind whatever wrote trowf
+size_t smp_row_class_ints(int rows) { return 4 + 2 * ((size_t)rows + 64) + (size_t)(rows + kRcBlock - 1) / kRcBlock + 1; }
+gf_status smp_build_row_classes(gf_ctx *ctx, hipStream_t stream, const int *trowf, int rows, int *buf) {
+    if (rows < 1) return GF_OK;
+    const int nb = (rows + kRcBlock - 1) / kRcBlock;
+    int *blockcnt = buf + 4 + 2 * ((size_t)rows + 64);
+    hipLaunchKernelGGL(row_class_count, dim3(nb), dim3(kRcBlock), 0, stream, trowf, rows, blockcnt);
+    hipLaunchKernelGGL(row_class_scan, dim3(1), dim3(kRcBlock), 0, stream, blockcnt, nb, rows, buf);
+    hipLaunchKernelGGL(row_class_fill, dim3(nb), dim3(kRcBlock), 0, stream, trowf, rows, blockcnt, buf, reinterpret_cast<int2 *>(buf + 4));
+    GF_LAUNCH_CHECK(ctx, "row_class_fill");
+    return GF_OK;
+}
 }  // namespace gf
 
 using gf::fail;

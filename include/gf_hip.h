@@ -359,6 +359,14 @@ gf_status gf_smp_level_products_ex_f32(gf_ctx *ctx, int backward, int C, int nf,
                                        float *Out);
 gf_status gf_smp_level_wgrad_ex_f32(gf_ctx *ctx, int C, int nf, int nx, int rows, const float *T, const float *dO, const float *rowfac,
                                     const int *trow, const int *trowf, float *dWst, float *dX);
+/* The row classes of a level's packed table, as the backward products at C = 64 take them under skip_zero_grads (panels of 32 rows of
+ * ONE class: rows whose S_ab / T6 blocks are structural zeros run three of the eight products; GF_SMP_ROW_CLASSES=0, read per call,
+ * selects the unclassed kernel):
+ * lists (device, 4 + 2 (rows + 64) + rows / 1024 + 2 ints) receives  [0] the number of rows with bit 31, [1] of rows without, and from
+ * int 4 on entries (row, packed word): the rows with bit 31 in ascending order, padded to a multiple of 32 entries, then the rows
+ * without, padded likewise.  A padding entry repeats the last row of its class with bit 31 of the row set.  The level builds this once
+ * per gf_smp_prepare; gf_smp_level_products_ex_f32 builds it per call (the backward products under skip_zero_grads walk it).  rows < 2^29.  Asynchronous on the context's stream. */
+gf_status gf_smp_level_row_classes(gf_ctx *ctx, int rows, const int *trowf, int *lists);
 /* Device memory of the handle's buffer pool: bytes held by the current batch, and bytes the pool keeps in total (idle
  * blocks included).  Sizing aid for batch selection (GraphFlow has no counterpart: its tensors live in host `new[]`). */
 gf_status gf_smp_device_bytes(const gf_smp *smp, size_t *in_use, size_t *reserved);
