@@ -1506,8 +1506,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // GF_SMP_ROWPANEL=0 (read per call: the parity tests switch it) selects the grouped tiled GEMM launches every other channel count uses.
 // Round 4: the split-operand row-panel products also run at C = 32 (32 x 32 blocks: one column half, two k-chunks per lane; weight
 // gradients on smp_wgrad_all<32>); the fp32-pipe variants, the panel combine and the small-product kernels stay C = 64 only.
+// C = 128: the same family as four 64-channel sub-block passes per product (smp_level_c64_split.hip: W = 2), on the split pipe only and
+// for the plain 18-slice model (no towers, slice dropout or embedded ver6 / ver7 model), unless GF_SMP_C128=0 (smp_c128_switch): then the grouped GEMMs.
+static bool smp_c128_kernels(const gf_smp *s) {
+    if (s->cfg.nChanels != 128 || s->cfg.nContractions != 18 || s->cfg.physics || s->drop_on || s->n_extra || s->dup_channels) return false;
+    if (!smp_split_products(s->ctx) || !smp_c128_switch() || !s->wbound || (int)s->lv.size() <= s->cfg.nLevels) return false;
+    for (int l = 1; l <= s->cfg.nLevels; ++l)
+        if (!s->lv[l].trow || !s->lv[l].wimg) return false;   // (the transposed-row tables and the four image sets: smp_prepare.hip)
+    return true;
+}
 static bool smp_c64_kernels(const gf_smp *s) {
     if (env_is("GF_SMP_ROWPANEL", '0')) return false;
+    if (s->cfg.nChanels == 128) return smp_c128_kernels(s);
     return s->cfg.nChanels == 64 || ((s->cfg.nChanels == 32 || s->cfg.nChanels == 16) && smp_split_products(s->ctx) && s->wbound != nullptr);
 }
 // compact projected matrix O = [O_loc | U] (2C) instead of [O_loc | Z | Z'] (3C): the dedicated C = 64 product kernels gather the
@@ -1538,7 +1548,7 @@ gf_status smp_fused_stack_all(gf_smp *s, const std::vector<const float *> &K) {
     }
     // ... and the split product kernels' weight images of every level, both directions (the backward pass reuses them)
     for (int l = 1; l <= L; ++l) s->lv[l].wimg_ready = false;
-    if (smp_panel_channels(C) && smp_compact_o(s) && smp_split_products(s->ctx)) {
+    if ((smp_panel_channels(C) || C == 128) && smp_compact_o(s) && smp_split_products(s->ctx)) {
         std::vector<const float *> w, x;
         std::vector<void *> im;
         for (int l = 1; l <= L; ++l)
@@ -1904,6 +1914,10 @@ gf_status smp_fused_backward_level_grouped(gf_smp *s, int l, float *dKl, float *
         rowg.splits = splits;
         rowg.n = 8 * CC;
         used = (size_t)splits * 8 * CC;
+    } else if (stationary && C == 128) {   // four sub-block launches of the C = 64 kernel, exact column bounds (T holds its zeros at 128)
+        st = smp_wgrad_partials_c128(ctx, T, dO, d.rowscale, rows, ws, ws_floats, &rowg, d.trow, d.trowf, s->wbound + (size_t)l * smp_wgrad_c128_words());
+        if (st != GF_OK) return st;
+        used = (size_t)rowg.splits * rowg.n;
     } else if (stationary) {
         unsigned *wb = (s->wbound && ocols == 2 && smp_split_products(ctx)) ? s->wbound + (size_t)l * smp_wgrad_bound_words() : nullptr;
         if (wb && !d.dzmax) wb = nullptr;
@@ -2086,7 +2100,7 @@ gf_status smp_fused_backward_level(gf_smp *s, int l, const float *Kl, float *dKl
     // The forward pass wrote O in the layout of ITS product kernels; at C = 32 those exist on the split path only, so an option flipped
     // between the two passes would make this sweep read dO in the other layout: refused instead of differentiated wrongly.
     if (d.fwd_c64 != smp_c64_kernels(s))
-        return fail(ctx, GF_ERR_INVALID, "gf_smp_backward: the product kernels' option (GF_OPT_SMP_FP32_PRODUCTS / GF_SMP_SPLIT / GF_SMP_ROWPANEL) "
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_backward: the product kernels' option (GF_OPT_SMP_FP32_PRODUCTS / GF_SMP_SPLIT / GF_SMP_ROWPANEL / GF_SMP_C128) "
                                          "changed since the forward pass of level %d", l);
     float *dzmax = (s->wbound && d.dzmax && d.fwd_c64) ? d.dzmax : (float *)nullptr;
     // round 5: on the forward's row panels where they exist (one wave per panel, every request up front; else the workgroup-per-(node,

@@ -55,7 +55,7 @@ gf_status smp_rowpanel_split_c64(gf_ctx *ctx, bool forward, const float *A, cons
 size_t smp_row_class_ints(int rows);
 gf_status smp_build_row_classes(gf_ctx *ctx, hipStream_t stream, const int *trowf, int rows, int *buf);
 // the split kernels' weight images of a level (both directions), built once per forward pass (smp_level_c64_split.hip)
-size_t smp_split_image_bytes();
+size_t smp_split_image_bytes(int C = 64);   // (C = 128: four sets, one per 64 x 64 sub-block of the 128 x 128 weight blocks)
 gf_status smp_split_build_images(gf_ctx *ctx, const float *const *Wst, void *const *img, int n, int C = 64, const float *const *X = nullptr);
 // weight gradients of a fused level at C = 32 or (round 5) 16 (smp_wgrad_all<C>): partial images of 8 x C x C floats per workgroup
 gf_status smp_wgrad_partials_all(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int splits, float *part,
@@ -78,6 +78,10 @@ struct WgradScales {
 };
 gf_status smp_wgrad_partials_split_c64(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int kchunk,
                                        int splits, float *part, const int *trow, const WgradScales &ws, const int *trowf = nullptr);
+// weight gradients of a fused level at C = 128: four sub-block launches of the C = 64 kernel into partial images of 8 x 128 x 128 floats
+size_t smp_wgrad_c128_words();
+gf_status smp_wgrad_partials_c128(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, float *part, size_t part_floats,
+                                  FoldGroup *out, const int *trow, const int *trowf, unsigned *words);
 size_t smp_wgrad_bound_words();
 gf_status smp_wgrad_channel_maxima(gf_ctx *ctx, const float *fprev, long long prev_rows, const float *dsrc, long long drows, unsigned *words);
 size_t smp_wgrad_bound_words_exact();
@@ -255,6 +259,11 @@ struct gf_smp {
 namespace gf {
 // channel counts the row-panel kernel family of the fused level is built for (models are padded to the next one: gf_smp_create)
 inline bool smp_panel_channels(int C) { return C == 64 || C == 32 || C == 16; }
+// A plain 18-slice 128-channel handle runs its block products as 64-channel sub-block passes of that family (smp_fused.hip:
+// smp_c128_kernels) unless GF_SMP_C128=0.  Read when a batch is prepared -- the transposed-row tables and the four image sets are taken
+// only then: a handle prepared under =0 is what it was before the path existed -- and per call: a pass runs the sub-block kernels when
+// neither saw the 0.
+inline bool smp_c128_switch() { return !env_is("GF_SMP_C128", '0'); }
 // Largest receptive field a fused level takes (round 6): up to 32 positions every kernel of the level; 33 .. 64 at C = 64 -- the few such
 // nodes of a level (a 48-atom molecule's level-3 fields reach 35) run tables-forward and the two combine steps on workgroup kernels,
 // everything else is row-based and does not care (smp_fused.hip: big_part)

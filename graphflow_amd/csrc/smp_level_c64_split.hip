@@ -85,17 +85,19 @@ __device__ __attribute__((aligned(256))) float sp_dump[kSpDumpRows * 64];
 // CB = channels (64, or 32 since round 4): a block is CB x CB, a lane (row, half lh) of the A operand holds CB / 2 columns of its row,
 // i.e. NC = CB / 16 k-chunks of eight, and the output has NH = CB / 32 column halves: NH NC 64 fragment entries per block, stored at
 // a stride of 512 entries per position whatever CB is.
-template <bool FWD, int NPOS, int CB = 64>
+// LD (C = 128: a 64 x 64 sub-block of a 128 x 128 weight block, NPOS = 1): floats from one row of the block to the next
+template <bool FWD, int NPOS, int CB = 64, int LD = CB>
 __device__ __forceinline__ void build_weight_images(const float *__restrict__ Wst, uint4 *imgH, uint4 *imgL, float *winv, unsigned *wmax,
                                                     int tid) {
     constexpr int NC = CB / 16, NH = CB >= 32 ? CB / 32 : 1, E = NH * NC * 64;   // (CB = 16: one column half, columns 16..31 are zeros)
+    static_assert(LD == CB || NPOS == 1, "a sub-block is built on its own");
     if (tid < NPOS) wmax[tid] = 0u;
     __syncthreads();
 #pragma unroll 1
     for (int pos = 0; pos < NPOS; ++pos) {
         unsigned m = 0u;
         for (int i = tid; i < CB * CB; i += kSpThreads) {
-            const unsigned b = __float_as_uint(Wst[pos * CB * CB + i]) & 0x7fffffffu;
+            const unsigned b = __float_as_uint(Wst[LD == CB ? pos * CB * CB + i : (i / CB) * LD + i % CB]) & 0x7fffffffu;
             m = b > m ? b : m;
         }
         atomicMax(&wmax[pos], m);
@@ -112,7 +114,7 @@ __device__ __forceinline__ void build_weight_images(const float *__restrict__ Ws
         const float *w = Wst + pos * CB * CB;
         float v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = n >= CB ? 0.f : FWD ? w[(k0 + j) * CB + n] : w[n * CB + k0 + j];
+        for (int j = 0; j < 8; ++j) v[j] = n >= CB ? 0.f : FWD ? w[(k0 + j) * LD + n] : w[n * LD + k0 + j];
         unsigned hw[4], lw[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -133,6 +135,8 @@ constexpr int kSpImgLevels = 8;
 // (positions 18, 19, 20: the three extra products of SMP_2D_ver7 on the 18-slice level -- gf_smp::n_extra -- from their own weight blocks X)
 constexpr int kSpPos = 21, kSpStacked = 18, kSpAll = kSpPos * 512;
 constexpr int kSpImgStride = 2 * kSpAll + 6;   // uint4 per (level, direction): images, then kSpPos inverse scales in six uint4
+// C = 128: a sub-block set holds the eight row products' positions only -- imgH [kSpAll128] | imgL [kSpAll128] | eight inverse scales in two uint4
+constexpr int kSpAll128 = 8 * 512, kSpImgStride128 = 2 * kSpAll128 + 2;
 struct SplitImages {
     const float *Wst[kSpImgLevels];
     const float *X[kSpImgLevels];   // or null: no extra products
@@ -163,6 +167,23 @@ __global__ __launch_bounds__(kSpThreads) void smp_split_weight_images(SplitImage
     }
 }
 
+// C = 128: every 128 x 128 block is four 64 x 64 sub-blocks, one image SET per (reduction half i, output half j) and level -- set q = 2 i + j
+// at img + 2 q kSpImgStride128 (forward images, then backward images; positions 0..7 only: the row products', see kSpAll128).
+// Forward, set (i, j) holds W[64 i .., 64 j ..]; backward it holds the transposed sub-block (W[64 j .., 64 i ..])^T, i.e. the one that takes
+// columns [64 i, +64) of dO to columns [64 j, +64) of dT.  Workgroup (direction, level, 8 q + position).
+__global__ __launch_bounds__(kSpThreads) void smp_split_weight_images_c128(SplitImages a) {
+    __shared__ unsigned wmax[1];
+    const int q = blockIdx.z >> 3, pos = blockIdx.z & 7, i = q >> 1, j = q & 1;
+    uint4 *out = a.img[blockIdx.y] + (size_t)(2 * q + blockIdx.x) * kSpImgStride128;
+    float *winv = reinterpret_cast<float *>(out + 2 * kSpAll128) + pos;
+    const float *w = a.Wst[blockIdx.y] + (size_t)pos * 128 * 128;
+    uint4 *H = out + pos * 512, *L = out + kSpAll128 + pos * 512;
+    if (blockIdx.x == 0)
+        build_weight_images<true, 1, 64, 128>(w + (size_t)64 * i * 128 + 64 * j, H, L, winv, wmax, threadIdx.x);
+    else
+        build_weight_images<false, 1, 64, 128>(w + (size_t)64 * j * 128 + 64 * i, H, L, winv, wmax, threadIdx.x);
+}
+
 // NF (round 5): factors per row in `rs` -- 2: (tot, tr) of the row's node; 8: one factor per stacked product 0..7, i.e. (tot, tot, tr, 1, 1,
 // 1, 1, 1) times the node's slice-dropout factors of K0, K2, K6, K5, K9, K8, K12, K11 (RisiContraction_18_dropout: a dropped slice
 // of the contraction is a zero factor on its block product, GraphFlow/RisiContraction_18_dropout.h:106-132)
@@ -177,15 +198,23 @@ __global__ __launch_bounds__(kSpThreads) void smp_split_weight_images(SplitImage
 // products 4 and 1 + 6 of the eight (no dT6 / dS_ab product, no transposed dU, no store into the scratch rows).  A row's arithmetic
 // does not depend on its panel: the results are the unclassed kernel's bit for bit.  Rows of a panel are no longer adjacent, so the
 // stores take each row's address from the wave's LDS slot.  (The forward products lost on the same lists, 0.78 -> 0.99 ms: NOTES.md.)
-template <bool FWD, bool MASK, int CB = 64, int NF = 2, int NX = 0, bool CLS = false>
+// W = 2 (C = 128, CB = 64): one (i, j) pass of the four a 128 x 128 product is made of -- the rows are W times as wide, a block starts at
+// CB W blk, and the pass reads columns [a_off, +64) of its operand blocks and writes columns [out_off, +64) of its output blocks with the
+// weight images of sub-block (i, j).  ACC: the pass of the second reduction half -- its accumulators start from what the first pass stored.
+template <bool FWD, bool MASK, int CB = 64, int NF = 2, int NX = 0, bool CLS = false, int W = 1, bool ACC = false>
 __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float *__restrict__ A, const float *__restrict__ rs,
                                                                      const float *__restrict__ Wst, float *__restrict__ Out, int rows,
                                                                      const int *__restrict__ trow, int store_mask,
                                                                      const uint4 *__restrict__ wimg,    // or null: this direction's
                                                                      // images, built by smp_split_weight_images
-                                                                     const int *__restrict__ rcls) {    // CLS: the row classes
+                                                                     const int *__restrict__ rcls,      // CLS: the row classes
+                                                                     int a_off, int out_off) {          // W > 1: see above
+    static_assert(W == 1 || (CB == 64 && NF == 2 && NX == 0 && !CLS), "sub-block passes: 64-channel panels, plain row factors");
+    static_assert(W > 1 || !ACC, "");
     static_assert(!CLS || (!FWD && MASK && CB == 64 && NF == 2 && NX == 0), "row classes: the masked backward products at 64 channels");
-    constexpr int LDA = FWD ? 4 * CB : 2 * CB, LDOUT = FWD ? 2 * CB : 4 * CB;
+    constexpr int LDA = (FWD ? 4 * CB : 2 * CB) * W, LDOUT = (FWD ? 2 * CB : 4 * CB) * W, BS = CB * W;   // BS: floats from a block to the next
+    if constexpr (W == 1) a_off = out_off = 0;
+    constexpr int ALL = W == 1 ? kSpAll : kSpAll128;   // entries of one half's images in the prebuilt set
     // values per lane and block, k-chunks, column halves, fragment entries per block.  CB = 16 (round 5: models of up to 16 channels, the
     // reference's own nChanels = 10): one k-chunk, one column half whose columns 16..31 are zero weights and are never stored
     constexpr int VPL = CB / 2, NC = CB / 16, NH = CB >= 32 ? CB / 32 : 1, E = NH * NC * 64;
@@ -210,9 +239,9 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
         for (int t = tid; t < NP * E; t += kSpThreads) {   // (512 entries apart per position in the prebuilt set, whatever CB is)
             const int pos = t / E, g = (pos < 8 ? pos : kSpStacked + pos - 8) * 512 + t % E;
             imgH[t] = wimg[g];
-            imgL[t] = wimg[kSpAll + g];
+            imgL[t] = wimg[ALL + g];
         }
-        if (tid < 2) reinterpret_cast<uint4 *>(winv)[tid] = wimg[2 * kSpAll + tid];
+        if (tid < 2) reinterpret_cast<uint4 *>(winv)[tid] = wimg[2 * ALL + tid];
         if (NX > 0 && tid < NX) winv[8 + tid] = reinterpret_cast<const float *>(wimg + 2 * kSpAll)[kSpStacked + tid];
     } else {
         static_assert(E == 512 || true, "");
@@ -236,7 +265,7 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
         __builtin_amdgcn_sched_barrier(0);  // (requests stay where the schedule below puts them: hoisted to the top of the panel
                                             //  they would all be live at once)
         asm volatile("" : "+v"(src_row));   // (nor is the address arithmetic on a prefetched row index moved up to its load)
-        const float *src = A + (size_t)src_row * LDA + blk * CB + VPL * lh;
+        const float *src = A + (size_t)src_row * LDA + blk * BS + a_off + VPL * lh;
         if constexpr (MASK) src = present ? src : sp_zero_page;  // (a select on the address: same requests, same registers)
 #pragma unroll
         for (int q = 0; q < VPL / 4; ++q) R.a[q] = gf_ld_s<1>(reinterpret_cast<const f4v *>(src + 4 * q));
@@ -348,13 +377,31 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.f;
     };
+    // the accumulators of output block o of panel p at the start of its products: zeros, or (ACC) what the pass of the first reduction
+    // half stored there -- the same elements this lane stores at the end (a row the masked store sends to the scratch rows is read all the
+    // same: its sum goes nowhere)
+    auto start = [&](int p, int o, f16v &acc0, f16v &acc1, auto full) {
+        if constexpr (!ACC) {
+            clear(acc0, acc1);
+        } else {
+            const int r0 = p * 32;
+            const float *out = Out + (size_t)(r0 + 4 * lh) * LDOUT + o * BS + out_off + li;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rr = (r & 3) + 8 * (r >> 2);
+                const bool ok = decltype(full)::value || r0 + 4 * lh + rr < rows;
+                acc0[r] = ok ? out[(size_t)rr * LDOUT] : 0.f;
+                acc1[r] = ok ? out[(size_t)rr * LDOUT + 32] : 0.f;
+            }
+        }
+    };
     // C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
     // (FULL: a panel wholly inside the matrix -- unconditional stores.  A conditional store or load anywhere in the panel loop
     //  makes the compiler give up counting the memory queue at the join: it then waits for vmcnt(0), requests just issued included,
     //  before every split.  The one partial panel of the matrix runs a second copy of the panel code.)
     auto store_out = [&](int p, int o, const f16v &acc0, const f16v &acc1, auto full, unsigned rowbits = 0xffffffffu) {
         const int r0 = p * 32;
-        float *out = Out + (size_t)(r0 + 4 * lh) * LDOUT + o * CB + li;
+        float *out = Out + (size_t)(r0 + 4 * lh) * LDOUT + o * BS + out_off + li;
         if constexpr (CB < 32)   // lanes of the zero columns store into the scratch rows (a select on the address: every store is issued)
             out = li < CB ? out : sp_dump + (size_t)((r0 & 255) + 4 * lh) * 64 + li;
         if constexpr (MASK && !FWD && decltype(full)::value) {
@@ -411,13 +458,13 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
             load_raw(Ra, p, 1, t_bc(tcur));          // S_bc
             split_blk(Rb, Z, iZ);
             load_raw(Rb, p, 2, t_own(tcur));         // T6
-            clear(acc0, acc1);
+            start(p, 1, acc0, acc1, full);
             prod(X, iX * sc.f[5], 5, acc0, acc1);
             prod(Z, iZ * sc.f[7], 7, acc0, acc1);
             split_blk(Ra, Y, iY);
             prod(Y, iY * sc.f[6], 6, acc0, acc1);
             store_out(p, 1, acc0, acc1, full);
-            clear(acc0, acc1);
+            start(p, 0, acc0, acc1, full);
             prod(X, iX * sc.f[0], 0, acc0, acc1);
             prod(X, iX * sc.f[2], 2, acc0, acc1);
             prod(Y, iY * sc.f[1], 1, acc0, acc1);
@@ -443,13 +490,13 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
             // (the dS_bc / dT10 blocks of rows no source covers are stored all the same -- 8 % of the rows at level 3: masking them as
             //  well cost the kernel fifteen spills and more than it saved, 0.84 -> 0.91 ms)
             const unsigned rowbits = (MASK && store_mask) ? (unsigned)__ballot(t_own(tcur)) : 0xffffffffu;
-            clear(acc0, acc1);
+            start(p, 2, acc0, acc1, full);
             prod(X, iX * sc.f[3], 3, acc0, acc1);
             store_out(p, 2, acc0, acc1, full, rowbits);
-            clear(acc0, acc1);
+            start(p, 3, acc0, acc1, full);
             prod(X, iX * sc.f[4], 4, acc0, acc1);
             store_out(p, 3, acc0, acc1, full);
-            clear(acc0, acc1);
+            start(p, 1, acc0, acc1, full);
             prod(X, iX * sc.f[1], 1, acc0, acc1);
             prod(Y, iY * sc.f[6], 6, acc0, acc1);
             if constexpr (NX == 3) {
@@ -463,7 +510,7 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
             load_raw_at(Ra, t_row(tcur), 1, !(MASK && store_mask) || t_own(tcur));
             load_raw(Rb, pn, 1, !(MASK && store_mask) || t_bc(tnext));   // dU of the next panel (a row no source covers has nothing to
                                                                          // back-propagate: its whole dT row is a gradient of structural zeros)
-            clear(acc0, acc1);
+            start(p, 0, acc0, acc1, full);
             prod(X, iX * sc.f[0], 0, acc0, acc1);
             prod(X, iX * sc.f[2], 2, acc0, acc1);
             prod(Y, iY * sc.f[5], 5, acc0, acc1);
@@ -872,6 +919,10 @@ constexpr size_t kWsLds = 2 * (size_t)kWsStageWords * 4 + 2 * (kWsACols + kWsBCo
 __constant__ int c_ws_ablk[8] = {0, 1, 0, 2, 3, 0, 1, 0};  // S_ab, S_bc, S_ab, T6, T10, S_ab, S_bc, S_ab
 __constant__ int c_ws_bblk[8] = {1, 1, 2, 0, 0, 3, 3, 4};  // tot L, tot L, tr L, L, L, dU, dU, dU[trow]
 
+// W = 2 (C = 128): one of the four independent 64 x 64 jobs of every product, dWst[p][64 i .., 64 j ..] = A_p[:, 64 i ..]^T B_p[:, 64 j ..] -- rows W
+// times as wide, columns [a_off, +64) of the blocks of T, [b_off, +64) of the blocks of dO; the image lands at float out_off of its
+// product's 128 x 128 partial image (the four jobs fill one set of images between them).  cmax: the bounds of THIS job's columns.
+template <int W = 1>
 __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__restrict__ T, const float *__restrict__ dO,
                                                                   const float *__restrict__ rs, int rows, int kchunk,
                                                                   float *__restrict__ part, const int *__restrict__ trow,
@@ -882,7 +933,10 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
                                                                   float smax, float max_tot, float max_tr,
                                                                   const unsigned *__restrict__ row_max,   // or null: {max |tot|, max |tr|} as float bits in
                                                                   // device memory (they replace max_tot / max_tr: the device-side table builder's)
-                                                                  int packed) {  // != 0: trow is the packed table (see smp_rowpanel_split)
+                                                                  int packed,   // != 0: trow is the packed table (see smp_rowpanel_split)
+                                                                  int a_off, int b_off, int out_off) {   // W > 1: see above
+    if constexpr (W == 1) a_off = b_off = out_off = 0;
+    constexpr int LDT = 256 * W, LDO = 128 * W, BS = 64 * W, LDW = 64 * W;   // rows of T, of dO; a block to the next; rows of an image
     extern __shared__ __attribute__((aligned(16))) unsigned ws_smem[];  // stage s: A h | A l | B h | B l; then the column scales
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lg = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -977,7 +1031,8 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
         fetch_trow(m + 2, ib0, ib1);
         const long long last = kend - 1, kk = K(m) + 2 * pair;
         const int c0 = (int)(kk < last ? kk : last), c1 = (int)(kk + 1 < last ? kk + 1 : last);
-        const float *t0 = T + (size_t)c0 * 256 + 4 * a_quad, *t1 = T + (size_t)c1 * 256 + 4 * a_quad;
+        const int a_col = W == 1 ? 4 * a_quad : (a_quad >> 4) * BS + a_off + ((4 * a_quad) & 63);   // the quad's first column in its row of T
+        const float *t0 = T + (size_t)c0 * LDT + a_col, *t1 = T + (size_t)c1 * LDT + a_col;
         S.ta.v0 = gf_ld_s<4>(reinterpret_cast<const f4v *>(z0 ? sp_zero_page + 4 * q_lo : t0));
         S.ta.v1 = gf_ld_s<4>(reinterpret_cast<const f4v *>(z1 ? sp_zero_page + 4 * q_lo : t1));
 #pragma unroll
@@ -986,8 +1041,8 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
             S.f0[e] = rs[(size_t)c0 * 2 + (blk == 2)];
             S.f1[e] = rs[(size_t)c1 * 2 + (blk == 2)];
             const bool gathered = blk == 4;
-            const float *src = blk < 5 ? dO + (blk >= 3 ? 64 : 0) + 4 * b_quad(e) : T + 4 * a_quad;
-            const int ld = blk < 5 ? 128 : 256;
+            const float *src = blk < 5 ? dO + (blk >= 3 ? BS : 0) + b_off + 4 * b_quad(e) : T + a_col;
+            const int ld = blk < 5 ? LDO : LDT;
             // (the gathered dU row only meets S_ab of ITS row in product 7: a row without data skips the gather as well)
             const float *s0 = src + (size_t)(gathered ? g0 : c0) * ld, *s1 = src + (size_t)(gathered ? g1 : c1) * ld;
             S.tb[e].v0 = gf_ld_s<256>(reinterpret_cast<const f4v *>((gathered && zg0) ? sp_zero_page + 4 * q_lo : s0));
@@ -1090,7 +1145,7 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
     }
     // back to fp32 units: row k of the product is column k of its A block, column n column n of its B block.
     // C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-    float *out = part + ((size_t)blockIdx.x * 8 + wave) * 4096 + li;
+    float *out = part + ((size_t)blockIdx.x * 8 + wave) * (LDW * LDW) + out_off + li;
     const float *ia = sInv + ablk * 64, *ib = sInv + kWsACols + bblk * 64;
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
@@ -1100,7 +1155,7 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * lg;
-                out[row * 64 + 32 * nt] = acc[mt][nt][r] * (ia[row] * ub);
+                out[row * LDW + 32 * nt] = acc[mt][nt][r] * (ia[row] * ub);
             }
         }
 }
@@ -1484,6 +1539,22 @@ __global__ void wgrad_bounds_exact(const unsigned *__restrict__ mt, const unsign
     cmax[kWsACols + 192 + c] = cmax[kWsACols + 256 + c] = __float_as_uint(u);
 }
 
+// C = 128: the same for the four (i, j) jobs of smp_wgrad_split<2>: mt [512] column maxima of T [rows][512], mo [256] of dO [rows][256];
+// cmax [4][kWsACols + kWsBCols], job q = 2 i + j = blockIdx.x
+__global__ void wgrad_bounds_exact_c128(const unsigned *__restrict__ mt, const unsigned *__restrict__ mo, const unsigned *__restrict__ mx,
+                                        unsigned *__restrict__ cmax) {
+    const int c = threadIdx.x, i = blockIdx.x >> 1, j = blockIdx.x & 1;   // 64 threads
+    cmax += blockIdx.x * (kWsACols + kWsBCols);
+    const float tot = __uint_as_float(mx[0]), tr = __uint_as_float(mx[1]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cmax[64 * k + c] = mt[128 * k + 64 * i + c];
+    const float l = __uint_as_float(mo[64 * j + c]), u = __uint_as_float(mo[128 + 64 * j + c]);
+    cmax[kWsACols + c] = __float_as_uint(l);
+    cmax[kWsACols + 64 + c] = __float_as_uint(tot * l);
+    cmax[kWsACols + 128 + c] = __float_as_uint(tr * l);
+    cmax[kWsACols + 192 + c] = cmax[kWsACols + 256 + c] = __float_as_uint(u);
+}
+
 }  // namespace
 
 bool smp_split_products(const gf_ctx *ctx) {  // (read per call: the parity tests switch it)
@@ -1497,7 +1568,7 @@ static bool packed_rows(const int *trowf, int rows, int row_limit) {
     return trowf && rows < row_limit && !env_is("GF_SMP_MASK_ZEROS", '0');
 }
 
-size_t smp_split_image_bytes() { return 2 * (size_t)kSpImgStride * sizeof(uint4); }
+size_t smp_split_image_bytes(int C) { return (C == 128 ? 8 * (size_t)kSpImgStride128 : 2 * (size_t)kSpImgStride) * sizeof(uint4); }   // (128: four sub-block sets)
 template <int C>
 static gf_status launch_small_split(gf_ctx *ctx, const char *name, int total, size_t lds, const SmallJobs &jb, const uint4 *img) {
     gf_status st = opt_in_lds(ctx, smp_small_split<C>, lds);
@@ -1542,7 +1613,10 @@ gf_status smp_split_build_images(gf_ctx *ctx, const float *const *Wst, void *con
             a.X[i] = X ? X[i0 + i] : nullptr;
             a.img[i] = static_cast<uint4 *>(img[i0 + i]);
         }
-        GF_LAUNCH(ctx, "smpf_stack_w", smp_split_weight_images, dim3(2, m, kSpPos), dim3(kSpThreads), 0, a, C);
+        if (C == 128)   // (four sub-block sets of the eight row products' blocks: smp_split_weight_images_c128)
+            GF_LAUNCH(ctx, "smpf_stack_w", smp_split_weight_images_c128, dim3(2, m, 32), dim3(kSpThreads), 0, a);
+        else
+            GF_LAUNCH(ctx, "smpf_stack_w", smp_split_weight_images, dim3(2, m, kSpPos), dim3(kSpThreads), 0, a, C);
     }
     return GF_OK;
 }
@@ -1557,14 +1631,27 @@ struct RowpanelArgs {
     int store_mask;
     const uint4 *img;   // this direction's weight images, or null
 };
-template <bool F, bool M, int CB, int NF, int NX, bool CLS = false>
-static gf_status launch_rowpanel_split(gf_ctx *ctx, const RowpanelArgs &a, const int *rcls = nullptr) {
+template <bool F, bool M, int CB, int NF, int NX, bool CLS = false, int W = 1, bool ACC = false>
+static gf_status launch_rowpanel_split(gf_ctx *ctx, const RowpanelArgs &a, const int *rcls = nullptr, int a_off = 0, int out_off = 0) {
     const size_t lds = 2 * (size_t)(8 + NX) * (CB >= 32 ? CB / 32 : 1) * (CB / 16) * 64 * 16 + 32 * sizeof(float) + (kSpThreads / 64) * 32 * sizeof(float) +
                        (CLS ? (kSpThreads / 64) * 32 * sizeof(float *) : 0);
-    gf_status st = opt_in_lds(ctx, smp_rowpanel_split<F, M, CB, NF, NX, CLS>, lds);
+    gf_status st = opt_in_lds(ctx, smp_rowpanel_split<F, M, CB, NF, NX, CLS, W, ACC>, lds);
     if (st != GF_OK) return st;
-    GF_LAUNCH(ctx, F ? "smpf_products_fwd" : "smpf_products_bwd", (smp_rowpanel_split<F, M, CB, NF, NX, CLS>), dim3((unsigned)a.grid), dim3(kSpThreads),
-              lds, a.A, a.rowscale, a.Wst, a.Out, a.rows, a.trow, a.store_mask, a.img, rcls);
+    GF_LAUNCH(ctx, F ? "smpf_products_fwd" : "smpf_products_bwd", (smp_rowpanel_split<F, M, CB, NF, NX, CLS, W, ACC>), dim3((unsigned)a.grid), dim3(kSpThreads),
+              lds, a.A, a.rowscale, a.Wst, a.Out, a.rows, a.trow, a.store_mask, a.img, rcls, a_off, out_off);
+    return GF_OK;
+}
+// C = 128: the four (reduction half i, output half j) passes of a level's products, each the 64-channel program on its sub-blocks; for an
+// output half the pass of i = 1 adds to what i = 0 stored -- a fixed order, the same bits every run.  img: the level's four image sets.
+template <bool F, bool M>
+static gf_status launch_rowpanel_c128(gf_ctx *ctx, RowpanelArgs a, const uint4 *sets) {
+    for (int j = 0; j < 2; ++j)
+        for (int i = 0; i < 2; ++i) {
+            a.img = sets + (size_t)(2 * (2 * i + j) + (F ? 0 : 1)) * kSpImgStride128;
+            const gf_status st = i == 0 ? launch_rowpanel_split<F, M, 64, 2, 0, false, 2, false>(ctx, a, nullptr, 64 * i, 64 * j)
+                                        : launch_rowpanel_split<F, M, 64, 2, 0, false, 2, true>(ctx, a, nullptr, 64 * i, 64 * j);
+            if (st != GF_OK) return st;
+        }
     return GF_OK;
 }
 template <int CB, int NF, int NX = 0>
@@ -1592,6 +1679,14 @@ gf_status smp_rowpanel_split_c64(gf_ctx *ctx, bool forward, const float *A, cons
     const int grid = want < slots ? want : slots;
     if (C != 64 && !wimg) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_rowpanel_split: %d channels need the level's prebuilt weight images", C);
     const bool mask = packed_rows(trowf, rows, 1 << 29);
+    if (C == 128) {   // four sub-block passes of the 64-channel program (launch_rowpanel_c128); the row classes are not used
+        if (nf != 2 || nx != 0) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_rowpanel_split: %d row factors / %d extra products at 128 channels", nf, nx);
+        const int want128 = ((rows + 31) / 32 + per - 1) / per;
+        const RowpanelArgs a = {want128 < cus ? want128 : cus, A, rowscale, Wst, Out, rows, mask ? trowf : trow, skip_zero_grads ? 1 : 0, nullptr};
+        const uint4 *sets = static_cast<const uint4 *>(wimg);
+        if (forward) return mask ? launch_rowpanel_c128<true, true>(ctx, a, sets) : launch_rowpanel_c128<true, false>(ctx, a, sets);
+        return mask ? launch_rowpanel_c128<false, true>(ctx, a, sets) : launch_rowpanel_c128<false, false>(ctx, a, sets);
+    }
     const RowpanelArgs a = {grid, A, rowscale, Wst, Out, rows, mask ? trowf : trow, skip_zero_grads ? 1 : 0,
                             wimg ? static_cast<const uint4 *>(wimg) + (forward ? 0 : kSpImgStride) : nullptr};
     if (nx != 0) {   // the extra products of SMP_2D_ver7 on the 18-slice level (see the kernel)
@@ -1617,11 +1712,50 @@ gf_status smp_rowpanel_split_c64(gf_ctx *ctx, bool forward, const float *A, cons
 // from (smp_internal.h: WgradScales).
 gf_status smp_wgrad_partials_split_c64(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int kchunk,
                                        int splits, float *part, const int *trow, const WgradScales &ws, const int *trowf) {
-    gf_status st = opt_in_lds(ctx, smp_wgrad_split, kWsLds);
+    gf_status st = opt_in_lds(ctx, smp_wgrad_split<1>, kWsLds);
     if (st != GF_OK) return st;
     const bool mask = packed_rows(trowf, rows, 1 << 29);
-    GF_LAUNCH(ctx, "smpf_wgrad", smp_wgrad_split, dim3((unsigned)splits), dim3(kWsThreads), kWsLds, T, dO, rowscale, rows, kchunk, part,
-              mask ? trowf : trow, ws.cmax, ws.chan, ws.smax, ws.max_tot, ws.max_tr, ws.row_max, mask ? 1 : 0);
+    GF_LAUNCH(ctx, "smpf_wgrad", smp_wgrad_split<1>, dim3((unsigned)splits), dim3(kWsThreads), kWsLds, T, dO, rowscale, rows, kchunk, part,
+              mask ? trowf : trow, ws.cmax, ws.chan, ws.smax, ws.max_tot, ws.max_tr, ws.row_max, mask ? 1 : 0, 0, 0, 0);
+    return GF_OK;
+}
+
+// The eight row block products of a fused level at C = 128 (compact layout) as partial images of 8 x 128 x 128 floats: four launches of
+// smp_wgrad_split<2>, one per 64 x 64 sub-block (i, j) of every product, each with the exact column bounds of its own operand halves
+// (column maxima of T [rows][512] and dO [rows][256] taken here, 64 columns a launch: T must hold its structural zeros).
+// words: smp_wgrad_c128_words() scratch words; part: `*splits` images (<= part_floats floats), folded by the caller.
+size_t smp_wgrad_c128_words() { return 1024 + 4 * (kWsACols + kWsBCols); }
+gf_status smp_wgrad_partials_c128(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, float *part, size_t part_floats,
+                                  FoldGroup *out, const int *trow, const int *trowf, unsigned *words) {
+    const size_t total = 8 * 128 * 128;
+    out->part = part;
+    out->n = total;
+    out->splits = 0;
+    if (rows < 1) return GF_OK;
+    // as smp_wgrad_partials_c64: one workgroup per CU, at least 8 slices each; the count depends on `rows` only
+    const int target = 256;
+    int kchunk = ((rows + target - 1) / target + kWsSlice - 1) / kWsSlice * kWsSlice;
+    if (kchunk < 8 * kWsSlice) kchunk = 8 * kWsSlice;
+    const int splits = (rows + kchunk - 1) / kchunk;
+    if ((size_t)splits * total > part_floats)
+        return fail(ctx, GF_ERR_NOMEM, "smp_wgrad_partials_c128: %d partial images, room for %zu", splits, part_floats / total);
+    out->splits = splits;
+    GF_HIP_TRY(ctx, hipMemsetAsync(words, 0, sizeof(unsigned) * 1024, ctx->stream));
+    const long long g0 = ((long long)rows + 15) / 16;
+    const unsigned g = (unsigned)(g0 < 1 ? 1 : g0 > 1024 ? 1024 : g0);
+    for (int k = 0; k < 8; ++k) GF_LAUNCH(ctx, "smpf_colmax", col_absmax64, dim3(g), dim3(256), 0, T + 64 * k, (long long)rows, 512, words + 64 * k);
+    for (int k = 0; k < 4; ++k) GF_LAUNCH(ctx, "smpf_colmax", col_absmax64, dim3(g), dim3(256), 0, dO + 64 * k, (long long)rows, 256, words + 512 + 64 * k);
+    GF_LAUNCH(ctx, "smpf_colmax", rowscale_absmax, dim3(64), dim3(256), 0, rowscale, rows, words + 768);
+    GF_LAUNCH(ctx, "smpf_colmax", wgrad_bounds_exact_c128, dim3(4), dim3(64), 0, words, words + 512, words + 768, words + 1024);
+    gf_status st = opt_in_lds(ctx, smp_wgrad_split<2>, kWsLds);
+    if (st != GF_OK) return st;
+    const bool mask = packed_rows(trowf, rows, 1 << 29);
+    for (int q = 0; q < 4; ++q) {
+        const int i = q >> 1, j = q & 1;
+        GF_LAUNCH(ctx, "smpf_wgrad", smp_wgrad_split<2>, dim3((unsigned)splits), dim3(kWsThreads), kWsLds, T, dO, rowscale, rows, kchunk, part,
+                  mask ? trowf : trow, words + 1024 + q * (kWsACols + kWsBCols), (const unsigned *)nullptr, 0.f, 0.f, 0.f, (const unsigned *)nullptr,
+                  mask ? 1 : 0, 64 * i, 64 * j, 64 * i * 128 + 64 * j);
+    }
     return GF_OK;
 }
 

@@ -1,6 +1,6 @@
 // smp_level_ops.hip -- the block products of the fused SMP level as stand-alone operators of the C ABI
 // (gf_smp_level_products_f32 / gf_smp_level_wgrad_f32 at C = 64, gf_smp_level_products_ex_f32 / gf_smp_level_wgrad_ex_f32 for every
-// variant the level has, include/gf_hip.h): the same kernels gf_smp_forward / gf_smp_backward launch
+// variant the level has -- 128 channels as four 64-channel sub-block passes included --, include/gf_hip.h): the same kernels gf_smp_forward / gf_smp_backward launch
 // on a level's rows (smp_level_c64.hip on the fp32 matrix pipe, smp_level_c64_split.hip on the f16 pipe with two-half operands),
 // on caller-supplied matrices.  They replace, for the rows of one level, the K-projection MatMul of the reference
 // (GraphFlow/SMP_omega.h:654-657 forward, MatMul.h:69-82 backward) in its regrouped form (smp_fused.hip header) -- and they are
@@ -63,10 +63,10 @@ gf_status check_tables(gf_ctx *ctx, const char *who, int rows, const int *trow, 
 
 // the variants the level's kernels have (before any launch): 0, or the status with the reason recorded
 gf_status check_variant(gf_ctx *ctx, const char *who, int C, int nf, int nx, bool products) {
-    if (!(C == 16 || C == 32 || (C == 64 && products))) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d channels", who, C);
+    if (!(C == 16 || C == 32 || (C == 64 && products) || C == 128)) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d channels", who, C);
     if ((nf != 2 && nf != 8) || (nx != 0 && nx != 3)) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d row factors / %d extra products", who, nf, nx);
     if (nx == 3 && nf == 8) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: the extra products take the plain (tot, tr) row factors", who);
-    if (C == 64 && (nx != 0 || nf != 2)) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d row factors / %d extra products at 64 channels", who, nf, nx);
+    if ((C == 64 || C == 128) && (nx != 0 || nf != 2)) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d row factors / %d extra products at %d channels", who, nf, nx, C);
     if (C != 64 && !smp_split_products(ctx)) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d channels on the fp32 matrix pipe", who, C);
     return GF_OK;
 }
@@ -124,7 +124,7 @@ gf_status gf_smp_level_products_ex_f32(gf_ctx *ctx, int backward, int C, int nf,
     if (gf::smp_split_products(ctx)) {
         // the level's prebuilt weight images (both directions).  The builder reads the level's EIGHTEEN stacked blocks: the eight row
         // products' first, the other ten as zeros
-        const size_t CC = (size_t)C * C, img_bytes = gf::align_up(gf::smp_split_image_bytes(), 256);
+        const size_t CC = (size_t)C * C, img_bytes = gf::align_up(gf::smp_split_image_bytes(C), 256);
         // ... and, for a packed table at C = 64, the table's row classes behind them (the level builds them once per batch)
         const size_t w_bytes = gf::align_up(sizeof(float) * 18 * CC, 256);
         const bool classes = trowf && C == 64 && rows < (1 << 29);
@@ -168,6 +168,17 @@ gf_status gf_smp_level_wgrad_ex_f32(gf_ctx *ctx, int C, int nf, int nx, int rows
     // workspace: the eight products' partial images (one set per workgroup, and the fold's second stage), the extra products', the
     // scratch words of the column bounds, three words of row-factor maxima
     const size_t CC = (size_t)C * C;
+    if (C == 128) {   // four sub-block launches of the C = 64 kernel (smp_wgrad_partials_c128): at most 256 images and the fold's nine
+        const size_t cap = (size_t)(rows / 128 + 1 < 256 ? rows / 128 + 1 : 256) + 9, words128 = gf::smp_wgrad_c128_words();
+        st = gf::ensure_ws(ctx, sizeof(float) * (cap * 8 * CC + words128) + 256);
+        if (st != GF_OK) return st;
+        float *part128 = static_cast<float *>(ctx->ws);
+        gf::FoldGroup fg;
+        st = gf::smp_wgrad_partials_c128(ctx, T, dO, rowfac, rows, part128, (cap - 9) * 8 * CC, &fg, trow, trowf,
+                                         reinterpret_cast<unsigned *>(part128 + cap * 8 * CC));
+        if (st != GF_OK) return st;
+        return gf::splitk_fold(ctx, fg.part, dWst, 8 * CC, fg.splits, 0);
+    }
     const int splits = gf::smp_wgrad_all_splits(ctx, rows);
     const size_t images = (size_t)splits + (splits + 31) / 32, words = gf::smp_wgrad_all_words();
     st = gf::ensure_ws(ctx, sizeof(float) * (images * 11 * CC + words + 4) + 256);

@@ -617,14 +617,17 @@ void alloc_level_gather(Taker &t, Level &h, DevLevel &d) {
 void alloc_level_panels(Taker &t, Level &h, DevLevel &d, int l) {
     const gfsmp::Config &cfg = t.s->cfg;
     const int L = cfg.nLevels, C = cfg.nChanels;
-    if (!(cfg.square() && smp_panel_channels(C) && h.rows < 0x7fffffffll)) return;
+    // (C = 128, the plain 18-slice model: the tables and four sets of weight images for the sub-block passes of the product kernels)
+    const bool c128 = C == 128 && cfg.nContractions == 18 && !cfg.physics && smp_c128_switch();
+    if (!(cfg.square() && (smp_panel_channels(C) || c128) && h.rows < 0x7fffffffll)) return;
     t.alloc(&d.trow, (size_t)h.rows);
     t.alloc(&d.trowf, (size_t)h.rows);
     if (C == 64 && cfg.nContractions == 18 && h.rows < (1ll << 29)) t.alloc(&d.rowcls, smp_row_class_ints((int)h.rows));   // (row classes of the masked products)
     unsigned char *img = nullptr;
-    t.alloc(&img, smp_split_image_bytes());
+    t.alloc(&img, smp_split_image_bytes(C));
     d.wimg = img;
     t.alloc(&d.rowflag, (size_t)h.rows);
+    if (c128) return;   // (the panel kernels of tables / combine are not built for 128 channels)
     if (!(cfg.nContractions == 18 && h.rows * 256 < 0x3fffffffll && !h.buckets.empty() && h.buckets.back().s <= kFusedMaxField)) return;
     // a node of size s has ceil(s / max(1, 32 / s)) panels
     const int np = h.npanels;   // (page-locked table of the layout: no wait for the copy)
@@ -772,6 +775,8 @@ gf_status alloc_readout(gf_smp *s, int nMol) {
     if (s->cfg.square() && C == 64) t.alloc(&s->wbound, smp_wgrad_bound_words() * (size_t)(L + 1));
     else if (s->cfg.square() && (C == 32 || C == 16))   // scratch words of the C = 32 / 16 weight-gradient kernel's column bounds
         t.alloc(&s->wbound, smp_wgrad_all_words() * (size_t)(L + 1));
+    else if (s->cfg.square() && C == 128 && s->cfg.nContractions == 18 && smp_c128_switch())   // ... and of the four sub-block launches at C = 128
+        t.alloc(&s->wbound, smp_wgrad_c128_words() * (size_t)(L + 1));
     t.alloc(&s->sh, (size_t)top.nNodes * C);
     t.alloc(&s->vf, (size_t)top.nNodes * C);
     t.alloc(&s->dsh, (size_t)top.nNodes * C);

@@ -331,7 +331,7 @@ gf_status gf_smp_level_products_f32(gf_ctx *ctx, int backward, int rows, const f
                                     const int *trow, float *Out);
 gf_status gf_smp_level_wgrad_f32(gf_ctx *ctx, int rows, const float *T, const float *dO, const float *rowscale, const int *trow,
                                  float *dWst);
-/* The same products in every variant the fused level has: C = 64, 32 or 16 channels (blocks of C columns: T [rows][4 C], O / dO
+/* The same products in every variant the fused level has: C = 128, 64, 32 or 16 channels (blocks of C columns: T [rows][4 C], O / dO
  * [rows][2 C], Wst [8][C][C]; forward A = T -> Out = O, backward A = dO -> Out = dT), with
  *   nf = 2: rowfac [rows][2] = (tot, tr) as above;   nf = 8 (C = 32, 16): rowfac [rows][8] = one factor per stacked product 0..7 --
  *           the plain (tot, tot, tr, 1, 1, 1, 1, 1) times the node's slice-dropout factors -- in place of tot / tr / 1 above.  The factors
@@ -346,14 +346,17 @@ gf_status gf_smp_level_wgrad_f32(gf_ctx *ctx, int rows, const float *T, const fl
  *   skip_zero_grads (backward, with trowf): the dS_ab / dT6 blocks of rows without bit 31 are NOT written (gradients of structural
  *           zeros), and dO of a row without bit 29 (no source covers it: nothing to back-propagate) counts as zero.  This relies
  *           on the level's structure: bit 31 implies bit 29, and bit 29 is the same for a row and its transposed row.
- * The weight gradients exist at C = 32 and 16 (gf_smp_level_wgrad_f32 is the C = 64 kernel); with nf = 2 the operand columns take
+ * C = 128 (nf = 2, nx = 0; trowf and skip_zero_grads as at 64): every 128 x 128 product runs as four 64 x 64 sub-block passes of the
+ * C = 64 kernels -- (reduction half, output half); the second reduction half adds to the first in a fixed order, so two runs give the
+ * same bits -- and a row's exponent is taken per 64-column sub-block.
+ * The weight gradients exist at C = 128, 32 and 16 (gf_smp_level_wgrad_f32 is the C = 64 kernel); with nf = 2 the operand columns take
  * their exponents from exact column maxima, with nf = 8 from per-channel upper bounds the operator derives from the operands.
  * Their gathered operand dU[trow] is fetched through a window of 64 x 64 rows on either side of the row's 16-row slice -- in a
  * level a transposed row lies inside its own node, at most (s - 1)^2 rows away -- and a row further off would silently load zeros:
  * that is a property of the level, so this operator checks trow on the host (one blocking copy of the tables per call; both
  * operators also refuse a trow outside the matrix, and a trowf whose low bits differ from trow) and answers GF_ERR_INVALID.
  * Combinations the kernels do not have are GF_ERR_UNSUPPORTED before anything is launched: nx = 3 with nf = 8, nx = 3 or nf = 8
- * at C = 64, and C != 64 on the fp32 pipe (GF_SMP_SPLIT=0 / GF_OPT_SMP_FP32_PRODUCTS).  The context stays usable after a refusal. */
+ * at C = 64 or 128, and C != 64 on the fp32 pipe (GF_SMP_SPLIT=0 / GF_OPT_SMP_FP32_PRODUCTS).  The context stays usable after a refusal. */
 gf_status gf_smp_level_products_ex_f32(gf_ctx *ctx, int backward, int C, int nf, int nx, int rows, const float *A, const float *rowfac,
                                        const float *Wst, const float *X, const int *trow, const int *trowf, int skip_zero_grads,
                                        float *Out);
