@@ -828,7 +828,7 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
     st = dup_level(s, 0);   // (SMP_2D_ver6 on the 18-slice level: channels [C, 2C) <- the transposed matrices; level 0: copies)
     if (st != GF_OK) return st;
     if (s->fused) {
-        if (s->wbound && C == 64) GF_HIP_TRY(ctx, hipMemsetAsync(s->wbound, 0, sizeof(unsigned) * smp_wgrad_bound_words() * (size_t)(L + 1), ctx->stream));
+        if (s->wbound && C == 64) GF_HIP_TRY(ctx, hipMemsetAsync(s->wbound, 0, sizeof(unsigned) * smp_wgrad_words(64, false) * (size_t)(L + 1), ctx->stream));
         st = smp_fused_stack_all(s, K);
         if (st != GF_OK) return st;
     }

@@ -900,7 +900,7 @@ __global__ __launch_bounds__(kThreads) void smp_combine_bwd(const float *__restr
                                                             const long long *__restrict__ node_pair, int C, int nwin,
                                                             const float *__restrict__ rsum, int ocols,
                                                             float *__restrict__ dzmax) {  // or null: [workgroups][CW] largest |dz| per column
-    // of this workgroup's rows (C = 64: the weight gradients' column exponents, smp_wgrad_column_bounds)
+    // of this workgroup's rows (C = 64: the weight gradients' column exponents, WgradScales::chan)
     constexpr int CW = 4 * LPC;
     constexpr int NGRP = kThreads / LPC;
     const int tid = threadIdx.x;
@@ -1806,7 +1806,7 @@ gf_status smp_fused_forward_level(gf_smp *s, int l, const float *Kl, const float
 //   smp_reduce_pairs            dSout per node + column partials of the bias gradient          (was 3 launches)
 //   diag_gather_bwd             dGc
 //   ONE NT launch               dFdc = [dG15 K15^T | dG16 K16^T], dVt = dVout [K1;K3;K7;K10]^T, dSt = dSout [K4;..]^T   (was 3)
-//   smp_wgrad_c64               row-range images of the eight row products
+//   smp_wgrad_partials          partial images of the eight row products
 //   ONE TN launch               dK15, dK16, Vt^T dVout, St^T dSout, each split over its own rows    (was 4 + their folds)
 //   smp_fold_level              every image folded, un-stacked and added into dK_l / db_l          (was ~8 launches)
 //   row-panel products          dT
@@ -1871,78 +1871,42 @@ gf_status smp_fused_backward_level_grouped(gf_smp *s, int l, float *dKl, float *
     size_t ws_floats = ctx->ws_bytes / sizeof(float), used = 0;
     FoldGroup rowg;
     const bool stationary = d.fwd_c64;
-    if (stationary && (C == 32 || C == 16)) {   // smp_wgrad_all<32 | 16>: one partial image of the eight products per workgroup
-        const int splits = smp_wgrad_all_splits(ctx, rows);
-        if ((size_t)splits * 8 * CC > ws_floats) return fail(ctx, GF_ERR_NOMEM, "fused level: workspace too small for %d weight-gradient images", splits);
-        // SMP_2D_ver7 on the 18-slice level: its three extra products ride in the same kernel (their operands are fragments it already
-        // holds); three more images per workgroup behind the eight, folded straight into dX below (not under slice dropout: the extra
-        // products take the plain (tot, tr) row factors)
-        float *xpart = nullptr;
-        if (s->n_extra && s->extra_g && !drop &&
-            (size_t)splits * 8 * CC + ((size_t)splits + (splits + 31) / 32) * 3 * CC <= ws_floats)
-            xpart = ws + (size_t)splits * 8 * CC;
-        unsigned *words = s->wbound + (size_t)l * smp_wgrad_all_words();   // (the same scratch layout at 16 channels)
-        const unsigned *chan = nullptr;
-        if (d.dzmax && d.row_max) {   // per-channel maxima of f_{l-1} and of this level's dz (combine-backward's per-workgroup maxima)
-            GF_HIP_TRY(ctx, hipMemsetAsync(words, 0, sizeof(unsigned) * 64, ctx->stream));
-            // (combine-backward's maxima: one row of a window's width per workgroup -- 32-channel windows at C = 32)
-            // (the largest |f_{l-1}| per channel from the per-panel maxima combine-forward of the level below left behind, as at C = 64 --
-            //  f_{l-1} itself was read for them: 94 MB at cfg3's level 3 -- or from f_0)
+    if (stationary) {   // the row-panel family (64 / 32 / 16 channels, 128 as sub-block passes): smp_wgrad_partials picks the kernel
+        // scratch words of the level: its channel maxima, and the exact bounds' where the level may take them (a 64-channel level never does)
+        unsigned *words = s->wbound ? s->wbound + (size_t)l * smp_wgrad_words(C, C != 64) : nullptr;
+        WgradCall wc = {T, dO, drop ? d.rowfac8 : d.rowscale, rows, C, drop ? 8 : 2, d.trow, d.trowf, WgradScales(), C == 64 ? nullptr : words, ws, ws_floats};
+        // The operand columns' exponents come from the largest |f_{l-1}| and |dz_l| of every channel where the level has them: the per-panel
+        // maxima combine-forward of the level below left behind (f_{l-1} itself was read for them: 94 MB at cfg3's level 3) or f_0, and
+        // the per-workgroup maxima of this level's combine-backward -- 17 - 19 MB of partials at cfg3's level 3 -- reduced by one small
+        // launch.  The 32- / 16-channel kernel wants the row factors' maxima on the device (device-built tables); 128 channels: exact only.
+        if (words && d.dzmax && smp_split_products(ctx) && (C == 64 || ((C == 32 || C == 16) && d.row_max))) {
+            if (C != 64) GF_HIP_TRY(ctx, hipMemsetAsync(words, 0, sizeof(unsigned) * 64, ctx->stream));   // (64: once per forward, smp.hip)
             const bool pm = pv.pmax && pv.pmax_ready;
-            st = smp_wgrad_channel_maxima_ld(ctx, pm ? pv.pmax : pv.f, pm ? (long long)pv.fwd_npanels : (long long)s->lay.level[l - 1].rows, C, d.dzmax,
-                                             d.dz_rows, d.dz_ld, C, words);
+            st = smp_wgrad_channel_maxima(ctx, pm ? pv.pmax : pv.f, pm ? (long long)pv.fwd_npanels : (long long)s->lay.level[l - 1].rows, C, d.dzmax,
+                                          d.dz_rows, d.dz_ld, C, words);
             if (st != GF_OK) return st;
-            if (d.dz_rows2 > 0) {   // (the big nodes' workgroups: maxima of another row width, folded into the same words -- atomicMax)
-                st = smp_wgrad_channel_maxima_ld(ctx, pv.f, 0, C, d.dzmax + d.dz_off2, d.dz_rows2, d.dz_ld2, C, words);
+            if (d.dz_rows2 > 0) {   // (the big nodes' workgroups at 32 / 16 channels: maxima of another row width, folded into the same words)
+                st = smp_wgrad_channel_maxima(ctx, pv.f, 0, C, d.dzmax + d.dz_off2, d.dz_rows2, d.dz_ld2, C, words);
                 if (st != GF_OK) return st;
             }
-            chan = words;
+            wc.bounds.chan = words;
+            wc.bounds.smax = (float)h.buckets.back().s;
+            wc.bounds.max_tot = d.max_tot, wc.bounds.max_tr = d.max_tr, wc.bounds.row_max = d.row_max;
         }
-        if (!chan) {   // (host-built tables: the exact column bounds are maxima over ALL of T -- the absent blocks need their zeros)
+        if (smp_wgrad_reads_absent_blocks(ctx, wc)) {   // (see smp_fused_forward_level: then T needs its structural zeros)
             st = smp_fused_ensure_zero_fill(s, l);
             if (st != GF_OK) return st;
         }
-        st = smp_wgrad_partials_all(ctx, T, dO, drop ? d.rowfac8 : d.rowscale, rows, splits, ws, d.trow, d.trowf, words, chan,
-                                    (float)h.buckets.back().s, d.row_max, drop ? 8 : 2, C, xpart);
+        // SMP_2D_ver7 on the 18-slice level: its three extra products ride in the same kernel where it has them, folded straight into dX
+        // (not under slice dropout: the extra products take the plain (tot, tr) row factors)
+        FoldGroup xg = {nullptr, 0, 0};
+        st = smp_wgrad_partials(ctx, wc, &rowg, (s->n_extra && s->extra_g && !drop) ? &xg : nullptr);
         if (st != GF_OK) return st;
-        if (xpart) {
-            st = splitk_fold(ctx, xpart, s->extra_g + (size_t)(l - 1) * 3 * CC, 3 * CC, splits, 0);
+        if (xg.splits) {
+            st = splitk_fold(ctx, xg.part, s->extra_g + (size_t)(l - 1) * 3 * CC, xg.n, xg.splits, 0);
             if (st != GF_OK) return st;
             x_wgrad_done = true;
         }
-        rowg.part = ws;
-        rowg.splits = splits;
-        rowg.n = 8 * CC;
-        used = (size_t)splits * 8 * CC;
-    } else if (stationary && C == 128) {   // four sub-block launches of the C = 64 kernel, exact column bounds (T holds its zeros at 128)
-        st = smp_wgrad_partials_c128(ctx, T, dO, d.rowscale, rows, ws, ws_floats, &rowg, d.trow, d.trowf, s->wbound + (size_t)l * smp_wgrad_c128_words());
-        if (st != GF_OK) return st;
-        used = (size_t)rowg.splits * rowg.n;
-    } else if (stationary) {
-        unsigned *wb = (s->wbound && ocols == 2 && smp_split_products(ctx)) ? s->wbound + (size_t)l * smp_wgrad_bound_words() : nullptr;
-        if (wb && !d.dzmax) wb = nullptr;
-        WgradScales sc;
-        if (wb) {   // the operand columns' exponents come from the largest |f_{l-1}| and |dz_l| of every channel: the per-panel maxima
-            // combine-forward of the level below left behind (or f_0 itself) and the per-workgroup maxima of this level's
-            // combine-backward -- 17 - 19 MB of partials at cfg3's level 3, reduced by one small launch
-            const bool pm = pv.pmax && pv.pmax_ready;
-            st = smp_wgrad_channel_maxima(ctx, pm ? pv.pmax : pv.f, pm ? (long long)pv.fwd_npanels : (long long)s->lay.level[l - 1].rows, d.dzmax,
-                                          d.dz_rows, wb);
-            if (st != GF_OK) return st;
-            sc.chan = wb;
-            sc.smax = (float)h.buckets.back().s;
-            sc.max_tot = d.max_tot, sc.max_tr = d.max_tr, sc.row_max = d.row_max;
-        }
-        {   // (a weight-gradient kernel that reads the absent blocks of T needs their zeros: see smp_fused_forward_level)
-            const bool packed = ocols == 2 && sc.any() && smp_split_products(ctx) && d.trowf && (long long)rows < (1ll << 29) &&
-                                !env_is("GF_SMP_MASK_ZEROS", '0');
-            if (!packed) {
-                st = smp_fused_ensure_zero_fill(s, l);
-                if (st != GF_OK) return st;
-            }
-        }
-        st = smp_wgrad_partials_c64(ctx, T, dO, d.rowscale, rows, ws, ws_floats, &rowg, ocols == 2 ? d.trow : nullptr, sc, d.trowf);
-        if (st != GF_OK) return st;
         used = (size_t)rowg.splits * rowg.n;
     } else {  // other channel counts: the grouped split-K launch (its own ordered reduction) into the stacked image, one "image"
         struct G { int tcol, kb, wpos, ocol, scol; };

@@ -57,40 +57,48 @@ gf_status smp_build_row_classes(gf_ctx *ctx, hipStream_t stream, const int *trow
 // the split kernels' weight images of a level (both directions), built once per forward pass (smp_level_c64_split.hip)
 size_t smp_split_image_bytes(int C = 64);   // (C = 128: four sets, one per 64 x 64 sub-block of the 128 x 128 weight blocks)
 gf_status smp_split_build_images(gf_ctx *ctx, const float *const *Wst, void *const *img, int n, int C = 64, const float *const *X = nullptr);
-// weight gradients of a fused level at C = 32 or (round 5) 16 (smp_wgrad_all<C>): partial images of 8 x C x C floats per workgroup
-gf_status smp_wgrad_partials_all(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int splits, float *part,
-                                 const int *trow, const int *trowf, unsigned *words, const unsigned *chan = nullptr, float smax = 0.f,
-                                 const unsigned *row_max = nullptr, int nf = 2, int C = 32, float *xpart = nullptr);
-gf_status smp_wgrad_channel_maxima_ld(gf_ctx *ctx, const float *fprev, long long prev_rows, int ld0, const float *dsrc, long long drows, int ld1, int C,
-                                      unsigned *words);
-size_t smp_wgrad_all_words();
-int smp_wgrad_all_splits(gf_ctx *ctx, long long rows);
 gf_status smp_small_split_c64(gf_ctx *ctx, bool transposed, int n, const int *prog, const float *const *In, float *const *Out, const int *rows,
                               const int *pos0, const void *wimg, const char *name, int C = 64);
-// where the split-operand weight gradients take their per-column exponents from (smp_level_c64_split.hip: smp_wgrad_split): either
-// `cmax`, explicit per-column bounds of the nine operand blocks (576 float bits, device), or `chan`, the level's per-channel maxima
-// (128 float bits: max |f_{l-1}| then max |dz_l|) with the largest receptive field and row factors of the level
-struct WgradScales {
-    const unsigned *cmax = nullptr, *chan = nullptr;
-    float smax = 0.f, max_tot = 0.f, max_tr = 0.f;
-    const unsigned *row_max = nullptr;   // or: {max |tot|, max |tr|} as float bits in device memory
-    bool any() const { return cmax || chan; }
-};
-gf_status smp_wgrad_partials_split_c64(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int kchunk,
-                                       int splits, float *part, const int *trow, const WgradScales &ws, const int *trowf = nullptr);
-// weight gradients of a fused level at C = 128: four sub-block launches of the C = 64 kernel into partial images of 8 x 128 x 128 floats
-size_t smp_wgrad_c128_words();
-gf_status smp_wgrad_partials_c128(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, float *part, size_t part_floats,
-                                  FoldGroup *out, const int *trow, const int *trowf, unsigned *words);
-size_t smp_wgrad_bound_words();
-gf_status smp_wgrad_channel_maxima(gf_ctx *ctx, const float *fprev, long long prev_rows, const float *dsrc, long long drows, unsigned *words);
-size_t smp_wgrad_bound_words_exact();
-gf_status smp_wgrad_column_bounds_exact(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, unsigned *words);
 gf_status splitk_fold(gf_ctx *ctx, const float *part, float *dest, size_t total, int splits, int accumulate);
-// the same product, partial images only (fold == caller's): `part` receives out->splits images of 8 * 64 * 64 floats
-gf_status smp_wgrad_partials_c64(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, float *part,
-                                 size_t part_floats, FoldGroup *out, const int *trow, const WgradScales &ws = WgradScales(),
-                                 const int *trowf = nullptr);
+
+// ---- the weight gradients of a fused level's eight row block products (the end of smp_level_c64_split.hip), C = 16 / 32 / 64 / 128 ----
+// Where the split-operand kernels take their per-column exponents from: the level's per-channel maxima `chan` ([2 C] float bits: max
+// |f_{l-1}| then max |dz_l|, smp_wgrad_channel_maxima) with the largest receptive field and row factors of the level -- or nothing: exact
+// column bounds are then taken from the operands themselves (one extra pass over T and dO).
+struct WgradScales {
+    const unsigned *chan = nullptr;
+    float smax = 0.f, max_tot = 0.f, max_tr = 0.f;
+    const unsigned *row_max = nullptr;   // {max |tot|, max |tr|} as float bits in device memory; they replace max_tot / max_tr at 64
+    // channels (device-built tables) and are the only form the 32- / 16-channel kernel takes
+    bool level(int C) const { return chan && (C == 64 || row_max); }
+};
+// One call: the operands T [rows][4 C], dO [rows][2 C] (compact layout; trow null at 64 channels: [rows][3 C] on the fp32 pipe) and
+// rowscale [rows][nf] (nf = 2: (tot, tr); 8: one factor per product, 32 / 16 channels with level bounds only), the level's plain and
+// packed transposed-row tables, the bounds, and the workspace: smp_wgrad_words(C) scratch words for exact bounds (null at 64 channels =
+// none: without level maxima the fp32 kernel runs, as it does when the split products are switched off) and room for the images.
+struct WgradCall {
+    const float *T, *dO, *rowscale;
+    int rows, C, nf;
+    const int *trow, *trowf;
+    WgradScales bounds;
+    unsigned *words;
+    float *part;
+    size_t part_floats;
+};
+// scratch words per level; exact = false: of a level that only ever keeps its channel maxima there (the 64-channel levels of a model)
+size_t smp_wgrad_words(int C, bool exact = true);
+// floats of partial images a call of `rows` rows may need, the folds' second stage and nx extra products' images included
+size_t smp_wgrad_part_floats(gf_ctx *ctx, int rows, int C, int nx = 0);
+// will this call read the absent S_ab / T6 blocks of T?  Then they must hold their zeros before it runs (smp_fused_ensure_zero_fill).
+bool smp_wgrad_reads_absent_blocks(const gf_ctx *ctx, const WgradCall &call);
+// Picks the kernel -- fp32 pipe or smp_wgrad_split at 64 channels, smp_wgrad_all<32 | 16>, four sub-block launches of smp_wgrad_split at
+// 128 -- and leaves out->splits partial images of 8 C^2 floats in call.part for the caller to fold in order.  xout (optional): the three
+// extra products of SMP_2D_ver7 in the same launch, images of 3 C^2 floats; xout->splits == 0 where the kernel or the room does not allow.
+gf_status smp_wgrad_partials(gf_ctx *ctx, const WgradCall &call, FoldGroup *out, FoldGroup *xout = nullptr);
+gf_status smp_wgrad_channel_maxima(gf_ctx *ctx, const float *fprev, long long prev_rows, int ld0, const float *dsrc, long long drows, int ld1, int C,
+                                   unsigned *words);
+gf_status smp_wgrad_fp32_c64(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int kchunk, int splits, float *part,
+                             const int *trow);   // (smp_level_c64.hip: the fp32 kernel's launch, for smp_wgrad_partials)
 }
 
 
@@ -176,7 +184,7 @@ struct gf_smp {
         float *psum = nullptr;     // top level, C = 64: [fwd_npanels][64] column sums of the row panels of f_L (readout)
         float *dshl = nullptr;     // towers: [nodes][C] gradient of the level's read-out per node (the fused level's combine-backward adds it)
         bool psum_ready = false;   // ... written by this forward pass
-        // per-channel maxima for the weight gradients' column exponents (smp_level_c64_split.hip: smp_wgrad_column_bounds), C = 64:
+        // per-channel maxima for the weight gradients' column exponents (smp_level_c64_split.hip: WgradScales::chan):
         float *pmax = nullptr;     // [fwd_npanels][64] largest |f_l| of every row panel, left by combine-forward (levels below the top)
         float *dzmax = nullptr;    // [max(quads, row panels)][64] largest |dz| of every workgroup / panel of combine-backward
         long long dz_rows = 0;     // ... rows of it the last combine-backward wrote
@@ -219,8 +227,8 @@ struct gf_smp {
     unsigned *tab_stats = nullptr;          // [levels + 1][4]: max |tot|, max |tr| (float bits), rows with data (two words)
     std::vector<unsigned> h_tab_stats;
     std::vector<long long> h_covered;       // [levels + 1] cache of gf_smp_level_covered_rows (-1 = not read yet), cleared by prepare
-    // [levels + 1][smp_wgrad_bound_words()] per-channel maxima of f_{l-1} and of df_l and the column bounds the split-operand weight
-    // gradients derive from them (smp_level_c64_split.hip: smp_wgrad_column_bounds); C = 64 only, zeroed at the start of every forward
+    // [levels + 1][smp_wgrad_words(C, C != 64)] scratch words of the levels' weight gradients (smp_level_c64_split.hip: wgrad_words): the
+    // per-channel maxima of f_{l-1} and of dz_l (at C = 64 nothing else, zeroed at the start of every forward) and the exact column bounds
     unsigned *wbound = nullptr;
     float *x = nullptr;      // [nVertices][FD]
     float *P = nullptr;      // shared promotion / dP buffer, max over levels of ppos*C; allocated on first use (ensure_P):

@@ -425,26 +425,11 @@ __global__ __launch_bounds__(TH, 1) void smp_rowpanel_c64(const float *__restric
 
 }  // namespace
 
-// The eight row block products A_p^T B_p of a fused SMP level at C = 64 (see smp_wgrad_c64) as PARTIAL images: one image of
-// 8 x 64 x 64 floats per row range.  T = [rows][256], dO = [rows][192], rowscale = [rows][2].  The row range per workgroup
-// depends on `rows` only: results are reproducible.  The caller folds the images in order.
-gf_status smp_wgrad_partials_c64(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, float *part,
-                                 size_t part_floats, FoldGroup *out, const int *trow, const WgradScales &ws, const int *trowf) {
-    const size_t total = 8 * 4096;
-    out->part = part;
-    out->n = total;
-    out->splits = 0;
-    if (rows < 1) return GF_OK;
-    // one workgroup fits a CU (two LDS stages): aim at `target` row ranges, at least 8 slices each
-    const int target = 256;
-    int kchunk = ((rows + target - 1) / target + BK - 1) / BK * BK;
-    if (kchunk < 8 * BK) kchunk = 8 * BK;
-    const int splits = (rows + kchunk - 1) / kchunk;
-    if ((size_t)splits * total > part_floats)
-        return fail(ctx, GF_ERR_NOMEM, "smp_wgrad_partials_c64: %d partial images, room for %zu", splits, part_floats / total);
-    out->splits = splits;
-    if (trow && ws.any() && smp_split_products(ctx))
-        return smp_wgrad_partials_split_c64(ctx, T, dO, rowscale, rows, kchunk, splits, part, trow, ws, trowf);
+// The eight row block products A_p^T B_p of a fused SMP level at C = 64 (see smp_wgrad_c64) on the fp32 matrix pipe, as PARTIAL images:
+// `splits` images of 8 x 64 x 64 floats, one per range of `kchunk` rows (a multiple of BK).  T = [rows][256], dO = [rows][192] or
+// (trow) [rows][128], rowscale = [rows][2].  Called by smp_wgrad_partials (smp_level_c64_split.hip), which plans the ranges.
+gf_status smp_wgrad_fp32_c64(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int kchunk, int splits, float *part,
+                             const int *trow) {
     const size_t lds = sizeof(float) * 2 * (size_t)kWgStage;
     gf_status st = opt_in_lds(ctx, smp_wgrad_c64, lds);
     if (st != GF_OK) return st;

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
     const float *__restrict__ bias, float *__restrict__ psum,   // psum (top level, or null): [npanels][64] column sums of the panel's
     // rows of f -- the readout's per-node sums (ShrinkTensor, SMP_omega.h:671-676) then read 22 MB of partials instead of f_L again
     float *__restrict__ pmax,  // pmax (or null): [npanels][64] largest |f| per column of the panel's rows (the level above scales the
-    // columns of its weight-gradient operands with the level's per-channel maxima: smp_wgrad_column_bounds)
+    // columns of its weight-gradient operands with the level's per-channel maxima: WgradScales::chan)
     const float *__restrict__ nodefac) {  // (or null) slice dropout: [nodes][18] factors; the compact products G15 / G16 take theirs here
     const int lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
     unsigned blk;

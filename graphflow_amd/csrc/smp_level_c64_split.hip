@@ -903,7 +903,7 @@ __global__ __launch_bounds__(kSmThreads, 2) void smp_small_split(SmallJobs jobs,
 //   dWst[p] = sum over rows of A_p[row]^T B_p[row],   A_p in T = [S_ab|S_bc|T6|T10],   B_p in {L, tot L, tr L, dU, dU[trow]}
 // reduce over the ROWS, so a row's exponent cannot scale it (the terms of one MFMA accumulation must share their scale) -- but a
 // COLUMN's can: every operand column carries one exponent for the whole level (see the kernel), derived from per-channel bounds that
-// smp_wgrad_column_bounds builds from the largest |f_{l-1}| and |df_l| of each channel.
+// smp_wgrad_channel_maxima gathers: the largest |f_{l-1}| and |df_l| of each channel.
 //
 // A workgroup of eight waves takes every gridDim-th 16-row slice of the level, four slices in flight and ONE
 // barrier per slice.  In the interval of slice i a thread splits its share of slice i + 1 (raw in registers, requested three
@@ -952,7 +952,7 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
     // review's weak #1: with one exponent per block the small channels' low halves went subnormal 2^17 below the loud channel);
     // inside a column, an element keeps its 22 bits down to 2^-17 of the column's bound and the absolute error floor is 2^-38 of
     // the bound -- far below what the fp32 accumulation of that column's sum resolves.  The bounds need not be tight (sum s x the
-    // largest |f_{l-1}| of the channel, etc.: smp_wgrad_column_bounds); a bound 2^10 above the true maximum still leaves the floor
+    // largest |f_{l-1}| of the channel, etc.); a bound 2^10 above the true maximum still leaves the floor
     // at 2^-28 of it.
     float *sScale = reinterpret_cast<float *>(ws_smem + 2 * kWsStageWords), *sInv = sScale + kWsACols + kWsBCols;
     if (cmax) {
@@ -1424,31 +1424,17 @@ __global__ __launch_bounds__(kW8Threads, 1) void smp_wgrad_all(const float *__re
     }
 }
 
-// exact column bounds of the nine operand blocks of smp_wgrad_all<CB, 2> from the column maxima of T [rows][4 CB] (mt) and of
-// dO [rows][2 CB] (mo) and the largest |tot|, |tr| (mx): cmax [9 CB]
-__global__ void wgrad_bounds_exact_cb(const unsigned *__restrict__ mt, const unsigned *__restrict__ mo, const unsigned *__restrict__ mx,
-                                      unsigned *__restrict__ cmax, int CB) {
-    const int c = threadIdx.x;   // CB threads
-    if (c >= CB) return;
-    const float tot = __uint_as_float(mx[0]), tr = __uint_as_float(mx[1]);
-    for (int k = 0; k < 4; ++k) cmax[CB * k + c] = mt[CB * k + c];
-    const float l = __uint_as_float(mo[c]), u = __uint_as_float(mo[CB + c]);
-    cmax[4 * CB + c] = __float_as_uint(l);
-    cmax[5 * CB + c] = __float_as_uint(tot * l);
-    cmax[6 * CB + c] = __float_as_uint(tr * l);
-    cmax[7 * CB + c] = cmax[8 * CB + c] = __float_as_uint(u);
-}
-
-// ---- the column bounds of a level's operand blocks (cmax of smp_wgrad_split) -------------------------------------------------
-// largest |x| of every column of X [rows][ld] (columns [0, 64)) into out[64] (float bits, atomicMax: out starts at 0)
-__global__ __launch_bounds__(256) void col_absmax64(const float *__restrict__ X, long long rows, int ld, unsigned *__restrict__ out) {
+// ---- the column bounds of a level's operand blocks (cmax of smp_wgrad_split / smp_wgrad_all) ----------------------------------
+// THE column-maxima loop (four rows in flight per thread): the largest |x| of columns [0, 64) of X [rows][ld] over the rows this
+// workgroup takes, reduced through LDS and added to out[64] (float bits, atomicMax: out starts at 0).  256 threads.
+__device__ __forceinline__ void col_absmax64_body(const float *__restrict__ X, long long rows, int ld, unsigned *__restrict__ out) {
     __shared__ unsigned red[64];
     if (threadIdx.x < 64) red[threadIdx.x] = 0u;
     __syncthreads();
     const int q = threadIdx.x & 15;   // channel quad
     f4v m = {0.f, 0.f, 0.f, 0.f};
     const long long step = (long long)gridDim.x * 16;
-    for (long long r0 = (long long)blockIdx.x * 16 + (threadIdx.x >> 4); r0 < rows; r0 += 4 * step) {   // four rows in flight per thread
+    for (long long r0 = (long long)blockIdx.x * 16 + (threadIdx.x >> 4); r0 < rows; r0 += 4 * step) {
         f4v v[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -1465,35 +1451,17 @@ __global__ __launch_bounds__(256) void col_absmax64(const float *__restrict__ X,
     __syncthreads();
     if (threadIdx.x < 64 && red[threadIdx.x]) atomicMax(&out[threadIdx.x], red[threadIdx.x]);
 }
-// both per-channel maxima of a level in ONE launch: blockIdx.y = 0: X0 [rows0][64] -> out[0, 64), 1: X1 [rows1][64] -> out[64, 128)
+// 64 columns of one operand (the exact bounds: wgrad_exact_bounds)
+__global__ __launch_bounds__(256) void col_absmax64(const float *__restrict__ X, long long rows, int ld, unsigned *__restrict__ out) {
+    col_absmax64_body(X, rows, ld, out);
+}
+// both per-channel maxima of a 64-channel level in ONE launch: blockIdx.y = 0: X0 [rows0][64] -> out[0, 64), 1: X1 [rows1][64] -> out[64, 128)
 __global__ __launch_bounds__(256) void level_channel_maxima(const float *__restrict__ X0, long long rows0, const float *__restrict__ X1,
                                                             long long rows1, unsigned *__restrict__ out) {
-    __shared__ unsigned red[64];
-    const float *X = blockIdx.y ? X1 : X0;
-    const long long rows = blockIdx.y ? rows1 : rows0;
-    if (threadIdx.x < 64) red[threadIdx.x] = 0u;
-    __syncthreads();
-    const int q = threadIdx.x & 15;
-    f4v m = {0.f, 0.f, 0.f, 0.f};
-    const long long step = (long long)gridDim.x * 16;
-    for (long long r0 = (long long)blockIdx.x * 16 + (threadIdx.x >> 4); r0 < rows; r0 += 4 * step) {
-        f4v v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const long long r = r0 + u * step;
-            v[u] = *reinterpret_cast<const f4v *>(X + (size_t)(r < rows ? r : r0) * 64 + 4 * q);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) m[j] = fmaxf(m[j], fabsf(v[u][j]));
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) atomicMax(&red[4 * q + j], __float_as_uint(m[j]));
-    __syncthreads();
-    if (threadIdx.x < 64 && red[threadIdx.x]) atomicMax(&out[64 * blockIdx.y + threadIdx.x], red[threadIdx.x]);
+    col_absmax64_body(blockIdx.y ? X1 : X0, blockIdx.y ? rows1 : rows0, 64, out + 64 * blockIdx.y);
 }
-// the same for other row widths: X0 [rows0][ld0], X1 [rows1][ld1], columns [0, C) of each -> out[0, C) | out[C, 2 C)  (C % 4 == 0, C <= 64)
+// the same for other row widths, one row in flight: X0 [rows0][ld0], X1 [rows1][ld1], columns [0, C) of each -> out[0, C) | out[C, 2 C)
+// (C % 4 == 0, C <= 64)
 __global__ __launch_bounds__(256) void level_channel_maxima_ld(const float *__restrict__ X0, long long rows0, int ld0, const float *__restrict__ X1,
                                                                long long rows1, int ld1, int C, unsigned *__restrict__ out) {
     __shared__ unsigned red[64];
@@ -1524,35 +1492,24 @@ __global__ void rowscale_absmax(const float *__restrict__ rs, int rows, unsigned
     atomicMax(&out[0], __float_as_uint(a));
     atomicMax(&out[1], __float_as_uint(b));
 }
-// cmax from the operands themselves (the stand-alone operator gf_smp_level_wgrad_f32: T and dO are the caller's, no level behind them):
-// exact column maxima of T [rows][256] and dO [rows][128]; mx[0..1] = largest |tot|, |tr| of rs [rows][2]
+// The exact column maxima spread over the nine operand blocks of a weight-gradient job, CB columns each: mt = the column maxima of
+// T = [S_ab | S_bc | T6 | T10], mo those of dO = [L | dU], mx[0..1] = the largest |tot|, |tr|.  One job per block of the launch, its
+// bounds `stride` words behind the job before: [S_ab | S_bc | T6 | T10 | L | tot L | tr L | dU | dU[trow]].  sub = 0: the one job of a
+// level of CB channels.  sub = 64 (C = 128): job blockIdx.x = 2 i + j of smp_wgrad_split<2> takes columns [sub i, +CB) of the blocks of
+// T and [sub j, +CB) of those of dO, whose blocks are CB + sub columns wide.
 __global__ void wgrad_bounds_exact(const unsigned *__restrict__ mt, const unsigned *__restrict__ mo, const unsigned *__restrict__ mx,
-                                   unsigned *__restrict__ cmax) {
-    const int c = threadIdx.x;   // 64 threads
-    const float tot = __uint_as_float(mx[0]), tr = __uint_as_float(mx[1]);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) cmax[64 * k + c] = mt[64 * k + c];
-    const float l = __uint_as_float(mo[c]), u = __uint_as_float(mo[64 + c]);
-    cmax[kWsACols + c] = __float_as_uint(l);
-    cmax[kWsACols + 64 + c] = __float_as_uint(tot * l);
-    cmax[kWsACols + 128 + c] = __float_as_uint(tr * l);
-    cmax[kWsACols + 192 + c] = cmax[kWsACols + 256 + c] = __float_as_uint(u);
-}
-
-// C = 128: the same for the four (i, j) jobs of smp_wgrad_split<2>: mt [512] column maxima of T [rows][512], mo [256] of dO [rows][256];
-// cmax [4][kWsACols + kWsBCols], job q = 2 i + j = blockIdx.x
-__global__ void wgrad_bounds_exact_c128(const unsigned *__restrict__ mt, const unsigned *__restrict__ mo, const unsigned *__restrict__ mx,
-                                        unsigned *__restrict__ cmax) {
+                                   unsigned *__restrict__ cmax, int CB, int stride, int sub) {
     const int c = threadIdx.x, i = blockIdx.x >> 1, j = blockIdx.x & 1;   // 64 threads
-    cmax += blockIdx.x * (kWsACols + kWsBCols);
+    if (c >= CB) return;
+    cmax += blockIdx.x * stride;
+    const int W = CB + sub;
     const float tot = __uint_as_float(mx[0]), tr = __uint_as_float(mx[1]);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) cmax[64 * k + c] = mt[128 * k + 64 * i + c];
-    const float l = __uint_as_float(mo[64 * j + c]), u = __uint_as_float(mo[128 + 64 * j + c]);
-    cmax[kWsACols + c] = __float_as_uint(l);
-    cmax[kWsACols + 64 + c] = __float_as_uint(tot * l);
-    cmax[kWsACols + 128 + c] = __float_as_uint(tr * l);
-    cmax[kWsACols + 192 + c] = cmax[kWsACols + 256 + c] = __float_as_uint(u);
+    for (int k = 0; k < 4; ++k) cmax[CB * k + c] = mt[W * k + sub * i + c];
+    const float l = __uint_as_float(mo[sub * j + c]), u = __uint_as_float(mo[W + sub * j + c]);
+    cmax[4 * CB + c] = __float_as_uint(l);
+    cmax[5 * CB + c] = __float_as_uint(tot * l);
+    cmax[6 * CB + c] = __float_as_uint(tr * l);
+    cmax[7 * CB + c] = cmax[8 * CB + c] = __float_as_uint(u);
 }
 
 }  // namespace
@@ -1563,7 +1520,8 @@ bool smp_split_products(const gf_ctx *ctx) {  // (read per call: the parity test
 }
 
 // the level's packed transposed-row table with the presence bits (see smp_rowpanel_split) in place of the plain one: for levels of
-// fewer than `row_limit` rows, unless GF_SMP_MASK_ZEROS=0 (read per call: the parity tests switch it)
+// fewer than `row_limit` rows, unless GF_SMP_MASK_ZEROS=0 (read per call: the parity tests switch it).  THE read of that switch for
+// the product and weight-gradient launches (wgrad_packed below: the weight gradients' one decision)
 static bool packed_rows(const int *trowf, int rows, int row_limit) {
     return trowf && rows < row_limit && !env_is("GF_SMP_MASK_ZEROS", '0');
 }
@@ -1707,120 +1665,78 @@ gf_status smp_rowpanel_split_c64(gf_ctx *ctx, bool forward, const float *A, cons
     return fail(ctx, GF_ERR_UNSUPPORTED, "smp_rowpanel_split: %d channels", C);
 }
 
-// The eight row block products of a fused level at C = 64 (compact layout) as partial images, split operands: the contract of
-// smp_wgrad_partials_c64 (same row ranges, same image layout, folded by the caller).  ws: where the operand columns' exponents come
-// from (smp_internal.h: WgradScales).
-gf_status smp_wgrad_partials_split_c64(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int kchunk,
-                                       int splits, float *part, const int *trow, const WgradScales &ws, const int *trowf) {
-    gf_status st = opt_in_lds(ctx, smp_wgrad_split<1>, kWsLds);
-    if (st != GF_OK) return st;
-    const bool mask = packed_rows(trowf, rows, 1 << 29);
-    GF_LAUNCH(ctx, "smpf_wgrad", smp_wgrad_split<1>, dim3((unsigned)splits), dim3(kWsThreads), kWsLds, T, dO, rowscale, rows, kchunk, part,
-              mask ? trowf : trow, ws.cmax, ws.chan, ws.smax, ws.max_tot, ws.max_tr, ws.row_max, mask ? 1 : 0, 0, 0, 0);
-    return GF_OK;
-}
+// ---------------------------------------------------------------------------------------------------------------
+// The weight gradients of a fused level's eight row block products, every channel count of the family: ONE entry point
+// (smp_wgrad_partials), ONE exact-bounds step (wgrad_exact_bounds), the two size queries, and the question whether the call reads the
+// absent blocks of T (smp_wgrad_reads_absent_blocks) -- answered from the same kernel choice and the same packed_rows decision the
+// launch makes.  smp_internal.h: WgradCall.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
 
-// The eight row block products of a fused level at C = 128 (compact layout) as partial images of 8 x 128 x 128 floats: four launches of
-// smp_wgrad_split<2>, one per 64 x 64 sub-block (i, j) of every product, each with the exact column bounds of its own operand halves
-// (column maxima of T [rows][512] and dO [rows][256] taken here, 64 columns a launch: T must hold its structural zeros).
-// words: smp_wgrad_c128_words() scratch words; part: `*splits` images (<= part_floats floats), folded by the caller.
-size_t smp_wgrad_c128_words() { return 1024 + 4 * (kWsACols + kWsBCols); }
-gf_status smp_wgrad_partials_c128(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, float *part, size_t part_floats,
-                                  FoldGroup *out, const int *trow, const int *trowf, unsigned *words) {
-    const size_t total = 8 * 128 * 128;
-    out->part = part;
-    out->n = total;
-    out->splits = 0;
-    if (rows < 1) return GF_OK;
-    // as smp_wgrad_partials_c64: one workgroup per CU, at least 8 slices each; the count depends on `rows` only
-    const int target = 256;
-    int kchunk = ((rows + target - 1) / target + kWsSlice - 1) / kWsSlice * kWsSlice;
-    if (kchunk < 8 * kWsSlice) kchunk = 8 * kWsSlice;
-    const int splits = (rows + kchunk - 1) / kchunk;
-    if ((size_t)splits * total > part_floats)
-        return fail(ctx, GF_ERR_NOMEM, "smp_wgrad_partials_c128: %d partial images, room for %zu", splits, part_floats / total);
-    out->splits = splits;
-    GF_HIP_TRY(ctx, hipMemsetAsync(words, 0, sizeof(unsigned) * 1024, ctx->stream));
-    const long long g0 = ((long long)rows + 15) / 16;
-    const unsigned g = (unsigned)(g0 < 1 ? 1 : g0 > 1024 ? 1024 : g0);
-    for (int k = 0; k < 8; ++k) GF_LAUNCH(ctx, "smpf_colmax", col_absmax64, dim3(g), dim3(256), 0, T + 64 * k, (long long)rows, 512, words + 64 * k);
-    for (int k = 0; k < 4; ++k) GF_LAUNCH(ctx, "smpf_colmax", col_absmax64, dim3(g), dim3(256), 0, dO + 64 * k, (long long)rows, 256, words + 512 + 64 * k);
-    GF_LAUNCH(ctx, "smpf_colmax", rowscale_absmax, dim3(64), dim3(256), 0, rowscale, rows, words + 768);
-    GF_LAUNCH(ctx, "smpf_colmax", wgrad_bounds_exact_c128, dim3(4), dim3(64), 0, words, words + 512, words + 768, words + 1024);
-    gf_status st = opt_in_lds(ctx, smp_wgrad_split<2>, kWsLds);
-    if (st != GF_OK) return st;
-    const bool mask = packed_rows(trowf, rows, 1 << 29);
-    for (int q = 0; q < 4; ++q) {
-        const int i = q >> 1, j = q & 1;
-        GF_LAUNCH(ctx, "smpf_wgrad", smp_wgrad_split<2>, dim3((unsigned)splits), dim3(kWsThreads), kWsLds, T, dO, rowscale, rows, kchunk, part,
-                  mask ? trowf : trow, words + 1024 + q * (kWsACols + kWsBCols), (const unsigned *)nullptr, 0.f, 0.f, 0.f, (const unsigned *)nullptr,
-                  mask ? 1 : 0, 64 * i, 64 * j, 64 * i * 128 + 64 * j);
+// which kernel a call runs
+enum class WgradKernel { None, Fp32, Split64, All, Split128 };
+WgradKernel wgrad_kernel(const gf_ctx *ctx, const WgradCall &a) {
+    switch (a.C) {
+    // 64 channels: the split-operand kernel where it has bounds to take its column exponents from, else the fp32 matrix pipe
+    case 64: return a.trow && smp_split_products(ctx) && (a.bounds.level(64) || a.words) ? WgradKernel::Split64 : WgradKernel::Fp32;
+    case 32:
+    case 16: return WgradKernel::All;
+    case 128: return WgradKernel::Split128;   // four sub-block launches of the 64-channel kernel, exact bounds only
     }
-    return GF_OK;
+    return WgradKernel::None;
+}
+// ... whether it takes the level's maxima (else exact bounds from the operands themselves)
+bool wgrad_level_bounds(WgradKernel k, const WgradCall &a) { return (k == WgradKernel::Split64 || k == WgradKernel::All) && a.bounds.level(a.C); }
+// ... and whether it walks the level's PACKED table, reading an absent S_ab / T6 block from the zero page: one row limit per kernel
+// (smp_wgrad_all keeps one bit more of a packed entry for itself)
+bool wgrad_packed(WgradKernel k, const WgradCall &a) {
+    return k != WgradKernel::Fp32 && packed_rows(a.trowf, a.rows, k == WgradKernel::All ? 1 << 28 : 1 << 29);
 }
 
+// The scratch words of a call: [0, mo) column maxima of T [rows][4 C], [mo, mx) of dO [rows][2 C], mx: max |tot|, |tr|, then from
+// `cmax` on the nine blocks' bounds of every job (wgrad_bounds_exact).  32 and 16 channels share one layout; [0, 2 C) of it also holds
+// the level's channel maxima (WgradScales::chan) of a model's level.
+struct WgradWords {
+    int mo, mx, cmax, jobs;
+    size_t total;
+};
+WgradWords wgrad_words(int C) {
+    if (C == 128) return {512, 768, 1024, 4, 1024 + 4 * (size_t)(kWsACols + kWsBCols)};
+    return {256, 384, 512, 1, 512 + 9 * (size_t)(C == 64 ? 64 : 32)};
+}
 
-// one launch of smp_wgrad_all: nf row factors per row of rowscale; xpart: with the three extra products of SMP_2D_ver7
-template <int CB>
-static gf_status launch_wgrad_all(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int splits, float *part,
-                                  const int *tr, const unsigned *cmax, const unsigned *chan, float smax, const unsigned *row_max, int packed, int nf,
-                                  float *xpart = nullptr) {
-    if (xpart) {
-        if (nf != 2) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_wgrad_all: extra products with %d row factors", nf);
-        GF_LAUNCH(ctx, "smpf_wgrad", (smp_wgrad_all<CB, 2, 3>), dim3((unsigned)splits), dim3(kW8Threads), 0, T, dO, rowscale, rows, part, tr, cmax, chan, smax,
-                  row_max, packed, xpart);
-    } else if (nf == 8) {
-        GF_LAUNCH(ctx, "smpf_wgrad", (smp_wgrad_all<CB, 8>), dim3((unsigned)splits), dim3(kW8Threads), 0, T, dO, rowscale, rows, part, tr, cmax, chan, smax,
-                  row_max, packed);
+// Exact column bounds of the operand blocks from the operands themselves (one extra pass over T and dO: T must hold its structural
+// zeros), C = 16 / 32 / 64 / 128, into words + wgrad_words(C).cmax.  The column maxima -- the next speed target named in NOTES.md -- are
+// taken HERE and nowhere else: 64 columns a launch of col_absmax64 (16 channels: the two operands are one narrow pass each).
+gf_status wgrad_exact_bounds(gf_ctx *ctx, const WgradCall &a) {
+    const int C = a.C;
+    const WgradWords w = wgrad_words(C);
+    unsigned *words = a.words;
+    GF_HIP_TRY(ctx, hipMemsetAsync(words, 0, sizeof(unsigned) * w.cmax, ctx->stream));
+    if (C >= 32) {
+        const long long g0 = ((long long)a.rows + 15) / 16;
+        const unsigned g = (unsigned)(g0 < 1 ? 1 : g0 > 1024 ? 1024 : g0);
+        for (int k = 0; k < 4 * C / 64; ++k)
+            GF_LAUNCH(ctx, "smpf_colmax", col_absmax64, dim3(g), dim3(256), 0, a.T + 64 * k, (long long)a.rows, 4 * C, words + 64 * k);
+        for (int k = 0; k < 2 * C / 64; ++k)
+            GF_LAUNCH(ctx, "smpf_colmax", col_absmax64, dim3(g), dim3(256), 0, a.dO + 64 * k, (long long)a.rows, 2 * C, words + w.mo + 64 * k);
     } else {
-        GF_LAUNCH(ctx, "smpf_wgrad", (smp_wgrad_all<CB, 2>), dim3((unsigned)splits), dim3(kW8Threads), 0, T, dO, rowscale, rows, part, tr, cmax, chan, smax,
-                  row_max, packed);
+        const long long g0 = ((long long)a.rows + 63) / 64;
+        const unsigned g = (unsigned)(g0 < 1 ? 1 : g0 > 256 ? 256 : g0);
+        GF_LAUNCH(ctx, "smpf_colmax", level_channel_maxima_ld, dim3(g, 1), dim3(256), 0, a.T, (long long)a.rows, 4 * C, (const float *)nullptr, 0ll, 0, 4 * C, words);
+        GF_LAUNCH(ctx, "smpf_colmax", level_channel_maxima_ld, dim3(g, 1), dim3(256), 0, a.dO, (long long)a.rows, 2 * C, (const float *)nullptr, 0ll, 0, 2 * C,
+                  words + w.mo);
     }
+    GF_LAUNCH(ctx, "smpf_colmax", rowscale_absmax, dim3(64), dim3(256), 0, a.rowscale, a.rows, words + w.mx);
+    const int CB = C == 128 ? 64 : C;
+    GF_LAUNCH(ctx, "smpf_colmax", wgrad_bounds_exact, dim3(w.jobs), dim3(64), 0, words, words + w.mo, words + w.mx, words + w.cmax, CB, 9 * CB, C == 128 ? 64 : 0);
     return GF_OK;
 }
-// The eight row block products of a fused level at C = 32 / 16 (compact layout) as partial images of 8 x C x C floats: smp_wgrad_all<C>.
-// Column exponents from the level's per-channel maxima (chan: [2 C] words, smax, row_max: see smp_wgrad_split), or -- chan null -- exact
-// column bounds taken from the operands themselves (one extra pass over T and dO; `words`: smp_wgrad_all_words() scratch words).
-gf_status smp_wgrad_partials_all(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int splits, float *part,
-                                  const int *trow, const int *trowf, unsigned *words, const unsigned *chan, float smax,
-                                  const unsigned *row_max, int nf, int C, float *xpart) {
-    const bool mask = packed_rows(trowf, rows, 1 << 28);
-    const int *tr = mask ? trowf : trow;
-    if (C == 16) {   // (round 5)
-        if (chan && row_max)
-            return launch_wgrad_all<16>(ctx, T, dO, rowscale, rows, splits, part, tr, (const unsigned *)nullptr, chan, smax, row_max, mask ? 1 : 0, nf, xpart);
-        // host-built level tables: exact column bounds from the operands themselves -- T [rows][64] and dO [rows][32] are one
-        // "channel maxima" pass each (words [0, 64) and [256, 288)), then the nine blocks' bounds (words [512, 512 + 144))
-        if (nf != 2) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_wgrad_all: exact column bounds with per-product row factors");
-        GF_HIP_TRY(ctx, hipMemsetAsync(words, 0, sizeof(unsigned) * 512, ctx->stream));
-        const long long g0 = ((long long)rows + 63) / 64;
-        const unsigned g = (unsigned)(g0 < 1 ? 1 : g0 > 256 ? 256 : g0);
-        GF_LAUNCH(ctx, "smpf_colmax", level_channel_maxima_ld, dim3(g, 1), dim3(256), 0, T, (long long)rows, 64, (const float *)nullptr, 0ll, 0, 64, words);
-        GF_LAUNCH(ctx, "smpf_colmax", level_channel_maxima_ld, dim3(g, 1), dim3(256), 0, dO, (long long)rows, 32, (const float *)nullptr, 0ll, 0, 32, words + 256);
-        GF_LAUNCH(ctx, "smpf_colmax", rowscale_absmax, dim3(64), dim3(256), 0, rowscale, rows, words + 384);
-        GF_LAUNCH(ctx, "smpf_colmax", wgrad_bounds_exact_cb, dim3(1), dim3(64), 0, words, words + 256, words + 384, words + 512, 16);
-        return launch_wgrad_all<16>(ctx, T, dO, rowscale, rows, splits, part, tr, words + 512, (const unsigned *)nullptr, 0.f, (const unsigned *)nullptr, mask ? 1 : 0, nf, xpart);
-    }
-    if (C != 32) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_wgrad_all: %d channels", C);
-    constexpr int CB = 32;
-    if (chan && row_max)
-        return launch_wgrad_all<CB>(ctx, T, dO, rowscale, rows, splits, part, tr, (const unsigned *)nullptr, chan, smax, row_max, mask ? 1 : 0, nf, xpart);
-    GF_HIP_TRY(ctx, hipMemsetAsync(words, 0, sizeof(unsigned) * 512, ctx->stream));
-    const long long g0 = ((long long)rows + 15) / 16;
-    const unsigned g = (unsigned)(g0 < 1 ? 1 : g0 > 1024 ? 1024 : g0);
-    // column maxima in chunks of 64 columns: T [rows][128] -> words [0, 128), dO [rows][64] -> words [256, 320)
-    for (int k = 0; k < 4 * CB / 64; ++k) GF_LAUNCH(ctx, "smpf_colmax", col_absmax64, dim3(g), dim3(256), 0, T + 64 * k, (long long)rows, 4 * CB, words + 64 * k);
-    for (int k = 0; k < 2 * CB / 64; ++k) GF_LAUNCH(ctx, "smpf_colmax", col_absmax64, dim3(g), dim3(256), 0, dO + 64 * k, (long long)rows, 2 * CB, words + 256 + 64 * k);
-    if (nf != 2) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_wgrad_all: exact column bounds with per-product row factors");
-    GF_LAUNCH(ctx, "smpf_colmax", rowscale_absmax, dim3(64), dim3(256), 0, rowscale, rows, words + 384);
-    GF_LAUNCH(ctx, "smpf_colmax", wgrad_bounds_exact_cb, dim3(1), dim3(64), 0, words, words + 256, words + 384, words + 512, CB);
-    return launch_wgrad_all<CB>(ctx, T, dO, rowscale, rows, splits, part, tr, words + 512, (const unsigned *)nullptr, 0.f, (const unsigned *)nullptr, mask ? 1 : 0, nf, xpart);
-}
-size_t smp_wgrad_all_words() { return 512 + 9 * 32; }
+
 // workgroups (= partial image sets) of the C = 32 / 16 weight-gradient launch for a level of `rows` rows.  smp_wgrad_all keeps one wave
 // per SIMD (its eight accumulators): ONE workgroup per CU -- measured at C = 32, cfg3: 0.44 ms with 256 workgroups, 0.53 with 512 (the
 // second half waits for whole CUs), 0.72 with 1024.
-int smp_wgrad_all_splits(gf_ctx *ctx, long long rows) {
+int wgrad_all_splits(gf_ctx *ctx, long long rows) {
     static int cu_count[64] = {};
     const int di = ctx->device & 63;
     if (!cu_count[di]) {
@@ -1830,34 +1746,113 @@ int smp_wgrad_all_splits(gf_ctx *ctx, long long rows) {
     const long long slices = (rows + 15) / 16, want = slices / 8;
     return (int)(want < 1 ? 1 : want > cap ? cap : want);
 }
+// the partial images of a call, and the rows of one (0: smp_wgrad_all deals slices, not ranges).  They depend on `rows` only (and the
+// device's CU count): results are reproducible.  64 / 128 channels: one workgroup per CU, at least 8 slices each.
+struct WgradPlan {
+    int splits, kchunk;
+};
+WgradPlan wgrad_plan(gf_ctx *ctx, int rows, int C) {
+    if (C == 32 || C == 16) return {wgrad_all_splits(ctx, rows), 0};
+    const int target = 256, slice = C == 128 ? kWsSlice : lds_image::BK;
+    int kchunk = ((rows + target - 1) / target + slice - 1) / slice * slice;
+    if (kchunk < 8 * slice) kchunk = 8 * slice;
+    return {(rows + kchunk - 1) / kchunk, kchunk};
+}
 
-size_t smp_wgrad_bound_words() { return 128; }
-// words: [0, 64) largest |f_{l-1}| per channel, [64, 128) largest |dz_l| per channel, accumulated here with atomicMax (the caller zeroes
-// them once per pass).  fprev [prev_rows][64]: f_{l-1} or the per-panel maxima its combine-forward left; dsrc [drows][64]: the
-// per-workgroup maxima of this level's combine-backward.  One launch.
-gf_status smp_wgrad_channel_maxima(gf_ctx *ctx, const float *fprev, long long prev_rows, const float *dsrc, long long drows, unsigned *words) {
-    const long long big = prev_rows > drows ? prev_rows : drows, g0 = (big + 63) / 64;
-    const unsigned g = (unsigned)(g0 < 1 ? 1 : g0 > 256 ? 256 : g0);
-    GF_LAUNCH(ctx, "smpf_colmax", level_channel_maxima, dim3(g, 2), dim3(256), 0, fprev, prev_rows, dsrc, drows, words);
+// one launch of smp_wgrad_all: nf row factors per row of rowscale; xpart: with the three extra products of SMP_2D_ver7
+template <int CB>
+gf_status launch_wgrad_all(gf_ctx *ctx, const WgradCall &a, int splits, const int *tr, const unsigned *cmax, const WgradScales &b, int packed, float *xpart) {
+    if (xpart) {
+        GF_LAUNCH(ctx, "smpf_wgrad", (smp_wgrad_all<CB, 2, 3>), dim3((unsigned)splits), dim3(kW8Threads), 0, a.T, a.dO, a.rowscale, a.rows, a.part, tr, cmax, b.chan,
+                  b.smax, b.row_max, packed, xpart);
+    } else if (a.nf == 8) {
+        GF_LAUNCH(ctx, "smpf_wgrad", (smp_wgrad_all<CB, 8>), dim3((unsigned)splits), dim3(kW8Threads), 0, a.T, a.dO, a.rowscale, a.rows, a.part, tr, cmax, b.chan,
+                  b.smax, b.row_max, packed);
+    } else {
+        GF_LAUNCH(ctx, "smpf_wgrad", (smp_wgrad_all<CB, 2>), dim3((unsigned)splits), dim3(kW8Threads), 0, a.T, a.dO, a.rowscale, a.rows, a.part, tr, cmax, b.chan,
+                  b.smax, b.row_max, packed);
+    }
     return GF_OK;
 }
-gf_status smp_wgrad_channel_maxima_ld(gf_ctx *ctx, const float *fprev, long long prev_rows, int ld0, const float *dsrc, long long drows, int ld1, int C,
-                                      unsigned *words) {
-    const long long big = prev_rows > drows ? prev_rows : drows, g0 = (big + 63) / 64;
-    const unsigned g = (unsigned)(g0 < 1 ? 1 : g0 > 256 ? 256 : g0);
-    GF_LAUNCH(ctx, "smpf_colmax", level_channel_maxima_ld, dim3(g, 2), dim3(256), 0, fprev, prev_rows, ld0, dsrc, drows, ld1, C, words);
+// W = 1: the 64-channel launch; W = 2: the four (i, j) sub-block launches at 128 channels, each with its own job's bounds
+template <int W>
+gf_status launch_wgrad_split(gf_ctx *ctx, const WgradCall &a, const WgradPlan &p, const int *tr, const unsigned *cmax, const WgradScales &b, int packed) {
+    const gf_status st = opt_in_lds(ctx, smp_wgrad_split<W>, kWsLds);
+    if (st != GF_OK) return st;
+    for (int q = 0; q < W * W; ++q) {
+        const int i = q >> 1, j = q & 1;
+        GF_LAUNCH(ctx, "smpf_wgrad", smp_wgrad_split<W>, dim3((unsigned)p.splits), dim3(kWsThreads), kWsLds, a.T, a.dO, a.rowscale, a.rows, p.kchunk, a.part, tr,
+                  cmax ? cmax + q * (kWsACols + kWsBCols) : cmax, b.chan, b.smax, b.max_tot, b.max_tr, b.row_max, packed, 64 * i, 64 * j, 64 * i * 128 + 64 * j);
+    }
     return GF_OK;
 }
-// the same from the operands themselves (gf_smp_level_wgrad_f32): words = 256 + 128 + 2 scratch words (zeroed here) + the bounds
-size_t smp_wgrad_bound_words_exact() { return 512 + kWsACols + kWsBCols; }
-gf_status smp_wgrad_column_bounds_exact(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, unsigned *words) {
-    GF_HIP_TRY(ctx, hipMemsetAsync(words, 0, sizeof(unsigned) * 512, ctx->stream));
-    const long long g0 = ((long long)rows + 15) / 16;
-    const unsigned g = (unsigned)(g0 < 1 ? 1 : g0 > 1024 ? 1024 : g0);
-    for (int k = 0; k < 4; ++k) GF_LAUNCH(ctx, "smpf_colmax", col_absmax64, dim3(g), dim3(256), 0, T + 64 * k, (long long)rows, 256, words + 64 * k);
-    for (int k = 0; k < 2; ++k) GF_LAUNCH(ctx, "smpf_colmax", col_absmax64, dim3(g), dim3(256), 0, dO + 64 * k, (long long)rows, 128, words + 256 + 64 * k);
-    GF_LAUNCH(ctx, "smpf_colmax", rowscale_absmax, dim3(64), dim3(256), 0, rowscale, rows, words + 384);
-    GF_LAUNCH(ctx, "smpf_colmax", wgrad_bounds_exact, dim3(1), dim3(64), 0, words, words + 256, words + 384, words + 512);
+
+}  // namespace
+
+size_t smp_wgrad_words(int C, bool exact) { return C == 64 && !exact ? 128 : wgrad_words(C).total; }
+
+// (the eight products' images, the extra products' behind them, each with the room splitk_fold's second stage takes behind its images)
+size_t smp_wgrad_part_floats(gf_ctx *ctx, int rows, int C, int nx) {
+    const size_t splits = (size_t)wgrad_plan(ctx, rows, C).splits;
+    return (splits + (splits + 31) / 32) * (size_t)(8 + nx) * C * C;
+}
+
+bool smp_wgrad_reads_absent_blocks(const gf_ctx *ctx, const WgradCall &a) {
+    const WgradKernel k = wgrad_kernel(ctx, a);
+    // the fp32 kernel does not mask; exact bounds are maxima over ALL of T; a split kernel masks iff it walks the packed table
+    return !wgrad_level_bounds(k, a) || !wgrad_packed(k, a);
+}
+
+gf_status smp_wgrad_partials(gf_ctx *ctx, const WgradCall &a, FoldGroup *out, FoldGroup *xout) {
+    const size_t CC = (size_t)a.C * a.C;
+    *out = {a.part, 0, 8 * CC};
+    if (xout) *xout = {nullptr, 0, 3 * CC};
+    if (a.rows < 1) return GF_OK;
+    const WgradKernel k = wgrad_kernel(ctx, a);
+    if (k == WgradKernel::None) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_wgrad_partials: %d channels", a.C);
+    if (a.nf != 2 && !(a.nf == 8 && k == WgradKernel::All)) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_wgrad_partials: %d row factors at %d channels", a.nf, a.C);
+    const bool level = wgrad_level_bounds(k, a), exact = !level && k != WgradKernel::Fp32;
+    if (exact && a.nf != 2) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_wgrad_partials: exact column bounds with per-product row factors");
+    if (exact && !a.words) return fail(ctx, GF_ERR_INVALID, "smp_wgrad_partials: exact column bounds without their scratch words");
+    const WgradPlan p = wgrad_plan(ctx, a.rows, a.C);
+    if ((size_t)p.splits * 8 * CC > a.part_floats)
+        return fail(ctx, GF_ERR_NOMEM, "smp_wgrad_partials: %d partial images, room for %zu", p.splits, a.part_floats / (8 * CC));
+    out->splits = p.splits;
+    // SMP_2D_ver7's three extra products ride in smp_wgrad_all (their operands are fragments it already holds): three more images per
+    // workgroup -- where the kernel has them (plain row factors) and the workspace the room; else the caller's own products
+    float *xpart = nullptr;
+    if (xout && k == WgradKernel::All && a.nf == 2 && smp_wgrad_part_floats(ctx, a.rows, a.C, 3) <= a.part_floats) {
+        xpart = a.part + smp_wgrad_part_floats(ctx, a.rows, a.C, 0);
+        *xout = {xpart, p.splits, 3 * CC};
+    }
+    if (exact) {
+        const gf_status st = wgrad_exact_bounds(ctx, a);
+        if (st != GF_OK) return st;
+    }
+    const unsigned *cmax = exact ? a.words + wgrad_words(a.C).cmax : nullptr;
+    const WgradScales b = level ? a.bounds : WgradScales();
+    const bool mask = wgrad_packed(k, a);
+    const int *tr = mask ? a.trowf : a.trow;
+    switch (k) {
+    case WgradKernel::Fp32: return smp_wgrad_fp32_c64(ctx, a.T, a.dO, a.rowscale, a.rows, p.kchunk, p.splits, a.part, a.trow);
+    case WgradKernel::Split64: return launch_wgrad_split<1>(ctx, a, p, tr, cmax, b, mask ? 1 : 0);
+    case WgradKernel::Split128: return launch_wgrad_split<2>(ctx, a, p, tr, cmax, b, mask ? 1 : 0);
+    default: break;
+    }
+    return a.C == 32 ? launch_wgrad_all<32>(ctx, a, p.splits, tr, cmax, b, mask ? 1 : 0, xpart) : launch_wgrad_all<16>(ctx, a, p.splits, tr, cmax, b, mask ? 1 : 0, xpart);
+}
+
+// words: [0, C) largest |f_{l-1}| per channel, [C, 2 C) largest |dz_l| per channel, accumulated here with atomicMax (the caller zeroes
+// them).  fprev [prev_rows][ld0]: f_{l-1} or the per-panel maxima its combine-forward left; dsrc [drows][ld1]: the per-workgroup maxima
+// of this level's combine-backward.  One launch: the four-rows-in-flight kernel for 64-float rows of 64 channels, else the general one.
+gf_status smp_wgrad_channel_maxima(gf_ctx *ctx, const float *fprev, long long prev_rows, int ld0, const float *dsrc, long long drows, int ld1, int C,
+                                   unsigned *words) {
+    const long long big = prev_rows > drows ? prev_rows : drows, g0 = (big + 63) / 64;
+    const unsigned g = (unsigned)(g0 < 1 ? 1 : g0 > 256 ? 256 : g0);
+    if (C == 64 && ld0 == 64 && ld1 == 64)
+        GF_LAUNCH(ctx, "smpf_colmax", level_channel_maxima, dim3(g, 2), dim3(256), 0, fprev, prev_rows, dsrc, drows, words);
+    else
+        GF_LAUNCH(ctx, "smpf_colmax", level_channel_maxima_ld, dim3(g, 2), dim3(256), 0, fprev, prev_rows, ld0, dsrc, drows, ld1, C, words);
     return GF_OK;
 }
 

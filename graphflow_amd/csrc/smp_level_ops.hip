@@ -37,7 +37,7 @@ __global__ void scale_words(unsigned *__restrict__ w, int n, const unsigned *__r
     if (i < n) w[i] = __float_as_uint(__uint_as_float(w[i]) * __uint_as_float(by[0]));
 }
 
-// rows the gathered operand dU[trow] of smp_wgrad_all may lie from its own row (kTrowWindow of smp_level_c64_split.hip)
+// rows the gathered operand dU[trow] of the weight-gradient kernels may lie from its own row (kTrowWindow of smp_level_c64_split.hip)
 constexpr long long kGatherWindow = (long long)kFusedMaxField * kFusedMaxField;
 
 // The tables of a stand-alone call, checked on the host (one blocking copy each: these are test operators): every trow inside the
@@ -90,21 +90,16 @@ gf_status gf_smp_level_wgrad_f32(gf_ctx *ctx, int rows, const float *T, const fl
     if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
     if (rows < 1 || !T || !dO || !rowscale || !trow || !dWst) return fail(ctx, GF_ERR_INVALID, "gf_smp_level_wgrad_f32: bad argument");
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t total = 8 * 4096, bound_words = gf::smp_wgrad_bound_words_exact();
-    // workspace: up to 256 + 8 partial images, then the column bounds of the operands (exact maxima: there is no level behind them)
-    const size_t img_floats = (size_t)(264 + 16) * total;
-    gf_status st = gf::ensure_ws(ctx, sizeof(float) * (img_floats + bound_words) + 256);
+    // workspace: the partial images, then the scratch words of the operands' column bounds (exact maxima: there is no level behind them)
+    const size_t part_floats = gf::smp_wgrad_part_floats(ctx, rows, 64);
+    gf_status st = gf::ensure_ws(ctx, sizeof(float) * (part_floats + gf::smp_wgrad_words(64)) + 256);
     if (st != GF_OK) return st;
     float *ws = static_cast<float *>(ctx->ws);
-    unsigned *bw = reinterpret_cast<unsigned *>(ws + img_floats);
-    st = gf::smp_wgrad_column_bounds_exact(ctx, T, dO, rowscale, rows, bw);
-    if (st != GF_OK) return st;
+    const gf::WgradCall wc = {T, dO, rowscale, rows, 64, 2, trow, nullptr, gf::WgradScales(), reinterpret_cast<unsigned *>(ws + part_floats), ws, part_floats};
     gf::FoldGroup fg;
-    gf::WgradScales sc;
-    sc.cmax = bw + 512;
-    st = gf::smp_wgrad_partials_c64(ctx, T, dO, rowscale, rows, ws, (size_t)264 * total, &fg, trow, sc);
+    st = gf::smp_wgrad_partials(ctx, wc, &fg);
     if (st != GF_OK) return st;
-    return gf::splitk_fold(ctx, fg.part, dWst, total, fg.splits, 0);
+    return gf::splitk_fold(ctx, fg.part, dWst, fg.n, fg.splits, 0);
 }
 
 gf_status gf_smp_level_products_ex_f32(gf_ctx *ctx, int backward, int C, int nf, int nx, int rows, const float *A, const float *rowfac,
@@ -165,46 +160,34 @@ gf_status gf_smp_level_wgrad_ex_f32(gf_ctx *ctx, int C, int nf, int nx, int rows
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     st = gf::check_tables(ctx, who, rows, trow, trowf, gf::kGatherWindow);
     if (st != GF_OK) return st;
-    // workspace: the eight products' partial images (one set per workgroup, and the fold's second stage), the extra products', the
-    // scratch words of the column bounds, three words of row-factor maxima
-    const size_t CC = (size_t)C * C;
-    if (C == 128) {   // four sub-block launches of the C = 64 kernel (smp_wgrad_partials_c128): at most 256 images and the fold's nine
-        const size_t cap = (size_t)(rows / 128 + 1 < 256 ? rows / 128 + 1 : 256) + 9, words128 = gf::smp_wgrad_c128_words();
-        st = gf::ensure_ws(ctx, sizeof(float) * (cap * 8 * CC + words128) + 256);
-        if (st != GF_OK) return st;
-        float *part128 = static_cast<float *>(ctx->ws);
-        gf::FoldGroup fg;
-        st = gf::smp_wgrad_partials_c128(ctx, T, dO, rowfac, rows, part128, (cap - 9) * 8 * CC, &fg, trow, trowf,
-                                         reinterpret_cast<unsigned *>(part128 + cap * 8 * CC));
-        if (st != GF_OK) return st;
-        return gf::splitk_fold(ctx, fg.part, dWst, 8 * CC, fg.splits, 0);
-    }
-    const int splits = gf::smp_wgrad_all_splits(ctx, rows);
-    const size_t images = (size_t)splits + (splits + 31) / 32, words = gf::smp_wgrad_all_words();
-    st = gf::ensure_ws(ctx, sizeof(float) * (images * 11 * CC + words + 4) + 256);
+    // workspace: the eight products' partial images and the extra products' (each with its fold's second stage), the scratch words of
+    // the column bounds, three words of row-factor maxima
+    const size_t part_floats = gf::smp_wgrad_part_floats(ctx, rows, C, nx), words = gf::smp_wgrad_words(C);
+    st = gf::ensure_ws(ctx, sizeof(float) * (part_floats + words + 4) + 256);
     if (st != GF_OK) return st;
-    float *part = static_cast<float *>(ctx->ws), *xpart = part + images * 8 * CC;
-    unsigned *bw = reinterpret_cast<unsigned *>(xpart + images * 3 * CC), *rmax = bw + words;
-    const unsigned *chan = nullptr;
+    float *part = static_cast<float *>(ctx->ws);
+    unsigned *bw = reinterpret_cast<unsigned *>(part + part_floats), *rmax = bw + words;
+    gf::WgradCall wc = {T, dO, rowfac, rows, C, nf, trow, trowf, gf::WgradScales(), bw, part, part_floats};
     if (nf == 8) {
         // per-product row factors: the kernel takes the level's bounds, not exact ones.  Any upper bound will do: chan = the largest
         // magnitude of every channel over the four blocks of T | over the two of dO (widened by the factors of products 3 and 4),
         // smax = 1, row_max = the largest factors that ride on tot / on tr
         GF_HIP_TRY(ctx, hipMemsetAsync(bw, 0, sizeof(unsigned) * (words + 4), ctx->stream));
         for (int k = 0; k < 4; ++k) {
-            st = gf::smp_wgrad_channel_maxima_ld(ctx, T + k * C, rows, 4 * C, dO + (k & 1) * C, k < 2 ? rows : 0, 2 * C, C, bw);
+            st = gf::smp_wgrad_channel_maxima(ctx, T + k * C, rows, 4 * C, dO + (k & 1) * C, k < 2 ? rows : 0, 2 * C, C, bw);
             if (st != GF_OK) return st;
         }
         GF_LAUNCH(ctx, "smpf_colmax", gf::rowfac8_absmax, dim3(64), dim3(256), 0, rowfac, rows, rmax);
         GF_LAUNCH(ctx, "smpf_colmax", gf::scale_words, dim3(1), dim3(64), 0, bw + C, C, rmax + 2);
-        chan = bw;
+        wc.bounds.chan = bw, wc.bounds.smax = 1.f, wc.bounds.row_max = rmax;
     }
-    st = gf::smp_wgrad_partials_all(ctx, T, dO, rowfac, rows, splits, part, trow, trowf, bw, chan, 1.f, chan ? rmax : nullptr, nf, C,
-                                    nx == 3 ? xpart : nullptr);
+    gf::FoldGroup fg, xg = {nullptr, 0, 0};
+    st = gf::smp_wgrad_partials(ctx, wc, &fg, nx == 3 ? &xg : nullptr);
     if (st != GF_OK) return st;
-    st = gf::splitk_fold(ctx, part, dWst, 8 * CC, splits, 0);
+    st = gf::splitk_fold(ctx, fg.part, dWst, fg.n, fg.splits, 0);
     if (st != GF_OK || nx != 3) return st;
-    return gf::splitk_fold(ctx, xpart, dX, 3 * CC, splits, 0);
+    if (!xg.splits) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: no kernel with the three extra products at %d channels / %d row factors", who, C, nf);
+    return gf::splitk_fold(ctx, xg.part, dX, xg.n, xg.splits, 0);
 }
 
 }  // extern "C"

@@ -772,11 +772,10 @@ gf_status alloc_readout(gf_smp *s, int nMol) {
     Taker t = {s};
     t.put(&s->x, B.x);
     s->wbound = nullptr;
-    if (s->cfg.square() && C == 64) t.alloc(&s->wbound, smp_wgrad_bound_words() * (size_t)(L + 1));
-    else if (s->cfg.square() && (C == 32 || C == 16))   // scratch words of the C = 32 / 16 weight-gradient kernel's column bounds
-        t.alloc(&s->wbound, smp_wgrad_all_words() * (size_t)(L + 1));
-    else if (s->cfg.square() && C == 128 && s->cfg.nContractions == 18 && smp_c128_switch())   // ... and of the four sub-block launches at C = 128
-        t.alloc(&s->wbound, smp_wgrad_c128_words() * (size_t)(L + 1));
+    // scratch words of the fused levels' weight gradients (channel maxima, exact column bounds; a 64-channel level keeps only its maxima);
+    // 128 channels: the plain 18-slice model's four sub-block launches
+    if (s->cfg.square() && (smp_panel_channels(C) || (C == 128 && s->cfg.nContractions == 18 && smp_c128_switch())))
+        t.alloc(&s->wbound, smp_wgrad_words(C, C != 64) * (size_t)(L + 1));
     t.alloc(&s->sh, (size_t)top.nNodes * C);
     t.alloc(&s->vf, (size_t)top.nNodes * C);
     t.alloc(&s->dsh, (size_t)top.nNodes * C);

@@ -1562,6 +1562,52 @@ def test_device_level_tables_equal_the_host_built_ones(gf, monkeypatch, C, fused
     assert np.isfinite(a[2]).all() and np.abs(a[2]).max() > 0
 
 
+def _host_vs_device_tables_small_levels(gf, monkeypatch, C):
+    """Gradients per parameter block (H, K_l, b_l, W) of a two-level model at C = 32 / 16 with host-built tables -- no device
+    statistics words, so the weight gradients take EXACT column bounds (smp_wgrad_partials), maxima over all of T, whose absent
+    blocks must hold their zeros first -- against the same model on device-built tables (the level's channel maxima)."""
+    L, F, D, cap = 2, 5, 2, 9
+    mols = [synthetic_molecule(4100 + i, nV=6 + (3 * i) % 4)[:2] for i in range(3)]   # 6, 9 and 8 atoms
+    tg = np.array([synthetic_molecule(4100 + i, nV=6 + (3 * i) % 4)[2] for i in range(3)])
+    params = smp_params(C, F, D, L, 11)
+    got = {}
+    for mode in ("0", "1"):
+        monkeypatch.setenv("GF_PREP_DEVICE_TABLES", mode)
+        got[mode] = run_batch(gf, mols, tg, params, L, C, F, D, cap)
+    assert np.array_equal(got["0"][0], got["1"][0]) and np.array_equal(got["0"][2], got["1"][2])   # (the same tables: the same forward)
+    g0, g1 = got["0"][3], got["1"][3]
+    assert np.isfinite(g0).all() and np.abs(g0).max() > 0
+    o, blocks = C * F * (D + 1), [("H", 0, C * F * (D + 1))]
+    for l in range(1, L + 1):
+        blocks += [("K%d" % l, o, o + 18 * C * C), ("b%d" % l, o + 18 * C * C, o + 18 * C * C + C)]
+        o += 18 * C * C + C
+    blocks.append(("W", o, o + C))
+    assert o + C == g0.size
+    for name, a, b in blocks:
+        e = rel_err(g0[a:b], g1[a:b])
+        print("host vs device tables, C = %d, block %s: %.2e" % (C, name, e))
+        assert e <= TOL_SELF, (name, e)   # (the bound of the file's fused-vs-op-by-op comparisons: two fp32 forms of the same sums)
+
+
+@pytest.mark.parametrize("C", [32, 16])
+def test_host_built_tables_take_exact_bounds_at_32_and_16_channels(gf, monkeypatch, C):
+    _host_vs_device_tables_small_levels(gf, monkeypatch, C)
+
+
+def test_host_built_tables_take_exact_bounds_with_dense_reads():
+    """The same two cases in a process with GF_SMP_MASK_ZEROS=0: nobody masks, tables-forward writes every block, and the caller's
+    zero-fill question and the kernel's choice of table (smp_wgrad_reads_absent_blocks / wgrad_packed) must still agree."""
+    import subprocess
+    import sys
+    env = dict(os.environ, GF_SMP_MASK_ZEROS="0")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k",
+                        "test_host_built_tables_take_exact_bounds_at_32_and_16_channels", "-p", "no:cacheprovider"], env=env,
+                       capture_output=True, text=True, timeout=300)
+    tail = (r.stdout + r.stderr)[-2000:]
+    assert r.returncode == 0, tail
+    assert "2 passed" in tail and "failed" not in tail, tail
+
+
 def test_row_flags_count_the_rows_with_data(gf):
     """The structural zeros the C = 64 level skips, counted from the receptive fields: row (a, b) of the S_ab / T6 blocks has data when
     b lies in the field of a's source; row (b, c) of the S_bc / T10 blocks when some source holds both (SMP_omega.h:461-474: the
