@@ -503,6 +503,7 @@ gf_status smp_contract(gf_smp *s, int l, bool backward) {
 }  // namespace
 
 LevelKind smp_level_kind(const gf_smp *s, int l) {
+    if (s->cfg.first_order) return LevelKind::Theta;   // (one plan: gf_smp_set_fused has no effect)
     if (s->fused && smp_fused_supported(s, l)) return LevelKind::Fused18;
     return smp_gamma_fused(s, l) ? LevelKind::Gamma : LevelKind::OpByOp;
 }
@@ -568,6 +569,7 @@ void gf::smp_derive_plan(gf_smp *s, bool allow_embed) {
     s->cfg = s->ucfg;
     s->dup_channels = 0;
     s->n_extra = 0;
+    if (s->cfg.first_order) return;   // (the first-order level takes any channel count: computed at the caller's)
     {
         const bool no_pad = gf::env_is("GF_SMP_PAD_CHANNELS", '0');
         const int C = s->cfg.nChanels;
@@ -630,6 +632,21 @@ gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channel
     s->cfg.custom_matmul = cfg->custom_matmul ? 1 : 0;
     s->cfg.physics = cfg->physics ? 1 : 0;
     s->cfg.nClass = nClass;
+    if (cfg->first_order) {   // SMP_theta: K_l = [2 C'][C], per-size blocks of max_nVertices entries (gfsmp::Config::first_order)
+        if (nClass) {
+            delete s;
+            return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: a first-order model (first_order = 1) has no classifier read-out");
+        }
+        if (cfg->nContractions || cfg->custom_matmul || cfg->max_nVertices < cfg->max_receptive_field) {
+            delete s;
+            return fail(ctx, GF_ERR_INVALID, "gf_smp_create: first_order = 1 needs nContractions = custom_matmul = 0 and max_nVertices (%d) >= "
+                                             "max_receptive_field (%d)", cfg->max_nVertices, cfg->max_receptive_field);
+        }
+        s->cfg.first_order = 1;
+        s->cfg.max_nVertices = cfg->max_nVertices;
+        s->cfg.nContractions = 2;
+        s->grad_allreduce = 0;   // (no data-parallel exchange: gf_smp_set_grad_allreduce(.., 1) is refused)
+    }
     s->ucfg = s->cfg;
     s->req_pad_channels = pad_channels;
     s->req_min_pad = min_pad;
@@ -640,11 +657,11 @@ gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channel
     }
     // (a tower of SMP_gamma_physics / SMP_gamma_pairgraphs: RisiContraction_4, K_l [4 C_{l-1}][C_l], computed at its own halving widths --
     //  smp_derive_plan pads only `_18` towers; the gamma tower level is smp_level_gamma.hip's rectangular one)
-    if (s->cfg.physics && (s->cfg.nDepth != 0 || (s->cfg.nContractions != 18 && s->cfg.nContractions != 4) || s->cfg.custom_matmul)) {
+    if (s->cfg.physics && (s->cfg.nDepth != 0 || (s->cfg.nContractions != 18 && s->cfg.nContractions != 4 && !s->cfg.first_order) || s->cfg.custom_matmul)) {
         delete s;
         return fail(ctx, GF_ERR_INVALID, "gf_smp_create: a physics tower has nDepth 0 (raw features), RisiContraction_18 or _4 and [nK C', C] weights");
     }
-    if (s->cfg.nContractions != 4 && s->cfg.nContractions != 10 && s->cfg.nContractions != 18 && s->cfg.nContractions != 50) {
+    if (!s->cfg.first_order && s->cfg.nContractions != 4 && s->cfg.nContractions != 10 && s->cfg.nContractions != 18 && s->cfg.nContractions != 50) {
         const int bad = cfg->nContractions;
         delete s;
         return fail(ctx, GF_ERR_INVALID, "gf_smp_create: nContractions = %d (expected 4, 10, 18 or 50)", bad);
@@ -678,6 +695,9 @@ extern "C" {
 
 // (a gamma physics tower is built by gf_smp_model_create only: the single-model handle keeps refusing it)
 gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out) {
+    if (cfg && cfg->physics && cfg->first_order)
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_create: first_order = 1 has no single-handle physics tower: set physics = 0, or build SMP_theta_physics / "
+                                         "SMP_theta_pairgraphs with gf_smp_model_create (first_order = 1)");
     if (cfg && cfg->physics && cfg->nContractions == 4)
         return fail(ctx, GF_ERR_INVALID, "gf_smp_create: nContractions = 4 (SMP_gamma) has no single-handle physics tower: set physics = 0, or build "
                                          "SMP_gamma_physics / SMP_gamma_pairgraphs with gf_smp_model_create (nContractions = 4)");
@@ -708,6 +728,8 @@ size_t gf_smp_param_count(const gf_smp *s) { return s ? gf::param_count(s->ucfg)
 gf_status gf_smp_create_classifier(gf_ctx *ctx, const gf_smp_config *cfg, int nClass, gf_smp **out) {
     if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
     if (!cfg || !out) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: null argument");
+    if (cfg->first_order)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: a first-order model (first_order = 1) has no classifier read-out");
     if (cfg->physics) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: a physics tower has no read-out of its own (physics = 0)");
     if (nClass < 2) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: nClass = %d (at least 2)", nClass);
     return gf::smp_create(ctx, cfg, /*pad_channels=*/true, out, /*min_pad=*/0, nClass);
@@ -781,6 +803,7 @@ gf_status readout_level(gf_smp *s, int l, float *sh, float *vf, bool panels) {
     const gfsmp::LevelLayout &h = s->lay.level[l];
     const gf_smp::DevLevel &d = s->lv[l];
     const int Cc = s->cfg.level_channels(l), nodes = h.nNodes;
+    if (s->cfg.first_order) return smp_theta_readout(s, l, sh, vf);   // (column sums over the node's s rows: f_l[v] is [s][C])
     const auto from_panels = !panels ? nullptr : Cc == 64 ? readout_nodes_panels<64> : Cc == 32 ? readout_nodes_panels<32>
                                               : Cc == 16 ? readout_nodes_panels<16> : nullptr;   // (smp_panel_channels)
     if (from_panels)   // 256 / Cc nodes per workgroup
@@ -827,7 +850,7 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
     s->bwd_consumed = false;
     st = dup_level(s, 0);   // (SMP_2D_ver6 on the 18-slice level: channels [C, 2C) <- the transposed matrices; level 0: copies)
     if (st != GF_OK) return st;
-    if (s->fused) {
+    if (s->fused && !s->cfg.first_order) {
         if (s->wbound && C == 64) GF_HIP_TRY(ctx, hipMemsetAsync(s->wbound, 0, sizeof(unsigned) * smp_wgrad_words(64, false) * (size_t)(L + 1), ctx->stream));
         st = smp_fused_stack_all(s, K);
         if (st != GF_OK) return st;
@@ -836,6 +859,7 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
         switch (kind[l]) {
         case LevelKind::Fused18: st = smp_fused_forward_level(s, l, K[l], b[l]); break;
         case LevelKind::Gamma: st = smp_gamma_forward_level(s, l, K[l], b[l]); break;   // products on the rows of level l - 1, one gather into f_l
+        case LevelKind::Theta: st = smp_theta_forward_level(s, l, K[l], b[l]); break;   // the same shape of level, first order (b[l]: the per-size block)
         case LevelKind::OpByOp: st = forward_level_opbyop(s, l, K[l], b[l]); break;
         }
         if (st == GF_OK && l < L) st = dup_level(s, l);
@@ -962,7 +986,7 @@ gf_status backward_level_opbyop(gf_smp *s, int l, const float *Kl, float *dKl) {
 // df_{l-1} from what level l left: the fused level's folded consumer gather, else the consumer-list gather of dP (a fused level's D_bb /
 // D_ac gradients arrive through dFdc beside it); the gamma level has written df_{l-1} itself
 gf_status send_df_down(gf_smp *s, int l, LevelKind kind) {
-    if (kind == LevelKind::Gamma) return GF_OK;
+    if (kind == LevelKind::Gamma || kind == LevelKind::Theta) return GF_OK;
     const bool fused = kind == LevelKind::Fused18;
     if (fused && smp_fused_gather_enabled(s, l)) return smp_fused_gather_backward(s, l);
     const gf_smp::DevLevel &d = s->lv[l], &pv = s->lv[l - 1];
@@ -1031,11 +1055,12 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
     if (!accumulate) GF_LAUNCH(ctx, "smp_zero", zero_f32, dim3(grid_for(np)), dim3(256), 0, grads, np);
     // the read-out's gradient into the top level: a fused level reads it as one vector per node, the others at every (i, j)
     const gfsmp::LevelLayout &top = B.level[L];
-    const bool top_fused = !dfeat && kind[L] == LevelKind::Fused18;
+    // (a first-order level takes the read-out's gradient the same way: one vector per node, added inside its per-node kernel)
+    const bool top_fused = !dfeat && (kind[L] == LevelKind::Fused18 || kind[L] == LevelKind::Theta);
     const bool classes = !dfeat && s->cfg.nClass;   // (a classifier: dg [nMol][C] goes down instead of dy[mol] * W)
     if (!dfeat && !classes) GF_LAUNCH(ctx, "smp_readout_dW", readout_dW, dim3(1), dim3(1024), 0, s->dy, s->g, dW, C, B.nMol);
     if (dfeat) {
-        if (kind[L] != LevelKind::Fused18) st = feature_backward(s, dfeat, L, 0);
+        if (kind[L] != LevelKind::Fused18 && kind[L] != LevelKind::Theta) st = feature_backward(s, dfeat, L, 0);
         if (st != GF_OK) return st;
     } else if (classes) {
         st = readout_classes_dW(s, dW);
@@ -1051,7 +1076,7 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
     for (int l = L; l >= 1; --l) {
         if (l < L) st = fold_level(s, l);   // (SMP_2D_ver6 on the 18-slice level: the gradient of the transposed copies joins the matrices')
         if (st != GF_OK) return st;
-        if (kind[l] != LevelKind::Fused18) s->bwd_consumed = true;
+        if (kind[l] != LevelKind::Fused18 && kind[l] != LevelKind::Theta) s->bwd_consumed = true;   // (a first-order level keeps f, A, B: repeatable)
         switch (kind[l]) {
         case LevelKind::Fused18:
             if (dfeat) st = feature_nodevec(s, dfeat, l);
@@ -1067,10 +1092,16 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
             st = bias_gradient(s, l, db[l]);
             if (st == GF_OK) st = backward_level_opbyop(s, l, K[l], dK[l]);
             break;
+        case LevelKind::Theta:   // dz, the per-size gradients, dG gathered from dz, dK_l and df_{l-1} on the rows of level l - 1
+            if (dfeat) st = feature_nodevec(s, dfeat, l);
+            if (st == GF_OK)
+                st = smp_theta_backward_level(s, l, K[l], b[l], dK[l], db[l], dfeat ? s->lv[l].dshl : l == L ? s->dsh : nullptr, /*rows_too=*/l < L,
+                                              smp_dp_level_done);
+            break;
         }
         if (st == GF_OK) st = send_df_down(s, l, kind[l]);
         // a tower: level l - 1 is read out too, and its own contribution joins what its consumers sent down (a fused level adds its own)
-        if (st == GF_OK && dfeat && kind[l - 1] != LevelKind::Fused18) st = feature_backward(s, dfeat, l - 1, 1);
+        if (st == GF_OK && dfeat && kind[l - 1] != LevelKind::Fused18 && kind[l - 1] != LevelKind::Theta) st = feature_backward(s, dfeat, l - 1, 1);
         if (st != GF_OK) return st;
     }
     st = backward_level0(s, dH);
@@ -1123,6 +1154,7 @@ gf_status gf_smp_forward(gf_smp *s, const float *params, const float *targets, f
 gf_status gf_smp_dropout_masks(gf_smp *s, const unsigned *masks, float scale) {
     if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
     gf_ctx *ctx = s->ctx;
+    if (s->cfg.first_order) return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_dropout_masks: a first-order handle has no contraction slices to drop");
     if (!masks) {
         s->drop_on = false;
         return GF_OK;
@@ -1165,6 +1197,8 @@ gf_status gf_smp_dropout_masks(gf_smp *s, const unsigned *masks, float scale) {
 
 gf_status gf_smp_set_grad_allreduce(gf_smp *s, int on) {
     if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
+    if (on && s->cfg.first_order)
+        return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_set_grad_allreduce: a first-order handle has no data-parallel exchange (reduce the flat gradient)");
     s->grad_allreduce = on ? 1 : 0;
     return GF_OK;
 }
@@ -1235,11 +1269,13 @@ static long long smp_read_node(gf_smp *s, int mol, int level, int v, float *out,
     if (n < 0) return -1;
     const size_t sz = (size_t)h.node_s[n], C = (size_t)s->cfg.level_channels(level);  // (physics towers halve per level)
     const size_t Cu = (size_t)s->ucfg.level_channels(level);                              // (the caller's channels: the padded ones are cropped)
-    const size_t count = adjacency ? sz * sz : sz * sz * Cu;
+    const size_t npos = s->cfg.first_order ? sz : sz * sz;   // (a first-order activation is [s][C])
+    if (adjacency && s->cfg.first_order) return -1;          // (... and the model has no reduced adjacency)
+    const size_t count = adjacency ? sz * sz : npos * Cu;
     if (count > capacity) return -1;
     const float *src = adjacency ? s->lv[level].adj + h.node_row[n] : s->lv[level].f + (size_t)h.node_row[n] * C;
     if (!adjacency && Cu != C) {
-        if (hipMemcpy2DAsync(out, Cu * sizeof(float), src, C * sizeof(float), Cu * sizeof(float), sz * sz, hipMemcpyDeviceToHost, s->ctx->stream) != hipSuccess)
+        if (hipMemcpy2DAsync(out, Cu * sizeof(float), src, C * sizeof(float), Cu * sizeof(float), npos, hipMemcpyDeviceToHost, s->ctx->stream) != hipSuccess)
             return -1;
     } else if (hipMemcpyAsync(out, src, count * sizeof(float), hipMemcpyDeviceToHost, s->ctx->stream) != hipSuccess) return -1;
     if (hipStreamSynchronize(s->ctx->stream) != hipSuccess) return -1;

@@ -218,6 +218,14 @@ struct gf_smp {
         float *Sout = nullptr, *dSout = nullptr;    // [nodes][C]
         float *dSpart = nullptr, *dbpart = nullptr; // [pairs][C]
         float *Wst = nullptr, *dWst = nullptr;      // [18][C][C] block-permuted K_l and its gradient
+        // first-order level (smp_level_theta.hip; tables of smp_prep.h: th_*): G / dG live in Q, the weight views in Wst / dWst
+        long long *th_child_ptr = nullptr, *th_src_row = nullptr, *th_pi_off = nullptr, *th_cons_ptr = nullptr, *th_cons_row = nullptr,
+                  *th_inv_off = nullptr;
+        int *th_src_s = nullptr, *th_cons_s = nullptr, *th_cons_node = nullptr, *th_bucket = nullptr, *th_weight = nullptr;
+        short *th_pi = nullptr, *th_inv = nullptr;
+        float *th_A = nullptr;     // [rows][Cc] A[i] = sum over the children of G_top (kept for dlambda1)
+        float *th_B = nullptr;     // [nodes][Cc] B = sum over positions and children of G_bot (kept for dlambda2)
+        float *th_node = nullptr;  // [nodes][3 Cc] reverse sweep: sum_i dz[i] | sum_i dz[i] A[i] | (sum_i dz[i]) B
     };
     std::vector<DevLevel> lv;
     // device-built level tables: the batch's adjacency matrices and the per-level statistics the kernels leave behind
@@ -279,7 +287,7 @@ constexpr int kFusedMaxField = 64;
 // What runs level l >= 1 of a pass: the fused 18-slice level (smp_fused.hip) where gf_smp_set_fused allows and smp_fused_supported takes the
 // shape, else the SMP_gamma level where smp_gamma_fused does, else the op-by-op pipeline (smp.hip); nobody else asks the two predicates.
 // Constant for the length of a pass, NOT between passes (gf_smp_set_fused, gf_smp_dropout_masks): a sweep asks at its start, keeps nothing.
-enum class LevelKind { OpByOp, Fused18, Gamma };
+enum class LevelKind { OpByOp, Fused18, Gamma, Theta };   // Theta: every level of a first-order handle (cfg.first_order), nothing else
 LevelKind smp_level_kind(const gf_smp *s, int l);
 bool smp_fused_supported(const gf_smp *s, int l);
 gf_status smp_backward_admissible(const gf_smp *s);   // smp.hip: refusals of a reverse sweep that must come before any work is issued
@@ -295,6 +303,19 @@ gf_status smp_fused_gather_backward(gf_smp *s, int l);
 bool smp_gamma_fused(const gf_smp *s, int l);
 gf_status smp_gamma_forward_level(gf_smp *s, int l, const float *Kl, const float *bl);
 gf_status smp_gamma_backward_level(gf_smp *s, int l, const float *Kl, float *dKl, gf_status (*wgrad_done)(gf_smp *, int));
+// First-order levels (SMP_theta, smp_level_theta.hip).  sizes = the level's per-size block (lambda1, lambda2, b[Cc]) x max_nVertices.
+// forward: G = f_{l-1} [K_top | K_bot] on the rows of level l - 1, one gather into f_l (A and B kept).  backward (d.df holds df_l): dz in
+// place, the per-size gradients as segment reductions over the size buckets, dG gathered per source node, dK_l, *wgrad_done, df_{l-1}.
+// smp_theta_prepare (smp_prepare.hip): gf_smp_prepare of a first-order handle -- the th_* tables, none of the other kinds' buffers.
+gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature);
+gf_status smp_theta_forward_level(gf_smp *s, int l, const float *Kl, const float *sizes);
+// node_df: the read-out's gradient as one vector per node or null; rows_too: d.df holds a per-row gradient as well (levels below the top)
+gf_status smp_theta_backward_level(gf_smp *s, int l, const float *Kl, const float *sizes, float *dKl, float *dsizes, const float *node_df,
+                                   bool rows_too, gf_status (*wgrad_done)(gf_smp *, int));
+// the first-order read-out of level l: sh[n] = column sums over the node's s rows (ShrinkMatrix), vf = LeakyReLU(sh); and its reverse,
+// df_l[n][i][:] (+)= dvec[n][:] at every row i of the node, dvec = one gradient vector per node
+gf_status smp_theta_readout(gf_smp *s, int l, float *sh, float *vf);
+gf_status smp_theta_readout_backward(gf_smp *s, int l, const float *dvec, int accumulate);
 bool smp_fused_gather_enabled(const gf_smp *s, int l);
 gf_status smp_fused_stack_all(gf_smp *s, const std::vector<const float *> &K);
 gf_status smp_build_gather_records(gf_smp *s, int l, hipStream_t stream);
@@ -307,12 +328,12 @@ gf_status smp_combine_bwd_panels_c64(gf_smp *s, int l, const float *dfrows, cons
 // level l's K_l / b_l gradients are complete on the context's CURRENT stream (l == 0: H): start their all-reduce
 gf_status smp_dp_level_done(gf_smp *s, int l);
 
-// ---- the parameter layout: H, (K_1, b_1), ..., (K_L, b_L), W -- the registration order of SMP_omega.h:289-295 (= save_model order) ----
+// ---- the parameter layout: H, (K_1, b_1), ..., (K_L, b_L), W (first-order models: H, (sizes_l, K_l) ..., W, gfsmp::Config::first_order) -- the registration order of SMP_omega.h:289-295 (= save_model order) ----
 // (W is [readout_rows()][C]: one row for the regression models, nClass rows for a classifier, SMP_2D_ver6_classification.h:211-217)
 inline size_t param_count(const gfsmp::Config &c) {
     size_t n = (size_t)c.nChanels * c.fdim();
     for (int l = 1; l <= c.nLevels; ++l)
-        n += (size_t)c.nContractions * c.level_channels(l - 1) * c.level_channels(l) + c.level_channels(l);
+        n += (size_t)c.nContractions * c.level_channels(l - 1) * c.level_channels(l) + c.size_block(l);
     return n + (c.physics ? 0 : (size_t)c.readout_rows() * c.nChanels);  // a physics tower ends in its level features: the head's weights are the caller's
 }
 template <typename P>
@@ -323,8 +344,13 @@ void view_params(const gfsmp::Config &c, P *base, P **H, std::vector<P *> *K, st
     K->assign(c.nLevels + 1, nullptr);
     b->assign(c.nLevels + 1, nullptr);
     for (int l = 1; l <= c.nLevels; ++l) {
+        if (c.first_order) {   // (SMP_theta.h:254-264: the per-size blocks are registered before K_l; b[l] = the first of them)
+            (*b)[l] = p;
+            p += c.size_block(l);
+        }
         (*K)[l] = p;
         p += (size_t)c.nContractions * c.level_channels(l - 1) * c.level_channels(l);
+        if (c.first_order) continue;
         (*b)[l] = p;
         p += c.level_channels(l);
     }

@@ -117,10 +117,15 @@ gf_status gf_smp_model_create(gf_ctx *ctx, const gf_smp_model_config *cfg, gf_sm
                     cfg->nContractions);
     if (nK == 4 && cfg->nKept > 0)
         return fail(ctx, GF_ERR_INVALID, "gf_smp_model_create: nKept > 0 (RisiContraction_18_dropout) with nContractions = 4: no such model");
+    const int maxV[2] = {cfg->max_nVertices[0], cfg->max_nVertices[1] ? cfg->max_nVertices[1] : cfg->max_nVertices[0]};
+    if (cfg->first_order && (cfg->nContractions || cfg->nKept > 0 || maxV[0] < cfg->max_receptive_field || maxV[1] < cfg->max_receptive_field))
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_model_create: first_order = 1 (SMP_theta_physics / _pairgraphs) needs nContractions = nKept = 0 and "
+                                         "max_nVertices (%d, %d) >= max_receptive_field (%d)", maxV[0], maxV[1], cfg->max_receptive_field);
     gf_smp_model *m = new gf_smp_model();
     m->ctx = ctx;
     m->cfg = *cfg;
-    m->cfg.nContractions = nK;
+    m->cfg.nContractions = cfg->first_order ? 2 : nK;   // (first order: K_l = [2 C_{l-1}][C_l])
+    m->cfg.max_nVertices[1] = maxV[1];
     m->nTowers = cfg->nTowers;
     m->L = cfg->nLevels;
     for (int l = 0; l <= m->L; ++l) {
@@ -132,7 +137,8 @@ gf_status gf_smp_model_create(gf_ctx *ctx, const gf_smp_model_config *cfg, gf_sm
     // the H matrices come first (one per tower), then the levels, towers interleaved inside a level
     size_t toff[2] = {0, 0};
     for (int t = 0; t < m->nTowers; ++t) {
-        gf_smp_config tc = {cfg->nLevels, cfg->nChanels, cfg->nFeatures[t], 0, cfg->max_receptive_field, 0, nK, 0, 1};
+        gf_smp_config tc = {cfg->nLevels, cfg->nChanels, cfg->nFeatures[t], 0, cfg->max_receptive_field, 0, cfg->first_order ? 0 : nK, 0, 1,
+                            cfg->first_order ? 1 : 0, cfg->first_order ? maxV[t] : 0};
         // (nKept > 0, RisiContraction_18_dropout: towers of up to 32 channels run the fused levels with per-product slice factors since
         //  round 5 -- padded like the others; wider ones keep their levels op by op, at their own halving widths)
         gf_status st = gf::smp_create(ctx, &tc, /*pad_channels=*/cfg->nKept <= 0 || cfg->nChanels <= 32, &m->tower[t]);
@@ -148,7 +154,9 @@ gf_status gf_smp_model_create(gf_ctx *ctx, const gf_smp_model_config *cfg, gf_sm
     }
     for (int l = 1; l <= m->L; ++l)
         for (int t = 0; t < m->nTowers; ++t) {
-            const size_t n = (size_t)nK * m->lvlC[l - 1] * m->lvlC[l] + m->lvlC[l];
+            // (first order: the per-size (lambda1, lambda2, b) blocks, then K_l -- one contiguous segment in either layout)
+            const size_t n = cfg->first_order ? (size_t)maxV[t] * (2 + m->lvlC[l]) + (size_t)2 * m->lvlC[l - 1] * m->lvlC[l]
+                                              : (size_t)nK * m->lvlC[l - 1] * m->lvlC[l] + m->lvlC[l];
             m->segs[t].push_back({off, toff[t], n});
             off += n;
             toff[t] += n;
@@ -371,8 +379,14 @@ gf_status gf_smp_model_uniform_init_host(const gf_smp_model *m, float *params) {
     for (int t = 0; t < m->nTowers; ++t) sizes.push_back((size_t)C * m->cfg.nFeatures[t]);
     for (int l = 1; l <= m->L; ++l)
         for (int t = 0; t < m->nTowers; ++t) {
+            if (m->cfg.first_order)   // (SMP_theta_physics.h:270-278: lambda1, lambda2, b per size, then K_l)
+                for (int size = 1; size <= m->cfg.max_nVertices[t]; ++size) {
+                    sizes.push_back(1);
+                    sizes.push_back(1);
+                    sizes.push_back((size_t)m->lvlC[l]);
+                }
             sizes.push_back((size_t)m->cfg.nContractions * m->lvlC[l - 1] * m->lvlC[l]);
-            sizes.push_back((size_t)m->lvlC[l]);
+            if (!m->cfg.first_order) sizes.push_back((size_t)m->lvlC[l]);
         }
     for (int i = 1; i <= m->nLayers; ++i) sizes.push_back((size_t)m->widths[i] * m->widths[i - 1]);
     sizes.push_back((size_t)m->widths[m->nLayers]);

@@ -187,17 +187,38 @@ gf_status gf_smp_adam_reset(gf_smp *s) {
 // SMP_omega::weights_initialization (SMP_omega.h:334-338) = GraphFlow::uniform_init (GraphFlow.h:1297-1306) over the
 // parameters in registration order, drawn from the C library's rand() exactly as the reference draws them: after the
 // same srand() a model built here starts from the same weights as one built by the reference.  Host buffer.
-static gf_status uniform_init_host(const gf_smp_config *cfg, int nClass, float *params) {
-    if (!cfg || !params) return GF_ERR_INVALID;
+// the layout of a configuration (what gf_smp_create derives before it touches the device); false: one it would refuse
+static bool host_config(const gf_smp_config *cfg, int nClass, gfsmp::Config *out) {
+    if (!cfg || cfg->nLevels < 1 || cfg->nChanels < 1 || cfg->nFeatures < 1 || cfg->nDepth < 0 || cfg->max_receptive_field < 1) return false;
     gfsmp::Config c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, cfg->has_WL_ordering};
     c.nContractions = cfg->nContractions ? cfg->nContractions : 18;
+    c.custom_matmul = cfg->custom_matmul ? 1 : 0;
     c.physics = cfg->physics ? 1 : 0;
+    c.nClass = nClass;
+    if (cfg->first_order) {   // SMP_theta (gf_smp_config.first_order)
+        if (cfg->nContractions || cfg->custom_matmul || cfg->max_nVertices < cfg->max_receptive_field || nClass) return false;
+        c.first_order = 1;
+        c.max_nVertices = cfg->max_nVertices;
+        c.nContractions = 2;
+    }
+    *out = c;
+    return true;
+}
+static gf_status uniform_init_host(const gf_smp_config *cfg, int nClass, float *params) {
+    gfsmp::Config c;
+    if (!params || !host_config(cfg, nClass, &c)) return GF_ERR_INVALID;
     const size_t C = (size_t)c.nChanels;
     std::vector<size_t> sizes;
     sizes.push_back(C * c.fdim());
     for (int l = 1; l <= c.nLevels; ++l) {
+        if (c.first_order)   // lambda1[size], lambda2[size], b[size] for size = 1 .. max_nVertices, then K_l (SMP_theta.h:254-264)
+            for (int size = 1; size <= c.max_nVertices; ++size) {
+                sizes.push_back(1);
+                sizes.push_back(1);
+                sizes.push_back((size_t)c.level_channels(l));
+            }
         sizes.push_back((size_t)c.nContractions * c.level_channels(l - 1) * c.level_channels(l));
-        sizes.push_back((size_t)c.level_channels(l));
+        if (!c.first_order) sizes.push_back((size_t)c.level_channels(l));
     }
     if (!c.physics) sizes.push_back((size_t)(nClass > 1 ? nClass : 1) * C);
     size_t off = 0;
@@ -210,6 +231,10 @@ static gf_status uniform_init_host(const gf_smp_config *cfg, int nClass, float *
     return GF_OK;
 }
 gf_status gf_smp_uniform_init_host(const gf_smp_config *cfg, float *params) { return uniform_init_host(cfg, 0, params); }
+size_t gf_smp_config_param_count(const gf_smp_config *cfg) {
+    gfsmp::Config c;
+    return host_config(cfg, 0, &c) ? gf::param_count(c) : 0;
+}
 // ... of the `_classification` models (SMP_2D_ver6_classification.h:256-259): sgd->params holds Vector*, so W [nClass][C] is drawn by
 // uniform_init(Vector*) like the rest, with the divisor 10 * nClass * C
 gf_status gf_smp_classifier_uniform_init_host(const gf_smp_config *cfg, int nClass, float *params) {

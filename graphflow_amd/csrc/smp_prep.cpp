@@ -564,4 +564,176 @@ void build_batch(const Config &cfg, int nMol, const int *nVertices, const int *a
     }
 }
 
+// ---- first-order models (GraphFlow/SMP_theta.h) ---------------------------------------------------------------------------------
+// The molecules are prepared as for SMP_omega (the two classes share Floyd-Warshall, the WL features, the ranking and the receptive
+// fields, SMP_theta.h:327-507).  Per level: nodes in bucket (size) order, rows = the field positions, and the level's own (node, child)
+// pairs -- the children of v are the vertices at hop distance <= 1 (:577-583), which under a cap need not lie inside phi_l(v).
+void build_batch_theta(const Config &cfg, int nMol, const int *nVertices, const int *adj, const double *feature, BatchLayout *out) {
+    const int L = cfg.nLevels, FD = cfg.fdim(), F = cfg.nFeatures;
+    out->device_tables = false;
+    out->nMol = nMol;
+    out->mols.resize(nMol);
+    out->mol_first_vertex.assign(nMol + 1, 0);
+    std::vector<size_t> adj_off(nMol + 1, 0);
+    out->max_vertices = 1;
+    for (int m = 0; m < nMol; ++m) {
+        out->mol_first_vertex[m + 1] = out->mol_first_vertex[m] + nVertices[m];
+        adj_off[m + 1] = adj_off[m] + (size_t)nVertices[m] * nVertices[m];
+        out->max_vertices = std::max(out->max_vertices, nVertices[m]);
+    }
+    const int totalV = out->mol_first_vertex[nMol];
+    out->x.assign((size_t)totalV * FD, 0.f);
+    parallel_for(nMol, [&](int m) {
+        const int V = nVertices[m], v0 = out->mol_first_vertex[m];
+        prepare_molecule(cfg, V, adj + adj_off[m], feature + (size_t)v0 * F, &out->mols[m]);
+        for (size_t i = 0; i < (size_t)V * FD; ++i) out->x[(size_t)v0 * FD + i] = (float)out->mols[m].wl[i];
+    });
+    out->level.assign(L + 1, LevelLayout());
+    std::vector<std::vector<int> > node_of(L + 1, std::vector<int>(totalV, -1));
+    parallel_tasks(L + 1, [&](int l) {   // node numbering: level 0 in (molecule, vertex) order, levels >= 1 by field size (stable)
+        LevelLayout &lv = out->level[l];
+        std::vector<std::pair<int, int> > order;
+        order.reserve(totalV);
+        for (int m = 0; m < nMol; ++m)
+            for (int v = 0; v < nVertices[m]; ++v)
+                order.push_back(std::make_pair((int)out->mols[m].phi[l][v].size(), out->mol_first_vertex[m] + v));
+        if (l > 0) std::stable_sort(order.begin(), order.end(),
+                                    [](const std::pair<int, int> &a, const std::pair<int, int> &b) { return a.first < b.first; });
+        lv.nNodes = totalV;
+        lv.node_s.resize(totalV);
+        lv.node_mol.resize(totalV);
+        lv.node_vertex.resize(totalV);
+        lv.node_row.resize(totalV);
+        int64_t row = 0;
+        for (int n = 0; n < totalV; ++n) {
+            const int s = order[n].first, gv = order[n].second;
+            const int m = (int)(std::upper_bound(out->mol_first_vertex.begin(), out->mol_first_vertex.end(), gv) -
+                                out->mol_first_vertex.begin()) - 1;
+            node_of[l][gv] = n;
+            lv.node_s[n] = s;
+            lv.node_mol[n] = m;
+            lv.node_vertex[n] = gv - out->mol_first_vertex[m];
+            lv.node_row[n] = row;
+            if (lv.buckets.empty() || lv.buckets.back().s != s) {
+                Bucket b = {s, 0, n, row, 0};
+                lv.buckets.push_back(b);
+            }
+            lv.buckets.back().count += 1;
+            row += s;
+        }
+        lv.rows = row;   // sum s: f_l[v] is [s][C]
+        lv.ppos = 0;
+        lv.th_bucket.clear();
+        for (const Bucket &b : lv.buckets) {
+            lv.th_bucket.push_back(b.s);
+            lv.th_bucket.push_back(b.first_node);
+            lv.th_bucket.push_back(b.count);
+        }
+    });
+    out->top_node_of_vertex = node_of[L];
+    out->node_of_vertex = node_of;
+    for (int l = 1; l <= L; ++l) {   // (the nodes of a level in parallel below)
+        LevelLayout &lv = out->level[l];
+        const LevelLayout &pv = out->level[l - 1];
+        // offsets first (serial prefix sums), then the maps of every node in parallel
+        lv.th_child_ptr.assign((size_t)totalV + 1, 0);
+        lv.th_cons_ptr.assign((size_t)totalV + 1, 0);
+        for (int n = 0; n < totalV; ++n) {
+            const int m = lv.node_mol[n], v = lv.node_vertex[n], V = nVertices[m];
+            const std::vector<int> &hops = out->mols[m].hops;
+            int nc = 0;
+            for (int w = 0; w < V; ++w) nc += hops[(size_t)v * V + w] <= 1;
+            lv.th_child_ptr[(size_t)n + 1] = nc;
+        }
+        for (int n = 0; n < totalV; ++n) lv.th_child_ptr[(size_t)n + 1] += lv.th_child_ptr[(size_t)n];
+        const int64_t pairs = lv.th_child_ptr[(size_t)totalV];
+        lv.pairs = pairs;
+        lv.th_src_row.resize((size_t)pairs);
+        lv.th_src_s.resize((size_t)pairs);
+        lv.th_pi_off.resize((size_t)pairs);
+        int64_t pi_total = 0;
+        for (int n = 0; n < totalV; ++n) {
+            const int64_t e0 = lv.th_child_ptr[(size_t)n], e1 = lv.th_child_ptr[(size_t)n + 1];
+            for (int64_t e = e0; e < e1; ++e) {
+                lv.th_pi_off[(size_t)e] = pi_total;
+                pi_total += lv.node_s[n];
+            }
+        }
+        lv.th_pi.resize((size_t)pi_total);
+        // consumers of a source node w of level l - 1: the vertices v with hops[v][w] <= 1, ascending
+        for (int w = 0; w < totalV; ++w) {
+            const int m = pv.node_mol[w], u = pv.node_vertex[w], V = nVertices[m];
+            const std::vector<int> &hops = out->mols[m].hops;
+            int nc = 0;
+            for (int v = 0; v < V; ++v) nc += hops[(size_t)v * V + u] <= 1;
+            lv.th_cons_ptr[(size_t)w + 1] = nc;
+        }
+        for (int w = 0; w < totalV; ++w) lv.th_cons_ptr[(size_t)w + 1] += lv.th_cons_ptr[(size_t)w];
+        lv.th_weight.assign((size_t)totalV, 0);
+        for (int m = 0; m < nMol; ++m) {   // the j-th vertex of its size in the molecule, ascending v (see th_weight)
+            const int V = nVertices[m], g0 = out->mol_first_vertex[m];
+            for (int v = 0; v < V; ++v) {
+                const size_t sv = out->mols[m].phi[l][v].size();
+                int j = 1;
+                for (int u = 0; u < v; ++u) j += out->mols[m].phi[l][u].size() == sv;
+                lv.th_weight[(size_t)node_of[l][g0 + v]] = j;
+            }
+        }
+        lv.th_cons_row.resize((size_t)pairs);
+        lv.th_cons_s.resize((size_t)pairs);
+        lv.th_cons_node.resize((size_t)pairs);
+        lv.th_inv_off.resize((size_t)pairs);
+        int64_t inv_total = 0;
+        for (int w = 0; w < totalV; ++w)
+            for (int64_t c = lv.th_cons_ptr[(size_t)w]; c < lv.th_cons_ptr[(size_t)w + 1]; ++c) {
+                lv.th_inv_off[(size_t)c] = inv_total;
+                inv_total += pv.node_s[w];
+            }
+        lv.th_inv.resize((size_t)inv_total);
+        lv.inv_count = inv_total;
+        parallel_for(totalV, [&](int n) {
+            {   // node n of level l as a consumer: its children
+                const int m = lv.node_mol[n], v = lv.node_vertex[n], V = nVertices[m], g0 = out->mol_first_vertex[m];
+                const Molecule &M = out->mols[m];
+                const std::vector<int> &fv = M.phi[l][v];
+                int64_t e = lv.th_child_ptr[(size_t)n];
+                for (int w = 0; w < V; ++w) {
+                    if (M.hops[(size_t)v * V + w] > 1) continue;
+                    const int wn = node_of[l - 1][g0 + w];
+                    const std::vector<int> &fw = M.phi[l - 1][w];
+                    lv.th_src_row[(size_t)e] = pv.node_row[wn];
+                    lv.th_src_s[(size_t)e] = (int)fw.size();
+                    int16_t *pi = &lv.th_pi[(size_t)lv.th_pi_off[(size_t)e]];
+                    for (size_t i = 0; i < fv.size(); ++i) {
+                        const std::vector<int>::const_iterator it = std::find(fw.begin(), fw.end(), fv[i]);
+                        pi[i] = it == fw.end() ? (int16_t)-1 : (int16_t)(it - fw.begin());
+                    }
+                    ++e;
+                }
+            }
+            {   // node n of level l - 1 as a source: its consumers
+                const int w = n, m = pv.node_mol[w], u = pv.node_vertex[w], V = nVertices[m], g0 = out->mol_first_vertex[m];
+                const Molecule &M = out->mols[m];
+                const std::vector<int> &fw = M.phi[l - 1][u];
+                int64_t c = lv.th_cons_ptr[(size_t)w];
+                for (int v = 0; v < V; ++v) {
+                    if (M.hops[(size_t)v * V + u] > 1) continue;
+                    const int vn = node_of[l][g0 + v];
+                    const std::vector<int> &fv = M.phi[l][v];
+                    lv.th_cons_row[(size_t)c] = lv.node_row[vn];
+                    lv.th_cons_s[(size_t)c] = (int)fv.size();
+                    lv.th_cons_node[(size_t)c] = vn;
+                    int16_t *inv = &lv.th_inv[(size_t)lv.th_inv_off[(size_t)c]];
+                    for (size_t j = 0; j < fw.size(); ++j) {
+                        const std::vector<int>::const_iterator it = std::find(fv.begin(), fv.end(), fw[j]);
+                        inv[j] = it == fv.end() ? (int16_t)-1 : (int16_t)(it - fv.begin());
+                    }
+                    ++c;
+                }
+            }
+        });
+    }
+}
+
+
 }  // namespace gfsmp

@@ -50,6 +50,10 @@ struct Config {
     // >= 2: the `_classification` models (gf_smp_create_classifier): the read-out weights are W [nClass][nChanels] (MatVecMul + LogLoss
     // instead of InnerProduct + SquaredLoss); 0: regression, W [nChanels] -- one row
     int nClass = 0;
+    // 1: the first-order models (GraphFlow/SMP_theta.h, gf_smp_config.first_order): f_l[v] is [s][C], nContractions = 2 (K_l = [2 C'][C]),
+    // and every level has a (lambda1, lambda2, b[C_l]) block per field size 1 .. max_nVertices in front of K_l
+    int first_order = 0, max_nVertices = 0;
+    size_t size_block(int l) const { return first_order ? (size_t)max_nVertices * (2 + (size_t)level_channels(l)) : (size_t)level_channels(l); }
     int readout_rows() const { return nClass > 1 ? nClass : 1; }   // rows of W: [1][C] is the regression's [C]
     bool square() const { return !physics || uniform; }   // K_l is [nContractions C][C] at every level
     int level_channels(int l) const {
@@ -129,6 +133,25 @@ struct LevelLayout {
     // the entries of a source back to back from cons_qbase[w] on
     tvec<int64_t> cons_qbase;    // [nNodes(l-1)]
     int64_t qrec_total = 0;
+    // ---- first-order levels (build_batch_theta; smp_level_theta.hip).  rows = sum s, node_row = first row of the node's [s][C] matrix.
+    // Children of node n = (molecule, v): the vertices w at hop distance <= 1, ascending (SMP_theta.h:577-583) -- pairs th_child_ptr[n] ..
+    tvec<int64_t> th_child_ptr;   // [nNodes + 1]
+    tvec<int64_t> th_src_row;     // [child pairs] first row of the child's node in level l - 1
+    tvec<int> th_src_s;           // [child pairs] its field size
+    tvec<int64_t> th_pi_off;      // [child pairs] offset into th_pi of the pair's s_n entries
+    tvec<int16_t> th_pi;          // index of phi_l(v)[i] in phi_{l-1}(w), or -1
+    // reverse sweep, by SOURCE node w of level l - 1: its consumers (the nodes it is a child of), ascending vertex
+    tvec<int64_t> th_cons_ptr;    // [nNodes(l-1) + 1]
+    tvec<int64_t> th_cons_row;    // [child pairs] first row of the consumer's node (level l)
+    tvec<int> th_cons_s;          // [child pairs] the consumer's field size
+    tvec<int> th_cons_node;       // [child pairs] the consumer's node
+    tvec<int64_t> th_inv_off;     // [child pairs] offset into th_inv of the entry's s_w values
+    tvec<int16_t> th_inv;         // index of phi_{l-1}(w)[j] in phi_l(v), or -1
+    tvec<int> th_bucket;          // [3 * buckets] (s, first node, count): the segments of the per-size weight gradients
+    // How often the reference counts a node's contribution to dlambda1_s / dlambda2_s.  SMP_theta adds the SHARED ops W_eye[s] / W_one[s]
+    // (ScalarMatMul) to the graph once per vertex of size s (SMP_theta.h:590-591), and GraphFlow::backward runs an op once per appearance:
+    // the j-th vertex of size s of a molecule (ascending v) has its gradient handed to lambda_s j times.  th_weight[n] = that j.
+    tvec<int> th_weight;          // [nNodes]
 };
 
 // Register classes of the backward gather: a source of size s_w runs the code path with gather_pad(s_w) accumulators (and
@@ -163,6 +186,10 @@ struct BatchLayout {
 // the use_coulomb constructors (SMP_omega.h:568-579) is then coulomb[v1][v2], diagonal included.
 void build_batch(const Config &cfg, int nMol, const int *nVertices, const int *adj, const double *feature,
                  const double *coulomb, BatchLayout *out);
+
+// The batch of a first-order model (Config::first_order): molecules, level-0 input, nodes in bucket order, rows = field positions, and the
+// th_* tables of every level >= 1; none of the tables of the 18-slice level.  Built on the host threads.
+void build_batch_theta(const Config &cfg, int nMol, const int *nVertices, const int *adj, const double *feature, BatchLayout *out);
 
 }  // namespace gfsmp
 #endif

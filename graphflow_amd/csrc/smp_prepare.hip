@@ -774,7 +774,7 @@ gf_status alloc_readout(gf_smp *s, int nMol) {
     s->wbound = nullptr;
     // scratch words of the fused levels' weight gradients (channel maxima, exact column bounds; a 64-channel level keeps only its maxima);
     // 128 channels: the plain 18-slice model's four sub-block launches
-    if (s->cfg.square() && (smp_panel_channels(C) || (C == 128 && s->cfg.nContractions == 18 && smp_c128_switch())))
+    if (!s->cfg.first_order && s->cfg.square() && (smp_panel_channels(C) || (C == 128 && s->cfg.nContractions == 18 && smp_c128_switch())))
         t.alloc(&s->wbound, smp_wgrad_words(C, C != 64) * (size_t)(L + 1));
     t.alloc(&s->sh, (size_t)top.nNodes * C);
     t.alloc(&s->vf, (size_t)top.nNodes * C);
@@ -804,6 +804,75 @@ gf_status alloc_readout(gf_smp *s, int nMol) {
 }
 
 }  // namespace
+
+// gf_smp_prepare of a first-order handle (SMP_theta): the host builds the batch and the level's own (node, child) tables
+// (gfsmp::build_batch_theta); the device gets those, the activations, A / B and G -- none of the 18-slice or gamma buffers.
+gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature) {
+    gf_ctx *ctx = s->ctx;
+    const gfsmp::Config &cfg = s->cfg;
+    for (int m = 0; m < nMol; ++m)
+        if (nVertices[m] > cfg.max_nVertices)
+            return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare: molecule %d has %d vertices, the model was created with max_nVertices = %d", m,
+                        nVertices[m], cfg.max_nVertices);
+    ensure_upload_stream(s);
+    release(s);
+    s->tab_stats = nullptr;
+    s->h_tab_stats.clear();
+    s->h_covered.clear();
+    gfsmp::build_batch_theta(cfg, nMol, nVertices, adj, feature, &s->lay);
+    const int L = cfg.nLevels;
+    for (int l = 0; l <= L; ++l)
+        if (s->lay.level[l].rows > 0x7fffffffll || (!s->lay.level[l].buckets.empty() && s->lay.level[l].buckets.back().s > 32767))
+            return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare: level %d is beyond the first-order level's int16 positions / 2^31 rows", l);
+    s->lv.assign(L + 1, gf_smp::DevLevel());
+    Taker t = {s};
+    for (int l = 0; l <= L; ++l) {
+        Level &h = s->lay.level[l];
+        DevLevel &d = s->lv[l];
+        const size_t Cl = cfg.level_channels(l), nodes = h.nNodes;
+        t.put(&d.node_s, h.node_s);
+        t.put(&d.node_row, h.node_row);
+        t.put(&d.node_mol, h.node_mol);
+        t.alloc(&d.f, (size_t)h.rows * Cl);
+        t.alloc(&d.df, (size_t)h.rows * Cl);
+        if (cfg.physics) {   // every level is read out: per-node sums, their activation and gradient, the vertex -> node map
+            t.alloc(&d.sh, nodes * Cl);
+            t.alloc(&d.vf, nodes * Cl);
+            t.alloc(&d.dshl, nodes * Cl);
+            t.put(&d.node_of_vertex, s->lay.node_of_vertex[l]);
+        }
+        if (l == 0) continue;
+        const size_t Cp = cfg.level_channels(l - 1);
+        t.put(&d.th_child_ptr, h.th_child_ptr);
+        t.put(&d.th_src_row, h.th_src_row);
+        t.put(&d.th_src_s, h.th_src_s);
+        t.put(&d.th_pi_off, h.th_pi_off);
+        t.put(&d.th_pi, h.th_pi);
+        t.put(&d.th_cons_ptr, h.th_cons_ptr);
+        t.put(&d.th_cons_row, h.th_cons_row);
+        t.put(&d.th_cons_s, h.th_cons_s);
+        t.put(&d.th_cons_node, h.th_cons_node);
+        t.put(&d.th_inv_off, h.th_inv_off);
+        t.put(&d.th_inv, h.th_inv);
+        t.put(&d.th_bucket, h.th_bucket);
+        t.put(&d.th_weight, h.th_weight);
+        t.alloc(&d.th_A, (size_t)h.rows * Cl);
+        t.alloc(&d.th_B, nodes * Cl);
+        t.alloc(&d.th_node, nodes * 3 * Cl);
+        t.alloc(&d.Q, (size_t)s->lay.level[l - 1].rows * 2 * Cl);   // G, then dG: [rows of level l - 1][2 Cc]
+        t.alloc(&d.Wst, 4 * Cp * Cl);                               // the weight views [Cp][2 Cc] and [2 Cc][Cp]
+        t.alloc(&d.dWst, 2 * Cp * Cl);
+    }
+    if (t.st != GF_OK) return t.st;
+    s->P = nullptr;
+    s->P_count = 0;
+    gf_status st = alloc_readout(s, nMol);
+    if (st != GF_OK) return st;
+    s->ws_need = 1 << 20;   // (the GEMMs grow the context's workspace for their split-K partials themselves)
+    GF_HIP_TRY(ctx, hipStreamSynchronize(upload_stream(s)));
+    s->prepared = true;
+    return GF_OK;
+}
 
 // ints of a level's row-class buffer (see row_class_count), and its builder: three launches on `stream` behind whatever wrote trowf
 size_t smp_row_class_ints(int rows) { return 4 + 2 * ((size_t)rows + 64) + (size_t)(rows + kRcBlock - 1) / kRcBlock + 1; }
@@ -835,6 +904,7 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
     for (int m = 0; m < nMol; ++m)
         if (nVertices[m] <= 0 || nVertices[m] > 4096) return fail(ctx, GF_ERR_INVALID, "molecule %d has %d vertices", m, nVertices[m]);
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (s->cfg.first_order) return gf::smp_theta_prepare(s, nMol, nVertices, adj, feature);   // (no reduced adjacency: coulomb is inert)
     gf_status st = gf::choose_plan(s, nMol, nVertices, adj, coulomb);
     if (st != GF_OK) return st;
     const bool prep_timing = std::getenv("GF_PREP_TIMING") != nullptr;

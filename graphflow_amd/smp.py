@@ -12,7 +12,7 @@ from .ops import default_context
 class SMPConfig(C.Structure):
     _fields_ = [("nLevels", C.c_int), ("nChanels", C.c_int), ("nFeatures", C.c_int), ("nDepth", C.c_int),
                 ("max_receptive_field", C.c_int), ("has_WL_ordering", C.c_int), ("nContractions", C.c_int),
-                ("custom_matmul", C.c_int), ("physics", C.c_int)]
+                ("custom_matmul", C.c_int), ("physics", C.c_int), ("first_order", C.c_int), ("max_nVertices", C.c_int)]
 
 
 class SMPOmega:
@@ -217,6 +217,35 @@ class SMPGamma(SMPOmega):
         super().__init__(nLevels, nChanels, nFeatures, nDepth, max_nVertices, has_WL_ordering, ctx=ctx, nContractions=4)
 
 
+class SMPTheta(SMPOmega):
+    """Batched SMP_theta (GraphFlow/SMP_theta.h), the first-order member of the family: f_l[v] is a matrix [s, C]; the children of a
+    vertex are its neighbours within one hop; lambda1, lambda2 and the bias b exist per field size.  Parameters in registration order:
+    H[C, F(D+1)]; for l = 1..L: (lambda1_s, lambda2_s, b_s[C]) for s = 1..max_nVertices, then K_l[2C, C]; W[C]."""
+
+    def __init__(self, max_nVertices, max_receptive_field, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering=True, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.cfg = self.config(max_nVertices, max_receptive_field, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering)
+        h = C.c_void_p()
+        self.ctx.check(self.lib.gf_smp_create(self.ctx.handle, C.byref(self.cfg), C.byref(h)))
+        self.handle = h
+        self.n_params = self.lib.gf_smp_param_count(h)
+        self.n_mol = 0
+
+    @staticmethod
+    def config(max_nVertices, max_receptive_field, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering=True):
+        return SMPConfig(nLevels, nChanels, nFeatures, nDepth, max_receptive_field, 1 if has_WL_ordering else 0, 0, 0, 0, 1, max_nVertices)
+
+    def activation(self, mol, level, v):
+        """f_level[v] of molecule `mol` after forward(): numpy [s, C] (level[l]->f[v]->value in the reference)."""
+        s = len(self.receptive_field(mol, level, v))
+        out = np.empty((s, self.cfg.nChanels), dtype=np.float32)
+        n = self.lib.gf_smp_read_activation(self.handle, mol, level, v, out.ctypes.data_as(C.c_void_p), out.size)
+        if n != out.size:
+            raise RuntimeError("gf_smp_read_activation(%d, %d, %d) returned %d" % (mol, level, v, n))
+        return out
+
+
 class SMPClassifier(SMPOmega):
     """The classification models of GraphFlow (SMP_2D_ver6_classification: nContractions=10, custom_matmul=True;
     SMP_2D_ver7_classification: 50, True) through gf_smp_create_classifier: the levels of the regression model, read out by
@@ -256,20 +285,24 @@ class SMPClassifier(SMPOmega):
 
 class SMPModelConfig(C.Structure):
     _fields_ = [("nTowers", C.c_int), ("nLevels", C.c_int), ("nChanels", C.c_int), ("max_receptive_field", C.c_int),
-                ("nFeatures", C.c_int * 2), ("nKept", C.c_int), ("nContractions", C.c_int)]
+                ("nFeatures", C.c_int * 2), ("nKept", C.c_int), ("nContractions", C.c_int), ("first_order", C.c_int),
+                ("max_nVertices", C.c_int * 2)]
 
 
 class SMPModel:
     """The _physics (one tower) / _pairgraphs (two towers, nKept > 0: SMP_sigma_pairgraphs) models of GraphFlow through
     gf_smp_model_*.  nContractions = 4: SMP_gamma_physics / SMP_gamma_pairgraphs (RisiContraction_4, K_l[4 C_{l-1}, C_l]).
+    first_order=True with max_nVertices (an int, or one per tower): SMP_theta_physics / SMP_theta_pairgraphs.
     Parameters / gradients: one flat fp32 tensor in the class's registration order."""
 
-    def __init__(self, nLevels, nChanels, max_receptive_field, nFeatures, nKept=0, ctx=None, nContractions=18):
+    def __init__(self, nLevels, nChanels, max_receptive_field, nFeatures, nKept=0, ctx=None, nContractions=18, first_order=False,
+                 max_nVertices=0):
         feats = list(nFeatures) if isinstance(nFeatures, (list, tuple)) else [nFeatures]
         self.ctx = ctx or default_context()
         self.lib = self.ctx.lib
         self.cfg = SMPModelConfig(len(feats), nLevels, nChanels, max_receptive_field, (C.c_int * 2)(*(feats + [0])[:2]), nKept,
-                                  nContractions)
+                                  0 if first_order else nContractions, 1 if first_order else 0,
+                                  (C.c_int * 2)(*((list(max_nVertices) if isinstance(max_nVertices, (list, tuple)) else [max_nVertices, 0]) + [0])[:2]))
         h = C.c_void_p()
         self.ctx.check(self.lib.gf_smp_model_create(self.ctx.handle, C.byref(self.cfg), C.byref(h)))
         self.handle = h

@@ -255,8 +255,28 @@ typedef struct {
      * head on top is gf_head_*.  SMP_beta_physics / _pairgraphs = the same with max_receptive_field = max_nVertices.
      * nContractions 18 (or 0); 4 (the towers of SMP_gamma_physics / _pairgraphs, K_l = [4 C_{l-1}][C_l]) only through gf_smp_model_create. */
     int physics;
+    /* first_order = 1: the FIRST-ORDER models SMP_theta (GraphFlow/SMP_theta.h) and, with physics = 1 through gf_smp_model_create only, the
+     * towers of SMP_theta_physics / SMP_theta_pairgraphs.  Same graph preparation, receptive fields (growth, cap, WL ordering), level-0
+     * embedding, read-out, Adam and API as SMP_omega; the level differs.  f_l[v] is a matrix [s][C] (s = |phi_l(v)|), not a tensor:
+     *   S = sum over the children w (hop distance <= 1 from v, NOT the members of the field, SMP_theta.h:577-583) of X[v][w] f_{l-1}[w],
+     *   f_l[v] = LeakyReLU([lambda1_s S | lambda2_s 1 1^T S] K_l + 1 b_s^T)                                      (:586-612)
+     * with scalars lambda1_s, lambda2_s and a bias b_s[C] PER FIELD SIZE s = 1 .. max_nVertices and K_l = [2 C][C] ([2 C_{l-1}][C_l] in a
+     * tower); the read-out sums a node's s rows (ShrinkMatrix).  Parameter order (registration order, :254-264): H; for l = 1..L: for size =
+     * 1 .. max_nVertices (lambda1, lambda2, b[C_l]), then K_l; W (no W in a tower).  max_nVertices >= max_receptive_field is required:
+     * the parameter count depends on it, and gf_smp_prepare refuses a molecule with more vertices.  nContractions / custom_matmul must be 0.
+     * The level is smp_level_theta.hip: products on the rows of the level below, deterministic gathers; any nChanels, no channel
+     * padding, no field-size limit other than int16 positions.  gf_smp_level_sizes: rows = sum of s, ppos = 0.  gf_smp_prepare_coulomb behaves
+     * as gf_smp_prepare (the model has no reduced adjacency), gf_smp_set_fused has no effect (there is one plan), gf_smp_read_activation
+     * returns [s][C].  Refused with GF_ERR_UNSUPPORTED before anything is launched:
+     *   - gf_smp_create_classifier on a first-order configuration,
+     *   - gf_smp_set_grad_allreduce(smp, 1) on a first-order handle (no data-parallel exchange: reduce the flat gradient yourself),
+     *   - gf_smp_dropout_masks on a first-order handle.
+     * Zero-initialised trailing fields give the behaviour described above. */
+    int first_order, max_nVertices;
 } gf_smp_config;
 gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out);
+/* gf_smp_param_count of the handle gf_smp_create would build from cfg (0 on a configuration it would refuse).  Host only. */
+size_t    gf_smp_config_param_count(const gf_smp_config *cfg);
 gf_status gf_smp_destroy(gf_smp *smp);
 size_t    gf_smp_param_count(const gf_smp *smp);
 /* The `_classification` models: SMP_2D_ver6_classification (nContractions 10, custom_matmul 1) and SMP_2D_ver7_classification (50, 1) of
@@ -454,6 +474,11 @@ typedef struct {
     int nFeatures[2];
     int nKept;   /* 0: RisiContraction_18; 1..18: RisiContraction_18_dropout */
     int nContractions;   /* 0 or 18: the `_omega` / `_beta` / `_sigma` models; 4: the `_gamma` ones */
+    /* first_order = 1: SMP_theta_physics (nTowers 1) / SMP_theta_pairgraphs (nTowers 2) -- towers of gf_smp_config.first_order levels,
+     * K_l = [2 C_{l-1}][C_l], per-size (lambda1, lambda2, b) blocks of max_nVertices entries in front of every K_l; heads, feature rows and
+     * the interleaving of two towers' parameters as in the other models.  max_nVertices is per tower (SMP_theta_pairgraphs.h:31:
+     * max_nVertices_1 / _2; [1] = 0 means [0]).  nContractions and nKept must be 0.  Zero: the models above. */
+    int first_order, max_nVertices[2];
 } gf_smp_model_config;
 gf_status gf_smp_model_create(gf_ctx *ctx, const gf_smp_model_config *cfg, gf_smp_model **out);
 gf_status gf_smp_model_destroy(gf_smp_model *model);
