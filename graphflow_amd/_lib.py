@@ -84,6 +84,7 @@ PROTOTYPES.update({
     "gf_smp_destroy": (_i, [_vp]),
     "gf_smp_param_count": (C.c_size_t, [_vp]),
     "gf_smp_config_param_count": (C.c_size_t, [_vp]),
+    "gf_smp_classifier_config_param_count": (C.c_size_t, [_vp, _i]),
     "gf_smp_create_classifier": (_i, [_vp, _vp, _i, C.POINTER(_vp)]),
     "gf_smp_classes": (_i, [_vp]),
     "gf_smp_class_scores": (_i, [_vp, _vp, _vp]),

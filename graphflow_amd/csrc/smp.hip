@@ -190,14 +190,18 @@ __global__ void promote_backward(const float *__restrict__ dP, float *__restrict
 }
 
 // ---- bias + LeakyReLU ---------------------------------------------------------------------------------------------
-__global__ void bias_lrelu_forward(float *__restrict__ Y, const float *__restrict__ b, int C, size_t total) {
-    GRID_STRIDE(i, total) Y[i] = lrelu(Y[i] + (b ? b[i % C] : 0.f));
+// (alpha: 0.01 everywhere but level 0 of SMP_1D_ver2 / ver3, whose LeakyReLU2D has slope 0 -- gfsmp::Config::level_slope)
+__global__ void bias_lrelu_forward(float *__restrict__ Y, const float *__restrict__ b, int C, size_t total, float alpha) {
+    GRID_STRIDE(i, total) {
+        const float z = Y[i] + (b ? b[i % C] : 0.f);
+        Y[i] = z > 0.f ? z : alpha * z;
+    }
 }
 
 // dZ = dF * lrelu'(z), decided from the sign of the stored activation (LeakyReLU is monotone: f > 0 <=> z > 0);
 // also leaves per-block partial column sums of dZ for the bias gradient (VectorAddTensor.h:61-72)
 __global__ void lrelu_backward_colsum(const float *__restrict__ F, float *__restrict__ dF, float *__restrict__ part, int C,
-                                      long long rows, int rows_per_block) {
+                                      long long rows, int rows_per_block, float alpha) {
     __shared__ float red[256];
     const long long r0 = (long long)blockIdx.x * rows_per_block;
     const long long r1 = (r0 + rows_per_block < rows) ? r0 + rows_per_block : rows;
@@ -210,7 +214,7 @@ __global__ void lrelu_backward_colsum(const float *__restrict__ F, float *__rest
         if (f < C && rr < rl)
             for (long long r = r0 + rr; r < r1; r += rl) {
                 const size_t i = (size_t)r * C + f;
-                const float d = dF[i] * (F[i] > 0.f ? 1.f : kAlpha);
+                const float d = dF[i] * (F[i] > 0.f ? 1.f : alpha);
                 dF[i] = d;
                 s += d;
             }
@@ -632,7 +636,18 @@ gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channel
     s->cfg.custom_matmul = cfg->custom_matmul ? 1 : 0;
     s->cfg.physics = cfg->physics ? 1 : 0;
     s->cfg.nClass = nClass;
-    if (cfg->first_order) {   // SMP_theta: K_l = [2 C'][C], per-size blocks of max_nVertices entries (gfsmp::Config::first_order)
+    if (cfg->first_order >= 2) {   // SMP_1D, SMP_1D_ver2, SMP_1D_ver3 (smp_level_1d.hip); a classifier read-out is allowed
+        if (!gf::smp_1d_config_ok(cfg)) {
+            delete s;
+            return fail(ctx, GF_ERR_INVALID, "gf_smp_create: first_order = %d (2: SMP_1D, 3: SMP_1D_ver2, 4: SMP_1D_ver3) needs max_receptive_field "
+                                             "(%d) == max_nVertices (%d) and nContractions = custom_matmul = physics = 0", cfg->first_order,
+                        cfg->max_receptive_field, cfg->max_nVertices);
+        }
+        s->cfg.first_order = cfg->first_order;
+        s->cfg.max_nVertices = cfg->max_nVertices;
+        s->cfg.nContractions = 2;
+        s->grad_allreduce = 0;
+    } else if (cfg->first_order) {   // SMP_theta: K_l = [2 C'][C], per-size blocks of max_nVertices entries (gfsmp::Config::first_order)
         if (nClass) {
             delete s;
             return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: a first-order model (first_order = 1) has no classifier read-out");
@@ -695,7 +710,7 @@ extern "C" {
 
 // (a gamma physics tower is built by gf_smp_model_create only: the single-model handle keeps refusing it)
 gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out) {
-    if (cfg && cfg->physics && cfg->first_order)
+    if (cfg && cfg->physics && cfg->first_order == 1)
         return fail(ctx, GF_ERR_INVALID, "gf_smp_create: first_order = 1 has no single-handle physics tower: set physics = 0, or build SMP_theta_physics / "
                                          "SMP_theta_pairgraphs with gf_smp_model_create (first_order = 1)");
     if (cfg && cfg->physics && cfg->nContractions == 4)
@@ -728,7 +743,7 @@ size_t gf_smp_param_count(const gf_smp *s) { return s ? gf::param_count(s->ucfg)
 gf_status gf_smp_create_classifier(gf_ctx *ctx, const gf_smp_config *cfg, int nClass, gf_smp **out) {
     if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
     if (!cfg || !out) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: null argument");
-    if (cfg->first_order)
+    if (cfg->first_order == 1)   // (SMP_theta has no `_classification` class; first_order = 2, 3, 4 do: SMP_1D*_classification)
         return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: a first-order model (first_order = 1) has no classifier read-out");
     if (cfg->physics) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: a physics tower has no read-out of its own (physics = 0)");
     if (nClass < 2) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: nClass = %d (at least 2)", nClass);
@@ -791,7 +806,7 @@ gf_status forward_level_opbyop(gf_smp *s, int l, const float *Kl, const float *b
                               : gemm(ctx, false, false, (int)h.rows, Cc, KC, d.Q, KC, 0, Kl, Cc, 0, d.f, Cc, 0, 1, 0);
     if (st == GF_OK) st = extra_products_forward(s, l);
     if (st != GF_OK) return st;
-    GF_LAUNCH(ctx, "smp_bias_lrelu", bias_lrelu_forward, dim3(grid_for((size_t)h.rows * Cc)), dim3(256), 0, d.f, bl, Cc, (size_t)h.rows * Cc);
+    GF_LAUNCH(ctx, "smp_bias_lrelu", bias_lrelu_forward, dim3(grid_for((size_t)h.rows * Cc)), dim3(256), 0, d.f, bl, Cc, (size_t)h.rows * Cc, kAlpha);
     return GF_OK;
 }
 
@@ -834,6 +849,7 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
     if (st != GF_OK) return st;
     const gfsmp::BatchLayout &B = s->lay;
     const int L = s->cfg.nLevels, C = s->cfg.nChanels, FD = s->cfg.fdim();
+    const int CL = s->cfg.top_channels();   // (the read-out's width: C but for the channel-doubling SMP_1D_ver2 / ver3)
     const float *H, *W;
     std::vector<const float *> K, b;
     view_params<const float>(s->cfg, params, &H, &K, &b, &W);
@@ -845,7 +861,7 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
     st = gemm(ctx, false, true, nV, C, FD, s->x, FD, 0, H, FD, 0, s->lv[0].f, C, 0, 1, 0);
     if (st != GF_OK) return st;
     GF_LAUNCH(ctx, "smp_bias_lrelu", bias_lrelu_forward, dim3(grid_for((size_t)nV * C)), dim3(256), 0, s->lv[0].f, (const float *)nullptr, C,
-              (size_t)nV * C);
+              (size_t)nV * C, s->cfg.level_slope());
     for (int l = 0; l <= L; ++l) s->lv[l].psum_ready = s->lv[l].pmax_ready = false;
     s->bwd_consumed = false;
     st = dup_level(s, 0);   // (SMP_2D_ver6 on the 18-slice level: channels [C, 2C) <- the transposed matrices; level 0: copies)
@@ -859,7 +875,9 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
         switch (kind[l]) {
         case LevelKind::Fused18: st = smp_fused_forward_level(s, l, K[l], b[l]); break;
         case LevelKind::Gamma: st = smp_gamma_forward_level(s, l, K[l], b[l]); break;   // products on the rows of level l - 1, one gather into f_l
-        case LevelKind::Theta: st = smp_theta_forward_level(s, l, K[l], b[l]); break;   // the same shape of level, first order (b[l]: the per-size block)
+        case LevelKind::Theta:   // the same shape of level, first order (b[l]: the per-size block); SMP_1D*: no [2 C'][C] matrix
+            st = s->cfg.first_order >= 2 ? smp_1d_forward_level(s, l, K[l], b[l]) : smp_theta_forward_level(s, l, K[l], b[l]);
+            break;
         case LevelKind::OpByOp: st = forward_level_opbyop(s, l, K[l], b[l]); break;
         }
         if (st == GF_OK && l < L) st = dup_level(s, l);
@@ -884,11 +902,11 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
             if (st != GF_OK) return st;
         } else {
             GF_LAUNCH(ctx, "smp_readout_mol", readout_molecules, dim3(B.nMol), dim3(256), 0, s->vf, s->mol_ptr, s->mol_nodes, W, targets, s->g, s->yhat,
-                      loss, s->dy, C);
+                      loss, s->dy, CL);
             if (predict) GF_HIP_TRY(ctx, hipMemcpyAsync(predict, s->yhat, sizeof(float) * B.nMol, hipMemcpyDeviceToDevice, ctx->stream));
         }
     }
-    const size_t gwidth = s->cfg.physics ? feature_width(s->cfg) : (size_t)C;
+    const size_t gwidth = s->cfg.physics ? feature_width(s->cfg) : (size_t)CL;
     if (graph_feature) GF_HIP_TRY(ctx, hipMemcpyAsync(graph_feature, s->g, sizeof(float) * B.nMol * gwidth, hipMemcpyDeviceToDevice, ctx->stream));
     s->forwarded = true;
     s->has_targets = targets != nullptr;   // (never a tower: forward_check)
@@ -954,7 +972,7 @@ gf_status bias_gradient(gf_smp *s, int l, float *dbl) {
     const gf_smp::DevLevel &d = s->lv[l];
     const long long rows = s->lay.level[l].rows;
     const int Cc = s->cfg.level_channels(l), rpb = 1024, nb = (int)((rows + rpb - 1) / rpb);
-    GF_LAUNCH(ctx, "smp_lrelu_bwd", lrelu_backward_colsum, dim3(nb), dim3(256), 0, d.f, d.df, s->colpart, Cc, rows, rpb);
+    GF_LAUNCH(ctx, "smp_lrelu_bwd", lrelu_backward_colsum, dim3(nb), dim3(256), 0, d.f, d.df, s->colpart, Cc, rows, rpb, kAlpha);
     GF_LAUNCH(ctx, "smp_colsum", colsum_finish, dim3(1), dim3(256), 0, s->colpart, dbl, Cc, nb);
     return GF_OK;
 }
@@ -1007,7 +1025,7 @@ gf_status backward_level0(gf_smp *s, float *dH) {
     int rpb = 64;
     while ((nV + rpb - 1) / rpb > (int)s->colpart_rows && rpb < 1024) rpb *= 2;
     const int nb = (nV + rpb - 1) / rpb;
-    GF_LAUNCH(ctx, "smp_lrelu_bwd", lrelu_backward_colsum, dim3(nb), dim3(256), 0, s->lv[0].f, s->lv[0].df, s->colpart, C, (long long)nV, rpb);
+    GF_LAUNCH(ctx, "smp_lrelu_bwd", lrelu_backward_colsum, dim3(nb), dim3(256), 0, s->lv[0].f, s->lv[0].df, s->colpart, C, (long long)nV, rpb, s->cfg.level_slope());
     return gemm(ctx, true, false, C, FD, nV, s->lv[0].df, C, 0, s->x, FD, 0, dH, FD, 0, 1, 1);
 }
 
@@ -1020,7 +1038,7 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
     gf_status st = ensure_ws(ctx, s->ws_need);
     if (st != GF_OK) return st;
     const gfsmp::BatchLayout &B = s->lay;
-    const int L = s->cfg.nLevels, C = s->cfg.nChanels;
+    const int L = s->cfg.nLevels, C = s->cfg.top_channels();   // (the read-out's width)
     const float *H, *W;
     std::vector<const float *> K, b;
     view_params<const float>(s->cfg, params, &H, &K, &b, &W);
@@ -1095,8 +1113,8 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
         case LevelKind::Theta:   // dz, the per-size gradients, dG gathered from dz, dK_l and df_{l-1} on the rows of level l - 1
             if (dfeat) st = feature_nodevec(s, dfeat, l);
             if (st == GF_OK)
-                st = smp_theta_backward_level(s, l, K[l], b[l], dK[l], db[l], dfeat ? s->lv[l].dshl : l == L ? s->dsh : nullptr, /*rows_too=*/l < L,
-                                              smp_dp_level_done);
+                st = (s->cfg.first_order >= 2 ? smp_1d_backward_level : smp_theta_backward_level)(
+                    s, l, K[l], b[l], dK[l], db[l], dfeat ? s->lv[l].dshl : l == L ? s->dsh : nullptr, /*rows_too=*/l < L, smp_dp_level_done);
             break;
         }
         if (st == GF_OK) st = send_df_down(s, l, kind[l]);
@@ -1217,7 +1235,7 @@ gf_status gf_smp_backward_features(gf_smp *s, const float *params, float *grads,
 
 size_t gf_smp_feature_width(const gf_smp *s) {
     if (!s) return 0;
-    return s->cfg.physics ? gf::feature_width(s->ucfg) : (size_t)s->ucfg.nChanels;
+    return s->cfg.physics ? gf::feature_width(s->ucfg) : (size_t)s->ucfg.top_channels();
 }
 
 /* 1 (default): fused level kernels where the shape allows; 0: the op-by-op pipeline (promotion, RisiContraction_18,

@@ -105,6 +105,14 @@ gf_status smp_wgrad_fp32_c64(gf_ctx *ctx, const float *T, const float *dO, const
 namespace gf {
 // min_pad: the smallest padded width the handle may compute at (32 for the towers of a slice-dropout model)
 gf_status smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channels, gf_smp **out, int min_pad = 0, int nClass = 0);   // gf_smp_create = (.., true, ..)
+// what first_order = 2, 3, 4 (SMP_1D, SMP_1D_ver2, SMP_1D_ver3) asks of the rest of a configuration: no cap (max_receptive_field ==
+// max_nVertices), nContractions = custom_matmul = physics = 0, channel counts and multiplicities that fit an int
+inline bool smp_1d_config_ok(const gf_smp_config *cfg) {
+    if (cfg->first_order < 2 || cfg->first_order > 4) return false;
+    if (cfg->nContractions || cfg->custom_matmul || cfg->physics || cfg->max_nVertices != cfg->max_receptive_field) return false;
+    if (cfg->first_order == 2) return cfg->max_nVertices <= 2000;   // (th_weight = j (j + 1) (j + 2) / 6, j <= max_nVertices)
+    return cfg->nLevels <= 16 && ((long long)cfg->nChanels << cfg->nLevels) <= (1 << 20);   // (C_l = C << l)
+}
 void smp_derive_plan(gf_smp *s, bool allow_embed);
 gf_status smp_switch_plan(gf_smp *s, bool embed);
 constexpr int kPadMaxLevels = 15;   // levels a padded model's layout map holds (gf_smp_create: deeper models compute at nChanels)
@@ -312,6 +320,11 @@ gf_status smp_theta_forward_level(gf_smp *s, int l, const float *Kl, const float
 // node_df: the read-out's gradient as one vector per node or null; rows_too: d.df holds a per-row gradient as well (levels below the top)
 gf_status smp_theta_backward_level(gf_smp *s, int l, const float *Kl, const float *sizes, float *dKl, float *dsizes, const float *node_df,
                                    bool rows_too, gf_status (*wgrad_done)(gf_smp *, int));
+// The levels of SMP_1D, SMP_1D_ver2, SMP_1D_ver3 (cfg.first_order = 2, 3, 4; smp_level_1d.hip): the same tables, sizes and arguments; Kl / dKl
+// are read by ver3 only (K_eye, K_one).  No GEMM in SMP_1D / ver2; one forward and two backward in ver3.
+gf_status smp_1d_forward_level(gf_smp *s, int l, const float *Kl, const float *sizes);
+gf_status smp_1d_backward_level(gf_smp *s, int l, const float *Kl, const float *sizes, float *dKl, float *dsizes, const float *node_df,
+                                bool rows_too, gf_status (*wgrad_done)(gf_smp *, int));
 // the first-order read-out of level l: sh[n] = column sums over the node's s rows (ShrinkMatrix), vf = LeakyReLU(sh); and its reverse,
 // df_l[n][i][:] (+)= dvec[n][:] at every row i of the node, dvec = one gradient vector per node
 gf_status smp_theta_readout(gf_smp *s, int l, float *sh, float *vf);
@@ -333,8 +346,8 @@ gf_status smp_dp_level_done(gf_smp *s, int l);
 inline size_t param_count(const gfsmp::Config &c) {
     size_t n = (size_t)c.nChanels * c.fdim();
     for (int l = 1; l <= c.nLevels; ++l)
-        n += (size_t)c.nContractions * c.level_channels(l - 1) * c.level_channels(l) + c.size_block(l);
-    return n + (c.physics ? 0 : (size_t)c.readout_rows() * c.nChanels);  // a physics tower ends in its level features: the head's weights are the caller's
+        n += c.weight_block(l) + c.size_block(l);
+    return n + (c.physics ? 0 : (size_t)c.readout_rows() * c.top_channels());  // a physics tower ends in its level features: the head's weights are the caller's
 }
 template <typename P>
 void view_params(const gfsmp::Config &c, P *base, P **H, std::vector<P *> *K, std::vector<P *> *b, P **W) {
@@ -349,7 +362,7 @@ void view_params(const gfsmp::Config &c, P *base, P **H, std::vector<P *> *K, st
             p += c.size_block(l);
         }
         (*K)[l] = p;
-        p += (size_t)c.nContractions * c.level_channels(l - 1) * c.level_channels(l);
+        p += c.weight_block(l);   // (SMP_1D / ver2: empty, K[l] is never read; ver3: K_eye then K_one = [2 C_{l-1}][C_{l-1}])
         if (c.first_order) continue;
         (*b)[l] = p;
         p += c.level_channels(l);

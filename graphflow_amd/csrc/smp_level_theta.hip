@@ -20,79 +20,15 @@
 // nodes into a workgroup (about 256 (position, channel vector) items, offsets from a wave scan in LDS), the vector 4 / 2 / 1 floats as Cc
 // allows.  Every sum runs in a fixed order (positions, children, consumers ascending; the segment reductions fold fixed trees), the GEMMs
 // are the deterministic ones of mixers.hip: two runs give the same bits, no atomics.  Every output element is written by its kernel.
-#include "smp_internal.h"
+#include "smp_first_order.h"
 
 namespace gf {
+using namespace first_order;
 namespace {
 
 constexpr float kThetaAlpha = 0.01f;   // LeakyReLU2D.h:31, LeakyReLU.h default
-constexpr int kThetaMaxPack = 64;      // nodes per workgroup: one wave builds their item offsets
 
 __device__ __forceinline__ float lrelu(float z) { return z > 0.f ? z : kThetaAlpha * z; }
-
-template <int V>
-struct Vf {
-    float v[V];
-};
-template <int V>
-__device__ __forceinline__ Vf<V> vzero() {
-    Vf<V> r;
-#pragma unroll
-    for (int k = 0; k < V; ++k) r.v[k] = 0.f;
-    return r;
-}
-template <int V>
-__device__ __forceinline__ Vf<V> vld(const float *p) {   // (p is V-float aligned: rows are multiples of Cc, V | Cc)
-    Vf<V> r;
-    if constexpr (V == 4) {
-        const float4 t = *reinterpret_cast<const float4 *>(p);
-        r.v[0] = t.x, r.v[1] = t.y, r.v[2] = t.z, r.v[3] = t.w;
-    } else if constexpr (V == 2) {
-        const float2 t = *reinterpret_cast<const float2 *>(p);
-        r.v[0] = t.x, r.v[1] = t.y;
-    } else {
-        r.v[0] = *p;
-    }
-    return r;
-}
-template <int V>
-__device__ __forceinline__ void vst(float *p, const Vf<V> &r) {
-    if constexpr (V == 4) *reinterpret_cast<float4 *>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    else if constexpr (V == 2) *reinterpret_cast<float2 *>(p) = make_float2(r.v[0], r.v[1]);
-    else *p = r.v[0];
-}
-template <int V>
-__device__ __forceinline__ void vadd(Vf<V> &a, const Vf<V> &b) {
-#pragma unroll
-    for (int k = 0; k < V; ++k) a.v[k] += b.v[k];
-}
-
-// off[0 .. np] = exclusive prefix of cnt over the workgroup's np <= 64 nodes (wave 0), then a barrier
-__device__ __forceinline__ void pack_offsets(int *off, int cnt, int np) {
-    if (threadIdx.x < 64) {
-        int v = (int)threadIdx.x < np ? cnt : 0;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int u = __shfl_up(v, d, 64);
-            if ((int)threadIdx.x >= d) v += u;
-        }
-        off[threadIdx.x + 1] = v;
-        if (threadIdx.x == 0) off[0] = 0;
-    }
-    __syncthreads();
-}
-__device__ __forceinline__ int pack_find(const int *off, int np, int i) {   // the j with off[j] <= i < off[j + 1]
-    int lo = 0, hi = np - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-// the per-size block of a level: entry s at (s - 1) * (2 + Cc) = lambda1_s, lambda2_s, b_s[Cc]
-__device__ __forceinline__ const float *size_entry(const float *sizes, int s, int Cc) { return sizes + (size_t)(s - 1) * (2 + Cc); }
-
 // Forward: nodes [blockIdx.x * npw, + npw); items (node j, position i, vector q) over sum_j s_j * Cc / V.  G rows are 2 Cc floats.
 template <int V>
 __global__ __launch_bounds__(256) void theta_level_fwd(const float *__restrict__ G, const float *__restrict__ sizes, float *__restrict__ f,
@@ -306,17 +242,6 @@ __global__ void theta_readout_bwd(const float *__restrict__ dvec, const int *__r
     }
 }
 
-int theta_vec(int Cc) { return Cc % 4 == 0 ? 4 : Cc % 2 == 0 ? 2 : 1; }
-// nodes per workgroup: ~256 lanes' worth of (position, vector) items, at most kThetaMaxPack nodes
-int theta_pack(double items_per_node) {
-    const int k = (int)(256.0 / (items_per_node > 1.0 ? items_per_node : 1.0));
-    return k < 1 ? 1 : k > kThetaMaxPack ? kThetaMaxPack : k;
-}
-unsigned grid_for(size_t total) {
-    const size_t blocks = (total + 255) / 256;
-    return (unsigned)(blocks > 1048576 ? 1048576 : (blocks == 0 ? 1 : blocks));
-}
-
 }  // namespace
 
 // G = f_{l-1} [K_top | K_bot] into the level's Q buffer, then the gather with the per-size factors, bias and LeakyReLU into f_l
@@ -386,6 +311,20 @@ gf_status smp_theta_backward_level(gf_smp *s, int l, const float *Kl, const floa
     st = wgrad_done(s, l);
     if (st != GF_OK) return st;
     return gemm(ctx, false, false, (int)rows_p, Cp, 2 * Cc, d.Q, 2 * Cc, 0, d.Wst + (size_t)2 * Cp * Cc, Cp, 0, pv.df, Cp, 0, 1, 0);
+}
+
+// pieces the other first-order levels share (smp_level_1d.hip): the per-size reduction as it is, and the [2 Cp][Cc] matrix's two views
+gf_status smp_theta_size_grads(gf_ctx *ctx, const float *acc, const int *bucket, int nbuckets, float *dsizes, int Cc) {
+    GF_LAUNCH(ctx, "smpt_size_grads", theta_size_grads, dim3(nbuckets), dim3(256), 0, acc, bucket, dsizes, Cc);
+    return GF_OK;
+}
+gf_status smp_theta_weight_views(gf_ctx *ctx, const float *K, float *Kh, float *Kt, int Cp, int Cc) {
+    GF_LAUNCH(ctx, "smpt_weight_views", theta_weight_views, dim3((2 * Cp * Cc + 255) / 256), dim3(256), 0, K, Kh, Kt, Cp, Cc);
+    return GF_OK;
+}
+gf_status smp_theta_wgrad_fold(gf_ctx *ctx, const float *dKh, float *dK, int Cp, int Cc) {
+    GF_LAUNCH(ctx, "smpt_wgrad_fold", theta_wgrad_fold, dim3((2 * Cp * Cc + 255) / 256), dim3(256), 0, dKh, dK, Cp, Cc);
+    return GF_OK;
 }
 
 gf_status smp_theta_readout(gf_smp *s, int l, float *sh, float *vf) {

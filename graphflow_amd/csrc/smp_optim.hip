@@ -108,7 +108,7 @@ gf_status gf_smp_forward_host(gf_smp *s, const double *targets, double *predict,
     gf_ctx *ctx = s->ctx;
     if (!s->prepared) return fail(ctx, GF_ERR_INVALID, "gf_smp_forward_host before gf_smp_prepare");
     if (!s->own_p) return fail(ctx, GF_ERR_INVALID, "gf_smp_forward_host: no handle-owned model (gf_smp_parameters_upload)");
-    const int nMol = s->lay.nMol, C = s->ucfg.nChanels;
+    const int nMol = s->lay.nMol, C = s->ucfg.top_channels();
     gf_status st = GF_OK;
     if (!s->own_y) {
         st = gf::upload(s, &s->own_t, nullptr, (size_t)nMol);
@@ -195,9 +195,14 @@ static bool host_config(const gf_smp_config *cfg, int nClass, gfsmp::Config *out
     c.custom_matmul = cfg->custom_matmul ? 1 : 0;
     c.physics = cfg->physics ? 1 : 0;
     c.nClass = nClass;
-    if (cfg->first_order) {   // SMP_theta (gf_smp_config.first_order)
+    if (cfg->first_order == 1) {   // SMP_theta (gf_smp_config.first_order)
         if (cfg->nContractions || cfg->custom_matmul || cfg->max_nVertices < cfg->max_receptive_field || nClass) return false;
         c.first_order = 1;
+        c.max_nVertices = cfg->max_nVertices;
+        c.nContractions = 2;
+    } else if (cfg->first_order) {   // 2, 3, 4: SMP_1D, SMP_1D_ver2, SMP_1D_ver3 (no cap; a classifier read-out is allowed)
+        if (!gf::smp_1d_config_ok(cfg)) return false;
+        c.first_order = cfg->first_order;
         c.max_nVertices = cfg->max_nVertices;
         c.nContractions = 2;
     }
@@ -217,10 +222,15 @@ static gf_status uniform_init_host(const gf_smp_config *cfg, int nClass, float *
                 sizes.push_back(1);
                 sizes.push_back((size_t)c.level_channels(l));
             }
-        sizes.push_back((size_t)c.nContractions * c.level_channels(l - 1) * c.level_channels(l));
+        if (c.first_order == 4) {   // K_eye, K_one: one block each (SMP_1D_ver3.h:238-239)
+            sizes.push_back(c.weight_block(l) / 2);
+            sizes.push_back(c.weight_block(l) / 2);
+        } else if (c.weight_block(l)) {
+            sizes.push_back(c.weight_block(l));
+        }
         if (!c.first_order) sizes.push_back((size_t)c.level_channels(l));
     }
-    if (!c.physics) sizes.push_back((size_t)(nClass > 1 ? nClass : 1) * C);
+    if (!c.physics) sizes.push_back((size_t)(nClass > 1 ? nClass : 1) * c.top_channels());
     size_t off = 0;
     for (size_t v = 0; v < sizes.size(); ++v)
         for (size_t i = 0; i < sizes[v]; ++i) {
@@ -234,6 +244,11 @@ gf_status gf_smp_uniform_init_host(const gf_smp_config *cfg, float *params) { re
 size_t gf_smp_config_param_count(const gf_smp_config *cfg) {
     gfsmp::Config c;
     return host_config(cfg, 0, &c) ? gf::param_count(c) : 0;
+}
+size_t gf_smp_classifier_config_param_count(const gf_smp_config *cfg, int nClass) {
+    gfsmp::Config c;
+    if (!cfg || cfg->physics || cfg->first_order == 1 || nClass < 2) return 0;   // (what gf_smp_create_classifier refuses)
+    return host_config(cfg, nClass, &c) ? gf::param_count(c) : 0;
 }
 // ... of the `_classification` models (SMP_2D_ver6_classification.h:256-259): sgd->params holds Vector*, so W [nClass][C] is drawn by
 // uniform_init(Vector*) like the rest, with the divisor 10 * nClass * C

@@ -676,7 +676,7 @@ void build_batch_theta(const Config &cfg, int nMol, const int *nVertices, const 
                 const size_t sv = out->mols[m].phi[l][v].size();
                 int j = 1;
                 for (int u = 0; u < v; ++u) j += out->mols[m].phi[l][u].size() == sv;
-                lv.th_weight[(size_t)node_of[l][g0 + v]] = j;
+                lv.th_weight[(size_t)node_of[l][g0 + v]] = cfg.first_order == 2 ? (int)((long long)j * (j + 1) * (j + 2) / 6) : j;   // (SMP_1D: see th_weight)
             }
         }
         lv.th_cons_row.resize((size_t)pairs);

@@ -52,11 +52,24 @@ struct Config {
     int nClass = 0;
     // 1: the first-order models (GraphFlow/SMP_theta.h, gf_smp_config.first_order): f_l[v] is [s][C], nContractions = 2 (K_l = [2 C'][C]),
     // and every level has a (lambda1, lambda2, b[C_l]) block per field size 1 .. max_nVertices in front of K_l
+    // 2, 3, 4: SMP_1D, SMP_1D_ver2, SMP_1D_ver3 (GraphFlow/SMP_1D*.h; smp_level_1d.hip) -- the same fields without a cap, children and
+    // per-size blocks, but no [2 C'][C] matrix: z = lambda1 S + lambda2 sumS + b (2: additive, C_l = C), [lambda1 S | lambda2 sumS] + b
+    // (3: concatenating, C_l = 2 C_{l-1}), [lambda1 S K_eye | lambda2 sumS K_one] + b (4: two [C_{l-1}][C_{l-1}] matrices BEHIND the
+    // per-size blocks).  LeakyReLU2D slope 0 instead of 0.01 in 3 and 4, level 0 included.
     int first_order = 0, max_nVertices = 0;
+    bool concat() const { return first_order >= 3; }   // C_l = 2 C_{l-1}
+    float level_slope() const { return concat() ? 0.f : 0.01f; }   // LeakyReLU2D of every level (the read-out's LeakyReLU stays at 0.01)
     size_t size_block(int l) const { return first_order ? (size_t)max_nVertices * (2 + (size_t)level_channels(l)) : (size_t)level_channels(l); }
+    // floats of the level's matrix block: K_l [nContractions C_{l-1}][C_l]; none in SMP_1D / ver2; K_eye, K_one in ver3
+    size_t weight_block(int l) const {
+        const size_t Cp = (size_t)level_channels(l - 1);
+        return first_order == 2 || first_order == 3 ? 0 : first_order == 4 ? 2 * Cp * Cp : (size_t)nContractions * Cp * level_channels(l);
+    }
+    int top_channels() const { return first_order >= 2 ? level_channels(nLevels) : nChanels;  }   // width of the graph feature and of W's rows
     int readout_rows() const { return nClass > 1 ? nClass : 1; }   // rows of W: [1][C] is the regression's [C]
     bool square() const { return !physics || uniform; }   // K_l is [nContractions C][C] at every level
     int level_channels(int l) const {
+        if (concat()) return nChanels << l;
         if (square()) return nChanels;
         int c = nChanels >> l;
         return c < 1 ? 1 : c;
@@ -151,6 +164,9 @@ struct LevelLayout {
     // How often the reference counts a node's contribution to dlambda1_s / dlambda2_s.  SMP_theta adds the SHARED ops W_eye[s] / W_one[s]
     // (ScalarMatMul) to the graph once per vertex of size s (SMP_theta.h:590-591), and GraphFlow::backward runs an op once per appearance:
     // the j-th vertex of size s of a molecule (ascending v) has its gradient handed to lambda_s j times.  th_weight[n] = that j.
+    // SMP_1D (Config::first_order == 2) puts three shared ops between a vertex and lambda_s -- W[s] (Reshape2D), W_flat[s] (Add), W_eye[s] /
+    // W_one[s] -- each run once per appearance on a gradient that keeps accumulating (SMP_1D.h:498-503): a running sum of a running sum of a
+    // running sum, th_weight[n] = j (j + 1) (j + 2) / 6.
     tvec<int> th_weight;          // [nNodes]
 };
 

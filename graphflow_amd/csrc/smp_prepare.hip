@@ -767,7 +767,7 @@ gf_status build_row_tables(gf_smp *s) {
 // the level-0 input, the read-out and the per-molecule buffers
 gf_status alloc_readout(gf_smp *s, int nMol) {
     const gfsmp::BatchLayout &B = s->lay;
-    const int L = s->cfg.nLevels, C = s->cfg.nChanels;
+    const int L = s->cfg.nLevels, C = s->cfg.top_channels();   // (the read-out's width: nChanels but for SMP_1D_ver2 / ver3)
     const gfsmp::LevelLayout &top = B.level[L];
     Taker t = {s};
     t.put(&s->x, B.x);
@@ -856,9 +856,19 @@ gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int
         t.put(&d.th_inv, h.th_inv);
         t.put(&d.th_bucket, h.th_bucket);
         t.put(&d.th_weight, h.th_weight);
+        t.alloc(&d.th_node, nodes * 3 * Cl);
+        if (cfg.first_order >= 2) {   // SMP_1D*: A = S and B = sumS are Cp wide; a matrix, and so G / dG and the weight views, only in ver3
+            t.alloc(&d.th_A, (size_t)h.rows * Cp);
+            t.alloc(&d.th_B, nodes * Cp);
+            if (cfg.first_order == 4) {
+                t.alloc(&d.Q, (size_t)s->lay.level[l - 1].rows * 2 * Cp);   // [rows of level l - 1][2 Cp]
+                t.alloc(&d.Wst, 4 * Cp * Cp);                               // [K_eye | K_one] as [Cp][2 Cp], and its transpose
+                t.alloc(&d.dWst, 2 * Cp * Cp);
+            }
+            continue;
+        }
         t.alloc(&d.th_A, (size_t)h.rows * Cl);
         t.alloc(&d.th_B, nodes * Cl);
-        t.alloc(&d.th_node, nodes * 3 * Cl);
         t.alloc(&d.Q, (size_t)s->lay.level[l - 1].rows * 2 * Cl);   // G, then dG: [rows of level l - 1][2 Cc]
         t.alloc(&d.Wst, 4 * Cp * Cl);                               // the weight views [Cp][2 Cc] and [2 Cc][Cp]
         t.alloc(&d.dWst, 2 * Cp * Cl);
@@ -954,6 +964,8 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
 gf_status gf_smp_prepare_molecule_host(const gf_smp_config *cfg, int V, const int *adj, const double *feature,
                                        int *phi_out, double *wl_out) {
     if (!cfg || V <= 0 || !adj || !feature || !phi_out) return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: bad argument");
+    if (cfg->first_order >= 2 && !gf::smp_1d_config_ok(cfg))   // (SMP_1D* have no cap: a capped field is not one of theirs)
+        return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: first_order = %d needs max_receptive_field == max_nVertices", cfg->first_order);
     gfsmp::Config c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, cfg->has_WL_ordering};
     c.physics = cfg->physics ? 1 : 0;
     gfsmp::Molecule m;

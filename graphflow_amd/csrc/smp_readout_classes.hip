@@ -135,10 +135,11 @@ __global__ void readout_backward_nodevec_classes(const float *__restrict__ dg, c
 
 }  // namespace
 
-// W [nClass][C] in the device's layout (C = gf_smp::cfg.nChanels: padded channels carry zero weights)
+// W [nClass][C] in the device's layout (C = gf_smp::cfg.top_channels(): nChanels -- padded channels carry zero weights -- or, for the
+// channel-doubling first-order forms SMP_1D_ver2 / ver3, the top level's width)
 gf_status readout_classes_forward(gf_smp *s, const float *W, const float *targets, float *predict, float *loss) {
     gf_ctx *ctx = s->ctx;
-    const int C = s->cfg.nChanels, nClass = s->cfg.nClass, nMol = s->lay.nMol;
+    const int C = s->cfg.top_channels(), nClass = s->cfg.nClass, nMol = s->lay.nMol;
     const size_t lds = sizeof(float) * ((size_t)C + 2 * (size_t)nClass);
     if (lds > 48 * 1024) return fail(ctx, GF_ERR_UNSUPPORTED, "classifier read-out: %d channels and %d classes exceed its LDS image", C, nClass);
     GF_LAUNCH(ctx, "smp_readout_mol_classes", readout_molecules_classes, dim3(nMol), dim3(256), lds, s->vf, s->mol_ptr, s->mol_nodes, W, targets, s->g,
@@ -147,7 +148,7 @@ gf_status readout_classes_forward(gf_smp *s, const float *W, const float *target
 }
 
 gf_status readout_classes_dW(gf_smp *s, float *dW) {
-    const int C = s->cfg.nChanels, nClass = s->cfg.nClass;
+    const int C = s->cfg.top_channels(), nClass = s->cfg.nClass;
     GF_LAUNCH(s->ctx, "smp_readout_dW_classes", readout_dW_classes, dim3((unsigned)((C + 15) / 16), (unsigned)nClass), dim3(256), 0, s->cls_dz, s->g, dW, C,
               nClass, s->lay.nMol);
     return GF_OK;
@@ -156,7 +157,7 @@ gf_status readout_classes_dW(gf_smp *s, float *dW) {
 // per_node: into gf_smp::dsh [nodes][C] for a fused top level; else into df_L at every (i, j) of every node
 gf_status readout_classes_backward(gf_smp *s, bool per_node) {
     gf_ctx *ctx = s->ctx;
-    const int L = s->cfg.nLevels, C = s->cfg.nChanels;
+    const int L = s->cfg.nLevels, C = s->cfg.top_channels();
     const int nodes = s->lay.level[L].nNodes;
     const size_t total = (size_t)nodes * C;
     if (per_node) {

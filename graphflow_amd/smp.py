@@ -246,6 +246,64 @@ class SMPTheta(SMPOmega):
         return out
 
 
+class SMP1D(SMPTheta):
+    """Batched SMP_1D (version 1), SMP_1D_ver2 (2) and SMP_1D_ver3 (3) of GraphFlow/SMP_1D*.h, and with nClass >= 2 their classifiers
+    (SMP_1D_classification, SMP_1D_ver3_classification; a version-2 classifier is the same read-out on SMP_1D_ver2).  First order as
+    SMP_theta, without a cap and without its [2C, C] matrix:
+      1: z = lambda1_s S + lambda2_s sumS + b_s, C channels at every level, LeakyReLU slope 0.01;
+      2: z = [lambda1_s S | lambda2_s sumS] + b_s, the channels double per level (C << l), slope 0;
+      3: z = [lambda1_s S K_eye | lambda2_s sumS K_one] + b_s, likewise.
+    Parameters in registration order: H[C, F(D+1)]; for l = 1..L: (lambda1_s, lambda2_s, b_s[C_l]) for s = 1..max_nVertices, then for
+    version 3 K_eye and K_one [C_{l-1}, C_{l-1}]; W[C_L], or W[nClass, C_L] for a classifier.  The optimiser is Momentum: step().
+    A classifier's forward(params, labels) returns (arg-max label, log p[label], graph_feature); scores() the logits and probabilities."""
+
+    def __init__(self, version, max_nVertices, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering=True, nClass=0, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.version, self.nClass = int(version), int(nClass)
+        self.cfg = self.config(version, max_nVertices, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering)
+        h = C.c_void_p()
+        if self.nClass:
+            self.ctx.check(self.lib.gf_smp_create_classifier(self.ctx.handle, C.byref(self.cfg), self.nClass, C.byref(h)))
+        else:
+            self.ctx.check(self.lib.gf_smp_create(self.ctx.handle, C.byref(self.cfg), C.byref(h)))
+        self.handle = h
+        self.n_params = self.lib.gf_smp_param_count(h)
+        self.n_mol = 0
+
+    @staticmethod
+    def config(version, max_nVertices, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering=True):
+        if version not in (1, 2, 3):
+            raise ValueError("SMP1D: version %r (1: SMP_1D, 2: SMP_1D_ver2, 3: SMP_1D_ver3)" % (version,))
+        return SMPConfig(nLevels, nChanels, nFeatures, nDepth, max_nVertices, 1 if has_WL_ordering else 0, 0, 0, 0, 1 + version, max_nVertices)
+
+    def level_channels(self, level):
+        return self.cfg.nChanels if self.version == 1 else self.cfg.nChanels << level
+
+    def step(self, params, grads, learning_rate, nBatch, gamma=0.9):
+        """Momentum::Learn(learning_rate, nBatch) as the classes' BatchLearn applies it; grads = the batch sum of backward()."""
+        return self.momentum_step(params, grads, learning_rate, nBatch, gamma)
+
+    def scores(self):
+        """(scores, probability) of a classifier's last forward, [nMol, nClass] each."""
+        if not self.nClass:
+            raise TypeError("SMP1D.scores: not a classifier (nClass = 0)")
+        return SMPClassifier.scores(self)
+
+    def uniform_init(self):
+        """Initial weights exactly as the reference constructor draws them from rand() (host numpy array; call srand first)."""
+        return SMPClassifier.uniform_init(self) if self.nClass else SMPOmega.uniform_init(self)
+
+    def activation(self, mol, level, v):
+        """f_level[v] of molecule `mol` after forward(): numpy [s, C_level]."""
+        s = len(self.receptive_field(mol, level, v))
+        out = np.empty((s, self.level_channels(level)), dtype=np.float32)
+        n = self.lib.gf_smp_read_activation(self.handle, mol, level, v, out.ctypes.data_as(C.c_void_p), out.size)
+        if n != out.size:
+            raise RuntimeError("gf_smp_read_activation(%d, %d, %d) returned %d" % (mol, level, v, n))
+        return out
+
+
 class SMPClassifier(SMPOmega):
     """The classification models of GraphFlow (SMP_2D_ver6_classification: nContractions=10, custom_matmul=True;
     SMP_2D_ver7_classification: 50, True) through gf_smp_create_classifier: the levels of the regression model, read out by

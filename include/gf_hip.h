@@ -268,15 +268,35 @@ typedef struct {
      * padding, no field-size limit other than int16 positions.  gf_smp_level_sizes: rows = sum of s, ppos = 0.  gf_smp_prepare_coulomb behaves
      * as gf_smp_prepare (the model has no reduced adjacency), gf_smp_set_fused has no effect (there is one plan), gf_smp_read_activation
      * returns [s][C].  Refused with GF_ERR_UNSUPPORTED before anything is launched:
-     *   - gf_smp_create_classifier on a first-order configuration,
+     *   - gf_smp_create_classifier on a first_order = 1 configuration,
      *   - gf_smp_set_grad_allreduce(smp, 1) on a first-order handle (no data-parallel exchange: reduce the flat gradient yourself),
      *   - gf_smp_dropout_masks on a first-order handle.
-     * Zero-initialised trailing fields give the behaviour described above. */
+     * Zero-initialised trailing fields give the behaviour described above.
+     *
+     * first_order = 2, 3, 4: the second first-order family, SMP_1D, SMP_1D_ver2 and SMP_1D_ver3 (GraphFlow/SMP_1D.h, SMP_1D_ver2.h,
+     * SMP_1D_ver3.h).  Fields (union over the vertices within one hop, WL ordering), children, S, the per-size lambda1_s, lambda2_s, b_s and
+     * the read-out are SMP_theta's; there is NO cap and no [2 C][C] matrix.  With sumS = sum_i S[i]:
+     *   2  SMP_1D       z[i] = lambda1_s S[i] + lambda2_s sumS + b_s                 C_l = C;        LeakyReLU2D slope 0.01
+     *   3  SMP_1D_ver2  z[i] = [lambda1_s S[i] | lambda2_s sumS] + b_s               C_l = C << l;   slope 0, level 0 included
+     *   4  SMP_1D_ver3  z[i] = [lambda1_s S[i] K_eye | lambda2_s sumS K_one] + b_s   C_l = C << l;   slope 0; K_eye, K_one [C_{l-1}][C_{l-1}]
+     * (the read-out's LeakyReLU keeps 0.01).  Parameter order (registration order): H [C][F (D + 1)]; for l = 1..L: for size = 1 ..
+     * max_nVertices (lambda1, lambda2, b[C_l]), then for first_order = 4 K_eye, K_one; W [C_L].  The graph feature, gf_smp_feature_width and
+     * the rows of W are C_L wide: C, or C << nLevels.  Required, else GF_ERR_INVALID: max_receptive_field == max_nVertices and
+     * nContractions = custom_matmul = physics = 0 (gf_smp_config_param_count then answers 0, gf_smp_prepare_molecule_host GF_ERR_INVALID).
+     * The gradients of lambda1_s / lambda2_s are the CLASSES', not the derivative: the reference runs its shared per-size ops once per vertex
+     * of the size on accumulating gradients, so the j-th such vertex of a molecule counts j times in SMP_1D_ver2 / ver3 (as in SMP_theta)
+     * and j (j + 1) (j + 2) / 6 times in SMP_1D (three shared ops in a row).  Every other gradient is plain.  The optimiser of the classes
+     * is Momentum: gf_smp_momentum_step.  The level is smp_level_1d.hip: no GEMM at all in SMP_1D / ver2, one forward and two backward per
+     * level in ver3; none of the 18-slice or gamma buffers.  gf_smp_create_classifier ACCEPTS these three values (SMP_1D_classification,
+     * SMP_1D_ver3_classification; 3 gives the same read-out on SMP_1D_ver2): W [nClass][C_L].  Still refused with GF_ERR_UNSUPPORTED:
+     * gf_smp_set_grad_allreduce(smp, 1) and gf_smp_dropout_masks.  gf_smp_model_create has no towers of these forms. */
     int first_order, max_nVertices;
 } gf_smp_config;
 gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out);
 /* gf_smp_param_count of the handle gf_smp_create would build from cfg (0 on a configuration it would refuse).  Host only. */
 size_t    gf_smp_config_param_count(const gf_smp_config *cfg);
+/* ... of the handle gf_smp_create_classifier would build from (cfg, nClass); 0 on what it would refuse.  Host only. */
+size_t    gf_smp_classifier_config_param_count(const gf_smp_config *cfg, int nClass);
 gf_status gf_smp_destroy(gf_smp *smp);
 size_t    gf_smp_param_count(const gf_smp *smp);
 /* The `_classification` models: SMP_2D_ver6_classification (nContractions 10, custom_matmul 1) and SMP_2D_ver7_classification (50, 1) of
