@@ -508,6 +508,7 @@ gf_status smp_contract(gf_smp *s, int l, bool backward) {
 
 LevelKind smp_level_kind(const gf_smp *s, int l) {
     if (s->cfg.first_order) return LevelKind::Theta;   // (one plan: gf_smp_set_fused has no effect)
+    if (s->cfg.steerable_2d) return LevelKind::Steerable2D;
     if (s->fused && smp_fused_supported(s, l)) return LevelKind::Fused18;
     return smp_gamma_fused(s, l) ? LevelKind::Gamma : LevelKind::OpByOp;
 }
@@ -573,7 +574,7 @@ void gf::smp_derive_plan(gf_smp *s, bool allow_embed) {
     s->cfg = s->ucfg;
     s->dup_channels = 0;
     s->n_extra = 0;
-    if (s->cfg.first_order) return;   // (the first-order level takes any channel count: computed at the caller's)
+    if (s->cfg.per_size()) return;   // (the first-order and the steerable levels take any channel count: computed at the caller's)
     {
         const bool no_pad = gf::env_is("GF_SMP_PAD_CHANNELS", '0');
         const int C = s->cfg.nChanels;
@@ -636,7 +637,18 @@ gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channel
     s->cfg.custom_matmul = cfg->custom_matmul ? 1 : 0;
     s->cfg.physics = cfg->physics ? 1 : 0;
     s->cfg.nClass = nClass;
-    if (cfg->first_order >= 2) {   // SMP_1D, SMP_1D_ver2, SMP_1D_ver3 (smp_level_1d.hip); a classifier read-out is allowed
+    if (cfg->steerable_2d) {   // SMP_2D, SMP_2D_ver4 (smp_level_2d.hip); a classifier read-out is allowed
+        if (!gf::smp_2d_config_ok(cfg)) {
+            delete s;
+            return fail(ctx, GF_ERR_INVALID, "gf_smp_create: steerable_2d = %d (1: SMP_2D, 2: SMP_2D_ver4) needs first_order = 0, max_receptive_field (%d) "
+                                             "== max_nVertices (%d) <= 4096 and nContractions = custom_matmul = physics = 0", cfg->steerable_2d,
+                        cfg->max_receptive_field, cfg->max_nVertices);
+        }
+        s->cfg.steerable_2d = cfg->steerable_2d;
+        s->cfg.max_nVertices = cfg->max_nVertices;
+        s->cfg.nContractions = 0;
+        s->grad_allreduce = 0;   // (no data-parallel exchange: gf_smp_set_grad_allreduce(.., 1) is refused)
+    } else if (cfg->first_order >= 2) {   // SMP_1D, SMP_1D_ver2, SMP_1D_ver3 (smp_level_1d.hip); a classifier read-out is allowed
         if (!gf::smp_1d_config_ok(cfg)) {
             delete s;
             return fail(ctx, GF_ERR_INVALID, "gf_smp_create: first_order = %d (2: SMP_1D, 3: SMP_1D_ver2, 4: SMP_1D_ver3) needs max_receptive_field "
@@ -676,7 +688,7 @@ gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channel
         delete s;
         return fail(ctx, GF_ERR_INVALID, "gf_smp_create: a physics tower has nDepth 0 (raw features), RisiContraction_18 or _4 and [nK C', C] weights");
     }
-    if (!s->cfg.first_order && s->cfg.nContractions != 4 && s->cfg.nContractions != 10 && s->cfg.nContractions != 18 && s->cfg.nContractions != 50) {
+    if (!s->cfg.per_size() && s->cfg.nContractions != 4 && s->cfg.nContractions != 10 && s->cfg.nContractions != 18 && s->cfg.nContractions != 50) {
         const int bad = cfg->nContractions;
         delete s;
         return fail(ctx, GF_ERR_INVALID, "gf_smp_create: nContractions = %d (expected 4, 10, 18 or 50)", bad);
@@ -866,7 +878,7 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
     s->bwd_consumed = false;
     st = dup_level(s, 0);   // (SMP_2D_ver6 on the 18-slice level: channels [C, 2C) <- the transposed matrices; level 0: copies)
     if (st != GF_OK) return st;
-    if (s->fused && !s->cfg.first_order) {
+    if (s->fused && !s->cfg.per_size()) {
         if (s->wbound && C == 64) GF_HIP_TRY(ctx, hipMemsetAsync(s->wbound, 0, sizeof(unsigned) * smp_wgrad_words(64, false) * (size_t)(L + 1), ctx->stream));
         st = smp_fused_stack_all(s, K);
         if (st != GF_OK) return st;
@@ -878,6 +890,7 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
         case LevelKind::Theta:   // the same shape of level, first order (b[l]: the per-size block); SMP_1D*: no [2 C'][C] matrix
             st = s->cfg.first_order >= 2 ? smp_1d_forward_level(s, l, K[l], b[l]) : smp_theta_forward_level(s, l, K[l], b[l]);
             break;
+        case LevelKind::Steerable2D: st = smp_2d_forward_level(s, l, K[l], b[l]); break;   // (K[l]: scalar_l, b[l]: the per-size block)
         case LevelKind::OpByOp: st = forward_level_opbyop(s, l, K[l], b[l]); break;
         }
         if (st == GF_OK && l < L) st = dup_level(s, l);
@@ -1004,7 +1017,7 @@ gf_status backward_level_opbyop(gf_smp *s, int l, const float *Kl, float *dKl) {
 // df_{l-1} from what level l left: the fused level's folded consumer gather, else the consumer-list gather of dP (a fused level's D_bb /
 // D_ac gradients arrive through dFdc beside it); the gamma level has written df_{l-1} itself
 gf_status send_df_down(gf_smp *s, int l, LevelKind kind) {
-    if (kind == LevelKind::Gamma || kind == LevelKind::Theta) return GF_OK;
+    if (kind == LevelKind::Gamma || kind == LevelKind::Theta || kind == LevelKind::Steerable2D) return GF_OK;
     const bool fused = kind == LevelKind::Fused18;
     if (fused && smp_fused_gather_enabled(s, l)) return smp_fused_gather_backward(s, l);
     const gf_smp::DevLevel &d = s->lv[l], &pv = s->lv[l - 1];
@@ -1074,7 +1087,7 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
     // the read-out's gradient into the top level: a fused level reads it as one vector per node, the others at every (i, j)
     const gfsmp::LevelLayout &top = B.level[L];
     // (a first-order level takes the read-out's gradient the same way: one vector per node, added inside its per-node kernel)
-    const bool top_fused = !dfeat && (kind[L] == LevelKind::Fused18 || kind[L] == LevelKind::Theta);
+    const bool top_fused = !dfeat && (kind[L] == LevelKind::Fused18 || kind[L] == LevelKind::Theta || kind[L] == LevelKind::Steerable2D);
     const bool classes = !dfeat && s->cfg.nClass;   // (a classifier: dg [nMol][C] goes down instead of dy[mol] * W)
     if (!dfeat && !classes) GF_LAUNCH(ctx, "smp_readout_dW", readout_dW, dim3(1), dim3(1024), 0, s->dy, s->g, dW, C, B.nMol);
     if (dfeat) {
@@ -1094,7 +1107,8 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
     for (int l = L; l >= 1; --l) {
         if (l < L) st = fold_level(s, l);   // (SMP_2D_ver6 on the 18-slice level: the gradient of the transposed copies joins the matrices')
         if (st != GF_OK) return st;
-        if (kind[l] != LevelKind::Fused18 && kind[l] != LevelKind::Theta) s->bwd_consumed = true;   // (a first-order level keeps f, A, B: repeatable)
+        if (kind[l] != LevelKind::Fused18 && kind[l] != LevelKind::Theta && kind[l] != LevelKind::Steerable2D)
+            s->bwd_consumed = true;   // (a first-order or steerable level keeps f, A, B: repeatable)
         switch (kind[l]) {
         case LevelKind::Fused18:
             if (dfeat) st = feature_nodevec(s, dfeat, l);
@@ -1115,6 +1129,9 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
             if (st == GF_OK)
                 st = (s->cfg.first_order >= 2 ? smp_1d_backward_level : smp_theta_backward_level)(
                     s, l, K[l], b[l], dK[l], db[l], dfeat ? s->lv[l].dshl : l == L ? s->dsh : nullptr, /*rows_too=*/l < L, smp_dp_level_done);
+            break;
+        case LevelKind::Steerable2D:   // dz, dS in place, the per-size gradients and dscalar_l, df_{l-1} gathered from dS (never a tower)
+            st = smp_2d_backward_level(s, l, K[l], b[l], dK[l], db[l], l == L ? s->dsh : nullptr, /*rows_too=*/l < L);
             break;
         }
         if (st == GF_OK) st = send_df_down(s, l, kind[l]);
@@ -1172,7 +1189,8 @@ gf_status gf_smp_forward(gf_smp *s, const float *params, const float *targets, f
 gf_status gf_smp_dropout_masks(gf_smp *s, const unsigned *masks, float scale) {
     if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
     gf_ctx *ctx = s->ctx;
-    if (s->cfg.first_order) return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_dropout_masks: a first-order handle has no contraction slices to drop");
+    if (s->cfg.per_size())
+        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_dropout_masks: a first-order or steerable_2d handle has no contraction slices to drop");
     if (!masks) {
         s->drop_on = false;
         return GF_OK;
@@ -1215,8 +1233,9 @@ gf_status gf_smp_dropout_masks(gf_smp *s, const unsigned *masks, float scale) {
 
 gf_status gf_smp_set_grad_allreduce(gf_smp *s, int on) {
     if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
-    if (on && s->cfg.first_order)
-        return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_set_grad_allreduce: a first-order handle has no data-parallel exchange (reduce the flat gradient)");
+    if (on && s->cfg.per_size())
+        return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_set_grad_allreduce: a first-order or steerable_2d handle has no data-parallel exchange (reduce "
+                                                "the flat gradient)");
     s->grad_allreduce = on ? 1 : 0;
     return GF_OK;
 }
@@ -1228,6 +1247,8 @@ gf_status gf_smp_backward(gf_smp *s, const float *params, float *grads, int accu
 
 gf_status gf_smp_backward_features(gf_smp *s, const float *params, float *grads, const float *d_feature, int accumulate) {
     if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
+    if (s->cfg.steerable_2d)
+        return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_backward_features: a steerable_2d handle (SMP_2D, SMP_2D_ver4) is no tower");
     if (!d_feature) return fail(s->ctx, GF_ERR_INVALID, "gf_smp_backward_features: null feature gradient");
     gf_status st = gf::backward_check(s, &params, &grads, accumulate, d_feature);
     return st == GF_OK ? gf::backward_run(s, params, grads, accumulate, d_feature) : st;

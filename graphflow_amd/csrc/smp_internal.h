@@ -113,6 +113,14 @@ inline bool smp_1d_config_ok(const gf_smp_config *cfg) {
     if (cfg->first_order == 2) return cfg->max_nVertices <= 2000;   // (th_weight = j (j + 1) (j + 2) / 6, j <= max_nVertices)
     return cfg->nLevels <= 16 && ((long long)cfg->nChanels << cfg->nLevels) <= (1 << 20);   // (C_l = C << l)
 }
+// what steerable_2d = 1, 2 (SMP_2D, SMP_2D_ver4) asks: first_order = 0, no cap, no contraction family / custom product / tower, a
+// multiplicity j (j + 1) / 2 (j <= max_nVertices) and channel counts that fit an int
+inline bool smp_2d_config_ok(const gf_smp_config *cfg) {
+    if (cfg->steerable_2d < 1 || cfg->steerable_2d > 2 || cfg->first_order) return false;
+    if (cfg->nContractions || cfg->custom_matmul || cfg->physics || cfg->max_nVertices != cfg->max_receptive_field) return false;
+    if (cfg->max_nVertices > 4096) return false;   // (th_weight <= 4096 * 4097 / 2; gf_smp_prepare takes no larger molecule)
+    return cfg->steerable_2d == 1 || (cfg->nLevels <= 16 && ((long long)cfg->nChanels << cfg->nLevels) <= (1 << 20));   // (C_l = C << l)
+}
 void smp_derive_plan(gf_smp *s, bool allow_embed);
 gf_status smp_switch_plan(gf_smp *s, bool embed);
 constexpr int kPadMaxLevels = 15;   // levels a padded model's layout map holds (gf_smp_create: deeper models compute at nChanels)
@@ -234,6 +242,9 @@ struct gf_smp {
         float *th_A = nullptr;     // [rows][Cc] A[i] = sum over the children of G_top (kept for dlambda1)
         float *th_B = nullptr;     // [nodes][Cc] B = sum over positions and children of G_bot (kept for dlambda2)
         float *th_node = nullptr;  // [nodes][3 Cc] reverse sweep: sum_i dz[i] | sum_i dz[i] A[i] | (sum_i dz[i]) B
+        // steerable second-order level (smp_level_2d.hip): th_A = S [rows][Cp], th_B = col [sum s][Cp], th_node = [sum s][Cc + 3 Cp] column
+        // partials of the reverse sweep, adj / node_pair as in gfsmp::LevelLayout, part2d = [blocks][Cp] partial sums of dscalar
+        float *part2d = nullptr;
     };
     std::vector<DevLevel> lv;
     // device-built level tables: the batch's adjacency matrices and the per-level statistics the kernels leave behind
@@ -295,7 +306,7 @@ constexpr int kFusedMaxField = 64;
 // What runs level l >= 1 of a pass: the fused 18-slice level (smp_fused.hip) where gf_smp_set_fused allows and smp_fused_supported takes the
 // shape, else the SMP_gamma level where smp_gamma_fused does, else the op-by-op pipeline (smp.hip); nobody else asks the two predicates.
 // Constant for the length of a pass, NOT between passes (gf_smp_set_fused, gf_smp_dropout_masks): a sweep asks at its start, keeps nothing.
-enum class LevelKind { OpByOp, Fused18, Gamma, Theta };   // Theta: every level of a first-order handle (cfg.first_order), nothing else
+enum class LevelKind { OpByOp, Fused18, Gamma, Theta, Steerable2D };   // Theta: every level of a first-order handle (cfg.first_order), Steerable2D: of a cfg.steerable_2d one, nothing else
 LevelKind smp_level_kind(const gf_smp *s, int l);
 bool smp_fused_supported(const gf_smp *s, int l);
 gf_status smp_backward_admissible(const gf_smp *s);   // smp.hip: refusals of a reverse sweep that must come before any work is issued
@@ -325,6 +336,12 @@ gf_status smp_theta_backward_level(gf_smp *s, int l, const float *Kl, const floa
 gf_status smp_1d_forward_level(gf_smp *s, int l, const float *Kl, const float *sizes);
 gf_status smp_1d_backward_level(gf_smp *s, int l, const float *Kl, const float *sizes, float *dKl, float *dsizes, const float *node_df,
                                 bool rows_too, gf_status (*wgrad_done)(gf_smp *, int));
+// The levels of SMP_2D and SMP_2D_ver4 (cfg.steerable_2d = 1, 2; smp_level_2d.hip) on the same tables: sizes = the level's per-size block
+// (lambda1[Cp], lambda2[Cp], b[Cc]) x max_nVertices, scalar = scalar_l[Cp].  No GEMM.  backward: node_df = the read-out's gradient as one
+// vector per node or null, rows_too: d.df holds a per-position gradient (levels below the top); dS is left in the first Cp columns of d.df.
+gf_status smp_2d_forward_level(gf_smp *s, int l, const float *scalar, const float *sizes);
+gf_status smp_2d_backward_level(gf_smp *s, int l, const float *scalar, const float *sizes, float *dscalar, float *dsizes, const float *node_df,
+                                bool rows_too);
 // the first-order read-out of level l: sh[n] = column sums over the node's s rows (ShrinkMatrix), vf = LeakyReLU(sh); and its reverse,
 // df_l[n][i][:] (+)= dvec[n][:] at every row i of the node, dvec = one gradient vector per node
 gf_status smp_theta_readout(gf_smp *s, int l, float *sh, float *vf);
@@ -357,13 +374,13 @@ void view_params(const gfsmp::Config &c, P *base, P **H, std::vector<P *> *K, st
     K->assign(c.nLevels + 1, nullptr);
     b->assign(c.nLevels + 1, nullptr);
     for (int l = 1; l <= c.nLevels; ++l) {
-        if (c.first_order) {   // (SMP_theta.h:254-264: the per-size blocks are registered before K_l; b[l] = the first of them)
+        if (c.per_size()) {   // (SMP_theta.h:254-264: the per-size blocks are registered before K_l; b[l] = the first of them)
             (*b)[l] = p;
             p += c.size_block(l);
         }
         (*K)[l] = p;
-        p += c.weight_block(l);   // (SMP_1D / ver2: empty, K[l] is never read; ver3: K_eye then K_one = [2 C_{l-1}][C_{l-1}])
-        if (c.first_order) continue;
+        p += c.weight_block(l);   // (SMP_1D / ver2: empty, K[l] is never read; ver3: K_eye then K_one = [2 C_{l-1}][C_{l-1}]; SMP_2D / ver4: scalar_l)
+        if (c.per_size()) continue;
         (*b)[l] = p;
         p += c.level_channels(l);
     }

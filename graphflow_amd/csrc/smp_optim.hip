@@ -195,7 +195,12 @@ static bool host_config(const gf_smp_config *cfg, int nClass, gfsmp::Config *out
     c.custom_matmul = cfg->custom_matmul ? 1 : 0;
     c.physics = cfg->physics ? 1 : 0;
     c.nClass = nClass;
-    if (cfg->first_order == 1) {   // SMP_theta (gf_smp_config.first_order)
+    if (cfg->steerable_2d) {   // SMP_2D, SMP_2D_ver4 (gf_smp_config.steerable_2d; a classifier read-out is allowed)
+        if (!gf::smp_2d_config_ok(cfg)) return false;
+        c.steerable_2d = cfg->steerable_2d;
+        c.max_nVertices = cfg->max_nVertices;
+        c.nContractions = 0;
+    } else if (cfg->first_order == 1) {   // SMP_theta (gf_smp_config.first_order)
         if (cfg->nContractions || cfg->custom_matmul || cfg->max_nVertices < cfg->max_receptive_field || nClass) return false;
         c.first_order = 1;
         c.max_nVertices = cfg->max_nVertices;
@@ -222,13 +227,19 @@ static gf_status uniform_init_host(const gf_smp_config *cfg, int nClass, float *
                 sizes.push_back(1);
                 sizes.push_back((size_t)c.level_channels(l));
             }
+        if (c.steerable_2d)   // lambda1[size], lambda2[size] [C_{l-1}], b[size] [C_l], then scalar_l below (SMP_2D.h:228-235)
+            for (int size = 1; size <= c.max_nVertices; ++size) {
+                sizes.push_back((size_t)c.level_channels(l - 1));
+                sizes.push_back((size_t)c.level_channels(l - 1));
+                sizes.push_back((size_t)c.level_channels(l));
+            }
         if (c.first_order == 4) {   // K_eye, K_one: one block each (SMP_1D_ver3.h:238-239)
             sizes.push_back(c.weight_block(l) / 2);
             sizes.push_back(c.weight_block(l) / 2);
         } else if (c.weight_block(l)) {
             sizes.push_back(c.weight_block(l));
         }
-        if (!c.first_order) sizes.push_back((size_t)c.level_channels(l));
+        if (!c.per_size()) sizes.push_back((size_t)c.level_channels(l));
     }
     if (!c.physics) sizes.push_back((size_t)(nClass > 1 ? nClass : 1) * c.top_channels());
     size_t off = 0;

@@ -604,7 +604,9 @@ void build_batch_theta(const Config &cfg, int nMol, const int *nVertices, const 
         lv.node_mol.resize(totalV);
         lv.node_vertex.resize(totalV);
         lv.node_row.resize(totalV);
-        int64_t row = 0;
+        const bool sq = cfg.steerable_2d != 0 && l > 0;   // SMP_2D / ver4: f_l[v] is [s][s][C]; node_pair = the node's first column
+        if (cfg.steerable_2d) lv.node_pair.resize(totalV);
+        int64_t row = 0, col = 0;
         for (int n = 0; n < totalV; ++n) {
             const int s = order[n].first, gv = order[n].second;
             const int m = (int)(std::upper_bound(out->mol_first_vertex.begin(), out->mol_first_vertex.end(), gv) -
@@ -619,9 +621,11 @@ void build_batch_theta(const Config &cfg, int nMol, const int *nVertices, const 
                 lv.buckets.push_back(b);
             }
             lv.buckets.back().count += 1;
-            row += s;
+            if (cfg.steerable_2d) lv.node_pair[n] = col;
+            row += sq ? (int64_t)s * s : s;
+            col += s;
         }
-        lv.rows = row;   // sum s: f_l[v] is [s][C]
+        lv.rows = row;   // sum s: f_l[v] is [s][C] (sum s^2 for a steerable second-order level)
         lv.ppos = 0;
         lv.th_bucket.clear();
         for (const Bucket &b : lv.buckets) {
@@ -676,7 +680,8 @@ void build_batch_theta(const Config &cfg, int nMol, const int *nVertices, const 
                 const size_t sv = out->mols[m].phi[l][v].size();
                 int j = 1;
                 for (int u = 0; u < v; ++u) j += out->mols[m].phi[l][u].size() == sv;
-                lv.th_weight[(size_t)node_of[l][g0 + v]] = cfg.first_order == 2 ? (int)((long long)j * (j + 1) * (j + 2) / 6) : j;   // (SMP_1D: see th_weight)
+                lv.th_weight[(size_t)node_of[l][g0 + v]] = cfg.first_order == 2 ? (int)((long long)j * (j + 1) * (j + 2) / 6)   // (SMP_1D: see th_weight)
+                                                           : cfg.steerable_2d == 1 ? (int)((long long)j * (j + 1) / 2) : j;   // (SMP_2D)
             }
         }
         lv.th_cons_row.resize((size_t)pairs);
@@ -691,7 +696,25 @@ void build_batch_theta(const Config &cfg, int nMol, const int *nVertices, const 
             }
         lv.th_inv.resize((size_t)inv_total);
         lv.inv_count = inv_total;
+        if (cfg.steerable_2d) lv.adj.resize((size_t)lv.rows);
         parallel_for(totalV, [&](int n) {
+            if (cfg.steerable_2d) {   // the reduced adjacency of phi_l(v) (SMP_2D.h:459-470; SMP_2D_ver4.h:478-503: unit diagonal, rows / their sums)
+                const int m = lv.node_mol[n], v = lv.node_vertex[n], V = nVertices[m];
+                const int *A = adj + adj_off[m];
+                const std::vector<int> &fv = out->mols[m].phi[l][v];
+                const size_t s = fv.size();
+                float *a = &lv.adj[(size_t)lv.node_row[n]];
+                for (size_t i = 0; i < s; ++i) {
+                    double degree = 0.0;
+                    for (size_t j = 0; j < s; ++j) {
+                        const double x = cfg.steerable_2d == 2 && fv[i] == fv[j] ? 1.0 : (double)A[(size_t)fv[i] * V + fv[j]];
+                        a[i * s + j] = (float)x;
+                        degree += x;
+                    }
+                    if (cfg.steerable_2d == 2)
+                        for (size_t j = 0; j < s; ++j) a[i * s + j] = (float)((double)a[i * s + j] / degree);
+                }
+            }
             {   // node n of level l as a consumer: its children
                 const int m = lv.node_mol[n], v = lv.node_vertex[n], V = nVertices[m], g0 = out->mol_first_vertex[m];
                 const Molecule &M = out->mols[m];

@@ -57,15 +57,25 @@ struct Config {
     // (3: concatenating, C_l = 2 C_{l-1}), [lambda1 S K_eye | lambda2 sumS K_one] + b (4: two [C_{l-1}][C_{l-1}] matrices BEHIND the
     // per-size blocks).  LeakyReLU2D slope 0 instead of 0.01 in 3 and 4, level 0 included.
     int first_order = 0, max_nVertices = 0;
-    bool concat() const { return first_order >= 3; }   // C_l = 2 C_{l-1}
-    float level_slope() const { return concat() ? 0.f : 0.01f; }   // LeakyReLU2D of every level (the read-out's LeakyReLU stays at 0.01)
-    size_t size_block(int l) const { return first_order ? (size_t)max_nVertices * (2 + (size_t)level_channels(l)) : (size_t)level_channels(l); }
-    // floats of the level's matrix block: K_l [nContractions C_{l-1}][C_l]; none in SMP_1D / ver2; K_eye, K_one in ver3
+    // 1, 2: the second-order steerable models SMP_2D and SMP_2D_ver4 (GraphFlow/SMP_2D.h, SMP_2D_ver4.h; gf_smp_config.steerable_2d;
+    // smp_level_2d.hip): f_l[v] is [s][s][C_l], the fields, children and pi are the first-order models' (no cap), applied to both indices.
+    // Per level: for size = 1 .. max_nVertices (lambda1_s[C_{l-1}], lambda2_s[C_{l-1}], b_s[C_l]), then scalar_l[C_{l-1}] (the "matrix
+    // block").  1: z = lambda1 S + lambda2 col + b, C_l = C; 2: z = [lambda1 S | lambda2 col] + b, C_l = 2 C_{l-1}.  Slope 0.01 everywhere.
+    int steerable_2d = 0;
+    bool per_size() const { return first_order || steerable_2d; }   // a handle on the th_* tables, per-size blocks in front of the matrix block
+    bool concat() const { return first_order >= 3 || steerable_2d == 2; }   // C_l = 2 C_{l-1}
+    float level_slope() const { return first_order >= 3 ? 0.f : 0.01f; }   // LeakyReLU2D / 3D of every level (the read-out's LeakyReLU stays at 0.01)
+    size_t size_block(int l) const {
+        if (steerable_2d) return (size_t)max_nVertices * (2 * (size_t)level_channels(l - 1) + (size_t)level_channels(l));
+        return first_order ? (size_t)max_nVertices * (2 + (size_t)level_channels(l)) : (size_t)level_channels(l);
+    }
+    // floats of the level's matrix block: K_l [nContractions C_{l-1}][C_l]; none in SMP_1D / ver2; K_eye, K_one in ver3; scalar_l in SMP_2D / ver4
     size_t weight_block(int l) const {
         const size_t Cp = (size_t)level_channels(l - 1);
+        if (steerable_2d) return Cp;
         return first_order == 2 || first_order == 3 ? 0 : first_order == 4 ? 2 * Cp * Cp : (size_t)nContractions * Cp * level_channels(l);
     }
-    int top_channels() const { return first_order >= 2 ? level_channels(nLevels) : nChanels;  }   // width of the graph feature and of W's rows
+    int top_channels() const { return first_order >= 2 || steerable_2d ? level_channels(nLevels) : nChanels;  }   // width of the graph feature and of W's rows
     int readout_rows() const { return nClass > 1 ? nClass : 1; }   // rows of W: [1][C] is the regression's [C]
     bool square() const { return !physics || uniform; }   // K_l is [nContractions C][C] at every level
     int level_channels(int l) const {
@@ -167,7 +177,12 @@ struct LevelLayout {
     // SMP_1D (Config::first_order == 2) puts three shared ops between a vertex and lambda_s -- W[s] (Reshape2D), W_flat[s] (Add), W_eye[s] /
     // W_one[s] -- each run once per appearance on a gradient that keeps accumulating (SMP_1D.h:498-503): a running sum of a running sum of a
     // running sum, th_weight[n] = j (j + 1) (j + 2) / 6.
+    // SMP_2D (Config::steerable_2d == 1) has two: W[s] (SumTensor3D) and W_eye[s] / W_one[s] (VectorBroadcastMat), SMP_2D.h:558-573 --
+    // th_weight[n] = j (j + 1) / 2; SMP_2D_ver4 hands W_eye[s] / W_one[s] to the vertex's TensorMul directly (SMP_2D_ver4.h:603-608): j.
     tvec<int> th_weight;          // [nNodes]
+    // steerable second-order levels (Config::steerable_2d): rows = sum s^2, node_row = first row of the node's [s][s][C] tensor, node_pair
+    // = first of its s columns (sum of s before it), adj = the class's reduced adjacency of phi_l(v) ([rows]; SMP_2D_ver4: unit diagonal,
+    // rows divided by their sums, SMP_2D_ver4.h:478-503); the th_* tables as above, pi / inv applied to both indices
 };
 
 // Register classes of the backward gather: a source of size s_w runs the code path with gather_pad(s_w) accumulators (and
@@ -203,7 +218,7 @@ struct BatchLayout {
 void build_batch(const Config &cfg, int nMol, const int *nVertices, const int *adj, const double *feature,
                  const double *coulomb, BatchLayout *out);
 
-// The batch of a first-order model (Config::first_order): molecules, level-0 input, nodes in bucket order, rows = field positions, and the
+// The batch of a first-order model (Config::first_order) or a steerable second-order one (Config::steerable_2d): molecules, level-0 input, nodes in bucket order, rows = field positions, and the
 // th_* tables of every level >= 1; none of the tables of the 18-slice level.  Built on the host threads.
 void build_batch_theta(const Config &cfg, int nMol, const int *nVertices, const int *adj, const double *feature, BatchLayout *out);
 

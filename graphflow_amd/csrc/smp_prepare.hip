@@ -774,7 +774,7 @@ gf_status alloc_readout(gf_smp *s, int nMol) {
     s->wbound = nullptr;
     // scratch words of the fused levels' weight gradients (channel maxima, exact column bounds; a 64-channel level keeps only its maxima);
     // 128 channels: the plain 18-slice model's four sub-block launches
-    if (!s->cfg.first_order && s->cfg.square() && (smp_panel_channels(C) || (C == 128 && s->cfg.nContractions == 18 && smp_c128_switch())))
+    if (!s->cfg.per_size() && s->cfg.square() && (smp_panel_channels(C) || (C == 128 && s->cfg.nContractions == 18 && smp_c128_switch())))
         t.alloc(&s->wbound, smp_wgrad_words(C, C != 64) * (size_t)(L + 1));
     t.alloc(&s->sh, (size_t)top.nNodes * C);
     t.alloc(&s->vf, (size_t)top.nNodes * C);
@@ -805,7 +805,7 @@ gf_status alloc_readout(gf_smp *s, int nMol) {
 
 }  // namespace
 
-// gf_smp_prepare of a first-order handle (SMP_theta): the host builds the batch and the level's own (node, child) tables
+// gf_smp_prepare of a first-order handle (SMP_theta, SMP_1D*) or a steerable second-order one (SMP_2D, SMP_2D_ver4): the host builds the batch and the level's own (node, child) tables
 // (gfsmp::build_batch_theta); the device gets those, the activations, A / B and G -- none of the 18-slice or gamma buffers.
 gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature) {
     gf_ctx *ctx = s->ctx;
@@ -823,7 +823,7 @@ gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int
     const int L = cfg.nLevels;
     for (int l = 0; l <= L; ++l)
         if (s->lay.level[l].rows > 0x7fffffffll || (!s->lay.level[l].buckets.empty() && s->lay.level[l].buckets.back().s > 32767))
-            return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare: level %d is beyond the first-order level's int16 positions / 2^31 rows", l);
+            return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare: level %d is beyond the level's int16 positions / 2^31 rows", l);
     s->lv.assign(L + 1, gf_smp::DevLevel());
     Taker t = {s};
     for (int l = 0; l <= L; ++l) {
@@ -856,6 +856,16 @@ gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int
         t.put(&d.th_inv, h.th_inv);
         t.put(&d.th_bucket, h.th_bucket);
         t.put(&d.th_weight, h.th_weight);
+        if (cfg.steerable_2d) {   // SMP_2D / ver4 (smp_level_2d.hip): S [rows][Cp], col and the reverse sweep's column partials per (node, column)
+            const size_t cols = nodes ? (size_t)(h.node_pair.back() + h.node_s.back()) : 0;   // sum s
+            t.put(&d.node_pair, h.node_pair);
+            t.put(&d.adj, h.adj);
+            t.alloc(&d.th_A, (size_t)h.rows * Cp);
+            t.alloc(&d.th_B, cols * Cp);
+            t.alloc(&d.th_node, cols * (Cl + 3 * Cp));
+            t.alloc(&d.part2d, h.buckets.size() * 16 * (Cl + 3 * Cp));   // [buckets][kSplit2d row chunks][Cc + 3 Cp]
+            continue;
+        }
         t.alloc(&d.th_node, nodes * 3 * Cl);
         if (cfg.first_order >= 2) {   // SMP_1D*: A = S and B = sumS are Cp wide; a matrix, and so G / dG and the weight views, only in ver3
             t.alloc(&d.th_A, (size_t)h.rows * Cp);
@@ -914,7 +924,9 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
     for (int m = 0; m < nMol; ++m)
         if (nVertices[m] <= 0 || nVertices[m] > 4096) return fail(ctx, GF_ERR_INVALID, "molecule %d has %d vertices", m, nVertices[m]);
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (s->cfg.first_order) return gf::smp_theta_prepare(s, nMol, nVertices, adj, feature);   // (no reduced adjacency: coulomb is inert)
+    if (s->cfg.steerable_2d && coulomb)   // (SMP_2D / SMP_2D_ver4 have no use_coulomb constructor: their adjacency is the molecule's)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_coulomb: a steerable_2d handle (SMP_2D, SMP_2D_ver4) has no Coulomb adjacency");
+    if (s->cfg.per_size()) return gf::smp_theta_prepare(s, nMol, nVertices, adj, feature);   // (first order: no reduced adjacency, coulomb is inert)
     gf_status st = gf::choose_plan(s, nMol, nVertices, adj, coulomb);
     if (st != GF_OK) return st;
     const bool prep_timing = std::getenv("GF_PREP_TIMING") != nullptr;
@@ -966,6 +978,9 @@ gf_status gf_smp_prepare_molecule_host(const gf_smp_config *cfg, int V, const in
     if (!cfg || V <= 0 || !adj || !feature || !phi_out) return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: bad argument");
     if (cfg->first_order >= 2 && !gf::smp_1d_config_ok(cfg))   // (SMP_1D* have no cap: a capped field is not one of theirs)
         return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: first_order = %d needs max_receptive_field == max_nVertices", cfg->first_order);
+    if (cfg->steerable_2d && !gf::smp_2d_config_ok(cfg))
+        return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: steerable_2d = %d needs first_order = 0 and max_receptive_field == max_nVertices",
+                    cfg->steerable_2d);
     gfsmp::Config c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, cfg->has_WL_ordering};
     c.physics = cfg->physics ? 1 : 0;
     gfsmp::Molecule m;

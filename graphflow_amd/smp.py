@@ -12,7 +12,8 @@ from .ops import default_context
 class SMPConfig(C.Structure):
     _fields_ = [("nLevels", C.c_int), ("nChanels", C.c_int), ("nFeatures", C.c_int), ("nDepth", C.c_int),
                 ("max_receptive_field", C.c_int), ("has_WL_ordering", C.c_int), ("nContractions", C.c_int),
-                ("custom_matmul", C.c_int), ("physics", C.c_int), ("first_order", C.c_int), ("max_nVertices", C.c_int)]
+                ("custom_matmul", C.c_int), ("physics", C.c_int), ("first_order", C.c_int), ("max_nVertices", C.c_int),
+                ("steerable_2d", C.c_int)]
 
 
 class SMPOmega:
@@ -298,6 +299,58 @@ class SMP1D(SMPTheta):
         """f_level[v] of molecule `mol` after forward(): numpy [s, C_level]."""
         s = len(self.receptive_field(mol, level, v))
         out = np.empty((s, self.level_channels(level)), dtype=np.float32)
+        n = self.lib.gf_smp_read_activation(self.handle, mol, level, v, out.ctypes.data_as(C.c_void_p), out.size)
+        if n != out.size:
+            raise RuntimeError("gf_smp_read_activation(%d, %d, %d) returned %d" % (mol, level, v, n))
+        return out
+
+
+class SMP2D(SMP1D):
+    """Batched SMP_2D (form "2d") and SMP_2D_ver4 (form "ver4") of GraphFlow/SMP_2D.h, SMP_2D_ver4.h, and with n_class >= 2 their
+    classifiers (SMP_2D_classification, SMP_2D_ver4_classification): the second-order steerable models, gf_smp_config.steerable_2d.
+    f_l[v] is [s, s, C_l]; with S = the children's tensors summed on the positions of phi_l(v) plus scalar_l * adj_v, col = its column sums:
+      "2d":   z = lambda1_s S + lambda2_s col + b_s, C channels at every level;
+      "ver4": z = [lambda1_s S | lambda2_s col] + b_s, the channels double per level (C << l).
+    Parameters in registration order: H[C, F(D+1)]; for l = 1..L: (lambda1_s[C_{l-1}], lambda2_s[C_{l-1}], b_s[C_l]) for
+    s = 1..max_nVertices, then scalar_l[C_{l-1}]; W[C_L], or W[n_class, C_L] for a classifier.  The optimiser is Momentum: step().
+    A classifier's forward(params, labels) returns (arg-max label, log p[label], graph_feature); scores() the logits and probabilities."""
+
+    FORMS = {"2d": 1, "ver4": 2}
+
+    def __init__(self, form, max_nVertices, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering=True, n_class=0, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.form, self.nClass = form, int(n_class)
+        self.cfg = self.config(form, max_nVertices, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering)
+        h = C.c_void_p()
+        if self.nClass:
+            self.ctx.check(self.lib.gf_smp_create_classifier(self.ctx.handle, C.byref(self.cfg), self.nClass, C.byref(h)))
+        else:
+            self.ctx.check(self.lib.gf_smp_create(self.ctx.handle, C.byref(self.cfg), C.byref(h)))
+        self.handle = h
+        self.n_params = self.lib.gf_smp_param_count(h)
+        self.n_mol = 0
+
+    @staticmethod
+    def config(form, max_nVertices, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering=True):
+        if form not in SMP2D.FORMS:
+            raise ValueError("SMP2D: form %r (\"2d\": SMP_2D, \"ver4\": SMP_2D_ver4)" % (form,))
+        return SMPConfig(nLevels, nChanels, nFeatures, nDepth, max_nVertices, 1 if has_WL_ordering else 0, 0, 0, 0, 0, max_nVertices,
+                         SMP2D.FORMS[form])
+
+    def level_channels(self, level):
+        return self.cfg.nChanels if self.form == "2d" else self.cfg.nChanels << level
+
+    def scores(self):
+        """(scores, probability) of a classifier's last forward, [nMol, n_class] each."""
+        if not self.nClass:
+            raise TypeError("SMP2D.scores: not a classifier (n_class = 0)")
+        return SMPClassifier.scores(self)
+
+    def activation(self, mol, level, v):
+        """f_level[v] of molecule `mol` after forward(): numpy [s, s, C_level]."""
+        s = len(self.receptive_field(mol, level, v))
+        out = np.empty((s, s, self.level_channels(level)), dtype=np.float32)
         n = self.lib.gf_smp_read_activation(self.handle, mol, level, v, out.ctypes.data_as(C.c_void_p), out.size)
         if n != out.size:
             raise RuntimeError("gf_smp_read_activation(%d, %d, %d) returned %d" % (mol, level, v, n))

@@ -291,6 +291,28 @@ typedef struct {
      * SMP_1D_ver3_classification; 3 gives the same read-out on SMP_1D_ver2): W [nClass][C_L].  Still refused with GF_ERR_UNSUPPORTED:
      * gf_smp_set_grad_allreduce(smp, 1) and gf_smp_dropout_masks.  gf_smp_model_create has no towers of these forms. */
     int first_order, max_nVertices;
+    /* 1: SMP_2D, 2: SMP_2D_ver4 (GraphFlow/SMP_2D.h, SMP_2D_ver4.h) -- the second-order STEERABLE models: no contraction and no matrix
+     * product.  f_l[v] is [s][s][C_l] on the field phi_l(v) = the union of the level-below fields of the vertices within one hop (no cap, WL
+     * ordering).  Level 0 is MatMul(H, feature) as [1][1][C]; for l >= 1, with pi_w the position map of a child w (hop distance <= 1):
+     *   S[i][j]   = sum_w f_{l-1}[w][pi_w(i)][pi_w(j)] + scalar_l * adj_v[i][j]         (terms with a missing position are zero)
+     *   col[j]    = sum_k S[k][j]
+     *   1  SMP_2D       z[i][j] = lambda1_s S[i][j] + lambda2_s col[j] + b_s              C_l = C
+     *   2  SMP_2D_ver4  z[i][j] = [lambda1_s S[i][j] | lambda2_s col[j]] + b_s            C_l = C << l
+     *   f_l[v] = LeakyReLU3D(z), slope 0.01 at every level
+     * per CHANNEL: lambda1_s, lambda2_s, scalar_l are [C_{l-1}], b_s is [C_l].  adj_v is the adjacency reduced to phi_l(v); in SMP_2D_ver4
+     * its diagonal is 1 and every row is divided by its sum.  Read-out: sum over (i, j), LeakyReLU, sum over the vertices; InnerProduct with
+     * W [C_L] and squared loss, or with gf_smp_create_classifier MatVecMul with W [nClass][C_L] and LogLoss (SMP_2D_classification,
+     * SMP_2D_ver4_classification).  Parameter order (registration order): H [C][F (D + 1)]; for l = 1..L: for size = 1 .. max_nVertices
+     * (lambda1, lambda2, b), then scalar_l; W.  gf_smp_feature_width is C_L.  Required, else GF_ERR_INVALID: first_order == 0,
+     * max_receptive_field == max_nVertices <= 4096, nContractions = custom_matmul = physics = 0 (gf_smp_config_param_count then answers 0).
+     * The gradients of lambda1_s / lambda2_s are the CLASSES', not the derivative (see first_order): the j-th vertex of a size in a
+     * molecule counts j (j + 1) / 2 times in SMP_2D (two shared ops in a row) and j times in SMP_2D_ver4; every other gradient is plain.
+     * The optimiser of the classes is Momentum: gf_smp_momentum_step.  gf_smp_read_activation returns [s][s][C_l],
+     * gf_smp_read_reduced_adjacency the class's adj_v, gf_smp_level_sizes rows = sum of s^2.  The level is smp_level_2d.hip: no GEMM, no
+     * atomics.  Refused with GF_ERR_UNSUPPORTED before anything is launched: gf_smp_set_grad_allreduce(smp, 1), gf_smp_dropout_masks,
+     * gf_smp_backward_features, gf_smp_prepare_coulomb with a Coulomb matrix (the classes have no such constructor).  gf_smp_model_create
+     * has no towers of these forms.  0 (a zero-initialised tail): everything as described above. */
+    int steerable_2d;
 } gf_smp_config;
 gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out);
 /* gf_smp_param_count of the handle gf_smp_create would build from cfg (0 on a configuration it would refuse).  Host only. */
