@@ -507,6 +507,7 @@ gf_status smp_contract(gf_smp *s, int l, bool backward) {
 }  // namespace
 
 LevelKind smp_level_kind(const gf_smp *s, int l) {
+    if (s->cfg.unrestricted) return LevelKind::Unrestricted;
     if (s->cfg.first_order) return LevelKind::Theta;   // (one plan: gf_smp_set_fused has no effect)
     if (s->cfg.steerable_2d) return LevelKind::Steerable2D;
     if (s->fused && smp_fused_supported(s, l)) return LevelKind::Fused18;
@@ -637,7 +638,21 @@ gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channel
     s->cfg.custom_matmul = cfg->custom_matmul ? 1 : 0;
     s->cfg.physics = cfg->physics ? 1 : 0;
     s->cfg.nClass = nClass;
-    if (cfg->steerable_2d) {   // SMP_2D, SMP_2D_ver4 (smp_level_2d.hip); a classifier read-out is allowed
+    if (cfg->unrestricted) {   // Unrestricted_SMP_1D, _1D_ver2, _2D (smp_level_unrestricted.hip)
+        if (!gf::smp_unrestricted_config_ok(cfg)) {
+            delete s;
+            return fail(ctx, GF_ERR_INVALID, "gf_smp_create: unrestricted = %d (1: Unrestricted_SMP_1D, 2: _1D_ver2, 3: _2D) needs first_order = "
+                                             "steerable_2d = 0, max_receptive_field (%d) == max_nVertices (%d) <= 4096, nContractions = custom_matmul = "
+                                             "physics = 0 and a parameter count that fits an int", cfg->unrestricted, cfg->max_receptive_field,
+                        cfg->max_nVertices);
+        }
+        if (nClass) {
+            delete s;
+            return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: the Unrestricted_SMP_* models have no `_classification` class");
+        }
+        gf::smp_unrestricted_config(cfg, &s->cfg);
+        s->grad_allreduce = 0;   // (no data-parallel exchange: gf_smp_set_grad_allreduce(.., 1) is refused)
+    } else if (cfg->steerable_2d) {   // SMP_2D, SMP_2D_ver4 (smp_level_2d.hip); a classifier read-out is allowed
         if (!gf::smp_2d_config_ok(cfg)) {
             delete s;
             return fail(ctx, GF_ERR_INVALID, "gf_smp_create: steerable_2d = %d (1: SMP_2D, 2: SMP_2D_ver4) needs first_order = 0, max_receptive_field (%d) "
@@ -757,6 +772,8 @@ gf_status gf_smp_create_classifier(gf_ctx *ctx, const gf_smp_config *cfg, int nC
     if (!cfg || !out) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: null argument");
     if (cfg->first_order == 1)   // (SMP_theta has no `_classification` class; first_order = 2, 3, 4 do: SMP_1D*_classification)
         return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: a first-order model (first_order = 1) has no classifier read-out");
+    if (cfg->unrestricted)   // (refused before the configuration is looked at: there is no class to hold the handle to)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: the Unrestricted_SMP_* models have no `_classification` class");
     if (cfg->physics) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: a physics tower has no read-out of its own (physics = 0)");
     if (nClass < 2) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: nClass = %d (at least 2)", nClass);
     return gf::smp_create(ctx, cfg, /*pad_channels=*/true, out, /*min_pad=*/0, nClass);
@@ -891,6 +908,7 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
             st = s->cfg.first_order >= 2 ? smp_1d_forward_level(s, l, K[l], b[l]) : smp_theta_forward_level(s, l, K[l], b[l]);
             break;
         case LevelKind::Steerable2D: st = smp_2d_forward_level(s, l, K[l], b[l]); break;   // (K[l]: scalar_l, b[l]: the per-size block)
+        case LevelKind::Unrestricted: st = smp_unrestricted_forward_level(s, l, K[l], b[l]); break;   // (the same two)
         case LevelKind::OpByOp: st = forward_level_opbyop(s, l, K[l], b[l]); break;
         }
         if (st == GF_OK && l < L) st = dup_level(s, l);
@@ -1017,7 +1035,7 @@ gf_status backward_level_opbyop(gf_smp *s, int l, const float *Kl, float *dKl) {
 // df_{l-1} from what level l left: the fused level's folded consumer gather, else the consumer-list gather of dP (a fused level's D_bb /
 // D_ac gradients arrive through dFdc beside it); the gamma level has written df_{l-1} itself
 gf_status send_df_down(gf_smp *s, int l, LevelKind kind) {
-    if (kind == LevelKind::Gamma || kind == LevelKind::Theta || kind == LevelKind::Steerable2D) return GF_OK;
+    if (kind == LevelKind::Gamma || kind == LevelKind::Theta || kind == LevelKind::Steerable2D || kind == LevelKind::Unrestricted) return GF_OK;
     const bool fused = kind == LevelKind::Fused18;
     if (fused && smp_fused_gather_enabled(s, l)) return smp_fused_gather_backward(s, l);
     const gf_smp::DevLevel &d = s->lv[l], &pv = s->lv[l - 1];
@@ -1087,7 +1105,8 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
     // the read-out's gradient into the top level: a fused level reads it as one vector per node, the others at every (i, j)
     const gfsmp::LevelLayout &top = B.level[L];
     // (a first-order level takes the read-out's gradient the same way: one vector per node, added inside its per-node kernel)
-    const bool top_fused = !dfeat && (kind[L] == LevelKind::Fused18 || kind[L] == LevelKind::Theta || kind[L] == LevelKind::Steerable2D);
+    const bool top_fused = !dfeat && (kind[L] == LevelKind::Fused18 || kind[L] == LevelKind::Theta || kind[L] == LevelKind::Steerable2D ||
+                                      kind[L] == LevelKind::Unrestricted);
     const bool classes = !dfeat && s->cfg.nClass;   // (a classifier: dg [nMol][C] goes down instead of dy[mol] * W)
     if (!dfeat && !classes) GF_LAUNCH(ctx, "smp_readout_dW", readout_dW, dim3(1), dim3(1024), 0, s->dy, s->g, dW, C, B.nMol);
     if (dfeat) {
@@ -1107,8 +1126,8 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
     for (int l = L; l >= 1; --l) {
         if (l < L) st = fold_level(s, l);   // (SMP_2D_ver6 on the 18-slice level: the gradient of the transposed copies joins the matrices')
         if (st != GF_OK) return st;
-        if (kind[l] != LevelKind::Fused18 && kind[l] != LevelKind::Theta && kind[l] != LevelKind::Steerable2D)
-            s->bwd_consumed = true;   // (a first-order or steerable level keeps f, A, B: repeatable)
+        if (kind[l] != LevelKind::Fused18 && kind[l] != LevelKind::Theta && kind[l] != LevelKind::Steerable2D && kind[l] != LevelKind::Unrestricted)
+            s->bwd_consumed = true;   // (a first-order, steerable or unrestricted level keeps f, A, B: repeatable)
         switch (kind[l]) {
         case LevelKind::Fused18:
             if (dfeat) st = feature_nodevec(s, dfeat, l);
@@ -1132,6 +1151,9 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
             break;
         case LevelKind::Steerable2D:   // dz, dS in place, the per-size gradients and dscalar_l, df_{l-1} gathered from dS (never a tower)
             st = smp_2d_backward_level(s, l, K[l], b[l], dK[l], db[l], l == L ? s->dsh : nullptr, /*rows_too=*/l < L);
+            break;
+        case LevelKind::Unrestricted:   // dz in place, dS beside it, the per-size gradients (and dscalar_l), df_{l-1} gathered from dS (never a tower)
+            st = smp_unrestricted_backward_level(s, l, b[l], dK[l], db[l], l == L ? s->dsh : nullptr, /*rows_too=*/l < L);
             break;
         }
         if (st == GF_OK) st = send_df_down(s, l, kind[l]);
@@ -1247,8 +1269,8 @@ gf_status gf_smp_backward(gf_smp *s, const float *params, float *grads, int accu
 
 gf_status gf_smp_backward_features(gf_smp *s, const float *params, float *grads, const float *d_feature, int accumulate) {
     if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
-    if (s->cfg.steerable_2d)
-        return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_backward_features: a steerable_2d handle (SMP_2D, SMP_2D_ver4) is no tower");
+    if (s->cfg.steerable_2d || s->cfg.unrestricted)
+        return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_backward_features: a steerable_2d or unrestricted handle is no tower");
     if (!d_feature) return fail(s->ctx, GF_ERR_INVALID, "gf_smp_backward_features: null feature gradient");
     gf_status st = gf::backward_check(s, &params, &grads, accumulate, d_feature);
     return st == GF_OK ? gf::backward_run(s, params, grads, accumulate, d_feature) : st;

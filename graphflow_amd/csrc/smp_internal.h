@@ -121,6 +121,29 @@ inline bool smp_2d_config_ok(const gf_smp_config *cfg) {
     if (cfg->max_nVertices > 4096) return false;   // (th_weight <= 4096 * 4097 / 2; gf_smp_prepare takes no larger molecule)
     return cfg->steerable_2d == 1 || (cfg->nLevels <= 16 && ((long long)cfg->nChanels << cfg->nLevels) <= (1 << 20));   // (C_l = C << l)
 }
+// what unrestricted = 1, 2, 3 (Unrestricted_SMP_1D, _1D_ver2, _2D) asks: first_order = steerable_2d = 0, no cap, no contraction family /
+// custom product / tower, channel counts and a parameter count that fit an int
+inline bool smp_unrestricted_config_ok(const gf_smp_config *cfg) {
+    if (cfg->unrestricted < 1 || cfg->unrestricted > 3 || cfg->first_order || cfg->steerable_2d) return false;
+    if (cfg->nContractions || cfg->custom_matmul || cfg->physics || cfg->max_nVertices != cfg->max_receptive_field) return false;
+    if (cfg->max_nVertices > 4096 || cfg->nLevels > 16 || ((long long)cfg->nChanels << cfg->nLevels) > (1 << 20)) return false;
+    const long long m = cfg->max_nVertices, sq = m * (m + 1) * (2 * m + 1) / 6;   // sum of s^2
+    long long n = (long long)cfg->nChanels * cfg->nFeatures * (cfg->nDepth + 1), Cl = cfg->nChanels;
+    for (int l = 1; l <= cfg->nLevels; ++l) {
+        const long long Cp = Cl;
+        if (cfg->unrestricted == 2) Cl *= 2;
+        n += (cfg->unrestricted == 3 ? Cp : cfg->unrestricted) * sq + m * Cl + (cfg->unrestricted == 3 ? Cp : 0);
+    }
+    return n + Cl <= 0x7fffffffll;
+}
+// the restricted sibling whose rows, tables and read-out an unrestricted form sits on (gfsmp::Config::unrestricted)
+inline void smp_unrestricted_config(const gf_smp_config *cfg, gfsmp::Config *c) {
+    c->unrestricted = cfg->unrestricted;
+    c->first_order = cfg->unrestricted == 1 ? 2 : cfg->unrestricted == 2 ? 3 : 0;
+    c->steerable_2d = cfg->unrestricted == 3 ? 1 : 0;
+    c->max_nVertices = cfg->max_nVertices;
+    c->nContractions = c->first_order ? 2 : 0;
+}
 void smp_derive_plan(gf_smp *s, bool allow_embed);
 gf_status smp_switch_plan(gf_smp *s, bool embed);
 constexpr int kPadMaxLevels = 15;   // levels a padded model's layout map holds (gf_smp_create: deeper models compute at nChanels)
@@ -245,6 +268,9 @@ struct gf_smp {
         // steerable second-order level (smp_level_2d.hip): th_A = S [rows][Cp], th_B = col [sum s][Cp], th_node = [sum s][Cc + 3 Cp] column
         // partials of the reverse sweep, adj / node_pair as in gfsmp::LevelLayout, part2d = [blocks][Cp] partial sums of dscalar
         float *part2d = nullptr;
+        // unrestricted level (smp_level_unrestricted.hip): th_A = S [rows][Cp], Q = dS [rows][Cp], part2d = the chunk partials of the
+        // per-size entries at un_part_off (gfsmp::LevelLayout), th_node = [sum s][2 Cp] column partials (db | dscalar) in form 3
+        long long *un_part_off = nullptr;
     };
     std::vector<DevLevel> lv;
     // device-built level tables: the batch's adjacency matrices and the per-level statistics the kernels leave behind
@@ -306,7 +332,7 @@ constexpr int kFusedMaxField = 64;
 // What runs level l >= 1 of a pass: the fused 18-slice level (smp_fused.hip) where gf_smp_set_fused allows and smp_fused_supported takes the
 // shape, else the SMP_gamma level where smp_gamma_fused does, else the op-by-op pipeline (smp.hip); nobody else asks the two predicates.
 // Constant for the length of a pass, NOT between passes (gf_smp_set_fused, gf_smp_dropout_masks): a sweep asks at its start, keeps nothing.
-enum class LevelKind { OpByOp, Fused18, Gamma, Theta, Steerable2D };   // Theta: every level of a first-order handle (cfg.first_order), Steerable2D: of a cfg.steerable_2d one, nothing else
+enum class LevelKind { OpByOp, Fused18, Gamma, Theta, Steerable2D, Unrestricted };   // Theta: every level of a first-order handle (cfg.first_order), Steerable2D: of a cfg.steerable_2d one, Unrestricted: of a cfg.unrestricted one (asked first), nothing else
 LevelKind smp_level_kind(const gf_smp *s, int l);
 bool smp_fused_supported(const gf_smp *s, int l);
 gf_status smp_backward_admissible(const gf_smp *s);   // smp.hip: refusals of a reverse sweep that must come before any work is issued
@@ -342,6 +368,11 @@ gf_status smp_1d_backward_level(gf_smp *s, int l, const float *Kl, const float *
 gf_status smp_2d_forward_level(gf_smp *s, int l, const float *scalar, const float *sizes);
 gf_status smp_2d_backward_level(gf_smp *s, int l, const float *scalar, const float *sizes, float *dscalar, float *dsizes, const float *node_df,
                                 bool rows_too);
+// The levels of Unrestricted_SMP_1D, _1D_ver2 and _2D (cfg.unrestricted = 1, 2, 3; smp_level_unrestricted.hip) on the same tables: sizes =
+// the level's per-size block (filter_s, b_s[Cc]) x max_nVertices, scalar = scalar_l[Cp] (form 3, else unused).  No GEMM.  backward:
+// node_df / rows_too as above; dS is left in d.Q.
+gf_status smp_unrestricted_forward_level(gf_smp *s, int l, const float *scalar, const float *sizes);
+gf_status smp_unrestricted_backward_level(gf_smp *s, int l, const float *sizes, float *dscalar, float *dsizes, const float *node_df, bool rows_too);
 // the first-order read-out of level l: sh[n] = column sums over the node's s rows (ShrinkMatrix), vf = LeakyReLU(sh); and its reverse,
 // df_l[n][i][:] (+)= dvec[n][:] at every row i of the node, dvec = one gradient vector per node
 gf_status smp_theta_readout(gf_smp *s, int l, float *sh, float *vf);

@@ -195,7 +195,10 @@ static bool host_config(const gf_smp_config *cfg, int nClass, gfsmp::Config *out
     c.custom_matmul = cfg->custom_matmul ? 1 : 0;
     c.physics = cfg->physics ? 1 : 0;
     c.nClass = nClass;
-    if (cfg->steerable_2d) {   // SMP_2D, SMP_2D_ver4 (gf_smp_config.steerable_2d; a classifier read-out is allowed)
+    if (cfg->unrestricted) {   // Unrestricted_SMP_1D, _1D_ver2, _2D (gf_smp_config.unrestricted; no classifier)
+        if (nClass || !gf::smp_unrestricted_config_ok(cfg)) return false;
+        gf::smp_unrestricted_config(cfg, &c);
+    } else if (cfg->steerable_2d) {   // SMP_2D, SMP_2D_ver4 (gf_smp_config.steerable_2d; a classifier read-out is allowed)
         if (!gf::smp_2d_config_ok(cfg)) return false;
         c.steerable_2d = cfg->steerable_2d;
         c.max_nVertices = cfg->max_nVertices;
@@ -221,13 +224,20 @@ static gf_status uniform_init_host(const gf_smp_config *cfg, int nClass, float *
     std::vector<size_t> sizes;
     sizes.push_back(C * c.fdim());
     for (int l = 1; l <= c.nLevels; ++l) {
-        if (c.first_order)   // lambda1[size], lambda2[size], b[size] for size = 1 .. max_nVertices, then K_l (SMP_theta.h:254-264)
+        if (c.unrestricted)   // W[size] (W1[size], W2[size]), b[size]: every one a block of its own, uniform_init(Vector*) divides by 10 x its
+            for (int size = 1; size <= c.max_nVertices; ++size) {   // size (Unrestricted_SMP_1D.h:168-171, _2D.h:189-193)
+                const size_t w = (size_t)size * size * (c.unrestricted == 3 ? (size_t)c.level_channels(l - 1) : 1);
+                sizes.push_back(w);
+                if (c.unrestricted == 2) sizes.push_back(w);
+                sizes.push_back((size_t)c.level_channels(l));
+            }
+        else if (c.first_order)   // lambda1[size], lambda2[size], b[size] for size = 1 .. max_nVertices, then K_l (SMP_theta.h:254-264)
             for (int size = 1; size <= c.max_nVertices; ++size) {
                 sizes.push_back(1);
                 sizes.push_back(1);
                 sizes.push_back((size_t)c.level_channels(l));
             }
-        if (c.steerable_2d)   // lambda1[size], lambda2[size] [C_{l-1}], b[size] [C_l], then scalar_l below (SMP_2D.h:228-235)
+        if (c.steerable_2d && !c.unrestricted)   // lambda1[size], lambda2[size] [C_{l-1}], b[size] [C_l], then scalar_l below (SMP_2D.h:228-235)
             for (int size = 1; size <= c.max_nVertices; ++size) {
                 sizes.push_back((size_t)c.level_channels(l - 1));
                 sizes.push_back((size_t)c.level_channels(l - 1));
@@ -258,7 +268,7 @@ size_t gf_smp_config_param_count(const gf_smp_config *cfg) {
 }
 size_t gf_smp_classifier_config_param_count(const gf_smp_config *cfg, int nClass) {
     gfsmp::Config c;
-    if (!cfg || cfg->physics || cfg->first_order == 1 || nClass < 2) return 0;   // (what gf_smp_create_classifier refuses)
+    if (!cfg || cfg->physics || cfg->first_order == 1 || cfg->unrestricted || nClass < 2) return 0;   // (what gf_smp_create_classifier refuses)
     return host_config(cfg, nClass, &c) ? gf::param_count(c) : 0;
 }
 // ... of the `_classification` models (SMP_2D_ver6_classification.h:256-259): sgd->params holds Vector*, so W [nClass][C] is drawn by

@@ -673,6 +673,16 @@ void build_batch_theta(const Config &cfg, int nMol, const int *nVertices, const 
             lv.th_cons_ptr[(size_t)w + 1] = nc;
         }
         for (int w = 0; w < totalV; ++w) lv.th_cons_ptr[(size_t)w + 1] += lv.th_cons_ptr[(size_t)w];
+        lv.un_part_off.clear();
+        if (cfg.unrestricted) {
+            int64_t o = 0;
+            for (const Bucket &b : lv.buckets) {
+                lv.un_part_off.push_back(o);
+                o += (int64_t)kUnrestrictedSplit * ((int64_t)cfg.filter_floats(l) * b.s * b.s + cfg.level_channels(l) +
+                                                     (cfg.unrestricted == 3 ? cfg.level_channels(l - 1) : 0));
+            }
+            lv.un_part_off.push_back(o);
+        }
         lv.th_weight.assign((size_t)totalV, 0);
         for (int m = 0; m < nMol; ++m) {   // the j-th vertex of its size in the molecule, ascending v (see th_weight)
             const int V = nVertices[m], g0 = out->mol_first_vertex[m];
@@ -680,7 +690,7 @@ void build_batch_theta(const Config &cfg, int nMol, const int *nVertices, const 
                 const size_t sv = out->mols[m].phi[l][v].size();
                 int j = 1;
                 for (int u = 0; u < v; ++u) j += out->mols[m].phi[l][u].size() == sv;
-                lv.th_weight[(size_t)node_of[l][g0 + v]] = cfg.first_order == 2 ? (int)((long long)j * (j + 1) * (j + 2) / 6)   // (SMP_1D: see th_weight)
+                lv.th_weight[(size_t)node_of[l][g0 + v]] = cfg.unrestricted ? 1 : cfg.first_order == 2 ? (int)((long long)j * (j + 1) * (j + 2) / 6)   // (SMP_1D: see th_weight)
                                                            : cfg.steerable_2d == 1 ? (int)((long long)j * (j + 1) / 2) : j;   // (SMP_2D)
             }
         }

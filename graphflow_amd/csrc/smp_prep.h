@@ -36,6 +36,8 @@ struct TableAlloc {
 template <class T>
 using tvec = std::vector<T, TableAlloc<T> >;
 
+constexpr int kUnrestrictedSplit = 16;   // node chunks per size bucket in the reduction of a dense filter's gradient
+
 struct Config {
     int nLevels, nChanels, nFeatures, nDepth, max_receptive_field, has_WL_ordering;
     int nContractions = 18;  // contraction family of the levels: 18 (SMP_omega/beta, SMP_2D_ver8), 10 (ver6), 50 (ver7)
@@ -62,10 +64,22 @@ struct Config {
     // Per level: for size = 1 .. max_nVertices (lambda1_s[C_{l-1}], lambda2_s[C_{l-1}], b_s[C_l]), then scalar_l[C_{l-1}] (the "matrix
     // block").  1: z = lambda1 S + lambda2 col + b, C_l = C; 2: z = [lambda1 S | lambda2 col] + b, C_l = 2 C_{l-1}.  Slope 0.01 everywhere.
     int steerable_2d = 0;
+    // 1, 2, 3: Unrestricted_SMP_1D, Unrestricted_SMP_1D_ver2, Unrestricted_SMP_2D (GraphFlow/Unrestricted_SMP_*.h;
+    // gf_smp_config.unrestricted; smp_level_unrestricted.hip): SMP_1D, SMP_1D_ver2 and SMP_2D with a dense learned filter per field size
+    // in place of lambda1_s I + lambda2_s 1 1^T.  Everything but the level and its per-size block is the restricted sibling's, so the
+    // handle's Config ALSO carries the sibling's form -- first_order = 2 (form 1), 3 (form 2), steerable_2d = 1 (form 3) -- for the rows,
+    // tables, channel counts, slopes, read-out and scalar_l; gf_smp_config itself asks for first_order = steerable_2d = 0.
+    // Per level: for size = 1 .. max_nVertices (W_s [s][s] | W1_s, W2_s [s][s] | W_s [s][s][C], then b_s[C_l]); form 3: then scalar_l.
+    int unrestricted = 0;
+    size_t filter_floats(int l) const { return unrestricted == 3 ? (size_t)level_channels(l - 1) : (size_t)unrestricted; }   // per s^2
     bool per_size() const { return first_order || steerable_2d; }   // a handle on the th_* tables, per-size blocks in front of the matrix block
     bool concat() const { return first_order >= 3 || steerable_2d == 2; }   // C_l = 2 C_{l-1}
     float level_slope() const { return first_order >= 3 ? 0.f : 0.01f; }   // LeakyReLU2D / 3D of every level (the read-out's LeakyReLU stays at 0.01)
     size_t size_block(int l) const {
+        if (unrestricted) {   // sum over s of (filter_floats s^2 + C_l)
+            const size_t m = (size_t)max_nVertices;
+            return filter_floats(l) * (m * (m + 1) * (2 * m + 1) / 6) + m * (size_t)level_channels(l);
+        }
         if (steerable_2d) return (size_t)max_nVertices * (2 * (size_t)level_channels(l - 1) + (size_t)level_channels(l));
         return first_order ? (size_t)max_nVertices * (2 + (size_t)level_channels(l)) : (size_t)level_channels(l);
     }
@@ -179,7 +193,11 @@ struct LevelLayout {
     // running sum, th_weight[n] = j (j + 1) (j + 2) / 6.
     // SMP_2D (Config::steerable_2d == 1) has two: W[s] (SumTensor3D) and W_eye[s] / W_one[s] (VectorBroadcastMat), SMP_2D.h:558-573 --
     // th_weight[n] = j (j + 1) / 2; SMP_2D_ver4 hands W_eye[s] / W_one[s] to the vertex's TensorMul directly (SMP_2D_ver4.h:603-608): j.
+    // The Unrestricted_* classes (Config::unrestricted) register W_s / b_s once per graph, not per vertex: th_weight = 1, the plain derivative.
     tvec<int> th_weight;          // [nNodes]
+    // Config::unrestricted: un_part_off[b] = first float of bucket b's kUnrestrictedSplit chunk partials of its per-size entry (filter,
+    // b_s, and in form 3 scalar_l's share), [buckets + 1]: the entries grow with s^2, so the offsets are a table
+    tvec<int64_t> un_part_off;
     // steerable second-order levels (Config::steerable_2d): rows = sum s^2, node_row = first row of the node's [s][s][C] tensor, node_pair
     // = first of its s columns (sum of s before it), adj = the class's reduced adjacency of phi_l(v) ([rows]; SMP_2D_ver4: unit diagonal,
     // rows divided by their sums, SMP_2D_ver4.h:478-503); the th_* tables as above, pi / inv applied to both indices

@@ -856,6 +856,18 @@ gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int
         t.put(&d.th_inv, h.th_inv);
         t.put(&d.th_bucket, h.th_bucket);
         t.put(&d.th_weight, h.th_weight);
+        if (cfg.unrestricted) {   // (smp_level_unrestricted.hip) S and dS [rows][Cp], the chunk partials of the per-size entries; form 3: adj, columns
+            t.alloc(&d.th_A, (size_t)h.rows * Cp);
+            t.alloc(&d.Q, (size_t)h.rows * Cp);
+            t.put(&d.un_part_off, h.un_part_off);
+            t.alloc(&d.part2d, (size_t)h.un_part_off.back());
+            if (cfg.unrestricted == 3) {
+                t.put(&d.node_pair, h.node_pair);
+                t.put(&d.adj, h.adj);
+                t.alloc(&d.th_node, (nodes ? (size_t)(h.node_pair.back() + h.node_s.back()) : 0) * 2 * Cp);
+            }
+            continue;
+        }
         if (cfg.steerable_2d) {   // SMP_2D / ver4 (smp_level_2d.hip): S [rows][Cp], col and the reverse sweep's column partials per (node, column)
             const size_t cols = nodes ? (size_t)(h.node_pair.back() + h.node_s.back()) : 0;   // sum s
             t.put(&d.node_pair, h.node_pair);
@@ -924,8 +936,8 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
     for (int m = 0; m < nMol; ++m)
         if (nVertices[m] <= 0 || nVertices[m] > 4096) return fail(ctx, GF_ERR_INVALID, "molecule %d has %d vertices", m, nVertices[m]);
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (s->cfg.steerable_2d && coulomb)   // (SMP_2D / SMP_2D_ver4 have no use_coulomb constructor: their adjacency is the molecule's)
-        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_coulomb: a steerable_2d handle (SMP_2D, SMP_2D_ver4) has no Coulomb adjacency");
+    if ((s->cfg.steerable_2d || s->cfg.unrestricted) && coulomb)   // (these classes have no use_coulomb constructor: their adjacency is the molecule's)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_coulomb: a steerable_2d or unrestricted handle has no Coulomb adjacency");
     if (s->cfg.per_size()) return gf::smp_theta_prepare(s, nMol, nVertices, adj, feature);   // (first order: no reduced adjacency, coulomb is inert)
     gf_status st = gf::choose_plan(s, nMol, nVertices, adj, coulomb);
     if (st != GF_OK) return st;
@@ -981,6 +993,9 @@ gf_status gf_smp_prepare_molecule_host(const gf_smp_config *cfg, int V, const in
     if (cfg->steerable_2d && !gf::smp_2d_config_ok(cfg))
         return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: steerable_2d = %d needs first_order = 0 and max_receptive_field == max_nVertices",
                     cfg->steerable_2d);
+    if (cfg->unrestricted && !gf::smp_unrestricted_config_ok(cfg))
+        return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: unrestricted = %d needs first_order = steerable_2d = 0 and max_receptive_field "
+                                             "== max_nVertices", cfg->unrestricted);
     gfsmp::Config c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, cfg->has_WL_ordering};
     c.physics = cfg->physics ? 1 : 0;
     gfsmp::Molecule m;

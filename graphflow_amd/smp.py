@@ -13,7 +13,7 @@ class SMPConfig(C.Structure):
     _fields_ = [("nLevels", C.c_int), ("nChanels", C.c_int), ("nFeatures", C.c_int), ("nDepth", C.c_int),
                 ("max_receptive_field", C.c_int), ("has_WL_ordering", C.c_int), ("nContractions", C.c_int),
                 ("custom_matmul", C.c_int), ("physics", C.c_int), ("first_order", C.c_int), ("max_nVertices", C.c_int),
-                ("steerable_2d", C.c_int)]
+                ("steerable_2d", C.c_int), ("unrestricted", C.c_int)]
 
 
 class SMPOmega:
@@ -351,6 +351,52 @@ class SMP2D(SMP1D):
         """f_level[v] of molecule `mol` after forward(): numpy [s, s, C_level]."""
         s = len(self.receptive_field(mol, level, v))
         out = np.empty((s, s, self.level_channels(level)), dtype=np.float32)
+        n = self.lib.gf_smp_read_activation(self.handle, mol, level, v, out.ctypes.data_as(C.c_void_p), out.size)
+        if n != out.size:
+            raise RuntimeError("gf_smp_read_activation(%d, %d, %d) returned %d" % (mol, level, v, n))
+        return out
+
+
+class SMPUnrestricted(SMP1D):
+    """Batched Unrestricted_SMP_1D (form "1d"), Unrestricted_SMP_1D_ver2 ("1d_ver2") and Unrestricted_SMP_2D ("2d") of
+    GraphFlow/Unrestricted_SMP_*.h, gf_smp_config.unrestricted = 1, 2, 3: SMP_1D, SMP_1D_ver2 and SMP_2D with a dense learned filter per
+    field size s.  With S = the children's activations summed on the positions of phi_l(v) (form "2d": on both indices, plus scalar_l * adj_v):
+      "1d":      z[i, c] = sum_k W_s[i, k] S[k, c] + b_s[c], C channels at every level, LeakyReLU slope 0.01;
+      "1d_ver2": z[i] = [(W1_s S)[i] | (W2_s S)[i]] + b_s, the channels double per level (C << l), slope 0;
+      "2d":      z[i, j, c] = sum_k W_s[i, k, c] S[k, j, c] + b_s[c], f_l[v] is [s, s, C], slope 0.01.
+    Parameters in registration order: H[C, F(D+1)]; for l = 1..L: for s = 1..max_nVertices (W_s[s, s] | W1_s, W2_s[s, s] | W_s[s, s, C],
+    then b_s[C_l]), for "2d" then scalar_l[C]; W[C_L].  Every gradient is the plain derivative.  The optimiser is Momentum: step().
+    There are no classifiers of these forms."""
+
+    FORMS = {"1d": 1, "1d_ver2": 2, "2d": 3}
+
+    def __init__(self, form, max_nVertices, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering=True, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.form, self.nClass = form, 0
+        self.cfg = self.config(form, max_nVertices, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering)
+        h = C.c_void_p()
+        self.ctx.check(self.lib.gf_smp_create(self.ctx.handle, C.byref(self.cfg), C.byref(h)))
+        self.handle = h
+        self.n_params = self.lib.gf_smp_param_count(h)
+        self.n_mol = 0
+
+    @staticmethod
+    def config(form, max_nVertices, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering=True):
+        if form not in SMPUnrestricted.FORMS:
+            raise ValueError("SMPUnrestricted: form %r (\"1d\": Unrestricted_SMP_1D, \"1d_ver2\": Unrestricted_SMP_1D_ver2, \"2d\": "
+                             "Unrestricted_SMP_2D)" % (form,))
+        return SMPConfig(nLevels, nChanels, nFeatures, nDepth, max_nVertices, 1 if has_WL_ordering else 0, 0, 0, 0, 0, max_nVertices, 0,
+                         SMPUnrestricted.FORMS[form])
+
+    def level_channels(self, level):
+        return self.cfg.nChanels << level if self.form == "1d_ver2" else self.cfg.nChanels
+
+    def activation(self, mol, level, v):
+        """f_level[v] of molecule `mol` after forward(): numpy [s, C_level], or [s, s, C] for form "2d"."""
+        s = len(self.receptive_field(mol, level, v))
+        shape = (s, s, self.cfg.nChanels) if self.form == "2d" else (s, self.level_channels(level))
+        out = np.empty(shape, dtype=np.float32)
         n = self.lib.gf_smp_read_activation(self.handle, mol, level, v, out.ctypes.data_as(C.c_void_p), out.size)
         if n != out.size:
             raise RuntimeError("gf_smp_read_activation(%d, %d, %d) returned %d" % (mol, level, v, n))

@@ -313,6 +313,26 @@ typedef struct {
      * gf_smp_backward_features, gf_smp_prepare_coulomb with a Coulomb matrix (the classes have no such constructor).  gf_smp_model_create
      * has no towers of these forms.  0 (a zero-initialised tail): everything as described above. */
     int steerable_2d;
+    /* 1: Unrestricted_SMP_1D, 2: Unrestricted_SMP_1D_ver2, 3: Unrestricted_SMP_2D (GraphFlow/Unrestricted_SMP_*.h) -- SMP_1D, SMP_1D_ver2
+     * and SMP_2D with a DENSE learned filter per field size s in place of lambda1_s I + lambda2_s 1 1^T.  Fields, children, level 0, the
+     * read-out and the loss are the restricted model's (first_order = 2, 3; steerable_2d = 1).  With S the gather-sum over the children
+     * (form 3: on both indices, plus scalar_l * adj_v, adj_v the molecule's adjacency on the field as it stands) and Cp = C_{l-1}:
+     *   1  z[i][c]    = sum_k W_s[i][k] S[k][c] + b_s[c]                 C_l = C        LeakyReLU2D slope 0.01
+     *   2  z[i]       = [ (W1_s S)[i] | (W2_s S)[i] ] + b_s              C_l = C << l   slope 0, level 0 included (the read-out keeps 0.01)
+     *   3  z[i][j][c] = sum_k W_s[i][k][c] S[k][j][c] + b_s[c]           C_l = C        LeakyReLU3D slope 0.01
+     * Parameter order (registration order): H [C][F (D + 1)]; for l = 1..L: for size = 1 .. max_nVertices (1: W_s [s][s]; 2: W1_s, W2_s
+     * [s][s]; 3: W_s [s][s][C], the channel innermost; then b_s [C_l]), in form 3 then scalar_l [C]; W [C_L].  The entries grow with the
+     * size: entry s of a level starts fl (s - 1) s (2 s - 1) / 6 + (s - 1) C_l floats into its block, fl = 1, 2, C.  Required, else
+     * GF_ERR_INVALID: first_order == 0 and steerable_2d == 0, max_receptive_field == max_nVertices <= 4096, nContractions = custom_matmul
+     * = physics = 0, a parameter count that fits an int (gf_smp_config_param_count then answers 0).  The classes register W_s / b_s once
+     * per graph, not once per vertex: EVERY gradient is the plain derivative (unlike first_order / steerable_2d).  The optimiser of the
+     * classes is Momentum: gf_smp_momentum_step; gf_smp_uniform_init_host draws every W_s, b_s as a block of its own.
+     * gf_smp_read_activation returns [s][C_l] (1, 2) or [s][s][C] (3); gf_smp_read_reduced_adjacency answers -1 (1, 2) or adj_v (3);
+     * gf_smp_level_sizes rows = sum of s (1, 2) or of s^2 (3).  The level is smp_level_unrestricted.hip: no GEMM, no atomics.  Refused with
+     * GF_ERR_UNSUPPORTED before anything is launched: gf_smp_create_classifier (the reference has no such class), gf_smp_set_grad_allreduce
+     * (smp, 1), gf_smp_dropout_masks, gf_smp_backward_features, gf_smp_prepare_coulomb with a Coulomb matrix.  gf_smp_model_create has no
+     * towers of these forms.  0 (a zero-initialised tail): everything as described above. */
+    int unrestricted;
 } gf_smp_config;
 gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out);
 /* gf_smp_param_count of the handle gf_smp_create would build from cfg (0 on a configuration it would refuse).  Host only. */
