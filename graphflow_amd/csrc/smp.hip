@@ -652,12 +652,17 @@ gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channel
         }
         gf::smp_unrestricted_config(cfg, &s->cfg);
         s->grad_allreduce = 0;   // (no data-parallel exchange: gf_smp_set_grad_allreduce(.., 1) is refused)
-    } else if (cfg->steerable_2d) {   // SMP_2D, SMP_2D_ver4 (smp_level_2d.hip); a classifier read-out is allowed
+    } else if (cfg->steerable_2d) {   // SMP_2D, SMP_2D_ver4 (smp_level_2d.hip; a classifier read-out is allowed), SMP_2D_ver5 (smp_level_2d_ver5.hip)
         if (!gf::smp_2d_config_ok(cfg)) {
             delete s;
-            return fail(ctx, GF_ERR_INVALID, "gf_smp_create: steerable_2d = %d (1: SMP_2D, 2: SMP_2D_ver4) needs first_order = 0, max_receptive_field (%d) "
-                                             "== max_nVertices (%d) <= 4096 and nContractions = custom_matmul = physics = 0", cfg->steerable_2d,
-                        cfg->max_receptive_field, cfg->max_nVertices);
+            return fail(ctx, GF_ERR_INVALID, "gf_smp_create: steerable_2d = %d (1: SMP_2D, 2: SMP_2D_ver4, 5: SMP_2D_ver5) needs first_order = 0, "
+                                             "max_receptive_field (%d) == max_nVertices (%d) <= 4096, nContractions = custom_matmul = physics = 0 and, "
+                                             "for 5, nChanels (%d) <= 128", cfg->steerable_2d, cfg->max_receptive_field, cfg->max_nVertices,
+                        cfg->nChanels);
+        }
+        if (nClass && cfg->steerable_2d == 5) {
+            delete s;
+            return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: SMP_2D_ver5 has no `_classification` class");
         }
         s->cfg.steerable_2d = cfg->steerable_2d;
         s->cfg.max_nVertices = cfg->max_nVertices;
@@ -907,7 +912,9 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
         case LevelKind::Theta:   // the same shape of level, first order (b[l]: the per-size block); SMP_1D*: no [2 C'][C] matrix
             st = s->cfg.first_order >= 2 ? smp_1d_forward_level(s, l, K[l], b[l]) : smp_theta_forward_level(s, l, K[l], b[l]);
             break;
-        case LevelKind::Steerable2D: st = smp_2d_forward_level(s, l, K[l], b[l]); break;   // (K[l]: scalar_l, b[l]: the per-size block)
+        case LevelKind::Steerable2D:   // (K[l]: scalar_l -- SMP_2D_ver5: K_l then scalar_l --, b[l]: the per-size block)
+            st = s->cfg.steerable_2d == 5 ? smp_2d_ver5_forward_level(s, l, K[l], b[l]) : smp_2d_forward_level(s, l, K[l], b[l]);
+            break;
         case LevelKind::Unrestricted: st = smp_unrestricted_forward_level(s, l, K[l], b[l]); break;   // (the same two)
         case LevelKind::OpByOp: st = forward_level_opbyop(s, l, K[l], b[l]); break;
         }
@@ -1150,7 +1157,8 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
                     s, l, K[l], b[l], dK[l], db[l], dfeat ? s->lv[l].dshl : l == L ? s->dsh : nullptr, /*rows_too=*/l < L, smp_dp_level_done);
             break;
         case LevelKind::Steerable2D:   // dz, dS in place, the per-size gradients and dscalar_l, df_{l-1} gathered from dS (never a tower)
-            st = smp_2d_backward_level(s, l, K[l], b[l], dK[l], db[l], l == L ? s->dsh : nullptr, /*rows_too=*/l < L);
+            st = (s->cfg.steerable_2d == 5 ? smp_2d_ver5_backward_level : smp_2d_backward_level)(s, l, K[l], b[l], dK[l], db[l],
+                                                                                                    l == L ? s->dsh : nullptr, /*rows_too=*/l < L);
             break;
         case LevelKind::Unrestricted:   // dz in place, dS beside it, the per-size gradients (and dscalar_l), df_{l-1} gathered from dS (never a tower)
             st = smp_unrestricted_backward_level(s, l, b[l], dK[l], db[l], l == L ? s->dsh : nullptr, /*rows_too=*/l < L);

@@ -113,13 +113,14 @@ inline bool smp_1d_config_ok(const gf_smp_config *cfg) {
     if (cfg->first_order == 2) return cfg->max_nVertices <= 2000;   // (th_weight = j (j + 1) (j + 2) / 6, j <= max_nVertices)
     return cfg->nLevels <= 16 && ((long long)cfg->nChanels << cfg->nLevels) <= (1 << 20);   // (C_l = C << l)
 }
-// what steerable_2d = 1, 2 (SMP_2D, SMP_2D_ver4) asks: first_order = 0, no cap, no contraction family / custom product / tower, a
-// multiplicity j (j + 1) / 2 (j <= max_nVertices) and channel counts that fit an int
+// what steerable_2d = 1, 2, 5 (SMP_2D, SMP_2D_ver4, SMP_2D_ver5; there is no 3 or 4) asks: first_order = 0, no cap, no contraction family /
+// custom product / tower, a multiplicity j (j + 1) / 2 (j <= max_nVertices) and channel counts that fit an int; 5: K1 [C][C] fits in LDS
 inline bool smp_2d_config_ok(const gf_smp_config *cfg) {
-    if (cfg->steerable_2d < 1 || cfg->steerable_2d > 2 || cfg->first_order) return false;
+    if ((cfg->steerable_2d != 1 && cfg->steerable_2d != 2 && cfg->steerable_2d != 5) || cfg->first_order) return false;
+    if (cfg->steerable_2d == 5 && cfg->nChanels > 128) return false;
     if (cfg->nContractions || cfg->custom_matmul || cfg->physics || cfg->max_nVertices != cfg->max_receptive_field) return false;
     if (cfg->max_nVertices > 4096) return false;   // (th_weight <= 4096 * 4097 / 2; gf_smp_prepare takes no larger molecule)
-    return cfg->steerable_2d == 1 || (cfg->nLevels <= 16 && ((long long)cfg->nChanels << cfg->nLevels) <= (1 << 20));   // (C_l = C << l)
+    return cfg->steerable_2d != 2 || (cfg->nLevels <= 16 && ((long long)cfg->nChanels << cfg->nLevels) <= (1 << 20));   // (C_l = C << l)
 }
 // what unrestricted = 1, 2, 3 (Unrestricted_SMP_1D, _1D_ver2, _2D) asks: first_order = steerable_2d = 0, no cap, no contraction family /
 // custom product / tower, channel counts and a parameter count that fit an int
@@ -268,6 +269,11 @@ struct gf_smp {
         // steerable second-order level (smp_level_2d.hip): th_A = S [rows][Cp], th_B = col [sum s][Cp], th_node = [sum s][Cc + 3 Cp] column
         // partials of the reverse sweep, adj / node_pair as in gfsmp::LevelLayout, part2d = [blocks][Cp] partial sums of dscalar
         float *part2d = nullptr;
+        // SMP_2D_ver5 (smp_level_2d_ver5.hip) beside them: row -> (column, s) and column -> s (written by its forward gather), u and dO
+        // [sum s][C], dE in Q [rows][C], the chunk partials of dK_l [smp_2d_ver5_wgrad_chunks][C][C]
+        int2 *v5_row_cs = nullptr;
+        int *v5_col_s = nullptr;
+        float *v5_u = nullptr, *v5_dO = nullptr, *v5_dKpart = nullptr;
         // unrestricted level (smp_level_unrestricted.hip): th_A = S [rows][Cp], Q = dS [rows][Cp], part2d = the chunk partials of the
         // per-size entries at un_part_off (gfsmp::LevelLayout), th_node = [sum s][2 Cp] column partials (db | dscalar) in form 3
         long long *un_part_off = nullptr;
@@ -368,6 +374,15 @@ gf_status smp_1d_backward_level(gf_smp *s, int l, const float *Kl, const float *
 gf_status smp_2d_forward_level(gf_smp *s, int l, const float *scalar, const float *sizes);
 gf_status smp_2d_backward_level(gf_smp *s, int l, const float *scalar, const float *sizes, float *dscalar, float *dsizes, const float *node_df,
                                 bool rows_too);
+// ... its last two steps, shared with SMP_2D_ver5: the column partials in d.th_node over the size buckets into dsizes and dscalar; df_{l-1}
+gf_status smp_2d_size_grads(gf_smp *s, int l, float *dscalar, float *dsizes);
+gf_status smp_2d_gather_down(gf_smp *s, int l);
+// The level of SMP_2D_ver5 (cfg.steerable_2d = 5; smp_level_2d_ver5.hip): Kl = K_l [C][2 C] then scalar_l[C], sizes as above with Cp = Cc = C.
+// Two small products on the columns and one MFMA row projection per direction, dK_l as chunked MFMA reductions; node_df / rows_too as above.
+gf_status smp_2d_ver5_forward_level(gf_smp *s, int l, const float *Kl, const float *sizes);
+gf_status smp_2d_ver5_backward_level(gf_smp *s, int l, const float *Kl, const float *sizes, float *dKl, float *dsizes, const float *node_df,
+                                     bool rows_too);
+size_t smp_2d_ver5_wgrad_chunks(long long rows, long long cols);   // partial images of dK_l a level of that many rows and columns writes
 // The levels of Unrestricted_SMP_1D, _1D_ver2 and _2D (cfg.unrestricted = 1, 2, 3; smp_level_unrestricted.hip) on the same tables: sizes =
 // the level's per-size block (filter_s, b_s[Cc]) x max_nVertices, scalar = scalar_l[Cp] (form 3, else unused).  No GEMM.  backward:
 // node_df / rows_too as above; dS is left in d.Q.
@@ -410,7 +425,7 @@ void view_params(const gfsmp::Config &c, P *base, P **H, std::vector<P *> *K, st
             p += c.size_block(l);
         }
         (*K)[l] = p;
-        p += c.weight_block(l);   // (SMP_1D / ver2: empty, K[l] is never read; ver3: K_eye then K_one = [2 C_{l-1}][C_{l-1}]; SMP_2D / ver4: scalar_l)
+        p += c.weight_block(l);   // (SMP_1D / ver2: empty, K[l] is never read; ver3: K_eye then K_one = [2 C_{l-1}][C_{l-1}]; SMP_2D / ver4: scalar_l; ver5: K_l [C][2 C] then scalar_l)
         if (c.per_size()) continue;
         (*b)[l] = p;
         p += c.level_channels(l);

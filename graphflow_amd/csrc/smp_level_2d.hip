@@ -314,10 +314,9 @@ gf_status smp_2d_backward_level(gf_smp *s, int l, const float *scalar, const flo
                                 bool rows_too) {
     (void)scalar;
     gf_ctx *ctx = s->ctx;
-    const gf_smp::DevLevel &d = s->lv[l], &pv = s->lv[l - 1];
-    const int Cp = s->cfg.level_channels(l - 1), Cc = s->cfg.level_channels(l), concat = s->cfg.concat() ? 1 : 0;
-    const int nodes = s->lay.level[l].nNodes, np = s->lay.level[l - 1].nNodes, V = theta_vec(Cp);
-    const int nbuckets = (int)(s->lay.level[l].th_bucket.size() / 3);
+    const gf_smp::DevLevel &d = s->lv[l];
+    const int Cp = s->cfg.level_channels(l - 1), concat = s->cfg.concat() ? 1 : 0;
+    const int nodes = s->lay.level[l].nNodes, V = theta_vec(Cp);
     if (!node_df && !rows_too) return fail(ctx, GF_ERR_INVALID, "steerable level %d: no gradient to back-propagate", l);
     if (nodes > 0) {
         const int npw = theta_pack((double)level_columns(s->lay.level[l]) / (double)nodes * (Cp / V));
@@ -330,11 +329,30 @@ gf_status smp_2d_backward_level(gf_smp *s, int l, const float *scalar, const flo
             default: GF_2D_NODE(1); break;
         }
 #undef GF_2D_NODE
-        GF_LAUNCH(ctx, "smp2d_bucket_partials", level2d_bucket_partials, dim3((unsigned)nbuckets, kSplit2d), dim3(256), 0, d.th_node, d.th_bucket,
-                  d.node_pair, d.part2d, Cc + 3 * Cp);
-        GF_LAUNCH(ctx, "smp2d_grads_finish", level2d_grads_finish, dim3((unsigned)nbuckets + 1), dim3(256), 0, d.part2d, d.th_bucket, dsizes, dscalar, Cp,
-                  Cc, nbuckets);
+        const gf_status st = smp_2d_size_grads(s, l, dscalar, dsizes);
+        if (st != GF_OK) return st;
     }
+    return smp_2d_gather_down(s, l);
+}
+
+// The column partials in d.th_node ([sum s][Cc + 3 Cp]) over the size buckets: `+=` into the per-size entries and dscalar_l
+gf_status smp_2d_size_grads(gf_smp *s, int l, float *dscalar, float *dsizes) {
+    gf_ctx *ctx = s->ctx;
+    const gf_smp::DevLevel &d = s->lv[l];
+    const int Cp = s->cfg.level_channels(l - 1), Cc = s->cfg.level_channels(l);
+    const int nbuckets = (int)(s->lay.level[l].th_bucket.size() / 3);
+    GF_LAUNCH(ctx, "smp2d_bucket_partials", level2d_bucket_partials, dim3((unsigned)nbuckets, kSplit2d), dim3(256), 0, d.th_node, d.th_bucket,
+              d.node_pair, d.part2d, Cc + 3 * Cp);
+    GF_LAUNCH(ctx, "smp2d_grads_finish", level2d_grads_finish, dim3((unsigned)nbuckets + 1), dim3(256), 0, d.part2d, d.th_bucket, dsizes, dscalar, Cp,
+              Cc, nbuckets);
+    return GF_OK;
+}
+
+// df_{l-1} gathered from dS (the first Cp columns of d.df's rows)
+gf_status smp_2d_gather_down(gf_smp *s, int l) {
+    gf_ctx *ctx = s->ctx;
+    const gf_smp::DevLevel &d = s->lv[l], &pv = s->lv[l - 1];
+    const int Cp = s->cfg.level_channels(l - 1), Cc = s->cfg.level_channels(l), np = s->lay.level[l - 1].nNodes, V = theta_vec(Cp);
     if (np > 0) {
         const int npw = theta_pack((double)level_columns(s->lay.level[l - 1]) / (double)np * (Cp / V));
         const dim3 grid((unsigned)((np + npw - 1) / npw));

@@ -199,7 +199,7 @@ static bool host_config(const gf_smp_config *cfg, int nClass, gfsmp::Config *out
         if (nClass || !gf::smp_unrestricted_config_ok(cfg)) return false;
         gf::smp_unrestricted_config(cfg, &c);
     } else if (cfg->steerable_2d) {   // SMP_2D, SMP_2D_ver4 (gf_smp_config.steerable_2d; a classifier read-out is allowed)
-        if (!gf::smp_2d_config_ok(cfg)) return false;
+        if (!gf::smp_2d_config_ok(cfg) || (nClass && cfg->steerable_2d == 5)) return false;   // (SMP_2D_ver5: no classifier)
         c.steerable_2d = cfg->steerable_2d;
         c.max_nVertices = cfg->max_nVertices;
         c.nContractions = 0;
@@ -246,6 +246,9 @@ static gf_status uniform_init_host(const gf_smp_config *cfg, int nClass, float *
         if (c.first_order == 4) {   // K_eye, K_one: one block each (SMP_1D_ver3.h:238-239)
             sizes.push_back(c.weight_block(l) / 2);
             sizes.push_back(c.weight_block(l) / 2);
+        } else if (c.steerable_2d == 5 && !c.unrestricted) {   // K_l [C][2 C] as one Vector of 2 C^2, then scalar_l (SMP_2D_ver5.h:241-242)
+            sizes.push_back(2 * C * C);
+            sizes.push_back(C);
         } else if (c.weight_block(l)) {
             sizes.push_back(c.weight_block(l));
         }

@@ -717,11 +717,11 @@ void build_batch_theta(const Config &cfg, int nMol, const int *nVertices, const 
                 for (size_t i = 0; i < s; ++i) {
                     double degree = 0.0;
                     for (size_t j = 0; j < s; ++j) {
-                        const double x = cfg.steerable_2d == 2 && fv[i] == fv[j] ? 1.0 : (double)A[(size_t)fv[i] * V + fv[j]];
+                        const double x = cfg.steerable_2d >= 2 && fv[i] == fv[j] ? 1.0 : (double)A[(size_t)fv[i] * V + fv[j]];
                         a[i * s + j] = (float)x;
                         degree += x;
                     }
-                    if (cfg.steerable_2d == 2)
+                    if (cfg.steerable_2d >= 2)   // (ver4, ver5)
                         for (size_t j = 0; j < s; ++j) a[i * s + j] = (float)((double)a[i * s + j] / degree);
                 }
             }

@@ -63,6 +63,8 @@ struct Config {
     // smp_level_2d.hip): f_l[v] is [s][s][C_l], the fields, children and pi are the first-order models' (no cap), applied to both indices.
     // Per level: for size = 1 .. max_nVertices (lambda1_s[C_{l-1}], lambda2_s[C_{l-1}], b_s[C_l]), then scalar_l[C_{l-1}] (the "matrix
     // block").  1: z = lambda1 S + lambda2 col + b, C_l = C; 2: z = [lambda1 S | lambda2 col] + b, C_l = 2 C_{l-1}.  Slope 0.01 everywhere.
+    // 5: SMP_2D_ver5 (SMP_2D_ver5.h; smp_level_2d_ver5.hip): ver4's level with z = K_l [lambda1 S | lambda2 col] + b, K_l [C][2 C] in front of
+    // scalar_l in the matrix block, C_l = C.  The value is the class's version number: there is no 3 or 4.
     int steerable_2d = 0;
     // 1, 2, 3: Unrestricted_SMP_1D, Unrestricted_SMP_1D_ver2, Unrestricted_SMP_2D (GraphFlow/Unrestricted_SMP_*.h;
     // gf_smp_config.unrestricted; smp_level_unrestricted.hip): SMP_1D, SMP_1D_ver2 and SMP_2D with a dense learned filter per field size
@@ -86,7 +88,7 @@ struct Config {
     // floats of the level's matrix block: K_l [nContractions C_{l-1}][C_l]; none in SMP_1D / ver2; K_eye, K_one in ver3; scalar_l in SMP_2D / ver4
     size_t weight_block(int l) const {
         const size_t Cp = (size_t)level_channels(l - 1);
-        if (steerable_2d) return Cp;
+        if (steerable_2d) return steerable_2d == 5 ? 2 * Cp * Cp + Cp : Cp;
         return first_order == 2 || first_order == 3 ? 0 : first_order == 4 ? 2 * Cp * Cp : (size_t)nContractions * Cp * level_channels(l);
     }
     int top_channels() const { return first_order >= 2 || steerable_2d ? level_channels(nLevels) : nChanels;  }   // width of the graph feature and of W's rows

@@ -876,6 +876,14 @@ gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int
             t.alloc(&d.th_B, cols * Cp);
             t.alloc(&d.th_node, cols * (Cl + 3 * Cp));
             t.alloc(&d.part2d, h.buckets.size() * 16 * (Cl + 3 * Cp));   // [buckets][kSplit2d row chunks][Cc + 3 Cp]
+            if (cfg.steerable_2d == 5) {   // SMP_2D_ver5 (smp_level_2d_ver5.hip): the tables of its projections, u, dO, dE and the partials of dK_l
+                t.alloc(&d.v5_row_cs, (size_t)h.rows);
+                t.alloc(&d.v5_col_s, cols);
+                t.alloc(&d.v5_u, cols * Cp);
+                t.alloc(&d.v5_dO, cols * Cp);
+                t.alloc(&d.Q, (size_t)h.rows * Cp);
+                t.alloc(&d.v5_dKpart, smp_2d_ver5_wgrad_chunks((long long)h.rows, (long long)cols) * Cp * Cp);
+            }
             continue;
         }
         t.alloc(&d.th_node, nodes * 3 * Cl);

@@ -310,12 +310,15 @@ class SMP2D(SMP1D):
     classifiers (SMP_2D_classification, SMP_2D_ver4_classification): the second-order steerable models, gf_smp_config.steerable_2d.
     f_l[v] is [s, s, C_l]; with S = the children's tensors summed on the positions of phi_l(v) plus scalar_l * adj_v, col = its column sums:
       "2d":   z = lambda1_s S + lambda2_s col + b_s, C channels at every level;
-      "ver4": z = [lambda1_s S | lambda2_s col] + b_s, the channels double per level (C << l).
+      "ver4": z = [lambda1_s S | lambda2_s col] + b_s, the channels double per level (C << l);
+      "ver5": z = K_l [lambda1_s S | lambda2_s col] + b_s (SMP_2D_ver5, steerable_2d = 5): ver4's level projected back to C channels by a
+              learned K_l[C, 2C], so the width stays constant; nChanels <= 128; no classifier (n_class is refused).
     Parameters in registration order: H[C, F(D+1)]; for l = 1..L: (lambda1_s[C_{l-1}], lambda2_s[C_{l-1}], b_s[C_l]) for
-    s = 1..max_nVertices, then scalar_l[C_{l-1}]; W[C_L], or W[n_class, C_L] for a classifier.  The optimiser is Momentum: step().
+    s = 1..max_nVertices, then ("ver5" only) K_l[C, 2C], then scalar_l[C_{l-1}]; W[C_L], or W[n_class, C_L] for a classifier.  The optimiser
+    is Momentum: step().
     A classifier's forward(params, labels) returns (arg-max label, log p[label], graph_feature); scores() the logits and probabilities."""
 
-    FORMS = {"2d": 1, "ver4": 2}
+    FORMS = {"2d": 1, "ver4": 2, "ver5": 5}
 
     def __init__(self, form, max_nVertices, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering=True, n_class=0, ctx=None):
         self.ctx = ctx or default_context()
@@ -334,12 +337,12 @@ class SMP2D(SMP1D):
     @staticmethod
     def config(form, max_nVertices, nLevels, nChanels, nFeatures, nDepth, has_WL_ordering=True):
         if form not in SMP2D.FORMS:
-            raise ValueError("SMP2D: form %r (\"2d\": SMP_2D, \"ver4\": SMP_2D_ver4)" % (form,))
+            raise ValueError("SMP2D: form %r (\"2d\": SMP_2D, \"ver4\": SMP_2D_ver4, \"ver5\": SMP_2D_ver5)" % (form,))
         return SMPConfig(nLevels, nChanels, nFeatures, nDepth, max_nVertices, 1 if has_WL_ordering else 0, 0, 0, 0, 0, max_nVertices,
                          SMP2D.FORMS[form])
 
     def level_channels(self, level):
-        return self.cfg.nChanels if self.form == "2d" else self.cfg.nChanels << level
+        return self.cfg.nChanels << level if self.form == "ver4" else self.cfg.nChanels
 
     def scores(self):
         """(scores, probability) of a classifier's last forward, [nMol, n_class] each."""

@@ -298,6 +298,7 @@ typedef struct {
      *   col[j]    = sum_k S[k][j]
      *   1  SMP_2D       z[i][j] = lambda1_s S[i][j] + lambda2_s col[j] + b_s              C_l = C
      *   2  SMP_2D_ver4  z[i][j] = [lambda1_s S[i][j] | lambda2_s col[j]] + b_s            C_l = C << l
+     *   5  SMP_2D_ver5  z[i][j] = K_l [lambda1_s S[i][j] | lambda2_s col[j]] + b_s        C_l = C   (K_l [C][2 C], CustomMatMulTensor)
      *   f_l[v] = LeakyReLU3D(z), slope 0.01 at every level
      * per CHANNEL: lambda1_s, lambda2_s, scalar_l are [C_{l-1}], b_s is [C_l].  adj_v is the adjacency reduced to phi_l(v); in SMP_2D_ver4
      * its diagonal is 1 and every row is divided by its sum.  Read-out: sum over (i, j), LeakyReLU, sum over the vertices; InnerProduct with
@@ -311,7 +312,14 @@ typedef struct {
      * gf_smp_read_reduced_adjacency the class's adj_v, gf_smp_level_sizes rows = sum of s^2.  The level is smp_level_2d.hip: no GEMM, no
      * atomics.  Refused with GF_ERR_UNSUPPORTED before anything is launched: gf_smp_set_grad_allreduce(smp, 1), gf_smp_dropout_masks,
      * gf_smp_backward_features, gf_smp_prepare_coulomb with a Coulomb matrix (the classes have no such constructor).  gf_smp_model_create
-     * has no towers of these forms.  0 (a zero-initialised tail): everything as described above. */
+     * has no towers of these forms.  0 (a zero-initialised tail): everything as described above.
+     * 5: SMP_2D_ver5 (GraphFlow/SMP_2D_ver5.h; the value is the class's version number, 3 and 4 are refused) -- SMP_2D_ver4's level, its
+     * reduced adjacency and its multiplicity j included, with the 2 C concatenated channels projected back to C by a learned K_l [C][2 C]
+     * (row = output channel, columns [eye half | one half]): the one steerable model whose width does not double per level.  Its matrix
+     * block is K_l then scalar_l; gf_smp_uniform_init_host draws K_l as one block (divisor 10 * 2 C^2).  dK_l is the plain derivative (K_l
+     * is one node of the class's graph).  Also required: nChanels <= 128 (a level's K1 image sits in LDS).  The level is
+     * smp_level_2d_ver5.hip: the row projection on v_mfma_f32_32x32x2_f32 with fp32 accumulation, no atomics.  gf_smp_create_classifier
+     * answers GF_ERR_UNSUPPORTED (there is no SMP_2D_ver5_classification); the other refusals are those of 1 and 2. */
     int steerable_2d;
     /* 1: Unrestricted_SMP_1D, 2: Unrestricted_SMP_1D_ver2, 3: Unrestricted_SMP_2D (GraphFlow/Unrestricted_SMP_*.h) -- SMP_1D, SMP_1D_ver2
      * and SMP_2D with a DENSE learned filter per field size s in place of lambda1_s I + lambda2_s 1 1^T.  Fields, children, level 0, the
