@@ -98,6 +98,30 @@ __device__ __forceinline__ void gf_st_s(V *p, V v) {
     if constexpr ((GF_NT_SITES & SITE) != 0) __builtin_nontemporal_store(v, p);
     else *p = v;
 }
+// The same accesses through pointers that KEEP the global address space.  A kernel argument is known to be global memory and so is a
+// `__device__` array, but a select between the two (`present ? src : zero_page`, `stored ? out : scratch_rows`), or a pointer that
+// went through LDS as an integer, is a generic pointer to the compiler: the access becomes a FLAT instruction, which counts against
+// LGKM_CNT as well as VM_CNT and is unordered against the kernel's LDS traffic -- the compiler then stops counting its memory queue
+// and waits for lgkmcnt(0) / vmcnt(0).  Convert BOTH sides with gf_global() before the select and access through gf_ld_g / gf_st_g.
+#define GF_GLOBAL __attribute__((address_space(1)))
+template <typename V>
+__device__ __forceinline__ const GF_GLOBAL V *gf_global(const V *p) {
+    return (const GF_GLOBAL V *)p;
+}
+template <typename V>
+__device__ __forceinline__ GF_GLOBAL V *gf_global(V *p) {
+    return (GF_GLOBAL V *)p;
+}
+template <int SITE, typename V>
+__device__ __forceinline__ V gf_ld_g(const GF_GLOBAL V *p) {
+    if constexpr ((GF_NT_SITES & SITE) != 0) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+template <int SITE, typename V>
+__device__ __forceinline__ void gf_st_g(GF_GLOBAL V *p, V v) {
+    if constexpr ((GF_NT_SITES & SITE) != 0) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
 #endif
 
 #define GF_HIP_TRY(ctx, expr)                                                                      \

@@ -70,6 +70,11 @@ __device__ __forceinline__ void split_plain2(float a, float b, float sa, float s
 // hold data, bit 30 = those of the transposed row do.  Half of the rows at QM9 sizes are structurally zero in those two blocks
 // (row (a, b) with b outside the field of a's source); the forward kernel then reads such a block from one 128-byte page of zeros
 // that never leaves the caches instead: 1.1 of the 3.3 GB the kernel read per cfg3 step are not fetched.
+// RULE: a select between a kernel argument and a `__device__` array (this page, sp_dump below) must be made, and the access issued, in
+// the GLOBAL address space -- gf_global() on both sides, gf_ld_g / gf_st_g (gf_internal.h).  Selected as plain pointers the result is a
+// generic pointer and every access through it a FLAT instruction: counted against LGKM_CNT as well, unordered against the LDS traffic
+// these kernels live on, so the compiler drains its queues (lgkmcnt(0) / vmcnt(0)) where it would otherwise count them.  The same holds
+// for an address that comes back from LDS as an integer (the row-class stores).
 __device__ __attribute__((aligned(256))) const float sp_zero_page[64] = {};
 // ... and the backward kernel sends the dS_ab / dT6 blocks of such rows -- gradients of structural zeros, which no consumer reads
 // (the gather of df_{l-1} only visits rows (a, b) with b inside the field of a's source) -- to a scratch area that stays in L2:
@@ -265,10 +270,15 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
         __builtin_amdgcn_sched_barrier(0);  // (requests stay where the schedule below puts them: hoisted to the top of the panel
                                             //  they would all be live at once)
         asm volatile("" : "+v"(src_row));   // (nor is the address arithmetic on a prefetched row index moved up to its load)
-        const float *src = A + (size_t)src_row * LDA + blk * BS + a_off + VPL * lh;
-        if constexpr (MASK) src = present ? src : sp_zero_page;  // (a select on the address: same requests, same registers)
+        // (a select on the address: same requests, same registers.  Made on the address as an INTEGER and turned into a global pointer
+        //  afterwards -- see the rule at sp_zero_page.  A select between two global POINTERS gives the same loads, but the compiler then
+        //  re-associates the address arithmetic around it and the panel spills: 104 -> 284 bytes of scratch per lane forward, none -> 96
+        //  in the row-class backward kernel.)
+        unsigned long long sa = (unsigned long long)(A + (size_t)src_row * LDA + blk * BS + a_off + VPL * lh);
+        if constexpr (MASK) sa = present ? sa : (unsigned long long)sp_zero_page;
+        const GF_GLOBAL float *src = (const GF_GLOBAL float *)sa;
 #pragma unroll
-        for (int q = 0; q < VPL / 4; ++q) R.a[q] = gf_ld_s<1>(reinterpret_cast<const f4v *>(src + 4 * q));
+        for (int q = 0; q < VPL / 4; ++q) R.a[q] = gf_ld_g<1>(reinterpret_cast<const GF_GLOBAL f4v *>(src + 4 * q));
         __builtin_amdgcn_sched_barrier(0);
     };
     auto load_raw = [&](Raw &R, int p, int blk, bool present) {
@@ -368,7 +378,15 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
             for (int g = 0; g < 4; ++g) {
                 const f4v fac = *reinterpret_cast<const f4v *>(myfac + 8 * g + 4 * lh);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[4 * g + j] += t[4 * g + j] * fac[j];
+                for (int j = 0; j < 4; ++j) {
+                    // (The masked and the plain build of a kernel must give the same bits, and every build the bits it always gave.  The
+                    //  compiler contracts this update as it likes: it fuses all of them except two to ten per forward 32-channel build, in
+                    //  both of its builds alike -- but with the masked operands loaded from global pointers it split four of them in
+                    //  the masked 16-channel backward builds alone.  Those builds fuse by name, as they always compiled; the others keep
+                    //  the expression they were built from.  tests/test_masked_operand_paths_gpu.py compares the pairs bit for bit.)
+                    if constexpr (!FWD && CB == 16) acc[4 * g + j] = __builtin_fmaf(t[4 * g + j], fac[j], acc[4 * g + j]);
+                    else acc[4 * g + j] += t[4 * g + j] * fac[j];
+                }
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -401,20 +419,20 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
     //  before every split.  The one partial panel of the matrix runs a second copy of the panel code.)
     auto store_out = [&](int p, int o, const f16v &acc0, const f16v &acc1, auto full, unsigned rowbits = 0xffffffffu) {
         const int r0 = p * 32;
-        float *out = Out + (size_t)(r0 + 4 * lh) * LDOUT + o * BS + out_off + li;
+        GF_GLOBAL float *out = gf_global(Out) + (size_t)(r0 + 4 * lh) * LDOUT + o * BS + out_off + li;
         if constexpr (CB < 32)   // lanes of the zero columns store into the scratch rows (a select on the address: every store is issued)
-            out = li < CB ? out : sp_dump + (size_t)((r0 & 255) + 4 * lh) * 64 + li;
+            out = li < CB ? out : gf_global(sp_dump) + (size_t)((r0 & 255) + 4 * lh) * 64 + li;
         if constexpr (MASK && !FWD && decltype(full)::value) {
             if (rowbits != 0xffffffffu) {  // (uniform; the blocks without structural zeros pass all ones)
                 // rows without data go to the scratch rows: a select on the address, every store is issued
                 const unsigned mine = rowbits >> (4 * lh);
-                float *dump = sp_dump + (size_t)((r0 & 255) + 4 * lh) * 64 + li;
+                GF_GLOBAL float *dump = gf_global(sp_dump) + (size_t)((r0 & 255) + 4 * lh) * 64 + li;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int rr = (r & 3) + 8 * (r >> 2);
-                    float *dst = ((mine >> rr) & 1u) ? out + (size_t)rr * LDOUT : dump + rr * 64;
-                    gf_st_s<2>(dst, acc0[r]);
-                    if constexpr (NH == 2) gf_st_s<2>(dst + 32, acc1[r]);
+                    GF_GLOBAL float *dst = ((mine >> rr) & 1u) ? out + (size_t)rr * LDOUT : dump + rr * 64;
+                    gf_st_g<2>(dst, acc0[r]);
+                    if constexpr (NH == 2) gf_st_g<2>(dst + 32, acc1[r]);
                 }
                 return;
             }
@@ -423,8 +441,8 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int rr = (r & 3) + 8 * (r >> 2);
-                gf_st_s<2>(out + (size_t)rr * LDOUT, acc0[r]);
-                if constexpr (NH == 2) gf_st_s<2>(out + (size_t)rr * LDOUT + 32, acc1[r]);
+                gf_st_g<2>(out + (size_t)rr * LDOUT, acc0[r]);
+                if constexpr (NH == 2) gf_st_g<2>(out + (size_t)rr * LDOUT + 32, acc1[r]);
             }
         } else {
             // (the partial panel skips the rows without data as the full ones do: until the stand-alone operator's test looked, it
@@ -434,8 +452,8 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
             for (int r = 0; r < 16; ++r) {
                 const int rr = (r & 3) + 8 * (r >> 2);
                 if (r0 + 4 * lh + rr < rows && li < CB && ((mine >> rr) & 1u)) {
-                    gf_st_s<2>(out + (size_t)rr * LDOUT, acc0[r]);
-                    if constexpr (NH == 2) gf_st_s<2>(out + (size_t)rr * LDOUT + 32, acc1[r]);
+                    gf_st_g<2>(out + (size_t)rr * LDOUT, acc0[r]);
+                    if constexpr (NH == 2) gf_st_g<2>(out + (size_t)rr * LDOUT + 32, acc1[r]);
                 }
             }
         }
@@ -545,7 +563,7 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
         // where the lane's row is stored (a padding entry: one of the scratch rows), on its way to the C/D layout like the row factors
         auto post_rows = [&](int rw) {
             __builtin_amdgcn_wave_barrier();
-            myrow[li] = reinterpret_cast<unsigned long long>(rw < 0 ? sp_dump + li * 64 : Out + (size_t)e_row(rw) * LDOUT);
+            myrow[li] = (unsigned long long)(rw < 0 ? gf_global(sp_dump) + li * 64 : gf_global(Out) + (size_t)e_row(rw) * LDOUT);
             __builtin_amdgcn_wave_barrier();
         };
         auto store_rows = [&](int o, const f16v &acc0, const f16v &acc1) {
@@ -554,9 +572,10 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
                 const u64x2 a = *reinterpret_cast<const u64x2 *>(myrow + 8 * g + 4 * lh), b = *reinterpret_cast<const u64x2 *>(myrow + 8 * g + 4 * lh + 2);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    float *dst = reinterpret_cast<float *>(j < 2 ? a[j & 1] : b[j & 1]) + o * CB + li;
-                    gf_st_s<2>(dst, acc0[4 * g + j]);
-                    gf_st_s<2>(dst + 32, acc1[4 * g + j]);
+                    // (an address that went through LDS is an integer: rebuilt as a GLOBAL pointer, see gf_global)
+                    GF_GLOBAL float *dst = (GF_GLOBAL float *)(j < 2 ? a[j & 1] : b[j & 1]) + o * CB + li;
+                    gf_st_g<2>(dst, acc0[4 * g + j]);
+                    gf_st_g<2>(dst + 32, acc1[4 * g + j]);
                 }
             }
         };
@@ -907,14 +926,32 @@ __global__ __launch_bounds__(kSmThreads, 2) void smp_small_split(SmallJobs jobs,
 //
 // A workgroup of eight waves takes every gridDim-th 16-row slice of the level, four slices in flight and ONE
 // barrier per slice.  In the interval of slice i a thread splits its share of slice i + 1 (raw in registers, requested three
-// intervals ago) and stores the halves TRANSPOSED ([column][row pair], 48-byte rows: conflict-free b128 fragment reads) into the
+// intervals ago) and stores the halves TRANSPOSED ([column][row pair], laid out per kWsQuadSlot: conflict-free b32 stores and b128 fragment reads) into the
 // other stage's four f16 images (A h / l: 256 columns, B h / l: 320 columns), requests its share of slice i + 4 into the
 // registers just freed, and runs its wave's product on the images of slice i: a 64 x 64 output as 2 x 2 MFMA tiles, 12 MFMAs
 // of 8 passes.  Partial images and their fold are those of smp_wgrad_c64: a fixed set of rows per image, fixed order, reproducible.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int kWsThreads = 512, kWsSlice = 16, kWsRowWords = 12;  // 16 rows = 8 words of f16 pairs, padded to 48 B
+constexpr int kWsThreads = 512, kWsSlice = 16;
 constexpr int kWsACols = 256, kWsBCols = 320;
-constexpr int kWsStageWords = 2 * (kWsACols + kWsBCols) * kWsRowWords;
+// The transposed image of 32 operand columns x 16 rows: a column is 8 words (f16 row pairs 0..7) = two 16-byte slots, the four columns
+// of a quad lie 4 slots apart, and quad q of the block starts at slot kWsQuadSlot[q] (byte q of the constant) -- two quads interleaved
+// fill 16 slots, the four such pairs are staggered by a slot or three.  Chosen by the bank rules of both accesses, so that nothing has to
+// move between registers on the way in:
+//   * the staging stores (ds_write_b32, banks = word % 32 over 32 lanes = 8 quads x 4 row pairs, every lane on the SAME column of its
+//     quad): the quads' start slots are distinct mod 8 -- {0, 4, 5, 1, 6, 2, 3, 7} -- so the 32 lanes cover the 32 banks once;
+//   * the fragment reads (ds_read_b128, slots mod 16 over the 16-lane groups {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} of columns):
+//     the quads {0, 3, 5, 6} start at slots 0, 1, 2, 3 mod 4 and so do the quads {1, 2, 4, 7}; with the columns 4 slots apart each
+//     group covers the 16 slots once.
+// 288 words per block (276 used) against the 384 of the [column][12 words] image it replaces, whose stores needed the lane's columns
+// rotated through registers to separate the banks (two times eight v_cndmask per task).
+constexpr unsigned long long kWsQuadSlot = 0x3713022611352400ull;   // quads 0..7: slots 0, 36, 53, 17, 38, 2, 19, 55
+constexpr int kWsBlockWords = 288;
+__device__ __forceinline__ int ws_col_word(int col) {   // word of (column, row pair 0) in its image
+    const int q = (col >> 2) & 7;
+    return (col >> 5) * kWsBlockWords + 4 * (int)((kWsQuadSlot >> (8 * q)) & 0xffu) + 16 * (col & 3);
+}
+constexpr int kWsAWords = kWsACols / 32 * kWsBlockWords, kWsBWords = kWsBCols / 32 * kWsBlockWords;   // one image (h or l)
+constexpr int kWsStageWords = 2 * (kWsAWords + kWsBWords);
 constexpr size_t kWsLds = 2 * (size_t)kWsStageWords * 4 + 2 * (kWsACols + kWsBCols) * sizeof(float);   // two stages + the column scales and their inverses
 __constant__ int c_ws_ablk[8] = {0, 1, 0, 2, 3, 0, 1, 0};  // S_ab, S_bc, S_ab, T6, T10, S_ab, S_bc, S_ab
 __constant__ int c_ws_bblk[8] = {1, 1, 2, 0, 0, 3, 3, 4};  // tot L, tot L, tr L, L, L, dU, dU, dU[trow]
@@ -995,16 +1032,14 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
     const int a_quad = 8 * wave + q_lo;
     auto b_blk = [&](int e) { return (wave + 8 * e) >> 1; };
     auto b_quad = [&](int e) { return 8 * ((wave + 8 * e) & 1) + q_lo; };
-    // (the scale of the i-th value a lane stores: its quad's column (i + rot) & 3, see `rotate` below)
-    const int rot = (q_lo >> 1) & 3;
-    f4v a_scale, b_scale[NB];
+    f4v a_scale, b_scale[NB];   // the scales of the lane's four columns
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        a_scale[i] = sScale[4 * a_quad + ((i + rot) & 3)];
+        a_scale[i] = sScale[4 * a_quad + i];
 #pragma unroll
         for (int e = 0; e < NB; ++e) {
             const int blk = b_blk(e) < 5 ? b_blk(e) : 0;   // (waves 2..7 have no second task: any column)
-            b_scale[e][i] = sScale[kWsACols + 64 * blk + 4 * b_quad(e) + ((i + rot) & 3)];
+            b_scale[e][i] = sScale[kWsACols + 64 * blk + 4 * b_quad(e) + i];
         }
     }
     // The gathered rows' indices (dU[trow]: waves 0 and 1, second task) are requested TWO requests ahead: a request that had to
@@ -1032,50 +1067,42 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
         const long long last = kend - 1, kk = K(m) + 2 * pair;
         const int c0 = (int)(kk < last ? kk : last), c1 = (int)(kk + 1 < last ? kk + 1 : last);
         const int a_col = W == 1 ? 4 * a_quad : (a_quad >> 4) * BS + a_off + ((4 * a_quad) & 63);   // the quad's first column in its row of T
-        const float *t0 = T + (size_t)c0 * LDT + a_col, *t1 = T + (size_t)c1 * LDT + a_col;
-        S.ta.v0 = gf_ld_s<4>(reinterpret_cast<const f4v *>(z0 ? sp_zero_page + 4 * q_lo : t0));
-        S.ta.v1 = gf_ld_s<4>(reinterpret_cast<const f4v *>(z1 ? sp_zero_page + 4 * q_lo : t1));
+        const GF_GLOBAL float *zero = gf_global(sp_zero_page) + 4 * q_lo;
+        const GF_GLOBAL float *t0 = gf_global(T) + (size_t)c0 * LDT + a_col, *t1 = gf_global(T) + (size_t)c1 * LDT + a_col;
+        S.ta.v0 = gf_ld_g<4>(reinterpret_cast<const GF_GLOBAL f4v *>(z0 ? zero : t0));
+        S.ta.v1 = gf_ld_g<4>(reinterpret_cast<const GF_GLOBAL f4v *>(z1 ? zero : t1));
 #pragma unroll
         for (int e = 0; e < NB; ++e) {
             const int blk = b_blk(e);  // (e == 1: 4 on waves 0 and 1, no block on the others)
             S.f0[e] = rs[(size_t)c0 * 2 + (blk == 2)];
             S.f1[e] = rs[(size_t)c1 * 2 + (blk == 2)];
             const bool gathered = blk == 4;
-            const float *src = blk < 5 ? dO + (blk >= 3 ? BS : 0) + b_off + 4 * b_quad(e) : T + a_col;
+            const GF_GLOBAL float *src = blk < 5 ? gf_global(dO) + (blk >= 3 ? BS : 0) + b_off + 4 * b_quad(e) : gf_global(T) + a_col;
             const int ld = blk < 5 ? LDO : LDT;
             // (the gathered dU row only meets S_ab of ITS row in product 7: a row without data skips the gather as well)
-            const float *s0 = src + (size_t)(gathered ? g0 : c0) * ld, *s1 = src + (size_t)(gathered ? g1 : c1) * ld;
-            S.tb[e].v0 = gf_ld_s<256>(reinterpret_cast<const f4v *>((gathered && zg0) ? sp_zero_page + 4 * q_lo : s0));
-            S.tb[e].v1 = gf_ld_s<256>(reinterpret_cast<const f4v *>((gathered && zg1) ? sp_zero_page + 4 * q_lo : s1));
+            const GF_GLOBAL float *s0 = src + (size_t)(gathered ? g0 : c0) * ld, *s1 = src + (size_t)(gathered ? g1 : c1) * ld;
+            S.tb[e].v0 = gf_ld_g<256>(reinterpret_cast<const GF_GLOBAL f4v *>((gathered && zg0) ? zero : s0));
+            S.tb[e].v1 = gf_ld_g<256>(reinterpret_cast<const GF_GLOBAL f4v *>((gathered && zg1) ? zero : s1));
         }
     };
-    // word (column col0 + j, pair) of the images <- halves of (row k, row k + 1) at column col0 + j
-    // The i-th store of a lane takes column (i + rot) & 3 of its quad, rot = (q_lo >> 1) & 3: with every lane on column i, the 32
-    // lanes of a store group (8 quads x 4 pairs; bank = word % 32, row stride 12 words, quad stride 48) sit on 8 banks, four to a
-    // bank (SQ_LDS_BANK_CONFLICT was twice the LDS-active cycles).  Rotated, the group covers the 32 banks once
-    // (16 (q_lo & 1) + 12 ((i + rot) & 3) + pair): no conflicts measured.  The rotation of the lane's two float4 is eight selects each.
-    auto rotate = [&](f4v v) {
-        if (rot & 1) v = f4v{v[1], v[2], v[3], v[0]};
-        if (rot & 2) v = f4v{v[2], v[3], v[0], v[1]};
-        return v;
-    };
-    // (sc: the columns' scales in store order; f0, f1: what rows k and k + 1 are multiplied by besides -- the row's factor for the tot L /
-    //  tr L copies, 0 for a row past the end of the level: everything rides in the one multiply the split starts with)
+    // word (column col0 + i, pair) of the images <- halves of (row k, row k + 1) at column col0 + i: the four columns of the lane's quad
+    // are 16 words apart (ws_col_word), one address and four immediate offsets per image -- conflict-free as issued, see kWsQuadSlot
+    // (sc: the columns' scales; f0, f1: what rows k and k + 1 are multiplied by besides -- the row's factor for the tot L / tr L copies,
+    //  0 for a row past the end of the level: everything rides in the one multiply the split starts with)
     auto store_task = [&](const f4v &v0, const f4v &v1, unsigned *H, unsigned *L, int col0, const f4v &sc, float f0, float f1) {
-        const f4v r0 = rotate(v0), r1 = rotate(v1);
+        const int w = ws_col_word(col0) + pair;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             h2 h, l;
-            split_plain2(r0[i], r1[i], sc[i] * f0, sc[i] * f1, &h, &l);
-            const int w = (col0 + ((i + rot) & 3)) * kWsRowWords + pair;
-            H[w] = __builtin_bit_cast(unsigned, h);
-            L[w] = __builtin_bit_cast(unsigned, l);
+            split_plain2(v0[i], v1[i], sc[i] * f0, sc[i] * f1, &h, &l);
+            H[w + 16 * i] = __builtin_bit_cast(unsigned, h);
+            L[w + 16 * i] = __builtin_bit_cast(unsigned, l);
         }
     };
     // rows past the range contribute zeros; the scaled copies of L take their row factors (fp32 factor times a power of two: the
     // product the fp32 kernel forms, rounded once)
     auto store_slice = [&](const Set &S, long long k0, unsigned *stage) {
-        unsigned *Ah = stage, *Al = Ah + kWsACols * kWsRowWords, *Bh = Al + kWsACols * kWsRowWords, *Bl = Bh + kWsBCols * kWsRowWords;
+        unsigned *Ah = stage, *Al = Ah + kWsAWords, *Bh = Al + kWsAWords, *Bl = Bh + kWsBWords;
         const long long k = k0 + 2 * pair;
         const float ok0 = k < kend ? 1.f : 0.f, ok1 = k + 1 < kend ? 1.f : 0.f;
         store_task(S.ta.v0, S.ta.v1, Ah, Al, 4 * a_quad, a_scale, ok0, ok1);
@@ -1094,15 +1121,15 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
     for (int r = 0; r < 16; ++r) acc[0][0][r] = acc[0][1][r] = acc[1][0][r] = acc[1][1][r] = 0.f;
     const int ablk = c_ws_ablk[wave], bblk = c_ws_bblk[wave];
     auto products = [&](const unsigned *stage) {
-        const unsigned *Ah = stage, *Al = Ah + kWsACols * kWsRowWords, *Bh = Al + kWsACols * kWsRowWords, *Bl = Bh + kWsBCols * kWsRowWords;
-        const int ao = (ablk * 64 + li) * kWsRowWords + 4 * lg, bo = (bblk * 64 + li) * kWsRowWords + 4 * lg;
+        const unsigned *Ah = stage, *Al = Ah + kWsAWords, *Bh = Al + kWsAWords, *Bl = Bh + kWsBWords;
+        const int ao = ws_col_word(ablk * 64 + li) + 4 * lg, bo = ws_col_word(bblk * 64 + li) + 4 * lg;   // (the next 32 columns: a block on)
         h8 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            ah[t] = __builtin_bit_cast(h8, *reinterpret_cast<const uint4 *>(Ah + ao + t * 32 * kWsRowWords));
-            al[t] = __builtin_bit_cast(h8, *reinterpret_cast<const uint4 *>(Al + ao + t * 32 * kWsRowWords));
-            bh[t] = __builtin_bit_cast(h8, *reinterpret_cast<const uint4 *>(Bh + bo + t * 32 * kWsRowWords));
-            bl[t] = __builtin_bit_cast(h8, *reinterpret_cast<const uint4 *>(Bl + bo + t * 32 * kWsRowWords));
+            ah[t] = __builtin_bit_cast(h8, *reinterpret_cast<const uint4 *>(Ah + ao + t * kWsBlockWords));
+            al[t] = __builtin_bit_cast(h8, *reinterpret_cast<const uint4 *>(Al + ao + t * kWsBlockWords));
+            bh[t] = __builtin_bit_cast(h8, *reinterpret_cast<const uint4 *>(Bh + bo + t * kWsBlockWords));
+            bl[t] = __builtin_bit_cast(h8, *reinterpret_cast<const uint4 *>(Bl + bo + t * kWsBlockWords));
         }
         // (plain low halves here -- split_plain2 -- not the 2^11-scaled ones of the row-panel kernels: with per-column exponents the
         //  subnormal floor sits 2^-38 below the column's bound, and the three products go straight into the accumulator)
