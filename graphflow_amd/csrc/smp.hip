@@ -909,13 +909,11 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
         switch (kind[l]) {
         case LevelKind::Fused18: st = smp_fused_forward_level(s, l, K[l], b[l]); break;
         case LevelKind::Gamma: st = smp_gamma_forward_level(s, l, K[l], b[l]); break;   // products on the rows of level l - 1, one gather into f_l
-        case LevelKind::Theta:   // the same shape of level, first order (b[l]: the per-size block); SMP_1D*: no [2 C'][C] matrix
-            st = s->cfg.first_order >= 2 ? smp_1d_forward_level(s, l, K[l], b[l]) : smp_theta_forward_level(s, l, K[l], b[l]);
+        case LevelKind::Theta:          // the same shape of level, first order (b[l]: the per-size block); SMP_1D*: no [2 C'][C] matrix
+        case LevelKind::Steerable2D:    // (K[l]: scalar_l -- SMP_2D_ver5: K_l then scalar_l --, b[l]: the per-size block)
+        case LevelKind::Unrestricted:   // (the same two)
+            st = smp_field_forward_level(s, l, K[l], b[l]);
             break;
-        case LevelKind::Steerable2D:   // (K[l]: scalar_l -- SMP_2D_ver5: K_l then scalar_l --, b[l]: the per-size block)
-            st = s->cfg.steerable_2d == 5 ? smp_2d_ver5_forward_level(s, l, K[l], b[l]) : smp_2d_forward_level(s, l, K[l], b[l]);
-            break;
-        case LevelKind::Unrestricted: st = smp_unrestricted_forward_level(s, l, K[l], b[l]); break;   // (the same two)
         case LevelKind::OpByOp: st = forward_level_opbyop(s, l, K[l], b[l]); break;
         }
         if (st == GF_OK && l < L) st = dup_level(s, l);
@@ -1042,7 +1040,7 @@ gf_status backward_level_opbyop(gf_smp *s, int l, const float *Kl, float *dKl) {
 // df_{l-1} from what level l left: the fused level's folded consumer gather, else the consumer-list gather of dP (a fused level's D_bb /
 // D_ac gradients arrive through dFdc beside it); the gamma level has written df_{l-1} itself
 gf_status send_df_down(gf_smp *s, int l, LevelKind kind) {
-    if (kind == LevelKind::Gamma || kind == LevelKind::Theta || kind == LevelKind::Steerable2D || kind == LevelKind::Unrestricted) return GF_OK;
+    if (kind == LevelKind::Gamma || is_field_level(kind)) return GF_OK;
     const bool fused = kind == LevelKind::Fused18;
     if (fused && smp_fused_gather_enabled(s, l)) return smp_fused_gather_backward(s, l);
     const gf_smp::DevLevel &d = s->lv[l], &pv = s->lv[l - 1];
@@ -1112,8 +1110,7 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
     // the read-out's gradient into the top level: a fused level reads it as one vector per node, the others at every (i, j)
     const gfsmp::LevelLayout &top = B.level[L];
     // (a first-order level takes the read-out's gradient the same way: one vector per node, added inside its per-node kernel)
-    const bool top_fused = !dfeat && (kind[L] == LevelKind::Fused18 || kind[L] == LevelKind::Theta || kind[L] == LevelKind::Steerable2D ||
-                                      kind[L] == LevelKind::Unrestricted);
+    const bool top_fused = !dfeat && (kind[L] == LevelKind::Fused18 || is_field_level(kind[L]));
     const bool classes = !dfeat && s->cfg.nClass;   // (a classifier: dg [nMol][C] goes down instead of dy[mol] * W)
     if (!dfeat && !classes) GF_LAUNCH(ctx, "smp_readout_dW", readout_dW, dim3(1), dim3(1024), 0, s->dy, s->g, dW, C, B.nMol);
     if (dfeat) {
@@ -1133,7 +1130,7 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
     for (int l = L; l >= 1; --l) {
         if (l < L) st = fold_level(s, l);   // (SMP_2D_ver6 on the 18-slice level: the gradient of the transposed copies joins the matrices')
         if (st != GF_OK) return st;
-        if (kind[l] != LevelKind::Fused18 && kind[l] != LevelKind::Theta && kind[l] != LevelKind::Steerable2D && kind[l] != LevelKind::Unrestricted)
+        if (kind[l] != LevelKind::Fused18 && !is_field_level(kind[l]))
             s->bwd_consumed = true;   // (a first-order, steerable or unrestricted level keeps f, A, B: repeatable)
         switch (kind[l]) {
         case LevelKind::Fused18:
@@ -1153,15 +1150,12 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
         case LevelKind::Theta:   // dz, the per-size gradients, dG gathered from dz, dK_l and df_{l-1} on the rows of level l - 1
             if (dfeat) st = feature_nodevec(s, dfeat, l);
             if (st == GF_OK)
-                st = (s->cfg.first_order >= 2 ? smp_1d_backward_level : smp_theta_backward_level)(
-                    s, l, K[l], b[l], dK[l], db[l], dfeat ? s->lv[l].dshl : l == L ? s->dsh : nullptr, /*rows_too=*/l < L, smp_dp_level_done);
+                st = smp_field_backward_level(s, l, K[l], b[l], dK[l], db[l], dfeat ? s->lv[l].dshl : l == L ? s->dsh : nullptr, /*rows_too=*/l < L,
+                                              smp_dp_level_done);
             break;
-        case LevelKind::Steerable2D:   // dz, dS in place, the per-size gradients and dscalar_l, df_{l-1} gathered from dS (never a tower)
-            st = (s->cfg.steerable_2d == 5 ? smp_2d_ver5_backward_level : smp_2d_backward_level)(s, l, K[l], b[l], dK[l], db[l],
-                                                                                                    l == L ? s->dsh : nullptr, /*rows_too=*/l < L);
-            break;
+        case LevelKind::Steerable2D:    // dz, dS in place, the per-size gradients and dscalar_l, df_{l-1} gathered from dS (never a tower)
         case LevelKind::Unrestricted:   // dz in place, dS beside it, the per-size gradients (and dscalar_l), df_{l-1} gathered from dS (never a tower)
-            st = smp_unrestricted_backward_level(s, l, b[l], dK[l], db[l], l == L ? s->dsh : nullptr, /*rows_too=*/l < L);
+            st = smp_field_backward_level(s, l, K[l], b[l], dK[l], db[l], l == L ? s->dsh : nullptr, /*rows_too=*/l < L, smp_dp_level_done);
             break;
         }
         if (st == GF_OK) st = send_df_down(s, l, kind[l]);

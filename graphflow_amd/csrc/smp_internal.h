@@ -258,7 +258,7 @@ struct gf_smp {
         float *Sout = nullptr, *dSout = nullptr;    // [nodes][C]
         float *dSpart = nullptr, *dbpart = nullptr; // [pairs][C]
         float *Wst = nullptr, *dWst = nullptr;      // [18][C][C] block-permuted K_l and its gradient
-        // first-order level (smp_level_theta.hip; tables of smp_prep.h: th_*): G / dG live in Q, the weight views in Wst / dWst
+        // first-order level (smp_level_theta.hip, smp_field_level.h; tables of smp_prep.h: th_*): G / dG live in Q, the weight views in Wst / dWst
         long long *th_child_ptr = nullptr, *th_src_row = nullptr, *th_pi_off = nullptr, *th_cons_ptr = nullptr, *th_cons_row = nullptr,
                   *th_inv_off = nullptr;
         int *th_src_s = nullptr, *th_cons_s = nullptr, *th_cons_node = nullptr, *th_bucket = nullptr, *th_weight = nullptr;
@@ -340,6 +340,9 @@ constexpr int kFusedMaxField = 64;
 // Constant for the length of a pass, NOT between passes (gf_smp_set_fused, gf_smp_dropout_masks): a sweep asks at its start, keeps nothing.
 enum class LevelKind { OpByOp, Fused18, Gamma, Theta, Steerable2D, Unrestricted };   // Theta: every level of a first-order handle (cfg.first_order), Steerable2D: of a cfg.steerable_2d one, Unrestricted: of a cfg.unrestricted one (asked first), nothing else
 LevelKind smp_level_kind(const gf_smp *s, int l);
+// the kinds on the th_* tables (smp_field_level.h): (namespace gf::field_level holds their kit) they take the read-out's gradient as one vector per node, write df_{l-1} themselves and
+// keep what a second reverse sweep needs
+inline bool is_field_level(LevelKind k) { return k == LevelKind::Theta || k == LevelKind::Steerable2D || k == LevelKind::Unrestricted; }
 bool smp_fused_supported(const gf_smp *s, int l);
 gf_status smp_backward_admissible(const gf_smp *s);   // smp.hip: refusals of a reverse sweep that must come before any work is issued
 gf_status smp_fused_forward_level(gf_smp *s, int l, const float *Kl, const float *bl);
@@ -354,42 +357,46 @@ gf_status smp_fused_gather_backward(gf_smp *s, int l);
 bool smp_gamma_fused(const gf_smp *s, int l);
 gf_status smp_gamma_forward_level(gf_smp *s, int l, const float *Kl, const float *bl);
 gf_status smp_gamma_backward_level(gf_smp *s, int l, const float *Kl, float *dKl, gf_status (*wgrad_done)(gf_smp *, int));
-// First-order levels (SMP_theta, smp_level_theta.hip).  sizes = the level's per-size block (lambda1, lambda2, b[Cc]) x max_nVertices.
-// forward: G = f_{l-1} [K_top | K_bot] on the rows of level l - 1, one gather into f_l (A and B kept).  backward (d.df holds df_l): dz in
-// place, the per-size gradients as segment reductions over the size buckets, dG gathered per source node, dK_l, *wgrad_done, df_{l-1}.
+// The field levels: one pair of signatures.  K / sizes = the level's two parameter blocks, dK / dsizes their gradients (`+=`); backward:
+// d.df holds df_l where rows_too (levels below the top), node_df = the read-out's gradient as one vector per node ([nodes][Cc]) or null;
+// *wgrad_done(s, l) is called by the levels with a matrix product once the level's gradients are final and before df_{l-1} is formed; a
+// level ignores what it does not need.  smp_field_*_level (smp_field_level.hip) pick the file from cfg in smp_level_kind's order.
+gf_status smp_field_forward_level(gf_smp *s, int l, const float *K, const float *sizes);
+gf_status smp_field_backward_level(gf_smp *s, int l, const float *K, const float *sizes, float *dK, float *dsizes, const float *node_df,
+                                   bool rows_too, gf_status (*wgrad_done)(gf_smp *, int));
+// SMP_theta (cfg.first_order = 1, smp_level_theta.hip).  sizes = (lambda1, lambda2, b[Cc]) x max_nVertices, K = K_l [2 Cp][Cc].
+// forward: G = f_{l-1} [K_top | K_bot] on the rows of level l - 1, one gather into f_l (A and B kept).  backward: dz in place, the per-size
+// gradients as segment reductions over the size buckets, dG gathered per source node, dK_l, *wgrad_done, df_{l-1}.
+gf_status smp_theta_forward_level(gf_smp *s, int l, const float *K, const float *sizes);
+gf_status smp_theta_backward_level(gf_smp *s, int l, const float *K, const float *sizes, float *dK, float *dsizes, const float *node_df,
+                                   bool rows_too, gf_status (*wgrad_done)(gf_smp *, int));
+// SMP_1D, SMP_1D_ver2, SMP_1D_ver3 (cfg.first_order = 2, 3, 4; smp_level_1d.hip): the same tables and sizes; K / dK are read by ver3 only
+// (K_eye, K_one).  No GEMM in SMP_1D / ver2; one forward and two backward in ver3.
+gf_status smp_1d_forward_level(gf_smp *s, int l, const float *K, const float *sizes);
+gf_status smp_1d_backward_level(gf_smp *s, int l, const float *K, const float *sizes, float *dK, float *dsizes, const float *node_df,
+                                bool rows_too, gf_status (*wgrad_done)(gf_smp *, int));
+// SMP_2D and SMP_2D_ver4 (cfg.steerable_2d = 1, 2; smp_level_2d.hip): sizes = (lambda1[Cp], lambda2[Cp], b[Cc]) x max_nVertices, K =
+// scalar_l[Cp].  No GEMM.  backward: dS is left in the first Cp columns of d.df.
+gf_status smp_2d_forward_level(gf_smp *s, int l, const float *K, const float *sizes);
+gf_status smp_2d_backward_level(gf_smp *s, int l, const float *K, const float *sizes, float *dK, float *dsizes, const float *node_df,
+                                bool rows_too, gf_status (*wgrad_done)(gf_smp *, int));
+// ... its reduction, shared with SMP_2D_ver5: the column partials in d.th_node over the size buckets into dsizes and dscalar
+gf_status smp_2d_size_grads(gf_smp *s, int l, float *dscalar, float *dsizes);
+// SMP_2D_ver5 (cfg.steerable_2d = 5; smp_level_2d_ver5.hip): K = K_l [C][2 C] then scalar_l[C], sizes as above with Cp = Cc = C.
+// Two small products on the columns and one MFMA row projection per direction, dK_l as chunked MFMA reductions.
+gf_status smp_2d_ver5_forward_level(gf_smp *s, int l, const float *K, const float *sizes);
+gf_status smp_2d_ver5_backward_level(gf_smp *s, int l, const float *K, const float *sizes, float *dK, float *dsizes, const float *node_df,
+                                     bool rows_too, gf_status (*wgrad_done)(gf_smp *, int));
+size_t smp_2d_ver5_wgrad_chunks(long long rows, long long cols);   // partial images of dK_l a level of that many rows and columns writes
+// Unrestricted_SMP_1D, _1D_ver2 and _2D (cfg.unrestricted = 1, 2, 3; smp_level_unrestricted.hip): sizes = (filter_s, b_s[Cc]) x
+// max_nVertices, K = scalar_l[Cp] (form 3, else unused).  No GEMM.  backward: dS is left in d.Q.
+gf_status smp_unrestricted_forward_level(gf_smp *s, int l, const float *K, const float *sizes);
+gf_status smp_unrestricted_backward_level(gf_smp *s, int l, const float *K, const float *sizes, float *dK, float *dsizes, const float *node_df,
+                                          bool rows_too, gf_status (*wgrad_done)(gf_smp *, int));
 // smp_theta_prepare (smp_prepare.hip): gf_smp_prepare of a first-order handle -- the th_* tables, none of the other kinds' buffers.
 gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature);
-gf_status smp_theta_forward_level(gf_smp *s, int l, const float *Kl, const float *sizes);
-// node_df: the read-out's gradient as one vector per node or null; rows_too: d.df holds a per-row gradient as well (levels below the top)
-gf_status smp_theta_backward_level(gf_smp *s, int l, const float *Kl, const float *sizes, float *dKl, float *dsizes, const float *node_df,
-                                   bool rows_too, gf_status (*wgrad_done)(gf_smp *, int));
-// The levels of SMP_1D, SMP_1D_ver2, SMP_1D_ver3 (cfg.first_order = 2, 3, 4; smp_level_1d.hip): the same tables, sizes and arguments; Kl / dKl
-// are read by ver3 only (K_eye, K_one).  No GEMM in SMP_1D / ver2; one forward and two backward in ver3.
-gf_status smp_1d_forward_level(gf_smp *s, int l, const float *Kl, const float *sizes);
-gf_status smp_1d_backward_level(gf_smp *s, int l, const float *Kl, const float *sizes, float *dKl, float *dsizes, const float *node_df,
-                                bool rows_too, gf_status (*wgrad_done)(gf_smp *, int));
-// The levels of SMP_2D and SMP_2D_ver4 (cfg.steerable_2d = 1, 2; smp_level_2d.hip) on the same tables: sizes = the level's per-size block
-// (lambda1[Cp], lambda2[Cp], b[Cc]) x max_nVertices, scalar = scalar_l[Cp].  No GEMM.  backward: node_df = the read-out's gradient as one
-// vector per node or null, rows_too: d.df holds a per-position gradient (levels below the top); dS is left in the first Cp columns of d.df.
-gf_status smp_2d_forward_level(gf_smp *s, int l, const float *scalar, const float *sizes);
-gf_status smp_2d_backward_level(gf_smp *s, int l, const float *scalar, const float *sizes, float *dscalar, float *dsizes, const float *node_df,
-                                bool rows_too);
-// ... its last two steps, shared with SMP_2D_ver5: the column partials in d.th_node over the size buckets into dsizes and dscalar; df_{l-1}
-gf_status smp_2d_size_grads(gf_smp *s, int l, float *dscalar, float *dsizes);
-gf_status smp_2d_gather_down(gf_smp *s, int l);
-// The level of SMP_2D_ver5 (cfg.steerable_2d = 5; smp_level_2d_ver5.hip): Kl = K_l [C][2 C] then scalar_l[C], sizes as above with Cp = Cc = C.
-// Two small products on the columns and one MFMA row projection per direction, dK_l as chunked MFMA reductions; node_df / rows_too as above.
-gf_status smp_2d_ver5_forward_level(gf_smp *s, int l, const float *Kl, const float *sizes);
-gf_status smp_2d_ver5_backward_level(gf_smp *s, int l, const float *Kl, const float *sizes, float *dKl, float *dsizes, const float *node_df,
-                                     bool rows_too);
-size_t smp_2d_ver5_wgrad_chunks(long long rows, long long cols);   // partial images of dK_l a level of that many rows and columns writes
-// The levels of Unrestricted_SMP_1D, _1D_ver2 and _2D (cfg.unrestricted = 1, 2, 3; smp_level_unrestricted.hip) on the same tables: sizes =
-// the level's per-size block (filter_s, b_s[Cc]) x max_nVertices, scalar = scalar_l[Cp] (form 3, else unused).  No GEMM.  backward:
-// node_df / rows_too as above; dS is left in d.Q.
-gf_status smp_unrestricted_forward_level(gf_smp *s, int l, const float *scalar, const float *sizes);
-gf_status smp_unrestricted_backward_level(gf_smp *s, int l, const float *sizes, float *dscalar, float *dsizes, const float *node_df, bool rows_too);
-// the first-order read-out of level l: sh[n] = column sums over the node's s rows (ShrinkMatrix), vf = LeakyReLU(sh); and its reverse,
-// df_l[n][i][:] (+)= dvec[n][:] at every row i of the node, dvec = one gradient vector per node
+// the first-order read-out of level l (smp_field_level.hip): sh[n] = column sums over the node's s rows (ShrinkMatrix), vf = LeakyReLU(sh);
+// and its reverse, df_l[n][i][:] (+)= dvec[n][:] at every row i of the node, dvec = one gradient vector per node
 gf_status smp_theta_readout(gf_smp *s, int l, float *sh, float *vf);
 gf_status smp_theta_readout_backward(gf_smp *s, int l, const float *dvec, int accumulate);
 bool smp_fused_gather_enabled(const gf_smp *s, int l);

@@ -20,10 +20,10 @@
 // The lane vector (4 / 2 / 1 floats) divides Cp, NOT Cc: with Cp = 3 a float2 at columns 2, 3 of a [.][6] row would straddle the halves.
 // Rows of Cp and of 2 Cp floats are then both multiples of the vector.  Every sum runs in a fixed order (children, positions, consumers
 // ascending), no atomics: two runs give the same bits.  Every element of f_l, A, B, acc and df_{l-1} / dG is written by its kernel.
-#include "smp_first_order.h"
+#include "smp_field_level.h"
 
 namespace gf {
-using namespace first_order;
+using namespace field_level;
 namespace {
 
 // Forward: nodes [blockIdx.x * npw, + npw).  Pass 1, items (node j, position i, vector q) over sum_j s_j * Cp / V: the two gathered
@@ -37,19 +37,15 @@ __global__ __launch_bounds__(256) void level1d_fwd(const float *__restrict__ G, 
                                                    const long long *__restrict__ child_ptr, const long long *__restrict__ src_row,
                                                    const long long *__restrict__ pi_off, const short *__restrict__ pi, int Cp, int concat,
                                                    float alpha, int nodes, int npw) {
-    __shared__ int off[kThetaMaxPack + 1];
-    const int nb = blockIdx.x * npw;
-    const int np = nodes - nb < npw ? nodes - nb : npw, Qc = Cp / V, Cc = concat ? 2 * Cp : Cp;
+    __shared__ int off[kMaxPack + 1];
+    const int Qc = Cp / V, Cc = concat ? 2 * Cp : Cp;
     const bool matrix = gs != Cp;
-    int cnt = 0;
-    if ((int)threadIdx.x < np) cnt = node_s[nb + threadIdx.x] * Qc;
-    pack_offsets(off, cnt, np);
-    const int total = off[np];
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-        const int j = pack_find(off, np, it);
-        const int n = nb + j, s = node_s[n];
-        const int r = it - off[j], i = r / Qc, q = r - i * Qc, cq = q * V;
-        Vf<V> a = vzero<V>(), t = vzero<V>();
+    const Run run = pack_run(off, node_s, nodes, npw, Qc);
+    const int nb = run.nb, np = run.np;
+    for (int it = threadIdx.x; it < run.total; it += blockDim.x) {
+        const Item x = pack_item<V>(off, np, it, Qc);
+        const int n = nb + x.j, s = node_s[n], i = x.pos, cq = x.cq;
+        Vf<V> a = vzero<V>(), t = vzero<V>();   // (both halves of a matrix form's G in one walk over the children)
         for (long long e = child_ptr[n]; e < child_ptr[n + 1]; ++e) {
             const int p = pi[pi_off[e] + i];
             if (p < 0) continue;
@@ -64,10 +60,7 @@ __global__ __launch_bounds__(256) void level1d_fwd(const float *__restrict__ G, 
         const float l1 = se[0];
         Vf<V> o;
 #pragma unroll
-        for (int k = 0; k < V; ++k) {
-            const float z = l1 * a.v[k] + se[2 + cq + k];
-            o.v[k] = z > 0.f ? z : alpha * z;
-        }
+        for (int k = 0; k < V; ++k) o.v[k] = lrelu(l1 * a.v[k] + se[2 + cq + k], alpha);
         vst<V>(f + row * Cc + cq, o);
         if (matrix) vst<V>(f + row * Cc + Cp + cq, t);
     }
@@ -86,20 +79,14 @@ __global__ __launch_bounds__(256) void level1d_fwd(const float *__restrict__ G, 
         if (concat) {
             Vf<V> o;
 #pragma unroll
-            for (int k = 0; k < V; ++k) {
-                const float z = l2 * b.v[k] + se[2 + Cp + cq + k];
-                o.v[k] = z > 0.f ? z : alpha * z;
-            }
+            for (int k = 0; k < V; ++k) o.v[k] = lrelu(l2 * b.v[k] + se[2 + Cp + cq + k], alpha);
             for (int i = 0; i < s; ++i) vst<V>(f + (r0 + i) * Cc + Cp + cq, o);
         } else {
             for (int i = 0; i < s; ++i) {
                 const Vf<V> a = vld<V>(A + (r0 + i) * Cp + cq);
                 Vf<V> o;
 #pragma unroll
-                for (int k = 0; k < V; ++k) {
-                    const float z = (l1 * a.v[k] + l2 * b.v[k]) + se[2 + cq + k];
-                    o.v[k] = z > 0.f ? z : alpha * z;
-                }
+                for (int k = 0; k < V; ++k) o.v[k] = lrelu((l1 * a.v[k] + l2 * b.v[k]) + se[2 + cq + k], alpha);
                 vst<V>(f + (r0 + i) * Cc + cq, o);
             }
         }
@@ -131,14 +118,8 @@ __global__ __launch_bounds__(256) void level1d_node_bwd(const float *__restrict_
         if (dvec) dv = vld<V>(dvec + (long long)n * Cc + c0);
         for (int i = 0; i < s; ++i) {
             const long long o = (r0 + i) * Cc + c0;
-            const Vf<V> fv = vld<V>(f + o);
-            Vf<V> d = dv;
-            if (has_df) vadd(d, vld<V>(df + o));
-#pragma unroll
-            for (int k = 0; k < V; ++k) {
-                d.v[k] *= fv.v[k] > 0.f ? 1.f : alpha;
-                zs[h].v[k] += d.v[k];
-            }
+            const Vf<V> d = dz_of<V>(f, df, o, dv, has_df, alpha);
+            vadd(zs[h], d);
             if (h == 0) {
                 const Vf<V> av = vld<V>(A + (r0 + i) * Cp + cq);
 #pragma unroll
@@ -172,17 +153,12 @@ __global__ __launch_bounds__(256) void level1d_gather_bwd(const float *__restric
                                                           const long long *__restrict__ cons_row, const int *__restrict__ cons_s,
                                                           const int *__restrict__ cons_node, const long long *__restrict__ inv_off,
                                                           const short *__restrict__ inv, int Cp, int concat, int split, int nodes, int npw) {
-    __shared__ int off[kThetaMaxPack + 1];
-    const int wb = blockIdx.x * npw;
-    const int np = nodes - wb < npw ? nodes - wb : npw, Qc = Cp / V, Cc = concat ? 2 * Cp : Cp, bot = concat ? Cp : 0;
-    int cnt = 0;
-    if ((int)threadIdx.x < np) cnt = prev_s[wb + threadIdx.x] * Qc;
-    pack_offsets(off, cnt, np);
-    const int total = off[np];
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-        const int j = pack_find(off, np, it);
-        const int w = wb + j;
-        const int r = it - off[j], p = r / Qc, q = r - p * Qc, cq = q * V;
+    __shared__ int off[kMaxPack + 1];
+    const int Cc = concat ? 2 * Cp : Cp, bot = concat ? Cp : 0;
+    const Run run = pack_run(off, prev_s, nodes, npw, Cp / V);
+    for (int it = threadIdx.x; it < run.total; it += blockDim.x) {
+        const Item x = pack_item<V>(off, run.np, it, Cp / V);
+        const int w = run.nb + x.j, p = x.pos, cq = x.cq;
         Vf<V> gt = vzero<V>(), gb = vzero<V>();
         for (long long c = cons_ptr[w]; c < cons_ptr[w + 1]; ++c) {
             const int i = inv[inv_off[c] + p];
@@ -215,26 +191,33 @@ gf_status smp_1d_forward_level(gf_smp *s, int l, const float *Kl, const float *s
     const gf_smp::DevLevel &d = s->lv[l], &pv = s->lv[l - 1];
     const int Cp = s->cfg.level_channels(l - 1), concat = s->cfg.concat() ? 1 : 0;
     const bool matrix = s->cfg.first_order == 4;
-    const long long rows_p = s->lay.level[l - 1].rows, rows = s->lay.level[l].rows;
-    const int nodes = s->lay.level[l].nNodes, V = theta_vec(Cp);
+    const long long rows_p = s->lay.level[l - 1].rows;
+    const int nodes = s->lay.level[l].nNodes, V = lane_vector(Cp);
     if (matrix) {
-        gf_status st = smp_theta_weight_views(ctx, Kl, d.Wst, d.Wst + (size_t)2 * Cp * Cp, Cp, Cp);
+        gf_status st = smp_field_weight_views(ctx, Kl, d.Wst, d.Wst + (size_t)2 * Cp * Cp, Cp, Cp);
         if (st == GF_OK) st = gemm(ctx, false, false, (int)rows_p, 2 * Cp, Cp, pv.f, Cp, 0, d.Wst, 2 * Cp, 0, d.Q, 2 * Cp, 0, 1, 0);
         if (st != GF_OK) return st;
     }
     if (nodes == 0) return GF_OK;
-    const int npw = theta_pack((double)rows / (double)nodes * (Cp / V));
-    const dim3 grid((unsigned)((nodes + npw - 1) / npw));
-#define GF_1D_FWD(V) GF_LAUNCH(ctx, "smp1d_level_fwd", level1d_fwd<V>, grid, dim3(256), 0, matrix ? d.Q : pv.f, matrix ? 2 * Cp : Cp, sizes, d.f, d.th_A, \
-                               d.th_B, d.node_s, d.node_row, d.th_child_ptr, d.th_src_row, d.th_pi_off, d.th_pi, Cp, concat, s->cfg.level_slope(),  \
-                               nodes, npw)
-    switch (V) {
-        case 4: GF_1D_FWD(4); break;
-        case 2: GF_1D_FWD(2); break;
-        default: GF_1D_FWD(1); break;
-    }
-#undef GF_1D_FWD
-    return GF_OK;
+    const RunGrid g = run_grid(s->lay.level[l], false, Cp / V);
+    return with_lane_vector(V, [&](auto v) -> gf_status {
+        GF_LAUNCH(ctx, "smp1d_level_fwd", level1d_fwd<v>, g.grid, dim3(256), 0, matrix ? d.Q : pv.f, matrix ? 2 * Cp : Cp, sizes, d.f, d.th_A, d.th_B,
+                  d.node_s, d.node_row, d.th_child_ptr, d.th_src_row, d.th_pi_off, d.th_pi, Cp, concat, s->cfg.level_slope(), nodes, g.npw);
+        return GF_OK;
+    });
+}
+
+// The reverse gather of level l at Cp channels per half under the caller's timer name: out = df_{l-1} [rows][Cp], or split: dG
+// [rows][2 Cp].  smp_level_theta.hip launches it too (Cp := its Cc, concat = 0, split).
+gf_status smp_1d_gather_bwd(gf_smp *s, int l, const char *timer, const float *sizes, int Cp, int concat, bool split, float *out) {
+    const gf_smp::DevLevel &d = s->lv[l], &pv = s->lv[l - 1];
+    const int np = s->lay.level[l - 1].nNodes, V = lane_vector(Cp);
+    const RunGrid g = run_grid(s->lay.level[l - 1], false, Cp / V);
+    return with_lane_vector(V, [&](auto v) -> gf_status {
+        GF_LAUNCH(s->ctx, timer, level1d_gather_bwd<v>, g.grid, dim3(256), 0, d.df, d.th_node, sizes, out, pv.node_s, pv.node_row, d.th_cons_ptr,
+                  d.th_cons_row, d.th_cons_s, d.th_cons_node, d.th_inv_off, d.th_inv, Cp, concat, split ? 1 : 0, np, g.npw);
+        return GF_OK;
+    });
 }
 
 // node_df / rows_too / wgrad_done as smp_theta_backward_level.  The per-size gradients are final after the reduction, ver3's dK after
@@ -246,42 +229,25 @@ gf_status smp_1d_backward_level(gf_smp *s, int l, const float *Kl, const float *
     const int Cp = s->cfg.level_channels(l - 1), Cc = s->cfg.level_channels(l), concat = s->cfg.concat() ? 1 : 0;
     const bool matrix = s->cfg.first_order == 4;
     const long long rows_p = s->lay.level[l - 1].rows;
-    const int nodes = s->lay.level[l].nNodes, np = s->lay.level[l - 1].nNodes, V = theta_vec(Cp);
     const int nbuckets = (int)(s->lay.level[l].th_bucket.size() / 3);
-    const float alpha = s->cfg.level_slope();
     if (!node_df && !rows_too) return fail(ctx, GF_ERR_INVALID, "first-order level %d: no gradient to back-propagate", l);
     gf_status st = GF_OK;
-    if (nodes > 0) {
-        const dim3 grid(grid_for((size_t)nodes * (Cp / V)));
-#define GF_1D_NODE(V) GF_LAUNCH(ctx, "smp1d_node_bwd", level1d_node_bwd<V>, grid, dim3(256), 0, d.f, d.df, node_df, d.th_A, d.th_B, d.th_node, d.node_s, \
-                                d.node_row, d.th_weight, Cp, concat, alpha, nodes, rows_too ? 1 : 0)
-        switch (V) {
-            case 4: GF_1D_NODE(4); break;
-            case 2: GF_1D_NODE(2); break;
-            default: GF_1D_NODE(1); break;
-        }
-#undef GF_1D_NODE
-        st = smp_theta_size_grads(ctx, d.th_node, d.th_bucket, nbuckets, dsizes, Cc);
-        if (st != GF_OK) return st;
+    if (s->lay.level[l].nNodes > 0) {
+        const int nodes = s->lay.level[l].nNodes, V = lane_vector(Cp);
+        st = with_lane_vector(V, [&](auto v) -> gf_status {
+            GF_LAUNCH(ctx, "smp1d_node_bwd", level1d_node_bwd<v>, dim3(grid_for((size_t)nodes * (Cp / V))), dim3(256), 0, d.f, d.df, node_df, d.th_A,
+                      d.th_B, d.th_node, d.node_s, d.node_row, d.th_weight, Cp, concat, s->cfg.level_slope(), nodes, rows_too ? 1 : 0);
+            return GF_OK;
+        });
+        if (st == GF_OK) st = smp_field_size_grads(ctx, d.th_node, d.th_bucket, nbuckets, dsizes, Cc);
     }
-    if (np > 0) {
-        const int npw = theta_pack((double)rows_p / (double)np * (Cp / V));
-        const dim3 grid((unsigned)((np + npw - 1) / npw));
-#define GF_1D_BWD(V) GF_LAUNCH(ctx, "smp1d_gather_bwd", level1d_gather_bwd<V>, grid, dim3(256), 0, d.df, d.th_node, sizes, matrix ? d.Q : pv.df, pv.node_s, \
-                               pv.node_row, d.th_cons_ptr, d.th_cons_row, d.th_cons_s, d.th_cons_node, d.th_inv_off, d.th_inv, Cp, concat,           \
-                               matrix ? 1 : 0, np, npw)
-        switch (V) {
-            case 4: GF_1D_BWD(4); break;
-            case 2: GF_1D_BWD(2); break;
-            default: GF_1D_BWD(1); break;
-        }
-#undef GF_1D_BWD
-    }
+    if (st == GF_OK && s->lay.level[l - 1].nNodes > 0) st = smp_1d_gather_bwd(s, l, "smp1d_gather_bwd", sizes, Cp, concat, matrix, matrix ? d.Q : pv.df);
+    if (st != GF_OK) return st;
     if (!matrix) return wgrad_done(s, l);
     // (the views again: this sweep's parameters need not be the forward's)
-    st = smp_theta_weight_views(ctx, Kl, d.Wst, d.Wst + (size_t)2 * Cp * Cp, Cp, Cp);
+    st = smp_field_weight_views(ctx, Kl, d.Wst, d.Wst + (size_t)2 * Cp * Cp, Cp, Cp);
     if (st == GF_OK) st = gemm(ctx, true, false, Cp, 2 * Cp, (int)rows_p, pv.f, Cp, 0, d.Q, 2 * Cp, 0, d.dWst, 2 * Cp, 0, 1, 0);
-    if (st == GF_OK) st = smp_theta_wgrad_fold(ctx, d.dWst, dKl, Cp, Cp);
+    if (st == GF_OK) st = smp_field_wgrad_fold(ctx, d.dWst, dKl, Cp, Cp);
     if (st == GF_OK) st = wgrad_done(s, l);
     if (st != GF_OK) return st;
     return gemm(ctx, false, false, (int)rows_p, Cp, 2 * Cp, d.Q, 2 * Cp, 0, d.Wst + (size_t)2 * Cp * Cp, Cp, 0, pv.df, Cp, 0, 1, 0);

@@ -21,16 +21,13 @@
 // The lane vector (4 / 2 / 1 floats) divides Cp.  Every sum runs in a fixed order (children, rows, consumers ascending; the reductions
 // fold fixed chunks in order), no atomics: two runs give the same bits.  Every element of f_l, S, col, the partials and df_{l-1} is
 // written by its kernel before anything reads it.
-#include "smp_first_order.h"
+#include "smp_field_level.h"
 
 namespace gf {
-using namespace first_order;
+using namespace field_level;
 namespace {
 
 constexpr int kSplit2d = 16;   // row chunks per size bucket in the reduction of the column partials
-
-// the per-size entry of a steerable level: lambda1[Cp], lambda2[Cp], b[Cc]
-__device__ __forceinline__ const float *size_entry_2d(const float *sizes, int s, int Cp, int Cc) { return sizes + (size_t)(s - 1) * (2 * Cp + Cc); }
 
 // Forward: nodes [blockIdx.x * npw, + npw); items (node, column j, vector q) over sum s * Cp / V.  Pass 1 over the rows i: S[i][j] gathered,
 // stored, summed into col[j]; the top half of f_l in the concatenating form.  Pass 2: what needs col[j].  S is read back by the lane
@@ -43,29 +40,18 @@ __global__ __launch_bounds__(256) void level2d_fwd(const float *__restrict__ fp,
                                                    const long long *__restrict__ src_row, const int *__restrict__ src_s,
                                                    const long long *__restrict__ pi_off, const short *__restrict__ pi, int Cp, int concat,
                                                    float alpha, int nodes, int npw) {
-    __shared__ int off[kThetaMaxPack + 1];
-    const int nb = blockIdx.x * npw;
-    const int np = nodes - nb < npw ? nodes - nb : npw, Qc = Cp / V, Cc = concat ? 2 * Cp : Cp;
-    int cnt = 0;
-    if ((int)threadIdx.x < np) cnt = node_s[nb + threadIdx.x] * Qc;
-    pack_offsets(off, cnt, np);
-    const int total = off[np];
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-        const int k = pack_find(off, np, it);
-        const int n = nb + k, s = node_s[n];
-        const int r = it - off[k], j = r / Qc, cq = (r - j * Qc) * V;
+    __shared__ int off[kMaxPack + 1];
+    const int Cc = concat ? 2 * Cp : Cp;
+    const Run run = pack_run(off, node_s, nodes, npw, Cp / V);
+    for (int it = threadIdx.x; it < run.total; it += blockDim.x) {
+        const Item x = pack_item<V>(off, run.np, it, Cp / V);
+        const int n = run.nb + x.j, s = node_s[n], j = x.pos, cq = x.cq;
         const long long r0 = node_row[n], e0 = child_ptr[n], e1 = child_ptr[n + 1];
         const float *se = size_entry_2d(sizes, s, Cp, Cc);
         const Vf<V> l1 = vld<V>(se + cq), l2 = vld<V>(se + Cp + cq), bt = vld<V>(se + 2 * Cp + cq), sc = vld<V>(scalar + cq);
         Vf<V> cs = vzero<V>();
         for (int i = 0; i < s; ++i) {
-            Vf<V> a = vzero<V>();
-            for (long long e = e0; e < e1; ++e) {
-                const short *pe = pi + pi_off[e];
-                const int p = pe[i], q = pe[j];
-                if (p < 0 || q < 0) continue;
-                vadd(a, vld<V>(fp + (src_row[e] + (long long)p * src_s[e] + q) * Cp + cq));
-            }
+            Vf<V> a = gather_pair<V>(fp, Cp, cq, e0, e1, src_row, src_s, pi_off, pi, i, j);
             const long long row = r0 + (long long)i * s + j;
             const float av = adj[row];
 #pragma unroll
@@ -75,10 +61,7 @@ __global__ __launch_bounds__(256) void level2d_fwd(const float *__restrict__ fp,
             if (concat) {
                 Vf<V> o;
 #pragma unroll
-                for (int c = 0; c < V; ++c) {
-                    const float z = l1.v[c] * a.v[c] + bt.v[c];
-                    o.v[c] = z > 0.f ? z : alpha * z;
-                }
+                for (int c = 0; c < V; ++c) o.v[c] = lrelu(l1.v[c] * a.v[c] + bt.v[c], alpha);
                 vst<V>(f + row * Cc + cq, o);
             }
         }
@@ -87,10 +70,7 @@ __global__ __launch_bounds__(256) void level2d_fwd(const float *__restrict__ fp,
             const Vf<V> bb = vld<V>(se + 3 * Cp + cq);
             Vf<V> o;
 #pragma unroll
-            for (int c = 0; c < V; ++c) {
-                const float z = l2.v[c] * cs.v[c] + bb.v[c];
-                o.v[c] = z > 0.f ? z : alpha * z;
-            }
+            for (int c = 0; c < V; ++c) o.v[c] = lrelu(l2.v[c] * cs.v[c] + bb.v[c], alpha);
             for (int i = 0; i < s; ++i) vst<V>(f + (r0 + (long long)i * s + j) * Cc + Cp + cq, o);
         } else {
             for (int i = 0; i < s; ++i) {
@@ -98,10 +78,7 @@ __global__ __launch_bounds__(256) void level2d_fwd(const float *__restrict__ fp,
                 const Vf<V> a = vld<V>(S + row * Cp + cq);
                 Vf<V> o;
 #pragma unroll
-                for (int c = 0; c < V; ++c) {
-                    const float z = (l1.v[c] * a.v[c] + l2.v[c] * cs.v[c]) + bt.v[c];
-                    o.v[c] = z > 0.f ? z : alpha * z;
-                }
+                for (int c = 0; c < V; ++c) o.v[c] = lrelu((l1.v[c] * a.v[c] + l2.v[c] * cs.v[c]) + bt.v[c], alpha);
                 vst<V>(f + row * Cc + cq, o);
             }
         }
@@ -119,17 +96,12 @@ __global__ __launch_bounds__(256) void level2d_node_bwd(const float *__restrict_
                                                         const long long *__restrict__ node_row, const long long *__restrict__ node_pair,
                                                         const int *__restrict__ weight, int Cp, int concat, float alpha, int nodes, int npw,
                                                         int has_df) {
-    __shared__ int off[kThetaMaxPack + 1];
-    const int nb = blockIdx.x * npw;
-    const int np = nodes - nb < npw ? nodes - nb : npw, Qc = Cp / V, Cc = concat ? 2 * Cp : Cp, Wd = Cc + 3 * Cp;
-    int cnt = 0;
-    if ((int)threadIdx.x < np) cnt = node_s[nb + threadIdx.x] * Qc;
-    pack_offsets(off, cnt, np);
-    const int total = off[np];
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-        const int k = pack_find(off, np, it);
-        const int n = nb + k, s = node_s[n];
-        const int r = it - off[k], j = r / Qc, cq = (r - j * Qc) * V;
+    __shared__ int off[kMaxPack + 1];
+    const int Cc = concat ? 2 * Cp : Cp, Wd = Cc + 3 * Cp;
+    const Run run = pack_run(off, node_s, nodes, npw, Cp / V);
+    for (int it = threadIdx.x; it < run.total; it += blockDim.x) {
+        const Item x = pack_item<V>(off, run.np, it, Cp / V);
+        const int n = run.nb + x.j, s = node_s[n], j = x.pos, cq = x.cq;
         const long long r0 = node_row[n];
         const float *se = size_entry_2d(sizes, s, Cp, Cc);
         const Vf<V> l1 = vld<V>(se + cq), l2 = vld<V>(se + Cp + cq);
@@ -141,11 +113,7 @@ __global__ __launch_bounds__(256) void level2d_node_bwd(const float *__restrict_
             if (dvec) dv = vld<V>(dvec + (long long)n * Cc + Cp + cq);
             for (int i = 0; i < s; ++i) {
                 const long long o = (r0 + (long long)i * s + j) * Cc + Cp + cq;
-                const Vf<V> fv = vld<V>(f + o);
-                Vf<V> d = dv;
-                if (has_df) vadd(d, vld<V>(df + o));
-#pragma unroll
-                for (int c = 0; c < V; ++c) cz.v[c] += d.v[c] * (fv.v[c] > 0.f ? 1.f : alpha);
+                vadd(cz, dz_of<V>(f, df, o, dv, has_df, alpha));
             }
             vst<V>(pr + Cp + cq, cz);
         }
@@ -153,12 +121,10 @@ __global__ __launch_bounds__(256) void level2d_node_bwd(const float *__restrict_
         if (dvec) dv = vld<V>(dvec + (long long)n * Cc + cq);
         for (int i = 0; i < s; ++i) {
             const long long row = r0 + (long long)i * s + j, o = row * Cc + cq;
-            const Vf<V> fv = vld<V>(f + o), sv = vld<V>(S + row * Cp + cq);
-            Vf<V> d = dv;
-            if (has_df) vadd(d, vld<V>(df + o));
+            const Vf<V> sv = vld<V>(S + row * Cp + cq);
+            Vf<V> d = dz_of<V>(f, df, o, dv, has_df, alpha);
 #pragma unroll
             for (int c = 0; c < V; ++c) {
-                d.v[c] *= fv.v[c] > 0.f ? 1.f : alpha;
                 zs.v[c] += d.v[c];
                 pa.v[c] += d.v[c] * sv.v[c];
             }
@@ -251,41 +217,6 @@ __global__ __launch_bounds__(256) void level2d_grads_finish(const float *__restr
     }
 }
 
-// Reverse gather: source nodes [blockIdx.x * npw, + npw) of level l - 1; items (node, column q of the source, vector) over sum s_w Cp / V,
-// walking the source's rows p.  dS rows are Cc floats apart (its first Cp columns), df_{l-1} rows Cp.
-template <int V>
-__global__ __launch_bounds__(256) void level2d_gather_bwd(const float *__restrict__ dS, float *__restrict__ out, const int *__restrict__ prev_s,
-                                                          const long long *__restrict__ prev_row, const long long *__restrict__ cons_ptr,
-                                                          const long long *__restrict__ cons_row, const int *__restrict__ cons_s,
-                                                          const long long *__restrict__ inv_off, const short *__restrict__ inv, int Cp, int Cc,
-                                                          int nodes, int npw) {
-    __shared__ int off[kThetaMaxPack + 1];
-    const int wb = blockIdx.x * npw;
-    const int np = nodes - wb < npw ? nodes - wb : npw, Qc = Cp / V;
-    int cnt = 0;
-    if ((int)threadIdx.x < np) cnt = prev_s[wb + threadIdx.x] * Qc;
-    pack_offsets(off, cnt, np);
-    const int total = off[np];
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-        const int k = pack_find(off, np, it);
-        const int w = wb + k, sw = prev_s[w];
-        const int r = it - off[k], q = r / Qc, cq = (r - q * Qc) * V;
-        const long long c0 = cons_ptr[w], c1 = cons_ptr[w + 1], r0 = prev_row[w];
-        for (int p = 0; p < sw; ++p) {
-            Vf<V> g = vzero<V>();
-            for (long long c = c0; c < c1; ++c) {
-                const short *ie = inv + inv_off[c];
-                const int i = ie[p], j = ie[q];
-                if (i < 0 || j < 0) continue;
-                vadd(g, vld<V>(dS + (cons_row[c] + (long long)i * cons_s[c] + j) * Cc + cq));
-            }
-            vst<V>(out + (r0 + (long long)p * sw + q) * Cp + cq, g);
-        }
-    }
-}
-
-inline long long level_columns(const gfsmp::LevelLayout &h) { return h.nNodes ? (long long)(h.node_pair.back() + h.node_s.back()) : 0; }   // sum s
-
 }  // namespace
 
 // f_l from f_{l-1}: one launch
@@ -293,46 +224,35 @@ gf_status smp_2d_forward_level(gf_smp *s, int l, const float *scalar, const floa
     gf_ctx *ctx = s->ctx;
     const gf_smp::DevLevel &d = s->lv[l], &pv = s->lv[l - 1];
     const int Cp = s->cfg.level_channels(l - 1), concat = s->cfg.concat() ? 1 : 0;
-    const int nodes = s->lay.level[l].nNodes, V = theta_vec(Cp);
+    const int nodes = s->lay.level[l].nNodes, V = lane_vector(Cp);
     if (nodes == 0) return GF_OK;
-    const int npw = theta_pack((double)level_columns(s->lay.level[l]) / (double)nodes * (Cp / V));
-    const dim3 grid((unsigned)((nodes + npw - 1) / npw));
-#define GF_2D_FWD(V) GF_LAUNCH(ctx, "smp2d_level_fwd", level2d_fwd<V>, grid, dim3(256), 0, pv.f, sizes, scalar, d.adj, d.f, d.th_A, d.th_B, d.node_s, \
-                               d.node_row, d.node_pair, d.th_child_ptr, d.th_src_row, d.th_src_s, d.th_pi_off, d.th_pi, Cp, concat,               \
-                               s->cfg.level_slope(), nodes, npw)
-    switch (V) {
-        case 4: GF_2D_FWD(4); break;
-        case 2: GF_2D_FWD(2); break;
-        default: GF_2D_FWD(1); break;
-    }
-#undef GF_2D_FWD
-    return GF_OK;
+    const RunGrid g = run_grid(s->lay.level[l], true, Cp / V);
+    return with_lane_vector(V, [&](auto v) -> gf_status {
+        GF_LAUNCH(ctx, "smp2d_level_fwd", level2d_fwd<v>, g.grid, dim3(256), 0, pv.f, sizes, scalar, d.adj, d.f, d.th_A, d.th_B, d.node_s, d.node_row,
+                  d.node_pair, d.th_child_ptr, d.th_src_row, d.th_src_s, d.th_pi_off, d.th_pi, Cp, concat, s->cfg.level_slope(), nodes, g.npw);
+        return GF_OK;
+    });
 }
 
-// dz and dS per node, the per-size gradients and dscalar_l over the buckets, then df_{l-1}
-gf_status smp_2d_backward_level(gf_smp *s, int l, const float *scalar, const float *sizes, float *dscalar, float *dsizes, const float *node_df,
-                                bool rows_too) {
-    (void)scalar;
+// dz and dS per node, the per-size gradients and dscalar_l over the buckets, then df_{l-1}.  (scalar_l itself and wgrad_done: not needed)
+gf_status smp_2d_backward_level(gf_smp *s, int l, const float *, const float *sizes, float *dscalar, float *dsizes, const float *node_df,
+                                bool rows_too, gf_status (*)(gf_smp *, int)) {
     gf_ctx *ctx = s->ctx;
     const gf_smp::DevLevel &d = s->lv[l];
     const int Cp = s->cfg.level_channels(l - 1), concat = s->cfg.concat() ? 1 : 0;
-    const int nodes = s->lay.level[l].nNodes, V = theta_vec(Cp);
+    const int nodes = s->lay.level[l].nNodes, V = lane_vector(Cp);
     if (!node_df && !rows_too) return fail(ctx, GF_ERR_INVALID, "steerable level %d: no gradient to back-propagate", l);
     if (nodes > 0) {
-        const int npw = theta_pack((double)level_columns(s->lay.level[l]) / (double)nodes * (Cp / V));
-        const dim3 grid((unsigned)((nodes + npw - 1) / npw));
-#define GF_2D_NODE(V) GF_LAUNCH(ctx, "smp2d_node_bwd", level2d_node_bwd<V>, grid, dim3(256), 0, d.f, d.df, node_df, d.th_A, d.th_B, sizes, d.adj, d.th_node, \
-                                d.node_s, d.node_row, d.node_pair, d.th_weight, Cp, concat, s->cfg.level_slope(), nodes, npw, rows_too ? 1 : 0)
-        switch (V) {
-            case 4: GF_2D_NODE(4); break;
-            case 2: GF_2D_NODE(2); break;
-            default: GF_2D_NODE(1); break;
-        }
-#undef GF_2D_NODE
-        const gf_status st = smp_2d_size_grads(s, l, dscalar, dsizes);
+        const RunGrid g = run_grid(s->lay.level[l], true, Cp / V);
+        gf_status st = with_lane_vector(V, [&](auto v) -> gf_status {
+            GF_LAUNCH(ctx, "smp2d_node_bwd", level2d_node_bwd<v>, g.grid, dim3(256), 0, d.f, d.df, node_df, d.th_A, d.th_B, sizes, d.adj, d.th_node,
+                      d.node_s, d.node_row, d.node_pair, d.th_weight, Cp, concat, s->cfg.level_slope(), nodes, g.npw, rows_too ? 1 : 0);
+            return GF_OK;
+        });
+        if (st == GF_OK) st = smp_2d_size_grads(s, l, dscalar, dsizes);
         if (st != GF_OK) return st;
     }
-    return smp_2d_gather_down(s, l);
+    return smp_field_gather_down(s, l, d.df, s->cfg.level_channels(l), true, "smp2d_gather_bwd");
 }
 
 // The column partials in d.th_node ([sum s][Cc + 3 Cp]) over the size buckets: `+=` into the per-size entries and dscalar_l
@@ -345,26 +265,6 @@ gf_status smp_2d_size_grads(gf_smp *s, int l, float *dscalar, float *dsizes) {
               d.node_pair, d.part2d, Cc + 3 * Cp);
     GF_LAUNCH(ctx, "smp2d_grads_finish", level2d_grads_finish, dim3((unsigned)nbuckets + 1), dim3(256), 0, d.part2d, d.th_bucket, dsizes, dscalar, Cp,
               Cc, nbuckets);
-    return GF_OK;
-}
-
-// df_{l-1} gathered from dS (the first Cp columns of d.df's rows)
-gf_status smp_2d_gather_down(gf_smp *s, int l) {
-    gf_ctx *ctx = s->ctx;
-    const gf_smp::DevLevel &d = s->lv[l], &pv = s->lv[l - 1];
-    const int Cp = s->cfg.level_channels(l - 1), Cc = s->cfg.level_channels(l), np = s->lay.level[l - 1].nNodes, V = theta_vec(Cp);
-    if (np > 0) {
-        const int npw = theta_pack((double)level_columns(s->lay.level[l - 1]) / (double)np * (Cp / V));
-        const dim3 grid((unsigned)((np + npw - 1) / npw));
-#define GF_2D_BWD(V) GF_LAUNCH(ctx, "smp2d_gather_bwd", level2d_gather_bwd<V>, grid, dim3(256), 0, d.df, pv.df, pv.node_s, pv.node_row, d.th_cons_ptr, \
-                               d.th_cons_row, d.th_cons_s, d.th_inv_off, d.th_inv, Cp, Cc, np, npw)
-        switch (V) {
-            case 4: GF_2D_BWD(4); break;
-            case 2: GF_2D_BWD(2); break;
-            default: GF_2D_BWD(1); break;
-        }
-#undef GF_2D_BWD
-    }
     return GF_OK;
 }
 

@@ -15,10 +15,10 @@
 // K_l is ONE node of the reference's graph (added in the preamble) and every vertex's CustomMatMulTensor adds into K_l->gradient itself:
 // dK_l is the plain derivative, unlike dlambda (th_weight = j, through the shared W_eye[s] / W_one[s]).
 // fp32 operands and accumulation throughout; no atomics, every sum in a fixed order; every buffer written before it is read.
-#include "smp_first_order.h"
+#include "smp_field_level.h"
 
 namespace gf {
-using namespace first_order;
+using namespace field_level;
 namespace {
 
 typedef float f16v __attribute__((ext_vector_type(16)));
@@ -27,8 +27,6 @@ typedef float f4v __attribute__((ext_vector_type(4)));
 constexpr int kV5Chunk = 512;    // rows (columns) per partial image of dK1 (dK2): a level of n rows writes ceil(n / kV5Chunk) images
 constexpr int kV5Steps = 8;      // MFMA steps of two rows whose operands a wave of wgrad loads together
 constexpr int kV5FoldGroups = 16;   // runs of consecutive partial images the fold sums side by side before it adds the runs in order
-
-__device__ __forceinline__ const float *size_entry_v5(const float *sizes, int s, int C) { return sizes + (size_t)(s - 1) * (3 * C); }
 
 // Pass 1 of smp_level_2d.hip's forward, storing only: items (node, column j, vector q); S[i][j] gathered, + scalar adj, stored and summed
 // into col[j].  Also the tables the projections read: row_cs[row] = (column index, s) by the lane of the row's first vector, col_s[column].
@@ -39,28 +37,16 @@ __global__ __launch_bounds__(256) void v5_store_S(const float *__restrict__ fp, 
                                                   const long long *__restrict__ node_pair, const long long *__restrict__ child_ptr,
                                                   const long long *__restrict__ src_row, const int *__restrict__ src_s,
                                                   const long long *__restrict__ pi_off, const short *__restrict__ pi, int C, int nodes, int npw) {
-    __shared__ int off[kThetaMaxPack + 1];
-    const int nb = blockIdx.x * npw;
-    const int np = nodes - nb < npw ? nodes - nb : npw, Qc = C / V;
-    int cnt = 0;
-    if ((int)threadIdx.x < np) cnt = node_s[nb + threadIdx.x] * Qc;
-    pack_offsets(off, cnt, np);
-    const int total = off[np];
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-        const int k = pack_find(off, np, it);
-        const int n = nb + k, s = node_s[n];
-        const int r = it - off[k], j = r / Qc, cq = (r - j * Qc) * V;
+    __shared__ int off[kMaxPack + 1];
+    const Run run = pack_run(off, node_s, nodes, npw, C / V);
+    for (int it = threadIdx.x; it < run.total; it += blockDim.x) {
+        const Item x = pack_item<V>(off, run.np, it, C / V);
+        const int n = run.nb + x.j, s = node_s[n], j = x.pos, cq = x.cq;
         const long long r0 = node_row[n], e0 = child_ptr[n], e1 = child_ptr[n + 1], cj = node_pair[n] + j;
         const Vf<V> sc = vld<V>(scalar + cq);
         Vf<V> cs = vzero<V>();
         for (int i = 0; i < s; ++i) {
-            Vf<V> a = vzero<V>();
-            for (long long e = e0; e < e1; ++e) {
-                const short *pe = pi + pi_off[e];
-                const int p = pe[i], q = pe[j];
-                if (p < 0 || q < 0) continue;
-                vadd(a, vld<V>(fp + (src_row[e] + (long long)p * src_s[e] + q) * C + cq));
-            }
+            Vf<V> a = gather_pair<V>(fp, C, cq, e0, e1, src_row, src_s, pi_off, pi, i, j);
             const long long row = r0 + (long long)i * s + j;
             const float av = adj[row];
 #pragma unroll
@@ -203,30 +189,18 @@ template <int V>
 __global__ __launch_bounds__(256) void v5_dz(const float *__restrict__ f, float *df, const float *__restrict__ dvec, float *__restrict__ part,
                                              const int *__restrict__ node_s, const long long *__restrict__ node_row,
                                              const long long *__restrict__ node_pair, int C, float alpha, int nodes, int npw, int has_df) {
-    __shared__ int off[kThetaMaxPack + 1];
-    const int nb = blockIdx.x * npw;
-    const int np = nodes - nb < npw ? nodes - nb : npw, Qc = C / V;
-    int cnt = 0;
-    if ((int)threadIdx.x < np) cnt = node_s[nb + threadIdx.x] * Qc;
-    pack_offsets(off, cnt, np);
-    const int total = off[np];
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-        const int k = pack_find(off, np, it);
-        const int n = nb + k, s = node_s[n];
-        const int r = it - off[k], j = r / Qc, cq = (r - j * Qc) * V;
+    __shared__ int off[kMaxPack + 1];
+    const Run run = pack_run(off, node_s, nodes, npw, C / V);
+    for (int it = threadIdx.x; it < run.total; it += blockDim.x) {
+        const Item x = pack_item<V>(off, run.np, it, C / V);
+        const int n = run.nb + x.j, s = node_s[n], j = x.pos, cq = x.cq;
         const long long r0 = node_row[n];
         Vf<V> dv = vzero<V>(), cz = vzero<V>();
         if (dvec) dv = vld<V>(dvec + (long long)n * C + cq);
         for (int i = 0; i < s; ++i) {
             const long long o = (r0 + (long long)i * s + j) * C + cq;
-            const Vf<V> fv = vld<V>(f + o);
-            Vf<V> d = dv;
-            if (has_df) vadd(d, vld<V>(df + o));
-#pragma unroll
-            for (int c = 0; c < V; ++c) {
-                d.v[c] *= fv.v[c] > 0.f ? 1.f : alpha;
-                cz.v[c] += d.v[c];
-            }
+            const Vf<V> d = dz_of<V>(f, df, o, dv, has_df, alpha);
+            vadd(cz, d);
             vst<V>(df + o, d);
         }
         vst<V>(part + (node_pair[n] + j) * 4 * C + cq, cz);
@@ -341,17 +315,11 @@ __global__ __launch_bounds__(256) void v5_combine(const float *__restrict__ dE, 
                                                   float *__restrict__ df, float *__restrict__ part, const int *__restrict__ node_s,
                                                   const long long *__restrict__ node_row, const long long *__restrict__ node_pair,
                                                   const int *__restrict__ weight, int C, int nodes, int npw) {
-    __shared__ int off[kThetaMaxPack + 1];
-    const int nb = blockIdx.x * npw;
-    const int np = nodes - nb < npw ? nodes - nb : npw, Qc = C / V;
-    int cnt = 0;
-    if ((int)threadIdx.x < np) cnt = node_s[nb + threadIdx.x] * Qc;
-    pack_offsets(off, cnt, np);
-    const int total = off[np];
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-        const int k = pack_find(off, np, it);
-        const int n = nb + k, s = node_s[n];
-        const int r = it - off[k], j = r / Qc, cq = (r - j * Qc) * V;
+    __shared__ int off[kMaxPack + 1];
+    const Run run = pack_run(off, node_s, nodes, npw, C / V);
+    for (int it = threadIdx.x; it < run.total; it += blockDim.x) {
+        const Item x = pack_item<V>(off, run.np, it, C / V);
+        const int n = run.nb + x.j, s = node_s[n], j = x.pos, cq = x.cq;
         const long long r0 = node_row[n], cj = node_pair[n] + j;
         const float *se = size_entry_v5(sizes, s, C);
         const Vf<V> l1 = vld<V>(se + cq), l2 = vld<V>(se + C + cq), dov = vld<V>(dO + cj * C + cq), cv = vld<V>(col + cj * C + cq);
@@ -381,8 +349,6 @@ __global__ __launch_bounds__(256) void v5_combine(const float *__restrict__ dE, 
         vst<V>(pr + 3 * C + cq, ps);
     }
 }
-
-inline long long level_columns(const gfsmp::LevelLayout &h) { return h.nNodes ? (long long)(h.node_pair.back() + h.node_s.back()) : 0; }   // sum s
 
 gf_status col_proj(gf_ctx *ctx, const char *name, const float *K, const float *in, int ldin, const float *sizes, const int *col_s, float *out,
                    long long cols, int C, int fwd) {
@@ -456,45 +422,39 @@ size_t smp_2d_ver5_wgrad_chunks(long long rows, long long cols) {
 gf_status smp_2d_ver5_forward_level(gf_smp *s, int l, const float *Kl, const float *sizes) {
     gf_ctx *ctx = s->ctx;
     const gf_smp::DevLevel &d = s->lv[l], &pv = s->lv[l - 1];
-    const int C = s->cfg.nChanels, nodes = s->lay.level[l].nNodes, V = theta_vec(C);
-    const long long rows = s->lay.level[l].rows, cols = level_columns(s->lay.level[l]);
+    const gfsmp::LevelLayout &h = s->lay.level[l];
+    const int C = s->cfg.nChanels, nodes = h.nNodes, V = lane_vector(C);
     const float *scalar = Kl + (size_t)2 * C * C;
     if (nodes == 0) return GF_OK;
-    const int npw = theta_pack((double)cols / (double)nodes * (C / V));
-    const dim3 grid((unsigned)((nodes + npw - 1) / npw));
-#define GF_V5_S(V) GF_LAUNCH(ctx, "smp2d5_store_S", v5_store_S<V>, grid, dim3(256), 0, pv.f, scalar, d.adj, d.th_A, d.th_B, d.v5_row_cs, d.v5_col_s, \
-                             d.node_s, d.node_row, d.node_pair, d.th_child_ptr, d.th_src_row, d.th_src_s, d.th_pi_off, d.th_pi, C, nodes, npw)
-    switch (V) {
-        case 4: GF_V5_S(4); break;
-        case 2: GF_V5_S(2); break;
-        default: GF_V5_S(1); break;
-    }
-#undef GF_V5_S
-    gf_status st = col_proj(ctx, "smp2d5_col_proj", Kl, d.th_B, C, sizes, d.v5_col_s, d.v5_u, cols, C, 1);
+    const long long cols = h.node_pair.back() + h.node_s.back();   // sum s
+    const RunGrid g = run_grid(h, true, C / V);
+    gf_status st = with_lane_vector(V, [&](auto v) -> gf_status {
+        GF_LAUNCH(ctx, "smp2d5_store_S", v5_store_S<v>, g.grid, dim3(256), 0, pv.f, scalar, d.adj, d.th_A, d.th_B, d.v5_row_cs, d.v5_col_s, d.node_s,
+                  d.node_row, d.node_pair, d.th_child_ptr, d.th_src_row, d.th_src_s, d.th_pi_off, d.th_pi, C, nodes, g.npw);
+        return GF_OK;
+    });
+    if (st == GF_OK) st = col_proj(ctx, "smp2d5_col_proj", Kl, d.th_B, C, sizes, d.v5_col_s, d.v5_u, cols, C, 1);
     if (st != GF_OK) return st;
-    return row_proj<true>(ctx, Kl, d.th_A, sizes, d.v5_u, d.v5_row_cs, d.f, rows, C, s->cfg.level_slope());
+    return row_proj<true>(ctx, Kl, d.th_A, sizes, d.v5_u, d.v5_row_cs, d.f, h.rows, C, s->cfg.level_slope());
 }
 
 // dz in place, dE and dO, dK_l, dS over dz with the column partials; then the steerable level's own reductions and the df_{l-1} gather
 gf_status smp_2d_ver5_backward_level(gf_smp *s, int l, const float *Kl, const float *sizes, float *dKl, float *dsizes, const float *node_df,
-                                     bool rows_too) {
+                                     bool rows_too, gf_status (*)(gf_smp *, int)) {
     gf_ctx *ctx = s->ctx;
     const gf_smp::DevLevel &d = s->lv[l];
-    const int C = s->cfg.nChanels, nodes = s->lay.level[l].nNodes, V = theta_vec(C);
-    const long long rows = s->lay.level[l].rows, cols = level_columns(s->lay.level[l]);
+    const gfsmp::LevelLayout &h = s->lay.level[l];
+    const int C = s->cfg.nChanels, nodes = h.nNodes, V = lane_vector(C);
     if (!node_df && !rows_too) return fail(ctx, GF_ERR_INVALID, "steerable level %d: no gradient to back-propagate", l);
     if (nodes > 0) {
-        const int npw = theta_pack((double)cols / (double)nodes * (C / V));
-        const dim3 grid((unsigned)((nodes + npw - 1) / npw));
-#define GF_V5_DZ(V) GF_LAUNCH(ctx, "smp2d5_dz", v5_dz<V>, grid, dim3(256), 0, d.f, d.df, node_df, d.th_node, d.node_s, d.node_row, d.node_pair, C, \
-                              s->cfg.level_slope(), nodes, npw, rows_too ? 1 : 0)
-        switch (V) {
-            case 4: GF_V5_DZ(4); break;
-            case 2: GF_V5_DZ(2); break;
-            default: GF_V5_DZ(1); break;
-        }
-#undef GF_V5_DZ
-        gf_status st = row_proj<false>(ctx, Kl, d.df, sizes, nullptr, d.v5_row_cs, d.Q, rows, C, 0.f);
+        const long long rows = h.rows, cols = h.node_pair.back() + h.node_s.back();   // sum s^2, sum s
+        const RunGrid g = run_grid(h, true, C / V);
+        gf_status st = with_lane_vector(V, [&](auto v) -> gf_status {
+            GF_LAUNCH(ctx, "smp2d5_dz", v5_dz<v>, g.grid, dim3(256), 0, d.f, d.df, node_df, d.th_node, d.node_s, d.node_row, d.node_pair, C,
+                      s->cfg.level_slope(), nodes, g.npw, rows_too ? 1 : 0);
+            return GF_OK;
+        });
+        if (st == GF_OK) st = row_proj<false>(ctx, Kl, d.df, sizes, nullptr, d.v5_row_cs, d.Q, rows, C, 0.f);
         if (st == GF_OK) st = col_proj(ctx, "smp2d5_col_proj_bwd", Kl, d.th_node, 4 * C, sizes, d.v5_col_s, d.v5_dO, cols, C, 0);
         // dK1 over the rows (dz is still in df_l), dK2 over the columns, their partial images back to back
         const int n1 = (int)((rows + kV5Chunk - 1) / kV5Chunk), n2 = (int)((cols + kV5Chunk - 1) / kV5Chunk);
@@ -502,18 +462,15 @@ gf_status smp_2d_ver5_backward_level(gf_smp *s, int l, const float *Kl, const fl
         if (st == GF_OK) st = wgrad(ctx, d.th_node, 4 * C, d.th_B, sizes, C, d.v5_col_s, 1, 0, d.v5_dKpart + (size_t)n1 * C * C, cols, C);
         if (st != GF_OK) return st;
         GF_LAUNCH(ctx, "smp2d5_wgrad_fold", v5_wgrad_fold, dim3((unsigned)((C * C + 63) / 64)), dim3(64 * kV5FoldGroups), 0, d.v5_dKpart, dKl, n1, n2, C);
-#define GF_V5_CB(V) GF_LAUNCH(ctx, "smp2d5_combine", v5_combine<V>, grid, dim3(256), 0, d.Q, d.v5_dO, d.th_A, d.th_B, sizes, d.adj, d.df, d.th_node, \
-                              d.node_s, d.node_row, d.node_pair, d.th_weight, C, nodes, npw)
-        switch (V) {
-            case 4: GF_V5_CB(4); break;
-            case 2: GF_V5_CB(2); break;
-            default: GF_V5_CB(1); break;
-        }
-#undef GF_V5_CB
-        st = smp_2d_size_grads(s, l, dKl + (size_t)2 * C * C, dsizes);
+        st = with_lane_vector(V, [&](auto v) -> gf_status {
+            GF_LAUNCH(ctx, "smp2d5_combine", v5_combine<v>, g.grid, dim3(256), 0, d.Q, d.v5_dO, d.th_A, d.th_B, sizes, d.adj, d.df, d.th_node, d.node_s,
+                      d.node_row, d.node_pair, d.th_weight, C, nodes, g.npw);
+            return GF_OK;
+        });
+        if (st == GF_OK) st = smp_2d_size_grads(s, l, dKl + (size_t)2 * C * C, dsizes);
         if (st != GF_OK) return st;
     }
-    return smp_2d_gather_down(s, l);
+    return smp_field_gather_down(s, l, d.df, C, true, "smp2d_gather_bwd");
 }
 
 }  // namespace gf

@@ -26,21 +26,15 @@
 // chunk's nodes in order -- forms 1 / 2 with kUnGroup lanes per element on the channels, folded by a fixed shuffle tree -- and a finish
 // kernel folds the kUnSplit chunks in order.  No atomics, fixed orders: two runs give the same bits.  Every element of f_l, S, dS, the
 // column partials, the chunk partials and df_{l-1} is written by its kernel before anything reads it.
-#include "smp_first_order.h"
+#include "smp_field_level.h"
 
 namespace gf {
-using namespace first_order;
+using namespace field_level;
 namespace {
 
 constexpr int kUnSplit = gfsmp::kUnrestrictedSplit;   // node chunks per size bucket in the reduction of the filter gradients
 constexpr int kUnLds = 2048;                          // floats of S a workgroup of the first-order forward keeps in LDS
 constexpr int kUnGroup = 16;                          // lanes on one element of a first-order filter gradient
-
-// floats in front of entry s of a per-size block: sum over t < s of (fl t^2 + Cc)
-__device__ __forceinline__ size_t entry_off(int s, int fl, int Cc) {
-    const size_t t = (size_t)(s - 1);
-    return (size_t)fl * (t * (t + 1) * (2 * t + 1) / 6) + t * (size_t)Cc;
-}
 
 // z[i][cq ..] of one half: b + sum_k Wrow[k] src[k * Cp]
 template <int V>
@@ -53,7 +47,7 @@ __device__ __forceinline__ Vf<V> filter_row(const float *__restrict__ Wrow, cons
         for (int c = 0; c < V; ++c) z.v[c] += w * a.v[c];
     }
 #pragma unroll
-    for (int c = 0; c < V; ++c) z.v[c] = z.v[c] > 0.f ? z.v[c] : alpha * z.v[c];
+    for (int c = 0; c < V; ++c) z.v[c] = lrelu(z.v[c], alpha);
     return z;
 }
 
@@ -66,33 +60,22 @@ __global__ __launch_bounds__(256) void unres1d_fwd(const float *__restrict__ fp,
                                                    const long long *__restrict__ child_ptr, const long long *__restrict__ src_row,
                                                    const long long *__restrict__ pi_off, const short *__restrict__ pi, int Cp, int halves,
                                                    float alpha, int nodes, int npw) {
-    __shared__ int off[kThetaMaxPack + 1];
+    __shared__ int off[kMaxPack + 1];
     __shared__ __align__(16) float lds[kUnLds];
-    const int nb = blockIdx.x * npw;
-    const int np = nodes - nb < npw ? nodes - nb : npw, Qc = Cp / V, Cc = halves * Cp;
-    int cnt = 0;
-    if ((int)threadIdx.x < np) cnt = node_s[nb + threadIdx.x] * Qc;
-    pack_offsets(off, cnt, np);
-    const int total = off[np];
-    const bool in_lds = (long long)total * V <= kUnLds;
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-        const int j = pack_find(off, np, it);
-        const int n = nb + j;
-        const int r = it - off[j], k = r / Qc, cq = (r - k * Qc) * V;
-        Vf<V> a = vzero<V>();
-        for (long long e = child_ptr[n]; e < child_ptr[n + 1]; ++e) {
-            const int p = pi[pi_off[e] + k];
-            if (p < 0) continue;
-            vadd(a, vld<V>(fp + (src_row[e] + p) * Cp + cq));
-        }
+    const int Cc = halves * Cp;
+    const Run run = pack_run(off, node_s, nodes, npw, Cp / V);
+    const bool in_lds = (long long)run.total * V <= kUnLds;
+    for (int it = threadIdx.x; it < run.total; it += blockDim.x) {
+        const Item x = pack_item<V>(off, run.np, it, Cp / V);
+        const int n = run.nb + x.j, k = x.pos, cq = x.cq;
+        const Vf<V> a = gather_row<V>(fp, Cp, cq, child_ptr[n], child_ptr[n + 1], src_row, pi_off, pi, k);
         vst<V>(S + (node_row[n] + k) * Cp + cq, a);
         if (in_lds) vst<V>(lds + (size_t)it * V, a);
     }
     __syncthreads();
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-        const int j = pack_find(off, np, it);
-        const int n = nb + j, s = node_s[n];
-        const int r = it - off[j], i = r / Qc, cq = (r - i * Qc) * V;
+    for (int it = threadIdx.x; it < run.total; it += blockDim.x) {
+        const Item x = pack_item<V>(off, run.np, it, Cp / V);
+        const int j = x.j, n = run.nb + j, s = node_s[n], i = x.pos, cq = x.cq;
         const long long r0 = node_row[n];
         const float *se = sizes + entry_off(s, halves, Cc);
         const float *b = se + (size_t)halves * s * s;
@@ -113,33 +96,23 @@ __global__ __launch_bounds__(256) void unres1d_node_bwd(const float *__restrict_
                                                         const float *__restrict__ sizes, float *__restrict__ dS, const int *__restrict__ node_s,
                                                         const long long *__restrict__ node_row, int Cp, int halves, float alpha, int nodes,
                                                         int npw, int has_df) {
-    __shared__ int off[kThetaMaxPack + 1];
-    const int nb = blockIdx.x * npw;
-    const int np = nodes - nb < npw ? nodes - nb : npw, Qc = Cp / V, Cc = halves * Cp;
-    int cnt = 0;
-    if ((int)threadIdx.x < np) cnt = node_s[nb + threadIdx.x] * Qc;
-    pack_offsets(off, cnt, np);
-    const int total = off[np];
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-        const int j = pack_find(off, np, it);
-        const int n = nb + j;
-        const int r = it - off[j], i = r / Qc, cq = (r - i * Qc) * V;
+    __shared__ int off[kMaxPack + 1];
+    const int Cc = halves * Cp;
+    const Run run = pack_run(off, node_s, nodes, npw, Cp / V);
+    for (int it = threadIdx.x; it < run.total; it += blockDim.x) {
+        const Item x = pack_item<V>(off, run.np, it, Cp / V);
+        const int n = run.nb + x.j, i = x.pos, cq = x.cq;
         for (int h = 0; h < halves; ++h) {
             const long long o = (node_row[n] + i) * Cc + h * Cp + cq;
-            const Vf<V> fv = vld<V>(f + o);
-            Vf<V> d = vzero<V>();
-            if (dvec) d = vld<V>(dvec + (long long)n * Cc + h * Cp + cq);
-            if (has_df) vadd(d, vld<V>(df + o));
-#pragma unroll
-            for (int c = 0; c < V; ++c) d.v[c] *= fv.v[c] > 0.f ? 1.f : alpha;
-            vst<V>(df + o, d);
+            Vf<V> dv = vzero<V>();
+            if (dvec) dv = vld<V>(dvec + (long long)n * Cc + h * Cp + cq);
+            vst<V>(df + o, dz_of<V>(f, df, o, dv, has_df, alpha));
         }
     }
     __syncthreads();
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-        const int j = pack_find(off, np, it);
-        const int n = nb + j, s = node_s[n];
-        const int r = it - off[j], k = r / Qc, cq = (r - k * Qc) * V;
+    for (int it = threadIdx.x; it < run.total; it += blockDim.x) {
+        const Item x = pack_item<V>(off, run.np, it, Cp / V);
+        const int n = run.nb + x.j, s = node_s[n], k = x.pos, cq = x.cq;
         const long long r0 = node_row[n];
         const float *se = sizes + entry_off(s, halves, Cc);
         Vf<V> g = vzero<V>();
@@ -164,12 +137,9 @@ __global__ __launch_bounds__(256) void unres1d_bucket_partials(const float *__re
                                                                const int *__restrict__ bucket, const long long *__restrict__ node_row,
                                                                const long long *__restrict__ part_off, float *__restrict__ out, int Cp,
                                                                int halves) {
-    const int s = bucket[3 * blockIdx.x], n0 = bucket[3 * blockIdx.x + 1], cnt = bucket[3 * blockIdx.x + 2];
-    const int chunk = (cnt + kUnSplit - 1) / kUnSplit;
-    int len = cnt - chunk * (int)blockIdx.y;
-    len = len < 0 ? 0 : len > chunk ? chunk : len;
-    const int Cc = halves * Cp, ss = s * s, Wd = halves * ss + Cc;
-    const long long r0 = len > 0 ? node_row[n0 + chunk * (int)blockIdx.y] : 0;
+    const BucketChunk bc = bucket_chunk(bucket, blockIdx.x, blockIdx.y, kUnSplit);
+    const int s = bc.s, len = bc.len, Cc = halves * Cp, ss = s * s, Wd = halves * ss + Cc;
+    const long long r0 = len > 0 ? node_row[bc.n0] : 0;
     float *o = out + part_off[blockIdx.x] + (size_t)blockIdx.y * Wd;
     const int g = threadIdx.x % kUnGroup, slot = threadIdx.x / kUnGroup;
     constexpr int per = 256 / kUnGroup;
@@ -202,28 +172,16 @@ __global__ __launch_bounds__(256) void unres2d_fwd(const float *__restrict__ fp,
                                                    const long long *__restrict__ src_row, const int *__restrict__ src_s,
                                                    const long long *__restrict__ pi_off, const short *__restrict__ pi, int C, float alpha,
                                                    int nodes, int npw) {
-    __shared__ int off[kThetaMaxPack + 1];
-    const int nb = blockIdx.x * npw;
-    const int np = nodes - nb < npw ? nodes - nb : npw, Qc = C / V;
-    int cnt = 0;
-    if ((int)threadIdx.x < np) cnt = node_s[nb + threadIdx.x] * Qc;
-    pack_offsets(off, cnt, np);
-    const int total = off[np];
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-        const int kk = pack_find(off, np, it);
-        const int n = nb + kk, s = node_s[n];
-        const int r = it - off[kk], j = r / Qc, cq = (r - j * Qc) * V;
+    __shared__ int off[kMaxPack + 1];
+    const Run run = pack_run(off, node_s, nodes, npw, C / V);
+    for (int it = threadIdx.x; it < run.total; it += blockDim.x) {
+        const Item x = pack_item<V>(off, run.np, it, C / V);
+        const int n = run.nb + x.j, s = node_s[n], j = x.pos, cq = x.cq;
         const long long r0 = node_row[n], e0 = child_ptr[n], e1 = child_ptr[n + 1];
         const float *W = sizes + entry_off(s, C, C);
         const Vf<V> bt = vld<V>(W + (size_t)s * s * C + cq), sc = vld<V>(scalar + cq);
         for (int i = 0; i < s; ++i) {
-            Vf<V> a = vzero<V>();
-            for (long long e = e0; e < e1; ++e) {
-                const short *pe = pi + pi_off[e];
-                const int p = pe[i], q = pe[j];
-                if (p < 0 || q < 0) continue;
-                vadd(a, vld<V>(fp + (src_row[e] + (long long)p * src_s[e] + q) * C + cq));
-            }
+            Vf<V> a = gather_pair<V>(fp, C, cq, e0, e1, src_row, src_s, pi_off, pi, i, j);
             const long long row = r0 + (long long)i * s + j;
             const float av = adj[row];
 #pragma unroll
@@ -238,7 +196,7 @@ __global__ __launch_bounds__(256) void unres2d_fwd(const float *__restrict__ fp,
                 for (int c = 0; c < V; ++c) z.v[c] += w.v[c] * a.v[c];
             }
 #pragma unroll
-            for (int c = 0; c < V; ++c) z.v[c] = z.v[c] > 0.f ? z.v[c] : alpha * z.v[c];
+            for (int c = 0; c < V; ++c) z.v[c] = lrelu(z.v[c], alpha);
             vst<V>(f + (r0 + (long long)i * s + j) * C + cq, z);
         }
     }
@@ -252,31 +210,19 @@ __global__ __launch_bounds__(256) void unres2d_node_bwd(const float *__restrict_
                                                         float *__restrict__ colpart, const int *__restrict__ node_s,
                                                         const long long *__restrict__ node_row, const long long *__restrict__ node_pair, int C,
                                                         float alpha, int nodes, int npw, int has_df) {
-    __shared__ int off[kThetaMaxPack + 1];
-    const int nb = blockIdx.x * npw;
-    const int np = nodes - nb < npw ? nodes - nb : npw, Qc = C / V;
-    int cnt = 0;
-    if ((int)threadIdx.x < np) cnt = node_s[nb + threadIdx.x] * Qc;
-    pack_offsets(off, cnt, np);
-    const int total = off[np];
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-        const int kk = pack_find(off, np, it);
-        const int n = nb + kk, s = node_s[n];
-        const int r = it - off[kk], j = r / Qc, cq = (r - j * Qc) * V;
+    __shared__ int off[kMaxPack + 1];
+    const Run run = pack_run(off, node_s, nodes, npw, C / V);
+    for (int it = threadIdx.x; it < run.total; it += blockDim.x) {
+        const Item x = pack_item<V>(off, run.np, it, C / V);
+        const int n = run.nb + x.j, s = node_s[n], j = x.pos, cq = x.cq;
         const long long r0 = node_row[n];
         const float *W = sizes + entry_off(s, C, C);
         Vf<V> dv = vzero<V>(), zs = vzero<V>(), ps = vzero<V>();
         if (dvec) dv = vld<V>(dvec + (long long)n * C + cq);
         for (int i = 0; i < s; ++i) {
             const long long o = (r0 + (long long)i * s + j) * C + cq;
-            const Vf<V> fv = vld<V>(f + o);
-            Vf<V> d = dv;
-            if (has_df) vadd(d, vld<V>(df + o));
-#pragma unroll
-            for (int c = 0; c < V; ++c) {
-                d.v[c] *= fv.v[c] > 0.f ? 1.f : alpha;
-                zs.v[c] += d.v[c];
-            }
+            const Vf<V> d = dz_of<V>(f, df, o, dv, has_df, alpha);
+            vadd(zs, d);
             vst<V>(df + o, d);
         }
         for (int k = 0; k < s; ++k) {
@@ -305,12 +251,10 @@ __global__ __launch_bounds__(256) void unres2d_bucket_partials(const float *__re
                                                                const float *__restrict__ colpart, const int *__restrict__ bucket,
                                                                const long long *__restrict__ node_row, const long long *__restrict__ node_pair,
                                                                const long long *__restrict__ part_off, float *__restrict__ out, int C) {
-    const int s = bucket[3 * blockIdx.x], n0 = bucket[3 * blockIdx.x + 1], cnt = bucket[3 * blockIdx.x + 2];
-    const int chunk = (cnt + kUnSplit - 1) / kUnSplit;
-    int len = cnt - chunk * (int)blockIdx.y;
-    len = len < 0 ? 0 : len > chunk ? chunk : len;
+    const BucketChunk bc = bucket_chunk(bucket, blockIdx.x, blockIdx.y, kUnSplit);
+    const int s = bc.s, len = bc.len;
     const long long ss = (long long)s * s, Wf = ss * C, Wp = Wf + 2 * C;
-    const long long r0 = len > 0 ? node_row[n0 + chunk * (int)blockIdx.y] : 0, p0 = len > 0 ? node_pair[n0 + chunk * (int)blockIdx.y] : 0;
+    const long long r0 = len > 0 ? node_row[bc.n0] : 0, p0 = len > 0 ? node_pair[bc.n0] : 0;
     float *o = out + part_off[blockIdx.x] + (size_t)blockIdx.y * Wp;
     for (long long e = (long long)blockIdx.z * 256 + threadIdx.x; e < Wp; e += (long long)gridDim.z * 256) {
         float acc = 0.f;
@@ -357,56 +301,6 @@ __global__ __launch_bounds__(256) void unres_grads_finish(const float *__restric
     }
 }
 
-// Reverse gather of dS ([rows of level l][Cp]) into df_{l-1}: source nodes [blockIdx.x * npw, + npw) of level l - 1.  SQ = false: items
-// (node, position p, vector); SQ = true: items (node, column q, vector) walking the source's rows p, inv applied to both indices.
-template <int V, bool SQ>
-__global__ __launch_bounds__(256) void unres_gather_bwd(const float *__restrict__ dS, float *__restrict__ out, const int *__restrict__ prev_s,
-                                                        const long long *__restrict__ prev_row, const long long *__restrict__ cons_ptr,
-                                                        const long long *__restrict__ cons_row, const int *__restrict__ cons_s,
-                                                        const long long *__restrict__ inv_off, const short *__restrict__ inv, int Cp, int nodes,
-                                                        int npw) {
-    __shared__ int off[kThetaMaxPack + 1];
-    const int wb = blockIdx.x * npw;
-    const int np = nodes - wb < npw ? nodes - wb : npw, Qc = Cp / V;
-    int cnt = 0;
-    if ((int)threadIdx.x < np) cnt = prev_s[wb + threadIdx.x] * Qc;
-    pack_offsets(off, cnt, np);
-    const int total = off[np];
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-        const int k = pack_find(off, np, it);
-        const int w = wb + k, sw = prev_s[w];
-        const int r = it - off[k], q = r / Qc, cq = (r - q * Qc) * V;
-        const long long c0 = cons_ptr[w], c1 = cons_ptr[w + 1], r0 = prev_row[w];
-        if (!SQ) {
-            Vf<V> g = vzero<V>();
-            for (long long c = c0; c < c1; ++c) {
-                const int i = inv[inv_off[c] + q];
-                if (i < 0) continue;
-                vadd(g, vld<V>(dS + (cons_row[c] + i) * Cp + cq));
-            }
-            vst<V>(out + (r0 + q) * Cp + cq, g);
-            continue;
-        }
-        for (int p = 0; p < sw; ++p) {
-            Vf<V> g = vzero<V>();
-            for (long long c = c0; c < c1; ++c) {
-                const short *ie = inv + inv_off[c];
-                const int i = ie[p], j = ie[q];
-                if (i < 0 || j < 0) continue;
-                vadd(g, vld<V>(dS + (cons_row[c] + (long long)i * cons_s[c] + j) * Cp + cq));
-            }
-            vst<V>(out + (r0 + (long long)p * sw + q) * Cp + cq, g);
-        }
-    }
-}
-
-// items (position or column, vector) of an average node of level h: sum s / nodes * Cp / V
-inline double items_per_node(const gfsmp::LevelLayout &h, bool sq, int Qc) {
-    if (h.nNodes == 0) return 1.0;
-    const double cols = sq ? (double)(h.node_pair.back() + h.node_s.back()) : (double)h.rows;
-    return cols / (double)h.nNodes * Qc;
-}
-
 }  // namespace
 
 // f_l from f_{l-1}: one launch
@@ -414,53 +308,44 @@ gf_status smp_unrestricted_forward_level(gf_smp *s, int l, const float *scalar, 
     gf_ctx *ctx = s->ctx;
     const gf_smp::DevLevel &d = s->lv[l], &pv = s->lv[l - 1];
     const int form = s->cfg.unrestricted, Cp = s->cfg.level_channels(l - 1);
-    const int nodes = s->lay.level[l].nNodes, V = theta_vec(Cp);
+    const int nodes = s->lay.level[l].nNodes, V = lane_vector(Cp);
     if (nodes == 0) return GF_OK;
-    const int npw = theta_pack(items_per_node(s->lay.level[l], form == 3, Cp / V));
-    const dim3 grid((unsigned)((nodes + npw - 1) / npw));
+    const RunGrid g = run_grid(s->lay.level[l], form == 3, Cp / V);
     const float alpha = s->cfg.level_slope();
-#define GF_UN_FWD(V)                                                                                                                                  \
-    if (form == 3)                                                                                                                                    \
-        GF_LAUNCH(ctx, "unres2d_level_fwd", unres2d_fwd<V>, grid, dim3(256), 0, pv.f, sizes, scalar, d.adj, d.f, d.th_A, d.node_s, d.node_row,        \
-                  d.th_child_ptr, d.th_src_row, d.th_src_s, d.th_pi_off, d.th_pi, Cp, alpha, nodes, npw);                                             \
-    else                                                                                                                                              \
-        GF_LAUNCH(ctx, "unres1d_level_fwd", unres1d_fwd<V>, grid, dim3(256), 0, pv.f, sizes, d.f, d.th_A, d.node_s, d.node_row, d.th_child_ptr,       \
-                  d.th_src_row, d.th_pi_off, d.th_pi, Cp, form, alpha, nodes, npw)
-    switch (V) {
-        case 4: GF_UN_FWD(4); break;
-        case 2: GF_UN_FWD(2); break;
-        default: GF_UN_FWD(1); break;
-    }
-#undef GF_UN_FWD
-    return GF_OK;
+    return with_lane_vector(V, [&](auto v) -> gf_status {
+        if (form == 3)
+            GF_LAUNCH(ctx, "unres2d_level_fwd", unres2d_fwd<v>, g.grid, dim3(256), 0, pv.f, sizes, scalar, d.adj, d.f, d.th_A, d.node_s, d.node_row,
+                      d.th_child_ptr, d.th_src_row, d.th_src_s, d.th_pi_off, d.th_pi, Cp, alpha, nodes, g.npw);
+        else
+            GF_LAUNCH(ctx, "unres1d_level_fwd", unres1d_fwd<v>, g.grid, dim3(256), 0, pv.f, sizes, d.f, d.th_A, d.node_s, d.node_row, d.th_child_ptr,
+                      d.th_src_row, d.th_pi_off, d.th_pi, Cp, form, alpha, nodes, g.npw);
+        return GF_OK;
+    });
 }
 
-// dz and dS per node, the per-size gradients (and dscalar_l) over the buckets, then df_{l-1}
-gf_status smp_unrestricted_backward_level(gf_smp *s, int l, const float *sizes, float *dscalar, float *dsizes, const float *node_df, bool rows_too) {
+// dz and dS per node, the per-size gradients (and dscalar_l) over the buckets, then df_{l-1}.  (scalar_l itself and wgrad_done: not needed)
+gf_status smp_unrestricted_backward_level(gf_smp *s, int l, const float *, const float *sizes, float *dscalar, float *dsizes, const float *node_df,
+                                          bool rows_too, gf_status (*)(gf_smp *, int)) {
     gf_ctx *ctx = s->ctx;
-    const gf_smp::DevLevel &d = s->lv[l], &pv = s->lv[l - 1];
+    const gf_smp::DevLevel &d = s->lv[l];
     const gfsmp::LevelLayout &h = s->lay.level[l];
     const int form = s->cfg.unrestricted, Cp = s->cfg.level_channels(l - 1), Cc = s->cfg.level_channels(l);
-    const int nodes = h.nNodes, np = s->lay.level[l - 1].nNodes, V = theta_vec(Cp);
+    const int nodes = h.nNodes, V = lane_vector(Cp);
     const int nbuckets = (int)(h.th_bucket.size() / 3);
     const float alpha = s->cfg.level_slope();
     if (!node_df && !rows_too) return fail(ctx, GF_ERR_INVALID, "unrestricted level %d: no gradient to back-propagate", l);
     if (nodes > 0) {
-        const int npw = theta_pack(items_per_node(h, form == 3, Cp / V));
-        const dim3 grid((unsigned)((nodes + npw - 1) / npw));
-#define GF_UN_NODE(V)                                                                                                                                 \
-    if (form == 3)                                                                                                                                    \
-        GF_LAUNCH(ctx, "unres2d_node_bwd", unres2d_node_bwd<V>, grid, dim3(256), 0, d.f, d.df, node_df, sizes, d.adj, d.Q, d.th_node, d.node_s,       \
-                  d.node_row, d.node_pair, Cp, alpha, nodes, npw, rows_too ? 1 : 0);                                                                  \
-    else                                                                                                                                              \
-        GF_LAUNCH(ctx, "unres1d_node_bwd", unres1d_node_bwd<V>, grid, dim3(256), 0, d.f, d.df, node_df, sizes, d.Q, d.node_s, d.node_row, Cp, form,   \
-                  alpha, nodes, npw, rows_too ? 1 : 0)
-        switch (V) {
-            case 4: GF_UN_NODE(4); break;
-            case 2: GF_UN_NODE(2); break;
-            default: GF_UN_NODE(1); break;
-        }
-#undef GF_UN_NODE
+        const RunGrid g = run_grid(h, form == 3, Cp / V);
+        const gf_status st = with_lane_vector(V, [&](auto v) -> gf_status {
+            if (form == 3)
+                GF_LAUNCH(ctx, "unres2d_node_bwd", unres2d_node_bwd<v>, g.grid, dim3(256), 0, d.f, d.df, node_df, sizes, d.adj, d.Q, d.th_node, d.node_s,
+                          d.node_row, d.node_pair, Cp, alpha, nodes, g.npw, rows_too ? 1 : 0);
+            else
+                GF_LAUNCH(ctx, "unres1d_node_bwd", unres1d_node_bwd<v>, g.grid, dim3(256), 0, d.f, d.df, node_df, sizes, d.Q, d.node_s, d.node_row, Cp,
+                          form, alpha, nodes, g.npw, rows_too ? 1 : 0);
+            return GF_OK;
+        });
+        if (st != GF_OK) return st;
         const long long smax = h.buckets.back().s;   // (buckets ascend by size) tiles of the largest entry, at most 64
         if (form == 3) {
             const long long tiles = (smax * smax * Cp + 2 * Cp + 255) / 256;
@@ -474,24 +359,7 @@ gf_status smp_unrestricted_backward_level(gf_smp *s, int l, const float *sizes, 
         GF_LAUNCH(ctx, "unres_grads_finish", unres_grads_finish, dim3((unsigned)nbuckets + (form == 3 ? 1 : 0)), dim3(256), 0, d.part2d, d.th_bucket,
                   d.un_part_off, dsizes, dscalar, form == 3 ? Cp : form, Cc, form == 3 ? Cp : 0, nbuckets);
     }
-    if (np > 0) {
-        const int npw = theta_pack(items_per_node(s->lay.level[l - 1], form == 3, Cp / V));
-        const dim3 grid((unsigned)((np + npw - 1) / npw));
-#define GF_UN_BWD(V)                                                                                                                                  \
-    if (form == 3)                                                                                                                                    \
-        GF_LAUNCH(ctx, "unres_gather_bwd", (unres_gather_bwd<V, true>), grid, dim3(256), 0, d.Q, pv.df, pv.node_s, pv.node_row, d.th_cons_ptr,        \
-                  d.th_cons_row, d.th_cons_s, d.th_inv_off, d.th_inv, Cp, np, npw);                                                                   \
-    else                                                                                                                                              \
-        GF_LAUNCH(ctx, "unres_gather_bwd", (unres_gather_bwd<V, false>), grid, dim3(256), 0, d.Q, pv.df, pv.node_s, pv.node_row, d.th_cons_ptr,       \
-                  d.th_cons_row, d.th_cons_s, d.th_inv_off, d.th_inv, Cp, np, npw)
-        switch (V) {
-            case 4: GF_UN_BWD(4); break;
-            case 2: GF_UN_BWD(2); break;
-            default: GF_UN_BWD(1); break;
-        }
-#undef GF_UN_BWD
-    }
-    return GF_OK;
+    return smp_field_gather_down(s, l, d.Q, Cp, form == 3, "unres_gather_bwd");
 }
 
 }  // namespace gf
