@@ -15,6 +15,8 @@
 // K_l is ONE node of the reference's graph (added in the preamble) and every vertex's CustomMatMulTensor adds into K_l->gradient itself:
 // dK_l is the plain derivative, unlike dlambda (th_weight = j, through the shared W_eye[s] / W_one[s]).
 // fp32 operands and accumulation throughout; no atomics, every sum in a fixed order; every buffer written before it is read.
+// The projections and the weight gradients are also operators of the C ABI on caller-supplied operands (gf_smp_2d_ver5_rows_ex_f32,
+// _cols_ex_f32, _wgrad_ex_f32 at the end of this file): what tests/test_smp_2d_ver5_ops_gpu.py holds to the fp64 product row by row.
 #include "smp_field_level.h"
 
 namespace gf {
@@ -362,7 +364,7 @@ gf_status col_proj(gf_ctx *ctx, const char *name, const float *K, const float *i
 
 template <int NT, bool VEC, bool FWD>
 gf_status row_proj_launch(gf_ctx *ctx, const float *K, const float *X, const float *sizes, const float *u, const int2 *row_cs, float *out,
-                          long long rows, int C, float alpha) {
+                          long long rows, int C, float alpha, int max_workgroups) {
     constexpr size_t lds = (size_t)(32 * NT) * (32 * NT + 4) * sizeof(float);
     gf_status st = opt_in_lds(ctx, v5_row_proj<NT, VEC, FWD>, lds);
     if (st != GF_OK) return st;
@@ -376,17 +378,20 @@ gf_status row_proj_launch(gf_ctx *ctx, const float *K, const float *X, const flo
         GF_HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v5_row_proj<NT, VEC, FWD>, 256, lds));
         resident[di] = (cus < 1 ? 256 : cus) * (per_cu < 1 ? 1 : per_cu);
     }
-    const long long blocks = ((rows + 31) / 32 + 3) / 4;
-    GF_LAUNCH(ctx, FWD ? "smp2d5_row_proj" : "smp2d5_row_proj_bwd", (v5_row_proj<NT, VEC, FWD>),
-              dim3((unsigned)(blocks > resident[di] ? resident[di] : blocks)), dim3(256), lds, K, X, sizes, u, row_cs, out, rows, C, alpha);
+    // (max_workgroups > 0: a smaller grid still, for the stand-alone operator -- a small input then strides; the level passes 0)
+    long long blocks = ((rows + 31) / 32 + 3) / 4;
+    if (blocks > resident[di]) blocks = resident[di];
+    if (max_workgroups > 0 && blocks > max_workgroups) blocks = max_workgroups;
+    GF_LAUNCH(ctx, FWD ? "smp2d5_row_proj" : "smp2d5_row_proj_bwd", (v5_row_proj<NT, VEC, FWD>), dim3((unsigned)blocks), dim3(256), lds, K, X, sizes, u,
+              row_cs, out, rows, C, alpha);
     return GF_OK;
 }
 template <bool FWD>
 gf_status row_proj(gf_ctx *ctx, const float *K, const float *X, const float *sizes, const float *u, const int2 *row_cs, float *out, long long rows,
-                   int C, float alpha) {
+                   int C, float alpha, int max_workgroups) {
     const int nt = (C + 31) / 32;
-#define GF_V5_ROW(NT) (C % 4 == 0 ? row_proj_launch<NT, true, FWD>(ctx, K, X, sizes, u, row_cs, out, rows, C, alpha) \
-                                  : row_proj_launch<NT, false, FWD>(ctx, K, X, sizes, u, row_cs, out, rows, C, alpha))
+#define GF_V5_ROW(NT) (C % 4 == 0 ? row_proj_launch<NT, true, FWD>(ctx, K, X, sizes, u, row_cs, out, rows, C, alpha, max_workgroups) \
+                                  : row_proj_launch<NT, false, FWD>(ctx, K, X, sizes, u, row_cs, out, rows, C, alpha, max_workgroups))
     switch (nt) {
         case 1: return GF_V5_ROW(1);
         case 2: return GF_V5_ROW(2);
@@ -409,6 +414,33 @@ gf_status wgrad(gf_ctx *ctx, const float *A, int lda, const float *B, const floa
         default: GF_V5_WG(4); break;
     }
 #undef GF_V5_WG
+    return GF_OK;
+}
+
+// dK [C][2 C] += (dK1 | dK2): the two chunked reductions, their partial images back to back in `part` (smp_2d_ver5_wgrad_chunks(rows,
+// cols) images of C x C floats), and the fold
+gf_status wgrad_both(gf_ctx *ctx, const float *dz, const float *S, const int2 *row_cs, long long rows, const float *cz, int ldcz, const float *col,
+                     const int *col_s, long long cols, const float *sizes, float *part, float *dK, int C) {
+    const int n1 = (int)((rows + kV5Chunk - 1) / kV5Chunk), n2 = (int)((cols + kV5Chunk - 1) / kV5Chunk);
+    gf_status st = wgrad(ctx, dz, C, S, sizes, 0, reinterpret_cast<const int *>(row_cs), 2, 1, part, rows, C);
+    if (st == GF_OK) st = wgrad(ctx, cz, ldcz, col, sizes, C, col_s, 1, 0, part + (size_t)n1 * C * C, cols, C);
+    if (st != GF_OK) return st;
+    GF_LAUNCH(ctx, "smp2d5_wgrad_fold", v5_wgrad_fold, dim3((unsigned)((C * C + 63) / 64)), dim3(64 * kV5FoldGroups), 0, part, dK, n1, n2, C);
+    return GF_OK;
+}
+
+// A table of a stand-alone call, checked on the host (one blocking copy: these are test operators): col_s (stride 1) or row_cs (stride 2:
+// (column, s)).  Every s in 1 .. nsizes -- the kernels index the size entries with it -- and every column of row_cs inside the cols columns.
+gf_status check_table(gf_ctx *ctx, const char *who, const char *what, const int *tab, int n, int stride, int nsizes, int cols) {
+    std::vector<int> t((size_t)n * stride);
+    GF_HIP_TRY(ctx, hipMemcpyAsync(t.data(), tab, sizeof(int) * t.size(), hipMemcpyDeviceToHost, ctx->stream));
+    GF_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < n; ++i) {
+        const int s = t[(size_t)i * stride + stride - 1];
+        if (s < 1 || s > nsizes) return fail(ctx, GF_ERR_INVALID, "%s: %s[%d] has size %d outside 1 .. %d", who, what, i, s, nsizes);
+        if (stride == 2 && (t[(size_t)i * 2] < 0 || t[(size_t)i * 2] >= cols))
+            return fail(ctx, GF_ERR_INVALID, "%s: %s[%d] names column %d outside the %d columns", who, what, i, t[(size_t)i * 2], cols);
+    }
     return GF_OK;
 }
 
@@ -435,7 +467,7 @@ gf_status smp_2d_ver5_forward_level(gf_smp *s, int l, const float *Kl, const flo
     });
     if (st == GF_OK) st = col_proj(ctx, "smp2d5_col_proj", Kl, d.th_B, C, sizes, d.v5_col_s, d.v5_u, cols, C, 1);
     if (st != GF_OK) return st;
-    return row_proj<true>(ctx, Kl, d.th_A, sizes, d.v5_u, d.v5_row_cs, d.f, h.rows, C, s->cfg.level_slope());
+    return row_proj<true>(ctx, Kl, d.th_A, sizes, d.v5_u, d.v5_row_cs, d.f, h.rows, C, s->cfg.level_slope(), 0);
 }
 
 // dz in place, dE and dO, dK_l, dS over dz with the column partials; then the steerable level's own reductions and the df_{l-1} gather
@@ -454,14 +486,11 @@ gf_status smp_2d_ver5_backward_level(gf_smp *s, int l, const float *Kl, const fl
                       s->cfg.level_slope(), nodes, g.npw, rows_too ? 1 : 0);
             return GF_OK;
         });
-        if (st == GF_OK) st = row_proj<false>(ctx, Kl, d.df, sizes, nullptr, d.v5_row_cs, d.Q, rows, C, 0.f);
+        if (st == GF_OK) st = row_proj<false>(ctx, Kl, d.df, sizes, nullptr, d.v5_row_cs, d.Q, rows, C, 0.f, 0);
         if (st == GF_OK) st = col_proj(ctx, "smp2d5_col_proj_bwd", Kl, d.th_node, 4 * C, sizes, d.v5_col_s, d.v5_dO, cols, C, 0);
-        // dK1 over the rows (dz is still in df_l), dK2 over the columns, their partial images back to back
-        const int n1 = (int)((rows + kV5Chunk - 1) / kV5Chunk), n2 = (int)((cols + kV5Chunk - 1) / kV5Chunk);
-        if (st == GF_OK) st = wgrad(ctx, d.df, C, d.th_A, sizes, 0, reinterpret_cast<const int *>(d.v5_row_cs), 2, 1, d.v5_dKpart, rows, C);
-        if (st == GF_OK) st = wgrad(ctx, d.th_node, 4 * C, d.th_B, sizes, C, d.v5_col_s, 1, 0, d.v5_dKpart + (size_t)n1 * C * C, cols, C);
+        // dK1 over the rows (dz is still in df_l), dK2 over the columns
+        if (st == GF_OK) st = wgrad_both(ctx, d.df, d.th_A, d.v5_row_cs, rows, d.th_node, 4 * C, d.th_B, d.v5_col_s, cols, sizes, d.v5_dKpart, dKl, C);
         if (st != GF_OK) return st;
-        GF_LAUNCH(ctx, "smp2d5_wgrad_fold", v5_wgrad_fold, dim3((unsigned)((C * C + 63) / 64)), dim3(64 * kV5FoldGroups), 0, d.v5_dKpart, dKl, n1, n2, C);
         st = with_lane_vector(V, [&](auto v) -> gf_status {
             GF_LAUNCH(ctx, "smp2d5_combine", v5_combine<v>, g.grid, dim3(256), 0, d.Q, d.v5_dO, d.th_A, d.th_B, sizes, d.adj, d.df, d.th_node, d.node_s,
                       d.node_row, d.node_pair, d.th_weight, C, nodes, g.npw);
@@ -474,3 +503,52 @@ gf_status smp_2d_ver5_backward_level(gf_smp *s, int l, const float *Kl, const fl
 }
 
 }  // namespace gf
+
+// ---- the level's projections and weight gradients as stand-alone operators (include/gf_hip.h; tests/test_smp_2d_ver5_ops_gpu.py) ----
+extern "C" {
+
+gf_status gf_smp_2d_ver5_rows_ex_f32(gf_ctx *ctx, int backward, int C, int rows, int cols, int nsizes, const float *K, const float *X,
+                                     const float *sizes, const float *u, const int *row_cs, float alpha, int max_workgroups, float *out) {
+    static const char *who = "gf_smp_2d_ver5_rows_ex_f32";
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    if (C < 1 || C > 128) return gf::fail(ctx, GF_ERR_INVALID, "%s: %d channels (1 .. 128)", who, C);
+    if (rows < 1 || max_workgroups < 0 || !K || !X || !out) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
+    if (!backward && (cols < 1 || nsizes < 1 || !sizes || !u || !row_cs)) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument of the forward", who);
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (backward) return gf::row_proj<false>(ctx, K, X, nullptr, nullptr, nullptr, out, rows, C, 0.f, max_workgroups);
+    const gf_status st = gf::check_table(ctx, who, "row_cs", row_cs, rows, 2, nsizes, cols);
+    if (st != GF_OK) return st;
+    return gf::row_proj<true>(ctx, K, X, sizes, u, reinterpret_cast<const int2 *>(row_cs), out, rows, C, alpha, max_workgroups);
+}
+
+gf_status gf_smp_2d_ver5_cols_ex_f32(gf_ctx *ctx, int backward, int C, int cols, int nsizes, const float *K, const float *in, int ldin,
+                                     const float *sizes, const int *col_s, float *out) {
+    static const char *who = "gf_smp_2d_ver5_cols_ex_f32";
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    if (C < 1 || C > 128) return gf::fail(ctx, GF_ERR_INVALID, "%s: %d channels (1 .. 128)", who, C);
+    if (cols < 1 || ldin < C || !K || !in || !out) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
+    if (!backward && (nsizes < 1 || !sizes || !col_s)) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument of the forward", who);
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (backward) return gf::col_proj(ctx, "smp2d5_col_proj_bwd", K, in, ldin, nullptr, nullptr, out, cols, C, 0);
+    const gf_status st = gf::check_table(ctx, who, "col_s", col_s, cols, 1, nsizes, 0);
+    if (st != GF_OK) return st;
+    return gf::col_proj(ctx, "smp2d5_col_proj", K, in, ldin, sizes, col_s, out, cols, C, 1);
+}
+
+gf_status gf_smp_2d_ver5_wgrad_ex_f32(gf_ctx *ctx, int C, int rows, int cols, int nsizes, const float *dz, const float *S, const int *row_cs,
+                                      const float *cz, int ldcz, const float *col, const int *col_s, const float *sizes, float *dK) {
+    static const char *who = "gf_smp_2d_ver5_wgrad_ex_f32";
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    if (C < 1 || C > 128) return gf::fail(ctx, GF_ERR_INVALID, "%s: %d channels (1 .. 128)", who, C);
+    if (rows < 1 || cols < 1 || nsizes < 1 || ldcz < C || !dz || !S || !row_cs || !cz || !col || !col_s || !sizes || !dK)
+        return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    gf_status st = gf::check_table(ctx, who, "row_cs", row_cs, rows, 2, nsizes, cols);
+    if (st == GF_OK) st = gf::check_table(ctx, who, "col_s", col_s, cols, 1, nsizes, 0);
+    // workspace: the partial images of both halves
+    if (st == GF_OK) st = gf::ensure_ws(ctx, sizeof(float) * gf::smp_2d_ver5_wgrad_chunks(rows, cols) * C * C + 256);
+    if (st != GF_OK) return st;
+    return gf::wgrad_both(ctx, dz, S, reinterpret_cast<const int2 *>(row_cs), rows, cz, ldcz, col, col_s, cols, sizes, static_cast<float *>(ctx->ws), dK, C);
+}
+
+}  // extern "C"

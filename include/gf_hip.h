@@ -460,6 +460,28 @@ gf_status gf_smp_level_wgrad_ex_f32(gf_ctx *ctx, int C, int nf, int nx, int rows
  * without, padded likewise.  A padding entry repeats the last row of its class with bit 31 of the row set.  The level builds this once
  * per gf_smp_prepare; gf_smp_level_products_ex_f32 builds it per call (the backward products under skip_zero_grads walk it).  rows < 2^29.  Asynchronous on the context's stream. */
 gf_status gf_smp_level_row_classes(gf_ctx *ctx, int rows, const int *trowf, int *lists);
+/* SMP_2D_ver5's level (gf_smp_config.steerable_2d = 5), its channel projections and weight gradients as stand-alone operators: the
+ * level's own kernels and launches on caller-supplied operands, for per-row tests (tests/test_smp_2d_ver5_ops_gpu.py).  Device
+ * pointers, fp32, asynchronous on the context's stream.  C = 1 .. 128 channels; K [C][2 C] = [K1 | K2]; sizes: nsizes entries of 3 C
+ * floats (lambda1_s | lambda2_s | b_s), entry s - 1 for a node of s positions; row_cs [rows][2] = (column of the row, s); col_s [cols].
+ *   rows, backward = 0: out[row] = LeakyReLU_alpha((lambda1_s . X[row]) K1^T + u[column of the row]),  X, out [rows][C], u [cols][C];
+ *         backward = 1: out[row] = X[row] K1  (sizes, u, row_cs, cols, nsizes are not read and may be NULL / 0).
+ *         max_workgroups = 0: the level's grid (no more workgroups than the device holds at once, striding over the 32-row tiles);
+ *         > 0: at most that many, so that a small input strides as a large one does.
+ *   cols, backward = 0: out[j] = (lambda2_s . in[j]) K2^T + b_s;   backward = 1: out[j] = in[j] K2  (sizes, col_s not read).
+ *         Rows of `in` are ldin >= C floats apart (the level's backward reads cz out of its 4 C-wide column partials), out [cols][C].
+ *   wgrad: dK [C][2 C] += (sum_rows dz^T (lambda1_s . S) | sum_cols cz^T (lambda2_s . col)): dz, S [rows][C]; cz (rows ldcz >= C floats
+ *         apart), col [cols][C]; per half one partial image per 512 rows, folded in a fixed order (the images live in the context's
+ *         workspace).
+ * GF_ERR_INVALID before anything is launched: C outside 1 .. 128, rows / cols < 1, ldin / ldcz < C, and -- checked on the host, one
+ * blocking copy of the tables per call -- a size outside 1 .. nsizes or (rows forward, wgrad) a column outside [0, cols).  The context
+ * stays usable after a refusal. */
+gf_status gf_smp_2d_ver5_rows_ex_f32(gf_ctx *ctx, int backward, int C, int rows, int cols, int nsizes, const float *K, const float *X,
+                                     const float *sizes, const float *u, const int *row_cs, float alpha, int max_workgroups, float *out);
+gf_status gf_smp_2d_ver5_cols_ex_f32(gf_ctx *ctx, int backward, int C, int cols, int nsizes, const float *K, const float *in, int ldin,
+                                     const float *sizes, const int *col_s, float *out);
+gf_status gf_smp_2d_ver5_wgrad_ex_f32(gf_ctx *ctx, int C, int rows, int cols, int nsizes, const float *dz, const float *S, const int *row_cs,
+                                      const float *cz, int ldcz, const float *col, const int *col_s, const float *sizes, float *dK);
 /* Device memory of the handle's buffer pool: bytes held by the current batch, and bytes the pool keeps in total (idle
  * blocks included).  Sizing aid for batch selection (GraphFlow has no counterpart: its tensors live in host `new[]`). */
 gf_status gf_smp_device_bytes(const gf_smp *smp, size_t *in_use, size_t *reserved);

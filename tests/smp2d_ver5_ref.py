@@ -51,7 +51,8 @@ def split(p, C, FD, L, maxV):
 
 
 def run(adj, feat, target, params, L, C, D, maxV, phi):
-    """one molecule: graph_feature, predict, loss, grads, the activations f[l][v] ([s, s, C]) and reduced adjacencies radj[l][v]"""
+    """one molecule: graph_feature, predict, loss, grads, the activations f[l][v] ([s, s, C]) and reduced adjacencies radj[l][v]; also the
+    level's operands S[l][v] and dz[l][v] ([s, s, C]; col = S.sum(0), cz = dz.sum(0)), for tests/smp2d_ver5_ops_ref.py"""
     feat = np.asarray(feat, dtype=np.float64)
     p = np.asarray(params, dtype=np.float64)
     V = len(adj)
@@ -97,6 +98,7 @@ def run(adj, feat, target, params, L, C, D, maxV, phi):
     dg = (y - target) * W
     out = {"graph_feature": g, "f": [[lrelu(zv) for zv in zl] for zl in z], "radj": radj, "predict": y, "loss": 0.5 * (y - target) ** 2}
     df = [[np.zeros_like(z[l][v]) for v in range(V)] for l in range(L + 1)]
+    out["S"], out["dz"] = Ss, [None] + [[None] * V for _ in range(L)]
     for v in range(V):
         df[L][v] += (dg * dlrelu(sh[v]))[None, None, :]
     for l in range(L, 0, -1):
@@ -104,7 +106,7 @@ def run(adj, feat, target, params, L, C, D, maxV, phi):
         gl1, gl2, gb, gK, gscalar = glv[l]
         for v in range(V):
             s = len(phi[l][v])
-            dz = df[l][v] * dlrelu(z[l][v])
+            dz = out["dz"][l][v] = df[l][v] * dlrelu(z[l][v])
             S = Ss[l][v]
             col = S.sum(0)
             cz = dz.sum(0)

@@ -7,8 +7,10 @@ import os
 import numpy as np
 import pytest
 
+import smp2d_ver5_ops_ref as ops
 import smp2d_ver5_ref
 from make_smp2d_ver5_golden import smp2d_ver5_blocks
+from smp2d_ref import ALPHA
 from util import rel_err
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -174,3 +176,37 @@ def test_ch4_gradients_pin_the_multiplicities(gz):
         assert rel_err(kk(ref_of(gz, tag)["grads"]), kk(real)) > 1e-3
     finally:
         smp2d_ver5_ref.multiplicity, smp2d_ver5_ref.k_multiplicity = saved
+
+
+def test_operator_references_compose_to_the_real_class(gz):
+    """tests/smp2d_ver5_ops_ref.py (the reference of the stand-alone level operators) on the 12-vertex molecule at (C, nLevels) = (8, 3):
+    with S, col = S.sum(0) and dz, cz = dz.sum(0) of smp2d_ver5_ref as operands, cols_forward -> rows_forward reproduce every level's
+    f_l, and wgrad the K_l block of the real class's gradient, at 1e-9 -- so the operator suite cannot agree with itself and not with
+    SMP_2D_ver5.  (row = r0 + i s + j, column = c0 + j: level_tables is the layout of v5_store_S.)"""
+    tag = [t for t in gz["tags"] if gz[t + "__cfg"][2] == 8 and len(gz[t + "__adj"]) == 12][0]
+    _, L, Cn, D, wl, maxV, _ = (int(x) for x in gz[tag + "__cfg"])
+    assert L == 3
+    r = ref_of(gz, tag)
+    phi = smp2d_ver5_ref.fields_of(gz[tag + "__phi"])
+    FD = gz[tag + "__feature"].shape[1] * (D + 1)
+    _, lv, _ = smp2d_ver5_ref.split(np.asarray(gz[tag + "__params"], dtype=np.float64), Cn, FD, L, maxV)
+    blocks = smp2d_ver5_blocks(Cn, FD, L, maxV)
+    off = {name: o for (name, _), o in zip(blocks, np.cumsum([0] + [n for _, n in blocks])[:-1])}
+    for l in range(1, L + 1):
+        lam1, lam2, b, K, _ = lv[l]
+        sizes = np.concatenate([lam1, lam2, b], axis=1)
+        node_sizes = [len(f) for f in phi[l]]
+        assert len(set(node_sizes)) > 1   # (a tile of rows spans nodes of different sizes)
+        row_cs, col_s = ops.level_tables(node_sizes)
+        S = np.concatenate([x.reshape(-1, Cn) for x in r["S"][l]])
+        dz = np.concatenate([x.reshape(-1, Cn) for x in r["dz"][l]])
+        col = np.concatenate([x.sum(0) for x in r["S"][l]])
+        cz = np.concatenate([x.sum(0) for x in r["dz"][l]])
+        f, _ = ops.rows_forward(K, S, sizes, ops.cols_forward(K, col, sizes, col_s), row_cs, ALPHA)
+        fl = np.concatenate([x.reshape(-1, Cn) for x in r["f"][l]])
+        assert np.abs(f - fl).max() <= TOL_REF * np.abs(fl).max(), (tag, l)
+        dK = ops.wgrad(dz, S, row_cs, cz, col, col_s, sizes)
+        o = off["K_%d" % l]
+        real = gz[tag + "__grads"][o:o + 2 * Cn * Cn].reshape(Cn, 2 * Cn)
+        for h in (slice(0, Cn), slice(Cn, 2 * Cn)):   # (each half against its own size)
+            assert np.abs(dK[:, h] - real[:, h]).max() <= TOL_REF * np.abs(real[:, h]).max(), (tag, l)

@@ -193,11 +193,13 @@ def packed_case(Cn):
     return _PACKED[Cn]
 
 
-@pytest.mark.parametrize("Cn", [5, 8, 32, 40])
+@pytest.mark.parametrize("Cn", [5, 8, 32, 40, 66, 72, 100, 128])
 def test_batch_across_the_packing_boundaries(gf, Cn):
     """against smp2d_ver5_ref, per molecule (prediction, graph feature) and per block of the summed gradient.  C = 32: exactly one MFMA
     tile, nothing padded; C = 40: a ragged second tile in the output and in the reduction dimension; 5 and 8: one padded tile, scalar
-    and 16-byte operand loads.  Every level has rows for at least two chunks of dK1, and a last 32-row tile that is not full."""
+    and 16-byte operand loads; 66 and 72: three tiles, scalar and 16-byte loads; 100 and 128: four tiles, ragged and full (at 128 the
+    LDS images of both projections need the opt-in).  Every level has rows for at least two chunks of dK1, and a last 32-row tile that
+    is not full.  Every width runs the whole batch: its fp64 reference takes 0.2 s (C = 40) to 0.5 s (C = 128) on the CPU."""
     mols, tg, params, blocks, out, res, rg = packed_case(Cn)
     assert len(mols) == 70 and sum(len(a) for a, _ in mols) > 64
     sizes = {int(s) for m in out[4] for l in (1, 2) for s in map(len, m[l])}
@@ -229,7 +231,7 @@ def test_one_molecule_isolated_inside_the_batch(gf):
     assert rel_err(batch[0][k:k + 1], alone[0]) <= TOL and rel_err(batch[2][k], alone[2][0]) <= TOL
 
 
-@pytest.mark.parametrize("Cn", [5, 40])
+@pytest.mark.parametrize("Cn", [5, 40, 128])
 def test_two_runs_give_the_same_bits(gf, Cn):
     mols, tg, params, _, out, _, _ = packed_case(Cn)
     again = run_net(mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV)
@@ -239,10 +241,12 @@ def test_two_runs_give_the_same_bits(gf, Cn):
 
 def test_parity_under_poison(gf):
     """GF_POISON=1 (every buffer the library hands out without contents starts as NaN patterns): no kernel of this level reads memory
-    nobody wrote.  The golden and packing-boundary cases in a fresh child process."""
+    nobody wrote.  The golden and packing-boundary cases, and the level's kernels one by one at every width
+    (tests/test_smp_2d_ver5_ops_gpu.py), in a fresh child process."""
     env = dict(os.environ, GF_POISON="1")
-    sel = "real_class or packing_boundaries"
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k", sel, "-p", "no:cacheprovider"],
+    sel = "real_class or packing_boundaries or every_instantiation"
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), os.path.join(HERE, "test_smp_2d_ver5_ops_gpu.py"), "-q", "-x", "-m",
+                        "gpu", "-k", sel, "-p", "no:cacheprovider"],
                        env=env, capture_output=True, text=True, timeout=600)
     tail = (r.stdout + r.stderr)[-2000:]
     assert r.returncode == 0, tail
