@@ -136,6 +136,7 @@ PROTOTYPES.update({
     "gf_smp_dropout_masks": (_i, [_vp, _vp, C.c_float]),
     "gf_adam_step_f32": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_double, _i, C.c_ulonglong]),
     "gf_smp_model_create": (_i, [_vp, _vp, C.POINTER(_vp)]),
+    "gf_smp_model_config_param_count": (C.c_size_t, [_vp]),
     "gf_smp_model_destroy": (_i, [_vp]),
     "gf_smp_model_param_count": (C.c_size_t, [_vp]),
     "gf_smp_model_set_mode": (_i, [_vp, _i]),

@@ -624,7 +624,7 @@ void gf::smp_derive_plan(gf_smp *s, bool allow_embed) {
 
 // pad_channels = false: compute at the configuration's own channel counts (the towers of a model with RisiContraction_18_dropout --
 // SMP_sigma_pairgraphs -- whose levels run op by op, where a padded width only costs)
-gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channels, gf_smp **out, int min_pad, int nClass) {
+gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channels, gf_smp **out, int min_pad, int nClass, double decay) {
     if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
     if (!cfg || !out) return fail(ctx, GF_ERR_INVALID, "gf_smp_create: null argument");
     if (cfg->nLevels < 1 || cfg->nChanels < 1 || cfg->nFeatures < 1 || cfg->nDepth < 0 || cfg->max_receptive_field < 1)
@@ -692,6 +692,7 @@ gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channel
         s->cfg.first_order = 1;
         s->cfg.max_nVertices = cfg->max_nVertices;
         s->cfg.nContractions = 2;
+        if (cfg->physics) s->cfg.decay = decay;   // (a CCN_1D tower, gf_smp_model_create only)
         s->grad_allreduce = 0;   // (no data-parallel exchange: gf_smp_set_grad_allreduce(.., 1) is refused)
     }
     s->ucfg = s->cfg;

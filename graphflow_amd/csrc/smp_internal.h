@@ -104,7 +104,9 @@ gf_status smp_wgrad_fp32_c64(gf_ctx *ctx, const float *T, const float *dO, const
 
 namespace gf {
 // min_pad: the smallest padded width the handle may compute at (32 for the towers of a slice-dropout model)
-gf_status smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channels, gf_smp **out, int min_pad = 0, int nClass = 0);   // gf_smp_create = (.., true, ..)
+// decay > 0: a first_order = 1 physics tower of CCN_1D (gfsmp::Config::decay)
+gf_status smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channels, gf_smp **out, int min_pad = 0, int nClass = 0,
+                     double decay = 0.0);   // gf_smp_create = (.., true, ..)
 // what first_order = 2, 3, 4 (SMP_1D, SMP_1D_ver2, SMP_1D_ver3) asks of the rest of a configuration: no cap (max_receptive_field ==
 // max_nVertices), nContractions = custom_matmul = physics = 0, channel counts and multiplicities that fit an int
 inline bool smp_1d_config_ok(const gf_smp_config *cfg) {

@@ -11,6 +11,8 @@
 // and the feature row handed to the head concatenates the level features level by level, tower 1 before tower 2 inside a
 // level (SMP_omega_pairgraphs.h:699-704).  The towers keep contiguous copies of their own parameters / gradients; segments
 // are copied device to device around every pass.
+#include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -18,6 +20,9 @@
 #include "libc_random.h"
 #include "smp_internal.h"
 
+namespace gf {
+struct ModelSeg { size_t model_off, tower_off, n; };   // a tower's contiguous run inside the model's parameter vector
+}
 struct gf_smp_model {
     gf_ctx *ctx = nullptr;
     gf_smp_model_config cfg;
@@ -28,7 +33,7 @@ struct gf_smp_model {
     int nLayers = 0;
     std::vector<int> lvlC;                   // channels per level
     int fwidth = 0;                          // feature columns of ONE tower
-    struct Seg { size_t model_off, tower_off, n; };
+    typedef gf::ModelSeg Seg;
     std::vector<Seg> segs[2];
     size_t head_off = 0;
     // device buffers (own)
@@ -98,6 +103,100 @@ void free_batch(gf_smp_model *m) {
     m->cap_mol = 0;
 }
 
+// What gf_smp_model_create derives from a configuration before it touches the device: level widths, head widths, the segments of the
+// towers inside the model vector.  false (and a message): a configuration it refuses.
+struct ModelPlan {
+    int nK = 18, maxV[2] = {0, 0}, fwidth = 0;
+    double decay = 0.0;                       // > 0: CCN_1D's width rule (gfsmp::Config::decay)
+    std::vector<int> lvlC, widths;
+    std::vector<ModelSeg> segs[2];
+    size_t head_off = 0, head_params = 0, n_params = 0;
+};
+
+bool model_plan(const gf_smp_model_config *cfg, ModelPlan *p, char *why, size_t nwhy) {
+    if (cfg->nTowers < 1 || cfg->nTowers > 2 || cfg->nLevels < 1 || cfg->nChanels < 1 || cfg->max_receptive_field < 1 || cfg->nKept < 0 ||
+        cfg->nKept > 18 || cfg->nFeatures[0] < 1 || (cfg->nTowers == 2 && cfg->nFeatures[1] < 1)) {   // (nFeatures: what gf_smp_create refuses of a tower)
+        snprintf(why, nwhy, "gf_smp_model_create: bad configuration");
+        return false;
+    }
+    const int nK = cfg->nContractions ? cfg->nContractions : 18;
+    if (nK != 18 && nK != 4) {
+        snprintf(why, nwhy, "gf_smp_model_create: nContractions = %d (expected 0 or 18: RisiContraction_18, 4: RisiContraction_4)", cfg->nContractions);
+        return false;
+    }
+    if (nK == 4 && cfg->nKept > 0) {
+        snprintf(why, nwhy, "gf_smp_model_create: nKept > 0 (RisiContraction_18_dropout) with nContractions = 4: no such model");
+        return false;
+    }
+    const int maxV[2] = {cfg->max_nVertices[0], cfg->max_nVertices[1] ? cfg->max_nVertices[1] : cfg->max_nVertices[0]};
+    if (cfg->first_order && (cfg->nContractions || cfg->nKept > 0 || maxV[0] < cfg->max_receptive_field || maxV[1] < cfg->max_receptive_field)) {
+        snprintf(why, nwhy, "gf_smp_model_create: first_order = 1 (SMP_theta_physics / _pairgraphs) needs nContractions = nKept = 0 and "
+                            "max_nVertices (%d, %d) >= max_receptive_field (%d)", maxV[0], maxV[1], cfg->max_receptive_field);
+        return false;
+    }
+    // CCN_1D (GraphFlow/CCN_1D.h:34-39): always two first-order towers, at least 16 channels, 0 < decay <= 1 (!(..): a NaN is refused too)
+    if (cfg->ccn_1d && (cfg->nTowers != 2 || cfg->first_order != 1 || cfg->nChanels < gfsmp::kCcnMinChanels ||
+                        !(cfg->nChanels_decay > 0.0 && cfg->nChanels_decay <= 1.0))) {
+        snprintf(why, nwhy, "gf_smp_model_create: ccn_1d = 1 (CCN_1D) needs nTowers = 2 (%d), first_order = 1 (%d), nChanels >= 16 (%d) and "
+                            "0 < nChanels_decay <= 1 (%g)", cfg->nTowers, cfg->first_order, cfg->nChanels, cfg->nChanels_decay);
+        return false;
+    }
+    p->nK = nK;
+    p->maxV[0] = maxV[0];
+    p->maxV[1] = maxV[1];
+    p->decay = cfg->ccn_1d ? cfg->nChanels_decay : 0.0;
+    gfsmp::Config widths = {cfg->nLevels, cfg->nChanels, 1, 0, cfg->max_receptive_field, 0};   // (a tower's width rule: halving, or the decay)
+    widths.physics = 1;
+    widths.decay = p->decay;
+    const int L = cfg->nLevels;
+    for (int l = 0; l <= L; ++l) {
+        p->lvlC.push_back(widths.level_channels(l));
+        p->fwidth += p->lvlC.back();
+    }
+    size_t off = 0;
+    // the H matrices come first (one per tower), then the levels, towers interleaved inside a level
+    size_t toff[2] = {0, 0};
+    for (int t = 0; t < cfg->nTowers; ++t) {
+        const size_t nH = (size_t)cfg->nChanels * cfg->nFeatures[t];
+        p->segs[t].push_back({off, 0, nH});
+        off += nH;
+        toff[t] = nH;
+    }
+    for (int l = 1; l <= L; ++l)
+        for (int t = 0; t < cfg->nTowers; ++t) {
+            // (first order: the per-size (lambda1, lambda2, b) blocks, then K_l -- one contiguous segment in either layout)
+            const size_t n = cfg->first_order ? (size_t)maxV[t] * (2 + p->lvlC[l]) + (size_t)2 * p->lvlC[l - 1] * p->lvlC[l]
+                                              : (size_t)nK * p->lvlC[l - 1] * p->lvlC[l] + p->lvlC[l];
+            p->segs[t].push_back({off, toff[t], n});
+            off += n;
+            toff[t] += n;
+        }
+    p->head_off = off;
+    // head widths: physics nTotal -> nTotal / 2 -> 1 (:229-238); pairgraphs nTotal -> max(nTotal / 2, 10) -> max(that / 2, 10) -> 1;
+    // CCN_1D nTotal -> max(int(ceil(nTotal * decay)), 16) -> max(int(ceil(that * decay)), 16) -> 1 (CCN_1D.h:352-353)
+    const int nTotal = cfg->nTowers * p->fwidth;
+    p->widths.push_back(nTotal);
+    if (p->decay > 0.0) {
+        for (int i = 0; i < 2; ++i) {
+            const int h = int(std::ceil(p->widths.back() * p->decay));
+            p->widths.push_back(h > gfsmp::kCcnMinChanels ? h : gfsmp::kCcnMinChanels);
+        }
+    } else if (cfg->nTowers == 1) {
+        p->widths.push_back(nTotal / 2);
+    } else {
+        const int h1 = nTotal / 2 > 10 ? nTotal / 2 : 10, h2 = h1 / 2 > 10 ? h1 / 2 : 10;
+        p->widths.push_back(h1);
+        p->widths.push_back(h2);
+    }
+    if (p->widths[1] < 1) {
+        snprintf(why, nwhy, "gf_smp_model_create: %d feature columns leave no hidden units (the reference uses nTotal / 2)", nTotal);
+        return false;
+    }
+    p->head_params = gf_head_param_count((int)p->widths.size() - 1, p->widths.data());
+    p->n_params = off + p->head_params;
+    return true;
+}
+
 }  // namespace
 }  // namespace gf
 
@@ -108,19 +207,11 @@ extern "C" {
 gf_status gf_smp_model_create(gf_ctx *ctx, const gf_smp_model_config *cfg, gf_smp_model **out) {
     if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
     if (!cfg || !out) return fail(ctx, GF_ERR_INVALID, "gf_smp_model_create: null argument");
-    if (cfg->nTowers < 1 || cfg->nTowers > 2 || cfg->nLevels < 1 || cfg->nChanels < 1 || cfg->max_receptive_field < 1 || cfg->nKept < 0 ||
-        cfg->nKept > 18)
-        return fail(ctx, GF_ERR_INVALID, "gf_smp_model_create: bad configuration");
-    const int nK = cfg->nContractions ? cfg->nContractions : 18;
-    if (nK != 18 && nK != 4)
-        return fail(ctx, GF_ERR_INVALID, "gf_smp_model_create: nContractions = %d (expected 0 or 18: RisiContraction_18, 4: RisiContraction_4)",
-                    cfg->nContractions);
-    if (nK == 4 && cfg->nKept > 0)
-        return fail(ctx, GF_ERR_INVALID, "gf_smp_model_create: nKept > 0 (RisiContraction_18_dropout) with nContractions = 4: no such model");
-    const int maxV[2] = {cfg->max_nVertices[0], cfg->max_nVertices[1] ? cfg->max_nVertices[1] : cfg->max_nVertices[0]};
-    if (cfg->first_order && (cfg->nContractions || cfg->nKept > 0 || maxV[0] < cfg->max_receptive_field || maxV[1] < cfg->max_receptive_field))
-        return fail(ctx, GF_ERR_INVALID, "gf_smp_model_create: first_order = 1 (SMP_theta_physics / _pairgraphs) needs nContractions = nKept = 0 and "
-                                         "max_nVertices (%d, %d) >= max_receptive_field (%d)", maxV[0], maxV[1], cfg->max_receptive_field);
+    gf::ModelPlan plan;
+    char why[512];
+    if (!gf::model_plan(cfg, &plan, why, sizeof why)) return fail(ctx, GF_ERR_INVALID, "%s", why);   // (before anything is allocated)
+    const int nK = plan.nK;
+    const int *maxV = plan.maxV;
     gf_smp_model *m = new gf_smp_model();
     m->ctx = ctx;
     m->cfg = *cfg;
@@ -128,57 +219,27 @@ gf_status gf_smp_model_create(gf_ctx *ctx, const gf_smp_model_config *cfg, gf_sm
     m->cfg.max_nVertices[1] = maxV[1];
     m->nTowers = cfg->nTowers;
     m->L = cfg->nLevels;
-    for (int l = 0; l <= m->L; ++l) {
-        int c = cfg->nChanels >> l;
-        m->lvlC.push_back(c < 1 ? 1 : c);
-        m->fwidth += m->lvlC.back();
-    }
-    size_t off = 0;
-    // the H matrices come first (one per tower), then the levels, towers interleaved inside a level
-    size_t toff[2] = {0, 0};
+    m->lvlC = plan.lvlC;
+    m->fwidth = plan.fwidth;
+    m->widths = plan.widths;
+    m->nLayers = (int)m->widths.size() - 1;
+    m->head_off = plan.head_off;
+    m->head_params = plan.head_params;
+    m->n_params = plan.n_params;
     for (int t = 0; t < m->nTowers; ++t) {
+        m->segs[t] = plan.segs[t];
         gf_smp_config tc = {cfg->nLevels, cfg->nChanels, cfg->nFeatures[t], 0, cfg->max_receptive_field, 0, cfg->first_order ? 0 : nK, 0, 1,
                             cfg->first_order ? 1 : 0, cfg->first_order ? maxV[t] : 0};
         // (nKept > 0, RisiContraction_18_dropout: towers of up to 32 channels run the fused levels with per-product slice factors since
         //  round 5 -- padded like the others; wider ones keep their levels op by op, at their own halving widths)
-        gf_status st = gf::smp_create(ctx, &tc, /*pad_channels=*/cfg->nKept <= 0 || cfg->nChanels <= 32, &m->tower[t]);
+        gf_status st = gf::smp_create(ctx, &tc, /*pad_channels=*/cfg->nKept <= 0 || cfg->nChanels <= 32, &m->tower[t], /*min_pad=*/0, /*nClass=*/0,
+                                      plan.decay);
         if (st != GF_OK) {
             gf_smp_model_destroy(m);
             return st;
         }
         m->tower_params[t] = gf_smp_param_count(m->tower[t]);
-        const size_t nH = (size_t)cfg->nChanels * cfg->nFeatures[t];
-        m->segs[t].push_back({off, 0, nH});
-        off += nH;
-        toff[t] = nH;
     }
-    for (int l = 1; l <= m->L; ++l)
-        for (int t = 0; t < m->nTowers; ++t) {
-            // (first order: the per-size (lambda1, lambda2, b) blocks, then K_l -- one contiguous segment in either layout)
-            const size_t n = cfg->first_order ? (size_t)maxV[t] * (2 + m->lvlC[l]) + (size_t)2 * m->lvlC[l - 1] * m->lvlC[l]
-                                              : (size_t)nK * m->lvlC[l - 1] * m->lvlC[l] + m->lvlC[l];
-            m->segs[t].push_back({off, toff[t], n});
-            off += n;
-            toff[t] += n;
-        }
-    m->head_off = off;
-    // head widths: physics nTotal -> nTotal / 2 -> 1 (:229-238); pairgraphs nTotal -> max(nTotal / 2, 10) -> max(that / 2, 10) -> 1
-    const int nTotal = m->nTowers * m->fwidth;
-    m->widths.push_back(nTotal);
-    if (m->nTowers == 1) {
-        m->widths.push_back(nTotal / 2);
-    } else {
-        const int h1 = nTotal / 2 > 10 ? nTotal / 2 : 10, h2 = h1 / 2 > 10 ? h1 / 2 : 10;
-        m->widths.push_back(h1);
-        m->widths.push_back(h2);
-    }
-    m->nLayers = (int)m->widths.size() - 1;
-    if (m->widths[1] < 1) {
-        gf_smp_model_destroy(m);
-        return fail(ctx, GF_ERR_INVALID, "gf_smp_model_create: %d feature columns leave no hidden units (the reference uses nTotal / 2)", nTotal);
-    }
-    m->head_params = gf_head_param_count(m->nLayers, m->widths.data());
-    m->n_params = off + m->head_params;
     for (int t = 0; t < m->nTowers; ++t) {
         if (hipMalloc(reinterpret_cast<void **>(&m->tp[t]), m->tower_params[t] * sizeof(float)) != hipSuccess ||
             hipMalloc(reinterpret_cast<void **>(&m->tg[t]), m->tower_params[t] * sizeof(float)) != hipSuccess) {
@@ -194,6 +255,13 @@ gf_status gf_smp_model_create(gf_ctx *ctx, const gf_smp_model_config *cfg, gf_sm
     }
     *out = m;
     return GF_OK;
+}
+
+// the parameter count gf_smp_model_create would give the configuration; 0: one it refuses.  Host only.
+size_t gf_smp_model_config_param_count(const gf_smp_model_config *cfg) {
+    gf::ModelPlan plan;
+    char why[512];
+    return cfg && gf::model_plan(cfg, &plan, why, sizeof why) ? plan.n_params : 0;
 }
 
 gf_status gf_smp_model_destroy(gf_smp_model *m) {
@@ -239,6 +307,30 @@ gf_status gf_smp_model_prepare(gf_smp_model *m, int nMol, const int *nVertices1,
         return fail(ctx, GF_ERR_INVALID, "gf_smp_model_prepare: bad argument");
     const int *nv[2] = {nVertices1, nVertices2}, *ad[2] = {adj1, adj2};
     const double *fe[2] = {feature1, feature2};
+    // CCN_1D divides every vertex's feature row by its L1 norm before level 0 (CCN_1D.h:439-448).  A row of zeros is 0 / 0 there:
+    // refused here, before either tower has taken the batch.
+    std::vector<double> normed[2];
+    if (m->cfg.ccn_1d)
+        for (int t = 0; t < m->nTowers; ++t) {
+            const int F = m->cfg.nFeatures[t];
+            size_t rows = 0;
+            for (int i = 0; i < nMol; ++i) {
+                if (nv[t][i] < 1) return fail(ctx, GF_ERR_INVALID, "gf_smp_model_prepare: sample %d, tower %d has %d vertices", i, t + 1, nv[t][i]);
+                rows += (size_t)nv[t][i];
+            }
+            normed[t].assign(fe[t], fe[t] + rows * F);
+            size_t r = 0;
+            for (int i = 0; i < nMol; ++i)
+                for (int v = 0; v < nv[t][i]; ++v, ++r) {
+                    double norm_l1 = 0.0;
+                    for (int f = 0; f < F; ++f) norm_l1 += std::fabs(normed[t][r * F + f]);
+                    if (!(norm_l1 > 0.0))
+                        return fail(ctx, GF_ERR_INVALID, "gf_smp_model_prepare: CCN_1D normalises every feature row by its L1 norm, and the row of "
+                                                         "sample %d, tower %d, vertex %d is zero", i, t + 1, v);
+                    for (int f = 0; f < F; ++f) normed[t][r * F + f] /= norm_l1;
+                }
+            fe[t] = normed[t].data();
+        }
     for (int t = 0; t < m->nTowers; ++t) {
         gf_status st = gf_smp_prepare(m->tower[t], nMol, nv[t], ad[t], fe[t]);
         if (st != GF_OK) return st;

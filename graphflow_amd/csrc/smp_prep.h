@@ -9,6 +9,7 @@
 #ifndef GF_SMP_PREP_H_INCLUDED
 #define GF_SMP_PREP_H_INCLUDED
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -37,6 +38,8 @@ template <class T>
 using tvec = std::vector<T, TableAlloc<T> >;
 
 constexpr int kUnrestrictedSplit = 16;   // node chunks per size bucket in the reduction of a dense filter's gradient
+
+constexpr int kCcnMinChanels = 16;      // CCN_1D_MINIMUM_NUMBER_OF_CHANELS (GraphFlow/CCN_1D.h:30)
 
 struct Config {
     int nLevels, nChanels, nFeatures, nDepth, max_receptive_field, has_WL_ordering;
@@ -73,6 +76,9 @@ struct Config {
     // tables, channel counts, slopes, read-out and scalar_l; gf_smp_config itself asks for first_order = steerable_2d = 0.
     // Per level: for size = 1 .. max_nVertices (W_s [s][s] | W1_s, W2_s [s][s] | W_s [s][s][C], then b_s[C_l]); form 3: then scalar_l.
     int unrestricted = 0;
+    // > 0: a tower of CCN_1D (GraphFlow/CCN_1D.h:200, :217; gf_smp_model_config.ccn_1d): C_0 = nChanels, C_l = max(int(ceil(C_{l-1} * decay)), 16),
+    // the product in double as the class writes it.  0: the halving of the other towers.
+    double decay = 0.0;
     size_t filter_floats(int l) const { return unrestricted == 3 ? (size_t)level_channels(l - 1) : (size_t)unrestricted; }   // per s^2
     bool per_size() const { return first_order || steerable_2d; }   // a handle on the th_* tables, per-size blocks in front of the matrix block
     bool concat() const { return first_order >= 3 || steerable_2d == 2; }   // C_l = 2 C_{l-1}
@@ -95,6 +101,14 @@ struct Config {
     int readout_rows() const { return nClass > 1 ? nClass : 1; }   // rows of W: [1][C] is the regression's [C]
     bool square() const { return !physics || uniform; }   // K_l is [nContractions C][C] at every level
     int level_channels(int l) const {
+        if (decay > 0.0) {
+            int c = nChanels;
+            for (int k = 0; k < l; ++k) {
+                const int d = int(std::ceil(c * decay));
+                c = d > kCcnMinChanels ? d : kCcnMinChanels;
+            }
+            return c;
+        }
         if (concat()) return nChanels << l;
         if (square()) return nChanels;
         int c = nChanels >> l;

@@ -8,6 +8,9 @@
 //   SMP_gamma_physics_hip([use_coulomb,] max_nVertices, max_receptive_field, nLevels, nChanels, nFeatures)
 //                                                                                                  GraphFlow/SMP_gamma_physics.h:31,47
 //   SMP_gamma_pairgraphs_hip(max_nV_1, max_nV_2, max_rf, nLevels, nChanels, nFeatures_1, _2)       GraphFlow/SMP_gamma_pairgraphs.h
+//   SMP_theta_physics_hip(max_nVertices, max_receptive_field, nLevels, nChanels, nFeatures)        GraphFlow/SMP_theta_physics.h
+//   SMP_theta_pairgraphs_hip(max_nV_1, max_nV_2, max_rf, nLevels, nChanels, nFeatures_1, _2)       GraphFlow/SMP_theta_pairgraphs.h
+//   CCN_1D_hip(max_nV_1, max_nV_2, max_rf, nLevels, nChanels, nFeatures_1, _2, nChanels_decay)     GraphFlow/CCN_1D.h:34
 // with the reference's public training / inference methods: BatchLearn, Threaded_BatchLearn, getLoss, Predict,
 // Threaded_Predict, init_multi_threads (accepted, nothing to do: a batch is one device pass), save_model / load_model (the
 // text format of SMP_omega_physics.h:927-949: every parameter value in registration order).  The constructors draw the initial
@@ -27,14 +30,23 @@
 
 class SMP_model_hip {
 protected:
-    // nContractions: 18 (RisiContraction_18 / _18_dropout towers) or 4 (the `_gamma` models: RisiContraction_4, K_l [4 C_{l-1}][C_l])
-    SMP_model_hip(int nTowers, int maxV1, int maxV2, int max_rf, int nLevels, int nChanels, int F1, int F2, int nKept, int nContractions = 18)
+    // nContractions: 18 (RisiContraction_18 / _18_dropout towers) or 4 (the `_gamma` models: RisiContraction_4, K_l [4 C_{l-1}][C_l]);
+    // 0 with first_order = 1: the first-order towers of the `_theta` models, and with ccn_1d and nChanels_decay those of CCN_1D
+    SMP_model_hip(int nTowers, int maxV1, int maxV2, int max_rf, int nLevels, int nChanels, int F1, int F2, int nKept, int nContractions = 18,
+                  int first_order = 0, double nChanels_decay = 0.0, bool ccn_1d = false)
         : net(NULL), towers(nTowers) {
         maxV[0] = maxV1;
         maxV[1] = maxV2;
         nF[0] = F1;
         nF[1] = F2;
         gf_smp_model_config cfg = {nTowers, nLevels, nChanels, max_rf, {F1, F2}, nKept, nContractions};
+        if (first_order) {
+            cfg.first_order = first_order;
+            cfg.max_nVertices[0] = maxV1;
+            cfg.max_nVertices[1] = maxV2;
+        }
+        cfg.ccn_1d = ccn_1d ? 1 : 0;
+        cfg.nChanels_decay = nChanels_decay;
         must(gf_smp_model_create(gfhost::default_context(), &cfg, &net), "gf_smp_model_create");
         std::vector<float> w(gf_smp_model_param_count(net));
         must(gf_smp_model_uniform_init_host(net, &w[0]), "gf_smp_model_uniform_init_host");  // weights_initialization()
@@ -139,6 +151,9 @@ protected:
     struct gamma_wiring {};
     SMP_omega_physics_hip(gamma_wiring, int max_nVertices, int max_receptive_field, int nLevels, int nChanels, int nFeatures)
         : SMP_model_hip(1, max_nVertices, 0, max_receptive_field, nLevels, nChanels, nFeatures, 0, 0, 4) {}
+    struct theta_wiring {};
+    SMP_omega_physics_hip(theta_wiring, int max_nVertices, int max_receptive_field, int nLevels, int nChanels, int nFeatures)
+        : SMP_model_hip(1, max_nVertices, 0, max_receptive_field, nLevels, nChanels, nFeatures, 0, 0, 0, 1) {}
 
 public:
     template <class Graph>
@@ -191,6 +206,12 @@ protected:
     SMP_omega_pairgraphs_hip(gamma_wiring, int max_nVertices_1, int max_nVertices_2, int max_receptive_field, int nLevels, int nChanels,
                              int nFeatures_1, int nFeatures_2)
         : SMP_model_hip(2, max_nVertices_1, max_nVertices_2, max_receptive_field, nLevels, nChanels, nFeatures_1, nFeatures_2, 0, 4) {}
+    // first-order towers; ccn_1d: CCN_1D's width rule, head and feature normalisation at nChanels_decay
+    struct theta_wiring {};
+    SMP_omega_pairgraphs_hip(theta_wiring, int max_nVertices_1, int max_nVertices_2, int max_receptive_field, int nLevels, int nChanels,
+                             int nFeatures_1, int nFeatures_2, double nChanels_decay = 0.0, bool ccn_1d = false)
+        : SMP_model_hip(2, max_nVertices_1, max_nVertices_2, max_receptive_field, nLevels, nChanels, nFeatures_1, nFeatures_2, 0, 0, 1,
+                        nChanels_decay, ccn_1d) {}
 
 public:
     template <class Graph>
@@ -263,6 +284,34 @@ public:
                              int nFeatures_2)
         : SMP_omega_pairgraphs_hip(gamma_wiring(), max_nVertices_1, max_nVertices_2, max_receptive_field, nLevels, nChanels, nFeatures_1,
                                    nFeatures_2) {}
+};
+
+// SMP_theta_physics (GraphFlow/SMP_theta_physics.h): one first-order tower (SMP_theta's level, K_l [2 C_{l-1}][C_l], per-size lambda1,
+// lambda2, b), channels halving per level, every level read out, the one-hidden-layer head
+class SMP_theta_physics_hip : public SMP_omega_physics_hip {
+public:
+    SMP_theta_physics_hip(int max_nVertices, int max_receptive_field, int nLevels, int nChanels, int nFeatures)
+        : SMP_omega_physics_hip(theta_wiring(), max_nVertices, max_receptive_field, nLevels, nChanels, nFeatures) {}
+};
+
+// SMP_theta_pairgraphs (GraphFlow/SMP_theta_pairgraphs.h): two such towers and the two-hidden-layer head
+class SMP_theta_pairgraphs_hip : public SMP_omega_pairgraphs_hip {
+public:
+    SMP_theta_pairgraphs_hip(int max_nVertices_1, int max_nVertices_2, int max_receptive_field, int nLevels, int nChanels, int nFeatures_1,
+                             int nFeatures_2)
+        : SMP_omega_pairgraphs_hip(theta_wiring(), max_nVertices_1, max_nVertices_2, max_receptive_field, nLevels, nChanels, nFeatures_1,
+                                   nFeatures_2) {}
+};
+
+// CCN_1D (GraphFlow/CCN_1D.h): SMP_theta_pairgraphs with widths and head sized by nChanels_decay (at least 16 channels), feature rows
+// divided by their L1 norm.  What the class asserts (nChanels >= 16, 0 < nChanels_decay <= 1, the cap within both vertex limits) the
+// library refuses, and the constructor aborts with its message.
+class CCN_1D_hip : public SMP_omega_pairgraphs_hip {
+public:
+    CCN_1D_hip(int max_nVertices_1, int max_nVertices_2, int max_receptive_field, int nLevels, int nChanels, int nFeatures_1, int nFeatures_2,
+               double nChanels_decay)
+        : SMP_omega_pairgraphs_hip(theta_wiring(), max_nVertices_1, max_nVertices_2, max_receptive_field, nLevels, nChanels, nFeatures_1,
+                                   nFeatures_2, nChanels_decay, true) {}
 };
 
 #endif

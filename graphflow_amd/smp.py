@@ -446,28 +446,38 @@ class SMPClassifier(SMPOmega):
 class SMPModelConfig(C.Structure):
     _fields_ = [("nTowers", C.c_int), ("nLevels", C.c_int), ("nChanels", C.c_int), ("max_receptive_field", C.c_int),
                 ("nFeatures", C.c_int * 2), ("nKept", C.c_int), ("nContractions", C.c_int), ("first_order", C.c_int),
-                ("max_nVertices", C.c_int * 2)]
+                ("max_nVertices", C.c_int * 2), ("ccn_1d", C.c_int), ("nChanels_decay", C.c_double)]
 
 
 class SMPModel:
     """The _physics (one tower) / _pairgraphs (two towers, nKept > 0: SMP_sigma_pairgraphs) models of GraphFlow through
     gf_smp_model_*.  nContractions = 4: SMP_gamma_physics / SMP_gamma_pairgraphs (RisiContraction_4, K_l[4 C_{l-1}, C_l]).
     first_order=True with max_nVertices (an int, or one per tower): SMP_theta_physics / SMP_theta_pairgraphs.
+    ccn_1d=True with nChanels_decay: CCN_1D (see CCN1D).
     Parameters / gradients: one flat fp32 tensor in the class's registration order."""
 
     def __init__(self, nLevels, nChanels, max_receptive_field, nFeatures, nKept=0, ctx=None, nContractions=18, first_order=False,
-                 max_nVertices=0):
-        feats = list(nFeatures) if isinstance(nFeatures, (list, tuple)) else [nFeatures]
+                 max_nVertices=0, ccn_1d=False, nChanels_decay=0.0):
         self.ctx = ctx or default_context()
         self.lib = self.ctx.lib
-        self.cfg = SMPModelConfig(len(feats), nLevels, nChanels, max_receptive_field, (C.c_int * 2)(*(feats + [0])[:2]), nKept,
-                                  0 if first_order else nContractions, 1 if first_order else 0,
-                                  (C.c_int * 2)(*((list(max_nVertices) if isinstance(max_nVertices, (list, tuple)) else [max_nVertices, 0]) + [0])[:2]))
+        self.cfg = SMPModel.config(nLevels, nChanels, max_receptive_field, nFeatures, nKept, nContractions, first_order, max_nVertices,
+                                   ccn_1d, nChanels_decay)
+        self._adam = None
         h = C.c_void_p()
         self.ctx.check(self.lib.gf_smp_model_create(self.ctx.handle, C.byref(self.cfg), C.byref(h)))
         self.handle = h
         self.n_params = self.lib.gf_smp_model_param_count(h)
         self.n_mol = 0
+
+    @staticmethod
+    def config(nLevels, nChanels, max_receptive_field, nFeatures, nKept=0, nContractions=18, first_order=False, max_nVertices=0,
+               ccn_1d=False, nChanels_decay=0.0):
+        """the gf_smp_model_config of a model (gf_smp_model_config_param_count takes it without a device)"""
+        feats = list(nFeatures) if isinstance(nFeatures, (list, tuple)) else [nFeatures]
+        maxV = list(max_nVertices) if isinstance(max_nVertices, (list, tuple)) else [max_nVertices, 0]
+        return SMPModelConfig(len(feats), nLevels, nChanels, max_receptive_field, (C.c_int * 2)(*(feats + [0])[:2]), nKept,
+                              0 if first_order else nContractions, 1 if first_order else 0, (C.c_int * 2)(*(maxV + [0])[:2]),
+                              1 if ccn_1d else 0, float(nChanels_decay))
 
     @staticmethod
     def _pack(graphs):
@@ -510,6 +520,32 @@ class SMPModel:
                                                       1 if accumulate else 0))
         return grads
 
+    def adam_step(self, params, grads, learning_rate, nBatch):
+        """Adam::Learn(learning_rate, nBatch) as the classes' BatchLearn applies it, over the whole registration-order vector; grads =
+        the batch sum of backward().  The moments live with this object."""
+        if self._adam is None:
+            self._adam = [torch.zeros_like(params), torch.zeros_like(params), 0]
+        m, v, n = self._adam
+        self.ctx.check(self.lib.gf_adam_step_f32(self.ctx.handle, C.c_void_p(params.data_ptr()), C.c_void_p(grads.data_ptr()),
+                                                 C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()), self.n_params, float(learning_rate),
+                                                 int(nBatch), n))
+        self._adam[2] = n + self.n_params
+        return params
+
+    def save_model(self, params, path):
+        """The classes' save_model: every parameter value in registration order as text, which their load_model reads.  Nine significant
+        digits: load_model gives back the same float32 bits."""
+        with open(str(path), "w") as f:
+            f.write("".join("%.9g " % x for x in params.detach().cpu().numpy()))
+
+    def load_model(self, path):
+        """The classes' load_model: the flat parameter tensor on the context's device from a text checkpoint (ours or the reference's)."""
+        with open(str(path)) as f:
+            vals = np.array(f.read().split(), dtype=np.float64)
+        if vals.size != self.n_params:
+            raise ValueError("load_model: %s holds %d values, the model has %d parameters" % (path, vals.size, self.n_params))
+        return torch.as_tensor(vals.astype(np.float32)).to(self.ctx.device)
+
     def close(self):
         if getattr(self, "handle", None):
             self.lib.gf_smp_model_destroy(self.handle)
@@ -520,3 +556,21 @@ class SMPModel:
             self.close()
         except Exception:
             pass
+
+
+class CCN1D(SMPModel):
+    """Batched CCN_1D (GraphFlow/CCN_1D.h), the first-order covariant compositional network on a pair of graphs: two SMP_theta towers
+    whose widths decay, C_0 = nChanels, C_l = max(ceil(C_{l-1} * nChanels_decay), 16); every vertex's feature row divided by its L1 norm
+    (a row of zeros is refused at prepare()); a head nTotal -> max(ceil(nTotal * decay), 16) -> max(ceil(that * decay), 16) -> 1.
+    Parameters in registration order: H_1[C, F_1], H_2[C, F_2]; for l = 1..L: (lambda1_s, lambda2_s, b_s[C_l]) for s = 1..max_nVertices_1
+    and K1_l[2 C_{l-1}, C_l], then the same for tower 2; W1, W2, W3.  The constructor takes the reference's argument list."""
+
+    def __init__(self, max_nVertices_1, max_nVertices_2, max_receptive_field, nLevels, nChanels, nFeatures_1, nFeatures_2, nChanels_decay,
+                 ctx=None):
+        super().__init__(nLevels, nChanels, max_receptive_field, [nFeatures_1, nFeatures_2], ctx=ctx, first_order=True,
+                         max_nVertices=[max_nVertices_1, max_nVertices_2], ccn_1d=True, nChanels_decay=nChanels_decay)
+
+    @staticmethod
+    def config(max_nVertices_1, max_nVertices_2, max_receptive_field, nLevels, nChanels, nFeatures_1, nFeatures_2, nChanels_decay):
+        return SMPModel.config(nLevels, nChanels, max_receptive_field, [nFeatures_1, nFeatures_2], first_order=True,
+                               max_nVertices=[max_nVertices_1, max_nVertices_2], ccn_1d=True, nChanels_decay=nChanels_decay)

@@ -571,8 +571,22 @@ typedef struct {
      * the interleaving of two towers' parameters as in the other models.  max_nVertices is per tower (SMP_theta_pairgraphs.h:31:
      * max_nVertices_1 / _2; [1] = 0 means [0]).  nContractions and nKept must be 0.  Zero: the models above. */
     int first_order, max_nVertices[2];
+    /* ccn_1d = 1: CCN_1D (GraphFlow/CCN_1D.h), the first-order covariant compositional network on a pair of graphs: SMP_theta_pairgraphs with
+     *   - the widths C_0 = nChanels, C_l = max(int(ceil(C_{l-1} * nChanels_decay)), 16) in both towers (the product in double, :200, :217),
+     *   - the head nTotal -> max(int(ceil(nTotal * decay)), 16) -> max(int(ceil(that * decay)), 16) -> 1 (:352-353),
+     *   - every vertex's feature row divided by its L1 norm before level 0 (:439-448); gf_smp_model_prepare does it on the host and refuses
+     *     a row of zeros (0 / 0 in the class) with GF_ERR_INVALID, naming sample, tower and vertex.
+     * Fields, cap, children, per-size blocks, read-out, registration order (H_1, H_2; per level tower 1's max_nVertices[0] size entries and
+     * K1_l, then tower 2's; W1, W2, W3), weights_initialization, Adam and the multiplicity of dlambda are SMP_theta_pairgraphs'.
+     * Required, else GF_ERR_INVALID before anything is allocated: nTowers = 2, first_order = 1, nKept = nContractions = 0, nChanels >= 16,
+     * 0 < nChanels_decay <= 1, max_receptive_field <= both max_nVertices.  Zero (an initialiser that stops before the fields): the models
+     * above, nChanels_decay is not read. */
+    int ccn_1d;
+    double nChanels_decay;
 } gf_smp_model_config;
 gf_status gf_smp_model_create(gf_ctx *ctx, const gf_smp_model_config *cfg, gf_smp_model **out);
+/* host only: the parameter count gf_smp_model_create gives the configuration, 0 for one it refuses */
+size_t    gf_smp_model_config_param_count(const gf_smp_model_config *cfg);
 gf_status gf_smp_model_destroy(gf_smp_model *model);
 size_t    gf_smp_model_param_count(const gf_smp_model *model);
 gf_status gf_smp_model_set_mode(gf_smp_model *model, int train);   /* SMP_sigma_pairgraphs::setMode (:139-149); default train */
