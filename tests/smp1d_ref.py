@@ -24,6 +24,7 @@ together.  Every other gradient is plain.
 The receptive fields are an INPUT, as in theta_ref (whose graph helpers this file uses)."""
 import numpy as np
 
+from theta_ref import executor_multiplicity as shared_op_multiplicity
 from theta_ref import fields_of, hop_distances, wl_features  # noqa: F401
 
 READOUT_ALPHA = 0.01
@@ -51,21 +52,8 @@ def multiplicity(version, j):
 
 
 def executor_multiplicity(version, k):
-    """The same numbers from the executor's semantics: k vertices of one size, processed in descending order; `depth` shared ops between a
-    vertex's op and lambda, every one adding its running gradient to the next on each appearance.  Returns the count of each vertex,
-    ascending."""
-    depth = 3 if version == 1 else 1
-    out = []
-    for j in range(1, k + 1):           # unit gradient at the j-th vertex (ascending) only
-        ops = [0] * depth                # gradients of the shared ops, nearest the vertex first
-        lam = 0
-        for v in range(k, 0, -1):        # reverse execution order
-            ops[0] += 1 if v == j else 0
-            for d in range(1, depth):
-                ops[d] += ops[d - 1]
-            lam += ops[-1]
-        out.append(lam)
-    return out
+    """the same numbers from the executor's semantics (theta_ref.executor_multiplicity): three shared ops in a row for version 1, else one"""
+    return shared_op_multiplicity(3 if version == 1 else 1, k)
 
 
 def split(p, version, C, FD, L, maxV, nClass=0):

@@ -21,6 +21,7 @@ is per vertex), b_s (VectorAddTensor per vertex), H and W are plain.
 The receptive fields are an INPUT, as in theta_ref (whose graph helpers this file uses)."""
 import numpy as np
 
+from theta_ref import executor_multiplicity as shared_op_multiplicity
 from theta_ref import fields_of, hop_distances, wl_features  # noqa: F401
 
 ALPHA = 0.01
@@ -44,21 +45,8 @@ def multiplicity(form, j):
 
 
 def executor_multiplicity(form, k):
-    """The same numbers from the executor's semantics: k vertices of one size, processed in descending order; `depth` shared ops between a
-    vertex's op and lambda, every one adding its running gradient to the next on each appearance.  Returns the count of each vertex,
-    ascending."""
-    depth = 2 if form == 1 else 1
-    out = []
-    for j in range(1, k + 1):
-        ops = [0] * depth
-        lam = 0
-        for v in range(k, 0, -1):
-            ops[0] += 1 if v == j else 0
-            for d in range(1, depth):
-                ops[d] += ops[d - 1]
-            lam += ops[-1]
-        out.append(lam)
-    return out
+    """the same numbers from the executor's semantics (theta_ref.executor_multiplicity): two shared ops in a row for form 1, else one"""
+    return shared_op_multiplicity(2 if form == 1 else 1, k)
 
 
 def param_count(form, C, FD, L, maxV, nClass=0):

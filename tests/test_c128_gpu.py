@@ -243,16 +243,8 @@ def test_no_kernel_reads_what_nobody_wrote_at_128():
     in a child process that starts with it.  The 128-channel path leans on unwritten memory in three places, and none may be read into
     a result: the accumulating passes load dT blocks that skip_zero_grads never stores (their sums go to the scratch rows), the weight
     gradients take column maxima over all of T and dO (T is written densely at 128), and the partial images are filled by four jobs."""
-    import os
-    import subprocess
-    import sys
-    env = dict(os.environ, GF_POISON="1")
-    sel = "level_shaped_rows or ragged_row_counts or one_sub_block or model_against_the_port"
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k", sel, "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, timeout=600)
-    tail = (r.stdout + r.stderr)[-2000:]
-    assert r.returncode == 0, tail
-    assert " passed" in tail and "failed" not in tail, tail
+    from field_suite import run_under_poison
+    run_under_poison(__file__, "level_shaped_rows or ragged_row_counts or one_sub_block or model_against_the_port")
 
 
 # ---- 3. the plan ---------------------------------------------------------------------------------------------------------------

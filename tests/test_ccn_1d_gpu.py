@@ -5,13 +5,13 @@ without a golden against tests/ccn1d_ref.py, which tests/test_ccn_1d.py pins to 
 tests/test_smp_theta_gpu.py."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import ccn1d_ref
+import field_suite as kit
+from field_suite import TOL, blockwise, dev, load_golden as load
 from make_ccn1d_golden import demo_pairs, model_blocks, random_params
 from theta_ref import fields_of
 from test_smp_theta_gpu import packing_batch
@@ -19,18 +19,6 @@ from util import rel_err
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-
-TOL = 1e-5   # the suite's end-to-end tolerance (tests/util.py)
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def dev(x, dtype=np.float32):
-    return torch.as_tensor(np.ascontiguousarray(x, dtype=dtype)).cuda()
-
-
-def load(name):
-    with np.load(os.path.join(HERE, "golden", name)) as z:
-        return {k: z[k] for k in z.files}
 
 
 def golden_cases():
@@ -43,16 +31,6 @@ def golden_cases():
     return out
 
 
-def blockwise(x, ref, blocks):
-    """the largest rel_err over the parameter blocks: one norm over the whole vector cannot see an error confined to a small block"""
-    off, worst = 0, (0.0, "")
-    for name, n in blocks:
-        worst = max(worst, (rel_err(x[off:off + n], ref[off:off + n]), name))
-        off += n
-    assert off == ref.size
-    return worst
-
-
 def settings(c):
     maxV1, maxV2, cap, L, Cn = (int(x) for x in c["cfg"])
     return maxV1, maxV2, cap, L, Cn, float(c["decay"][0]), [c["feature"].shape[1], c["feature2"].shape[1]]
@@ -61,16 +39,7 @@ def settings(c):
 def run_pairs(cfg, g1, g2, targets, params, ctx=None):
     """prediction, loss and the batch gradient of CCN1D(*cfg) on the pairs (g1[i], g2[i]), as float64 arrays"""
     from graphflow_amd.smp import CCN1D
-    net = CCN1D(*cfg, ctx=ctx)
-    assert net.n_params == len(params)
-    net.prepare(g1, g2)
-    p = dev(params)
-    pred, loss = net.forward(p, dev(targets))
-    grads = torch.empty(net.n_params, device="cuda")
-    net.backward(p, grads)
-    out = [x.cpu().numpy().astype(np.float64) for x in (pred, loss, grads)]
-    net.close()
-    return out
+    return kit.run_net(lambda: CCN1D(*cfg, ctx=ctx), (g1, g2), targets, params)
 
 
 def check_case(tag, c, ctx=None):
@@ -106,33 +75,16 @@ def test_initial_weights_match_the_real_class(gf):
 
 def test_batchlearn_steps_match_the_real_ccn_1d(gf):
     """Three BatchLearn steps of the real class on the 16 toy pairs at the demo's settings (L = 3): initial weights after the same srand,
-    Adam over the whole vector; then Predict.  Bounds of test_batchlearn_steps_match_the_real_smp_theta."""
+    Adam over the whole vector; then Predict.  The bounds are field_suite.check_momentum_trajectory's."""
     z = load("ccn_1d_demo.npz")
     *_, L, _, seed, nIter = (int(x) for x in z["train__cfg"])
     pairs = demo_pairs()
     g1, g2 = [a for a, _, _ in pairs], [b for _, b, _ in pairs]
     assert np.array_equal(z["train__targets"], [t for *_, t in pairs])
-    tg = dev(z["train__targets"])
     lr = float(z["train__lr"][0])
     net = demo_net(L)
-    C.CDLL(None).srand(seed)
-    p = dev(net.uniform_init_host())
-    net.prepare(g1, g2)
-    grads = torch.empty(net.n_params, device="cuda")
-    for it in range(nIter):
-        _, loss = net.forward(p, tg)
-        before = float(loss.sum())
-        net.backward(p, grads)
-        net.adam_step(p, grads, lr, len(pairs))
-        _, loss = net.forward(p, tg)
-        after = float(loss.sum())
-        print(it, before, z["train__losses"][it, 0], after, z["train__losses"][it, 1])
-        assert abs(before - z["train__losses"][it, 0]) <= TOL * max(1.0, before), it
-        assert abs(after - z["train__losses"][it, 1]) <= 5 * TOL * max(1.0, after), it
-    err = np.abs(p.cpu().numpy().astype(np.float64) - z["train__params"])
-    print(err.max(), np.median(err))
-    assert err.max() <= 0.005 * lr
-    assert np.median(err) <= 1e-6
+    p = kit.check_momentum_trajectory(net, lambda p, g: net.adam_step(p, g, lr, len(pairs)), z, "train__", (g1, g2), seed, nIter, lr,
+                                      init=net.uniform_init_host, show="%s %s")
     pred, _ = net.forward(p)
     assert rel_err(pred.cpu().numpy(), z["train__predict"]) <= TOL
     net.close()
@@ -145,7 +97,7 @@ def test_checkpoints(gf, tmp_path):
     *_, L, _, seed, _ = (int(x) for x in z["train__cfg"])
     pairs = demo_pairs()
     net = demo_net(L)
-    p = net.load_model(os.path.join(HERE, "golden", "ccn_1d_checkpoint.dat"))
+    p = net.load_model(os.path.join(kit.HERE, "golden", "ccn_1d_checkpoint.dat"))
     assert rel_err(p.cpu().numpy(), z["train__params"]) <= 1e-6   # (six printed digits of values below 0.1)
     net.prepare([a for a, _, _ in pairs], [b for _, b, _ in pairs])
     pred, _ = net.forward(p)
@@ -162,7 +114,6 @@ def test_checkpoints(gf, tmp_path):
 
 # ---- a batch across the packing boundaries: 70 pairs, tower 2 sees the list reversed -------------------------------------------------
 PACK = (9, 9, 6, 2, 18, 5, 5, 0.9)   # widths 18 -> 17 -> 16: lane vectors of 2, 1 and 4 floats; the cap of 6 bites on the 7- to 9-vertex molecules
-_PACKED = {}
 
 
 def host_fields(lib, maxV, cap, L, Cn, adj, feat):
@@ -177,20 +128,26 @@ def host_fields(lib, maxV, cap, L, Cn, adj, feat):
     return fields_of(phi)
 
 
-def packed_case(gf):
-    """the 70-pair batch on the device and its fp64 expectation, computed once"""
-    if not _PACKED:
-        from graphflow_amd import _lib
+def run_packed(pairs, tg, params):
+    return run_pairs(PACK, pairs[0], pairs[1], tg, params)
+
+
+def packed_case():
+    """((g1, g2), targets, params, out, ref): the 70-pair batch on the device and its fp64 expectation, computed once"""
+    maxV1, maxV2, cap, L, Cn, F1, F2, decay = PACK
+
+    def batch():
         mols, tg = packing_batch()
-        g1, g2 = mols, mols[::-1]
-        maxV1, maxV2, cap, L, Cn, F1, F2, decay = PACK
-        params = random_params(Cn, L, [F1, F2], [maxV1, maxV2], decay, [np.ones(F1), np.ones(F2)], np.random.default_rng(118))
-        out = run_pairs(PACK, g1, g2, tg, params)
+        return (mols, mols[::-1]), tg
+
+    def reference(pairs, tg, params, out):
+        from graphflow_amd import _lib
         lib = _lib.load()
-        phis = [(host_fields(lib, maxV1, cap, L, Cn, *a), host_fields(lib, maxV2, cap, L, Cn, *b)) for a, b in zip(g1, g2)]
-        ref = ccn1d_ref.run_batch(list(zip(g1, g2)), tg, params, L, Cn, [maxV1, maxV2], decay, phis)
-        _PACKED.update(g1=g1, g2=g2, tg=tg, params=params, out=out, ref=ref)
-    return _PACKED
+        phis = [(host_fields(lib, maxV1, cap, L, Cn, *a), host_fields(lib, maxV2, cap, L, Cn, *b)) for a, b in zip(*pairs)]
+        return ccn1d_ref.run_batch(list(zip(*pairs)), tg, params, L, Cn, [maxV1, maxV2], decay, phis)
+
+    return kit.packed_case("ccn_1d", batch, lambda: random_params(Cn, L, [F1, F2], [maxV1, maxV2], decay, [np.ones(F1), np.ones(F2)],
+                                                                  np.random.default_rng(118)), run_packed, reference)
 
 
 def pack_blocks():
@@ -199,62 +156,39 @@ def pack_blocks():
 
 
 def test_batch_across_the_packing_boundaries(gf):
-    k = packed_case(gf)
-    assert len(k["g1"]) == 70 and sum(len(a) for a, _ in k["g1"]) > 64
-    (pred, loss, grads), (rp, rg) = k["out"], k["ref"]
+    (g1, _), tg, _, (pred, loss, grads), (rp, rg) = packed_case()
+    assert len(g1) == 70 and sum(len(a) for a, _ in g1) > 64
     e = blockwise(grads, rg, pack_blocks())
     print(rel_err(pred, rp), e)
     assert rel_err(pred, rp) <= TOL
-    assert rel_err(loss, 0.5 * (rp - k["tg"]) ** 2) <= 2 * TOL
+    assert rel_err(loss, 0.5 * (rp - tg) ** 2) <= 2 * TOL
     assert e[0] <= TOL, e
 
 
 def test_one_pair_isolated_inside_the_batch(gf):
     """With every other target equal to its prediction only pair 37 has a loss gradient: the batch gradient is then that pair's own."""
-    k = packed_case(gf)
-    i = 37
-    t2 = k["out"][0].astype(np.float32).astype(np.float64).copy()   # (the device's own fp32 predictions: y - t is exactly 0)
-    t2[i] = k["tg"][i]
-    batch = run_pairs(PACK, k["g1"], k["g2"], t2, k["params"])
-    alone = run_pairs(PACK, k["g1"][i:i + 1], k["g2"][i:i + 1], k["tg"][i:i + 1], k["params"])
-    assert np.abs(alone[2]).max() > 0
-    e = blockwise(batch[2], alone[2], pack_blocks())
-    assert e[0] <= TOL, e
-    assert rel_err(batch[0][i:i + 1], alone[0]) <= TOL
+    kit.check_isolated(packed_case(), 37, run_packed, pack_blocks(), outputs=True)
 
 
 def test_two_runs_give_the_same_bits(gf):
-    k = packed_case(gf)
-    again = run_pairs(PACK, k["g1"], k["g2"], k["tg"], k["params"])
-    for x, y in zip(k["out"], again):
-        assert np.array_equal(x, y)
+    kit.check_same_bits(packed_case(), run_packed)
 
 
 def test_parity_under_poison(gf):
     """GF_POISON=1 (every buffer the library hands out without contents starts as NaN patterns): no kernel reads memory nobody wrote at
     the new widths.  The golden and packing-boundary cases in a child process."""
-    env = dict(os.environ, GF_POISON="1")
-    sel = "real_ccn_1d or packing_boundaries"
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k", sel, "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, timeout=600)
-    tail = (r.stdout + r.stderr)[-2000:]
-    assert r.returncode == 0, tail
-    assert " passed" in tail and "failed" not in tail, tail
+    kit.run_under_poison(__file__, "real_ccn_1d or packing_boundaries")
 
 
 def test_only_the_first_order_kernels_run(gf):
     from graphflow_amd.smp import CCN1D
-    k = packed_case(gf)
+    (g1, g2), tg, params = packed_case()[:3]
     L = PACK[3]
     net = CCN1D(*PACK)
-    net.prepare(k["g1"], k["g2"])
-    p = dev(k["params"])
+    net.prepare(g1, g2)
+    p = dev(params)
     grads = torch.empty(net.n_params, device="cuda")
-    net.ctx.set_timing(True)
-    net.forward(p, dev(k["tg"]))
-    net.backward(p, grads)
-    counts = {name: n for name, (_, n) in net.ctx.timings().items()}
-    net.ctx.set_timing(False)
+    counts = kit.traced_counts(net, lambda: (net.forward(p, dev(tg)), net.backward(p, grads)))
     net.close()
     for name in ("smpt_level_fwd", "smpt_node_bwd", "smpt_size_grads", "smpt_gather_bwd"):
         assert counts.get(name) == 2 * L, (name, counts)   # (two towers)

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import classification_ref as cref
+from field_suite import dev
 from inputs import f32exact, synthetic_molecule, toy_molecules
 from util import rel_err
 
@@ -38,10 +39,6 @@ NK = {6: 10, 7: 50}
 def note(name, **errs):
     for k, v in errs.items():
         MARGINS[name + "." + k] = max(MARGINS.get(name + "." + k, 0.0), float(v))
-
-
-def dev(x, dtype=np.float32):
-    return torch.as_tensor(np.ascontiguousarray(x, dtype=dtype)).cuda()
 
 
 def make(nClass, L, C, F, D, cap, wl=True, nK=10, custom=True, fused=True, ctx=None):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import level_ref as lr
+from field_suite import dev
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -25,10 +26,6 @@ RAGGED = [1, 15, 16, 17, 31, 32, 33, 48, 63, 65, 80]  # around the 32-row panel 
                                                       # 17, 33, 48, 65, 80 leave a half-slice short or empty, 33 .. 80 make 2 or 3 slices)
 # (C, row factors, extra products) the kernels have
 VARIANTS = [(64, 2, 0), (32, 2, 0), (32, 8, 0), (32, 2, 3), (16, 2, 0), (16, 8, 0), (16, 2, 3)]
-
-
-def dev(x, dtype=np.float32):
-    return torch.as_tensor(np.ascontiguousarray(x, dtype=dtype)).cuda()
 
 
 def ptr(t):

@@ -40,14 +40,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from field_suite import dev
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 TOL = 1e-5
-
-
-def dev(x, dtype=np.float32):
-    return torch.as_tensor(np.ascontiguousarray(x, dtype=dtype)).cuda()
 
 
 def ptr(t):

@@ -3,14 +3,13 @@ on the level of smp_level_1d.hip.  Checked against the real classes' numbers (te
 vector, and at shapes without a golden against tests/smp1d_ref.py, which tests/test_smp_1d.py pins to the real classes at 1e-9.
 Tolerance: the suite's 1e-5 (tests/util.py: rel_err), for the graph feature, the prediction, the loss and every parameter block."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import field_suite as kit
 import smp1d_ref
+from field_suite import TOL, blockwise
 from inputs import synthetic_molecule, toy_molecules
 from make_smp1d_golden import random_params, smp1d_blocks
 from util import rel_err
@@ -18,22 +17,9 @@ from util import rel_err
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-TOL = 1e-5
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def dev(x, dtype=np.float32):
-    return torch.as_tensor(np.ascontiguousarray(x, dtype=dtype)).cuda()
-
-
-_GOLDEN = {}
-
 
 def golden():
-    if not _GOLDEN:
-        with np.load(os.path.join(HERE, "golden", "smp_1d.npz")) as z:
-            _GOLDEN.update({k: z[k] for k in z.files})
-    return _GOLDEN
+    return kit.load_golden("smp_1d.npz")
 
 
 def net_of(version, L, Cn, F, D, maxV, wl=True, nClass=0):
@@ -43,31 +29,8 @@ def net_of(version, L, Cn, F, D, maxV, wl=True, nClass=0):
 
 def run_net(version, mols, targets, params, L, Cn, D, maxV, wl=True, nClass=0, want_fields=False):
     """[predict, loss, feature, grads (, scores, probability) (, fields)] as float64 arrays"""
-    net = net_of(version, L, Cn, mols[0][1].shape[1], D, maxV, wl, nClass)
-    assert net.n_params == np.asarray(params).size
-    net.prepare(mols)
-    p = dev(params)
-    pred, loss, feat = net.forward(p, dev(targets))
-    out = [pred.cpu().numpy().astype(np.float64), loss.cpu().numpy().astype(np.float64), feat.cpu().numpy().astype(np.float64)]
-    grads = torch.empty(net.n_params, device="cuda")
-    net.backward(p, grads)
-    out.append(grads.cpu().numpy().astype(np.float64))
-    if nClass:
-        out += [t.cpu().numpy().astype(np.float64) for t in net.scores()]
-    if want_fields:
-        out.append([[[net.receptive_field(m, l, v) for v in range(len(mols[m][0]))] for l in range(L + 1)] for m in range(len(mols))])
-    net.close()
-    return out
-
-
-def blockwise(x, ref, blocks):
-    """the largest rel_err over the parameter blocks: one norm over the whole vector cannot see an error confined to a small block"""
-    off, worst = 0, (0.0, "")
-    for name, n in blocks:
-        worst = max(worst, (rel_err(x[off:off + n], ref[off:off + n]), name))
-        off += n
-    assert off == ref.size
-    return worst
+    return kit.run_net(lambda: net_of(version, L, Cn, mols[0][1].shape[1], D, maxV, wl, nClass), mols, targets, params, n_class=nClass,
+                       want_fields=want_fields)
 
 
 @pytest.mark.parametrize("version", [1, 2, 3])
@@ -129,32 +92,13 @@ def test_version2_classifier_matches_the_restatement(gf):
 
 def test_momentum_steps_match_the_real_smp_1d_ver3(gf):
     """Three BatchLearn steps of the real SMP_1D_ver3 on the four toy molecules: initial weights from gf_smp_uniform_init_host after the
-    same srand, gf_smp_momentum_step.  Tolerances of test_batchlearn_steps_match_the_real_smp_theta."""
+    same srand, gf_smp_momentum_step.  The bounds are field_suite.check_momentum_trajectory's."""
     z = golden()
     version, L, Cn, D, wl, maxV, _, seed, nIter = (int(x) for x in z["train__cfg"])
     mols = [(adj, feat) for _, adj, feat, _ in toy_molecules()]
-    tg = dev(z["train__targets"])
     lr, gamma = float(z["train__lr"][0]), float(z["train__momentum"][0])
     net = net_of(version, L, Cn, 4, D, maxV, bool(wl))
-    C.CDLL(None).srand(seed)
-    p = dev(net.uniform_init())
-    assert np.array_equal(p.cpu().numpy(), z["train__params0"].astype(np.float32))
-    net.prepare(mols)
-    grads = torch.empty(net.n_params, device="cuda")
-    for it in range(nIter):
-        _, loss, _ = net.forward(p, tg)
-        before = float(loss.sum())
-        net.backward(p, grads)
-        net.step(p, grads, lr, len(mols), gamma)
-        _, loss, _ = net.forward(p, tg)
-        after = float(loss.sum())
-        print(it, before, z["train__losses"][it, 0], after, z["train__losses"][it, 1])
-        assert abs(before - z["train__losses"][it, 0]) <= TOL * max(1.0, before), it
-        assert abs(after - z["train__losses"][it, 1]) <= 5 * TOL * max(1.0, after), it
-    err = np.abs(p.cpu().numpy().astype(np.float64) - z["train__params"])
-    print("trajectory: max", err.max(), "median", np.median(err))
-    assert err.max() <= 0.005 * lr
-    assert np.median(err) <= 1e-6
+    kit.check_momentum_trajectory(net, lambda p, g: net.step(p, g, lr, len(mols), gamma), z, "train__", mols, seed, nIter, lr)
     net.close()
 
 
@@ -174,20 +118,20 @@ def packing_batch():
     return mols, np.array(tg)
 
 
-_PACKED = {}
 PACK_L, PACK_D, PACK_MAXV = 2, 1, 9
 
 
+def run_packed(version, Cn):
+    return lambda mols, tg, params, **kw: run_net(version, mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV, **kw)
+
+
 def packed_case(version, Cn):
-    """the packing batch on the device and its fp64 expectation, computed once per (form, channel count)"""
-    if (version, Cn) not in _PACKED:
-        mols, tg = packing_batch()
-        blocks = smp1d_blocks(version, Cn, 5 * (PACK_D + 1), PACK_L, PACK_MAXV)
-        params = random_params(blocks, np.random.default_rng(100 * version + Cn))
-        out = run_net(version, mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV, want_fields=True)
-        res, rg = smp1d_ref.run_batch(version, mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV, out[4])
-        _PACKED[(version, Cn)] = (mols, tg, params, blocks, out, res, rg)
-    return _PACKED[(version, Cn)]
+    """the packing batch on the device and its fp64 expectation (per molecule, summed gradient), computed once per (form, channel count)"""
+    blocks = smp1d_blocks(version, Cn, 5 * (PACK_D + 1), PACK_L, PACK_MAXV)
+    return kit.packed_case(("smp_1d", version, Cn), packing_batch, lambda: random_params(blocks, np.random.default_rng(100 * version + Cn)),
+                           run_packed(version, Cn),
+                           lambda mols, tg, params, out: smp1d_ref.run_batch(version, mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV, out[4]),
+                           want_fields=True) + (blocks,)
 
 
 PACKED_SHAPES = [(1, 5), (2, 3), (2, 4), (3, 3), (3, 4)]
@@ -196,7 +140,7 @@ PACKED_SHAPES = [(1, 5), (2, 3), (2, 4), (3, 3), (3, 4)]
 @pytest.mark.parametrize("version,Cn", PACKED_SHAPES)
 def test_batch_across_the_packing_boundaries(gf, version, Cn):
     """against smp1d_ref, per molecule (prediction, graph feature) and per block of the summed gradient"""
-    mols, tg, params, blocks, out, res, rg = packed_case(version, Cn)
+    mols, tg, params, out, (res, rg), blocks = packed_case(version, Cn)
     assert sum(len(a) for a, _ in mols) > 64
     e = blockwise(out[3], rg, blocks)
     worst_feat = max(rel_err(out[2][m], res[m]["graph_feature"]) for m in range(len(mols)))
@@ -210,35 +154,19 @@ def test_batch_across_the_packing_boundaries(gf, version, Cn):
 def test_one_molecule_isolated_inside_the_batch(gf, version, Cn):
     """With every other target equal to its prediction only molecule 37 has a loss gradient: the batch gradient is then that molecule's
     single-molecule gradient."""
-    mols, tg, params, blocks, out, _, _ = packed_case(version, Cn)
-    k = 37
-    t2 = out[0].astype(np.float32).astype(np.float64).copy()   # (the device's own fp32 predictions: y - t is exactly 0)
-    t2[k] = tg[k]
-    batch = run_net(version, mols, t2, params, PACK_L, Cn, PACK_D, PACK_MAXV)
-    alone = run_net(version, [mols[k]], tg[k:k + 1], params, PACK_L, Cn, PACK_D, PACK_MAXV)
-    e = blockwise(batch[3], alone[3], blocks)
-    assert np.abs(alone[3]).max() > 0
-    assert e[0] <= TOL, e
+    case = packed_case(version, Cn)
+    kit.check_isolated(case, 37, run_packed(version, Cn), case[5])
 
 
 @pytest.mark.parametrize("version,Cn", [(1, 5), (2, 4), (3, 3)])
 def test_two_runs_give_the_same_bits(gf, version, Cn):
-    mols, tg, params, _, out, _, _ = packed_case(version, Cn)
-    again = run_net(version, mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV)
-    for x, y in zip(out[:4], again):
-        assert np.array_equal(x, y)
+    kit.check_same_bits(packed_case(version, Cn), run_packed(version, Cn))
 
 
 def test_parity_under_poison(gf):
     """GF_POISON=1 (every buffer the library hands out without contents starts as NaN patterns): no kernel of these levels reads memory
     nobody wrote.  The golden, classifier and packing-boundary cases in a fresh child process."""
-    env = dict(os.environ, GF_POISON="1")
-    sel = "real_classes or packing_boundaries"
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k", sel, "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, timeout=600)
-    tail = (r.stdout + r.stderr)[-2000:]
-    assert r.returncode == 0, tail
-    assert " passed" in tail and "failed" not in tail, tail
+    kit.run_under_poison(__file__, "real_classes or packing_boundaries")
 
 
 @pytest.mark.parametrize("version", [1, 2, 3])
@@ -249,13 +177,9 @@ def test_kernel_table(gf, version):
     L, Cn = PACK_L, 4
     net = net_of(version, L, Cn, 5, PACK_D, PACK_MAXV)
     net.prepare(mols)
-    p = dev(random_params(smp1d_blocks(version, Cn, 5 * (PACK_D + 1), L, PACK_MAXV), np.random.default_rng(1)))
+    p = kit.dev(random_params(smp1d_blocks(version, Cn, 5 * (PACK_D + 1), L, PACK_MAXV), np.random.default_rng(1)))
     grads = torch.empty(net.n_params, device="cuda")
-    net.ctx.set_timing(True)
-    net.forward(p, dev(tg))
-    net.backward(p, grads)
-    counts = {k: n for k, (_, n) in net.ctx.timings().items()}
-    net.ctx.set_timing(False)
+    counts = kit.traced_counts(net, lambda: (net.forward(p, kit.dev(tg)), net.backward(p, grads)))
     nodes, rows, ppos = net.level_sizes(L)
     assert nodes == sum(len(a) for a, _ in mols) and ppos == 0
     net.close()
@@ -303,12 +227,5 @@ def test_feature_is_invariant_under_vertex_permutation(gf, version):
     adj, x, _ = synthetic_molecule(5, 12)
     L, Cn, D, maxV = 2, 4, 2, 12
     params = random_params(smp1d_blocks(version, Cn, 5 * (D + 1), L, maxV), np.random.default_rng(9))
-    perm = np.random.default_rng(0).permutation(len(adj))
-    padj, px = adj[np.ix_(perm, perm)], x[perm]
-    a = run_net(version, [(adj, x)], np.array([1.0]), params, L, Cn, D, maxV, want_fields=True)
-    b = run_net(version, [(padj, px)], np.array([1.0]), params, L, Cn, D, maxV, want_fields=True)
-    ra = smp1d_ref.run(version, adj, x, 1.0, params, L, Cn, D, maxV, a[4][0])
-    rb = smp1d_ref.run(version, padj, px, 1.0, params, L, Cn, D, maxV, b[4][0])
-    assert rel_err(rb["graph_feature"], ra["graph_feature"]) <= 1e-12
-    assert rel_err(b[2], a[2]) <= TOL
-    assert rel_err(a[2][0], ra["graph_feature"]) <= TOL
+    kit.check_permutation_invariance(adj, x, lambda mols, tg: run_net(version, mols, tg, params, L, Cn, D, maxV, want_fields=True),
+                                     lambda a, f, fields: smp1d_ref.run(version, a, f, 1.0, params, L, Cn, D, maxV, fields)["graph_feature"])

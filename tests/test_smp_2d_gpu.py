@@ -3,14 +3,13 @@ smp_level_2d.hip.  Checked against the real classes' numbers (tests/golden/smp_2
 shapes without a golden against tests/smp2d_ref.py, which tests/test_smp_2d.py pins to the real classes at 1e-9.
 Tolerance: the suite's 1e-5 (tests/util.py: rel_err), for the graph feature, the prediction, the loss and every parameter block."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import field_suite as kit
 import smp2d_ref
+from field_suite import TOL, blockwise, dev
 from inputs import synthetic_molecule, toy_molecules
 from make_smp2d_golden import random_params, smp2d_blocks
 from util import rel_err
@@ -18,23 +17,11 @@ from util import rel_err
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-TOL = 1e-5
-HERE = os.path.dirname(os.path.abspath(__file__))
 FORM = {1: "2d", 2: "ver4"}
 
 
-def dev(x, dtype=np.float32):
-    return torch.as_tensor(np.ascontiguousarray(x, dtype=dtype)).cuda()
-
-
-_GOLDEN = {}
-
-
 def golden():
-    if not _GOLDEN:
-        with np.load(os.path.join(HERE, "golden", "smp_2d.npz")) as z:
-            _GOLDEN.update({k: z[k] for k in z.files})
-    return _GOLDEN
+    return kit.load_golden("smp_2d.npz")
 
 
 def net_of(form, L, Cn, F, D, maxV, wl=True, nClass=0):
@@ -42,35 +29,9 @@ def net_of(form, L, Cn, F, D, maxV, wl=True, nClass=0):
     return SMP2D(FORM[form], maxV, L, Cn, F, D, wl, nClass)
 
 
-def run_net(form, mols, targets, params, L, Cn, D, maxV, wl=True, nClass=0, want_fields=False, inspect=None):
+def run_net(form, mols, targets, params, L, Cn, D, maxV, wl=True, nClass=0, **kw):
     """[predict, loss, feature, grads (, scores, probability) (, fields) (, inspect(net))] as float64 arrays"""
-    net = net_of(form, L, Cn, mols[0][1].shape[1], D, maxV, wl, nClass)
-    assert net.n_params == np.asarray(params).size
-    net.prepare(mols)
-    p = dev(params)
-    pred, loss, feat = net.forward(p, dev(targets))
-    out = [pred.cpu().numpy().astype(np.float64), loss.cpu().numpy().astype(np.float64), feat.cpu().numpy().astype(np.float64)]
-    grads = torch.empty(net.n_params, device="cuda")
-    net.backward(p, grads)
-    out.append(grads.cpu().numpy().astype(np.float64))
-    if nClass:
-        out += [t.cpu().numpy().astype(np.float64) for t in net.scores()]
-    if want_fields:
-        out.append([[[net.receptive_field(m, l, v) for v in range(len(mols[m][0]))] for l in range(L + 1)] for m in range(len(mols))])
-    if inspect:
-        out.append(inspect(net))
-    net.close()
-    return out
-
-
-def blockwise(x, ref, blocks):
-    """the largest rel_err over the parameter blocks: one norm over the whole vector cannot see an error confined to a small block"""
-    off, worst = 0, (0.0, "")
-    for name, n in blocks:
-        worst = max(worst, (rel_err(x[off:off + n], ref[off:off + n]), name))
-        off += n
-    assert off == ref.size
-    return worst
+    return kit.run_net(lambda: net_of(form, L, Cn, mols[0][1].shape[1], D, maxV, wl, nClass), mols, targets, params, n_class=nClass, **kw)
 
 
 @pytest.mark.parametrize("form", [1, 2])
@@ -125,32 +86,13 @@ def test_classifiers_match_the_real_classes(gf):
 
 def test_momentum_steps_match_the_real_smp_2d_ver4(gf):
     """Three BatchLearn steps of the real SMP_2D_ver4 on the four toy molecules: initial weights from gf_smp_uniform_init_host after the
-    same srand, gf_smp_momentum_step.  Tolerances of test_momentum_steps_match_the_real_smp_1d_ver3."""
+    same srand, gf_smp_momentum_step.  The bounds are field_suite.check_momentum_trajectory's."""
     z = golden()
     form, L, Cn, D, wl, maxV, _, seed, nIter = (int(x) for x in z["train__cfg"])
     mols = [(adj, feat) for _, adj, feat, _ in toy_molecules()]
-    tg = dev(z["train__targets"])
     lr, gamma = float(z["train__lr"][0]), float(z["train__momentum"][0])
     net = net_of(form, L, Cn, 4, D, maxV, bool(wl))
-    C.CDLL(None).srand(seed)
-    p = dev(net.uniform_init())
-    assert np.array_equal(p.cpu().numpy(), z["train__params0"].astype(np.float32))
-    net.prepare(mols)
-    grads = torch.empty(net.n_params, device="cuda")
-    for it in range(nIter):
-        _, loss, _ = net.forward(p, tg)
-        before = float(loss.sum())
-        net.backward(p, grads)
-        net.step(p, grads, lr, len(mols), gamma)
-        _, loss, _ = net.forward(p, tg)
-        after = float(loss.sum())
-        print(it, before, z["train__losses"][it, 0], after, z["train__losses"][it, 1])
-        assert abs(before - z["train__losses"][it, 0]) <= TOL * max(1.0, before), it
-        assert abs(after - z["train__losses"][it, 1]) <= 5 * TOL * max(1.0, after), it
-    err = np.abs(p.cpu().numpy().astype(np.float64) - z["train__params"])
-    print("trajectory: max", err.max(), "median", np.median(err))
-    assert err.max() <= 0.005 * lr
-    assert np.median(err) <= 1e-6
+    kit.check_momentum_trajectory(net, lambda p, g: net.step(p, g, lr, len(mols), gamma), z, "train__", mols, seed, nIter, lr)
     net.close()
 
 
@@ -160,25 +102,10 @@ def test_checkpoint_round_trip_reproduces_the_golden_prediction(gf, tmp_path):
     gz = golden()
     for tag in ("f1_C2H4_c5", "f2_C2H4_c5"):
         form, L, Cn, D, wl, maxV, _ = (int(x) for x in gz[tag + "__cfg"])
-        mol = (gz[tag + "__adj"], gz[tag + "__feature"])
-        net = net_of(form, L, Cn, 4, D, maxV, bool(wl))
-        p = dev(gz[tag + "__params"])
-        path = tmp_path / (tag + ".txt")
-        net.save_model(p, path)
-        text = path.read_text().split()
-        assert len(text) == net.n_params and text == ["%g" % x for x in gz[tag + "__params"]]
-        q = net.load_model(torch.zeros_like(p), path)
-        loaded = q.cpu().numpy()
-        assert np.array_equal(loaded, np.array([float(t) for t in text], dtype=np.float32))
-        net.prepare([mol])
-        pred, _, _ = net.forward(q, dev(gz[tag + "__target"]))
-        fields = [[net.receptive_field(0, l, v) for v in range(len(mol[0]))] for l in range(L + 1)]
-        net.close()
-        r = smp2d_ref.run(form, mol[0], mol[1], float(gz[tag + "__target"][0]), loaded, L, Cn, D, maxV, fields)
-        pred = pred.cpu().numpy().astype(np.float64)
-        print(tag, pred, r["predict"], gz[tag + "__predict"])
-        assert rel_err(pred, [r["predict"]]) <= TOL, tag
-        assert rel_err(pred, gz[tag + "__predict"]) <= TOL, tag
+        adj, x, target = gz[tag + "__adj"], gz[tag + "__feature"], gz[tag + "__target"]
+        kit.check_checkpoint_round_trip(
+            net_of(form, L, Cn, 4, D, maxV, bool(wl)), tag, (adj, x), gz[tag + "__params"], target, gz[tag + "__predict"],
+            lambda loaded, fields: smp2d_ref.run(form, adj, x, float(target[0]), loaded, L, Cn, D, maxV, fields)["predict"], tmp_path)
 
 
 def packing_batch():
@@ -196,20 +123,21 @@ def packing_batch():
     return mols, np.array(tg)
 
 
-_PACKED = {}
 PACK_L, PACK_D, PACK_MAXV = 2, 1, 13
 
 
+def run_packed(form, Cn):
+    return lambda mols, tg, params, **kw: run_net(form, mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV, **kw)
+
+
 def packed_case(form, Cn):
-    """the packing batch on the device and its fp64 expectation, computed once per (form, channel count)"""
-    if (form, Cn) not in _PACKED:
-        mols, tg = packing_batch()
-        blocks = smp2d_blocks(form, Cn, 5 * (PACK_D + 1), PACK_L, PACK_MAXV)
-        params = random_params(form, Cn, 5 * (PACK_D + 1), PACK_L, PACK_MAXV, np.random.default_rng(100 * form + Cn))
-        out = run_net(form, mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV, want_fields=True)
-        res, rg = smp2d_ref.run_batch(form, mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV, out[4])
-        _PACKED[(form, Cn)] = (mols, tg, params, blocks, out, res, rg)
-    return _PACKED[(form, Cn)]
+    """the packing batch on the device and its fp64 expectation (per molecule, summed gradient), computed once per (form, channel count)"""
+    blocks = smp2d_blocks(form, Cn, 5 * (PACK_D + 1), PACK_L, PACK_MAXV)
+    return kit.packed_case(("smp_2d", form, Cn), packing_batch,
+                           lambda: random_params(form, Cn, 5 * (PACK_D + 1), PACK_L, PACK_MAXV, np.random.default_rng(100 * form + Cn)),
+                           run_packed(form, Cn),
+                           lambda mols, tg, params, out: smp2d_ref.run_batch(form, mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV, out[4]),
+                           want_fields=True) + (blocks,)
 
 
 PACKED_SHAPES = [(1, 5), (1, 8), (2, 3), (2, 6), (2, 4)]
@@ -218,7 +146,7 @@ PACKED_SHAPES = [(1, 5), (1, 8), (2, 3), (2, 6), (2, 4)]
 @pytest.mark.parametrize("form,Cn", PACKED_SHAPES)
 def test_batch_across_the_packing_boundaries(gf, form, Cn):
     """against smp2d_ref, per molecule (prediction, graph feature) and per block of the summed gradient"""
-    mols, tg, params, blocks, out, res, rg = packed_case(form, Cn)
+    mols, tg, params, out, (res, rg), blocks = packed_case(form, Cn)
     assert len(mols) == 70 and sum(len(a) for a, _ in mols) > 64
     e = blockwise(out[3], rg, blocks)
     worst_feat = max(rel_err(out[2][m], res[m]["graph_feature"]) for m in range(len(mols)))
@@ -232,36 +160,19 @@ def test_batch_across_the_packing_boundaries(gf, form, Cn):
 def test_one_molecule_isolated_inside_the_batch(gf, form, Cn):
     """With every other target equal to its prediction only molecule 68 (the 12-vertex one) has a loss gradient: the batch gradient is
     then that molecule's single-molecule gradient, and its prediction and graph feature are those it has alone."""
-    mols, tg, params, blocks, out, _, _ = packed_case(form, Cn)
-    k = 68
-    t2 = out[0].astype(np.float32).astype(np.float64).copy()   # (the device's own fp32 predictions: y - t is exactly 0)
-    t2[k] = tg[k]
-    batch = run_net(form, mols, t2, params, PACK_L, Cn, PACK_D, PACK_MAXV)
-    alone = run_net(form, [mols[k]], tg[k:k + 1], params, PACK_L, Cn, PACK_D, PACK_MAXV)
-    e = blockwise(batch[3], alone[3], blocks)
-    assert np.abs(alone[3]).max() > 0
-    assert e[0] <= TOL, e
-    assert rel_err(batch[0][k:k + 1], alone[0]) <= TOL and rel_err(batch[2][k], alone[2][0]) <= TOL
+    case = packed_case(form, Cn)
+    kit.check_isolated(case, 68, run_packed(form, Cn), case[5], outputs=True)
 
 
 @pytest.mark.parametrize("form,Cn", [(1, 8), (2, 3)])
 def test_two_runs_give_the_same_bits(gf, form, Cn):
-    mols, tg, params, _, out, _, _ = packed_case(form, Cn)
-    again = run_net(form, mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV)
-    for x, y in zip(out[:4], again):
-        assert np.array_equal(x, y)
+    kit.check_same_bits(packed_case(form, Cn), run_packed(form, Cn))
 
 
 def test_parity_under_poison(gf):
     """GF_POISON=1 (every buffer the library hands out without contents starts as NaN patterns): no kernel of these levels reads memory
     nobody wrote.  The golden, classifier and packing-boundary cases in a fresh child process."""
-    env = dict(os.environ, GF_POISON="1")
-    sel = "real_classes or packing_boundaries"
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k", sel, "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, timeout=600)
-    tail = (r.stdout + r.stderr)[-2000:]
-    assert r.returncode == 0, tail
-    assert " passed" in tail and "failed" not in tail, tail
+    kit.run_under_poison(__file__, "real_classes or packing_boundaries")
 
 
 @pytest.mark.parametrize("form", [1, 2])
@@ -274,11 +185,7 @@ def test_kernel_table(gf, form):
     net.prepare(mols)
     p = dev(random_params(form, Cn, 5 * (PACK_D + 1), L, PACK_MAXV, np.random.default_rng(1)))
     grads = torch.empty(net.n_params, device="cuda")
-    net.ctx.set_timing(True)
-    net.forward(p, dev(tg))
-    net.backward(p, grads)
-    counts = {k: n for k, (_, n) in net.ctx.timings().items()}
-    net.ctx.set_timing(False)
+    counts = kit.traced_counts(net, lambda: (net.forward(p, dev(tg)), net.backward(p, grads)))
     net.close()
     for k in ("smp2d_level_fwd", "smp2d_node_bwd", "smp2d_bucket_partials", "smp2d_grads_finish", "smp2d_gather_bwd"):
         assert counts.get(k) == L, (k, counts)
@@ -330,12 +237,5 @@ def test_feature_is_invariant_under_vertex_permutation(gf, form):
     adj, x, _ = synthetic_molecule(5, 12)
     L, Cn, D, maxV = 2, 4, 2, 12
     params = random_params(form, Cn, 5 * (D + 1), L, maxV, np.random.default_rng(9))
-    perm = np.random.default_rng(0).permutation(len(adj))
-    padj, px = adj[np.ix_(perm, perm)], x[perm]
-    a = run_net(form, [(adj, x)], np.array([1.0]), params, L, Cn, D, maxV, want_fields=True)
-    b = run_net(form, [(padj, px)], np.array([1.0]), params, L, Cn, D, maxV, want_fields=True)
-    ra = smp2d_ref.run(form, adj, x, 1.0, params, L, Cn, D, maxV, a[4][0])
-    rb = smp2d_ref.run(form, padj, px, 1.0, params, L, Cn, D, maxV, b[4][0])
-    assert rel_err(rb["graph_feature"], ra["graph_feature"]) <= 1e-12
-    assert rel_err(b[2], a[2]) <= TOL
-    assert rel_err(a[2][0], ra["graph_feature"]) <= TOL
+    kit.check_permutation_invariance(adj, x, lambda mols, tg: run_net(form, mols, tg, params, L, Cn, D, maxV, want_fields=True),
+                                     lambda a, f, fields: smp2d_ref.run(form, a, f, 1.0, params, L, Cn, D, maxV, fields)["graph_feature"])

@@ -4,13 +4,13 @@ tests/smp2d_ver5_ref.py, which tests/test_smp_2d_ver5.py pins to the real class 
 Tolerance: the suite's 1e-5 (tests/util.py: rel_err), for the graph feature, the prediction, the loss and every parameter block."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import field_suite as kit
 import smp2d_ver5_ref
+from field_suite import TOL, blockwise, dev
 from inputs import synthetic_molecule, toy_molecules
 from make_smp2d_ver5_golden import random_params, smp2d_ver5_blocks
 from util import rel_err
@@ -18,23 +18,11 @@ from util import rel_err
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-TOL = 1e-5
-HERE = os.path.dirname(os.path.abspath(__file__))
 DK_CHUNK = 512   # rows per partial image of dK1 (kV5Chunk of smp_level_2d_ver5.hip)
 
 
-def dev(x, dtype=np.float32):
-    return torch.as_tensor(np.ascontiguousarray(x, dtype=dtype)).cuda()
-
-
-_GOLDEN = {}
-
-
 def golden():
-    if not _GOLDEN:
-        with np.load(os.path.join(HERE, "golden", "smp_2d_ver5.npz")) as z:
-            _GOLDEN.update({k: z[k] for k in z.files})
-    return _GOLDEN
+    return kit.load_golden("smp_2d_ver5.npz")
 
 
 def net_of(L, Cn, F, D, maxV, wl=True):
@@ -42,33 +30,9 @@ def net_of(L, Cn, F, D, maxV, wl=True):
     return SMP2D("ver5", maxV, L, Cn, F, D, wl)
 
 
-def run_net(mols, targets, params, L, Cn, D, maxV, wl=True, want_fields=False, inspect=None):
+def run_net(mols, targets, params, L, Cn, D, maxV, wl=True, **kw):
     """[predict, loss, feature, grads (, fields) (, inspect(net))] as float64 arrays"""
-    net = net_of(L, Cn, mols[0][1].shape[1], D, maxV, wl)
-    assert net.n_params == np.asarray(params).size
-    net.prepare(mols)
-    p = dev(params)
-    pred, loss, feat = net.forward(p, dev(targets))
-    out = [pred.cpu().numpy().astype(np.float64), loss.cpu().numpy().astype(np.float64), feat.cpu().numpy().astype(np.float64)]
-    grads = torch.empty(net.n_params, device="cuda")
-    net.backward(p, grads)
-    out.append(grads.cpu().numpy().astype(np.float64))
-    if want_fields:
-        out.append([[[net.receptive_field(m, l, v) for v in range(len(mols[m][0]))] for l in range(L + 1)] for m in range(len(mols))])
-    if inspect:
-        out.append(inspect(net))
-    net.close()
-    return out
-
-
-def blockwise(x, ref, blocks):
-    """the largest rel_err over the parameter blocks: one norm over the whole vector cannot see an error confined to a small block"""
-    off, worst = 0, (0.0, "")
-    for name, n in blocks:
-        worst = max(worst, (rel_err(x[off:off + n], ref[off:off + n]), name))
-        off += n
-    assert off == ref.size
-    return worst
+    return kit.run_net(lambda: net_of(L, Cn, mols[0][1].shape[1], D, maxV, wl), mols, targets, params, **kw)
 
 
 def test_device_matches_the_real_class(gf):
@@ -103,33 +67,14 @@ def test_device_matches_the_real_class(gf):
 
 def test_momentum_steps_match_the_real_class(gf):
     """Three BatchLearn steps of the real SMP_2D_ver5 on the four toy molecules: initial weights from gf_smp_uniform_init_host after the
-    same srand, gf_smp_momentum_step.  Tolerances of test_momentum_steps_match_the_real_smp_2d_ver4."""
+    same srand, gf_smp_momentum_step.  The bounds are field_suite.check_momentum_trajectory's."""
     z = golden()
     form, L, Cn, D, wl, maxV, _, seed, nIter = (int(x) for x in z["train__cfg"])
     assert form == 5
     mols = [(adj, feat) for _, adj, feat, _ in toy_molecules()]
-    tg = dev(z["train__targets"])
     lr, gamma = float(z["train__lr"][0]), float(z["train__momentum"][0])
     net = net_of(L, Cn, 4, D, maxV, bool(wl))
-    C.CDLL(None).srand(seed)
-    p = dev(net.uniform_init())
-    assert np.array_equal(p.cpu().numpy(), z["train__params0"].astype(np.float32))
-    net.prepare(mols)
-    grads = torch.empty(net.n_params, device="cuda")
-    for it in range(nIter):
-        _, loss, _ = net.forward(p, tg)
-        before = float(loss.sum())
-        net.backward(p, grads)
-        net.step(p, grads, lr, len(mols), gamma)
-        _, loss, _ = net.forward(p, tg)
-        after = float(loss.sum())
-        print(it, before, z["train__losses"][it, 0], after, z["train__losses"][it, 1])
-        assert abs(before - z["train__losses"][it, 0]) <= TOL * max(1.0, before), it
-        assert abs(after - z["train__losses"][it, 1]) <= 5 * TOL * max(1.0, after), it
-    err = np.abs(p.cpu().numpy().astype(np.float64) - z["train__params"])
-    print("trajectory: max", err.max(), "median", np.median(err))
-    assert err.max() <= 0.005 * lr
-    assert np.median(err) <= 1e-6
+    kit.check_momentum_trajectory(net, lambda p, g: net.step(p, g, lr, len(mols), gamma), z, "train__", mols, seed, nIter, lr)
     net.close()
 
 
@@ -139,25 +84,10 @@ def test_checkpoint_round_trip_reproduces_the_golden_prediction(gf, tmp_path):
     gz = golden()
     tag = "f5_C2H4_c5"
     _, L, Cn, D, wl, maxV, _ = (int(x) for x in gz[tag + "__cfg"])
-    mol = (gz[tag + "__adj"], gz[tag + "__feature"])
-    net = net_of(L, Cn, 4, D, maxV, bool(wl))
-    p = dev(gz[tag + "__params"])
-    path = tmp_path / (tag + ".txt")
-    net.save_model(p, path)
-    text = path.read_text().split()
-    assert len(text) == net.n_params and text == ["%g" % x for x in gz[tag + "__params"]]
-    q = net.load_model(torch.zeros_like(p), path)
-    loaded = q.cpu().numpy()
-    assert np.array_equal(loaded, np.array([float(t) for t in text], dtype=np.float32))
-    net.prepare([mol])
-    pred, _, _ = net.forward(q, dev(gz[tag + "__target"]))
-    fields = [[net.receptive_field(0, l, v) for v in range(len(mol[0]))] for l in range(L + 1)]
-    net.close()
-    r = smp2d_ver5_ref.run(mol[0], mol[1], float(gz[tag + "__target"][0]), loaded, L, Cn, D, maxV, fields)
-    pred = pred.cpu().numpy().astype(np.float64)
-    print(tag, pred, r["predict"], gz[tag + "__predict"])
-    assert rel_err(pred, [r["predict"]]) <= TOL, tag
-    assert rel_err(pred, gz[tag + "__predict"]) <= TOL, tag
+    adj, x, target = gz[tag + "__adj"], gz[tag + "__feature"], gz[tag + "__target"]
+    kit.check_checkpoint_round_trip(
+        net_of(L, Cn, 4, D, maxV, bool(wl)), tag, (adj, x), gz[tag + "__params"], target, gz[tag + "__predict"],
+        lambda loaded, fields: smp2d_ver5_ref.run(adj, x, float(target[0]), loaded, L, Cn, D, maxV, fields)["predict"], tmp_path)
 
 
 def packing_batch():
@@ -176,21 +106,20 @@ def packing_batch():
     return mols, np.array(tg)
 
 
-_PACKED = {}
 PACK_L, PACK_D, PACK_MAXV = 2, 1, 13
 
 
+def run_packed(Cn):
+    return lambda mols, tg, params, **kw: run_net(mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV, **kw)
+
+
 def packed_case(Cn):
-    """the packing batch on the device and its fp64 expectation, computed once per channel count"""
-    if Cn not in _PACKED:
-        mols, tg = packing_batch()
-        blocks = smp2d_ver5_blocks(Cn, 5 * (PACK_D + 1), PACK_L, PACK_MAXV)
-        params = random_params(Cn, 5 * (PACK_D + 1), PACK_L, PACK_MAXV, np.random.default_rng(500 + Cn))
-        out = run_net(mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV, want_fields=True,
-                      inspect=lambda net: [net.level_sizes(l) for l in range(PACK_L + 1)])
-        res, rg = smp2d_ver5_ref.run_batch(mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV, out[4])
-        _PACKED[Cn] = (mols, tg, params, blocks, out, res, rg)
-    return _PACKED[Cn]
+    """the packing batch on the device (with every level's sizes) and its fp64 expectation, computed once per channel count"""
+    blocks = smp2d_ver5_blocks(Cn, 5 * (PACK_D + 1), PACK_L, PACK_MAXV)
+    return kit.packed_case(("smp_2d_ver5", Cn), packing_batch,
+                           lambda: random_params(Cn, 5 * (PACK_D + 1), PACK_L, PACK_MAXV, np.random.default_rng(500 + Cn)), run_packed(Cn),
+                           lambda mols, tg, params, out: smp2d_ver5_ref.run_batch(mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV, out[4]),
+                           want_fields=True, inspect=lambda net: [net.level_sizes(l) for l in range(PACK_L + 1)]) + (blocks,)
 
 
 @pytest.mark.parametrize("Cn", [5, 8, 32, 40, 66, 72, 100, 128])
@@ -200,7 +129,7 @@ def test_batch_across_the_packing_boundaries(gf, Cn):
     and 16-byte operand loads; 66 and 72: three tiles, scalar and 16-byte loads; 100 and 128: four tiles, ragged and full (at 128 the
     LDS images of both projections need the opt-in).  Every level has rows for at least two chunks of dK1, and a last 32-row tile that
     is not full.  Every width runs the whole batch: its fp64 reference takes 0.2 s (C = 40) to 0.5 s (C = 128) on the CPU."""
-    mols, tg, params, blocks, out, res, rg = packed_case(Cn)
+    mols, tg, params, out, (res, rg), blocks = packed_case(Cn)
     assert len(mols) == 70 and sum(len(a) for a, _ in mols) > 64
     sizes = {int(s) for m in out[4] for l in (1, 2) for s in map(len, m[l])}
     assert sizes == set(range(2, 10))   # (two levels above the 12-vertex molecule: its largest field has 9 vertices)
@@ -218,39 +147,21 @@ def test_batch_across_the_packing_boundaries(gf, Cn):
 def test_one_molecule_isolated_inside_the_batch(gf):
     """With every other target equal to its prediction only molecule 68 (the 12-vertex one) has a loss gradient: the batch gradient is
     then that molecule's single-molecule gradient, and its prediction and graph feature are those it has alone."""
-    Cn = 8
-    mols, tg, params, blocks, out, _, _ = packed_case(Cn)
-    k = 68
-    t2 = out[0].astype(np.float32).astype(np.float64).copy()   # (the device's own fp32 predictions: y - t is exactly 0)
-    t2[k] = tg[k]
-    batch = run_net(mols, t2, params, PACK_L, Cn, PACK_D, PACK_MAXV)
-    alone = run_net([mols[k]], tg[k:k + 1], params, PACK_L, Cn, PACK_D, PACK_MAXV)
-    e = blockwise(batch[3], alone[3], blocks)
-    assert np.abs(alone[3]).max() > 0
-    assert e[0] <= TOL, e
-    assert rel_err(batch[0][k:k + 1], alone[0]) <= TOL and rel_err(batch[2][k], alone[2][0]) <= TOL
+    case = packed_case(8)
+    kit.check_isolated(case, 68, run_packed(8), case[5], outputs=True)
 
 
 @pytest.mark.parametrize("Cn", [5, 40, 128])
 def test_two_runs_give_the_same_bits(gf, Cn):
-    mols, tg, params, _, out, _, _ = packed_case(Cn)
-    again = run_net(mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV)
-    for x, y in zip(out[:4], again):
-        assert np.array_equal(x, y)
+    kit.check_same_bits(packed_case(Cn), run_packed(Cn))
 
 
 def test_parity_under_poison(gf):
     """GF_POISON=1 (every buffer the library hands out without contents starts as NaN patterns): no kernel of this level reads memory
     nobody wrote.  The golden and packing-boundary cases, and the level's kernels one by one at every width
     (tests/test_smp_2d_ver5_ops_gpu.py), in a fresh child process."""
-    env = dict(os.environ, GF_POISON="1")
-    sel = "real_class or packing_boundaries or every_instantiation"
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), os.path.join(HERE, "test_smp_2d_ver5_ops_gpu.py"), "-q", "-x", "-m",
-                        "gpu", "-k", sel, "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, timeout=600)
-    tail = (r.stdout + r.stderr)[-2000:]
-    assert r.returncode == 0, tail
-    assert " passed" in tail and "failed" not in tail, tail
+    kit.run_under_poison([__file__, os.path.join(kit.HERE, "test_smp_2d_ver5_ops_gpu.py")],
+                         "real_class or packing_boundaries or every_instantiation")
 
 
 def test_kernel_table(gf):
@@ -327,12 +238,5 @@ def test_feature_is_invariant_under_vertex_permutation(gf):
     adj, x, _ = synthetic_molecule(5, 12)
     L, Cn, D, maxV = 2, 4, 2, 12
     params = random_params(Cn, 5 * (D + 1), L, maxV, np.random.default_rng(9))
-    perm = np.random.default_rng(0).permutation(len(adj))
-    padj, px = adj[np.ix_(perm, perm)], x[perm]
-    a = run_net([(adj, x)], np.array([1.0]), params, L, Cn, D, maxV, want_fields=True)
-    b = run_net([(padj, px)], np.array([1.0]), params, L, Cn, D, maxV, want_fields=True)
-    ra = smp2d_ver5_ref.run(adj, x, 1.0, params, L, Cn, D, maxV, a[4][0])
-    rb = smp2d_ver5_ref.run(padj, px, 1.0, params, L, Cn, D, maxV, b[4][0])
-    assert rel_err(rb["graph_feature"], ra["graph_feature"]) <= 1e-12
-    assert rel_err(b[2], a[2]) <= TOL
-    assert rel_err(a[2][0], ra["graph_feature"]) <= TOL
+    kit.check_permutation_invariance(adj, x, lambda mols, tg: run_net(mols, tg, params, L, Cn, D, maxV, want_fields=True),
+                                     lambda a, f, fields: smp2d_ver5_ref.run(a, f, 1.0, params, L, Cn, D, maxV, fields)["graph_feature"])

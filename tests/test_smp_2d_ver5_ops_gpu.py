@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import smp2d_ver5_ops_ref as ops
+from field_suite import dev
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -26,10 +27,6 @@ CHUNK, FOLD_RUNS = 512, 16        # kV5Chunk, kV5FoldGroups of smp_level_2d_ver5
 WIDTHS = [5, 6, 8, 31, 32, 33, 40, 64, 65, 66, 72, 96, 97, 100, 127, 128]
 NODES = [1, 2, 3, 5, 7, 9, 12] * 6   # 1,878 rows (58 full tiles and one of 22 rows, four chunks of dK1), 234 columns
 RAGGED = [1, 15, 16, 17, 31, 32, 33, 127, 128, 129, 511, 512, 513, 1023, 1025]
-
-
-def dev(x, dtype=np.float32):
-    return torch.as_tensor(np.ascontiguousarray(x, dtype=dtype)).cuda()
 
 
 def ptr(t):

@@ -6,11 +6,11 @@ which tests/test_smp_gamma_cpu.py pins to the real class, and against the real c
 import ctypes as C
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from field_suite import dev, run_under_poison
 from inputs import er_graph, synthetic_molecule, toy_molecules
 from make_gamma_golden import gamma_params
 from util import rel_err
@@ -21,10 +21,6 @@ torch = pytest.importorskip("torch")
 TOL = 1e-5   # the suite's end-to-end tolerance (tests/test_smp_gpu.py)
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-
-
-def dev(x, dtype=np.float32):
-    return torch.as_tensor(np.ascontiguousarray(x, dtype=dtype)).cuda()
 
 
 def gamma_net(L, Cn, F, D, maxV, wl=True, fused=True):
@@ -267,13 +263,7 @@ def test_refusals(gf):
 def test_gamma_tests_pass_under_poison(gf):
     """GF_POISON=1 (every buffer the library hands out without contents starts as NaN patterns): no gamma kernel reads memory nobody
     wrote."""
-    env = dict(os.environ, GF_POISON="1")
-    sel = "matches_the_oracle or real_smp_gamma or wide_fields or qm9_sizes"
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k", sel, "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, timeout=900)
-    tail = (r.stdout + r.stderr)[-2000:]
-    assert r.returncode == 0, tail
-    assert " passed" in tail and "failed" not in tail, tail
+    run_under_poison(__file__, "matches_the_oracle or real_smp_gamma or wide_fields or qm9_sizes", timeout=900)
 
 
 CPP = r"""

@@ -4,6 +4,7 @@ import os
 import numpy as np
 import pytest
 
+from field_suite import dev
 from inputs import f32exact, smp_params, synthetic_molecule, toy_molecules
 from util import golden_cases, rel_err
 
@@ -22,10 +23,6 @@ def note(name, **errs):
     """Record the measured maxima (printed with -s and summarised by test_zz_print_margins)."""
     for k, v in errs.items():
         MARGINS[name + "." + k] = max(MARGINS.get(name + "." + k, 0.0), float(v))
-
-
-def dev(x, dtype=np.float32):
-    return torch.as_tensor(np.ascontiguousarray(x, dtype=dtype)).cuda()
 
 
 def run_batch(gf, mols, targets, params, L, C, F, D, cap, wl=True, fused=True, coulomb=None, wiring=(18, False)):

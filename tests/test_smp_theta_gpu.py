@@ -3,32 +3,19 @@ through gf_smp_model_create, on the level of smp_level_theta.hip.  Checked again
 smp_theta_physics.npz), block by block of the parameter vector, and at shapes without a golden against tests/theta_ref.py, which
 tests/test_smp_theta.py pins to the real classes.  Tolerances: those of tests/test_smp_gamma_gpu.py / test_gamma_physics_gpu.py."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import field_suite as kit
 import theta_ref
+from field_suite import TOL, blockwise, dev, load_golden as load
 from inputs import synthetic_molecule
 from make_theta_golden import model_blocks, random_params, small_molecules, theta_blocks
 from util import rel_err
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-
-TOL = 1e-5   # the suite's end-to-end tolerance (tests/test_smp_gpu.py, tests/test_smp_gamma_gpu.py)
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def dev(x, dtype=np.float32):
-    return torch.as_tensor(np.ascontiguousarray(x, dtype=dtype)).cuda()
-
-
-def load(name):
-    with np.load(os.path.join(HERE, "golden", name)) as z:
-        return {k: z[k] for k in z.files}
 
 
 def theta_net(L, Cn, F, D, cap, maxV, wl=True):
@@ -37,28 +24,7 @@ def theta_net(L, Cn, F, D, cap, maxV, wl=True):
 
 
 def run_theta(mols, targets, params, L, Cn, D, cap, maxV, wl=True, want_fields=False):
-    net = theta_net(L, Cn, mols[0][1].shape[1], D, cap, maxV, wl)
-    net.prepare(mols)
-    p = dev(params)
-    pred, loss, feat = net.forward(p, dev(targets))
-    out = [pred.cpu().numpy().astype(np.float64), loss.cpu().numpy().astype(np.float64), feat.cpu().numpy().astype(np.float64)]
-    grads = torch.empty(net.n_params, device="cuda")
-    net.backward(p, grads)
-    out.append(grads.cpu().numpy().astype(np.float64))
-    if want_fields:
-        out.append([[[net.receptive_field(m, l, v) for v in range(len(mols[m][0]))] for l in range(L + 1)] for m in range(len(mols))])
-    net.close()
-    return out
-
-
-def blockwise(x, ref, blocks):
-    """the largest rel_err over the parameter blocks: one norm over the whole vector cannot see an error confined to a small block"""
-    off, worst = 0, (0.0, "")
-    for name, n in blocks:
-        worst = max(worst, (rel_err(x[off:off + n], ref[off:off + n]), name))
-        off += n
-    assert off == ref.size
-    return worst
+    return kit.run_net(lambda: theta_net(L, Cn, mols[0][1].shape[1], D, cap, maxV, wl), mols, targets, params, want_fields=want_fields)
 
 
 def test_device_matches_the_real_smp_theta(gf):
@@ -112,30 +78,13 @@ def test_tower_initial_weights_match_the_real_class(gf):
 
 def test_batchlearn_steps_match_the_real_smp_theta(gf):
     """Three BatchLearn steps of the real SMP_theta on the four small molecules: initial weights from gf_smp_uniform_init_host after the
-    same srand, gf_smp_adam_step.  Tolerances of test_batchlearn_steps_match_the_real_smp_gamma."""
+    same srand, gf_smp_adam_step.  The bounds are field_suite.check_momentum_trajectory's."""
     z = load("smp_theta.npz")
     L, Cn, D, cap, maxV, seed, nIter = (int(x) for x in z["train__cfg"])
     mols = [(adj, feat) for _, adj, feat, _ in small_molecules()]
-    tg = dev(z["train__targets"])
     lr = float(z["train__lr"][0])
     net = theta_net(L, Cn, 4, D, cap, maxV)
-    C.CDLL(None).srand(seed)
-    p = dev(net.uniform_init())
-    assert np.array_equal(p.cpu().numpy(), z["train__params0"].astype(np.float32))
-    net.prepare(mols)
-    grads = torch.empty(net.n_params, device="cuda")
-    for it in range(nIter):
-        _, loss, _ = net.forward(p, tg)
-        before = float(loss.sum())
-        net.backward(p, grads)
-        net.adam_step(p, grads, lr, len(mols))
-        _, loss, _ = net.forward(p, tg)
-        after = float(loss.sum())
-        assert abs(before - z["train__losses"][it, 0]) <= TOL * max(1.0, before), it
-        assert abs(after - z["train__losses"][it, 1]) <= 5 * TOL * max(1.0, after), it
-    err = np.abs(p.cpu().numpy().astype(np.float64) - z["train__params"])
-    assert err.max() <= 0.005 * lr
-    assert np.median(err) <= 1e-6
+    kit.check_momentum_trajectory(net, lambda p, g: net.adam_step(p, g, lr, len(mols)), z, "train__", mols, seed, nIter, lr, show=None)
     net.close()
 
 
@@ -155,26 +104,26 @@ def packing_batch():
     return mols, np.array(tg)
 
 
-_PACKED = {}
+PACK_L, PACK_D, PACK_MAXV = 2, 1, 9
+
+
+def run_packed(Cn):
+    return lambda mols, tg, params, **kw: run_theta(mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV, PACK_MAXV, **kw)
 
 
 def packed_case(Cn):
     """the packing batch on the device and its fp64 expectation, computed once per channel count"""
-    if Cn not in _PACKED:
-        mols, tg = packing_batch()
-        L, D, maxV = 2, 1, 9
-        params = random_params(theta_blocks(Cn, 5 * (D + 1), L, maxV), np.random.default_rng(100 + Cn))
-        out = run_theta(mols, tg, params, L, Cn, D, maxV, maxV, want_fields=True)
-        ref = theta_ref.run_batch(mols, tg, params, L, Cn, D, maxV, out[4])
-        _PACKED[Cn] = (mols, tg, params, (L, D, maxV), out, ref)
-    return _PACKED[Cn]
+    blocks = theta_blocks(Cn, 5 * (PACK_D + 1), PACK_L, PACK_MAXV)
+    return kit.packed_case(("theta", Cn), packing_batch, lambda: random_params(blocks, np.random.default_rng(100 + Cn)),
+                           run_packed(Cn), lambda mols, tg, params, out: theta_ref.run_batch(mols, tg, params, PACK_L, Cn, PACK_D, PACK_MAXV, out[4]),
+                           want_fields=True) + (blocks,)
 
 
 @pytest.mark.parametrize("Cn", [10, 8])
 def test_batch_across_the_packing_boundaries(gf, Cn):
-    mols, tg, params, (L, D, maxV), out, (rp, rf, rg) = packed_case(Cn)
+    mols, tg, params, out, (rp, rf, rg), blocks = packed_case(Cn)
     assert sum(len(a) for a, _ in mols) > 64
-    e = blockwise(out[3], rg, theta_blocks(Cn, 5 * (D + 1), L, maxV))
+    e = blockwise(out[3], rg, blocks)
     print(Cn, rel_err(out[0], rp), rel_err(out[2], rf), e)
     assert rel_err(out[0], rp) <= TOL
     assert rel_err(out[2], rf) <= TOL
@@ -184,36 +133,18 @@ def test_batch_across_the_packing_boundaries(gf, Cn):
 def test_one_molecule_isolated_inside_the_batch(gf):
     """With every other target equal to its prediction only molecule 37 has a loss gradient: the batch gradient is then that molecule's
     single-molecule gradient."""
-    Cn = 10
-    mols, tg, params, (L, D, maxV), out, _ = packed_case(Cn)
-    k = 37
-    t2 = out[0].astype(np.float32).astype(np.float64).copy()   # (the device's own fp32 predictions: y - t is exactly 0)
-    t2[k] = tg[k]
-    batch = run_theta(mols, t2, params, L, Cn, D, maxV, maxV)
-    alone = run_theta([mols[k]], tg[k:k + 1], params, L, Cn, D, maxV, maxV)
-    e = blockwise(batch[3], alone[3], theta_blocks(Cn, 5 * (D + 1), L, maxV))
-    assert np.abs(alone[3]).max() > 0
-    assert e[0] <= TOL, e
+    case = packed_case(10)
+    kit.check_isolated(case, 37, run_packed(10), case[5])
 
 
 def test_two_runs_give_the_same_bits(gf):
-    Cn = 8
-    mols, tg, params, (L, D, maxV), out, _ = packed_case(Cn)
-    again = run_theta(mols, tg, params, L, Cn, D, maxV, maxV)
-    for x, y in zip(out[:4], again):
-        assert np.array_equal(x, y)
+    kit.check_same_bits(packed_case(8), run_packed(8))
 
 
 def test_parity_under_poison(gf):
     """GF_POISON=1 (every buffer the library hands out without contents starts as NaN patterns): no first-order kernel reads memory
     nobody wrote.  The golden and packing-boundary cases in a child process."""
-    env = dict(os.environ, GF_POISON="1")
-    sel = "real_smp_theta or real_classes or packing_boundaries"
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k", sel, "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, timeout=600)
-    tail = (r.stdout + r.stderr)[-2000:]
-    assert r.returncode == 0, tail
-    assert " passed" in tail and "failed" not in tail, tail
+    kit.run_under_poison(__file__, "real_smp_theta or real_classes or packing_boundaries")
 
 
 def test_only_the_first_order_kernels_run(gf):
@@ -223,11 +154,7 @@ def test_only_the_first_order_kernels_run(gf):
     net.prepare(mols)
     p = dev(random_params(theta_blocks(Cn, 5 * (D + 1), L, maxV), np.random.default_rng(1)))
     grads = torch.empty(net.n_params, device="cuda")
-    net.ctx.set_timing(True)
-    net.forward(p, dev(tg))
-    net.backward(p, grads)
-    counts = {k: n for k, (_, n) in net.ctx.timings().items()}
-    net.ctx.set_timing(False)
+    counts = kit.traced_counts(net, lambda: (net.forward(p, dev(tg)), net.backward(p, grads)))
     nodes, rows, ppos = net.level_sizes(L)
     assert nodes == sum(len(a) for a, _ in mols) and ppos == 0
     assert rows == sum(len(net.receptive_field(m, L, v)) for m in range(len(mols)) for v in range(len(mols[m][0])))
@@ -269,12 +196,5 @@ def test_feature_is_invariant_under_vertex_permutation(gf):
     _, adj, x, _ = small_molecules()[3]
     L, Cn, D, maxV = 2, 8, 2, 9
     params = random_params(theta_blocks(Cn, 4 * (D + 1), L, maxV), np.random.default_rng(9))
-    perm = np.random.default_rng(0).permutation(len(adj))
-    padj, px = adj[np.ix_(perm, perm)], x[perm]
-    a = run_theta([(adj, x)], np.array([1.0]), params, L, Cn, D, maxV, maxV, want_fields=True)
-    b = run_theta([(padj, px)], np.array([1.0]), params, L, Cn, D, maxV, maxV, want_fields=True)
-    ra = theta_ref.run(adj, x, 1.0, params, L, Cn, D, maxV, a[4][0])
-    rb = theta_ref.run(padj, px, 1.0, params, L, Cn, D, maxV, b[4][0])
-    assert rel_err(rb["graph_feature"], ra["graph_feature"]) <= 1e-12
-    assert rel_err(b[2], a[2]) <= TOL
-    assert rel_err(a[2][0], ra["graph_feature"]) <= TOL
+    kit.check_permutation_invariance(adj, x, lambda mols, tg: run_theta(mols, tg, params, L, Cn, D, maxV, maxV, want_fields=True),
+                                     lambda a, f, fields: theta_ref.run(a, f, 1.0, params, L, Cn, D, maxV, fields)["graph_feature"])

@@ -7,15 +7,14 @@ parameter block; no element is excused.
 There is no permutation-invariance test: a dense W_s depends on the order of the field, and the classes break WL ties by vertex index, so
 the reference itself is not invariant on molecules with tied vertices (CH4's hydrogens)."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import field_suite as kit
 import unrestricted_cases as cases
 import unrestricted_ref as uref
+from field_suite import TOL, blockwise, dev
 from inputs import toy_molecules
 from make_unrestricted_golden import random_params, unrestricted_blocks
 from util import rel_err
@@ -23,23 +22,11 @@ from util import rel_err
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-TOL = 1e-5
-HERE = os.path.dirname(os.path.abspath(__file__))
 FORM = cases.FORM
 
 
-def dev(x, dtype=np.float32):
-    return torch.as_tensor(np.ascontiguousarray(x, dtype=dtype)).cuda()
-
-
-_GOLDEN = {}
-
-
 def golden():
-    if not _GOLDEN:
-        with np.load(os.path.join(HERE, "golden", "smp_unrestricted.npz")) as z:
-            _GOLDEN.update({k: z[k] for k in z.files})
-    return _GOLDEN
+    return kit.load_golden("smp_unrestricted.npz")
 
 
 def params_of(gz, tag):
@@ -52,33 +39,9 @@ def net_of(form, L, Cn, F, D, maxV, wl=True):
     return SMPUnrestricted(FORM[form], maxV, L, Cn, F, D, wl)
 
 
-def run_net(form, mols, targets, params, L, Cn, D, maxV, wl=True, want_fields=False, inspect=None):
+def run_net(form, mols, targets, params, L, Cn, D, maxV, wl=True, **kw):
     """[predict, loss, feature, grads (, fields) (, inspect(net))] as float64 arrays"""
-    net = net_of(form, L, Cn, mols[0][1].shape[1], D, maxV, wl)
-    assert net.n_params == np.asarray(params).size
-    net.prepare(mols)
-    p = dev(params)
-    pred, loss, feat = net.forward(p, dev(targets))
-    out = [pred.cpu().numpy().astype(np.float64), loss.cpu().numpy().astype(np.float64), feat.cpu().numpy().astype(np.float64)]
-    grads = torch.empty(net.n_params, device="cuda")
-    net.backward(p, grads)
-    out.append(grads.cpu().numpy().astype(np.float64))
-    if want_fields:
-        out.append([[[net.receptive_field(m, l, v) for v in range(len(mols[m][0]))] for l in range(L + 1)] for m in range(len(mols))])
-    if inspect:
-        out.append(inspect(net))
-    net.close()
-    return out
-
-
-def blockwise(x, ref, blocks):
-    """the largest rel_err over the parameter blocks: one norm over the whole vector cannot see an error confined to a small block"""
-    off, worst = 0, (0.0, "")
-    for name, n in blocks:
-        worst = max(worst, (rel_err(x[off:off + n], ref[off:off + n]), name))
-        off += n
-    assert off == ref.size
-    return worst
+    return kit.run_net(lambda: net_of(form, L, Cn, mols[0][1].shape[1], D, maxV, wl), mols, targets, params, **kw)
 
 
 @pytest.mark.parametrize("form", [1, 2, 3])
@@ -124,33 +87,14 @@ def test_device_matches_the_real_classes(gf, form):
 @pytest.mark.parametrize("form", [3, 2])
 def test_momentum_steps_match_the_real_classes(gf, form):
     """Three BatchLearn steps of the real Unrestricted_SMP_2D / Unrestricted_SMP_1D_ver2 on the four toy molecules: initial weights from
-    gf_smp_uniform_init_host after the same srand, gf_smp_momentum_step.  Tolerances of test_momentum_steps_match_the_real_smp_2d_ver4."""
+    gf_smp_uniform_init_host after the same srand, gf_smp_momentum_step.  The bounds are field_suite.check_momentum_trajectory's."""
     z = golden()
     p_ = "train_u%d__" % form
     _, L, Cn, D, wl, maxV, seed, nIter = (int(x) for x in z[p_ + "cfg"])
     mols = [(adj, feat) for _, adj, feat, _ in toy_molecules()]
-    tg = dev(z[p_ + "targets"])
     lr, gamma = float(z[p_ + "lr"][0]), float(z[p_ + "momentum"][0])
     net = net_of(form, L, Cn, 4, D, maxV, bool(wl))
-    C.CDLL(None).srand(seed)
-    p = dev(net.uniform_init())
-    assert np.array_equal(p.cpu().numpy(), z[p_ + "params0"].astype(np.float32))
-    net.prepare(mols)
-    grads = torch.empty(net.n_params, device="cuda")
-    for it in range(nIter):
-        _, loss, _ = net.forward(p, tg)
-        before = float(loss.sum())
-        net.backward(p, grads)
-        net.step(p, grads, lr, len(mols), gamma)
-        _, loss, _ = net.forward(p, tg)
-        after = float(loss.sum())
-        print(it, before, z[p_ + "losses"][it, 0], after, z[p_ + "losses"][it, 1])
-        assert abs(before - z[p_ + "losses"][it, 0]) <= TOL * max(1.0, before), it
-        assert abs(after - z[p_ + "losses"][it, 1]) <= 5 * TOL * max(1.0, after), it
-    err = np.abs(p.cpu().numpy().astype(np.float64) - z[p_ + "params"])
-    print("trajectory: max", err.max(), "median", np.median(err))
-    assert err.max() <= 0.005 * lr
-    assert np.median(err) <= 1e-6
+    kit.check_momentum_trajectory(net, lambda p, g: net.step(p, g, lr, len(mols), gamma), z, p_, mols, seed, nIter, lr)
     net.close()
 
 
@@ -160,46 +104,34 @@ def test_checkpoint_round_trip_reproduces_the_golden_prediction(gf, tmp_path):
     gz = golden()
     for tag in ("u1_C2H4_c5", "u2_C2H4_c5", "u3_C2H4_c5"):
         form, L, Cn, D, wl, maxV = (int(x) for x in gz[tag + "__cfg"])
-        mol = (gz[tag + "__adj"], gz[tag + "__feature"])
-        net = net_of(form, L, Cn, 4, D, maxV, bool(wl))
-        p = dev(params_of(gz, tag))
-        path = tmp_path / (tag + ".txt")
-        net.save_model(p, path)
-        text = path.read_text().split()
-        assert len(text) == net.n_params and text == ["%g" % x for x in params_of(gz, tag)]
-        q = net.load_model(torch.zeros_like(p), path)
-        loaded = q.cpu().numpy()
-        assert np.array_equal(loaded, np.array([float(t) for t in text], dtype=np.float32))
-        net.prepare([mol])
-        pred, _, _ = net.forward(q, dev(gz[tag + "__result"][2:3]))
-        fields = [[net.receptive_field(0, l, v) for v in range(len(mol[0]))] for l in range(L + 1)]
-        net.close()
-        r = uref.run(form, mol[0], mol[1], float(gz[tag + "__result"][2]), loaded, L, Cn, D, maxV, fields)
-        pred = pred.cpu().numpy().astype(np.float64)
-        print(tag, pred, r["predict"], gz[tag + "__result"][0])
-        assert rel_err(pred, [r["predict"]]) <= TOL, tag
-        assert rel_err(pred, gz[tag + "__result"][:1]) <= TOL, tag
+        adj, x, result = gz[tag + "__adj"], gz[tag + "__feature"], gz[tag + "__result"]
+        kit.check_checkpoint_round_trip(
+            net_of(form, L, Cn, 4, D, maxV, bool(wl)), tag, (adj, x), params_of(gz, tag), result[2:3], result[0],
+            lambda loaded, fields: uref.run(form, adj, x, float(result[2]), loaded, L, Cn, D, maxV, fields)["predict"], tmp_path)
 
 
-_PACKED = {}
+def run_packed(form, Cn):
+    return lambda mols, tg, params, **kw: run_net(form, mols, tg, params, cases.PACK_L, Cn, cases.PACK_D, cases.PACK_MAXV, **kw)
 
 
 def packed_case(form, Cn):
     """the packing batch on the device beside its fp64 expectation (unrestricted_cases), once per (form, channel count)"""
-    if (form, Cn) not in _PACKED:
-        mols, tg, params, blocks, phis, res, rg, margin = cases.packed_reference(form, Cn)
-        assert margin >= cases.MARGIN   # (before anything is compared)
-        out = run_net(form, mols, tg, params, cases.PACK_L, Cn, cases.PACK_D, cases.PACK_MAXV, want_fields=True)
+    mols, tg, params, blocks, phis, res, rg, margin = cases.packed_reference(form, Cn)
+    assert margin >= cases.MARGIN   # (before anything is compared)
+
+    def reference(mols, tg, params, out):
         assert out[4] == phis
-        _PACKED[(form, Cn)] = (mols, tg, params, blocks, out, res, rg, phis)
-    return _PACKED[(form, Cn)]
+        return res, rg, phis
+
+    return kit.packed_case(("unrestricted", form, Cn), lambda: (mols, tg), lambda: params, run_packed(form, Cn), reference,
+                           want_fields=True) + (blocks,)
 
 
 @pytest.mark.parametrize("form,Cn", cases.PACKED_SHAPES)
 def test_batch_across_the_packing_boundaries(gf, form, Cn):
     """against unrestricted_ref, per molecule (prediction, graph feature) and per block of the summed gradient: packed runs that break
     inside and between molecules, a size bucket with a single node, one with more nodes than a reduction chunk holds"""
-    mols, tg, params, blocks, out, res, rg, phis = packed_case(form, Cn)
+    mols, tg, params, out, (res, rg, phis), blocks = packed_case(form, Cn)
     assert len(mols) == 70 and sum(len(a) for a, _ in mols) > 64
     counts = [np.bincount([len(f) for phi in phis for f in phi[l]]) for l in (1, 2)]
     assert (counts[1] == 1).any(), counts   # (level 2: one node of 7 positions, one of 9)
@@ -237,36 +169,19 @@ def test_fields_on_both_sides_of_the_lds_limit(gf, which):
 def test_one_molecule_isolated_inside_the_batch(gf, form, Cn):
     """With every other target equal to its prediction only molecule 68 (the 12-vertex one) has a loss gradient: the batch gradient is
     then that molecule's single-molecule gradient, and its prediction and graph feature are those it has alone."""
-    mols, tg, params, blocks, out = packed_case(form, Cn)[:5]
-    k = 68
-    t2 = out[0].astype(np.float32).astype(np.float64).copy()   # (the device's own fp32 predictions: y - t is exactly 0)
-    t2[k] = tg[k]
-    batch = run_net(form, mols, t2, params, cases.PACK_L, Cn, cases.PACK_D, cases.PACK_MAXV)
-    alone = run_net(form, [mols[k]], tg[k:k + 1], params, cases.PACK_L, Cn, cases.PACK_D, cases.PACK_MAXV)
-    e = blockwise(batch[3], alone[3], blocks)
-    assert np.abs(alone[3]).max() > 0
-    assert e[0] <= TOL, e
-    assert rel_err(batch[0][k:k + 1], alone[0]) <= TOL and rel_err(batch[2][k], alone[2][0]) <= TOL
+    case = packed_case(form, Cn)
+    kit.check_isolated(case, 68, run_packed(form, Cn), case[5], outputs=True)
 
 
 @pytest.mark.parametrize("form,Cn", [(1, 6), (2, 4), (3, 8)])
 def test_two_runs_give_the_same_bits(gf, form, Cn):
-    mols, tg, params, _, out = packed_case(form, Cn)[:5]
-    again = run_net(form, mols, tg, params, cases.PACK_L, Cn, cases.PACK_D, cases.PACK_MAXV)
-    for x, y in zip(out[:4], again):
-        assert np.array_equal(x, y)
+    kit.check_same_bits(packed_case(form, Cn), run_packed(form, Cn))
 
 
 def test_parity_under_poison(gf):
     """GF_POISON=1 (every buffer the library hands out without contents starts as NaN patterns): no kernel of these levels reads memory
     nobody wrote.  The golden, packing-boundary and LDS-limit cases in a fresh child process."""
-    env = dict(os.environ, GF_POISON="1")
-    sel = "real_classes or packing_boundaries or lds_limit"
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k", sel, "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, timeout=600)
-    tail = (r.stdout + r.stderr)[-2000:]
-    assert r.returncode == 0, tail
-    assert " passed" in tail and "failed" not in tail, tail
+    kit.run_under_poison(__file__, "real_classes or packing_boundaries or lds_limit")
 
 
 @pytest.mark.parametrize("form", [1, 2, 3])
@@ -279,11 +194,7 @@ def test_kernel_table(gf, form):
     net.prepare(mols)
     p = dev(random_params(form, Cn, 5 * (cases.PACK_D + 1), L, cases.PACK_MAXV, np.random.default_rng(1)))
     grads = torch.empty(net.n_params, device="cuda")
-    net.ctx.set_timing(True)
-    net.forward(p, dev(tg))
-    net.backward(p, grads)
-    counts = {k: n for k, (_, n) in net.ctx.timings().items()}
-    net.ctx.set_timing(False)
+    counts = kit.traced_counts(net, lambda: (net.forward(p, dev(tg)), net.backward(p, grads)))
     net.close()
     d = "unres2d_" if form == 3 else "unres1d_"
     for k in (d + "level_fwd", d + "node_bwd", d + "bucket_partials", "unres_grads_finish", "unres_gather_bwd"):

@@ -33,6 +33,21 @@ def hop_distances(adj):
     return sp
 
 
+def executor_multiplicity(depth, k):
+    """The executor's semantics of a shared op's gradient: k vertices of one size, processed in descending order; `depth` shared ops
+    between a vertex's op and the parameter, every one adding its running gradient to the next on each appearance (depth 0: the vertex's
+    op adds into the parameter's gradient directly).  Returns how often each vertex is counted, ascending."""
+    out = []
+    for j in range(1, k + 1):           # unit gradient at the j-th vertex (ascending) only
+        ops = [0] * (depth + 1)          # gradients of the shared ops, nearest the vertex first, then the parameter's
+        for v in range(k, 0, -1):        # reverse execution order
+            ops[0] += 1 if v == j else 0
+            for d in range(1, depth + 1):
+                ops[d] += ops[d - 1]
+        out.append(ops[-1])
+    return out
+
+
 def wl_features(feat, hops, D):
     V, F = feat.shape
     out = np.zeros((V, F * (D + 1)))

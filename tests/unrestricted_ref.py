@@ -18,6 +18,7 @@ TensorMul adds into its gradient directly -- `depth` = 0 shared ops in `executor
 `momentum_step` is Momentum::Learn(learning_rate, nBatch).  The receptive fields are an INPUT, as in theta_ref."""
 import numpy as np
 
+from theta_ref import executor_multiplicity as shared_op_multiplicity
 from theta_ref import fields_of, hop_distances, wl_features  # noqa: F401
 
 READOUT_ALPHA = 0.01
@@ -45,23 +46,8 @@ def multiplicity(j):
 
 
 def executor_multiplicity(k, depth=0):
-    """k vertices of one size, processed in descending order; `depth` shared ops between a vertex's op and the parameter, every one adding
-    its running gradient to the next on each appearance.  Returns the count of each vertex, ascending.  depth 0: the unrestricted classes."""
-    out = []
-    for j in range(1, k + 1):
-        ops = [0] * depth
-        lam = 0
-        for v in range(k, 0, -1):
-            hit = 1 if v == j else 0
-            if depth == 0:
-                lam += hit
-                continue
-            ops[0] += hit
-            for d in range(1, depth):
-                ops[d] += ops[d - 1]
-            lam += ops[-1]
-        out.append(lam)
-    return out
+    """theta_ref.executor_multiplicity with the unrestricted classes' depth as the default: no shared op, every vertex counted once"""
+    return shared_op_multiplicity(depth, k)
 
 
 def param_count(form, C, FD, L, maxV):

@@ -3,30 +3,18 @@ QM9-size molecules, L = 3, cap 29, F = 5 (the second tower sees the same molecul
 C = 16 and 32, three ways: the packed gamma tower level (fused), op by op (set_fused(False) on the same handle and batch), and
 SMP_omega_physics / _pairgraphs (nContractions = 18) on the same batch.  All configurations run alternately in one process, timed with
 HIP events after a warm-up; prints one JSON line with the median ms per step of each.
-usage: python tools/gamma_physics_time.py [rounds] [steps per round] [batch]"""
-import json
-import os
+usage: python tools/gamma_physics_time.py [rounds] [steps per round] [batch] [--out file.json]"""
 import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-from inputs import synthetic_molecule  # noqa: E402
-from graphflow_amd.smp import SMPModel  # noqa: E402
+import step_timing as st
+from graphflow_amd.smp import SMPModel
 
-rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-B = int(sys.argv[3]) if len(sys.argv) > 3 else 1024
+rounds, steps, B, out_path = st.parse_args(sys.argv[1:])
 L, cap, F = 3, 29, 5
-mols, tg = [], []
-for i in range(B):
-    adj, feat, t = synthetic_molecule(i)   # (bench.py cfg3's molecules)
-    mols.append((adj, feat))
-    tg.append(t)
-targets = torch.as_tensor(np.array(tg, dtype=np.float32)).cuda()
+mols, targets, _ = st.cfg3_batch(B)
 
 nets, modes = [], {}
 for towers in (1, 2):
@@ -51,27 +39,13 @@ def step(name):
     net.backward(p, g)
 
 
-times = {k: [] for k in modes}
-for name in modes:   # warm-up: pools, workspaces, code objects
-    for _ in range(3):
-        step(name)
-torch.cuda.synchronize()
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-for r in range(rounds):
-    for name in modes:
-        step(name)   # (one untimed step after a switch of handle or plan)
-        e0.record()
-        for _ in range(steps):
-            step(name)
-        e1.record()
-        e1.synchronize()
-        times[name].append(e0.elapsed_time(e1) / steps)
+times = st.time_handles(modes, step, rounds, steps)
 med = {k: float(np.median(v)) for k, v in times.items()}
 keys = sorted({k.rsplit("_gamma", 1)[0].rsplit("_omega", 1)[0] for k in modes})
-print(json.dumps({"tool": "gamma_physics_time", "batch": B, "L": L, "cap": cap, "F": F, "rounds": rounds, "steps": steps,
-                  "ms_per_step_median": {k: round(v, 4) for k, v in med.items()},
-                  "ms_per_step_all": {k: [round(x, 4) for x in v] for k, v in times.items()},
-                  "fused_speedup_vs_op_by_op": {k: round(med[k + "_gamma_op_by_op"] / med[k + "_gamma_fused"], 3) for k in keys},
-                  "gamma_fused_vs_omega": {k: round(med[k + "_gamma_fused"] / med[k + "_omega"], 3) for k in keys}}), flush=True)
+st.emit({"tool": "gamma_physics_time", "batch": B, "L": L, "cap": cap, "F": F, "rounds": rounds, "steps": steps,
+         "ms_per_step_median": {k: round(v, 4) for k, v in med.items()},
+         "ms_per_step_all": {k: [round(x, 4) for x in v] for k, v in times.items()},
+         "fused_speedup_vs_op_by_op": {k: round(med[k + "_gamma_op_by_op"] / med[k + "_gamma_fused"], 3) for k in keys},
+         "gamma_fused_vs_omega": {k: round(med[k + "_gamma_fused"] / med[k + "_omega"], 3) for k in keys}}, out_path)
 for net in nets:
     net.close()

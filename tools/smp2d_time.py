@@ -6,35 +6,20 @@ min .. max ms per step, the per-kernel table of one traced step of each (gf_ctx_
 says where the time goes, not what the step costs), and for the three kernels of the steerable level the bytes they must move at least
 (every input once, every output once, fp32) with the fraction of 8 TB/s that makes in the traced time.
 usage: python tools/smp2d_time.py [regions] [steps per region] [batch] [--out file.json]"""
-import json
-import os
 import sys
 
 import numpy as np
-import torch
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-from inputs import smp_params, synthetic_molecule  # noqa: E402
-from make_smp1d_golden import random_params as params_1d, smp1d_blocks  # noqa: E402
-from make_smp2d_golden import random_params as params_2d  # noqa: E402
-from graphflow_amd.smp import SMP1D, SMP2D, SMPOmega  # noqa: E402
+import step_timing as st
+from inputs import smp_params
+from make_smp1d_golden import random_params as params_1d, smp1d_blocks
+from make_smp2d_golden import random_params as params_2d
+from graphflow_amd.smp import SMP1D, SMP2D, SMPOmega
 
-out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
-args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] != "--out"]
-regions = int(args[0]) if len(args) > 0 else 5
-steps = int(args[1]) if len(args) > 1 else 10
-B = int(args[2]) if len(args) > 2 else 1024
+regions, steps, B, out_path = st.parse_args(sys.argv[1:])
 L, F, D = 3, 5, 5
 CH = {"smp_2d": 64, "smp_2d_ver4": 16, "smp_1d": 64, "smp_omega": 64}
-mols, tg = [], []
-for i in range(B):
-    adj, feat, t = synthetic_molecule(i)   # (bench.py cfg3's molecules)
-    mols.append((adj, feat))
-    tg.append(t)
-maxV = max(len(a) for a, _ in mols)
-targets = torch.as_tensor(np.array(tg, dtype=np.float32)).cuda()
+mols, targets, maxV = st.cfg3_batch(B)
 modes = {}
 for form, name in (("2d", "smp_2d"), ("ver4", "smp_2d_ver4")):
     net = SMP2D(form, maxV, L, CH[name], F, D)
@@ -46,7 +31,7 @@ modes["smp_1d"] = (one, params_1d(smp1d_blocks(1, CH["smp_1d"], F * (D + 1), L, 
 omega = SMPOmega(L, CH["smp_omega"], F, D, maxV)
 omega.prepare(mols)
 modes["smp_omega"] = (omega, smp_params(CH["smp_omega"], F, D, L, 3))
-state = {k: (torch.as_tensor(np.asarray(p, dtype=np.float32)).cuda(), torch.empty(net.n_params, device="cuda")) for k, (net, p) in modes.items()}
+state = st.device_state(modes)
 
 
 def step(name):
@@ -60,27 +45,8 @@ def step(name):
         net.step(p, g, 1e-6, B)
 
 
-for name in modes:   # warm-up: pools, workspaces, code objects
-    for _ in range(3):
-        step(name)
-torch.cuda.synchronize()
-times = {k: [] for k in modes}
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-for r in range(regions):
-    for name in modes:
-        step(name)   # (one untimed step after a switch of handle)
-        e0.record()
-        for _ in range(steps):
-            step(name)
-        e1.record()
-        e1.synchronize()
-        times[name].append(e0.elapsed_time(e1) / steps)
-kernels = {}
-for name, (net, _) in modes.items():
-    net.ctx.set_timing(True)
-    step(name)
-    kernels[name] = {k: [round(ms, 4), int(n)] for k, (ms, n) in sorted(net.ctx.timings().items(), key=lambda kv: -kv[1][0])}
-    net.ctx.set_timing(False)
+times = st.time_handles(modes, step, regions, steps)
+kernels = st.trace_one_step({k: net for k, (net, _) in modes.items()}, step)
 
 
 def level_bytes(name):
@@ -101,17 +67,11 @@ for name in ("smp_2d", "smp_2d_ver4"):
     traffic[name] = {k: {"min_bytes": int(b), "fraction_of_8TBps": round(b / (kernels[name][k][0] * 1e-3) / 8e12, 4)}
                      for k, b in level_bytes(name).items()}
 sizes = {l: modes["smp_2d"][0].level_sizes(l) for l in range(L + 1)}
-line = json.dumps({"tool": "smp2d_time", "batch": B, "L": L, "channels": CH, "F": F, "D": D, "max_nVertices": maxV, "regions": regions, "steps": steps,
-                   "n_params": {k: int(net.n_params) for k, (net, _) in modes.items()},
-                   "ms_per_step_median": {k: round(float(np.median(v)), 4) for k, v in times.items()},
-                   "ms_per_step_min_max": {k: [round(min(v), 4), round(max(v), 4)] for k, v in times.items()},
-                   "level_nodes_rows": {str(l): [int(s[0]), int(s[1])] for l, s in sizes.items()},
-                   "device_bytes": {k: net.device_bytes()[0] for k, (net, _) in modes.items()},
-                   "level_kernel_traffic": traffic,
-                   "kernels_ms_launches_one_step": kernels})
-print(line, flush=True)
-if out_path:
-    with open(out_path, "w") as f:
-        f.write(line + "\n")
+st.emit({"tool": "smp2d_time", "batch": B, "L": L, "channels": CH, "F": F, "D": D, "max_nVertices": maxV, "regions": regions, "steps": steps,
+         "n_params": {k: int(net.n_params) for k, (net, _) in modes.items()}, **st.summary(times),
+         "level_nodes_rows": {str(l): [int(s[0]), int(s[1])] for l, s in sizes.items()},
+         "device_bytes": {k: net.device_bytes()[0] for k, (net, _) in modes.items()},
+         "level_kernel_traffic": traffic,
+         "slowest_kernel": {k: next(iter(v)) for k, v in kernels.items()}, "kernels_ms_launches_one_step": kernels}, out_path)
 for net, _ in modes.values():
     net.close()
