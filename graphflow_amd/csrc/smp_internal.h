@@ -84,7 +84,10 @@ struct WgradCall {
     unsigned *words;
     float *part;
     size_t part_floats;
+    bool any_trow = false;   // trow may leave the gather window of the split kernels (a caller's table at 64 channels): smp_wgrad_split then
+                             // reaches dU[trow] through one descriptor over all of dO, which must be smaller than kWgradWholeBytes
 };
+constexpr size_t kWgradWholeBytes = 0x40000000;   // (1 GiB: the out-of-range offset of an absent block must stay beyond that descriptor)
 // scratch words per level; exact = false: of a level that only ever keeps its channel maxima there (the 64-channel levels of a model)
 size_t smp_wgrad_words(int C, bool exact = true);
 // floats of partial images a call of `rows` rows may need, the folds' second stage and nx extra products' images included

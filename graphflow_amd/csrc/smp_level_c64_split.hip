@@ -65,6 +65,22 @@ __device__ __forceinline__ void split_plain2(float a, float b, float sa, float s
     const f2v r = x - __builtin_convertvector(*h, f2v);
     *l = __builtin_convertvector(r, h2);
 }
+// The same split with the form of the residual FIXED (smp_wgrad_split).  Left to the compiler, `x - h` with x = a sa is contracted into
+// fma(a, sa, -h) in some copies of the code and not in others -- the residual of the unrounded product is not the residual of the rounded
+// one, so the low halves differ in their last bit -- and which copies changes with the code around them (it changed between the loop
+// and its exits when the operand addressing moved to buffer descriptors).  FMA = true: h from the rounded product, l from the fused
+// residual; false: both from the rounded product.  The kernel's tasks keep the forms the builds of record gave them.
+template <bool FMA>
+__device__ __forceinline__ void split_plain2_as(float a, float b, float sa, float sb, h2 *h, h2 *l) {
+#pragma clang fp contract(off)
+    const f2v x = {a * sa, b * sb};
+    *h = __builtin_convertvector(x, h2);
+    const f2v hf = __builtin_convertvector(*h, f2v);
+    f2v r;
+    if constexpr (FMA) r = f2v{__builtin_fmaf(a, sa, -hf[0]), __builtin_fmaf(b, sb, -hf[1])};
+    else r = x - hf;
+    *l = __builtin_convertvector(r, h2);
+}
 
 // MASK: `trow` is the level's PACKED table (DevLevel::trowf) -- bits 0..29 the transposed row, bit 31 = the row's S_ab / T6 blocks
 // hold data, bit 30 = those of the transposed row do.  Half of the rows at QM9 sizes are structurally zero in those two blocks
@@ -930,6 +946,13 @@ __global__ __launch_bounds__(kSmThreads, 2) void smp_small_split(SmallJobs jobs,
 // other stage's four f16 images (A h / l: 256 columns, B h / l: 320 columns), requests its share of slice i + 4 into the
 // registers just freed, and runs its wave's product on the images of slice i: a 64 x 64 output as 2 x 2 MFMA tiles, 12 MFMAs
 // of 8 passes.  Partial images and their fold are those of smp_wgrad_c64: a fixed set of rows per image, fixed order, reproducible.
+//
+// Operands are ADDRESSED per slice, on the scalar unit: every slice of the workgroup is wave-uniform, so its rows of T and dO, the
+// window of dO its gathered rows dU[trow] lie in (kTrowWindow rows on either side), and its entries of trow and of the row factors are
+// reached through buffer descriptors built from blockIdx, gridDim and the loop counter; a lane adds a loop-constant offset (the
+// gathered rows: (trow - window start) x row bytes).  Rows past the end of the level and structurally absent blocks (packed table)
+// take an out-of-range offset and load zeros -- no 64-bit vector address, no row clamp, no page of zeros, no past-the-end factor
+// (they were a quarter of the loop's instructions: NOTES.md, "Weight gradients: slice-based buffer loads").
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kWsThreads = 512, kWsSlice = 16;
 constexpr int kWsACols = 256, kWsBCols = 320;
@@ -953,6 +976,15 @@ __device__ __forceinline__ int ws_col_word(int col) {   // word of (column, row 
 constexpr int kWsAWords = kWsACols / 32 * kWsBlockWords, kWsBWords = kWsBCols / 32 * kWsBlockWords;   // one image (h or l)
 constexpr int kWsStageWords = 2 * (kWsAWords + kWsBWords);
 constexpr size_t kWsLds = 2 * (size_t)kWsStageWords * 4 + 2 * (kWsACols + kWsBCols) * sizeof(float);   // two stages + the column scales and their inverses
+// THE gather window of the weight-gradient kernels (smp_wgrad_split, smp_wgrad_all): the rows a transposed row (e, x) lies from its row
+// (x, e) at most.  Both kernels reach dU[trow] through a descriptor that spans this many rows below and above the slice; a row farther
+// away loads zeros silently, so the contract -- |trow[r] - r| <= kTrowWindow -- is checked on the host before any launch of a
+// caller-supplied table (check_tables of smp_level_ops.hip, kGatherWindow), and holds by construction inside a level, where trow
+// stays in the row's own node of at most kFusedMaxField positions.
+constexpr long long kTrowWindow = (long long)kFusedMaxField * kFusedMaxField;
+// A caller-supplied table that leaves the window (gf_smp_level_wgrad_f32 takes any permutation of the rows) is served by smp_wgrad_split
+// with ONE descriptor over all of dO instead -- WgradCall::any_trow -- while dO is smaller than kWgradWholeBytes (smp_internal.h).
+constexpr size_t kWsWholeBytes = kWgradWholeBytes;
 __constant__ int c_ws_ablk[8] = {0, 1, 0, 2, 3, 0, 1, 0};  // S_ab, S_bc, S_ab, T6, T10, S_ab, S_bc, S_ab
 __constant__ int c_ws_bblk[8] = {1, 1, 2, 0, 0, 3, 3, 4};  // tot L, tot L, tr L, L, L, dU, dU, dU[trow]
 
@@ -961,7 +993,9 @@ __constant__ int c_ws_bblk[8] = {1, 1, 2, 0, 0, 3, 3, 4};  // tot L, tot L, tr L
 // product's 128 x 128 partial image (the four jobs fill one set of images between them).  cmax: the bounds of THIS job's columns.
 template <int W = 1>
 __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__restrict__ T, const float *__restrict__ dO,
-                                                                  const float *__restrict__ rs, int rows, int kchunk,
+                                                                  const float *__restrict__ rs, int rows,
+                                                                  int window,   // rows dU[trow] may lie from its row: kTrowWindow, or
+                                                                  // `rows` (any row of a dO smaller than kWsWholeBytes), see load_slice
                                                                   float *__restrict__ part, const int *__restrict__ trow,
                                                                   const unsigned *__restrict__ cmax,   // [kWsACols + kWsBCols] per-COLUMN magnitude
                                                                   // bounds (float bits) of the nine operand blocks over the level, see below; or
@@ -1025,7 +1059,7 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
     constexpr int NB = 2;
     struct Set {  // one slice's share of a thread: raw rows on their way from HBM
         Task ta, tb[NB];
-        float f0[NB], f1[NB];  // the two rows' factor (tot for the tot L copy, tr for the tr L copy, else unused)
+        float f0, f1;  // the two rows' factor for the first B task (tot for the tot L copy, tr for the tr L copy, else unused)
     };
     const bool has_b1 = wave < 2;
     const int zbit = ((wave >> 1) & 1) == 0 ? 31 : 29;  // the wave stages S_ab / T6 (waves 0, 1, 4, 5) or S_bc / T10 (2, 3, 6, 7)
@@ -1045,75 +1079,99 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
     // The gathered rows' indices (dU[trow]: waves 0 and 1, second task) are requested TWO requests ahead: a request that had to
     // wait for its own indices would wait for everything the wave has in flight before them (loads return in order) -- a full HBM
     // round trip inside every interval, which the barrier hands to all eight waves (measured: the interval WAS that round trip).
-    int ia0 = 0, ia1 = 0, ib0 = 0, ib1 = 0;  // trow of the rows (k, k + 1) of the wave's next / next-but-one request
-    auto fetch_trow = [&](int m, int &t0, int &t1) {
-        const long long k = K(m) + 2 * pair, last = kend - 1;
-        t0 = trow[k < last ? k : last];
-        t1 = trow[k + 1 < last ? k + 1 : last];
+    //
+    // Every request goes through a buffer descriptor whose base and size are wave-uniform: the slice K(m) rides in the descriptor (or
+    // in the scalar offset), a lane's offset is a loop constant, and whatever must not be fetched -- a row past the end of the level,
+    // a structurally absent block of the packed table, the second "task" of waves 2..7 -- gets an offset out of the descriptor's
+    // range and loads zeros without a request leaving the wave.  No 64-bit address, row clamp or select is formed on the vector unit.
+    constexpr int kOor = (int)kWsWholeBytes;            // beyond every descriptor below (the window's spans 8,208 rows of 1 KiB)
+    constexpr unsigned kRsrcFlags = 0x00020000;
+    constexpr int kAuxA = (GF_NT_SITES & 4) ? 2 : 0;   // the rows of T are read once: streamed (aux bit 1 = nt); dO is read five times
+    // the first row of the workgroup's m-th slice, `rows` when the slice lies past the end (then every entry is out of range).  32-bit
+    // unsigned on purpose -- the scalar unit compares no 64-bit integers; a workgroup requests at most six slices past the end, far
+    // less than 2^31 rows
+    auto first_row = [&](int m) {
+        const unsigned k = (blockIdx.x + (unsigned)m * gridDim.x) * (unsigned)kWsSlice;
+        return __builtin_amdgcn_readfirstlane((int)(k < (unsigned)rows ? k : (unsigned)rows));
     };
-    // NO branch in a request or around it: every wave issues the same loads every interval (waves 2..7 repeat their T request as
-    // a second "task" that is never stored; requests past the end of the level re-read its last rows).  With a conditional load
+    const __amdgpu_buffer_rsrc_t rTr = __builtin_amdgcn_make_buffer_rsrc(const_cast<int *>(trow), 0, (unsigned)rows * 4u, kRsrcFlags);
+    const __amdgpu_buffer_rsrc_t rRs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(rs), 0, (unsigned)rows * 8u, kRsrcFlags);
+    int ia0 = 0, ia1 = 0, ib0 = 0, ib1 = 0;  // trow of the rows (k, k + 1) of the wave's next / next-but-one request
+    const int off_tr = 8 * pair;             // rows (2 pair, 2 pair + 1) of a slice in the table of 4-byte entries
+    auto fetch_trow = [&](int m, int &t0, int &t1) {   // (entries past the end read 0: their rows of T are zeros, see load_slice)
+        const int ks = first_row(m);
+        t0 = __builtin_amdgcn_raw_buffer_load_b32(rTr, off_tr, ks * 4, 0);
+        t1 = __builtin_amdgcn_raw_buffer_load_b32(rTr, off_tr + 4, ks * 4, 0);
+    };
+    // a lane's constant byte offsets: its two rows of T in the slice's descriptor, of dO behind the window's scalar offset
+    const int a_col = W == 1 ? 4 * a_quad : (a_quad >> 4) * BS + a_off + ((4 * a_quad) & 63);   // the quad's first column in its row of T
+    const int off_a = 2 * pair * (LDT * 4) + a_col * 4;
+    const int b0_col = (b_blk(0) >= 3 ? BS : 0) + b_off + 4 * b_quad(0);   // first task: L (blocks 0..2) or dU (3) of the lane's own rows
+    const int off_b = 2 * pair * (LDO * 4) + b0_col * 4;
+    const int g_col = (BS + b_off + 4 * b_quad(1)) * 4;                     // second task (waves 0, 1): dU of the gathered rows
+    const int off_rs = 16 * pair + 4 * (b_blk(0) == 2 ? 1 : 0);             // the row's factor: tot, or tr for the tr L copy
+    // NO branch in a request or around it: every wave issues the same loads every interval (waves 2..7 issue a second "task" that is
+    // never stored, at an out-of-range offset: an issue slot and no traffic).  With a conditional load
     // anywhere in the loop the compiler cannot count what is in flight at the join and waits for vmcnt(0) before every split --
     // the whole queue, the requests just issued included (the interval was one HBM round trip for that reason, too).
     auto load_slice = [&](Set &S, int m) {  // the workgroup's m-th slice; calls come with consecutive m
-        // (packed table: bit 31 of a row's entry = its S_ab / T6 blocks hold data; the waves that stage those blocks read the rows
-        //  without from the page of zeros -- 0.73 GB a cfg3 step that is not fetched)
+        // (packed table: bit 31 of a row's entry = its S_ab / T6 blocks hold data; the waves that stage those blocks do not fetch the
+        //  rows without -- 0.73 GB a cfg3 step)
         const int g0 = packed ? (ia0 & 0x1fffffff) : ia0, g1 = packed ? (ia1 & 0x1fffffff) : ia1;
         // (absent: bit 31 clear for the S_ab / T6 waves, bit 29 clear for the S_bc / T10 waves)
         const bool z0 = packed && !((ia0 >> zbit) & 1), z1 = packed && !((ia1 >> zbit) & 1);
-        const bool zg0 = packed && ia0 >= 0, zg1 = packed && ia1 >= 0;   // the gathered dU row meets S_ab of its row only
+        // the gathered dU row meets S_ab of its row only: a row without data skips the gather as well (and waves 2..7 have none)
+        const bool zg0 = !has_b1 || (packed && ia0 >= 0), zg1 = !has_b1 || (packed && ia1 >= 0);
         ia0 = ib0, ia1 = ib1;
         fetch_trow(m + 2, ib0, ib1);
-        const long long last = kend - 1, kk = K(m) + 2 * pair;
-        const int c0 = (int)(kk < last ? kk : last), c1 = (int)(kk + 1 < last ? kk + 1 : last);
-        const int a_col = W == 1 ? 4 * a_quad : (a_quad >> 4) * BS + a_off + ((4 * a_quad) & 63);   // the quad's first column in its row of T
-        const GF_GLOBAL float *zero = gf_global(sp_zero_page) + 4 * q_lo;
-        const GF_GLOBAL float *t0 = gf_global(T) + (size_t)c0 * LDT + a_col, *t1 = gf_global(T) + (size_t)c1 * LDT + a_col;
-        S.ta.v0 = gf_ld_g<4>(reinterpret_cast<const GF_GLOBAL f4v *>(z0 ? zero : t0));
-        S.ta.v1 = gf_ld_g<4>(reinterpret_cast<const GF_GLOBAL f4v *>(z1 ? zero : t1));
-#pragma unroll
-        for (int e = 0; e < NB; ++e) {
-            const int blk = b_blk(e);  // (e == 1: 4 on waves 0 and 1, no block on the others)
-            S.f0[e] = rs[(size_t)c0 * 2 + (blk == 2)];
-            S.f1[e] = rs[(size_t)c1 * 2 + (blk == 2)];
-            const bool gathered = blk == 4;
-            const GF_GLOBAL float *src = blk < 5 ? gf_global(dO) + (blk >= 3 ? BS : 0) + b_off + 4 * b_quad(e) : gf_global(T) + a_col;
-            const int ld = blk < 5 ? LDO : LDT;
-            // (the gathered dU row only meets S_ab of ITS row in product 7: a row without data skips the gather as well)
-            const GF_GLOBAL float *s0 = src + (size_t)(gathered ? g0 : c0) * ld, *s1 = src + (size_t)(gathered ? g1 : c1) * ld;
-            S.tb[e].v0 = gf_ld_g<256>(reinterpret_cast<const GF_GLOBAL f4v *>((gathered && zg0) ? zero : s0));
-            S.tb[e].v1 = gf_ld_g<256>(reinterpret_cast<const GF_GLOBAL f4v *>((gathered && zg1) ? zero : s1));
-        }
+        // the slice's descriptors, on the scalar unit: rows [k0, min(k0 + 16, rows)) of T, and the window of dO that holds the slice's
+        // own rows and every row they may gather: [max(0, k0 - kTrowWindow), min(rows, k0 + 16 + kTrowWindow))
+        const int k0 = first_row(m);
+        const int left = rows - k0 < kWsSlice ? rows - k0 : kWsSlice;   // (0 past the end)
+        const int w0 = __builtin_amdgcn_readfirstlane(k0 > window ? k0 - window : 0);
+        const unsigned w1u = (unsigned)k0 + (unsigned)kWsSlice + (unsigned)window;   // (k0, window <= rows < 2^31)
+        const int w1 = __builtin_amdgcn_readfirstlane((int)(w1u < (unsigned)rows ? w1u : (unsigned)rows));
+        const __amdgpu_buffer_rsrc_t rT =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(T + (size_t)k0 * LDT), 0, (unsigned)(left * (LDT * 4)), kRsrcFlags);
+        // (window = rows: the descriptor spans all of dO, which the launcher admits below kWsWholeBytes only -- kOor stays out of range)
+        const __amdgpu_buffer_rsrc_t rD = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(dO + (size_t)w0 * LDO), 0,
+                                                                             left > 0 ? (unsigned)((w1 - w0) * (LDO * 4)) : 0u, kRsrcFlags);
+        const int own = (k0 - w0) * (LDO * 4);
+        S.ta.v0 = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rT, z0 ? kOor : off_a, 0, kAuxA));
+        S.ta.v1 = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rT, z1 ? kOor : off_a + LDT * 4, 0, kAuxA));
+        S.f0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rRs, off_rs, k0 * 8, 0));
+        S.f1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rRs, off_rs + 8, k0 * 8, 0));
+        S.tb[0].v0 = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rD, off_b, own, 0));
+        S.tb[0].v1 = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rD, off_b + LDO * 4, own, 0));
+        // (unsigned: the zero entry of a row past the end may wrap -- harmless, its rows of T are zeros and the descriptor bounds it)
+        const int og0 = (int)((unsigned)(g0 - w0) * (unsigned)(LDO * 4) + (unsigned)g_col);
+        const int og1 = (int)((unsigned)(g1 - w0) * (unsigned)(LDO * 4) + (unsigned)g_col);
+        S.tb[1].v0 = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rD, zg0 ? kOor : og0, 0, 0));
+        S.tb[1].v1 = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rD, zg1 ? kOor : og1, 0, 0));
     };
     // word (column col0 + i, pair) of the images <- halves of (row k, row k + 1) at column col0 + i: the four columns of the lane's quad
     // are 16 words apart (ws_col_word), one address and four immediate offsets per image -- conflict-free as issued, see kWsQuadSlot
     // (sc: the columns' scales; f0, f1: what rows k and k + 1 are multiplied by besides -- the row's factor for the tot L / tr L copies,
-    //  0 for a row past the end of the level: everything rides in the one multiply the split starts with)
-    auto store_task = [&](const f4v &v0, const f4v &v1, unsigned *H, unsigned *L, int col0, const f4v &sc, float f0, float f1) {
+    //  1 otherwise: it rides in the one multiply the split starts with.  Rows past the end of the level arrive as zeros.)
+    auto store_task = [&](const f4v &v0, const f4v &v1, unsigned *H, unsigned *L, int col0, const f4v &sc, float f0, float f1, auto fma) {
         const int w = ws_col_word(col0) + pair;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             h2 h, l;
-            split_plain2(v0[i], v1[i], sc[i] * f0, sc[i] * f1, &h, &l);
+            split_plain2_as<decltype(fma)::value>(v0[i], v1[i], sc[i] * f0, sc[i] * f1, &h, &l);
             H[w + 16 * i] = __builtin_bit_cast(unsigned, h);
             L[w + 16 * i] = __builtin_bit_cast(unsigned, l);
         }
     };
-    // rows past the range contribute zeros; the scaled copies of L take their row factors (fp32 factor times a power of two: the
+    // rows past the range arrived as zeros; the scaled copies of L take their row factors (fp32 factor times a power of two: the
     // product the fp32 kernel forms, rounded once)
-    auto store_slice = [&](const Set &S, long long k0, unsigned *stage) {
+    auto store_slice = [&](const Set &S, unsigned *stage) {
         unsigned *Ah = stage, *Al = Ah + kWsAWords, *Bh = Al + kWsAWords, *Bl = Bh + kWsBWords;
-        const long long k = k0 + 2 * pair;
-        const float ok0 = k < kend ? 1.f : 0.f, ok1 = k + 1 < kend ? 1.f : 0.f;
-        store_task(S.ta.v0, S.ta.v1, Ah, Al, 4 * a_quad, a_scale, ok0, ok1);
-#pragma unroll
-        for (int e = 0; e < NB; ++e) {
-            if (e == 1 && !has_b1) break;
-            const int blk = b_blk(e);
-            const bool scaled = blk == 1 || blk == 2;
-            const float m0 = scaled ? S.f0[e] : 1.f, m1 = scaled ? S.f1[e] : 1.f;
-            store_task(S.tb[e].v0, S.tb[e].v1, Bh, Bl, 64 * blk + 4 * b_quad(e), b_scale[e], ok0 * m0, ok1 * m1);
-        }
+        // (which task takes its low half from a fused residual is fixed here, not left to the compiler: see split_plain2_as)
+        store_task(S.ta.v0, S.ta.v1, Ah, Al, 4 * a_quad, a_scale, 1.f, 1.f, std::true_type());
+        const bool scaled = b_blk(0) == 1 || b_blk(0) == 2;   // (the second task is the gathered dU: no factor)
+        store_task(S.tb[0].v0, S.tb[0].v1, Bh, Bl, 64 * b_blk(0) + 4 * b_quad(0), b_scale[0], scaled ? S.f0 : 1.f, scaled ? S.f1 : 1.f, std::false_type());
+        if (has_b1) store_task(S.tb[1].v0, S.tb[1].v1, Bh, Bl, 64 * b_blk(1) + 4 * b_quad(1), b_scale[1], 1.f, 1.f, std::true_type());
     };
 
     f16v acc[2][2];
@@ -1144,7 +1202,7 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
     };
     // interval of the workgroup's slice n: Ra holds slice n + 1; the requests of slices n + 2 and n + 3 are in the other two sets
     auto interval = [&](Set &Ra, int n) {
-        store_slice(Ra, K(n + 1), ws_smem + ((n + 1) & 1) * kWsStageWords);  // (past the end: zeros)
+        store_slice(Ra, ws_smem + ((n + 1) & 1) * kWsStageWords);  // (past the end: zeros)
         load_slice(Ra, n + 4);
         products(ws_smem + (n & 1) * kWsStageWords);
         __syncthreads();
@@ -1156,7 +1214,7 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
         load_slice(S0, 0);
         load_slice(S1, 1);
         load_slice(S2, 2);
-        store_slice(S0, K(0), ws_smem);
+        store_slice(S0, ws_smem);
         load_slice(S0, 3);
         __syncthreads();
         // now: images of slice 0 in stage 0; S1 = slice 1, S2 = slice 2, S0 = slice 3
@@ -1208,7 +1266,6 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
 //   * The four waves of a workgroup take its slices in turn; their images are added in wave order through LDS: the same partial
 //     images (8 x CB x CB floats per workgroup), same fold as the staged kernel, and the result does not depend on timing.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr long long kTrowWindow = (long long)kFusedMaxField * kFusedMaxField;   // rows a transposed row (e, x) lies from its row (x, e) at most
 constexpr int kW8Threads = 256;
 // NX = 3 (SMP_2D_ver7 on the 18-slice level, gf_smp::n_extra): three more products on operands the slice already holds as fragments --
 // S_ab^T L, S_bc^T L, S_bc^T (tr L) -- whose images go to `xpart` (three per workgroup), folded by the caller into dX.
@@ -1806,9 +1863,12 @@ template <int W>
 gf_status launch_wgrad_split(gf_ctx *ctx, const WgradCall &a, const WgradPlan &p, const int *tr, const unsigned *cmax, const WgradScales &b, int packed) {
     const gf_status st = opt_in_lds(ctx, smp_wgrad_split<W>, kWsLds);
     if (st != GF_OK) return st;
+    if (a.any_trow && (size_t)a.rows * 2 * a.C * sizeof(float) >= kWsWholeBytes)
+        return fail(ctx, GF_ERR_INVALID, "smp_wgrad_partials: a table beyond the gather window of %lld rows on a dO of 1 GiB or more", kTrowWindow);
+    const int window = a.any_trow ? a.rows : (int)kTrowWindow;
     for (int q = 0; q < W * W; ++q) {
         const int i = q >> 1, j = q & 1;
-        GF_LAUNCH(ctx, "smpf_wgrad", smp_wgrad_split<W>, dim3((unsigned)p.splits), dim3(kWsThreads), kWsLds, a.T, a.dO, a.rowscale, a.rows, p.kchunk, a.part, tr,
+        GF_LAUNCH(ctx, "smpf_wgrad", smp_wgrad_split<W>, dim3((unsigned)p.splits), dim3(kWsThreads), kWsLds, a.T, a.dO, a.rowscale, a.rows, window, a.part, tr,
                   cmax ? cmax + q * (kWsACols + kWsBCols) : cmax, b.chan, b.smax, b.max_tot, b.max_tr, b.row_max, packed, 64 * i, 64 * j, 64 * i * 128 + 64 * j);
     }
     return GF_OK;

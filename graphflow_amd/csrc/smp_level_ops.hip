@@ -41,8 +41,9 @@ __global__ void scale_words(unsigned *__restrict__ w, int n, const unsigned *__r
 constexpr long long kGatherWindow = (long long)kFusedMaxField * kFusedMaxField;
 
 // The tables of a stand-alone call, checked on the host (one blocking copy each: these are test operators): every trow inside the
-// matrix and, `window` > 0, within that many rows of its own row; the low 29 bits of a packed entry equal to the plain one.
-gf_status check_tables(gf_ctx *ctx, const char *who, int rows, const int *trow, const int *trowf, long long window) {
+// matrix and, `window` > 0, within that many rows of its own row (`beyond` given: reported there instead of refused); the low 29 bits
+// of a packed entry equal to the plain one.
+gf_status check_tables(gf_ctx *ctx, const char *who, int rows, const int *trow, const int *trowf, long long window, bool *beyond = nullptr) {
     std::vector<int> t((size_t)rows), f;
     GF_HIP_TRY(ctx, hipMemcpyAsync(t.data(), trow, sizeof(int) * (size_t)rows, hipMemcpyDeviceToHost, ctx->stream));
     if (trowf) {
@@ -53,7 +54,8 @@ gf_status check_tables(gf_ctx *ctx, const char *who, int rows, const int *trow, 
     for (int r = 0; r < rows; ++r) {
         if (t[r] < 0 || t[r] >= rows) return fail(ctx, GF_ERR_INVALID, "%s: trow[%d] = %d outside the %d rows", who, r, t[r], rows);
         const long long d = (long long)t[r] - r;
-        if (window > 0 && (d > window || -d > window))
+        if (window > 0 && (d > window || -d > window) && beyond) *beyond = true;
+        else if (window > 0 && (d > window || -d > window))
             return fail(ctx, GF_ERR_INVALID, "%s: trow[%d] = %d lies more than %lld rows from its row (the gather window of the level)", who, r, t[r], window);
         if (trowf && (f[r] & 0x1fffffff) != t[r])
             return fail(ctx, GF_ERR_INVALID, "%s: trowf[%d] holds row %d, trow[%d] = %d", who, r, f[r] & 0x1fffffff, r, t[r]);
@@ -62,8 +64,11 @@ gf_status check_tables(gf_ctx *ctx, const char *who, int rows, const int *trow, 
 }
 
 // the variants the level's kernels have (before any launch): 0, or the status with the reason recorded
-gf_status check_variant(gf_ctx *ctx, const char *who, int C, int nf, int nx, bool products) {
-    if (!(C == 16 || C == 32 || (C == 64 && products) || C == 128)) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d channels", who, C);
+// (weight gradients, `products` false, at C = 64: with a packed table only -- `packed` -- the plain table is gf_smp_level_wgrad_f32's)
+gf_status check_variant(gf_ctx *ctx, const char *who, int C, int nf, int nx, bool products, bool packed = false) {
+    if (!(C == 16 || C == 32 || (C == 64 && (products || packed)) || C == 128)) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d channels", who, C);
+    if (C == 64 && !products && !smp_split_products(ctx))   // (the fp32 kernel does not mask: it would read the absent blocks)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "%s: the packed table at 64 channels on the fp32 matrix pipe", who);
     if ((nf != 2 && nf != 8) || (nx != 0 && nx != 3)) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d row factors / %d extra products", who, nf, nx);
     if (nx == 3 && nf == 8) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: the extra products take the plain (tot, tr) row factors", who);
     if ((C == 64 || C == 128) && (nx != 0 || nf != 2)) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d row factors / %d extra products at %d channels", who, nf, nx, C);
@@ -90,12 +95,20 @@ gf_status gf_smp_level_wgrad_f32(gf_ctx *ctx, int rows, const float *T, const fl
     if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
     if (rows < 1 || !T || !dO || !rowscale || !trow || !dWst) return fail(ctx, GF_ERR_INVALID, "gf_smp_level_wgrad_f32: bad argument");
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // The split kernel reaches dU[trow] through the gather window of a level and would load zeros beyond it.  This operator takes any
+    // permutation of the rows: a table that leaves the window is served through one descriptor over all of dO (WgradCall::any_trow; the
+    // launch refuses it on a dO of 1 GiB or more), a row outside the matrix is refused here.
+    bool beyond = false;
+    gf_status st = gf::check_tables(ctx, "gf_smp_level_wgrad_f32", rows, trow, nullptr, gf::kGatherWindow, &beyond);
+    if (st != GF_OK) return st;
+    if (beyond && gf::smp_split_products(ctx) && (size_t)rows * 128 * sizeof(float) >= gf::kWgradWholeBytes)
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_level_wgrad_f32: a table beyond the gather window of %lld rows on a dO of 1 GiB or more", gf::kGatherWindow);
     // workspace: the partial images, then the scratch words of the operands' column bounds (exact maxima: there is no level behind them)
     const size_t part_floats = gf::smp_wgrad_part_floats(ctx, rows, 64);
-    gf_status st = gf::ensure_ws(ctx, sizeof(float) * (part_floats + gf::smp_wgrad_words(64)) + 256);
+    st = gf::ensure_ws(ctx, sizeof(float) * (part_floats + gf::smp_wgrad_words(64)) + 256);
     if (st != GF_OK) return st;
     float *ws = static_cast<float *>(ctx->ws);
-    const gf::WgradCall wc = {T, dO, rowscale, rows, 64, 2, trow, nullptr, gf::WgradScales(), reinterpret_cast<unsigned *>(ws + part_floats), ws, part_floats};
+    const gf::WgradCall wc = {T, dO, rowscale, rows, 64, 2, trow, nullptr, gf::WgradScales(), reinterpret_cast<unsigned *>(ws + part_floats), ws, part_floats, beyond};
     gf::FoldGroup fg;
     st = gf::smp_wgrad_partials(ctx, wc, &fg);
     if (st != GF_OK) return st;
@@ -155,7 +168,7 @@ gf_status gf_smp_level_wgrad_ex_f32(gf_ctx *ctx, int C, int nf, int nx, int rows
     if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
     if (rows < 1 || !T || !dO || !rowfac || !trow || !dWst) return fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
     if (nx == 3 && !dX) return fail(ctx, GF_ERR_INVALID, "%s: three extra products without a place for their gradients", who);
-    gf_status st = gf::check_variant(ctx, who, C, nf, nx, false);
+    gf_status st = gf::check_variant(ctx, who, C, nf, nx, false, trowf != nullptr);
     if (st != GF_OK) return st;
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     st = gf::check_tables(ctx, who, rows, trow, trowf, gf::kGatherWindow);

@@ -412,7 +412,9 @@ gf_status gf_smp_set_fused(gf_smp *smp, int on);
  * kernels gf_smp_forward / gf_smp_backward launch on a level's rows (the regrouped K-projection MatMul of GraphFlow/SMP_omega.h:654-657,
  * MatMul.h:48-82).  rows x 64-column blocks, row-major:  T = [S_ab|S_bc|T6|T10] (256 columns),  O / dO = [O_loc | U] (128),
  * rowscale [rows][2] = (tot, tr) of the row's node, trow [rows] = the row holding the transposed position (any permutation of the
- * rows), Wst [8][64][64] = stacked weight blocks W0..W7:
+ * rows; gf_smp_level_wgrad_f32 checks it on the host -- one blocking copy per call -- answers GF_ERR_INVALID for a row outside the
+ * matrix, and serves a table that leaves the level's gather window of 64 x 64 rows, see below, while dO is smaller than 1 GiB),
+ * Wst [8][64][64] = stacked weight blocks W0..W7:
  *   forward  (backward == 0):  O_loc = tot (S_ab W0 + S_bc W1) + tr S_ab W2 + T6 W3 + T10 W4,   U = S_ab W5 + S_bc W6 + S_ab[trow] W7
  *   backward (backward != 0):  dT from dO, the transposed products (dS_ab = tot L W0^T + tr L W2^T + dU W5^T + dU[trow] W7^T, ...)
  *   wgrad:  dWst[p] = sum over rows of (T block of p)^T (dO block of p, with the factor of p)
@@ -439,7 +441,8 @@ gf_status gf_smp_level_wgrad_f32(gf_ctx *ctx, int rows, const float *T, const fl
  * C = 128 (nf = 2, nx = 0; trowf and skip_zero_grads as at 64): every 128 x 128 product runs as four 64 x 64 sub-block passes of the
  * C = 64 kernels -- (reduction half, output half); the second reduction half adds to the first in a fixed order, so two runs give the
  * same bits -- and a row's exponent is taken per 64-column sub-block.
- * The weight gradients exist at C = 128, 32 and 16 (gf_smp_level_wgrad_f32 is the C = 64 kernel); with nf = 2 the operand columns take
+ * The weight gradients exist at C = 128, 32 and 16, and at C = 64 WITH a packed table (trowf; nf = 2, nx = 0; not on the fp32 pipe) --
+ * with the plain table alone gf_smp_level_wgrad_f32 is the C = 64 operator and this one answers GF_ERR_UNSUPPORTED; with nf = 2 the operand columns take
  * their exponents from exact column maxima, with nf = 8 from per-channel upper bounds the operator derives from the operands.
  * Their gathered operand dU[trow] is fetched through a window of 64 x 64 rows on either side of the row's 16-row slice -- in a
  * level a transposed row lies inside its own node, at most (s - 1)^2 rows away -- and a row further off would silently load zeros:
