@@ -507,6 +507,7 @@ gf_status smp_contract(gf_smp *s, int l, bool backward) {
 }  // namespace
 
 LevelKind smp_level_kind(const gf_smp *s, int l) {
+    if (s->cfg.neighbourhood) return LevelKind::Neighbourhood;
     if (s->cfg.unrestricted) return LevelKind::Unrestricted;
     if (s->cfg.first_order) return LevelKind::Theta;   // (one plan: gf_smp_set_fused has no effect)
     if (s->cfg.steerable_2d) return LevelKind::Steerable2D;
@@ -627,6 +628,23 @@ void gf::smp_derive_plan(gf_smp *s, bool allow_embed) {
 gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channels, gf_smp **out, int min_pad, int nClass, double decay) {
     if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
     if (!cfg || !out) return fail(ctx, GF_ERR_INVALID, "gf_smp_create: null argument");
+    if (cfg->neighbourhood) {   // NeuralFingerprint, GCN_1D, GCN_2D (smp_level_neighbourhood.hip): nLevels = 0 is a model; no padding, one plan
+        if (!gf::smp_neighbourhood_config_ok(cfg))
+            return fail(ctx, GF_ERR_INVALID, "gf_smp_create: neighbourhood = %d (1: NeuralFingerprint, 2: GCN_1D, 3: GCN_2D) needs first_order = steerable_2d = "
+                                             "unrestricted = physics = nContractions = custom_matmul = 0, max_receptive_field (%d) == max_nVertices (%d) <= "
+                                             "4096, nLevels >= 0, nDepth = 0 in form 1, max_Radius (%d) >= 0 in form 2, nChanels (%d) <= %d and W1_l, W2_l "
+                                             "within 160 KiB", cfg->neighbourhood, cfg->max_receptive_field, cfg->max_nVertices, cfg->max_Radius,
+                        cfg->nChanels, gf::kNeighbourhoodMaxChanels);
+        gfsmp::table_alloc = gf::pinned_table_alloc;
+        gfsmp::table_free = gf::pinned_table_free;
+        gf_smp *s = new gf_smp();
+        s->ctx = ctx;
+        gf::smp_neighbourhood_config(cfg, &s->cfg);
+        s->ucfg = s->cfg;
+        s->grad_allreduce = 0;   // (no data-parallel exchange: gf_smp_set_grad_allreduce(.., 1) is refused)
+        *out = s;
+        return GF_OK;
+    }
     if (cfg->nLevels < 1 || cfg->nChanels < 1 || cfg->nFeatures < 1 || cfg->nDepth < 0 || cfg->max_receptive_field < 1)
         return fail(ctx, GF_ERR_INVALID, "gf_smp_create: bad configuration");
     gfsmp::table_alloc = gf::pinned_table_alloc;   // (before the first table is built; idempotent)
@@ -780,6 +798,8 @@ gf_status gf_smp_create_classifier(gf_ctx *ctx, const gf_smp_config *cfg, int nC
         return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: a first-order model (first_order = 1) has no classifier read-out");
     if (cfg->unrestricted)   // (refused before the configuration is looked at: there is no class to hold the handle to)
         return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: the Unrestricted_SMP_* models have no `_classification` class");
+    if (cfg->neighbourhood)   // (likewise)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: NeuralFingerprint / GCN_1D / GCN_2D have no `_classification` class");
     if (cfg->physics) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: a physics tower has no read-out of its own (physics = 0)");
     if (nClass < 2) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: nClass = %d (at least 2)", nClass);
     return gf::smp_create(ctx, cfg, /*pad_channels=*/true, out, /*min_pad=*/0, nClass);
@@ -882,6 +902,7 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
     gf_ctx *ctx = s->ctx;
     gf_status st = ensure_ws(ctx, s->ws_need);
     if (st != GF_OK) return st;
+    if (s->cfg.neighbourhood) return smp_neighbourhood_forward(s, params, targets, predict, loss, graph_feature);   // (its own level 0 and read-out)
     const gfsmp::BatchLayout &B = s->lay;
     const int L = s->cfg.nLevels, C = s->cfg.nChanels, FD = s->cfg.fdim();
     const int CL = s->cfg.top_channels();   // (the read-out's width: C but for the channel-doubling SMP_1D_ver2 / ver3)
@@ -916,6 +937,7 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
             st = smp_field_forward_level(s, l, K[l], b[l]);
             break;
         case LevelKind::OpByOp: st = forward_level_opbyop(s, l, K[l], b[l]); break;
+        case LevelKind::Neighbourhood: break;   // (never here: smp_neighbourhood_forward took the pass above)
         }
         if (st == GF_OK && l < L) st = dup_level(s, l);
         if (st != GF_OK) return st;
@@ -1074,6 +1096,7 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
     // (a no-op after this batch's forward; it makes the reverse sweep independent of who grew the context's workspace last)
     gf_status st = ensure_ws(ctx, s->ws_need);
     if (st != GF_OK) return st;
+    if (s->cfg.neighbourhood) return smp_neighbourhood_backward(s, params, grads, accumulate);   // (never a tower: gf_smp_backward_features refuses)
     const gfsmp::BatchLayout &B = s->lay;
     const int L = s->cfg.nLevels, C = s->cfg.top_channels();   // (the read-out's width)
     const float *H, *W;
@@ -1158,6 +1181,7 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
         case LevelKind::Unrestricted:   // dz in place, dS beside it, the per-size gradients (and dscalar_l), df_{l-1} gathered from dS (never a tower)
             st = smp_field_backward_level(s, l, K[l], b[l], dK[l], db[l], l == L ? s->dsh : nullptr, /*rows_too=*/l < L, smp_dp_level_done);
             break;
+        case LevelKind::Neighbourhood: break;   // (never here: smp_neighbourhood_backward took the pass above)
         }
         if (st == GF_OK) st = send_df_down(s, l, kind[l]);
         // a tower: level l - 1 is read out too, and its own contribution joins what its consumers sent down (a fused level adds its own)
@@ -1214,8 +1238,8 @@ gf_status gf_smp_forward(gf_smp *s, const float *params, const float *targets, f
 gf_status gf_smp_dropout_masks(gf_smp *s, const unsigned *masks, float scale) {
     if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
     gf_ctx *ctx = s->ctx;
-    if (s->cfg.per_size())
-        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_dropout_masks: a first-order or steerable_2d handle has no contraction slices to drop");
+    if (s->cfg.per_size() || s->cfg.neighbourhood)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_dropout_masks: a first-order, steerable_2d or neighbourhood handle has no contraction slices to drop");
     if (!masks) {
         s->drop_on = false;
         return GF_OK;
@@ -1258,9 +1282,9 @@ gf_status gf_smp_dropout_masks(gf_smp *s, const unsigned *masks, float scale) {
 
 gf_status gf_smp_set_grad_allreduce(gf_smp *s, int on) {
     if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
-    if (on && s->cfg.per_size())
-        return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_set_grad_allreduce: a first-order or steerable_2d handle has no data-parallel exchange (reduce "
-                                                "the flat gradient)");
+    if (on && (s->cfg.per_size() || s->cfg.neighbourhood))
+        return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_set_grad_allreduce: a first-order, steerable_2d or neighbourhood handle has no data-parallel "
+                                                "exchange (reduce the flat gradient)");
     s->grad_allreduce = on ? 1 : 0;
     return GF_OK;
 }
@@ -1272,8 +1296,8 @@ gf_status gf_smp_backward(gf_smp *s, const float *params, float *grads, int accu
 
 gf_status gf_smp_backward_features(gf_smp *s, const float *params, float *grads, const float *d_feature, int accumulate) {
     if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
-    if (s->cfg.steerable_2d || s->cfg.unrestricted)
-        return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_backward_features: a steerable_2d or unrestricted handle is no tower");
+    if (s->cfg.steerable_2d || s->cfg.unrestricted || s->cfg.neighbourhood)
+        return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_backward_features: a steerable_2d, unrestricted or neighbourhood handle is no tower");
     if (!d_feature) return fail(s->ctx, GF_ERR_INVALID, "gf_smp_backward_features: null feature gradient");
     gf_status st = gf::backward_check(s, &params, &grads, accumulate, d_feature);
     return st == GF_OK ? gf::backward_run(s, params, grads, accumulate, d_feature) : st;
@@ -1310,6 +1334,17 @@ int gf_smp_receptive_field(const gf_smp *s, int mol, int level, int v, int *out,
     if (!s || !s->prepared || mol < 0 || mol >= s->lay.nMol || level < 0 || level > s->cfg.nLevels) return -1;
     const gfsmp::Molecule &M = s->lay.mols[mol];
     if (v < 0 || v >= M.V) return -1;
+    if (s->cfg.neighbourhood) {   // N_level(v), ascending (level 0: the vertex itself)
+        if (level == 0) {
+            if (capacity > 0) out[0] = v;
+            return 1;
+        }
+        const gfsmp::BatchLayout::NeighbourList &nl = s->lay.nb_lists[(size_t)s->lay.nb_list_of_level[level]];
+        const int v0 = s->lay.mol_first_vertex[mol];
+        const long long e0 = nl.ptr[(size_t)v0 + v], n = nl.ptr[(size_t)v0 + v + 1] - e0;
+        for (long long i = 0; i < n && i < capacity; ++i) out[i] = nl.idx[(size_t)(e0 + i)] - v0;
+        return (int)n;
+    }
     const std::vector<int> &f = M.phi[level][v];
     for (int i = 0; i < (int)f.size() && i < capacity; ++i) out[i] = f[i];
     return (int)f.size();
@@ -1321,6 +1356,14 @@ int gf_smp_receptive_field(const gf_smp *s, int mol, int level, int v, int *out,
 static long long smp_read_node(gf_smp *s, int mol, int level, int v, float *out, size_t capacity, bool adjacency) {
     if (!s || !s->prepared || !out || mol < 0 || mol >= s->lay.nMol || level < 0 || level > s->cfg.nLevels) return -1;
     if (adjacency ? level < 1 : !s->forwarded) return -1;
+    if (s->cfg.neighbourhood) {   // h_level[v] [H]; the models have no reduced adjacency
+        const size_t H = (size_t)s->cfg.nChanels;
+        if (adjacency || v < 0 || v >= s->lay.mols[mol].V || H > capacity) return -1;
+        const float *src = s->lv[level].f + ((size_t)s->lay.mol_first_vertex[mol] + v) * H;
+        if (hipMemcpyAsync(out, src, H * sizeof(float), hipMemcpyDeviceToHost, s->ctx->stream) != hipSuccess) return -1;
+        if (hipStreamSynchronize(s->ctx->stream) != hipSuccess) return -1;
+        return (long long)H;
+    }
     const gfsmp::LevelLayout &h = s->lay.level[level];
     int n = -1;
     if (level == 0) {

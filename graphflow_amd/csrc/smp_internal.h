@@ -150,6 +150,33 @@ inline void smp_unrestricted_config(const gf_smp_config *cfg, gfsmp::Config *c) 
     c->max_nVertices = cfg->max_nVertices;
     c->nContractions = c->first_order ? 2 : 0;
 }
+// what neighbourhood = 1, 2, 3 (NeuralFingerprint, GCN_1D, GCN_2D; smp_level_neighbourhood.hip) asks: no other form, no cap, nLevels >= 0,
+// at most kNeighbourhoodMaxChanels channels and the forward level's LDS images within 160 KiB
+constexpr int kNeighbourhoodMaxChanels = 128;
+// the lanes that share one vertex in the level's kernels: the power of two at or above H, at least 8, at most a wave
+inline int smp_neighbourhood_group_width(int H) { return H > 32 ? 64 : H > 16 ? 32 : H > 8 ? 16 : 8; }
+// LDS of the forward level: W1_l^T [F'][H | 1] and W2_l^T [H][H | 1] (odd row strides), one vector of H floats per vertex slot of 256 lanes
+inline size_t smp_neighbourhood_lds_bytes(int H, int FD) {
+    return sizeof(float) * ((size_t)(FD + H) * (size_t)(H | 1) + (size_t)(256 / smp_neighbourhood_group_width(H)) * H);
+}
+inline bool smp_neighbourhood_config_ok(const gf_smp_config *cfg) {
+    if (cfg->neighbourhood < 1 || cfg->neighbourhood > 3) return false;
+    if (cfg->first_order || cfg->steerable_2d || cfg->unrestricted || cfg->physics || cfg->nContractions || cfg->custom_matmul) return false;
+    if (cfg->nLevels < 0 || cfg->nLevels > 64 || cfg->nChanels < 1 || cfg->nFeatures < 1 || cfg->nDepth < 0 || cfg->max_nVertices < 1) return false;
+    if (cfg->max_receptive_field != cfg->max_nVertices || cfg->max_nVertices > 4096) return false;
+    if (cfg->neighbourhood == 1 && cfg->nDepth != 0) return false;
+    if (cfg->neighbourhood == 2 && cfg->max_Radius < 0) return false;
+    if (cfg->nChanels > kNeighbourhoodMaxChanels) return false;
+    const long long FD = (long long)cfg->nFeatures * (cfg->nDepth + 1);
+    return FD <= 65536 && smp_neighbourhood_lds_bytes(cfg->nChanels, (int)FD) <= 160 * 1024;
+}
+inline void smp_neighbourhood_config(const gf_smp_config *cfg, gfsmp::Config *c) {
+    *c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, 0};
+    c->nContractions = 0;
+    c->max_nVertices = cfg->max_nVertices;
+    c->neighbourhood = cfg->neighbourhood;
+    c->max_Radius = cfg->neighbourhood == 2 ? cfg->max_Radius : 0;   // (form 3 stores it and never reads it; form 1 has none)
+}
 void smp_derive_plan(gf_smp *s, bool allow_embed);
 gf_status smp_switch_plan(gf_smp *s, bool embed);
 constexpr int kPadMaxLevels = 15;   // levels a padded model's layout map holds (gf_smp_create: deeper models compute at nChanels)
@@ -282,6 +309,13 @@ struct gf_smp {
         // unrestricted level (smp_level_unrestricted.hip): th_A = S [rows][Cp], Q = dS [rows][Cp], part2d = the chunk partials of the
         // per-size entries at un_part_off (gfsmp::LevelLayout), th_node = [sum s][2 Cp] column partials (db | dscalar) in form 3
         long long *un_part_off = nullptr;
+        // neighbourhood level (smp_level_neighbourhood.hip; every buffer [vertices][H] unless noted): f = h_l, df = dh_l and then dz_l in
+        // place, th_A = n_l, Q = dn_l; form 3: th_B = A = sum of the members' h_{l-1}, th_node = dn_l Tt, nb_T [vertices] = sum_k h_l[v][k],
+        // nb_Tt [vertices] = sum of the members' nb_T of level l - 1, nb_sA [vertices] = <dn_l, A>.  The lists are shared between the levels
+        // of one radius (gfsmp::BatchLayout::nb_lists).
+        const long long *nb_ptr = nullptr, *nb_tptr = nullptr;
+        const int *nb_idx = nullptr, *nb_tidx = nullptr;
+        float *nb_T = nullptr, *nb_Tt = nullptr, *nb_sA = nullptr;
     };
     std::vector<DevLevel> lv;
     // device-built level tables: the batch's adjacency matrices and the per-level statistics the kernels leave behind
@@ -343,7 +377,7 @@ constexpr int kFusedMaxField = 64;
 // What runs level l >= 1 of a pass: the fused 18-slice level (smp_fused.hip) where gf_smp_set_fused allows and smp_fused_supported takes the
 // shape, else the SMP_gamma level where smp_gamma_fused does, else the op-by-op pipeline (smp.hip); nobody else asks the two predicates.
 // Constant for the length of a pass, NOT between passes (gf_smp_set_fused, gf_smp_dropout_masks): a sweep asks at its start, keeps nothing.
-enum class LevelKind { OpByOp, Fused18, Gamma, Theta, Steerable2D, Unrestricted };   // Theta: every level of a first-order handle (cfg.first_order), Steerable2D: of a cfg.steerable_2d one, Unrestricted: of a cfg.unrestricted one (asked first), nothing else
+enum class LevelKind { OpByOp, Fused18, Gamma, Theta, Steerable2D, Unrestricted, Neighbourhood };   // Theta: every level of a first-order handle (cfg.first_order), Steerable2D: of a cfg.steerable_2d one, Unrestricted: of a cfg.unrestricted one (asked first), Neighbourhood: of a cfg.neighbourhood one (level 0 and the read-out too: its sweeps are smp_neighbourhood_forward / _backward), nothing else
 LevelKind smp_level_kind(const gf_smp *s, int l);
 // the kinds on the th_* tables (smp_field_level.h): (namespace gf::field_level holds their kit) they take the read-out's gradient as one vector per node, write df_{l-1} themselves and
 // keep what a second reverse sweep needs
@@ -398,6 +432,11 @@ size_t smp_2d_ver5_wgrad_chunks(long long rows, long long cols);   // partial im
 gf_status smp_unrestricted_forward_level(gf_smp *s, int l, const float *K, const float *sizes);
 gf_status smp_unrestricted_backward_level(gf_smp *s, int l, const float *K, const float *sizes, float *dK, float *dsizes, const float *node_df,
                                           bool rows_too, gf_status (*wgrad_done)(gf_smp *, int));
+// NeuralFingerprint, GCN_1D, GCN_2D (cfg.neighbourhood = 1, 2, 3; smp_level_neighbourhood.hip): the whole sweeps of such a handle -- level 0
+// and the read-out are softmax / plain sums, not the other kinds' -- and its gf_smp_prepare.  params / grads: W1_0; (W1_l, W2_l); W.
+gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature);
+gf_status smp_neighbourhood_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature);
+gf_status smp_neighbourhood_backward(gf_smp *s, const float *params, float *grads, int accumulate);
 // smp_theta_prepare (smp_prepare.hip): gf_smp_prepare of a first-order handle -- the th_* tables, none of the other kinds' buffers.
 gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature);
 // the first-order read-out of level l (smp_field_level.hip): sh[n] = column sums over the node's s rows (ShrinkMatrix), vf = LeakyReLU(sh);
@@ -419,6 +458,10 @@ gf_status smp_dp_level_done(gf_smp *s, int l);
 // ---- the parameter layout: H, (K_1, b_1), ..., (K_L, b_L), W (first-order models: H, (sizes_l, K_l) ..., W, gfsmp::Config::first_order) -- the registration order of SMP_omega.h:289-295 (= save_model order) ----
 // (W is [readout_rows()][C]: one row for the regression models, nClass rows for a classifier, SMP_2D_ver6_classification.h:211-217)
 inline size_t param_count(const gfsmp::Config &c) {
+    if (c.neighbourhood) {   // W1_0; (W1_l, W2_l) for l = 1..L; W
+        const size_t H = (size_t)c.nChanels;
+        return H * c.fdim() + (size_t)c.nLevels * (H * c.fdim() + H * H) + H;
+    }
     size_t n = (size_t)c.nChanels * c.fdim();
     for (int l = 1; l <= c.nLevels; ++l)
         n += c.weight_block(l) + c.size_block(l);

@@ -1,0 +1,408 @@
+// smp_level_neighbourhood.hip -- NeuralFingerprint, GCN_1D and GCN_2D (cfg.neighbourhood = 1, 2, 3; GraphFlow/NeuralFingerprint.h, GCN_1D.h,
+// GCN_2D.h): the seventh LevelKind and, because level 0 and the read-out are these models' own (softmax, a plain sum), both sweeps of such a
+// handle.  One vector h_l[v] [H] per vertex and level:
+//   h_0[v] = softmax(W1_0 x[v]);   n_l[v] = aggregate of h_{l-1}[u] over N_l(v);   h_l[v] = softmax(W1_l x[v] + W2_l n_l[v])
+//   predict = <W, sum_v h_L[v]>, loss = 0.5 (predict - target)^2
+// N_l(v) is a neighbour list of the batch (gfsmp::BatchLayout::nb_lists, members ascending), the aggregate a sum (forms 1, 2) or RisiLayer2D
+// (form 3) in closed form: with T_u = sum_k a_u[k], A = sum_u a_u, Tt = sum_u T_u,  n[i] = A[i] Tt - sum_u a_u[i] T_u  and
+// da_w[j] = g[j] (Tt - T_w) + <g, A - a_w>.  Summed over the consumers v of a source w that is
+//   dh_{l-1}[w][j] = sum_v g_v[j] Tt_v  -  T_w sum_v g_v[j]  +  sum_v <g_v, A_v>  -  <sum_v g_v, a_w>:
+// two vector gathers, one scalar gather and one dot product per source.  Softmax::backward is the class's diagonal rule dz = dh h (1 - h).
+//   nbh_level_fwd    one launch per level (level 0: no aggregate): W1_l^T and W2_l^T in LDS once per workgroup, a group of G lanes
+//                    (G = 8 .. 64, the power of two at or above H; two channels per lane above 64) per vertex: gather, the two products,
+//                    max / exp / sum across the group's lanes; stores h_l, n_l and in form 3 A, Tt and T = sum_k h_l[k]
+//   nbh_node_bwd     dz in place of dh_l (the top level takes dy[mol] W instead), dn = W2_l^T dz; form 3: dn Tt and <dn, A> beside it
+//   nbh_gather_bwd   dh_{l-1} over the transposed list
+//   nbh_readout, nbh_readout_dW   the sum over a molecule's vertices, prediction, loss, dy; dW
+// dW1_l = dz^T X and dW2_l = dz^T N are the library's deterministic TN products.  Every sum runs in a fixed order; no atomics; an operand
+// of a lane without a channel is loaded from a clamped address and never stored (NOTES.md: no guard around an operand load).
+#include <cmath>
+
+#include "smp_field_level.h"
+
+namespace gf {
+namespace {
+
+constexpr int kBlock = 256;   // four waves
+
+// the row stride of the transposed LDS images (smp_neighbourhood_lds_bytes): odd, so their transposing stores hit 32 different banks
+__host__ __device__ inline int row_stride(int H) { return H | 1; }
+
+__device__ __forceinline__ float group_sum(float v, int G) {   // every lane of the group gets the same bits (a + b == b + a)
+    for (int d = G >> 1; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ __forceinline__ float group_max(float v, int G) {
+    for (int d = G >> 1; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
+    return v;
+}
+
+// a * b rounded on its own: the subtraction that follows must not fuse it into an fma (one member: A Tt - a T has to be exactly 0)
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
+// a workgroup's vertex slots: slot = one group of G lanes, kBlock / G of them; it takes vertices vbase + it + slot, it = 0, slots, .. < vpg
+struct Slot {
+    int slot, slots, c0;
+};
+__device__ __forceinline__ Slot slot_of(int G) {
+    const int lane = threadIdx.x & 63, per_wave = 64 / G;
+    return {(int)(threadIdx.x >> 6) * per_wave + lane / G, kBlock / G, lane % G};
+}
+
+template <int NK, bool PAIRS>
+__global__ __launch_bounds__(kBlock) void nbh_level_fwd(const float *__restrict__ W1, const float *__restrict__ W2, const float *__restrict__ x,
+                                                        const float *__restrict__ hprev, const float *__restrict__ Tprev,
+                                                        const long long *__restrict__ ptr, const int *__restrict__ idx, float *__restrict__ h,
+                                                        float *__restrict__ n, float *__restrict__ A, float *__restrict__ T,
+                                                        float *__restrict__ Tt, int nV, int H, int FD, int G, int vpg) {
+    extern __shared__ __align__(16) float lds[];
+    const int Hp = row_stride(H);
+    float *W1t = lds;                            // [FD][Hp]: W1t[f][c] = W1[c][f]
+    float *W2t = W1t + (size_t)FD * Hp;          // [H][Hp]:  W2t[k][c] = W2[c][k]
+    float *nbuf = W2t + (size_t)H * Hp;          // [slots][H]
+    for (int i = threadIdx.x; i < H * FD; i += kBlock) {
+        const int c = i / FD, f = i - c * FD;
+        W1t[f * Hp + c] = W1[i];
+    }
+    if (W2)
+        for (int i = threadIdx.x; i < H * H; i += kBlock) {
+            const int c = i / H, k = i - c * H;
+            W2t[k * Hp + c] = W2[i];
+        }
+    __syncthreads();
+    const Slot sl = slot_of(G);
+    float *nb = nbuf + sl.slot * H;
+    int cc[NK];
+    bool ok[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        ok[k] = sl.c0 + 64 * k < H;
+        cc[k] = ok[k] ? sl.c0 + 64 * k : H - 1;
+    }
+    const int vbase = blockIdx.x * vpg;
+    for (int it = 0; it < vpg; it += sl.slots) {   // (the same trip count in every wave: the barriers below are the workgroup's)
+        const int v = vbase + it + sl.slot;
+        const bool live = v < nV;
+        const size_t vv = live ? v : nV - 1;
+        if (W2) {
+            float a[NK], sacc[NK], tt = 0.f;
+#pragma unroll
+            for (int k = 0; k < NK; ++k) a[k] = sacc[k] = 0.f;
+            const long long e1 = ptr[vv + 1];
+            for (long long e = ptr[vv]; e < e1; ++e) {
+                const size_t u = (size_t)idx[e];
+                const float tu = PAIRS ? Tprev[u] : 0.f;
+#pragma unroll
+                for (int k = 0; k < NK; ++k) {
+                    const float hv = hprev[u * H + cc[k]];
+                    a[k] += hv;
+                    if (PAIRS) sacc[k] = fmaf(hv, tu, sacc[k]);
+                }
+                tt += tu;
+            }
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                // (one member: A Tt and the sum are the same rounded product, n = 0 exactly as in the class)
+                const float nk = PAIRS ? mul_rounded(a[k], tt) - sacc[k] : a[k];
+                if (ok[k]) nb[cc[k]] = nk;
+                if (live && ok[k]) {
+                    n[vv * H + cc[k]] = nk;
+                    if (PAIRS) A[vv * H + cc[k]] = a[k];
+                }
+            }
+            if (PAIRS && live && sl.c0 == 0) Tt[vv] = tt;
+            __syncthreads();
+        }
+        float z[NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) z[k] = 0.f;
+        for (int f = 0; f < FD; ++f) {
+            const float xf = x[vv * FD + f];
+#pragma unroll
+            for (int k = 0; k < NK; ++k) z[k] = fmaf(W1t[f * Hp + cc[k]], xf, z[k]);
+        }
+        if (W2) {
+            for (int j = 0; j < H; ++j) {
+                const float nj = nb[j];
+#pragma unroll
+                for (int k = 0; k < NK; ++k) z[k] = fmaf(W2t[j * Hp + cc[k]], nj, z[k]);
+            }
+            __syncthreads();   // (nb is rewritten by the next vertex of the slot)
+        }
+        float m = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) m = fmaxf(m, ok[k] ? z[k] : -INFINITY);
+        m = group_max(m, G);
+        float ex[NK], sum = 0.f;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            ex[k] = ok[k] ? expf(z[k] - m) : 0.f;
+            sum += ex[k];
+        }
+        sum = group_sum(sum, G);
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const float hv = ex[k] / sum;
+            if (live && ok[k]) h[vv * H + cc[k]] = hv;
+            t += ok[k] ? hv : 0.f;
+        }
+        if (PAIRS) {
+            t = group_sum(t, G);
+            if (live && sl.c0 == 0) T[vv] = t;
+        }
+    }
+}
+
+// dz = dh h (1 - h) in place of dh (top: dh = dy[mol] W), and below level 0's: dn = W2^T dz; PAIRS: dn Tt and <dn, A>
+template <int NK, bool PAIRS>
+__global__ __launch_bounds__(kBlock) void nbh_node_bwd(const float *__restrict__ W2, const float *__restrict__ h, float *__restrict__ dh,
+                                                       const float *__restrict__ dy, const float *__restrict__ Wout,
+                                                       const int *__restrict__ vmol, const float *__restrict__ A,
+                                                       const float *__restrict__ Tt, float *__restrict__ dn, float *__restrict__ gTt,
+                                                       float *__restrict__ sA, int nV, int H, int G, int vpg) {
+    extern __shared__ __align__(16) float lds[];
+    float *W2s = lds;                                  // [H][H] as it is: lanes run along a row
+    float *dzbuf = W2s + (W2 ? (size_t)H * H : 0);     // [slots][H]
+    if (W2)
+        for (int i = threadIdx.x; i < H * H; i += kBlock) W2s[i] = W2[i];
+    __syncthreads();
+    const Slot sl = slot_of(G);
+    float *dzb = dzbuf + sl.slot * H;
+    int cc[NK];
+    bool ok[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        ok[k] = sl.c0 + 64 * k < H;
+        cc[k] = ok[k] ? sl.c0 + 64 * k : H - 1;
+    }
+    const int vbase = blockIdx.x * vpg;
+    for (int it = 0; it < vpg; it += sl.slots) {
+        const int v = vbase + it + sl.slot;
+        const bool live = v < nV;
+        const size_t vv = live ? v : nV - 1;
+        const float top = dy ? dy[vmol[vv]] : 0.f;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const float hv = h[vv * H + cc[k]];
+            const float d = dy ? top * Wout[cc[k]] : dh[vv * H + cc[k]];
+            const float dz = d * hv * (1.f - hv);
+            if (ok[k]) dzb[cc[k]] = dz;
+            if (live && ok[k]) dh[vv * H + cc[k]] = dz;
+        }
+        if (!W2) continue;   // (level 0: uniform for the launch)
+        __syncthreads();
+        float g[NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) g[k] = 0.f;
+        for (int c = 0; c < H; ++c) {
+            const float dzc = dzb[c];
+#pragma unroll
+            for (int k = 0; k < NK; ++k) g[k] = fmaf(W2s[c * H + cc[k]], dzc, g[k]);
+        }
+        __syncthreads();
+        float dot = 0.f;
+        const float ttv = PAIRS ? Tt[vv] : 0.f;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            if (PAIRS) dot += ok[k] ? g[k] * A[vv * H + cc[k]] : 0.f;
+            if (live && ok[k]) {
+                dn[vv * H + cc[k]] = g[k];
+                if (PAIRS) gTt[vv * H + cc[k]] = g[k] * ttv;
+            }
+        }
+        if (PAIRS) {
+            dot = group_sum(dot, G);
+            if (live && sl.c0 == 0) sA[vv] = dot;
+        }
+    }
+}
+
+// dh_{l-1}[w] over the consumers of w (the transposed list, ascending): the sum of dn, or form 3's closed form (see the head of the file)
+template <int NK, bool PAIRS>
+__global__ __launch_bounds__(kBlock) void nbh_gather_bwd(const long long *__restrict__ tptr, const int *__restrict__ tidx,
+                                                         const float *__restrict__ dn, const float *__restrict__ gTt,
+                                                         const float *__restrict__ sA, const float *__restrict__ hprev,
+                                                         const float *__restrict__ Tprev, float *__restrict__ dhprev, int nV, int H, int G) {
+    const Slot sl = slot_of(G);
+    const long long w = (long long)blockIdx.x * sl.slots + sl.slot;
+    const bool live = w < nV;
+    const size_t ww = live ? (size_t)w : (size_t)nV - 1;
+    int cc[NK];
+    bool ok[NK];
+    float gs[NK], ps[NK], sa = 0.f;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        ok[k] = sl.c0 + 64 * k < H;
+        cc[k] = ok[k] ? sl.c0 + 64 * k : H - 1;
+        gs[k] = ps[k] = 0.f;
+    }
+    const long long e1 = tptr[ww + 1];
+    for (long long e = tptr[ww]; e < e1; ++e) {
+        const size_t v = (size_t)tidx[e];
+        if (PAIRS) sa += sA[v];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            gs[k] += dn[v * H + cc[k]];
+            if (PAIRS) ps[k] += gTt[v * H + cc[k]];
+        }
+    }
+    if (PAIRS) {
+        float dot = 0.f;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) dot += ok[k] ? gs[k] * hprev[ww * H + cc[k]] : 0.f;
+        dot = group_sum(dot, G);
+        const float tw = Tprev[ww];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) gs[k] = (ps[k] - tw * gs[k]) + (sa - dot);
+    }
+#pragma unroll
+    for (int k = 0; k < NK; ++k)
+        if (live && ok[k]) dhprev[ww * H + cc[k]] = gs[k];
+}
+
+// one wave per molecule: g = sum over its vertices (ascending) of h_L, predict = <W, g>, the squared loss and dy = predict - target
+__global__ __launch_bounds__(64) void nbh_readout(const float *__restrict__ hL, const int *__restrict__ mol_ptr, const float *__restrict__ W,
+                                                  const float *__restrict__ target, float *__restrict__ g, float *__restrict__ yhat,
+                                                  float *__restrict__ loss, float *__restrict__ dy, int H) {
+    const int m = blockIdx.x;
+    float part = 0.f;
+    for (int c = threadIdx.x; c < H; c += 64) {
+        float acc = 0.f;
+        for (int v = mol_ptr[m]; v < mol_ptr[m + 1]; ++v) acc += hL[(size_t)v * H + c];
+        g[(size_t)m * H + c] = acc;
+        part = fmaf(acc, W[c], part);
+    }
+    part = group_sum(part, 64);
+    if (threadIdx.x == 0) {
+        const float t = target ? target[m] : 0.f;
+        yhat[m] = part;
+        if (loss) loss[m] = 0.5f * (part - t) * (part - t);
+        dy[m] = part - t;   // SquaredLoss::backward
+    }
+}
+
+// dW[c] += sum_m dy[m] g[m][c] (InnerProduct::backward, second operand): 64 channels per workgroup, row r of its 16 sums the molecules
+// r, r + 16, .., the 16 partials are folded in order
+__global__ __launch_bounds__(1024) void nbh_readout_dW(const float *__restrict__ dy, const float *__restrict__ g, float *__restrict__ dW, int H,
+                                                       int nMol) {
+    __shared__ float part[16][64];
+    const int lane = threadIdx.x & 63, r = threadIdx.x >> 6, c = blockIdx.x * 64 + lane;
+    const int cc = c < H ? c : H - 1;
+    float acc = 0.f;
+    for (int m = r; m < nMol; m += 16) acc = fmaf(dy[m], g[(size_t)m * H + cc], acc);
+    part[r][lane] = acc;
+    __syncthreads();
+    if (r == 0 && c < H) {
+        float t = 0.f;
+        for (int k = 0; k < 16; ++k) t += part[k][lane];
+        dW[c] += t;
+    }
+}
+
+// W1_0; (W1_l, W2_l) l = 1..L; W
+template <typename P>
+struct View {
+    std::vector<P *> W1, W2;
+    P *W;
+    View(const gfsmp::Config &c, P *p) : W1(c.nLevels + 1), W2(c.nLevels + 1, nullptr) {
+        const size_t H = (size_t)c.nChanels, FD = (size_t)c.fdim();
+        for (int l = 0; l <= c.nLevels; ++l) {
+            W1[l] = p;
+            p += H * FD;
+            if (l == 0) continue;
+            W2[l] = p;
+            p += H * H;
+        }
+        W = p;
+    }
+};
+
+// vertices per workgroup: whole rounds of its slots, at most GF_NBH_MAX_ROUNDS of them (an A/B build may set another: NOTES.md has what
+// was measured).  A workgroup stages W1_l^T and W2_l^T once however many vertices it takes, but its vertices run one after the other
+// between two barriers each: more workgroups hide that latency, and the staging comes out of L2.
+#ifndef GF_NBH_MAX_ROUNDS
+#define GF_NBH_MAX_ROUNDS 2
+#endif
+inline int vertices_per_group(int nV, int slots) {
+    int rounds = nV / (slots * 256);
+    rounds = rounds < 1 ? 1 : rounds > GF_NBH_MAX_ROUNDS ? GF_NBH_MAX_ROUNDS : rounds;
+    return slots * rounds;
+}
+
+template <int NK, bool PAIRS>
+gf_status launch_level(gf_smp *s, int l, const float *W1, const float *W2, bool forward, bool top, const float *Wout) {
+    gf_ctx *ctx = s->ctx;
+    const int H = s->cfg.nChanels, FD = s->cfg.fdim(), G = smp_neighbourhood_group_width(H), slots = kBlock / G;
+    const int nV = s->lay.level[0].nNodes, vpg = vertices_per_group(nV, slots);
+    const dim3 grid((unsigned)((nV + vpg - 1) / vpg));
+    gf_smp::DevLevel &d = s->lv[l];
+    const gf_smp::DevLevel *pv = l ? &s->lv[l - 1] : nullptr;
+    if (forward) {
+        const size_t bytes = smp_neighbourhood_lds_bytes(H, FD);   // (level 0 leaves W2's part unused: one grant per kernel)
+        gf_status st = opt_in_lds(ctx, nbh_level_fwd<NK, PAIRS>, bytes);
+        if (st != GF_OK) return st;
+        GF_LAUNCH(ctx, "nbh_level_fwd", (nbh_level_fwd<NK, PAIRS>), grid, dim3(kBlock), bytes, W1, W2, s->x, pv ? pv->f : nullptr,
+                  pv ? pv->nb_T : nullptr, d.nb_ptr, d.nb_idx, d.f, d.th_A, d.th_B, d.nb_T, d.nb_Tt, nV, H, FD, G, vpg);
+        return GF_OK;
+    }
+    const size_t bytes = sizeof(float) * ((W2 ? (size_t)H * H : 0) + (size_t)slots * H);
+    gf_status st = opt_in_lds(ctx, nbh_node_bwd<NK, PAIRS>, bytes);
+    if (st != GF_OK) return st;
+    GF_LAUNCH(ctx, "nbh_node_bwd", (nbh_node_bwd<NK, PAIRS>), grid, dim3(kBlock), bytes, W2, d.f, d.df, top ? s->dy : nullptr, Wout,
+              s->top_node_mol, d.th_B, d.nb_Tt, d.Q, d.th_node, d.nb_sA, nV, H, G, vpg);
+    if (!l) return GF_OK;
+    GF_LAUNCH(ctx, "nbh_gather_bwd", (nbh_gather_bwd<NK, PAIRS>), dim3((unsigned)((nV + slots - 1) / slots)), dim3(kBlock), 0, d.nb_tptr,
+              d.nb_tidx, d.Q, d.th_node, d.nb_sA, pv->f, pv->nb_T, pv->df, nV, H, G);
+    return GF_OK;
+}
+// the one place the run-time (channels per lane, aggregate) picks an instantiation
+gf_status level(gf_smp *s, int l, const float *W1, const float *W2, bool forward, bool top = false, const float *Wout = nullptr) {
+    const bool two = s->cfg.nChanels > 64, pairs = s->cfg.neighbourhood == 3;
+    if (two) return pairs ? launch_level<2, true>(s, l, W1, W2, forward, top, Wout) : launch_level<2, false>(s, l, W1, W2, forward, top, Wout);
+    return pairs ? launch_level<1, true>(s, l, W1, W2, forward, top, Wout) : launch_level<1, false>(s, l, W1, W2, forward, top, Wout);
+}
+
+}  // namespace
+
+gf_status smp_neighbourhood_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature) {
+    gf_ctx *ctx = s->ctx;
+    const int L = s->cfg.nLevels, H = s->cfg.nChanels, nMol = s->lay.nMol;
+    const View<const float> p(s->cfg, params);
+    for (int l = 0; l <= L; ++l) {
+        const gf_status st = level(s, l, p.W1[l], p.W2[l], /*forward=*/true);
+        if (st != GF_OK) return st;
+    }
+    GF_LAUNCH(ctx, "nbh_readout", nbh_readout, dim3(nMol), dim3(64), 0, s->lv[L].f, s->mol_ptr, p.W, targets, s->g, s->yhat, loss, s->dy, H);
+    if (predict) GF_HIP_TRY(ctx, hipMemcpyAsync(predict, s->yhat, sizeof(float) * nMol, hipMemcpyDeviceToDevice, ctx->stream));
+    if (graph_feature) GF_HIP_TRY(ctx, hipMemcpyAsync(graph_feature, s->g, sizeof(float) * nMol * H, hipMemcpyDeviceToDevice, ctx->stream));
+    s->bwd_consumed = false;
+    s->forwarded = true;
+    s->has_targets = targets != nullptr;
+    mark_used(s);
+    return GF_OK;
+}
+
+// The reverse sweep from the loss of the last forward; every level keeps what a second sweep needs (dz is rebuilt from dy downwards).
+gf_status smp_neighbourhood_backward(gf_smp *s, const float *params, float *grads, int accumulate) {
+    gf_ctx *ctx = s->ctx;
+    const int L = s->cfg.nLevels, H = s->cfg.nChanels, FD = s->cfg.fdim(), nMol = s->lay.nMol, nV = s->lay.level[0].nNodes;
+    const View<const float> p(s->cfg, params);
+    const View<float> d(s->cfg, grads);
+    if (!accumulate) GF_HIP_TRY(ctx, hipMemsetAsync(grads, 0, sizeof(float) * param_count(s->cfg), ctx->stream));
+    GF_LAUNCH(ctx, "nbh_readout_dW", nbh_readout_dW, dim3((unsigned)((H + 63) / 64)), dim3(1024), 0, s->dy, s->g, d.W, H, nMol);
+    for (int l = L; l >= 0; --l) {
+        gf_status st = level(s, l, nullptr, p.W2[l], /*forward=*/false, /*top=*/l == L, p.W);   // dz_l in lv[l].df, dh_{l-1} in lv[l - 1].df
+        // dW1_l [H][F'] += dz^T X,  dW2_l [H][H] += dz^T N: tall-skinny TN products over the vertices of the batch
+        if (st == GF_OK) st = gemm(ctx, true, false, H, FD, nV, s->lv[l].df, H, 0, s->x, FD, 0, d.W1[l], FD, 0, 1, 1);
+        if (st == GF_OK && l) st = gemm(ctx, true, false, H, H, nV, s->lv[l].df, H, 0, s->lv[l].th_A, H, 0, d.W2[l], H, 0, 1, 1);
+        if (st != GF_OK) return st;
+    }
+    mark_used(s);
+    return GF_OK;
+}
+
+}  // namespace gf

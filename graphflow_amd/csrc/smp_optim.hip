@@ -189,6 +189,11 @@ gf_status gf_smp_adam_reset(gf_smp *s) {
 // same srand() a model built here starts from the same weights as one built by the reference.  Host buffer.
 // the layout of a configuration (what gf_smp_create derives before it touches the device); false: one it would refuse
 static bool host_config(const gf_smp_config *cfg, int nClass, gfsmp::Config *out) {
+    if (cfg && cfg->neighbourhood) {   // NeuralFingerprint, GCN_1D, GCN_2D (gf_smp_config.neighbourhood; nLevels = 0 is a model; no classifier)
+        if (nClass || !gf::smp_neighbourhood_config_ok(cfg)) return false;
+        gf::smp_neighbourhood_config(cfg, out);
+        return true;
+    }
     if (!cfg || cfg->nLevels < 1 || cfg->nChanels < 1 || cfg->nFeatures < 1 || cfg->nDepth < 0 || cfg->max_receptive_field < 1) return false;
     gfsmp::Config c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, cfg->has_WL_ordering};
     c.nContractions = cfg->nContractions ? cfg->nContractions : 18;
@@ -222,6 +227,15 @@ static gf_status uniform_init_host(const gf_smp_config *cfg, int nClass, float *
     if (!params || !host_config(cfg, nClass, &c)) return GF_ERR_INVALID;
     const size_t C = (size_t)c.nChanels;
     std::vector<size_t> sizes;
+    if (c.neighbourhood) {   // W1_l, W2_l by uniform_init(Matrix*): 10 x nRows = 10 H; W by uniform_init(Vector*): 10 x its size = 10 H
+        size_t off = 0;      // (NeuralFingerprint.h:109-119, GCN_1D.h / GCN_2D.h:119-129)
+        for (size_t i = 0, n = gf::param_count(c); i < n; ++i) {
+            double x = (double)(rand() % 10) / (10.0 * (double)C);
+            if (rand() % 2 == 1) x = -x;
+            params[off++] = (float)x;
+        }
+        return GF_OK;
+    }
     sizes.push_back(C * c.fdim());
     for (int l = 1; l <= c.nLevels; ++l) {
         if (c.unrestricted)   // W[size] (W1[size], W2[size]), b[size]: every one a block of its own, uniform_init(Vector*) divides by 10 x its
@@ -271,7 +285,7 @@ size_t gf_smp_config_param_count(const gf_smp_config *cfg) {
 }
 size_t gf_smp_classifier_config_param_count(const gf_smp_config *cfg, int nClass) {
     gfsmp::Config c;
-    if (!cfg || cfg->physics || cfg->first_order == 1 || cfg->unrestricted || nClass < 2) return 0;   // (what gf_smp_create_classifier refuses)
+    if (!cfg || cfg->physics || cfg->first_order == 1 || cfg->unrestricted || cfg->neighbourhood || nClass < 2) return 0;   // (what gf_smp_create_classifier refuses)
     return host_config(cfg, nClass, &c) ? gf::param_count(c) : 0;
 }
 // ... of the `_classification` models (SMP_2D_ver6_classification.h:256-259): sgd->params holds Vector*, so W [nClass][C] is drawn by

@@ -768,5 +768,86 @@ void build_batch_theta(const Config &cfg, int nMol, const int *nVertices, const 
     }
 }
 
+// NeuralFingerprint, GCN_1D, GCN_2D (Config::neighbourhood).  Per molecule: the hop distances and x (wl_features: the classes' shell sums;
+// nDepth = 0 in form 1, where block 0 is the vertex's own feature).  Per distinct list: member (v, u) iff adj[v][u] > 0 (form 1, as
+// NeuralFingerprint.h:186-190 writes it: no self loop, one-sided) or hops[v][u] <= radius (GCN_1D.h:230, GCN_2D.h:230), u ascending.
+void build_batch_neighbourhood(const Config &cfg, int nMol, const int *nVertices, const int *adj, const double *feature, BatchLayout *out) {
+    const int L = cfg.nLevels, FD = cfg.fdim(), F = cfg.nFeatures;
+    out->device_tables = false;
+    out->nMol = nMol;
+    out->mols.assign(nMol, Molecule());
+    out->mol_first_vertex.assign(nMol + 1, 0);
+    std::vector<size_t> adj_off(nMol + 1, 0);
+    out->max_vertices = 1;
+    for (int m = 0; m < nMol; ++m) {
+        out->mol_first_vertex[m + 1] = out->mol_first_vertex[m] + nVertices[m];
+        adj_off[m + 1] = adj_off[m] + (size_t)nVertices[m] * nVertices[m];
+        out->max_vertices = std::max(out->max_vertices, nVertices[m]);
+    }
+    const int totalV = out->mol_first_vertex[nMol];
+    out->x.assign((size_t)totalV * FD, 0.f);
+    out->nb_vertex_mol.assign((size_t)totalV, 0);
+    parallel_for(nMol, [&](int m) {
+        const int V = nVertices[m], v0 = out->mol_first_vertex[m];
+        Molecule &M = out->mols[m];
+        M.V = V;
+        hop_distances(V, adj + adj_off[m], &M.hops);
+        wl_features(cfg, V, feature + (size_t)v0 * F, M.hops, &M.wl);
+        for (size_t i = 0; i < (size_t)V * FD; ++i) out->x[(size_t)v0 * FD + i] = (float)M.wl[i];
+        for (int v = 0; v < V; ++v) out->nb_vertex_mol[(size_t)v0 + v] = m;
+    });
+    out->level.assign(L + 1, LevelLayout());
+    for (int l = 0; l <= L; ++l) {
+        out->level[l].nNodes = totalV;
+        out->level[l].rows = totalV;
+    }
+    out->top_node_of_vertex.clear();
+    out->node_of_vertex.clear();
+    // the distinct lists: form 1 one (the adjacency), else one per radius that occurs
+    std::vector<int> radius;
+    out->nb_list_of_level.assign(L + 1, -1);
+    for (int l = 1; l <= L; ++l) {
+        const int r = cfg.nb_radius(l);
+        size_t k = std::find(radius.begin(), radius.end(), r) - radius.begin();
+        if (k == radius.size()) radius.push_back(r);
+        out->nb_list_of_level[l] = (int)k;
+    }
+    out->nb_lists.assign(radius.size(), BatchLayout::NeighbourList());
+    for (size_t k = 0; k < radius.size(); ++k) {
+        BatchLayout::NeighbourList &nl = out->nb_lists[k];
+        const int r = radius[k];
+        nl.ptr.assign((size_t)totalV + 1, 0);
+        nl.tptr.assign((size_t)totalV + 1, 0);
+        auto member = [&](int m, int v, int u) {
+            const int V = nVertices[m];
+            return cfg.neighbourhood == 1 ? adj[adj_off[m] + (size_t)v * V + u] > 0 : out->mols[m].hops[(size_t)v * V + u] <= r;
+        };
+        for (int m = 0; m < nMol; ++m) {
+            const int V = nVertices[m], v0 = out->mol_first_vertex[m];
+            for (int v = 0; v < V; ++v)
+                for (int u = 0; u < V; ++u)
+                    if (member(m, v, u)) {
+                        nl.ptr[(size_t)v0 + v + 1] += 1;
+                        nl.tptr[(size_t)v0 + u + 1] += 1;
+                    }
+        }
+        for (int g = 0; g < totalV; ++g) {
+            nl.ptr[(size_t)g + 1] += nl.ptr[(size_t)g];
+            nl.tptr[(size_t)g + 1] += nl.tptr[(size_t)g];
+        }
+        nl.idx.assign((size_t)nl.ptr[(size_t)totalV], 0);
+        nl.tidx.assign((size_t)nl.ptr[(size_t)totalV], 0);
+        parallel_for(nMol, [&](int m) {   // (a molecule's vertices own disjoint ranges of both tables)
+            const int V = nVertices[m], v0 = out->mol_first_vertex[m];
+            for (int v = 0; v < V; ++v) {
+                int64_t e = nl.ptr[(size_t)v0 + v], t = nl.tptr[(size_t)v0 + v];
+                for (int u = 0; u < V; ++u) {
+                    if (member(m, v, u)) nl.idx[(size_t)e++] = v0 + u;
+                    if (member(m, u, v)) nl.tidx[(size_t)t++] = v0 + u;   // (consumer u of source v)
+                }
+            }
+        });
+    }
+}
 
 }  // namespace gfsmp

@@ -79,6 +79,12 @@ struct Config {
     // > 0: a tower of CCN_1D (GraphFlow/CCN_1D.h:200, :217; gf_smp_model_config.ccn_1d): C_0 = nChanels, C_l = max(int(ceil(C_{l-1} * decay)), 16),
     // the product in double as the class writes it.  0: the halving of the other towers.
     double decay = 0.0;
+    // 1, 2, 3: NeuralFingerprint, GCN_1D, GCN_2D (GraphFlow/NeuralFingerprint.h, GCN_1D.h, GCN_2D.h; gf_smp_config.neighbourhood;
+    // smp_level_neighbourhood.hip): one vector h_l[v] [nChanels] per vertex and level, aggregated over a neighbourhood N_l(v) (adjacency | hop
+    // distance <= min(l, max_Radius) | <= l) by a sum or, in form 3, RisiLayer2D; softmax at every level.  Parameters: W1_0 [H][F']; for l =
+    // 1..L: W1_l [H][F'], W2_l [H][H]; W [H].  None of the other forms' fields is set: the handle has no fields, rows or per-size blocks.
+    int neighbourhood = 0, max_Radius = 0;
+    int nb_radius(int l) const { return neighbourhood == 1 ? 1 : neighbourhood == 3 || l < max_Radius ? l : max_Radius; }   // of N_l (form 1: the adjacency itself)
     size_t filter_floats(int l) const { return unrestricted == 3 ? (size_t)level_channels(l - 1) : (size_t)unrestricted; }   // per s^2
     bool per_size() const { return first_order || steerable_2d; }   // a handle on the th_* tables, per-size blocks in front of the matrix block
     bool concat() const { return first_order >= 3 || steerable_2d == 2; }   // C_l = 2 C_{l-1}
@@ -245,6 +251,16 @@ struct BatchLayout {
     std::vector<int> top_node_of_vertex;  // [nVertices] node index at level L of global vertex id
     std::vector<std::vector<int> > node_of_vertex;  // [L+1][nVertices] the same for every level (per-level readout)
     std::vector<Molecule> mols;         // kept for introspection (receptive fields)
+    // Config::neighbourhood (build_batch_neighbourhood): one CSR list per distinct neighbourhood the model uses, over GLOBAL vertex ids
+    // (molecules back to back), members ascending; its transpose (t*: the vertices whose list holds u, ascending) for the reverse sweep --
+    // form 1's adjacency may be asymmetric.  nb_list_of_level[l] = the list of N_l, l >= 1.  mols keep only V and the hop distances.
+    struct NeighbourList {
+        tvec<int64_t> ptr, tptr;   // [vertices + 1]
+        tvec<int> idx, tidx;
+    };
+    std::vector<NeighbourList> nb_lists;
+    std::vector<int> nb_list_of_level;   // [L + 1], [0] unused
+    tvec<int> nb_vertex_mol;             // [vertices]
 };
 
 // coulomb: NULL, or the molecules' V x V Coulomb matrices back to back (DenseGraph::coulomb) -- the reduced adjacency of
@@ -255,6 +271,10 @@ void build_batch(const Config &cfg, int nMol, const int *nVertices, const int *a
 // The batch of a first-order model (Config::first_order) or a steerable second-order one (Config::steerable_2d): molecules, level-0 input, nodes in bucket order, rows = field positions, and the
 // th_* tables of every level >= 1; none of the tables of the 18-slice level.  Built on the host threads.
 void build_batch_theta(const Config &cfg, int nMol, const int *nVertices, const int *adj, const double *feature, BatchLayout *out);
+
+// The batch of a neighbourhood model (Config::neighbourhood): hop distances, the shell-sum features x, the neighbour lists and their
+// transposes; none of the field, selection or reduced-adjacency tables.  level[l]: nNodes = rows = vertices.
+void build_batch_neighbourhood(const Config &cfg, int nMol, const int *nVertices, const int *adj, const double *feature, BatchLayout *out);
 
 }  // namespace gfsmp
 #endif

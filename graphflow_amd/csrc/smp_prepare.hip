@@ -914,6 +914,77 @@ gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int
     return GF_OK;
 }
 
+// gf_smp_prepare of a neighbourhood handle (NeuralFingerprint, GCN_1D, GCN_2D; smp_level_neighbourhood.hip): the host builds hop distances,
+// the shell-sum features and one neighbour list (with its transpose) per distinct radius (gfsmp::build_batch_neighbourhood); the device gets
+// those and one [vertices][H] buffer per level and quantity -- none of the field, selection or reduced-adjacency tables.
+gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature) {
+    gf_ctx *ctx = s->ctx;
+    const gfsmp::Config &cfg = s->cfg;
+    for (int m = 0; m < nMol; ++m)
+        if (nVertices[m] > cfg.max_nVertices)
+            return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare: molecule %d has %d vertices, the model was created with max_nVertices = %d", m,
+                        nVertices[m], cfg.max_nVertices);
+    ensure_upload_stream(s);
+    release(s);
+    s->tab_stats = nullptr;
+    s->h_tab_stats.clear();
+    s->h_covered.clear();
+    gfsmp::build_batch_neighbourhood(cfg, nMol, nVertices, adj, feature, &s->lay);
+    const gfsmp::BatchLayout &B = s->lay;
+    const int L = cfg.nLevels;
+    const size_t nV = (size_t)B.mol_first_vertex[nMol], H = (size_t)cfg.nChanels;
+    for (const gfsmp::BatchLayout::NeighbourList &nl : B.nb_lists)
+        if (nl.idx.size() > 0x7fffffffull) return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare: a neighbour list beyond 2^31 entries");
+    s->lv.assign(L + 1, gf_smp::DevLevel());
+    Taker t = {s};
+    struct DevList {
+        long long *ptr = nullptr, *tptr = nullptr;
+        int *idx = nullptr, *tidx = nullptr;
+    };
+    std::vector<DevList> lists(B.nb_lists.size());
+    for (size_t k = 0; k < lists.size(); ++k) {
+        t.put(&lists[k].ptr, B.nb_lists[k].ptr);
+        t.put(&lists[k].idx, B.nb_lists[k].idx);
+        t.put(&lists[k].tptr, B.nb_lists[k].tptr);
+        t.put(&lists[k].tidx, B.nb_lists[k].tidx);
+    }
+    const bool pairs = cfg.neighbourhood == 3;   // RisiLayer2D: A, T, Tt and the three quantities of its closed-form reverse
+    for (int l = 0; l <= L; ++l) {
+        DevLevel &d = s->lv[l];
+        t.alloc(&d.f, nV * H);
+        t.alloc(&d.df, nV * H);
+        if (pairs) t.alloc(&d.nb_T, nV);
+        if (l == 0) continue;
+        const DevList &dl = lists[(size_t)B.nb_list_of_level[l]];
+        d.nb_ptr = dl.ptr, d.nb_idx = dl.idx, d.nb_tptr = dl.tptr, d.nb_tidx = dl.tidx;
+        t.alloc(&d.th_A, nV * H);
+        t.alloc(&d.Q, nV * H);
+        if (pairs) {
+            t.alloc(&d.th_B, nV * H);
+            t.alloc(&d.th_node, nV * H);
+            t.alloc(&d.nb_Tt, nV);
+            t.alloc(&d.nb_sA, nV);
+        }
+    }
+    t.put(&s->x, B.x);
+    t.alloc(&s->g, (size_t)nMol * H);
+    t.alloc(&s->yhat, (size_t)nMol);
+    t.alloc(&s->dy, (size_t)nMol);
+    t.put(&s->top_node_mol, B.nb_vertex_mol);
+    t.put(&s->mol_ptr, B.mol_first_vertex);
+    if (t.st != GF_OK) return t.st;
+    s->wbound = nullptr;
+    s->sh = s->vf = s->dsh = s->colpart = nullptr;
+    s->cls_scores = s->cls_prob = s->cls_dz = s->cls_dg = nullptr;
+    s->mol_nodes = nullptr;
+    s->P = nullptr;
+    s->P_count = 0;
+    s->ws_need = 1 << 20;   // (the TN products of dW1_l / dW2_l grow the context's workspace for their split-K partials themselves)
+    GF_HIP_TRY(ctx, hipStreamSynchronize(upload_stream(s)));
+    s->prepared = true;
+    return GF_OK;
+}
+
 // ints of a level's row-class buffer (see row_class_count), and its builder: three launches on `stream` behind whatever wrote trowf
 size_t smp_row_class_ints(int rows) { return 4 + 2 * ((size_t)rows + 64) + (size_t)(rows + kRcBlock - 1) / kRcBlock + 1; }
 gf_status smp_build_row_classes(gf_ctx *ctx, hipStream_t stream, const int *trowf, int rows, int *buf) {
@@ -944,8 +1015,9 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
     for (int m = 0; m < nMol; ++m)
         if (nVertices[m] <= 0 || nVertices[m] > 4096) return fail(ctx, GF_ERR_INVALID, "molecule %d has %d vertices", m, nVertices[m]);
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((s->cfg.steerable_2d || s->cfg.unrestricted) && coulomb)   // (these classes have no use_coulomb constructor: their adjacency is the molecule's)
-        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_coulomb: a steerable_2d or unrestricted handle has no Coulomb adjacency");
+    if ((s->cfg.steerable_2d || s->cfg.unrestricted || s->cfg.neighbourhood) && coulomb)   // (these classes have no use_coulomb constructor: their adjacency is the molecule's)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_coulomb: a steerable_2d, unrestricted or neighbourhood handle has no Coulomb adjacency");
+    if (s->cfg.neighbourhood) return gf::smp_neighbourhood_prepare(s, nMol, nVertices, adj, feature);
     if (s->cfg.per_size()) return gf::smp_theta_prepare(s, nMol, nVertices, adj, feature);   // (first order: no reduced adjacency, coulomb is inert)
     gf_status st = gf::choose_plan(s, nMol, nVertices, adj, coulomb);
     if (st != GF_OK) return st;
@@ -1001,6 +1073,8 @@ gf_status gf_smp_prepare_molecule_host(const gf_smp_config *cfg, int V, const in
     if (cfg->steerable_2d && !gf::smp_2d_config_ok(cfg))
         return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: steerable_2d = %d needs first_order = 0 and max_receptive_field == max_nVertices",
                     cfg->steerable_2d);
+    if (cfg->neighbourhood)
+        return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: a neighbourhood model (NeuralFingerprint, GCN_1D, GCN_2D) has no receptive fields");
     if (cfg->unrestricted && !gf::smp_unrestricted_config_ok(cfg))
         return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: unrestricted = %d needs first_order = steerable_2d = 0 and max_receptive_field "
                                              "== max_nVertices", cfg->unrestricted);

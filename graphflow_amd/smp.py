@@ -13,7 +13,7 @@ class SMPConfig(C.Structure):
     _fields_ = [("nLevels", C.c_int), ("nChanels", C.c_int), ("nFeatures", C.c_int), ("nDepth", C.c_int),
                 ("max_receptive_field", C.c_int), ("has_WL_ordering", C.c_int), ("nContractions", C.c_int),
                 ("custom_matmul", C.c_int), ("physics", C.c_int), ("first_order", C.c_int), ("max_nVertices", C.c_int),
-                ("steerable_2d", C.c_int), ("unrestricted", C.c_int)]
+                ("steerable_2d", C.c_int), ("unrestricted", C.c_int), ("neighbourhood", C.c_int), ("max_Radius", C.c_int)]
 
 
 class SMPOmega:
@@ -400,6 +400,49 @@ class SMPUnrestricted(SMP1D):
         s = len(self.receptive_field(mol, level, v))
         shape = (s, s, self.cfg.nChanels) if self.form == "2d" else (s, self.level_channels(level))
         out = np.empty(shape, dtype=np.float32)
+        n = self.lib.gf_smp_read_activation(self.handle, mol, level, v, out.ctypes.data_as(C.c_void_p), out.size)
+        if n != out.size:
+            raise RuntimeError("gf_smp_read_activation(%d, %d, %d) returned %d" % (mol, level, v, n))
+        return out
+
+
+class SMPNeighbourhood(SMP1D):
+    """Batched NeuralFingerprint (form "fingerprint"), GCN_1D ("gcn_1d") and GCN_2D ("gcn_2d") of GraphFlow/NeuralFingerprint.h, GCN_1D.h,
+    GCN_2D.h, gf_smp_config.neighbourhood = 1, 2, 3: the baselines of the CCN / SMP models.  One vector h_l[v] [nHiddens] per vertex:
+      h_0[v] = softmax(W1_0 x[v]);  h_l[v] = softmax(W1_l x[v] + W2_l n_l[v]),  n_l[v] = the aggregate of h_{l-1} over N_l(v);
+      "fingerprint": x = the vertex's features (nDepth must be 0), N_l(v) = {u: adj[v, u] > 0}, sum;
+      "gcn_1d":      x = the shell sums up to nDepth, N_l(v) = {u: dist(v, u) <= min(l, max_Radius)}, sum;
+      "gcn_2d":      x likewise, N_l(v) = {u: dist(v, u) <= l} (max_Radius is not read), RisiLayer2D.
+    predict = <W, sum_v h_L[v]>, squared loss.  Parameters in registration order: W1_0[H, F']; for l = 1..L: W1_l[H, F'], W2_l[H, H]; W[H],
+    F' = nFeatures (nDepth + 1).  The softmax gradient is the classes' diagonal rule.  nLevels = 0 is a model.  nHiddens <= 128.  The optimiser
+    is Momentum: step().  There are no classifiers of these forms."""
+
+    FORMS = {"fingerprint": 1, "gcn_1d": 2, "gcn_2d": 3}
+
+    def __init__(self, form, nLevels, nHiddens, nFeatures, nDepth, max_nVertices, max_Radius=1, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.form, self.nClass = form, 0
+        self.cfg = self.config(form, nLevels, nHiddens, nFeatures, nDepth, max_nVertices, max_Radius)
+        h = C.c_void_p()
+        self.ctx.check(self.lib.gf_smp_create(self.ctx.handle, C.byref(self.cfg), C.byref(h)))
+        self.handle = h
+        self.n_params = self.lib.gf_smp_param_count(h)
+        self.n_mol = 0
+
+    @staticmethod
+    def config(form, nLevels, nHiddens, nFeatures, nDepth, max_nVertices, max_Radius=1):
+        if form not in SMPNeighbourhood.FORMS:
+            raise ValueError("SMPNeighbourhood: form %r (\"fingerprint\": NeuralFingerprint, \"gcn_1d\": GCN_1D, \"gcn_2d\": GCN_2D)" % (form,))
+        return SMPConfig(nLevels, nHiddens, nFeatures, nDepth, max_nVertices, 0, 0, 0, 0, 0, max_nVertices, 0, 0,
+                         SMPNeighbourhood.FORMS[form], max_Radius)
+
+    def level_channels(self, level):
+        return self.cfg.nChanels
+
+    def activation(self, mol, level, v):
+        """h_level[v] of molecule `mol` after forward(): numpy [nHiddens]."""
+        out = np.empty(self.cfg.nChanels, dtype=np.float32)
         n = self.lib.gf_smp_read_activation(self.handle, mol, level, v, out.ctypes.data_as(C.c_void_p), out.size)
         if n != out.size:
             raise RuntimeError("gf_smp_read_activation(%d, %d, %d) returned %d" % (mol, level, v, n))

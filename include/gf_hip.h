@@ -341,6 +341,38 @@ typedef struct {
      * (smp, 1), gf_smp_dropout_masks, gf_smp_backward_features, gf_smp_prepare_coulomb with a Coulomb matrix.  gf_smp_model_create has no
      * towers of these forms.  0 (a zero-initialised tail): everything as described above. */
     int unrestricted;
+    /* neighbourhood = 1: NeuralFingerprint, 2: GCN_1D, 3: GCN_2D (GraphFlow/NeuralFingerprint.h, GCN_1D.h, GCN_2D.h) -- the baselines the
+     * CCN / SMP results are reported against.  One vector h_l[v] [H] per vertex and level, H = nChanels (the classes' nHiddens); no receptive-
+     * field tables, no contraction, no per-size blocks:
+     *   h_0[v] = softmax(W1_0 x[v])
+     *   n_l[v] = aggregate of h_{l-1}[u] over N_l(v);   h_l[v] = softmax(W1_l x[v] + W2_l n_l[v])        l = 1 .. nLevels
+     *   predict = <W, sum_v h_L[v]>,  loss = 0.5 (predict - target)^2
+     *   1  x[v] = feature[v] (F' = nFeatures; nDepth must be 0)   N_l(v) = { u : adj[v][u] > 0 } as written: v itself is NOT a member and an
+     *      asymmetric matrix is taken one-sided; an isolated vertex has n = 0                        aggregate: sum (SumVectors)
+     *   2  x[v] = the shell sums, block d = sum of feature[u] over dist(u, v) == d, d = 0 .. nDepth (F' = nFeatures (nDepth + 1))
+     *      N_l(v) = { u : dist(v, u) <= min(l, max_Radius) }, v included                             aggregate: sum (RisiLayer1D)
+     *   3  x as 2;  N_l(v) = { u : dist(v, u) <= l } (the class stores max_Radius and never reads it: ignored here too)
+     *      aggregate RisiLayer2D: n[i] = sum_k sum_{u<w} (a_u[i] a_w[k] + a_u[k] a_w[i]) = A[i] Tt - sum_u a_u[i] T_u with T_u = sum_k a_u[k],
+     *      A = sum_u a_u, Tt = sum_u T_u -- evaluated in that closed form, O(m H) for m members; T_u is 1 only in exact arithmetic and the
+     *      class differentiates through it, so the device does too.  A one-vertex neighbourhood gives n = 0.
+     * dist is the hop distance of the other models (the classes' Floyd-Warshall, literally).  The gradient is the CLASSES': Softmax::backward
+     * is diagonal-only, dz[i] = dh[i] h[i] (1 - h[i]), not the full Jacobian; every other gradient is the plain derivative (W1_l, W2_l enter
+     * the graph once per level).  Parameter order (registration and save_model order): W1_0 [H][F']; for l = 1..L: W1_l [H][F'], W2_l [H][H];
+     * W [H].  nLevels = 0 is valid (level 0 and the read-out).  Required, else GF_ERR_INVALID (gf_smp_config_param_count then answers 0):
+     * first_order = steerable_2d = unrestricted = physics = nContractions = custom_matmul = 0, max_receptive_field == max_nVertices, form 1:
+     * nDepth == 0, form 2: max_Radius >= 0, nChanels <= 128 and (F' + nChanels) (nChanels | 1) + (256 / G) nChanels floats within 160 KiB, G = the
+     * power of two at or above nChanels, at least 8 and at most 64 (a level's W1_l and W2_l sit in LDS beside one vector per group of G
+     * lanes: F' <= 185 at 128 channels).  gf_smp_prepare refuses a molecule above max_nVertices.  The optimiser of the classes is
+     * Momentum: gf_smp_momentum_step.  gf_smp_uniform_init_host draws in the classes' order: every W1_l / W2_l by uniform_init(Matrix*)
+     * (divisor 10 * nRows = 10 H), W by uniform_init(Vector*) (10 H) -- after srand(seed) the classes' weights bit for bit.
+     * gf_smp_read_activation(mol, l, v) returns h_l[v] [H]; gf_smp_receptive_field N_l(v) in ascending vertex order (level 0: {v});
+     * gf_smp_level_sizes nodes = rows = vertices, ppos = 0; gf_smp_feature_width H; gf_smp_read_reduced_adjacency answers -1;
+     * gf_smp_set_fused has no effect.  The level is smp_level_neighbourhood.hip: one forward launch per level, deterministic gathers over
+     * the neighbour lists and their transposes, dW1_l / dW2_l as deterministic TN products; no atomics.  Refused with GF_ERR_UNSUPPORTED
+     * before anything is launched: gf_smp_create_classifier, gf_smp_set_grad_allreduce(smp, 1), gf_smp_dropout_masks,
+     * gf_smp_backward_features, gf_smp_prepare_coulomb with a Coulomb matrix.  gf_smp_model_create has no towers of these forms.
+     * 0 (a zero-initialised tail): everything as described above, max_Radius is not read. */
+    int neighbourhood, max_Radius;
 } gf_smp_config;
 gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out);
 /* gf_smp_param_count of the handle gf_smp_create would build from cfg (0 on a configuration it would refuse).  Host only. */
