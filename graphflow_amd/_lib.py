@@ -120,6 +120,10 @@ PROTOTYPES.update({
     "gf_smp_2d_ver5_rows_ex_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_float, _i, _vp]),
     "gf_smp_2d_ver5_cols_ex_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "gf_smp_2d_ver5_wgrad_ex_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "gf_smp_neighbourhood_fwd_ex_f32": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 12),
+    "gf_smp_neighbourhood_node_bwd_ex_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gf_smp_neighbourhood_gather_bwd_ex_f32": (_i, [_vp, _i, _i, _i] + [_vp] * 8),
+    "gf_smp_neighbourhood_readout_ex_f32": (_i, [_vp, _i, _i, _i] + [_vp] * 9),
     "gf_smp_prepare_molecule_host": (_i, [_vp, _i, C.POINTER(C.c_int), _dp, C.POINTER(C.c_int), _dp]),
     "gf_smp_receptive_field": (_i, [_vp, _i, _i, _i, C.POINTER(C.c_int), _i]),
     "gf_smp_read_activation": (C.c_longlong, [_vp, _i, _i, _i, _vp, C.c_size_t]),

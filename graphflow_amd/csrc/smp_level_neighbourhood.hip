@@ -16,6 +16,8 @@
 //   nbh_readout, nbh_readout_dW   the sum over a molecule's vertices, prediction, loss, dy; dW
 // dW1_l = dz^T X and dW2_l = dz^T N are the library's deterministic TN products.  Every sum runs in a fixed order; no atomics; an operand
 // of a lane without a channel is loaded from a clamped address and never stored (NOTES.md: no guard around an operand load).
+// The four kernels and the read-out are also operators of the C ABI on caller-supplied operands (gf_smp_neighbourhood_fwd_ex_f32,
+// _node_bwd_ex_f32, _gather_bwd_ex_f32, _readout_ex_f32 at the end of the file), through the launchers the level uses.
 #include <cmath>
 
 #include "smp_field_level.h"
@@ -333,37 +335,98 @@ inline int vertices_per_group(int nV, int slots) {
     return slots * rounds;
 }
 
+// The three launches of a level on raw operands: the level below and the stand-alone operators at the end of the file share them.
+// rounds = 0: vertices_per_group; > 0: that many rounds of a workgroup's slots.
+inline int group_vertices(int nV, int slots, int rounds) { return rounds > 0 ? slots * rounds : vertices_per_group(nV, slots); }
+
 template <int NK, bool PAIRS>
-gf_status launch_level(gf_smp *s, int l, const float *W1, const float *W2, bool forward, bool top, const float *Wout) {
-    gf_ctx *ctx = s->ctx;
-    const int H = s->cfg.nChanels, FD = s->cfg.fdim(), G = smp_neighbourhood_group_width(H), slots = kBlock / G;
-    const int nV = s->lay.level[0].nNodes, vpg = vertices_per_group(nV, slots);
-    const dim3 grid((unsigned)((nV + vpg - 1) / vpg));
-    gf_smp::DevLevel &d = s->lv[l];
-    const gf_smp::DevLevel *pv = l ? &s->lv[l - 1] : nullptr;
-    if (forward) {
-        const size_t bytes = smp_neighbourhood_lds_bytes(H, FD);   // (level 0 leaves W2's part unused: one grant per kernel)
-        gf_status st = opt_in_lds(ctx, nbh_level_fwd<NK, PAIRS>, bytes);
-        if (st != GF_OK) return st;
-        GF_LAUNCH(ctx, "nbh_level_fwd", (nbh_level_fwd<NK, PAIRS>), grid, dim3(kBlock), bytes, W1, W2, s->x, pv ? pv->f : nullptr,
-                  pv ? pv->nb_T : nullptr, d.nb_ptr, d.nb_idx, d.f, d.th_A, d.th_B, d.nb_T, d.nb_Tt, nV, H, FD, G, vpg);
-        return GF_OK;
-    }
-    const size_t bytes = sizeof(float) * ((W2 ? (size_t)H * H : 0) + (size_t)slots * H);
-    gf_status st = opt_in_lds(ctx, nbh_node_bwd<NK, PAIRS>, bytes);
+gf_status fwd_launch(gf_ctx *ctx, int H, int FD, int nV, int rounds, const float *W1, const float *W2, const float *x, const float *hprev,
+                     const float *Tprev, const long long *ptr, const int *idx, float *h, float *n, float *A, float *T, float *Tt) {
+    const int G = smp_neighbourhood_group_width(H), vpg = group_vertices(nV, kBlock / G, rounds);
+    const size_t bytes = smp_neighbourhood_lds_bytes(H, FD);   // (level 0 leaves W2's part unused: one grant per kernel)
+    const gf_status st = opt_in_lds(ctx, nbh_level_fwd<NK, PAIRS>, bytes);
     if (st != GF_OK) return st;
-    GF_LAUNCH(ctx, "nbh_node_bwd", (nbh_node_bwd<NK, PAIRS>), grid, dim3(kBlock), bytes, W2, d.f, d.df, top ? s->dy : nullptr, Wout,
-              s->top_node_mol, d.th_B, d.nb_Tt, d.Q, d.th_node, d.nb_sA, nV, H, G, vpg);
-    if (!l) return GF_OK;
-    GF_LAUNCH(ctx, "nbh_gather_bwd", (nbh_gather_bwd<NK, PAIRS>), dim3((unsigned)((nV + slots - 1) / slots)), dim3(kBlock), 0, d.nb_tptr,
-              d.nb_tidx, d.Q, d.th_node, d.nb_sA, pv->f, pv->nb_T, pv->df, nV, H, G);
+    GF_LAUNCH(ctx, "nbh_level_fwd", (nbh_level_fwd<NK, PAIRS>), dim3((unsigned)((nV + vpg - 1) / vpg)), dim3(kBlock), bytes, W1, W2, x, hprev,
+              Tprev, ptr, idx, h, n, A, T, Tt, nV, H, FD, G, vpg);
     return GF_OK;
 }
-// the one place the run-time (channels per lane, aggregate) picks an instantiation
+
+template <int NK, bool PAIRS>
+gf_status node_launch(gf_ctx *ctx, int H, int nV, int rounds, const float *W2, const float *h, float *dh, const float *dy, const float *Wout,
+                      const int *vmol, const float *A, const float *Tt, float *dn, float *gTt, float *sA) {
+    const int G = smp_neighbourhood_group_width(H), slots = kBlock / G, vpg = group_vertices(nV, slots, rounds);
+    const size_t bytes = sizeof(float) * ((W2 ? (size_t)H * H : 0) + (size_t)slots * H);
+    const gf_status st = opt_in_lds(ctx, nbh_node_bwd<NK, PAIRS>, bytes);
+    if (st != GF_OK) return st;
+    GF_LAUNCH(ctx, "nbh_node_bwd", (nbh_node_bwd<NK, PAIRS>), dim3((unsigned)((nV + vpg - 1) / vpg)), dim3(kBlock), bytes, W2, h, dh, dy, Wout,
+              vmol, A, Tt, dn, gTt, sA, nV, H, G, vpg);
+    return GF_OK;
+}
+
+template <int NK, bool PAIRS>
+gf_status gather_launch(gf_ctx *ctx, int H, int nV, const long long *tptr, const int *tidx, const float *dn, const float *gTt, const float *sA,
+                        const float *hprev, const float *Tprev, float *dhprev) {
+    const int G = smp_neighbourhood_group_width(H), slots = kBlock / G;
+    GF_LAUNCH(ctx, "nbh_gather_bwd", (nbh_gather_bwd<NK, PAIRS>), dim3((unsigned)((nV + slots - 1) / slots)), dim3(kBlock), 0, tptr, tidx, dn,
+              gTt, sA, hprev, Tprev, dhprev, nV, H, G);
+    return GF_OK;
+}
+
+// the one place the run-time (channels per lane, aggregate) picks an instantiation: f(channels per lane, pairs) as integral constants
+template <typename F>
+gf_status with_instantiation(int H, bool pairs, F &&f) {
+    using one = std::integral_constant<int, 1>;
+    using two = std::integral_constant<int, 2>;
+    if (H > 64) return pairs ? f(two{}, std::true_type{}) : f(two{}, std::false_type{});
+    return pairs ? f(one{}, std::true_type{}) : f(one{}, std::false_type{});
+}
+
 gf_status level(gf_smp *s, int l, const float *W1, const float *W2, bool forward, bool top = false, const float *Wout = nullptr) {
-    const bool two = s->cfg.nChanels > 64, pairs = s->cfg.neighbourhood == 3;
-    if (two) return pairs ? launch_level<2, true>(s, l, W1, W2, forward, top, Wout) : launch_level<2, false>(s, l, W1, W2, forward, top, Wout);
-    return pairs ? launch_level<1, true>(s, l, W1, W2, forward, top, Wout) : launch_level<1, false>(s, l, W1, W2, forward, top, Wout);
+    gf_ctx *ctx = s->ctx;
+    const int H = s->cfg.nChanels, FD = s->cfg.fdim(), nV = s->lay.level[0].nNodes;
+    gf_smp::DevLevel &d = s->lv[l];
+    const gf_smp::DevLevel *pv = l ? &s->lv[l - 1] : nullptr;
+    return with_instantiation(H, s->cfg.neighbourhood == 3, [&](auto nk, auto pairs) -> gf_status {
+        constexpr int NK = decltype(nk)::value;
+        constexpr bool PAIRS = decltype(pairs)::value;
+        if (forward)
+            return fwd_launch<NK, PAIRS>(ctx, H, FD, nV, 0, W1, W2, s->x, pv ? pv->f : nullptr, pv ? pv->nb_T : nullptr, d.nb_ptr, d.nb_idx, d.f,
+                                         d.th_A, d.th_B, d.nb_T, d.nb_Tt);
+        const gf_status st = node_launch<NK, PAIRS>(ctx, H, nV, 0, W2, d.f, d.df, top ? s->dy : nullptr, Wout, s->top_node_mol, d.th_B, d.nb_Tt,
+                                                    d.Q, d.th_node, d.nb_sA);
+        if (st != GF_OK || !l) return st;
+        return gather_launch<NK, PAIRS>(ctx, H, nV, d.nb_tptr, d.nb_tidx, d.Q, d.th_node, d.nb_sA, pv->f, pv->nb_T, pv->df);
+    });
+}
+
+// every one of the n device ints lies in [0, bound) (one blocking copy)
+gf_status check_members(gf_ctx *ctx, const char *who, const char *what, const int *idx, size_t n, int bound) {
+    std::vector<int> t(n);
+    if (n) {
+        GF_HIP_TRY(ctx, hipMemcpyAsync(t.data(), idx, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
+        GF_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    for (size_t i = 0; i < n; ++i)
+        if (t[i] < 0 || t[i] >= bound) return fail(ctx, GF_ERR_INVALID, "%s: %s[%zu] = %d outside [0, %d)", who, what, i, t[i], bound);
+    return GF_OK;
+}
+
+// A list of a stand-alone call, checked on the host (one blocking copy: these are test operators): ptr [n + 1] starts at 0 and never
+// decreases, every member lies in [0, bound).  `idx` null: ptr alone (32-bit: mol_ptr), its last entry at most `bound`.
+template <typename P>
+gf_status check_list(gf_ctx *ctx, const char *who, const char *what, const P *ptr, const int *idx, int n, int bound) {
+    std::vector<P> p((size_t)n + 1);
+    GF_HIP_TRY(ctx, hipMemcpyAsync(p.data(), ptr, sizeof(P) * p.size(), hipMemcpyDeviceToHost, ctx->stream));
+    GF_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (p[0] != 0) return fail(ctx, GF_ERR_INVALID, "%s: %s starts at %lld, not at 0", who, what, (long long)p[0]);
+    for (int i = 0; i < n; ++i)
+        if (p[i + 1] < p[i]) return fail(ctx, GF_ERR_INVALID, "%s: %s decreases at entry %d", who, what, i + 1);
+    if (!idx) {
+        if ((long long)p[n] > bound) return fail(ctx, GF_ERR_INVALID, "%s: %s ends at %lld, beyond the %d rows", who, what, (long long)p[n], bound);
+        return GF_OK;
+    }
+    if ((long long)p[n] > (1ll << 31)) return fail(ctx, GF_ERR_INVALID, "%s: %s ends at %lld: more than 2^31 members", who, what, (long long)p[n]);
+    return check_members(ctx, who, what, idx, (size_t)p[n], bound);
 }
 
 }  // namespace
@@ -406,3 +469,88 @@ gf_status smp_neighbourhood_backward(gf_smp *s, const float *params, float *grad
 }
 
 }  // namespace gf
+
+// ---- the level's kernels as stand-alone operators (include/gf_hip.h; tests/test_smp_neighbourhood_ops_gpu.py) ----
+namespace {
+
+// H, nV and the largest accepted rounds of a stand-alone call
+gf_status check_shape(gf_ctx *ctx, const char *who, int H, int nV, int rounds) {
+    if (H < 1 || H > gf::kNeighbourhoodMaxChanels) return gf::fail(ctx, GF_ERR_INVALID, "%s: %d channels (1 .. %d)", who, H, gf::kNeighbourhoodMaxChanels);
+    if (nV < 1 || rounds < 0 || rounds > 65536) return gf::fail(ctx, GF_ERR_INVALID, "%s: %d vertices, %d rounds", who, nV, rounds);
+    return GF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+gf_status gf_smp_neighbourhood_fwd_ex_f32(gf_ctx *ctx, int pairs, int H, int FD, int nV, int rounds, const float *W1, const float *x, const float *W2,
+                                          const float *hprev, const float *Tprev, const long long *ptr, const int *idx, float *h, float *n, float *A,
+                                          float *T, float *Tt) {
+    static const char *who = "gf_smp_neighbourhood_fwd_ex_f32";
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    gf_status st = check_shape(ctx, who, H, nV, rounds);
+    if (st != GF_OK) return st;
+    if (FD < 1 || !W1 || !x || !h) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
+    if (W2 && (!hprev || !ptr || !idx || !n)) return gf::fail(ctx, GF_ERR_INVALID, "%s: a level with W2 needs hprev, ptr, idx and n", who);
+    if (pairs && (!T || (W2 && (!Tprev || !A || !Tt)))) return gf::fail(ctx, GF_ERR_INVALID, "%s: the pair form needs T, and with W2 Tprev, A and Tt", who);
+    if (gf::smp_neighbourhood_lds_bytes(H, FD) > 160 * 1024)
+        return gf::fail(ctx, GF_ERR_INVALID, "%s: H = %d, F' = %d need %zu bytes of LDS (160 KiB)", who, H, FD, gf::smp_neighbourhood_lds_bytes(H, FD));
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (W2) st = gf::check_list(ctx, who, "ptr", ptr, idx, nV, nV);
+    if (st != GF_OK) return st;
+    return gf::with_instantiation(H, pairs != 0, [&](auto nk, auto pr) -> gf_status {
+        return gf::fwd_launch<decltype(nk)::value, decltype(pr)::value>(ctx, H, FD, nV, rounds, W1, W2, x, hprev, Tprev, ptr, idx, h, n, A, T, Tt);
+    });
+}
+
+gf_status gf_smp_neighbourhood_node_bwd_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, int rounds, const float *W2, const float *h, float *dh,
+                                               const float *dy, const float *Wout, const int *vmol, int nMol, const float *A, const float *Tt,
+                                               float *dn, float *gTt, float *sA) {
+    static const char *who = "gf_smp_neighbourhood_node_bwd_ex_f32";
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    gf_status st = check_shape(ctx, who, H, nV, rounds);
+    if (st != GF_OK) return st;
+    if (!h || !dh) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
+    if (dy && (!Wout || !vmol || nMol < 1)) return gf::fail(ctx, GF_ERR_INVALID, "%s: the top level needs Wout, vmol and nMol >= 1", who);
+    if (W2 && (!dn || (pairs && (!A || !Tt || !gTt || !sA)))) return gf::fail(ctx, GF_ERR_INVALID, "%s: a level with W2 needs dn, the pair form A, Tt, gTt, sA", who);
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (dy) st = gf::check_members(ctx, who, "vmol", vmol, (size_t)nV, nMol);
+    if (st != GF_OK) return st;
+    return gf::with_instantiation(H, pairs != 0, [&](auto nk, auto pr) -> gf_status {
+        return gf::node_launch<decltype(nk)::value, decltype(pr)::value>(ctx, H, nV, rounds, W2, h, dh, dy, Wout, vmol, A, Tt, dn, gTt, sA);
+    });
+}
+
+gf_status gf_smp_neighbourhood_gather_bwd_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, const long long *tptr, const int *tidx, const float *dn,
+                                                 const float *gTt, const float *sA, const float *hprev, const float *Tprev, float *dhprev) {
+    static const char *who = "gf_smp_neighbourhood_gather_bwd_ex_f32";
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    gf_status st = check_shape(ctx, who, H, nV, 0);
+    if (st != GF_OK) return st;
+    if (!tptr || !tidx || !dn || !dhprev) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
+    if (pairs && (!gTt || !sA || !hprev || !Tprev)) return gf::fail(ctx, GF_ERR_INVALID, "%s: the pair form needs gTt, sA, hprev and Tprev", who);
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = gf::check_list(ctx, who, "tptr", tptr, tidx, nV, nV);
+    if (st != GF_OK) return st;
+    return gf::with_instantiation(H, pairs != 0, [&](auto nk, auto pr) -> gf_status {
+        return gf::gather_launch<decltype(nk)::value, decltype(pr)::value>(ctx, H, nV, tptr, tidx, dn, gTt, sA, hprev, Tprev, dhprev);
+    });
+}
+
+gf_status gf_smp_neighbourhood_readout_ex_f32(gf_ctx *ctx, int H, int nV, int nMol, const float *hL, const int *mol_ptr, const float *W,
+                                              const float *target, float *g, float *yhat, float *loss, float *dy, float *dW) {
+    static const char *who = "gf_smp_neighbourhood_readout_ex_f32";
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    gf_status st = check_shape(ctx, who, H, nV, 0);
+    if (st != GF_OK) return st;
+    if (nMol < 1 || !hL || !mol_ptr || !W || !g || !yhat || !dy || !dW) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = gf::check_list<int>(ctx, who, "mol_ptr", mol_ptr, nullptr, nMol, nV);
+    if (st != GF_OK) return st;
+    GF_LAUNCH(ctx, "nbh_readout", gf::nbh_readout, dim3(nMol), dim3(64), 0, hL, mol_ptr, W, target, g, yhat, loss, dy, H);
+    GF_LAUNCH(ctx, "nbh_readout_dW", gf::nbh_readout_dW, dim3((unsigned)((H + 63) / 64)), dim3(1024), 0, dy, g, dW, H, nMol);
+    return GF_OK;
+}
+
+}  // extern "C"

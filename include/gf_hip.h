@@ -517,6 +517,34 @@ gf_status gf_smp_2d_ver5_cols_ex_f32(gf_ctx *ctx, int backward, int C, int cols,
                                      const float *sizes, const int *col_s, float *out);
 gf_status gf_smp_2d_ver5_wgrad_ex_f32(gf_ctx *ctx, int C, int rows, int cols, int nsizes, const float *dz, const float *S, const int *row_cs,
                                       const float *cz, int ldcz, const float *col, const int *col_s, const float *sizes, float *dK);
+/* The softmax neighbourhood level (gf_smp_config.neighbourhood = 1, 2, 3), its kernels as stand-alone operators: the level's own kernels
+ * and launchers on caller-supplied operands, for per-row tests (tests/test_smp_neighbourhood_ops_gpu.py).  Device pointers, fp32,
+ * asynchronous on the context's stream.  H = 1 .. 128 channels, nV vertices, pairs != 0: RisiLayer2D (form 3), else the sum.
+ * Lists are CSR: ptr long long [nV + 1] from 0, idx int members in [0, nV).  rounds = 0: the level's own vertices per workgroup;
+ * > 0: that many rounds of a workgroup's 256 / G vertex slots (G = 8, 16, 32, 64: the lane group of H).
+ *   fwd:      h[v] = softmax(W1 x[v] + W2 n[v]), W1 [H][FD], x [nV][FD], W2 [H][H] (NULL: level 0, no aggregate, n / A / Tt untouched);
+ *             n[v] = sum_u hprev[u] over ptr / idx, or with pairs A Tt - sum_u hprev[u] Tprev[u], A = sum_u hprev[u], Tt = sum_u Tprev[u];
+ *             pairs also stores A [nV][H], Tt [nV] and T[v] = sum_k h[v][k] (T at level 0 too).
+ *   node_bwd: dh[v] <- dz = d h (1 - h) in place, d = dh[v], or dy[vmol[v]] Wout when dy is not NULL (the top level; vmol in [0, nMol));
+ *             with W2: dn[v] = W2^T dz, and with pairs gTt[v] = dn[v] Tt[v], sA[v] = <dn[v], A[v]>.  W2 NULL: level 0, dz alone.
+ *   gather_bwd: dhprev[w] = sum of dn[v] over the consumers v of w (the transposed list tptr / tidx); pairs:
+ *             sum_v gTt[v] - Tprev[w] sum_v dn[v] + sum_v sA[v] - <sum_v dn[v], hprev[w]>.
+ *   readout:  g[m] = sum of hL[v] over mol_ptr[m] <= v < mol_ptr[m + 1] (int [nMol + 1], within the nV rows), yhat = <W, g>,
+ *             dy = yhat - target (target NULL: 0), loss = 0.5 dy^2 (NULL: not stored); then dW[c] += sum_m dy[m] g[m][c].
+ * GF_ERR_INVALID before anything is launched: H outside 1 .. 128, nV / nMol / FD < 1, rounds < 0, a missing operand of the chosen
+ * form, more than 160 KiB of LDS for (H, FD), and -- checked on the host, one blocking copy of the tables per call -- a list that does
+ * not start at 0 or decreases, a member outside [0, nV), vmol outside [0, nMol), a mol_ptr that decreases or leaves the nV rows.  The
+ * context stays usable after a refusal. */
+gf_status gf_smp_neighbourhood_fwd_ex_f32(gf_ctx *ctx, int pairs, int H, int FD, int nV, int rounds, const float *W1, const float *x, const float *W2,
+                                          const float *hprev, const float *Tprev, const long long *ptr, const int *idx, float *h, float *n, float *A,
+                                          float *T, float *Tt);
+gf_status gf_smp_neighbourhood_node_bwd_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, int rounds, const float *W2, const float *h, float *dh,
+                                               const float *dy, const float *Wout, const int *vmol, int nMol, const float *A, const float *Tt,
+                                               float *dn, float *gTt, float *sA);
+gf_status gf_smp_neighbourhood_gather_bwd_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, const long long *tptr, const int *tidx, const float *dn,
+                                                 const float *gTt, const float *sA, const float *hprev, const float *Tprev, float *dhprev);
+gf_status gf_smp_neighbourhood_readout_ex_f32(gf_ctx *ctx, int H, int nV, int nMol, const float *hL, const int *mol_ptr, const float *W,
+                                              const float *target, float *g, float *yhat, float *loss, float *dy, float *dW);
 /* Device memory of the handle's buffer pool: bytes held by the current batch, and bytes the pool keeps in total (idle
  * blocks included).  Sizing aid for batch selection (GraphFlow has no counterpart: its tensors live in host `new[]`). */
 gf_status gf_smp_device_bytes(const gf_smp *smp, size_t *in_use, size_t *reserved);

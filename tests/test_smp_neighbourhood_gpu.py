@@ -21,7 +21,8 @@ torch = pytest.importorskip("torch")
 
 FORMS = {1: "fingerprint", 2: "gcn_1d", 3: "gcn_2d"}
 PACK_L, PACK_R, PACK_MAXV = 3, 2, 12   # (form 2 then walks two lists: radius 1 at level 1, 2 at levels 2 and 3)
-WIDTHS = (5, 6, 8, 31, 32, 33, 64, 65, 128)   # lane groups of 8 / 16 / 32 / 64, two channels per lane above 64, the largest LDS image
+# lane groups of 8 / 16 / 32 / 64 with both edges of the 16-lane group, two channels per lane above 64, the largest LDS image
+WIDTHS = (5, 6, 8, 9, 16, 17, 31, 32, 33, 64, 65, 128)
 
 
 def golden():
@@ -123,6 +124,54 @@ def test_batch_across_the_widths(gf, form, H, FD):
     assert rel_err(out[1], np.array([r["loss"] for r in res])) <= TOL
     assert worst_feat <= TOL
     assert e[0] <= TOL, e
+
+
+@pytest.mark.parametrize("form,H,reps", [(1, 64, 7), (3, 64, 7), (2, 20, 13)])
+def test_batch_the_level_runs_in_two_rounds(gf, form, H, reps):
+    """The packing batch seven (thirteen) times over: 2,275 vertices at H = 64 (4,225 at H = 20), where a workgroup of nbh_level_fwd and
+    nbh_node_bwd takes two rounds of its slots and the TN products of dW1_l / dW2_l split their K (the traced launch table shows the
+    fold).  The reference runs the 70 distinct (molecule, target) pairs once: every copy has its molecule's prediction, loss and final
+    feature, and the batch gradient is `reps` times the 70's."""
+    mols, tg, params, _, (res, rg) = packed_case(form, H, 4)
+    G = 64 if H > 32 else 32
+    assert sum(len(a) for a, _ in mols) * reps // ((256 // G) * 256) >= 2
+    traced = {}
+
+    def inspect(net):
+        p, t, grads = dev(params), dev(np.tile(tg, reps)), torch.empty(net.n_params, device="cuda")
+        traced.update(kit.traced_counts(net, lambda: (net.forward(p, t), net.backward(p, grads))))
+
+    out = run_packed(form, H, 4)(mols * reps, np.tile(tg, reps), params, inspect=inspect)
+    pick = lambda k: np.array([res[m % 70][k] for m in range(70 * reps)])   # noqa: E731
+    e = blockwise(out[3], reps * rg, nref.blocks(H, 4, PACK_L))
+    worst_feat = max(rel_err(out[2][m], res[m % 70]["final_feature"]) for m in range(70 * reps))
+    print(form, H, reps, rel_err(out[0], pick("predict")), rel_err(out[1], pick("loss")), worst_feat, e, traced)
+    assert rel_err(out[0], pick("predict")) <= TOL
+    assert rel_err(out[1], pick("loss")) <= TOL
+    assert worst_feat <= TOL
+    assert e[0] <= TOL, e
+    assert traced.get("splitk_reduce", 0) >= 1, traced
+
+
+@pytest.mark.parametrize("form,H", [(3, 65), (1, 20)])
+def test_accumulate_and_a_second_sweep(gf, form, H):
+    """after one forward a second backward gives the bits of the first (every level keeps what a second sweep needs), and
+    backward(accumulate=True) onto the first result gives twice the first result, which is exact in fp32"""
+    mols, tg, D = pack_shape(form, 4)
+    net = net_of(form, PACK_L, H, 4, D, PACK_MAXV, PACK_R)
+    net.prepare(mols)
+    p = dev(random_params(form, H, 4, PACK_L, np.random.default_rng(H), 0.5))
+    net.forward(p, dev(tg))
+    first, again = torch.full((net.n_params,), float("nan"), device="cuda"), torch.full((net.n_params,), float("nan"), device="cuda")
+    net.backward(p, first)
+    net.backward(p, again)
+    twice = first.clone()
+    net.backward(p, twice, accumulate=True)
+    net.close()
+    a, b, c = (t.cpu().numpy() for t in (first, again, twice))
+    assert np.isfinite(a).all() and np.abs(a).max() > 0
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    assert np.array_equal(c, 2 * a)
 
 
 @pytest.mark.parametrize("form", [1, 3])
