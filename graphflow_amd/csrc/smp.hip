@@ -625,114 +625,26 @@ void gf::smp_derive_plan(gf_smp *s, bool allow_embed) {
 
 // pad_channels = false: compute at the configuration's own channel counts (the towers of a model with RisiContraction_18_dropout --
 // SMP_sigma_pairgraphs -- whose levels run op by op, where a padded width only costs)
-gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channels, gf_smp **out, int min_pad, int nClass, double decay) {
+gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, const gfsmp::ConfigEntry &entry, bool pad_channels, gf_smp **out, int min_pad) {
     if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
-    if (!cfg || !out) return fail(ctx, GF_ERR_INVALID, "gf_smp_create: null argument");
-    if (cfg->neighbourhood) {   // NeuralFingerprint, GCN_1D, GCN_2D (smp_level_neighbourhood.hip): nLevels = 0 is a model; no padding, one plan
-        if (!gf::smp_neighbourhood_config_ok(cfg))
-            return fail(ctx, GF_ERR_INVALID, "gf_smp_create: neighbourhood = %d (1: NeuralFingerprint, 2: GCN_1D, 3: GCN_2D) needs first_order = steerable_2d = "
-                                             "unrestricted = physics = nContractions = custom_matmul = 0, max_receptive_field (%d) == max_nVertices (%d) <= "
-                                             "4096, nLevels >= 0, nDepth = 0 in form 1, max_Radius (%d) >= 0 in form 2, nChanels (%d) <= %d and W1_l, W2_l "
-                                             "within 160 KiB", cfg->neighbourhood, cfg->max_receptive_field, cfg->max_nVertices, cfg->max_Radius,
-                        cfg->nChanels, gf::kNeighbourhoodMaxChanels);
-        gfsmp::table_alloc = gf::pinned_table_alloc;
-        gfsmp::table_free = gf::pinned_table_free;
-        gf_smp *s = new gf_smp();
-        s->ctx = ctx;
-        gf::smp_neighbourhood_config(cfg, &s->cfg);
-        s->ucfg = s->cfg;
-        s->grad_allreduce = 0;   // (no data-parallel exchange: gf_smp_set_grad_allreduce(.., 1) is refused)
-        *out = s;
-        return GF_OK;
-    }
-    if (cfg->nLevels < 1 || cfg->nChanels < 1 || cfg->nFeatures < 1 || cfg->nDepth < 0 || cfg->max_receptive_field < 1)
-        return fail(ctx, GF_ERR_INVALID, "gf_smp_create: bad configuration");
+    gfsmp::Config c;
+    char why[640];
+    const gf_status verdict = gfsmp::resolve_config(out ? cfg : nullptr, entry, &c, why, sizeof why);   // (a null `out` is a null argument)
+    if (verdict != GF_OK) return fail(ctx, verdict, "%s", why);
     gfsmp::table_alloc = gf::pinned_table_alloc;   // (before the first table is built; idempotent)
     gfsmp::table_free = gf::pinned_table_free;
     gf_smp *s = new gf_smp();
     s->ctx = ctx;
-    s->cfg = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, cfg->has_WL_ordering};
-    s->cfg.nContractions = cfg->nContractions ? cfg->nContractions : 18;
-    s->cfg.custom_matmul = cfg->custom_matmul ? 1 : 0;
-    s->cfg.physics = cfg->physics ? 1 : 0;
-    s->cfg.nClass = nClass;
-    if (cfg->unrestricted) {   // Unrestricted_SMP_1D, _1D_ver2, _2D (smp_level_unrestricted.hip)
-        if (!gf::smp_unrestricted_config_ok(cfg)) {
-            delete s;
-            return fail(ctx, GF_ERR_INVALID, "gf_smp_create: unrestricted = %d (1: Unrestricted_SMP_1D, 2: _1D_ver2, 3: _2D) needs first_order = "
-                                             "steerable_2d = 0, max_receptive_field (%d) == max_nVertices (%d) <= 4096, nContractions = custom_matmul = "
-                                             "physics = 0 and a parameter count that fits an int", cfg->unrestricted, cfg->max_receptive_field,
-                        cfg->max_nVertices);
-        }
-        if (nClass) {
-            delete s;
-            return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: the Unrestricted_SMP_* models have no `_classification` class");
-        }
-        gf::smp_unrestricted_config(cfg, &s->cfg);
-        s->grad_allreduce = 0;   // (no data-parallel exchange: gf_smp_set_grad_allreduce(.., 1) is refused)
-    } else if (cfg->steerable_2d) {   // SMP_2D, SMP_2D_ver4 (smp_level_2d.hip; a classifier read-out is allowed), SMP_2D_ver5 (smp_level_2d_ver5.hip)
-        if (!gf::smp_2d_config_ok(cfg)) {
-            delete s;
-            return fail(ctx, GF_ERR_INVALID, "gf_smp_create: steerable_2d = %d (1: SMP_2D, 2: SMP_2D_ver4, 5: SMP_2D_ver5) needs first_order = 0, "
-                                             "max_receptive_field (%d) == max_nVertices (%d) <= 4096, nContractions = custom_matmul = physics = 0 and, "
-                                             "for 5, nChanels (%d) <= 128", cfg->steerable_2d, cfg->max_receptive_field, cfg->max_nVertices,
-                        cfg->nChanels);
-        }
-        if (nClass && cfg->steerable_2d == 5) {
-            delete s;
-            return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: SMP_2D_ver5 has no `_classification` class");
-        }
-        s->cfg.steerable_2d = cfg->steerable_2d;
-        s->cfg.max_nVertices = cfg->max_nVertices;
-        s->cfg.nContractions = 0;
-        s->grad_allreduce = 0;   // (no data-parallel exchange: gf_smp_set_grad_allreduce(.., 1) is refused)
-    } else if (cfg->first_order >= 2) {   // SMP_1D, SMP_1D_ver2, SMP_1D_ver3 (smp_level_1d.hip); a classifier read-out is allowed
-        if (!gf::smp_1d_config_ok(cfg)) {
-            delete s;
-            return fail(ctx, GF_ERR_INVALID, "gf_smp_create: first_order = %d (2: SMP_1D, 3: SMP_1D_ver2, 4: SMP_1D_ver3) needs max_receptive_field "
-                                             "(%d) == max_nVertices (%d) and nContractions = custom_matmul = physics = 0", cfg->first_order,
-                        cfg->max_receptive_field, cfg->max_nVertices);
-        }
-        s->cfg.first_order = cfg->first_order;
-        s->cfg.max_nVertices = cfg->max_nVertices;
-        s->cfg.nContractions = 2;
-        s->grad_allreduce = 0;
-    } else if (cfg->first_order) {   // SMP_theta: K_l = [2 C'][C], per-size blocks of max_nVertices entries (gfsmp::Config::first_order)
-        if (nClass) {
-            delete s;
-            return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: a first-order model (first_order = 1) has no classifier read-out");
-        }
-        if (cfg->nContractions || cfg->custom_matmul || cfg->max_nVertices < cfg->max_receptive_field) {
-            delete s;
-            return fail(ctx, GF_ERR_INVALID, "gf_smp_create: first_order = 1 needs nContractions = custom_matmul = 0 and max_nVertices (%d) >= "
-                                             "max_receptive_field (%d)", cfg->max_nVertices, cfg->max_receptive_field);
-        }
-        s->cfg.first_order = 1;
-        s->cfg.max_nVertices = cfg->max_nVertices;
-        s->cfg.nContractions = 2;
-        if (cfg->physics) s->cfg.decay = decay;   // (a CCN_1D tower, gf_smp_model_create only)
-        s->grad_allreduce = 0;   // (no data-parallel exchange: gf_smp_set_grad_allreduce(.., 1) is refused)
-    }
-    s->ucfg = s->cfg;
+    s->ucfg = c;
+    if (c.per_size() || c.neighbourhood) s->grad_allreduce = 0;   // (no data-parallel exchange: gf_smp_set_grad_allreduce(.., 1) is refused)
     s->req_pad_channels = pad_channels;
     s->req_min_pad = min_pad;
-    gf::smp_derive_plan(s, /*allow_embed=*/true);
-    if (s->cfg.nContractions == 4 && s->cfg.custom_matmul) {   // SMP_gamma: Reshape2D + MatMul on [4 C][C]
-        delete s;
-        return fail(ctx, GF_ERR_INVALID, "gf_smp_create: nContractions = 4 (SMP_gamma) applies K_l [4 C][C] by Reshape2D + MatMul: set custom_matmul = 0");
+    if (c.neighbourhood) {   // (no padding, one plan, none of the fused level's switches)
+        s->cfg = c;
+    } else {
+        gf::smp_derive_plan(s, /*allow_embed=*/true);
+        s->bwd_gather = gf::env_is("GF_SMP_BWD_GATHER", '0') ? 0 : 1;   // 0: keep the two-kernel tables-backward + consumer gather
     }
-    // (a tower of SMP_gamma_physics / SMP_gamma_pairgraphs: RisiContraction_4, K_l [4 C_{l-1}][C_l], computed at its own halving widths --
-    //  smp_derive_plan pads only `_18` towers; the gamma tower level is smp_level_gamma.hip's rectangular one)
-    if (s->cfg.physics && (s->cfg.nDepth != 0 || (s->cfg.nContractions != 18 && s->cfg.nContractions != 4 && !s->cfg.first_order) || s->cfg.custom_matmul)) {
-        delete s;
-        return fail(ctx, GF_ERR_INVALID, "gf_smp_create: a physics tower has nDepth 0 (raw features), RisiContraction_18 or _4 and [nK C', C] weights");
-    }
-    if (!s->cfg.per_size() && s->cfg.nContractions != 4 && s->cfg.nContractions != 10 && s->cfg.nContractions != 18 && s->cfg.nContractions != 50) {
-        const int bad = cfg->nContractions;
-        delete s;
-        return fail(ctx, GF_ERR_INVALID, "gf_smp_create: nContractions = %d (expected 4, 10, 18 or 50)", bad);
-    }
-    s->bwd_gather = gf::env_is("GF_SMP_BWD_GATHER", '0') ? 0 : 1;   // 0: keep the two-kernel tables-backward + consumer gather
     *out = s;
     return GF_OK;
 }
@@ -759,15 +671,8 @@ gf_status gf::smp_switch_plan(gf_smp *s, bool embed) {
 
 extern "C" {
 
-// (a gamma physics tower is built by gf_smp_model_create only: the single-model handle keeps refusing it)
 gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out) {
-    if (cfg && cfg->physics && cfg->first_order == 1)
-        return fail(ctx, GF_ERR_INVALID, "gf_smp_create: first_order = 1 has no single-handle physics tower: set physics = 0, or build SMP_theta_physics / "
-                                         "SMP_theta_pairgraphs with gf_smp_model_create (first_order = 1)");
-    if (cfg && cfg->physics && cfg->nContractions == 4)
-        return fail(ctx, GF_ERR_INVALID, "gf_smp_create: nContractions = 4 (SMP_gamma) has no single-handle physics tower: set physics = 0, or build "
-                                         "SMP_gamma_physics / SMP_gamma_pairgraphs with gf_smp_model_create (nContractions = 4)");
-    return gf::smp_create(ctx, cfg, /*pad_channels=*/true, out);
+    return gf::smp_create(ctx, cfg, gfsmp::kHandleEntry, /*pad_channels=*/true, out);
 }
 
 gf_status gf_smp_destroy(gf_smp *s) {
@@ -792,17 +697,7 @@ size_t gf_smp_param_count(const gf_smp *s) { return s ? gf::param_count(s->ucfg)
 
 // The `_classification` models (smp_readout_classes.hip): the levels of gf_smp_create, W [nClass][C] read out by MatVecMul + LogLoss
 gf_status gf_smp_create_classifier(gf_ctx *ctx, const gf_smp_config *cfg, int nClass, gf_smp **out) {
-    if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
-    if (!cfg || !out) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: null argument");
-    if (cfg->first_order == 1)   // (SMP_theta has no `_classification` class; first_order = 2, 3, 4 do: SMP_1D*_classification)
-        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: a first-order model (first_order = 1) has no classifier read-out");
-    if (cfg->unrestricted)   // (refused before the configuration is looked at: there is no class to hold the handle to)
-        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: the Unrestricted_SMP_* models have no `_classification` class");
-    if (cfg->neighbourhood)   // (likewise)
-        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: NeuralFingerprint / GCN_1D / GCN_2D have no `_classification` class");
-    if (cfg->physics) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: a physics tower has no read-out of its own (physics = 0)");
-    if (nClass < 2) return fail(ctx, GF_ERR_INVALID, "gf_smp_create_classifier: nClass = %d (at least 2)", nClass);
-    return gf::smp_create(ctx, cfg, /*pad_channels=*/true, out, /*min_pad=*/0, nClass);
+    return gf::smp_create(ctx, cfg, {gfsmp::ConfigEntry::Classifier, nClass, 0.0}, /*pad_channels=*/true, out);
 }
 
 int gf_smp_classes(const gf_smp *s) { return s ? s->ucfg.nClass : 0; }

@@ -1,0 +1,155 @@
+// smp_config.cpp -- resolve_config: see smp_config.h.  The checks run in the order the create functions have always made them; the
+// first refusal wins.  Every product and shift of the caller's fields is guarded or widened first: the struct may hold anything.
+#include <cstdio>
+
+#include "smp_config.h"
+
+namespace gfsmp {
+namespace {
+
+constexpr int kMaxFieldVertices = 4096;   // gf_smp_prepare takes no larger molecule
+constexpr long long kMaxInt = 0x7fffffffll;
+
+bool no_cap(const gf_smp_config *cfg) { return cfg->max_nVertices == cfg->max_receptive_field; }
+bool plain_levels(const gf_smp_config *cfg) { return !cfg->nContractions && !cfg->custom_matmul && !cfg->physics; }   // no contraction family / custom product / tower
+// the concatenating forms: C_l = C << l must stay a sane int
+bool doubling_fits(const gf_smp_config *cfg) { return cfg->nLevels <= 16 && ((long long)cfg->nChanels << cfg->nLevels) <= (1 << 20); }
+
+// first_order = 2, 3, 4 (SMP_1D, SMP_1D_ver2, SMP_1D_ver3): no cap, plain levels, channel counts and multiplicities that fit an int
+bool rule_1d(const gf_smp_config *cfg) {
+    if (cfg->first_order < 2 || cfg->first_order > 4 || !plain_levels(cfg) || !no_cap(cfg)) return false;
+    if (cfg->first_order == 2) return cfg->max_nVertices <= 2000;   // (th_weight = j (j + 1) (j + 2) / 6, j <= max_nVertices)
+    return doubling_fits(cfg);
+}
+// steerable_2d = 1, 2, 5 (SMP_2D, SMP_2D_ver4, SMP_2D_ver5; there is no 3 or 4): first_order = 0, no cap, plain levels, a multiplicity
+// j (j + 1) / 2 (j <= max_nVertices) and channel counts that fit an int; 5: K1 [C][C] fits in LDS
+bool rule_2d(const gf_smp_config *cfg) {
+    if ((cfg->steerable_2d != 1 && cfg->steerable_2d != 2 && cfg->steerable_2d != 5) || cfg->first_order) return false;
+    if (cfg->steerable_2d == 5 && cfg->nChanels > 128) return false;
+    if (!plain_levels(cfg) || !no_cap(cfg) || cfg->max_nVertices > kMaxFieldVertices) return false;
+    return cfg->steerable_2d != 2 || doubling_fits(cfg);
+}
+// unrestricted = 1, 2, 3 (Unrestricted_SMP_1D, _1D_ver2, _2D): first_order = steerable_2d = 0, no cap, plain levels, channel counts and a
+// parameter count that fit an int
+bool rule_unrestricted(const gf_smp_config *cfg) {
+    if (cfg->unrestricted < 1 || cfg->unrestricted > 3 || cfg->first_order || cfg->steerable_2d) return false;
+    if (!plain_levels(cfg) || !no_cap(cfg) || cfg->max_nVertices > kMaxFieldVertices || !doubling_fits(cfg)) return false;
+    const long long FD = (long long)cfg->nFeatures * ((long long)cfg->nDepth + 1);
+    if (FD > kMaxInt) return false;   // (H alone is too large; keeps the sum below inside a long long)
+    const long long m = cfg->max_nVertices, sq = m * (m + 1) * (2 * m + 1) / 6;   // sum of s^2
+    long long n = (long long)cfg->nChanels * FD, Cl = cfg->nChanels;
+    for (int l = 1; l <= cfg->nLevels; ++l) {
+        const long long Cp = Cl;
+        if (cfg->unrestricted == 2) Cl *= 2;
+        n += (cfg->unrestricted == 3 ? Cp : cfg->unrestricted) * sq + m * Cl + (cfg->unrestricted == 3 ? Cp : 0);
+    }
+    return n + Cl <= kMaxInt;
+}
+// neighbourhood = 1, 2, 3 (NeuralFingerprint, GCN_1D, GCN_2D): no other form, no cap, nLevels >= 0, what the level's kernels take
+bool rule_neighbourhood(const gf_smp_config *cfg) {
+    if (cfg->neighbourhood < 1 || cfg->neighbourhood > 3) return false;
+    if (cfg->first_order || cfg->steerable_2d || cfg->unrestricted || !plain_levels(cfg)) return false;
+    if (cfg->nLevels < 0 || cfg->nLevels > 64 || cfg->nChanels < 1 || cfg->nFeatures < 1 || cfg->nDepth < 0 || cfg->max_nVertices < 1) return false;
+    if (!no_cap(cfg) || cfg->max_nVertices > kMaxFieldVertices) return false;
+    if (cfg->neighbourhood == 1 && cfg->nDepth != 0) return false;
+    if (cfg->neighbourhood == 2 && cfg->max_Radius < 0) return false;
+    if (cfg->nChanels > gf::kNeighbourhoodMaxChanels) return false;
+    const long long FD = (long long)cfg->nFeatures * ((long long)cfg->nDepth + 1);
+    return FD <= 65536 && gf::smp_neighbourhood_lds_bytes(cfg->nChanels, (int)FD) <= 160 * 1024;
+}
+
+}  // namespace
+
+#define GF_REFUSE(status, ...) return (std::snprintf(why, nwhy, __VA_ARGS__), (status))
+
+gf_status resolve_config(const gf_smp_config *cfg, const ConfigEntry &entry, Config *out, char *why, size_t nwhy) {
+    const int nClass = entry.kind == ConfigEntry::Classifier ? entry.nClass : 0;
+    // ---- what the entry itself refuses ----
+    if (entry.kind == ConfigEntry::Handle && cfg && cfg->physics) {   // (such towers are built by gf_smp_model_create only)
+        if (cfg->first_order == 1)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: first_order = 1 has no single-handle physics tower: set physics = 0, or build SMP_theta_physics / "
+                                      "SMP_theta_pairgraphs with gf_smp_model_create (first_order = 1)");
+        if (cfg->nContractions == 4)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: nContractions = 4 (SMP_gamma) has no single-handle physics tower: set physics = 0, or build "
+                                      "SMP_gamma_physics / SMP_gamma_pairgraphs with gf_smp_model_create (nContractions = 4)");
+    }
+    if (!cfg) GF_REFUSE(GF_ERR_INVALID, "%s: null argument", entry.kind == ConfigEntry::Classifier ? "gf_smp_create_classifier" : "gf_smp_create");
+    if (entry.kind == ConfigEntry::Classifier) {   // (the first three before the configuration is looked at: there is no class to hold the handle to)
+        if (cfg->first_order == 1)   // (SMP_theta has no `_classification` class; first_order = 2, 3, 4 do: SMP_1D*_classification)
+            GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: a first-order model (first_order = 1) has no classifier read-out");
+        if (cfg->unrestricted) GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: the Unrestricted_SMP_* models have no `_classification` class");
+        if (cfg->neighbourhood)
+            GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: NeuralFingerprint / GCN_1D / GCN_2D have no `_classification` class");
+        if (cfg->physics) GF_REFUSE(GF_ERR_INVALID, "gf_smp_create_classifier: a physics tower has no read-out of its own (physics = 0)");
+        if (nClass < 2) GF_REFUSE(GF_ERR_INVALID, "gf_smp_create_classifier: nClass = %d (at least 2)", nClass);
+    }
+    // ---- the configuration, family by family ----
+    if (cfg->neighbourhood) {   // NeuralFingerprint, GCN_1D, GCN_2D (smp_level_neighbourhood.hip): nLevels = 0 is a model
+        if (!rule_neighbourhood(cfg))
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: neighbourhood = %d (1: NeuralFingerprint, 2: GCN_1D, 3: GCN_2D) needs first_order = steerable_2d = "
+                                      "unrestricted = physics = nContractions = custom_matmul = 0, max_receptive_field (%d) == max_nVertices (%d) <= "
+                                      "4096, nLevels >= 0, nDepth = 0 in form 1, max_Radius (%d) >= 0 in form 2, nChanels (%d) <= %d and W1_l, W2_l "
+                                      "within 160 KiB", cfg->neighbourhood, cfg->max_receptive_field, cfg->max_nVertices, cfg->max_Radius, cfg->nChanels,
+                      gf::kNeighbourhoodMaxChanels);
+        Config c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, 0};
+        c.nContractions = 0;
+        c.max_nVertices = cfg->max_nVertices;
+        c.neighbourhood = cfg->neighbourhood;
+        c.max_Radius = cfg->neighbourhood == 2 ? cfg->max_Radius : 0;   // (form 3 stores it and never reads it; form 1 has none)
+        *out = c;
+        return GF_OK;
+    }
+    if (cfg->nLevels < 1 || cfg->nChanels < 1 || cfg->nFeatures < 1 || cfg->nDepth < 0 || cfg->max_receptive_field < 1)
+        GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: bad configuration");
+    Config c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, cfg->has_WL_ordering};
+    c.nContractions = cfg->nContractions ? cfg->nContractions : 18;
+    c.custom_matmul = cfg->custom_matmul ? 1 : 0;
+    c.physics = cfg->physics ? 1 : 0;
+    c.nClass = nClass;
+    c.max_nVertices = cfg->first_order || cfg->steerable_2d || cfg->unrestricted ? cfg->max_nVertices : 0;
+    if (cfg->unrestricted) {   // Unrestricted_SMP_1D, _1D_ver2, _2D (smp_level_unrestricted.hip)
+        if (!rule_unrestricted(cfg))
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: unrestricted = %d (1: Unrestricted_SMP_1D, 2: _1D_ver2, 3: _2D) needs first_order = "
+                                      "steerable_2d = 0, max_receptive_field (%d) == max_nVertices (%d) <= 4096, nContractions = custom_matmul = "
+                                      "physics = 0 and a parameter count that fits an int", cfg->unrestricted, cfg->max_receptive_field, cfg->max_nVertices);
+        // the handle also carries the restricted sibling whose rows, tables and read-out the form sits on (Config::unrestricted)
+        c.unrestricted = cfg->unrestricted;
+        c.first_order = cfg->unrestricted == 1 ? 2 : cfg->unrestricted == 2 ? 3 : 0;
+        c.steerable_2d = cfg->unrestricted == 3 ? 1 : 0;
+        c.nContractions = c.first_order ? 2 : 0;
+    } else if (cfg->steerable_2d) {   // SMP_2D, SMP_2D_ver4 (smp_level_2d.hip; a classifier read-out is allowed), SMP_2D_ver5 (smp_level_2d_ver5.hip)
+        if (!rule_2d(cfg))
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: steerable_2d = %d (1: SMP_2D, 2: SMP_2D_ver4, 5: SMP_2D_ver5) needs first_order = 0, "
+                                      "max_receptive_field (%d) == max_nVertices (%d) <= 4096, nContractions = custom_matmul = physics = 0 and, "
+                                      "for 5, nChanels (%d) <= 128", cfg->steerable_2d, cfg->max_receptive_field, cfg->max_nVertices, cfg->nChanels);
+        if (nClass && cfg->steerable_2d == 5) GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: SMP_2D_ver5 has no `_classification` class");
+        c.steerable_2d = cfg->steerable_2d;
+        c.nContractions = 0;
+    } else if (cfg->first_order >= 2) {   // SMP_1D, SMP_1D_ver2, SMP_1D_ver3 (smp_level_1d.hip); a classifier read-out is allowed
+        if (!rule_1d(cfg))
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: first_order = %d (2: SMP_1D, 3: SMP_1D_ver2, 4: SMP_1D_ver3) needs max_receptive_field "
+                                      "(%d) == max_nVertices (%d) and nContractions = custom_matmul = physics = 0", cfg->first_order,
+                      cfg->max_receptive_field, cfg->max_nVertices);
+        c.first_order = cfg->first_order;
+        c.nContractions = 2;
+    } else if (cfg->first_order) {   // SMP_theta: K_l = [2 C'][C], per-size blocks of max_nVertices entries (Config::first_order)
+        if (cfg->nContractions || cfg->custom_matmul || cfg->max_nVertices < cfg->max_receptive_field)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: first_order = 1 needs nContractions = custom_matmul = 0 and max_nVertices (%d) >= "
+                                      "max_receptive_field (%d)", cfg->max_nVertices, cfg->max_receptive_field);
+        c.first_order = 1;
+        c.nContractions = 2;
+        if (cfg->physics && entry.kind == ConfigEntry::Tower) c.decay = entry.decay;   // (a CCN_1D tower)
+    }
+    if (c.nContractions == 4 && c.custom_matmul)   // SMP_gamma: Reshape2D + MatMul on [4 C][C]
+        GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: nContractions = 4 (SMP_gamma) applies K_l [4 C][C] by Reshape2D + MatMul: set custom_matmul = 0");
+    // (a tower of SMP_gamma_physics / SMP_gamma_pairgraphs: RisiContraction_4, K_l [4 C_{l-1}][C_l], computed at its own halving widths)
+    if (c.physics && (c.nDepth != 0 || (c.nContractions != 18 && c.nContractions != 4 && !c.first_order) || c.custom_matmul))
+        GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: a physics tower has nDepth 0 (raw features), RisiContraction_18 or _4 and [nK C', C] weights");
+    if (!c.per_size() && c.nContractions != 4 && c.nContractions != 10 && c.nContractions != 18 && c.nContractions != 50)
+        GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: nContractions = %d (expected 4, 10, 18 or 50)", cfg->nContractions);
+    *out = c;
+    return GF_OK;
+}
+#undef GF_REFUSE
+
+}  // namespace gfsmp

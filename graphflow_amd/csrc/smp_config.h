@@ -1,0 +1,35 @@
+// smp_config.h -- the one place that decides which gf_smp_config a handle is built from, and what gfsmp::Config it becomes.
+// Pure host C++ (smp_config.cpp, built beside smp_prep.cpp): gf_smp_create, gf_smp_create_classifier, the towers of gf_smp_model_create,
+// the host-only gf_smp_*config_param_count / *_uniform_init_host and gf_smp_prepare_molecule_host all ask here, so they cannot disagree.
+// A new model family edits two places: resolve_config below and gfsmp::Config::level_blocks (smp_prep.h).
+#ifndef GF_SMP_CONFIG_H_INCLUDED
+#define GF_SMP_CONFIG_H_INCLUDED
+
+#include "../../include/gf_hip.h"
+#include "smp_prep.h"
+
+namespace gf {
+// the neighbourhood level's kernels (smp_level_neighbourhood.hip) and the configurations they take: at most kNeighbourhoodMaxChanels
+// channels, the forward level's LDS images within 160 KiB
+constexpr int kNeighbourhoodMaxChanels = 128;
+// the lanes that share one vertex in the level's kernels: the power of two at or above H, at least 8, at most a wave
+inline int smp_neighbourhood_group_width(int H) { return H > 32 ? 64 : H > 16 ? 32 : H > 8 ? 16 : 8; }
+// LDS of the forward level: W1_l^T [F'][H | 1] and W2_l^T [H][H | 1] (odd row strides), one vector of H floats per vertex slot of 256 lanes
+inline size_t smp_neighbourhood_lds_bytes(int H, int FD) {
+    return sizeof(float) * ((size_t)(FD + H) * (size_t)(H | 1) + (size_t)(256 / smp_neighbourhood_group_width(H)) * H);
+}
+}  // namespace gf
+
+namespace gfsmp {
+// who asks: the three ways a handle comes to be
+struct ConfigEntry {
+    enum Kind { Handle, Classifier, Tower } kind;   // gf_smp_create, gf_smp_create_classifier, a tower of gf_smp_model_create
+    int nClass;                                     // Classifier: rows of W
+    double decay;                                   // Tower: > 0 = CCN_1D's width rule (Config::decay)
+};
+constexpr ConfigEntry kHandleEntry = {ConfigEntry::Handle, 0, 0.0};
+// The caller's configuration as the Config in the caller's layout (gf_smp::ucfg), or the refusal: GF_ERR_INVALID / GF_ERR_UNSUPPORTED and,
+// in why, the message gf_last_error gives.  Touches no device and allocates nothing.
+gf_status resolve_config(const gf_smp_config *cfg, const ConfigEntry &entry, Config *out, char *why, size_t nwhy);
+}  // namespace gfsmp
+#endif

@@ -1,12 +1,14 @@
 // smp_internal.h -- state of one gf_smp handle and what its translation units share: smp.hip (create / plan, the forward and reverse
 // sweeps, op-by-op levels), smp_prepare.hip (buffer pool, device-built tables, gf_smp_prepare), smp_pad.hip (channel padding, the ver6 / ver7
 // embedding), smp_optim.hip (host-pointer mode, optimisers, checkpoints), smp_fused.hip + smp_level_*.hip (fused levels), smp_model.hip.
+// Which configurations become a handle is smp_config.h's business, the parameter layout smp_prep.h's (gfsmp::Config::level_blocks).
 #ifndef GF_SMP_INTERNAL_H_INCLUDED
 #define GF_SMP_INTERNAL_H_INCLUDED
 
 #include <vector>
 
 #include "gf_internal.h"
+#include "smp_config.h"
 #include "smp_prep.h"
 
 namespace gf {
@@ -106,77 +108,10 @@ gf_status smp_wgrad_fp32_c64(gf_ctx *ctx, const float *T, const float *dO, const
 
 
 namespace gf {
-// min_pad: the smallest padded width the handle may compute at (32 for the towers of a slice-dropout model)
-// decay > 0: a first_order = 1 physics tower of CCN_1D (gfsmp::Config::decay)
-gf_status smp_create(gf_ctx *ctx, const gf_smp_config *cfg, bool pad_channels, gf_smp **out, int min_pad = 0, int nClass = 0,
-                     double decay = 0.0);   // gf_smp_create = (.., true, ..)
-// what first_order = 2, 3, 4 (SMP_1D, SMP_1D_ver2, SMP_1D_ver3) asks of the rest of a configuration: no cap (max_receptive_field ==
-// max_nVertices), nContractions = custom_matmul = physics = 0, channel counts and multiplicities that fit an int
-inline bool smp_1d_config_ok(const gf_smp_config *cfg) {
-    if (cfg->first_order < 2 || cfg->first_order > 4) return false;
-    if (cfg->nContractions || cfg->custom_matmul || cfg->physics || cfg->max_nVertices != cfg->max_receptive_field) return false;
-    if (cfg->first_order == 2) return cfg->max_nVertices <= 2000;   // (th_weight = j (j + 1) (j + 2) / 6, j <= max_nVertices)
-    return cfg->nLevels <= 16 && ((long long)cfg->nChanels << cfg->nLevels) <= (1 << 20);   // (C_l = C << l)
-}
-// what steerable_2d = 1, 2, 5 (SMP_2D, SMP_2D_ver4, SMP_2D_ver5; there is no 3 or 4) asks: first_order = 0, no cap, no contraction family /
-// custom product / tower, a multiplicity j (j + 1) / 2 (j <= max_nVertices) and channel counts that fit an int; 5: K1 [C][C] fits in LDS
-inline bool smp_2d_config_ok(const gf_smp_config *cfg) {
-    if ((cfg->steerable_2d != 1 && cfg->steerable_2d != 2 && cfg->steerable_2d != 5) || cfg->first_order) return false;
-    if (cfg->steerable_2d == 5 && cfg->nChanels > 128) return false;
-    if (cfg->nContractions || cfg->custom_matmul || cfg->physics || cfg->max_nVertices != cfg->max_receptive_field) return false;
-    if (cfg->max_nVertices > 4096) return false;   // (th_weight <= 4096 * 4097 / 2; gf_smp_prepare takes no larger molecule)
-    return cfg->steerable_2d != 2 || (cfg->nLevels <= 16 && ((long long)cfg->nChanels << cfg->nLevels) <= (1 << 20));   // (C_l = C << l)
-}
-// what unrestricted = 1, 2, 3 (Unrestricted_SMP_1D, _1D_ver2, _2D) asks: first_order = steerable_2d = 0, no cap, no contraction family /
-// custom product / tower, channel counts and a parameter count that fit an int
-inline bool smp_unrestricted_config_ok(const gf_smp_config *cfg) {
-    if (cfg->unrestricted < 1 || cfg->unrestricted > 3 || cfg->first_order || cfg->steerable_2d) return false;
-    if (cfg->nContractions || cfg->custom_matmul || cfg->physics || cfg->max_nVertices != cfg->max_receptive_field) return false;
-    if (cfg->max_nVertices > 4096 || cfg->nLevels > 16 || ((long long)cfg->nChanels << cfg->nLevels) > (1 << 20)) return false;
-    const long long m = cfg->max_nVertices, sq = m * (m + 1) * (2 * m + 1) / 6;   // sum of s^2
-    long long n = (long long)cfg->nChanels * cfg->nFeatures * (cfg->nDepth + 1), Cl = cfg->nChanels;
-    for (int l = 1; l <= cfg->nLevels; ++l) {
-        const long long Cp = Cl;
-        if (cfg->unrestricted == 2) Cl *= 2;
-        n += (cfg->unrestricted == 3 ? Cp : cfg->unrestricted) * sq + m * Cl + (cfg->unrestricted == 3 ? Cp : 0);
-    }
-    return n + Cl <= 0x7fffffffll;
-}
-// the restricted sibling whose rows, tables and read-out an unrestricted form sits on (gfsmp::Config::unrestricted)
-inline void smp_unrestricted_config(const gf_smp_config *cfg, gfsmp::Config *c) {
-    c->unrestricted = cfg->unrestricted;
-    c->first_order = cfg->unrestricted == 1 ? 2 : cfg->unrestricted == 2 ? 3 : 0;
-    c->steerable_2d = cfg->unrestricted == 3 ? 1 : 0;
-    c->max_nVertices = cfg->max_nVertices;
-    c->nContractions = c->first_order ? 2 : 0;
-}
-// what neighbourhood = 1, 2, 3 (NeuralFingerprint, GCN_1D, GCN_2D; smp_level_neighbourhood.hip) asks: no other form, no cap, nLevels >= 0,
-// at most kNeighbourhoodMaxChanels channels and the forward level's LDS images within 160 KiB
-constexpr int kNeighbourhoodMaxChanels = 128;
-// the lanes that share one vertex in the level's kernels: the power of two at or above H, at least 8, at most a wave
-inline int smp_neighbourhood_group_width(int H) { return H > 32 ? 64 : H > 16 ? 32 : H > 8 ? 16 : 8; }
-// LDS of the forward level: W1_l^T [F'][H | 1] and W2_l^T [H][H | 1] (odd row strides), one vector of H floats per vertex slot of 256 lanes
-inline size_t smp_neighbourhood_lds_bytes(int H, int FD) {
-    return sizeof(float) * ((size_t)(FD + H) * (size_t)(H | 1) + (size_t)(256 / smp_neighbourhood_group_width(H)) * H);
-}
-inline bool smp_neighbourhood_config_ok(const gf_smp_config *cfg) {
-    if (cfg->neighbourhood < 1 || cfg->neighbourhood > 3) return false;
-    if (cfg->first_order || cfg->steerable_2d || cfg->unrestricted || cfg->physics || cfg->nContractions || cfg->custom_matmul) return false;
-    if (cfg->nLevels < 0 || cfg->nLevels > 64 || cfg->nChanels < 1 || cfg->nFeatures < 1 || cfg->nDepth < 0 || cfg->max_nVertices < 1) return false;
-    if (cfg->max_receptive_field != cfg->max_nVertices || cfg->max_nVertices > 4096) return false;
-    if (cfg->neighbourhood == 1 && cfg->nDepth != 0) return false;
-    if (cfg->neighbourhood == 2 && cfg->max_Radius < 0) return false;
-    if (cfg->nChanels > kNeighbourhoodMaxChanels) return false;
-    const long long FD = (long long)cfg->nFeatures * (cfg->nDepth + 1);
-    return FD <= 65536 && smp_neighbourhood_lds_bytes(cfg->nChanels, (int)FD) <= 160 * 1024;
-}
-inline void smp_neighbourhood_config(const gf_smp_config *cfg, gfsmp::Config *c) {
-    *c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, 0};
-    c->nContractions = 0;
-    c->max_nVertices = cfg->max_nVertices;
-    c->neighbourhood = cfg->neighbourhood;
-    c->max_Radius = cfg->neighbourhood == 2 ? cfg->max_Radius : 0;   // (form 3 stores it and never reads it; form 1 has none)
-}
+// The handle of a configuration as `entry` asks for it (gfsmp::resolve_config decides, before anything is allocated).
+// pad_channels = false: compute at the configuration's own channel counts; min_pad: the smallest padded width the handle may compute at
+// (32 for the towers of a slice-dropout model)
+gf_status smp_create(gf_ctx *ctx, const gf_smp_config *cfg, const gfsmp::ConfigEntry &entry, bool pad_channels, gf_smp **out, int min_pad = 0);
 void smp_derive_plan(gf_smp *s, bool allow_embed);
 gf_status smp_switch_plan(gf_smp *s, bool embed);
 constexpr int kPadMaxLevels = 15;   // levels a padded model's layout map holds (gf_smp_create: deeper models compute at nChanels)
@@ -455,38 +390,8 @@ gf_status smp_combine_bwd_panels_c64(gf_smp *s, int l, const float *dfrows, cons
 // level l's K_l / b_l gradients are complete on the context's CURRENT stream (l == 0: H): start their all-reduce
 gf_status smp_dp_level_done(gf_smp *s, int l);
 
-// ---- the parameter layout: H, (K_1, b_1), ..., (K_L, b_L), W (first-order models: H, (sizes_l, K_l) ..., W, gfsmp::Config::first_order) -- the registration order of SMP_omega.h:289-295 (= save_model order) ----
-// (W is [readout_rows()][C]: one row for the regression models, nClass rows for a classifier, SMP_2D_ver6_classification.h:211-217)
-inline size_t param_count(const gfsmp::Config &c) {
-    if (c.neighbourhood) {   // W1_0; (W1_l, W2_l) for l = 1..L; W
-        const size_t H = (size_t)c.nChanels;
-        return H * c.fdim() + (size_t)c.nLevels * (H * c.fdim() + H * H) + H;
-    }
-    size_t n = (size_t)c.nChanels * c.fdim();
-    for (int l = 1; l <= c.nLevels; ++l)
-        n += c.weight_block(l) + c.size_block(l);
-    return n + (c.physics ? 0 : (size_t)c.readout_rows() * c.top_channels());  // a physics tower ends in its level features: the head's weights are the caller's
-}
-template <typename P>
-void view_params(const gfsmp::Config &c, P *base, P **H, std::vector<P *> *K, std::vector<P *> *b, P **W) {
-    P *p = base;
-    *H = p;
-    p += (size_t)c.nChanels * c.fdim();
-    K->assign(c.nLevels + 1, nullptr);
-    b->assign(c.nLevels + 1, nullptr);
-    for (int l = 1; l <= c.nLevels; ++l) {
-        if (c.per_size()) {   // (SMP_theta.h:254-264: the per-size blocks are registered before K_l; b[l] = the first of them)
-            (*b)[l] = p;
-            p += c.size_block(l);
-        }
-        (*K)[l] = p;
-        p += c.weight_block(l);   // (SMP_1D / ver2: empty, K[l] is never read; ver3: K_eye then K_one = [2 C_{l-1}][C_{l-1}]; SMP_2D / ver4: scalar_l; ver5: K_l [C][2 C] then scalar_l)
-        if (c.per_size()) continue;
-        (*b)[l] = p;
-        p += c.level_channels(l);
-    }
-    *W = p;
-}
+using gfsmp::param_count;   // the parameter layout: smp_prep.h
+using gfsmp::view_params;
 inline size_t feature_width(const gfsmp::Config &c) {  // physics tower: sum over the levels of their channel counts
     size_t w = 0;
     for (int l = 0; l <= c.nLevels; ++l) w += (size_t)c.level_channels(l);

@@ -310,16 +310,10 @@ template <typename P>
 struct View {
     std::vector<P *> W1, W2;
     P *W;
-    View(const gfsmp::Config &c, P *p) : W1(c.nLevels + 1), W2(c.nLevels + 1, nullptr) {
-        const size_t H = (size_t)c.nChanels, FD = (size_t)c.fdim();
-        for (int l = 0; l <= c.nLevels; ++l) {
-            W1[l] = p;
-            p += H * FD;
-            if (l == 0) continue;
-            W2[l] = p;
-            p += H * H;
-        }
-        W = p;
+    View(const gfsmp::Config &c, P *p) {   // (view_params: the matrix block of level l is W1_l then W2_l)
+        view_params<P>(c, p, &p, &W1, &W2, &W);
+        W1[0] = p;
+        for (int l = 1; l <= c.nLevels; ++l) W2[l] = W1[l] + c.level_blocks(l).mat[0].n;
     }
 };
 

@@ -110,6 +110,7 @@ struct ModelPlan {
     double decay = 0.0;                       // > 0: CCN_1D's width rule (gfsmp::Config::decay)
     std::vector<int> lvlC, widths;
     std::vector<ModelSeg> segs[2];
+    gf_smp_config tower_cfg[2];                // what gf_smp_create is asked for, tower by tower
     size_t head_off = 0, head_params = 0, n_params = 0;
 };
 
@@ -145,28 +146,30 @@ bool model_plan(const gf_smp_model_config *cfg, ModelPlan *p, char *why, size_t 
     p->maxV[0] = maxV[0];
     p->maxV[1] = maxV[1];
     p->decay = cfg->ccn_1d ? cfg->nChanels_decay : 0.0;
-    gfsmp::Config widths = {cfg->nLevels, cfg->nChanels, 1, 0, cfg->max_receptive_field, 0};   // (a tower's width rule: halving, or the decay)
-    widths.physics = 1;
-    widths.decay = p->decay;
+    // the towers: what gf_smp_create is asked for, and what it will make of it (the width rule -- halving, or the decay -- and the blocks)
+    gfsmp::Config tower[2];
+    for (int t = 0; t < cfg->nTowers; ++t) {
+        p->tower_cfg[t] = {cfg->nLevels, cfg->nChanels, cfg->nFeatures[t], 0, cfg->max_receptive_field, 0, cfg->first_order ? 0 : nK, 0, 1,
+                           cfg->first_order ? 1 : 0, cfg->first_order ? maxV[t] : 0};
+        if (gfsmp::resolve_config(&p->tower_cfg[t], {gfsmp::ConfigEntry::Tower, 0, p->decay}, &tower[t], why, nwhy) != GF_OK) return false;
+    }
     const int L = cfg->nLevels;
     for (int l = 0; l <= L; ++l) {
-        p->lvlC.push_back(widths.level_channels(l));
+        p->lvlC.push_back(tower[0].level_channels(l));
         p->fwidth += p->lvlC.back();
     }
     size_t off = 0;
     // the H matrices come first (one per tower), then the levels, towers interleaved inside a level
     size_t toff[2] = {0, 0};
     for (int t = 0; t < cfg->nTowers; ++t) {
-        const size_t nH = (size_t)cfg->nChanels * cfg->nFeatures[t];
+        const size_t nH = tower[t].first_block().n;
         p->segs[t].push_back({off, 0, nH});
         off += nH;
         toff[t] = nH;
     }
     for (int l = 1; l <= L; ++l)
         for (int t = 0; t < cfg->nTowers; ++t) {
-            // (first order: the per-size (lambda1, lambda2, b) blocks, then K_l -- one contiguous segment in either layout)
-            const size_t n = cfg->first_order ? (size_t)maxV[t] * (2 + p->lvlC[l]) + (size_t)2 * p->lvlC[l - 1] * p->lvlC[l]
-                                              : (size_t)nK * p->lvlC[l - 1] * p->lvlC[l] + p->lvlC[l];
+            const size_t n = tower[t].level_blocks(l).total();   // (one contiguous segment in either layout)
             p->segs[t].push_back({off, toff[t], n});
             off += n;
             toff[t] += n;
@@ -228,12 +231,10 @@ gf_status gf_smp_model_create(gf_ctx *ctx, const gf_smp_model_config *cfg, gf_sm
     m->n_params = plan.n_params;
     for (int t = 0; t < m->nTowers; ++t) {
         m->segs[t] = plan.segs[t];
-        gf_smp_config tc = {cfg->nLevels, cfg->nChanels, cfg->nFeatures[t], 0, cfg->max_receptive_field, 0, cfg->first_order ? 0 : nK, 0, 1,
-                            cfg->first_order ? 1 : 0, cfg->first_order ? maxV[t] : 0};
         // (nKept > 0, RisiContraction_18_dropout: towers of up to 32 channels run the fused levels with per-product slice factors since
         //  round 5 -- padded like the others; wider ones keep their levels op by op, at their own halving widths)
-        gf_status st = gf::smp_create(ctx, &tc, /*pad_channels=*/cfg->nKept <= 0 || cfg->nChanels <= 32, &m->tower[t], /*min_pad=*/0, /*nClass=*/0,
-                                      plan.decay);
+        gf_status st = gf::smp_create(ctx, &plan.tower_cfg[t], {gfsmp::ConfigEntry::Tower, 0, plan.decay},
+                                      /*pad_channels=*/cfg->nKept <= 0 || cfg->nChanels <= 32, &m->tower[t]);
         if (st != GF_OK) {
             gf_smp_model_destroy(m);
             return st;
@@ -466,30 +467,16 @@ gf_status gf_smp_model_backward(gf_smp_model *m, const float *params, float *gra
 // the parameters in registration order, drawn from rand(): the same srand() gives the reference's initial weights.  Host buffer.
 gf_status gf_smp_model_uniform_init_host(const gf_smp_model *m, float *params) {
     if (!m || !params) return GF_ERR_INVALID;
-    std::vector<size_t> sizes;
-    const int C = m->cfg.nChanels;
-    for (int t = 0; t < m->nTowers; ++t) sizes.push_back((size_t)C * m->cfg.nFeatures[t]);
-    for (int l = 1; l <= m->L; ++l)
-        for (int t = 0; t < m->nTowers; ++t) {
-            if (m->cfg.first_order)   // (SMP_theta_physics.h:270-278: lambda1, lambda2, b per size, then K_l)
-                for (int size = 1; size <= m->cfg.max_nVertices[t]; ++size) {
-                    sizes.push_back(1);
-                    sizes.push_back(1);
-                    sizes.push_back((size_t)m->lvlC[l]);
-                }
-            sizes.push_back((size_t)m->cfg.nContractions * m->lvlC[l - 1] * m->lvlC[l]);
-            if (!m->cfg.first_order) sizes.push_back((size_t)m->lvlC[l]);
-        }
-    for (int i = 1; i <= m->nLayers; ++i) sizes.push_back((size_t)m->widths[i] * m->widths[i - 1]);
-    sizes.push_back((size_t)m->widths[m->nLayers]);
-    size_t off = 0;
-    for (size_t v = 0; v < sizes.size(); ++v)
-        for (size_t i = 0; i < sizes[v]; ++i) {
-            double x = (double)(rand() % 10) / (10.0 * (double)sizes[v]);
-            if (rand() % 2 == 1) x = -x;
-            params[off++] = (float)x;
-        }
-    return off == m->n_params ? GF_OK : GF_ERR_INVALID;
+    float *p = params;
+    const auto draw = [&p](const gfsmp::Config::Block &b) { gfsmp::uniform_draw(b, &p); };
+    for (int t = 0; t < m->nTowers; ++t) draw(m->tower[t]->ucfg.first_block());
+    for (int l = 1; l <= m->L; ++l)   // (SMP_theta_physics.h:270-278: lambda1, lambda2, b per size, then K_l; else K_l, b_l)
+        for (int t = 0; t < m->nTowers; ++t) m->tower[t]->ucfg.level_blocks(l).each_draw(draw);
+    for (int i = 1; i <= m->nLayers + 1; ++i) {   // the head: one block per layer, then one of the last width
+        const size_t n = i <= m->nLayers ? (size_t)m->widths[i] * m->widths[i - 1] : (size_t)m->widths[m->nLayers];
+        draw({n, n});
+    }
+    return (size_t)(p - params) == m->n_params ? GF_OK : GF_ERR_INVALID;
 }
 
 // ---- host-pointer mode (the C++ model classes): the handle owns parameters, gradients and the Adam moments ---------------

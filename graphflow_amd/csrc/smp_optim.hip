@@ -186,113 +186,32 @@ gf_status gf_smp_adam_reset(gf_smp *s) {
 
 // SMP_omega::weights_initialization (SMP_omega.h:334-338) = GraphFlow::uniform_init (GraphFlow.h:1297-1306) over the
 // parameters in registration order, drawn from the C library's rand() exactly as the reference draws them: after the
-// same srand() a model built here starts from the same weights as one built by the reference.  Host buffer.
-// the layout of a configuration (what gf_smp_create derives before it touches the device); false: one it would refuse
-static bool host_config(const gf_smp_config *cfg, int nClass, gfsmp::Config *out) {
-    if (cfg && cfg->neighbourhood) {   // NeuralFingerprint, GCN_1D, GCN_2D (gf_smp_config.neighbourhood; nLevels = 0 is a model; no classifier)
-        if (nClass || !gf::smp_neighbourhood_config_ok(cfg)) return false;
-        gf::smp_neighbourhood_config(cfg, out);
-        return true;
-    }
-    if (!cfg || cfg->nLevels < 1 || cfg->nChanels < 1 || cfg->nFeatures < 1 || cfg->nDepth < 0 || cfg->max_receptive_field < 1) return false;
-    gfsmp::Config c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, cfg->has_WL_ordering};
-    c.nContractions = cfg->nContractions ? cfg->nContractions : 18;
-    c.custom_matmul = cfg->custom_matmul ? 1 : 0;
-    c.physics = cfg->physics ? 1 : 0;
-    c.nClass = nClass;
-    if (cfg->unrestricted) {   // Unrestricted_SMP_1D, _1D_ver2, _2D (gf_smp_config.unrestricted; no classifier)
-        if (nClass || !gf::smp_unrestricted_config_ok(cfg)) return false;
-        gf::smp_unrestricted_config(cfg, &c);
-    } else if (cfg->steerable_2d) {   // SMP_2D, SMP_2D_ver4 (gf_smp_config.steerable_2d; a classifier read-out is allowed)
-        if (!gf::smp_2d_config_ok(cfg) || (nClass && cfg->steerable_2d == 5)) return false;   // (SMP_2D_ver5: no classifier)
-        c.steerable_2d = cfg->steerable_2d;
-        c.max_nVertices = cfg->max_nVertices;
-        c.nContractions = 0;
-    } else if (cfg->first_order == 1) {   // SMP_theta (gf_smp_config.first_order)
-        if (cfg->nContractions || cfg->custom_matmul || cfg->max_nVertices < cfg->max_receptive_field || nClass) return false;
-        c.first_order = 1;
-        c.max_nVertices = cfg->max_nVertices;
-        c.nContractions = 2;
-    } else if (cfg->first_order) {   // 2, 3, 4: SMP_1D, SMP_1D_ver2, SMP_1D_ver3 (no cap; a classifier read-out is allowed)
-        if (!gf::smp_1d_config_ok(cfg)) return false;
-        c.first_order = cfg->first_order;
-        c.max_nVertices = cfg->max_nVertices;
-        c.nContractions = 2;
-    }
-    *out = c;
-    return true;
-}
-static gf_status uniform_init_host(const gf_smp_config *cfg, int nClass, float *params) {
+// same srand() a model built here starts from the same weights as one built by the reference.  Host buffer, host only:
+// gfsmp::resolve_config says what gf_smp_create / gf_smp_create_classifier would build, Config::level_blocks what it holds.
+static gf_status uniform_init_host(const gf_smp_config *cfg, const gfsmp::ConfigEntry &entry, float *params) {
     gfsmp::Config c;
-    if (!params || !host_config(cfg, nClass, &c)) return GF_ERR_INVALID;
-    const size_t C = (size_t)c.nChanels;
-    std::vector<size_t> sizes;
-    if (c.neighbourhood) {   // W1_l, W2_l by uniform_init(Matrix*): 10 x nRows = 10 H; W by uniform_init(Vector*): 10 x its size = 10 H
-        size_t off = 0;      // (NeuralFingerprint.h:109-119, GCN_1D.h / GCN_2D.h:119-129)
-        for (size_t i = 0, n = gf::param_count(c); i < n; ++i) {
-            double x = (double)(rand() % 10) / (10.0 * (double)C);
-            if (rand() % 2 == 1) x = -x;
-            params[off++] = (float)x;
-        }
-        return GF_OK;
-    }
-    sizes.push_back(C * c.fdim());
-    for (int l = 1; l <= c.nLevels; ++l) {
-        if (c.unrestricted)   // W[size] (W1[size], W2[size]), b[size]: every one a block of its own, uniform_init(Vector*) divides by 10 x its
-            for (int size = 1; size <= c.max_nVertices; ++size) {   // size (Unrestricted_SMP_1D.h:168-171, _2D.h:189-193)
-                const size_t w = (size_t)size * size * (c.unrestricted == 3 ? (size_t)c.level_channels(l - 1) : 1);
-                sizes.push_back(w);
-                if (c.unrestricted == 2) sizes.push_back(w);
-                sizes.push_back((size_t)c.level_channels(l));
-            }
-        else if (c.first_order)   // lambda1[size], lambda2[size], b[size] for size = 1 .. max_nVertices, then K_l (SMP_theta.h:254-264)
-            for (int size = 1; size <= c.max_nVertices; ++size) {
-                sizes.push_back(1);
-                sizes.push_back(1);
-                sizes.push_back((size_t)c.level_channels(l));
-            }
-        if (c.steerable_2d && !c.unrestricted)   // lambda1[size], lambda2[size] [C_{l-1}], b[size] [C_l], then scalar_l below (SMP_2D.h:228-235)
-            for (int size = 1; size <= c.max_nVertices; ++size) {
-                sizes.push_back((size_t)c.level_channels(l - 1));
-                sizes.push_back((size_t)c.level_channels(l - 1));
-                sizes.push_back((size_t)c.level_channels(l));
-            }
-        if (c.first_order == 4) {   // K_eye, K_one: one block each (SMP_1D_ver3.h:238-239)
-            sizes.push_back(c.weight_block(l) / 2);
-            sizes.push_back(c.weight_block(l) / 2);
-        } else if (c.steerable_2d == 5 && !c.unrestricted) {   // K_l [C][2 C] as one Vector of 2 C^2, then scalar_l (SMP_2D_ver5.h:241-242)
-            sizes.push_back(2 * C * C);
-            sizes.push_back(C);
-        } else if (c.weight_block(l)) {
-            sizes.push_back(c.weight_block(l));
-        }
-        if (!c.per_size()) sizes.push_back((size_t)c.level_channels(l));
-    }
-    if (!c.physics) sizes.push_back((size_t)(nClass > 1 ? nClass : 1) * c.top_channels());
-    size_t off = 0;
-    for (size_t v = 0; v < sizes.size(); ++v)
-        for (size_t i = 0; i < sizes[v]; ++i) {
-            double x = (double)(rand() % 10) / (10.0 * (double)sizes[v]);
-            if (rand() % 2 == 1) x = -x;
-            params[off++] = (float)x;
-        }
+    char why[640];
+    if (!params || gfsmp::resolve_config(cfg, entry, &c, why, sizeof why) != GF_OK) return GF_ERR_INVALID;
+    const auto draw = [&params](const gfsmp::Config::Block &b) { gfsmp::uniform_draw(b, &params); };
+    draw(c.first_block());
+    for (int l = 1; l <= c.nLevels; ++l) c.level_blocks(l).each_draw(draw);
+    draw(c.readout_block());
     return GF_OK;
 }
-gf_status gf_smp_uniform_init_host(const gf_smp_config *cfg, float *params) { return uniform_init_host(cfg, 0, params); }
-size_t gf_smp_config_param_count(const gf_smp_config *cfg) {
+static size_t config_param_count(const gf_smp_config *cfg, const gfsmp::ConfigEntry &entry) {
     gfsmp::Config c;
-    return host_config(cfg, 0, &c) ? gf::param_count(c) : 0;
+    char why[640];
+    return gfsmp::resolve_config(cfg, entry, &c, why, sizeof why) == GF_OK ? gf::param_count(c) : 0;
 }
+gf_status gf_smp_uniform_init_host(const gf_smp_config *cfg, float *params) { return uniform_init_host(cfg, gfsmp::kHandleEntry, params); }
+size_t gf_smp_config_param_count(const gf_smp_config *cfg) { return config_param_count(cfg, gfsmp::kHandleEntry); }
 size_t gf_smp_classifier_config_param_count(const gf_smp_config *cfg, int nClass) {
-    gfsmp::Config c;
-    if (!cfg || cfg->physics || cfg->first_order == 1 || cfg->unrestricted || cfg->neighbourhood || nClass < 2) return 0;   // (what gf_smp_create_classifier refuses)
-    return host_config(cfg, nClass, &c) ? gf::param_count(c) : 0;
+    return config_param_count(cfg, {gfsmp::ConfigEntry::Classifier, nClass, 0.0});
 }
 // ... of the `_classification` models (SMP_2D_ver6_classification.h:256-259): sgd->params holds Vector*, so W [nClass][C] is drawn by
 // uniform_init(Vector*) like the rest, with the divisor 10 * nClass * C
 gf_status gf_smp_classifier_uniform_init_host(const gf_smp_config *cfg, int nClass, float *params) {
-    if (!cfg || cfg->physics || nClass < 2) return GF_ERR_INVALID;
-    return uniform_init_host(cfg, nClass, params);
+    return uniform_init_host(cfg, {gfsmp::ConfigEntry::Classifier, nClass, 0.0}, params);
 }
 
 // Text checkpoints in the reference's format (SMP_omega.h:1033-1042 / :1044-1055): every parameter value in

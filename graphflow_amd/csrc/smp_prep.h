@@ -12,6 +12,8 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
+#include <initializer_list>
 #include <vector>
 
 namespace gfsmp {
@@ -85,23 +87,89 @@ struct Config {
     // 1..L: W1_l [H][F'], W2_l [H][H]; W [H].  None of the other forms' fields is set: the handle has no fields, rows or per-size blocks.
     int neighbourhood = 0, max_Radius = 0;
     int nb_radius(int l) const { return neighbourhood == 1 ? 1 : neighbourhood == 3 || l < max_Radius ? l : max_Radius; }   // of N_l (form 1: the adjacency itself)
-    size_t filter_floats(int l) const { return unrestricted == 3 ? (size_t)level_channels(l - 1) : (size_t)unrestricted; }   // per s^2
+    size_t filter_floats(int l) const { return level_blocks(l).size_quad(); }   // of an unrestricted level's filter, per s^2
     bool per_size() const { return first_order || steerable_2d; }   // a handle on the th_* tables, per-size blocks in front of the matrix block
     bool concat() const { return first_order >= 3 || steerable_2d == 2; }   // C_l = 2 C_{l-1}
     float level_slope() const { return first_order >= 3 ? 0.f : 0.01f; }   // LeakyReLU2D / 3D of every level (the read-out's LeakyReLU stays at 0.01)
-    size_t size_block(int l) const {
-        if (unrestricted) {   // sum over s of (filter_floats s^2 + C_l)
-            const size_t m = (size_t)max_nVertices;
-            return filter_floats(l) * (m * (m + 1) * (2 * m + 1) / 6) + m * (size_t)level_channels(l);
+    // ---- The parameter blocks in registration order: first_block(); level_blocks(l) for l = 1 .. nLevels; readout_block().  This is the one
+    // account of the layout: param_count, view_params, the tower segments of a composite model and the uniform_init functions all read it.
+    // A Block is n floats that GraphFlow::uniform_init draws together, with the divisor 10 * div: its own size for a Vector, the row count
+    // for a Matrix of the neighbourhood classes (uniform_init(Matrix*)).
+    struct Block {
+        size_t n, div;
+    };
+    // One level's segment: for size = 1 .. max_size an entry of nsize blocks (block i of a size: quad * size^2 + lin floats), then the nmat
+    // blocks of the matrix block, then the bias.  A family has the per-size entries or the bias, never both.
+    struct LevelBlocks {
+        struct SizeTerm {
+            size_t quad, lin;
+        };
+        size_t max_size = 0, bias = 0;
+        int nsize = 0, nmat = 0;
+        SizeTerm size[3];
+        Block mat[2];
+        size_t size_quad() const {
+            size_t q = 0;
+            for (int i = 0; i < nsize; ++i) q += size[i].quad;
+            return q;
         }
-        if (steerable_2d) return (size_t)max_nVertices * (2 * (size_t)level_channels(l - 1) + (size_t)level_channels(l));
-        return first_order ? (size_t)max_nVertices * (2 + (size_t)level_channels(l)) : (size_t)level_channels(l);
+        size_t sizes() const {   // the per-size entries together, in closed form: a sweep asks per pass, an unrestricted level has up to 4096 sizes
+            size_t lin = 0;
+            for (int i = 0; i < nsize; ++i) lin += size[i].lin;
+            return size_quad() * (max_size * (max_size + 1) * (2 * max_size + 1) / 6) + lin * max_size;
+        }
+        size_t matrix() const { return (nmat > 0 ? mat[0].n : 0) + (nmat > 1 ? mat[1].n : 0); }
+        size_t total() const { return sizes() + matrix() + bias; }
+        template <class F>
+        void each_draw(F f) const {   // f(Block) for every block uniform_init draws with a divisor of its own, in order
+            for (size_t s = 1; s <= max_size; ++s)
+                for (int i = 0; i < nsize; ++i) {
+                    const size_t n = size[i].quad * s * s + size[i].lin;
+                    f(Block{n, n});
+                }
+            for (int i = 0; i < nmat; ++i) f(mat[i]);
+            if (bias) f(Block{bias, bias});
+        }
+    };
+    LevelBlocks level_blocks(int l) const {
+        const size_t Cp = (size_t)level_channels(l - 1), Cl = (size_t)level_channels(l);
+        LevelBlocks b;
+        auto sizes = [&b](std::initializer_list<LevelBlocks::SizeTerm> t) { for (const LevelBlocks::SizeTerm &x : t) b.size[b.nsize++] = x; };
+        auto matrix = [&b](size_t n, size_t div = 0) { b.mat[b.nmat++] = {n, div ? div : n}; };   // (div = 0: a Vector, divided by its own size)
+        if (neighbourhood) {   // W1_l [H][F'], W2_l [H][H]: no per-size entries, no bias (l = 0: W1_0 is first_block())
+            matrix(Cl * fdim(), Cl);
+            matrix(Cl * Cl, Cl);
+            return b;
+        }
+        if (per_size()) b.max_size = (size_t)max_nVertices;
+        if (unrestricted == 1) sizes({{1, 0}, {0, Cl}});                 // W_s [s][s], b_s
+        else if (unrestricted == 2) sizes({{1, 0}, {1, 0}, {0, Cl}});    // W1_s, W2_s [s][s], b_s
+        else if (unrestricted == 3) sizes({{Cp, 0}, {0, Cl}});           // W_s [s][s][C], b_s
+        else if (steerable_2d) sizes({{0, Cp}, {0, Cp}, {0, Cl}});       // lambda1_s, lambda2_s [C_{l-1}], b_s (SMP_2D.h:228-235)
+        else if (first_order) sizes({{0, 1}, {0, 1}, {0, Cl}});          // lambda1_s, lambda2_s, b_s (SMP_theta.h:254-264)
+        else b.bias = Cl;
+        if (steerable_2d == 5) {   // K_l [C][2 C] as one Vector, then scalar_l (SMP_2D_ver5.h:241-242)
+            matrix(2 * Cp * Cp);
+            matrix(Cp);
+        } else if (steerable_2d) {   // scalar_l (SMP_2D / ver4, Unrestricted_SMP_2D)
+            matrix(Cp);
+        } else if (first_order == 4) {   // K_eye, K_one: one block each (SMP_1D_ver3.h:238-239)
+            matrix(Cp * Cp);
+            matrix(Cp * Cp);
+        } else if (first_order < 2) {   // K_l [nContractions C_{l-1}][C_l]; SMP_1D / ver2 and their unrestricted forms have no matrix block
+            matrix((size_t)nContractions * Cp * Cl);
+        }
+        return b;
     }
-    // floats of the level's matrix block: K_l [nContractions C_{l-1}][C_l]; none in SMP_1D / ver2; K_eye, K_one in ver3; scalar_l in SMP_2D / ver4
-    size_t weight_block(int l) const {
-        const size_t Cp = (size_t)level_channels(l - 1);
-        if (steerable_2d) return steerable_2d == 5 ? 2 * Cp * Cp + Cp : Cp;
-        return first_order == 2 || first_order == 3 ? 0 : first_order == 4 ? 2 * Cp * Cp : (size_t)nContractions * Cp * level_channels(l);
+    Block first_block() const {   // H [C][F (D + 1)]; W1_0 [H][F'] of a neighbourhood form
+        const size_t n = (size_t)nChanels * fdim();
+        return {n, neighbourhood ? (size_t)nChanels : n};
+    }
+    // W [readout_rows()][top_channels()] (SMP_2D_ver6_classification.h:211-217), drawn as one Vector; none in a physics tower, which ends in
+    // its level features: the head's weights are the caller's
+    Block readout_block() const {
+        const size_t n = physics ? 0 : (size_t)readout_rows() * top_channels();
+        return {n, n};
     }
     int top_channels() const { return first_order >= 2 || steerable_2d ? level_channels(nLevels) : nChanels;  }   // width of the graph feature and of W's rows
     int readout_rows() const { return nClass > 1 ? nClass : 1; }   // rows of W: [1][C] is the regression's [C]
@@ -122,6 +190,42 @@ struct Config {
     }
     int fdim() const { return nFeatures * (nDepth + 1); }
 };
+
+// ---- the flat parameter vector: H, then per level (per-size entries, matrix block, bias), then W -- the registration order of
+// SMP_omega.h:289-295 (= save_model order); Config::level_blocks has what each family puts where ----
+inline size_t param_count(const Config &c) {
+    size_t n = c.first_block().n + c.readout_block().n;
+    for (int l = 1; l <= c.nLevels; ++l) n += c.level_blocks(l).total();
+    return n;
+}
+// K[l] = the level's matrix block (empty in SMP_1D / ver2: never read; W1_l then W2_l in a neighbourhood form), b[l] = its bias or, where
+// the family has them instead, the first of its per-size entries
+template <typename P>
+void view_params(const Config &c, P *base, P **H, std::vector<P *> *K, std::vector<P *> *b, P **W) {
+    P *p = base;
+    *H = p;
+    p += c.first_block().n;
+    K->assign(c.nLevels + 1, nullptr);
+    b->assign(c.nLevels + 1, nullptr);
+    for (int l = 1; l <= c.nLevels; ++l) {
+        const Config::LevelBlocks lb = c.level_blocks(l);
+        P *sizes = p;
+        p += lb.sizes();
+        (*K)[l] = p;
+        p += lb.matrix();
+        (*b)[l] = lb.bias ? p : sizes;
+        p += lb.bias;
+    }
+    *W = p;
+}
+// GraphFlow::uniform_init (GraphFlow.h:1297-1306) of one block, drawn from the C library's rand() exactly as the reference draws it
+inline void uniform_draw(const Config::Block &blk, float **p) {
+    for (size_t i = 0; i < blk.n; ++i) {
+        double x = (double)(rand() % 10) / (10.0 * (double)blk.div);
+        if (rand() % 2 == 1) x = -x;
+        *(*p)++ = (float)x;
+    }
+}
 
 // everything the reference derives from one molecule
 struct Molecule {

@@ -1068,16 +1068,21 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
 gf_status gf_smp_prepare_molecule_host(const gf_smp_config *cfg, int V, const int *adj, const double *feature,
                                        int *phi_out, double *wl_out) {
     if (!cfg || V <= 0 || !adj || !feature || !phi_out) return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: bad argument");
-    if (cfg->first_order >= 2 && !gf::smp_1d_config_ok(cfg))   // (SMP_1D* have no cap: a capped field is not one of theirs)
-        return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: first_order = %d needs max_receptive_field == max_nVertices", cfg->first_order);
-    if (cfg->steerable_2d && !gf::smp_2d_config_ok(cfg))
-        return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: steerable_2d = %d needs first_order = 0 and max_receptive_field == max_nVertices",
-                    cfg->steerable_2d);
-    if (cfg->neighbourhood)
+    // The families without a cap: a configuration no handle or tower is built from is not one of theirs (gfsmp::resolve_config's verdict, asked
+    // as a tower -- the widest entry; the family named is the one it judged).  Everything else is prepared as it stands.
+    gfsmp::Config resolved;
+    char why[640];
+    const bool refused = gfsmp::resolve_config(cfg, {gfsmp::ConfigEntry::Tower, 0, 0.0}, &resolved, why, sizeof why) != GF_OK;
+    if (cfg->neighbourhood)   // (about this call, not the configuration)
         return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: a neighbourhood model (NeuralFingerprint, GCN_1D, GCN_2D) has no receptive fields");
-    if (cfg->unrestricted && !gf::smp_unrestricted_config_ok(cfg))
+    if (refused && cfg->unrestricted)
         return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: unrestricted = %d needs first_order = steerable_2d = 0 and max_receptive_field "
                                              "== max_nVertices", cfg->unrestricted);
+    if (refused && cfg->steerable_2d)
+        return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: steerable_2d = %d needs first_order = 0 and max_receptive_field == max_nVertices",
+                    cfg->steerable_2d);
+    if (refused && cfg->first_order >= 2)   // (SMP_1D* have no cap: a capped field is not one of theirs)
+        return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: first_order = %d needs max_receptive_field == max_nVertices", cfg->first_order);
     gfsmp::Config c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, cfg->has_WL_ordering};
     c.physics = cfg->physics ? 1 : 0;
     gfsmp::Molecule m;
