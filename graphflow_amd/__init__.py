@@ -11,10 +11,10 @@ from .ops import (Context, GraphFlowHipError, contract18_dropout_backward, contr
                   mattensormul_backward, mattensormul_forward, stack_backward, stack_forward,
                   tensormatmul_backward, tensormatmul_forward)
 
-from .smp import SMPNeighbourhood  # noqa: F401
+from .smp import SMPGatedNeighbourhood, SMPNeighbourhood  # noqa: F401
 
 __all__ = ["Context", "GraphFlowHipError", "contract_forward", "contract_backward", "contract_workspace_bytes",
-           "default_context", "build", "SMPNeighbourhood"]
+           "default_context", "build", "SMPNeighbourhood", "SMPGatedNeighbourhood"]
 
 
 def build(verbose=False):

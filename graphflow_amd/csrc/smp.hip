@@ -797,6 +797,7 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
     gf_ctx *ctx = s->ctx;
     gf_status st = ensure_ws(ctx, s->ws_need);
     if (st != GF_OK) return st;
+    if (s->cfg.gated()) return smp_gru_forward(s, params, targets, predict, loss, graph_feature);   // (the neighbourhood kind's second set of sweeps)
     if (s->cfg.neighbourhood) return smp_neighbourhood_forward(s, params, targets, predict, loss, graph_feature);   // (its own level 0 and read-out)
     const gfsmp::BatchLayout &B = s->lay;
     const int L = s->cfg.nLevels, C = s->cfg.nChanels, FD = s->cfg.fdim();
@@ -991,6 +992,7 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
     // (a no-op after this batch's forward; it makes the reverse sweep independent of who grew the context's workspace last)
     gf_status st = ensure_ws(ctx, s->ws_need);
     if (st != GF_OK) return st;
+    if (s->cfg.gated()) return smp_gru_backward(s, params, grads, accumulate);
     if (s->cfg.neighbourhood) return smp_neighbourhood_backward(s, params, grads, accumulate);   // (never a tower: gf_smp_backward_features refuses)
     const gfsmp::BatchLayout &B = s->lay;
     const int L = s->cfg.nLevels, C = s->cfg.top_channels();   // (the read-out's width)

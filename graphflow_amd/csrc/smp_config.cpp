@@ -57,6 +57,13 @@ bool rule_neighbourhood(const gf_smp_config *cfg) {
     const long long FD = (long long)cfg->nFeatures * ((long long)cfg->nDepth + 1);
     return FD <= 65536 && gf::smp_neighbourhood_lds_bytes(cfg->nChanels, (int)FD) <= 160 * 1024;
 }
+// neighbourhood = 4, 5 (GRU_GCN_1D, GRU_GCN_2D): form 2's rules -- both read max_Radius -- apart from the channel count, which the caller
+// checks for a message of its own
+bool rule_gated(const gf_smp_config *cfg) {
+    gf_smp_config as2 = *cfg;
+    as2.neighbourhood = 2;
+    return (cfg->neighbourhood == 4 || cfg->neighbourhood == 5) && rule_neighbourhood(&as2);
+}
 
 }  // namespace
 
@@ -79,11 +86,30 @@ gf_status resolve_config(const gf_smp_config *cfg, const ConfigEntry &entry, Con
             GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: a first-order model (first_order = 1) has no classifier read-out");
         if (cfg->unrestricted) GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: the Unrestricted_SMP_* models have no `_classification` class");
         if (cfg->neighbourhood)
-            GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: NeuralFingerprint / GCN_1D / GCN_2D have no `_classification` class");
+            GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: NeuralFingerprint / GCN_1D / GCN_2D%s have no `_classification` class",
+                      cfg->neighbourhood >= 4 ? " / GRU_GCN_1D / GRU_GCN_2D" : "");
         if (cfg->physics) GF_REFUSE(GF_ERR_INVALID, "gf_smp_create_classifier: a physics tower has no read-out of its own (physics = 0)");
         if (nClass < 2) GF_REFUSE(GF_ERR_INVALID, "gf_smp_create_classifier: nClass = %d (at least 2)", nClass);
     }
     // ---- the configuration, family by family ----
+    if (cfg->neighbourhood == 4 || cfg->neighbourhood == 5) {   // GRU_GCN_1D, GRU_GCN_2D (smp_level_gru.hip): nLevels = 0 is a model
+        if (cfg->nChanels > gf::kGruMaxChanels)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: neighbourhood = %d with nChanels = %d: the six [H][H] matrices of a GRU cell are resident in "
+                                      "LDS for the length of a level (%zu bytes at %d channels, 160 KiB per workgroup): at most %d channels",
+                      cfg->neighbourhood, cfg->nChanels, gf::smp_gru_lds_bytes(cfg->nChanels), cfg->nChanels, gf::kGruMaxChanels);
+        if (!rule_gated(cfg))
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: neighbourhood = %d (4: GRU_GCN_1D, 5: GRU_GCN_2D) needs first_order = steerable_2d = unrestricted "
+                                      "= physics = nContractions = custom_matmul = 0, max_receptive_field (%d) == max_nVertices (%d) <= 4096, "
+                                      "nLevels >= 0, max_Radius (%d) >= 0 and W within 160 KiB", cfg->neighbourhood, cfg->max_receptive_field,
+                      cfg->max_nVertices, cfg->max_Radius);
+        Config c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, 0};
+        c.nContractions = 0;
+        c.max_nVertices = cfg->max_nVertices;
+        c.neighbourhood = cfg->neighbourhood;
+        c.max_Radius = cfg->max_Radius;
+        *out = c;
+        return GF_OK;
+    }
     if (cfg->neighbourhood) {   // NeuralFingerprint, GCN_1D, GCN_2D (smp_level_neighbourhood.hip): nLevels = 0 is a model
         if (!rule_neighbourhood(cfg))
             GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: neighbourhood = %d (1: NeuralFingerprint, 2: GCN_1D, 3: GCN_2D) needs first_order = steerable_2d = "

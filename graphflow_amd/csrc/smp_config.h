@@ -18,6 +18,12 @@ inline int smp_neighbourhood_group_width(int H) { return H > 32 ? 64 : H > 16 ? 
 inline size_t smp_neighbourhood_lds_bytes(int H, int FD) {
     return sizeof(float) * ((size_t)(FD + H) * (size_t)(H | 1) + (size_t)(256 / smp_neighbourhood_group_width(H)) * H);
 }
+// the gated level (smp_level_gru.hip; neighbourhood = 4, 5): six [H][H | 1] images and three vectors of H floats per vertex slot in LDS
+// -- 99.8 KB at 64 channels, 396 KB at 128: one launch per level holds at most 64 channels in the 160 KiB
+constexpr int kGruMaxChanels = 64;
+inline size_t smp_gru_lds_bytes(int H) {
+    return sizeof(float) * (6 * (size_t)H * (size_t)(H | 1) + 3 * (size_t)(256 / smp_neighbourhood_group_width(H)) * H);
+}
 }  // namespace gf
 
 namespace gfsmp {

@@ -251,6 +251,11 @@ struct gf_smp {
         const long long *nb_ptr = nullptr, *nb_tptr = nullptr;
         const int *nb_idx = nullptr, *nb_tidx = nullptr;
         float *nb_T = nullptr, *nb_Tt = nullptr, *nb_sA = nullptr;
+        // gated level (smp_level_gru.hip; levels >= 1, [vertices][H] each) beside them: the gates z_l, r_l, the candidate c_l, q = r h_{l-1};
+        // dz', dr', dc' (the operands of the six weight gradients) and the direct part of dh_{l-1}.  nb_T of a level >= 1 is the sum of an
+        // arbitrary vector.  The read-out's sigmoid, tanh and their two gradients live in the handle (gf_smp::gru_*).
+        float *gru_z = nullptr, *gru_r = nullptr, *gru_c = nullptr, *gru_q = nullptr;
+        float *gru_dz = nullptr, *gru_dr = nullptr, *gru_dc = nullptr, *gru_direct = nullptr;
     };
     std::vector<DevLevel> lv;
     // device-built level tables: the batch's adjacency matrices and the per-level statistics the kernels leave behind
@@ -270,6 +275,9 @@ struct gf_smp {
     float *dsh = nullptr;                // [nNodes][C] gradient of sh (the fused top level reads it per node)
     float *g = nullptr;      // [nMol][C] graph features
     float *yhat = nullptr, *dy = nullptr;  // [nMol]
+    // gated read-out (smp_level_gru.hip; [vertices][H] each): sigmoid(W_g h_L), tanh(U_g h_L), and the gradients of their arguments
+    float *gru_s = nullptr, *gru_t = nullptr, *gru_ds = nullptr, *gru_dt = nullptr;
+    float *gru_acc = nullptr;   // [param_count] the sweep of a gf_smp_backward with accumulate = 1, before it is added (taken on first use)
     // classifier handles (cfg.nClass >= 2, smp_readout_classes.hip): logits, softmax, dz = p - onehot [nMol][nClass]; dg = W^T dz [nMol][C]
     float *cls_scores = nullptr, *cls_prob = nullptr, *cls_dz = nullptr, *cls_dg = nullptr;
     float *colpart = nullptr;  // partial column sums for bias gradients, [colpart_rows][C]
@@ -312,7 +320,7 @@ constexpr int kFusedMaxField = 64;
 // What runs level l >= 1 of a pass: the fused 18-slice level (smp_fused.hip) where gf_smp_set_fused allows and smp_fused_supported takes the
 // shape, else the SMP_gamma level where smp_gamma_fused does, else the op-by-op pipeline (smp.hip); nobody else asks the two predicates.
 // Constant for the length of a pass, NOT between passes (gf_smp_set_fused, gf_smp_dropout_masks): a sweep asks at its start, keeps nothing.
-enum class LevelKind { OpByOp, Fused18, Gamma, Theta, Steerable2D, Unrestricted, Neighbourhood };   // Theta: every level of a first-order handle (cfg.first_order), Steerable2D: of a cfg.steerable_2d one, Unrestricted: of a cfg.unrestricted one (asked first), Neighbourhood: of a cfg.neighbourhood one (level 0 and the read-out too: its sweeps are smp_neighbourhood_forward / _backward), nothing else
+enum class LevelKind { OpByOp, Fused18, Gamma, Theta, Steerable2D, Unrestricted, Neighbourhood };   // Theta: every level of a first-order handle (cfg.first_order), Steerable2D: of a cfg.steerable_2d one, Unrestricted: of a cfg.unrestricted one (asked first), Neighbourhood: of a cfg.neighbourhood one (level 0 and the read-out too: its sweeps are smp_neighbourhood_forward / _backward, smp_gru_forward / _backward where cfg.gated()), nothing else
 LevelKind smp_level_kind(const gf_smp *s, int l);
 // the kinds on the th_* tables (smp_field_level.h): (namespace gf::field_level holds their kit) they take the read-out's gradient as one vector per node, write df_{l-1} themselves and
 // keep what a second reverse sweep needs
@@ -372,6 +380,20 @@ gf_status smp_unrestricted_backward_level(gf_smp *s, int l, const float *K, cons
 gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature);
 gf_status smp_neighbourhood_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature);
 gf_status smp_neighbourhood_backward(gf_smp *s, const float *params, float *grads, int accumulate);
+// ... and the launchers of its three level kernels on raw operands (the arguments of nbh_level_fwd / nbh_node_bwd / nbh_gather_bwd; pairs:
+// the RisiLayer2D instantiation; rounds = 0: the level's own choice), for the gated level, whose level 0 and reverse gather they are
+gf_status smp_neighbourhood_fwd_launch(gf_ctx *ctx, bool pairs, int H, int FD, int nV, int rounds, const float *W1, const float *W2, const float *x,
+                                       const float *hprev, const float *Tprev, const long long *ptr, const int *idx, float *h, float *n, float *A,
+                                       float *T, float *Tt);
+gf_status smp_neighbourhood_node_launch(gf_ctx *ctx, bool pairs, int H, int nV, int rounds, const float *W2, const float *h, float *dh,
+                                        const float *dy, const float *Wout, const int *vmol, const float *A, const float *Tt, float *dn, float *gTt,
+                                        float *sA);
+gf_status smp_neighbourhood_gather_launch(gf_ctx *ctx, bool pairs, int H, int nV, const long long *tptr, const int *tidx, const float *dn,
+                                          const float *gTt, const float *sA, const float *hprev, const float *Tprev, float *dhprev);
+// GRU_GCN_1D, GRU_GCN_2D (cfg.neighbourhood = 4, 5; smp_level_gru.hip): the sweeps of a gated handle on the same lists and buffers.
+// params / grads: W; W_z, U_z, W_r, U_r, W_h, U_h, W_g, U_g (shared by the levels: their gradients accumulate across them); U.
+gf_status smp_gru_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature);
+gf_status smp_gru_backward(gf_smp *s, const float *params, float *grads, int accumulate);
 // smp_theta_prepare (smp_prepare.hip): gf_smp_prepare of a first-order handle -- the th_* tables, none of the other kinds' buffers.
 gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature);
 // the first-order read-out of level l (smp_field_level.hip): sh[n] = column sums over the node's s rows (ShrinkMatrix), vf = LeakyReLU(sh);

@@ -425,6 +425,28 @@ gf_status check_list(gf_ctx *ctx, const char *who, const char *what, const P *pt
 
 }  // namespace
 
+// the launchers for another translation unit (smp_level_gru.hip): no new instantiation, the run-time pick of with_instantiation
+gf_status smp_neighbourhood_fwd_launch(gf_ctx *ctx, bool pairs, int H, int FD, int nV, int rounds, const float *W1, const float *W2, const float *x,
+                                       const float *hprev, const float *Tprev, const long long *ptr, const int *idx, float *h, float *n, float *A,
+                                       float *T, float *Tt) {
+    return with_instantiation(H, pairs, [&](auto nk, auto pr) -> gf_status {
+        return fwd_launch<decltype(nk)::value, decltype(pr)::value>(ctx, H, FD, nV, rounds, W1, W2, x, hprev, Tprev, ptr, idx, h, n, A, T, Tt);
+    });
+}
+gf_status smp_neighbourhood_node_launch(gf_ctx *ctx, bool pairs, int H, int nV, int rounds, const float *W2, const float *h, float *dh,
+                                        const float *dy, const float *Wout, const int *vmol, const float *A, const float *Tt, float *dn, float *gTt,
+                                        float *sA) {
+    return with_instantiation(H, pairs, [&](auto nk, auto pr) -> gf_status {
+        return node_launch<decltype(nk)::value, decltype(pr)::value>(ctx, H, nV, rounds, W2, h, dh, dy, Wout, vmol, A, Tt, dn, gTt, sA);
+    });
+}
+gf_status smp_neighbourhood_gather_launch(gf_ctx *ctx, bool pairs, int H, int nV, const long long *tptr, const int *tidx, const float *dn,
+                                          const float *gTt, const float *sA, const float *hprev, const float *Tprev, float *dhprev) {
+    return with_instantiation(H, pairs, [&](auto nk, auto pr) -> gf_status {
+        return gather_launch<decltype(nk)::value, decltype(pr)::value>(ctx, H, nV, tptr, tidx, dn, gTt, sA, hprev, Tprev, dhprev);
+    });
+}
+
 gf_status smp_neighbourhood_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature) {
     gf_ctx *ctx = s->ctx;
     const int L = s->cfg.nLevels, H = s->cfg.nChanels, nMol = s->lay.nMol;

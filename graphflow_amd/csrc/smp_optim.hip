@@ -194,6 +194,7 @@ static gf_status uniform_init_host(const gf_smp_config *cfg, const gfsmp::Config
     if (!params || gfsmp::resolve_config(cfg, entry, &c, why, sizeof why) != GF_OK) return GF_ERR_INVALID;
     const auto draw = [&params](const gfsmp::Config::Block &b) { gfsmp::uniform_draw(b, &params); };
     draw(c.first_block());
+    c.shared_blocks().each_draw(draw);
     for (int l = 1; l <= c.nLevels; ++l) c.level_blocks(l).each_draw(draw);
     draw(c.readout_block());
     return GF_OK;

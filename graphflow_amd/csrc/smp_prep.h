@@ -85,8 +85,12 @@ struct Config {
     // smp_level_neighbourhood.hip): one vector h_l[v] [nChanels] per vertex and level, aggregated over a neighbourhood N_l(v) (adjacency | hop
     // distance <= min(l, max_Radius) | <= l) by a sum or, in form 3, RisiLayer2D; softmax at every level.  Parameters: W1_0 [H][F']; for l =
     // 1..L: W1_l [H][F'], W2_l [H][H]; W [H].  None of the other forms' fields is set: the handle has no fields, rows or per-size blocks.
+    // 4, 5: GRU_GCN_1D, GRU_GCN_2D (GraphFlow/GRU_GCN_1D.h, GRU_GCN_2D.h; smp_level_gru.hip): forms 2 and 3 with a GRU cell as the level's
+    // update and a gated read-out; N_l(v) = hop distance <= min(l, max_Radius) in BOTH (GRU_GCN_2D does read max_Radius).  Parameters, shared
+    // by all levels: W [H][F']; W_z, U_z, W_r, U_r, W_h, U_h, W_g, U_g [H][H] (shared_blocks()); U [H].  The levels own nothing.
     int neighbourhood = 0, max_Radius = 0;
-    int nb_radius(int l) const { return neighbourhood == 1 ? 1 : neighbourhood == 3 || l < max_Radius ? l : max_Radius; }   // of N_l (form 1: the adjacency itself)
+    bool gated() const { return neighbourhood >= 4; }
+    int nb_radius(int l) const { return neighbourhood == 1 ? 1 : neighbourhood == 3 || l < max_Radius ? l : max_Radius; }   // of N_l (form 1: the adjacency itself; 3 alone ignores max_Radius)
     size_t filter_floats(int l) const { return level_blocks(l).size_quad(); }   // of an unrestricted level's filter, per s^2
     bool per_size() const { return first_order || steerable_2d; }   // a handle on the th_* tables, per-size blocks in front of the matrix block
     bool concat() const { return first_order >= 3 || steerable_2d == 2; }   // C_l = 2 C_{l-1}
@@ -131,9 +135,30 @@ struct Config {
             if (bias) f(Block{bias, bias});
         }
     };
+    // The segment all levels share, between first_block() and the levels' own: `count` blocks of one size, each drawn as a Vector (the
+    // gated classes draw through sgd->params[i]).  Empty in every family but the gated neighbourhood forms.
+    struct SharedBlocks {
+        int count = 0;
+        Block each = {0, 0};
+        size_t total() const { return (size_t)count * each.n; }
+        template <class F>
+        void each_draw(F f) const {
+            for (int i = 0; i < count; ++i) f(each);
+        }
+    };
+    SharedBlocks shared_blocks() const {
+        SharedBlocks sb;
+        if (gated()) {   // W_z, U_z, W_r, U_r, W_h, U_h, W_g, U_g
+            const size_t n = (size_t)nChanels * nChanels;
+            sb.count = 8;
+            sb.each = {n, n};
+        }
+        return sb;
+    }
     LevelBlocks level_blocks(int l) const {
         const size_t Cp = (size_t)level_channels(l - 1), Cl = (size_t)level_channels(l);
         LevelBlocks b;
+        if (gated()) return b;   // (every block is shared: shared_blocks())
         auto sizes = [&b](std::initializer_list<LevelBlocks::SizeTerm> t) { for (const LevelBlocks::SizeTerm &x : t) b.size[b.nsize++] = x; };
         auto matrix = [&b](size_t n, size_t div = 0) { b.mat[b.nmat++] = {n, div ? div : n}; };   // (div = 0: a Vector, divided by its own size)
         if (neighbourhood) {   // W1_l [H][F'], W2_l [H][H]: no per-size entries, no bias (l = 0: W1_0 is first_block())
@@ -161,9 +186,9 @@ struct Config {
         }
         return b;
     }
-    Block first_block() const {   // H [C][F (D + 1)]; W1_0 [H][F'] of a neighbourhood form
+    Block first_block() const {   // H [C][F (D + 1)]; W1_0 [H][F'] of a neighbourhood form (a Matrix: 10 x rows), W of a gated one (a Vector)
         const size_t n = (size_t)nChanels * fdim();
-        return {n, neighbourhood ? (size_t)nChanels : n};
+        return {n, neighbourhood && !gated() ? (size_t)nChanels : n};
     }
     // W [readout_rows()][top_channels()] (SMP_2D_ver6_classification.h:211-217), drawn as one Vector; none in a physics tower, which ends in
     // its level features: the head's weights are the caller's
@@ -191,20 +216,22 @@ struct Config {
     int fdim() const { return nFeatures * (nDepth + 1); }
 };
 
-// ---- the flat parameter vector: H, then per level (per-size entries, matrix block, bias), then W -- the registration order of
-// SMP_omega.h:289-295 (= save_model order); Config::level_blocks has what each family puts where ----
+// ---- the flat parameter vector: H, (the shared segment,) then per level (per-size entries, matrix block, bias), then W -- the registration
+// order of SMP_omega.h:289-295 (= save_model order); Config::level_blocks has what each family puts where ----
 inline size_t param_count(const Config &c) {
-    size_t n = c.first_block().n + c.readout_block().n;
+    size_t n = c.first_block().n + c.shared_blocks().total() + c.readout_block().n;
     for (int l = 1; l <= c.nLevels; ++l) n += c.level_blocks(l).total();
     return n;
 }
 // K[l] = the level's matrix block (empty in SMP_1D / ver2: never read; W1_l then W2_l in a neighbourhood form), b[l] = its bias or, where
-// the family has them instead, the first of its per-size entries
+// the family has them instead, the first of its per-size entries; shared (optional) = the first block of Config::shared_blocks()
 template <typename P>
-void view_params(const Config &c, P *base, P **H, std::vector<P *> *K, std::vector<P *> *b, P **W) {
+void view_params(const Config &c, P *base, P **H, std::vector<P *> *K, std::vector<P *> *b, P **W, P **shared = nullptr) {
     P *p = base;
     *H = p;
     p += c.first_block().n;
+    if (shared) *shared = p;
+    p += c.shared_blocks().total();
     K->assign(c.nLevels + 1, nullptr);
     b->assign(c.nLevels + 1, nullptr);
     for (int l = 1; l <= c.nLevels; ++l) {

@@ -948,7 +948,7 @@ gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, c
         t.put(&lists[k].tptr, B.nb_lists[k].tptr);
         t.put(&lists[k].tidx, B.nb_lists[k].tidx);
     }
-    const bool pairs = cfg.neighbourhood == 3;   // RisiLayer2D: A, T, Tt and the three quantities of its closed-form reverse
+    const bool pairs = cfg.neighbourhood == 3 || cfg.neighbourhood == 5;   // RisiLayer2D: A, T, Tt and the three quantities of its closed-form reverse
     for (int l = 0; l <= L; ++l) {
         DevLevel &d = s->lv[l];
         t.alloc(&d.f, nV * H);
@@ -959,6 +959,8 @@ gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, c
         d.nb_ptr = dl.ptr, d.nb_idx = dl.idx, d.nb_tptr = dl.tptr, d.nb_tidx = dl.tidx;
         t.alloc(&d.th_A, nV * H);
         t.alloc(&d.Q, nV * H);
+        if (cfg.gated())   // the GRU cell's gates and what its weight gradients read (smp_level_gru.hip)
+            for (float **p : {&d.gru_z, &d.gru_r, &d.gru_c, &d.gru_q, &d.gru_dz, &d.gru_dr, &d.gru_dc, &d.gru_direct}) t.alloc(p, nV * H);
         if (pairs) {
             t.alloc(&d.th_B, nV * H);
             t.alloc(&d.th_node, nV * H);
@@ -970,6 +972,9 @@ gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, c
     t.alloc(&s->g, (size_t)nMol * H);
     t.alloc(&s->yhat, (size_t)nMol);
     t.alloc(&s->dy, (size_t)nMol);
+    s->gru_s = s->gru_t = s->gru_ds = s->gru_dt = s->gru_acc = nullptr;
+    if (cfg.gated())   // the gated read-out's two factors per vertex and their gradients
+        for (float **p : {&s->gru_s, &s->gru_t, &s->gru_ds, &s->gru_dt}) t.alloc(p, nV * H);
     t.put(&s->top_node_mol, B.nb_vertex_mol);
     t.put(&s->mol_ptr, B.mol_first_vertex);
     if (t.st != GF_OK) return t.st;

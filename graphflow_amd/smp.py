@@ -449,6 +449,25 @@ class SMPNeighbourhood(SMP1D):
         return out
 
 
+class SMPGatedNeighbourhood(SMPNeighbourhood):
+    """Batched GRU_GCN_1D (form "gru_gcn_1d") and GRU_GCN_2D ("gru_gcn_2d") of GraphFlow/GRU_GCN_1D.h, GRU_GCN_2D.h,
+    gf_smp_config.neighbourhood = 4, 5: GCN_1D / GCN_2D's features and aggregates with a GRU cell as the level's update and a gated read-out.
+      h_0[v] = softmax(W x[v]);  n = the aggregate of h_{l-1} over N_l(v) = {u: dist(v, u) <= min(l, max_Radius)} (both forms), hp = h_{l-1}[v]:
+      z = sigmoid(W_z n + U_z hp), r = sigmoid(W_r n + U_r hp), c = tanh(W_h n + U_h (r hp)), h_l[v] = (1 - z) hp + z c;
+      graph_feature = tanh(sum_v sigmoid(W_g h_L[v]) tanh(U_g h_L[v])), predict = <U, graph_feature>, squared loss.
+    Parameters in registration order, shared by all levels: W[H, F']; W_z, U_z, W_r, U_r, W_h, U_h, W_g, U_g [H, H]; U[H].  nLevels = 0 is a
+    model.  nHiddens <= 64.  The optimiser is Momentum: step().  There are no classifiers of these forms."""
+
+    FORMS = {"gru_gcn_1d": 4, "gru_gcn_2d": 5}
+
+    @staticmethod
+    def config(form, nLevels, nHiddens, nFeatures, nDepth, max_nVertices, max_Radius=1):
+        if form not in SMPGatedNeighbourhood.FORMS:
+            raise ValueError("SMPGatedNeighbourhood: form %r (\"gru_gcn_1d\": GRU_GCN_1D, \"gru_gcn_2d\": GRU_GCN_2D)" % (form,))
+        return SMPConfig(nLevels, nHiddens, nFeatures, nDepth, max_nVertices, 0, 0, 0, 0, 0, max_nVertices, 0, 0,
+                         SMPGatedNeighbourhood.FORMS[form], max_Radius)
+
+
 class SMPClassifier(SMPOmega):
     """The classification models of GraphFlow (SMP_2D_ver6_classification: nContractions=10, custom_matmul=True;
     SMP_2D_ver7_classification: 50, True) through gf_smp_create_classifier: the levels of the regression model, read out by

@@ -371,6 +371,23 @@ typedef struct {
      * the neighbour lists and their transposes, dW1_l / dW2_l as deterministic TN products; no atomics.  Refused with GF_ERR_UNSUPPORTED
      * before anything is launched: gf_smp_create_classifier, gf_smp_set_grad_allreduce(smp, 1), gf_smp_dropout_masks,
      * gf_smp_backward_features, gf_smp_prepare_coulomb with a Coulomb matrix.  gf_smp_model_create has no towers of these forms.
+     * neighbourhood = 4: GRU_GCN_1D, 5: GRU_GCN_2D (GraphFlow/GRU_GCN_1D.h, GRU_GCN_2D.h) -- the gated graph networks of the same comparison:
+     * x, dist and the aggregates of forms 2 (4: sum) and 3 (5: RisiLayer2D in the closed form), N_l(v) = { u : dist(v, u) <= min(l, max_Radius) },
+     * v included, in BOTH forms (GRU_GCN_2D does read max_Radius), and a GRU cell as the level's update:
+     *   h_0[v] = softmax(W x[v])
+     *   l = 1..L:  n = the aggregate of h_{l-1}[u] over N_l(v), hp = h_{l-1}[v]
+     *              z = sigmoid(W_z n + U_z hp)   r = sigmoid(W_r n + U_r hp)   c = tanh(W_h n + U_h (r * hp))   h_l[v] = (1 - z) * hp + z * c
+     *   g_v = sigmoid(W_g h_L[v]) * tanh(U_g h_L[v]);  graph_feature = tanh(sum_v g_v);  predict = <U, graph_feature>, squared loss
+     * The parameters are shared by all levels; order (registration and save_model order): W [H][F']; W_z, U_z, W_r, U_r, W_h, U_h, W_g, U_g
+     * [H][H]; U [H] -- H F' + 8 H^2 + H floats whatever nLevels is.  Gradients are the plain derivatives, summed over the levels, except level
+     * 0's softmax (the classes' diagonal rule, as above).  From level 1 on h_l is no softmax vector: T = sum_k h_l[k] is kept per level.
+     * Required, else GF_ERR_INVALID: form 2's rules (max_Radius >= 0 in both forms) and nChanels <= 64 -- the six [H][H | 1] images of a cell
+     * are resident in LDS for the length of a level: 99.8 KB at 64 channels, 396 KB at 128 against 160 KiB per workgroup.  gf_smp_uniform_init_host
+     * draws every block by uniform_init(Vector*) -- the classes initialise through sgd->params[i] -- so the divisor is 10 * the block's size
+     * (10 H F', 10 H^2, 10 H), not form 2's 10 H.  Introspection, the Momentum optimiser and the five GF_ERR_UNSUPPORTED refusals are those of
+     * forms 1 - 3; gf_smp_classifier_config_param_count answers 0.  The level is smp_level_gru.hip: level 0 and the reverse gather are
+     * smp_level_neighbourhood.hip's kernels, one gru_cell_fwd / gru_cell_bwd launch per level, the eight weight gradients deterministic TN
+     * products accumulated over the levels from the top down; no atomics.
      * 0 (a zero-initialised tail): everything as described above, max_Radius is not read. */
     int neighbourhood, max_Radius;
 } gf_smp_config;
