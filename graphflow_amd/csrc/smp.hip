@@ -309,10 +309,13 @@ __global__ __launch_bounds__(256) void readout_nodes_panels(const float *__restr
 }
 
 // one workgroup per molecule: g = sum_v vf (SumVectors), y = <g, W> (InnerProduct.h:39-46), loss (SquaredLoss.h:45-53)
+// g_out / y_out (or null): the caller's graph_feature / predict, written here beside the handle's own g / yhat (which the reverse sweep
+// reads) -- no copy kernels behind the read-out
 __global__ void readout_molecules(const float *__restrict__ vf, const int *__restrict__ mol_ptr,
                                   const int *__restrict__ mol_nodes, const float *__restrict__ W,
                                   const float *__restrict__ target, float *__restrict__ g, float *__restrict__ yhat,
-                                  float *__restrict__ loss, float *__restrict__ dy, int C) {
+                                  float *__restrict__ loss, float *__restrict__ dy, int C, float *__restrict__ g_out,
+                                  float *__restrict__ y_out) {
     __shared__ float red[256];
     const int m = blockIdx.x;
     float part = 0.f;
@@ -320,6 +323,7 @@ __global__ void readout_molecules(const float *__restrict__ vf, const int *__res
         float acc = 0.f;
         for (int k = mol_ptr[m]; k < mol_ptr[m + 1]; ++k) acc += vf[(size_t)mol_nodes[k] * C + f];
         g[(size_t)m * C + f] = acc;
+        if (g_out) g_out[(size_t)m * C + f] = acc;
         part += acc * W[f];
     }
     red[threadIdx.x] = part;
@@ -331,6 +335,7 @@ __global__ void readout_molecules(const float *__restrict__ vf, const int *__res
     if (threadIdx.x == 0) {
         const float y = red[0], t = target ? target[m] : 0.f;
         yhat[m] = y;
+        if (y_out) y_out[m] = y;
         if (loss) loss[m] = 0.5f * (y - t) * (y - t);
         dy[m] = y - t;  // SquaredLoss::backward: predict->gradient += predict - target
     }
@@ -814,7 +819,7 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
     if (st != GF_OK) return st;
     GF_LAUNCH(ctx, "smp_bias_lrelu", bias_lrelu_forward, dim3(grid_for((size_t)nV * C)), dim3(256), 0, s->lv[0].f, (const float *)nullptr, C,
               (size_t)nV * C, s->cfg.level_slope());
-    for (int l = 0; l <= L; ++l) s->lv[l].psum_ready = s->lv[l].pmax_ready = false;
+    for (int l = 0; l <= L; ++l) s->lv[l].psum_ready = s->lv[l].pmax_ready = s->lv[l].sgn_ready = false;
     s->bwd_consumed = false;
     st = dup_level(s, 0);   // (SMP_2D_ver6 on the 18-slice level: channels [C, 2C) <- the transposed matrices; level 0: copies)
     if (st != GF_OK) return st;
@@ -856,9 +861,11 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
             st = readout_classes_forward(s, W, targets, predict, loss);
             if (st != GF_OK) return st;
         } else {
+            // (predict and graph_feature are written by the kernel itself; a caller's buffer that IS the handle's own is written once)
+            float *g_out = graph_feature == s->g ? nullptr : graph_feature, *y_out = predict == s->yhat ? nullptr : predict;
             GF_LAUNCH(ctx, "smp_readout_mol", readout_molecules, dim3(B.nMol), dim3(256), 0, s->vf, s->mol_ptr, s->mol_nodes, W, targets, s->g, s->yhat,
-                      loss, s->dy, CL);
-            if (predict) GF_HIP_TRY(ctx, hipMemcpyAsync(predict, s->yhat, sizeof(float) * B.nMol, hipMemcpyDeviceToDevice, ctx->stream));
+                      loss, s->dy, CL, g_out, y_out);
+            graph_feature = nullptr;
         }
     }
     const size_t gwidth = s->cfg.physics ? feature_width(s->cfg) : (size_t)CL;

@@ -1529,7 +1529,7 @@ static bool smp_extras_in_kernel(const gf_smp *s, int l) {
     return s->n_extra && (C == 32 || C == 16) && smp_c64_kernels(s) && s->lv[l].wimg_ready && s->lv[l].wimg && !s->drop_on && smp_split_products(s->ctx) &&
            s->lv[l].trow;
 }
-gf_status smp_fused_backward_level_grouped(gf_smp *s, int l, float *dKl, float *dbl);
+gf_status smp_fused_backward_level_grouped(gf_smp *s, int l, float *dKl, float *dbl, const float *dz_vec = nullptr);
 
 // every level's block-permuted weight copy in one launch (gf_smp_forward, before the first level)
 gf_status smp_fused_stack_all(gf_smp *s, const std::vector<const float *> &K) {
@@ -1810,7 +1810,9 @@ gf_status smp_fused_forward_level(gf_smp *s, int l, const float *Kl, const float
 //   ONE TN launch               dK15, dK16, Vt^T dVout, St^T dSout, each split over its own rows    (was 4 + their folds)
 //   smp_fold_level              every image folded, un-stacked and added into dK_l / db_l          (was ~8 launches)
 //   row-panel products          dT
-gf_status smp_fused_backward_level_grouped(gf_smp *s, int l, float *dKl, float *dbl) {
+// dz_vec (or null): combine-backward's gradient was this per-node vector alone and the level's sign words are this pass's -- the backward
+// products then form the dz block of dO themselves instead of reading it, where the row-class kernel runs them
+gf_status smp_fused_backward_level_grouped(gf_smp *s, int l, float *dKl, float *dbl, const float *dz_vec) {
     gf_ctx *ctx = s->ctx;
     const gfsmp::LevelLayout &h = s->lay.level[l];
     const gf_smp::DevLevel &d = s->lv[l], &pv = s->lv[l - 1];
@@ -1967,9 +1969,13 @@ gf_status smp_fused_backward_level_grouped(gf_smp *s, int l, float *dKl, float *
     // table gradients dT from dO
     if (d.fwd_c64) {
         // (with the consumer gather reading dT, the gradients of the structurally-zero S_ab / T6 rows have no reader: not written)
+        const int nx = (ocols == 2 && smp_extras_in_kernel(s, l)) ? 3 : 0;
+        const RowpanelDz dz = {dz_vec, d.sgn, d.rowcls_node};
+        const bool form_dz = dz_vec && d.rowcls_node && ocols == 2 &&
+                             smp_rowpanel_dz_applies(ctx, rows, d.trow, d.trowf, smp_fused_gather_enabled(s, l), C, drop ? 8 : 2, nx, d.rowcls);
         st = smp_rowpanel_products_c64(ctx, false, dO, drop ? d.rowfac8 : d.rowscale, d.Wst, dT, rows, ocols == 2 ? d.trow : nullptr, d.trowf,
-                                       smp_fused_gather_enabled(s, l), d.wimg_ready ? d.wimg : nullptr, C, drop ? 8 : 2,
-                                       (ocols == 2 && smp_extras_in_kernel(s, l)) ? 3 : 0, d.rowcls);
+                                       smp_fused_gather_enabled(s, l), d.wimg_ready ? d.wimg : nullptr, C, drop ? 8 : 2, nx, d.rowcls,
+                                       form_dz ? &dz : nullptr);
         x_bwd_done = ocols == 2 && smp_extras_in_kernel(s, l);
         if (st != GF_OK) return st;
     } else {
@@ -2101,7 +2107,9 @@ gf_status smp_fused_backward_level(gf_smp *s, int l, const float *Kl, float *dKl
             }
         }
         (void)Kl;
-        return smp_fused_backward_level_grouped(s, l, dKl, dbl);
+        // the top level of a plain model without nodes above 32 positions: dz[row] = node_df[node(row)] * slope(sign words of the row)
+        const bool vec_only = !dfrows && node_df && big.nodes == 0 && smp_sign_mask(s, l);
+        return smp_fused_backward_level_grouped(s, l, dKl, dbl, vec_only ? node_df : nullptr);
     }
     s->lv[l].dz_rows = (long long)h.quad_node.size();
     s->lv[l].dz_rows2 = 0;

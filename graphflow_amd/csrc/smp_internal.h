@@ -43,19 +43,32 @@ gf_status gemm_grouped_rows(gf_ctx *ctx, bool ta, bool tb, const GemmSpec *specs
 gf_status gemm_grouped_splitk(gf_ctx *ctx, const GemmSpec *specs, int n, int rows, float *dest, int accumulate);
 // trow != nullptr: compact O / dO layout ([O_loc | U], 2C wide) with the transposed-row gather inside the product (see kernel)
 // trowf (optional): the level's packed table with the presence bits of the S_ab / T6 blocks (DevLevel::trowf)
+// dz (backward, C = 64, the row-class kernel -- smp_rowpanel_dz_applies; else null): the L block of dO is formed by the kernel from the
+// read-out's per-node vector and the level's sign words instead of read (see smp_rowpanel_split, DZ)
+struct RowpanelDz {
+    const float *node_df = nullptr;   // [nodes][64]
+    const unsigned *sgn = nullptr;    // [rows][2]
+    const int *ent_node = nullptr;    // [class-list entries] node of the entry's row
+};
 gf_status smp_rowpanel_products_c64(gf_ctx *ctx, bool forward, const float *A, const float *rowscale, const float *Wst, float *Out,
                                     int rows, const int *trow, const int *trowf = nullptr, bool skip_zero_grads = false,
                                     const void *wimg = nullptr, int C = 64,   // C = 32 (round 4): split products with prebuilt images only
                                     int nf = 2, int nx = 0,   // row factors per row of `rowscale`: 2 = (tot, tr); 8 = one per product (slice dropout, C = 32)
-                                    const int *rowcls = nullptr);   // the table's row classes (C = 64 with trowf: panels of one class, see smp_rowpanel_split)
+                                    const int *rowcls = nullptr,   // the table's row classes (C = 64 with trowf: panels of one class, see smp_rowpanel_split)
+                                    const RowpanelDz *dz = nullptr);
+// will a backward call with these arguments run the row-class kernel (the one that can form dz itself)?
+bool smp_rowpanel_dz_applies(const gf_ctx *ctx, int rows, const int *trow, const int *trowf, bool skip_zero_grads, int C, int nf, int nx, const int *rowcls);
 // the compact-layout products on the f16 matrix pipe with two-half fp32 operands (smp_level_c64_split.hip; GF_SMP_SPLIT=0: fp32 MFMA)
 bool smp_split_products(const gf_ctx *ctx);
 gf_status smp_rowpanel_split_c64(gf_ctx *ctx, bool forward, const float *A, const float *rowscale, const float *Wst, float *Out,
                                  int rows, const int *trow, int cus, const int *trowf = nullptr, bool skip_zero_grads = false,
-                                 const void *wimg = nullptr, int C = 64, int nf = 2, int nx = 0, const int *rowcls = nullptr);
+                                 const void *wimg = nullptr, int C = 64, int nf = 2, int nx = 0, const int *rowcls = nullptr,
+                                 const RowpanelDz *dz = nullptr);
 // the row classes of a level's packed table (smp_prepare.hip: row_class_count): buffer size in ints, and the builder
 size_t smp_row_class_ints(int rows);
 gf_status smp_build_row_classes(gf_ctx *ctx, hipStream_t stream, const int *trowf, int rows, int *buf);
+// ... and the node of every entry of the two lists (rows + 64 ints), for the kernel that forms dz from a per-node vector
+gf_status smp_build_row_class_nodes(gf_ctx *ctx, hipStream_t stream, const int *buf, int rows, const long long *node_row, int nodes, int *ent_node);
 // the split kernels' weight images of a level (both directions), built once per forward pass (smp_level_c64_split.hip)
 size_t smp_split_image_bytes(int C = 64);   // (C = 128: four sets, one per 64 x 64 sub-block of the 128 x 128 weight blocks)
 gf_status smp_split_build_images(gf_ctx *ctx, const float *const *Wst, void *const *img, int n, int C = 64, const float *const *X = nullptr);
@@ -191,6 +204,10 @@ struct gf_smp {
         float *psum = nullptr;     // top level, C = 64: [fwd_npanels][64] column sums of the row panels of f_L (readout)
         float *dshl = nullptr;     // towers: [nodes][C] gradient of the level's read-out per node (the fused level's combine-backward adds it)
         bool psum_ready = false;   // ... written by this forward pass
+        // C = 64: [rows][2] sign words of z_l, written by the panel combine-forward (bit c of word h: z[row][32 h + c] > 0).  The reverse
+        // sweep takes LeakyReLU'(f_l) from them instead of reading f_l (smp_sign_mask).  Rows of nodes above 32 positions: not written.
+        unsigned *sgn = nullptr;
+        bool sgn_ready = false;    // ... written by this forward pass
         // per-channel maxima for the weight gradients' column exponents (smp_level_c64_split.hip: WgradScales::chan):
         float *pmax = nullptr;     // [fwd_npanels][64] largest |f_l| of every row panel, left by combine-forward (levels below the top)
         float *dzmax = nullptr;    // [max(quads, row panels)][64] largest |dz| of every workgroup / panel of combine-backward
@@ -204,6 +221,7 @@ struct gf_smp {
         bool fwd_c64 = false;  // the last forward ran this level's products on the dedicated row-panel kernels (compact O = [O_loc | U])
         int *trowf = nullptr;  // [rows] trow | bit 31: rowflag of the row | bit 30: rowflag of the transposed row (smp_rowpanel_split)
         int *rowcls = nullptr;  // C = 64: the rows with and without S_ab / T6 data as two padded lists (smp_prepare.hip: row_class_count)
+        int *rowcls_node = nullptr;  // ... the node of every list entry (top level of a plain model: the backward products form dz themselves)
         float max_tot = 0.f, max_tr = 0.f;  // largest |tot|, |tr| of the level's row factors (split-operand weight gradients' column bounds)
         const unsigned *row_max = nullptr;  // the same two as float bits in device memory when the tables are built there
         long long *pair_src_pair = nullptr, *cons_row = nullptr, *cons_pair = nullptr;  // compact diagonal path (smp_prep.h)
@@ -313,6 +331,12 @@ inline bool smp_panel_channels(int C) { return C == 64 || C == 32 || C == 16; }
 // only then: a handle prepared under =0 is what it was before the path existed -- and per call: a pass runs the sub-block kernels when
 // neither saw the 0.
 inline bool smp_c128_switch() { return !env_is("GF_SMP_C128", '0'); }
+// The reverse sweep of fused level l takes LeakyReLU'(f_l) from the sign words this pass's panel combine-forward left (DevLevel::sgn)
+// instead of reading f_l.  64 channels; not where f_l's upper channels were overwritten after combine-forward (dup_level: SMP_2D_ver6 on
+// the 18-slice level).  GF_SMP_SIGN_MASK=0 (read per call: the parity test switches it): f_l is read, dz is stored and read, as before.
+inline bool smp_sign_mask(const gf_smp *s, int l) {
+    return s->cfg.nChanels == 64 && !s->dup_channels && s->lv[l].sgn && s->lv[l].sgn_ready && !env_is("GF_SMP_SIGN_MASK", '0');
+}
 // Largest receptive field a fused level takes (round 6): up to 32 positions every kernel of the level; 33 .. 64 at C = 64 -- the few such
 // nodes of a level (a 48-atom molecule's level-3 fields reach 35) run tables-forward and the two combine steps on workgroup kernels,
 // everything else is row-based and does not care (smp_fused.hip: big_part)

@@ -53,6 +53,9 @@ __device__ __forceinline__ void ff_st1s(__amdgpu_buffer_rsrc_t r, int voff, floa
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, 0, (GF_NT_SITES & 16) ? 2 : 0);
 }
 
+// v_writelane_b32: a wave-uniform value into ONE lane of a vector register (this hipcc has no builtin of that name; the intrinsic by its own)
+extern "C" __device__ int ff_writelane(int value, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
+
 // pan[p] = {first row of the panel, rows | s << 8 | groups << 16 | x0 << 24, first row of the node, first pair of the node}
 // (x0 = index x of the panel's first row group inside its node); pan_node[p] = the node
 // ---------------------------------------------------------------------------------------------------------------
@@ -73,7 +76,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
     // rows of f -- the readout's per-node sums (ShrinkTensor, SMP_omega.h:671-676) then read 22 MB of partials instead of f_L again
     float *__restrict__ pmax,  // pmax (or null): [npanels][64] largest |f| per column of the panel's rows (the level above scales the
     // columns of its weight-gradient operands with the level's per-channel maxima: WgradScales::chan)
-    const float *__restrict__ nodefac) {  // (or null) slice dropout: [nodes][18] factors; the compact products G15 / G16 take theirs here
+    const float *__restrict__ nodefac,   // (or null) slice dropout: [nodes][18] factors; the compact products G15 / G16 take theirs here
+    unsigned *__restrict__ sgn) {  // sgn (CB = 64, or null): [rows][2] sign words of z -- bit c of word h of a row is z[row][32 h + c] > 0, which is
+    // f[row][32 h + c] > 0 (the slope is positive); combine-backward and the top level's backward products take LeakyReLU' from it
     const int lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
     unsigned blk;
     {
@@ -181,17 +186,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
         }
     }
     float c0 = 0.f, c1 = 0.f, x0m = 0.f, x1m = 0.f;
+    // the panel's sign words: lane j ends up with word (j & 1) of panel row j >> 1 -- the ballot of register r over a column half is that
+    // half's word of rows (r & 3) + 8 (r >> 2) (low 32 lanes) and + 4 (high 32 lanes), the compare is the one LeakyReLU selects on, and
+    // each word goes into its lane with one v_writelane; one 256-byte store per panel
+    const int srow = lane >> 1;
+    int sword = 0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int rr = (r & 3) + 8 * (r >> 2) + 4 * lh;
         const int vo = rr < nrows ? (P.x + rr) * FB + colb : kFfOor;
         const float z0 = m0[r], z1 = m1[r];
+        if constexpr (TWO) {
+            const unsigned long long b0 = __ballot(z0 > 0.f), b1 = __ballot(z1 > 0.f);
+            const int ra = (r & 3) + 8 * (r >> 2);
+            sword = ff_writelane((int)(unsigned)b0, 2 * ra, sword);
+            sword = ff_writelane((int)(unsigned)b1, 2 * ra + 1, sword);
+            sword = ff_writelane((int)(unsigned)(b0 >> 32), 2 * ra + 8, sword);
+            sword = ff_writelane((int)(unsigned)(b1 >> 32), 2 * ra + 9, sword);
+        }
         const float f0 = z0 > 0.f ? z0 : kAlphaFf * z0, f1 = z1 > 0.f ? z1 : kAlphaFf * z1;
         ff_st1s(rF, vo, f0);
         if constexpr (TWO) ff_st1s(rF, vo + 128, f1);
         if (rr < nrows) {   // (rows in register order: a fixed order)
             c0 += f0, c1 += f1;
             x0m = fmaxf(x0m, fabsf(f0)), x1m = fmaxf(x1m, fabsf(f1));
+        }
+    }
+    if constexpr (TWO) {
+        if (sgn) {  // (uniform; rows past the panel store nothing)
+            const __amdgpu_buffer_rsrc_t rS = ff_rsrc(sgn, (size_t)rows * 8);
+            __builtin_amdgcn_raw_buffer_store_b32((unsigned)sword, rS, srow < nrows ? (P.x + srow) * 8 + (lane & 1) * 4 : kFfOor, 0, 0);
         }
     }
     if (psum) {  // (uniform)
@@ -217,10 +241,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
 //               the three weights of an input row are what ITS lane holds for the forward pass (r[y], A+[x, y]), read with v_readlane
 // and the per-column maxima of |dz| over the panel (the weight gradients' column exponents).  Same sums per output element as
 // smp_combine_bwd (fixed order: the MFMA's k order), held to it by the parity tests (GF_SMP_ROWPANEL=0 runs smp_combine_bwd).
+// SGN (CB = 64): LeakyReLU'(f) comes from the sign words combine-forward left (`sgn`, 8 bytes per row) and f is not read: f > 0 exactly
+// where z > 0, so the slopes -- and every bit of the results -- are those of the build that reads f (GF_SMP_SIGN_MASK=0 runs that one).
 // ---------------------------------------------------------------------------------------------------------------
-template <int CB>
+// NODF (SGN): no row gradient dF either (the top level of a plain model: node_dF alone) -- its thirty-two requests, which a null dF answers
+// with zeros through an empty descriptor, are not issued; dz = (0 + node_dF) * slope, the sum they gave.
+template <int CB, bool SGN = false, bool NODF = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) void smp_combine_bwd_panels(
-    const float *__restrict__ F, const float *__restrict__ dF,   // dF null: the gradient is node_dF's vector at every row of the node
+    const float *__restrict__ F, const unsigned *__restrict__ sgn,
+    const float *__restrict__ dF,   // dF null: the gradient is node_dF's vector at every row of the node
     const float *__restrict__ node_dF,                            // [nodes][CB] or null; with dF: both are added (a tower's level below the top)
     float *__restrict__ dO, const int4 *__restrict__ pan, const int *__restrict__ pan_node, int npanels, int rows,
     const float *__restrict__ adj, const float *__restrict__ rsum, long long pairs, float *__restrict__ dVout, float *__restrict__ dSpart,
@@ -241,6 +270,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
     const bool rowok = li < nrows;
     const int row = P.x + (rowok ? li : nrows - 1);
     constexpr bool TWO = CB == 64;
+    static_assert(!SGN || TWO, "sign words: 64 channels");
+    static_assert(!NODF || SGN, "");
     constexpr int OB = 2 * CB * 4, FB = CB * 4;
     const __amdgpu_buffer_rsrc_t rF = ff_rsrc(F, (size_t)rows * CB * sizeof(float));
     const __amdgpu_buffer_rsrc_t rG = ff_rsrc(dF ? dF : F, dF ? (size_t)rows * CB * sizeof(float) : 0);   // (no dF: every load returns 0)
@@ -252,15 +283,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
     const int colb = colok ? li * 4 : kFfOor;
     // every operand of the panel, requested up front
     f16v f0, f1, g0, g1;
+    unsigned sword = 0u;   // SGN: lane j holds word (j & 1) of panel row j >> 1 (rows past the panel: 0, their dz is zeroed below)
+    if constexpr (SGN) {
+        const __amdgpu_buffer_rsrc_t rS = ff_rsrc(sgn, (size_t)rows * 8);
+        sword = __builtin_amdgcn_raw_buffer_load_b32(rS, (lane >> 1) < nrows ? (P.x + (lane >> 1)) * 8 + (lane & 1) * 4 : kFfOor, 0, 0);
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int rr = (r & 3) + 8 * (r >> 2) + 4 * lh;
         const int vo = rr < nrows ? (P.x + rr) * FB + colb : kFfOor;
-        f0[r] = ff_ld1s(rF, vo);
-        g0[r] = ff_ld1s(rG, vo);
+        if constexpr (!SGN) f0[r] = ff_ld1s(rF, vo);
+        g0[r] = NODF ? 0.f : ff_ld1s(rG, vo);
         if constexpr (TWO) {
-            f1[r] = ff_ld1s(rF, vo + 128);
-            g1[r] = ff_ld1s(rG, vo + 128);
+            if constexpr (!SGN) f1[r] = ff_ld1s(rF, vo + 128);
+            g1[r] = NODF ? 0.f : ff_ld1s(rG, vo + 128);
         } else {
             f1[r] = g1[r] = 0.f;
         }
@@ -285,7 +321,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
     for (int r = 0; r < 16; ++r) {
         const int rr = (r & 3) + 8 * (r >> 2) + 4 * lh;
         const bool ok = rr < nrows;
-        const float a = (g0[r] + gn0) * (f0[r] > 0.f ? 1.f : kAlphaFf), b = (g1[r] + gn1) * (f1[r] > 0.f ? 1.f : kAlphaFf);
+        bool up0, up1;   // z > 0 at the lane's column of row rr, per column half
+        if constexpr (SGN) {
+            const int ra = (r & 3) + 8 * (r >> 2);   // row of the low lane half; the high half holds row ra + 4
+            // (the two rows' words of a column half, low lanes' row first, ARE the wave's lane mask of that half: bit 32 lh + li)
+            const unsigned a0 = __builtin_amdgcn_readlane(sword, 2 * ra), a1 = __builtin_amdgcn_readlane(sword, 2 * ra + 1);
+            const unsigned b0 = __builtin_amdgcn_readlane(sword, 2 * ra + 8), b1 = __builtin_amdgcn_readlane(sword, 2 * ra + 9);
+            up0 = __builtin_amdgcn_inverse_ballot_w64((unsigned long long)a0 | ((unsigned long long)b0 << 32));
+            up1 = __builtin_amdgcn_inverse_ballot_w64((unsigned long long)a1 | ((unsigned long long)b1 << 32));
+        } else {
+            up0 = f0[r] > 0.f;
+            up1 = f1[r] > 0.f;
+        }
+        const float a = (g0[r] + gn0) * (up0 ? 1.f : kAlphaFf), b = (g1[r] + gn1) * (up1 ? 1.f : kAlphaFf);
         z0[r] = ok ? a : 0.f;
         z1[r] = ok ? b : 0.f;
         x0m = fmaxf(x0m, fabsf(z0[r]));
@@ -406,11 +454,12 @@ gf_status smp_combine_fwd_panels_c64(gf_smp *s, int l, const float *O, const flo
 #define GF_CFP_LAUNCH(CBv)                                                                                                               \
     GF_LAUNCH(ctx, "smpf_combine_fwd", (smp_combine_fwd_panels<CBv>), dim3((unsigned)((npanels + 3) / 4)), dim3(256), 0, O, d.f, d.fwd_pan,  \
               d.fwd_pan_node, npanels, (int)h.rows, d.fwd_goff, d.Gc, (long long)s->lay.level[l - 1].pairs, d.adj, d.rsum, d.Vout,          \
-              (long long)h.pairs, d.Sout, bias, psum, pmax, nodefac)
+              (long long)h.pairs, d.Sout, bias, psum, pmax, nodefac, s->cfg.nChanels == 64 ? d.sgn : (unsigned *)nullptr)
     if (s->cfg.nChanels == 64) GF_CFP_LAUNCH(64);
     else if (s->cfg.nChanels == 16) GF_CFP_LAUNCH(16);
     else GF_CFP_LAUNCH(32);
 #undef GF_CFP_LAUNCH
+    s->lv[l].sgn_ready = s->cfg.nChanels == 64 && d.sgn != nullptr;
     return GF_OK;
 }
 
@@ -421,10 +470,13 @@ gf_status smp_combine_bwd_panels_c64(gf_smp *s, int l, const float *dfrows, cons
     const gfsmp::LevelLayout &h = s->lay.level[l];
     const int npanels = d.fwd_npanels;
     if (npanels < 1) return GF_OK;
-#define GF_CBP_LAUNCH(CBv)                                                                                                              \
-    GF_LAUNCH(ctx, "smpf_combine_bwd", (smp_combine_bwd_panels<CBv>), dim3((unsigned)((npanels + 3) / 4)), dim3(256), 0, d.f, dfrows, node_df, dO, \
+#define GF_CBP_LAUNCH(...)                                                                                                              \
+    GF_LAUNCH(ctx, "smpf_combine_bwd", (smp_combine_bwd_panels<__VA_ARGS__>), dim3((unsigned)((npanels + 3) / 4)), dim3(256), 0, d.f, d.sgn, dfrows, node_df, dO, \
               d.fwd_pan, d.fwd_pan_node, npanels, (int)h.rows, d.adj, d.rsum, (long long)h.pairs, d.dVout, d.dSpart, d.dbpart, dzmax)
-    if (s->cfg.nChanels == 64) GF_CBP_LAUNCH(64);
+    // (with the sign words and no row gradient -- the top level of a plain model -- the kernel requests no streamed operand at all)
+    if (s->cfg.nChanels == 64 && smp_sign_mask(s, l) && !dfrows) GF_CBP_LAUNCH(64, true, true);
+    else if (s->cfg.nChanels == 64 && smp_sign_mask(s, l)) GF_CBP_LAUNCH(64, true);
+    else if (s->cfg.nChanels == 64) GF_CBP_LAUNCH(64);
     else if (s->cfg.nChanels == 16) GF_CBP_LAUNCH(16);
     else GF_CBP_LAUNCH(32);
 #undef GF_CBP_LAUNCH

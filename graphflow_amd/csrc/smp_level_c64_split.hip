@@ -222,15 +222,21 @@ __global__ __launch_bounds__(kSpThreads) void smp_split_weight_images_c128(Split
 // W = 2 (C = 128, CB = 64): one (i, j) pass of the four a 128 x 128 product is made of -- the rows are W times as wide, a block starts at
 // CB W blk, and the pass reads columns [a_off, +64) of its operand blocks and writes columns [out_off, +64) of its output blocks with the
 // weight images of sub-block (i, j).  ACC: the pass of the second reduction half -- its accumulators start from what the first pass stored.
-template <bool FWD, bool MASK, int CB = 64, int NF = 2, int NX = 0, bool CLS = false, int W = 1, bool ACC = false>
+// DZ (CLS): the L block of dO is not read.  At the top level of a plain model it is dz[row] = node_df[node(row)] * LeakyReLU'(z[row]) -- the
+// read-out's vector of the row's node (dz.node_df, [nodes][64]: 4 MB at cfg3, L2 hits) times the slope from the row's sign words (dz.sgn,
+// smp_combine_fwd_panels) -- and the kernel forms the lane's 32 floats itself: the same request shape, the operands and the product of
+// combine-backward ((0 + v) * slope), the same bits.  dz.ent_node: the node of every class-list entry (smp_build_row_class_nodes).
+template <bool FWD, bool MASK, int CB = 64, int NF = 2, int NX = 0, bool CLS = false, int W = 1, bool ACC = false, bool DZ = false>
 __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float *__restrict__ A, const float *__restrict__ rs,
                                                                      const float *__restrict__ Wst, float *__restrict__ Out, int rows,
                                                                      const int *__restrict__ trow, int store_mask,
                                                                      const uint4 *__restrict__ wimg,    // or null: this direction's
                                                                      // images, built by smp_split_weight_images
                                                                      const int *__restrict__ rcls,      // CLS: the row classes
-                                                                     int a_off, int out_off) {          // W > 1: see above
+                                                                     int a_off, int out_off,            // W > 1: see above
+                                                                     RowpanelDz dz) {                   // DZ: see above
     static_assert(W == 1 || (CB == 64 && NF == 2 && NX == 0 && !CLS), "sub-block passes: 64-channel panels, plain row factors");
+    static_assert(!DZ || CLS, "dz formed in the kernel: the row-class panels");
     static_assert(W > 1 || !ACC, "");
     static_assert(!CLS || (!FWD && MASK && CB == 64 && NF == 2 && NX == 0), "row classes: the masked backward products at 64 channels");
     constexpr int LDA = (FWD ? 4 * CB : 2 * CB) * W, LDOUT = (FWD ? 2 * CB : 4 * CB) * W, BS = CB * W;   // BS: floats from a block to the next
@@ -562,11 +568,39 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
         // the lane's entry of panel q (panels past the end read the last entry: requests made for them are never used): the packed
         // word, and through *rw the row with bit 31 set on a padding entry.  Fetched a panel ahead, like fetch_trow -- and the row with it,
         // so no block request waits for an index.
+        int nd_next = 0;   // DZ: the node of the lane's row of the next panel, fetched with its entry
         auto fetch_entry = [&](int q, int *rw) {
             const int i = q * 32 + li;
             const int2 e = ent[i < n_ent ? i : n_ent - 1];
+            if constexpr (DZ) nd_next = dz.ent_node[i < n_ent ? i : n_ent - 1];
             *rw = e.x;
             return e.y;
+        };
+        // DZ: the request for block L of `row` becomes the lane's 32 floats of the node's vector (a row no source covers: the zero page, as
+        // load_raw_at) and the row's sign word of the lane's column half; dz_scale turns them into dz when the block is split
+        unsigned sg_next = 0u;
+        auto load_L_at = [&](Raw &R, int row, bool present) {
+            if constexpr (!DZ) {
+                load_raw_at(R, row, 0, present);
+            } else {
+                __builtin_amdgcn_sched_barrier(0);
+                asm volatile("" : "+v"(row));
+                unsigned long long sa = (unsigned long long)(dz.node_df + (size_t)nd_next * CB + VPL * lh);
+                sa = present ? sa : (unsigned long long)sp_zero_page;
+                const GF_GLOBAL float *src = (const GF_GLOBAL float *)sa;
+#pragma unroll
+                for (int q = 0; q < VPL / 4; ++q) R.a[q] = gf_ld_g<1>(reinterpret_cast<const GF_GLOBAL f4v *>(src + 4 * q));
+                sg_next = dz.sgn[(size_t)row * 2 + lh];
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+        auto dz_scale = [&](Raw &R, unsigned sg) {
+            if constexpr (DZ) {
+#pragma unroll
+                for (int q = 0; q < VPL / 4; ++q)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) R.a[q][j] = (0.f + R.a[q][j]) * (((sg >> (4 * q + j)) & 1u) ? 1.f : 0.01f);
+            }
         };
         auto e_row = [](int rw) { return rw & 0x1fffffff; };
         auto scale_at = [&](int row) {
@@ -599,15 +633,17 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
         int rnext, tn = fetch_entry(p, &rnext);
         Raw Ra, Rb;   // on entry of a panel: Ra = L, Rb = dU (of a row no source covers: zeros, see `panel`)
         load_raw_at(Rb, e_row(rnext), 1, t_bc(tn));
-        load_raw_at(Ra, e_row(rnext), 0, t_bc(tn));
+        load_L_at(Ra, e_row(rnext), t_bc(tn));
         auto panel_own = [&](int q) {   // the program of `panel` below, its rows taken from the list; every row stores all four blocks
             const int qn = q + nwaves, rcur = rnext, tcur = tn;
+            const unsigned sg = sg_next;
             tn = fetch_entry(qn, &rnext);
             const RowFac sc = scale_at(e_row(rcur));
             post_rows(rcur);
             f16v acc0, acc1;
             Spl X, Y, Z;
             float iX, iY, iZ;
+            dz_scale(Ra, sg);
             split_blk(Ra, X, iX);
             split_blk(Rb, Y, iY);
             clear(acc0, acc1);
@@ -627,22 +663,24 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
             prod(X, iX * sc.f[2], 2, acc0, acc1);
             prod(Y, iY * sc.f[5], 5, acc0, acc1);
             split_blk(Ra, Z, iZ);
-            load_raw_at(Ra, e_row(rnext), 0, t_bc(tn));    // L of the next panel
+            load_L_at(Ra, e_row(rnext), t_bc(tn));         // L of the next panel
             prod(Z, iZ * sc.f[7], 7, acc0, acc1);
             store_rows(0, acc0, acc1);
         };
         auto panel_absent = [&](int q) {   // rows whose S_ab / T6 blocks are structural zeros: dT10 = 4 and dS_bc = 1 + 6 are all they store
             const int qn = q + nwaves, rcur = rnext;
+            const unsigned sg = sg_next;
             tn = fetch_entry(qn, &rnext);
             const RowFac sc = scale_at(e_row(rcur));
             post_rows(rcur);
             f16v acc0, acc1;
             Spl X, Y;
             float iX, iY;
+            dz_scale(Ra, sg);
             split_blk(Ra, X, iX);
             split_blk(Rb, Y, iY);
             load_raw_at(Rb, e_row(rnext), 1, t_bc(tn));
-            load_raw_at(Ra, e_row(rnext), 0, t_bc(tn));
+            load_L_at(Ra, e_row(rnext), t_bc(tn));
             clear(acc0, acc1);
             prod(X, iX * sc.f[4], 4, acc0, acc1);
             store_rows(3, acc0, acc1);
@@ -1673,14 +1711,15 @@ struct RowpanelArgs {
     int store_mask;
     const uint4 *img;   // this direction's weight images, or null
 };
-template <bool F, bool M, int CB, int NF, int NX, bool CLS = false, int W = 1, bool ACC = false>
-static gf_status launch_rowpanel_split(gf_ctx *ctx, const RowpanelArgs &a, const int *rcls = nullptr, int a_off = 0, int out_off = 0) {
+template <bool F, bool M, int CB, int NF, int NX, bool CLS = false, int W = 1, bool ACC = false, bool DZ = false>
+static gf_status launch_rowpanel_split(gf_ctx *ctx, const RowpanelArgs &a, const int *rcls = nullptr, int a_off = 0, int out_off = 0,
+                                       RowpanelDz dz = RowpanelDz()) {
     const size_t lds = 2 * (size_t)(8 + NX) * (CB >= 32 ? CB / 32 : 1) * (CB / 16) * 64 * 16 + 32 * sizeof(float) + (kSpThreads / 64) * 32 * sizeof(float) +
                        (CLS ? (kSpThreads / 64) * 32 * sizeof(float *) : 0);
-    gf_status st = opt_in_lds(ctx, smp_rowpanel_split<F, M, CB, NF, NX, CLS, W, ACC>, lds);
+    gf_status st = opt_in_lds(ctx, smp_rowpanel_split<F, M, CB, NF, NX, CLS, W, ACC, DZ>, lds);
     if (st != GF_OK) return st;
-    GF_LAUNCH(ctx, F ? "smpf_products_fwd" : "smpf_products_bwd", (smp_rowpanel_split<F, M, CB, NF, NX, CLS, W, ACC>), dim3((unsigned)a.grid), dim3(kSpThreads),
-              lds, a.A, a.rowscale, a.Wst, a.Out, a.rows, a.trow, a.store_mask, a.img, rcls, a_off, out_off);
+    GF_LAUNCH(ctx, F ? "smpf_products_fwd" : "smpf_products_bwd", (smp_rowpanel_split<F, M, CB, NF, NX, CLS, W, ACC, DZ>), dim3((unsigned)a.grid), dim3(kSpThreads),
+              lds, a.A, a.rowscale, a.Wst, a.Out, a.rows, a.trow, a.store_mask, a.img, rcls, a_off, out_off, dz);
     return GF_OK;
 }
 // C = 128: the four (reduction half i, output half j) passes of a level's products, each the 64-channel program on its sub-blocks; for an
@@ -1702,18 +1741,24 @@ static gf_status launch_rowpanel_split(gf_ctx *ctx, bool forward, bool mask, con
     return mask ? launch_rowpanel_split<false, true, CB, NF, NX>(ctx, a) : launch_rowpanel_split<false, false, CB, NF, NX>(ctx, a);
 }
 
+// Panels of one row class (see the kernel): the masked backward products at C = 64 with the level's class lists, when the gradients
+// of structural zeros are skipped -- otherwise every row runs the full program and writes all four blocks, and the classes buy
+// nothing.  GF_SMP_ROW_CLASSES=0 (read per call): the unclassed kernel.
+static bool rowpanel_classed(bool forward, int rows, const int *trowf, bool skip_zero_grads, int C, int nf, int nx, const int *rowcls) {
+    return rowcls && !forward && skip_zero_grads && C == 64 && nf == 2 && nx == 0 && packed_rows(trowf, rows, 1 << 29) && !env_is("GF_SMP_ROW_CLASSES", '0');
+}
+bool smp_rowpanel_dz_applies(const gf_ctx *ctx, int rows, const int *trow, const int *trowf, bool skip_zero_grads, int C, int nf, int nx, const int *rowcls) {
+    return trow && smp_split_products(ctx) && rowpanel_classed(false, rows, trowf, skip_zero_grads, C, nf, nx, rowcls);
+}
+
 // Row-panel products of a fused SMP level at C = 64, compact layout (O = [O_loc | U]; trow = the transposed-row table of the
 // level): forward O from T = [S_ab|S_bc|T6|T10], or backward dT from dO.  Every output element is produced by one wave in a
 // fixed order: results do not depend on the grid size.
 gf_status smp_rowpanel_split_c64(gf_ctx *ctx, bool forward, const float *A, const float *rowscale, const float *Wst, float *Out,
                                  int rows, const int *trow, int cus, const int *trowf, bool skip_zero_grads, const void *wimg, int C, int nf, int nx,
-                                 const int *rowcls) {
+                                 const int *rowcls, const RowpanelDz *dz) {
     const int per = kSpThreads / 64;
-    // Panels of one row class (see the kernel): the masked backward products at C = 64 with the level's class lists, when the gradients
-    // of structural zeros are skipped -- otherwise every row runs the full program and writes all four blocks, and the classes buy
-    // nothing.  GF_SMP_ROW_CLASSES=0 (read per call): the unclassed kernel.
-    const bool classed = rowcls && !forward && skip_zero_grads && C == 64 && nf == 2 && nx == 0 && packed_rows(trowf, rows, 1 << 29) &&
-                         !env_is("GF_SMP_ROW_CLASSES", '0');
+    const bool classed = rowpanel_classed(forward, rows, trowf, skip_zero_grads, C, nf, nx, rowcls);
     const int npanels = (rows + 31) / 32 + (classed ? 1 : 0);   // (two padded lists: one panel more at the most)
     const int want = (npanels + per - 1) / per;
     // C = 64: one persistent workgroup per CU (the weight images take 128 KB of LDS); C = 32 (32 KB of images): two
@@ -1741,6 +1786,8 @@ gf_status smp_rowpanel_split_c64(gf_ctx *ctx, bool forward, const float *A, cons
         return C == 32 ? launch_rowpanel_split<32, 8>(ctx, forward, mask, a) : launch_rowpanel_split<16, 8>(ctx, forward, mask, a);
     switch (C) {
     case 64:
+        if (classed && dz) return launch_rowpanel_split<false, true, 64, 2, 0, true, 1, false, true>(ctx, a, rowcls, 0, 0, *dz);
+        if (dz) return fail(ctx, GF_ERR_INVALID, "smp_rowpanel_split: dz is formed by the row-class kernel only");
         if (classed) return launch_rowpanel_split<false, true, 64, 2, 0, true>(ctx, a, rowcls);
         return launch_rowpanel_split<64, 2>(ctx, forward, mask, a);
     case 32: return launch_rowpanel_split<32, 2>(ctx, forward, mask, a);

@@ -454,6 +454,22 @@ __global__ __launch_bounds__(kRcBlock) void row_class_fill(const int *__restrict
     }
 }
 
+// the node of every entry of the two lists (padding entries: their row's): node_row is ascending, a bisection per entry
+__global__ void row_class_nodes(const int *__restrict__ hdr, const int2 *__restrict__ ent, const long long *__restrict__ node_row, int nodes,
+                                int *__restrict__ ent_node) {
+    const int n_ent = ((hdr[0] + 31) & ~31) + ((hdr[1] + 31) & ~31);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_ent) return;
+    const long long row = ent[i].x & 0x1fffffff;
+    int lo = 0, hi = nodes - 1;   // the last node whose first row is <= row
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (node_row[mid] <= row) lo = mid;
+        else hi = mid - 1;
+    }
+    ent_node[i] = lo;
+}
+
 // ---- gf_smp_prepare: the steps ------------------------------------------------------------------------------------
 // The ONE way a batch's buffers are taken from the pool: the first failure is kept and every later request does nothing, so a step asks
 // for its buffers in order and checks `st` at its end (and before it launches anything on them).  The ORDER of the requests is behaviour:
@@ -623,6 +639,8 @@ void alloc_level_panels(Taker &t, Level &h, DevLevel &d, int l) {
     t.alloc(&d.trow, (size_t)h.rows);
     t.alloc(&d.trowf, (size_t)h.rows);
     if (C == 64 && cfg.nContractions == 18 && h.rows < (1ll << 29)) t.alloc(&d.rowcls, smp_row_class_ints((int)h.rows));   // (row classes of the masked products)
+    // (the top level of a plain model: its backward products form dz from the read-out's per-node vector -- the node of every list entry)
+    if (d.rowcls && l == L && !cfg.physics) t.alloc(&d.rowcls_node, (size_t)h.rows + 64);
     unsigned char *img = nullptr;
     t.alloc(&img, smp_split_image_bytes(C));
     d.wimg = img;
@@ -640,6 +658,7 @@ void alloc_level_panels(Taker &t, Level &h, DevLevel &d, int l) {
     t.alloc(&d.dzmax, (h.quad_node.size() + np1) * 64);   // (panels, then the workgroups of the nodes above 32 positions)
     t.alloc(&d.fwd_pan_node, np1);
     t.alloc(&d.fwd_goff, (size_t)h.rows);
+    if (C == 64) t.alloc(&d.sgn, (size_t)h.rows * 2);   // (the sign words of z_l: 8 bytes per row)
 }
 
 // the contraction's output and what the level's kind works in beside it
@@ -759,6 +778,7 @@ gf_status build_row_tables(gf_smp *s) {
         if (st != GF_OK) return st;
         if (d.trow && !merged) hipLaunchKernelGGL(build_trow, dim3(nNodes), dim3(64), 0, up, d.trow, d.node_s, d.node_row, d.pi, d.rowflag, d.trowf);
         if (d.rowcls) st = smp_build_row_classes(s->ctx, up, d.trowf, (int)s->lay.level[l].rows, d.rowcls);
+        if (st == GF_OK && d.rowcls_node) st = smp_build_row_class_nodes(s->ctx, up, d.rowcls, (int)s->lay.level[l].rows, d.node_row, nNodes, d.rowcls_node);
         if (st != GF_OK) return st;
     }
     return GF_OK;
@@ -1000,6 +1020,13 @@ gf_status smp_build_row_classes(gf_ctx *ctx, hipStream_t stream, const int *trow
     hipLaunchKernelGGL(row_class_scan, dim3(1), dim3(kRcBlock), 0, stream, blockcnt, nb, rows, buf);
     hipLaunchKernelGGL(row_class_fill, dim3(nb), dim3(kRcBlock), 0, stream, trowf, rows, blockcnt, buf, reinterpret_cast<int2 *>(buf + 4));
     GF_LAUNCH_CHECK(ctx, "row_class_fill");
+    return GF_OK;
+}
+gf_status smp_build_row_class_nodes(gf_ctx *ctx, hipStream_t stream, const int *buf, int rows, const long long *node_row, int nodes, int *ent_node) {
+    if (rows < 1 || nodes < 1) return GF_OK;
+    hipLaunchKernelGGL(row_class_nodes, dim3((unsigned)((rows + 64 + 255) / 256)), dim3(256), 0, stream, buf, reinterpret_cast<const int2 *>(buf + 4), node_row,
+                       nodes, ent_node);
+    GF_LAUNCH_CHECK(ctx, "row_class_nodes");
     return GF_OK;
 }
 }  // namespace gf
