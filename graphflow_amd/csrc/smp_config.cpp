@@ -85,6 +85,8 @@ gf_status resolve_config(const gf_smp_config *cfg, const ConfigEntry &entry, Con
         if (cfg->first_order == 1)   // (SMP_theta has no `_classification` class; first_order = 2, 3, 4 do: SMP_1D*_classification)
             GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: a first-order model (first_order = 1) has no classifier read-out");
         if (cfg->unrestricted) GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: the Unrestricted_SMP_* models have no `_classification` class");
+        if (cfg->neighbourhood == 6 || cfg->neighbourhood == 7)
+            GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: GCN_3D / GRU_GCN_3D have no `_classification` class");
         if (cfg->neighbourhood)
             GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: NeuralFingerprint / GCN_1D / GCN_2D%s have no `_classification` class",
                       cfg->neighbourhood >= 4 ? " / GRU_GCN_1D / GRU_GCN_2D" : "");
@@ -92,6 +94,31 @@ gf_status resolve_config(const gf_smp_config *cfg, const ConfigEntry &entry, Con
         if (nClass < 2) GF_REFUSE(GF_ERR_INVALID, "gf_smp_create_classifier: nClass = %d (at least 2)", nClass);
     }
     // ---- the configuration, family by family ----
+    if (cfg->neighbourhood == 6 || cfg->neighbourhood == 7) {   // GCN_3D, GRU_GCN_3D (smp_level_third.hip): nLevels = 0 is a model
+        if (cfg->nChanels > gf::kThirdMaxChanels)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: neighbourhood = %d (6: GCN_3D, 7: GRU_GCN_3D) with nChanels = %d: the third-order pool packs "
+                                      "a triple of channels into 18 bits and keeps B [H][H] in LDS: at most %d channels",
+                      cfg->neighbourhood, cfg->nChanels, gf::kThirdMaxChanels);
+        gf_smp_config as2 = *cfg;
+        as2.neighbourhood = 2;
+        if (!rule_neighbourhood(&as2))
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: neighbourhood = %d (6: GCN_3D, 7: GRU_GCN_3D) needs first_order = steerable_2d = unrestricted "
+                                      "= physics = nContractions = custom_matmul = 0, max_receptive_field (%d) == max_nVertices (%d) <= 4096, "
+                                      "nLevels >= 0, max_Radius (%d) >= 0 and the level's matrices within 160 KiB", cfg->neighbourhood,
+                      cfg->max_receptive_field, cfg->max_nVertices, cfg->max_Radius);
+        if (cfg->max_nVertices > gf::smp_third_max_members(cfg->nChanels))
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: neighbourhood = %d (6: GCN_3D, 7: GRU_GCN_3D) with max_nVertices = %d: the third-order pool "
+                                      "stages a neighbourhood's members in LDS (%zu bytes and %d per member at %d channels, 160 KiB per workgroup): "
+                                      "at most %d vertices", cfg->neighbourhood, cfg->max_nVertices, gf::smp_third_lds_bytes(cfg->nChanels, 0),
+                      4 * cfg->nChanels, cfg->nChanels, gf::smp_third_max_members(cfg->nChanels));
+        Config c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, 0};
+        c.nContractions = 0;
+        c.max_nVertices = cfg->max_nVertices;
+        c.neighbourhood = cfg->neighbourhood;
+        c.max_Radius = cfg->max_Radius;
+        *out = c;
+        return GF_OK;
+    }
     if (cfg->neighbourhood == 4 || cfg->neighbourhood == 5) {   // GRU_GCN_1D, GRU_GCN_2D (smp_level_gru.hip): nLevels = 0 is a model
         if (cfg->nChanels > gf::kGruMaxChanels)
             GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: neighbourhood = %d with nChanels = %d: the six [H][H] matrices of a GRU cell are resident in "

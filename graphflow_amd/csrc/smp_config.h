@@ -24,6 +24,15 @@ constexpr int kGruMaxChanels = 64;
 inline size_t smp_gru_lds_bytes(int H) {
     return sizeof(float) * (6 * (size_t)H * (size_t)(H | 1) + 3 * (size_t)(256 / smp_neighbourhood_group_width(H)) * H);
 }
+// the third-order pool (smp_level_third.hip; neighbourhood = 6, 7): at most kThirdMaxChanels channels (a canonical triple packs into 18
+// bits).  LDS of one vertex's workgroup: two arrays of kThirdCand 64-bit keys, kThirdBins + 256 + 8 counters, A [H], B [H][H] and the
+// members' vectors [members][H] -- 42,272 bytes and 256 per member at 64 channels, so a neighbourhood holds at most 474 vertices there.
+constexpr int kThirdMaxChanels = 64;
+constexpr int kThirdBins = 2048, kThirdCand = 1024;
+inline size_t smp_third_lds_bytes(int H, int members) {
+    return 8 * 2 * (size_t)kThirdCand + 4 * ((size_t)kThirdBins + 256 + 8) + sizeof(float) * ((size_t)H + (size_t)H * H + (size_t)members * H);
+}
+inline int smp_third_max_members(int H) { return (int)((160 * 1024 - smp_third_lds_bytes(H, 0)) / (sizeof(float) * (size_t)H)); }
 }  // namespace gf
 
 namespace gfsmp {

@@ -274,7 +274,16 @@ struct gf_smp {
         // arbitrary vector.  The read-out's sigmoid, tanh and their two gradients live in the handle (gf_smp::gru_*).
         float *gru_z = nullptr, *gru_r = nullptr, *gru_c = nullptr, *gru_q = nullptr;
         float *gru_dz = nullptr, *gru_dr = nullptr, *gru_dc = nullptr, *gru_direct = nullptr;
+        // third-order pool (smp_level_third.hip; neighbourhood = 6, 7; levels >= 1): nb_sel [vertices][H] = the canonical triple per rank
+        // (x | y << 8 | z << 16, -1 under three members), nb_pool [vertices][H] = the pooled n_l where the update kernel reads it through
+        // the identity list (form 6; form 7's cell reads th_A), nb_max_members = the longest list of the level
+        int *nb_sel = nullptr;
+        float *nb_pool = nullptr;
+        int nb_max_members = 0;
     };
+    // the list N(v) = {v} over the batch's vertices (form 6: the sum instantiation of nbh_level_fwd over it hands the pooled n on unchanged)
+    long long *nb_id_ptr = nullptr;
+    int *nb_id_idx = nullptr;
     std::vector<DevLevel> lv;
     // device-built level tables: the batch's adjacency matrices and the per-level statistics the kernels leave behind
     int *mol_nv = nullptr, *mol_adj = nullptr;
@@ -418,6 +427,13 @@ gf_status smp_neighbourhood_gather_launch(gf_ctx *ctx, bool pairs, int H, int nV
 // params / grads: W; W_z, U_z, W_r, U_r, W_h, U_h, W_g, U_g (shared by the levels: their gradients accumulate across them); U.
 gf_status smp_gru_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature);
 gf_status smp_gru_backward(gf_smp *s, const float *params, float *grads, int accumulate);
+// GCN_3D, GRU_GCN_3D (cfg.neighbourhood = 6, 7; smp_level_third.hip): the aggregate n_l[v] = KMax(RisiLayer3D) of the two sweeps above, on
+// raw operands.  forward: n, sel [nV][H] from hprev over the list (max_members = its longest entry); backward: dhprev [nV][H] from dn over
+// the transposed list, consumer by consumer in ascending order.
+gf_status smp_third_pool_fwd_launch(gf_ctx *ctx, int H, int nV, int max_members, const float *hprev, const long long *ptr, const int *idx, float *n,
+                                    int *sel);
+gf_status smp_third_pool_bwd_launch(gf_ctx *ctx, int H, int nV, const long long *ptr, const int *idx, const long long *tptr, const int *tidx,
+                                    const float *hprev, const int *sel, const float *dn, float *dhprev);
 // smp_theta_prepare (smp_prepare.hip): gf_smp_prepare of a first-order handle -- the th_* tables, none of the other kinds' buffers.
 gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature);
 // the first-order read-out of level l (smp_field_level.hip): sh[n] = column sums over the node's s rows (ShrinkMatrix), vf = LeakyReLU(sh);

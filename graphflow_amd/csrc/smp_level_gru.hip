@@ -48,8 +48,8 @@ __device__ __forceinline__ Slot slot_of(int G) {
 
 __device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
 
-// M6 = W_z, U_z, W_r, U_r, W_h, U_h back to back, [H][H] each
-template <bool PAIRS>
+// M6 = W_z, U_z, W_r, U_r, W_h, U_h back to back, [H][H] each.  GIVEN: n holds the aggregate already (GRU_GCN_3D: smp_level_third.hip)
+template <bool PAIRS, bool GIVEN = false>
 __global__ __launch_bounds__(kBlock) void gru_cell_fwd(const float *__restrict__ M6, const float *__restrict__ hprev, const float *__restrict__ Tprev,
                                                        const long long *__restrict__ ptr, const int *__restrict__ idx, float *__restrict__ h,
                                                        float *__restrict__ n, float *__restrict__ z, float *__restrict__ r, float *__restrict__ c,
@@ -77,8 +77,8 @@ __global__ __launch_bounds__(kBlock) void gru_cell_fwd(const float *__restrict__
         const bool live = v < nV;
         const size_t vv = live ? v : nV - 1;
         float a = 0.f, sacc = 0.f, tt = 0.f;
-        const long long e1 = ptr[vv + 1];
-        for (long long e = ptr[vv]; e < e1; ++e) {
+        const long long e1 = GIVEN ? 0 : ptr[vv + 1];
+        for (long long e = GIVEN ? 0 : ptr[vv]; e < e1; ++e) {
             const size_t u = (size_t)idx[e];
             const float hv = hprev[u * H + cc];
             a += hv;
@@ -88,11 +88,11 @@ __global__ __launch_bounds__(kBlock) void gru_cell_fwd(const float *__restrict__
                 tt += tu;
             }
         }
-        const float nk = PAIRS ? mul_rounded(a, tt) - sacc : a;
+        const float nk = GIVEN ? n[vv * H + cc] : PAIRS ? mul_rounded(a, tt) - sacc : a;
         const float hp = hprev[vv * H + cc];
         if (ok) nb[cc] = nk, hb[cc] = hp;
         if (live && ok) {
-            n[vv * H + cc] = nk;
+            if (!GIVEN) n[vv * H + cc] = nk;
             if (PAIRS) A[vv * H + cc] = a;
         }
         if (PAIRS && live && sl.c0 == 0) Tt[vv] = tt;
@@ -344,14 +344,14 @@ struct Shape {
     dim3 grid(int vpg) const { return dim3((unsigned)((nV + vpg - 1) / vpg)); }
 };
 
-template <bool PAIRS>
+template <bool PAIRS, bool GIVEN = false>
 gf_status cell_fwd_launch(gf_ctx *ctx, const Shape &sh, const float *M6, const float *hprev, const float *Tprev, const long long *ptr,
                           const int *idx, float *h, float *n, float *z, float *r, float *c, float *A, float *T, float *Tt) {
     const size_t bytes = smp_gru_lds_bytes(sh.H);
     const int vpg = vertices_per_group(sh.nV, sh.slots, bytes);
-    const gf_status st = opt_in_lds(ctx, gru_cell_fwd<PAIRS>, bytes);
+    const gf_status st = opt_in_lds(ctx, gru_cell_fwd<PAIRS, GIVEN>, bytes);
     if (st != GF_OK) return st;
-    GF_LAUNCH(ctx, "gru_cell_fwd", (gru_cell_fwd<PAIRS>), sh.grid(vpg), dim3(kBlock), bytes, M6, hprev, Tprev, ptr, idx, h, n, z, r, c, A, T, Tt,
+    GF_LAUNCH(ctx, "gru_cell_fwd", (gru_cell_fwd<PAIRS, GIVEN>), sh.grid(vpg), dim3(kBlock), bytes, M6, hprev, Tprev, ptr, idx, h, n, z, r, c, A, T, Tt,
               sh.nV, sh.H, sh.G, vpg);
     return GF_OK;
 }
@@ -415,6 +415,13 @@ gf_status smp_gru_forward(gf_smp *s, const float *params, const float *targets, 
     for (int l = 1; l <= L && st == GF_OK; ++l) {
         gf_smp::DevLevel &d = s->lv[l];
         const gf_smp::DevLevel &pv = s->lv[l - 1];
+        if (s->cfg.third_order()) {   // GRU_GCN_3D: the pool leaves n_l in th_A, the cell reads it there
+            st = smp_third_pool_fwd_launch(ctx, H, nV, d.nb_max_members, pv.f, d.nb_ptr, d.nb_idx, d.th_A, d.nb_sel);
+            if (st == GF_OK)
+                st = cell_fwd_launch<false, true>(ctx, sh, p.mat(0), pv.f, nullptr, d.nb_ptr, d.nb_idx, d.f, d.th_A, d.gru_z, d.gru_r, d.gru_c, nullptr,
+                                                  nullptr, nullptr);
+            continue;
+        }
         st = with_aggregate(pairs, [&](auto pr) -> gf_status {
             return cell_fwd_launch<decltype(pr)::value>(ctx, sh, p.mat(0), pv.f, pv.nb_T, d.nb_ptr, d.nb_idx, d.f, d.th_A, d.gru_z, d.gru_r, d.gru_c,
                                                         d.th_B, d.nb_T, d.nb_Tt);
@@ -463,7 +470,10 @@ gf_status smp_gru_backward(gf_smp *s, const float *params, float *grads, int acc
         const float *lhs[6] = {v.gru_dz, v.gru_dz, v.gru_dr, v.gru_dr, v.gru_dc, v.gru_dc};
         const float *rhs[6] = {v.th_A, pv.f, v.th_A, pv.f, v.th_A, v.gru_q};   // n, hp, n, hp, n, q
         for (int i = 0; i < 6 && st == GF_OK; ++i) st = wgrad(ctx, sh, lhs[i], rhs[i], d.mat(i));
-        if (st == GF_OK) st = smp_neighbourhood_gather_launch(ctx, pairs, H, nV, v.nb_tptr, v.nb_tidx, v.Q, v.th_node, v.nb_sA, pv.f, pv.nb_T, pv.df);
+        if (st == GF_OK && s->cfg.third_order())
+            st = smp_third_pool_bwd_launch(ctx, H, nV, v.nb_ptr, v.nb_idx, v.nb_tptr, v.nb_tidx, pv.f, v.nb_sel, v.Q, pv.df);
+        else if (st == GF_OK)
+            st = smp_neighbourhood_gather_launch(ctx, pairs, H, nV, v.nb_tptr, v.nb_tidx, v.Q, v.th_node, v.nb_sA, pv.f, pv.nb_T, pv.df);
         if (st != GF_OK) break;
         const size_t count = (size_t)nV * H, blocks = (count + kBlock - 1) / kBlock;
         GF_LAUNCH(ctx, "gru_add", gru_add, dim3((unsigned)(blocks > 65536 ? 65536 : blocks)), dim3(kBlock), 0, pv.df, v.gru_direct, count);

@@ -383,12 +383,20 @@ gf_status level(gf_smp *s, int l, const float *W1, const float *W2, bool forward
     return with_instantiation(H, s->cfg.neighbourhood == 3, [&](auto nk, auto pairs) -> gf_status {
         constexpr int NK = decltype(nk)::value;
         constexpr bool PAIRS = decltype(pairs)::value;
+        const bool third = l && s->cfg.third_order();   // GCN_3D: n_l is smp_level_third.hip's, handed on as a sum of one term over N(v) = {v}
+        if (forward && third) {
+            const gf_status pooled = smp_third_pool_fwd_launch(ctx, H, nV, d.nb_max_members, pv->f, d.nb_ptr, d.nb_idx, d.nb_pool, d.nb_sel);
+            if (pooled != GF_OK) return pooled;
+            return fwd_launch<NK, PAIRS>(ctx, H, FD, nV, 0, W1, W2, s->x, d.nb_pool, nullptr, s->nb_id_ptr, s->nb_id_idx, d.f, d.th_A, d.th_B, d.nb_T,
+                                         d.nb_Tt);
+        }
         if (forward)
             return fwd_launch<NK, PAIRS>(ctx, H, FD, nV, 0, W1, W2, s->x, pv ? pv->f : nullptr, pv ? pv->nb_T : nullptr, d.nb_ptr, d.nb_idx, d.f,
                                          d.th_A, d.th_B, d.nb_T, d.nb_Tt);
         const gf_status st = node_launch<NK, PAIRS>(ctx, H, nV, 0, W2, d.f, d.df, top ? s->dy : nullptr, Wout, s->top_node_mol, d.th_B, d.nb_Tt,
                                                     d.Q, d.th_node, d.nb_sA);
         if (st != GF_OK || !l) return st;
+        if (third) return smp_third_pool_bwd_launch(ctx, H, nV, d.nb_ptr, d.nb_idx, d.nb_tptr, d.nb_tidx, pv->f, d.nb_sel, d.Q, pv->df);
         return gather_launch<NK, PAIRS>(ctx, H, nV, d.nb_tptr, d.nb_tidx, d.Q, d.th_node, d.nb_sA, pv->f, pv->nb_T, pv->df);
     });
 }

@@ -88,8 +88,11 @@ struct Config {
     // 4, 5: GRU_GCN_1D, GRU_GCN_2D (GraphFlow/GRU_GCN_1D.h, GRU_GCN_2D.h; smp_level_gru.hip): forms 2 and 3 with a GRU cell as the level's
     // update and a gated read-out; N_l(v) = hop distance <= min(l, max_Radius) in BOTH (GRU_GCN_2D does read max_Radius).  Parameters, shared
     // by all levels: W [H][F']; W_z, U_z, W_r, U_r, W_h, U_h, W_g, U_g [H][H] (shared_blocks()); U [H].  The levels own nothing.
+    // 6, 7: GCN_3D, GRU_GCN_3D (GraphFlow/GCN_3D.h, GRU_GCN_3D.h; smp_level_third.hip): forms 2 and 4 with n_l[v] = KMax(RisiLayer3D of the
+    // members, K = nChanels) as the aggregate; N_l(v) = hop distance <= min(l, max_Radius) in both; the parameter blocks of forms 2 / 4.
     int neighbourhood = 0, max_Radius = 0;
-    bool gated() const { return neighbourhood >= 4; }
+    bool gated() const { return neighbourhood == 4 || neighbourhood == 5 || neighbourhood == 7; }
+    bool third_order() const { return neighbourhood == 6 || neighbourhood == 7; }
     int nb_radius(int l) const { return neighbourhood == 1 ? 1 : neighbourhood == 3 || l < max_Radius ? l : max_Radius; }   // of N_l (form 1: the adjacency itself; 3 alone ignores max_Radius)
     size_t filter_floats(int l) const { return level_blocks(l).size_quad(); }   // of an unrestricted level's filter, per s^2
     bool per_size() const { return first_order || steerable_2d; }   // a handle on the th_* tables, per-size blocks in front of the matrix block

@@ -981,6 +981,14 @@ gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, c
         t.alloc(&d.Q, nV * H);
         if (cfg.gated())   // the GRU cell's gates and what its weight gradients read (smp_level_gru.hip)
             for (float **p : {&d.gru_z, &d.gru_r, &d.gru_c, &d.gru_q, &d.gru_dz, &d.gru_dr, &d.gru_dc, &d.gru_direct}) t.alloc(p, nV * H);
+        if (cfg.third_order()) {   // the selection record, the longest list, and form 6's pooled vector (smp_level_third.hip)
+            const auto &lp = B.nb_lists[(size_t)B.nb_list_of_level[l]].ptr;
+            long long longest = 0;
+            for (size_t v = 0; v + 1 < lp.size(); ++v) longest = lp[v + 1] - lp[v] > longest ? lp[v + 1] - lp[v] : longest;
+            d.nb_max_members = (int)longest;
+            t.alloc(&d.nb_sel, nV * H);
+            if (!cfg.gated()) t.alloc(&d.nb_pool, nV * H);
+        }
         if (pairs) {
             t.alloc(&d.th_B, nV * H);
             t.alloc(&d.th_node, nV * H);
@@ -997,6 +1005,16 @@ gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, c
         for (float **p : {&s->gru_s, &s->gru_t, &s->gru_ds, &s->gru_dt}) t.alloc(p, nV * H);
     t.put(&s->top_node_mol, B.nb_vertex_mol);
     t.put(&s->mol_ptr, B.mol_first_vertex);
+    s->nb_id_ptr = nullptr;
+    s->nb_id_idx = nullptr;
+    if (cfg.neighbourhood == 6) {   // N(v) = {v}
+        std::vector<long long> ip(nV + 1);
+        std::vector<int> ii(nV);
+        for (size_t v = 0; v <= nV; ++v) ip[v] = (long long)v;
+        for (size_t v = 0; v < nV; ++v) ii[v] = (int)v;
+        t.put(&s->nb_id_ptr, ip);
+        t.put(&s->nb_id_idx, ii);
+    }
     if (t.st != GF_OK) return t.st;
     s->wbound = nullptr;
     s->sh = s->vf = s->dsh = s->colpart = nullptr;

@@ -412,12 +412,14 @@ class SMPNeighbourhood(SMP1D):
       h_0[v] = softmax(W1_0 x[v]);  h_l[v] = softmax(W1_l x[v] + W2_l n_l[v]),  n_l[v] = the aggregate of h_{l-1} over N_l(v);
       "fingerprint": x = the vertex's features (nDepth must be 0), N_l(v) = {u: adj[v, u] > 0}, sum;
       "gcn_1d":      x = the shell sums up to nDepth, N_l(v) = {u: dist(v, u) <= min(l, max_Radius)}, sum;
-      "gcn_2d":      x likewise, N_l(v) = {u: dist(v, u) <= l} (max_Radius is not read), RisiLayer2D.
+      "gcn_2d":      x likewise, N_l(v) = {u: dist(v, u) <= l} (max_Radius is not read), RisiLayer2D;
+      "gcn_3d":      GCN_3D (GraphFlow/GCN_3D.h, neighbourhood = 6): x and N_l(v) as "gcn_1d" (max_Radius is read), n_l[v] = the nHiddens largest
+                     entries of RisiLayer3D's H^3 triple products over the members, ascending (KMax); 0 under three members; nHiddens <= 64.
     predict = <W, sum_v h_L[v]>, squared loss.  Parameters in registration order: W1_0[H, F']; for l = 1..L: W1_l[H, F'], W2_l[H, H]; W[H],
     F' = nFeatures (nDepth + 1).  The softmax gradient is the classes' diagonal rule.  nLevels = 0 is a model.  nHiddens <= 128.  The optimiser
     is Momentum: step().  There are no classifiers of these forms."""
 
-    FORMS = {"fingerprint": 1, "gcn_1d": 2, "gcn_2d": 3}
+    FORMS = {"fingerprint": 1, "gcn_1d": 2, "gcn_2d": 3, "gcn_3d": 6}
 
     def __init__(self, form, nLevels, nHiddens, nFeatures, nDepth, max_nVertices, max_Radius=1, ctx=None):
         self.ctx = ctx or default_context()
@@ -433,7 +435,8 @@ class SMPNeighbourhood(SMP1D):
     @staticmethod
     def config(form, nLevels, nHiddens, nFeatures, nDepth, max_nVertices, max_Radius=1):
         if form not in SMPNeighbourhood.FORMS:
-            raise ValueError("SMPNeighbourhood: form %r (\"fingerprint\": NeuralFingerprint, \"gcn_1d\": GCN_1D, \"gcn_2d\": GCN_2D)" % (form,))
+            raise ValueError("SMPNeighbourhood: form %r (\"fingerprint\": NeuralFingerprint, \"gcn_1d\": GCN_1D, \"gcn_2d\": GCN_2D, "
+                             "\"gcn_3d\": GCN_3D)" % (form,))
         return SMPConfig(nLevels, nHiddens, nFeatures, nDepth, max_nVertices, 0, 0, 0, 0, 0, max_nVertices, 0, 0,
                          SMPNeighbourhood.FORMS[form], max_Radius)
 
@@ -456,14 +459,17 @@ class SMPGatedNeighbourhood(SMPNeighbourhood):
       z = sigmoid(W_z n + U_z hp), r = sigmoid(W_r n + U_r hp), c = tanh(W_h n + U_h (r hp)), h_l[v] = (1 - z) hp + z c;
       graph_feature = tanh(sum_v sigmoid(W_g h_L[v]) tanh(U_g h_L[v])), predict = <U, graph_feature>, squared loss.
     Parameters in registration order, shared by all levels: W[H, F']; W_z, U_z, W_r, U_r, W_h, U_h, W_g, U_g [H, H]; U[H].  nLevels = 0 is a
-    model.  nHiddens <= 64.  The optimiser is Momentum: step().  There are no classifiers of these forms."""
+    model.  nHiddens <= 64.  The optimiser is Momentum: step().  There are no classifiers of these forms.
+    "gru_gcn_3d" is GRU_GCN_3D (GraphFlow/GRU_GCN_3D.h, neighbourhood = 7): the same cell with n = the nHiddens largest entries of RisiLayer3D
+    over the members (KMax, ascending; 0 under three members)."""
 
-    FORMS = {"gru_gcn_1d": 4, "gru_gcn_2d": 5}
+    FORMS = {"gru_gcn_1d": 4, "gru_gcn_2d": 5, "gru_gcn_3d": 7}
 
     @staticmethod
     def config(form, nLevels, nHiddens, nFeatures, nDepth, max_nVertices, max_Radius=1):
         if form not in SMPGatedNeighbourhood.FORMS:
-            raise ValueError("SMPGatedNeighbourhood: form %r (\"gru_gcn_1d\": GRU_GCN_1D, \"gru_gcn_2d\": GRU_GCN_2D)" % (form,))
+            raise ValueError("SMPGatedNeighbourhood: form %r (\"gru_gcn_1d\": GRU_GCN_1D, \"gru_gcn_2d\": GRU_GCN_2D, "
+                             "\"gru_gcn_3d\": GRU_GCN_3D)" % (form,))
         return SMPConfig(nLevels, nHiddens, nFeatures, nDepth, max_nVertices, 0, 0, 0, 0, 0, max_nVertices, 0, 0,
                          SMPGatedNeighbourhood.FORMS[form], max_Radius)
 

@@ -388,6 +388,20 @@ typedef struct {
      * forms 1 - 3; gf_smp_classifier_config_param_count answers 0.  The level is smp_level_gru.hip: level 0 and the reverse gather are
      * smp_level_neighbourhood.hip's kernels, one gru_cell_fwd / gru_cell_bwd launch per level, the eight weight gradients deterministic TN
      * products accumulated over the levels from the top down; no atomics.
+     * neighbourhood = 6: GCN_3D, 7: GRU_GCN_3D (GraphFlow/GCN_3D.h, GRU_GCN_3D.h) -- forms 2 and 4 (x, N_l(v) = { u : dist(v, u) <= min(l,
+     * max_Radius) } in both, level 0, the update, the read-out, the parameter blocks, their order and the way uniform_init draws them) with the
+     * third-order aggregate  n_l[v] = KMax(RisiLayer3D(members), K = H):  T[x, y, z] = sum over ordered triples (i, j, k) of distinct members of
+     * a_i[x] a_j[y] a_k[z], of whose H^3 entries the H largest are kept in ascending order (n[H - 1] the largest).  T is symmetric, so it is
+     * evaluated per class x <= y <= z (6, 3 or 1 equal entries) in the closed form A_x A_y A_z - B_yz A_x - B_xz A_y - B_xy A_z + 2 sum_u
+     * a_u[x] a_u[y] a_u[z], A = sum_u a_u, B_pq = sum_u a_u[p] a_u[q]; which entries of a class are kept changes no value and no gradient.
+     * Between classes the choice is a kink: the device agrees with the fp64 class wherever adjacent classes around the cut differ by more
+     * than the fp32 evaluation error (about 1e-6 max|T|).  Exactly equal fp32 values of two classes: the larger flat index z H^2 + y H + x of
+     * the classes' largest entries is kept first.  Under three members T = 0: n = 0 exactly and nothing flows back (max_Radius = 0: every
+     * level is softmax(W1_l x), or a cell with n = 0).  Required, else GF_ERR_INVALID: form 2's rules, nChanels <= 64, and max_nVertices within
+     * what a neighbourhood's members take in LDS beside the select's tables: (160 KiB - 25,632 - 4 H - 4 H^2) / (4 H) vertices, 474 at 64
+     * channels.  Introspection, the Momentum optimiser and the five GF_ERR_UNSUPPORTED refusals are those of forms 1 - 5.  The level is
+     * smp_level_third.hip: one third_pool_fwd launch per level ahead of the update kernel of form 2 / 4, one third_pool_bwd in place of their
+     * reverse gather; no float atomics, two runs give the same bits.
      * 0 (a zero-initialised tail): everything as described above, max_Radius is not read. */
     int neighbourhood, max_Radius;
 } gf_smp_config;
@@ -562,6 +576,23 @@ gf_status gf_smp_neighbourhood_gather_bwd_ex_f32(gf_ctx *ctx, int pairs, int H, 
                                                  const float *gTt, const float *sA, const float *hprev, const float *Tprev, float *dhprev);
 gf_status gf_smp_neighbourhood_readout_ex_f32(gf_ctx *ctx, int H, int nV, int nMol, const float *hL, const int *mol_ptr, const float *W,
                                               const float *target, float *g, float *yhat, float *loss, float *dy, float *dW);
+/* The third-order pool (gf_smp_config.neighbourhood = 6, 7), its two kernels as stand-alone operators on caller-supplied operands, for
+ * per-vertex tests (tests/test_smp_third_order_ops_gpu.py).  Device pointers, fp32, asynchronous on the context's stream.  H = 1 .. 64
+ * channels, nV vertices; lists are CSR: ptr long long [nV + 1] from 0, idx int members in [0, nV), tptr / tidx the transposed list
+ * (the consumers of a source, ascending).
+ *   fwd: n[v] [H] = the H largest of T[x, y, z] over the members hprev[u], u in the list of v, counted with the multiplicity of their
+ *        class, ascending; sel[v] [H] = the canonical triple per rank, x | y << 8 | z << 16 with x <= y <= z.  A list of fewer than three
+ *        members gives n = 0 and sel = -1.
+ *   bwd: dhprev[w] [H] = sum over the consumers v of w, ascending, and their ranks r with sel[v][r] = (x, y, z), g = dn[v][r], of
+ *        g D_w(y, z) into channel x, g D_w(x, z) into y, g D_w(x, y) into z; D_w(p, q) = (A_p - a_w[p]) (A_q - a_w[q]) - (B_pq - a_w[p] a_w[q])
+ *        with A, B of v's members (recomputed from ptr / idx and hprev).  A source without a consumer gets 0.
+ * GF_ERR_INVALID before anything is launched: H outside 1 .. 64, nV < 1, a missing operand, and -- checked on the host, one blocking copy
+ * per call -- a list that does not start at 0 or decreases, a member outside [0, nV), a list longer than the LDS plan takes (474 members
+ * at 64 channels), a sel entry that is neither -1 nor a triple x <= y <= z < H.  The context stays usable after a refusal. */
+gf_status gf_smp_third_order_pool_fwd_ex_f32(gf_ctx *ctx, int H, int nV, const long long *ptr, const int *idx, const float *hprev, float *n,
+                                             int *sel);
+gf_status gf_smp_third_order_pool_bwd_ex_f32(gf_ctx *ctx, int H, int nV, const long long *ptr, const int *idx, const long long *tptr,
+                                             const int *tidx, const float *hprev, const int *sel, const float *dn, float *dhprev);
 /* Device memory of the handle's buffer pool: bytes held by the current batch, and bytes the pool keeps in total (idle
  * blocks included).  Sizing aid for batch selection (GraphFlow has no counterpart: its tensors live in host `new[]`). */
 gf_status gf_smp_device_bytes(const gf_smp *smp, size_t *in_use, size_t *reserved);
