@@ -1064,7 +1064,7 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
         case LevelKind::Fused18:
             if (dfeat) st = feature_nodevec(s, dfeat, l);
             if (st == GF_OK)
-                st = smp_fused_backward_level(s, l, K[l], dK[l], db[l], dfeat ? s->lv[l].dshl : (l == L && top_fused) ? s->dsh : nullptr,
+                st = smp_fused_backward_level(s, l, dK[l], db[l], dfeat ? s->lv[l].dshl : (l == L && top_fused) ? s->dsh : nullptr,
                                               /*rows_too=*/dfeat && l < L);
             break;
         case LevelKind::Gamma:   // dG gathered from dz, dK_l and df_{l-1} on the rows of level l - 1

@@ -363,7 +363,7 @@ gf_status smp_backward_admissible(const gf_smp *s);   // smp.hip: refusals of a 
 gf_status smp_fused_forward_level(gf_smp *s, int l, const float *Kl, const float *bl);
 gf_status smp_fused_ensure_zero_fill(gf_smp *s, int l);
 // node_df != nullptr (top level): df_l is the same C-vector at every position of a node, given as [nodes][C]
-gf_status smp_fused_backward_level(gf_smp *s, int l, const float *Kl, float *dKl, float *dbl, const float *node_df, bool rows_too = false);
+gf_status smp_fused_backward_level(gf_smp *s, int l, float *dKl, float *dbl, const float *node_df, bool rows_too = false);
 gf_status smp_fused_gather_backward(gf_smp *s, int l);
 // SMP_gamma levels (RisiContraction_4, smp_level_gamma.hip): G = f_{l-1} [K0 | K1 | K2 | K3] on the rows of level l - 1 into Q, then one gather
 // with bias + LeakyReLU into f_l; backward the consumer gather of dG from dz, dK_l and df_{l-1} as products on the rows of level l - 1.
