@@ -126,6 +126,9 @@ PROTOTYPES.update({
     "gf_smp_neighbourhood_readout_ex_f32": (_i, [_vp, _i, _i, _i] + [_vp] * 9),
     "gf_smp_third_order_pool_fwd_ex_f32": (_i, [_vp, _i, _i] + [_vp] * 5),
     "gf_smp_third_order_pool_bwd_ex_f32": (_i, [_vp, _i, _i] + [_vp] * 8),
+    "gf_smp_rowlist_product_ex_f32": (_i, [_vp, _i, _i, _i, _i, _i, _i] + [_vp] * 7 + [_i, _vp]),
+    "gf_smp_rowlist_wgrad_ex_f32": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 8),
+    "gf_smp_matrix_form_molecule_host": (_i, [_vp, _i, C.POINTER(C.c_int), _dp, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp]),
     "gf_smp_prepare_molecule_host": (_i, [_vp, _i, C.POINTER(C.c_int), _dp, C.POINTER(C.c_int), _dp]),
     "gf_smp_receptive_field": (_i, [_vp, _i, _i, _i, C.POINTER(C.c_int), _i]),
     "gf_smp_read_activation": (C.c_longlong, [_vp, _i, _i, _i, _vp, C.c_size_t]),

@@ -641,10 +641,10 @@ gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, const gfsmp::Con
     gf_smp *s = new gf_smp();
     s->ctx = ctx;
     s->ucfg = c;
-    if (c.per_size() || c.neighbourhood) s->grad_allreduce = 0;   // (no data-parallel exchange: gf_smp_set_grad_allreduce(.., 1) is refused)
+    if (c.per_size() || c.neighbourhood || c.matrix_form) s->grad_allreduce = 0;   // (no data-parallel exchange: gf_smp_set_grad_allreduce(.., 1) is refused)
     s->req_pad_channels = pad_channels;
     s->req_min_pad = min_pad;
-    if (c.neighbourhood) {   // (no padding, one plan, none of the fused level's switches)
+    if (c.neighbourhood || c.matrix_form) {   // (no padding, one plan, none of the fused level's switches)
         s->cfg = c;
     } else {
         gf::smp_derive_plan(s, /*allow_embed=*/true);
@@ -802,6 +802,7 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
     gf_ctx *ctx = s->ctx;
     gf_status st = ensure_ws(ctx, s->ws_need);
     if (st != GF_OK) return st;
+    if (s->cfg.matrix_form) return smp_matrix_form_forward(s, params, targets, predict, loss, graph_feature);   // (LCNN, GCN_MW: smp_level_rowlist.hip)
     if (s->cfg.gated()) return smp_gru_forward(s, params, targets, predict, loss, graph_feature);   // (the neighbourhood kind's second set of sweeps)
     if (s->cfg.neighbourhood) return smp_neighbourhood_forward(s, params, targets, predict, loss, graph_feature);   // (its own level 0 and read-out)
     const gfsmp::BatchLayout &B = s->lay;
@@ -999,6 +1000,7 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
     // (a no-op after this batch's forward; it makes the reverse sweep independent of who grew the context's workspace last)
     gf_status st = ensure_ws(ctx, s->ws_need);
     if (st != GF_OK) return st;
+    if (s->cfg.matrix_form) return smp_matrix_form_backward(s, params, grads, accumulate);
     if (s->cfg.gated()) return smp_gru_backward(s, params, grads, accumulate);
     if (s->cfg.neighbourhood) return smp_neighbourhood_backward(s, params, grads, accumulate);   // (never a tower: gf_smp_backward_features refuses)
     const gfsmp::BatchLayout &B = s->lay;
@@ -1144,6 +1146,7 @@ gf_status gf_smp_dropout_masks(gf_smp *s, const unsigned *masks, float scale) {
     gf_ctx *ctx = s->ctx;
     if (s->cfg.per_size() || s->cfg.neighbourhood)
         return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_dropout_masks: a first-order, steerable_2d or neighbourhood handle has no contraction slices to drop");
+    if (s->cfg.matrix_form) return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_dropout_masks: a matrix-form handle (LCNN, GCN_MW) has no contraction slices to drop");
     if (!masks) {
         s->drop_on = false;
         return GF_OK;
@@ -1189,6 +1192,9 @@ gf_status gf_smp_set_grad_allreduce(gf_smp *s, int on) {
     if (on && (s->cfg.per_size() || s->cfg.neighbourhood))
         return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_set_grad_allreduce: a first-order, steerable_2d or neighbourhood handle has no data-parallel "
                                                 "exchange (reduce the flat gradient)");
+    if (on && s->cfg.matrix_form)
+        return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_set_grad_allreduce: a matrix-form handle (LCNN, GCN_MW) has no data-parallel exchange (reduce the "
+                                                "flat gradient)");
     s->grad_allreduce = on ? 1 : 0;
     return GF_OK;
 }
@@ -1202,6 +1208,7 @@ gf_status gf_smp_backward_features(gf_smp *s, const float *params, float *grads,
     if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
     if (s->cfg.steerable_2d || s->cfg.unrestricted || s->cfg.neighbourhood)
         return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_backward_features: a steerable_2d, unrestricted or neighbourhood handle is no tower");
+    if (s->cfg.matrix_form) return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_backward_features: a matrix-form handle (LCNN, GCN_MW) is no tower");
     if (!d_feature) return fail(s->ctx, GF_ERR_INVALID, "gf_smp_backward_features: null feature gradient");
     gf_status st = gf::backward_check(s, &params, &grads, accumulate, d_feature);
     return st == GF_OK ? gf::backward_run(s, params, grads, accumulate, d_feature) : st;
@@ -1237,7 +1244,23 @@ gf_status gf_smp_set_fused(gf_smp *s, int on) {
 int gf_smp_receptive_field(const gf_smp *s, int mol, int level, int v, int *out, int capacity) {
     if (!s || !s->prepared || mol < 0 || mol >= s->lay.nMol || level < 0 || level > s->cfg.nLevels) return -1;
     const gfsmp::Molecule &M = s->lay.mols[mol];
+    if (s->cfg.matrix_form == 1) {   // LCNN: the k entries of rank position v's sequence (level 0: the vertex at that position)
+        const int V = s->cfg.max_nVertices, k = s->cfg.nNeighbors;
+        if (v < 0 || v >= V) return -1;
+        if (level == 0) {
+            if (capacity > 0) out[0] = s->lay.rl.order[(size_t)mol * V + v];
+            return 1;
+        }
+        for (int j = 0; j < k && j < capacity; ++j) out[j] = s->lay.rl.seq[((size_t)mol * V + v) * k + j];
+        return k;
+    }
     if (v < 0 || v >= M.V) return -1;
+    if (s->cfg.matrix_form) {   // GCN_MW: the non-zero columns of row v of A-hat, ascending (the same at every level)
+        const int v0 = s->lay.mol_first_vertex[mol];
+        const long long e0 = s->lay.rl.ptr[(size_t)v0 + v], n = s->lay.rl.ptr[(size_t)v0 + v + 1] - e0;
+        for (long long i = 0; i < n && i < capacity; ++i) out[i] = s->lay.rl.src[(size_t)(e0 + i)] - v0;
+        return (int)n;
+    }
     if (s->cfg.neighbourhood) {   // N_level(v), ascending (level 0: the vertex itself)
         if (level == 0) {
             if (capacity > 0) out[0] = v;
@@ -1260,6 +1283,16 @@ int gf_smp_receptive_field(const gf_smp *s, int mol, int level, int v, int *out,
 static long long smp_read_node(gf_smp *s, int mol, int level, int v, float *out, size_t capacity, bool adjacency) {
     if (!s || !s->prepared || !out || mol < 0 || mol >= s->lay.nMol || level < 0 || level > s->cfg.nLevels) return -1;
     if (adjacency ? level < 1 : !s->forwarded) return -1;
+    if (s->cfg.matrix_form) {   // GCN_MW: h_level[v] [H]; LCNN: a1[i] [C1] (level 1), c2[i] [C2] (level 2), i a rank position; no reduced adjacency
+        const bool lcnn = s->cfg.matrix_form == 1;
+        const size_t W = lcnn && level == 2 ? (size_t)s->cfg.nChanels2 : (size_t)s->cfg.nChanels;
+        const int nrows = lcnn ? s->cfg.max_nVertices : s->lay.mols[mol].V;
+        if (adjacency || (lcnn && level == 0) || v < 0 || v >= nrows || W > capacity) return -1;
+        const float *src = s->lv[level].f + ((size_t)s->lay.mol_first_vertex[mol] + v) * W;
+        if (hipMemcpyAsync(out, src, W * sizeof(float), hipMemcpyDeviceToHost, s->ctx->stream) != hipSuccess) return -1;
+        if (hipStreamSynchronize(s->ctx->stream) != hipSuccess) return -1;
+        return (long long)W;
+    }
     if (s->cfg.neighbourhood) {   // h_level[v] [H]; the models have no reduced adjacency
         const size_t H = (size_t)s->cfg.nChanels;
         if (adjacency || v < 0 || v >= s->lay.mols[mol].V || H > capacity) return -1;

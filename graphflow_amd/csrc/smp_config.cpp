@@ -65,6 +65,27 @@ bool rule_gated(const gf_smp_config *cfg) {
     return (cfg->neighbourhood == 4 || cfg->neighbourhood == 5) && rule_neighbourhood(&as2);
 }
 
+// matrix_form = 1, 2 (LCNN, GCN_MW): no other form, no cap, the fields each class reads
+bool rule_matrix_form(const gf_smp_config *cfg) {
+    if (cfg->matrix_form < 1 || cfg->matrix_form > 2) return false;
+    if (cfg->first_order || cfg->steerable_2d || cfg->unrestricted || cfg->neighbourhood || !plain_levels(cfg)) return false;
+    if (cfg->nChanels < 1 || cfg->nFeatures < 1 || cfg->nDepth < 0 || cfg->max_nVertices < 1) return false;
+    if (!no_cap(cfg) || cfg->max_nVertices > kMaxFieldVertices) return false;
+    if (cfg->matrix_form == 2) return cfg->nLevels >= 0 && cfg->nLevels <= 64;
+    return cfg->nLevels == 2 && cfg->nNeighbors >= 1 && cfg->nChanels2 >= 1 && cfg->nDense >= 1;
+}
+// ... and the widest operand row its kernels would index (rule_matrix_form holds)
+long long matrix_form_widest(const gf_smp_config *cfg) {
+    const long long FD = (long long)cfg->nFeatures * ((long long)cfg->nDepth + 1);
+    long long w = FD > cfg->nChanels ? FD : cfg->nChanels;
+    if (w > gf::kRowlistMaxWidth) return w;   // (keeps the products below inside a long long)
+    if (cfg->matrix_form == 1)
+        for (long long x : {(long long)cfg->nChanels2, (long long)cfg->nDense, (long long)cfg->nNeighbors * FD,
+                            (long long)cfg->nNeighbors * cfg->nChanels, (long long)cfg->max_nVertices * cfg->nChanels2})
+            w = x > w ? x : w;
+    return w;
+}
+
 }  // namespace
 
 #define GF_REFUSE(status, ...) return (std::snprintf(why, nwhy, __VA_ARGS__), (status))
@@ -85,6 +106,7 @@ gf_status resolve_config(const gf_smp_config *cfg, const ConfigEntry &entry, Con
         if (cfg->first_order == 1)   // (SMP_theta has no `_classification` class; first_order = 2, 3, 4 do: SMP_1D*_classification)
             GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: a first-order model (first_order = 1) has no classifier read-out");
         if (cfg->unrestricted) GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: the Unrestricted_SMP_* models have no `_classification` class");
+        if (cfg->matrix_form) GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: LCNN / GCN_MW have no `_classification` class");
         if (cfg->neighbourhood == 6 || cfg->neighbourhood == 7)
             GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: GCN_3D / GRU_GCN_3D have no `_classification` class");
         if (cfg->neighbourhood)
@@ -94,6 +116,30 @@ gf_status resolve_config(const gf_smp_config *cfg, const ConfigEntry &entry, Con
         if (nClass < 2) GF_REFUSE(GF_ERR_INVALID, "gf_smp_create_classifier: nClass = %d (at least 2)", nClass);
     }
     // ---- the configuration, family by family ----
+    if (cfg->matrix_form) {   // LCNN, GCN_MW (smp_level_rowlist.hip)
+        if (entry.kind == ConfigEntry::Tower)
+            GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_model_create: LCNN / GCN_MW (matrix_form = %d) are no towers", cfg->matrix_form);
+        if (!rule_matrix_form(cfg))
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: matrix_form = %d (1: LCNN, 2: GCN_MW) needs first_order = steerable_2d = unrestricted = "
+                                      "neighbourhood = physics = nContractions = custom_matmul = 0, max_receptive_field (%d) == max_nVertices (%d) "
+                                      "<= 4096, nChanels, nFeatures >= 1, nDepth >= 0, nLevels (%d) in 0 .. 64 for GCN_MW and == 2 for LCNN, and "
+                                      "for LCNN nNeighbors (%d), nChanels2 (%d), nDense (%d) >= 1", cfg->matrix_form, cfg->max_receptive_field,
+                      cfg->max_nVertices, cfg->nLevels, cfg->nNeighbors, cfg->nChanels2, cfg->nDense);
+        const long long wide = matrix_form_widest(cfg);
+        if (wide > gf::kRowlistMaxWidth)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: matrix_form = %d with an operand %lld floats wide: the row-list level indexes an operand row "
+                                      "and its tile counts with ints: at most %d (F', nChanels, nChanels2, nDense, nNeighbors F', nNeighbors "
+                                      "nChanels, max_nVertices nChanels2)", cfg->matrix_form, wide, gf::kRowlistMaxWidth);
+        Config c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, 0};
+        c.nContractions = 0;
+        c.max_nVertices = cfg->max_nVertices;
+        c.matrix_form = cfg->matrix_form;
+        if (cfg->matrix_form == 1) c.nNeighbors = cfg->nNeighbors, c.nChanels2 = cfg->nChanels2, c.nDense = cfg->nDense;
+        if (param_count(c) > (size_t)kMaxInt)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: matrix_form = %d with %zu parameters: the count must fit an int", cfg->matrix_form, param_count(c));
+        *out = c;
+        return GF_OK;
+    }
     if (cfg->neighbourhood == 6 || cfg->neighbourhood == 7) {   // GCN_3D, GRU_GCN_3D (smp_level_third.hip): nLevels = 0 is a model
         if (cfg->nChanels > gf::kThirdMaxChanels)
             GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: neighbourhood = %d (6: GCN_3D, 7: GRU_GCN_3D) with nChanels = %d: the third-order pool packs "

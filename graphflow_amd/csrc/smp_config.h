@@ -33,6 +33,12 @@ inline size_t smp_third_lds_bytes(int H, int members) {
     return 8 * 2 * (size_t)kThirdCand + 4 * ((size_t)kThirdBins + 256 + 8) + sizeof(float) * ((size_t)H + (size_t)H * H + (size_t)members * H);
 }
 inline int smp_third_max_members(int H) { return (int)((160 * 1024 - smp_third_lds_bytes(H, 0)) / (sizeof(float) * (size_t)H)); }
+// the row-list level (smp_level_rowlist.hip; matrix_form = 1, 2): no weights resident in LDS, so no channel limit of that kind.  Its kernels
+// index a column of an operand row and a tile of a launch with ints: a width (slots * Cin, or N) of at most 2^16 keeps slot * Cin + c, the
+// 64-wide tiles of a row (2^10) and a partial image of width x width floats (2^32 elements, counted in a size_t) in range; every launch
+// checks its own tile count (rows / 128 x 2^10, or 2^9 x 2^10 x splits) against 2^31 - 1.
+constexpr int kRowlistMaxWidth = 65536;
+constexpr int kRowlistSplits = 256;   // most partial images of a weight gradient, folded in ascending order
 }  // namespace gf
 
 namespace gfsmp {

@@ -117,6 +117,22 @@ gf_status smp_wgrad_channel_maxima(gf_ctx *ctx, const float *fprev, long long pr
                                    unsigned *words);
 gf_status smp_wgrad_fp32_c64(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int kchunk, int splits, float *part,
                              const int *trow);   // (smp_level_c64.hip: the fp32 kernel's launch, for smp_wgrad_partials)
+
+// ---- the row-list GEMM level (smp_level_rowlist.hip): A[r][slot * Cin + c] = sum over the entries e of row r with that slot of
+// coef[e] * X[src[e]][c], as a CSR list whose rows are in ascending slot order; device pointers ----
+struct RowList {
+    const long long *ptr = nullptr;   // [R + 1]
+    const int *src = nullptr, *slot = nullptr;
+    const float *coef = nullptr;      // null: every coefficient is 1
+    const long long *sptr = nullptr;  // optional [R slots + 1]: the first entry of every (row, slot); the kernels then search nothing
+};
+// out [R][N] = act(A B + bias) (act 1: LeakyReLU 0.01; bias may be null); tb: B is the forward's [slots][N][Cin], read transposed per slot
+gf_status smp_rowlist_product(gf_ctx *ctx, const RowList &list, bool tb, int R, int slots, int Cin, int N, const float *X, const float *B,
+                              const float *bias, int act, float *out);
+// dB [slots Cin][N] += A^T dOut, at most kRowlistSplits partial images in the context's workspace, folded in ascending order
+gf_status smp_rowlist_wgrad(gf_ctx *ctx, const RowList &list, int R, int slots, int Cin, int N, const float *X, const float *dOut, float *dB);
+size_t smp_rowlist_wgrad_ws_bytes(int R, int K, int N);
+gf_status smp_rowlist_bias_grad(gf_ctx *ctx, const float *dOut, int R, int N, float *db);   // db [N] += the column sums of dOut
 }
 
 
@@ -281,6 +297,10 @@ struct gf_smp {
         float *nb_pool = nullptr;
         int nb_max_members = 0;
     };
+    // matrix-form handles (cfg.matrix_form; smp_level_rowlist.hip): the level's row lists, forward and transposed.  GCN_MW: lv[l].f = h_l,
+    // lv[l].df = dh_l and then dz_l in place, [vertices][H].  LCNN: lv[1].f = a1 and lv[1].df = da1 / dc1 [nMol V][C1], lv[2].f = c2 and
+    // lv[2].df = dc2 [nMol V][C2], lv[2].Q = the gradient of the dense layer [nMol][nDense]; g = the dense layer itself.
+    gf::RowList rl_fwd, rl_bwd;
     // the list N(v) = {v} over the batch's vertices (form 6: the sum instantiation of nbh_level_fwd over it hands the pooled n on unchanged)
     long long *nb_id_ptr = nullptr;
     int *nb_id_idx = nullptr;
@@ -434,6 +454,11 @@ gf_status smp_third_pool_fwd_launch(gf_ctx *ctx, int H, int nV, int max_members,
                                     int *sel);
 gf_status smp_third_pool_bwd_launch(gf_ctx *ctx, int H, int nV, const long long *ptr, const int *idx, const long long *tptr, const int *tidx,
                                     const float *hprev, const int *sel, const float *dn, float *dhprev);
+// LCNN, GCN_MW (cfg.matrix_form = 1, 2; smp_level_rowlist.hip): the whole sweeps of such a handle, and its gf_smp_prepare (smp_prepare.hip).
+// params / grads: GCN_MW W_0; W_l; W.  LCNN F1, b1, F2, b2, Dm, W.
+gf_status smp_matrix_form_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature);
+gf_status smp_matrix_form_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature);
+gf_status smp_matrix_form_backward(gf_smp *s, const float *params, float *grads, int accumulate);
 // smp_theta_prepare (smp_prepare.hip): gf_smp_prepare of a first-order handle -- the th_* tables, none of the other kinds' buffers.
 gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature);
 // the first-order read-out of level l (smp_field_level.hip): sh[n] = column sums over the node's s rows (ShrinkMatrix), vf = LeakyReLU(sh);

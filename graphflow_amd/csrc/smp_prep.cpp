@@ -850,4 +850,171 @@ void build_batch_neighbourhood(const Config &cfg, int nMol, const int *nVertices
     }
 }
 
+// LCNN, GCN_MW (Config::matrix_form).
+void matrix_form_molecule(const Config &cfg, int molV, const int *adj, const double *feature, MatrixFormMolecule *out) {
+    const int F = cfg.nFeatures;
+    if (cfg.matrix_form == 2) {
+        hop_distances(molV, adj, &out->hops);
+        wl_features(cfg, molV, feature, out->hops, &out->wl);
+        // create_norm_adj: D = the row sums of A + I, d = 1 / sqrt(D) where D > 0 (else D itself), P = D (A + I), A-hat = P D
+        std::vector<double> d((size_t)molV, 0.0);
+        auto a1 = [&](int i, int j) { return (double)adj[(size_t)i * molV + j] + (i == j ? 1.0 : 0.0); };
+        for (int i = 0; i < molV; ++i) {
+            for (int j = 0; j < molV; ++j) d[i] += a1(i, j);
+            if (d[i] > 0.0) d[i] = 1.0 / std::sqrt(d[i]);
+        }
+        out->norm_adj.assign((size_t)molV * molV, 0.0);
+        for (int i = 0; i < molV; ++i)
+            for (int j = 0; j < molV; ++j) out->norm_adj[(size_t)i * molV + j] = (d[i] * a1(i, j)) * d[j];
+        return;
+    }
+    // update_adjacency, update_feature: dummy vertices have no edges and zero features
+    const int V = cfg.max_nVertices, FD = cfg.fdim(), k = cfg.nNeighbors;
+    std::vector<int> padj((size_t)V * V, 0);
+    std::vector<double> pfeat((size_t)V * F, 0.0);
+    for (int i = 0; i < molV; ++i) {
+        for (int j = 0; j < molV; ++j) padj[(size_t)i * V + j] = adj[(size_t)i * molV + j];
+        for (int f = 0; f < F; ++f) pfeat[(size_t)i * F + f] = feature[(size_t)i * F + f];
+    }
+    hop_distances(V, padj.data(), &out->hops);
+    wl_features(cfg, V, pfeat.data(), out->hops, &out->wl);
+    // rank_vertices (LCNN.h:276-292): the exchange sort, descending
+    std::vector<int> &order = out->order;
+    order.resize((size_t)V);
+    for (int v = 0; v < V; ++v) order[v] = v;
+    for (int i = 0; i < V; ++i)
+        for (int j = i + 1; j < V; ++j)
+            if (compare_wl(out->wl, FD, order[i], order[j]) < 0) std::swap(order[i], order[j]);
+    // find_sequence (LCNN.h:294-320)
+    out->seq.assign((size_t)V * k, molV);
+    for (int i = 0; i < V; ++i) {
+        int j = 0;
+        for (int dd = 0; dd < V && j < k; ++dd)
+            for (int v = 0; v < V && j < k; ++v)
+                if (out->hops[(size_t)order[i] * V + order[v]] == dd && order[v] < molV) out->seq[(size_t)i * k + j++] = order[v];
+    }
+}
+
+bool lcnn_reads_past(const Config &cfg, int molV, const std::vector<int> &seq) {
+    if (molV < cfg.max_nVertices) return false;
+    for (size_t i = 0; i < seq.size(); ++i)
+        if (seq[i] >= cfg.max_nVertices) return true;
+    return false;
+}
+
+int build_batch_matrix_form(const Config &cfg, int nMol, const int *nVertices, const int *adj, const double *feature, BatchLayout *out) {
+    const int L = cfg.nLevels, FD = cfg.fdim(), F = cfg.nFeatures;
+    const bool lcnn = cfg.matrix_form == 1;
+    const int V = cfg.max_nVertices, k = lcnn ? cfg.nNeighbors : 1;
+    out->device_tables = false;
+    out->nMol = nMol;
+    out->mols.assign(nMol, Molecule());
+    out->mol_first_vertex.assign(nMol + 1, 0);   // (the first ROW of a molecule: LCNN's molecules have V rows each)
+    std::vector<size_t> adj_off(nMol + 1, 0), feat_off(nMol + 1, 0);
+    out->max_vertices = 1;
+    for (int m = 0; m < nMol; ++m) {
+        out->mol_first_vertex[m + 1] = out->mol_first_vertex[m] + (lcnn ? V : nVertices[m]);
+        adj_off[m + 1] = adj_off[m] + (size_t)nVertices[m] * nVertices[m];
+        feat_off[m + 1] = feat_off[m] + (size_t)nVertices[m] * F;
+        out->max_vertices = std::max(out->max_vertices, nVertices[m]);
+    }
+    const int rows = out->mol_first_vertex[nMol];
+    out->x.assign((size_t)rows * FD, 0.f);
+    out->nb_vertex_mol.assign((size_t)rows, 0);
+    BatchLayout::RowLists &rl = out->rl;
+    rl.order.assign(lcnn ? (size_t)nMol * V : 0, 0);
+    rl.seq.assign(lcnn ? (size_t)nMol * V * k : 0, 0);
+    rl.ptr.assign((size_t)rows + 1, 0);
+    rl.tptr.assign((size_t)rows + 1, 0);
+    std::vector<MatrixFormMolecule> mf((size_t)nMol);
+    std::atomic<int> bad(nMol);
+    parallel_for(nMol, [&](int m) {
+        const int molV = nVertices[m], r0 = out->mol_first_vertex[m], nr = out->mol_first_vertex[m + 1] - r0;
+        MatrixFormMolecule &M = mf[(size_t)m];
+        matrix_form_molecule(cfg, molV, adj + adj_off[m], feature + feat_off[m], &M);
+        out->mols[m].V = molV;
+        out->mols[m].hops = M.hops;
+        for (size_t i = 0; i < (size_t)nr * FD; ++i) out->x[(size_t)r0 * FD + i] = (float)M.wl[i];
+        for (int r = 0; r < nr; ++r) out->nb_vertex_mol[(size_t)r0 + r] = m;
+        if (lcnn) {
+            if (lcnn_reads_past(cfg, molV, M.seq)) {
+                int seen = bad.load();
+                while (m < seen && !bad.compare_exchange_weak(seen, m)) {}
+                return;
+            }
+            for (int i = 0; i < V; ++i) rl.order[(size_t)m * V + i] = M.order[i];
+            for (size_t i = 0; i < (size_t)V * k; ++i) rl.seq[(size_t)m * V * k + i] = M.seq[i];
+            for (int i = 0; i < V; ++i) {   // k entries per row, one per slot; the transposed row of u counts the (i, j) that read u
+                rl.ptr[(size_t)r0 + i + 1] = k;
+                for (int j = 0; j < k; ++j) rl.tptr[(size_t)r0 + M.seq[(size_t)i * k + j] + 1] += 1;
+            }
+        } else {
+            for (int i = 0; i < molV; ++i)
+                for (int j = 0; j < molV; ++j)
+                    if (M.norm_adj[(size_t)i * molV + j] != 0.0) {
+                        rl.ptr[(size_t)r0 + i + 1] += 1;
+                        rl.tptr[(size_t)r0 + j + 1] += 1;
+                    }
+        }
+    });
+    if (bad.load() < nMol) return bad.load();
+    for (int r = 0; r < rows; ++r) {
+        rl.ptr[(size_t)r + 1] += rl.ptr[(size_t)r];
+        rl.tptr[(size_t)r + 1] += rl.tptr[(size_t)r];
+    }
+    const size_t ne = (size_t)rl.ptr[(size_t)rows];
+    rl.src.assign(ne, 0), rl.slot.assign(ne, 0), rl.coef.assign(ne, 1.f);
+    rl.tsrc.assign(ne, 0), rl.tslot.assign(ne, 0), rl.tcoef.assign(ne, 1.f);
+    parallel_for(nMol, [&](int m) {   // (a molecule's rows own disjoint ranges of both lists)
+        const int molV = nVertices[m], r0 = out->mol_first_vertex[m];
+        const MatrixFormMolecule &M = mf[(size_t)m];
+        if (lcnn) {
+            for (int i = 0; i < V; ++i)
+                for (int j = 0; j < k; ++j) {
+                    const size_t e = (size_t)rl.ptr[(size_t)r0 + i] + j;
+                    rl.src[e] = r0 + M.seq[(size_t)i * k + j];
+                    rl.slot[e] = j;
+                }
+            std::vector<int64_t> fill((size_t)V);
+            for (int u = 0; u < V; ++u) fill[u] = rl.tptr[(size_t)r0 + u];
+            for (int j = 0; j < k; ++j)   // slot-major, then ascending row: the fixed order of the reverse gather
+                for (int i = 0; i < V; ++i) {
+                    const size_t e = (size_t)fill[M.seq[(size_t)i * k + j]]++;
+                    rl.tsrc[e] = r0 + i;
+                    rl.tslot[e] = j;
+                }
+        } else {
+            for (int i = 0; i < molV; ++i) {
+                int64_t e = rl.ptr[(size_t)r0 + i], t = rl.tptr[(size_t)r0 + i];
+                for (int j = 0; j < molV; ++j) {
+                    const double a = M.norm_adj[(size_t)i * molV + j], at = M.norm_adj[(size_t)j * molV + i];
+                    if (a != 0.0) rl.src[(size_t)e] = r0 + j, rl.coef[(size_t)e++] = (float)a;
+                    if (at != 0.0) rl.tsrc[(size_t)t] = r0 + j, rl.tcoef[(size_t)t++] = (float)at;   // (consumer j of source i)
+                }
+            }
+        }
+    });
+    rl.sptr.clear(), rl.tsptr.clear();
+    if (lcnn) {   // the entries are ordered by (row, slot): counts per (row, slot), then their prefix sums
+        auto offsets = [&](const tvec<int64_t> &ptr, const tvec<int> &slot, tvec<int64_t> *sp) {
+            sp->assign((size_t)rows * k + 1, 0);
+            for (int r = 0; r < rows; ++r)
+                for (int64_t e = ptr[(size_t)r]; e < ptr[(size_t)r + 1]; ++e) (*sp)[(size_t)r * k + slot[(size_t)e] + 1] += 1;
+            for (size_t i = 0; i < (size_t)rows * k; ++i) (*sp)[i + 1] += (*sp)[i];
+        };
+        offsets(rl.ptr, rl.slot, &rl.sptr);
+        offsets(rl.tptr, rl.tslot, &rl.tsptr);
+    }
+    out->level.assign(L + 1, LevelLayout());
+    for (int l = 0; l <= L; ++l) {
+        out->level[l].nNodes = rows;
+        out->level[l].rows = rows;
+    }
+    out->top_node_of_vertex.clear();
+    out->node_of_vertex.clear();
+    out->nb_lists.clear();
+    out->nb_list_of_level.clear();
+    return -1;
+}
+
 }  // namespace gfsmp

@@ -91,6 +91,11 @@ struct Config {
     // 6, 7: GCN_3D, GRU_GCN_3D (GraphFlow/GCN_3D.h, GRU_GCN_3D.h; smp_level_third.hip): forms 2 and 4 with n_l[v] = KMax(RisiLayer3D of the
     // members, K = nChanels) as the aggregate; N_l(v) = hop distance <= min(l, max_Radius) in both; the parameter blocks of forms 2 / 4.
     int neighbourhood = 0, max_Radius = 0;
+    // 1: LCNN, 2: GCN_MW (GraphFlow/LCNN.h, GCN_MW.h; gf_smp_config.matrix_form; smp_level_rowlist.hip): products whose A operand is a short list
+    // of rows of the level below per output row.  2: nChanels = H; W_0 [F'][H] (first_block), W_l [H][H] (one Matrix per level), W [H].
+    // 1: nLevels = 2 (the two convolutions), nChanels = C1, max_nVertices = V, nNeighbors = k; F1 [k][F'][C1] (first_block); level 1: b1
+    // [C1], F2 [k][C1][C2]; level 2: b2 [C2], Dm [nDense][V C2]; W [nDense] -- each drawn as a Vector.  None of the other forms' fields is set.
+    int matrix_form = 0, nNeighbors = 0, nChanels2 = 0, nDense = 0;
     bool gated() const { return neighbourhood == 4 || neighbourhood == 5 || neighbourhood == 7; }
     bool third_order() const { return neighbourhood == 6 || neighbourhood == 7; }
     int nb_radius(int l) const { return neighbourhood == 1 ? 1 : neighbourhood == 3 || l < max_Radius ? l : max_Radius; }   // of N_l (form 1: the adjacency itself; 3 alone ignores max_Radius)
@@ -164,6 +169,16 @@ struct Config {
         if (gated()) return b;   // (every block is shared: shared_blocks())
         auto sizes = [&b](std::initializer_list<LevelBlocks::SizeTerm> t) { for (const LevelBlocks::SizeTerm &x : t) b.size[b.nsize++] = x; };
         auto matrix = [&b](size_t n, size_t div = 0) { b.mat[b.nmat++] = {n, div ? div : n}; };   // (div = 0: a Vector, divided by its own size)
+        if (matrix_form == 2) {   // W_l [H][H], a Matrix
+            matrix(Cl * Cl, Cl);
+            return b;
+        }
+        if (matrix_form == 1) {   // b1 then F2 (l = 1), b2 then Dm (l = 2)
+            const size_t k = (size_t)nNeighbors, C1 = (size_t)nChanels, C2 = (size_t)nChanels2;
+            matrix(l == 1 ? C1 : C2);
+            matrix(l == 1 ? k * C1 * C2 : (size_t)nDense * (size_t)max_nVertices * C2);
+            return b;
+        }
         if (neighbourhood) {   // W1_l [H][F'], W2_l [H][H]: no per-size entries, no bias (l = 0: W1_0 is first_block())
             matrix(Cl * fdim(), Cl);
             matrix(Cl * Cl, Cl);
@@ -191,6 +206,8 @@ struct Config {
     }
     Block first_block() const {   // H [C][F (D + 1)]; W1_0 [H][F'] of a neighbourhood form (a Matrix: 10 x rows), W of a gated one (a Vector)
         const size_t n = (size_t)nChanels * fdim();
+        if (matrix_form == 2) return {n, (size_t)fdim()};   // W_0 [F'][H], a Matrix of F' rows
+        if (matrix_form == 1) return {n * (size_t)nNeighbors, n * (size_t)nNeighbors};   // F1 [k][F'][C1], a Vector
         return {n, neighbourhood && !gated() ? (size_t)nChanels : n};
     }
     // W [readout_rows()][top_channels()] (SMP_2D_ver6_classification.h:211-217), drawn as one Vector; none in a physics tower, which ends in
@@ -199,7 +216,7 @@ struct Config {
         const size_t n = physics ? 0 : (size_t)readout_rows() * top_channels();
         return {n, n};
     }
-    int top_channels() const { return first_order >= 2 || steerable_2d ? level_channels(nLevels) : nChanels;  }   // width of the graph feature and of W's rows
+    int top_channels() const { return matrix_form == 1 ? nDense : first_order >= 2 || steerable_2d ? level_channels(nLevels) : nChanels;  }   // width of the graph feature and of W's rows
     int readout_rows() const { return nClass > 1 ? nClass : 1; }   // rows of W: [1][C] is the regression's [C]
     bool square() const { return !physics || uniform; }   // K_l is [nContractions C][C] at every level
     int level_channels(int l) const {
@@ -395,6 +412,18 @@ struct BatchLayout {
     std::vector<NeighbourList> nb_lists;
     std::vector<int> nb_list_of_level;   // [L + 1], [0] unused
     tvec<int> nb_vertex_mol;             // [vertices]
+    // Config::matrix_form (build_batch_matrix_form): the row lists of the level's A operand, forward and transposed, as CSR over the batch's
+    // rows (GCN_MW: global vertex ids; LCNN: molecule m's rows are m V .. m V + V - 1) -- per entry the source row, the slot and the
+    // coefficient, a row's entries in ascending slot order and, inside a slot, ascending source row.  LCNN also keeps every molecule's
+    // order [V] and sequence [V][k] for introspection; mols keep V (the molecule's own vertex count).
+    struct RowLists {
+        tvec<int64_t> ptr, tptr;   // [rows + 1]
+        tvec<int64_t> sptr, tsptr;  // LCNN: [rows k + 1] the first entry of every (row, slot), so that the kernels search nothing (one slot: ptr itself)
+        tvec<int> src, slot, tsrc, tslot;
+        tvec<float> coef, tcoef;
+        std::vector<int> order, seq;
+    };
+    RowLists rl;
 };
 
 // coulomb: NULL, or the molecules' V x V Coulomb matrices back to back (DenseGraph::coulomb) -- the reduced adjacency of
@@ -409,6 +438,20 @@ void build_batch_theta(const Config &cfg, int nMol, const int *nVertices, const 
 // The batch of a neighbourhood model (Config::neighbourhood): hop distances, the shell-sum features x, the neighbour lists and their
 // transposes; none of the field, selection or reduced-adjacency tables.  level[l]: nNodes = rows = vertices.
 void build_batch_neighbourhood(const Config &cfg, int nMol, const int *nVertices, const int *adj, const double *feature, BatchLayout *out);
+
+// One molecule of a matrix-form model (Config::matrix_form), as the class derives it.  LCNN (LCNN.h:175-320): the molecule padded to V =
+// max_nVertices vertices, hops and wl of the padded graph, order [V] and seq [V][k]; a pad entry holds molV.  GCN_MW (DenseGraph.h:69-111,
+// GCN_MW.h:166-206): hops, wl and norm_adj [molV][molV] = d_i (A + I)[i][j] d_j in double.
+struct MatrixFormMolecule {
+    std::vector<int> hops, order, seq;
+    std::vector<double> wl, norm_adj;
+};
+void matrix_form_molecule(const Config &cfg, int molV, const int *adj, const double *feature, MatrixFormMolecule *out);
+// does a sequence with pad entries read past the class's matrix (molV == max_nVertices)?
+bool lcnn_reads_past(const Config &cfg, int molV, const std::vector<int> &seq);
+// The batch of a matrix-form model: x, the row lists (BatchLayout::rl), level[l]: nNodes = rows = the batch's rows.  Returns the first
+// molecule lcnn_reads_past, or -1 (the batch is then complete).
+int build_batch_matrix_form(const Config &cfg, int nMol, const int *nVertices, const int *adj, const double *feature, BatchLayout *out);
 
 }  // namespace gfsmp
 #endif

@@ -1028,6 +1028,92 @@ gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, c
     return GF_OK;
 }
 
+// gf_smp_prepare of a matrix-form handle (LCNN, GCN_MW; smp_level_rowlist.hip): the host builds x and the level's row lists, forward and
+// transposed (gfsmp::build_batch_matrix_form); the device gets those and one activation / gradient buffer per level.
+gf_status smp_matrix_form_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature) {
+    gf_ctx *ctx = s->ctx;
+    const gfsmp::Config &cfg = s->cfg;
+    const bool lcnn = cfg.matrix_form == 1;
+    long long rows = 0, entries = 0;
+    for (int m = 0; m < nMol; ++m) {
+        if (nVertices[m] > cfg.max_nVertices)
+            return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare: molecule %d has %d vertices, the model was created with max_nVertices = %d", m,
+                        nVertices[m], cfg.max_nVertices);
+        rows += lcnn ? cfg.max_nVertices : nVertices[m];
+        entries += lcnn ? (long long)cfg.max_nVertices * cfg.nNeighbors : (long long)nVertices[m] * nVertices[m];   // (an upper bound)
+    }
+    if (rows > 0x7fffffffll || entries > 0x7fffffffll)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare: a matrix-form batch of %lld rows and up to %lld list entries (2^31 - 1 each)", rows, entries);
+    ensure_upload_stream(s);
+    release(s);
+    s->tab_stats = nullptr;
+    s->h_tab_stats.clear();
+    s->h_covered.clear();
+    s->rl_fwd = s->rl_bwd = RowList();
+    const int bad = gfsmp::build_batch_matrix_form(cfg, nMol, nVertices, adj, feature, &s->lay);
+    if (bad >= 0)
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare: molecule %d has max_nVertices = %d vertices and a vertex that reaches fewer than nNeighbors = %d "
+                                         "of them: LCNN pads its sequence with row %d, past its matrix", bad, cfg.max_nVertices, cfg.nNeighbors,
+                    cfg.max_nVertices);
+    const gfsmp::BatchLayout &B = s->lay;
+    const int L = cfg.nLevels;
+    const size_t R = (size_t)rows, H = (size_t)cfg.nChanels;
+    s->lv.assign(L + 1, gf_smp::DevLevel());
+    Taker t = {s};
+    t.put(&s->rl_fwd.ptr, B.rl.ptr);
+    t.put(&s->rl_fwd.src, B.rl.src);
+    t.put(&s->rl_fwd.slot, B.rl.slot);
+    t.put(&s->rl_fwd.coef, B.rl.coef);
+    t.put(&s->rl_bwd.ptr, B.rl.tptr);
+    t.put(&s->rl_bwd.src, B.rl.tsrc);
+    t.put(&s->rl_bwd.slot, B.rl.tslot);
+    t.put(&s->rl_bwd.coef, B.rl.tcoef);
+    if (lcnn) {
+        t.put(&s->rl_fwd.sptr, B.rl.sptr);
+        t.put(&s->rl_bwd.sptr, B.rl.tsptr);
+    } else {   // one slot: a row's entries are the slot's
+        s->rl_fwd.sptr = s->rl_fwd.ptr;
+        s->rl_bwd.sptr = s->rl_bwd.ptr;
+    }
+    size_t ws = 1 << 20;
+    if (lcnn) {
+        const size_t C2 = (size_t)cfg.nChanels2, k = (size_t)cfg.nNeighbors;
+        t.alloc(&s->lv[1].f, R * H);
+        t.alloc(&s->lv[1].df, R * H);
+        t.alloc(&s->lv[2].f, R * C2);
+        t.alloc(&s->lv[2].df, R * C2);
+        t.alloc(&s->lv[2].Q, (size_t)nMol * cfg.nDense);
+        t.alloc(&s->g, (size_t)nMol * cfg.nDense);
+        ws = std::max(ws, std::max(smp_rowlist_wgrad_ws_bytes((int)R, (int)(k * cfg.fdim()), (int)H), smp_rowlist_wgrad_ws_bytes((int)R, (int)(k * H), (int)C2)));
+    } else {
+        for (int l = 0; l <= L; ++l) {
+            t.alloc(&s->lv[l].f, R * H);
+            t.alloc(&s->lv[l].df, R * H);
+        }
+        t.alloc(&s->g, (size_t)nMol * H);
+        ws = std::max(ws, std::max(smp_rowlist_wgrad_ws_bytes((int)R, cfg.fdim(), (int)H), smp_rowlist_wgrad_ws_bytes((int)R, (int)H, (int)H)));
+    }
+    t.put(&s->x, B.x);
+    t.alloc(&s->yhat, (size_t)nMol);
+    t.alloc(&s->dy, (size_t)nMol);
+    t.put(&s->top_node_mol, B.nb_vertex_mol);
+    t.put(&s->mol_ptr, B.mol_first_vertex);
+    if (t.st != GF_OK) return t.st;
+    s->gru_s = s->gru_t = s->gru_ds = s->gru_dt = s->gru_acc = nullptr;
+    s->nb_id_ptr = nullptr;
+    s->nb_id_idx = nullptr;
+    s->wbound = nullptr;
+    s->sh = s->vf = s->dsh = s->colpart = nullptr;
+    s->cls_scores = s->cls_prob = s->cls_dz = s->cls_dg = nullptr;
+    s->mol_nodes = nullptr;
+    s->P = nullptr;
+    s->P_count = 0;
+    s->ws_need = ws;   // (the weight gradients' partial images; the dense layer's TN product grows the workspace for its own)
+    GF_HIP_TRY(ctx, hipStreamSynchronize(upload_stream(s)));
+    s->prepared = true;
+    return GF_OK;
+}
+
 // ints of a level's row-class buffer (see row_class_count), and its builder: three launches on `stream` behind whatever wrote trowf
 size_t smp_row_class_ints(int rows) { return 4 + 2 * ((size_t)rows + 64) + (size_t)(rows + kRcBlock - 1) / kRcBlock + 1; }
 gf_status smp_build_row_classes(gf_ctx *ctx, hipStream_t stream, const int *trowf, int rows, int *buf) {
@@ -1067,6 +1153,9 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((s->cfg.steerable_2d || s->cfg.unrestricted || s->cfg.neighbourhood) && coulomb)   // (these classes have no use_coulomb constructor: their adjacency is the molecule's)
         return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_coulomb: a steerable_2d, unrestricted or neighbourhood handle has no Coulomb adjacency");
+    if (s->cfg.matrix_form && coulomb)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_coulomb: a matrix-form handle (LCNN, GCN_MW) has no Coulomb adjacency");
+    if (s->cfg.matrix_form) return gf::smp_matrix_form_prepare(s, nMol, nVertices, adj, feature);
     if (s->cfg.neighbourhood) return gf::smp_neighbourhood_prepare(s, nMol, nVertices, adj, feature);
     if (s->cfg.per_size()) return gf::smp_theta_prepare(s, nMol, nVertices, adj, feature);   // (first order: no reduced adjacency, coulomb is inert)
     gf_status st = gf::choose_plan(s, nMol, nVertices, adj, coulomb);
@@ -1112,6 +1201,32 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
     return GF_OK;
 }
 
+/* Host only: one molecule of a matrix-form configuration as gf_smp_prepare derives it -- LCNN's order and sequence, GCN_MW's A-hat. */
+gf_status gf_smp_matrix_form_molecule_host(const gf_smp_config *cfg, int V, const int *adj, const double *feature, int *order, int *sequence,
+                                           double *norm_adj) {
+    if (!cfg || !adj || !feature) return fail(nullptr, GF_ERR_INVALID, "gf_smp_matrix_form_molecule_host: bad argument");
+    gfsmp::Config c;
+    char why[640];
+    const gf_status verdict = gfsmp::resolve_config(cfg, gfsmp::kHandleEntry, &c, why, sizeof why);
+    if (verdict != GF_OK) return fail(nullptr, verdict, "%s", why);
+    if (!c.matrix_form) return fail(nullptr, GF_ERR_INVALID, "gf_smp_matrix_form_molecule_host: matrix_form = 0 is no matrix-form model");
+    if (V < 1 || V > c.max_nVertices)
+        return fail(nullptr, GF_ERR_INVALID, "gf_smp_matrix_form_molecule_host: %d vertices, the configuration has max_nVertices = %d", V, c.max_nVertices);
+    if (c.matrix_form == 1 ? !order || !sequence : !norm_adj) return fail(nullptr, GF_ERR_INVALID, "gf_smp_matrix_form_molecule_host: missing output");
+    gfsmp::MatrixFormMolecule m;
+    gfsmp::matrix_form_molecule(c, V, adj, feature, &m);
+    if (c.matrix_form == 2) {
+        for (size_t i = 0; i < m.norm_adj.size(); ++i) norm_adj[i] = m.norm_adj[i];
+        return GF_OK;
+    }
+    if (gfsmp::lcnn_reads_past(c, V, m.seq))
+        return fail(nullptr, GF_ERR_INVALID, "gf_smp_matrix_form_molecule_host: the molecule has max_nVertices = %d vertices and a vertex that reaches fewer "
+                                             "than nNeighbors = %d of them: LCNN pads its sequence with row %d, past its matrix", V, c.nNeighbors, V);
+    for (size_t i = 0; i < m.order.size(); ++i) order[i] = m.order[i];
+    for (size_t i = 0; i < m.seq.size(); ++i) sequence[i] = m.seq[i];
+    return GF_OK;
+}
+
 /* Host-only graph preparation of ONE molecule (no device needed): receptive fields phi[l][v] as
  * [L+1][V][cap+1] ints (slot 0 = size) and, optionally, the WL features [V][F(D+1)].  Lets the host logic be tested
  * on a CPU-only box and inspected by callers. */
@@ -1123,6 +1238,9 @@ gf_status gf_smp_prepare_molecule_host(const gf_smp_config *cfg, int V, const in
     gfsmp::Config resolved;
     char why[640];
     const bool refused = gfsmp::resolve_config(cfg, {gfsmp::ConfigEntry::Tower, 0, 0.0}, &resolved, why, sizeof why) != GF_OK;
+    if (cfg->matrix_form)
+        return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: a matrix-form model (LCNN, GCN_MW) has no receptive fields: "
+                                             "gf_smp_matrix_form_molecule_host");
     if (cfg->neighbourhood)   // (about this call, not the configuration)
         return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: a neighbourhood model (NeuralFingerprint, GCN_1D, GCN_2D) has no receptive fields");
     if (refused && cfg->unrestricted)

@@ -13,7 +13,8 @@ class SMPConfig(C.Structure):
     _fields_ = [("nLevels", C.c_int), ("nChanels", C.c_int), ("nFeatures", C.c_int), ("nDepth", C.c_int),
                 ("max_receptive_field", C.c_int), ("has_WL_ordering", C.c_int), ("nContractions", C.c_int),
                 ("custom_matmul", C.c_int), ("physics", C.c_int), ("first_order", C.c_int), ("max_nVertices", C.c_int),
-                ("steerable_2d", C.c_int), ("unrestricted", C.c_int), ("neighbourhood", C.c_int), ("max_Radius", C.c_int)]
+                ("steerable_2d", C.c_int), ("unrestricted", C.c_int), ("neighbourhood", C.c_int), ("max_Radius", C.c_int),
+                ("matrix_form", C.c_int), ("nNeighbors", C.c_int), ("nChanels2", C.c_int), ("nDense", C.c_int)]
 
 
 class SMPOmega:
@@ -472,6 +473,67 @@ class SMPGatedNeighbourhood(SMPNeighbourhood):
                              "\"gru_gcn_3d\": GRU_GCN_3D)" % (form,))
         return SMPConfig(nLevels, nHiddens, nFeatures, nDepth, max_nVertices, 0, 0, 0, 0, 0, max_nVertices, 0, 0,
                          SMPGatedNeighbourhood.FORMS[form], max_Radius)
+
+
+class GCNMW(SMPNeighbourhood):
+    """Batched GCN_MW (GraphFlow/GCN_MW.h, gf_smp_config.matrix_form = 2): the Kipf-Welling GCN in matrix form on the row-list GEMM level.
+      A-hat = D^-1/2 (A + I) D^-1/2;  h_0 = LeakyReLU((A-hat x) W_0);  h_l = LeakyReLU((A-hat h_{l-1}) W_l);  x = the shell sums up to nDepth;
+      predict = <W, sum_v h_L[v]>, squared loss.  Parameters in registration order: W_0[F', H]; W_l[H, H] for l = 1..L; W[H], F' = nFeatures
+    (nDepth + 1).  nLevels = 0 is a model.  The optimiser is Momentum: step().  receptive_field(mol, l, v) gives the non-zero columns of row v
+    of A-hat, activation(mol, l, v) h_l[v]."""
+
+    def __init__(self, nLevels, max_nVertices, nFeatures, nHiddens, nDepth, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.form, self.nClass = "gcn_mw", 0
+        self.cfg = self.config(nLevels, max_nVertices, nFeatures, nHiddens, nDepth)
+        h = C.c_void_p()
+        self.ctx.check(self.lib.gf_smp_create(self.ctx.handle, C.byref(self.cfg), C.byref(h)))
+        self.handle = h
+        self.n_params = self.lib.gf_smp_param_count(h)
+        self.n_mol = 0
+
+    @staticmethod
+    def config(nLevels, max_nVertices, nFeatures, nHiddens, nDepth):
+        return SMPConfig(nLevels, nHiddens, nFeatures, nDepth, max_nVertices, 0, 0, 0, 0, 0, max_nVertices, 0, 0, 0, 0, 2, 0, 0, 0)
+
+
+class LCNN(GCNMW):
+    """Batched LCNN (PATCHY-SAN, GraphFlow/LCNN.h, gf_smp_config.matrix_form = 1) on the row-list GEMM level.  Every molecule is padded to
+    nVertices vertices; order = the class's exchange sort by the shell-sum rows, seq[i] = the first nNeighbors real vertices around rank
+    position i by (hop distance, rank), padded with the molecule's vertex count;
+      c1[i] = [x[seq[i][0]] | ..] F1 + b1, a1 = LeakyReLU(c1);  c2[i] = [a1[seq[i][0]] | ..] F2 + b2 (a1 is indexed by the sequence's vertex
+      ids, as the class does);  dense = Dm vec(c2);  predict = <W, dense>, squared loss; the graph feature is dense.
+    Parameters in registration order: F1[k, F', C1], b1[C1], F2[k, C1, C2], b2[C2], Dm[nDense, V C2], W[nDense].  prepare() refuses a
+    full-size molecule one of whose vertices reaches fewer than nNeighbors vertices (the class reads past its matrix there).
+    receptive_field(mol, l, i) gives the sequence of rank position i (level 0: the vertex at that position), activation(mol, 1, i) a1[i],
+    activation(mol, 2, i) c2[i]."""
+
+    def __init__(self, nVertices, nFeatures, nNeighbors, nDepth, nChanels1, nChanels2, nDense, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.form, self.nClass = "lcnn", 0
+        self.cfg = self.config(nVertices, nFeatures, nNeighbors, nDepth, nChanels1, nChanels2, nDense)
+        h = C.c_void_p()
+        self.ctx.check(self.lib.gf_smp_create(self.ctx.handle, C.byref(self.cfg), C.byref(h)))
+        self.handle = h
+        self.n_params = self.lib.gf_smp_param_count(h)
+        self.n_mol = 0
+
+    @staticmethod
+    def config(nVertices, nFeatures, nNeighbors, nDepth, nChanels1, nChanels2, nDense):
+        return SMPConfig(2, nChanels1, nFeatures, nDepth, nVertices, 0, 0, 0, 0, 0, nVertices, 0, 0, 0, 0, 1, nNeighbors, nChanels2, nDense)
+
+    def level_channels(self, level):
+        return self.cfg.nChanels2 if level == 2 else self.cfg.nChanels
+
+    def activation(self, mol, level, v):
+        """a1[v] (level 1, [nChanels1]) or c2[v] (level 2, [nChanels2]) of rank position v of molecule `mol` after forward()."""
+        out = np.empty(self.level_channels(level), dtype=np.float32)
+        n = self.lib.gf_smp_read_activation(self.handle, mol, level, v, out.ctypes.data_as(C.c_void_p), out.size)
+        if n != out.size:
+            raise RuntimeError("gf_smp_read_activation(%d, %d, %d) returned %d" % (mol, level, v, n))
+        return out
 
 
 class SMPClassifier(SMPOmega):

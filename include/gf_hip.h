@@ -404,6 +404,42 @@ typedef struct {
      * reverse gather; no float atomics, two runs give the same bits.
      * 0 (a zero-initialised tail): everything as described above, max_Radius is not read. */
     int neighbourhood, max_Radius;
+    /* matrix_form = 1: LCNN (PATCHY-SAN, GraphFlow/LCNN.h), 2: GCN_MW (the Kipf-Welling GCN in matrix form, GraphFlow/GCN_MW.h) -- the two
+     * matrix-form baselines.  Both run on the row-list GEMM level (smp_level_rowlist.hip): every output row is a short list of rows of the level
+     * below, concatenated slot by slot (LCNN) or weighted and summed (GCN_MW), times a learned matrix; the A operand is assembled from the
+     * list inside the product and never written to memory.  x [V][F'], F' = nFeatures (nDepth + 1), and dist are those of forms 2 .. 7.
+     * LeakyReLU has slope 0.01, the loss is 0.5 (predict - target)^2, every gradient is the plain derivative, the optimiser is Momentum
+     * (gf_smp_momentum_step).
+     *   2  GCN_MW: A-hat = D^-1/2 (A + I) D^-1/2 with D the row sums of A + I (DenseGraph::create_norm_adj: A-hat[i][j] = d_i (A + I)[i][j]
+     *      d_j in double, also for an asymmetric A), h_0 = LeakyReLU((A-hat x) W_0), h_l = LeakyReLU((A-hat h_{l-1}) W_l), graph feature =
+     *      sum_v h_L[v] [H], predict = <W, graph feature>.  nChanels = nHiddens = H.  Parameters in registration (= save_model) order:
+     *      W_0 [F'][H], W_l [H][H] for l = 1 .. nLevels, W [H]; uniform_init draws every W_l as a Matrix (divisor 10 x rows), W as a Vector.
+     *      nLevels = 0 is a model.  nNeighbors, nChanels2, nDense are not read.
+     *   1  LCNN(nVertices = max_nVertices, nFeatures, nNeighbors = k, nDepth, nChanels1 = nChanels, nChanels2, nDense); nLevels must be 2
+     *      (the two convolutions).  Every molecule is padded to V = max_nVertices vertices: dummy vertices have zero features and no edges;
+     *      dist and x are those of the padded graph.  order = the class's exchange sort, descending by the lexicographic comparison of the x
+     *      rows (rank_vertices); sequence (find_sequence): for rank position i, walking d = 0 .. V - 1 and inside that the rank positions
+     *      v = 0 .. V - 1, vertex order[v] is appended when dist(order[i], order[v]) == d and order[v] < molV, up to k entries; the rest is
+     *      padded with the value molV (a dummy order[i] gets k pads).  Layer 1: c1[i] = [x[seq[i][0]] | .. | x[seq[i][k - 1]]] F1 + b1, F1
+     *      [k][F'][C1]; a1 = LeakyReLU(c1); row i belongs to rank position i.  Layer 2: c2[i] = [a1[seq[i][0]] | ..] F2 + b2, F2 [k][C1][C2]:
+     *      the class indexes a1, whose rows are RANK POSITIONS, with the VERTEX IDS of the sequence, and so does the device.  The dense layer
+     *      reads the pre-activation c2 (the class's second LeakyReLU feeds nothing): dense = Dm vec(c2), Dm [nDense][V C2], vec row-major;
+     *      predict = <W, dense>; the graph feature is dense (gf_smp_feature_width = nDense).  Parameters: F1, b1 [C1], F2, b2 [C2], Dm,
+     *      W [nDense], each drawn as a Vector (divisor 10 x its size).  A pad entry reads row molV: with molV < V a valid row; with molV == V
+     *      the class reads past its matrix, and gf_smp_prepare refuses such a batch with GF_ERR_INVALID, naming the molecule (a full-size
+     *      molecule with a vertex that reaches fewer than k vertices).
+     * Required, else GF_ERR_INVALID: every other form selector (first_order, steerable_2d, unrestricted, neighbourhood, physics,
+     * nContractions, custom_matmul) 0, max_receptive_field == max_nVertices <= 4096, nChanels, nFeatures >= 1, nDepth >= 0; form 2: nLevels
+     * in 0 .. 64; form 1: nLevels == 2, nNeighbors, nChanels2, nDense >= 1.  The kernels index an operand row and a tile count with ints:
+     * every operand width -- F', nChanels, nChanels2, nDense, nNeighbors F', nNeighbors nChanels, max_nVertices nChanels2 -- is at most
+     * 65536 and the parameter count fits an int; a batch of more than 2^31 - 1 rows or list entries is refused by gf_smp_prepare.
+     * Refused with GF_ERR_UNSUPPORTED before anything is launched: gf_smp_create_classifier, gf_smp_set_grad_allreduce(smp, 1),
+     * gf_smp_dropout_masks, gf_smp_backward_features, gf_smp_prepare_coulomb with a matrix; gf_smp_model_create has no towers of these
+     * forms.  gf_smp_set_fused has no effect.  gf_smp_receptive_field(mol, l, i): LCNN: the k entries of the sequence of rank position i
+     * (level 0: {order[i]}), GCN_MW: the non-zero columns of row i of A-hat, ascending.  gf_smp_read_activation: LCNN level 1: a1[i] [C1],
+     * level 2: c2[i] [C2]; GCN_MW: h_l[v] [H].  gf_smp_level_sizes: nodes = rows = nMol V (LCNN) or the batch's vertices (GCN_MW), ppos = 0.
+     * 0 (a zero-initialised tail): everything as described above, the three LCNN fields are not read. */
+    int matrix_form, nNeighbors, nChanels2, nDense;
 } gf_smp_config;
 gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out);
 /* gf_smp_param_count of the handle gf_smp_create would build from cfg (0 on a configuration it would refuse).  Host only. */
@@ -593,6 +629,30 @@ gf_status gf_smp_third_order_pool_fwd_ex_f32(gf_ctx *ctx, int H, int nV, const l
                                              int *sel);
 gf_status gf_smp_third_order_pool_bwd_ex_f32(gf_ctx *ctx, int H, int nV, const long long *ptr, const int *idx, const long long *tptr,
                                              const int *tidx, const float *hprev, const int *sel, const float *dn, float *dhprev);
+/* The row-list GEMM level (gf_smp_config.matrix_form = 1, 2), its two products as stand-alone operators on caller-supplied operands, for
+ * per-row tests (tests/test_rowlist_ops_gpu.py).  Device pointers, fp32, asynchronous on the context's stream.  The operand is
+ *   A[r][slot * Cin + c] = sum over the entries e of row r with that slot of coef[e] * X[src[e]][c],      r < R, slot < slots, c < Cin,
+ * given as a CSR list: ptr long long [R + 1] from 0, and per entry src in [0, nX) (X is [nX][Cin]), slot in [0, slots), coef (NULL: every
+ * coefficient is 1); the entries of a row in ascending slot order.  A row may have no entries, a slot any number of them.
+ *   product: out [R][N] = act(A B + bias), act = 0: none, 1: LeakyReLU(0.01); bias [N] or NULL.  transposed_b = 0: B is [slots Cin][N];
+ *            1: B is the matrix of the forward product this one is the backward-data of, [slots][N][Cin], read transposed slot by slot
+ *            (element (slot Cin + a, n) = B[(slot N + n) Cin + a]; one slot: the plain transpose).
+ *   wgrad:   dB [slots Cin][N] += A^T dOut (dOut [R][N]) as a split over row chunks folded in ascending order; db [N] += the column sums
+ *            of dOut when db is not NULL.  Uses the context's workspace.
+ * GF_ERR_INVALID before anything is launched: a shape below 1, slots Cin or N above 65536, a missing operand, and -- checked on the host,
+ * one blocking copy per call -- a list that does not start at 0 or decreases, more than 2^31 - 1 entries, a source row outside [0, nX), a
+ * slot outside [0, slots), slots that decrease inside a row.  The context stays usable after a refusal. */
+gf_status gf_smp_rowlist_product_ex_f32(gf_ctx *ctx, int transposed_b, int R, int slots, int Cin, int N, int nX, const long long *ptr,
+                                        const int *src, const int *slot, const float *coef, const float *X, const float *B, const float *bias,
+                                        int act, float *out);
+gf_status gf_smp_rowlist_wgrad_ex_f32(gf_ctx *ctx, int R, int slots, int Cin, int N, int nX, const long long *ptr, const int *src,
+                                      const int *slot, const float *coef, const float *X, const float *dOut, float *dB, float *db);
+/* Host only (no device): what gf_smp_prepare derives from ONE molecule of a matrix_form configuration.  LCNN: order [V] and sequence
+ * [V][nNeighbors] with V = max_nVertices (norm_adj is not written); GCN_MW: norm_adj = A-hat [V][V] in double (order, sequence are not
+ * written).  GF_ERR_INVALID: a configuration gf_smp_create refuses, V outside 1 .. max_nVertices, a missing output, and an LCNN molecule
+ * with V == max_nVertices one of whose vertices reaches fewer than nNeighbors vertices (see gf_smp_config.matrix_form). */
+gf_status gf_smp_matrix_form_molecule_host(const gf_smp_config *cfg, int V, const int *adj, const double *feature, int *order, int *sequence,
+                                           double *norm_adj);
 /* Device memory of the handle's buffer pool: bytes held by the current batch, and bytes the pool keeps in total (idle
  * blocks included).  Sizing aid for batch selection (GraphFlow has no counterpart: its tensors live in host `new[]`). */
 gf_status gf_smp_device_bytes(const gf_smp *smp, size_t *in_use, size_t *reserved);
