@@ -803,6 +803,7 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
     gf_status st = ensure_ws(ctx, s->ws_need);
     if (st != GF_OK) return st;
     if (s->cfg.matrix_form) return smp_matrix_form_forward(s, params, targets, predict, loss, graph_feature);   // (LCNN, GCN_MW: smp_level_rowlist.hip)
+    if (s->cfg.distance_channel) return smp_distance_forward(s, params, targets, predict, loss, graph_feature);   // (two channels of that kind)
     if (s->cfg.gated()) return smp_gru_forward(s, params, targets, predict, loss, graph_feature);   // (the neighbourhood kind's second set of sweeps)
     if (s->cfg.neighbourhood) return smp_neighbourhood_forward(s, params, targets, predict, loss, graph_feature);   // (its own level 0 and read-out)
     const gfsmp::BatchLayout &B = s->lay;
@@ -1001,6 +1002,7 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
     gf_status st = ensure_ws(ctx, s->ws_need);
     if (st != GF_OK) return st;
     if (s->cfg.matrix_form) return smp_matrix_form_backward(s, params, grads, accumulate);
+    if (s->cfg.distance_channel) return smp_distance_backward(s, params, grads, accumulate);
     if (s->cfg.gated()) return smp_gru_backward(s, params, grads, accumulate);
     if (s->cfg.neighbourhood) return smp_neighbourhood_backward(s, params, grads, accumulate);   // (never a tower: gf_smp_backward_features refuses)
     const gfsmp::BatchLayout &B = s->lay;
@@ -1293,13 +1295,16 @@ static long long smp_read_node(gf_smp *s, int mol, int level, int v, float *out,
         if (hipStreamSynchronize(s->ctx->stream) != hipSuccess) return -1;
         return (long long)W;
     }
-    if (s->cfg.neighbourhood) {   // h_level[v] [H]; the models have no reduced adjacency
-        const size_t H = (size_t)s->cfg.nChanels;
-        if (adjacency || v < 0 || v >= s->lay.mols[mol].V || H > capacity) return -1;
-        const float *src = s->lv[level].f + ((size_t)s->lay.mol_first_vertex[mol] + v) * H;
-        if (hipMemcpyAsync(out, src, H * sizeof(float), hipMemcpyDeviceToHost, s->ctx->stream) != hipSuccess) return -1;
+    if (s->cfg.neighbourhood) {   // h_level[v] [H] (a distance handle: [h^v | h^d], 2 H); the models have no reduced adjacency
+        const size_t H = (size_t)s->cfg.nChanels, width = s->cfg.distance_channel ? 2 * H : H;
+        if (adjacency || v < 0 || v >= s->lay.mols[mol].V || width > capacity) return -1;
+        const size_t at = ((size_t)s->lay.mol_first_vertex[mol] + v) * H;
+        if (hipMemcpyAsync(out, s->lv[level].f + at, H * sizeof(float), hipMemcpyDeviceToHost, s->ctx->stream) != hipSuccess) return -1;
+        if (s->cfg.distance_channel &&
+            hipMemcpyAsync(out + H, s->lvd[level].f + at, H * sizeof(float), hipMemcpyDeviceToHost, s->ctx->stream) != hipSuccess)
+            return -1;
         if (hipStreamSynchronize(s->ctx->stream) != hipSuccess) return -1;
-        return (long long)H;
+        return (long long)width;
     }
     const gfsmp::LevelLayout &h = s->lay.level[level];
     int n = -1;

@@ -116,6 +116,38 @@ gf_status resolve_config(const gf_smp_config *cfg, const ConfigEntry &entry, Con
         if (nClass < 2) GF_REFUSE(GF_ERR_INVALID, "gf_smp_create_classifier: nClass = %d (at least 2)", nClass);
     }
     // ---- the configuration, family by family ----
+    if (cfg->distance_channel) {   // GCN_1D_Distance, GCN_2D_Distance, GCN_3D_Distance (smp_level_distance.hip): forms 2, 3, 6 on two channels
+        const int form = cfg->neighbourhood;
+        if (cfg->distance_channel != 1 || cfg->matrix_form || (form != 2 && form != 3 && form != 6))
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: distance_channel = %d with neighbourhood = %d, matrix_form = %d: the distance models are "
+                                      "distance_channel = 1 with neighbourhood = 2 (GCN_1D_Distance), 3 (GCN_2D_Distance) or 6 (GCN_3D_Distance)",
+                      cfg->distance_channel, form, cfg->matrix_form);
+        if (form == 6 && cfg->nChanels > gf::kThirdMaxChanels)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: GCN_3D_Distance with nChanels = %d: the third-order pool takes at most %d channels", cfg->nChanels,
+                      gf::kThirdMaxChanels);
+        gf_smp_config as2 = *cfg;   // (form 2's rules: all three read max_Radius)
+        as2.neighbourhood = 2;
+        as2.distance_channel = 0;
+        if (!rule_neighbourhood(&as2) || gf::smp_neighbourhood_lds_bytes(cfg->nChanels, cfg->max_nVertices) > 160 * 1024)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: distance_channel = 1 (neighbourhood = %d) needs first_order = steerable_2d = unrestricted = physics "
+                                      "= nContractions = custom_matmul = 0, max_receptive_field (%d) == max_nVertices (%d) <= 4096, nLevels >= 0, "
+                                      "max_Radius (%d) >= 0, nChanels (%d) <= %d and the level's matrices within 160 KiB at both operand widths, F' and "
+                                      "max_nVertices", form, cfg->max_receptive_field, cfg->max_nVertices, cfg->max_Radius, cfg->nChanels,
+                      gf::kNeighbourhoodMaxChanels);
+        if (form == 6 && cfg->max_nVertices > gf::smp_third_max_members(cfg->nChanels))
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: GCN_3D_Distance with max_nVertices = %d: the third-order pool stages a neighbourhood's members in "
+                                      "LDS: at most %d vertices at %d channels", cfg->max_nVertices, gf::smp_third_max_members(cfg->nChanels), cfg->nChanels);
+        Config c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, 0};
+        c.nContractions = 0;
+        c.max_nVertices = cfg->max_nVertices;
+        c.neighbourhood = form;
+        c.max_Radius = cfg->max_Radius;
+        c.distance_channel = 1;
+        if (param_count(c) > (size_t)kMaxInt)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: distance_channel = 1 with %zu parameters: the count must fit an int", param_count(c));
+        *out = c;
+        return GF_OK;
+    }
     if (cfg->matrix_form) {   // LCNN, GCN_MW (smp_level_rowlist.hip)
         if (entry.kind == ConfigEntry::Tower)
             GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_model_create: LCNN / GCN_MW (matrix_form = %d) are no towers", cfg->matrix_form);

@@ -305,6 +305,13 @@ struct gf_smp {
     long long *nb_id_ptr = nullptr;
     int *nb_id_idx = nullptr;
     std::vector<DevLevel> lv;
+    // distance handles (cfg.distance_channel; smp_level_distance.hip): the distance channel's levels -- the neighbourhood level's buffers of
+    // DevLevel, the lists shared with lv -- its input rows xd [vertices][max_nVertices] (dist_rows_sort), and what the sort reads: the
+    // molecules' distance matrices and their offsets.  g is [nMol][2 H].
+    std::vector<DevLevel> lvd;
+    float *xd = nullptr;
+    double *mol_dist = nullptr;
+    long long *mol_dist_off = nullptr;
     // device-built level tables: the batch's adjacency matrices and the per-level statistics the kernels leave behind
     int *mol_nv = nullptr, *mol_adj = nullptr;
     long long *mol_adj_off = nullptr;
@@ -443,6 +450,26 @@ gf_status smp_neighbourhood_node_launch(gf_ctx *ctx, bool pairs, int H, int nV, 
                                         float *sA);
 gf_status smp_neighbourhood_gather_launch(gf_ctx *ctx, bool pairs, int H, int nV, const long long *tptr, const int *tidx, const float *dn,
                                           const float *gTt, const float *sA, const float *hprev, const float *Tprev, float *dhprev);
+// ... and on two operand sets in one launch each (blockIdx.y picks the set; the sets of include/gf_hip.h): a level of a distance handle
+gf_status smp_neighbourhood_fwd2_launch(gf_ctx *ctx, bool pairs, int H, int nV, int rounds, const gf_nbh_fwd_set *sets, const long long *ptr,
+                                        const int *idx);
+gf_status smp_neighbourhood_node2_launch(gf_ctx *ctx, bool pairs, int H, int nV, int rounds, const gf_nbh_node_set *sets, const float *dy,
+                                         const int *vmol);
+gf_status smp_neighbourhood_gather2_launch(gf_ctx *ctx, bool pairs, int H, int nV, const long long *tptr, const int *tidx,
+                                           const gf_nbh_gather_set *sets);
+// the stand-alone operators' checks of a list and of member indices (smp_level_neighbourhood.hip; one blocking copy each)
+gf_status smp_neighbourhood_check_list(gf_ctx *ctx, const char *who, const char *what, const long long *ptr, const int *idx, int n, int bound);
+gf_status smp_neighbourhood_check_members(gf_ctx *ctx, const char *who, const char *what, const int *idx, size_t n, int bound);
+// GCN_1D_Distance, GCN_2D_Distance, GCN_3D_Distance (cfg.distance_channel; smp_level_distance.hip): the sweeps of a distance handle, its
+// gf_smp_prepare_distance (smp_prepare.hip) and the sort that builds the distance channel's input rows on the handle's upload stream.
+// params / grads: per level W1^v, W1^d (, W2^v, W2^d); W [2 H].
+gf_status smp_distance_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature, const double *distance);
+gf_status smp_distance_rows_launch(gf_ctx *ctx, hipStream_t stream, int nV, int M, const double *dist, const long long *mat_off, const int *mol_ptr,
+                                   const int *vmol, float *xd);
+gf_status smp_distance_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature);
+gf_status smp_distance_backward(gf_smp *s, const float *params, float *grads, int accumulate);
+// the classes' save_model order against the registration order: perm[i] = the flat index of the i-th value of a checkpoint
+void smp_distance_checkpoint_order(const gfsmp::Config &c, std::vector<size_t> *perm);
 // GRU_GCN_1D, GRU_GCN_2D (cfg.neighbourhood = 4, 5; smp_level_gru.hip): the sweeps of a gated handle on the same lists and buffers.
 // params / grads: W; W_z, U_z, W_r, U_r, W_h, U_h, W_g, U_g (shared by the levels: their gradients accumulate across them); U.
 gf_status smp_gru_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature);

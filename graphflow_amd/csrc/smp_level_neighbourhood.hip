@@ -18,6 +18,9 @@
 // of a lane without a channel is loaded from a clamped address and never stored (NOTES.md: no guard around an operand load).
 // The four kernels and the read-out are also operators of the C ABI on caller-supplied operands (gf_smp_neighbourhood_fwd_ex_f32,
 // _node_bwd_ex_f32, _gather_bwd_ex_f32, _readout_ex_f32 at the end of the file), through the launchers the level uses.
+// The three level kernels take TWO operand sets by value (gf_nbh_fwd_set / _node_set / _gather_set of include/gf_hip.h) and blockIdx.y
+// picks one: a distance handle (smp_level_distance.hip) runs its vertex and its distance channel in one launch each (*_sets launchers,
+// gf_smp_neighbourhood_*2_ex_f32).  Everybody else launches grid.y = 1 with the one set given twice; the bodies are unchanged.
 #include <cmath>
 
 #include "smp_field_level.h"
@@ -55,11 +58,11 @@ __device__ __forceinline__ Slot slot_of(int G) {
 }
 
 template <int NK, bool PAIRS>
-__global__ __launch_bounds__(kBlock) void nbh_level_fwd(const float *__restrict__ W1, const float *__restrict__ W2, const float *__restrict__ x,
-                                                        const float *__restrict__ hprev, const float *__restrict__ Tprev,
-                                                        const long long *__restrict__ ptr, const int *__restrict__ idx, float *__restrict__ h,
-                                                        float *__restrict__ n, float *__restrict__ A, float *__restrict__ T,
-                                                        float *__restrict__ Tt, int nV, int H, int FD, int G, int vpg) {
+__device__ __forceinline__ void level_fwd_body(const float *__restrict__ W1, const float *__restrict__ W2, const float *__restrict__ x,
+                                               const float *__restrict__ hprev, const float *__restrict__ Tprev,
+                                               const long long *__restrict__ ptr, const int *__restrict__ idx, float *__restrict__ h,
+                                               float *__restrict__ n, float *__restrict__ A, float *__restrict__ T, float *__restrict__ Tt, int nV,
+                                               int H, int FD, int G, int vpg) {
     extern __shared__ __align__(16) float lds[];
     const int Hp = row_stride(H);
     float *W1t = lds;                            // [FD][Hp]: W1t[f][c] = W1[c][f]
@@ -158,14 +161,23 @@ __global__ __launch_bounds__(kBlock) void nbh_level_fwd(const float *__restrict_
         }
     }
 }
+// The launch: blockIdx.y picks one of two operand sets passed by value (a distance handle's vertex and distance channel; grid.y = 1: the
+// one set of every other caller, given twice).  The pick is uniform for the workgroup; the dynamic LDS is sized for the wider operand.
+template <int NK, bool PAIRS>
+__global__ __launch_bounds__(kBlock) void nbh_level_fwd(const gf_nbh_fwd_set s0, const gf_nbh_fwd_set s1, const long long *__restrict__ ptr,
+                                                        const int *__restrict__ idx, int nV, int H, int G, int vpg) {
+    const bool second = blockIdx.y != 0;
+    level_fwd_body<NK, PAIRS>(second ? s1.W1 : s0.W1, second ? s1.W2 : s0.W2, second ? s1.x : s0.x, second ? s1.hprev : s0.hprev,
+                              second ? s1.Tprev : s0.Tprev, ptr, idx, second ? s1.h : s0.h, second ? s1.n : s0.n, second ? s1.A : s0.A,
+                              second ? s1.T : s0.T, second ? s1.Tt : s0.Tt, nV, H, second ? s1.FD : s0.FD, G, vpg);
+}
 
 // dz = dh h (1 - h) in place of dh (top: dh = dy[mol] W), and below level 0's: dn = W2^T dz; PAIRS: dn Tt and <dn, A>
 template <int NK, bool PAIRS>
-__global__ __launch_bounds__(kBlock) void nbh_node_bwd(const float *__restrict__ W2, const float *__restrict__ h, float *__restrict__ dh,
-                                                       const float *__restrict__ dy, const float *__restrict__ Wout,
-                                                       const int *__restrict__ vmol, const float *__restrict__ A,
-                                                       const float *__restrict__ Tt, float *__restrict__ dn, float *__restrict__ gTt,
-                                                       float *__restrict__ sA, int nV, int H, int G, int vpg) {
+__device__ __forceinline__ void node_bwd_body(const float *__restrict__ W2, const float *__restrict__ h, float *__restrict__ dh,
+                                              const float *__restrict__ dy, const float *__restrict__ Wout, const int *__restrict__ vmol,
+                                              const float *__restrict__ A, const float *__restrict__ Tt, float *__restrict__ dn,
+                                              float *__restrict__ gTt, float *__restrict__ sA, int nV, int H, int G, int vpg) {
     extern __shared__ __align__(16) float lds[];
     float *W2s = lds;                                  // [H][H] as it is: lanes run along a row
     float *dzbuf = W2s + (W2 ? (size_t)H * H : 0);     // [slots][H]
@@ -222,13 +234,20 @@ __global__ __launch_bounds__(kBlock) void nbh_node_bwd(const float *__restrict__
         }
     }
 }
+template <int NK, bool PAIRS>
+__global__ __launch_bounds__(kBlock) void nbh_node_bwd(const gf_nbh_node_set s0, const gf_nbh_node_set s1, const float *__restrict__ dy,
+                                                       const int *__restrict__ vmol, int nV, int H, int G, int vpg) {
+    const bool second = blockIdx.y != 0;
+    node_bwd_body<NK, PAIRS>(second ? s1.W2 : s0.W2, second ? s1.h : s0.h, second ? s1.dh : s0.dh, dy, second ? s1.Wout : s0.Wout, vmol,
+                             second ? s1.A : s0.A, second ? s1.Tt : s0.Tt, second ? s1.dn : s0.dn, second ? s1.gTt : s0.gTt,
+                             second ? s1.sA : s0.sA, nV, H, G, vpg);
+}
 
 // dh_{l-1}[w] over the consumers of w (the transposed list, ascending): the sum of dn, or form 3's closed form (see the head of the file)
 template <int NK, bool PAIRS>
-__global__ __launch_bounds__(kBlock) void nbh_gather_bwd(const long long *__restrict__ tptr, const int *__restrict__ tidx,
-                                                         const float *__restrict__ dn, const float *__restrict__ gTt,
-                                                         const float *__restrict__ sA, const float *__restrict__ hprev,
-                                                         const float *__restrict__ Tprev, float *__restrict__ dhprev, int nV, int H, int G) {
+__device__ __forceinline__ void gather_bwd_body(const long long *__restrict__ tptr, const int *__restrict__ tidx, const float *__restrict__ dn,
+                                                const float *__restrict__ gTt, const float *__restrict__ sA, const float *__restrict__ hprev,
+                                                const float *__restrict__ Tprev, float *__restrict__ dhprev, int nV, int H, int G) {
     const Slot sl = slot_of(G);
     const long long w = (long long)blockIdx.x * sl.slots + sl.slot;
     const bool live = w < nV;
@@ -264,6 +283,13 @@ __global__ __launch_bounds__(kBlock) void nbh_gather_bwd(const long long *__rest
 #pragma unroll
     for (int k = 0; k < NK; ++k)
         if (live && ok[k]) dhprev[ww * H + cc[k]] = gs[k];
+}
+template <int NK, bool PAIRS>
+__global__ __launch_bounds__(kBlock) void nbh_gather_bwd(const long long *__restrict__ tptr, const int *__restrict__ tidx, const gf_nbh_gather_set s0,
+                                                         const gf_nbh_gather_set s1, int nV, int H, int G) {
+    const bool second = blockIdx.y != 0;
+    gather_bwd_body<NK, PAIRS>(tptr, tidx, second ? s1.dn : s0.dn, second ? s1.gTt : s0.gTt, second ? s1.sA : s0.sA, second ? s1.hprev : s0.hprev,
+                               second ? s1.Tprev : s0.Tprev, second ? s1.dhprev : s0.dhprev, nV, H, G);
 }
 
 // one wave per molecule: g = sum over its vertices (ascending) of h_L, predict = <W, g>, the squared loss and dy = predict - target
@@ -333,37 +359,57 @@ inline int vertices_per_group(int nV, int slots) {
 // rounds = 0: vertices_per_group; > 0: that many rounds of a workgroup's slots.
 inline int group_vertices(int nV, int slots, int rounds) { return rounds > 0 ? slots * rounds : vertices_per_group(nV, slots); }
 
+// `sets` operand sets (1 or 2) in one launch: grid.y = sets, the dynamic LDS sized for the wider operand
 template <int NK, bool PAIRS>
-gf_status fwd_launch(gf_ctx *ctx, int H, int FD, int nV, int rounds, const float *W1, const float *W2, const float *x, const float *hprev,
-                     const float *Tprev, const long long *ptr, const int *idx, float *h, float *n, float *A, float *T, float *Tt) {
+gf_status fwd_launch_sets(gf_ctx *ctx, int H, int nV, int rounds, int sets, const gf_nbh_fwd_set &s0, const gf_nbh_fwd_set &s1, const long long *ptr,
+                          const int *idx) {
     const int G = smp_neighbourhood_group_width(H), vpg = group_vertices(nV, kBlock / G, rounds);
+    const int FD = sets > 1 && s1.FD > s0.FD ? s1.FD : s0.FD;
     const size_t bytes = smp_neighbourhood_lds_bytes(H, FD);   // (level 0 leaves W2's part unused: one grant per kernel)
     const gf_status st = opt_in_lds(ctx, nbh_level_fwd<NK, PAIRS>, bytes);
     if (st != GF_OK) return st;
-    GF_LAUNCH(ctx, "nbh_level_fwd", (nbh_level_fwd<NK, PAIRS>), dim3((unsigned)((nV + vpg - 1) / vpg)), dim3(kBlock), bytes, W1, W2, x, hprev,
-              Tprev, ptr, idx, h, n, A, T, Tt, nV, H, FD, G, vpg);
+    GF_LAUNCH(ctx, "nbh_level_fwd", (nbh_level_fwd<NK, PAIRS>), dim3((unsigned)((nV + vpg - 1) / vpg), (unsigned)sets), dim3(kBlock), bytes, s0, s1,
+              ptr, idx, nV, H, G, vpg);
     return GF_OK;
 }
+template <int NK, bool PAIRS>
+gf_status fwd_launch(gf_ctx *ctx, int H, int FD, int nV, int rounds, const float *W1, const float *W2, const float *x, const float *hprev,
+                     const float *Tprev, const long long *ptr, const int *idx, float *h, float *n, float *A, float *T, float *Tt) {
+    const gf_nbh_fwd_set one = {FD, W1, x, W2, hprev, Tprev, h, n, A, T, Tt};
+    return fwd_launch_sets<NK, PAIRS>(ctx, H, nV, rounds, 1, one, one, ptr, idx);
+}
 
+template <int NK, bool PAIRS>
+gf_status node_launch_sets(gf_ctx *ctx, int H, int nV, int rounds, int sets, const gf_nbh_node_set &s0, const gf_nbh_node_set &s1, const float *dy,
+                           const int *vmol) {
+    const int G = smp_neighbourhood_group_width(H), slots = kBlock / G, vpg = group_vertices(nV, slots, rounds);
+    const size_t bytes = sizeof(float) * ((s0.W2 ? (size_t)H * H : 0) + (size_t)slots * H);
+    const gf_status st = opt_in_lds(ctx, nbh_node_bwd<NK, PAIRS>, bytes);
+    if (st != GF_OK) return st;
+    GF_LAUNCH(ctx, "nbh_node_bwd", (nbh_node_bwd<NK, PAIRS>), dim3((unsigned)((nV + vpg - 1) / vpg), (unsigned)sets), dim3(kBlock), bytes, s0, s1, dy,
+              vmol, nV, H, G, vpg);
+    return GF_OK;
+}
 template <int NK, bool PAIRS>
 gf_status node_launch(gf_ctx *ctx, int H, int nV, int rounds, const float *W2, const float *h, float *dh, const float *dy, const float *Wout,
                       const int *vmol, const float *A, const float *Tt, float *dn, float *gTt, float *sA) {
-    const int G = smp_neighbourhood_group_width(H), slots = kBlock / G, vpg = group_vertices(nV, slots, rounds);
-    const size_t bytes = sizeof(float) * ((W2 ? (size_t)H * H : 0) + (size_t)slots * H);
-    const gf_status st = opt_in_lds(ctx, nbh_node_bwd<NK, PAIRS>, bytes);
-    if (st != GF_OK) return st;
-    GF_LAUNCH(ctx, "nbh_node_bwd", (nbh_node_bwd<NK, PAIRS>), dim3((unsigned)((nV + vpg - 1) / vpg)), dim3(kBlock), bytes, W2, h, dh, dy, Wout,
-              vmol, A, Tt, dn, gTt, sA, nV, H, G, vpg);
-    return GF_OK;
+    const gf_nbh_node_set one = {W2, h, dh, Wout, A, Tt, dn, gTt, sA};
+    return node_launch_sets<NK, PAIRS>(ctx, H, nV, rounds, 1, one, one, dy, vmol);
 }
 
 template <int NK, bool PAIRS>
+gf_status gather_launch_sets(gf_ctx *ctx, int H, int nV, int sets, const long long *tptr, const int *tidx, const gf_nbh_gather_set &s0,
+                             const gf_nbh_gather_set &s1) {
+    const int G = smp_neighbourhood_group_width(H), slots = kBlock / G;
+    GF_LAUNCH(ctx, "nbh_gather_bwd", (nbh_gather_bwd<NK, PAIRS>), dim3((unsigned)((nV + slots - 1) / slots), (unsigned)sets), dim3(kBlock), 0, tptr,
+              tidx, s0, s1, nV, H, G);
+    return GF_OK;
+}
+template <int NK, bool PAIRS>
 gf_status gather_launch(gf_ctx *ctx, int H, int nV, const long long *tptr, const int *tidx, const float *dn, const float *gTt, const float *sA,
                         const float *hprev, const float *Tprev, float *dhprev) {
-    const int G = smp_neighbourhood_group_width(H), slots = kBlock / G;
-    GF_LAUNCH(ctx, "nbh_gather_bwd", (nbh_gather_bwd<NK, PAIRS>), dim3((unsigned)((nV + slots - 1) / slots)), dim3(kBlock), 0, tptr, tidx, dn,
-              gTt, sA, hprev, Tprev, dhprev, nV, H, G);
-    return GF_OK;
+    const gf_nbh_gather_set one = {dn, gTt, sA, hprev, Tprev, dhprev};
+    return gather_launch_sets<NK, PAIRS>(ctx, H, nV, 1, tptr, tidx, one, one);
 }
 
 // the one place the run-time (channels per lane, aggregate) picks an instantiation: f(channels per lane, pairs) as integral constants
@@ -453,6 +499,31 @@ gf_status smp_neighbourhood_gather_launch(gf_ctx *ctx, bool pairs, int H, int nV
     return with_instantiation(H, pairs, [&](auto nk, auto pr) -> gf_status {
         return gather_launch<decltype(nk)::value, decltype(pr)::value>(ctx, H, nV, tptr, tidx, dn, gTt, sA, hprev, Tprev, dhprev);
     });
+}
+
+gf_status smp_neighbourhood_fwd2_launch(gf_ctx *ctx, bool pairs, int H, int nV, int rounds, const gf_nbh_fwd_set *sets, const long long *ptr,
+                                        const int *idx) {
+    return with_instantiation(H, pairs, [&](auto nk, auto pr) -> gf_status {
+        return fwd_launch_sets<decltype(nk)::value, decltype(pr)::value>(ctx, H, nV, rounds, 2, sets[0], sets[1], ptr, idx);
+    });
+}
+gf_status smp_neighbourhood_node2_launch(gf_ctx *ctx, bool pairs, int H, int nV, int rounds, const gf_nbh_node_set *sets, const float *dy,
+                                         const int *vmol) {
+    return with_instantiation(H, pairs, [&](auto nk, auto pr) -> gf_status {
+        return node_launch_sets<decltype(nk)::value, decltype(pr)::value>(ctx, H, nV, rounds, 2, sets[0], sets[1], dy, vmol);
+    });
+}
+gf_status smp_neighbourhood_gather2_launch(gf_ctx *ctx, bool pairs, int H, int nV, const long long *tptr, const int *tidx,
+                                           const gf_nbh_gather_set *sets) {
+    return with_instantiation(H, pairs, [&](auto nk, auto pr) -> gf_status {
+        return gather_launch_sets<decltype(nk)::value, decltype(pr)::value>(ctx, H, nV, 2, tptr, tidx, sets[0], sets[1]);
+    });
+}
+gf_status smp_neighbourhood_check_list(gf_ctx *ctx, const char *who, const char *what, const long long *ptr, const int *idx, int n, int bound) {
+    return check_list(ctx, who, what, ptr, idx, n, bound);
+}
+gf_status smp_neighbourhood_check_members(gf_ctx *ctx, const char *who, const char *what, const int *idx, size_t n, int bound) {
+    return check_members(ctx, who, what, idx, n, bound);
 }
 
 gf_status smp_neighbourhood_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature) {
@@ -575,6 +646,69 @@ gf_status gf_smp_neighbourhood_readout_ex_f32(gf_ctx *ctx, int H, int nV, int nM
     GF_LAUNCH(ctx, "nbh_readout", gf::nbh_readout, dim3(nMol), dim3(64), 0, hL, mol_ptr, W, target, g, yhat, loss, dy, H);
     GF_LAUNCH(ctx, "nbh_readout_dW", gf::nbh_readout_dW, dim3((unsigned)((H + 63) / 64)), dim3(1024), 0, dy, g, dW, H, nMol);
     return GF_OK;
+}
+
+// ---- the same kernels on two operand sets in one launch (a level of a distance handle) ----
+gf_status gf_smp_neighbourhood_fwd2_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, int rounds, const gf_nbh_fwd_set *sets, const long long *ptr,
+                                           const int *idx) {
+    static const char *who = "gf_smp_neighbourhood_fwd2_ex_f32";
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    gf_status st = check_shape(ctx, who, H, nV, rounds);
+    if (st != GF_OK) return st;
+    if (!sets) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
+    if ((sets[0].W2 != nullptr) != (sets[1].W2 != nullptr)) return gf::fail(ctx, GF_ERR_INVALID, "%s: W2 in one set only", who);
+    for (int c = 0; c < 2; ++c) {
+        const gf_nbh_fwd_set &o = sets[c];
+        if (o.FD < 1 || !o.W1 || !o.x || !o.h) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument in set %d", who, c);
+        if (o.W2 && (!o.hprev || !ptr || !idx || !o.n)) return gf::fail(ctx, GF_ERR_INVALID, "%s: a level with W2 needs hprev, ptr, idx and n (set %d)", who, c);
+        if (pairs && (!o.T || (o.W2 && (!o.Tprev || !o.A || !o.Tt))))
+            return gf::fail(ctx, GF_ERR_INVALID, "%s: the pair form needs T, and with W2 Tprev, A and Tt (set %d)", who, c);
+        if (gf::smp_neighbourhood_lds_bytes(H, o.FD) > 160 * 1024)
+            return gf::fail(ctx, GF_ERR_INVALID, "%s: H = %d, F' = %d need %zu bytes of LDS (160 KiB)", who, H, o.FD, gf::smp_neighbourhood_lds_bytes(H, o.FD));
+    }
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (sets[0].W2) st = gf::check_list(ctx, who, "ptr", ptr, idx, nV, nV);
+    if (st != GF_OK) return st;
+    return gf::smp_neighbourhood_fwd2_launch(ctx, pairs != 0, H, nV, rounds, sets, ptr, idx);
+}
+
+gf_status gf_smp_neighbourhood_node_bwd2_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, int rounds, const gf_nbh_node_set *sets, const float *dy,
+                                                const int *vmol, int nMol) {
+    static const char *who = "gf_smp_neighbourhood_node_bwd2_ex_f32";
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    gf_status st = check_shape(ctx, who, H, nV, rounds);
+    if (st != GF_OK) return st;
+    if (!sets) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
+    if ((sets[0].W2 != nullptr) != (sets[1].W2 != nullptr)) return gf::fail(ctx, GF_ERR_INVALID, "%s: W2 in one set only", who);
+    if (dy && (!vmol || nMol < 1)) return gf::fail(ctx, GF_ERR_INVALID, "%s: the top level needs vmol and nMol >= 1", who);
+    for (int c = 0; c < 2; ++c) {
+        const gf_nbh_node_set &o = sets[c];
+        if (!o.h || !o.dh || (dy && !o.Wout)) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument in set %d", who, c);
+        if (o.W2 && (!o.dn || (pairs && (!o.A || !o.Tt || !o.gTt || !o.sA))))
+            return gf::fail(ctx, GF_ERR_INVALID, "%s: a level with W2 needs dn, the pair form A, Tt, gTt, sA (set %d)", who, c);
+    }
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (dy) st = gf::check_members(ctx, who, "vmol", vmol, (size_t)nV, nMol);
+    if (st != GF_OK) return st;
+    return gf::smp_neighbourhood_node2_launch(ctx, pairs != 0, H, nV, rounds, sets, dy, vmol);
+}
+
+gf_status gf_smp_neighbourhood_gather_bwd2_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, const long long *tptr, const int *tidx,
+                                                  const gf_nbh_gather_set *sets) {
+    static const char *who = "gf_smp_neighbourhood_gather_bwd2_ex_f32";
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    gf_status st = check_shape(ctx, who, H, nV, 0);
+    if (st != GF_OK) return st;
+    if (!tptr || !tidx || !sets) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
+    for (int c = 0; c < 2; ++c) {
+        const gf_nbh_gather_set &o = sets[c];
+        if (!o.dn || !o.dhprev) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument in set %d", who, c);
+        if (pairs && (!o.gTt || !o.sA || !o.hprev || !o.Tprev)) return gf::fail(ctx, GF_ERR_INVALID, "%s: the pair form needs gTt, sA, hprev and Tprev (set %d)", who, c);
+    }
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = gf::check_list(ctx, who, "tptr", tptr, tidx, nV, nV);
+    if (st != GF_OK) return st;
+    return gf::smp_neighbourhood_gather2_launch(ctx, pairs != 0, H, nV, tptr, tidx, sets);
 }
 
 }  // extern "C"

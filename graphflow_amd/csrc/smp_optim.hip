@@ -228,7 +228,9 @@ gf_status gf_smp_save_model(const gf_smp *s, const float *params, const char *pa
     FILE *f = std::fopen(path, "w");
     if (!f) return fail(s->ctx, GF_ERR_INVALID, "gf_smp_save_model: cannot open %s", path);
     bool ok = true;
-    for (size_t i = 0; i < n && ok; ++i) ok = std::fprintf(f, "%g ", (double)host[i]) > 0;
+    std::vector<size_t> order;   // (a distance handle: the classes write channel by channel, not in registration order)
+    if (s->ucfg.distance_channel) gf::smp_distance_checkpoint_order(s->ucfg, &order);
+    for (size_t i = 0; i < n && ok; ++i) ok = std::fprintf(f, "%g ", (double)host[order.empty() ? i : order[i]]) > 0;
     ok = (std::fclose(f) == 0) && ok;
     return ok ? GF_OK : fail(s->ctx, GF_ERR_INVALID, "gf_smp_save_model: write to %s failed", path);
 }
@@ -247,7 +249,12 @@ gf_status gf_smp_load_model(gf_smp *s, float *params, const char *path) {
     std::vector<float> host(n);
     size_t got = 0;
     double v;
-    while (got < n && std::fscanf(f, "%lf", &v) == 1) host[got++] = (float)v;
+    std::vector<size_t> order;   // (a distance handle: the classes' files go channel by channel)
+    if (s->ucfg.distance_channel) gf::smp_distance_checkpoint_order(s->ucfg, &order);
+    while (got < n && std::fscanf(f, "%lf", &v) == 1) {
+        host[order.empty() ? got : order[got]] = (float)v;
+        ++got;
+    }
     std::fclose(f);
     // the reference would silently keep reading garbage; a short file is an error here
     if (got != n) return fail(s->ctx, GF_ERR_INVALID, "gf_smp_load_model: %s holds %zu values, the model has %zu", path, got, n);

@@ -96,9 +96,14 @@ struct Config {
     // 1: nLevels = 2 (the two convolutions), nChanels = C1, max_nVertices = V, nNeighbors = k; F1 [k][F'][C1] (first_block); level 1: b1
     // [C1], F2 [k][C1][C2]; level 2: b2 [C2], Dm [nDense][V C2]; W [nDense] -- each drawn as a Vector.  None of the other forms' fields is set.
     int matrix_form = 0, nNeighbors = 0, nChanels2 = 0, nDense = 0;
+    // 1 with neighbourhood = 2, 3, 6: GCN_1D_Distance, GCN_2D_Distance, GCN_3D_Distance (GraphFlow/GCN_*D_Distance.h; gf_smp_config.distance_channel;
+    // smp_level_distance.hip): two copies of the form's level side by side, the vertex channel on x [F'] and the distance channel on the sorted
+    // distance rows [max_nVertices], read out over [sum h^v_L | sum h^d_L].  Parameters: W1^v_0 [H][F'], W1^d_0 [H][M] (first_block()); for l =
+    // 1..L: W1^v_l, W1^d_l, W2^v_l [H][H], W2^d_l [H][H]; W [2 H].  N_l(v) reads max_Radius in all three.
+    int distance_channel = 0;
     bool gated() const { return neighbourhood == 4 || neighbourhood == 5 || neighbourhood == 7; }
     bool third_order() const { return neighbourhood == 6 || neighbourhood == 7; }
-    int nb_radius(int l) const { return neighbourhood == 1 ? 1 : neighbourhood == 3 || l < max_Radius ? l : max_Radius; }   // of N_l (form 1: the adjacency itself; 3 alone ignores max_Radius)
+    int nb_radius(int l) const { return neighbourhood == 1 ? 1 : (neighbourhood == 3 && !distance_channel) || l < max_Radius ? l : max_Radius; }   // of N_l (form 1: the adjacency itself; 3 alone ignores max_Radius)
     size_t filter_floats(int l) const { return level_blocks(l).size_quad(); }   // of an unrestricted level's filter, per s^2
     bool per_size() const { return first_order || steerable_2d; }   // a handle on the th_* tables, per-size blocks in front of the matrix block
     bool concat() const { return first_order >= 3 || steerable_2d == 2; }   // C_l = 2 C_{l-1}
@@ -119,7 +124,7 @@ struct Config {
         size_t max_size = 0, bias = 0;
         int nsize = 0, nmat = 0;
         SizeTerm size[3];
-        Block mat[2];
+        Block mat[4];
         size_t size_quad() const {
             size_t q = 0;
             for (int i = 0; i < nsize; ++i) q += size[i].quad;
@@ -130,7 +135,11 @@ struct Config {
             for (int i = 0; i < nsize; ++i) lin += size[i].lin;
             return size_quad() * (max_size * (max_size + 1) * (2 * max_size + 1) / 6) + lin * max_size;
         }
-        size_t matrix() const { return (nmat > 0 ? mat[0].n : 0) + (nmat > 1 ? mat[1].n : 0); }
+        size_t matrix() const {
+            size_t n = 0;
+            for (int i = 0; i < nmat; ++i) n += mat[i].n;
+            return n;
+        }
         size_t total() const { return sizes() + matrix() + bias; }
         template <class F>
         void each_draw(F f) const {   // f(Block) for every block uniform_init draws with a divisor of its own, in order
@@ -179,6 +188,13 @@ struct Config {
             matrix(l == 1 ? k * C1 * C2 : (size_t)nDense * (size_t)max_nVertices * C2);
             return b;
         }
+        if (distance_channel) {   // W1^v_l [H][F'], W1^d_l [H][M], W2^v_l, W2^d_l [H][H]: the registration order interleaves the channels
+            matrix(Cl * fdim(), Cl);
+            matrix(Cl * (size_t)max_nVertices, Cl);
+            matrix(Cl * Cl, Cl);
+            matrix(Cl * Cl, Cl);
+            return b;
+        }
         if (neighbourhood) {   // W1_l [H][F'], W2_l [H][H]: no per-size entries, no bias (l = 0: W1_0 is first_block())
             matrix(Cl * fdim(), Cl);
             matrix(Cl * Cl, Cl);
@@ -206,6 +222,7 @@ struct Config {
     }
     Block first_block() const {   // H [C][F (D + 1)]; W1_0 [H][F'] of a neighbourhood form (a Matrix: 10 x rows), W of a gated one (a Vector)
         const size_t n = (size_t)nChanels * fdim();
+        if (distance_channel) return {n + (size_t)nChanels * (size_t)max_nVertices, (size_t)nChanels};   // W1^v_0 then W1^d_0: two Matrices of H rows, one divisor
         if (matrix_form == 2) return {n, (size_t)fdim()};   // W_0 [F'][H], a Matrix of F' rows
         if (matrix_form == 1) return {n * (size_t)nNeighbors, n * (size_t)nNeighbors};   // F1 [k][F'][C1], a Vector
         return {n, neighbourhood && !gated() ? (size_t)nChanels : n};
@@ -216,7 +233,7 @@ struct Config {
         const size_t n = physics ? 0 : (size_t)readout_rows() * top_channels();
         return {n, n};
     }
-    int top_channels() const { return matrix_form == 1 ? nDense : first_order >= 2 || steerable_2d ? level_channels(nLevels) : nChanels;  }   // width of the graph feature and of W's rows
+    int top_channels() const { return distance_channel ? 2 * nChanels : matrix_form == 1 ? nDense : first_order >= 2 || steerable_2d ? level_channels(nLevels) : nChanels;  }   // width of the graph feature and of W's rows
     int readout_rows() const { return nClass > 1 ? nClass : 1; }   // rows of W: [1][C] is the regression's [C]
     bool square() const { return !physics || uniform; }   // K_l is [nContractions C][C] at every level
     int level_channels(int l) const {

@@ -937,13 +937,26 @@ gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int
 // gf_smp_prepare of a neighbourhood handle (NeuralFingerprint, GCN_1D, GCN_2D; smp_level_neighbourhood.hip): the host builds hop distances,
 // the shell-sum features and one neighbour list (with its transpose) per distinct radius (gfsmp::build_batch_neighbourhood); the device gets
 // those and one [vertices][H] buffer per level and quantity -- none of the field, selection or reduced-adjacency tables.
-gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature) {
+// A distance handle (cfg.distance_channel; `distance` = the molecules' V x V matrices of doubles back to back) gets the same buffers a second
+// time for its distance channel (gf_smp::lvd, the lists shared) and that channel's input rows, sorted on the device (smp_level_distance.hip).
+static gf_status neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature, const double *distance) {
     gf_ctx *ctx = s->ctx;
     const gfsmp::Config &cfg = s->cfg;
-    for (int m = 0; m < nMol; ++m)
+    const char *who = distance ? "gf_smp_prepare_distance" : "gf_smp_prepare";
+    size_t dist_count = 0;
+    for (int m = 0; m < nMol; ++m) {
         if (nVertices[m] > cfg.max_nVertices)
-            return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare: molecule %d has %d vertices, the model was created with max_nVertices = %d", m,
+            return fail(ctx, GF_ERR_INVALID, "%s: molecule %d has %d vertices, the model was created with max_nVertices = %d", who, m,
                         nVertices[m], cfg.max_nVertices);
+        if (distance) {   // (every entry finite, before anything is launched)
+            const size_t n = (size_t)nVertices[m] * (size_t)nVertices[m];
+            for (size_t i = 0; i < n; ++i)
+                if (!std::isfinite(distance[dist_count + i]))
+                    return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare_distance: molecule %d has a distance entry that is not finite (row %zu, column %zu)",
+                                m, i / (size_t)nVertices[m], i % (size_t)nVertices[m]);
+            dist_count += n;
+        }
+    }
     ensure_upload_stream(s);
     release(s);
     s->tab_stats = nullptr;
@@ -969,8 +982,10 @@ gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, c
         t.put(&lists[k].tidx, B.nb_lists[k].tidx);
     }
     const bool pairs = cfg.neighbourhood == 3 || cfg.neighbourhood == 5;   // RisiLayer2D: A, T, Tt and the three quantities of its closed-form reverse
-    for (int l = 0; l <= L; ++l) {
-        DevLevel &d = s->lv[l];
+    s->lvd.assign(distance ? L + 1 : 0, gf_smp::DevLevel());
+    for (int k = 0; k <= (distance ? 2 * L + 1 : L); ++k) {   // (then the distance channel's levels)
+        const int l = k <= L ? k : k - L - 1;
+        DevLevel &d = k <= L ? s->lv[l] : s->lvd[l];
         t.alloc(&d.f, nV * H);
         t.alloc(&d.df, nV * H);
         if (pairs) t.alloc(&d.nb_T, nV);
@@ -997,9 +1012,23 @@ gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, c
         }
     }
     t.put(&s->x, B.x);
-    t.alloc(&s->g, (size_t)nMol * H);
+    t.alloc(&s->g, (size_t)nMol * (size_t)cfg.top_channels());
     t.alloc(&s->yhat, (size_t)nMol);
     t.alloc(&s->dy, (size_t)nMol);
+    s->xd = nullptr;
+    s->mol_dist = nullptr;
+    s->mol_dist_off = nullptr;
+    if (distance) {
+        std::vector<long long> off((size_t)nMol);
+        long long o = 0;
+        for (int m = 0; m < nMol; ++m) {
+            off[(size_t)m] = o;
+            o += (long long)nVertices[m] * nVertices[m];
+        }
+        if (t.st == GF_OK) t.st = upload(s, &s->mol_dist, distance, dist_count);
+        t.put(&s->mol_dist_off, off);
+        t.alloc(&s->xd, nV * (size_t)cfg.max_nVertices);
+    }
     s->gru_s = s->gru_t = s->gru_ds = s->gru_dt = s->gru_acc = nullptr;
     if (cfg.gated())   // the gated read-out's two factors per vertex and their gradients
         for (float **p : {&s->gru_s, &s->gru_t, &s->gru_ds, &s->gru_dt}) t.alloc(p, nV * H);
@@ -1023,9 +1052,20 @@ gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, c
     s->P = nullptr;
     s->P_count = 0;
     s->ws_need = 1 << 20;   // (the TN products of dW1_l / dW2_l grow the context's workspace for their split-K partials themselves)
+    if (distance) {   // x_d: every vertex's column, padded and sorted, behind the uploads on the handle's stream
+        const gf_status st = smp_distance_rows_launch(ctx, upload_stream(s), (int)nV, cfg.max_nVertices, s->mol_dist, s->mol_dist_off, s->mol_ptr,
+                                                      s->top_node_mol, s->xd);
+        if (st != GF_OK) return st;
+    }
     GF_HIP_TRY(ctx, hipStreamSynchronize(upload_stream(s)));
     s->prepared = true;
     return GF_OK;
+}
+gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature) {
+    return neighbourhood_prepare(s, nMol, nVertices, adj, feature, nullptr);
+}
+gf_status smp_distance_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature, const double *distance) {
+    return neighbourhood_prepare(s, nMol, nVertices, adj, feature, distance);
 }
 
 // gf_smp_prepare of a matrix-form handle (LCNN, GCN_MW; smp_level_rowlist.hip): the host builds x and the level's row lists, forward and
@@ -1151,6 +1191,8 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
     for (int m = 0; m < nMol; ++m)
         if (nVertices[m] <= 0 || nVertices[m] > 4096) return fail(ctx, GF_ERR_INVALID, "molecule %d has %d vertices", m, nVertices[m]);
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (s->cfg.distance_channel)
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare: a distance handle (distance_channel = 1) takes its molecules through gf_smp_prepare_distance");
     if ((s->cfg.steerable_2d || s->cfg.unrestricted || s->cfg.neighbourhood) && coulomb)   // (these classes have no use_coulomb constructor: their adjacency is the molecule's)
         return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_coulomb: a steerable_2d, unrestricted or neighbourhood handle has no Coulomb adjacency");
     if (s->cfg.matrix_form && coulomb)
@@ -1199,6 +1241,18 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
     }
     s->prepared = true;
     return GF_OK;
+}
+
+gf_status gf_smp_prepare_distance(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature, const double *distance) {
+    if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
+    gf_ctx *ctx = s->ctx;
+    if (!s->cfg.distance_channel)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_distance: the handle has no distance channel (gf_smp_config.distance_channel = 0)");
+    if (nMol <= 0 || !nVertices || !adj || !feature || !distance) return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare_distance: bad argument");
+    for (int m = 0; m < nMol; ++m)
+        if (nVertices[m] <= 0 || nVertices[m] > 4096) return fail(ctx, GF_ERR_INVALID, "molecule %d has %d vertices", m, nVertices[m]);
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return gf::smp_distance_prepare(s, nMol, nVertices, adj, feature, distance);
 }
 
 /* Host only: one molecule of a matrix-form configuration as gf_smp_prepare derives it -- LCNN's order and sequence, GCN_MW's A-hat. */

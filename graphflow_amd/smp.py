@@ -14,7 +14,8 @@ class SMPConfig(C.Structure):
                 ("max_receptive_field", C.c_int), ("has_WL_ordering", C.c_int), ("nContractions", C.c_int),
                 ("custom_matmul", C.c_int), ("physics", C.c_int), ("first_order", C.c_int), ("max_nVertices", C.c_int),
                 ("steerable_2d", C.c_int), ("unrestricted", C.c_int), ("neighbourhood", C.c_int), ("max_Radius", C.c_int),
-                ("matrix_form", C.c_int), ("nNeighbors", C.c_int), ("nChanels2", C.c_int), ("nDense", C.c_int)]
+                ("matrix_form", C.c_int), ("nNeighbors", C.c_int), ("nChanels2", C.c_int), ("nDense", C.c_int),
+                ("distance_channel", C.c_int)]
 
 
 class SMPOmega:
@@ -473,6 +474,60 @@ class SMPGatedNeighbourhood(SMPNeighbourhood):
                              "\"gru_gcn_3d\": GRU_GCN_3D)" % (form,))
         return SMPConfig(nLevels, nHiddens, nFeatures, nDepth, max_nVertices, 0, 0, 0, 0, 0, max_nVertices, 0, 0,
                          SMPGatedNeighbourhood.FORMS[form], max_Radius)
+
+
+class SMPDistance(SMPNeighbourhood):
+    """Batched GCN_1D_Distance (form "gcn_1d_distance"), GCN_2D_Distance ("gcn_2d_distance") and GCN_3D_Distance ("gcn_3d_distance") of
+    GraphFlow/GCN_*D_Distance.h, gf_smp_config.distance_channel = 1 with neighbourhood = 2, 3, 6: the only models that read a molecule's
+    distance matrix.  Two copies of the softmax level of "gcn_1d" / "gcn_2d" / "gcn_3d" run side by side over the same neighbour lists
+    N_l(v) = {u: dist(v, u) <= min(l, max_Radius)} (all three read max_Radius), each with weights of its own:
+      the vertex channel reads x_v[v] = the shell sums [F'], the distance channel x_d[v] = column v of the distance matrix, padded with
+      zeros to max_nVertices and sorted ascending (on the device);
+      graph feature = [sum_v h^v_L[v] | sum_v h^d_L[v]] (2 nHiddens), predict = <W, graph feature>, squared loss.
+    Parameters in registration order: for l = 0..L: W1v_l[H, F'], W1d_l[H, M], and for l > 0 W2v_l[H, H], W2d_l[H, H]; W[2 H].
+    save_model / load_model read and write the classes' files, whose order differs (channel by channel).  prepare() takes molecules as
+    (adj, feature, distance) triples, distance float[V, V]; activation(mol, l, v) is [h^v_l[v] | h^d_l[v]].  The optimiser is Momentum: step()."""
+
+    FORMS = {"gcn_1d_distance": 2, "gcn_2d_distance": 3, "gcn_3d_distance": 6}
+
+    @staticmethod
+    def config(form, nLevels, nHiddens, nFeatures, nDepth, max_nVertices, max_Radius=1):
+        if form not in SMPDistance.FORMS:
+            raise ValueError("SMPDistance: form %r (\"gcn_1d_distance\": GCN_1D_Distance, \"gcn_2d_distance\": GCN_2D_Distance, "
+                             "\"gcn_3d_distance\": GCN_3D_Distance)" % (form,))
+        return SMPConfig(nLevels, nHiddens, nFeatures, nDepth, max_nVertices, 0, 0, 0, 0, 0, max_nVertices, 0, 0,
+                         SMPDistance.FORMS[form], max_Radius, 0, 0, 0, 0, 1)
+
+    @staticmethod
+    def pack(molecules, coulomb=None):
+        """The flat host arrays gf_smp_prepare_distance takes: vertex counts, adjacency, feature and distance matrices back to back."""
+        pk = SMPOmega.pack(molecules)
+        pk["distance"] = np.concatenate([np.ascontiguousarray(m[2], dtype=np.float64).ravel() for m in molecules])
+        assert pk["distance"].size == pk["adj"].size
+        return pk
+
+    def prepare(self, molecules, coulomb=None):
+        """molecules: list of (adj int[V, V], feature float[V, F], distance float[V, V]) or the dict pack() returns.  Blocking."""
+        if coulomb is not None:
+            raise TypeError("SMPDistance.prepare: the distance models have no Coulomb adjacency")
+        pk = molecules if isinstance(molecules, dict) else self.pack(molecules)
+        nV, adj, feat, dist = pk["nV"], pk["adj"], pk["feature"], pk["distance"]
+        self.ctx.check(self.lib.gf_smp_prepare_distance(self.handle, len(nV), nV.ctypes.data_as(C.POINTER(C.c_int)),
+                                                        adj.ctypes.data_as(C.POINTER(C.c_int)), feat.ctypes.data_as(C.POINTER(C.c_double)),
+                                                        dist.ctypes.data_as(C.POINTER(C.c_double))))
+        self.n_mol = len(nV)
+        dev = self.ctx.device
+        self.predict = torch.empty(self.n_mol, dtype=torch.float32, device=dev)
+        self.loss = torch.empty(self.n_mol, dtype=torch.float32, device=dev)
+        self.feature = torch.empty((self.n_mol, 2 * self.cfg.nChanels), dtype=torch.float32, device=dev)
+
+    def activation(self, mol, level, v):
+        """[h^v_level[v] | h^d_level[v]] of molecule `mol` after forward(): numpy [2 nHiddens]."""
+        out = np.empty(2 * self.cfg.nChanels, dtype=np.float32)
+        n = self.lib.gf_smp_read_activation(self.handle, mol, level, v, out.ctypes.data_as(C.c_void_p), out.size)
+        if n != out.size:
+            raise RuntimeError("gf_smp_read_activation(%d, %d, %d) returned %d" % (mol, level, v, n))
+        return out
 
 
 class GCNMW(SMPNeighbourhood):

@@ -440,6 +440,29 @@ typedef struct {
      * level 2: c2[i] [C2]; GCN_MW: h_l[v] [H].  gf_smp_level_sizes: nodes = rows = nMol V (LCNN) or the batch's vertices (GCN_MW), ppos = 0.
      * 0 (a zero-initialised tail): everything as described above, the three LCNN fields are not read. */
     int matrix_form, nNeighbors, nChanels2, nDense;
+    /* distance_channel = 1 with neighbourhood = 2, 3, 6: GCN_1D_Distance, GCN_2D_Distance, GCN_3D_Distance (GraphFlow/GCN_1D_Distance.h,
+     * GCN_2D_Distance.h, GCN_3D_Distance.h) -- the only models that read DenseGraph::distance.  Each is two copies of the softmax level of
+     * forms 2 / 3 / 6 side by side over the same neighbour lists, with weights of their own: the vertex channel reads the shell sums x_v[v]
+     * [F'], the distance channel x_d[v] [M], M = max_nVertices: COLUMN v of the molecule's V x V distance matrix (distance[u][v], u = 0 .. V - 1),
+     * padded with M - V zeros and sorted ascending (the class's Sort op; the zeros of the padding and of the diagonal sort among the values,
+     * negative entries before them; the values are data, nothing flows back through the sort).  Per channel c in {v, d}:
+     *   h^c_0[v] = softmax(W1^c_0 x_c[v]);   h^c_l[v] = softmax(W1^c_l x_c[v] + W2^c_l n^c_l[v]),  n^c_l = the aggregate of h^c_{l-1} over N_l(v)
+     *   graph feature = [ sum_v h^v_L[v] | sum_v h^d_L[v] ]  [2 H];   predict = <W, graph feature>;   loss = 0.5 (predict - target)^2
+     * N_l(v) = { u : dist(v, u) <= min(l, max_Radius) } in ALL three (GCN_2D_Distance reads max_Radius, unlike GCN_2D); the aggregate is the
+     * sum (2), RisiLayer2D in the closed form (3), KMax(RisiLayer3D, H) (6).  Softmax::backward is the diagonal rule of forms 1 - 7.
+     * Parameter order (registration, Momentum and uniform_init order): for l = 0 .. L: W1^v_l [H][F'], W1^d_l [H][M], and for l > 0 W2^v_l [H][H],
+     * W2^d_l [H][H]; then W [2 H].  Matrices draw with the divisor 10 H, W as a Vector with 10 * 2 H.  The classes' save_model / load_model
+     * use ANOTHER order -- all vertex-channel blocks by level, all distance-channel blocks by level, W -- and gf_smp_save_model /
+     * gf_smp_load_model permute for these handles, so checkpoints are the classes' files.
+     * The molecules come through gf_smp_prepare_distance; gf_smp_prepare / gf_smp_prepare_coulomb on such a handle are GF_ERR_INVALID.
+     * Required, else GF_ERR_INVALID: neighbourhood in {2, 3, 6} with that form's rules (6: nChanels <= 64 and its max_nVertices bound),
+     * max_Radius >= 0 in all three, and the LDS bound of form 2 for BOTH operand widths F' and M.  gf_smp_read_activation(mol, l, v) returns
+     * [h^v_l[v] | h^d_l[v]] (2 H); gf_smp_feature_width 2 H; the other introspection calls, the Momentum optimiser and the five
+     * GF_ERR_UNSUPPORTED refusals are those of forms 1 - 7.  x_d is built on the device (smp_level_distance.hip: dist_rows_sort, a bitonic
+     * network across lanes up to 64 entries, through LDS above); a level is one forward launch, one node launch and one gather for both
+     * channels (blockIdx.y selects the operand set); the weight gradients are 2 (2 L + 1) deterministic TN products; no atomics.
+     * 0 (a zero-initialised tail): everything as described above. */
+    int distance_channel;
 } gf_smp_config;
 gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out);
 /* gf_smp_param_count of the handle gf_smp_create would build from cfg (0 on a configuration it would refuse).  Host only. */
@@ -479,6 +502,11 @@ gf_status gf_smp_prepare(gf_smp *smp, int nMol, const int *nVertices, const int 
  * bonds in `adj` still define hops, features and fields.  coulomb == NULL is gf_smp_prepare. */
 gf_status gf_smp_prepare_coulomb(gf_smp *smp, int nMol, const int *nVertices, const int *adj, const double *feature,
                                  const double *coulomb);
+/* The molecules of a distance handle (gf_smp_config.distance_channel = 1): distance = the molecules' V x V matrices of doubles, row-major,
+ * back to back like coulomb (DenseGraph::distance).  GF_ERR_INVALID, before anything is launched: an entry that is not finite (the
+ * molecule is named), a molecule above max_nVertices.  GF_ERR_UNSUPPORTED on any other handle.  The context stays usable. */
+gf_status gf_smp_prepare_distance(gf_smp *smp, int nMol, const int *nVertices, const int *adj, const double *feature,
+                                  const double *distance);
 /* Device pointers.  targets may be NULL (Predict / Feature); predict, loss [nMol] and graph_feature [nMol][C] are
  * optional outputs (graph_feature is what SMP_omega::Feature returns, :984-996). */
 gf_status gf_smp_forward(gf_smp *smp, const float *params, const float *targets, float *predict, float *loss,
@@ -612,6 +640,39 @@ gf_status gf_smp_neighbourhood_gather_bwd_ex_f32(gf_ctx *ctx, int pairs, int H, 
                                                  const float *gTt, const float *sA, const float *hprev, const float *Tprev, float *dhprev);
 gf_status gf_smp_neighbourhood_readout_ex_f32(gf_ctx *ctx, int H, int nV, int nMol, const float *hL, const int *mol_ptr, const float *W,
                                               const float *target, float *g, float *yhat, float *loss, float *dy, float *dW);
+/* The same three kernels on TWO operand sets in one launch each (gf_smp_config.distance_channel: the vertex and the distance channel
+ * of a level; blockIdx.y picks the set).  pairs, H, nV, rounds and the lists are shared; a set is the single-channel call's operands, with
+ * an operand width FD of its own in fwd.  W2 (fwd, node_bwd) must be NULL in both sets or in neither; dy / vmol / nMol are shared.  The
+ * validation is that of the single-channel entries, applied to both sets; set 0 gives the bits of the single-channel call. */
+typedef struct gf_nbh_fwd_set {
+    int FD;
+    const float *W1, *x, *W2, *hprev, *Tprev;
+    float *h, *n, *A, *T, *Tt;
+} gf_nbh_fwd_set;
+typedef struct gf_nbh_node_set {
+    const float *W2, *h;
+    float *dh;
+    const float *Wout, *A, *Tt;
+    float *dn, *gTt, *sA;
+} gf_nbh_node_set;
+typedef struct gf_nbh_gather_set {
+    const float *dn, *gTt, *sA, *hprev, *Tprev;
+    float *dhprev;
+} gf_nbh_gather_set;
+gf_status gf_smp_neighbourhood_fwd2_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, int rounds, const gf_nbh_fwd_set *sets, const long long *ptr,
+                                           const int *idx);
+gf_status gf_smp_neighbourhood_node_bwd2_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, int rounds, const gf_nbh_node_set *sets, const float *dy,
+                                                const int *vmol, int nMol);
+gf_status gf_smp_neighbourhood_gather_bwd2_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, const long long *tptr, const int *tidx,
+                                                  const gf_nbh_gather_set *sets);
+/* The distance channel's input rows (gf_smp_config.distance_channel) as a stand-alone operator, for tests/test_smp_distance_ops_gpu.py.
+ * Device pointers: mol_ptr int [nMol + 1] (prefix sums of the vertex counts, from 0), nVertices int [nMol], distance = the molecules' V x V
+ * matrices of doubles back to back, x_d float [mol_ptr[nMol]][M].  x_d[v] = the ascending sort of (float) distance[u][j], u = 0 .. V - 1 --
+ * COLUMN j = v - mol_ptr[m] of molecule m -- and M - V zeros.  GF_ERR_INVALID before anything is launched (one blocking copy of the
+ * operands per call): nMol or M below 1, M above 4096, a missing operand, a mol_ptr that does not start at 0 or disagrees with nVertices,
+ * a molecule with fewer than 1 or more than M vertices, an entry that is not finite.  Blocking.  The context stays usable. */
+gf_status gf_smp_distance_rows_ex_f32(gf_ctx *ctx, int nMol, int M, const int *mol_ptr, const int *nVertices, const double *distance,
+                                      float *x_d);
 /* The third-order pool (gf_smp_config.neighbourhood = 6, 7), its two kernels as stand-alone operators on caller-supplied operands, for
  * per-vertex tests (tests/test_smp_third_order_ops_gpu.py).  Device pointers, fp32, asynchronous on the context's stream.  H = 1 .. 64
  * channels, nV vertices; lists are CSR: ptr long long [nV + 1] from 0, idx int members in [0, nV), tptr / tidx the transposed list
