@@ -129,6 +129,10 @@ PROTOTYPES.update({
     "gf_smp_neighbourhood_gather_bwd2_ex_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "gf_smp_distance_rows_ex_f32": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "gf_smp_prepare_distance": (_i, [_vp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, _dp]),
+    "gf_smp_prepare_pairs": (_i, [_vp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp]),
+    "gf_smp_gram": (_i, [_vp, _vp]),
+    "gf_smp_pair_readout_ex_f32": (_i, [_vp, _i, _i, _i] + [_vp] * 10),
+    "gf_smp_gram_readout_ex_f32": (_i, [_vp, _i, _i, _i] + [_vp] * 6),
     "gf_smp_third_order_pool_fwd_ex_f32": (_i, [_vp, _i, _i] + [_vp] * 5),
     "gf_smp_third_order_pool_bwd_ex_f32": (_i, [_vp, _i, _i] + [_vp] * 8),
     "gf_smp_rowlist_product_ex_f32": (_i, [_vp, _i, _i, _i, _i, _i, _i] + [_vp] * 7 + [_i, _vp]),

@@ -728,7 +728,7 @@ namespace {
 bool padded_channels(const gf_smp *s) { return s->cfg.nChanels != s->ucfg.nChanels || s->cfg.uniform != s->ucfg.uniform; }
 
 // What gf_smp_forward refuses, padded model or not, before anything is launched.  *params == null: the handle's own model.
-gf_status forward_check(gf_smp *s, const float **params, const float *targets, const float *predict, const float *loss) {
+gf_status forward_check(gf_smp *s, const float **params, const float *targets, const float *predict, const float *loss, const float *graph_feature) {
     if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
     gf_ctx *ctx = s->ctx;
     if (!s->prepared) return fail(ctx, GF_ERR_INVALID, "gf_smp_forward before gf_smp_prepare");
@@ -738,6 +738,9 @@ gf_status forward_check(gf_smp *s, const float **params, const float *targets, c
     }
     if (s->cfg.physics && (targets || predict || loss))
         return fail(ctx, GF_ERR_INVALID, "gf_smp_forward: a physics tower only produces graph_feature (the head owns targets, predict and loss)");
+    if (s->cfg.readout == 2 && (targets || predict || graph_feature))
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_forward: a Gram handle (readout = 2) has no targets, predict or graph_feature: its target is the batch's "
+                                         "adjacency, its prediction comes through gf_smp_gram");
     return GF_OK;
 }
 
@@ -903,6 +906,8 @@ gf_status backward_check(gf_smp *s, const float **params, float **grads, int acc
     if (accumulate && data_parallel(s))
         return fail(ctx, GF_ERR_INVALID, "gf_smp_backward: accumulate with a communicator would re-sum earlier global sums "
                                          "(gf_smp_set_grad_allreduce(smp, 0) and reduce once at the end instead)");
+    if (s->bwd_consumed && s->cfg.readout == 2)   // (the top level's dz_L has replaced the dh_L that gram_readout left)
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_backward: a second reverse sweep of a Gram handle needs a new gf_smp_forward (dz_L replaced dh_L in place)");
     if (s->bwd_consumed)   // (an op-by-op level's reverse sweep overwrites its Q with dQ: the forward state is gone)
         return fail(ctx, GF_ERR_INVALID, "gf_smp_backward: a second reverse sweep needs a new gf_smp_forward (op-by-op levels keep dQ in place of Q)");
     return GF_OK;
@@ -1128,7 +1133,7 @@ extern "C" {
 
 gf_status gf_smp_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss,
                          float *graph_feature) {
-    gf_status st = gf::forward_check(s, &params, targets, predict, loss);
+    gf_status st = gf::forward_check(s, &params, targets, predict, loss, graph_feature);
     if (st != GF_OK) return st;
     gf_ctx *ctx = s->ctx;
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));

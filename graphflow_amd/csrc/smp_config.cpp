@@ -116,6 +116,42 @@ gf_status resolve_config(const gf_smp_config *cfg, const ConfigEntry &entry, Con
         if (nClass < 2) GF_REFUSE(GF_ERR_INVALID, "gf_smp_create_classifier: nClass = %d (at least 2)", nClass);
     }
     // ---- the configuration, family by family ----
+    if (cfg->readout) {   // GCN_1D_Kernel, GCN_2D_Kernel, GCN_3D_Kernel (1: forms 2, 3, 6 on pairs), GCA_1D (2: form 2 under the Gram read-out); smp_level_readouts.hip
+        const int form = cfg->neighbourhood, ro = cfg->readout;
+        if (entry.kind == ConfigEntry::Tower) GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_model_create: the pair and Gram read-outs (readout = %d) are no towers", ro);
+        const bool named = ro == 1 ? form == 2 || form == 3 || form == 6 : ro == 2 && form == 2;
+        if (!named || cfg->distance_channel || cfg->matrix_form)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: readout = %d with neighbourhood = %d, distance_channel = %d, matrix_form = %d: the read-outs are "
+                                      "readout = 1 (pairs) with neighbourhood = 2 (GCN_1D_Kernel), 3 (GCN_2D_Kernel) or 6 (GCN_3D_Kernel) and readout = 2 "
+                                      "(Gram) with neighbourhood = 2 (GCA_1D), distance_channel = matrix_form = 0", ro, form, cfg->distance_channel,
+                      cfg->matrix_form);
+        if (form == 6 && cfg->nChanels > gf::kThirdMaxChanels)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: GCN_3D_Kernel with nChanels = %d: the third-order pool takes at most %d channels", cfg->nChanels,
+                      gf::kThirdMaxChanels);
+        gf_smp_config as2 = *cfg;   // (form 2's rules: all four classes read max_Radius)
+        as2.neighbourhood = 2;
+        as2.readout = 0;
+        if (!rule_neighbourhood(&as2))
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: readout = %d (neighbourhood = %d) needs first_order = steerable_2d = unrestricted = physics = "
+                                      "nContractions = custom_matmul = 0, max_receptive_field (%d) == max_nVertices (%d) <= 4096, nLevels >= 0, "
+                                      "max_Radius (%d) >= 0, nChanels (%d) <= %d and W1_l, W2_l within 160 KiB", ro, form, cfg->max_receptive_field,
+                      cfg->max_nVertices, cfg->max_Radius, cfg->nChanels, gf::kNeighbourhoodMaxChanels);
+        if (form == 6 && cfg->max_nVertices > gf::smp_third_max_members(cfg->nChanels))
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: GCN_3D_Kernel with max_nVertices = %d: the third-order pool stages a neighbourhood's members in "
+                                      "LDS: at most %d vertices at %d channels", cfg->max_nVertices, gf::smp_third_max_members(cfg->nChanels), cfg->nChanels);
+        if (ro == 2 && gf::smp_gram_lds_bytes(cfg->max_nVertices, cfg->nChanels) > 160 * 1024)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: GCA_1D with max_nVertices = %d, nChanels = %d: the Gram read-out keeps a molecule's h_L and E in LDS, "
+                                      "4 (V (H | 1) + V (V | 1) + 4) = %zu bytes against 160 KiB per workgroup", cfg->max_nVertices, cfg->nChanels,
+                      gf::smp_gram_lds_bytes(cfg->max_nVertices, cfg->nChanels));
+        Config c = {cfg->nLevels, cfg->nChanels, cfg->nFeatures, cfg->nDepth, cfg->max_receptive_field, 0};
+        c.nContractions = 0;
+        c.max_nVertices = cfg->max_nVertices;
+        c.neighbourhood = form;
+        c.max_Radius = cfg->max_Radius;
+        c.readout = ro;
+        *out = c;
+        return GF_OK;
+    }
     if (cfg->distance_channel) {   // GCN_1D_Distance, GCN_2D_Distance, GCN_3D_Distance (smp_level_distance.hip): forms 2, 3, 6 on two channels
         const int form = cfg->neighbourhood;
         if (cfg->distance_channel != 1 || cfg->matrix_form || (form != 2 && form != 3 && form != 6))

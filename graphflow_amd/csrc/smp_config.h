@@ -33,6 +33,10 @@ inline size_t smp_third_lds_bytes(int H, int members) {
     return 8 * 2 * (size_t)kThirdCand + 4 * ((size_t)kThirdBins + 256 + 8) + sizeof(float) * ((size_t)H + (size_t)H * H + (size_t)members * H);
 }
 inline int smp_third_max_members(int H) { return (int)((160 * 1024 - smp_third_lds_bytes(H, 0)) / (sizeof(float) * (size_t)H)); }
+// the Gram read-out (smp_level_readouts.hip: gram_readout; readout = 2): one workgroup per molecule keeps h_L [V][H | 1] (the odd row stride
+// serves both of its products without bank conflicts), E [V][V | 1] and four wave partials of the loss in LDS:
+//   4 (V (H | 1) + V (V | 1) + 4) bytes -- 10,920 at V = 29, H = 64; within 160 KiB up to V = 147 at 128 channels, 172 at 64, 199 at 5
+inline size_t smp_gram_lds_bytes(int V, int H) { return sizeof(float) * ((size_t)V * (size_t)(H | 1) + (size_t)V * (size_t)(V | 1) + 4); }
 // the row-list level (smp_level_rowlist.hip; matrix_form = 1, 2): no weights resident in LDS, so no channel limit of that kind.  Its kernels
 // index a column of an operand row and a tile of a launch with ints: a width (slots * Cin, or N) of at most 2^16 keeps slot * Cin + c, the
 // 64-wide tiles of a row (2^10) and a partial image of width x width floats (2^32 elements, counted in a size_t) in range; every launch

@@ -312,6 +312,11 @@ struct gf_smp {
     float *xd = nullptr;
     double *mol_dist = nullptr;
     long long *mol_dist_off = nullptr;
+    // Gram handles (cfg.readout = 2; smp_level_readouts.hip): the molecules' adjacency VALUES as floats and the last forward's Gram matrices,
+    // V_m^2 floats each, back to back (gram_count together), gram_off [nMol + 1] the molecules' first entries
+    float *gram_adj = nullptr, *gram = nullptr;
+    long long *gram_off = nullptr;
+    size_t gram_count = 0;
     // device-built level tables: the batch's adjacency matrices and the per-level statistics the kernels leave behind
     int *mol_nv = nullptr, *mol_adj = nullptr;
     long long *mol_adj_off = nullptr;
@@ -470,6 +475,15 @@ gf_status smp_distance_forward(gf_smp *s, const float *params, const float *targ
 gf_status smp_distance_backward(gf_smp *s, const float *params, float *grads, int accumulate);
 // the classes' save_model order against the registration order: perm[i] = the flat index of the i-th value of a checkpoint
 void smp_distance_checkpoint_order(const gfsmp::Config &c, std::vector<size_t> *perm);
+// GCN_*D_Kernel and GCA_1D (cfg.readout = 1, 2; smp_level_readouts.hip): what smp_neighbourhood_forward / _backward run in place of
+// nbh_readout and nbh_readout_dW.  forward: s->g, s->yhat, s->dy (pairs) or s->gram (Gram), the loss, and dh_L in lv[L].df -- the top level's
+// nbh_node_bwd then runs with dy = NULL; dW: the pair model's dW [2 H] += the fold over the pairs (a Gram handle has no W).
+gf_status smp_readout_forward(gf_smp *s, const float *W, const float *targets, float *predict, float *loss, float *graph_feature);
+gf_status smp_readout_dW(gf_smp *s, const float *W, float *dW);
+// ... and the check of a 32-bit prefix-sum table (mol_ptr, graph_ptr) of a stand-alone call: from 0, never decreasing, within `bound` rows
+gf_status smp_neighbourhood_check_ptr(gf_ctx *ctx, const char *who, const char *what, const int *ptr, int n, int bound);
+gf_status smp_pairs_prepare(gf_smp *s, int nPairs, const int *nVertices1, const int *adj1, const double *feature1, const int *nVertices2,
+                            const int *adj2, const double *feature2);
 // GRU_GCN_1D, GRU_GCN_2D (cfg.neighbourhood = 4, 5; smp_level_gru.hip): the sweeps of a gated handle on the same lists and buffers.
 // params / grads: W; W_z, U_z, W_r, U_r, W_h, U_h, W_g, U_g (shared by the levels: their gradients accumulate across them); U.
 gf_status smp_gru_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature);

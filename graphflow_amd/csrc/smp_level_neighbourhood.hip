@@ -525,6 +525,9 @@ gf_status smp_neighbourhood_check_list(gf_ctx *ctx, const char *who, const char 
 gf_status smp_neighbourhood_check_members(gf_ctx *ctx, const char *who, const char *what, const int *idx, size_t n, int bound) {
     return check_members(ctx, who, what, idx, n, bound);
 }
+gf_status smp_neighbourhood_check_ptr(gf_ctx *ctx, const char *who, const char *what, const int *ptr, int n, int bound) {
+    return check_list<int>(ctx, who, what, ptr, nullptr, n, bound);
+}
 
 gf_status smp_neighbourhood_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature) {
     gf_ctx *ctx = s->ctx;
@@ -534,12 +537,17 @@ gf_status smp_neighbourhood_forward(gf_smp *s, const float *params, const float 
         const gf_status st = level(s, l, p.W1[l], p.W2[l], /*forward=*/true);
         if (st != GF_OK) return st;
     }
-    GF_LAUNCH(ctx, "nbh_readout", nbh_readout, dim3(nMol), dim3(64), 0, s->lv[L].f, s->mol_ptr, p.W, targets, s->g, s->yhat, loss, s->dy, H);
-    if (predict) GF_HIP_TRY(ctx, hipMemcpyAsync(predict, s->yhat, sizeof(float) * nMol, hipMemcpyDeviceToDevice, ctx->stream));
-    if (graph_feature) GF_HIP_TRY(ctx, hipMemcpyAsync(graph_feature, s->g, sizeof(float) * nMol * H, hipMemcpyDeviceToDevice, ctx->stream));
+    if (s->cfg.readout) {   // GCN_*D_Kernel, GCA_1D: the pair and the Gram read-out (smp_level_readouts.hip)
+        const gf_status st = smp_readout_forward(s, p.W, targets, predict, loss, graph_feature);
+        if (st != GF_OK) return st;
+    } else {
+        GF_LAUNCH(ctx, "nbh_readout", nbh_readout, dim3(nMol), dim3(64), 0, s->lv[L].f, s->mol_ptr, p.W, targets, s->g, s->yhat, loss, s->dy, H);
+        if (predict) GF_HIP_TRY(ctx, hipMemcpyAsync(predict, s->yhat, sizeof(float) * nMol, hipMemcpyDeviceToDevice, ctx->stream));
+        if (graph_feature) GF_HIP_TRY(ctx, hipMemcpyAsync(graph_feature, s->g, sizeof(float) * nMol * H, hipMemcpyDeviceToDevice, ctx->stream));
+    }
     s->bwd_consumed = false;
     s->forwarded = true;
-    s->has_targets = targets != nullptr;
+    s->has_targets = targets != nullptr || s->cfg.readout == 2;   // (a Gram handle's target is the batch itself)
     mark_used(s);
     return GF_OK;
 }
@@ -551,9 +559,15 @@ gf_status smp_neighbourhood_backward(gf_smp *s, const float *params, float *grad
     const View<const float> p(s->cfg, params);
     const View<float> d(s->cfg, grads);
     if (!accumulate) GF_HIP_TRY(ctx, hipMemsetAsync(grads, 0, sizeof(float) * param_count(s->cfg), ctx->stream));
-    GF_LAUNCH(ctx, "nbh_readout_dW", nbh_readout_dW, dim3((unsigned)((H + 63) / 64)), dim3(1024), 0, s->dy, s->g, d.W, H, nMol);
+    const bool own_readout = s->cfg.readout != 0;   // (smp_level_readouts.hip: its reverse leaves dh_L in lv[L].df, the top level is then a level like the others)
+    if (own_readout) {
+        const gf_status st = smp_readout_dW(s, p.W, d.W);
+        if (st != GF_OK) return st;
+    } else {
+        GF_LAUNCH(ctx, "nbh_readout_dW", nbh_readout_dW, dim3((unsigned)((H + 63) / 64)), dim3(1024), 0, s->dy, s->g, d.W, H, nMol);
+    }
     for (int l = L; l >= 0; --l) {
-        gf_status st = level(s, l, nullptr, p.W2[l], /*forward=*/false, /*top=*/l == L, p.W);   // dz_l in lv[l].df, dh_{l-1} in lv[l - 1].df
+        gf_status st = level(s, l, nullptr, p.W2[l], /*forward=*/false, /*top=*/l == L && !own_readout, p.W);   // dz_l in lv[l].df, dh_{l-1} in lv[l - 1].df
         // dW1_l [H][F'] += dz^T X,  dW2_l [H][H] += dz^T N: tall-skinny TN products over the vertices of the batch
         if (st == GF_OK) st = gemm(ctx, true, false, H, FD, nV, s->lv[l].df, H, 0, s->x, FD, 0, d.W1[l], FD, 0, 1, 1);
         if (st == GF_OK && l) st = gemm(ctx, true, false, H, H, nV, s->lv[l].df, H, 0, s->lv[l].th_A, H, 0, d.W2[l], H, 0, 1, 1);

@@ -850,6 +850,35 @@ void build_batch_neighbourhood(const Config &cfg, int nMol, const int *nVertices
     }
 }
 
+// GCN_*D_Kernel (Config::readout = 1): X_0, Y_0, X_1, Y_1, ..
+void interleave_pairs(int nFeatures, int nPairs, const int *nVertices1, const int *adj1, const double *feature1, const int *nVertices2,
+                      const int *adj2, const double *feature2, PairBatch *out) {
+    size_t nv = 0, na = 0;
+    for (int p = 0; p < nPairs; ++p)
+        for (const int V : {nVertices1[p], nVertices2[p]}) {
+            nv += (size_t)V;
+            na += (size_t)V * (size_t)V;
+        }
+    out->nVertices.clear();
+    out->adj.clear();
+    out->feature.clear();
+    out->nVertices.reserve(2 * (size_t)nPairs);
+    out->adj.reserve(na);
+    out->feature.reserve(nv * (size_t)nFeatures);
+    size_t a1 = 0, a2 = 0, f1 = 0, f2 = 0;
+    for (int p = 0; p < nPairs; ++p) {
+        const size_t V1 = (size_t)nVertices1[p], V2 = (size_t)nVertices2[p];
+        out->nVertices.push_back(nVertices1[p]);
+        out->nVertices.push_back(nVertices2[p]);
+        out->adj.insert(out->adj.end(), adj1 + a1, adj1 + a1 + V1 * V1);
+        out->adj.insert(out->adj.end(), adj2 + a2, adj2 + a2 + V2 * V2);
+        out->feature.insert(out->feature.end(), feature1 + f1, feature1 + f1 + V1 * (size_t)nFeatures);
+        out->feature.insert(out->feature.end(), feature2 + f2, feature2 + f2 + V2 * (size_t)nFeatures);
+        a1 += V1 * V1, a2 += V2 * V2;
+        f1 += V1 * (size_t)nFeatures, f2 += V2 * (size_t)nFeatures;
+    }
+}
+
 // LCNN, GCN_MW (Config::matrix_form).
 void matrix_form_molecule(const Config &cfg, int molV, const int *adj, const double *feature, MatrixFormMolecule *out) {
     const int F = cfg.nFeatures;

@@ -101,9 +101,15 @@ struct Config {
     // distance rows [max_nVertices], read out over [sum h^v_L | sum h^d_L].  Parameters: W1^v_0 [H][F'], W1^d_0 [H][M] (first_block()); for l =
     // 1..L: W1^v_l, W1^d_l, W2^v_l [H][H], W2^d_l [H][H]; W [2 H].  N_l(v) reads max_Radius in all three.
     int distance_channel = 0;
+    // 1 with neighbourhood = 2, 3, 6: GCN_1D_Kernel, GCN_2D_Kernel, GCN_3D_Kernel (GraphFlow/GCN_*D_Kernel.h; gf_smp_config.readout;
+    // smp_level_readouts.hip): the form's levels on a batch of graph pairs X_0, Y_0, X_1, Y_1, .. (interleave_pairs), read out over
+    // [sum h^X_L | sum h^Y_L].  Parameters: the form's W1_0; W1_l, W2_l; then W [2 H].  N_l(v) reads max_Radius in all three.
+    // 2 with neighbourhood = 2: GCA_1D (GraphFlow/GCA_1D.h, LinearGram.h): GCN_1D's levels, read out as the Gram matrix of the top-level
+    // vectors against the molecule's adjacency values.  Parameters: GCN_1D's without W (readout_block() is empty).
+    int readout = 0;
     bool gated() const { return neighbourhood == 4 || neighbourhood == 5 || neighbourhood == 7; }
     bool third_order() const { return neighbourhood == 6 || neighbourhood == 7; }
-    int nb_radius(int l) const { return neighbourhood == 1 ? 1 : (neighbourhood == 3 && !distance_channel) || l < max_Radius ? l : max_Radius; }   // of N_l (form 1: the adjacency itself; 3 alone ignores max_Radius)
+    int nb_radius(int l) const { return neighbourhood == 1 ? 1 : (neighbourhood == 3 && !distance_channel && readout != 1) || l < max_Radius ? l : max_Radius; }   // of N_l (form 1: the adjacency itself; 3 alone ignores max_Radius)
     size_t filter_floats(int l) const { return level_blocks(l).size_quad(); }   // of an unrestricted level's filter, per s^2
     bool per_size() const { return first_order || steerable_2d; }   // a handle on the th_* tables, per-size blocks in front of the matrix block
     bool concat() const { return first_order >= 3 || steerable_2d == 2; }   // C_l = 2 C_{l-1}
@@ -228,12 +234,12 @@ struct Config {
         return {n, neighbourhood && !gated() ? (size_t)nChanels : n};
     }
     // W [readout_rows()][top_channels()] (SMP_2D_ver6_classification.h:211-217), drawn as one Vector; none in a physics tower, which ends in
-    // its level features: the head's weights are the caller's
+    // its level features: the head's weights are the caller's; none in GCA_1D (readout = 2: top_channels() is 0), W [2 H] of a pair model
     Block readout_block() const {
         const size_t n = physics ? 0 : (size_t)readout_rows() * top_channels();
         return {n, n};
     }
-    int top_channels() const { return distance_channel ? 2 * nChanels : matrix_form == 1 ? nDense : first_order >= 2 || steerable_2d ? level_channels(nLevels) : nChanels;  }   // width of the graph feature and of W's rows
+    int top_channels() const { return readout == 2 ? 0 : distance_channel || readout == 1 ? 2 * nChanels : matrix_form == 1 ? nDense : first_order >= 2 || steerable_2d ? level_channels(nLevels) : nChanels;  }   // width of the graph feature and of W's rows
     int readout_rows() const { return nClass > 1 ? nClass : 1; }   // rows of W: [1][C] is the regression's [C]
     bool square() const { return !physics || uniform; }   // K_l is [nContractions C][C] at every level
     int level_channels(int l) const {
@@ -455,6 +461,17 @@ void build_batch_theta(const Config &cfg, int nMol, const int *nVertices, const 
 // The batch of a neighbourhood model (Config::neighbourhood): hop distances, the shell-sum features x, the neighbour lists and their
 // transposes; none of the field, selection or reduced-adjacency tables.  level[l]: nNodes = rows = vertices.
 void build_batch_neighbourhood(const Config &cfg, int nMol, const int *nVertices, const int *adj, const double *feature, BatchLayout *out);
+
+// The batch of a pair model (Config::readout = 1) in gf_smp_prepare's convention: the 2 nPairs graphs X_0, Y_0, X_1, Y_1, .. -- graph 2 p is
+// X_p (the first batch), 2 p + 1 is Y_p (the second); a global vertex's pair is its graph >> 1, its side its graph & 1.  Vertex counts,
+// adjacency and feature matrices back to back in that order; nFeatures columns per feature row.  Plain copies: the result goes through
+// build_batch_neighbourhood unchanged.
+struct PairBatch {
+    std::vector<int> nVertices, adj;
+    std::vector<double> feature;
+};
+void interleave_pairs(int nFeatures, int nPairs, const int *nVertices1, const int *adj1, const double *feature1, const int *nVertices2,
+                      const int *adj2, const double *feature2, PairBatch *out);
 
 // One molecule of a matrix-form model (Config::matrix_form), as the class derives it.  LCNN (LCNN.h:175-320): the molecule padded to V =
 // max_nVertices vertices, hops and wl of the padded graph, order [V] and seq [V][k]; a pad entry holds molV.  GCN_MW (DenseGraph.h:69-111,

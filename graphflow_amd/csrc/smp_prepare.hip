@@ -1029,6 +1029,21 @@ static gf_status neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices
         t.put(&s->mol_dist_off, off);
         t.alloc(&s->xd, nV * (size_t)cfg.max_nVertices);
     }
+    s->gram_adj = s->gram = nullptr;
+    s->gram_off = nullptr;
+    s->gram_count = 0;
+    std::vector<float> gram_adj;   // (alive until the upload stream has been waited for)
+    std::vector<long long> gram_off;
+    if (cfg.readout == 2) {   // GCA_1D: the adjacency VALUES as floats, the molecules' offsets, room for the Gram matrices (smp_level_readouts.hip)
+        gram_off.assign((size_t)nMol + 1, 0);
+        for (int m = 0; m < nMol; ++m) gram_off[(size_t)m + 1] = gram_off[(size_t)m] + (long long)nVertices[m] * nVertices[m];
+        gram_adj.resize((size_t)gram_off[(size_t)nMol]);
+        for (size_t i = 0; i < gram_adj.size(); ++i) gram_adj[i] = (float)adj[i];
+        t.put(&s->gram_adj, gram_adj);
+        t.put(&s->gram_off, gram_off);
+        t.alloc(&s->gram, gram_adj.size());
+        s->gram_count = gram_adj.size();
+    }
     s->gru_s = s->gru_t = s->gru_ds = s->gru_dt = s->gru_acc = nullptr;
     if (cfg.gated())   // the gated read-out's two factors per vertex and their gradients
         for (float **p : {&s->gru_s, &s->gru_t, &s->gru_ds, &s->gru_dt}) t.alloc(p, nV * H);
@@ -1066,6 +1081,13 @@ gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, c
 }
 gf_status smp_distance_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature, const double *distance) {
     return neighbourhood_prepare(s, nMol, nVertices, adj, feature, distance);
+}
+// gf_smp_prepare_pairs of a pair handle (cfg.readout = 1): the 2 nPairs graphs X_0, Y_0, X_1, Y_1, .. as one neighbourhood batch
+gf_status smp_pairs_prepare(gf_smp *s, int nPairs, const int *nVertices1, const int *adj1, const double *feature1, const int *nVertices2,
+                            const int *adj2, const double *feature2) {
+    gfsmp::PairBatch pb;
+    gfsmp::interleave_pairs(s->cfg.nFeatures, nPairs, nVertices1, adj1, feature1, nVertices2, adj2, feature2, &pb);
+    return neighbourhood_prepare(s, 2 * nPairs, pb.nVertices.data(), pb.adj.data(), pb.feature.data(), nullptr);
 }
 
 // gf_smp_prepare of a matrix-form handle (LCNN, GCN_MW; smp_level_rowlist.hip): the host builds x and the level's row lists, forward and
@@ -1193,6 +1215,8 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (s->cfg.distance_channel)
         return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare: a distance handle (distance_channel = 1) takes its molecules through gf_smp_prepare_distance");
+    if (s->cfg.readout == 1)
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare: a pair handle (readout = 1) takes its graphs through gf_smp_prepare_pairs");
     if ((s->cfg.steerable_2d || s->cfg.unrestricted || s->cfg.neighbourhood) && coulomb)   // (these classes have no use_coulomb constructor: their adjacency is the molecule's)
         return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_coulomb: a steerable_2d, unrestricted or neighbourhood handle has no Coulomb adjacency");
     if (s->cfg.matrix_form && coulomb)
@@ -1246,6 +1270,8 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
 gf_status gf_smp_prepare_distance(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature, const double *distance) {
     if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
     gf_ctx *ctx = s->ctx;
+    if (s->cfg.readout == 1)
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare_distance: a pair handle (readout = 1) takes its graphs through gf_smp_prepare_pairs");
     if (!s->cfg.distance_channel)
         return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_distance: the handle has no distance channel (gf_smp_config.distance_channel = 0)");
     if (nMol <= 0 || !nVertices || !adj || !feature || !distance) return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare_distance: bad argument");
@@ -1253,6 +1279,26 @@ gf_status gf_smp_prepare_distance(gf_smp *s, int nMol, const int *nVertices, con
         if (nVertices[m] <= 0 || nVertices[m] > 4096) return fail(ctx, GF_ERR_INVALID, "molecule %d has %d vertices", m, nVertices[m]);
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     return gf::smp_distance_prepare(s, nMol, nVertices, adj, feature, distance);
+}
+
+gf_status gf_smp_prepare_pairs(gf_smp *s, int nPairs, const int *nVertices1, const int *adj1, const double *feature1, const int *nVertices2,
+                               const int *adj2, const double *feature2) {
+    if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
+    gf_ctx *ctx = s->ctx;
+    if (s->cfg.readout != 1)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_pairs: the handle has no pair read-out (gf_smp_config.readout = %d)", s->cfg.readout);
+    if (nPairs <= 0 || nPairs > 0x3fffffff || !nVertices1 || !adj1 || !feature1 || !nVertices2 || !adj2 || !feature2)
+        return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare_pairs: bad argument");
+    for (int p = 0; p < nPairs; ++p)
+        for (int side = 0; side < 2; ++side) {
+            const int V = side ? nVertices2[p] : nVertices1[p];
+            if (V <= 0 || V > 4096) return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare_pairs: graph %c of pair %d has %d vertices", side ? 'Y' : 'X', p, V);
+            if (V > s->cfg.max_nVertices)   // (before the batch is copied)
+                return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare_pairs: graph %c of pair %d has %d vertices, the model was created with max_nVertices = %d",
+                            side ? 'Y' : 'X', p, V, s->cfg.max_nVertices);
+        }
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return gf::smp_pairs_prepare(s, nPairs, nVertices1, adj1, feature1, nVertices2, adj2, feature2);
 }
 
 /* Host only: one molecule of a matrix-form configuration as gf_smp_prepare derives it -- LCNN's order and sequence, GCN_MW's A-hat. */

@@ -15,7 +15,7 @@ class SMPConfig(C.Structure):
                 ("custom_matmul", C.c_int), ("physics", C.c_int), ("first_order", C.c_int), ("max_nVertices", C.c_int),
                 ("steerable_2d", C.c_int), ("unrestricted", C.c_int), ("neighbourhood", C.c_int), ("max_Radius", C.c_int),
                 ("matrix_form", C.c_int), ("nNeighbors", C.c_int), ("nChanels2", C.c_int), ("nDense", C.c_int),
-                ("distance_channel", C.c_int)]
+                ("distance_channel", C.c_int), ("readout", C.c_int)]
 
 
 class SMPOmega:
@@ -527,6 +527,90 @@ class SMPDistance(SMPNeighbourhood):
         n = self.lib.gf_smp_read_activation(self.handle, mol, level, v, out.ctypes.data_as(C.c_void_p), out.size)
         if n != out.size:
             raise RuntimeError("gf_smp_read_activation(%d, %d, %d) returned %d" % (mol, level, v, n))
+        return out
+
+
+class SMPKernelPairs(SMPNeighbourhood):
+    """Batched GCN_1D_Kernel (form "gcn_1d_kernel"), GCN_2D_Kernel ("gcn_2d_kernel") and GCN_3D_Kernel ("gcn_3d_kernel") of
+    GraphFlow/GCN_*D_Kernel.h, gf_smp_config.readout = 1 with neighbourhood = 2, 3, 6: kernel learning on pairs of graphs.  Graphs X and Y go
+    through the levels of "gcn_1d" / "gcn_2d" / "gcn_3d" with the same weights, N_l(v) = {u: dist(v, u) <= min(l, max_Radius)} in all three
+    (GCN_2D_Kernel reads max_Radius):
+      graph feature = [sum_v h^X_L[v] | sum_v h^Y_L[v]] (2 nHiddens), predict = <W, graph feature>, squared loss.
+    Parameters in registration order: W1_0[H, F']; for l = 1..L: W1_l[H, F'], W2_l[H, H]; W[2 H].  The arguments are the classes' constructor's.
+    prepare(graphs_x, graphs_y) takes two lists of (adj, feature) of equal length; X_p and Y_p may differ in size.  forward() returns predict,
+    loss [nPairs] and the features [nPairs, 2 H]; receptive_field / activation / level_sizes count graph 2 p for X_p and 2 p + 1 for Y_p.
+    The optimiser is Momentum: step()."""
+
+    FORMS = {"gcn_1d_kernel": 2, "gcn_2d_kernel": 3, "gcn_3d_kernel": 6}
+
+    def __init__(self, form, nLevels, max_nVertices, nFeatures, nHiddens, nDepth, max_Radius, ctx=None):
+        super().__init__(form, nLevels, nHiddens, nFeatures, nDepth, max_nVertices, max_Radius, ctx=ctx)
+
+    @staticmethod
+    def config(form, nLevels, nHiddens, nFeatures, nDepth, max_nVertices, max_Radius=1):
+        if form not in SMPKernelPairs.FORMS:
+            raise ValueError("SMPKernelPairs: form %r (\"gcn_1d_kernel\": GCN_1D_Kernel, \"gcn_2d_kernel\": GCN_2D_Kernel, "
+                             "\"gcn_3d_kernel\": GCN_3D_Kernel)" % (form,))
+        return SMPConfig(nLevels, nHiddens, nFeatures, nDepth, max_nVertices, 0, 0, 0, 0, 0, max_nVertices, 0, 0,
+                         SMPKernelPairs.FORMS[form], max_Radius, 0, 0, 0, 0, 0, 1)
+
+    def prepare(self, graphs_x, graphs_y=None, coulomb=None):
+        """graphs_x, graphs_y: lists of (adj int[V, V], feature float[V, F]) of equal length (or the dicts pack() returns).  Blocking."""
+        if graphs_y is None or coulomb is not None:
+            raise TypeError("SMPKernelPairs.prepare(graphs_x, graphs_y): a pair model takes two lists of graphs and no Coulomb adjacency")
+        px = graphs_x if isinstance(graphs_x, dict) else self.pack(graphs_x)
+        py = graphs_y if isinstance(graphs_y, dict) else self.pack(graphs_y)
+        if len(px["nV"]) != len(py["nV"]):
+            raise ValueError("SMPKernelPairs.prepare: %d graphs X, %d graphs Y" % (len(px["nV"]), len(py["nV"])))
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        self.ctx.check(self.lib.gf_smp_prepare_pairs(self.handle, len(px["nV"]), px["nV"].ctypes.data_as(ip), px["adj"].ctypes.data_as(ip),
+                                                     px["feature"].ctypes.data_as(dp), py["nV"].ctypes.data_as(ip), py["adj"].ctypes.data_as(ip),
+                                                     py["feature"].ctypes.data_as(dp)))
+        self.n_mol = len(px["nV"])   # (pairs: what targets, predict and loss count)
+        dev = self.ctx.device
+        self.predict = torch.empty(self.n_mol, dtype=torch.float32, device=dev)
+        self.loss = torch.empty(self.n_mol, dtype=torch.float32, device=dev)
+        self.feature = torch.empty((self.n_mol, 2 * self.cfg.nChanels), dtype=torch.float32, device=dev)
+
+
+class GCA1D(SMPNeighbourhood):
+    """Batched GCA_1D (GraphFlow/GCA_1D.h, LinearGram.h), gf_smp_config.readout = 2 with neighbourhood = 2: the graph auto-encoder on
+    GCN_1D's levels.  There is no W and no target:
+      G[x, y] = <h_L[x], h_L[y]>;  loss = 0.5 sum (G - adj)^2 with the adjacency taken by VALUE (an entry of 2 counts as 2, an asymmetric
+      matrix as written);  dh_L[x] = sum_y (E[x, y] + E[y, x]) h_L[y],  E = G - adj.
+    Parameters: W1_0[H, F']; for l = 1..L: W1_l[H, F'], W2_l[H, H].  The arguments are the class's constructor's.  forward(params) returns the
+    per-molecule loss; gram() the list of V x V matrices of the last forward (Predict); backward() works after any forward, once per forward.
+    The optimiser is Momentum: step()."""
+
+    def __init__(self, nLevels, max_nVertices, nFeatures, nHiddens, nDepth, max_Radius, ctx=None):
+        super().__init__("gca_1d", nLevels, nHiddens, nFeatures, nDepth, max_nVertices, max_Radius, ctx=ctx)
+
+    @staticmethod
+    def config(form, nLevels, nHiddens, nFeatures, nDepth, max_nVertices, max_Radius=1):
+        if form != "gca_1d":
+            raise ValueError("GCA1D: form %r (\"gca_1d\": GCA_1D)" % (form,))
+        return SMPConfig(nLevels, nHiddens, nFeatures, nDepth, max_nVertices, 0, 0, 0, 0, 0, max_nVertices, 0, 0, 2, max_Radius, 0, 0, 0, 0, 0, 2)
+
+    def prepare(self, molecules, coulomb=None):
+        super().prepare(molecules, coulomb)
+        nV = molecules["nV"] if isinstance(molecules, dict) else [len(m[0]) for m in molecules]
+        self.n_vertices = [int(v) for v in nV]
+
+    def forward(self, params, targets=None):
+        if targets is not None:
+            raise TypeError("GCA1D.forward: the auto-encoder's target is the batch's own adjacency")
+        self._flat(params, "params")
+        self.ctx.check(self.lib.gf_smp_forward(self.handle, C.c_void_p(params.data_ptr()), None, None, C.c_void_p(self.loss.data_ptr()), None))
+        return self.loss
+
+    def gram(self):
+        """The Gram matrices of the last forward(): a list of numpy [V, V] float32 arrays, one per molecule."""
+        flat = torch.empty(sum(v * v for v in self.n_vertices), dtype=torch.float32, device=self.ctx.device)
+        self.ctx.check(self.lib.gf_smp_gram(self.handle, C.c_void_p(flat.data_ptr())))
+        host, out, at = flat.cpu().numpy(), [], 0
+        for v in self.n_vertices:
+            out.append(host[at:at + v * v].reshape(v, v))
+            at += v * v
         return out
 
 

@@ -463,6 +463,36 @@ typedef struct {
      * channels (blockIdx.y selects the operand set); the weight gradients are 2 (2 L + 1) deterministic TN products; no atomics.
      * 0 (a zero-initialised tail): everything as described above. */
     int distance_channel;
+    /* readout = 1 with neighbourhood = 2, 3, 6: GCN_1D_Kernel, GCN_2D_Kernel, GCN_3D_Kernel (GraphFlow/GCN_1D_Kernel.h, GCN_2D_Kernel.h,
+     * GCN_3D_Kernel.h) -- kernel learning on a PAIR of graphs.  Graphs X and Y go through the levels of forms 2 / 3 / 6 with the same weights
+     * (x, dist, level 0, the update, the aggregates and the diagonal Softmax::backward are the forms' own); only what sits above h_L differs:
+     *   graph feature = [ sum_v h^X_L[v] | sum_v h^Y_L[v] ]  [2 H];   predict = <W, graph feature>, W [2 H];   loss = 0.5 (predict - target)^2
+     * N_l(v) = { u : dist(v, u) <= min(l, max_Radius) } in ALL three (GCN_2D_Kernel reads max_Radius, as GCN_2D_Distance does and GCN_2D does
+     * not).  W1_l and W2_l enter the graph once per level: their gradient is the sum over the vertices of both graphs.  Parameter order
+     * (registration, Momentum and save_model order): W1_0 [H][F']; for l = 1..L: W1_l [H][F'], W2_l [H][H]; W [2 H].  Matrices draw with the
+     * divisor 10 H, W as a Vector with 10 * 2 H.  The batch comes through gf_smp_prepare_pairs (gf_smp_prepare, _coulomb and _distance on such a
+     * handle are GF_ERR_INVALID): it is the 2 nPairs graphs X_0, Y_0, X_1, Y_1, .. on the lists and tables of forms 2 / 3 / 6; X and Y may have
+     * different vertex counts, each at most max_nVertices.  gf_smp_forward: targets, predict, loss [nPairs], graph_feature [nPairs][2 H];
+     * gf_smp_feature_width 2 H.  The molecule index of gf_smp_receptive_field, gf_smp_read_activation and gf_smp_level_sizes is 2 p for X_p,
+     * 2 p + 1 for Y_p.  The read-out is smp_level_readouts.hip: one wave per pair (the two segment sums in ascending vertex order), dW as a
+     * fold over the pairs in fixed order, dh_L[v] = dy[pair(v)] W[side(v) H + c] written before the levels' unchanged reverse kernels.
+     * readout = 2 with neighbourhood = 2: GCA_1D (GraphFlow/GCA_1D.h, LinearGram.h) -- the graph auto-encoder.  The levels are GCN_1D's; there
+     * is no W and no target:
+     *   G[x][y] = <h_L[x], h_L[y]>  (V x V per molecule);   loss = 0.5 sum_{x,y} (G[x][y] - adj[x][y])^2,  adj[x][y] taken as its integer VALUE
+     *   (an entry of 2 counts as 2, an asymmetric matrix is taken as written);   with E = G - adj:  dh_L[x] = sum_y (E[x][y] + E[y][x]) h_L[y]
+     *   (LinearGram::backward: the diagonal term counts twice).
+     * Parameters: GCN_1D's without W.  gf_smp_prepare as for form 2 (it also uploads the adjacency values as floats).  gf_smp_forward: targets,
+     * predict and graph_feature must be NULL (GF_ERR_INVALID otherwise), loss [nMol] is the per-molecule loss; gf_smp_feature_width 0; gf_smp_gram
+     * copies G.  gf_smp_backward works after any forward (the target is the batch itself).  The read-out is gram_readout of
+     * smp_level_readouts.hip: one workgroup per molecule, h_L [V][H] staged once into LDS with the row stride H | 1, E [V][V | 1] beside it, G,
+     * the loss (a fixed-order reduction) and dh_L = (E + E^T) h_L from one launch, fp32 FMAs.  Required beside form 2's rules: 4 (max_nVertices
+     * (nChanels | 1) + max_nVertices (max_nVertices | 1) + 4) bytes within 160 KiB.
+     * Both: required, else GF_ERR_INVALID (gf_smp_config_param_count answers 0): readout in 0 .. 2, distance_channel = matrix_form = 0, the
+     * neighbourhood named above, and the underlying form's rules unchanged (the LDS bound, nChanels <= 64 and the max_nVertices bound of form
+     * 6, max_Radius >= 0).  The optimiser is Momentum; the five GF_ERR_UNSUPPORTED refusals are those of forms 1 - 7; gf_smp_forward_host
+     * refuses both read-outs by name (GF_ERR_UNSUPPORTED).  No float atomics; two runs give the same bits.
+     * 0 (a zero-initialised tail): everything as described above. */
+    int readout;
 } gf_smp_config;
 gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out);
 /* gf_smp_param_count of the handle gf_smp_create would build from cfg (0 on a configuration it would refuse).  Host only. */
@@ -507,6 +537,15 @@ gf_status gf_smp_prepare_coulomb(gf_smp *smp, int nMol, const int *nVertices, co
  * molecule is named), a molecule above max_nVertices.  GF_ERR_UNSUPPORTED on any other handle.  The context stays usable. */
 gf_status gf_smp_prepare_distance(gf_smp *smp, int nMol, const int *nVertices, const int *adj, const double *feature,
                                   const double *distance);
+/* The pairs of a pair handle (gf_smp_config.readout = 1): two batches in the convention of gf_smp_prepare, nVertices1 / adj1 / feature1 the
+ * graphs X_p, nVertices2 / adj2 / feature2 the graphs Y_p, p = 0 .. nPairs - 1.  The device batch is X_0, Y_0, X_1, Y_1, ..  GF_ERR_INVALID
+ * before anything is launched: a graph above max_nVertices (the pair and the side are named).  GF_ERR_UNSUPPORTED on any other handle.
+ * The context stays usable. */
+gf_status gf_smp_prepare_pairs(gf_smp *smp, int nPairs, const int *nVertices1, const int *adj1, const double *feature1, const int *nVertices2,
+                               const int *adj2, const double *feature2);
+/* The Gram matrices of the last gf_smp_forward of a Gram handle (gf_smp_config.readout = 2) to a DEVICE pointer: the molecules back to back,
+ * V_m^2 floats each, row-major.  GF_ERR_UNSUPPORTED on any other handle, GF_ERR_INVALID before a forward. */
+gf_status gf_smp_gram(gf_smp *smp, float *out);
 /* Device pointers.  targets may be NULL (Predict / Feature); predict, loss [nMol] and graph_feature [nMol][C] are
  * optional outputs (graph_feature is what SMP_omega::Feature returns, :984-996). */
 gf_status gf_smp_forward(gf_smp *smp, const float *params, const float *targets, float *predict, float *loss,
@@ -673,6 +712,25 @@ gf_status gf_smp_neighbourhood_gather_bwd2_ex_f32(gf_ctx *ctx, int pairs, int H,
  * a molecule with fewer than 1 or more than M vertices, an entry that is not finite.  Blocking.  The context stays usable. */
 gf_status gf_smp_distance_rows_ex_f32(gf_ctx *ctx, int nMol, int M, const int *mol_ptr, const int *nVertices, const double *distance,
                                       float *x_d);
+/* The two read-outs of gf_smp_config.readout as stand-alone operators on caller-supplied operands (smp_level_readouts.hip;
+ * tests/test_pair_gram_ops_gpu.py).  Device pointers, fp32.  H = 1 .. 128 channels, nV rows of hL.  pair_readout validates with one blocking
+ * copy and then launches asynchronously on the context's stream; gram_readout is BLOCKING: a test operator that allocates its table of
+ * matrix offsets for the length of the call, waits for the stream and frees it.
+ *   pair_readout: graph_ptr int [2 nPairs + 1] (prefix sums of the graphs' vertex counts X_0, Y_0, X_1, .., from 0, within the nV rows);
+ *             g[p] = [sum of hL over X_p | over Y_p] [2 H] in ascending vertex order, yhat[p] = <W, g[p]> (W [2 H]), dy = yhat - target (target
+ *             NULL: 0), loss = 0.5 dy^2 (NULL: not stored); dW[c] += sum_p dy[p] g[p][c], folded over the pairs in a fixed order; dhL[v][c] =
+ *             dy[pair(v)] W[side(v) H + c] for every vertex of a graph (dhL NULL: not written).  A graph may be empty.
+ *   gram_readout: mol_ptr int [nMol + 1]; adj = the molecules' V x V matrices as floats, row-major, back to back; gram the same shape:
+ *             gram[x][y] = <hL[x], hL[y]>, loss[m] = 0.5 sum (gram - adj)^2 (NULL: not stored), dhL[x] = sum_y (E[x][y] + E[y][x]) hL[y] with
+ *             E = gram - adj (dhL NULL: not written).  One workgroup per molecule; every molecule needs 4 (V (H | 1) + V (V | 1) + 4) bytes
+ *             of LDS within 160 KiB.
+ * GF_ERR_INVALID before anything is launched: H outside 1 .. 128, nV / nPairs / nMol < 1, a missing operand, and -- checked on the host, one
+ * blocking copy per call -- a list that does not start at 0, decreases or leaves the nV rows, a molecule beyond the LDS bound (named).  The
+ * context stays usable after a refusal. */
+gf_status gf_smp_pair_readout_ex_f32(gf_ctx *ctx, int H, int nV, int nPairs, const float *hL, const int *graph_ptr, const float *W,
+                                     const float *target, float *g, float *yhat, float *loss, float *dy, float *dW, float *dhL);
+gf_status gf_smp_gram_readout_ex_f32(gf_ctx *ctx, int H, int nV, int nMol, const float *hL, const int *mol_ptr, const float *adj, float *gram,
+                                     float *loss, float *dhL);
 /* The third-order pool (gf_smp_config.neighbourhood = 6, 7), its two kernels as stand-alone operators on caller-supplied operands, for
  * per-vertex tests (tests/test_smp_third_order_ops_gpu.py).  Device pointers, fp32, asynchronous on the context's stream.  H = 1 .. 64
  * channels, nV vertices; lists are CSR: ptr long long [nV + 1] from 0, idx int members in [0, nV), tptr / tidx the transposed list
