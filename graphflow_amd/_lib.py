@@ -127,6 +127,10 @@ PROTOTYPES.update({
     "gf_smp_neighbourhood_fwd2_ex_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gf_smp_neighbourhood_node_bwd2_ex_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i]),
     "gf_smp_neighbourhood_gather_bwd2_ex_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "gf_smp_gru_cell_fwd_ex_f32": (_i, [_vp, _i, _i, _i, _i] + [_vp] * 13),
+    "gf_smp_gru_cell_bwd_ex_f32": (_i, [_vp, _i, _i, _i, _i] + [_vp] * 16),
+    "gf_smp_gru_readout_fwd_ex_f32": (_i, [_vp, _i, _i, _i, _i] + [_vp] * 11),
+    "gf_smp_gru_readout_bwd_ex_f32": (_i, [_vp, _i, _i, _i, _i] + [_vp] * 11),
     "gf_smp_distance_rows_ex_f32": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "gf_smp_prepare_distance": (_i, [_vp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, _dp]),
     "gf_smp_prepare_pairs": (_i, [_vp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp]),

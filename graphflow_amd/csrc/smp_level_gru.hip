@@ -14,6 +14,9 @@
 // The eight weight gradients are the library's deterministic TN products.  Every sum runs in a fixed order; no atomics; every wave of a
 // workgroup makes the same trips around the barriers; an operand of a lane without a channel is loaded from a clamped address and never
 // stored (NOTES.md: no guard around an operand load).
+// The cell, its reverse and the read-out are also operators of the C ABI on caller-supplied operands (gf_smp_gru_cell_fwd_ex_f32,
+// gf_smp_gru_cell_bwd_ex_f32, gf_smp_gru_readout_fwd_ex_f32, gf_smp_gru_readout_bwd_ex_f32, at the end of this file): the launchers
+// below, for tests/test_smp_gru_ops_gpu.py.
 #include <cmath>
 
 #include "smp_internal.h"
@@ -337,6 +340,11 @@ inline int vertices_per_group(int nV, int slots, size_t lds_bytes) {
     return slots * (int)(rounds < 1 ? 1 : rounds);
 }
 
+// rounds = 0: the level's own vertices per workgroup; > 0: that many rounds of a workgroup's slots (the stand-alone operators)
+inline int group_vertices(int nV, int slots, size_t lds_bytes, int rounds) {
+    return rounds > 0 ? slots * rounds : vertices_per_group(nV, slots, lds_bytes);
+}
+
 // the launches on raw operands
 struct Shape {
     int H, nV, G, slots;
@@ -345,10 +353,10 @@ struct Shape {
 };
 
 template <bool PAIRS, bool GIVEN = false>
-gf_status cell_fwd_launch(gf_ctx *ctx, const Shape &sh, const float *M6, const float *hprev, const float *Tprev, const long long *ptr,
-                          const int *idx, float *h, float *n, float *z, float *r, float *c, float *A, float *T, float *Tt) {
+gf_status cell_fwd_launch(gf_ctx *ctx, const Shape &sh, int rounds, const float *M6, const float *hprev, const float *Tprev,
+                          const long long *ptr, const int *idx, float *h, float *n, float *z, float *r, float *c, float *A, float *T, float *Tt) {
     const size_t bytes = smp_gru_lds_bytes(sh.H);
-    const int vpg = vertices_per_group(sh.nV, sh.slots, bytes);
+    const int vpg = group_vertices(sh.nV, sh.slots, bytes, rounds);
     const gf_status st = opt_in_lds(ctx, gru_cell_fwd<PAIRS, GIVEN>, bytes);
     if (st != GF_OK) return st;
     GF_LAUNCH(ctx, "gru_cell_fwd", (gru_cell_fwd<PAIRS, GIVEN>), sh.grid(vpg), dim3(kBlock), bytes, M6, hprev, Tprev, ptr, idx, h, n, z, r, c, A, T, Tt,
@@ -357,11 +365,11 @@ gf_status cell_fwd_launch(gf_ctx *ctx, const Shape &sh, const float *M6, const f
 }
 
 template <bool PAIRS>
-gf_status cell_bwd_launch(gf_ctx *ctx, const Shape &sh, const float *M6, const float *hprev, const float *dh, const float *z, const float *r,
-                          const float *c, const float *A, const float *Tt, float *dzp, float *drp, float *dcp, float *q, float *dn, float *gTt,
-                          float *sA, float *direct) {
+gf_status cell_bwd_launch(gf_ctx *ctx, const Shape &sh, int rounds, const float *M6, const float *hprev, const float *dh, const float *z,
+                          const float *r, const float *c, const float *A, const float *Tt, float *dzp, float *drp, float *dcp, float *q,
+                          float *dn, float *gTt, float *sA, float *direct) {
     const size_t bytes = sizeof(float) * (6 * (size_t)sh.H * sh.H + 3 * (size_t)sh.slots * sh.H);
-    const int vpg = vertices_per_group(sh.nV, sh.slots, bytes);
+    const int vpg = group_vertices(sh.nV, sh.slots, bytes, rounds);
     const gf_status st = opt_in_lds(ctx, gru_cell_bwd<PAIRS>, bytes);
     if (st != GF_OK) return st;
     GF_LAUNCH(ctx, "gru_cell_bwd", (gru_cell_bwd<PAIRS>), sh.grid(vpg), dim3(kBlock), bytes, M6, hprev, dh, z, r, c, A, Tt, dzp, drp, dcp, q, dn,
@@ -369,10 +377,10 @@ gf_status cell_bwd_launch(gf_ctx *ctx, const Shape &sh, const float *M6, const f
     return GF_OK;
 }
 
-gf_status readout_fwd_launch(gf_ctx *ctx, const Shape &sh, int nMol, const float *M2, const float *U, const float *hL, const int *mol_ptr,
-                             const float *target, float *s, float *t, float *g, float *yhat, float *loss, float *dy) {
+gf_status readout_fwd_launch(gf_ctx *ctx, const Shape &sh, int rounds, int nMol, const float *M2, const float *U, const float *hL,
+                             const int *mol_ptr, const float *target, float *s, float *t, float *g, float *yhat, float *loss, float *dy) {
     const size_t bytes = sizeof(float) * (2 * (size_t)sh.H * row_stride(sh.H) + (size_t)sh.slots * sh.H);
-    const int vpg = vertices_per_group(sh.nV, sh.slots, bytes);
+    const int vpg = group_vertices(sh.nV, sh.slots, bytes, rounds);
     const gf_status st = opt_in_lds(ctx, gru_readout_fwd, bytes);
     if (st != GF_OK) return st;
     GF_LAUNCH(ctx, "gru_readout_fwd", gru_readout_fwd, sh.grid(vpg), dim3(kBlock), bytes, M2, hL, s, t, sh.nV, sh.H, sh.G, vpg);
@@ -380,14 +388,19 @@ gf_status readout_fwd_launch(gf_ctx *ctx, const Shape &sh, int nMol, const float
     return GF_OK;
 }
 
-gf_status readout_bwd_launch(gf_ctx *ctx, const Shape &sh, const float *M2, const float *U, const float *s, const float *t, const float *g,
-                             const float *dy, const int *vmol, float *ds, float *dt, float *dh) {
+gf_status readout_bwd_launch(gf_ctx *ctx, const Shape &sh, int rounds, const float *M2, const float *U, const float *s, const float *t,
+                             const float *g, const float *dy, const int *vmol, float *ds, float *dt, float *dh) {
     const size_t bytes = sizeof(float) * (2 * (size_t)sh.H * sh.H + 2 * (size_t)sh.slots * sh.H);
-    const int vpg = vertices_per_group(sh.nV, sh.slots, bytes);
+    const int vpg = group_vertices(sh.nV, sh.slots, bytes, rounds);
     const gf_status st = opt_in_lds(ctx, gru_readout_bwd, bytes);
     if (st != GF_OK) return st;
     GF_LAUNCH(ctx, "gru_readout_bwd", gru_readout_bwd, sh.grid(vpg), dim3(kBlock), bytes, M2, s, t, g, dy, U, vmol, ds, dt, dh, sh.nV, sh.H, sh.G,
               vpg);
+    return GF_OK;
+}
+
+gf_status readout_dU_launch(gf_ctx *ctx, int H, int nMol, const float *dy, const float *g, float *dU) {
+    GF_LAUNCH(ctx, "gru_readout_dU", gru_readout_dU, dim3((unsigned)((H + 63) / 64)), dim3(1024), 0, dy, g, dU, H, nMol);
     return GF_OK;
 }
 
@@ -418,17 +431,18 @@ gf_status smp_gru_forward(gf_smp *s, const float *params, const float *targets, 
         if (s->cfg.third_order()) {   // GRU_GCN_3D: the pool leaves n_l in th_A, the cell reads it there
             st = smp_third_pool_fwd_launch(ctx, H, nV, d.nb_max_members, pv.f, d.nb_ptr, d.nb_idx, d.th_A, d.nb_sel);
             if (st == GF_OK)
-                st = cell_fwd_launch<false, true>(ctx, sh, p.mat(0), pv.f, nullptr, d.nb_ptr, d.nb_idx, d.f, d.th_A, d.gru_z, d.gru_r, d.gru_c, nullptr,
-                                                  nullptr, nullptr);
+                st = cell_fwd_launch<false, true>(ctx, sh, 0, p.mat(0), pv.f, nullptr, d.nb_ptr, d.nb_idx, d.f, d.th_A, d.gru_z, d.gru_r, d.gru_c,
+                                                  nullptr, nullptr, nullptr);
             continue;
         }
         st = with_aggregate(pairs, [&](auto pr) -> gf_status {
-            return cell_fwd_launch<decltype(pr)::value>(ctx, sh, p.mat(0), pv.f, pv.nb_T, d.nb_ptr, d.nb_idx, d.f, d.th_A, d.gru_z, d.gru_r, d.gru_c,
-                                                        d.th_B, d.nb_T, d.nb_Tt);
+            return cell_fwd_launch<decltype(pr)::value>(ctx, sh, 0, p.mat(0), pv.f, pv.nb_T, d.nb_ptr, d.nb_idx, d.f, d.th_A, d.gru_z, d.gru_r,
+                                                        d.gru_c, d.th_B, d.nb_T, d.nb_Tt);
         });
     }
     if (st == GF_OK)
-        st = readout_fwd_launch(ctx, sh, nMol, p.mat(6), p.U, s->lv[L].f, s->mol_ptr, targets, s->gru_s, s->gru_t, s->g, s->yhat, loss, s->dy);
+        st = readout_fwd_launch(ctx, sh, 0, nMol, p.mat(6), p.U, s->lv[L].f, s->mol_ptr, targets, s->gru_s, s->gru_t, s->g, s->yhat, loss,
+                                s->dy);
     if (st != GF_OK) return st;
     if (predict) GF_HIP_TRY(ctx, hipMemcpyAsync(predict, s->yhat, sizeof(float) * nMol, hipMemcpyDeviceToDevice, ctx->stream));
     if (graph_feature) GF_HIP_TRY(ctx, hipMemcpyAsync(graph_feature, s->g, sizeof(float) * nMol * H, hipMemcpyDeviceToDevice, ctx->stream));
@@ -456,16 +470,17 @@ gf_status smp_gru_backward(gf_smp *s, const float *params, float *grads, int acc
     float *sweep = accumulate ? s->gru_acc : grads;
     const View<float> d(s->cfg, sweep);
     GF_HIP_TRY(ctx, hipMemsetAsync(sweep, 0, sizeof(float) * np, ctx->stream));
-    GF_LAUNCH(ctx, "gru_readout_dU", gru_readout_dU, dim3((unsigned)((H + 63) / 64)), dim3(1024), 0, s->dy, s->g, d.U, H, nMol);
-    gf_status st = readout_bwd_launch(ctx, sh, p.mat(6), p.U, s->gru_s, s->gru_t, s->g, s->dy, s->top_node_mol, s->gru_ds, s->gru_dt, s->lv[L].df);
+    gf_status st = readout_dU_launch(ctx, H, nMol, s->dy, s->g, d.U);
+    if (st == GF_OK)
+        st = readout_bwd_launch(ctx, sh, 0, p.mat(6), p.U, s->gru_s, s->gru_t, s->g, s->dy, s->top_node_mol, s->gru_ds, s->gru_dt, s->lv[L].df);
     if (st == GF_OK) st = wgrad(ctx, sh, s->gru_ds, s->lv[L].f, d.mat(6));   // dW_g += ds^T h_L
     if (st == GF_OK) st = wgrad(ctx, sh, s->gru_dt, s->lv[L].f, d.mat(7));   // dU_g += dt^T h_L
     for (int l = L; l >= 1 && st == GF_OK; --l) {   // dh_l in lv[l].df -> dh_{l-1} in lv[l - 1].df
         gf_smp::DevLevel &v = s->lv[l];
         gf_smp::DevLevel &pv = s->lv[l - 1];
         st = with_aggregate(pairs, [&](auto pr) -> gf_status {
-            return cell_bwd_launch<decltype(pr)::value>(ctx, sh, p.mat(0), pv.f, v.df, v.gru_z, v.gru_r, v.gru_c, v.th_B, v.nb_Tt, v.gru_dz, v.gru_dr,
-                                                        v.gru_dc, v.gru_q, v.Q, v.th_node, v.nb_sA, v.gru_direct);
+            return cell_bwd_launch<decltype(pr)::value>(ctx, sh, 0, p.mat(0), pv.f, v.df, v.gru_z, v.gru_r, v.gru_c, v.th_B, v.nb_Tt, v.gru_dz,
+                                                        v.gru_dr, v.gru_dc, v.gru_q, v.Q, v.th_node, v.nb_sA, v.gru_direct);
         });
         const float *lhs[6] = {v.gru_dz, v.gru_dz, v.gru_dr, v.gru_dr, v.gru_dc, v.gru_dc};
         const float *rhs[6] = {v.th_A, pv.f, v.th_A, pv.f, v.th_A, v.gru_q};   // n, hp, n, hp, n, q
@@ -490,3 +505,88 @@ gf_status smp_gru_backward(gf_smp *s, const float *params, float *grads, int acc
 }
 
 }  // namespace gf
+
+// ---- the level's kernels as stand-alone operators (include/gf_hip.h; tests/test_smp_gru_ops_gpu.py) ----
+namespace {
+
+// H, nV and the largest accepted rounds of a stand-alone call
+gf_status check_shape(gf_ctx *ctx, const char *who, int H, int nV, int rounds) {
+    if (H < 1 || H > gf::kGruMaxChanels) return gf::fail(ctx, GF_ERR_INVALID, "%s: %d channels (1 .. %d)", who, H, gf::kGruMaxChanels);
+    if (nV < 1 || rounds < 0 || rounds > 65536) return gf::fail(ctx, GF_ERR_INVALID, "%s: %d vertices, %d rounds", who, nV, rounds);
+    return GF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+gf_status gf_smp_gru_cell_fwd_ex_f32(gf_ctx *ctx, int aggregate, int H, int nV, int rounds, const float *M6, const float *hprev, const float *Tprev,
+                                     const long long *ptr, const int *idx, float *h, float *n, float *z, float *r, float *c, float *A, float *T,
+                                     float *Tt) {
+    static const char *who = "gf_smp_gru_cell_fwd_ex_f32";
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    gf_status st = check_shape(ctx, who, H, nV, rounds);
+    if (st != GF_OK) return st;
+    if (aggregate < 0 || aggregate > 2) return gf::fail(ctx, GF_ERR_INVALID, "%s: aggregate = %d (0: sum, 1: pairs, 2: given)", who, aggregate);
+    if (!M6 || !hprev || !h || !n || !z || !r || !c) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
+    if (aggregate != 2 && (!ptr || !idx)) return gf::fail(ctx, GF_ERR_INVALID, "%s: the sum and the pair form need ptr and idx", who);
+    if (aggregate == 1 && (!Tprev || !A || !T || !Tt)) return gf::fail(ctx, GF_ERR_INVALID, "%s: the pair form needs Tprev, A, T and Tt", who);
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (aggregate != 2) st = gf::smp_neighbourhood_check_list(ctx, who, "ptr", ptr, idx, nV, nV);
+    if (st != GF_OK) return st;
+    const gf::Shape sh(H, nV);
+    if (aggregate == 2) return gf::cell_fwd_launch<false, true>(ctx, sh, rounds, M6, hprev, Tprev, ptr, idx, h, n, z, r, c, A, T, Tt);
+    return gf::with_aggregate(aggregate == 1, [&](auto pr) -> gf_status {
+        return gf::cell_fwd_launch<decltype(pr)::value>(ctx, sh, rounds, M6, hprev, Tprev, ptr, idx, h, n, z, r, c, A, T, Tt);
+    });
+}
+
+gf_status gf_smp_gru_cell_bwd_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, int rounds, const float *M6, const float *hprev, const float *dh,
+                                     const float *z, const float *r, const float *c, const float *A, const float *Tt, float *dzp, float *drp,
+                                     float *dcp, float *q, float *dn, float *gTt, float *sA, float *direct) {
+    static const char *who = "gf_smp_gru_cell_bwd_ex_f32";
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    const gf_status st = check_shape(ctx, who, H, nV, rounds);
+    if (st != GF_OK) return st;
+    if (!M6 || !hprev || !dh || !z || !r || !c || !dzp || !drp || !dcp || !q || !dn || !direct)
+        return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
+    if (pairs && (!A || !Tt || !gTt || !sA)) return gf::fail(ctx, GF_ERR_INVALID, "%s: the pair form needs A, Tt, gTt and sA", who);
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const gf::Shape sh(H, nV);
+    return gf::with_aggregate(pairs != 0, [&](auto pr) -> gf_status {
+        return gf::cell_bwd_launch<decltype(pr)::value>(ctx, sh, rounds, M6, hprev, dh, z, r, c, A, Tt, dzp, drp, dcp, q, dn, gTt, sA, direct);
+    });
+}
+
+gf_status gf_smp_gru_readout_fwd_ex_f32(gf_ctx *ctx, int H, int nV, int nMol, int rounds, const float *M2, const float *U, const float *hL,
+                                        const int *mol_ptr, const float *target, float *s, float *t, float *g, float *yhat, float *loss,
+                                        float *dy) {
+    static const char *who = "gf_smp_gru_readout_fwd_ex_f32";
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    gf_status st = check_shape(ctx, who, H, nV, rounds);
+    if (st != GF_OK) return st;
+    if (nMol < 1 || !M2 || !U || !hL || !mol_ptr || !s || !t || !g || !yhat || !dy) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = gf::smp_neighbourhood_check_ptr(ctx, who, "mol_ptr", mol_ptr, nMol, nV);
+    if (st != GF_OK) return st;
+    return gf::readout_fwd_launch(ctx, gf::Shape(H, nV), rounds, nMol, M2, U, hL, mol_ptr, target, s, t, g, yhat, loss, dy);
+}
+
+gf_status gf_smp_gru_readout_bwd_ex_f32(gf_ctx *ctx, int H, int nV, int nMol, int rounds, const float *M2, const float *U, const float *s,
+                                        const float *t, const float *g, const float *dy, const int *vmol, float *ds, float *dt, float *dh,
+                                        float *dU) {
+    static const char *who = "gf_smp_gru_readout_bwd_ex_f32";
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    gf_status st = check_shape(ctx, who, H, nV, rounds);
+    if (st != GF_OK) return st;
+    if (nMol < 1 || !M2 || !U || !s || !t || !g || !dy || !vmol || !ds || !dt || !dh || !dU)
+        return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = gf::smp_neighbourhood_check_members(ctx, who, "vmol", vmol, (size_t)nV, nMol);
+    if (st != GF_OK) return st;
+    st = gf::readout_dU_launch(ctx, H, nMol, dy, g, dU);
+    if (st != GF_OK) return st;
+    return gf::readout_bwd_launch(ctx, gf::Shape(H, nV), rounds, M2, U, s, t, g, dy, vmol, ds, dt, dh);
+}
+
+}  // extern "C"

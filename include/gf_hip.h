@@ -679,6 +679,35 @@ gf_status gf_smp_neighbourhood_gather_bwd_ex_f32(gf_ctx *ctx, int pairs, int H, 
                                                  const float *gTt, const float *sA, const float *hprev, const float *Tprev, float *dhprev);
 gf_status gf_smp_neighbourhood_readout_ex_f32(gf_ctx *ctx, int H, int nV, int nMol, const float *hL, const int *mol_ptr, const float *W,
                                               const float *target, float *g, float *yhat, float *loss, float *dy, float *dW);
+/* The gated level's kernels (GRU_GCN_1D, GRU_GCN_2D and GRU_GCN_3D's cell: smp_level_gru.hip) as stand-alone operators through the level's
+ * own launchers, for tests/test_smp_gru_ops_gpu.py.  Device pointers, fp32, asynchronous on the context's stream.  H = 1 .. 64 channels,
+ * nV vertices, lists and rounds as above.  M6 = W_z, U_z, W_r, U_r, W_h, U_h back to back, M2 = W_g, U_g, [H][H] each.
+ *   cell_fwd: aggregate 0: n[v] = sum_u hprev[u] over ptr / idx; 1: the pair form A Tt - sum_u hprev[u] Tprev[u], which also stores
+ *             A [nV][H], Tt [nV] and T[v] = sum_k h[v][k]; 2: n is an INPUT (GRU_GCN_3D), ptr / idx / Tprev / A / T / Tt may be NULL and
+ *             stay untouched.  With hp = hprev[v]: z = sigmoid(W_z n + U_z hp), r = sigmoid(W_r n + U_r hp), c = tanh(W_h n + U_h (r hp)),
+ *             h[v] = (1 - z) hp + z c; h, n, z, r, c [nV][H].
+ *   cell_bwd: from dh and the stored z, r, c: dzp = dh (c - hp) z (1 - z), dcp = dh z (1 - c^2), dq = U_h^T dcp, drp = dq hp r (1 - r),
+ *             q = r hp, dn = W_z^T dzp + W_r^T drp + W_h^T dcp, direct = dh (1 - z) + dq r + U_z^T dzp + U_r^T drp; with pairs also
+ *             gTt[v] = dn[v] Tt[v] and sA[v] = <dn[v], A[v]>.  dh_{l-1} = gf_smp_neighbourhood_gather_bwd_ex_f32 of dn (, gTt, sA) + direct.
+ *   readout_fwd: s = sigmoid(W_g hL[v]), t = tanh(U_g hL[v]) [nV][H]; g[m] = tanh(sum of s t over mol_ptr[m] <= v < mol_ptr[m + 1])
+ *             (an empty molecule: 0), yhat = <U, g>, dy = yhat - target (target NULL: 0), loss = 0.5 dy^2 (NULL: not stored).
+ *   readout_bwd: dU[c] += sum_m dy[m] g[m][c]; with dg = dy[vmol[v]] U (1 - g^2): ds = dg t s (1 - s), dt = dg s (1 - t^2),
+ *             dh[v] = W_g^T ds + U_g^T dt.
+ * GF_ERR_INVALID before anything is launched: H outside 1 .. 64, nV / nMol < 1, rounds < 0, aggregate outside 0 .. 2, a missing operand
+ * of the chosen form, and -- one blocking copy of the tables per call -- a list that does not start at 0 or decreases, a member outside
+ * [0, nV), vmol outside [0, nMol), a mol_ptr that decreases or leaves the nV rows.  The context stays usable after a refusal. */
+gf_status gf_smp_gru_cell_fwd_ex_f32(gf_ctx *ctx, int aggregate, int H, int nV, int rounds, const float *M6, const float *hprev, const float *Tprev,
+                                     const long long *ptr, const int *idx, float *h, float *n, float *z, float *r, float *c, float *A, float *T,
+                                     float *Tt);
+gf_status gf_smp_gru_cell_bwd_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, int rounds, const float *M6, const float *hprev, const float *dh,
+                                     const float *z, const float *r, const float *c, const float *A, const float *Tt, float *dzp, float *drp,
+                                     float *dcp, float *q, float *dn, float *gTt, float *sA, float *direct);
+gf_status gf_smp_gru_readout_fwd_ex_f32(gf_ctx *ctx, int H, int nV, int nMol, int rounds, const float *M2, const float *U, const float *hL,
+                                        const int *mol_ptr, const float *target, float *s, float *t, float *g, float *yhat, float *loss,
+                                        float *dy);
+gf_status gf_smp_gru_readout_bwd_ex_f32(gf_ctx *ctx, int H, int nV, int nMol, int rounds, const float *M2, const float *U, const float *s,
+                                        const float *t, const float *g, const float *dy, const int *vmol, float *ds, float *dt, float *dh,
+                                        float *dU);
 /* The same three kernels on TWO operand sets in one launch each (gf_smp_config.distance_channel: the vertex and the distance channel
  * of a level; blockIdx.y picks the set).  pairs, H, nV, rounds and the lists are shared; a set is the single-channel call's operands, with
  * an operand width FD of its own in fwd.  W2 (fwd, node_bwd) must be NULL in both sets or in neither; dy / vmol / nMol are shared.  The
