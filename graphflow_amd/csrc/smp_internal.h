@@ -1,5 +1,6 @@
-// smp_internal.h -- state of one gf_smp handle and what its translation units share: smp.hip (create / plan, the forward and reverse
-// sweeps, op-by-op levels), smp_prepare.hip (buffer pool, device-built tables, gf_smp_prepare), smp_pad.hip (channel padding, the ver6 / ver7
+// smp_internal.h -- state of one gf_smp handle (gf_smp_batch: what one prepared batch owns; gf_smp: what survives it) and what its translation
+// units share: smp.hip (create / plan, the sweeps, op-by-op levels), smp_prepare.hip (buffer pool, device-built tables, every path of
+// gf_smp_prepare* on one begin_batch / finish_batch skeleton), smp_pad.hip (channel padding, the ver6 / ver7
 // embedding), smp_optim.hip (host-pointer mode, optimisers, checkpoints), smp_fused.hip + smp_level_*.hip (fused levels), smp_model.hip.
 // Which configurations become a handle is smp_config.h's business, the parameter layout smp_prep.h's (gfsmp::Config::level_blocks).
 #ifndef GF_SMP_INTERNAL_H_INCLUDED
@@ -145,52 +146,17 @@ void smp_derive_plan(gf_smp *s, bool allow_embed);
 gf_status smp_switch_plan(gf_smp *s, bool embed);
 constexpr int kPadMaxLevels = 15;   // levels a padded model's layout map holds (gf_smp_create: deeper models compute at nChanels)
 }
-struct gf_smp {
-    gf_ctx *ctx = nullptr;
-    gfsmp::Config cfg;    // what the device computes with: nChanels padded to 32 / 64 / a multiple of 4 (gf_smp_create, round 4)
-    bool bwd_consumed = false;   // an op-by-op level's reverse sweep has overwritten its Q since the last forward
-    gfsmp::Config ucfg;   // the caller's configuration: the layout of parameters, gradients, features and activations at the C ABI
-    float *pad_p = nullptr, *pad_g = nullptr, *pad_feat = nullptr;   // padded copies (cfg.nChanels != ucfg.nChanels)
-    // Round 5, SMP_2D_ver6 (RisiContraction_10) on the fused RisiContraction_18 level: != 0 = the caller's channel count C.  With a symmetric
-    // reduced adjacency every one of the ten "1+1+1" slices is a slice of RisiContraction_18 applied to f_{l-1} or to its per-node
-    // TRANSPOSE (smp_pad.hip: v6_slot), so the device computes an 18-slice model on [f | f^T | 0] channels: channels [C, 2C) of every level's
-    // activations hold the transposed matrices (dup_transposed_channels after each level, fold_transposed_channels in the reverse sweep)
-    int dup_channels = 0;
-    // ... and SMP_2D_ver7 (RisiContraction_50) likewise: 46 of its 50 slices are slices of RisiContraction_18 on f or f^T; the other four
-    // (cases 25, 41, 42, 45: S_bc tr and the three pair marginals weighted by the adjacency's diagonal, which is 1 in a reduced adjacency)
-    // are n_extra = 3 more C x C products on the level's tables -- (S_ab, 1), (S_bc, 1), (S_bc, tr) -- whose weights X_l sit BEHIND the
-    // padded parameter vector ([.. W | X_1 | .. | X_L], three [Cc][Cc] blocks per level) and run as plain fp32 GEMMs on T
-    int n_extra = 0;
-    // what gf_smp_create was asked for (smp_derive_plan re-derives cfg / dup_channels / n_extra from ucfg and these), and whether the handle
-    // currently runs its `_10` / `_50` levels op by op because the prepared batch cannot be embedded (gf_smp_prepare switches per batch)
-    bool req_pad_channels = true, embed_auto_off = false;
-    int req_min_pad = 0;
-    const float *extra_w = nullptr;   // X of the running pass (set by gf_smp_forward / gf_smp_backward)
-    float *extra_g = nullptr;         // ... and its gradient
-    float *rs_inv = nullptr;          // [rows of the largest level][2] (1 / tot, tr / tot): the extra products of an op-by-op level
-    size_t rs_inv_rows = 0;
-    size_t pad_feat_n = 0;
-    gfsmp::BatchLayout lay;
+// The state of ONE prepared batch.  The rule: from the pool (upload_bytes) or derived from the batch => here; release() resets all of it, with
+// one assignment of a value-initialised gf_smp_batch, so no pointer outlives the block behind it and no prepare path nulls a field by hand.
+// What survives a batch is gf_smp's: configuration and plan, the pool, the upload stream, `lay` (its host vectors are reused for their
+// capacity), everything from hipMalloc (rs_inv, pad_*, own_p / own_g, adam_*, mask_stage), the per-pass flags (the passes' own business).
+struct gf_smp_batch {
     bool prepared = false, forwarded = false;
     // context workspace this batch needs.  gf_smp_prepare only RECORDS it (prepare may run on a loader thread while another
     // handle's step uses the context's workspace on the compute thread); gf_smp_forward / gf_smp_backward grow the workspace, on
     // the thread that owns the context's stream
     size_t ws_need = 0;
-    bool has_targets = false;  // the last gf_smp_forward was given targets: only then does dy hold a loss gradient
-    // data-parallel reverse sweep (the context has a communicator, gf_dist.hip): the gradient segment of a level is
-    // all-reduced on the communicator's stream as soon as it is complete, beside the rest of the sweep
-    bool drop_on = false;      // RisiContraction_18_dropout instead of RisiContraction_18 (SMP_sigma_pairgraphs)
-    float drop_scale = 1.f;    // test mode: nKept / 18 on every slice
-    unsigned *mask_stage = nullptr;   // page-locked staging of the slice masks, [levels][vertices] in node order (gf_smp_dropout_masks)
-    size_t mask_stage_n = 0;
-    hipEvent_t ev_mask = nullptr;     // the last upload out of mask_stage
-    int grad_allreduce = 1;
-    float *dp_grads = nullptr;           // gradient buffer of the running gf_smp_backward, null when not data-parallel
-    hipEvent_t ev_grad = nullptr, ev_comm = nullptr;
-    bool dp_join_pending = false;        // ev_comm was recorded behind the last sweep's all-reduces and nobody has waited for it on the host yet
-    int fused = 1;  // use the fused level path where supported (gf_smp_set_fused)
-    int bwd_gather = 0;  // fused levels: evaluate dP inside the consumer gather instead of materialising it (GF_SMP_BWD_GATHER)
-    // device buffers (owned)
+    // device buffers (from the pool)
     struct DevLevel {
         int *node_s = nullptr;
         long long *node_row = nullptr, *node_p = nullptr, *node_pair = nullptr;
@@ -342,6 +308,48 @@ struct gf_smp {
     float *colpart = nullptr;  // partial column sums for bias gradients, [colpart_rows][C]
     size_t colpart_rows = 0;
     int *top_node_mol = nullptr, *mol_ptr = nullptr, *mol_nodes = nullptr;
+    float *own_t = nullptr, *own_y = nullptr, *own_loss = nullptr, *own_feat = nullptr;  // per-batch, freed by release()
+};
+struct gf_smp : gf_smp_batch {
+    gf_ctx *ctx = nullptr;
+    gfsmp::Config cfg;    // what the device computes with: nChanels padded to 32 / 64 / a multiple of 4 (gf_smp_create, round 4)
+    bool bwd_consumed = false;   // an op-by-op level's reverse sweep has overwritten its Q since the last forward
+    gfsmp::Config ucfg;   // the caller's configuration: the layout of parameters, gradients, features and activations at the C ABI
+    float *pad_p = nullptr, *pad_g = nullptr, *pad_feat = nullptr;   // padded copies (cfg.nChanels != ucfg.nChanels)
+    // Round 5, SMP_2D_ver6 (RisiContraction_10) on the fused RisiContraction_18 level: != 0 = the caller's channel count C.  With a symmetric
+    // reduced adjacency every one of the ten "1+1+1" slices is a slice of RisiContraction_18 applied to f_{l-1} or to its per-node
+    // TRANSPOSE (smp_pad.hip: v6_slot), so the device computes an 18-slice model on [f | f^T | 0] channels: channels [C, 2C) of every level's
+    // activations hold the transposed matrices (dup_transposed_channels after each level, fold_transposed_channels in the reverse sweep)
+    int dup_channels = 0;
+    // ... and SMP_2D_ver7 (RisiContraction_50) likewise: 46 of its 50 slices are slices of RisiContraction_18 on f or f^T; the other four
+    // (cases 25, 41, 42, 45: S_bc tr and the three pair marginals weighted by the adjacency's diagonal, which is 1 in a reduced adjacency)
+    // are n_extra = 3 more C x C products on the level's tables -- (S_ab, 1), (S_bc, 1), (S_bc, tr) -- whose weights X_l sit BEHIND the
+    // padded parameter vector ([.. W | X_1 | .. | X_L], three [Cc][Cc] blocks per level) and run as plain fp32 GEMMs on T
+    int n_extra = 0;
+    // what gf_smp_create was asked for (smp_derive_plan re-derives cfg / dup_channels / n_extra from ucfg and these), and whether the handle
+    // currently runs its `_10` / `_50` levels op by op because the prepared batch cannot be embedded (gf_smp_prepare switches per batch)
+    bool req_pad_channels = true, embed_auto_off = false;
+    int req_min_pad = 0;
+    const float *extra_w = nullptr;   // X of the running pass (set by gf_smp_forward / gf_smp_backward)
+    float *extra_g = nullptr;         // ... and its gradient
+    float *rs_inv = nullptr;          // [rows of the largest level][2] (1 / tot, tr / tot): the extra products of an op-by-op level
+    size_t rs_inv_rows = 0;
+    size_t pad_feat_n = 0;
+    gfsmp::BatchLayout lay;
+    bool has_targets = false;  // the last gf_smp_forward was given targets: only then does dy hold a loss gradient
+    // data-parallel reverse sweep (the context has a communicator, gf_dist.hip): the gradient segment of a level is
+    // all-reduced on the communicator's stream as soon as it is complete, beside the rest of the sweep
+    bool drop_on = false;      // RisiContraction_18_dropout instead of RisiContraction_18 (SMP_sigma_pairgraphs)
+    float drop_scale = 1.f;    // test mode: nKept / 18 on every slice
+    unsigned *mask_stage = nullptr;   // page-locked staging of the slice masks, [levels][vertices] in node order (gf_smp_dropout_masks)
+    size_t mask_stage_n = 0;
+    hipEvent_t ev_mask = nullptr;     // the last upload out of mask_stage
+    int grad_allreduce = 1;
+    float *dp_grads = nullptr;           // gradient buffer of the running gf_smp_backward, null when not data-parallel
+    hipEvent_t ev_grad = nullptr, ev_comm = nullptr;
+    bool dp_join_pending = false;        // ev_comm was recorded behind the last sweep's all-reduces and nobody has waited for it on the host yet
+    int fused = 1;  // use the fused level path where supported (gf_smp_set_fused)
+    int bwd_gather = 0;  // fused levels: evaluate dP inside the consumer gather instead of materialising it (GF_SMP_BWD_GATHER)
     // device buffers of the current batch come from a pool that survives gf_smp_prepare: a training loop prepares a new
     // batch every step, and hipMalloc of the level buffers (GBs) cost 4x the host graph preparation itself
     struct Block {
@@ -360,7 +368,6 @@ struct gf_smp {
     float *adam_m = nullptr, *adam_v = nullptr;
     // handle-owned model (host-pointer mode of the driver): parameters and their gradient, [param_count] each
     float *own_p = nullptr, *own_g = nullptr;
-    float *own_t = nullptr, *own_y = nullptr, *own_loss = nullptr, *own_feat = nullptr;  // per-batch, freed by release()
     unsigned long long adam_n = 0;  // parameter elements processed so far (the reference's running beta powers)
 };
 
@@ -442,7 +449,6 @@ gf_status smp_unrestricted_backward_level(gf_smp *s, int l, const float *K, cons
                                           bool rows_too, gf_status (*wgrad_done)(gf_smp *, int));
 // NeuralFingerprint, GCN_1D, GCN_2D (cfg.neighbourhood = 1, 2, 3; smp_level_neighbourhood.hip): the whole sweeps of such a handle -- level 0
 // and the read-out are softmax / plain sums, not the other kinds' -- and its gf_smp_prepare.  params / grads: W1_0; (W1_l, W2_l); W.
-gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature);
 gf_status smp_neighbourhood_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature);
 gf_status smp_neighbourhood_backward(gf_smp *s, const float *params, float *grads, int accumulate);
 // ... and the launchers of its three level kernels on raw operands (the arguments of nbh_level_fwd / nbh_node_bwd / nbh_gather_bwd; pairs:
@@ -468,7 +474,6 @@ gf_status smp_neighbourhood_check_members(gf_ctx *ctx, const char *who, const ch
 // GCN_1D_Distance, GCN_2D_Distance, GCN_3D_Distance (cfg.distance_channel; smp_level_distance.hip): the sweeps of a distance handle, its
 // gf_smp_prepare_distance (smp_prepare.hip) and the sort that builds the distance channel's input rows on the handle's upload stream.
 // params / grads: per level W1^v, W1^d (, W2^v, W2^d); W [2 H].
-gf_status smp_distance_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature, const double *distance);
 gf_status smp_distance_rows_launch(gf_ctx *ctx, hipStream_t stream, int nV, int M, const double *dist, const long long *mat_off, const int *mol_ptr,
                                    const int *vmol, float *xd);
 gf_status smp_distance_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature);
@@ -482,8 +487,6 @@ gf_status smp_readout_forward(gf_smp *s, const float *W, const float *targets, f
 gf_status smp_readout_dW(gf_smp *s, const float *W, float *dW);
 // ... and the check of a 32-bit prefix-sum table (mol_ptr, graph_ptr) of a stand-alone call: from 0, never decreasing, within `bound` rows
 gf_status smp_neighbourhood_check_ptr(gf_ctx *ctx, const char *who, const char *what, const int *ptr, int n, int bound);
-gf_status smp_pairs_prepare(gf_smp *s, int nPairs, const int *nVertices1, const int *adj1, const double *feature1, const int *nVertices2,
-                            const int *adj2, const double *feature2);
 // GRU_GCN_1D, GRU_GCN_2D (cfg.neighbourhood = 4, 5; smp_level_gru.hip): the sweeps of a gated handle on the same lists and buffers.
 // params / grads: W; W_z, U_z, W_r, U_r, W_h, U_h, W_g, U_g (shared by the levels: their gradients accumulate across them); U.
 gf_status smp_gru_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature);
@@ -497,11 +500,8 @@ gf_status smp_third_pool_bwd_launch(gf_ctx *ctx, int H, int nV, const long long 
                                     const float *hprev, const int *sel, const float *dn, float *dhprev);
 // LCNN, GCN_MW (cfg.matrix_form = 1, 2; smp_level_rowlist.hip): the whole sweeps of such a handle, and its gf_smp_prepare (smp_prepare.hip).
 // params / grads: GCN_MW W_0; W_l; W.  LCNN F1, b1, F2, b2, Dm, W.
-gf_status smp_matrix_form_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature);
 gf_status smp_matrix_form_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature);
 gf_status smp_matrix_form_backward(gf_smp *s, const float *params, float *grads, int accumulate);
-// smp_theta_prepare (smp_prepare.hip): gf_smp_prepare of a first-order handle -- the th_* tables, none of the other kinds' buffers.
-gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature);
 // the first-order read-out of level l (smp_field_level.hip): sh[n] = column sums over the node's s rows (ShrinkMatrix), vf = LeakyReLU(sh);
 // and its reverse, df_l[n][i][:] (+)= dvec[n][:] at every row i of the node, dvec = one gradient vector per node
 gf_status smp_theta_readout(gf_smp *s, int l, float *sh, float *vf);

@@ -96,9 +96,7 @@ void release(gf_smp *s) {
         keep.push_back(b);
     }
     s->pool.swap(keep);
-    s->lv.clear();
-    s->own_t = s->own_y = s->own_loss = s->own_feat = nullptr;
-    s->prepared = s->forwarded = false;
+    static_cast<gf_smp_batch &>(*s) = gf_smp_batch();   // every pointer into those blocks and everything derived from the batch
 }
 
 void release_pool(gf_smp *s) {
@@ -537,6 +535,26 @@ void ensure_upload_stream(gf_smp *s) {
 }
 hipStream_t upload_stream(const gf_smp *s) { return s->upload ? s->upload : s->ctx->stream; }
 
+// The two ends of every prepare path.  A path refuses what it can BEFORE begin_batch (the previous batch then stays usable); between the two
+// it lays the batch out on the host, assigns s->lv and takes its buffers through a Taker; a refusal there leaves the handle unprepared.
+void begin_batch(gf_smp *s) {
+    ensure_upload_stream(s);
+    release(s);
+}
+// the tables are on the device when this returns (the host vectors are reused by the next batch); the context's stream is NOT waited for:
+// it may be running another handle's step.  ws_need: grown by forward / backward on the compute thread (smp_internal.h)
+gf_status finish_batch(gf_smp *s, size_t ws_need) {
+    s->ws_need = ws_need;
+    GF_HIP_TRY(s->ctx, hipStreamSynchronize(upload_stream(s)));
+    s->prepared = true;
+    return GF_OK;
+}
+// molecule m above the configuration's max_nVertices (the paths whose buffers or parameters are sized by it), in the entry point's name
+gf_status check_max_vertices(const gf_smp *s, const char *who, int m, int V) {
+    if (V <= s->cfg.max_nVertices) return GF_OK;
+    return fail(s->ctx, GF_ERR_INVALID, "%s: molecule %d has %d vertices, the model was created with max_nVertices = %d", who, m, V, s->cfg.max_nVertices);
+}
+
 // rows-sized level tables on the device (GF_PREP_DEVICE_TABLES=0: on the host, as rounds 1-2 built them; the parity tests hold
 // the two against each other bit for bit)
 void choose_table_builder(gf_smp *s, int nMol, const int *nVertices) {
@@ -582,7 +600,6 @@ gf_status alloc_level_topology(Taker &t, Level &h, DevLevel &d, int l) {
     gf_smp *s = t.s;
     const bool dev = s->lay.device_tables;
     t.put(&d.node_p, h.node_p);
-    d.max_tot = d.max_tr = 0.f;
     t.table(&d.adj, h.adj, (size_t)h.rows);
     t.table(&d.rsum, h.rsum, (size_t)h.pairs);
     t.table(&d.node_scale, h.rowscale, (size_t)h.nNodes * 2);
@@ -712,7 +729,6 @@ gf_status build_device_tables(gf_smp *s, bool coulomb) {
     t.put(&s->mol_nv, B.mol_nv);
     t.put(&s->mol_adj, B.mol_adj);
     t.put(&s->mol_adj_off, B.mol_adj_off);
-    s->mol_coul = nullptr;
     if (coulomb) t.put(&s->mol_coul, B.mol_coul);
     t.alloc(&s->tab_stats, (size_t)4 * (L + 1));  // per level: max |tot|, max |tr| (float bits), rows with data (64 bit)
     if (t.st != GF_OK) return t.st;
@@ -791,7 +807,6 @@ gf_status alloc_readout(gf_smp *s, int nMol) {
     const gfsmp::LevelLayout &top = B.level[L];
     Taker t = {s};
     t.put(&s->x, B.x);
-    s->wbound = nullptr;
     // scratch words of the fused levels' weight gradients (channel maxima, exact column bounds; a 64-channel level keeps only its maxima);
     // 128 channels: the plain 18-slice model's four sub-block launches
     if (!s->cfg.per_size() && s->cfg.square() && (smp_panel_channels(C) || (C == 128 && s->cfg.nContractions == 18 && smp_c128_switch())))
@@ -802,7 +817,6 @@ gf_status alloc_readout(gf_smp *s, int nMol) {
     t.alloc(&s->g, (size_t)nMol * (s->cfg.physics ? feature_width(s->cfg) : (size_t)C));
     t.alloc(&s->yhat, (size_t)nMol);
     t.alloc(&s->dy, (size_t)nMol);
-    s->cls_scores = s->cls_prob = s->cls_dz = s->cls_dg = nullptr;
     if (s->cfg.nClass) {   // classifier read-out (smp_readout_classes.hip)
         t.alloc(&s->cls_scores, (size_t)nMol * s->cfg.nClass);
         t.alloc(&s->cls_prob, (size_t)nMol * s->cfg.nClass);
@@ -823,358 +837,356 @@ gf_status alloc_readout(gf_smp *s, int nMol) {
     return t.st;
 }
 
-}  // namespace
+// ---- the field levels (SMP_theta, SMP_1D*, SMP_2D / ver4 / ver5, Unrestricted_*): the host builds the batch and the level's own (node, child)
+// tables (gfsmp::build_batch_theta); the device gets those, the activations and the family's buffers -- none of the 18-slice or gamma ones ----
+// every level: node bookkeeping, the activations and their gradient; a tower reads every level out
+void alloc_field_state(Taker &t, Level &h, DevLevel &d, int l) {
+    const size_t Cl = t.s->cfg.level_channels(l), nodes = h.nNodes;
+    t.put(&d.node_s, h.node_s);
+    t.put(&d.node_row, h.node_row);
+    t.put(&d.node_mol, h.node_mol);
+    t.alloc(&d.f, (size_t)h.rows * Cl);
+    t.alloc(&d.df, (size_t)h.rows * Cl);
+    if (!t.s->cfg.physics) return;
+    t.alloc(&d.sh, nodes * Cl);   // per-node sums, their activation and gradient, the vertex -> node map
+    t.alloc(&d.vf, nodes * Cl);
+    t.alloc(&d.dshl, nodes * Cl);
+    t.put(&d.node_of_vertex, t.s->lay.node_of_vertex[l]);
+}
+// levels >= 1, every family: the (node, child) tables of smp_prep.h
+void alloc_field_tables(Taker &t, Level &h, DevLevel &d) {
+    t.put(&d.th_child_ptr, h.th_child_ptr);
+    t.put(&d.th_src_row, h.th_src_row);
+    t.put(&d.th_src_s, h.th_src_s);
+    t.put(&d.th_pi_off, h.th_pi_off);
+    t.put(&d.th_pi, h.th_pi);
+    t.put(&d.th_cons_ptr, h.th_cons_ptr);
+    t.put(&d.th_cons_row, h.th_cons_row);
+    t.put(&d.th_cons_s, h.th_cons_s);
+    t.put(&d.th_cons_node, h.th_cons_node);
+    t.put(&d.th_inv_off, h.th_inv_off);
+    t.put(&d.th_inv, h.th_inv);
+    t.put(&d.th_bucket, h.th_bucket);
+    t.put(&d.th_weight, h.th_weight);
+}
+// SMP_theta (smp_level_theta.hip): the reverse sweep's per-node sums, A, B, G / dG and the weight views
+void alloc_theta_level(Taker &t, Level &h, DevLevel &d, int l) {
+    const size_t Cl = t.s->cfg.level_channels(l), Cp = t.s->cfg.level_channels(l - 1), nodes = h.nNodes;
+    t.alloc(&d.th_node, nodes * 3 * Cl);
+    t.alloc(&d.th_A, (size_t)h.rows * Cl);
+    t.alloc(&d.th_B, nodes * Cl);
+    t.alloc(&d.Q, (size_t)t.s->lay.level[l - 1].rows * 2 * Cl);   // G, then dG: [rows of level l - 1][2 Cc]
+    t.alloc(&d.Wst, 4 * Cp * Cl);                                 // the weight views [Cp][2 Cc] and [2 Cc][Cp]
+    t.alloc(&d.dWst, 2 * Cp * Cl);
+}
+// SMP_1D* (smp_level_1d.hip): A = S and B = sumS are Cp wide; a matrix, and so G / dG and the weight views, only in ver3
+void alloc_1d_level(Taker &t, Level &h, DevLevel &d, int l) {
+    const size_t Cl = t.s->cfg.level_channels(l), Cp = t.s->cfg.level_channels(l - 1), nodes = h.nNodes;
+    t.alloc(&d.th_node, nodes * 3 * Cl);
+    t.alloc(&d.th_A, (size_t)h.rows * Cp);
+    t.alloc(&d.th_B, nodes * Cp);
+    if (t.s->cfg.first_order != 4) return;
+    t.alloc(&d.Q, (size_t)t.s->lay.level[l - 1].rows * 2 * Cp);   // [rows of level l - 1][2 Cp]
+    t.alloc(&d.Wst, 4 * Cp * Cp);                                 // [K_eye | K_one] as [Cp][2 Cp], and its transpose
+    t.alloc(&d.dWst, 2 * Cp * Cp);
+}
+// SMP_2D / ver4 (smp_level_2d.hip): S [rows][Cp], col and the reverse sweep's column partials per (node, column); SMP_2D_ver5
+// (smp_level_2d_ver5.hip) beside them: the tables of its projections, u, dO, dE and the partials of dK_l
+void alloc_steerable_level(Taker &t, Level &h, DevLevel &d, int l) {
+    const size_t Cl = t.s->cfg.level_channels(l), Cp = t.s->cfg.level_channels(l - 1);
+    const size_t cols = h.nNodes ? (size_t)(h.node_pair.back() + h.node_s.back()) : 0;   // sum s
+    t.put(&d.node_pair, h.node_pair);
+    t.put(&d.adj, h.adj);
+    t.alloc(&d.th_A, (size_t)h.rows * Cp);
+    t.alloc(&d.th_B, cols * Cp);
+    t.alloc(&d.th_node, cols * (Cl + 3 * Cp));
+    t.alloc(&d.part2d, h.buckets.size() * 16 * (Cl + 3 * Cp));   // [buckets][kSplit2d row chunks][Cc + 3 Cp]
+    if (t.s->cfg.steerable_2d != 5) return;
+    t.alloc(&d.v5_row_cs, (size_t)h.rows);
+    t.alloc(&d.v5_col_s, cols);
+    t.alloc(&d.v5_u, cols * Cp);
+    t.alloc(&d.v5_dO, cols * Cp);
+    t.alloc(&d.Q, (size_t)h.rows * Cp);
+    t.alloc(&d.v5_dKpart, smp_2d_ver5_wgrad_chunks((long long)h.rows, (long long)cols) * Cp * Cp);
+}
+// Unrestricted_* (smp_level_unrestricted.hip): S and dS [rows][Cp], the chunk partials of the per-size entries; form 3: adj, columns
+void alloc_unrestricted_level(Taker &t, Level &h, DevLevel &d, int l) {
+    const size_t Cp = t.s->cfg.level_channels(l - 1);
+    t.alloc(&d.th_A, (size_t)h.rows * Cp);
+    t.alloc(&d.Q, (size_t)h.rows * Cp);
+    t.put(&d.un_part_off, h.un_part_off);
+    t.alloc(&d.part2d, (size_t)h.un_part_off.back());
+    if (t.s->cfg.unrestricted != 3) return;
+    t.put(&d.node_pair, h.node_pair);
+    t.put(&d.adj, h.adj);
+    t.alloc(&d.th_node, (h.nNodes ? (size_t)(h.node_pair.back() + h.node_s.back()) : 0) * 2 * Cp);
+}
 
-// gf_smp_prepare of a first-order handle (SMP_theta, SMP_1D*) or a steerable second-order one (SMP_2D, SMP_2D_ver4): the host builds the batch and the level's own (node, child) tables
-// (gfsmp::build_batch_theta); the device gets those, the activations, A / B and G -- none of the 18-slice or gamma buffers.
 gf_status smp_theta_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature) {
-    gf_ctx *ctx = s->ctx;
     const gfsmp::Config &cfg = s->cfg;
-    for (int m = 0; m < nMol; ++m)
-        if (nVertices[m] > cfg.max_nVertices)
-            return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare: molecule %d has %d vertices, the model was created with max_nVertices = %d", m,
-                        nVertices[m], cfg.max_nVertices);
-    ensure_upload_stream(s);
-    release(s);
-    s->tab_stats = nullptr;
-    s->h_tab_stats.clear();
-    s->h_covered.clear();
+    gf_status st = GF_OK;
+    for (int m = 0; m < nMol && st == GF_OK; ++m) st = check_max_vertices(s, "gf_smp_prepare", m, nVertices[m]);
+    if (st != GF_OK) return st;
+    begin_batch(s);
     gfsmp::build_batch_theta(cfg, nMol, nVertices, adj, feature, &s->lay);
     const int L = cfg.nLevels;
     for (int l = 0; l <= L; ++l)
         if (s->lay.level[l].rows > 0x7fffffffll || (!s->lay.level[l].buckets.empty() && s->lay.level[l].buckets.back().s > 32767))
-            return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare: level %d is beyond the level's int16 positions / 2^31 rows", l);
-    s->lv.assign(L + 1, gf_smp::DevLevel());
+            return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare: level %d is beyond the level's int16 positions / 2^31 rows", l);
+    s->lv.assign(L + 1, DevLevel());
+    const auto family = cfg.unrestricted ? alloc_unrestricted_level : cfg.steerable_2d ? alloc_steerable_level
+                        : cfg.first_order >= 2 ? alloc_1d_level : alloc_theta_level;
     Taker t = {s};
     for (int l = 0; l <= L; ++l) {
-        Level &h = s->lay.level[l];
-        DevLevel &d = s->lv[l];
-        const size_t Cl = cfg.level_channels(l), nodes = h.nNodes;
-        t.put(&d.node_s, h.node_s);
-        t.put(&d.node_row, h.node_row);
-        t.put(&d.node_mol, h.node_mol);
-        t.alloc(&d.f, (size_t)h.rows * Cl);
-        t.alloc(&d.df, (size_t)h.rows * Cl);
-        if (cfg.physics) {   // every level is read out: per-node sums, their activation and gradient, the vertex -> node map
-            t.alloc(&d.sh, nodes * Cl);
-            t.alloc(&d.vf, nodes * Cl);
-            t.alloc(&d.dshl, nodes * Cl);
-            t.put(&d.node_of_vertex, s->lay.node_of_vertex[l]);
-        }
+        alloc_field_state(t, s->lay.level[l], s->lv[l], l);
         if (l == 0) continue;
-        const size_t Cp = cfg.level_channels(l - 1);
-        t.put(&d.th_child_ptr, h.th_child_ptr);
-        t.put(&d.th_src_row, h.th_src_row);
-        t.put(&d.th_src_s, h.th_src_s);
-        t.put(&d.th_pi_off, h.th_pi_off);
-        t.put(&d.th_pi, h.th_pi);
-        t.put(&d.th_cons_ptr, h.th_cons_ptr);
-        t.put(&d.th_cons_row, h.th_cons_row);
-        t.put(&d.th_cons_s, h.th_cons_s);
-        t.put(&d.th_cons_node, h.th_cons_node);
-        t.put(&d.th_inv_off, h.th_inv_off);
-        t.put(&d.th_inv, h.th_inv);
-        t.put(&d.th_bucket, h.th_bucket);
-        t.put(&d.th_weight, h.th_weight);
-        if (cfg.unrestricted) {   // (smp_level_unrestricted.hip) S and dS [rows][Cp], the chunk partials of the per-size entries; form 3: adj, columns
-            t.alloc(&d.th_A, (size_t)h.rows * Cp);
-            t.alloc(&d.Q, (size_t)h.rows * Cp);
-            t.put(&d.un_part_off, h.un_part_off);
-            t.alloc(&d.part2d, (size_t)h.un_part_off.back());
-            if (cfg.unrestricted == 3) {
-                t.put(&d.node_pair, h.node_pair);
-                t.put(&d.adj, h.adj);
-                t.alloc(&d.th_node, (nodes ? (size_t)(h.node_pair.back() + h.node_s.back()) : 0) * 2 * Cp);
-            }
-            continue;
-        }
-        if (cfg.steerable_2d) {   // SMP_2D / ver4 (smp_level_2d.hip): S [rows][Cp], col and the reverse sweep's column partials per (node, column)
-            const size_t cols = nodes ? (size_t)(h.node_pair.back() + h.node_s.back()) : 0;   // sum s
-            t.put(&d.node_pair, h.node_pair);
-            t.put(&d.adj, h.adj);
-            t.alloc(&d.th_A, (size_t)h.rows * Cp);
-            t.alloc(&d.th_B, cols * Cp);
-            t.alloc(&d.th_node, cols * (Cl + 3 * Cp));
-            t.alloc(&d.part2d, h.buckets.size() * 16 * (Cl + 3 * Cp));   // [buckets][kSplit2d row chunks][Cc + 3 Cp]
-            if (cfg.steerable_2d == 5) {   // SMP_2D_ver5 (smp_level_2d_ver5.hip): the tables of its projections, u, dO, dE and the partials of dK_l
-                t.alloc(&d.v5_row_cs, (size_t)h.rows);
-                t.alloc(&d.v5_col_s, cols);
-                t.alloc(&d.v5_u, cols * Cp);
-                t.alloc(&d.v5_dO, cols * Cp);
-                t.alloc(&d.Q, (size_t)h.rows * Cp);
-                t.alloc(&d.v5_dKpart, smp_2d_ver5_wgrad_chunks((long long)h.rows, (long long)cols) * Cp * Cp);
-            }
-            continue;
-        }
-        t.alloc(&d.th_node, nodes * 3 * Cl);
-        if (cfg.first_order >= 2) {   // SMP_1D*: A = S and B = sumS are Cp wide; a matrix, and so G / dG and the weight views, only in ver3
-            t.alloc(&d.th_A, (size_t)h.rows * Cp);
-            t.alloc(&d.th_B, nodes * Cp);
-            if (cfg.first_order == 4) {
-                t.alloc(&d.Q, (size_t)s->lay.level[l - 1].rows * 2 * Cp);   // [rows of level l - 1][2 Cp]
-                t.alloc(&d.Wst, 4 * Cp * Cp);                               // [K_eye | K_one] as [Cp][2 Cp], and its transpose
-                t.alloc(&d.dWst, 2 * Cp * Cp);
-            }
-            continue;
-        }
-        t.alloc(&d.th_A, (size_t)h.rows * Cl);
-        t.alloc(&d.th_B, nodes * Cl);
-        t.alloc(&d.Q, (size_t)s->lay.level[l - 1].rows * 2 * Cl);   // G, then dG: [rows of level l - 1][2 Cc]
-        t.alloc(&d.Wst, 4 * Cp * Cl);                               // the weight views [Cp][2 Cc] and [2 Cc][Cp]
-        t.alloc(&d.dWst, 2 * Cp * Cl);
+        alloc_field_tables(t, s->lay.level[l], s->lv[l]);
+        family(t, s->lay.level[l], s->lv[l], l);
     }
     if (t.st != GF_OK) return t.st;
-    s->P = nullptr;
-    s->P_count = 0;
-    gf_status st = alloc_readout(s, nMol);
-    if (st != GF_OK) return st;
-    s->ws_need = 1 << 20;   // (the GEMMs grow the context's workspace for their split-K partials themselves)
-    GF_HIP_TRY(ctx, hipStreamSynchronize(upload_stream(s)));
-    s->prepared = true;
-    return GF_OK;
+    st = alloc_readout(s, nMol);
+    return st != GF_OK ? st : finish_batch(s, 1 << 20);   // (the GEMMs grow the context's workspace for their split-K partials themselves)
 }
 
-// gf_smp_prepare of a neighbourhood handle (NeuralFingerprint, GCN_1D, GCN_2D; smp_level_neighbourhood.hip): the host builds hop distances,
-// the shell-sum features and one neighbour list (with its transpose) per distinct radius (gfsmp::build_batch_neighbourhood); the device gets
-// those and one [vertices][H] buffer per level and quantity -- none of the field, selection or reduced-adjacency tables.
-// A distance handle (cfg.distance_channel; `distance` = the molecules' V x V matrices of doubles back to back) gets the same buffers a second
-// time for its distance channel (gf_smp::lvd, the lists shared) and that channel's input rows, sorted on the device (smp_level_distance.hip).
-static gf_status neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature, const double *distance) {
-    gf_ctx *ctx = s->ctx;
-    const gfsmp::Config &cfg = s->cfg;
-    const char *who = distance ? "gf_smp_prepare_distance" : "gf_smp_prepare";
-    size_t dist_count = 0;
+// ---- the neighbourhood levels (NeuralFingerprint, GCN_*, GRU_GCN_*; smp_level_neighbourhood.hip): the host builds hop distances, the
+// shell-sum features and one neighbour list (with its transpose) per distinct radius (gfsmp::build_batch_neighbourhood); the device gets those
+// and one [vertices][H] buffer per level and quantity -- none of the field, selection or reduced-adjacency tables.  A distance handle
+// (cfg.distance_channel; `distance` = the molecules' V x V matrices of doubles back to back) gets the same buffers a second time for its
+// distance channel (gf_smp::lvd, the lists shared) and that channel's input rows, sorted on the device (smp_level_distance.hip) ----
+struct DevList {
+    long long *ptr = nullptr, *tptr = nullptr;
+    int *idx = nullptr, *tidx = nullptr;
+};
+struct NbhHostTables {   // the host tables this path builds itself: alive until the upload stream has been waited for
+    std::vector<long long> dist_off, gram_off, id_ptr;
+    std::vector<float> gram_adj;
+    std::vector<int> id_idx;
+};
+// what is refused before the previous batch is let go, molecule by molecule; *dist_count: the entries of `distance`
+gf_status check_neighbourhood_batch(const gf_smp *s, const char *who, int nMol, const int *nVertices, const double *distance, size_t *dist_count) {
     for (int m = 0; m < nMol; ++m) {
-        if (nVertices[m] > cfg.max_nVertices)
-            return fail(ctx, GF_ERR_INVALID, "%s: molecule %d has %d vertices, the model was created with max_nVertices = %d", who, m,
-                        nVertices[m], cfg.max_nVertices);
-        if (distance) {   // (every entry finite, before anything is launched)
-            const size_t n = (size_t)nVertices[m] * (size_t)nVertices[m];
-            for (size_t i = 0; i < n; ++i)
-                if (!std::isfinite(distance[dist_count + i]))
-                    return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare_distance: molecule %d has a distance entry that is not finite (row %zu, column %zu)",
-                                m, i / (size_t)nVertices[m], i % (size_t)nVertices[m]);
-            dist_count += n;
-        }
+        const gf_status st = check_max_vertices(s, who, m, nVertices[m]);
+        if (st != GF_OK) return st;
+        if (!distance) continue;   // (every entry finite, before anything is launched)
+        const size_t n = (size_t)nVertices[m] * (size_t)nVertices[m];
+        for (size_t i = 0; i < n; ++i)
+            if (!std::isfinite(distance[*dist_count + i]))
+                return fail(s->ctx, GF_ERR_INVALID, "gf_smp_prepare_distance: molecule %d has a distance entry that is not finite (row %zu, column %zu)",
+                            m, i / (size_t)nVertices[m], i % (size_t)nVertices[m]);
+        *dist_count += n;
     }
-    ensure_upload_stream(s);
-    release(s);
-    s->tab_stats = nullptr;
-    s->h_tab_stats.clear();
-    s->h_covered.clear();
-    gfsmp::build_batch_neighbourhood(cfg, nMol, nVertices, adj, feature, &s->lay);
-    const gfsmp::BatchLayout &B = s->lay;
-    const int L = cfg.nLevels;
-    const size_t nV = (size_t)B.mol_first_vertex[nMol], H = (size_t)cfg.nChanels;
-    for (const gfsmp::BatchLayout::NeighbourList &nl : B.nb_lists)
-        if (nl.idx.size() > 0x7fffffffull) return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare: a neighbour list beyond 2^31 entries");
-    s->lv.assign(L + 1, gf_smp::DevLevel());
-    Taker t = {s};
-    struct DevList {
-        long long *ptr = nullptr, *tptr = nullptr;
-        int *idx = nullptr, *tidx = nullptr;
-    };
-    std::vector<DevList> lists(B.nb_lists.size());
+    return GF_OK;
+}
+void put_neighbour_lists(Taker &t, std::vector<DevList> &lists) {
+    const gfsmp::BatchLayout &B = t.s->lay;
+    lists.resize(B.nb_lists.size());
     for (size_t k = 0; k < lists.size(); ++k) {
         t.put(&lists[k].ptr, B.nb_lists[k].ptr);
         t.put(&lists[k].idx, B.nb_lists[k].idx);
         t.put(&lists[k].tptr, B.nb_lists[k].tptr);
         t.put(&lists[k].tidx, B.nb_lists[k].tidx);
     }
+}
+// level l of one channel (gf_smp::lv, and lvd of a distance handle) on the lists of the level's radius
+void alloc_neighbourhood_level(Taker &t, DevLevel &d, int l, const std::vector<DevList> &lists, size_t nV) {
+    const gfsmp::Config &cfg = t.s->cfg;
+    const size_t H = (size_t)cfg.nChanels;
     const bool pairs = cfg.neighbourhood == 3 || cfg.neighbourhood == 5;   // RisiLayer2D: A, T, Tt and the three quantities of its closed-form reverse
-    s->lvd.assign(distance ? L + 1 : 0, gf_smp::DevLevel());
-    for (int k = 0; k <= (distance ? 2 * L + 1 : L); ++k) {   // (then the distance channel's levels)
-        const int l = k <= L ? k : k - L - 1;
-        DevLevel &d = k <= L ? s->lv[l] : s->lvd[l];
-        t.alloc(&d.f, nV * H);
-        t.alloc(&d.df, nV * H);
-        if (pairs) t.alloc(&d.nb_T, nV);
-        if (l == 0) continue;
-        const DevList &dl = lists[(size_t)B.nb_list_of_level[l]];
-        d.nb_ptr = dl.ptr, d.nb_idx = dl.idx, d.nb_tptr = dl.tptr, d.nb_tidx = dl.tidx;
-        t.alloc(&d.th_A, nV * H);
-        t.alloc(&d.Q, nV * H);
-        if (cfg.gated())   // the GRU cell's gates and what its weight gradients read (smp_level_gru.hip)
-            for (float **p : {&d.gru_z, &d.gru_r, &d.gru_c, &d.gru_q, &d.gru_dz, &d.gru_dr, &d.gru_dc, &d.gru_direct}) t.alloc(p, nV * H);
-        if (cfg.third_order()) {   // the selection record, the longest list, and form 6's pooled vector (smp_level_third.hip)
-            const auto &lp = B.nb_lists[(size_t)B.nb_list_of_level[l]].ptr;
-            long long longest = 0;
-            for (size_t v = 0; v + 1 < lp.size(); ++v) longest = lp[v + 1] - lp[v] > longest ? lp[v + 1] - lp[v] : longest;
-            d.nb_max_members = (int)longest;
-            t.alloc(&d.nb_sel, nV * H);
-            if (!cfg.gated()) t.alloc(&d.nb_pool, nV * H);
-        }
-        if (pairs) {
-            t.alloc(&d.th_B, nV * H);
-            t.alloc(&d.th_node, nV * H);
-            t.alloc(&d.nb_Tt, nV);
-            t.alloc(&d.nb_sA, nV);
-        }
+    t.alloc(&d.f, nV * H);
+    t.alloc(&d.df, nV * H);
+    if (pairs) t.alloc(&d.nb_T, nV);
+    if (l == 0) return;
+    const size_t k = (size_t)t.s->lay.nb_list_of_level[l];
+    d.nb_ptr = lists[k].ptr, d.nb_idx = lists[k].idx, d.nb_tptr = lists[k].tptr, d.nb_tidx = lists[k].tidx;
+    t.alloc(&d.th_A, nV * H);
+    t.alloc(&d.Q, nV * H);
+    if (cfg.gated())   // the GRU cell's gates and what its weight gradients read (smp_level_gru.hip)
+        for (float **p : {&d.gru_z, &d.gru_r, &d.gru_c, &d.gru_q, &d.gru_dz, &d.gru_dr, &d.gru_dc, &d.gru_direct}) t.alloc(p, nV * H);
+    if (cfg.third_order()) {   // the selection record, the longest list, and form 6's pooled vector (smp_level_third.hip)
+        const auto &lp = t.s->lay.nb_lists[k].ptr;
+        long long longest = 0;
+        for (size_t v = 0; v + 1 < lp.size(); ++v) longest = lp[v + 1] - lp[v] > longest ? lp[v + 1] - lp[v] : longest;
+        d.nb_max_members = (int)longest;
+        t.alloc(&d.nb_sel, nV * H);
+        if (!cfg.gated()) t.alloc(&d.nb_pool, nV * H);
     }
+    if (pairs) {
+        t.alloc(&d.th_B, nV * H);
+        t.alloc(&d.th_node, nV * H);
+        t.alloc(&d.nb_Tt, nV);
+        t.alloc(&d.nb_sA, nV);
+    }
+}
+// a distance handle: the molecules' distance matrices, their offsets and room for the sorted input rows x_d (smp_level_distance.hip)
+void put_distance_inputs(Taker &t, int nMol, const int *nVertices, const double *distance, size_t dist_count, size_t nV, NbhHostTables &host) {
+    gf_smp *s = t.s;
+    host.dist_off.resize((size_t)nMol);
+    long long o = 0;
+    for (int m = 0; m < nMol; ++m) {
+        host.dist_off[(size_t)m] = o;
+        o += (long long)nVertices[m] * nVertices[m];
+    }
+    if (t.st == GF_OK) t.st = upload(s, &s->mol_dist, distance, dist_count);
+    t.put(&s->mol_dist_off, host.dist_off);
+    t.alloc(&s->xd, nV * (size_t)s->cfg.max_nVertices);
+}
+// GCA_1D: the adjacency VALUES as floats, the molecules' offsets, room for the Gram matrices (smp_level_readouts.hip)
+void put_gram_inputs(Taker &t, int nMol, const int *nVertices, const int *adj, NbhHostTables &host) {
+    gf_smp *s = t.s;
+    host.gram_off.assign((size_t)nMol + 1, 0);
+    for (int m = 0; m < nMol; ++m) host.gram_off[(size_t)m + 1] = host.gram_off[(size_t)m] + (long long)nVertices[m] * nVertices[m];
+    host.gram_adj.resize((size_t)host.gram_off[(size_t)nMol]);
+    for (size_t i = 0; i < host.gram_adj.size(); ++i) host.gram_adj[i] = (float)adj[i];
+    t.put(&s->gram_adj, host.gram_adj);
+    t.put(&s->gram_off, host.gram_off);
+    t.alloc(&s->gram, host.gram_adj.size());
+    s->gram_count = host.gram_adj.size();
+}
+// form 6: the list N(v) = {v}
+void put_identity_list(Taker &t, size_t nV, NbhHostTables &host) {
+    host.id_ptr.resize(nV + 1);
+    host.id_idx.resize(nV);
+    for (size_t v = 0; v <= nV; ++v) host.id_ptr[v] = (long long)v;
+    for (size_t v = 0; v < nV; ++v) host.id_idx[v] = (int)v;
+    t.put(&t.s->nb_id_ptr, host.id_ptr);
+    t.put(&t.s->nb_id_idx, host.id_idx);
+}
+
+gf_status neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature, const double *distance) {
+    gf_ctx *ctx = s->ctx;
+    const gfsmp::Config &cfg = s->cfg;
+    size_t dist_count = 0;
+    gf_status st = check_neighbourhood_batch(s, distance ? "gf_smp_prepare_distance" : "gf_smp_prepare", nMol, nVertices, distance, &dist_count);
+    if (st != GF_OK) return st;
+    begin_batch(s);
+    gfsmp::build_batch_neighbourhood(cfg, nMol, nVertices, adj, feature, &s->lay);
+    const gfsmp::BatchLayout &B = s->lay;
+    const int L = cfg.nLevels;
+    const size_t nV = (size_t)B.mol_first_vertex[nMol], H = (size_t)cfg.nChanels;
+    for (const gfsmp::BatchLayout::NeighbourList &nl : B.nb_lists)
+        if (nl.idx.size() > 0x7fffffffull) return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare: a neighbour list beyond 2^31 entries");
+    s->lv.assign(L + 1, DevLevel());
+    s->lvd.assign(distance ? L + 1 : 0, DevLevel());
+    Taker t = {s};
+    std::vector<DevList> lists;
+    NbhHostTables host;
+    put_neighbour_lists(t, lists);
+    for (std::vector<DevLevel> *channel : {&s->lv, &s->lvd})   // (then the distance channel's levels)
+        for (size_t l = 0; l < channel->size(); ++l) alloc_neighbourhood_level(t, (*channel)[l], (int)l, lists, nV);
     t.put(&s->x, B.x);
     t.alloc(&s->g, (size_t)nMol * (size_t)cfg.top_channels());
     t.alloc(&s->yhat, (size_t)nMol);
     t.alloc(&s->dy, (size_t)nMol);
-    s->xd = nullptr;
-    s->mol_dist = nullptr;
-    s->mol_dist_off = nullptr;
-    if (distance) {
-        std::vector<long long> off((size_t)nMol);
-        long long o = 0;
-        for (int m = 0; m < nMol; ++m) {
-            off[(size_t)m] = o;
-            o += (long long)nVertices[m] * nVertices[m];
-        }
-        if (t.st == GF_OK) t.st = upload(s, &s->mol_dist, distance, dist_count);
-        t.put(&s->mol_dist_off, off);
-        t.alloc(&s->xd, nV * (size_t)cfg.max_nVertices);
-    }
-    s->gram_adj = s->gram = nullptr;
-    s->gram_off = nullptr;
-    s->gram_count = 0;
-    std::vector<float> gram_adj;   // (alive until the upload stream has been waited for)
-    std::vector<long long> gram_off;
-    if (cfg.readout == 2) {   // GCA_1D: the adjacency VALUES as floats, the molecules' offsets, room for the Gram matrices (smp_level_readouts.hip)
-        gram_off.assign((size_t)nMol + 1, 0);
-        for (int m = 0; m < nMol; ++m) gram_off[(size_t)m + 1] = gram_off[(size_t)m] + (long long)nVertices[m] * nVertices[m];
-        gram_adj.resize((size_t)gram_off[(size_t)nMol]);
-        for (size_t i = 0; i < gram_adj.size(); ++i) gram_adj[i] = (float)adj[i];
-        t.put(&s->gram_adj, gram_adj);
-        t.put(&s->gram_off, gram_off);
-        t.alloc(&s->gram, gram_adj.size());
-        s->gram_count = gram_adj.size();
-    }
-    s->gru_s = s->gru_t = s->gru_ds = s->gru_dt = s->gru_acc = nullptr;
+    if (distance) put_distance_inputs(t, nMol, nVertices, distance, dist_count, nV, host);
+    if (cfg.readout == 2) put_gram_inputs(t, nMol, nVertices, adj, host);
     if (cfg.gated())   // the gated read-out's two factors per vertex and their gradients
         for (float **p : {&s->gru_s, &s->gru_t, &s->gru_ds, &s->gru_dt}) t.alloc(p, nV * H);
     t.put(&s->top_node_mol, B.nb_vertex_mol);
     t.put(&s->mol_ptr, B.mol_first_vertex);
-    s->nb_id_ptr = nullptr;
-    s->nb_id_idx = nullptr;
-    if (cfg.neighbourhood == 6) {   // N(v) = {v}
-        std::vector<long long> ip(nV + 1);
-        std::vector<int> ii(nV);
-        for (size_t v = 0; v <= nV; ++v) ip[v] = (long long)v;
-        for (size_t v = 0; v < nV; ++v) ii[v] = (int)v;
-        t.put(&s->nb_id_ptr, ip);
-        t.put(&s->nb_id_idx, ii);
-    }
+    if (cfg.neighbourhood == 6) put_identity_list(t, nV, host);
     if (t.st != GF_OK) return t.st;
-    s->wbound = nullptr;
-    s->sh = s->vf = s->dsh = s->colpart = nullptr;
-    s->cls_scores = s->cls_prob = s->cls_dz = s->cls_dg = nullptr;
-    s->mol_nodes = nullptr;
-    s->P = nullptr;
-    s->P_count = 0;
-    s->ws_need = 1 << 20;   // (the TN products of dW1_l / dW2_l grow the context's workspace for their split-K partials themselves)
-    if (distance) {   // x_d: every vertex's column, padded and sorted, behind the uploads on the handle's stream
-        const gf_status st = smp_distance_rows_launch(ctx, upload_stream(s), (int)nV, cfg.max_nVertices, s->mol_dist, s->mol_dist_off, s->mol_ptr,
-                                                      s->top_node_mol, s->xd);
-        if (st != GF_OK) return st;
-    }
-    GF_HIP_TRY(ctx, hipStreamSynchronize(upload_stream(s)));
-    s->prepared = true;
-    return GF_OK;
-}
-gf_status smp_neighbourhood_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature) {
-    return neighbourhood_prepare(s, nMol, nVertices, adj, feature, nullptr);
-}
-gf_status smp_distance_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature, const double *distance) {
-    return neighbourhood_prepare(s, nMol, nVertices, adj, feature, distance);
-}
-// gf_smp_prepare_pairs of a pair handle (cfg.readout = 1): the 2 nPairs graphs X_0, Y_0, X_1, Y_1, .. as one neighbourhood batch
-gf_status smp_pairs_prepare(gf_smp *s, int nPairs, const int *nVertices1, const int *adj1, const double *feature1, const int *nVertices2,
-                            const int *adj2, const double *feature2) {
-    gfsmp::PairBatch pb;
-    gfsmp::interleave_pairs(s->cfg.nFeatures, nPairs, nVertices1, adj1, feature1, nVertices2, adj2, feature2, &pb);
-    return neighbourhood_prepare(s, 2 * nPairs, pb.nVertices.data(), pb.adj.data(), pb.feature.data(), nullptr);
+    if (distance)   // x_d: every vertex's column, padded and sorted, behind the uploads on the handle's stream
+        st = smp_distance_rows_launch(ctx, upload_stream(s), (int)nV, cfg.max_nVertices, s->mol_dist, s->mol_dist_off, s->mol_ptr, s->top_node_mol, s->xd);
+    // (the TN products of dW1_l / dW2_l grow the context's workspace for their split-K partials themselves)
+    return st != GF_OK ? st : finish_batch(s, 1 << 20);
 }
 
-// gf_smp_prepare of a matrix-form handle (LCNN, GCN_MW; smp_level_rowlist.hip): the host builds x and the level's row lists, forward and
-// transposed (gfsmp::build_batch_matrix_form); the device gets those and one activation / gradient buffer per level.
+// ---- the matrix-form handles (LCNN, GCN_MW; smp_level_rowlist.hip): the host builds x and the level's row lists, forward and transposed
+// (gfsmp::build_batch_matrix_form); the device gets those and one activation / gradient buffer per level ----
+void put_row_lists(Taker &t, bool lcnn) {
+    gf_smp *s = t.s;
+    const auto &rl = s->lay.rl;
+    t.put(&s->rl_fwd.ptr, rl.ptr);
+    t.put(&s->rl_fwd.src, rl.src);
+    t.put(&s->rl_fwd.slot, rl.slot);
+    t.put(&s->rl_fwd.coef, rl.coef);
+    t.put(&s->rl_bwd.ptr, rl.tptr);
+    t.put(&s->rl_bwd.src, rl.tsrc);
+    t.put(&s->rl_bwd.slot, rl.tslot);
+    t.put(&s->rl_bwd.coef, rl.tcoef);
+    if (lcnn) {
+        t.put(&s->rl_fwd.sptr, rl.sptr);
+        t.put(&s->rl_bwd.sptr, rl.tsptr);
+    } else {   // one slot: a row's entries are the slot's
+        s->rl_fwd.sptr = s->rl_fwd.ptr;
+        s->rl_bwd.sptr = s->rl_bwd.ptr;
+    }
+}
+// the two convolutions' activations and gradients, the dense layer and its gradient; returns the weight gradients' partial images in bytes
+size_t alloc_lcnn(Taker &t, size_t R, int nMol) {
+    gf_smp *s = t.s;
+    const gfsmp::Config &cfg = s->cfg;
+    const size_t H = (size_t)cfg.nChanels, C2 = (size_t)cfg.nChanels2, k = (size_t)cfg.nNeighbors;
+    t.alloc(&s->lv[1].f, R * H);
+    t.alloc(&s->lv[1].df, R * H);
+    t.alloc(&s->lv[2].f, R * C2);
+    t.alloc(&s->lv[2].df, R * C2);
+    t.alloc(&s->lv[2].Q, (size_t)nMol * cfg.nDense);
+    t.alloc(&s->g, (size_t)nMol * cfg.nDense);
+    return std::max(smp_rowlist_wgrad_ws_bytes((int)R, (int)(k * cfg.fdim()), (int)H), smp_rowlist_wgrad_ws_bytes((int)R, (int)(k * H), (int)C2));
+}
+size_t alloc_gcn_mw(Taker &t, size_t R, int nMol) {
+    gf_smp *s = t.s;
+    const size_t H = (size_t)s->cfg.nChanels;
+    for (int l = 0; l <= s->cfg.nLevels; ++l) {
+        t.alloc(&s->lv[l].f, R * H);
+        t.alloc(&s->lv[l].df, R * H);
+    }
+    t.alloc(&s->g, (size_t)nMol * H);
+    return std::max(smp_rowlist_wgrad_ws_bytes((int)R, s->cfg.fdim(), (int)H), smp_rowlist_wgrad_ws_bytes((int)R, (int)H, (int)H));
+}
+
 gf_status smp_matrix_form_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature) {
     gf_ctx *ctx = s->ctx;
     const gfsmp::Config &cfg = s->cfg;
     const bool lcnn = cfg.matrix_form == 1;
     long long rows = 0, entries = 0;
     for (int m = 0; m < nMol; ++m) {
-        if (nVertices[m] > cfg.max_nVertices)
-            return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare: molecule %d has %d vertices, the model was created with max_nVertices = %d", m,
-                        nVertices[m], cfg.max_nVertices);
+        const gf_status st = check_max_vertices(s, "gf_smp_prepare", m, nVertices[m]);
+        if (st != GF_OK) return st;
         rows += lcnn ? cfg.max_nVertices : nVertices[m];
         entries += lcnn ? (long long)cfg.max_nVertices * cfg.nNeighbors : (long long)nVertices[m] * nVertices[m];   // (an upper bound)
     }
     if (rows > 0x7fffffffll || entries > 0x7fffffffll)
         return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare: a matrix-form batch of %lld rows and up to %lld list entries (2^31 - 1 each)", rows, entries);
-    ensure_upload_stream(s);
-    release(s);
-    s->tab_stats = nullptr;
-    s->h_tab_stats.clear();
-    s->h_covered.clear();
-    s->rl_fwd = s->rl_bwd = RowList();
+    begin_batch(s);
     const int bad = gfsmp::build_batch_matrix_form(cfg, nMol, nVertices, adj, feature, &s->lay);
     if (bad >= 0)
         return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare: molecule %d has max_nVertices = %d vertices and a vertex that reaches fewer than nNeighbors = %d "
                                          "of them: LCNN pads its sequence with row %d, past its matrix", bad, cfg.max_nVertices, cfg.nNeighbors,
                     cfg.max_nVertices);
-    const gfsmp::BatchLayout &B = s->lay;
-    const int L = cfg.nLevels;
-    const size_t R = (size_t)rows, H = (size_t)cfg.nChanels;
-    s->lv.assign(L + 1, gf_smp::DevLevel());
+    s->lv.assign(cfg.nLevels + 1, DevLevel());
     Taker t = {s};
-    t.put(&s->rl_fwd.ptr, B.rl.ptr);
-    t.put(&s->rl_fwd.src, B.rl.src);
-    t.put(&s->rl_fwd.slot, B.rl.slot);
-    t.put(&s->rl_fwd.coef, B.rl.coef);
-    t.put(&s->rl_bwd.ptr, B.rl.tptr);
-    t.put(&s->rl_bwd.src, B.rl.tsrc);
-    t.put(&s->rl_bwd.slot, B.rl.tslot);
-    t.put(&s->rl_bwd.coef, B.rl.tcoef);
-    if (lcnn) {
-        t.put(&s->rl_fwd.sptr, B.rl.sptr);
-        t.put(&s->rl_bwd.sptr, B.rl.tsptr);
-    } else {   // one slot: a row's entries are the slot's
-        s->rl_fwd.sptr = s->rl_fwd.ptr;
-        s->rl_bwd.sptr = s->rl_bwd.ptr;
-    }
-    size_t ws = 1 << 20;
-    if (lcnn) {
-        const size_t C2 = (size_t)cfg.nChanels2, k = (size_t)cfg.nNeighbors;
-        t.alloc(&s->lv[1].f, R * H);
-        t.alloc(&s->lv[1].df, R * H);
-        t.alloc(&s->lv[2].f, R * C2);
-        t.alloc(&s->lv[2].df, R * C2);
-        t.alloc(&s->lv[2].Q, (size_t)nMol * cfg.nDense);
-        t.alloc(&s->g, (size_t)nMol * cfg.nDense);
-        ws = std::max(ws, std::max(smp_rowlist_wgrad_ws_bytes((int)R, (int)(k * cfg.fdim()), (int)H), smp_rowlist_wgrad_ws_bytes((int)R, (int)(k * H), (int)C2)));
-    } else {
-        for (int l = 0; l <= L; ++l) {
-            t.alloc(&s->lv[l].f, R * H);
-            t.alloc(&s->lv[l].df, R * H);
-        }
-        t.alloc(&s->g, (size_t)nMol * H);
-        ws = std::max(ws, std::max(smp_rowlist_wgrad_ws_bytes((int)R, cfg.fdim(), (int)H), smp_rowlist_wgrad_ws_bytes((int)R, (int)H, (int)H)));
-    }
-    t.put(&s->x, B.x);
+    put_row_lists(t, lcnn);
+    const size_t wgrad_ws = lcnn ? alloc_lcnn(t, (size_t)rows, nMol) : alloc_gcn_mw(t, (size_t)rows, nMol);
+    t.put(&s->x, s->lay.x);
     t.alloc(&s->yhat, (size_t)nMol);
     t.alloc(&s->dy, (size_t)nMol);
-    t.put(&s->top_node_mol, B.nb_vertex_mol);
-    t.put(&s->mol_ptr, B.mol_first_vertex);
+    t.put(&s->top_node_mol, s->lay.nb_vertex_mol);
+    t.put(&s->mol_ptr, s->lay.mol_first_vertex);
     if (t.st != GF_OK) return t.st;
-    s->gru_s = s->gru_t = s->gru_ds = s->gru_dt = s->gru_acc = nullptr;
-    s->nb_id_ptr = nullptr;
-    s->nb_id_idx = nullptr;
-    s->wbound = nullptr;
-    s->sh = s->vf = s->dsh = s->colpart = nullptr;
-    s->cls_scores = s->cls_prob = s->cls_dz = s->cls_dg = nullptr;
-    s->mol_nodes = nullptr;
-    s->P = nullptr;
-    s->P_count = 0;
-    s->ws_need = ws;   // (the weight gradients' partial images; the dense layer's TN product grows the workspace for its own)
-    GF_HIP_TRY(ctx, hipStreamSynchronize(upload_stream(s)));
-    s->prepared = true;
+    // (the weight gradients' partial images; the dense layer's TN product grows the workspace for its own)
+    return finish_batch(s, std::max<size_t>(1 << 20, wgrad_ws));
+}
+
+// null arguments (`have_all` = every pointer given and the count in range) / every graph has 1 .. 4096 vertices, in the entry point's words.
+// nV2: the Y graphs of gf_smp_prepare_pairs, which also come under max_nVertices here, before the batch is copied.
+gf_status check_graph_sizes(const gf_smp *s, const char *who, bool have_all, int n, const int *nV1, const int *nV2 = nullptr) {
+    if (n <= 0 || !have_all) return fail(s->ctx, GF_ERR_INVALID, "%s: bad argument", who);
+    for (int i = 0; i < n; ++i)
+        for (int side = 0; side < (nV2 ? 2 : 1); ++side) {
+            const int V = side ? nV2[i] : nV1[i];
+            char what[96];
+            if (nV2) std::snprintf(what, sizeof what, "%s: graph %c of pair %d", who, side ? 'Y' : 'X', i);
+            else std::snprintf(what, sizeof what, "molecule %d", i);
+            if (V <= 0 || V > 4096) return fail(s->ctx, GF_ERR_INVALID, "%s has %d vertices", what, V);
+            if (nV2 && V > s->cfg.max_nVertices)
+                return fail(s->ctx, GF_ERR_INVALID, "%s has %d vertices, the model was created with max_nVertices = %d", what, V, s->cfg.max_nVertices);
+        }
     return GF_OK;
 }
+
+}  // namespace
 
 // ints of a level's row-class buffer (see row_class_count), and its builder: three launches on `stream` behind whatever wrote trowf
 size_t smp_row_class_ints(int rows) { return 4 + 2 * ((size_t)rows + 64) + (size_t)(rows + kRcBlock - 1) / kRcBlock + 1; }
@@ -1209,9 +1221,8 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
                                  const double *coulomb) {
     if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
     gf_ctx *ctx = s->ctx;
-    if (nMol <= 0 || !nVertices || !adj || !feature) return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare: bad argument");
-    for (int m = 0; m < nMol; ++m)
-        if (nVertices[m] <= 0 || nVertices[m] > 4096) return fail(ctx, GF_ERR_INVALID, "molecule %d has %d vertices", m, nVertices[m]);
+    gf_status st = gf::check_graph_sizes(s, "gf_smp_prepare", nVertices && adj && feature, nMol, nVertices);
+    if (st != GF_OK) return st;
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (s->cfg.distance_channel)
         return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare: a distance handle (distance_channel = 1) takes its molecules through gf_smp_prepare_distance");
@@ -1222,19 +1233,15 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
     if (s->cfg.matrix_form && coulomb)
         return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_coulomb: a matrix-form handle (LCNN, GCN_MW) has no Coulomb adjacency");
     if (s->cfg.matrix_form) return gf::smp_matrix_form_prepare(s, nMol, nVertices, adj, feature);
-    if (s->cfg.neighbourhood) return gf::smp_neighbourhood_prepare(s, nMol, nVertices, adj, feature);
+    if (s->cfg.neighbourhood) return gf::neighbourhood_prepare(s, nMol, nVertices, adj, feature, nullptr);
     if (s->cfg.per_size()) return gf::smp_theta_prepare(s, nMol, nVertices, adj, feature);   // (first order: no reduced adjacency, coulomb is inert)
-    gf_status st = gf::choose_plan(s, nMol, nVertices, adj, coulomb);
+    st = gf::choose_plan(s, nMol, nVertices, adj, coulomb);
     if (st != GF_OK) return st;
     const bool prep_timing = std::getenv("GF_PREP_TIMING") != nullptr;
     const auto tp0 = std::chrono::steady_clock::now();
-    gf::ensure_upload_stream(s);
-    gf::release(s);
+    gf::begin_batch(s);
     const auto tp1 = std::chrono::steady_clock::now();
     gf::choose_table_builder(s, nMol, nVertices);
-    s->tab_stats = nullptr;
-    s->h_tab_stats.clear();
-    s->h_covered.clear();
     gfsmp::build_batch(s->cfg, nMol, nVertices, adj, feature, coulomb, &s->lay);
     const auto tp2 = std::chrono::steady_clock::now();
     static_assert(sizeof(long long) == sizeof(int64_t), "int64 layout");
@@ -1245,17 +1252,14 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
     for (int l = 0; l <= L && st == GF_OK; ++l) st = gf::alloc_level(s, l, &maxp, &contract_ws);
     if (st == GF_OK && s->lay.device_tables) st = gf::build_device_tables(s, coulomb != nullptr);
     if (st == GF_OK) st = gf::build_row_tables(s);
-    s->P = nullptr;  // [max ppos][C]: by far the largest buffer of the op-by-op path, taken from the pool only when a level needs it
-    s->P_count = (size_t)maxp;  // (positions x channels of the level below, maximised over the levels)
+    // P [max ppos][C of the level below]: by far the largest buffer of the op-by-op path, taken from the pool only when a level needs it (ensure_P)
+    s->P_count = (size_t)maxp;
     if (st == GF_OK) st = gf::alloc_readout(s, nMol);
     if (st != GF_OK) return st;
     // split-K partials of the weight gradients also live in the context workspace
     const size_t gemm_ws = sizeof(float) * 4400 * (size_t)4 * C * C + sizeof(float) * 4400 * (size_t)C * s->cfg.fdim() + (1 << 20);
-    s->ws_need = std::max(contract_ws, gemm_ws);  // grown by forward / backward on the compute thread (smp_internal.h)
-    // the tables are on the device when this returns (the host vectors are reused by the next batch); the context's stream
-    // is NOT waited for: it may be running another handle's step
-    GF_HIP_TRY(ctx, hipStreamSynchronize(gf::upload_stream(s)));
-    if (prep_timing) {
+    st = gf::finish_batch(s, std::max(contract_ws, gemm_ws));
+    if (st == GF_OK && prep_timing) {
         const auto tp3 = std::chrono::steady_clock::now();
         auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
             return std::chrono::duration<double, std::milli>(b - a).count();
@@ -1263,8 +1267,7 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
         std::fprintf(stderr, "gf_smp_prepare: release %.1f ms, host graph preparation %.1f ms, device allocation + upload %.1f ms\n",
                      ms(tp0, tp1), ms(tp1, tp2), ms(tp2, tp3));
     }
-    s->prepared = true;
-    return GF_OK;
+    return st;
 }
 
 gf_status gf_smp_prepare_distance(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature, const double *distance) {
@@ -1274,11 +1277,10 @@ gf_status gf_smp_prepare_distance(gf_smp *s, int nMol, const int *nVertices, con
         return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare_distance: a pair handle (readout = 1) takes its graphs through gf_smp_prepare_pairs");
     if (!s->cfg.distance_channel)
         return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_distance: the handle has no distance channel (gf_smp_config.distance_channel = 0)");
-    if (nMol <= 0 || !nVertices || !adj || !feature || !distance) return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare_distance: bad argument");
-    for (int m = 0; m < nMol; ++m)
-        if (nVertices[m] <= 0 || nVertices[m] > 4096) return fail(ctx, GF_ERR_INVALID, "molecule %d has %d vertices", m, nVertices[m]);
+    const gf_status st = gf::check_graph_sizes(s, "gf_smp_prepare_distance", nVertices && adj && feature && distance, nMol, nVertices);
+    if (st != GF_OK) return st;
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return gf::smp_distance_prepare(s, nMol, nVertices, adj, feature, distance);
+    return gf::neighbourhood_prepare(s, nMol, nVertices, adj, feature, distance);
 }
 
 gf_status gf_smp_prepare_pairs(gf_smp *s, int nPairs, const int *nVertices1, const int *adj1, const double *feature1, const int *nVertices2,
@@ -1287,18 +1289,13 @@ gf_status gf_smp_prepare_pairs(gf_smp *s, int nPairs, const int *nVertices1, con
     gf_ctx *ctx = s->ctx;
     if (s->cfg.readout != 1)
         return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_pairs: the handle has no pair read-out (gf_smp_config.readout = %d)", s->cfg.readout);
-    if (nPairs <= 0 || nPairs > 0x3fffffff || !nVertices1 || !adj1 || !feature1 || !nVertices2 || !adj2 || !feature2)
-        return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare_pairs: bad argument");
-    for (int p = 0; p < nPairs; ++p)
-        for (int side = 0; side < 2; ++side) {
-            const int V = side ? nVertices2[p] : nVertices1[p];
-            if (V <= 0 || V > 4096) return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare_pairs: graph %c of pair %d has %d vertices", side ? 'Y' : 'X', p, V);
-            if (V > s->cfg.max_nVertices)   // (before the batch is copied)
-                return fail(ctx, GF_ERR_INVALID, "gf_smp_prepare_pairs: graph %c of pair %d has %d vertices, the model was created with max_nVertices = %d",
-                            side ? 'Y' : 'X', p, V, s->cfg.max_nVertices);
-        }
+    const bool have_all = nPairs <= 0x3fffffff && nVertices1 && adj1 && feature1 && nVertices2 && adj2 && feature2;
+    const gf_status st = gf::check_graph_sizes(s, "gf_smp_prepare_pairs", have_all, nPairs, nVertices1, nVertices2);
+    if (st != GF_OK) return st;
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return gf::smp_pairs_prepare(s, nPairs, nVertices1, adj1, feature1, nVertices2, adj2, feature2);
+    gfsmp::PairBatch pb;   // the 2 nPairs graphs X_0, Y_0, X_1, Y_1, .. as one neighbourhood batch
+    gfsmp::interleave_pairs(s->cfg.nFeatures, nPairs, nVertices1, adj1, feature1, nVertices2, adj2, feature2, &pb);
+    return gf::neighbourhood_prepare(s, 2 * nPairs, pb.nVertices.data(), pb.adj.data(), pb.feature.data(), nullptr);
 }
 
 /* Host only: one molecule of a matrix-form configuration as gf_smp_prepare derives it -- LCNN's order and sequence, GCN_MW's A-hat. */
