@@ -15,10 +15,11 @@ from .smp import SMPGatedNeighbourhood, SMPNeighbourhood  # noqa: F401
 from .smp import GCNMW, LCNN  # noqa: F401
 from .smp import SMPDistance  # noqa: F401
 from .smp import GCA1D, SMPKernelPairs  # noqa: F401
+from .smp import CGCN1D, CGCN2D  # noqa: F401
 
 __all__ = ["Context", "GraphFlowHipError", "contract_forward", "contract_backward", "contract_workspace_bytes",
            "default_context", "build", "SMPNeighbourhood", "SMPGatedNeighbourhood", "GCNMW", "LCNN", "SMPDistance",
-           "SMPKernelPairs", "GCA1D"]
+           "SMPKernelPairs", "GCA1D", "CGCN1D", "CGCN2D"]
 
 
 def build(verbose=False):

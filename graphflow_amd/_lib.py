@@ -19,6 +19,37 @@ _fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 
+SMP_CONFIG_BYTES = 22 * C.sizeof(C.c_int)   # sizeof(gf_smp_config) of include/gf_hip.h (graphflow_amd.smp.SMPConfigCovariant is checked against it)
+
+
+class ConfigPointer:
+    """The `const gf_smp_config *` of a prototype.  gf_smp_config grows at its end, one int per model family, and a zero tail means
+    "everything as before"; a caller may still hold a structure of an earlier layout (graphflow_amd.smp.SMPConfig ends at `readout`; a
+    test builds its own).  Where the argument says how large the structure behind it is -- a ctypes structure, byref() of one, a typed
+    pointer -- and that is less than the library's structure, the library gets a copy with a zero tail instead of reading past the
+    caller's.  The library only reads a configuration, so the copy is not seen.  None, an address or a c_void_p pass as they are."""
+
+    @classmethod
+    def from_param(cls, obj):
+        if obj is None or isinstance(obj, (int, C.c_void_p)):
+            return _vp(obj) if isinstance(obj, int) else obj
+        src = getattr(obj, "_obj", None)   # byref(x)
+        if src is None and isinstance(obj, C._Pointer):
+            if not obj:
+                return None
+            src = obj.contents
+        if src is None:
+            src = obj
+        n = C.sizeof(src)
+        if n >= SMP_CONFIG_BYTES:
+            return C.cast(C.pointer(src), _vp) if src is obj else obj
+        padded = (C.c_char * SMP_CONFIG_BYTES)()
+        C.memmove(padded, C.addressof(src), n)
+        return C.byref(padded)
+
+
+_cfgp = ConfigPointer
+
 # name -> (restype, argtypes); mirrors include/gf_hip.h one to one (tests/test_abi.py checks the two agree)
 PROTOTYPES = {
     "gf_ctx_create": (C.c_int, [C.POINTER(_vp), C.c_int, _vp]),
@@ -80,15 +111,15 @@ PROTOTYPES.update({
     "gf_tensormatmul_backward_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "gf_custommatmultensor_forward_f32": (_i, [_vp, _vp, _vp, _vp, C.c_longlong, _i, _i]),
     "gf_custommatmultensor_backward_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _i, _i, _i]),
-    "gf_smp_create": (_i, [_vp, _vp, C.POINTER(_vp)]),
+    "gf_smp_create": (_i, [_vp, _cfgp, C.POINTER(_vp)]),
     "gf_smp_destroy": (_i, [_vp]),
     "gf_smp_param_count": (C.c_size_t, [_vp]),
-    "gf_smp_config_param_count": (C.c_size_t, [_vp]),
-    "gf_smp_classifier_config_param_count": (C.c_size_t, [_vp, _i]),
-    "gf_smp_create_classifier": (_i, [_vp, _vp, _i, C.POINTER(_vp)]),
+    "gf_smp_config_param_count": (C.c_size_t, [_cfgp]),
+    "gf_smp_classifier_config_param_count": (C.c_size_t, [_cfgp, _i]),
+    "gf_smp_create_classifier": (_i, [_vp, _cfgp, _i, C.POINTER(_vp)]),
     "gf_smp_classes": (_i, [_vp]),
     "gf_smp_class_scores": (_i, [_vp, _vp, _vp]),
-    "gf_smp_classifier_uniform_init_host": (_i, [_vp, _i, _fp]),
+    "gf_smp_classifier_uniform_init_host": (_i, [_cfgp, _i, _fp]),
     "gf_smp_prepare": (_i, [_vp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp]),
     "gf_smp_prepare_coulomb": (_i, [_vp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, _dp]),
     "gf_smp_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
@@ -107,7 +138,7 @@ PROTOTYPES.update({
     "gf_smp_adam_step": (_i, [_vp, _vp, _vp, C.c_double, _i]),
     "gf_smp_adam_reset": (_i, [_vp]),
     "gf_smp_momentum_step": (_i, [_vp, _vp, _vp, C.c_double, _i, C.c_double]),
-    "gf_smp_uniform_init_host": (_i, [_vp, _fp]),
+    "gf_smp_uniform_init_host": (_i, [_cfgp, _fp]),
     "gf_smp_save_model": (_i, [_vp, _vp, C.c_char_p]),
     "gf_smp_load_model": (_i, [_vp, _vp, C.c_char_p]),
     "gf_smp_set_fused": (_i, [_vp, _i]),
@@ -141,8 +172,11 @@ PROTOTYPES.update({
     "gf_smp_third_order_pool_bwd_ex_f32": (_i, [_vp, _i, _i] + [_vp] * 8),
     "gf_smp_rowlist_product_ex_f32": (_i, [_vp, _i, _i, _i, _i, _i, _i] + [_vp] * 7 + [_i, _vp]),
     "gf_smp_rowlist_wgrad_ex_f32": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 8),
-    "gf_smp_matrix_form_molecule_host": (_i, [_vp, _i, C.POINTER(C.c_int), _dp, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp]),
-    "gf_smp_prepare_molecule_host": (_i, [_vp, _i, C.POINTER(C.c_int), _dp, C.POINTER(C.c_int), _dp]),
+    "gf_smp_covariant_forward_ex_f32": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 13),
+    "gf_smp_covariant_backward_ex_f32": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 12),
+    "gf_smp_covariant_molecule_host": (_i, [_cfgp, _i, C.POINTER(C.c_int), _dp, C.POINTER(C.c_int), _vp, _dp]),
+    "gf_smp_matrix_form_molecule_host": (_i, [_cfgp, _i, C.POINTER(C.c_int), _dp, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp]),
+    "gf_smp_prepare_molecule_host": (_i, [_cfgp, _i, C.POINTER(C.c_int), _dp, C.POINTER(C.c_int), _dp]),
     "gf_smp_receptive_field": (_i, [_vp, _i, _i, _i, C.POINTER(C.c_int), _i]),
     "gf_smp_read_activation": (C.c_longlong, [_vp, _i, _i, _i, _vp, C.c_size_t]),
     "gf_smp_read_reduced_adjacency": (C.c_longlong, [_vp, _i, _i, _i, _vp, C.c_size_t]),

@@ -641,10 +641,10 @@ gf_status gf::smp_create(gf_ctx *ctx, const gf_smp_config *cfg, const gfsmp::Con
     gf_smp *s = new gf_smp();
     s->ctx = ctx;
     s->ucfg = c;
-    if (c.per_size() || c.neighbourhood || c.matrix_form) s->grad_allreduce = 0;   // (no data-parallel exchange: gf_smp_set_grad_allreduce(.., 1) is refused)
+    if (c.per_size() || c.neighbourhood || c.matrix_form || c.covariant) s->grad_allreduce = 0;   // (no data-parallel exchange: gf_smp_set_grad_allreduce(.., 1) is refused)
     s->req_pad_channels = pad_channels;
     s->req_min_pad = min_pad;
-    if (c.neighbourhood || c.matrix_form) {   // (no padding, one plan, none of the fused level's switches)
+    if (c.neighbourhood || c.matrix_form || c.covariant) {   // (no padding, one plan, none of the fused level's switches)
         s->cfg = c;
     } else {
         gf::smp_derive_plan(s, /*allow_embed=*/true);
@@ -806,6 +806,7 @@ gf_status forward_sweep(gf_smp *s, const float *params, const float *targets, fl
     gf_status st = ensure_ws(ctx, s->ws_need);
     if (st != GF_OK) return st;
     if (s->cfg.matrix_form) return smp_matrix_form_forward(s, params, targets, predict, loss, graph_feature);   // (LCNN, GCN_MW: smp_level_rowlist.hip)
+    if (s->cfg.covariant) return smp_covariant_forward(s, params, targets, predict, loss, graph_feature);   // (CGCN_1D, CGCN_2D: smp_level_covariant.hip)
     if (s->cfg.distance_channel) return smp_distance_forward(s, params, targets, predict, loss, graph_feature);   // (two channels of that kind)
     if (s->cfg.gated()) return smp_gru_forward(s, params, targets, predict, loss, graph_feature);   // (the neighbourhood kind's second set of sweeps)
     if (s->cfg.neighbourhood) return smp_neighbourhood_forward(s, params, targets, predict, loss, graph_feature);   // (its own level 0 and read-out)
@@ -1007,6 +1008,7 @@ gf_status backward_sweep(gf_smp *s, const float *params, float *grads, int accum
     gf_status st = ensure_ws(ctx, s->ws_need);
     if (st != GF_OK) return st;
     if (s->cfg.matrix_form) return smp_matrix_form_backward(s, params, grads, accumulate);
+    if (s->cfg.covariant) return smp_covariant_backward(s, params, grads, accumulate);
     if (s->cfg.distance_channel) return smp_distance_backward(s, params, grads, accumulate);
     if (s->cfg.gated()) return smp_gru_backward(s, params, grads, accumulate);
     if (s->cfg.neighbourhood) return smp_neighbourhood_backward(s, params, grads, accumulate);   // (never a tower: gf_smp_backward_features refuses)
@@ -1154,6 +1156,7 @@ gf_status gf_smp_dropout_masks(gf_smp *s, const unsigned *masks, float scale) {
     if (s->cfg.per_size() || s->cfg.neighbourhood)
         return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_dropout_masks: a first-order, steerable_2d or neighbourhood handle has no contraction slices to drop");
     if (s->cfg.matrix_form) return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_dropout_masks: a matrix-form handle (LCNN, GCN_MW) has no contraction slices to drop");
+    if (s->cfg.covariant) return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_dropout_masks: a covariant handle (CGCN_1D, CGCN_2D) has no contraction slices to drop");
     if (!masks) {
         s->drop_on = false;
         return GF_OK;
@@ -1202,6 +1205,9 @@ gf_status gf_smp_set_grad_allreduce(gf_smp *s, int on) {
     if (on && s->cfg.matrix_form)
         return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_set_grad_allreduce: a matrix-form handle (LCNN, GCN_MW) has no data-parallel exchange (reduce the "
                                                 "flat gradient)");
+    if (on && s->cfg.covariant)
+        return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_set_grad_allreduce: a covariant handle (CGCN_1D, CGCN_2D) has no data-parallel exchange (reduce the "
+                                                "flat gradient)");
     s->grad_allreduce = on ? 1 : 0;
     return GF_OK;
 }
@@ -1216,6 +1222,7 @@ gf_status gf_smp_backward_features(gf_smp *s, const float *params, float *grads,
     if (s->cfg.steerable_2d || s->cfg.unrestricted || s->cfg.neighbourhood)
         return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_backward_features: a steerable_2d, unrestricted or neighbourhood handle is no tower");
     if (s->cfg.matrix_form) return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_backward_features: a matrix-form handle (LCNN, GCN_MW) is no tower");
+    if (s->cfg.covariant) return fail(s->ctx, GF_ERR_UNSUPPORTED, "gf_smp_backward_features: a covariant handle (CGCN_1D, CGCN_2D) is no tower");
     if (!d_feature) return fail(s->ctx, GF_ERR_INVALID, "gf_smp_backward_features: null feature gradient");
     gf_status st = gf::backward_check(s, &params, &grads, accumulate, d_feature);
     return st == GF_OK ? gf::backward_run(s, params, grads, accumulate, d_feature) : st;
@@ -1268,6 +1275,15 @@ int gf_smp_receptive_field(const gf_smp *s, int mol, int level, int v, int *out,
         for (long long i = 0; i < n && i < capacity; ++i) out[i] = s->lay.rl.src[(size_t)(e0 + i)] - v0;
         return (int)n;
     }
+    if (s->cfg.covariant) {   // the mask of level `level`: { u : sp[u][v] <= level }, ascending
+        int n = 0;
+        for (int u = 0; u < M.V; ++u)
+            if (M.hops[(size_t)u * M.V + v] <= level) {
+                if (n < capacity) out[n] = u;
+                ++n;
+            }
+        return n;
+    }
     if (s->cfg.neighbourhood) {   // N_level(v), ascending (level 0: the vertex itself)
         if (level == 0) {
             if (capacity > 0) out[0] = v;
@@ -1296,6 +1312,14 @@ static long long smp_read_node(gf_smp *s, int mol, int level, int v, float *out,
         const int nrows = lcnn ? s->cfg.max_nVertices : s->lay.mols[mol].V;
         if (adjacency || (lcnn && level == 0) || v < 0 || v >= nrows || W > capacity) return -1;
         const float *src = s->lv[level].f + ((size_t)s->lay.mol_first_vertex[mol] + v) * W;
+        if (hipMemcpyAsync(out, src, W * sizeof(float), hipMemcpyDeviceToHost, s->ctx->stream) != hipSuccess) return -1;
+        if (hipStreamSynchronize(s->ctx->stream) != hipSuccess) return -1;
+        return (long long)W;
+    }
+    if (s->cfg.covariant) {   // h_level[v] [M]; no reduced adjacency
+        const size_t W = (size_t)s->cfg.max_nVertices, nV = (size_t)s->lay.level[0].nNodes;
+        if (adjacency || v < 0 || v >= s->lay.mols[mol].V || W > capacity) return -1;
+        const float *src = s->cov_h + ((size_t)level * nV + (size_t)s->lay.mol_first_vertex[mol] + v) * W;
         if (hipMemcpyAsync(out, src, W * sizeof(float), hipMemcpyDeviceToHost, s->ctx->stream) != hipSuccess) return -1;
         if (hipStreamSynchronize(s->ctx->stream) != hipSuccess) return -1;
         return (long long)W;

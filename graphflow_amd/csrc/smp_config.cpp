@@ -106,6 +106,7 @@ gf_status resolve_config(const gf_smp_config *cfg, const ConfigEntry &entry, Con
         if (cfg->first_order == 1)   // (SMP_theta has no `_classification` class; first_order = 2, 3, 4 do: SMP_1D*_classification)
             GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: a first-order model (first_order = 1) has no classifier read-out");
         if (cfg->unrestricted) GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: the Unrestricted_SMP_* models have no `_classification` class");
+        if (cfg->covariant) GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: CGCN_1D / CGCN_2D have no `_classification` class");
         if (cfg->matrix_form) GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: LCNN / GCN_MW have no `_classification` class");
         if (cfg->neighbourhood == 6 || cfg->neighbourhood == 7)
             GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_create_classifier: GCN_3D / GRU_GCN_3D have no `_classification` class");
@@ -116,6 +117,39 @@ gf_status resolve_config(const gf_smp_config *cfg, const ConfigEntry &entry, Con
         if (nClass < 2) GF_REFUSE(GF_ERR_INVALID, "gf_smp_create_classifier: nClass = %d (at least 2)", nClass);
     }
     // ---- the configuration, family by family ----
+    if (cfg->covariant) {   // CGCN_1D, CGCN_2D (smp_level_covariant.hip): nLevels = 0 is a model
+        if (entry.kind == ConfigEntry::Tower)
+            GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_model_create: CGCN_1D / CGCN_2D (covariant = %d) are no towers", cfg->covariant);
+        if (cfg->covariant < 1 || cfg->covariant > 2)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: covariant = %d: the covariant models are covariant = 1 (CGCN_1D) and 2 (CGCN_2D)", cfg->covariant);
+        if (cfg->first_order || cfg->steerable_2d || cfg->unrestricted || cfg->neighbourhood || cfg->matrix_form || cfg->distance_channel ||
+            cfg->readout || !plain_levels(cfg))
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: covariant = %d needs every other form selector 0: first_order = steerable_2d = unrestricted = "
+                                      "neighbourhood = matrix_form = distance_channel = readout = physics = nContractions = custom_matmul = 0",
+                      cfg->covariant);
+        if (cfg->nChanels != 1)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: covariant = %d with nChanels = %d: a vertex carries one vector over the vertex ids, nChanels = 1",
+                      cfg->covariant, cfg->nChanels);
+        if (cfg->nLevels < 0 || cfg->nLevels > 64)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: covariant = %d with nLevels = %d: nLevels in 0 .. 64", cfg->covariant, cfg->nLevels);
+        if (cfg->nFeatures < 1 || cfg->nDepth < 0)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: covariant = %d with nFeatures = %d, nDepth = %d: nFeatures >= 1 and nDepth >= 0", cfg->covariant,
+                      cfg->nFeatures, cfg->nDepth);
+        if ((long long)cfg->nFeatures * ((long long)cfg->nDepth + 1) > 65536)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: covariant = %d with nFeatures (nDepth + 1) = %lld: at most 65536", cfg->covariant,
+                      (long long)cfg->nFeatures * ((long long)cfg->nDepth + 1));
+        if (cfg->max_nVertices < 1 || cfg->max_nVertices > gf::kCovariantMaxVertices ||
+            gf::smp_covariant_lds_bytes(cfg->max_nVertices) > 160 * 1024)
+            GF_REFUSE(GF_ERR_INVALID, "gf_smp_create: covariant = %d with max_nVertices = %d: the kernels keep a molecule's whole network in LDS, "
+                                      "4 (7 M (M | 1) + 2 M + 8) + M M bytes against 160 KiB per workgroup: max_nVertices in 1 .. %d", cfg->covariant,
+                      cfg->max_nVertices, gf::kCovariantMaxVertices);
+        Config c = {cfg->nLevels, 1, cfg->nFeatures, cfg->nDepth, cfg->max_nVertices, 0};
+        c.nContractions = 0;
+        c.max_nVertices = cfg->max_nVertices;
+        c.covariant = cfg->covariant;
+        *out = c;
+        return GF_OK;
+    }
     if (cfg->readout) {   // GCN_1D_Kernel, GCN_2D_Kernel, GCN_3D_Kernel (1: forms 2, 3, 6 on pairs), GCA_1D (2: form 2 under the Gram read-out); smp_level_readouts.hip
         const int form = cfg->neighbourhood, ro = cfg->readout;
         if (entry.kind == ConfigEntry::Tower) GF_REFUSE(GF_ERR_UNSUPPORTED, "gf_smp_model_create: the pair and Gram read-outs (readout = %d) are no towers", ro);

@@ -43,6 +43,15 @@ inline size_t smp_gram_lds_bytes(int V, int H) { return sizeof(float) * ((size_t
 // checks its own tile count (rows / 128 x 2^10, or 2^9 x 2^10 x splits) against 2^31 - 1.
 constexpr int kRowlistMaxWidth = 65536;
 constexpr int kRowlistSplits = 256;   // most partial images of a weight gradient, folded in ascending order
+// the covariant level (smp_level_covariant.hip; covariant = 1, 2): one workgroup keeps a molecule's whole network in LDS -- seven [V][V | 1]
+// images in the reverse kernel (dh_l / dz, dh_{l-1}, n_l / dn, F_l[:V, :V] / the pair dots, h_{l-1}, the exclusive sums, the pair
+// constants; the forward kernel uses five of them), two vectors of V floats, eight floats of reductions and the V V hop counts as bytes:
+//   4 (7 V (V | 1) + 2 V + 8) + V V bytes (rounded up to 16) -- 24,660 at V = 29, 121,120 at 64; within 160 KiB up to V = 75
+inline size_t smp_covariant_lds_bytes(int V) {
+    return sizeof(float) * (7 * (size_t)V * (size_t)(V | 1) + 2 * (size_t)V + 8) + (((size_t)V * (size_t)V + 15) & ~(size_t)15);
+}
+constexpr int kCovariantMaxVertices = 75;   // the largest V with smp_covariant_lds_bytes(V) <= 160 KiB
+constexpr int kCovariantSplits = 256;       // most partial images of the gradient: chunks of ceil(nMol / 256) molecules, folded in ascending order
 }  // namespace gf
 
 namespace gfsmp {

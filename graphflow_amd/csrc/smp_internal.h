@@ -267,6 +267,13 @@ struct gf_smp_batch {
     // lv[l].df = dh_l and then dz_l in place, [vertices][H].  LCNN: lv[1].f = a1 and lv[1].df = da1 / dc1 [nMol V][C1], lv[2].f = c2 and
     // lv[2].df = dc2 [nMol V][C2], lv[2].Q = the gradient of the dense layer [nMol][nDense]; g = the dense layer itself.
     gf::RowList rl_fwd, rl_bwd;
+    // covariant handles (cfg.covariant; smp_level_covariant.hip): the column lists N(v) and their transposes over global vertex ids, the hop
+    // counts cov_hop [vertices][M] (gfsmp::BatchLayout::cov_hop), and what the forward leaves for the reverse: cov_h [L + 1][vertices][M] =
+    // every h_l[v], cov_n [L][vertices][M] = every n_l[v] (l = 1 .. L), cov_ds0 [vertices] = the gradient of <x[v], H>.  g is [nMol][M].
+    const long long *cov_ptr = nullptr, *cov_tptr = nullptr;
+    const int *cov_idx = nullptr, *cov_tidx = nullptr;
+    unsigned char *cov_hop = nullptr;
+    float *cov_h = nullptr, *cov_n = nullptr, *cov_ds0 = nullptr;
     // the list N(v) = {v} over the batch's vertices (form 6: the sum instantiation of nbh_level_fwd over it hands the pooled n on unchanged)
     long long *nb_id_ptr = nullptr;
     int *nb_id_idx = nullptr;
@@ -502,6 +509,11 @@ gf_status smp_third_pool_bwd_launch(gf_ctx *ctx, int H, int nV, const long long 
 // params / grads: GCN_MW W_0; W_l; W.  LCNN F1, b1, F2, b2, Dm, W.
 gf_status smp_matrix_form_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature);
 gf_status smp_matrix_form_backward(gf_smp *s, const float *params, float *grads, int accumulate);
+// CGCN_1D, CGCN_2D (cfg.covariant = 1, 2; smp_level_covariant.hip): the whole sweeps of such a handle -- one launch each for all levels, and
+// one fold of the gradient's partial images -- the bytes of those images, and its gf_smp_prepare (smp_prepare.hip).  params / grads: H; F_l.
+gf_status smp_covariant_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature);
+gf_status smp_covariant_backward(gf_smp *s, const float *params, float *grads, int accumulate);
+size_t smp_covariant_ws_bytes(int nMol, size_t image_floats);
 // the first-order read-out of level l (smp_field_level.hip): sh[n] = column sums over the node's s rows (ShrinkMatrix), vf = LeakyReLU(sh);
 // and its reverse, df_l[n][i][:] (+)= dvec[n][:] at every row i of the node, dvec = one gradient vector per node
 gf_status smp_theta_readout(gf_smp *s, int l, float *sh, float *vf);

@@ -109,6 +109,8 @@ gf_status gf_smp_forward_host(gf_smp *s, const double *targets, double *predict,
     if (s->cfg.readout)   // (in every state of the handle: its outputs are per pair, or a Gram matrix: not this call's per-molecule arrays)
         return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_forward_host: the %s read-out (readout = %d) has no host-pointer forward: gf_smp_forward",
                     s->cfg.readout == 1 ? "pair" : "Gram", s->cfg.readout);
+    if (s->cfg.covariant)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_forward_host: a covariant handle (CGCN_1D, CGCN_2D) has no host-pointer forward: gf_smp_forward");
     if (!s->prepared) return fail(ctx, GF_ERR_INVALID, "gf_smp_forward_host before gf_smp_prepare");
     if (!s->own_p) return fail(ctx, GF_ERR_INVALID, "gf_smp_forward_host: no handle-owned model (gf_smp_parameters_upload)");
     const int nMol = s->lay.nMol, C = s->ucfg.top_channels();

@@ -850,6 +850,77 @@ void build_batch_neighbourhood(const Config &cfg, int nMol, const int *nVertices
     }
 }
 
+// CGCN_1D, CGCN_2D (Config::covariant).  Per molecule: the hop distances (CGCN_1D.h:156-176, the text of GCN_1D.h's), x (:179-193, the
+// shell sums), the masks' hop counts transposed -- cov_hop[v][i] = sp[i][v] (:203-209 reads shortest_paths[u][v]) -- and ONE list:
+// member (v, u) iff adj[u][v] > 0 (:225-229: column v, the diagonal included), u ascending; its transpose for the reverse gather.
+void build_batch_covariant(const Config &cfg, int nMol, const int *nVertices, const int *adj, const double *feature, BatchLayout *out) {
+    const int L = cfg.nLevels, FD = cfg.fdim(), F = cfg.nFeatures, M = cfg.max_nVertices;
+    out->device_tables = false;
+    out->nMol = nMol;
+    out->mols.assign(nMol, Molecule());
+    out->mol_first_vertex.assign(nMol + 1, 0);
+    std::vector<size_t> adj_off(nMol + 1, 0);
+    out->max_vertices = 1;
+    for (int m = 0; m < nMol; ++m) {
+        out->mol_first_vertex[m + 1] = out->mol_first_vertex[m] + nVertices[m];
+        adj_off[m + 1] = adj_off[m] + (size_t)nVertices[m] * nVertices[m];
+        out->max_vertices = std::max(out->max_vertices, nVertices[m]);
+    }
+    const int totalV = out->mol_first_vertex[nMol];
+    out->x.assign((size_t)totalV * FD, 0.f);
+    out->nb_vertex_mol.assign((size_t)totalV, 0);
+    out->cov_hop.assign((size_t)totalV * M, (unsigned char)255);
+    out->nb_lists.assign(1, BatchLayout::NeighbourList());
+    BatchLayout::NeighbourList &nl = out->nb_lists[0];
+    nl.ptr.assign((size_t)totalV + 1, 0);
+    nl.tptr.assign((size_t)totalV + 1, 0);
+    parallel_for(nMol, [&](int m) {
+        const int V = nVertices[m], v0 = out->mol_first_vertex[m];
+        const int *A = adj + adj_off[m];
+        Molecule &mol = out->mols[m];
+        mol.V = V;
+        hop_distances(V, A, &mol.hops);
+        wl_features(cfg, V, feature + (size_t)v0 * F, mol.hops, &mol.wl);
+        for (size_t i = 0; i < (size_t)V * FD; ++i) out->x[(size_t)v0 * FD + i] = (float)mol.wl[i];
+        for (int v = 0; v < V; ++v) {
+            out->nb_vertex_mol[(size_t)v0 + v] = m;
+            for (int i = 0; i < V && i < M; ++i) {
+                const int h = mol.hops[(size_t)i * V + v];
+                out->cov_hop[((size_t)v0 + v) * M + i] = (unsigned char)(h < 0 || h > 255 ? 255 : h);
+            }
+            for (int u = 0; u < V; ++u) {   // (counts; the prefix sums follow)
+                if (A[(size_t)u * V + v] > 0) nl.ptr[(size_t)v0 + v + 1] += 1;    // u in N(v)
+                if (A[(size_t)v * V + u] > 0) nl.tptr[(size_t)v0 + v + 1] += 1;   // v in N(u): u consumes v
+            }
+        }
+    });
+    for (int g = 0; g < totalV; ++g) {
+        nl.ptr[(size_t)g + 1] += nl.ptr[(size_t)g];
+        nl.tptr[(size_t)g + 1] += nl.tptr[(size_t)g];
+    }
+    nl.idx.assign((size_t)nl.ptr[(size_t)totalV], 0);
+    nl.tidx.assign((size_t)nl.tptr[(size_t)totalV], 0);
+    parallel_for(nMol, [&](int m) {   // (a molecule's vertices own disjoint ranges of both tables)
+        const int V = nVertices[m], v0 = out->mol_first_vertex[m];
+        const int *A = adj + adj_off[m];
+        for (int v = 0; v < V; ++v) {
+            int64_t e = nl.ptr[(size_t)v0 + v], t = nl.tptr[(size_t)v0 + v];
+            for (int u = 0; u < V; ++u) {
+                if (A[(size_t)u * V + v] > 0) nl.idx[(size_t)e++] = v0 + u;
+                if (A[(size_t)v * V + u] > 0) nl.tidx[(size_t)t++] = v0 + u;
+            }
+        }
+    });
+    out->nb_list_of_level.assign(L + 1, 0);
+    out->level.assign(L + 1, LevelLayout());
+    for (int l = 0; l <= L; ++l) {
+        out->level[l].nNodes = totalV;
+        out->level[l].rows = totalV;
+    }
+    out->top_node_of_vertex.clear();
+    out->node_of_vertex.clear();
+}
+
 // GCN_*D_Kernel (Config::readout = 1): X_0, Y_0, X_1, Y_1, ..
 void interleave_pairs(int nFeatures, int nPairs, const int *nVertices1, const int *adj1, const double *feature1, const int *nVertices2,
                       const int *adj2, const double *feature2, PairBatch *out) {

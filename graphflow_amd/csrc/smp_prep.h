@@ -107,6 +107,11 @@ struct Config {
     // 2 with neighbourhood = 2: GCA_1D (GraphFlow/GCA_1D.h, LinearGram.h): GCN_1D's levels, read out as the Gram matrix of the top-level
     // vectors against the molecule's adjacency values.  Parameters: GCN_1D's without W (readout_block() is empty).
     int readout = 0;
+    // 1, 2: CGCN_1D, CGCN_2D (GraphFlow/CGCN_1D.h, CGCN_2D.h; gf_smp_config.covariant; smp_level_covariant.hip): one vector h_l[v]
+    // [max_nVertices] per vertex, indexed by the molecule's vertex ids; the aggregate over N(v) = column v of the adjacency is a sum (1) or
+    // RisiLayer2D (2), the update F_l n masked by the receptive field { i : sp[i][v] <= l }, LeakyReLU 0.01; the graph feature is the sum of
+    // the h_L[v], the prediction the sum of its components.  Parameters: H [F'] (first_block, a Vector); F_l [M][M] (a Matrix) per level; no W.
+    int covariant = 0;
     bool gated() const { return neighbourhood == 4 || neighbourhood == 5 || neighbourhood == 7; }
     bool third_order() const { return neighbourhood == 6 || neighbourhood == 7; }
     int nb_radius(int l) const { return neighbourhood == 1 ? 1 : (neighbourhood == 3 && !distance_channel && readout != 1) || l < max_Radius ? l : max_Radius; }   // of N_l (form 1: the adjacency itself; 3 alone ignores max_Radius)
@@ -184,6 +189,10 @@ struct Config {
         if (gated()) return b;   // (every block is shared: shared_blocks())
         auto sizes = [&b](std::initializer_list<LevelBlocks::SizeTerm> t) { for (const LevelBlocks::SizeTerm &x : t) b.size[b.nsize++] = x; };
         auto matrix = [&b](size_t n, size_t div = 0) { b.mat[b.nmat++] = {n, div ? div : n}; };   // (div = 0: a Vector, divided by its own size)
+        if (covariant) {   // F_l [M][M], a Matrix
+            matrix((size_t)max_nVertices * (size_t)max_nVertices, (size_t)max_nVertices);
+            return b;
+        }
         if (matrix_form == 2) {   // W_l [H][H], a Matrix
             matrix(Cl * Cl, Cl);
             return b;
@@ -236,10 +245,10 @@ struct Config {
     // W [readout_rows()][top_channels()] (SMP_2D_ver6_classification.h:211-217), drawn as one Vector; none in a physics tower, which ends in
     // its level features: the head's weights are the caller's; none in GCA_1D (readout = 2: top_channels() is 0), W [2 H] of a pair model
     Block readout_block() const {
-        const size_t n = physics ? 0 : (size_t)readout_rows() * top_channels();
+        const size_t n = physics || covariant ? 0 : (size_t)readout_rows() * top_channels();   // (CGCN_*: SumComponents, no W)
         return {n, n};
     }
-    int top_channels() const { return readout == 2 ? 0 : distance_channel || readout == 1 ? 2 * nChanels : matrix_form == 1 ? nDense : first_order >= 2 || steerable_2d ? level_channels(nLevels) : nChanels;  }   // width of the graph feature and of W's rows
+    int top_channels() const { return covariant ? max_nVertices : readout == 2 ? 0 : distance_channel || readout == 1 ? 2 * nChanels : matrix_form == 1 ? nDense : first_order >= 2 || steerable_2d ? level_channels(nLevels) : nChanels;  }   // width of the graph feature and of W's rows
     int readout_rows() const { return nClass > 1 ? nClass : 1; }   // rows of W: [1][C] is the regression's [C]
     bool square() const { return !physics || uniform; }   // K_l is [nContractions C][C] at every level
     int level_channels(int l) const {
@@ -447,6 +456,7 @@ struct BatchLayout {
         std::vector<int> order, seq;
     };
     RowLists rl;
+    tvec<unsigned char> cov_hop;   // Config::covariant (build_batch_covariant)
 };
 
 // coulomb: NULL, or the molecules' V x V Coulomb matrices back to back (DenseGraph::coulomb) -- the reduced adjacency of
@@ -486,6 +496,12 @@ bool lcnn_reads_past(const Config &cfg, int molV, const std::vector<int> &seq);
 // The batch of a matrix-form model: x, the row lists (BatchLayout::rl), level[l]: nNodes = rows = the batch's rows.  Returns the first
 // molecule lcnn_reads_past, or -1 (the batch is then complete).
 int build_batch_matrix_form(const Config &cfg, int nMol, const int *nVertices, const int *adj, const double *feature, BatchLayout *out);
+
+// The batch of a covariant model (Config::covariant): hop distances, the shell-sum features x, nb_lists[0] = the column lists N(v) = { u :
+// adj[u][v] > 0 } with their transposes (global vertex ids, ascending), and cov_hop [vertices][max_nVertices]: cov_hop[v][i] = sp[i][v]
+// clipped to 255 (unreachable), positions beyond the molecule 255.  level[l]: nNodes = rows = vertices.  Every molecule has at most
+// max_nVertices vertices (the caller checks).
+void build_batch_covariant(const Config &cfg, int nMol, const int *nVertices, const int *adj, const double *feature, BatchLayout *out);
 
 }  // namespace gfsmp
 #endif

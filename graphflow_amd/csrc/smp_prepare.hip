@@ -1169,6 +1169,47 @@ gf_status smp_matrix_form_prepare(gf_smp *s, int nMol, const int *nVertices, con
     return finish_batch(s, std::max<size_t>(1 << 20, wgrad_ws));
 }
 
+// ---- the covariant handles (CGCN_1D, CGCN_2D; smp_level_covariant.hip): the host builds x, the hop counts and the column lists with their
+// transposes (gfsmp::build_batch_covariant); the device gets those and the two buffers the forward kernel leaves for the reverse ----
+gf_status covariant_prepare(gf_smp *s, int nMol, const int *nVertices, const int *adj, const double *feature) {
+    gf_ctx *ctx = s->ctx;
+    const gfsmp::Config &cfg = s->cfg;
+    long long rows = 0;
+    for (int m = 0; m < nMol; ++m) {
+        const gf_status st = check_max_vertices(s, "gf_smp_prepare", m, nVertices[m]);
+        if (st != GF_OK) return st;
+        rows += nVertices[m];
+    }
+    const size_t M = (size_t)cfg.max_nVertices, L = (size_t)cfg.nLevels;
+    if (rows > 0x7fffffffll || (unsigned long long)rows * M * (L + 1) > 0x7fffffffull)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare: a covariant batch of %lld vertices: (nLevels + 1) x vertices x max_nVertices activations "
+                                             "must stay below 2^31", rows);
+    begin_batch(s);
+    gfsmp::build_batch_covariant(cfg, nMol, nVertices, adj, feature, &s->lay);
+    const gfsmp::BatchLayout::NeighbourList &nl = s->lay.nb_lists[0];
+    s->lv.assign(cfg.nLevels + 1, DevLevel());
+    Taker t = {s};
+    long long *ptr = nullptr, *tptr = nullptr;
+    int *idx = nullptr, *tidx = nullptr;
+    t.put(&ptr, nl.ptr);
+    t.put(&idx, nl.idx);
+    t.put(&tptr, nl.tptr);
+    t.put(&tidx, nl.tidx);
+    s->cov_ptr = ptr, s->cov_idx = idx, s->cov_tptr = tptr, s->cov_tidx = tidx;
+    t.put(&s->cov_hop, s->lay.cov_hop);
+    t.put(&s->x, s->lay.x);
+    t.alloc(&s->cov_h, (size_t)rows * M * (L + 1));
+    t.alloc(&s->cov_n, (size_t)rows * M * L);
+    t.alloc(&s->cov_ds0, (size_t)rows);
+    t.alloc(&s->g, (size_t)nMol * M);
+    t.alloc(&s->yhat, (size_t)nMol);
+    t.alloc(&s->dy, (size_t)nMol);
+    t.put(&s->top_node_mol, s->lay.nb_vertex_mol);
+    t.put(&s->mol_ptr, s->lay.mol_first_vertex);
+    if (t.st != GF_OK) return t.st;
+    return finish_batch(s, std::max<size_t>(1 << 20, smp_covariant_ws_bytes(nMol, param_count(cfg))));   // (the gradient's partial images)
+}
+
 // null arguments (`have_all` = every pointer given and the count in range) / every graph has 1 .. 4096 vertices, in the entry point's words.
 // nV2: the Y graphs of gf_smp_prepare_pairs, which also come under max_nVertices here, before the batch is copied.
 gf_status check_graph_sizes(const gf_smp *s, const char *who, bool have_all, int n, const int *nV1, const int *nV2 = nullptr) {
@@ -1233,6 +1274,9 @@ gf_status gf_smp_prepare_coulomb(gf_smp *s, int nMol, const int *nVertices, cons
     if (s->cfg.matrix_form && coulomb)
         return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_coulomb: a matrix-form handle (LCNN, GCN_MW) has no Coulomb adjacency");
     if (s->cfg.matrix_form) return gf::smp_matrix_form_prepare(s, nMol, nVertices, adj, feature);
+    if (s->cfg.covariant && coulomb)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_prepare_coulomb: a covariant handle (CGCN_1D, CGCN_2D) has no Coulomb adjacency");
+    if (s->cfg.covariant) return gf::covariant_prepare(s, nMol, nVertices, adj, feature);
     if (s->cfg.neighbourhood) return gf::neighbourhood_prepare(s, nMol, nVertices, adj, feature, nullptr);
     if (s->cfg.per_size()) return gf::smp_theta_prepare(s, nMol, nVertices, adj, feature);   // (first order: no reduced adjacency, coulomb is inert)
     st = gf::choose_plan(s, nMol, nVertices, adj, coulomb);
@@ -1324,6 +1368,35 @@ gf_status gf_smp_matrix_form_molecule_host(const gf_smp_config *cfg, int V, cons
     return GF_OK;
 }
 
+/* Host only: one molecule of a covariant configuration (CGCN_1D, CGCN_2D) as gf_smp_prepare derives it -- lists [V][M + 1] (slot 0 = the
+ * size of N(v), then its members, -1 behind them), hop [V][M] (hop[v][i] = sp[i][v], 255 = unreachable or beyond the molecule) and,
+ * optionally, x [V][F (D + 1)]. */
+gf_status gf_smp_covariant_molecule_host(const gf_smp_config *cfg, int V, const int *adj, const double *feature, int *lists, unsigned char *hop,
+                                         double *x) {
+    if (!cfg || !adj || !feature || !lists || !hop) return fail(nullptr, GF_ERR_INVALID, "gf_smp_covariant_molecule_host: bad argument");
+    gfsmp::Config c;
+    char why[640];
+    const gf_status verdict = gfsmp::resolve_config(cfg, gfsmp::kHandleEntry, &c, why, sizeof why);
+    if (verdict != GF_OK) return fail(nullptr, verdict, "%s", why);
+    if (!c.covariant) return fail(nullptr, GF_ERR_INVALID, "gf_smp_covariant_molecule_host: covariant = 0 is no covariant model");
+    if (V < 1 || V > c.max_nVertices)
+        return fail(nullptr, GF_ERR_INVALID, "gf_smp_covariant_molecule_host: %d vertices, the configuration has max_nVertices = %d", V, c.max_nVertices);
+    gfsmp::BatchLayout B;
+    gfsmp::build_batch_covariant(c, 1, &V, adj, feature, &B);
+    const int M = c.max_nVertices;
+    const gfsmp::BatchLayout::NeighbourList &nl = B.nb_lists[0];
+    for (int v = 0; v < V; ++v) {
+        int *row = lists + (size_t)v * (M + 1);
+        const long long e0 = nl.ptr[(size_t)v], n = nl.ptr[(size_t)v + 1] - e0;
+        row[0] = (int)n;
+        for (int i = 0; i < M; ++i) row[1 + i] = i < n ? nl.idx[(size_t)(e0 + i)] : -1;
+    }
+    for (size_t i = 0; i < (size_t)V * M; ++i) hop[i] = B.cov_hop[i];
+    if (x)
+        for (size_t i = 0; i < B.mols[0].wl.size(); ++i) x[i] = B.mols[0].wl[i];
+    return GF_OK;
+}
+
 /* Host-only graph preparation of ONE molecule (no device needed): receptive fields phi[l][v] as
  * [L+1][V][cap+1] ints (slot 0 = size) and, optionally, the WL features [V][F(D+1)].  Lets the host logic be tested
  * on a CPU-only box and inspected by callers. */
@@ -1338,6 +1411,9 @@ gf_status gf_smp_prepare_molecule_host(const gf_smp_config *cfg, int V, const in
     if (cfg->matrix_form)
         return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: a matrix-form model (LCNN, GCN_MW) has no receptive fields: "
                                              "gf_smp_matrix_form_molecule_host");
+    if (cfg->covariant)
+        return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: a covariant model (CGCN_1D, CGCN_2D) has masks, not capped receptive "
+                                             "fields: gf_smp_covariant_molecule_host");
     if (cfg->neighbourhood)   // (about this call, not the configuration)
         return fail(nullptr, GF_ERR_INVALID, "gf_smp_prepare_molecule_host: a neighbourhood model (NeuralFingerprint, GCN_1D, GCN_2D) has no receptive fields");
     if (refused && cfg->unrestricted)

@@ -18,6 +18,16 @@ class SMPConfig(C.Structure):
                 ("distance_channel", C.c_int), ("readout", C.c_int)]
 
 
+class SMPConfigCovariant(SMPConfig):
+    """gf_smp_config in full: SMPConfig's fields, then the trailing `covariant` (1: CGCN_1D, 2: CGCN_2D).  SMPConfig itself stays the
+    structure up to `readout`: the library's prototypes take a configuration through _lib.ConfigPointer, which hands a structure of an
+    earlier, shorter layout on with a zero tail -- what the C ABI defines as "everything as before"."""
+    _fields_ = [("covariant", C.c_int)]
+
+
+assert C.sizeof(SMPConfigCovariant) == _lib.SMP_CONFIG_BYTES
+
+
 class SMPOmega:
     """Batched SMP_omega (GraphFlow/SMP_omega.h).  Parameters/gradients are one flat fp32 tensor in the reference's
     registration order: H[C, F(D+1)], (K_l[18C, C], b_l[C]) for l = 1..L, W[C]."""
@@ -673,6 +683,52 @@ class LCNN(GCNMW):
         if n != out.size:
             raise RuntimeError("gf_smp_read_activation(%d, %d, %d) returned %d" % (mol, level, v, n))
         return out
+
+
+class CGCN1D(SMPNeighbourhood):
+    """Batched CGCN_1D (GraphFlow/CGCN_1D.h, gf_smp_config.covariant = 1): the covariant graph convolution network on the whole-network
+    vertex level.  A vertex carries one vector of length M = max_nVertices, indexed by the molecule's vertex ids:
+      h_0[v] = e_v <x[v], H>;  n_l[v] = sum of h_{l-1}[u] over N(v) = {u: adj[u, v] > 0};  h_l[v] = LeakyReLU(mask_l(v) * (F_l n_l[v])),
+      mask_l(v) = {i: dist(i, v) <= l};  x = the shell sums up to nDepth;  predict = the sum of the components of sum_v h_L[v], squared loss.
+    Parameters in registration order: H[F'], F_l[M, M] for l = 1..L, F' = nFeatures (nDepth + 1); there is no W.  nLevels = 0 is a model.
+    One forward and one backward launch for all levels.  The optimiser is Momentum: step().  receptive_field(mol, l, v) gives mask_l(v),
+    activation(mol, l, v) h_l[v] [M]."""
+
+    COVARIANT = 1
+
+    def __init__(self, nLevels, max_nVertices, nFeatures, nDepth, ctx=None):
+        self.ctx = ctx or default_context()
+        self.lib = self.ctx.lib
+        self.form, self.nClass = "cgcn_%dd" % self.COVARIANT, 0
+        self.cfg = self.config(nLevels, max_nVertices, nFeatures, nDepth)
+        h = C.c_void_p()
+        self.ctx.check(self.lib.gf_smp_create(self.ctx.handle, C.byref(self.cfg), C.byref(h)))
+        self.handle = h
+        self.n_params = self.lib.gf_smp_param_count(h)
+        self.n_mol = 0
+
+    @classmethod
+    def config(cls, nLevels, max_nVertices, nFeatures, nDepth):
+        return SMPConfigCovariant(nLevels, 1, nFeatures, nDepth, max_nVertices, 0, 0, 0, 0, 0, max_nVertices, covariant=cls.COVARIANT)
+
+    def level_channels(self, level):
+        return self.cfg.max_nVertices
+
+    def activation(self, mol, level, v):
+        """h_level[v] of molecule `mol` after forward(): numpy [max_nVertices]."""
+        out = np.empty(self.cfg.max_nVertices, dtype=np.float32)
+        n = self.lib.gf_smp_read_activation(self.handle, mol, level, v, out.ctypes.data_as(C.c_void_p), out.size)
+        if n != out.size:
+            raise RuntimeError("gf_smp_read_activation(%d, %d, %d) returned %d" % (mol, level, v, n))
+        return out
+
+
+class CGCN2D(CGCN1D):
+    """Batched CGCN_2D (GraphFlow/CGCN_2D.h, gf_smp_config.covariant = 2): CGCN1D with RisiLayer2D as the aggregate,
+      n_l[v][i] = sum over u in N(v) of h_{l-1}[u][i] * (sum over the OTHER members w of N(v) of sum_k h_{l-1}[w][k]),
+    zero with fewer than two neighbours; the exclusive sums are evaluated directly."""
+
+    COVARIANT = 2
 
 
 class SMPClassifier(SMPOmega):

@@ -493,6 +493,35 @@ typedef struct {
      * refuses both read-outs by name (GF_ERR_UNSUPPORTED).  No float atomics; two runs give the same bits.
      * 0 (a zero-initialised tail): everything as described above. */
     int readout;
+    /* covariant = 1, 2: CGCN_1D, CGCN_2D (GraphFlow/CGCN_1D.h, CGCN_2D.h) -- the covariant graph convolution networks, on a whole-network
+     * vertex level (smp_level_covariant.hip).  A vertex carries ONE vector h_l[v] of length M = max_nVertices, indexed by the molecule's
+     * vertex ids; nChanels must be 1.  With sp = the classes' Floyd-Warshall hop counts, x[v] [F'] the shell sums of forms 2 .. 7 and
+     * N(v) = { u : adj[u][v] > 0 } (column v of the adjacency itself, ascending; a set diagonal entry makes v its own neighbour):
+     *   h_0[v]    = e_v <x[v], H>                                                         (VertexRepresentation)
+     *   n_l[v]    = sum_{u in N(v)} h_{l-1}[u]                                            (1: RisiLayer1D)
+     *   n_l[v][i] = sum_{u in N(v)} h_{l-1}[u][i] (sum_{w in N(v), w != u} s_w),  s_u = sum_k h_{l-1}[u][k]      (2: RisiLayer2D)
+     *   h_l[v][i] = LeakyReLU(sp[i][v] <= l ? (F_l n_l[v])[i] : 0), slope 0.01            (MatVecMul, Masking, LeakyReLU)
+     *   graph feature = sum_v h_L[v] [M], predict = the sum of its components (there is no W), loss = 0.5 (predict - target)^2.
+     * The exclusive sums of form 2 are evaluated directly, never as S - s_u.  Parameters in registration, Momentum and save_model order:
+     * H [F'] (drawn as a Vector, divisor 10 F'), then F_1 .. F_L, each [M][M] row-major (a Matrix, divisor 10 M): F' + L M^2 values.
+     * nLevels = 0 is a model.  Positions >= V and positions outside the mask are zero in every h_l, so a level only touches F_l[:V, :V];
+     * the classes' reverse pass also puts gradient on such positions, which the mask one level down and VertexRepresentation::backward
+     * discard: the device never forms it.
+     * Required, else GF_ERR_INVALID (gf_smp_config_param_count answers 0): covariant in 0 .. 2, every other form selector 0 (first_order,
+     * steerable_2d, unrestricted, neighbourhood, matrix_form, distance_channel, readout, physics, nContractions, custom_matmul),
+     * nChanels = 1, nLevels in 0 .. 64, nFeatures >= 1, nDepth >= 0, 1 <= max_nVertices <= 75 (the kernels keep a molecule's whole
+     * network in LDS: 4 (7 M (M | 1) + 2 M + 8) + M M bytes within 160 KiB).  max_receptive_field, has_WL_ordering and max_Radius are
+     * not read.  gf_smp_prepare takes the molecules (one above max_nVertices is GF_ERR_INVALID); gf_smp_prepare_distance, _pairs and
+     * gf_smp_forward_host answer GF_ERR_UNSUPPORTED, as do the five refusals of forms 1 - 7 (classifier, gf_smp_set_grad_allreduce(1),
+     * gf_smp_dropout_masks, gf_smp_backward_features, gf_smp_prepare_coulomb with a matrix).  gf_smp_read_activation(mol, l, v) returns
+     * h_l[v] [M]; gf_smp_receptive_field(mol, l, v) the set { u : sp[u][v] <= l }, ascending; gf_smp_feature_width M; gf_smp_level_sizes
+     * nodes = rows = the batch's vertices; the optimiser is Momentum (gf_smp_momentum_step); checkpoints are the classes' files.
+     * One forward launch (cov_network_fwd: a workgroup per molecule, all levels, h_{l-1} / h_l ping-pong and F_l[:V, :V] in LDS) and one
+     * backward launch (cov_network_bwd: a workgroup per chunk of molecules -- the chunks depend on nMol only -- levels in reverse, dh_{l-1}
+     * gathered over the transposed lists) plus one fold of at most 256 partial gradient images in ascending order.  No matrix pipe, no
+     * float atomics; two runs give the same bits.
+     * 0 (a zero-initialised tail): everything as described above. */
+    int covariant;
 } gf_smp_config;
 gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out);
 /* gf_smp_param_count of the handle gf_smp_create would build from cfg (0 on a configuration it would refuse).  Host only. */
@@ -760,6 +789,31 @@ gf_status gf_smp_pair_readout_ex_f32(gf_ctx *ctx, int H, int nV, int nPairs, con
                                      const float *target, float *g, float *yhat, float *loss, float *dy, float *dW, float *dhL);
 gf_status gf_smp_gram_readout_ex_f32(gf_ctx *ctx, int H, int nV, int nMol, const float *hL, const int *mol_ptr, const float *adj, float *gram,
                                      float *loss, float *dhL);
+/* The covariant vertex level (gf_smp_config.covariant = 1, 2: CGCN_1D, CGCN_2D), its two network kernels as stand-alone operators on
+ * caller-supplied operands (tests/test_cgcn_ops_gpu.py).  Device pointers, fp32, asynchronous on the context's stream.  form = 1 (the sum
+ * aggregate) or 2 (RisiLayer2D); L = 0 .. 64 levels; M = 1 .. 75, the length of a vertex's vector and the side of F_l; nV vertices in nMol
+ * molecules, molecule m = the vertices mol_ptr[m] .. mol_ptr[m + 1] - 1 (int [nMol + 1]; at most M each; a molecule may be empty).
+ *   nb_ptr long long [nV + 1], nb_idx int: the column neighbour lists N(v) as GLOBAL vertex ids of v's own molecule, strictly ascending
+ *             (the order the aggregate adds them in); nb_tptr / nb_tidx: the transposed lists { v : u in N(v) }, likewise.
+ *   hop       unsigned char [nV][M]: hop[v][i] = the hop count sp[i][v] of position i < V (255: unreachable); position i of vertex v is
+ *             inside the mask of level l where hop[v][i] <= l.  Entries i >= V are not read.
+ *   s0 [nV]   the level-0 scalars <x[v], H>;  F [L][M][M] the stacked F_l, row-major;  target [nMol] or NULL (0).
+ * forward:  h [L + 1][nV][M] = every h_l[v], n [L][nV][M] = every n_l[v] (l = 1 .. L at index l - 1), positions >= V written as zeros;
+ *           g [nMol][M] the graph features, yhat [nMol] their component sums, loss [nMol] = 0.5 (yhat - target)^2 (NULL: not stored),
+ *           dy [nMol] = yhat - target (NULL: not stored).  One launch, one workgroup per molecule; every sum in a fixed order.
+ * backward: from h, n and dy [nMol] of a forward: dF [L][M][M] += the gradients of the F_l, ds0 [nV] = the gradients of the level-0 scalars.
+ *           One launch over min(nMol, 256) chunks of ceil(nMol / chunks) consecutive molecules and one fold of the chunks' partial images in
+ *           ascending order (the context's workspace holds them); dh_{l-1} is gathered over the transposed lists.  No float atomics: two
+ *           calls give the same bits.
+ * GF_ERR_INVALID before anything is launched: form, L, M, nV or nMol out of range, a missing operand, and -- checked on the host, one
+ * blocking copy per call -- a table that does not start at 0, decreases or leaves its range, a molecule above M vertices (named), a
+ * list entry outside its vertex's molecule (named).  The context stays usable after a refusal. */
+gf_status gf_smp_covariant_forward_ex_f32(gf_ctx *ctx, int form, int L, int M, int nV, int nMol, const int *mol_ptr, const long long *nb_ptr,
+                                          const int *nb_idx, const unsigned char *hop, const float *s0, const float *F, const float *target,
+                                          float *h, float *n, float *g, float *yhat, float *loss, float *dy);
+gf_status gf_smp_covariant_backward_ex_f32(gf_ctx *ctx, int form, int L, int M, int nV, int nMol, const int *mol_ptr, const long long *nb_ptr,
+                                           const int *nb_idx, const long long *nb_tptr, const int *nb_tidx, const unsigned char *hop,
+                                           const float *F, const float *h, const float *n, const float *dy, float *dF, float *ds0);
 /* The third-order pool (gf_smp_config.neighbourhood = 6, 7), its two kernels as stand-alone operators on caller-supplied operands, for
  * per-vertex tests (tests/test_smp_third_order_ops_gpu.py).  Device pointers, fp32, asynchronous on the context's stream.  H = 1 .. 64
  * channels, nV vertices; lists are CSR: ptr long long [nV + 1] from 0, idx int members in [0, nV), tptr / tidx the transposed list
@@ -801,6 +855,13 @@ gf_status gf_smp_rowlist_wgrad_ex_f32(gf_ctx *ctx, int R, int slots, int Cin, in
  * with V == max_nVertices one of whose vertices reaches fewer than nNeighbors vertices (see gf_smp_config.matrix_form). */
 gf_status gf_smp_matrix_form_molecule_host(const gf_smp_config *cfg, int V, const int *adj, const double *feature, int *order, int *sequence,
                                            double *norm_adj);
+/* Host only: one molecule of a covariant configuration (covariant = 1, 2) as gf_smp_prepare derives it.  lists int [V][M + 1], M =
+ * max_nVertices: slot 0 = the size of N(v) = { u : adj[u][v] > 0 }, then its members in ascending order, -1 behind them; hop unsigned
+ * char [V][M]: hop[v][i] = the hop count sp[i][v] (255: unreachable, or i beyond the molecule) -- position i of vertex v is inside the mask
+ * of level l where hop[v][i] <= l; x (optional) double [V][nFeatures (nDepth + 1)], the shell sums.  GF_ERR_INVALID: a configuration
+ * gf_smp_create would refuse (its message), covariant = 0, V outside 1 .. max_nVertices, a missing argument. */
+gf_status gf_smp_covariant_molecule_host(const gf_smp_config *cfg, int V, const int *adj, const double *feature, int *lists, unsigned char *hop,
+                                         double *x);
 /* Device memory of the handle's buffer pool: bytes held by the current batch, and bytes the pool keeps in total (idle
  * blocks included).  Sizing aid for batch selection (GraphFlow has no counterpart: its tensors live in host `new[]`). */
 gf_status gf_smp_device_bytes(const gf_smp *smp, size_t *in_use, size_t *reserved);
