@@ -143,6 +143,7 @@ PROTOTYPES.update({
     "gf_smp_load_model": (_i, [_vp, _vp, C.c_char_p]),
     "gf_smp_set_fused": (_i, [_vp, _i]),
     "gf_smp_device_bytes": (_i, [_vp, _vp, _vp]),
+    "gf_smp_single_vertex_launches": (C.c_longlong, [_vp]),
     "gf_smp_level_products_f32": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "gf_smp_level_wgrad_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "gf_smp_level_products_ex_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),

@@ -342,9 +342,13 @@ __global__ void readout_molecules(const float *__restrict__ vf, const int *__res
 }
 
 // dW[f] += sum_m dy[m] g[m][f]   (InnerProduct.h:48-53, second operand)
+// One workgroup (C outputs): a thread's run of molecules m = rr, rr + rl, .. is REQUESTED sixteen at a time and summed in the run's
+// order -- the same sums as a plain loop, which waited for one molecule's two loads per step (64 dependent round trips at 1,024
+// molecules and C = 64).
 __global__ __launch_bounds__(1024) void readout_dW(const float *__restrict__ dy, const float *__restrict__ g, float *__restrict__ dW,
                                                    int C, int nMol) {
     __shared__ float red[1024];
+    constexpr int kAhead = 16;
     const int nt = (int)blockDim.x;
     const int lanes = (C < nt) ? C : nt, rl = nt / lanes;
     const int f0 = threadIdx.x % lanes, rr = threadIdx.x / lanes;
@@ -352,7 +356,19 @@ __global__ __launch_bounds__(1024) void readout_dW(const float *__restrict__ dy,
         const int f = fb + f0;
         float acc = 0.f;
         if (f < C && rr < rl)
-            for (int m = rr; m < nMol; m += rl) acc += dy[m] * g[(size_t)m * C + f];
+            for (int m0 = rr; m0 < nMol; m0 += kAhead * rl) {
+                float d[kAhead], v[kAhead];
+#pragma unroll
+                for (int k = 0; k < kAhead; ++k) {
+                    const int m = m0 + k * rl;
+                    const bool in = m < nMol;
+                    d[k] = in ? dy[m] : 0.f;
+                    v[k] = in ? g[(size_t)m * C + f] : 0.f;
+                }
+#pragma unroll
+                for (int k = 0; k < kAhead; ++k)
+                    if (m0 + k * rl < nMol) acc += d[k] * v[k];
+            }
         red[threadIdx.x] = acc;
         __syncthreads();
         if (rr == 0 && f < C) {
@@ -1253,6 +1269,10 @@ gf_status gf_smp_set_fused(gf_smp *s, int on) {
     s->forwarded = false;
     return GF_OK;
 }
+
+/* introspection for parity tests: how often this handle launched the single-vertex-source kernels of level 1 (the launch names are the
+ * general kernels', so the timing table cannot tell) */
+long long gf_smp_single_vertex_launches(const gf_smp *s) { return s ? s->single_launches : 0; }
 
 /* introspection for parity tests: receptive field phi_level(v) of molecule mol; returns its size */
 int gf_smp_receptive_field(const gf_smp *s, int mol, int level, int v, int *out, int capacity) {

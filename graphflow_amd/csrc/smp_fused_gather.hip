@@ -264,6 +264,98 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// A level whose sources are ALL single vertices (level 1: the sources are the level-0 nodes).  Every source is one item of the list
+// and has one row (p = q = 0) of C / 4 = NL channel quads: as a wave of its own it runs with NL of 64 lanes live and pays one memory
+// round trip per consumer for that quarter (at C = 64) of a wave's requests.  Here a wave takes 64 / NL CONSECUTIVE items, NL lanes
+// each.  What was wave-uniform per source is now uniform per lane group only, so
+//   * headers and records come by ordinary (per-lane, group-broadcast) loads, all of them one consumer ahead, and
+//   * one buffer resource spans each table of the whole level: a consumer's base joins the lane offset (the launcher takes this kernel
+//     only while those offsets stay below kOorAll);
+//   * the loop runs to the longest consumer list of the wave; a group that is through requests nothing (every offset out of range)
+//     and adds nothing.
+// Per source the consumers come in the same order and the sums are the expression of gather_source<1, 1>, term for term.
+// ---------------------------------------------------------------------------------------------------------------
+// The offset of a lane that requests nothing: beyond every whole-level table this kernel is launched on (the launcher checks
+// bytes < kOorAll).  Bit 31 is set on purpose: a raw buffer load range-checks voffset + the instruction's immediate as an UNSIGNED
+// 32-bit byte offset against num_records, so the value is 2 GiB, not negative, whatever the builtin's `int` parameter suggests; the
+// block constants added to it (at most 3 C 4 + 12 bytes: static_assert below) cannot wrap it, and an immediate the compiler folds
+// out of the sum is added by the hardware as an unsigned 12-bit field -- the same sum.
+constexpr unsigned kOorAll = 0x80000000u;
+static_assert((unsigned long long)kOorAll + 3ull * 64 * 4 + 16 <= 0xffffffffull, "block offsets added to kOorAll stay below 2^32 (C <= 64)");
+template <int NL>
+__global__ __launch_bounds__(256) void smp_bwd_gather_single(GF_GATHER_PARAMS, const int2 *__restrict__ items, int n_items, unsigned bytesT,
+                                                             unsigned bytesV, unsigned bytesS) {
+    constexpr int PER = 64 / NL;   // sources per wave
+    unsigned blk;
+    {
+        const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, x = blockIdx.x % 8;
+        blk = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + blockIdx.x / 8;
+    }
+    const int lane = (int)(threadIdx.x & 63);
+    const int i0 = (int)(blk * 4 + (threadIdx.x >> 6)) * PER;
+    if (i0 >= n_items) return;   // (wave-uniform)
+    const int i = i0 + lane / NL;
+    const bool live = i < n_items;   // (the ragged last wave)
+    const int w = live ? items[i].x : 0;
+    const int cw = prev_center[w];
+    const int f4b = 16 * (lane % NL), C4 = C * 4, ldtb = T_COLS * C4;
+    const long long c0r = cons_ptr[w], c1r = cons_ptr[w + 1];
+    const int cnt = live ? (int)(c1r - c0r) : 0;
+    // (a group without consumers reads entry 0 of the tables, which exists whenever any lane of the wave enters the loop)
+    const long long c0 = cnt > 0 ? c0r : 0, ioff0 = cnt > 0 ? cons_inv_off[c0r] : 0, qb = cnt > 0 ? cons_qbase[w] : 0;
+    f4 acc = splat(0.f), accd = splat(0.f), accc = splat(0.f);
+    if (live) {
+        const float *dfd = dFdc + (size_t)prev_pair[w] * 2 * C;
+        accd = ld4(dfd + (f4b >> 2));
+        accc = ld4(dfd + C + (f4b >> 2));
+    }
+    const __amdgpu_buffer_rsrc_t rT = make_rsrc(dT, bytesT), rV = make_rsrc(dVt, bytesV), rS = make_rsrc(dSt, bytesS);
+    int4 h0 = make_int4(0, 0, 0, 0), h1 = h0, rec = h0;
+    int b = -1;
+    if (__builtin_amdgcn_ballot_w64(cnt > 0) != 0) {
+        h0 = G.hdr[2 * c0], h1 = G.hdr[2 * c0 + 1], rec = G.qrec[qb];
+        b = inv[ioff0];
+    }
+    for (int k = 0; __builtin_amdgcn_ballot_w64(k < cnt) != 0; ++k) {
+        const bool on = k < cnt;
+        const int kn = (k + 1 < cnt) ? k + 1 : (cnt > 0 ? cnt - 1 : 0);
+        const int4 n0 = G.hdr[2 * (c0 + kn)], n1 = G.hdr[2 * (c0 + kn) + 1], recn = G.qrec[qb + kn];
+        const int bn = inv[ioff0 + kn];
+        const int s = h0.x, a = h0.y;
+        const long long urow = ((long long)h0.w << 32) | (unsigned)h0.z, upb = ((long long)h1.y << 32) | (unsigned)h1.x;
+        const unsigned baseT = (unsigned)(urow * ldtb), baseV = (unsigned)(upb * 4 * C4), baseS = (unsigned)h1.z * 4u * (unsigned)C4;
+        const bool has = on && b >= 0;
+        const unsigned tab = has ? baseT + (unsigned)((a * s + b) * ldtb + f4b) : kOorAll;   // row (a, b) of the consumer's tables
+        const unsigned va = has ? baseV + (unsigned)(a * 4 * C4 + f4b) : kOorAll, vb = has ? baseV + (unsigned)(b * 4 * C4 + f4b) : kOorAll;
+        const unsigned vs = has ? baseS + (unsigned)f4b : kOorAll, vd = (has && cw == 0) ? baseS + (unsigned)f4b : kOorAll;
+        const unsigned tb = has ? baseT + (unsigned)(b * s * ldtb + f4b) + (unsigned)rec.x : kOorAll;   // row (b, c)
+        const f4 l0 = gbuf_ld4_once(rT, (int)(tab + T_SAB * C4)), g5 = gbuf_ld4_once(rT, (int)(tab + T_T6 * C4));
+        const f4 l1 = buf_ld4(rV, (int)va, 0), l4 = buf_ld4(rV, (int)(va + 2 * C4), 0);
+        const f4 l2 = buf_ld4(rV, (int)(vb + C4), 0), z2 = buf_ld4(rV, (int)(vb + 3 * C4), 0);
+        const f4 l3 = buf_ld4(rS, (int)vs, 0), l5 = buf_ld4(rS, (int)(vs + 2 * C4), 0);
+        const f4 l6 = buf_ld4(rS, (int)(vd + C4), 0), l7 = buf_ld4(rS, (int)(vd + 3 * C4), 0);
+        const f4 y = buf_ld4(rT, (int)(tb + T_SBC * C4), 0), g9 = buf_ld4(rT, (int)(tb + T_T10 * C4), 0);
+        const f4 x = ((l0 + l1) + (l2 + l3)) + l6;
+        const float rho = __int_as_float(rec.y), m = __int_as_float(rec.z), mra = __int_as_float(rec.w);
+        if (on) {
+            acc += m * (x + y) + g5 * rho + g9 * mra;
+            accd += (l4 + l5) + l7;
+            accc += z2;
+        }
+        h0 = n0;
+        h1 = n1;
+        rec = recn;
+        b = bn;
+    }
+    if (live) {
+        f4 o = acc;
+        o += accd;   // (q == p: the one position)
+        if (cw == 0) o += accc;
+        gf_st_s<64>(reinterpret_cast<f4 *>(dfprev + prev_row[w] * C + (f4b >> 2)), o);
+    }
+}
+
 }  // namespace
 
 gf_status smp_build_gather_records(gf_smp *s, int l, hipStream_t stream) {
@@ -297,7 +389,22 @@ gf_status smp_fused_gather_backward(gf_smp *s, int l) {
     gf_ctx *ctx = s->ctx;
     const GatherTables G = {d.cons_hdr, d.cons_qrec};
     const int n_items = (int)(hp.gather_items.size() / 2);
-    if (n_items > 0)
+    // single-vertex sources only (level 1): 64 / (C / 4) sources per wave, while one buffer resource per table reaches the whole level
+    const size_t bT = (size_t)h.rows * T_COLS * C * 4, bV = (size_t)h.pairs * 4 * C * 4, bS = (size_t)h.nNodes * 4 * C * 4;
+    const bool single = n_items > 0 && !hp.buckets.empty() && hp.buckets.back().s == 1 && (C == 64 || C == 32 || C == 16) &&
+                        bT < kOorAll && bV < kOorAll && bS < kOorAll && smp_level1_switch();
+    if (single) {
+#define GF_GATHER_SINGLE(NL_)                                                                                                              \
+    GF_LAUNCH(ctx, "smpf_bwd_gather", smp_bwd_gather_single<NL_>, dim3((unsigned)((n_items + 4 * (64 / NL_) - 1) / (4 * (64 / NL_)))),       \
+              dim3(256), 0, dT, d.dVt, d.dSt, pv.df, d.dFdc, pv.node_s, pv.node_row, pv.node_pair, pv.node_center, d.cons_ptr,              \
+              d.cons_inv_off, d.cons_qbase, d.inv, G, C, reinterpret_cast<const int2 *>(pv.gather_items), n_items, (unsigned)bT,            \
+              (unsigned)bV, (unsigned)bS)
+        if (C == 64) GF_GATHER_SINGLE(16);
+        else if (C == 32) GF_GATHER_SINGLE(8);
+        else GF_GATHER_SINGLE(4);
+#undef GF_GATHER_SINGLE
+        ++s->single_launches;
+    } else if (n_items > 0)
         GF_LAUNCH(ctx, "smpf_bwd_gather", smp_bwd_gather_all, dim3((unsigned)((n_items + 3) / 4)), dim3(256), 0, dT, d.dVt, d.dSt, pv.df,
                   d.dFdc, pv.node_s, pv.node_row, pv.node_pair, pv.node_center, d.cons_ptr, d.cons_inv_off, d.cons_qbase, d.inv, G, C,
                   reinterpret_cast<const int2 *>(pv.gather_items), n_items);

@@ -593,6 +593,81 @@ __global__ __launch_bounds__(kThreads, 3) void smp_tables_bwd(const float *__res
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// tables-forward of a level whose sources are ALL single vertices (level 1: the sources are the level-0 nodes).  Then
+// P[a, b, c] = f_0[src(n, b)] where a == b == c and 0 elsewhere, and every output of smp_tables_fwd_w<NI, true, true, LPC> is a copy of
+// a row of f_0, that row times r[b], a zero, or -- the per-node scalars -- the sum of the node's source rows in the order of b:
+//   T[(b, b)] = [f | f | r f | r f],  Vt[(n, b)] = [f | f | f | f],  scal[(n, b)] = [f | f | f | f],  St[n] = 4 x sum_b f
+// and the zeros of the rows (a, b), a != b, under the policy of that kernel (none where the level keeps its zeros; S_bc / T10 only on
+// the rows flagged as covered).  The general kernel spends a workgroup, its staged maps and two barriers per node on this; here LPC
+// lanes take a (node, b) pair -- no LDS, no barrier -- and behind the pairs one lane group per node forms St.  The sums of the general
+// kernel have one non-zero term each, so the values are its values (a zero may differ in sign: it adds its term to +0).
+// One difference on non-finite data: the general kernel forms St with batched_sum, which pads a batch of eight with 0 x (a re-read
+// row) -- NaN if f_0 holds an Inf or a NaN there -- and this kernel skips the padding terms: with finite f_0 the same bits, with an
+// Inf or NaN in f_0 St may differ (both are already non-finite downstream of that row).
+// C = 4 LPC channels (one window).
+// ---------------------------------------------------------------------------------------------------------------
+template <int LPC>
+__global__ __launch_bounds__(256) void smp_tables_fwd_single(const float *__restrict__ fprev, const float *__restrict__ rsum, float *__restrict__ T,
+                                                             float *__restrict__ Vt, float *__restrict__ scal, float *__restrict__ St,
+                                                             const long long *__restrict__ pair_src_row, const int *__restrict__ pair_node,
+                                                             const int *__restrict__ node_s, const long long *__restrict__ node_row,
+                                                             const long long *__restrict__ node_pair, long long pair_lo, int npairs, int node_lo,
+                                                             int nnodes, int zeros_kept, const unsigned char *__restrict__ rowflag) {
+    constexpr int C = 4 * LPC, GPB = 256 / LPC;
+    constexpr size_t ldt = (size_t)T_COLS * C;
+    const int fl = (int)threadIdx.x % LPC;
+    const long long g = (long long)blockIdx.x * GPB + (int)threadIdx.x / LPC;
+    if (g < npairs) {
+        const long long pe = pair_lo + g;
+        const int n = pair_node[pe], N = node_s[n];
+        const long long pairbase = node_pair[n], rowbase = node_row[n];
+        const int b = (int)(pe - pairbase);
+        const f4 v = ld4(fprev + pair_src_row[pe] * C + 4 * fl);
+        const f4 vz = v + splat(0.f), rz = rsum[pe] * v + splat(0.f);   // (as the sums that start from +0 leave them)
+        const bool skip_bc = zeros_kept && rowflag;
+        float *Tn = T + (size_t)rowbase * ldt + 4 * fl;
+        for (int x = 0; x < N; ++x) {
+            if (x == b) continue;
+            if (!zeros_kept) {   // row (a = x, b): no image
+                st4(Tn + ((size_t)x * N + b) * ldt + T_SAB * C, splat(0.f));
+                st4(Tn + ((size_t)x * N + b) * ldt + T_T6 * C, splat(0.f));
+            }
+            if (!skip_bc || (rowflag[rowbase + b * N + x] & 2)) {   // row (b, c = x)
+                st4(Tn + ((size_t)b * N + x) * ldt + T_SBC * C, splat(0.f));
+                st4(Tn + ((size_t)b * N + x) * ldt + T_T10 * C, splat(0.f));
+            }
+        }
+        float *td = Tn + ((size_t)b * N + b) * ldt;
+        st4(td + T_SAB * C, vz);
+        st4(td + T_T6 * C, rz);
+        if (!skip_bc || (rowflag[rowbase + b * N + b] & 2)) {
+            st4(td + T_SBC * C, vz);
+            st4(td + T_T10 * C, rz);
+        }
+        float *vt = Vt + (size_t)pe * 4 * C + 4 * fl, *sc = scal + (size_t)pe * 4 * C + 4 * fl;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            st4(vt + k * C, vz);
+            st4(sc + k * C, k == 3 ? v : vz);   // (block 3 is the loaded row itself)
+        }
+    } else if (g < (long long)npairs + nnodes) {
+        const int n = node_lo + (int)(g - npairs), N = node_s[n];
+        const long long pairbase = node_pair[n];
+        f4 s = splat(0.f);
+        for (int b0 = 0; b0 < N; b0 += 8) {
+            f4 t[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) t[j] = ld4(fprev + pair_src_row[pairbase + (b0 + j < N ? b0 + j : 0)] * C + 4 * fl);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (b0 + j < N) s += t[j];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) st4(St + (size_t)n * 4 * C + k * C + 4 * fl, s);
+    }
+}
+
 template <int LPC>
 size_t tables_bwd_lds(int N) {
     constexpr int CW = 4 * LPC;
@@ -631,6 +706,17 @@ gf_status launch_tables_fwd_class(gf_smp *s, int l, const SizeClass &c, bool fol
         if constexpr (LPC == 16)
             GF_LAUNCH(ctx, tables_fwd_name<NI>(), (smp_tables_fwd_w<NI, false>), grid, dim3(kThreads), lds, s->lv[l - 1].f, d.rsum, d.Q, d.Vt, d.scal,
                       d.pair_src_row, d.pair_src_s, d.pi, d.tf_recs + 2 * (size_t)n_lo, C, nwin, flags, (const unsigned char *)nullptr, (float *)nullptr);
+        return GF_OK;
+    }
+    // a level of single-vertex sources (level 1) at one window of channels: a lane group per (node, b) pair (GF_SMP_LEVEL1=0: the kernel below)
+    const std::vector<gfsmp::Bucket> &src = s->lay.level[l - 1].buckets;
+    if (!src.empty() && src.back().s == 1 && C == CW && smp_level1_switch()) {
+        const long long work = (c.hi - c.lo) + (n_hi - n_lo);
+        constexpr int GPB = 256 / LPC;
+        GF_LAUNCH(ctx, tables_fwd_name<NI>(), smp_tables_fwd_single<LPC>, dim3((unsigned)((work + GPB - 1) / GPB)), dim3(256), 0, s->lv[l - 1].f, d.rsum,
+                  d.Q, d.Vt, d.scal, d.St, d.pair_src_row, d.pair_node, d.node_s, d.node_row, d.node_pair, (long long)c.lo, (int)(c.hi - c.lo), n_lo,
+                  n_hi - n_lo, flags, flags ? d.rowflag : (const unsigned char *)nullptr);
+        ++s->single_launches;
         return GF_OK;
     }
     const int nwv = kThreads / 64;

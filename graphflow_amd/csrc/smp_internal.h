@@ -321,6 +321,7 @@ struct gf_smp : gf_smp_batch {
     gf_ctx *ctx = nullptr;
     gfsmp::Config cfg;    // what the device computes with: nChanels padded to 32 / 64 / a multiple of 4 (gf_smp_create, round 4)
     bool bwd_consumed = false;   // an op-by-op level's reverse sweep has overwritten its Q since the last forward
+    long long single_launches = 0;   // launches of smp_tables_fwd_single / smp_bwd_gather_single so far (gf_smp_single_vertex_launches)
     gfsmp::Config ucfg;   // the caller's configuration: the layout of parameters, gradients, features and activations at the C ABI
     float *pad_p = nullptr, *pad_g = nullptr, *pad_feat = nullptr;   // padded copies (cfg.nChanels != ucfg.nChanels)
     // Round 5, SMP_2D_ver6 (RisiContraction_10) on the fused RisiContraction_18 level: != 0 = the caller's channel count C.  With a symmetric
@@ -386,6 +387,10 @@ inline bool smp_panel_channels(int C) { return C == 64 || C == 32 || C == 16; }
 // only then: a handle prepared under =0 is what it was before the path existed -- and per call: a pass runs the sub-block kernels when
 // neither saw the 0.
 inline bool smp_c128_switch() { return !env_is("GF_SMP_C128", '0'); }
+// GF_SMP_LEVEL1=0 (read per call: the parity tests switch it): a fused level whose sources are all single vertices (level 1) runs the
+// general kernels -- smp_tables_fwd_w, a workgroup per node, and smp_bwd_gather_all, a wave per source -- instead of
+// smp_tables_fwd_single (smp_fused_tables.hip) and smp_bwd_gather_single (smp_fused_gather.hip)
+inline bool smp_level1_switch() { return !env_is("GF_SMP_LEVEL1", '0'); }
 // The reverse sweep of fused level l takes LeakyReLU'(f_l) from the sign words this pass's panel combine-forward left (DevLevel::sgn)
 // instead of reading f_l.  64 channels; not where f_l's upper channels were overwritten after combine-forward (dup_level: SMP_2D_ver6 on
 // the 18-slice level).  GF_SMP_SIGN_MASK=0 (read per call: the parity test switches it): f_l is read, dz is stored and read, as before.

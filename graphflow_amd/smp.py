@@ -162,6 +162,10 @@ class SMPOmega:
         self.ctx.check(self.lib.gf_smp_device_bytes(self.handle, C.byref(used), C.byref(res)))
         return int(used.value), int(res.value)
 
+    def single_vertex_launches(self):
+        """Launches so far of the level-1 kernels for single-vertex sources (they run under the general kernels' launch names)."""
+        return int(self.lib.gf_smp_single_vertex_launches(self.handle))
+
     def receptive_field(self, mol, level, v):
         buf = (C.c_int * 4096)()
         n = self.lib.gf_smp_receptive_field(self.handle, mol, level, v, buf, 4096)

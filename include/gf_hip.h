@@ -865,6 +865,10 @@ gf_status gf_smp_covariant_molecule_host(const gf_smp_config *cfg, int V, const 
 /* Device memory of the handle's buffer pool: bytes held by the current batch, and bytes the pool keeps in total (idle
  * blocks included).  Sizing aid for batch selection (GraphFlow has no counterpart: its tensors live in host `new[]`). */
 gf_status gf_smp_device_bytes(const gf_smp *smp, size_t *in_use, size_t *reserved);
+/* Introspection for tests: launches so far of the kernels a fused level takes when all its sources are single vertices (level 1 of
+ * SMP_omega at 64 / 32 / 16 channels: one per size class in tables-forward, one in the backward gather); they run under the general
+ * kernels' launch names.  GF_SMP_LEVEL1=0 keeps it where it is.  0 for a null handle. */
+long long gf_smp_single_vertex_launches(const gf_smp *smp);
 /* Host-pointer mode of the driver (what graphflow_amd/host/SMP_omega_hip.h uses): the handle owns the model -- a device
  * parameter buffer and its gradient.  Wherever the entry points of this section take `params` / `grads`, NULL selects the
  * handle-owned buffers.  gf_smp_forward_host runs gf_smp_forward on them and returns per-molecule results as doubles
