@@ -144,11 +144,14 @@ PROTOTYPES.update({
     "gf_smp_set_fused": (_i, [_vp, _i]),
     "gf_smp_device_bytes": (_i, [_vp, _vp, _vp]),
     "gf_smp_single_vertex_launches": (C.c_longlong, [_vp]),
+    "gf_smp_empty_row_calls": (C.c_longlong, [_vp]),
+    "gf_smp_level_projected_f32": (_i, [_vp, _i, _vp]),
     "gf_smp_level_products_f32": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "gf_smp_level_wgrad_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "gf_smp_level_products_ex_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "gf_smp_level_wgrad_ex_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gf_smp_level_row_classes": (_i, [_vp, _i, _vp, _vp]),
+    "gf_smp_level_row_classes_ex": (_i, [_vp, _i, _vp, _vp, _i]),
     "gf_smp_2d_ver5_rows_ex_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_float, _i, _vp]),
     "gf_smp_2d_ver5_cols_ex_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "gf_smp_2d_ver5_wgrad_ex_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

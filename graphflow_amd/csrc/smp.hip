@@ -1273,6 +1273,16 @@ gf_status gf_smp_set_fused(gf_smp *s, int on) {
 /* introspection for parity tests: how often this handle launched the single-vertex-source kernels of level 1 (the launch names are the
  * general kernels', so the timing table cannot tell) */
 long long gf_smp_single_vertex_launches(const gf_smp *s) { return s ? s->single_launches : 0; }
+/* ... and how many level passes skipped the projected matrix of their empty rows (FusedRoute::skip_empty) */
+long long gf_smp_empty_row_calls(const gf_smp *s) { return s ? s->empty_row_calls : 0; }
+gf_status gf_smp_level_projected_f32(gf_smp *s, int level, float *out) {
+    if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
+    if (!s->prepared || !s->forwarded || level < 1 || level > s->cfg.nLevels || !out || (int)s->lv.size() <= level)
+        return fail(s->ctx, GF_ERR_INVALID, "gf_smp_level_projected_f32: bad argument, or no forward pass yet");
+    if (s->cfg.nChanels != s->ucfg.nChanels) return fail(s->ctx, GF_ERR_INVALID, "gf_smp_level_projected_f32: a handle computed at padded channels");
+    GF_HIP_TRY(s->ctx, hipSetDevice(s->ctx->device));
+    return gf::smp_fused_copy_projected(s, level, out);
+}
 
 /* introspection for parity tests: receptive field phi_level(v) of molecule mol; returns its size */
 int gf_smp_receptive_field(const gf_smp *s, int mol, int level, int v, int *out, int capacity) {

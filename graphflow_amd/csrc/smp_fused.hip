@@ -307,6 +307,15 @@ FusedRoute fused_route(const gf_smp *s, int l) {
     r.gather = smp_fused_gather_enabled(s, l);
     r.fuse_small = !env_is("GF_SMP_FUSE_SMALL", '0');
     r.sign_mask = smp_sign_mask(s, l);
+    // The EMPTY rows of the level -- none of bits 31 / 30 / 29 of trowf: no data in any block of T, 17 % of cfg3's rows -- have exact zeros
+    // in O and a dO nobody reads.  Neither is stored or read where EVERY writer and reader of the region in this call masks them: the
+    // split forward products, the two panel combine kernels, smp_wgrad_split on the level's maxima (exact bounds scan all of dO) and the
+    // masked backward products (classed: the driver's lists leave the rows out; unclassed: dO is read where a source covers the row).
+    // Excluded: the workgroup combine kernels (nodes above 32 positions), slice dropout, the extra products and transposed channels of
+    // the embedded `_10` / `_50` models, every other channel count.  GF_SMP_EMPTY_ROWS=0 (read per call): everything moves as before.
+    r.skip_empty = C == 64 && r.panels && r.split && r.readers_mask && r.panel_combine && r.gather && r.skip_zero_rows && !r.drop && !s->n_extra &&
+                   !s->dup_channels && !s->lay.level[l].buckets.empty() && s->lay.level[l].buckets.back().s <= 32 && d.pan_live && d.rowcls && s->wbound && d.dzmax &&
+                   !env_is("GF_SMP_EMPTY_ROWS", '0');
     return r;
 }
 
@@ -424,6 +433,13 @@ static gf_status dropout_scale(gf_smp *s, int l, float *Vt, float *St) {
     return GF_OK;
 }
 
+gf_status smp_fused_copy_projected(gf_smp *s, int l, float *out) {
+    if (!s->lv[l].Q || !s->lv[l].fwd_c64) return fail(s->ctx, GF_ERR_INVALID, "level %d has no compact projected matrix (no fused forward on the row-panel kernels)", l);
+    const size_t bytes = (size_t)s->lay.level[l].rows * 2 * s->cfg.nChanels * sizeof(float);
+    GF_HIP_TRY(s->ctx, hipMemcpyAsync(out, level_O(s, l), bytes, hipMemcpyDeviceToDevice, s->ctx->stream));
+    return GF_OK;
+}
+
 // ---- the forward pass of a level, step by step ----
 static gf_status fwd_zero_rows(gf_smp *s, int l, const FusedRoute &r) {
     s->lv[l].t_zeros = r.skip_zero_rows;
@@ -483,7 +499,7 @@ static gf_status fwd_row_products(gf_smp *s, int l, const FusedRoute &r) {
     float *T = level_T(s, l), *O = level_O(s, l);
     if (r.panels)
         return smp_rowpanel_products_c64(ctx, true, T, r.drop ? d.rowfac8 : d.rowscale, d.Wst, O, rows, d.trow, d.trowf, false,
-                                         d.wimg_ready ? d.wimg : nullptr, C, r.nf, r.extras_in_kernel ? 3 : 0, d.rowcls);
+                                         d.wimg_ready ? d.wimg : nullptr, C, r.nf, r.extras_in_kernel ? 3 : 0, d.rowcls, nullptr, r.skip_empty);
     const int ldt = T_COLS * C, ldo = O_COLS * C;   // (the tiled launches always use the three-block layout)
     const long long tC = C, wCC = (long long)CC;
     const GemmSpec sp[3] = {
@@ -537,7 +553,7 @@ static gf_status fwd_combine(gf_smp *s, int l, const FusedRoute &r, const BigPar
     // weight-gradient operands with
     float *psum = (l == s->cfg.nLevels || s->cfg.physics) ? d.psum : nullptr;   // (a tower reads every level out)
     const float *nodefac = r.drop ? d.nodefac : nullptr;
-    const gf_status st = smp_combine_fwd_panels_c64(s, l, O, bl, psum, d.pmax, nodefac);
+    const gf_status st = smp_combine_fwd_panels_c64(s, l, O, bl, psum, d.pmax, nodefac, r.skip_empty);
     if (st != GF_OK) return st;
     if (psum) s->lv[l].psum_ready = true;
     if (d.pmax && big.nodes == 0) s->lv[l].pmax_ready = true;   // (maxima of the panels only: a level with bigger nodes is scanned)
@@ -552,6 +568,7 @@ gf_status smp_fused_forward_level(gf_smp *s, int l, const float *Kl, const float
     // what this pass runs the level's products on decides the layout of O / dO (two or three blocks) at C = 32: the reverse sweep
     // follows the forward's choice, not the option's value at the time it runs (round-4 advice)
     s->lv[l].fwd_c64 = r.panels;
+    if (r.skip_empty) ++s->empty_row_calls;
     gf_status st = fwd_zero_rows(s, l, r);
     if (st == GF_OK && r.drop) st = fwd_dropout_factors(s, l);
     if (st == GF_OK) st = fwd_tables(s, l, r, big);
@@ -599,7 +616,7 @@ static gf_status bwd_combine(gf_smp *s, int l, const FusedRoute &r, const BigPar
         d.dz_ld = wg_ld;
         return launch_combine_bwd(s, l, all_quads(h), "smpf_combine_bwd", dfrows, node_df, dO, r.ocols, dzmax);
     }
-    gf_status st = smp_combine_bwd_panels_c64(s, l, dfrows, node_df, dO, dzmax);
+    gf_status st = smp_combine_bwd_panels_c64(s, l, dfrows, node_df, dO, dzmax, r.skip_empty);
     if (st != GF_OK) return st;
     d.dz_rows = d.fwd_npanels;
     d.dz_ld = C;
@@ -729,6 +746,8 @@ static gf_status bwd_weight_grads(gf_smp *s, int l, const FusedRoute &r, FoldGro
         wc.bounds.smax = (float)h.buckets.back().s;
         wc.bounds.max_tot = d.max_tot, wc.bounds.max_tr = d.max_tr, wc.bounds.row_max = d.row_max;
     }
+    if (r.skip_empty && !wc.bounds.level(C)) return fail(ctx, GF_ERR_INVALID, "fused level %d: empty rows skipped without the level's maxima", l);
+    wc.skip_empty = r.skip_empty;
     if (smp_wgrad_reads_absent_blocks(ctx, wc)) {   // (see fused_route: then T needs its structural zeros)
         st = smp_fused_ensure_zero_fill(s, l);
         if (st != GF_OK) return st;
@@ -884,6 +903,7 @@ gf_status smp_fused_backward_level(gf_smp *s, int l, float *dKl, float *dbl, con
     const BigPart big = big_part(s->lay.level[l]);
     gf_status st = bwd_refusals(s, l, r);
     if (st != GF_OK) return st;
+    if (r.skip_empty) ++s->empty_row_calls;
     const float *dfrows = (node_df && !rows_too) ? nullptr : d.df;
     st = bwd_combine(s, l, r, big, dfrows, node_df);
     if (st != GF_OK) return st;

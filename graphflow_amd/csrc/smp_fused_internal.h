@@ -57,6 +57,9 @@ struct FusedRoute {
     bool sign_mask = false;         // reverse sweep: LeakyReLU' from the forward's sign words (smp_sign_mask)
     bool drop = false;              // slice dropout ...
     int nf = 2;                     // ... and the row factors per row it implies: 8 (one per product), else 2 = (tot, tr)
+    // C = 64: O / dO of the level's EMPTY rows (no data in any block of T: none of bits 31 / 30 / 29 of trowf) is neither stored nor
+    // read -- true only where every writer and reader of the region in this call is a kernel that masks them (fused_route)
+    bool skip_empty = false;
 };
 FusedRoute fused_route(const gf_smp *s, int l);
 

@@ -56,7 +56,8 @@ gf_status smp_rowpanel_products_c64(gf_ctx *ctx, bool forward, const float *A, c
                                     const void *wimg = nullptr, int C = 64,   // C = 32 (round 4): split products with prebuilt images only
                                     int nf = 2, int nx = 0,   // row factors per row of `rowscale`: 2 = (tot, tr); 8 = one per product (slice dropout, C = 32)
                                     const int *rowcls = nullptr,   // the table's row classes (C = 64 with trowf: panels of one class, see smp_rowpanel_split)
-                                    const RowpanelDz *dz = nullptr);
+                                    const RowpanelDz *dz = nullptr,
+                                    bool skip_empty = false);   // forward, C = 64, packed table: rows without any data are not stored (FusedRoute::skip_empty)
 // will a backward call with these arguments run the row-class kernel (the one that can form dz itself)?
 bool smp_rowpanel_dz_applies(const gf_ctx *ctx, int rows, const int *trow, const int *trowf, bool skip_zero_grads, int C, int nf, int nx, const int *rowcls);
 // the compact-layout products on the f16 matrix pipe with two-half fp32 operands (smp_level_c64_split.hip; GF_SMP_SPLIT=0: fp32 MFMA)
@@ -64,10 +65,11 @@ bool smp_split_products(const gf_ctx *ctx);
 gf_status smp_rowpanel_split_c64(gf_ctx *ctx, bool forward, const float *A, const float *rowscale, const float *Wst, float *Out,
                                  int rows, const int *trow, int cus, const int *trowf = nullptr, bool skip_zero_grads = false,
                                  const void *wimg = nullptr, int C = 64, int nf = 2, int nx = 0, const int *rowcls = nullptr,
-                                 const RowpanelDz *dz = nullptr);
+                                 const RowpanelDz *dz = nullptr, bool skip_empty = false);
 // the row classes of a level's packed table (smp_prepare.hip: row_class_count): buffer size in ints, and the builder
-size_t smp_row_class_ints(int rows);
-gf_status smp_build_row_classes(gf_ctx *ctx, hipStream_t stream, const int *trowf, int rows, int *buf);
+// live_only: a row with none of the three presence bits (an EMPTY row: no data in any block of T) goes into neither list
+size_t smp_row_class_ints(int rows, bool live_only = false);
+gf_status smp_build_row_classes(gf_ctx *ctx, hipStream_t stream, const int *trowf, int rows, int *buf, bool live_only = false);
 // ... and the node of every entry of the two lists (rows + 64 ints), for the kernel that forms dz from a per-node vector
 gf_status smp_build_row_class_nodes(gf_ctx *ctx, hipStream_t stream, const int *buf, int rows, const long long *node_row, int nodes, int *ent_node);
 // the split kernels' weight images of a level (both directions), built once per forward pass (smp_level_c64_split.hip)
@@ -102,6 +104,7 @@ struct WgradCall {
     size_t part_floats;
     bool any_trow = false;   // trow may leave the gather window of the split kernels (a caller's table at 64 channels): smp_wgrad_split then
                              // reaches dU[trow] through one descriptor over all of dO, which must be smaller than kWgradWholeBytes
+    bool skip_empty = false; // 64 channels, packed table: dO of a row without any data was not written and is not read (FusedRoute::skip_empty)
 };
 constexpr size_t kWgradWholeBytes = 0x40000000;   // (1 GiB: the out-of-range offset of an absent block must stay beyond that descriptor)
 // scratch words per level; exact = false: of a level that only ever keeps its channel maxima there (the 64-channel levels of a model)
@@ -204,6 +207,9 @@ struct gf_smp_batch {
         int *trowf = nullptr;  // [rows] trow | bit 31: rowflag of the row | bit 30: rowflag of the transposed row (smp_rowpanel_split)
         int *rowcls = nullptr;  // C = 64: the rows with and without S_ab / T6 data as two padded lists (smp_prepare.hip: row_class_count)
         int *rowcls_node = nullptr;  // ... the node of every list entry (top level of a plain model: the backward products form dz themselves)
+        // C = 64: one word per combine panel, bit i = row pan[p].x + i has data in some block of T (any of bits 31 / 30 / 29 of trowf);
+        // with it the level's lists in rowcls leave the empty rows out (smp_prepare.hip: row_class_count, live_only)
+        unsigned *pan_live = nullptr;
         float max_tot = 0.f, max_tr = 0.f;  // largest |tot|, |tr| of the level's row factors (split-operand weight gradients' column bounds)
         const unsigned *row_max = nullptr;  // the same two as float bits in device memory when the tables are built there
         long long *pair_src_pair = nullptr, *cons_row = nullptr, *cons_pair = nullptr;  // compact diagonal path (smp_prep.h)
@@ -322,6 +328,7 @@ struct gf_smp : gf_smp_batch {
     gfsmp::Config cfg;    // what the device computes with: nChanels padded to 32 / 64 / a multiple of 4 (gf_smp_create, round 4)
     bool bwd_consumed = false;   // an op-by-op level's reverse sweep has overwritten its Q since the last forward
     long long single_launches = 0;   // launches of smp_tables_fwd_single / smp_bwd_gather_single so far (gf_smp_single_vertex_launches)
+    long long empty_row_calls = 0;   // level passes, forward or backward, that ran with FusedRoute::skip_empty (gf_smp_empty_row_calls)
     gfsmp::Config ucfg;   // the caller's configuration: the layout of parameters, gradients, features and activations at the C ABI
     float *pad_p = nullptr, *pad_g = nullptr, *pad_feat = nullptr;   // padded copies (cfg.nChanels != ucfg.nChanels)
     // Round 5, SMP_2D_ver6 (RisiContraction_10) on the fused RisiContraction_18 level: != 0 = the caller's channel count C.  With a symmetric
@@ -528,10 +535,15 @@ gf_status smp_fused_stack_all(gf_smp *s, const std::vector<const float *> &K);
 gf_status smp_build_gather_records(gf_smp *s, int l, hipStream_t stream);
 gf_status smp_build_tf_records(gf_smp *s, int l, hipStream_t stream);
 gf_status smp_fwd_fused_build_tables(gf_smp *s, int l, hipStream_t stream, bool gather_offsets = true);
+// the panels' live-row words (DevLevel::pan_live) from the packed table, behind build_fwd_panels and whatever wrote trowf on `stream`
+gf_status smp_build_pan_live(gf_smp *s, int l, hipStream_t stream);
+// skip_empty (C = 64): O / dO of the rows whose pan_live bit is clear are not requested / not stored
 gf_status smp_combine_fwd_panels_c64(gf_smp *s, int l, const float *O, const float *bias, float *psum = nullptr, float *pmax = nullptr,
-                                     const float *nodefac = nullptr);
+                                     const float *nodefac = nullptr, bool skip_empty = false);
 // combine-backward on the forward's row panels (C = 64 / 32, compact dO): dzmax = [fwd_npanels][C] per-panel column maxima of |dz| or null
-gf_status smp_combine_bwd_panels_c64(gf_smp *s, int l, const float *dfrows, const float *node_df, float *dO, float *dzmax);
+gf_status smp_combine_bwd_panels_c64(gf_smp *s, int l, const float *dfrows, const float *node_df, float *dO, float *dzmax, bool skip_empty = false);
+// the level's O / dO region [rows][2 C] (compact layout) copied to a caller's device buffer (gf_smp_level_projected_f32)
+gf_status smp_fused_copy_projected(gf_smp *s, int l, float *out);
 // level l's K_l / b_l gradients are complete on the context's CURRENT stream (l == 0: H): start their all-reduce
 gf_status smp_dp_level_done(gf_smp *s, int l);
 

@@ -441,7 +441,7 @@ gf_status smp_wgrad_fp32_c64(gf_ctx *ctx, const float *T, const float *dO, const
 // Every output element is produced by one wave in a fixed order: results do not depend on the grid size.
 gf_status smp_rowpanel_products_c64(gf_ctx *ctx, bool forward, const float *A, const float *rowscale, const float *Wst, float *Out,
                                     int rows, const int *trow, const int *trowf, bool skip_zero_grads, const void *wimg, int C, int nf, int nx,
-                                    const int *rowcls, const RowpanelDz *dz) {
+                                    const int *rowcls, const RowpanelDz *dz, bool skip_empty) {
     if (rows < 1) return GF_OK;
     static int cu_count[64] = {};
     const int di = ctx->device & 63;
@@ -450,7 +450,8 @@ gf_status smp_rowpanel_products_c64(gf_ctx *ctx, bool forward, const float *A, c
         if (cu_count[di] < 1) cu_count[di] = 256;
     }
     const int cus = cu_count[di];
-    if (trow && smp_split_products(ctx)) return smp_rowpanel_split_c64(ctx, forward, A, rowscale, Wst, Out, rows, trow, cus, trowf, skip_zero_grads, wimg, C, nf, nx, rowcls, dz);
+    if (trow && smp_split_products(ctx)) return smp_rowpanel_split_c64(ctx, forward, A, rowscale, Wst, Out, rows, trow, cus, trowf, skip_zero_grads, wimg, C, nf, nx, rowcls, dz, skip_empty);
+    if (skip_empty) return fail(ctx, GF_ERR_INVALID, "smp_rowpanel_products: only the split row-panel kernel leaves the empty rows unstored");
     if (dz) return fail(ctx, GF_ERR_INVALID, "smp_rowpanel_products: dz is formed by the split row-class kernel only");
     if (C != 64 || nf != 2 || nx != 0) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_rowpanel_products: %d channels / %d row factors / %d extra products on the fp32 matrix pipe", C, nf, nx);
     const size_t lds = sizeof(float) * 8 * 2 * 2 * 32 * (size_t)kRpWRow;

@@ -77,8 +77,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
     float *__restrict__ pmax,  // pmax (or null): [npanels][64] largest |f| per column of the panel's rows (the level above scales the
     // columns of its weight-gradient operands with the level's per-channel maxima: WgradScales::chan)
     const float *__restrict__ nodefac,   // (or null) slice dropout: [nodes][18] factors; the compact products G15 / G16 take theirs here
-    unsigned *__restrict__ sgn) {  // sgn (CB = 64, or null): [rows][2] sign words of z -- bit c of word h of a row is z[row][32 h + c] > 0, which is
+    unsigned *__restrict__ sgn,  // sgn (CB = 64, or null): [rows][2] sign words of z -- bit c of word h of a row is z[row][32 h + c] > 0, which is
     // f[row][32 h + c] > 0 (the slope is positive); combine-backward and the top level's backward products take LeakyReLU' from it
+    const unsigned *__restrict__ pan_live) {  // (or null: every row) bit i of word p: row i of panel p has data in some block of T.  The O of an
+    // empty row is exact zeros (O_loc = Z = Z'[trow] = 0) that the products did not store: not requested, the out-of-range offset gives them
     const int lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
     unsigned blk;
     {
@@ -94,6 +96,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
     const int nrows = P.y & 0xff, s = (P.y >> 8) & 0xff, G = (P.y >> 16) & 0xff, x0 = (P.y >> 24) & 0xff;
     const bool rowok = li < nrows;
     const int row = P.x + (rowok ? li : nrows - 1);
+    const unsigned live = (CB == 64 && pan_live) ? (unsigned)rfl((int)pan_live[p]) : 0xffffffffu;   // (the 64-channel build only)
+    // one test per request: bit ra of the lane's word = row ra + 4 lh lies inside the panel and has data
+    const unsigned ld_rows = (live & (nrows >= 32 ? 0xffffffffu : (1u << nrows) - 1u)) >> (4 * lh);
     const int2 go = goff[row];
     constexpr bool TWO = CB == 64;   // a second column half
     constexpr int OB = 2 * CB * 4, FB = CB * 4;   // bytes of a row of O = [O_loc | U] and of Gc = [G15 | G16], of f and of Vout
@@ -111,7 +116,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int rr = (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const int vo = rr < nrows ? (P.x + rr) * OB + colb : kFfOor;
+        const int vo = ((ld_rows >> ((r & 3) + 8 * (r >> 2))) & 1u) ? (P.x + rr) * OB + colb : kFfOor;
         m0[r] = ff_ld1s(rO, vo);
         u0[r] = ff_ld1s(rO, vo + FB);
         if constexpr (TWO) {
@@ -253,7 +258,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
     const float *__restrict__ node_dF,                            // [nodes][CB] or null; with dF: both are added (a tower's level below the top)
     float *__restrict__ dO, const int4 *__restrict__ pan, const int *__restrict__ pan_node, int npanels, int rows,
     const float *__restrict__ adj, const float *__restrict__ rsum, long long pairs, float *__restrict__ dVout, float *__restrict__ dSpart,
-    float *__restrict__ dbpart, float *__restrict__ dzmax) {   // dzmax (or null): [npanels][CB]
+    float *__restrict__ dbpart, float *__restrict__ dzmax,   // dzmax (or null): [npanels][CB]
+    const unsigned *__restrict__ pan_live) {   // (or null: every row) as in combine-forward: the dO of an empty row has no reader (its T row is
+    // zero, its table gradients are gradients of structural zeros or uncovered) and is not stored; dz, dzmax and the partials cover every row
     const int lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
     unsigned blk;
     {
@@ -269,6 +276,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
     const int nrows = P.y & 0xff, s = (P.y >> 8) & 0xff, G = (P.y >> 16) & 0xff, x0 = (P.y >> 24) & 0xff;
     const bool rowok = li < nrows;
     const int row = P.x + (rowok ? li : nrows - 1);
+    const unsigned live = (CB == 64 && pan_live) ? (unsigned)rfl((int)pan_live[p]) : 0xffffffffu;   // (the 64-channel build only)
+    // one test per store: bit ra of the lane's word = row ra + 4 lh lies inside the panel and has data
+    const unsigned st_rows = (live & (nrows >= 32 ? 0xffffffffu : (1u << nrows) - 1u)) >> (4 * lh);
     constexpr bool TWO = CB == 64;
     static_assert(!SGN || TWO, "sign words: 64 channels");
     static_assert(!NODF || SGN, "");
@@ -338,7 +348,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
         z1[r] = ok ? b : 0.f;
         x0m = fmaxf(x0m, fabsf(z0[r]));
         x1m = fmaxf(x1m, fabsf(z1[r]));
-        const int vo = ok ? (P.x + rr) * OB + colb : kFfOor;
+        const int vo = ((st_rows >> ((r & 3) + 8 * (r >> 2))) & 1u) ? (P.x + rr) * OB + colb : kFfOor;
         ff_st1s(rO, vo, z0[r]);
         if constexpr (TWO) ff_st1s(rO, vo + 128, z1[r]);
     }
@@ -355,7 +365,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int rr = (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const int vo = rr < nrows ? (P.x + rr) * OB + FB + colb : kFfOor;
+        const int vo = ((st_rows >> ((r & 3) + 8 * (r >> 2))) & 1u) ? (P.x + rr) * OB + FB + colb : kFfOor;
         ff_st1s(rO, vo, u0[r]);
         if constexpr (TWO) ff_st1s(rO, vo + 128, u1[r]);
     }
@@ -416,6 +426,16 @@ __global__ void build_fwd_panels(const int *__restrict__ node_s, const long long
         pan_node[p] = n;
     }
 }
+// pan_live[p]: bit i = row pan[p].x + i has any of the three presence bits of the packed table (own, transposed, covered)
+__global__ void build_pan_live(const int4 *__restrict__ pan, int npanels, const int *__restrict__ trowf, unsigned *__restrict__ pan_live) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npanels) return;
+    const int4 P = pan[p];
+    const int nrows = P.y & 0xff;
+    unsigned w = 0u;
+    for (int i = 0; i < nrows; ++i) w |= ((trowf[P.x + i] & 0xe0000000) != 0 ? 1u : 0u) << i;
+    pan_live[p] = w;
+}
 // goff[row of (x, e)] = {Gc row of G15[x, e], Gc row of G16[e, x]} (pair index of level l-1, -1 = structurally absent)
 __global__ void build_fwd_goff(const int *__restrict__ node_s, const long long *__restrict__ node_row, const long long *__restrict__ node_pair,
                                const long long *__restrict__ pair_src_pair, const short *__restrict__ pi, int2 *__restrict__ goff) {
@@ -444,8 +464,17 @@ gf_status smp_fwd_fused_build_tables(gf_smp *s, int l, hipStream_t stream, bool 
     return GF_OK;
 }
 
+gf_status smp_build_pan_live(gf_smp *s, int l, hipStream_t stream) {
+    const gf_smp::DevLevel &d = s->lv[l];
+    if (!d.pan_live || !d.fwd_pan || !d.trowf || d.fwd_npanels < 1) return GF_OK;
+    hipLaunchKernelGGL(build_pan_live, dim3((unsigned)((d.fwd_npanels + 255) / 256)), dim3(256), 0, stream, d.fwd_pan, d.fwd_npanels, d.trowf, d.pan_live);
+    GF_LAUNCH_CHECK(s->ctx, "build_pan_live");
+    return GF_OK;
+}
+
 // f_l from the projected matrix O = [O_loc | U] (compact layout) of a fused level at C = 64: smp_combine_fwd_panels
-gf_status smp_combine_fwd_panels_c64(gf_smp *s, int l, const float *O, const float *bias, float *psum, float *pmax, const float *nodefac) {
+gf_status smp_combine_fwd_panels_c64(gf_smp *s, int l, const float *O, const float *bias, float *psum, float *pmax, const float *nodefac,
+                                     bool skip_empty) {
     gf_ctx *ctx = s->ctx;
     const gf_smp::DevLevel &d = s->lv[l];
     const gfsmp::LevelLayout &h = s->lay.level[l];
@@ -454,7 +483,8 @@ gf_status smp_combine_fwd_panels_c64(gf_smp *s, int l, const float *O, const flo
 #define GF_CFP_LAUNCH(CBv)                                                                                                               \
     GF_LAUNCH(ctx, "smpf_combine_fwd", (smp_combine_fwd_panels<CBv>), dim3((unsigned)((npanels + 3) / 4)), dim3(256), 0, O, d.f, d.fwd_pan,  \
               d.fwd_pan_node, npanels, (int)h.rows, d.fwd_goff, d.Gc, (long long)s->lay.level[l - 1].pairs, d.adj, d.rsum, d.Vout,          \
-              (long long)h.pairs, d.Sout, bias, psum, pmax, nodefac, s->cfg.nChanels == 64 ? d.sgn : (unsigned *)nullptr)
+              (long long)h.pairs, d.Sout, bias, psum, pmax, nodefac, s->cfg.nChanels == 64 ? d.sgn : (unsigned *)nullptr,                   \
+              (skip_empty && s->cfg.nChanels == 64) ? d.pan_live : (const unsigned *)nullptr)
     if (s->cfg.nChanels == 64) GF_CFP_LAUNCH(64);
     else if (s->cfg.nChanels == 16) GF_CFP_LAUNCH(16);
     else GF_CFP_LAUNCH(32);
@@ -464,7 +494,7 @@ gf_status smp_combine_fwd_panels_c64(gf_smp *s, int l, const float *O, const flo
 }
 
 // dO = [L | dU] and the per-(node, x) partials of a fused level from df_l (rows, a per-node vector, or both): smp_combine_bwd_panels
-gf_status smp_combine_bwd_panels_c64(gf_smp *s, int l, const float *dfrows, const float *node_df, float *dO, float *dzmax) {
+gf_status smp_combine_bwd_panels_c64(gf_smp *s, int l, const float *dfrows, const float *node_df, float *dO, float *dzmax, bool skip_empty) {
     gf_ctx *ctx = s->ctx;
     const gf_smp::DevLevel &d = s->lv[l];
     const gfsmp::LevelLayout &h = s->lay.level[l];
@@ -472,7 +502,8 @@ gf_status smp_combine_bwd_panels_c64(gf_smp *s, int l, const float *dfrows, cons
     if (npanels < 1) return GF_OK;
 #define GF_CBP_LAUNCH(...)                                                                                                              \
     GF_LAUNCH(ctx, "smpf_combine_bwd", (smp_combine_bwd_panels<__VA_ARGS__>), dim3((unsigned)((npanels + 3) / 4)), dim3(256), 0, d.f, d.sgn, dfrows, node_df, dO, \
-              d.fwd_pan, d.fwd_pan_node, npanels, (int)h.rows, d.adj, d.rsum, (long long)h.pairs, d.dVout, d.dSpart, d.dbpart, dzmax)
+              d.fwd_pan, d.fwd_pan_node, npanels, (int)h.rows, d.adj, d.rsum, (long long)h.pairs, d.dVout, d.dSpart, d.dbpart, dzmax,         \
+              (skip_empty && s->cfg.nChanels == 64) ? d.pan_live : (const unsigned *)nullptr)
     // (with the sign words and no row gradient -- the top level of a plain model -- the kernel requests no streamed operand at all)
     if (s->cfg.nChanels == 64 && smp_sign_mask(s, l) && !dfrows) GF_CBP_LAUNCH(64, true, true);
     else if (s->cfg.nChanels == 64 && smp_sign_mask(s, l)) GF_CBP_LAUNCH(64, true);

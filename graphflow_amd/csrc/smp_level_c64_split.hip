@@ -251,6 +251,9 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
     auto t_bc = [](int t) { return MASK ? ((t >> 29) & 1) != 0 : true; };   // the row's S_bc / T10 blocks hold data
     static_assert(NX == 0 || (NX == 3 && CB <= 32 && NF == 2), "the extra products: prebuilt images, plain row factors");
     constexpr int NP = 8 + NX;   // weight images in LDS
+    // FWD with store_mask (the plain 64-channel program only): the rows of O without data in ANY block of T -- none of the three bits, exact
+    // zeros that combine-forward does not request either (FusedRoute::skip_empty) -- go to the scratch rows, like the dS_ab / dT6 rows backward
+    constexpr bool FWD_ROWMASK = FWD && MASK && CB == 64 && NF == 2 && NX == 0 && W == 1;
     extern __shared__ __attribute__((aligned(16))) uint4 sp_smem[];
     uint4 *imgH = sp_smem, *imgL = sp_smem + NP * E;
     float *winv = reinterpret_cast<float *>(sp_smem + 2 * NP * E);  // [NP] 2^-k of the weight blocks (padded to 16 floats)
@@ -444,7 +447,7 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
         GF_GLOBAL float *out = gf_global(Out) + (size_t)(r0 + 4 * lh) * LDOUT + o * BS + out_off + li;
         if constexpr (CB < 32)   // lanes of the zero columns store into the scratch rows (a select on the address: every store is issued)
             out = li < CB ? out : gf_global(sp_dump) + (size_t)((r0 & 255) + 4 * lh) * 64 + li;
-        if constexpr (MASK && !FWD && decltype(full)::value) {
+        if constexpr (MASK && (!FWD || FWD_ROWMASK) && decltype(full)::value) {
             if (rowbits != 0xffffffffu) {  // (uniform; the blocks without structural zeros pass all ones)
                 // rows without data go to the scratch rows: a select on the address, every store is issued
                 const unsigned mine = rowbits >> (4 * lh);
@@ -469,7 +472,7 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
         } else {
             // (the partial panel skips the rows without data as the full ones do: until the stand-alone operator's test looked, it
             //  stored them -- numbers no consumer reads, but "not written" then held for every row except the level's last few)
-            const unsigned mine = (MASK && !FWD) ? rowbits >> (4 * lh) : 0xffffffffu;
+            const unsigned mine = (MASK && (!FWD || FWD_ROWMASK)) ? rowbits >> (4 * lh) : 0xffffffffu;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int rr = (r & 3) + 8 * (r >> 2);
@@ -494,6 +497,7 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
         Spl X, Y, Z;
         float iX, iY, iZ;
         if (FWD) {  // T blocks: 0 S_ab, 1 S_bc, 2 T6, 3 T10; outputs: 0 O_loc, 1 U.  Entry: Ra = S_ab, Rb = S_ab at the transposed rows
+            const unsigned rowbits = (FWD_ROWMASK && store_mask) ? (unsigned)__ballot((tcur & 0xe0000000) != 0) : 0xffffffffu;
             split_blk(Ra, X, iX);
             load_raw(Ra, p, 1, t_bc(tcur));          // S_bc
             split_blk(Rb, Z, iZ);
@@ -503,7 +507,7 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
             prod(Z, iZ * sc.f[7], 7, acc0, acc1);
             split_blk(Ra, Y, iY);
             prod(Y, iY * sc.f[6], 6, acc0, acc1);
-            store_out(p, 1, acc0, acc1, full);
+            store_out(p, 1, acc0, acc1, full, rowbits);
             start(p, 0, acc0, acc1, full);
             prod(X, iX * sc.f[0], 0, acc0, acc1);
             prod(X, iX * sc.f[2], 2, acc0, acc1);
@@ -521,7 +525,7 @@ __global__ __launch_bounds__(kSpThreads, 1) void smp_rowpanel_split(const float 
             split_blk(Ra, Z, iZ);
             load_raw(Ra, pn, 0, t_own(tnext));       // S_ab of the next panel
             prod(Z, iZ * sc.f[4], 4, acc0, acc1);
-            store_out(p, 0, acc0, acc1, full);
+            store_out(p, 0, acc0, acc1, full, rowbits);
         } else {    // dO blocks: 0 L, 1 dU; outputs: 0 dS_ab, 1 dS_bc, 2 dT6, 3 dT10.  Entry: Ra = L, Rb = dU
             split_blk(Ra, X, iX);
             split_blk(Rb, Y, iY);
@@ -1042,7 +1046,8 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
                                                                   float smax, float max_tot, float max_tr,
                                                                   const unsigned *__restrict__ row_max,   // or null: {max |tot|, max |tr|} as float bits in
                                                                   // device memory (they replace max_tot / max_tr: the device-side table builder's)
-                                                                  int packed,   // != 0: trow is the packed table (see smp_rowpanel_split)
+                                                                  int packed,   // != 0: trow is the packed table (see smp_rowpanel_split); 2: and
+                                                                  // dO of a row with none of its three bits was not written (FusedRoute::skip_empty)
                                                                   int a_off, int b_off, int out_off) {   // W > 1: see above
     if constexpr (W == 1) a_off = b_off = out_off = 0;
     constexpr int LDT = 256 * W, LDO = 128 * W, BS = 64 * W, LDW = 64 * W;   // rows of T, of dO; a block to the next; rows of an image
@@ -1160,6 +1165,8 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
         const bool z0 = packed && !((ia0 >> zbit) & 1), z1 = packed && !((ia1 >> zbit) & 1);
         // the gathered dU row meets S_ab of its row only: a row without data skips the gather as well (and waves 2..7 have none)
         const bool zg0 = !has_b1 || (packed && ia0 >= 0), zg1 = !has_b1 || (packed && ia1 >= 0);
+        // an empty row (no data in any block of T): its dO was not stored and meets zeros only -- not requested either
+        const bool ze0 = packed > 1 && !(ia0 & 0xe0000000), ze1 = packed > 1 && !(ia1 & 0xe0000000);
         ia0 = ib0, ia1 = ib1;
         fetch_trow(m + 2, ib0, ib1);
         // the slice's descriptors, on the scalar unit: rows [k0, min(k0 + 16, rows)) of T, and the window of dO that holds the slice's
@@ -1179,8 +1186,8 @@ __global__ __launch_bounds__(kWsThreads, 1) void smp_wgrad_split(const float *__
         S.ta.v1 = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rT, z1 ? kOor : off_a + LDT * 4, 0, kAuxA));
         S.f0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rRs, off_rs, k0 * 8, 0));
         S.f1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rRs, off_rs + 8, k0 * 8, 0));
-        S.tb[0].v0 = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rD, off_b, own, 0));
-        S.tb[0].v1 = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rD, off_b + LDO * 4, own, 0));
+        S.tb[0].v0 = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rD, ze0 ? kOor : off_b, own, 0));
+        S.tb[0].v1 = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rD, ze1 ? kOor : off_b + LDO * 4, own, 0));
         // (unsigned: the zero entry of a row past the end may wrap -- harmless, its rows of T are zeros and the descriptor bounds it)
         const int og0 = (int)((unsigned)(g0 - w0) * (unsigned)(LDO * 4) + (unsigned)g_col);
         const int og1 = (int)((unsigned)(g1 - w0) * (unsigned)(LDO * 4) + (unsigned)g_col);
@@ -1756,7 +1763,7 @@ bool smp_rowpanel_dz_applies(const gf_ctx *ctx, int rows, const int *trow, const
 // fixed order: results do not depend on the grid size.
 gf_status smp_rowpanel_split_c64(gf_ctx *ctx, bool forward, const float *A, const float *rowscale, const float *Wst, float *Out,
                                  int rows, const int *trow, int cus, const int *trowf, bool skip_zero_grads, const void *wimg, int C, int nf, int nx,
-                                 const int *rowcls, const RowpanelDz *dz) {
+                                 const int *rowcls, const RowpanelDz *dz, bool skip_empty) {
     const int per = kSpThreads / 64;
     const bool classed = rowpanel_classed(forward, rows, trowf, skip_zero_grads, C, nf, nx, rowcls);
     const int npanels = (rows + 31) / 32 + (classed ? 1 : 0);   // (two padded lists: one panel more at the most)
@@ -1774,7 +1781,8 @@ gf_status smp_rowpanel_split_c64(gf_ctx *ctx, bool forward, const float *A, cons
         if (forward) return mask ? launch_rowpanel_c128<true, true>(ctx, a, sets) : launch_rowpanel_c128<true, false>(ctx, a, sets);
         return mask ? launch_rowpanel_c128<false, true>(ctx, a, sets) : launch_rowpanel_c128<false, false>(ctx, a, sets);
     }
-    const RowpanelArgs a = {grid, A, rowscale, Wst, Out, rows, mask ? trowf : trow, skip_zero_grads ? 1 : 0,
+    // (store_mask: backward, the gradients of structural zeros are not stored; forward, 64 channels: the rows of O without any data are not)
+    const RowpanelArgs a = {grid, A, rowscale, Wst, Out, rows, mask ? trowf : trow, (forward ? (skip_empty && mask && C == 64) : skip_zero_grads) ? 1 : 0,
                             wimg ? static_cast<const uint4 *>(wimg) + (forward ? 0 : kSpImgStride) : nullptr};
     if (nx != 0) {   // the extra products of SMP_2D_ver7 on the 18-slice level (see the kernel)
         if (nx != 3 || nf != 2 || !(C == 32 || C == 16) || !wimg)
@@ -1969,7 +1977,7 @@ gf_status smp_wgrad_partials(gf_ctx *ctx, const WgradCall &a, FoldGroup *out, Fo
     const int *tr = mask ? a.trowf : a.trow;
     switch (k) {
     case WgradKernel::Fp32: return smp_wgrad_fp32_c64(ctx, a.T, a.dO, a.rowscale, a.rows, p.kchunk, p.splits, a.part, a.trow);
-    case WgradKernel::Split64: return launch_wgrad_split<1>(ctx, a, p, tr, cmax, b, mask ? 1 : 0);
+    case WgradKernel::Split64: return launch_wgrad_split<1>(ctx, a, p, tr, cmax, b, mask ? (a.skip_empty ? 2 : 1) : 0);
     case WgradKernel::Split128: return launch_wgrad_split<2>(ctx, a, p, tr, cmax, b, mask ? 1 : 0);
     default: break;
     }

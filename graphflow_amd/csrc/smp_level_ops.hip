@@ -161,6 +161,12 @@ gf_status gf_smp_level_row_classes(gf_ctx *ctx, int rows, const int *trowf, int 
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     return gf::smp_build_row_classes(ctx, ctx->stream, trowf, rows, lists);
 }
+gf_status gf_smp_level_row_classes_ex(gf_ctx *ctx, int rows, const int *trowf, int *lists, int live_only) {
+    if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
+    if (rows < 1 || rows >= (1 << 29) || !trowf || !lists) return fail(ctx, GF_ERR_INVALID, "gf_smp_level_row_classes_ex: bad argument");
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return gf::smp_build_row_classes(ctx, ctx->stream, trowf, rows, lists, live_only != 0);
+}
 
 gf_status gf_smp_level_wgrad_ex_f32(gf_ctx *ctx, int C, int nf, int nx, int rows, const float *T, const float *dO, const float *rowfac,
                                     const int *trow, const int *trowf, float *dWst, float *dX) {

@@ -401,49 +401,70 @@ __global__ void build_trow(int *__restrict__ trow, const int *__restrict__ node_
 // the scratch words of the scan.  A padding entry repeats the last entry of its class with bit 31 of the row set: the kernel loads
 // that row and stores into its scratch rows.  A stable partition in three launches: own rows per 1,024-row block, an exclusive scan of
 // the block counts, the scatter.
+// live_only (the driver's lists of a 64-channel level, FusedRoute::skip_empty): a third outcome -- a row with none of bits 31 / 30 / 29
+// (an EMPTY row: no data in any block of T, nothing reads its gradients) goes into NEITHER list; [1] then counts the absent rows that
+// are left, and a second set of block counts (behind the first) ranks them.
 constexpr int kRcBlock = 1024;
-__global__ __launch_bounds__(kRcBlock) void row_class_count(const int *__restrict__ trowf, int rows, int *__restrict__ blockcnt) {
+__device__ __forceinline__ bool rc_kept_absent(int t, bool live_only) { return t >= 0 && (!live_only || (t & 0x60000000) != 0); }
+__global__ __launch_bounds__(kRcBlock) void row_class_count(const int *__restrict__ trowf, int rows, int *__restrict__ blockcnt, int live_only) {
     const int r = blockIdx.x * kRcBlock + threadIdx.x;
-    const int n = __syncthreads_count(r < rows && trowf[r] < 0);
+    const int t = r < rows ? trowf[r] : 0;
+    const int n = __syncthreads_count(r < rows && t < 0);
     if (threadIdx.x == 0) blockcnt[blockIdx.x] = n;
+    if (live_only) {   // (uniform)
+        const int m = __syncthreads_count(r < rows && rc_kept_absent(t, true));
+        if (threadIdx.x == 0) blockcnt[gridDim.x + blockIdx.x] = m;
+    }
 }
-__global__ __launch_bounds__(kRcBlock) void row_class_scan(int *__restrict__ blockcnt, int nb, int rows, int *__restrict__ hdr) {
+__global__ __launch_bounds__(kRcBlock) void row_class_scan(int *__restrict__ blockcnt, int nb, int rows, int *__restrict__ hdr, int live_only) {
     __shared__ int part[kRcBlock];
     const int tid = threadIdx.x, per = (nb + kRcBlock - 1) / kRcBlock;
     const int i0 = tid * per < nb ? tid * per : nb, i1 = i0 + per < nb ? i0 + per : nb;
-    int sum = 0;
-    for (int i = i0; i < i1; ++i) sum += blockcnt[i];
-    part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < kRcBlock; d <<= 1) {
-        const int v = tid >= d ? part[tid - d] : 0;
+    for (int set = 0; set < (live_only ? 2 : 1); ++set) {   // own rows; live_only: then the absent rows that are kept
+        int *cnt = blockcnt + set * nb;
+        int sum = 0;
+        for (int i = i0; i < i1; ++i) sum += cnt[i];
         __syncthreads();
-        part[tid] += v;
+        part[tid] = sum;
         __syncthreads();
+        for (int d = 1; d < kRcBlock; d <<= 1) {
+            const int v = tid >= d ? part[tid - d] : 0;
+            __syncthreads();
+            part[tid] += v;
+            __syncthreads();
+        }
+        int run = part[tid] - sum;
+        for (int i = i0; i < i1; ++i) {
+            const int c = cnt[i];
+            cnt[i] = run;
+            run += c;
+        }
+        if (tid == kRcBlock - 1) {
+            if (set == 0) hdr[0] = part[tid], hdr[1] = rows - part[tid], hdr[2] = hdr[3] = 0;
+            else hdr[1] = part[tid];
+        }
     }
-    int run = part[tid] - sum;
-    for (int i = i0; i < i1; ++i) {
-        const int c = blockcnt[i];
-        blockcnt[i] = run;
-        run += c;
-    }
-    if (tid == kRcBlock - 1) hdr[0] = part[tid], hdr[1] = rows - part[tid], hdr[2] = hdr[3] = 0;
 }
 __global__ __launch_bounds__(kRcBlock) void row_class_fill(const int *__restrict__ trowf, int rows, const int *__restrict__ blockoff,
-                                                           const int *__restrict__ hdr, int2 *__restrict__ ent) {
-    __shared__ int wcnt[kRcBlock / 64];
+                                                           const int *__restrict__ hdr, int2 *__restrict__ ent, int live_only) {
+    __shared__ int wcnt[kRcBlock / 64], wabs[kRcBlock / 64];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int r = blockIdx.x * kRcBlock + tid;
     const int t = r < rows ? trowf[r] : 0;
-    const bool own = t < 0;
-    const unsigned long long b = __ballot(own);
-    if (lane == 0) wcnt[w] = __popcll(b);
+    const bool own = t < 0, kept = r < rows && rc_kept_absent(t, live_only != 0);
+    const unsigned long long b = __ballot(own), ba = __ballot(kept);
+    if (lane == 0) wcnt[w] = __popcll(b), wabs[w] = __popcll(ba);
     __syncthreads();
     int before = blockoff[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));   // own rows in front of row r
     for (int i = 0; i < w; ++i) before += wcnt[i];
-    if (r >= rows) return;
+    int abs_before = r - before;                                                  // absent rows in front of it: all of them, or the kept ones
+    if (live_only) {   // (uniform)
+        abs_before = blockoff[gridDim.x + blockIdx.x] + __popcll(ba & ((1ull << lane) - 1ull));
+        for (int i = 0; i < w; ++i) abs_before += wabs[i];
+    }
+    if (r >= rows || (!own && !kept)) return;
     const int n_own = hdr[0], n_abs = hdr[1], own_pad = (n_own + 31) & ~31;
-    const int k = own ? before : r - before;   // the row's rank in its class
+    const int k = own ? before : abs_before;   // the row's rank in its class
     const int at = own ? k : own_pad + k;
     ent[at] = make_int2(r, t);
     if (k == (own ? n_own : n_abs) - 1) {   // the last row of a class fills the class's padding
@@ -655,7 +676,8 @@ void alloc_level_panels(Taker &t, Level &h, DevLevel &d, int l) {
     if (!(cfg.square() && (smp_panel_channels(C) || c128) && h.rows < 0x7fffffffll)) return;
     t.alloc(&d.trow, (size_t)h.rows);
     t.alloc(&d.trowf, (size_t)h.rows);
-    if (C == 64 && cfg.nContractions == 18 && h.rows < (1ll << 29)) t.alloc(&d.rowcls, smp_row_class_ints((int)h.rows));   // (row classes of the masked products)
+    // (row classes of the masked products; the driver's lists leave the empty rows out: smp_build_row_classes, live_only)
+    if (C == 64 && cfg.nContractions == 18 && h.rows < (1ll << 29)) t.alloc(&d.rowcls, smp_row_class_ints((int)h.rows, true));
     // (the top level of a plain model: its backward products form dz from the read-out's per-node vector -- the node of every list entry)
     if (d.rowcls && l == L && !cfg.physics) t.alloc(&d.rowcls_node, (size_t)h.rows + 64);
     unsigned char *img = nullptr;
@@ -676,6 +698,7 @@ void alloc_level_panels(Taker &t, Level &h, DevLevel &d, int l) {
     t.alloc(&d.fwd_pan_node, np1);
     t.alloc(&d.fwd_goff, (size_t)h.rows);
     if (C == 64) t.alloc(&d.sgn, (size_t)h.rows * 2);   // (the sign words of z_l: 8 bytes per row)
+    if (C == 64 && d.rowcls) t.alloc(&d.pan_live, np1);   // (the panels' live-row words: FusedRoute::skip_empty)
 }
 
 // the contraction's output and what the level's kind works in beside it
@@ -793,7 +816,8 @@ gf_status build_row_tables(gf_smp *s) {
         if (st == GF_OK) st = smp_fwd_fused_build_tables(s, l, up, !merged);
         if (st != GF_OK) return st;
         if (d.trow && !merged) hipLaunchKernelGGL(build_trow, dim3(nNodes), dim3(64), 0, up, d.trow, d.node_s, d.node_row, d.pi, d.rowflag, d.trowf);
-        if (d.rowcls) st = smp_build_row_classes(s->ctx, up, d.trowf, (int)s->lay.level[l].rows, d.rowcls);
+        if (d.rowcls) st = smp_build_row_classes(s->ctx, up, d.trowf, (int)s->lay.level[l].rows, d.rowcls, true);
+        if (st == GF_OK && d.pan_live) st = smp_build_pan_live(s, l, up);
         if (st == GF_OK && d.rowcls_node) st = smp_build_row_class_nodes(s->ctx, up, d.rowcls, (int)s->lay.level[l].rows, d.node_row, nNodes, d.rowcls_node);
         if (st != GF_OK) return st;
     }
@@ -1230,14 +1254,17 @@ gf_status check_graph_sizes(const gf_smp *s, const char *who, bool have_all, int
 }  // namespace
 
 // ints of a level's row-class buffer (see row_class_count), and its builder: three launches on `stream` behind whatever wrote trowf
-size_t smp_row_class_ints(int rows) { return 4 + 2 * ((size_t)rows + 64) + (size_t)(rows + kRcBlock - 1) / kRcBlock + 1; }
-gf_status smp_build_row_classes(gf_ctx *ctx, hipStream_t stream, const int *trowf, int rows, int *buf) {
+// (live_only: a second set of block counts)
+size_t smp_row_class_ints(int rows, bool live_only) {
+    return 4 + 2 * ((size_t)rows + 64) + (live_only ? 2 : 1) * ((size_t)(rows + kRcBlock - 1) / kRcBlock + 1);
+}
+gf_status smp_build_row_classes(gf_ctx *ctx, hipStream_t stream, const int *trowf, int rows, int *buf, bool live_only) {
     if (rows < 1) return GF_OK;
-    const int nb = (rows + kRcBlock - 1) / kRcBlock;
+    const int nb = (rows + kRcBlock - 1) / kRcBlock, lv = live_only ? 1 : 0;
     int *blockcnt = buf + 4 + 2 * ((size_t)rows + 64);
-    hipLaunchKernelGGL(row_class_count, dim3(nb), dim3(kRcBlock), 0, stream, trowf, rows, blockcnt);
-    hipLaunchKernelGGL(row_class_scan, dim3(1), dim3(kRcBlock), 0, stream, blockcnt, nb, rows, buf);
-    hipLaunchKernelGGL(row_class_fill, dim3(nb), dim3(kRcBlock), 0, stream, trowf, rows, blockcnt, buf, reinterpret_cast<int2 *>(buf + 4));
+    hipLaunchKernelGGL(row_class_count, dim3(nb), dim3(kRcBlock), 0, stream, trowf, rows, blockcnt, lv);
+    hipLaunchKernelGGL(row_class_scan, dim3(1), dim3(kRcBlock), 0, stream, blockcnt, nb, rows, buf, lv);
+    hipLaunchKernelGGL(row_class_fill, dim3(nb), dim3(kRcBlock), 0, stream, trowf, rows, blockcnt, buf, reinterpret_cast<int2 *>(buf + 4), lv);
     GF_LAUNCH_CHECK(ctx, "row_class_fill");
     return GF_OK;
 }

@@ -166,6 +166,18 @@ class SMPOmega:
         """Launches so far of the level-1 kernels for single-vertex sources (they run under the general kernels' launch names)."""
         return int(self.lib.gf_smp_single_vertex_launches(self.handle))
 
+    def empty_row_calls(self):
+        """Level passes so far, forward or backward, that neither stored nor read O / dO of the level's empty rows (gf_smp_empty_row_calls)."""
+        return int(self.lib.gf_smp_empty_row_calls(self.handle))
+
+    def level_projected(self, level):
+        """The level's projected matrix as the last pass left it, [rows][2 C] on the device: O after a forward, dO after a backward."""
+        rows = self.level_sizes(level)[1]
+        out = torch.empty((rows, 2 * self.cfg.nChanels), dtype=torch.float32, device=self.ctx.device)
+        self.ctx.check(self.lib.gf_smp_level_projected_f32(self.handle, level, C.c_void_p(out.data_ptr())))
+        torch.cuda.synchronize()
+        return out
+
     def receptive_field(self, mol, level, v):
         buf = (C.c_int * 4096)()
         n = self.lib.gf_smp_receptive_field(self.handle, mol, level, v, buf, 4096)

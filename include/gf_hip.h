@@ -658,6 +658,11 @@ gf_status gf_smp_level_wgrad_ex_f32(gf_ctx *ctx, int C, int nf, int nx, int rows
  * without, padded likewise.  A padding entry repeats the last row of its class with bit 31 of the row set.  The level builds this once
  * per gf_smp_prepare; gf_smp_level_products_ex_f32 builds it per call (the backward products under skip_zero_grads walk it).  rows < 2^29.  Asynchronous on the context's stream. */
 gf_status gf_smp_level_row_classes(gf_ctx *ctx, int rows, const int *trowf, int *lists);
+/* The same lists as a fused 64-channel level of a model keeps them (live_only != 0): a row with none of bits 31 / 30 / 29 of its packed
+ * word -- an EMPTY row: no data in any block of T, its O is exact zeros and nothing reads its gradients -- goes into NEITHER list, and
+ * [1] counts the rows without bit 31 that are left.  lists: 4 + 2 (rows + 64) + 2 (rows / 1024 + 2) ints.  live_only = 0:
+ * gf_smp_level_row_classes. */
+gf_status gf_smp_level_row_classes_ex(gf_ctx *ctx, int rows, const int *trowf, int *lists, int live_only);
 /* SMP_2D_ver5's level (gf_smp_config.steerable_2d = 5), its channel projections and weight gradients as stand-alone operators: the
  * level's own kernels and launches on caller-supplied operands, for per-row tests (tests/test_smp_2d_ver5_ops_gpu.py).  Device
  * pointers, fp32, asynchronous on the context's stream.  C = 1 .. 128 channels; K [C][2 C] = [K1 | K2]; sizes: nsizes entries of 3 C
@@ -869,6 +874,14 @@ gf_status gf_smp_device_bytes(const gf_smp *smp, size_t *in_use, size_t *reserve
  * SMP_omega at 64 / 32 / 16 channels: one per size class in tables-forward, one in the backward gather); they run under the general
  * kernels' launch names.  GF_SMP_LEVEL1=0 keeps it where it is.  0 for a null handle. */
 long long gf_smp_single_vertex_launches(const gf_smp *smp);
+/* Introspection for tests: level passes so far, forward or backward, in which a fused 64-channel level neither stored nor read the
+ * projected matrix O / dO of its empty rows (rows (a, b) with no data in any table block: no source covers them).  One per level and
+ * direction where the call's kernels all mask those rows; GF_SMP_EMPTY_ROWS=0 (read per call) keeps it where it is.  0 for a null handle. */
+long long gf_smp_empty_row_calls(const gf_smp *smp);
+/* ... and the level's projected matrix as the last pass left it -- O = [O_loc | U] after a forward, dO = [dz | dU] after a backward of
+ * the level -- copied to `out` (device, [rows][2 C] floats), asynchronously on the context's stream.  GF_ERR_INVALID unless the level's
+ * last forward ran fused on the row-panel kernels (the compact layout) at the caller's own channel count (no padding). */
+gf_status gf_smp_level_projected_f32(gf_smp *smp, int level, float *out);
 /* Host-pointer mode of the driver (what graphflow_amd/host/SMP_omega_hip.h uses): the handle owns the model -- a device
  * parameter buffer and its gradient.  Wherever the entry points of this section take `params` / `grads`, NULL selects the
  * handle-owned buffers.  gf_smp_forward_host runs gf_smp_forward on them and returns per-molecule results as doubles
