@@ -67,6 +67,15 @@ template <typename Kern>
 gf_status opt_in_lds(gf_ctx *ctx, Kern kern, size_t bytes) {
     return opt_in_lds_fn(ctx, reinterpret_cast<const void *>(kern), bytes);
 }
+// compute units of the context's device, asked once per device; 256 where the query fails (THE cache: persistent kernels size their grids by it)
+inline int device_cu_count(const gf_ctx *ctx) {
+    static int cu_count[64] = {};
+    const int di = ctx->device & 63;
+    if (!cu_count[di]) {
+        if (hipDeviceGetAttribute(&cu_count[di], hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cu_count[di] < 1) cu_count[di] = 256;
+    }
+    return cu_count[di];
+}
 // data-parallel hooks (gf_dist.hip): is a communicator attached, and the collective on an explicit stream
 bool dist_active(const gf_ctx *ctx);
 bool dist_poisoned(const gf_ctx *ctx);   // a watchdog limit fired on this context's communicator: never wait for its streams unbounded

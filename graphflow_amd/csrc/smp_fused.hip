@@ -489,6 +489,20 @@ static gf_status fwd_small_products(gf_smp *s, int l, const FusedRoute &r) {
     return gemm_grouped_free(s->ctx, false, sm, 4, "smpf_small_nn");
 }
 
+// the row-panel family's call for level l in one direction: forward O from T, backward dT from dO (without dz: bwd_table_grads asks for it)
+static RowProductsCall row_products_call(const gf_smp *s, int l, const FusedRoute &r, bool forward) {
+    const gf_smp::DevLevel &d = s->lv[l];
+    RowProductsCall c = {forward, forward ? level_T(s, l) : level_O(s, l), r.drop ? d.rowfac8 : d.rowscale, d.Wst, forward ? level_O(s, l) : level_dT(s, l),
+                         (int)s->lay.level[l].rows, d.trow};
+    c.trowf = d.trowf, c.rowcls = d.rowcls;
+    c.wimg = d.wimg_ready ? d.wimg : nullptr;
+    c.C = s->cfg.nChanels, c.nf = r.nf, c.nx = r.extras_in_kernel ? 3 : 0;
+    // (backward, with the consumer gather reading dT: the gradients of the structurally-zero S_ab / T6 rows have no reader: not written)
+    c.skip_zero_grads = !forward && r.gather;
+    c.skip_empty = forward && r.skip_empty;
+    return c;
+}
+
 // block products: A = T column range, B = stacked weights, C = O column block.  The row-panel family (weights in LDS), else one grouped
 // launch (every row panel of T is fetched from HBM once and shared through L2 by the three products), separate launches as a fallback.
 static gf_status fwd_row_products(gf_smp *s, int l, const FusedRoute &r) {
@@ -497,9 +511,7 @@ static gf_status fwd_row_products(gf_smp *s, int l, const FusedRoute &r) {
     const int C = s->cfg.nChanels, rows = (int)s->lay.level[l].rows;
     const size_t CC = (size_t)C * C;
     float *T = level_T(s, l), *O = level_O(s, l);
-    if (r.panels)
-        return smp_rowpanel_products_c64(ctx, true, T, r.drop ? d.rowfac8 : d.rowscale, d.Wst, O, rows, d.trow, d.trowf, false,
-                                         d.wimg_ready ? d.wimg : nullptr, C, r.nf, r.extras_in_kernel ? 3 : 0, d.rowcls, nullptr, r.skip_empty);
+    if (r.panels) return smp_row_products(ctx, row_products_call(s, l, r, true));
     const int ldt = T_COLS * C, ldo = O_COLS * C;   // (the tiled launches always use the three-block layout)
     const long long tC = C, wCC = (long long)CC;
     const GemmSpec sp[3] = {
@@ -812,12 +824,9 @@ static gf_status bwd_table_grads(gf_smp *s, int l, const FusedRoute &r, const fl
     const size_t CC = (size_t)C * C;
     float *dO = level_O(s, l), *dT = level_dT(s, l);
     if (r.panels) {
-        // (with the consumer gather reading dT, the gradients of the structurally-zero S_ab / T6 rows have no reader: not written)
-        const int nx = r.extras_in_kernel ? 3 : 0;
-        const RowpanelDz dz = {dz_vec, d.sgn, d.rowcls_node};
-        const bool form_dz = dz_vec && d.rowcls_node && smp_rowpanel_dz_applies(ctx, rows, d.trow, d.trowf, r.gather, C, r.nf, nx, d.rowcls);
-        return smp_rowpanel_products_c64(ctx, false, dO, r.drop ? d.rowfac8 : d.rowscale, d.Wst, dT, rows, d.trow, d.trowf, r.gather,
-                                         d.wimg_ready ? d.wimg : nullptr, C, r.nf, nx, d.rowcls, form_dz ? &dz : nullptr);
+        RowProductsCall call = row_products_call(s, l, r, false);
+        if (dz_vec && d.rowcls_node && smp_row_products_can_form_dz(ctx, call)) call.dz = {dz_vec, d.sgn, d.rowcls_node};
+        return smp_row_products(ctx, call);
     }
     const int ldt = T_COLS * C, ldo = O_COLS * C;
     const long long oC = C, wCC = (long long)CC;

@@ -1,7 +1,8 @@
 // smp_internal.h -- state of one gf_smp handle (gf_smp_batch: what one prepared batch owns; gf_smp: what survives it) and what its translation
 // units share: smp.hip (create / plan, the sweeps, op-by-op levels), smp_prepare.hip (buffer pool, device-built tables, every path of
 // gf_smp_prepare* on one begin_batch / finish_batch skeleton), smp_pad.hip (channel padding, the ver6 / ver7
-// embedding), smp_optim.hip (host-pointer mode, optimisers, checkpoints), smp_fused.hip + smp_level_*.hip (fused levels), smp_model.hip.
+// embedding), smp_optim.hip (host-pointer mode, optimisers, checkpoints), smp_fused.hip + smp_level_*.hip (fused levels; the fused level's block products
+// and their weight gradients are called through RowProductsCall / WgradCall below, their two files share smp_split.h), smp_model.hip.
 // Which configurations become a handle is smp_config.h's business, the parameter layout smp_prep.h's (gfsmp::Config::level_blocks).
 #ifndef GF_SMP_INTERNAL_H_INCLUDED
 #define GF_SMP_INTERNAL_H_INCLUDED
@@ -42,30 +43,42 @@ gf_status gemm_grouped_free_tn(gf_ctx *ctx, const GemmSpec *specs, int n, float 
 bool gemm_grouped_supported(const GemmSpec *specs, int n, bool ta, bool tb);
 gf_status gemm_grouped_rows(gf_ctx *ctx, bool ta, bool tb, const GemmSpec *specs, int n, int rows, int accumulate = 0);
 gf_status gemm_grouped_splitk(gf_ctx *ctx, const GemmSpec *specs, int n, int rows, float *dest, int accumulate);
-// trow != nullptr: compact O / dO layout ([O_loc | U], 2C wide) with the transposed-row gather inside the product (see kernel)
-// trowf (optional): the level's packed table with the presence bits of the S_ab / T6 blocks (DevLevel::trowf)
-// dz (backward, C = 64, the row-class kernel -- smp_rowpanel_dz_applies; else null): the L block of dO is formed by the kernel from the
-// read-out's per-node vector and the level's sign words instead of read (see smp_rowpanel_split, DZ)
+// ---- the eight row block products of a fused level (smp_level_c64_split.hip; the fp32 pipe's kernel: smp_level_c64.hip), C = 16 / 32 / 64 / 128 ----
+// dz (backward, C = 64, the row-class kernel -- smp_row_products_can_form_dz; else its members null): the L block of dO is formed by the
+// kernel from the read-out's per-node vector and the level's sign words instead of read (see smp_rowpanel_split, DZ)
 struct RowpanelDz {
     const float *node_df = nullptr;   // [nodes][64]
     const unsigned *sgn = nullptr;    // [rows][2]
     const int *ent_node = nullptr;    // [class-list entries] node of the entry's row
 };
-gf_status smp_rowpanel_products_c64(gf_ctx *ctx, bool forward, const float *A, const float *rowscale, const float *Wst, float *Out,
-                                    int rows, const int *trow, const int *trowf = nullptr, bool skip_zero_grads = false,
-                                    const void *wimg = nullptr, int C = 64,   // C = 32 (round 4): split products with prebuilt images only
-                                    int nf = 2, int nx = 0,   // row factors per row of `rowscale`: 2 = (tot, tr); 8 = one per product (slice dropout, C = 32)
-                                    const int *rowcls = nullptr,   // the table's row classes (C = 64 with trowf: panels of one class, see smp_rowpanel_split)
-                                    const RowpanelDz *dz = nullptr,
-                                    bool skip_empty = false);   // forward, C = 64, packed table: rows without any data are not stored (FusedRoute::skip_empty)
-// will a backward call with these arguments run the row-class kernel (the one that can form dz itself)?
-bool smp_rowpanel_dz_applies(const gf_ctx *ctx, int rows, const int *trow, const int *trowf, bool skip_zero_grads, int C, int nf, int nx, const int *rowcls);
+// One call: forward O from T = [S_ab|S_bc|T6|T10], or backward dT from dO, on `rows` rows.
+struct RowProductsCall {
+    bool forward;
+    const float *A, *rowscale, *Wst;   // the operand rows, nf factors per row, the level's stacked weights
+    float *Out;
+    int rows;
+    const int *trow;             // != nullptr: compact O / dO layout ([O_loc | U], 2C wide) with the transposed-row gather inside the product (see kernel)
+    const int *trowf = nullptr;  // (optional) the level's packed table with the presence bits of the S_ab / T6 blocks (DevLevel::trowf)
+    const int *rowcls = nullptr; // the table's row classes (C = 64 with trowf: panels of one class, see smp_rowpanel_split)
+    const void *wimg = nullptr;  // the level's prebuilt weight images (smp_split_build_images); C != 64: split products with prebuilt images only
+    int C = 64;
+    int nf = 2, nx = 0;          // row factors per row of `rowscale`: 2 = (tot, tr); 8 = one per product (slice dropout, C = 32 / 16); nx = 3: SMP_2D_ver7's extra products
+    bool skip_zero_grads = false;   // backward: the gradients of the structurally-zero S_ab / T6 blocks have no reader and are not stored
+    bool skip_empty = false;     // forward, C = 64, packed table: rows without any data are not stored (FusedRoute::skip_empty)
+    RowpanelDz dz;               // dz.node_df null: none
+};
+// THE entry point: picks the kernel (row_products_kernel of smp_level_c64_split.hip -- the one place that decides which kernel runs and
+// whether a call is admissible) and launches it.  Every output element is produced by one wave in a fixed order: results do not depend
+// on the grid size.
+gf_status smp_row_products(gf_ctx *ctx, const RowProductsCall &call);
+// the refusal of a call the choice does not admit (status, reason recorded), before anything is launched; GF_OK otherwise
+gf_status smp_row_products_admissible(gf_ctx *ctx, const RowProductsCall &call);
+// will this backward call run the row-class kernel (the one that can form dz itself)?  Asked with call.dz still empty.
+bool smp_row_products_can_form_dz(const gf_ctx *ctx, const RowProductsCall &call);
 // the compact-layout products on the f16 matrix pipe with two-half fp32 operands (smp_level_c64_split.hip; GF_SMP_SPLIT=0: fp32 MFMA)
 bool smp_split_products(const gf_ctx *ctx);
-gf_status smp_rowpanel_split_c64(gf_ctx *ctx, bool forward, const float *A, const float *rowscale, const float *Wst, float *Out,
-                                 int rows, const int *trow, int cus, const int *trowf = nullptr, bool skip_zero_grads = false,
-                                 const void *wimg = nullptr, int C = 64, int nf = 2, int nx = 0, const int *rowcls = nullptr,
-                                 const RowpanelDz *dz = nullptr, bool skip_empty = false);
+// (smp_level_c64.hip: the fp32 kernel's launch, for smp_row_products; trow null: the three-block O layout)
+gf_status smp_row_products_fp32_c64(gf_ctx *ctx, bool forward, const float *A, const float *rowscale, const float *Wst, float *Out, int rows, const int *trow);
 // the row classes of a level's packed table (smp_prepare.hip: row_class_count): buffer size in ints, and the builder
 // live_only: a row with none of the three presence bits (an EMPTY row: no data in any block of T) goes into neither list
 size_t smp_row_class_ints(int rows, bool live_only = false);
@@ -79,7 +92,7 @@ gf_status smp_small_split_c64(gf_ctx *ctx, bool transposed, int n, const int *pr
                               const int *pos0, const void *wimg, const char *name, int C = 64);
 gf_status splitk_fold(gf_ctx *ctx, const float *part, float *dest, size_t total, int splits, int accumulate);
 
-// ---- the weight gradients of a fused level's eight row block products (the end of smp_level_c64_split.hip), C = 16 / 32 / 64 / 128 ----
+// ---- the weight gradients of a fused level's eight row block products (smp_level_wgrad_split.hip), C = 16 / 32 / 64 / 128 ----
 // Where the split-operand kernels take their per-column exponents from: the level's per-channel maxima `chan` ([2 C] float bits: max
 // |f_{l-1}| then max |dz_l|, smp_wgrad_channel_maxima) with the largest receptive field and row factors of the level -- or nothing: exact
 // column bounds are then taken from the operands themselves (one extra pass over T and dO).
@@ -193,7 +206,7 @@ struct gf_smp_batch {
         // sweep takes LeakyReLU'(f_l) from them instead of reading f_l (smp_sign_mask).  Rows of nodes above 32 positions: not written.
         unsigned *sgn = nullptr;
         bool sgn_ready = false;    // ... written by this forward pass
-        // per-channel maxima for the weight gradients' column exponents (smp_level_c64_split.hip: WgradScales::chan):
+        // per-channel maxima for the weight gradients' column exponents (smp_level_wgrad_split.hip: WgradScales::chan):
         float *pmax = nullptr;     // [fwd_npanels][64] largest |f_l| of every row panel, left by combine-forward (levels below the top)
         float *dzmax = nullptr;    // [max(quads, row panels)][64] largest |dz| of every workgroup / panel of combine-backward
         long long dz_rows = 0;     // ... rows of it the last combine-backward wrote
@@ -303,7 +316,7 @@ struct gf_smp_batch {
     unsigned *tab_stats = nullptr;          // [levels + 1][4]: max |tot|, max |tr| (float bits), rows with data (two words)
     std::vector<unsigned> h_tab_stats;
     std::vector<long long> h_covered;       // [levels + 1] cache of gf_smp_level_covered_rows (-1 = not read yet), cleared by prepare
-    // [levels + 1][smp_wgrad_words(C, C != 64)] scratch words of the levels' weight gradients (smp_level_c64_split.hip: wgrad_words): the
+    // [levels + 1][smp_wgrad_words(C, C != 64)] scratch words of the levels' weight gradients (smp_level_wgrad_split.hip: wgrad_words): the
     // per-channel maxima of f_{l-1} and of dz_l (at C = 64 nothing else, zeroed at the start of every forward) and the exact column bounds
     unsigned *wbound = nullptr;
     float *x = nullptr;      // [nVertices][FD]

@@ -373,10 +373,9 @@ gf_status row_proj_launch(gf_ctx *ctx, const float *K, const float *X, const flo
     static int resident[64] = {};
     const int di = ctx->device & 63;
     if (!resident[di]) {
-        int cus = 0, per_cu = 0;
-        GF_HIP_TRY(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+        int per_cu = 0;
         GF_HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v5_row_proj<NT, VEC, FWD>, 256, lds));
-        resident[di] = (cus < 1 ? 256 : cus) * (per_cu < 1 ? 1 : per_cu);
+        resident[di] = device_cu_count(ctx) * (per_cu < 1 ? 1 : per_cu);
     }
     // (max_workgroups > 0: a smaller grid still, for the stand-alone operator -- a small input then strides; the level passes 0)
     long long blocks = ((rows + 31) / 32 + 3) / 4;

@@ -427,7 +427,7 @@ __global__ __launch_bounds__(TH, 1) void smp_rowpanel_c64(const float *__restric
 
 // The eight row block products A_p^T B_p of a fused SMP level at C = 64 (see smp_wgrad_c64) on the fp32 matrix pipe, as PARTIAL images:
 // `splits` images of 8 x 64 x 64 floats, one per range of `kchunk` rows (a multiple of BK).  T = [rows][256], dO = [rows][192] or
-// (trow) [rows][128], rowscale = [rows][2].  Called by smp_wgrad_partials (smp_level_c64_split.hip), which plans the ranges.
+// (trow) [rows][128], rowscale = [rows][2].  Called by smp_wgrad_partials (smp_level_wgrad_split.hip), which plans the ranges.
 gf_status smp_wgrad_fp32_c64(gf_ctx *ctx, const float *T, const float *dO, const float *rowscale, int rows, int kchunk, int splits, float *part,
                              const int *trow) {
     const size_t lds = sizeof(float) * 2 * (size_t)kWgStage;
@@ -437,48 +437,29 @@ gf_status smp_wgrad_fp32_c64(gf_ctx *ctx, const float *T, const float *dO, const
     return GF_OK;
 }
 
-// Row-panel products of a fused SMP level at C = 64 (see smp_rowpanel_c64): forward O from T, or backward dT from dO.
-// Every output element is produced by one wave in a fixed order: results do not depend on the grid size.
-gf_status smp_rowpanel_products_c64(gf_ctx *ctx, bool forward, const float *A, const float *rowscale, const float *Wst, float *Out,
-                                    int rows, const int *trow, const int *trowf, bool skip_zero_grads, const void *wimg, int C, int nf, int nx,
-                                    const int *rowcls, const RowpanelDz *dz, bool skip_empty) {
-    if (rows < 1) return GF_OK;
-    static int cu_count[64] = {};
-    const int di = ctx->device & 63;
-    if (!cu_count[di]) {
-        GF_HIP_TRY(ctx, hipDeviceGetAttribute(&cu_count[di], hipDeviceAttributeMultiprocessorCount, ctx->device));
-        if (cu_count[di] < 1) cu_count[di] = 256;
-    }
-    const int cus = cu_count[di];
-    if (trow && smp_split_products(ctx)) return smp_rowpanel_split_c64(ctx, forward, A, rowscale, Wst, Out, rows, trow, cus, trowf, skip_zero_grads, wimg, C, nf, nx, rowcls, dz, skip_empty);
-    if (skip_empty) return fail(ctx, GF_ERR_INVALID, "smp_rowpanel_products: only the split row-panel kernel leaves the empty rows unstored");
-    if (dz) return fail(ctx, GF_ERR_INVALID, "smp_rowpanel_products: dz is formed by the split row-class kernel only");
-    if (C != 64 || nf != 2 || nx != 0) return fail(ctx, GF_ERR_UNSUPPORTED, "smp_rowpanel_products: %d channels / %d row factors / %d extra products on the fp32 matrix pipe", C, nf, nx);
+namespace {
+// one instantiation of smp_rowpanel_c64 on one persistent workgroup per CU (the weight image takes 144 KB of LDS)
+template <bool F, int T, bool Cm>
+gf_status launch_rowpanel_c64(gf_ctx *ctx, const float *A, const float *rowscale, const float *Wst, float *Out, int rows, const int *trow) {
     const size_t lds = sizeof(float) * 8 * 2 * 2 * 32 * (size_t)kRpWRow;
-    // forward: four waves per SIMD (measured equal to two); backward: two waves per SIMD with 256 registers -- the 128-register
-    // build of the backward panel spills 100 B per lane and waits for one block request per panel (1.84 -> 1.66 ms at cfg3).
-    // The compact layout (trow given) keeps four operand blocks in registers: two waves per SIMD in both directions.
-    const int th = (forward && !trow) ? 1024 : 512;
-    const int npanels = (rows + 31) / 32, per = th / 64;
+    const int npanels = (rows + 31) / 32, per = T / 64, cus = device_cu_count(ctx);
     const int want = (npanels + per - 1) / per;
-    const int grid = want < cus ? want : cus;  // one persistent workgroup per CU (the weight image takes 144 KB of LDS)
-    const char *name = forward ? "smpf_products_fwd" : "smpf_products_bwd";
-#define GF_RP_LAUNCH(F, T, Cm)                                                                                              \
-    do {                                                                                                                    \
-        gf_status st__ = opt_in_lds(ctx, smp_rowpanel_c64<F, T, Cm>, lds);                                                  \
-        if (st__ != GF_OK) return st__;                                                                                     \
-        GF_LAUNCH(ctx, name, (smp_rowpanel_c64<F, T, Cm>), dim3((unsigned)grid), dim3(T), lds, A, rowscale, Wst, Out, rows, trow); \
-    } while (0)
-    if (trow) {
-        if (forward) GF_RP_LAUNCH(true, 512, true);
-        else GF_RP_LAUNCH(false, 512, true);
-    } else if (forward) {
-        GF_RP_LAUNCH(true, 1024, false);
-    } else {
-        GF_RP_LAUNCH(false, 512, false);
-    }
-#undef GF_RP_LAUNCH
+    const int grid = want < cus ? want : cus;
+    const gf_status st = opt_in_lds(ctx, smp_rowpanel_c64<F, T, Cm>, lds);
+    if (st != GF_OK) return st;
+    GF_LAUNCH(ctx, F ? "smpf_products_fwd" : "smpf_products_bwd", (smp_rowpanel_c64<F, T, Cm>), dim3((unsigned)grid), dim3(T), lds, A, rowscale, Wst, Out, rows, trow);
     return GF_OK;
+}
+}  // namespace
+
+// Row-panel products of a fused SMP level at C = 64 (see smp_rowpanel_c64) on the fp32 matrix pipe: forward O from T, or backward dT from
+// dO.  Called by smp_row_products (smp_level_c64_split.hip), which decides that this kernel runs.
+// forward: four waves per SIMD (measured equal to two); backward: two waves per SIMD with 256 registers -- the 128-register
+// build of the backward panel spills 100 B per lane and waits for one block request per panel (1.84 -> 1.66 ms at cfg3).
+// The compact layout (trow given) keeps four operand blocks in registers: two waves per SIMD in both directions.
+gf_status smp_row_products_fp32_c64(gf_ctx *ctx, bool forward, const float *A, const float *rowscale, const float *Wst, float *Out, int rows, const int *trow) {
+    if (trow) return forward ? launch_rowpanel_c64<true, 512, true>(ctx, A, rowscale, Wst, Out, rows, trow) : launch_rowpanel_c64<false, 512, true>(ctx, A, rowscale, Wst, Out, rows, trow);
+    return forward ? launch_rowpanel_c64<true, 1024, false>(ctx, A, rowscale, Wst, Out, rows, trow) : launch_rowpanel_c64<false, 512, false>(ctx, A, rowscale, Wst, Out, rows, trow);
 }
 
 }  // namespace gf

@@ -1,7 +1,7 @@
 // smp_level_ops.hip -- the block products of the fused SMP level as stand-alone operators of the C ABI
 // (gf_smp_level_products_f32 / gf_smp_level_wgrad_f32 at C = 64, gf_smp_level_products_ex_f32 / gf_smp_level_wgrad_ex_f32 for every
 // variant the level has -- 128 channels as four 64-channel sub-block passes included --, include/gf_hip.h): the same kernels gf_smp_forward / gf_smp_backward launch
-// on a level's rows (smp_level_c64.hip on the fp32 matrix pipe, smp_level_c64_split.hip on the f16 pipe with two-half operands),
+// on a level's rows (smp_level_c64.hip on the fp32 matrix pipe, smp_level_c64_split.hip / smp_level_wgrad_split.hip on the f16 pipe with two-half operands),
 // on caller-supplied matrices.  They replace, for the rows of one level, the K-projection MatMul of the reference
 // (GraphFlow/SMP_omega.h:654-657 forward, MatMul.h:69-82 backward) in its regrouped form (smp_fused.hip header) -- and they are
 // what the parity suite uses to hold the split-operand arithmetic to the fp64 product per output ROW and per weight-gradient ROW,
@@ -37,7 +37,7 @@ __global__ void scale_words(unsigned *__restrict__ w, int n, const unsigned *__r
     if (i < n) w[i] = __float_as_uint(__uint_as_float(w[i]) * __uint_as_float(by[0]));
 }
 
-// rows the gathered operand dU[trow] of the weight-gradient kernels may lie from its own row (kTrowWindow of smp_level_c64_split.hip)
+// rows the gathered operand dU[trow] of the weight-gradient kernels may lie from its own row (kTrowWindow of smp_level_wgrad_split.hip)
 constexpr long long kGatherWindow = (long long)kFusedMaxField * kFusedMaxField;
 
 // The tables of a stand-alone call, checked on the host (one blocking copy each: these are test operators): every trow inside the
@@ -63,11 +63,12 @@ gf_status check_tables(gf_ctx *ctx, const char *who, int rows, const int *trow, 
     return GF_OK;
 }
 
-// the variants the level's kernels have (before any launch): 0, or the status with the reason recorded
-// (weight gradients, `products` false, at C = 64: with a packed table only -- `packed` -- the plain table is gf_smp_level_wgrad_f32's)
-gf_status check_variant(gf_ctx *ctx, const char *who, int C, int nf, int nx, bool products, bool packed = false) {
-    if (!(C == 16 || C == 32 || (C == 64 && (products || packed)) || C == 128)) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d channels", who, C);
-    if (C == 64 && !products && !smp_split_products(ctx))   // (the fp32 kernel does not mask: it would read the absent blocks)
+// the variants the level's weight-gradient kernels have (before any launch): 0, or the status with the reason recorded
+// (at C = 64: with a packed table only -- `packed` -- the plain table is gf_smp_level_wgrad_f32's).  The products' variants:
+// smp_row_products_admissible.
+gf_status check_wgrad_variant(gf_ctx *ctx, const char *who, int C, int nf, int nx, bool packed) {
+    if (!(C == 16 || C == 32 || (C == 64 && packed) || C == 128)) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d channels", who, C);
+    if (C == 64 && !smp_split_products(ctx))   // (the fp32 kernel does not mask: it would read the absent blocks)
         return fail(ctx, GF_ERR_UNSUPPORTED, "%s: the packed table at 64 channels on the fp32 matrix pipe", who);
     if ((nf != 2 && nf != 8) || (nx != 0 && nx != 3)) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: %d row factors / %d extra products", who, nf, nx);
     if (nx == 3 && nf == 8) return fail(ctx, GF_ERR_UNSUPPORTED, "%s: the extra products take the plain (tot, tr) row factors", who);
@@ -87,7 +88,8 @@ gf_status gf_smp_level_products_f32(gf_ctx *ctx, int backward, int rows, const f
     if (rows < 0 || (rows > 0 && (!A || !rowscale || !Wst || !trow || !Out)))
         return fail(ctx, GF_ERR_INVALID, "gf_smp_level_products_f32: null argument");
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return gf::smp_rowpanel_products_c64(ctx, backward == 0, A, rowscale, Wst, Out, rows, trow);
+    const gf::RowProductsCall call = {backward == 0, A, rowscale, Wst, Out, rows, trow};
+    return gf::smp_row_products(ctx, call);
 }
 
 gf_status gf_smp_level_wgrad_f32(gf_ctx *ctx, int rows, const float *T, const float *dO, const float *rowscale, const int *trow,
@@ -121,30 +123,34 @@ gf_status gf_smp_level_products_ex_f32(gf_ctx *ctx, int backward, int C, int nf,
     if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
     if (rows < 0 || (rows > 0 && (!A || !rowfac || !Wst || !trow || !Out))) return fail(ctx, GF_ERR_INVALID, "%s: null argument", who);
     if (nx == 3 && !X) return fail(ctx, GF_ERR_INVALID, "%s: three extra products without their weight blocks", who);
-    gf_status st = gf::check_variant(ctx, who, C, nf, nx, true);
-    if (st != GF_OK) return st;
-    if (rows == 0) return GF_OK;
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    st = gf::check_tables(ctx, who, rows, trow, trowf, 0);
-    if (st != GF_OK) return st;
-    void *img = nullptr;
-    const int *rowcls = nullptr;
-    if (gf::smp_split_products(ctx)) {
-        // the level's prebuilt weight images (both directions).  The builder reads the level's EIGHTEEN stacked blocks: the eight row
-        // products' first, the other ten as zeros
-        const size_t CC = (size_t)C * C, img_bytes = gf::align_up(gf::smp_split_image_bytes(C), 256);
-        // ... and, for a packed table at C = 64, the table's row classes behind them (the level builds them once per batch)
-        const size_t w_bytes = gf::align_up(sizeof(float) * 18 * CC, 256);
-        const bool classes = trowf && C == 64 && rows < (1 << 29);
+    gf::RowProductsCall call = {backward == 0, A, rowfac, Wst, Out, rows, trow};
+    call.trowf = trowf, call.C = C, call.nf = nf, call.nx = nx, call.skip_zero_grads = skip_zero_grads != 0;
+    // On the split kernels the call carries what a level prepares for them: its prebuilt weight images (both directions) and, for a
+    // packed table at C = 64, the table's row classes (the level builds them once per batch).  Their room in the workspace comes first,
+    // so that the choice sees the whole call, refusals come before anything is launched, and an empty matrix is refused like any other.
+    const size_t CC = (size_t)C * C, img_bytes = gf::align_up(gf::smp_split_image_bytes(C), 256), w_bytes = gf::align_up(sizeof(float) * 18 * CC, 256);
+    const bool split = gf::smp_split_products(ctx), classes = split && trowf && C == 64 && rows < (1 << 29);
+    gf_status st = GF_OK;
+    int *cls = nullptr;
+    if (split) {
         st = gf::ensure_ws(ctx, img_bytes + w_bytes + (classes ? sizeof(int) * gf::smp_row_class_ints(rows) : 0) + 256);
         if (st != GF_OK) return st;
-        if (classes) {
-            int *buf = reinterpret_cast<int *>(static_cast<char *>(ctx->ws) + img_bytes + w_bytes);
-            st = gf::smp_build_row_classes(ctx, ctx->stream, trowf, rows, buf);
+        call.wimg = ctx->ws;
+        if (classes) call.rowcls = cls = reinterpret_cast<int *>(static_cast<char *>(ctx->ws) + img_bytes + w_bytes);
+    }
+    st = gf::smp_row_products_admissible(ctx, call);
+    if (st != GF_OK) return st;
+    if (rows == 0) return GF_OK;
+    st = gf::check_tables(ctx, who, rows, trow, trowf, 0);
+    if (st != GF_OK) return st;
+    if (split) {
+        if (cls) {
+            st = gf::smp_build_row_classes(ctx, ctx->stream, trowf, rows, cls);
             if (st != GF_OK) return st;
-            rowcls = buf;
         }
-        img = ctx->ws;
+        // the builder reads the level's EIGHTEEN stacked blocks: the eight row products' first, the other ten as zeros
+        void *img = ctx->ws;
         float *w18 = reinterpret_cast<float *>(static_cast<char *>(ctx->ws) + img_bytes);
         GF_HIP_TRY(ctx, hipMemcpyAsync(w18, Wst, sizeof(float) * 8 * CC, hipMemcpyDeviceToDevice, ctx->stream));
         GF_HIP_TRY(ctx, hipMemsetAsync(w18 + 8 * CC, 0, sizeof(float) * 10 * CC, ctx->stream));
@@ -152,7 +158,7 @@ gf_status gf_smp_level_products_ex_f32(gf_ctx *ctx, int backward, int C, int nf,
         st = gf::smp_split_build_images(ctx, &wp, &img, 1, C, &xp);
         if (st != GF_OK) return st;
     }
-    return gf::smp_rowpanel_products_c64(ctx, backward == 0, A, rowfac, Wst, Out, rows, trow, trowf, skip_zero_grads != 0, img, C, nf, nx, rowcls);
+    return gf::smp_row_products(ctx, call);
 }
 
 gf_status gf_smp_level_row_classes(gf_ctx *ctx, int rows, const int *trowf, int *lists) {
@@ -174,7 +180,7 @@ gf_status gf_smp_level_wgrad_ex_f32(gf_ctx *ctx, int C, int nf, int nx, int rows
     if (!ctx) return fail(nullptr, GF_ERR_INVALID, "null context");
     if (rows < 1 || !T || !dO || !rowfac || !trow || !dWst) return fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
     if (nx == 3 && !dX) return fail(ctx, GF_ERR_INVALID, "%s: three extra products without a place for their gradients", who);
-    gf_status st = gf::check_variant(ctx, who, C, nf, nx, false, trowf != nullptr);
+    gf_status st = gf::check_wgrad_variant(ctx, who, C, nf, nx, trowf != nullptr);
     if (st != GF_OK) return st;
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     st = gf::check_tables(ctx, who, rows, trow, trowf, gf::kGatherWindow);

@@ -1,5 +1,5 @@
 """The fused SMP level at 128 channels: every 128 x 128 block product as four 64 x 64 sub-block passes (reduction half i, output half j)
-of the split-operand row-panel kernels, the weight gradients as four independent 64 x 64 jobs per product (smp_level_c64_split.hip, W = 2).
+of the split-operand row-panel kernels, the weight gradients as four independent 64 x 64 jobs per product (smp_level_c64_split.hip, smp_level_wgrad_split.hip: W = 2).
 
 1. The stand-alone operators gf_smp_level_products_ex_f32 / gf_smp_level_wgrad_ex_f32 at C = 128 against the fp64 product of the same
    operands (tests/level_ref.py), per (row, block of 128 columns) and per (weight-gradient block, row), TOL = 1e-5: level-shaped rows

@@ -1,5 +1,5 @@
-"""Every variant of the fused level's block products (gf_smp_level_products_ex_f32 / gf_smp_level_wgrad_ex_f32: smp_rowpanel_split and
-smp_wgrad_all of smp_level_c64_split.hip at C = 64 / 32 / 16, two or eight row factors, with and without the three extra products, on the
+"""Every variant of the fused level's block products (gf_smp_level_products_ex_f32 / gf_smp_level_wgrad_ex_f32: smp_rowpanel_split of
+smp_level_c64_split.hip and smp_wgrad_all of smp_level_wgrad_split.hip at C = 64 / 32 / 16, two or eight row factors, with and without the three extra products, on the
 plain and on the packed table) against the fp64 product of the same operands (tests/level_ref.py), normalised per (row, block of C
 columns) and per (weight-gradient block, row) -- on level-shaped rows that sit on the kernels' edges: nodes of 1 .. 64 positions (the
 gathered row 3,969 rows before and after its slice, at both ends of the buffer), row counts around the 32-row panel and the 16 / 32-row
@@ -261,7 +261,7 @@ def test_refusals_leave_the_context_usable(gf):
         c = Case(list(sizes), Cc, nf if nf in (2, 8) else 2, nx, False, seed=6)
         return wgrad_status(Cc, nf, nx, c.T, c.dO, c.rf, c.trow if trow is None else trow)
 
-    for Cc, nf, nx in [(32, 8, 3), (16, 8, 3), (64, 2, 3), (64, 8, 0), (48, 2, 0), (32, 4, 0), (32, 2, 1)]:
+    for Cc, nf, nx in [(32, 8, 3), (16, 8, 3), (64, 2, 3), (64, 8, 0), (48, 2, 0), (32, 4, 0), (32, 2, 1), (128, 8, 0), (128, 2, 3)]:
         st, out = prod(Cc, nf, nx)
         assert st == _lib.GF_ERR_UNSUPPORTED and np.all(out == SENTINEL), (Cc, nf, nx, st)
         st, dW, _ = wg(Cc, nf, nx)

@@ -1,4 +1,4 @@
-"""The slice-based operand loads of the staged weight gradients (smp_wgrad_split of smp_level_c64_split.hip, W = 1 at 64 channels and
+"""The slice-based operand loads of the staged weight gradients (smp_wgrad_split of smp_level_wgrad_split.hip, W = 1 at 64 channels and
 W = 2 at 128): every request goes through a buffer descriptor rebased per 16-row slice -- the slice's own rows of T and dO, the gathered
 rows dU[trow] through a window of 64 x 64 rows on either side of the slice, trow and the row factors through descriptors over their
 tables -- and whatever must not be fetched (rows past the end of the level, absent blocks of the packed table) takes an out-of-range
