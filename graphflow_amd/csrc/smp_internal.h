@@ -483,26 +483,7 @@ gf_status smp_unrestricted_backward_level(gf_smp *s, int l, const float *K, cons
 // and the read-out are softmax / plain sums, not the other kinds' -- and its gf_smp_prepare.  params / grads: W1_0; (W1_l, W2_l); W.
 gf_status smp_neighbourhood_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature);
 gf_status smp_neighbourhood_backward(gf_smp *s, const float *params, float *grads, int accumulate);
-// ... and the launchers of its three level kernels on raw operands (the arguments of nbh_level_fwd / nbh_node_bwd / nbh_gather_bwd; pairs:
-// the RisiLayer2D instantiation; rounds = 0: the level's own choice), for the gated level, whose level 0 and reverse gather they are
-gf_status smp_neighbourhood_fwd_launch(gf_ctx *ctx, bool pairs, int H, int FD, int nV, int rounds, const float *W1, const float *W2, const float *x,
-                                       const float *hprev, const float *Tprev, const long long *ptr, const int *idx, float *h, float *n, float *A,
-                                       float *T, float *Tt);
-gf_status smp_neighbourhood_node_launch(gf_ctx *ctx, bool pairs, int H, int nV, int rounds, const float *W2, const float *h, float *dh,
-                                        const float *dy, const float *Wout, const int *vmol, const float *A, const float *Tt, float *dn, float *gTt,
-                                        float *sA);
-gf_status smp_neighbourhood_gather_launch(gf_ctx *ctx, bool pairs, int H, int nV, const long long *tptr, const int *tidx, const float *dn,
-                                          const float *gTt, const float *sA, const float *hprev, const float *Tprev, float *dhprev);
-// ... and on two operand sets in one launch each (blockIdx.y picks the set; the sets of include/gf_hip.h): a level of a distance handle
-gf_status smp_neighbourhood_fwd2_launch(gf_ctx *ctx, bool pairs, int H, int nV, int rounds, const gf_nbh_fwd_set *sets, const long long *ptr,
-                                        const int *idx);
-gf_status smp_neighbourhood_node2_launch(gf_ctx *ctx, bool pairs, int H, int nV, int rounds, const gf_nbh_node_set *sets, const float *dy,
-                                         const int *vmol);
-gf_status smp_neighbourhood_gather2_launch(gf_ctx *ctx, bool pairs, int H, int nV, const long long *tptr, const int *tidx,
-                                           const gf_nbh_gather_set *sets);
-// the stand-alone operators' checks of a list and of member indices (smp_level_neighbourhood.hip; one blocking copy each)
-gf_status smp_neighbourhood_check_list(gf_ctx *ctx, const char *who, const char *what, const long long *ptr, const int *idx, int n, int bound);
-gf_status smp_neighbourhood_check_members(gf_ctx *ctx, const char *who, const char *what, const int *idx, size_t n, int bound);
+// (the launches of its three level kernels on operand sets, for the gated and the distance level: smp_vertex_level.h)
 // GCN_1D_Distance, GCN_2D_Distance, GCN_3D_Distance (cfg.distance_channel; smp_level_distance.hip): the sweeps of a distance handle, its
 // gf_smp_prepare_distance (smp_prepare.hip) and the sort that builds the distance channel's input rows on the handle's upload stream.
 // params / grads: per level W1^v, W1^d (, W2^v, W2^d); W [2 H].
@@ -517,8 +498,6 @@ void smp_distance_checkpoint_order(const gfsmp::Config &c, std::vector<size_t> *
 // nbh_node_bwd then runs with dy = NULL; dW: the pair model's dW [2 H] += the fold over the pairs (a Gram handle has no W).
 gf_status smp_readout_forward(gf_smp *s, const float *W, const float *targets, float *predict, float *loss, float *graph_feature);
 gf_status smp_readout_dW(gf_smp *s, const float *W, float *dW);
-// ... and the check of a 32-bit prefix-sum table (mol_ptr, graph_ptr) of a stand-alone call: from 0, never decreasing, within `bound` rows
-gf_status smp_neighbourhood_check_ptr(gf_ctx *ctx, const char *who, const char *what, const int *ptr, int n, int bound);
 // GRU_GCN_1D, GRU_GCN_2D (cfg.neighbourhood = 4, 5; smp_level_gru.hip): the sweeps of a gated handle on the same lists and buffers.
 // params / grads: W; W_z, U_z, W_r, U_r, W_h, U_h, W_g, U_g (shared by the levels: their gradients accumulate across them); U.
 gf_status smp_gru_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature);

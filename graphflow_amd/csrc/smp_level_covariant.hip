@@ -34,12 +34,12 @@
 #include <vector>
 
 #include "smp_config.h"
-#include "smp_internal.h"
+#include "smp_vertex_level.h"
 
 namespace gf {
+using namespace vertex_level;
 namespace {
 
-constexpr int kBlock = 256;   // four waves
 constexpr float kSlope = 0.01f;
 
 // The network of one molecule per workgroup.  LDS (gf::smp_covariant_lds_bytes): five of the seven [V][Vp] images, Vp = V | 1, the vector of
@@ -369,16 +369,9 @@ size_t smp_covariant_ws_bytes(int nMol, size_t image_floats) { return sizeof(flo
 
 gf_status smp_covariant_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature) {
     gf_ctx *ctx = s->ctx;
-    const int FD = s->cfg.fdim(), M = s->cfg.max_nVertices, nMol = s->lay.nMol;
+    const int FD = s->cfg.fdim(), M = s->cfg.max_nVertices;
     const gf_status st = fwd_launch(ctx, of_handle(s), nullptr, s->x, params, FD, params + FD, targets, s->cov_h, s->cov_n, s->g, s->yhat, loss, s->dy);
-    if (st != GF_OK) return st;
-    if (predict) GF_HIP_TRY(ctx, hipMemcpyAsync(predict, s->yhat, sizeof(float) * nMol, hipMemcpyDeviceToDevice, ctx->stream));
-    if (graph_feature) GF_HIP_TRY(ctx, hipMemcpyAsync(graph_feature, s->g, sizeof(float) * nMol * M, hipMemcpyDeviceToDevice, ctx->stream));
-    s->bwd_consumed = false;
-    s->forwarded = true;
-    s->has_targets = targets != nullptr;
-    mark_used(s);
-    return GF_OK;
+    return st == GF_OK ? finish_forward(s, targets != nullptr, predict, graph_feature, M) : st;
 }
 
 // The reverse sweep from the loss of the last forward; nothing a second sweep needs is overwritten.

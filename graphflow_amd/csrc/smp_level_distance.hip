@@ -9,17 +9,16 @@
 //                    A compare-exchange swaps on a strict `<` only, so the row stays a permutation of its inputs (-0.0 and 0.0 included).
 //   the level        smp_level_neighbourhood.hip's three kernels with blockIdx.y = the channel (one forward launch, one node launch and one
 //                    gather per level for both channels); GCN_3D_Distance runs third_pool_fwd / third_pool_bwd once per channel
-//   dist_readout, dist_readout_dW   final, prediction, loss, dy; dW [2 H] in molecule order
+//   dist_readout     final, prediction, loss, dy; dW [2 H] in molecule order is smp_vertex_level.hip's vertex_readout_dW
 // The weight gradients are the library's deterministic TN products, 2 (2 L + 1) per step.  No atomics; two runs give the same bits.
 // GF_SMP_DISTANCE_LAUNCHES=2 (read per call; tools/distance_time.py): every level kernel once per channel instead -- the same bits.
 #include <cmath>
 
-#include "smp_field_level.h"
+#include "smp_vertex_level.h"
 
 namespace gf {
+using namespace vertex_level;
 namespace {
-
-constexpr int kBlock = 256;   // four waves
 
 // what a vertex's row is gathered from: entry i of column j of molecule m, zeros up to M, +inf beyond (never stored)
 struct Column {
@@ -80,11 +79,6 @@ __global__ __launch_bounds__(kBlock) void dist_rows_sort_lds(const double *__res
     for (int i = threadIdx.x; i < M; i += kBlock) xd[v * M + i] = row[i];
 }
 
-__device__ __forceinline__ float wave_sum(float v) {   // every lane gets the same bits
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // one wave per molecule: g = [sum_v h^v_L | sum_v h^d_L] over its vertices (ascending), predict = <W, g>, the squared loss, dy
 __global__ __launch_bounds__(64) void dist_readout(const float *__restrict__ hv, const float *__restrict__ hd, const int *__restrict__ mol_ptr,
                                                    const float *__restrict__ W, const float *__restrict__ target, float *__restrict__ g,
@@ -99,29 +93,7 @@ __global__ __launch_bounds__(64) void dist_readout(const float *__restrict__ hv,
         part = fmaf(acc, W[c], part);
     }
     part = wave_sum(part);
-    if (threadIdx.x == 0) {
-        const float t = target ? target[m] : 0.f;
-        yhat[m] = part;
-        if (loss) loss[m] = 0.5f * (part - t) * (part - t);
-        dy[m] = part - t;   // SquaredLoss::backward
-    }
-}
-
-// dW[c] += sum_m dy[m] g[m][c], c < 2 H: 64 columns per workgroup, row r of its 16 sums the molecules r, r + 16, .., folded in order
-__global__ __launch_bounds__(1024) void dist_readout_dW(const float *__restrict__ dy, const float *__restrict__ g, float *__restrict__ dW, int W2,
-                                                        int nMol) {
-    __shared__ float part[16][64];
-    const int lane = threadIdx.x & 63, r = threadIdx.x >> 6, c = blockIdx.x * 64 + lane;
-    const int cc = c < W2 ? c : W2 - 1;
-    float acc = 0.f;
-    for (int m = r; m < nMol; m += 16) acc = fmaf(dy[m], g[(size_t)m * W2 + cc], acc);
-    part[r][lane] = acc;
-    __syncthreads();
-    if (r == 0 && c < W2) {
-        float t = 0.f;
-        for (int k = 0; k < 16; ++k) t += part[k][lane];
-        dW[c] += t;
-    }
+    GF_STORE_PREDICTION(m, part, target, yhat, loss, dy);
 }
 
 // The flat buffer in registration order: per level W1^v_l [H][F'], W1^d_l [H][M] and from level 1 on W2^v_l, W2^d_l [H][H]; W [2 H].
@@ -183,19 +155,16 @@ gf_status level_forward(gf_smp *s, int l, const View<const float> &p) {
             const gf_status st = smp_third_pool_fwd_launch(ctx, H, nV, d.nb_max_members, pv->f, d.nb_ptr, d.nb_idx, d.nb_pool, d.nb_sel);
             if (st != GF_OK) return st;
         }
-        set[ch] = {width[ch], p.W1[ch][l], x[ch], p.W2[ch][l], third ? d.nb_pool : pv ? pv->f : nullptr, pv ? pv->nb_T : nullptr, d.f, d.th_A, d.th_B,
-                   d.nb_T, d.nb_Tt};
+        set[ch] = {width[ch], p.W1[ch][l], x[ch], p.W2[ch][l], /*hprev=*/third ? d.nb_pool : pv ? pv->f : nullptr, /*Tprev=*/pv ? pv->nb_T : nullptr,
+                   /*h=*/d.f, /*n=*/d.th_A, /*A=*/d.th_B, /*T=*/d.nb_T, /*Tt=*/d.nb_Tt};
     }
     const gf_smp::DevLevel &d0 = s->lv[l];
     const long long *ptr = third ? s->nb_id_ptr : d0.nb_ptr;
     const int *idx = third ? s->nb_id_idx : d0.nb_idx;
-    if (!per_channel_launches()) return smp_neighbourhood_fwd2_launch(ctx, pairs, H, nV, 0, set, ptr, idx);
-    for (int ch = 0; ch < 2; ++ch) {
-        const gf_nbh_fwd_set &o = set[ch];
-        const gf_status st = smp_neighbourhood_fwd_launch(ctx, pairs, H, o.FD, nV, 0, o.W1, o.W2, o.x, o.hprev, o.Tprev, ptr, idx, o.h, o.n, o.A, o.T, o.Tt);
-        if (st != GF_OK) return st;
-    }
-    return GF_OK;
+    if (!per_channel_launches()) return smp_neighbourhood_fwd(ctx, pairs, H, nV, 0, set, 2, ptr, idx);
+    gf_status st = GF_OK;
+    for (int ch = 0; ch < 2 && st == GF_OK; ++ch) st = smp_neighbourhood_fwd(ctx, pairs, H, nV, 0, &set[ch], 1, ptr, idx);
+    return st;
 }
 
 // dz_l in place of dh_l (the top level from dy and its half of W) and dh_{l-1}, both channels
@@ -210,15 +179,14 @@ gf_status level_backward(gf_smp *s, int l, const View<const float> &p) {
     for (int ch = 0; ch < 2; ++ch) {
         gf_smp::DevLevel &d = level_of(s, ch, l);
         gf_smp::DevLevel *pv = l ? &level_of(s, ch, l - 1) : nullptr;
-        node[ch] = {p.W2[ch][l], d.f, d.df, top ? p.W + (size_t)ch * H : nullptr, d.th_B, d.nb_Tt, d.Q, d.th_node, d.nb_sA};
-        gat[ch] = {d.Q, d.th_node, d.nb_sA, pv ? pv->f : nullptr, pv ? pv->nb_T : nullptr, pv ? pv->df : nullptr};
+        node[ch] = {p.W2[ch][l], /*h=*/d.f, /*dh=*/d.df, /*Wout=*/top ? p.W + (size_t)ch * H : nullptr, /*A=*/d.th_B, /*Tt=*/d.nb_Tt,
+                    /*dn=*/d.Q, /*gTt=*/d.th_node, /*sA=*/d.nb_sA};
+        gat[ch] = {/*dn=*/d.Q, /*gTt=*/d.th_node, /*sA=*/d.nb_sA, /*hprev=*/pv ? pv->f : nullptr, /*Tprev=*/pv ? pv->nb_T : nullptr,
+                   /*dhprev=*/pv ? pv->df : nullptr};
     }
     gf_status st = GF_OK;
-    if (!split) st = smp_neighbourhood_node2_launch(ctx, pairs, H, nV, 0, node, dy, s->top_node_mol);
-    for (int ch = 0; ch < 2 && split && st == GF_OK; ++ch) {
-        const gf_nbh_node_set &o = node[ch];
-        st = smp_neighbourhood_node_launch(ctx, pairs, H, nV, 0, o.W2, o.h, o.dh, dy, o.Wout, s->top_node_mol, o.A, o.Tt, o.dn, o.gTt, o.sA);
-    }
+    if (!split) st = smp_neighbourhood_node(ctx, pairs, H, nV, 0, node, 2, dy, s->top_node_mol);
+    for (int ch = 0; ch < 2 && split && st == GF_OK; ++ch) st = smp_neighbourhood_node(ctx, pairs, H, nV, 0, &node[ch], 1, dy, s->top_node_mol);
     if (st != GF_OK || !l) return st;
     const gf_smp::DevLevel &d0 = s->lv[l];
     if (third) {
@@ -228,11 +196,8 @@ gf_status level_backward(gf_smp *s, int l, const View<const float> &p) {
         }
         return st;
     }
-    if (!split) return smp_neighbourhood_gather2_launch(ctx, pairs, H, nV, d0.nb_tptr, d0.nb_tidx, gat);
-    for (int ch = 0; ch < 2 && st == GF_OK; ++ch) {
-        const gf_nbh_gather_set &o = gat[ch];
-        st = smp_neighbourhood_gather_launch(ctx, pairs, H, nV, d0.nb_tptr, d0.nb_tidx, o.dn, o.gTt, o.sA, o.hprev, o.Tprev, o.dhprev);
-    }
+    if (!split) return smp_neighbourhood_gather(ctx, pairs, H, nV, d0.nb_tptr, d0.nb_tidx, gat, 2);
+    for (int ch = 0; ch < 2 && st == GF_OK; ++ch) st = smp_neighbourhood_gather(ctx, pairs, H, nV, d0.nb_tptr, d0.nb_tidx, &gat[ch], 1);
     return st;
 }
 
@@ -269,13 +234,7 @@ gf_status smp_distance_forward(gf_smp *s, const float *params, const float *targ
     }
     GF_LAUNCH(ctx, "dist_readout", dist_readout, dim3(nMol), dim3(64), 0, s->lv[L].f, s->lvd[L].f, s->mol_ptr, p.W, targets, s->g, s->yhat, loss, s->dy,
               H);
-    if (predict) GF_HIP_TRY(ctx, hipMemcpyAsync(predict, s->yhat, sizeof(float) * nMol, hipMemcpyDeviceToDevice, ctx->stream));
-    if (graph_feature) GF_HIP_TRY(ctx, hipMemcpyAsync(graph_feature, s->g, sizeof(float) * nMol * 2 * H, hipMemcpyDeviceToDevice, ctx->stream));
-    s->bwd_consumed = false;
-    s->forwarded = true;
-    s->has_targets = targets != nullptr;
-    mark_used(s);
-    return GF_OK;
+    return finish_forward(s, targets != nullptr, predict, graph_feature, 2 * (size_t)H);
 }
 
 // The reverse sweep from the loss of the last forward; every level keeps what a second sweep needs (dz is rebuilt from dy downwards).
@@ -287,7 +246,8 @@ gf_status smp_distance_backward(gf_smp *s, const float *params, float *grads, in
     const float *x[2] = {s->x, s->xd};
     const int width[2] = {s->cfg.fdim(), s->cfg.max_nVertices};
     if (!accumulate) GF_HIP_TRY(ctx, hipMemsetAsync(grads, 0, sizeof(float) * param_count(s->cfg), ctx->stream));
-    GF_LAUNCH(ctx, "dist_readout_dW", dist_readout_dW, dim3((unsigned)((2 * H + 63) / 64)), dim3(1024), 0, s->dy, s->g, d.W, 2 * H, nMol);
+    const gf_status wst = smp_vertex_readout_dW(ctx, "dist_readout_dW", 2 * H, nMol, s->dy, s->g, d.W);
+    if (wst != GF_OK) return wst;
     for (int l = L; l >= 0; --l) {
         gf_status st = level_backward(s, l, p);   // dz_l in lv / lvd[l].df, dh_{l-1} in [l - 1].df
         // per channel dW1_l [H][width] += dz^T X, dW2_l [H][H] += dz^T N: tall-skinny TN products over the vertices of the batch

@@ -5,12 +5,13 @@
 //   z = sigmoid(W_z n + U_z hp),  r = sigmoid(W_r n + U_r hp),  q = r hp,  c = tanh(W_h n + U_h q),  h_l[v] = (1 - z) hp + z c
 //   g_v = sigmoid(W_g h_L[v]) tanh(U_g h_L[v]),  graph_feature = tanh(sum_v g_v),  predict = <U, graph_feature>, loss = 0.5 (predict - target)^2
 // The eight matrices are shared by all levels: their gradients accumulate across them, levels from the top down.
-//   nbh_level_fwd / nbh_node_bwd (W2 = nullptr)   level 0, through smp_neighbourhood_fwd_launch / _node_launch
+//   nbh_level_fwd / nbh_node_bwd (W2 = nullptr)   level 0, through smp_neighbourhood_fwd / _node on one operand set
 //   gru_cell_fwd     one launch per level: the six matrices transposed in LDS once per workgroup, a group of G lanes per vertex; the
 //                    gather, n and hp staged per slot, five products, q through LDS, the sixth product, gates and blend
 //   gru_cell_bwd     the six matrices as they are (lanes along a row): dz', dc', dq = U_h^T dc', dr', dn and the direct part of dh_{l-1}
-//   nbh_gather_bwd   dh_{l-1} over the transposed list (smp_neighbourhood_gather_launch), then gru_add: gather + direct
-//   gru_readout_fwd, gru_readout_mol, gru_readout_bwd, gru_readout_dU   the gates per vertex, the sum per molecule, their reverse
+//   nbh_gather_bwd   dh_{l-1} over the transposed list (smp_neighbourhood_gather), then gru_add: gather + direct
+//   gru_readout_fwd, gru_readout_mol, gru_readout_bwd   the gates per vertex, the sum per molecule, their reverse; dU is
+//                    smp_vertex_level.hip's vertex_readout_dW under the timer name gru_readout_dU
 // The eight weight gradients are the library's deterministic TN products.  Every sum runs in a fixed order; no atomics; every wave of a
 // workgroup makes the same trips around the barriers; an operand of a lane without a channel is loaded from a clamped address and never
 // stored (NOTES.md: no guard around an operand load).
@@ -19,35 +20,11 @@
 // below, for tests/test_smp_gru_ops_gpu.py.
 #include <cmath>
 
-#include "smp_internal.h"
+#include "smp_vertex_level.h"
 
 namespace gf {
+using namespace vertex_level;
 namespace {
-
-constexpr int kBlock = 256;   // four waves
-
-// (the next five are smp_level_neighbourhood.hip's, restated: that file's code object stays what it was)
-__host__ __device__ inline int row_stride(int H) { return H | 1; }   // odd: the transposing stores hit 32 different banks
-
-__device__ __forceinline__ float group_sum(float v, int G) {   // every lane of the group gets the same bits
-    for (int d = G >> 1; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// a * b rounded on its own: one member gives A Tt - a T = 0 exactly
-__device__ __forceinline__ float mul_rounded(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-
-// slot = one group of G lanes, kBlock / G of them, never across a wave; it takes vertices vbase + it + slot, it = 0, slots, .. < vpg
-struct Slot {
-    int slot, slots, c0;
-};
-__device__ __forceinline__ Slot slot_of(int G) {
-    const int lane = threadIdx.x & 63, per_wave = 64 / G;
-    return {(int)(threadIdx.x >> 6) * per_wave + lane / G, kBlock / G, lane % G};
-}
 
 __device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
 
@@ -250,13 +227,8 @@ __global__ __launch_bounds__(64) void gru_readout_mol(const float *__restrict__ 
         g[(size_t)m * H + c] = gf;
         part = fmaf(gf, U[c], part);
     }
-    part = group_sum(part, 64);
-    if (threadIdx.x == 0) {
-        const float tg = target ? target[m] : 0.f;
-        yhat[m] = part;
-        if (loss) loss[m] = 0.5f * (part - tg) * (part - tg);
-        dy[m] = part - tg;   // SquaredLoss::backward
-    }
+    part = wave_sum(part);
+    GF_STORE_PREDICTION(m, part, target, yhat, loss, dy);
 }
 
 // dgf = dy[mol] U (1 - gf^2) per vertex; ds = dgf t s (1 - s), dt = dgf s (1 - t^2) (the gradients of the two arguments), and
@@ -298,23 +270,6 @@ __global__ __launch_bounds__(kBlock) void gru_readout_bwd(const float *__restric
             dh[o] = acc;
         }
         __syncthreads();
-    }
-}
-
-// dU[c] += sum_m dy[m] g[m][c]: 64 channels per workgroup, row r of its 16 sums the molecules r, r + 16, .., the partials folded in order
-__global__ __launch_bounds__(1024) void gru_readout_dU(const float *__restrict__ dy, const float *__restrict__ g, float *__restrict__ dU, int H,
-                                                       int nMol) {
-    __shared__ float part[16][64];
-    const int lane = threadIdx.x & 63, r = threadIdx.x >> 6, c = blockIdx.x * 64 + lane;
-    const int cc = c < H ? c : H - 1;
-    float acc = 0.f;
-    for (int m = r; m < nMol; m += 16) acc = fmaf(dy[m], g[(size_t)m * H + cc], acc);
-    part[r][lane] = acc;
-    __syncthreads();
-    if (r == 0 && c < H) {
-        float t = 0.f;
-        for (int k = 0; k < 16; ++k) t += part[k][lane];
-        dU[c] += t;
     }
 }
 
@@ -399,11 +354,6 @@ gf_status readout_bwd_launch(gf_ctx *ctx, const Shape &sh, int rounds, const flo
     return GF_OK;
 }
 
-gf_status readout_dU_launch(gf_ctx *ctx, int H, int nMol, const float *dy, const float *g, float *dU) {
-    GF_LAUNCH(ctx, "gru_readout_dU", gru_readout_dU, dim3((unsigned)((H + 63) / 64)), dim3(1024), 0, dy, g, dU, H, nMol);
-    return GF_OK;
-}
-
 // f(pairs as an integral constant): the one place the aggregate picks an instantiation
 template <typename F>
 gf_status with_aggregate(bool pairs, F &&f) {
@@ -423,8 +373,9 @@ gf_status smp_gru_forward(gf_smp *s, const float *params, const float *targets, 
     const bool pairs = s->cfg.neighbourhood == 5;
     const View<const float> p(s->cfg, params);
     const Shape sh(H, nV);
-    gf_status st = smp_neighbourhood_fwd_launch(ctx, pairs, H, FD, nV, 0, p.W, nullptr, s->x, nullptr, nullptr, nullptr, nullptr, s->lv[0].f, nullptr,
-                                                nullptr, s->lv[0].nb_T, nullptr);
+    gf_nbh_fwd_set level0 = {};   // (no W2: no aggregate, every other operand stays null)
+    level0.FD = FD, level0.W1 = p.W, level0.x = s->x, level0.h = s->lv[0].f, level0.T = s->lv[0].nb_T;
+    gf_status st = smp_neighbourhood_fwd(ctx, pairs, H, nV, 0, &level0, 1, nullptr, nullptr);
     for (int l = 1; l <= L && st == GF_OK; ++l) {
         gf_smp::DevLevel &d = s->lv[l];
         const gf_smp::DevLevel &pv = s->lv[l - 1];
@@ -443,14 +394,7 @@ gf_status smp_gru_forward(gf_smp *s, const float *params, const float *targets, 
     if (st == GF_OK)
         st = readout_fwd_launch(ctx, sh, 0, nMol, p.mat(6), p.U, s->lv[L].f, s->mol_ptr, targets, s->gru_s, s->gru_t, s->g, s->yhat, loss,
                                 s->dy);
-    if (st != GF_OK) return st;
-    if (predict) GF_HIP_TRY(ctx, hipMemcpyAsync(predict, s->yhat, sizeof(float) * nMol, hipMemcpyDeviceToDevice, ctx->stream));
-    if (graph_feature) GF_HIP_TRY(ctx, hipMemcpyAsync(graph_feature, s->g, sizeof(float) * nMol * H, hipMemcpyDeviceToDevice, ctx->stream));
-    s->bwd_consumed = false;
-    s->forwarded = true;
-    s->has_targets = targets != nullptr;
-    mark_used(s);
-    return GF_OK;
+    return st == GF_OK ? finish_forward(s, targets != nullptr, predict, graph_feature, H) : st;
 }
 
 // The reverse sweep from the loss of the last forward.  Every level keeps what a second sweep needs: dh_l is rebuilt from dy downwards.
@@ -470,7 +414,7 @@ gf_status smp_gru_backward(gf_smp *s, const float *params, float *grads, int acc
     float *sweep = accumulate ? s->gru_acc : grads;
     const View<float> d(s->cfg, sweep);
     GF_HIP_TRY(ctx, hipMemsetAsync(sweep, 0, sizeof(float) * np, ctx->stream));
-    gf_status st = readout_dU_launch(ctx, H, nMol, s->dy, s->g, d.U);
+    gf_status st = smp_vertex_readout_dW(ctx, "gru_readout_dU", H, nMol, s->dy, s->g, d.U);
     if (st == GF_OK)
         st = readout_bwd_launch(ctx, sh, 0, p.mat(6), p.U, s->gru_s, s->gru_t, s->g, s->dy, s->top_node_mol, s->gru_ds, s->gru_dt, s->lv[L].df);
     if (st == GF_OK) st = wgrad(ctx, sh, s->gru_ds, s->lv[L].f, d.mat(6));   // dW_g += ds^T h_L
@@ -487,16 +431,18 @@ gf_status smp_gru_backward(gf_smp *s, const float *params, float *grads, int acc
         for (int i = 0; i < 6 && st == GF_OK; ++i) st = wgrad(ctx, sh, lhs[i], rhs[i], d.mat(i));
         if (st == GF_OK && s->cfg.third_order())
             st = smp_third_pool_bwd_launch(ctx, H, nV, v.nb_ptr, v.nb_idx, v.nb_tptr, v.nb_tidx, pv.f, v.nb_sel, v.Q, pv.df);
-        else if (st == GF_OK)
-            st = smp_neighbourhood_gather_launch(ctx, pairs, H, nV, v.nb_tptr, v.nb_tidx, v.Q, v.th_node, v.nb_sA, pv.f, pv.nb_T, pv.df);
+        else if (st == GF_OK) {
+            const gf_nbh_gather_set gat = {/*dn=*/v.Q, /*gTt=*/v.th_node, /*sA=*/v.nb_sA, /*hprev=*/pv.f, /*Tprev=*/pv.nb_T, /*dhprev=*/pv.df};
+            st = smp_neighbourhood_gather(ctx, pairs, H, nV, v.nb_tptr, v.nb_tidx, &gat, 1);
+        }
         if (st != GF_OK) break;
         const size_t count = (size_t)nV * H, blocks = (count + kBlock - 1) / kBlock;
         GF_LAUNCH(ctx, "gru_add", gru_add, dim3((unsigned)(blocks > 65536 ? 65536 : blocks)), dim3(kBlock), 0, pv.df, v.gru_direct, count);
     }
     // level 0: dz = dh h (1 - h) in place (the classes' diagonal softmax rule), dW [H][F'] += dz^T X
-    if (st == GF_OK)
-        st = smp_neighbourhood_node_launch(ctx, pairs, H, nV, 0, nullptr, s->lv[0].f, s->lv[0].df, nullptr, nullptr, s->top_node_mol, nullptr, nullptr,
-                                           nullptr, nullptr, nullptr);
+    gf_nbh_node_set level0 = {};   // (no W2: dz alone)
+    level0.h = s->lv[0].f, level0.dh = s->lv[0].df;
+    if (st == GF_OK) st = smp_neighbourhood_node(ctx, pairs, H, nV, 0, &level0, 1, nullptr, s->top_node_mol);
     if (st == GF_OK) st = gemm(ctx, true, false, H, FD, nV, s->lv[0].df, H, 0, s->x, FD, 0, d.W, FD, 0, 1, 1);
     if (st != GF_OK) return st;
     if (accumulate) GF_LAUNCH(ctx, "gru_add", gru_add, dim3((unsigned)((np + kBlock - 1) / kBlock)), dim3(kBlock), 0, grads, sweep, np);
@@ -507,17 +453,6 @@ gf_status smp_gru_backward(gf_smp *s, const float *params, float *grads, int acc
 }  // namespace gf
 
 // ---- the level's kernels as stand-alone operators (include/gf_hip.h; tests/test_smp_gru_ops_gpu.py) ----
-namespace {
-
-// H, nV and the largest accepted rounds of a stand-alone call
-gf_status check_shape(gf_ctx *ctx, const char *who, int H, int nV, int rounds) {
-    if (H < 1 || H > gf::kGruMaxChanels) return gf::fail(ctx, GF_ERR_INVALID, "%s: %d channels (1 .. %d)", who, H, gf::kGruMaxChanels);
-    if (nV < 1 || rounds < 0 || rounds > 65536) return gf::fail(ctx, GF_ERR_INVALID, "%s: %d vertices, %d rounds", who, nV, rounds);
-    return GF_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 gf_status gf_smp_gru_cell_fwd_ex_f32(gf_ctx *ctx, int aggregate, int H, int nV, int rounds, const float *M6, const float *hprev, const float *Tprev,
@@ -525,14 +460,14 @@ gf_status gf_smp_gru_cell_fwd_ex_f32(gf_ctx *ctx, int aggregate, int H, int nV, 
                                      float *Tt) {
     static const char *who = "gf_smp_gru_cell_fwd_ex_f32";
     if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
-    gf_status st = check_shape(ctx, who, H, nV, rounds);
+    gf_status st = gf::check_shape(ctx, who, H, gf::kGruMaxChanels, nV, rounds);
     if (st != GF_OK) return st;
     if (aggregate < 0 || aggregate > 2) return gf::fail(ctx, GF_ERR_INVALID, "%s: aggregate = %d (0: sum, 1: pairs, 2: given)", who, aggregate);
     if (!M6 || !hprev || !h || !n || !z || !r || !c) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
     if (aggregate != 2 && (!ptr || !idx)) return gf::fail(ctx, GF_ERR_INVALID, "%s: the sum and the pair form need ptr and idx", who);
     if (aggregate == 1 && (!Tprev || !A || !T || !Tt)) return gf::fail(ctx, GF_ERR_INVALID, "%s: the pair form needs Tprev, A, T and Tt", who);
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (aggregate != 2) st = gf::smp_neighbourhood_check_list(ctx, who, "ptr", ptr, idx, nV, nV);
+    if (aggregate != 2) st = gf::check_list(ctx, who, "ptr", ptr, idx, nV, nV);
     if (st != GF_OK) return st;
     const gf::Shape sh(H, nV);
     if (aggregate == 2) return gf::cell_fwd_launch<false, true>(ctx, sh, rounds, M6, hprev, Tprev, ptr, idx, h, n, z, r, c, A, T, Tt);
@@ -546,7 +481,7 @@ gf_status gf_smp_gru_cell_bwd_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, int 
                                      float *dcp, float *q, float *dn, float *gTt, float *sA, float *direct) {
     static const char *who = "gf_smp_gru_cell_bwd_ex_f32";
     if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
-    const gf_status st = check_shape(ctx, who, H, nV, rounds);
+    const gf_status st = gf::check_shape(ctx, who, H, gf::kGruMaxChanels, nV, rounds);
     if (st != GF_OK) return st;
     if (!M6 || !hprev || !dh || !z || !r || !c || !dzp || !drp || !dcp || !q || !dn || !direct)
         return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
@@ -563,11 +498,11 @@ gf_status gf_smp_gru_readout_fwd_ex_f32(gf_ctx *ctx, int H, int nV, int nMol, in
                                         float *dy) {
     static const char *who = "gf_smp_gru_readout_fwd_ex_f32";
     if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
-    gf_status st = check_shape(ctx, who, H, nV, rounds);
+    gf_status st = gf::check_shape(ctx, who, H, gf::kGruMaxChanels, nV, rounds);
     if (st != GF_OK) return st;
     if (nMol < 1 || !M2 || !U || !hL || !mol_ptr || !s || !t || !g || !yhat || !dy) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    st = gf::smp_neighbourhood_check_ptr(ctx, who, "mol_ptr", mol_ptr, nMol, nV);
+    st = gf::check_ptr(ctx, who, "mol_ptr", mol_ptr, nMol, nV);
     if (st != GF_OK) return st;
     return gf::readout_fwd_launch(ctx, gf::Shape(H, nV), rounds, nMol, M2, U, hL, mol_ptr, target, s, t, g, yhat, loss, dy);
 }
@@ -577,14 +512,14 @@ gf_status gf_smp_gru_readout_bwd_ex_f32(gf_ctx *ctx, int H, int nV, int nMol, in
                                         float *dU) {
     static const char *who = "gf_smp_gru_readout_bwd_ex_f32";
     if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
-    gf_status st = check_shape(ctx, who, H, nV, rounds);
+    gf_status st = gf::check_shape(ctx, who, H, gf::kGruMaxChanels, nV, rounds);
     if (st != GF_OK) return st;
     if (nMol < 1 || !M2 || !U || !s || !t || !g || !dy || !vmol || !ds || !dt || !dh || !dU)
         return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    st = gf::smp_neighbourhood_check_members(ctx, who, "vmol", vmol, (size_t)nV, nMol);
+    st = gf::check_members(ctx, who, "vmol", vmol, (size_t)nV, nMol);
     if (st != GF_OK) return st;
-    st = gf::readout_dU_launch(ctx, H, nMol, dy, g, dU);
+    st = gf::smp_vertex_readout_dW(ctx, "gru_readout_dU", H, nMol, dy, g, dU);
     if (st != GF_OK) return st;
     return gf::readout_bwd_launch(ctx, gf::Shape(H, nV), rounds, M2, U, s, t, g, dy, vmol, ds, dt, dh);
 }

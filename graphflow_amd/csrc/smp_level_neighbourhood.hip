@@ -13,49 +13,22 @@
 //                    max / exp / sum across the group's lanes; stores h_l, n_l and in form 3 A, Tt and T = sum_k h_l[k]
 //   nbh_node_bwd     dz in place of dh_l (the top level takes dy[mol] W instead), dn = W2_l^T dz; form 3: dn Tt and <dn, A> beside it
 //   nbh_gather_bwd   dh_{l-1} over the transposed list
-//   nbh_readout, nbh_readout_dW   the sum over a molecule's vertices, prediction, loss, dy; dW
+//   nbh_readout      the sum over a molecule's vertices, prediction, loss, dy; dW is smp_vertex_level.hip's vertex_readout_dW
 // dW1_l = dz^T X and dW2_l = dz^T N are the library's deterministic TN products.  Every sum runs in a fixed order; no atomics; an operand
 // of a lane without a channel is loaded from a clamped address and never stored (NOTES.md: no guard around an operand load).
 // The four kernels and the read-out are also operators of the C ABI on caller-supplied operands (gf_smp_neighbourhood_fwd_ex_f32,
 // _node_bwd_ex_f32, _gather_bwd_ex_f32, _readout_ex_f32 at the end of the file), through the launchers the level uses.
 // The three level kernels take TWO operand sets by value (gf_nbh_fwd_set / _node_set / _gather_set of include/gf_hip.h) and blockIdx.y
-// picks one: a distance handle (smp_level_distance.hip) runs its vertex and its distance channel in one launch each (*_sets launchers,
-// gf_smp_neighbourhood_*2_ex_f32).  Everybody else launches grid.y = 1 with the one set given twice; the bodies are unchanged.
+// picks one: a distance handle (smp_level_distance.hip) runs its vertex and its distance channel in one launch each (nsets = 2 of
+// smp_neighbourhood_fwd / _node / _gather, gf_smp_neighbourhood_*2_ex_f32).  Everybody else launches grid.y = 1 with the one set given
+// twice.  The lane helpers, the list checks and the sweep's tail are smp_vertex_level.h's.
 #include <cmath>
 
-#include "smp_field_level.h"
+#include "smp_vertex_level.h"
 
 namespace gf {
+using namespace vertex_level;
 namespace {
-
-constexpr int kBlock = 256;   // four waves
-
-// the row stride of the transposed LDS images (smp_neighbourhood_lds_bytes): odd, so their transposing stores hit 32 different banks
-__host__ __device__ inline int row_stride(int H) { return H | 1; }
-
-__device__ __forceinline__ float group_sum(float v, int G) {   // every lane of the group gets the same bits (a + b == b + a)
-    for (int d = G >> 1; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ float group_max(float v, int G) {
-    for (int d = G >> 1; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-    return v;
-}
-
-// a * b rounded on its own: the subtraction that follows must not fuse it into an fma (one member: A Tt - a T has to be exactly 0)
-__device__ __forceinline__ float mul_rounded(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-
-// a workgroup's vertex slots: slot = one group of G lanes, kBlock / G of them; it takes vertices vbase + it + slot, it = 0, slots, .. < vpg
-struct Slot {
-    int slot, slots, c0;
-};
-__device__ __forceinline__ Slot slot_of(int G) {
-    const int lane = threadIdx.x & 63, per_wave = 64 / G;
-    return {(int)(threadIdx.x >> 6) * per_wave + lane / G, kBlock / G, lane % G};
-}
 
 template <int NK, bool PAIRS>
 __device__ __forceinline__ void level_fwd_body(const float *__restrict__ W1, const float *__restrict__ W2, const float *__restrict__ x,
@@ -304,31 +277,8 @@ __global__ __launch_bounds__(64) void nbh_readout(const float *__restrict__ hL, 
         g[(size_t)m * H + c] = acc;
         part = fmaf(acc, W[c], part);
     }
-    part = group_sum(part, 64);
-    if (threadIdx.x == 0) {
-        const float t = target ? target[m] : 0.f;
-        yhat[m] = part;
-        if (loss) loss[m] = 0.5f * (part - t) * (part - t);
-        dy[m] = part - t;   // SquaredLoss::backward
-    }
-}
-
-// dW[c] += sum_m dy[m] g[m][c] (InnerProduct::backward, second operand): 64 channels per workgroup, row r of its 16 sums the molecules
-// r, r + 16, .., the 16 partials are folded in order
-__global__ __launch_bounds__(1024) void nbh_readout_dW(const float *__restrict__ dy, const float *__restrict__ g, float *__restrict__ dW, int H,
-                                                       int nMol) {
-    __shared__ float part[16][64];
-    const int lane = threadIdx.x & 63, r = threadIdx.x >> 6, c = blockIdx.x * 64 + lane;
-    const int cc = c < H ? c : H - 1;
-    float acc = 0.f;
-    for (int m = r; m < nMol; m += 16) acc = fmaf(dy[m], g[(size_t)m * H + cc], acc);
-    part[r][lane] = acc;
-    __syncthreads();
-    if (r == 0 && c < H) {
-        float t = 0.f;
-        for (int k = 0; k < 16; ++k) t += part[k][lane];
-        dW[c] += t;
-    }
+    part = wave_sum(part);
+    GF_STORE_PREDICTION(m, part, target, yhat, loss, dy);
 }
 
 // W1_0; (W1_l, W2_l) l = 1..L; W
@@ -355,62 +305,8 @@ inline int vertices_per_group(int nV, int slots) {
     return slots * rounds;
 }
 
-// The three launches of a level on raw operands: the level below and the stand-alone operators at the end of the file share them.
 // rounds = 0: vertices_per_group; > 0: that many rounds of a workgroup's slots.
 inline int group_vertices(int nV, int slots, int rounds) { return rounds > 0 ? slots * rounds : vertices_per_group(nV, slots); }
-
-// `sets` operand sets (1 or 2) in one launch: grid.y = sets, the dynamic LDS sized for the wider operand
-template <int NK, bool PAIRS>
-gf_status fwd_launch_sets(gf_ctx *ctx, int H, int nV, int rounds, int sets, const gf_nbh_fwd_set &s0, const gf_nbh_fwd_set &s1, const long long *ptr,
-                          const int *idx) {
-    const int G = smp_neighbourhood_group_width(H), vpg = group_vertices(nV, kBlock / G, rounds);
-    const int FD = sets > 1 && s1.FD > s0.FD ? s1.FD : s0.FD;
-    const size_t bytes = smp_neighbourhood_lds_bytes(H, FD);   // (level 0 leaves W2's part unused: one grant per kernel)
-    const gf_status st = opt_in_lds(ctx, nbh_level_fwd<NK, PAIRS>, bytes);
-    if (st != GF_OK) return st;
-    GF_LAUNCH(ctx, "nbh_level_fwd", (nbh_level_fwd<NK, PAIRS>), dim3((unsigned)((nV + vpg - 1) / vpg), (unsigned)sets), dim3(kBlock), bytes, s0, s1,
-              ptr, idx, nV, H, G, vpg);
-    return GF_OK;
-}
-template <int NK, bool PAIRS>
-gf_status fwd_launch(gf_ctx *ctx, int H, int FD, int nV, int rounds, const float *W1, const float *W2, const float *x, const float *hprev,
-                     const float *Tprev, const long long *ptr, const int *idx, float *h, float *n, float *A, float *T, float *Tt) {
-    const gf_nbh_fwd_set one = {FD, W1, x, W2, hprev, Tprev, h, n, A, T, Tt};
-    return fwd_launch_sets<NK, PAIRS>(ctx, H, nV, rounds, 1, one, one, ptr, idx);
-}
-
-template <int NK, bool PAIRS>
-gf_status node_launch_sets(gf_ctx *ctx, int H, int nV, int rounds, int sets, const gf_nbh_node_set &s0, const gf_nbh_node_set &s1, const float *dy,
-                           const int *vmol) {
-    const int G = smp_neighbourhood_group_width(H), slots = kBlock / G, vpg = group_vertices(nV, slots, rounds);
-    const size_t bytes = sizeof(float) * ((s0.W2 ? (size_t)H * H : 0) + (size_t)slots * H);
-    const gf_status st = opt_in_lds(ctx, nbh_node_bwd<NK, PAIRS>, bytes);
-    if (st != GF_OK) return st;
-    GF_LAUNCH(ctx, "nbh_node_bwd", (nbh_node_bwd<NK, PAIRS>), dim3((unsigned)((nV + vpg - 1) / vpg), (unsigned)sets), dim3(kBlock), bytes, s0, s1, dy,
-              vmol, nV, H, G, vpg);
-    return GF_OK;
-}
-template <int NK, bool PAIRS>
-gf_status node_launch(gf_ctx *ctx, int H, int nV, int rounds, const float *W2, const float *h, float *dh, const float *dy, const float *Wout,
-                      const int *vmol, const float *A, const float *Tt, float *dn, float *gTt, float *sA) {
-    const gf_nbh_node_set one = {W2, h, dh, Wout, A, Tt, dn, gTt, sA};
-    return node_launch_sets<NK, PAIRS>(ctx, H, nV, rounds, 1, one, one, dy, vmol);
-}
-
-template <int NK, bool PAIRS>
-gf_status gather_launch_sets(gf_ctx *ctx, int H, int nV, int sets, const long long *tptr, const int *tidx, const gf_nbh_gather_set &s0,
-                             const gf_nbh_gather_set &s1) {
-    const int G = smp_neighbourhood_group_width(H), slots = kBlock / G;
-    GF_LAUNCH(ctx, "nbh_gather_bwd", (nbh_gather_bwd<NK, PAIRS>), dim3((unsigned)((nV + slots - 1) / slots), (unsigned)sets), dim3(kBlock), 0, tptr,
-              tidx, s0, s1, nV, H, G);
-    return GF_OK;
-}
-template <int NK, bool PAIRS>
-gf_status gather_launch(gf_ctx *ctx, int H, int nV, const long long *tptr, const int *tidx, const float *dn, const float *gTt, const float *sA,
-                        const float *hprev, const float *Tprev, float *dhprev) {
-    const gf_nbh_gather_set one = {dn, gTt, sA, hprev, Tprev, dhprev};
-    return gather_launch_sets<NK, PAIRS>(ctx, H, nV, 1, tptr, tidx, one, one);
-}
 
 // the one place the run-time (channels per lane, aggregate) picks an instantiation: f(channels per lane, pairs) as integral constants
 template <typename F>
@@ -421,113 +317,82 @@ gf_status with_instantiation(int H, bool pairs, F &&f) {
     return pairs ? f(one{}, std::true_type{}) : f(one{}, std::false_type{});
 }
 
-gf_status level(gf_smp *s, int l, const float *W1, const float *W2, bool forward, bool top = false, const float *Wout = nullptr) {
-    gf_ctx *ctx = s->ctx;
-    const int H = s->cfg.nChanels, FD = s->cfg.fdim(), nV = s->lay.level[0].nNodes;
-    gf_smp::DevLevel &d = s->lv[l];
-    const gf_smp::DevLevel *pv = l ? &s->lv[l - 1] : nullptr;
-    return with_instantiation(H, s->cfg.neighbourhood == 3, [&](auto nk, auto pairs) -> gf_status {
+}  // namespace
+
+// The three launches of a level on `nsets` operand sets (1 or 2): grid.y = nsets, one set is given to the kernel twice.  The level below,
+// the gated and the distance level and the stand-alone operators at the end of the file share them.
+gf_status smp_neighbourhood_fwd(gf_ctx *ctx, bool pairs, int H, int nV, int rounds, const gf_nbh_fwd_set *sets, int nsets, const long long *ptr,
+                                const int *idx) {
+    const gf_nbh_fwd_set &s0 = sets[0], &s1 = sets[nsets - 1];
+    const int G = smp_neighbourhood_group_width(H), vpg = group_vertices(nV, kBlock / G, rounds);
+    const size_t bytes = smp_neighbourhood_lds_bytes(H, s1.FD > s0.FD ? s1.FD : s0.FD);   // (the wider operand; level 0 leaves W2's part unused: one grant per kernel)
+    return with_instantiation(H, pairs, [&](auto nk, auto pr) -> gf_status {
         constexpr int NK = decltype(nk)::value;
-        constexpr bool PAIRS = decltype(pairs)::value;
-        const bool third = l && s->cfg.third_order();   // GCN_3D: n_l is smp_level_third.hip's, handed on as a sum of one term over N(v) = {v}
-        if (forward && third) {
-            const gf_status pooled = smp_third_pool_fwd_launch(ctx, H, nV, d.nb_max_members, pv->f, d.nb_ptr, d.nb_idx, d.nb_pool, d.nb_sel);
-            if (pooled != GF_OK) return pooled;
-            return fwd_launch<NK, PAIRS>(ctx, H, FD, nV, 0, W1, W2, s->x, d.nb_pool, nullptr, s->nb_id_ptr, s->nb_id_idx, d.f, d.th_A, d.th_B, d.nb_T,
-                                         d.nb_Tt);
-        }
-        if (forward)
-            return fwd_launch<NK, PAIRS>(ctx, H, FD, nV, 0, W1, W2, s->x, pv ? pv->f : nullptr, pv ? pv->nb_T : nullptr, d.nb_ptr, d.nb_idx, d.f,
-                                         d.th_A, d.th_B, d.nb_T, d.nb_Tt);
-        const gf_status st = node_launch<NK, PAIRS>(ctx, H, nV, 0, W2, d.f, d.df, top ? s->dy : nullptr, Wout, s->top_node_mol, d.th_B, d.nb_Tt,
-                                                    d.Q, d.th_node, d.nb_sA);
-        if (st != GF_OK || !l) return st;
-        if (third) return smp_third_pool_bwd_launch(ctx, H, nV, d.nb_ptr, d.nb_idx, d.nb_tptr, d.nb_tidx, pv->f, d.nb_sel, d.Q, pv->df);
-        return gather_launch<NK, PAIRS>(ctx, H, nV, d.nb_tptr, d.nb_tidx, d.Q, d.th_node, d.nb_sA, pv->f, pv->nb_T, pv->df);
+        constexpr bool PAIRS = decltype(pr)::value;
+        const gf_status st = opt_in_lds(ctx, nbh_level_fwd<NK, PAIRS>, bytes);
+        if (st != GF_OK) return st;
+        GF_LAUNCH(ctx, "nbh_level_fwd", (nbh_level_fwd<NK, PAIRS>), dim3((unsigned)((nV + vpg - 1) / vpg), (unsigned)nsets), dim3(kBlock), bytes, s0,
+                  s1, ptr, idx, nV, H, G, vpg);
+        return GF_OK;
     });
 }
 
-// every one of the n device ints lies in [0, bound) (one blocking copy)
-gf_status check_members(gf_ctx *ctx, const char *who, const char *what, const int *idx, size_t n, int bound) {
-    std::vector<int> t(n);
-    if (n) {
-        GF_HIP_TRY(ctx, hipMemcpyAsync(t.data(), idx, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
-        GF_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    for (size_t i = 0; i < n; ++i)
-        if (t[i] < 0 || t[i] >= bound) return fail(ctx, GF_ERR_INVALID, "%s: %s[%zu] = %d outside [0, %d)", who, what, i, t[i], bound);
-    return GF_OK;
+gf_status smp_neighbourhood_node(gf_ctx *ctx, bool pairs, int H, int nV, int rounds, const gf_nbh_node_set *sets, int nsets, const float *dy,
+                                 const int *vmol) {
+    const gf_nbh_node_set &s0 = sets[0], &s1 = sets[nsets - 1];
+    const int G = smp_neighbourhood_group_width(H), slots = kBlock / G, vpg = group_vertices(nV, slots, rounds);
+    const size_t bytes = sizeof(float) * ((s0.W2 ? (size_t)H * H : 0) + (size_t)slots * H);
+    return with_instantiation(H, pairs, [&](auto nk, auto pr) -> gf_status {
+        constexpr int NK = decltype(nk)::value;
+        constexpr bool PAIRS = decltype(pr)::value;
+        const gf_status st = opt_in_lds(ctx, nbh_node_bwd<NK, PAIRS>, bytes);
+        if (st != GF_OK) return st;
+        GF_LAUNCH(ctx, "nbh_node_bwd", (nbh_node_bwd<NK, PAIRS>), dim3((unsigned)((nV + vpg - 1) / vpg), (unsigned)nsets), dim3(kBlock), bytes, s0,
+                  s1, dy, vmol, nV, H, G, vpg);
+        return GF_OK;
+    });
 }
 
-// A list of a stand-alone call, checked on the host (one blocking copy: these are test operators): ptr [n + 1] starts at 0 and never
-// decreases, every member lies in [0, bound).  `idx` null: ptr alone (32-bit: mol_ptr), its last entry at most `bound`.
-template <typename P>
-gf_status check_list(gf_ctx *ctx, const char *who, const char *what, const P *ptr, const int *idx, int n, int bound) {
-    std::vector<P> p((size_t)n + 1);
-    GF_HIP_TRY(ctx, hipMemcpyAsync(p.data(), ptr, sizeof(P) * p.size(), hipMemcpyDeviceToHost, ctx->stream));
-    GF_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (p[0] != 0) return fail(ctx, GF_ERR_INVALID, "%s: %s starts at %lld, not at 0", who, what, (long long)p[0]);
-    for (int i = 0; i < n; ++i)
-        if (p[i + 1] < p[i]) return fail(ctx, GF_ERR_INVALID, "%s: %s decreases at entry %d", who, what, i + 1);
-    if (!idx) {
-        if ((long long)p[n] > bound) return fail(ctx, GF_ERR_INVALID, "%s: %s ends at %lld, beyond the %d rows", who, what, (long long)p[n], bound);
+gf_status smp_neighbourhood_gather(gf_ctx *ctx, bool pairs, int H, int nV, const long long *tptr, const int *tidx, const gf_nbh_gather_set *sets,
+                                   int nsets) {
+    const gf_nbh_gather_set &s0 = sets[0], &s1 = sets[nsets - 1];
+    const int G = smp_neighbourhood_group_width(H), slots = kBlock / G;
+    return with_instantiation(H, pairs, [&](auto nk, auto pr) -> gf_status {
+        constexpr int NK = decltype(nk)::value;
+        constexpr bool PAIRS = decltype(pr)::value;
+        GF_LAUNCH(ctx, "nbh_gather_bwd", (nbh_gather_bwd<NK, PAIRS>), dim3((unsigned)((nV + slots - 1) / slots), (unsigned)nsets), dim3(kBlock), 0,
+                  tptr, tidx, s0, s1, nV, H, G);
         return GF_OK;
+    });
+}
+
+namespace {
+
+gf_status level(gf_smp *s, int l, const float *W1, const float *W2, bool forward, bool top = false, const float *Wout = nullptr) {
+    gf_ctx *ctx = s->ctx;
+    const int H = s->cfg.nChanels, nV = s->lay.level[0].nNodes;
+    const bool pairs = s->cfg.neighbourhood == 3;
+    gf_smp::DevLevel &d = s->lv[l];
+    const gf_smp::DevLevel *pv = l ? &s->lv[l - 1] : nullptr;
+    const bool third = l && s->cfg.third_order();   // GCN_3D: n_l is smp_level_third.hip's, handed on as a sum of one term over N(v) = {v}
+    if (forward) {
+        gf_nbh_fwd_set set = {s->cfg.fdim(), W1, s->x, W2, /*hprev=*/pv ? pv->f : nullptr, /*Tprev=*/pv ? pv->nb_T : nullptr,
+                              /*h=*/d.f, /*n=*/d.th_A, /*A=*/d.th_B, /*T=*/d.nb_T, /*Tt=*/d.nb_Tt};
+        if (!third) return smp_neighbourhood_fwd(ctx, pairs, H, nV, 0, &set, 1, d.nb_ptr, d.nb_idx);
+        const gf_status pooled = smp_third_pool_fwd_launch(ctx, H, nV, d.nb_max_members, pv->f, d.nb_ptr, d.nb_idx, d.nb_pool, d.nb_sel);
+        if (pooled != GF_OK) return pooled;
+        set.hprev = d.nb_pool, set.Tprev = nullptr;
+        return smp_neighbourhood_fwd(ctx, pairs, H, nV, 0, &set, 1, s->nb_id_ptr, s->nb_id_idx);
     }
-    if ((long long)p[n] > (1ll << 31)) return fail(ctx, GF_ERR_INVALID, "%s: %s ends at %lld: more than 2^31 members", who, what, (long long)p[n]);
-    return check_members(ctx, who, what, idx, (size_t)p[n], bound);
+    const gf_nbh_node_set node = {W2, /*h=*/d.f, /*dh=*/d.df, Wout, /*A=*/d.th_B, /*Tt=*/d.nb_Tt, /*dn=*/d.Q, /*gTt=*/d.th_node, /*sA=*/d.nb_sA};
+    const gf_status st = smp_neighbourhood_node(ctx, pairs, H, nV, 0, &node, 1, top ? s->dy : nullptr, s->top_node_mol);
+    if (st != GF_OK || !l) return st;
+    if (third) return smp_third_pool_bwd_launch(ctx, H, nV, d.nb_ptr, d.nb_idx, d.nb_tptr, d.nb_tidx, pv->f, d.nb_sel, d.Q, pv->df);
+    const gf_nbh_gather_set gat = {/*dn=*/d.Q, /*gTt=*/d.th_node, /*sA=*/d.nb_sA, /*hprev=*/pv->f, /*Tprev=*/pv->nb_T, /*dhprev=*/pv->df};
+    return smp_neighbourhood_gather(ctx, pairs, H, nV, d.nb_tptr, d.nb_tidx, &gat, 1);
 }
 
 }  // namespace
-
-// the launchers for another translation unit (smp_level_gru.hip): no new instantiation, the run-time pick of with_instantiation
-gf_status smp_neighbourhood_fwd_launch(gf_ctx *ctx, bool pairs, int H, int FD, int nV, int rounds, const float *W1, const float *W2, const float *x,
-                                       const float *hprev, const float *Tprev, const long long *ptr, const int *idx, float *h, float *n, float *A,
-                                       float *T, float *Tt) {
-    return with_instantiation(H, pairs, [&](auto nk, auto pr) -> gf_status {
-        return fwd_launch<decltype(nk)::value, decltype(pr)::value>(ctx, H, FD, nV, rounds, W1, W2, x, hprev, Tprev, ptr, idx, h, n, A, T, Tt);
-    });
-}
-gf_status smp_neighbourhood_node_launch(gf_ctx *ctx, bool pairs, int H, int nV, int rounds, const float *W2, const float *h, float *dh,
-                                        const float *dy, const float *Wout, const int *vmol, const float *A, const float *Tt, float *dn, float *gTt,
-                                        float *sA) {
-    return with_instantiation(H, pairs, [&](auto nk, auto pr) -> gf_status {
-        return node_launch<decltype(nk)::value, decltype(pr)::value>(ctx, H, nV, rounds, W2, h, dh, dy, Wout, vmol, A, Tt, dn, gTt, sA);
-    });
-}
-gf_status smp_neighbourhood_gather_launch(gf_ctx *ctx, bool pairs, int H, int nV, const long long *tptr, const int *tidx, const float *dn,
-                                          const float *gTt, const float *sA, const float *hprev, const float *Tprev, float *dhprev) {
-    return with_instantiation(H, pairs, [&](auto nk, auto pr) -> gf_status {
-        return gather_launch<decltype(nk)::value, decltype(pr)::value>(ctx, H, nV, tptr, tidx, dn, gTt, sA, hprev, Tprev, dhprev);
-    });
-}
-
-gf_status smp_neighbourhood_fwd2_launch(gf_ctx *ctx, bool pairs, int H, int nV, int rounds, const gf_nbh_fwd_set *sets, const long long *ptr,
-                                        const int *idx) {
-    return with_instantiation(H, pairs, [&](auto nk, auto pr) -> gf_status {
-        return fwd_launch_sets<decltype(nk)::value, decltype(pr)::value>(ctx, H, nV, rounds, 2, sets[0], sets[1], ptr, idx);
-    });
-}
-gf_status smp_neighbourhood_node2_launch(gf_ctx *ctx, bool pairs, int H, int nV, int rounds, const gf_nbh_node_set *sets, const float *dy,
-                                         const int *vmol) {
-    return with_instantiation(H, pairs, [&](auto nk, auto pr) -> gf_status {
-        return node_launch_sets<decltype(nk)::value, decltype(pr)::value>(ctx, H, nV, rounds, 2, sets[0], sets[1], dy, vmol);
-    });
-}
-gf_status smp_neighbourhood_gather2_launch(gf_ctx *ctx, bool pairs, int H, int nV, const long long *tptr, const int *tidx,
-                                           const gf_nbh_gather_set *sets) {
-    return with_instantiation(H, pairs, [&](auto nk, auto pr) -> gf_status {
-        return gather_launch_sets<decltype(nk)::value, decltype(pr)::value>(ctx, H, nV, 2, tptr, tidx, sets[0], sets[1]);
-    });
-}
-gf_status smp_neighbourhood_check_list(gf_ctx *ctx, const char *who, const char *what, const long long *ptr, const int *idx, int n, int bound) {
-    return check_list(ctx, who, what, ptr, idx, n, bound);
-}
-gf_status smp_neighbourhood_check_members(gf_ctx *ctx, const char *who, const char *what, const int *idx, size_t n, int bound) {
-    return check_members(ctx, who, what, idx, n, bound);
-}
-gf_status smp_neighbourhood_check_ptr(gf_ctx *ctx, const char *who, const char *what, const int *ptr, int n, int bound) {
-    return check_list<int>(ctx, who, what, ptr, nullptr, n, bound);
-}
 
 gf_status smp_neighbourhood_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature) {
     gf_ctx *ctx = s->ctx;
@@ -537,19 +402,13 @@ gf_status smp_neighbourhood_forward(gf_smp *s, const float *params, const float 
         const gf_status st = level(s, l, p.W1[l], p.W2[l], /*forward=*/true);
         if (st != GF_OK) return st;
     }
-    if (s->cfg.readout) {   // GCN_*D_Kernel, GCA_1D: the pair and the Gram read-out (smp_level_readouts.hip)
+    const bool has_targets = targets != nullptr || s->cfg.readout == 2;   // (a Gram handle's target is the batch itself)
+    if (s->cfg.readout) {   // GCN_*D_Kernel, GCA_1D: the pair and the Gram read-out (smp_level_readouts.hip), which copy out what they have
         const gf_status st = smp_readout_forward(s, p.W, targets, predict, loss, graph_feature);
-        if (st != GF_OK) return st;
-    } else {
-        GF_LAUNCH(ctx, "nbh_readout", nbh_readout, dim3(nMol), dim3(64), 0, s->lv[L].f, s->mol_ptr, p.W, targets, s->g, s->yhat, loss, s->dy, H);
-        if (predict) GF_HIP_TRY(ctx, hipMemcpyAsync(predict, s->yhat, sizeof(float) * nMol, hipMemcpyDeviceToDevice, ctx->stream));
-        if (graph_feature) GF_HIP_TRY(ctx, hipMemcpyAsync(graph_feature, s->g, sizeof(float) * nMol * H, hipMemcpyDeviceToDevice, ctx->stream));
+        return st == GF_OK ? finish_forward(s, has_targets, nullptr, nullptr, 0) : st;
     }
-    s->bwd_consumed = false;
-    s->forwarded = true;
-    s->has_targets = targets != nullptr || s->cfg.readout == 2;   // (a Gram handle's target is the batch itself)
-    mark_used(s);
-    return GF_OK;
+    GF_LAUNCH(ctx, "nbh_readout", nbh_readout, dim3(nMol), dim3(64), 0, s->lv[L].f, s->mol_ptr, p.W, targets, s->g, s->yhat, loss, s->dy, H);
+    return finish_forward(s, has_targets, predict, graph_feature, H);
 }
 
 // The reverse sweep from the loss of the last forward; every level keeps what a second sweep needs (dz is rebuilt from dy downwards).
@@ -560,12 +419,8 @@ gf_status smp_neighbourhood_backward(gf_smp *s, const float *params, float *grad
     const View<float> d(s->cfg, grads);
     if (!accumulate) GF_HIP_TRY(ctx, hipMemsetAsync(grads, 0, sizeof(float) * param_count(s->cfg), ctx->stream));
     const bool own_readout = s->cfg.readout != 0;   // (smp_level_readouts.hip: its reverse leaves dh_L in lv[L].df, the top level is then a level like the others)
-    if (own_readout) {
-        const gf_status st = smp_readout_dW(s, p.W, d.W);
-        if (st != GF_OK) return st;
-    } else {
-        GF_LAUNCH(ctx, "nbh_readout_dW", nbh_readout_dW, dim3((unsigned)((H + 63) / 64)), dim3(1024), 0, s->dy, s->g, d.W, H, nMol);
-    }
+    const gf_status wst = own_readout ? smp_readout_dW(s, p.W, d.W) : smp_vertex_readout_dW(ctx, "nbh_readout_dW", H, nMol, s->dy, s->g, d.W);
+    if (wst != GF_OK) return wst;
     for (int l = L; l >= 0; --l) {
         gf_status st = level(s, l, nullptr, p.W2[l], /*forward=*/false, /*top=*/l == L && !own_readout, p.W);   // dz_l in lv[l].df, dh_{l-1} in lv[l - 1].df
         // dW1_l [H][F'] += dz^T X,  dW2_l [H][H] += dz^T N: tall-skinny TN products over the vertices of the batch
@@ -579,14 +434,78 @@ gf_status smp_neighbourhood_backward(gf_smp *s, const float *params, float *grad
 
 }  // namespace gf
 
-// ---- the level's kernels as stand-alone operators (include/gf_hip.h; tests/test_smp_neighbourhood_ops_gpu.py) ----
+// ---- the level's kernels as stand-alone operators (include/gf_hip.h; tests/test_smp_neighbourhood_ops_gpu.py), on one operand set built
+// from positional arguments or on the caller's two (a level of a distance handle): one validation and one launcher for both ----
 namespace {
 
-// H, nV and the largest accepted rounds of a stand-alone call
-gf_status check_shape(gf_ctx *ctx, const char *who, int H, int nV, int rounds) {
-    if (H < 1 || H > gf::kNeighbourhoodMaxChanels) return gf::fail(ctx, GF_ERR_INVALID, "%s: %d channels (1 .. %d)", who, H, gf::kNeighbourhoodMaxChanels);
-    if (nV < 1 || rounds < 0 || rounds > 65536) return gf::fail(ctx, GF_ERR_INVALID, "%s: %d vertices, %d rounds", who, nV, rounds);
+// a refusal of operand set c of a two-set call, or of the one set of a one-set call (c = -1)
+gf_status refuse(gf_ctx *ctx, const char *who, const char *what, int c) {
+    return c < 0 ? gf::fail(ctx, GF_ERR_INVALID, "%s: %s", who, what) : gf::fail(ctx, GF_ERR_INVALID, "%s: %s (set %d)", who, what, c);
+}
+
+gf_status check_fwd_set(gf_ctx *ctx, const char *who, int pairs, int H, const gf_nbh_fwd_set &o, const long long *ptr, const int *idx, int c) {
+    if (o.FD < 1 || !o.W1 || !o.x || !o.h) return refuse(ctx, who, "bad argument", c);
+    if (o.W2 && (!o.hprev || !ptr || !idx || !o.n)) return refuse(ctx, who, "a level with W2 needs hprev, ptr, idx and n", c);
+    if (pairs && (!o.T || (o.W2 && (!o.Tprev || !o.A || !o.Tt)))) return refuse(ctx, who, "the pair form needs T, and with W2 Tprev, A and Tt", c);
+    if (gf::smp_neighbourhood_lds_bytes(H, o.FD) > 160 * 1024)
+        return gf::fail(ctx, GF_ERR_INVALID, "%s: H = %d, F' = %d need %zu bytes of LDS (160 KiB)", who, H, o.FD, gf::smp_neighbourhood_lds_bytes(H, o.FD));
     return GF_OK;
+}
+gf_status check_node_set(gf_ctx *ctx, const char *who, int pairs, const gf_nbh_node_set &o, const float *dy, const int *vmol, int nMol, int c) {
+    if (!o.h || !o.dh) return refuse(ctx, who, "bad argument", c);
+    if (dy && (!o.Wout || !vmol || nMol < 1)) return refuse(ctx, who, "the top level needs Wout, vmol and nMol >= 1", c);
+    if (o.W2 && (!o.dn || (pairs && (!o.A || !o.Tt || !o.gTt || !o.sA)))) return refuse(ctx, who, "a level with W2 needs dn, the pair form A, Tt, gTt, sA", c);
+    return GF_OK;
+}
+gf_status check_gather_set(gf_ctx *ctx, const char *who, int pairs, const gf_nbh_gather_set &o, int c) {
+    if (!o.dn || !o.dhprev) return refuse(ctx, who, "bad argument", c);
+    if (pairs && (!o.gTt || !o.sA || !o.hprev || !o.Tprev)) return refuse(ctx, who, "the pair form needs gTt, sA, hprev and Tprev", c);
+    return GF_OK;
+}
+
+// what the one-set and the two-set entry of a kernel share, from the shape to the launch (W2 is in both sets of two or in neither)
+gf_status fwd_op(gf_ctx *ctx, const char *who, int pairs, int H, int nV, int rounds, const gf_nbh_fwd_set *sets, int nsets, const long long *ptr,
+                 const int *idx) {
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    gf_status st = gf::check_shape(ctx, who, H, gf::kNeighbourhoodMaxChanels, nV, rounds);
+    if (st != GF_OK) return st;
+    if (!sets) return refuse(ctx, who, "bad argument", -1);
+    if ((sets[0].W2 != nullptr) != (sets[nsets - 1].W2 != nullptr)) return refuse(ctx, who, "W2 in one set only", -1);
+    for (int c = 0; c < nsets && st == GF_OK; ++c) st = check_fwd_set(ctx, who, pairs, H, sets[c], ptr, idx, nsets > 1 ? c : -1);
+    if (st != GF_OK) return st;
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (sets[0].W2) st = gf::check_list(ctx, who, "ptr", ptr, idx, nV, nV);
+    if (st != GF_OK) return st;
+    return gf::smp_neighbourhood_fwd(ctx, pairs != 0, H, nV, rounds, sets, nsets, ptr, idx);
+}
+
+gf_status node_op(gf_ctx *ctx, const char *who, int pairs, int H, int nV, int rounds, const gf_nbh_node_set *sets, int nsets, const float *dy,
+                  const int *vmol, int nMol) {
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    gf_status st = gf::check_shape(ctx, who, H, gf::kNeighbourhoodMaxChanels, nV, rounds);
+    if (st != GF_OK) return st;
+    if (!sets) return refuse(ctx, who, "bad argument", -1);
+    if ((sets[0].W2 != nullptr) != (sets[nsets - 1].W2 != nullptr)) return refuse(ctx, who, "W2 in one set only", -1);
+    for (int c = 0; c < nsets && st == GF_OK; ++c) st = check_node_set(ctx, who, pairs, sets[c], dy, vmol, nMol, nsets > 1 ? c : -1);
+    if (st != GF_OK) return st;
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (dy) st = gf::check_members(ctx, who, "vmol", vmol, (size_t)nV, nMol);
+    if (st != GF_OK) return st;
+    return gf::smp_neighbourhood_node(ctx, pairs != 0, H, nV, rounds, sets, nsets, dy, vmol);
+}
+
+gf_status gather_op(gf_ctx *ctx, const char *who, int pairs, int H, int nV, const long long *tptr, const int *tidx, const gf_nbh_gather_set *sets,
+                    int nsets) {
+    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
+    gf_status st = gf::check_shape(ctx, who, H, gf::kNeighbourhoodMaxChanels, nV, 0);
+    if (st != GF_OK) return st;
+    if (!tptr || !tidx || !sets) return refuse(ctx, who, "bad argument", -1);
+    for (int c = 0; c < nsets && st == GF_OK; ++c) st = check_gather_set(ctx, who, pairs, sets[c], nsets > 1 ? c : -1);
+    if (st != GF_OK) return st;
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    st = gf::check_list(ctx, who, "tptr", tptr, tidx, nV, nV);
+    if (st != GF_OK) return st;
+    return gf::smp_neighbourhood_gather(ctx, pairs != 0, H, nV, tptr, tidx, sets, nsets);
 }
 
 }  // namespace
@@ -596,133 +515,47 @@ extern "C" {
 gf_status gf_smp_neighbourhood_fwd_ex_f32(gf_ctx *ctx, int pairs, int H, int FD, int nV, int rounds, const float *W1, const float *x, const float *W2,
                                           const float *hprev, const float *Tprev, const long long *ptr, const int *idx, float *h, float *n, float *A,
                                           float *T, float *Tt) {
-    static const char *who = "gf_smp_neighbourhood_fwd_ex_f32";
-    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
-    gf_status st = check_shape(ctx, who, H, nV, rounds);
-    if (st != GF_OK) return st;
-    if (FD < 1 || !W1 || !x || !h) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
-    if (W2 && (!hprev || !ptr || !idx || !n)) return gf::fail(ctx, GF_ERR_INVALID, "%s: a level with W2 needs hprev, ptr, idx and n", who);
-    if (pairs && (!T || (W2 && (!Tprev || !A || !Tt)))) return gf::fail(ctx, GF_ERR_INVALID, "%s: the pair form needs T, and with W2 Tprev, A and Tt", who);
-    if (gf::smp_neighbourhood_lds_bytes(H, FD) > 160 * 1024)
-        return gf::fail(ctx, GF_ERR_INVALID, "%s: H = %d, F' = %d need %zu bytes of LDS (160 KiB)", who, H, FD, gf::smp_neighbourhood_lds_bytes(H, FD));
-    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (W2) st = gf::check_list(ctx, who, "ptr", ptr, idx, nV, nV);
-    if (st != GF_OK) return st;
-    return gf::with_instantiation(H, pairs != 0, [&](auto nk, auto pr) -> gf_status {
-        return gf::fwd_launch<decltype(nk)::value, decltype(pr)::value>(ctx, H, FD, nV, rounds, W1, W2, x, hprev, Tprev, ptr, idx, h, n, A, T, Tt);
-    });
+    const gf_nbh_fwd_set set = {FD, W1, x, W2, hprev, Tprev, h, n, A, T, Tt};
+    return fwd_op(ctx, "gf_smp_neighbourhood_fwd_ex_f32", pairs, H, nV, rounds, &set, 1, ptr, idx);
+}
+gf_status gf_smp_neighbourhood_fwd2_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, int rounds, const gf_nbh_fwd_set *sets, const long long *ptr,
+                                           const int *idx) {
+    return fwd_op(ctx, "gf_smp_neighbourhood_fwd2_ex_f32", pairs, H, nV, rounds, sets, 2, ptr, idx);
 }
 
 gf_status gf_smp_neighbourhood_node_bwd_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, int rounds, const float *W2, const float *h, float *dh,
                                                const float *dy, const float *Wout, const int *vmol, int nMol, const float *A, const float *Tt,
                                                float *dn, float *gTt, float *sA) {
-    static const char *who = "gf_smp_neighbourhood_node_bwd_ex_f32";
-    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
-    gf_status st = check_shape(ctx, who, H, nV, rounds);
-    if (st != GF_OK) return st;
-    if (!h || !dh) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
-    if (dy && (!Wout || !vmol || nMol < 1)) return gf::fail(ctx, GF_ERR_INVALID, "%s: the top level needs Wout, vmol and nMol >= 1", who);
-    if (W2 && (!dn || (pairs && (!A || !Tt || !gTt || !sA)))) return gf::fail(ctx, GF_ERR_INVALID, "%s: a level with W2 needs dn, the pair form A, Tt, gTt, sA", who);
-    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (dy) st = gf::check_members(ctx, who, "vmol", vmol, (size_t)nV, nMol);
-    if (st != GF_OK) return st;
-    return gf::with_instantiation(H, pairs != 0, [&](auto nk, auto pr) -> gf_status {
-        return gf::node_launch<decltype(nk)::value, decltype(pr)::value>(ctx, H, nV, rounds, W2, h, dh, dy, Wout, vmol, A, Tt, dn, gTt, sA);
-    });
+    const gf_nbh_node_set set = {W2, h, dh, Wout, A, Tt, dn, gTt, sA};
+    return node_op(ctx, "gf_smp_neighbourhood_node_bwd_ex_f32", pairs, H, nV, rounds, &set, 1, dy, vmol, nMol);
+}
+gf_status gf_smp_neighbourhood_node_bwd2_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, int rounds, const gf_nbh_node_set *sets, const float *dy,
+                                                const int *vmol, int nMol) {
+    return node_op(ctx, "gf_smp_neighbourhood_node_bwd2_ex_f32", pairs, H, nV, rounds, sets, 2, dy, vmol, nMol);
 }
 
 gf_status gf_smp_neighbourhood_gather_bwd_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, const long long *tptr, const int *tidx, const float *dn,
                                                  const float *gTt, const float *sA, const float *hprev, const float *Tprev, float *dhprev) {
-    static const char *who = "gf_smp_neighbourhood_gather_bwd_ex_f32";
-    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
-    gf_status st = check_shape(ctx, who, H, nV, 0);
-    if (st != GF_OK) return st;
-    if (!tptr || !tidx || !dn || !dhprev) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
-    if (pairs && (!gTt || !sA || !hprev || !Tprev)) return gf::fail(ctx, GF_ERR_INVALID, "%s: the pair form needs gTt, sA, hprev and Tprev", who);
-    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    st = gf::check_list(ctx, who, "tptr", tptr, tidx, nV, nV);
-    if (st != GF_OK) return st;
-    return gf::with_instantiation(H, pairs != 0, [&](auto nk, auto pr) -> gf_status {
-        return gf::gather_launch<decltype(nk)::value, decltype(pr)::value>(ctx, H, nV, tptr, tidx, dn, gTt, sA, hprev, Tprev, dhprev);
-    });
+    const gf_nbh_gather_set set = {dn, gTt, sA, hprev, Tprev, dhprev};
+    return gather_op(ctx, "gf_smp_neighbourhood_gather_bwd_ex_f32", pairs, H, nV, tptr, tidx, &set, 1);
+}
+gf_status gf_smp_neighbourhood_gather_bwd2_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, const long long *tptr, const int *tidx,
+                                                  const gf_nbh_gather_set *sets) {
+    return gather_op(ctx, "gf_smp_neighbourhood_gather_bwd2_ex_f32", pairs, H, nV, tptr, tidx, sets, 2);
 }
 
 gf_status gf_smp_neighbourhood_readout_ex_f32(gf_ctx *ctx, int H, int nV, int nMol, const float *hL, const int *mol_ptr, const float *W,
                                               const float *target, float *g, float *yhat, float *loss, float *dy, float *dW) {
     static const char *who = "gf_smp_neighbourhood_readout_ex_f32";
     if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
-    gf_status st = check_shape(ctx, who, H, nV, 0);
+    gf_status st = gf::check_shape(ctx, who, H, gf::kNeighbourhoodMaxChanels, nV, 0);
     if (st != GF_OK) return st;
     if (nMol < 1 || !hL || !mol_ptr || !W || !g || !yhat || !dy || !dW) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    st = gf::check_list<int>(ctx, who, "mol_ptr", mol_ptr, nullptr, nMol, nV);
+    st = gf::check_ptr(ctx, who, "mol_ptr", mol_ptr, nMol, nV);
     if (st != GF_OK) return st;
     GF_LAUNCH(ctx, "nbh_readout", gf::nbh_readout, dim3(nMol), dim3(64), 0, hL, mol_ptr, W, target, g, yhat, loss, dy, H);
-    GF_LAUNCH(ctx, "nbh_readout_dW", gf::nbh_readout_dW, dim3((unsigned)((H + 63) / 64)), dim3(1024), 0, dy, g, dW, H, nMol);
-    return GF_OK;
-}
-
-// ---- the same kernels on two operand sets in one launch (a level of a distance handle) ----
-gf_status gf_smp_neighbourhood_fwd2_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, int rounds, const gf_nbh_fwd_set *sets, const long long *ptr,
-                                           const int *idx) {
-    static const char *who = "gf_smp_neighbourhood_fwd2_ex_f32";
-    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
-    gf_status st = check_shape(ctx, who, H, nV, rounds);
-    if (st != GF_OK) return st;
-    if (!sets) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
-    if ((sets[0].W2 != nullptr) != (sets[1].W2 != nullptr)) return gf::fail(ctx, GF_ERR_INVALID, "%s: W2 in one set only", who);
-    for (int c = 0; c < 2; ++c) {
-        const gf_nbh_fwd_set &o = sets[c];
-        if (o.FD < 1 || !o.W1 || !o.x || !o.h) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument in set %d", who, c);
-        if (o.W2 && (!o.hprev || !ptr || !idx || !o.n)) return gf::fail(ctx, GF_ERR_INVALID, "%s: a level with W2 needs hprev, ptr, idx and n (set %d)", who, c);
-        if (pairs && (!o.T || (o.W2 && (!o.Tprev || !o.A || !o.Tt))))
-            return gf::fail(ctx, GF_ERR_INVALID, "%s: the pair form needs T, and with W2 Tprev, A and Tt (set %d)", who, c);
-        if (gf::smp_neighbourhood_lds_bytes(H, o.FD) > 160 * 1024)
-            return gf::fail(ctx, GF_ERR_INVALID, "%s: H = %d, F' = %d need %zu bytes of LDS (160 KiB)", who, H, o.FD, gf::smp_neighbourhood_lds_bytes(H, o.FD));
-    }
-    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (sets[0].W2) st = gf::check_list(ctx, who, "ptr", ptr, idx, nV, nV);
-    if (st != GF_OK) return st;
-    return gf::smp_neighbourhood_fwd2_launch(ctx, pairs != 0, H, nV, rounds, sets, ptr, idx);
-}
-
-gf_status gf_smp_neighbourhood_node_bwd2_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, int rounds, const gf_nbh_node_set *sets, const float *dy,
-                                                const int *vmol, int nMol) {
-    static const char *who = "gf_smp_neighbourhood_node_bwd2_ex_f32";
-    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
-    gf_status st = check_shape(ctx, who, H, nV, rounds);
-    if (st != GF_OK) return st;
-    if (!sets) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
-    if ((sets[0].W2 != nullptr) != (sets[1].W2 != nullptr)) return gf::fail(ctx, GF_ERR_INVALID, "%s: W2 in one set only", who);
-    if (dy && (!vmol || nMol < 1)) return gf::fail(ctx, GF_ERR_INVALID, "%s: the top level needs vmol and nMol >= 1", who);
-    for (int c = 0; c < 2; ++c) {
-        const gf_nbh_node_set &o = sets[c];
-        if (!o.h || !o.dh || (dy && !o.Wout)) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument in set %d", who, c);
-        if (o.W2 && (!o.dn || (pairs && (!o.A || !o.Tt || !o.gTt || !o.sA))))
-            return gf::fail(ctx, GF_ERR_INVALID, "%s: a level with W2 needs dn, the pair form A, Tt, gTt, sA (set %d)", who, c);
-    }
-    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (dy) st = gf::check_members(ctx, who, "vmol", vmol, (size_t)nV, nMol);
-    if (st != GF_OK) return st;
-    return gf::smp_neighbourhood_node2_launch(ctx, pairs != 0, H, nV, rounds, sets, dy, vmol);
-}
-
-gf_status gf_smp_neighbourhood_gather_bwd2_ex_f32(gf_ctx *ctx, int pairs, int H, int nV, const long long *tptr, const int *tidx,
-                                                  const gf_nbh_gather_set *sets) {
-    static const char *who = "gf_smp_neighbourhood_gather_bwd2_ex_f32";
-    if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
-    gf_status st = check_shape(ctx, who, H, nV, 0);
-    if (st != GF_OK) return st;
-    if (!tptr || !tidx || !sets) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
-    for (int c = 0; c < 2; ++c) {
-        const gf_nbh_gather_set &o = sets[c];
-        if (!o.dn || !o.dhprev) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument in set %d", who, c);
-        if (pairs && (!o.gTt || !o.sA || !o.hprev || !o.Tprev)) return gf::fail(ctx, GF_ERR_INVALID, "%s: the pair form needs gTt, sA, hprev and Tprev (set %d)", who, c);
-    }
-    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    st = gf::check_list(ctx, who, "tptr", tptr, tidx, nV, nV);
-    if (st != GF_OK) return st;
-    return gf::smp_neighbourhood_gather2_launch(ctx, pairs != 0, H, nV, tptr, tidx, sets);
+    return gf::smp_vertex_readout_dW(ctx, "nbh_readout_dW", H, nMol, dy, g, dW);
 }
 
 }  // extern "C"

@@ -7,24 +7,18 @@
 //                  G[x][y] = <h_L[x], h_L[y]>,  loss = 0.5 sum_{x,y} (G[x][y] - adj[x][y])^2,  E = G - adj,
 //                  dh_L[x] = sum_y (E[x][y] + E[y][x]) h_L[y]      (LinearGram::backward: the diagonal term counts twice)
 //   pair_readout     one wave per pair: the two segment sums in ascending vertex order, predict, loss, dy
-//   pair_readout_dW  dW [2 H] += sum_p dy[p] g[p]: 16 rows of partial sums over the pairs p = r, r + 16, .., folded in order
+//   dW [2 H] += sum_p dy[p] g[p] is smp_vertex_level.hip's vertex_readout_dW under the timer name pair_readout_dW
 //   pair_dh          dh_L[v][c] = dy[pair(v)] W[side(v) H + c], one workgroup per graph; the levels' reverse kernels then run with dy = NULL
 //   gram_readout     one workgroup per molecule, one launch for G, the loss and dh_L (below)
 // Every sum runs in a fixed order; no atomics; two runs give the same bits.  Both read-outs are also operators of the C ABI on
 // caller-supplied operands (gf_smp_pair_readout_ex_f32, gf_smp_gram_readout_ex_f32 at the end of the file).
 #include <cmath>
 
-#include "smp_field_level.h"
+#include "smp_vertex_level.h"
 
 namespace gf {
+using namespace vertex_level;
 namespace {
-
-constexpr int kBlock = 256;   // four waves
-
-__device__ __forceinline__ float wave_sum(float v) {   // every lane gets the same bits
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(64) void pair_readout(const float *__restrict__ hL, const int *__restrict__ graph_ptr, const float *__restrict__ W,
                                                    const float *__restrict__ target, float *__restrict__ g, float *__restrict__ yhat,
@@ -41,30 +35,7 @@ __global__ __launch_bounds__(64) void pair_readout(const float *__restrict__ hL,
         }
     }
     part = wave_sum(part);
-    if (threadIdx.x == 0) {
-        const float t = target ? target[p] : 0.f;
-        yhat[p] = part;
-        if (loss) loss[p] = 0.5f * (part - t) * (part - t);
-        dy[p] = part - t;   // SquaredLoss::backward
-    }
-}
-
-// dW[c] += sum_p dy[p] g[p][c] over the width 2 H (InnerProduct::backward, second operand): 64 columns per workgroup, row r of its 16 sums
-// the pairs r, r + 16, .., the 16 partials are folded in order
-__global__ __launch_bounds__(1024) void pair_readout_dW(const float *__restrict__ dy, const float *__restrict__ g, float *__restrict__ dW, int width,
-                                                        int nPairs) {
-    __shared__ float part[16][64];
-    const int lane = threadIdx.x & 63, r = threadIdx.x >> 6, c = blockIdx.x * 64 + lane;
-    const int cc = c < width ? c : width - 1;
-    float acc = 0.f;
-    for (int p = r; p < nPairs; p += 16) acc = fmaf(dy[p], g[(size_t)p * width + cc], acc);
-    part[r][lane] = acc;
-    __syncthreads();
-    if (r == 0 && c < width) {
-        float t = 0.f;
-        for (int k = 0; k < 16; ++k) t += part[k][lane];
-        dW[c] += t;
-    }
+    GF_STORE_PREDICTION(p, part, target, yhat, loss, dy);
 }
 
 // ConCat::backward and RisiLayer1D::backward: every vertex of graph 2 p + side gets dy[p] W[side H ..]
@@ -141,10 +112,6 @@ gf_status gram_launch(gf_ctx *ctx, int H, int nMol, int maxV, const float *hL, c
     return GF_OK;
 }
 
-gf_status pair_dW_launch(gf_ctx *ctx, int H, int nPairs, const float *dy, const float *g, float *dW) {
-    GF_LAUNCH(ctx, "pair_readout_dW", pair_readout_dW, dim3((unsigned)((2 * H + 63) / 64)), dim3(1024), 0, dy, g, dW, 2 * H, nPairs);
-    return GF_OK;
-}
 gf_status pair_dh_launch(gf_ctx *ctx, int H, int nPairs, const int *graph_ptr, const float *dy, const float *W, float *dhL) {
     GF_LAUNCH(ctx, "pair_dh", pair_dh, dim3((unsigned)(2 * nPairs)), dim3(kBlock), 0, graph_ptr, dy, W, dhL, H);
     return GF_OK;
@@ -174,7 +141,7 @@ gf_status smp_readout_dW(gf_smp *s, const float *W, float *dW) {
         return GF_OK;
     }
     const int L = s->cfg.nLevels, H = s->cfg.nChanels, nPairs = s->lay.nMol / 2;
-    const gf_status st = pair_dW_launch(s->ctx, H, nPairs, s->dy, s->g, dW);
+    const gf_status st = smp_vertex_readout_dW(s->ctx, "pair_readout_dW", 2 * H, nPairs, s->dy, s->g, dW);
     return st == GF_OK ? pair_dh_launch(s->ctx, H, nPairs, s->mol_ptr, s->dy, W, s->lv[L].df) : st;
 }
 
@@ -203,10 +170,10 @@ gf_status gf_smp_pair_readout_ex_f32(gf_ctx *ctx, int H, int nV, int nPairs, con
     if (nV < 1 || nPairs < 1 || nPairs > 0x3fffffff) return gf::fail(ctx, GF_ERR_INVALID, "%s: %d vertices, %d pairs", who, nV, nPairs);
     if (!hL || !graph_ptr || !W || !g || !yhat || !dy || !dW) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const gf_status st = gf::smp_neighbourhood_check_ptr(ctx, who, "graph_ptr", graph_ptr, 2 * nPairs, nV);
+    const gf_status st = gf::check_ptr(ctx, who, "graph_ptr", graph_ptr, 2 * nPairs, nV);
     if (st != GF_OK) return st;
     GF_LAUNCH(ctx, "pair_readout", gf::pair_readout, dim3((unsigned)nPairs), dim3(64), 0, hL, graph_ptr, W, target, g, yhat, loss, dy, H);
-    gf_status st2 = gf::pair_dW_launch(ctx, H, nPairs, dy, g, dW);
+    gf_status st2 = gf::smp_vertex_readout_dW(ctx, "pair_readout_dW", 2 * H, nPairs, dy, g, dW);
     if (st2 == GF_OK && dhL) st2 = gf::pair_dh_launch(ctx, H, nPairs, graph_ptr, dy, W, dhL);
     return st2;
 }
@@ -219,7 +186,7 @@ gf_status gf_smp_gram_readout_ex_f32(gf_ctx *ctx, int H, int nV, int nMol, const
     if (nV < 1 || nMol < 1) return gf::fail(ctx, GF_ERR_INVALID, "%s: %d vertices, %d molecules", who, nV, nMol);
     if (!hL || !mol_ptr || !adj || !gram) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const gf_status st = gf::smp_neighbourhood_check_ptr(ctx, who, "mol_ptr", mol_ptr, nMol, nV);
+    const gf_status st = gf::check_ptr(ctx, who, "mol_ptr", mol_ptr, nMol, nV);
     if (st != GF_OK) return st;
     std::vector<int> mp((size_t)nMol + 1);   // (checked above: from 0, never decreasing, within the nV rows)
     GF_HIP_TRY(ctx, hipMemcpyAsync(mp.data(), mol_ptr, sizeof(int) * mp.size(), hipMemcpyDeviceToHost, ctx->stream));

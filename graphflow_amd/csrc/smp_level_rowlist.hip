@@ -28,9 +28,10 @@
 #include <vector>
 
 #include "gemm_lds.h"
-#include "smp_internal.h"
+#include "smp_vertex_level.h"
 
 namespace gf {
+using namespace vertex_level;
 namespace {
 
 using namespace lds_image;
@@ -236,13 +237,8 @@ __global__ __launch_bounds__(64) void mf_readout(const float *__restrict__ g, co
     const int m = blockIdx.x;
     float part = 0.f;
     for (int c = threadIdx.x; c < C; c += 64) part = fmaf(g[(size_t)m * C + c], W[c], part);
-    for (int d = 32; d > 0; d >>= 1) part += __shfl_xor(part, d, 64);
-    if (threadIdx.x == 0) {
-        const float t = target ? target[m] : 0.f;
-        yhat[m] = part;
-        if (loss) loss[m] = 0.5f * (part - t) * (part - t);
-        dy[m] = part - t;
-    }
+    part = wave_sum(part);
+    GF_STORE_PREDICTION(m, part, target, yhat, loss, dy);
 }
 
 // dW[c] += sum_m dy[m] g[m][c], the molecules in 16 classes folded in order; dg (optional) [nMol][C] = dy[m] W[c]
@@ -348,13 +344,7 @@ gf_status readout(gf_smp *s, const float *W, const float *targets, float *predic
     gf_ctx *ctx = s->ctx;
     const int nMol = s->lay.nMol;
     GF_LAUNCH(ctx, "mf_readout", mf_readout, dim3(nMol), dim3(64), 0, s->g, W, targets, s->yhat, loss, s->dy, width);
-    if (predict) GF_HIP_TRY(ctx, hipMemcpyAsync(predict, s->yhat, sizeof(float) * nMol, hipMemcpyDeviceToDevice, ctx->stream));
-    if (graph_feature) GF_HIP_TRY(ctx, hipMemcpyAsync(graph_feature, s->g, sizeof(float) * nMol * width, hipMemcpyDeviceToDevice, ctx->stream));
-    s->bwd_consumed = false;
-    s->forwarded = true;
-    s->has_targets = targets != nullptr;
-    mark_used(s);
-    return GF_OK;
+    return finish_forward(s, targets != nullptr, predict, graph_feature, width);
 }
 
 gf_status gcn_mw_forward(gf_smp *s, const float *params, const float *targets, float *predict, float *loss, float *graph_feature) {

@@ -23,22 +23,18 @@
 // caller-supplied operands (gf_smp_third_order_pool_fwd_ex_f32, _bwd_ex_f32 at the end of the file).
 #include <cmath>
 
-#include "smp_internal.h"
+#include "smp_vertex_level.h"
 
 namespace gf {
+using namespace vertex_level;
 namespace {
 
-constexpr int kBlock = 256;   // four waves
 constexpr int kDigit = 11;    // key bits per pass: kThirdBins = 1 << kDigit
 constexpr int kKeyBits = 50;  // 32 of the value, 18 of the flat index
 typedef unsigned long long u64;
 static_assert(kThirdBins == 1 << kDigit && kThirdBins == 8 * kBlock, "one thread folds eight bins");
 
-// a * b rounded on its own: a class's value must be the same bits wherever it is recomputed
-__device__ __forceinline__ float mul_rounded(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
+// (mul_rounded, smp_vertex_level.h: a class's value must be the same bits wherever it is recomputed)
 // fp32 bits <-> an unsigned that orders as the values do
 __device__ __forceinline__ unsigned ord_key(float t) {
     const unsigned b = __float_as_uint(t);
@@ -247,50 +243,17 @@ gf_status smp_third_pool_bwd_launch(gf_ctx *ctx, int H, int nV, const long long 
 }  // namespace gf
 
 // ---- the two kernels as stand-alone operators (include/gf_hip.h; tests/test_smp_third_order_ops_gpu.py) ----
-namespace {
-
-// A list of a stand-alone call, checked on the host (one blocking copy: these are test operators): ptr [nV + 1] starts at 0 and never
-// decreases, every member lies in [0, nV); *longest = its longest entry
-gf_status check_list(gf_ctx *ctx, const char *who, const char *what, const long long *ptr, const int *idx, int nV, long long *longest) {
-    std::vector<long long> p((size_t)nV + 1);
-    GF_HIP_TRY(ctx, hipMemcpyAsync(p.data(), ptr, sizeof(long long) * p.size(), hipMemcpyDeviceToHost, ctx->stream));
-    GF_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (p[0] != 0) return gf::fail(ctx, GF_ERR_INVALID, "%s: %s starts at %lld, not at 0", who, what, p[0]);
-    *longest = 0;
-    for (int i = 0; i < nV; ++i) {
-        if (p[i + 1] < p[i]) return gf::fail(ctx, GF_ERR_INVALID, "%s: %s decreases at entry %d", who, what, i + 1);
-        if (p[i + 1] - p[i] > *longest) *longest = p[i + 1] - p[i];
-    }
-    if (p[nV] > (1ll << 31)) return gf::fail(ctx, GF_ERR_INVALID, "%s: %s ends at %lld: more than 2^31 members", who, what, p[nV]);
-    std::vector<int> t((size_t)p[nV]);
-    if (!t.empty()) {
-        GF_HIP_TRY(ctx, hipMemcpyAsync(t.data(), idx, sizeof(int) * t.size(), hipMemcpyDeviceToHost, ctx->stream));
-        GF_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    for (size_t i = 0; i < t.size(); ++i)
-        if (t[i] < 0 || t[i] >= nV) return gf::fail(ctx, GF_ERR_INVALID, "%s: %s member %zu = %d outside [0, %d)", who, what, i, t[i], nV);
-    return GF_OK;
-}
-
-gf_status check_shape(gf_ctx *ctx, const char *who, int H, int nV) {
-    if (H < 1 || H > gf::kThirdMaxChanels) return gf::fail(ctx, GF_ERR_INVALID, "%s: %d channels (1 .. %d)", who, H, gf::kThirdMaxChanels);
-    if (nV < 1) return gf::fail(ctx, GF_ERR_INVALID, "%s: %d vertices", who, nV);
-    return GF_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 gf_status gf_smp_third_order_pool_fwd_ex_f32(gf_ctx *ctx, int H, int nV, const long long *ptr, const int *idx, const float *hprev, float *n, int *sel) {
     static const char *who = "gf_smp_third_order_pool_fwd_ex_f32";
     if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
-    gf_status st = check_shape(ctx, who, H, nV);
+    gf_status st = gf::check_shape(ctx, who, H, gf::kThirdMaxChanels, nV, 0);
     if (st != GF_OK) return st;
     if (!ptr || !idx || !hprev || !n || !sel) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     long long longest = 0;
-    st = check_list(ctx, who, "ptr", ptr, idx, nV, &longest);
+    st = gf::check_list(ctx, who, "ptr", ptr, idx, nV, nV, &longest);
     if (st != GF_OK) return st;
     if (longest > gf::smp_third_max_members(H))
         return gf::fail(ctx, GF_ERR_INVALID, "%s: a list of %lld members at %d channels (at most %d: the members are staged in LDS)", who, longest, H,
@@ -302,13 +265,12 @@ gf_status gf_smp_third_order_pool_bwd_ex_f32(gf_ctx *ctx, int H, int nV, const l
                                              const float *hprev, const int *sel, const float *dn, float *dhprev) {
     static const char *who = "gf_smp_third_order_pool_bwd_ex_f32";
     if (!ctx) return gf::fail(nullptr, GF_ERR_INVALID, "null context");
-    gf_status st = check_shape(ctx, who, H, nV);
+    gf_status st = gf::check_shape(ctx, who, H, gf::kThirdMaxChanels, nV, 0);
     if (st != GF_OK) return st;
     if (!ptr || !idx || !tptr || !tidx || !hprev || !sel || !dn || !dhprev) return gf::fail(ctx, GF_ERR_INVALID, "%s: bad argument", who);
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    long long longest = 0;
-    st = check_list(ctx, who, "ptr", ptr, idx, nV, &longest);
-    if (st == GF_OK) st = check_list(ctx, who, "tptr", tptr, tidx, nV, &longest);
+    st = gf::check_list(ctx, who, "ptr", ptr, idx, nV, nV);
+    if (st == GF_OK) st = gf::check_list(ctx, who, "tptr", tptr, tidx, nV, nV);
     if (st != GF_OK) return st;
     std::vector<int> t((size_t)nV * H);   // the record's triples index hprev's channels
     GF_HIP_TRY(ctx, hipMemcpyAsync(t.data(), sel, sizeof(int) * t.size(), hipMemcpyDeviceToHost, ctx->stream));

@@ -13,7 +13,8 @@ import pytest
 
 import neighbourhood_ops_cases as cases
 from field_suite import TOL, dev
-from test_smp_neighbourhood_ops_gpu import DEVICE, SENTINEL, context, guarded, merge, padded, ptr, report, same_bits, taken
+from test_smp_neighbourhood_ops_gpu import (DEVICE, SENTINEL, FwdSet, GatherSet, NodeSet, addr, context, flat, guarded, merge, padded, ptr, report,
+                                            same_bits, taken)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -22,23 +23,6 @@ ROW_WIDTHS = (1, 2, 3, 29, 63, 64, 65, 185)
 CHAIN_WIDTHS = (5, 16, 33, 64, 65, 128)
 OPERAND_WIDTHS = ((4, 29), (30, 3))   # (F', M): the narrower operand in either channel
 INVALID = 1
-_V = C.c_void_p
-
-
-class FwdSet(C.Structure):   # gf_nbh_fwd_set
-    _fields_ = [("FD", C.c_int)] + [(k, _V) for k in ("W1", "x", "W2", "hprev", "Tprev", "h", "n", "A", "T", "Tt")]
-
-
-class NodeSet(C.Structure):   # gf_nbh_node_set
-    _fields_ = [(k, _V) for k in ("W2", "h", "dh", "Wout", "A", "Tt", "dn", "gTt", "sA")]
-
-
-class GatherSet(C.Structure):   # gf_nbh_gather_set
-    _fields_ = [(k, _V) for k in ("dn", "gTt", "sA", "hprev", "Tprev", "dhprev")]
-
-
-def addr(t):
-    return t.data_ptr() if t is not None else None
 
 
 # ---- the row builder -----------------------------------------------------------------------------------------------------------------
@@ -217,10 +201,6 @@ def gather2(cs, nodes):
     ctx.check(ctx.lib.gf_smp_neighbourhood_gather_bwd2_ex_f32(ctx.handle, int(c0.pairs), c0.H, c0.nV, ptr(tp), ptr(ti), C.byref(sets)))
     torch.cuda.synchronize()
     return [taken(out, c.nV, c.H) for c, out in zip(cs, outs)]
-
-
-def flat(d, keys):
-    return [d[k] for k in keys if d.get(k) is not None]
 
 
 @pytest.mark.parametrize("top", [False, True], ids=["inner", "top"])

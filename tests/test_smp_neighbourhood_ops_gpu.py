@@ -51,6 +51,25 @@ def taken(t, rows, width, written=True, prefilled=False):
     return a[:n].reshape((rows, width) if width > 1 else (rows,))
 
 
+_V = C.c_void_p
+
+
+class FwdSet(C.Structure):   # gf_nbh_fwd_set
+    _fields_ = [("FD", C.c_int)] + [(k, _V) for k in ("W1", "x", "W2", "hprev", "Tprev", "h", "n", "A", "T", "Tt")]
+
+
+class NodeSet(C.Structure):   # gf_nbh_node_set
+    _fields_ = [(k, _V) for k in ("W2", "h", "dh", "Wout", "A", "Tt", "dn", "gTt", "sA")]
+
+
+class GatherSet(C.Structure):   # gf_nbh_gather_set
+    _fields_ = [(k, _V) for k in ("dn", "gTt", "sA", "hprev", "Tprev", "dhprev")]
+
+
+def addr(t):
+    return t.data_ptr() if t is not None else None
+
+
 def padded(idx):
     """an index list on the device, one spare entry behind it (an empty list still has an address)"""
     return dev(np.append(np.asarray(idx, dtype=np.int64), 0), np.int32)
@@ -72,50 +91,92 @@ def call(name, args, over):
     return st
 
 
+def call2(name, cls, at, args, over, second):
+    """the two-set entry of an operator on the arguments of its one-set entry: those that are fields of cls are set 0; set 1 is the same
+    set with the buffers `second` (by argument name) in place of set 0's and with `over`'s fields -- an offence sits in position 1.  The
+    other arguments, with `over`'s, are the call's own; the sets go in at position `at` of them."""
+    ctx = context()
+    fields = [f for f, _ in cls._fields_]
+    unknown = set(over) - {k for k, _ in args}
+    assert not unknown, unknown
+    keep, sets, shared = [], (cls * 2)(), []
+
+    def value(v):
+        if isinstance(v, np.ndarray):
+            v = torch.as_tensor(np.ascontiguousarray(v)).cuda()
+            keep.append(v)
+        return v if isinstance(v, int) else addr(v)
+
+    for k, v in args:
+        if k in fields:
+            setattr(sets[0], k, value(v))
+            setattr(sets[1], k, value(over[k] if k in over else second.get(k, v)))
+        else:
+            shared.append(value(over[k] if k in over else v))
+    shared.insert(at, C.byref(sets))
+    st = getattr(ctx.lib, name)(ctx.handle, *shared)
+    torch.cuda.synchronize()
+    return st
+
+
 class Device:
     """the backend of neighbourhood_ops_cases.check_*: with status=True a method returns (status, the output buffers, [(in/out
-    buffer, its prefill)]), else it checks the status and returns the outputs as arrays (None for one the form does not store)"""
+    buffer, its prefill)]), else it checks the status and returns the outputs as arrays (None for one the form does not store).
+    twice=True: the two-set entry with the call's one set given twice, each with output buffers of its own -- the buffers of both sets
+    with status=True, else [the outputs of set 0, of set 1]"""
 
-    def forward(self, c, rounds=0, status=False, **over):
+    def forward(self, c, rounds=0, status=False, twice=False, **over):
         H, nV = c.H, c.nV
-        out = {k: guarded(nV, H) for k in ("h", "n", "A")}
-        out.update({k: guarded(nV, 1) for k in ("T", "Tt")})
+        outs = [{k: guarded(nV, 1 if k in ("T", "Tt") else H) for k in ("h", "n", "A", "T", "Tt")} for _ in range(2 if twice else 1)]
+        out = outs[0]
         lvl = c.W2 is not None
         args = [("pairs", int(c.pairs)), ("H", H), ("FD", c.FD), ("nV", nV), ("rounds", rounds), ("W1", dev(c.W1)), ("x", dev(c.x)),
                 ("W2", dev(c.W2) if lvl else None), ("hprev", dev(c.hprev)), ("Tprev", dev(c.Tprev)), ("ptr", dev(c.ptr, np.int64)),
                 ("idx", padded(c.idx))] + [(k, out[k]) for k in ("h", "n", "A", "T", "Tt")]
-        st = call("gf_smp_neighbourhood_fwd_ex_f32", args, over)
+        st = call2("gf_smp_neighbourhood_fwd2_ex_f32", FwdSet, 4, args, over, outs[1]) if twice else call("gf_smp_neighbourhood_fwd_ex_f32", args, over)
         if status:
-            return st, list(out.values()), []
+            return st, [t for o in outs for t in o.values()], []
         context().check(st)
         wr = {"h": True, "n": lvl, "A": lvl and c.pairs, "T": c.pairs, "Tt": lvl and c.pairs}
-        return {k: taken(out[k], nV, H if k in ("h", "n", "A") else 1, wr[k]) for k in out}
+        res = [{k: taken(o[k], nV, H if k in ("h", "n", "A") else 1, wr[k]) for k in o} for o in outs]
+        return res if twice else res[0]
 
-    def node(self, c, h_, A_, Tt_, top=False, rounds=0, status=False, **over):
+    def node(self, c, h_, A_, Tt_, top=False, rounds=0, status=False, twice=False, **over):
         H, nV = c.H, c.nV
         lvl = c.W2 is not None
-        out = {"dz": guarded(nV, H, c.dh), "dn": guarded(nV, H), "gTt": guarded(nV, H), "sA": guarded(nV, 1)}
+        outs = [{"dz": guarded(nV, H, c.dh), "dn": guarded(nV, H), "gTt": guarded(nV, H), "sA": guarded(nV, 1)} for _ in range(2 if twice else 1)]
+        out = outs[0]
         args = [("pairs", int(c.pairs)), ("H", H), ("nV", nV), ("rounds", rounds), ("W2", dev(c.W2) if lvl else None), ("h", dev(h_)),
                 ("dh", out["dz"]), ("dy", dev(c.dy_top) if top else None), ("Wout", dev(c.W)), ("vmol", dev(c.vmol, np.int32)),
                 ("nMol", c.nMol), ("A", dev(A_) if A_ is not None else None), ("Tt", dev(Tt_) if Tt_ is not None else None),
                 ("dn", out["dn"]), ("gTt", out["gTt"]), ("sA", out["sA"])]
-        st = call("gf_smp_neighbourhood_node_bwd_ex_f32", args, over)
+        if twice:
+            second = {"dh" if k == "dz" else k: t for k, t in outs[1].items()}
+            st = call2("gf_smp_neighbourhood_node_bwd2_ex_f32", NodeSet, 4, args, over, second)
+        else:
+            st = call("gf_smp_neighbourhood_node_bwd_ex_f32", args, over)
         if status:
-            return st, [out[k] for k in ("dn", "gTt", "sA")], [(out["dz"], c.dh)]
+            return st, [o[k] for o in outs for k in ("dn", "gTt", "sA")], [(o["dz"], c.dh) for o in outs]
         context().check(st)
         wr = {"dz": True, "dn": lvl, "gTt": lvl and c.pairs, "sA": lvl and c.pairs}
-        return {k: taken(out[k], nV, 1 if k == "sA" else H, wr[k], prefilled=k == "dz") for k in out}
+        res = [{k: taken(o[k], nV, 1 if k == "sA" else H, wr[k], prefilled=k == "dz") for k in o} for o in outs]
+        return res if twice else res[0]
 
-    def gather(self, c, dn_, gTt_, sA_, status=False, **over):
-        out = guarded(c.nV, c.H)
+    def gather(self, c, dn_, gTt_, sA_, status=False, twice=False, **over):
+        outs = [guarded(c.nV, c.H) for _ in range(2 if twice else 1)]
+        out = outs[0]
         args = [("pairs", int(c.pairs)), ("H", c.H), ("nV", c.nV), ("tptr", dev(c.tptr, np.int64)), ("tidx", padded(c.tidx)), ("dn", dev(dn_)),
                 ("gTt", dev(gTt_) if gTt_ is not None else None), ("sA", dev(sA_) if sA_ is not None else None), ("hprev", dev(c.hprev)),
                 ("Tprev", dev(c.Tprev)), ("dhprev", out)]
-        st = call("gf_smp_neighbourhood_gather_bwd_ex_f32", args, over)
+        if twice:
+            st = call2("gf_smp_neighbourhood_gather_bwd2_ex_f32", GatherSet, 5, args, over, {"dhprev": outs[1]})
+        else:
+            st = call("gf_smp_neighbourhood_gather_bwd_ex_f32", args, over)
         if status:
-            return st, [out], []
+            return st, outs, []
         context().check(st)
-        return taken(out, c.nV, c.H)
+        res = [taken(o, c.nV, c.H) for o in outs]
+        return res if twice else res[0]
 
     def readout(self, c, hL_, target=True, loss=True, status=False, **over):
         H, nMol = c.H, c.nMol
@@ -144,6 +205,10 @@ def report(title, err):
     print("%s: %s" % (title, ", ".join("%s %.2e" % kv for kv in sorted(err.items()))))
     bad = {k: v for k, v in err.items() if not v <= TOL}
     assert not bad, (title, bad)
+
+
+def flat(d, keys):
+    return [d[k] for k in keys if d.get(k) is not None]
 
 
 def same_bits(a, b):
@@ -250,13 +315,33 @@ def test_same_bits_twice(gf, case):
     same_bits(cases.check_chain(c, DEVICE, rounds)[1], cases.check_chain(c, DEVICE, rounds)[1])
 
 
+@pytest.mark.parametrize("pairs", [False, True], ids=["sum", "pairs"])
+@pytest.mark.parametrize("H", [5, 65])
+def test_one_set_and_two_set_entries_share_one_path(gf, H, pairs):
+    """each of the three kernels through its one-set entry, and through its two-set entry with that set given twice and outputs of its
+    own per set: the three results are the same bits.  One and two channels per lane; 37 vertices are more than a workgroup's slots at
+    either width (32 and 4), the last round ragged; the node kernel as an inner and as the top level"""
+    c = cases.Case(H, 4, pairs, cases.mixed_lists(37, np.random.default_rng(8000 + H)), seed=23 * H + pairs)
+    assert c.nV == 37 > cases.slots(H)
+    f, f2 = DEVICE.forward(c), DEVICE.forward(c, twice=True)
+    for two in f2:
+        same_bits(flat(f, ("h", "n", "A", "T", "Tt")), flat(two, ("h", "n", "A", "T", "Tt")))
+    for top in (False, True):
+        nb, nb2 = DEVICE.node(c, f["h"], f["A"], f["Tt"], top), DEVICE.node(c, f["h"], f["A"], f["Tt"], top, twice=True)
+        for two in nb2:
+            same_bits(flat(nb, ("dz", "dn", "gTt", "sA")), flat(two, ("dz", "dn", "gTt", "sA")))
+    g, g2 = DEVICE.gather(c, nb["dn"], nb["gTt"], nb["sA"]), DEVICE.gather(c, nb["dn"], nb["gTt"], nb["sA"], twice=True)
+    same_bits([g, g], g2)
+
+
 def test_parity_under_poison(gf):
     """GF_POISON=1: no kernel of the level reads memory nobody wrote -- the instantiation and rounds tests in a fresh child process"""
     kit.run_under_poison(__file__, "every_instantiation or rounds_and_ragged")
 
 
 def test_refusals_leave_the_context_usable(gf):
-    """every refusal answers GF_ERR_INVALID, names its reason and writes nothing; then the same context serves a call"""
+    """every refusal answers GF_ERR_INVALID, names its reason and writes nothing; then the same context serves a call.  Every case of
+    a level kernel is asked of its one-set entry and of its two-set entry with the offending set in position 1"""
     from graphflow_amd import _lib
     c = cases.instantiation_case(9, 4, True)
     f = cases.Numpy32().forward(c)
@@ -286,16 +371,20 @@ def test_refusals_leave_the_context_usable(gf):
                         dict(H=128, FD=186), dict(ptr=i64(bad(c.ptr, 0, 1))), dict(ptr=i64(bad(c.ptr, 5, c.ptr[4] - 1))),
                         dict(idx=i32(bad(np.append(c.idx, 0), 3, c.nV))), dict(idx=i32(bad(np.append(c.idx, 0), 0, -1)))]:
         refused(DEVICE.forward(c, status=True, **kw))
+        refused(DEVICE.forward(c, status=True, twice=True, **kw))
     still_works()
     for kw in shapes + [dict(rounds=-1), dict(h=None), dict(dh=None), dict(dn=None), dict(A=None), dict(Tt=None), dict(gTt=None), dict(sA=None)]:
         refused(DEVICE.node(c, f["h"], f["A"], f["Tt"], status=True, **kw))
+        refused(DEVICE.node(c, f["h"], f["A"], f["Tt"], status=True, twice=True, **kw))
     for kw in (dict(Wout=None), dict(vmol=None), dict(nMol=0), dict(vmol=i32(bad(c.vmol, 2, c.nMol))), dict(vmol=i32(bad(c.vmol, c.nV - 1, -1)))):
         refused(DEVICE.node(c, f["h"], f["A"], f["Tt"], top=True, status=True, **kw))
+        refused(DEVICE.node(c, f["h"], f["A"], f["Tt"], top=True, status=True, twice=True, **kw))
     still_works()
     for kw in shapes + [dict(tptr=None), dict(tidx=None), dict(dn=None), dict(dhprev=None), dict(gTt=None), dict(sA=None), dict(hprev=None),
                         dict(Tprev=None), dict(tptr=i64(bad(c.tptr, 0, 2))), dict(tptr=i64(bad(c.tptr, 7, c.tptr[6] - 1))),
                         dict(tidx=i32(bad(np.append(c.tidx, 0), 1, c.nV))), dict(tidx=i32(bad(np.append(c.tidx, 0), 1, -2)))]:
         refused(DEVICE.gather(c, nb["dn"], nb["gTt"], nb["sA"], status=True, **kw))
+        refused(DEVICE.gather(c, nb["dn"], nb["gTt"], nb["sA"], status=True, twice=True, **kw))
     still_works()
     for kw in shapes + [dict(nMol=0), dict(hL=None), dict(mol_ptr=None), dict(W=None), dict(g=None), dict(yhat=None), dict(dy=None), dict(dW=None),
                         dict(mol_ptr=i32(bad(c.mol_ptr, 0, 1))), dict(mol_ptr=i32(bad(c.mol_ptr, 2, c.mol_ptr[1] - 1))),
