@@ -211,6 +211,34 @@ PROTOTYPES.update({
     "gf_smp_model_adam_step": (_i, [_vp, C.c_double, _i]),
 })
 
+
+class FitConfig(C.Structure):
+    """gf_smp_fit_config"""
+    _fields_ = [("kind", _i), ("optimiser", _i), ("nIterations", _i), ("learning_rate", C.c_double), ("epsilon", C.c_double),
+                ("gamma", C.c_double)]
+
+
+class FitReport(C.Structure):
+    """gf_smp_fit_report"""
+    _fields_ = [("first", C.c_double), ("second", C.c_double), ("iterations", _i), ("accepted", _i), ("rejected", _i),
+                ("left_early", _i), ("learning_rate", C.c_double)]
+
+
+_fitc, _fitr, _u8p = C.POINTER(FitConfig), C.POINTER(FitReport), C.POINTER(C.c_ubyte)
+PROTOTYPES.update({
+    "gf_smp_parameters_snapshot": (_i, [_vp, _vp]),
+    "gf_smp_parameters_rollback": (_i, [_vp, _vp]),
+    "gf_smp_forward_host_samples": (_i, [_vp, _dp, _dp, _dp, _dp]),
+    "gf_smp_gram_host": (_i, [_vp, _dp]),
+    "gf_smp_fit": (_i, [_vp, _vp, _vp, _vp, _fitc, _fitr, _u8p]),
+    "gf_smp_fit_host": (_i, [_vp, _dp, _fitc, _fitr, _u8p]),
+    "gf_smp_loss_sum_f32": (_i, [_vp, _vp, C.c_size_t, _dp]),
+    "gf_smp_model_parameters_snapshot": (_i, [_vp, _vp]),
+    "gf_smp_model_parameters_rollback": (_i, [_vp, _vp]),
+    "gf_smp_model_fit": (_i, [_vp, _vp, _vp, _vp, _fitc, _fitr, _u8p]),
+    "gf_smp_model_fit_host": (_i, [_vp, _dp, _fitc, _fitr, _u8p]),
+})
+
 _lib = None
 
 

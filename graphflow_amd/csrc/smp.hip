@@ -708,8 +708,9 @@ gf_status gf_smp_destroy(gf_smp *s) {
         (void)hipEventDestroy(s->ev_mask);
     }
     if (s->mask_stage) (void)hipHostFree(s->mask_stage);
-    for (float *p : {s->rs_inv, s->adam_m, s->adam_v, s->own_p, s->own_g, s->pad_p, s->pad_g, s->pad_feat})
+    for (float *p : {s->rs_inv, s->adam_m, s->adam_v, s->own_p, s->own_g, s->pad_p, s->pad_g, s->pad_feat, s->fit_cache})
         if (p) (void)hipFree(p);
+    if (s->fit_sum) (void)hipFree(s->fit_sum);
     delete s;
     return GF_OK;
 }

@@ -335,6 +335,8 @@ struct gf_smp_batch {
     size_t colpart_rows = 0;
     int *top_node_mol = nullptr, *mol_ptr = nullptr, *mol_nodes = nullptr;
     float *own_t = nullptr, *own_y = nullptr, *own_loss = nullptr, *own_feat = nullptr;  // per-batch, freed by release()
+    float *fit_t = nullptr, *fit_y = nullptr, *fit_loss = nullptr, *fit_feat = nullptr;  // the same per SAMPLE (smp_fit.hip: a pair, else a molecule)
+    float *fit_gram = nullptr;   // [gram_count] staging of gf_smp_gram_host
 };
 struct gf_smp : gf_smp_batch {
     gf_ctx *ctx = nullptr;
@@ -397,6 +399,10 @@ struct gf_smp : gf_smp_batch {
     // handle-owned model (host-pointer mode of the driver): parameters and their gradient, [param_count] each
     float *own_p = nullptr, *own_g = nullptr;
     unsigned long long adam_n = 0;  // parameter elements processed so far (the reference's running beta powers)
+    // smp_fit.hip: the parameter cache of gf_smp_parameters_snapshot / _rollback [param_count] and the 8 bytes of the loop's loss sum;
+    // taken on first use, freed by gf_smp_destroy
+    float *fit_cache = nullptr;
+    double *fit_sum = nullptr;
 };
 
 namespace gf {

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "libc_random.h"
+#include "smp_fit.h"
 #include "smp_internal.h"
 
 namespace gf {
@@ -54,6 +55,9 @@ struct gf_smp_model {
     float *own_p = nullptr, *own_g = nullptr, *adam_m = nullptr, *adam_v = nullptr;
     unsigned long long adam_n = 0;
     float *own_t = nullptr, *own_y = nullptr, *own_loss = nullptr;
+    // the parameter cache of gf_smp_model_parameters_snapshot / _rollback and the 8 bytes of gf_smp_model_fit's loss sum (smp_fit.h)
+    float *fit_cache = nullptr;
+    double *fit_sum = nullptr;
 };
 
 namespace gf {
@@ -275,9 +279,10 @@ gf_status gf_smp_model_destroy(gf_smp_model *m) {
     }
     gf::free_batch(m);
     if (m->lvl_off) (void)hipFree(m->lvl_off);
-    float *own[] = {m->own_p, m->own_g, m->adam_m, m->adam_v};
+    float *own[] = {m->own_p, m->own_g, m->adam_m, m->adam_v, m->fit_cache};
     for (float *p : own)
         if (p) (void)hipFree(p);
+    if (m->fit_sum) (void)hipFree(m->fit_sum);
     delete m;
     return GF_OK;
 }
@@ -534,6 +539,75 @@ gf_status gf_smp_model_adam_step(gf_smp_model *m, double learning_rate, int nBat
     gf_status st = gf_adam_step_f32(m->ctx, m->own_p, m->own_g, m->adam_m, m->adam_v, m->n_params, learning_rate, nBatch, m->adam_n);
     if (st == GF_OK) m->adam_n += m->n_params;
     return st;
+}
+
+// ---- the classes' iterative training calls (smp_fit.h) on the composite handle ----------------------------------------------
+gf_status gf_smp_model_parameters_snapshot(gf_smp_model *m, const float *params) {
+    if (!m) return fail(nullptr, GF_ERR_INVALID, "null model");
+    if (!params) params = m->own_p;
+    if (!params) return fail(m->ctx, GF_ERR_INVALID, "gf_smp_model_parameters_snapshot: null params and no handle-owned model");
+    return gf::fit_snapshot(m->ctx, &m->fit_cache, params, m->n_params);
+}
+
+gf_status gf_smp_model_parameters_rollback(gf_smp_model *m, float *params) {
+    if (!m) return fail(nullptr, GF_ERR_INVALID, "null model");
+    if (!params) params = m->own_p;
+    if (!params) return fail(m->ctx, GF_ERR_INVALID, "gf_smp_model_parameters_rollback: null params and no handle-owned model");
+    return gf::fit_rollback(m->ctx, &m->fit_cache, params, m->n_params, "gf_smp_model_parameters_rollback");
+}
+
+// Every composite class of the reference trains with Adam (SMP_omega_physics.h:264): optimiser = 1 is refused.
+gf_status gf_smp_model_fit(gf_smp_model *m, float *params, float *grads, const float *targets, const gf_smp_fit_config *cfg,
+                           gf_smp_fit_report *report, unsigned char *decisions) {
+    if (!m) return fail(nullptr, GF_ERR_INVALID, "null model");
+    gf_ctx *ctx = m->ctx;
+    if (!params && !grads && m->own_p) {
+        params = m->own_p;
+        grads = m->own_g;
+    }
+    if (!params || !grads || !targets) return fail(ctx, GF_ERR_INVALID, "gf_smp_model_fit: null params / grads (and no handle-owned model) or null targets");
+    gf_status st = gf::fit_check_config(ctx, cfg, report, m->nMol, "gf_smp_model_fit");
+    if (st != GF_OK) return st;
+    if (cfg->optimiser != 0) return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_model_fit: the composite models train with Adam (optimiser = 0)");
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!m->adam_m) {
+        float **bufs[] = {&m->adam_m, &m->adam_v};
+        for (float **b : bufs) {
+            GF_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(b), m->n_params * sizeof(float)));
+            GF_HIP_TRY(ctx, hipMemsetAsync(*b, 0, m->n_params * sizeof(float), ctx->stream));
+        }
+        m->adam_n = 0;
+    }
+    gf::FitDriver d;
+    d.ctx = ctx;
+    d.who = "gf_smp_model_fit";
+    d.params = params;
+    d.n_params = m->n_params;
+    d.nSamples = m->nMol;
+    d.loss = m->own_loss;
+    d.cache = &m->fit_cache;
+    d.sum = &m->fit_sum;
+    d.forward = [=]() { return gf_smp_model_forward(m, params, targets, nullptr, m->own_loss); };
+    d.backward = [=]() { return gf_smp_model_backward(m, params, grads, 0); };
+    d.step = [=](double lr, int nBatch, bool per_call) {
+        if (per_call) return gf::fit_adam_step_per_call(ctx, params, grads, m->adam_m, m->adam_v, m->n_params, lr, &m->adam_n);
+        const gf_status s2 = gf_adam_step_f32(ctx, params, grads, m->adam_m, m->adam_v, m->n_params, lr, nBatch, m->adam_n);
+        if (s2 == GF_OK) m->adam_n += m->n_params;
+        return s2;
+    };
+    return gf::fit_run(d, cfg, report, decisions);
+}
+
+gf_status gf_smp_model_fit_host(gf_smp_model *m, const double *targets, const gf_smp_fit_config *cfg, gf_smp_fit_report *report,
+                                unsigned char *decisions) {
+    if (!m || !m->own_p) return fail(m ? m->ctx : nullptr, GF_ERR_INVALID, "gf_smp_model_fit_host: no handle-owned model");
+    gf_ctx *ctx = m->ctx;
+    if (!targets || m->nMol < 1) return fail(ctx, GF_ERR_INVALID, "gf_smp_model_fit_host: null targets / no prepared batch");
+    std::vector<float> tmp((size_t)m->nMol);
+    for (int i = 0; i < m->nMol; ++i) tmp[i] = (float)targets[i];
+    GF_HIP_TRY(ctx, hipMemcpyAsync(m->own_t, tmp.data(), sizeof(float) * m->nMol, hipMemcpyHostToDevice, ctx->stream));
+    GF_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return gf_smp_model_fit(m, nullptr, nullptr, m->own_t, cfg, report, decisions);
 }
 
 }  // extern "C"

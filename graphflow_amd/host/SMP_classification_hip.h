@@ -26,7 +26,7 @@
 
 #include "gf_runtime.h"
 
-class SMP_classification_hip {
+class SMP_classification_hip : public gfhost::FitLog {   // (last_fit / last_decisions of the last iterative call)
 protected:
     SMP_classification_hip(int nClass, int max_nVertices, int nLevels, int nChanels, int nFeatures, int nDepth, double momentum_param,
                            bool has_WL_ordering, int nContractions)
@@ -56,6 +56,18 @@ public:
         must(gf_smp_momentum_step(net, NULL, NULL, learning_rate, nBatch, momentum), "gf_smp_momentum_step");
         ret.second = forward_loss(nBatch, target);
         return ret;
+    }
+
+    // the two iterative calls (SMP_2D_ver6_classification.h:604-697): the class's loops on LogLoss values, inside the library
+    template <class Graph>
+    std::pair<double, double> BatchLearn(int nBatch, Graph **molecule, double *target, int nIterations, double learning_rate, double epsilon) {
+        bind(nBatch, molecule);
+        return fit(0, target, nIterations, learning_rate, epsilon);
+    }
+    template <class Graph>
+    std::pair<double, double> Learn(Graph *molecule, double target, int nIterations, double learning_rate, double epsilon) {
+        bind(1, &molecule);
+        return fit(1, &target, nIterations, learning_rate, epsilon);
     }
 
     template <class Graph>
@@ -114,6 +126,9 @@ private:
             }
         }
         must(gf_smp_prepare(net, nBatch, &nV[0], &adj[0], &feature[0]), "gf_smp_prepare");
+    }
+    std::pair<double, double> fit(int kind, const double *target, int nIterations, double learning_rate, double epsilon) {
+        return gfhost::fit_host(gf_smp_fit_host, "gf_smp_fit_host", net, target, kind, 1, nIterations, learning_rate, epsilon, momentum, this);
     }
     void must(gf_status st, const char *what) {
         if (st != GF_OK) gfhost::die(gfhost::default_context(), what, st);

@@ -6,6 +6,8 @@
 //             nLevels, nChanels, nFeatures, nDepth[, wl])  rand() exactly as weights_initialization does (:334-338)
 //   BatchLearn(nBatch, DenseGraph**, target, lr)  :798     one device pass over the whole batch (loss before, summed
 //                                                          gradients, Adam::Learn(lr, nBatch), loss after)
+//   BatchLearn(nBatch, ..., nIterations, lr, eps) :827     the class's backtracking loop inside the library (gf_smp_fit_host, kind 0)
+//   Learn(molecule, target, nIterations, lr, eps) :876     ... on one sample (kind 1)
 //   Threaded_BatchLearn(...)                      :750     the same update without the two loss evaluations
 //   getLoss / Predict / Threaded_Predict / Feature         forward only            (:695, :924, :944, :984)
 //   init_multi_threads(nThreads)                  :115     accepted, nothing to do: a batch already runs as one launch
@@ -25,7 +27,7 @@
 
 #include "gf_runtime.h"
 
-class SMP_omega_hip {
+class SMP_omega_hip : public gfhost::FitLog {   // (last_fit / last_decisions of the last iterative call)
 public:
     SMP_omega_hip(int max_nVertices, int max_receptive_field, int nLevels, int nChanels, int nFeatures, int nDepth,
                   bool has_WL_ordering = true)
@@ -101,6 +103,18 @@ public:
         ret.second = 0.0;
         for (int i = 0; i < nBatch; ++i) ret.second += loss[i];
         return ret;
+    }
+
+    // the two iterative calls (SMP_omega.h:827-922): the class's loops, comparison for comparison, inside the library (gf_smp_fit_host)
+    template <class Graph>
+    std::pair<double, double> BatchLearn(int nBatch, Graph **molecule, double *target, int nIterations, double learning_rate, double epsilon) {
+        bind(nBatch, molecule);
+        return fit(0, target, nIterations, learning_rate, epsilon);
+    }
+    template <class Graph>
+    std::pair<double, double> Learn(Graph *molecule, double target, int nIterations, double learning_rate, double epsilon) {
+        bind(1, &molecule);
+        return fit(1, &target, nIterations, learning_rate, epsilon);
     }
 
     template <class Graph>
@@ -194,6 +208,10 @@ private:
             must(gf_smp_momentum_step(net, NULL, NULL, learning_rate, nBatch, momentum), "gf_smp_momentum_step");
         else
             must(gf_smp_adam_step(net, NULL, NULL, learning_rate, nBatch), "gf_smp_adam_step");
+    }
+    std::pair<double, double> fit(int kind, const double *target, int nIterations, double learning_rate, double epsilon) {
+        return gfhost::fit_host(gf_smp_fit_host, "gf_smp_fit_host", net, target, kind, use_momentum ? 1 : 0, nIterations, learning_rate, epsilon,
+                                momentum, this);
     }
     void must(gf_status st, const char *what) {
         if (st != GF_OK) gfhost::die(gfhost::default_context(), what, st);

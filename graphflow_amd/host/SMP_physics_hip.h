@@ -28,7 +28,7 @@
 
 #include "gf_runtime.h"
 
-class SMP_model_hip {
+class SMP_model_hip : public gfhost::FitLog {   // (last_fit / last_decisions of the last iterative call)
 protected:
     // nContractions: 18 (RisiContraction_18 / _18_dropout towers) or 4 (the `_gamma` models: RisiContraction_4, K_l [4 C_{l-1}][C_l]);
     // 0 with first_order = 1: the first-order towers of the `_theta` models, and with ccn_1d and nChanels_decay those of CCN_1D
@@ -128,6 +128,13 @@ protected:
         return ret;
     }
     void predict_batch(int nBatch, double *predict) { must(gf_smp_model_forward_host(net, NULL, predict, NULL), "gf_smp_model_forward_host"); }
+    // the two iterative calls on the prepared batch (SMP_omega_physics.h:730-825): kind 0 BatchLearn, 1 Learn; Adam (gf_smp_model_fit_host).
+    // With RisiContraction_18_dropout in the towers (SMP_sigma_pairgraphs_hip, train mode) this is NOT the class's loop draw for draw: the
+    // class evaluates the loss with one set of slice masks and draws fresh ones for the forward its reverse sweep starts from; here the
+    // reverse sweep starts from the forward that evaluated the loss (one draw per iteration where the class has two).
+    std::pair<double, double> fit(int kind, const double *target, int nIterations, double learning_rate, double epsilon) {
+        return gfhost::fit_host(gf_smp_model_fit_host, "gf_smp_model_fit_host", net, target, kind, 0, nIterations, learning_rate, epsilon, 0.0, this);
+    }
     void must(gf_status st, const char *what) {
         if (st != GF_OK) gfhost::die(gfhost::default_context(), what, st);
     }
@@ -167,6 +174,18 @@ public:
         pack(0, nBatch, molecule);
         prepare(nBatch);
         return learn(nBatch, target, learning_rate, true);
+    }
+    template <class Graph>
+    std::pair<double, double> BatchLearn(int nBatch, Graph **molecule, double *target, int nIterations, double learning_rate, double epsilon) {
+        pack(0, nBatch, molecule);
+        prepare(nBatch);
+        return fit(0, target, nIterations, learning_rate, epsilon);
+    }
+    template <class Graph>
+    std::pair<double, double> Learn(Graph *molecule, double target, int nIterations, double learning_rate, double epsilon) {
+        pack(0, 1, &molecule);
+        prepare(1);
+        return fit(1, &target, nIterations, learning_rate, epsilon);
     }
     template <class Graph>
     void Threaded_BatchLearn(int nBatch, Graph **molecule, double *target, double learning_rate) {
@@ -225,6 +244,17 @@ public:
         return learn(nBatch, target, learning_rate, true);
     }
     template <class Graph>
+    std::pair<double, double> BatchLearn(int nBatch, Graph **molecule_1, Graph **molecule_2, double *target, int nIterations, double learning_rate,
+                                         double epsilon) {
+        bind(nBatch, molecule_1, molecule_2);
+        return fit(0, target, nIterations, learning_rate, epsilon);
+    }
+    template <class Graph>
+    std::pair<double, double> Learn(Graph *molecule_1, Graph *molecule_2, double target, int nIterations, double learning_rate, double epsilon) {
+        bind(1, &molecule_1, &molecule_2);
+        return fit(1, &target, nIterations, learning_rate, epsilon);
+    }
+    template <class Graph>
     void Threaded_BatchLearn(int nBatch, Graph **molecule_1, Graph **molecule_2, double *target, double learning_rate) {
         bind(nBatch, molecule_1, molecule_2);
         learn(nBatch, target, learning_rate, false);
@@ -257,7 +287,8 @@ public:
                                    nLevels, nChanels, nFeatures_1, nFeatures_2) {}
 };
 
-// RisiContraction_18_dropout inside the towers (SMP_sigma_pairgraphs.h:81): nKept of the 18 slices in train mode
+// RisiContraction_18_dropout inside the towers (SMP_sigma_pairgraphs.h:81): nKept of the 18 slices in train mode.  Its iterative
+// BatchLearn / Learn draw the slice masks once per iteration, not twice as the class does (SMP_model_hip::fit says how).
 class SMP_sigma_pairgraphs_hip : public SMP_omega_pairgraphs_hip {
 public:
     SMP_sigma_pairgraphs_hip(int max_nVertices_1, int max_nVertices_2, int max_receptive_field, int nLevels, int nChanels,

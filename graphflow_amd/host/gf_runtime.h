@@ -9,6 +9,9 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <utility>
+#include <vector>
 
 #include <sys/syscall.h>
 #include <unistd.h>
@@ -111,6 +114,27 @@ GF_HOST_OVERLOAD2(stack_forward_host, (gf_ctx * c, const double *const *t, doubl
 GF_HOST_OVERLOAD2(stack_backward_host, (gf_ctx * c, const double *g, double *const *d, int n, size_t per),
                   (gf_ctx * c, const float *g, float *const *d, int n, size_t per), (c, g, d, n, per))
 #undef GF_HOST_OVERLOAD2
+
+// What the model classes keep of their last iterative BatchLearn / Learn: gf_smp_fit's report, and one entry per iteration it ran
+// (1 kept, 2 restored, 3 restored and left, 4 left on error < epsilon).  Zero / empty before the first such call.
+struct FitLog {
+    gf_smp_fit_report last_fit;
+    std::vector<unsigned char> last_decisions;
+    FitLog() { std::memset(&last_fit, 0, sizeof last_fit); }
+};
+// The two iterative calls of every model class on the batch its handle holds: `call` is gf_smp_fit_host or gf_smp_model_fit_host.
+// kind 0: BatchLearn(nBatch, ..., nIterations, learning_rate, epsilon), 1: Learn(...); optimiser 0: Adam, 1: Momentum(gamma).
+template <class Handle>
+inline std::pair<double, double> fit_host(gf_status (*call)(Handle *, const double *, const gf_smp_fit_config *, gf_smp_fit_report *, unsigned char *),
+                                          const char *what, Handle *net, const double *target, int kind, int optimiser, int nIterations,
+                                          double learning_rate, double epsilon, double gamma, FitLog *log) {
+    gf_smp_fit_config fc = {kind, optimiser, nIterations, learning_rate, epsilon, gamma};
+    log->last_decisions.assign(nIterations > 0 ? nIterations : 1, 0);
+    const gf_status st = call(net, target, &fc, &log->last_fit, &log->last_decisions[0]);
+    if (st != GF_OK) die(default_context(), what, st);
+    log->last_decisions.resize(log->last_fit.iterations);
+    return std::make_pair(log->last_fit.first, log->last_fit.second);
+}
 
 }  // namespace gfhost
 #endif

@@ -135,6 +135,36 @@ class SMPOmega:
     def adam_reset(self):
         self.ctx.check(self.lib.gf_smp_adam_reset(self.handle))
 
+    def fit(self, params, grads, targets, nIterations, learning_rate, epsilon=0.0, kind=0, optimiser="adam", gamma=0.9):
+        """The classes' iterative training calls on the prepared batch (gf_smp_fit): kind 0 = BatchLearn(nBatch, molecule, target,
+        nIterations, learning_rate, epsilon), kind 1 = Learn(molecule, target, ...) on a batch of one sample.  optimiser "adam" or
+        "momentum" (with gamma).  targets: one float32 per sample on the device (None for the Gram auto-encoder).  Returns (report,
+        decisions): the dict of gf_smp_fit_report and one entry per iteration run -- 1 kept, 2 restored, 3 restored and left, 4 left on
+        error < epsilon."""
+        self._flat(params, "params")
+        self._flat(grads, "grads")
+        if optimiser not in ("adam", "momentum"):
+            raise ValueError("fit: optimiser %r (\"adam\" or \"momentum\")" % (optimiser,))
+        cfg = _lib.FitConfig(int(kind), 1 if optimiser == "momentum" else 0, int(nIterations), float(learning_rate), float(epsilon), float(gamma))
+        rep = _lib.FitReport()
+        log = (C.c_ubyte * max(1, int(nIterations)))()
+        t = C.c_void_p(targets.data_ptr()) if targets is not None else None
+        self.ctx.check(self.lib.gf_smp_fit(self.handle, C.c_void_p(params.data_ptr()), C.c_void_p(grads.data_ptr()), t, C.byref(cfg),
+                                           C.byref(rep), log))
+        report = {name: getattr(rep, name) for name, _ in _lib.FitReport._fields_}
+        return report, list(log[:rep.iterations])
+
+    def parameters_snapshot(self, params):
+        """The classes' cache_parameters(): the values of params into the handle's cache (optimiser state is not part of it)."""
+        self._flat(params, "params")
+        self.ctx.check(self.lib.gf_smp_parameters_snapshot(self.handle, C.c_void_p(params.data_ptr())))
+
+    def parameters_rollback(self, params):
+        """The classes' restore_parameters(): the cached values back into params."""
+        self._flat(params, "params")
+        self.ctx.check(self.lib.gf_smp_parameters_rollback(self.handle, C.c_void_p(params.data_ptr())))
+        return params
+
     def uniform_init(self):
         """Initial weights exactly as SMP_omega's constructor draws them from rand() (host numpy array; call srand first)."""
         out = np.zeros(self.n_params, dtype=np.float32)
@@ -872,6 +902,20 @@ class SMPModel:
                                                  int(nBatch), n))
         self._adam[2] = n + self.n_params
         return params
+
+    def fit(self, params, grads, targets, nIterations, learning_rate, epsilon=0.0, kind=0):
+        """The classes' iterative training calls (gf_smp_model_fit; see SMPOmega.fit) with Adam, whose moments live in the HANDLE here --
+        not those of adam_step().  Returns (report, decisions)."""
+        for t, name in ((params, "params"), (grads, "grads")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == self.n_params):
+                raise TypeError("%s must be a contiguous float32 CUDA tensor of %d elements" % (name, self.n_params))
+        cfg = _lib.FitConfig(int(kind), 0, int(nIterations), float(learning_rate), float(epsilon), 0.0)
+        rep = _lib.FitReport()
+        log = (C.c_ubyte * max(1, int(nIterations)))()
+        self.ctx.check(self.lib.gf_smp_model_fit(self.handle, C.c_void_p(params.data_ptr()), C.c_void_p(grads.data_ptr()),
+                                                 C.c_void_p(targets.data_ptr()), C.byref(cfg), C.byref(rep), log))
+        report = {name: getattr(rep, name) for name, _ in _lib.FitReport._fields_}
+        return report, list(log[:rep.iterations])
 
     def save_model(self, params, path):
         """The classes' save_model: every parameter value in registration order as text, which their load_model reads.  Nine significant

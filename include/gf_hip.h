@@ -898,6 +898,54 @@ gf_status gf_smp_adam_reset(gf_smp *smp);   /* zeroes the moment buffers (Adam a
 /* Momentum::Learn(learning_rate, nBatch) (GraphFlow/Momentum.h:64-71), the optimiser of SMP_2D_ver6-8
  * (SMP_2D_ver6.h:204, :593): m = gamma m + learning_rate * grads / nBatch, params -= m. */
 gf_status gf_smp_momentum_step(gf_smp *smp, float *params, const float *grads, double learning_rate, int nBatch, double gamma);
+/* The classes' CacheParameters (GraphFlow/CacheParameters.h:45-59): a device-to-device copy of the flat parameter buffer into
+ * (snapshot) or out of (rollback) a cache the handle owns, allocated by the first snapshot.  params NULL: the handle-owned model.
+ * Values only -- Momentum's velocity, Adam's moments and its element counter stay as they are, as in the classes.  Rollback before any
+ * snapshot of the handle is GF_ERR_INVALID.  Asynchronous on the context's stream. */
+gf_status gf_smp_parameters_snapshot(gf_smp *smp, const float *params);
+gf_status gf_smp_parameters_rollback(gf_smp *smp, float *params);
+/* gf_smp_forward_host for EVERY handle kind but a physics tower: the arrays are per sample -- a pair for readout = 1, a molecule
+ * otherwise -- and a feature row is gf_smp_feature_width wide (2 nChanels for the pair and distance handles, max_nVertices for the
+ * covariant ones).  A Gram handle (readout = 2) takes NULL targets, predict and graph_feature and returns the per-molecule loss.
+ * gf_smp_forward_host itself keeps its refusals.  Blocking. */
+gf_status gf_smp_forward_host_samples(gf_smp *smp, const double *targets, double *predict, double *loss, double *graph_feature);
+/* gf_smp_gram to a HOST array of doubles (the molecules back to back, V_m^2 values each).  Blocking. */
+gf_status gf_smp_gram_host(gf_smp *smp, double *out);
+/* The iterative training calls every model class of the reference has, on the prepared batch:
+ *   kind 0  BatchLearn(nBatch, molecule, target, nIterations, learning_rate, epsilon)      (GraphFlow/SMP_omega.h:827-874, GCN_1D.h:347-392)
+ *           cache; first = second = loss; per iteration: reverse sweep, Learn(lr, nBatch), loss; loss > second: restore, lr *= 0.5,
+ *           leave when lr < 1e-6; else second = loss, cache.  epsilon is not read.
+ *   kind 1  Learn(molecule, target, nIterations, learning_rate, epsilon)                   (SMP_omega.h:876-922, GCN_1D.h:394-438)
+ *           a batch of ONE sample (else GF_ERR_INVALID); first loss < epsilon: return (loss, loss) at once; per iteration: reverse sweep,
+ *           Learn(lr) -- for Adam the overload that advances the bias-correction powers once per CALL (Adam.h:77-105), not per element --,
+ *           error; error < epsilon: leave (the step stays); error >= best: restore, lr = max(0.5 lr, 1e-6); else best = error, cache.
+ * "loss" is the sum of the per-sample losses of a forward, added in double in ascending sample order on the device and read back (8
+ * bytes, one blocking copy per iteration); a classifier's is its LogLoss value (at most 0) under the same comparisons, as in the
+ * reference.  lr and every comparison live on the host in double (graphflow_amd/csrc/smp_fit_policy.h).  The passes are gf_smp_forward
+ * / gf_smp_backward / gf_smp_adam_step / gf_smp_momentum_step, in the order a caller would issue them; after a restore the loop runs a
+ * forward before the next reverse sweep (and before it returns), so the handle is left forwarded at the parameters it is left with. */
+typedef struct {
+    int kind;        /* 0: the BatchLearn overload, 1: Learn */
+    int optimiser;   /* 0: Adam, 1: Momentum with `gamma` */
+    int nIterations;
+    double learning_rate, epsilon, gamma;
+} gf_smp_fit_config;
+typedef struct {
+    double first, second;   /* the pair the class returns */
+    int iterations, accepted, rejected;   /* iterations run; steps kept; steps restored */
+    int left_early;         /* a break (kind 0: lr < 1e-6, kind 1: error < epsilon) or kind 1's immediate return */
+    double learning_rate;   /* the rate the loop ended with */
+} gf_smp_fit_report;
+/* params / grads: device pointers, or both NULL for the handle-owned model; targets: device, one per sample (NULL on a Gram handle);
+ * decisions (optional, host, nIterations bytes): per iteration run 1 = kept, 2 = restored, 3 = restored and left (kind 0),
+ * 4 = left on error < epsilon (kind 1).  gf_smp_fit_host: the handle-owned model with host targets.  Blocking. */
+gf_status gf_smp_fit(gf_smp *smp, float *params, float *grads, const float *targets, const gf_smp_fit_config *cfg,
+                     gf_smp_fit_report *report, unsigned char *decisions);
+gf_status gf_smp_fit_host(gf_smp *smp, const double *targets, const gf_smp_fit_config *cfg, gf_smp_fit_report *report,
+                          unsigned char *decisions);
+/* The loop's loss sum as a stand-alone operator, for tests/test_fit_gpu.py: *sum (host) = the n device floats of `loss` added as doubles
+ * in ascending order -- the bits of a host loop `total += loss[i]` -- by the loop's own kernel.  1 <= n < 2^31.  Blocking. */
+gf_status gf_smp_loss_sum_f32(gf_ctx *ctx, const float *loss, size_t n, double *sum);
 /* SMP_omega::weights_initialization (SMP_omega.h:334-338; GraphFlow.h:1297-1306) into a HOST buffer of
  * gf_smp_param_count floats, drawing from rand() in the reference's order: same srand() -> same initial weights. */
 gf_status gf_smp_uniform_init_host(const gf_smp_config *cfg, float *params);
@@ -1000,6 +1048,15 @@ gf_status gf_smp_model_parameters_upload(gf_smp_model *model, const float *host_
 gf_status gf_smp_model_parameters_download(gf_smp_model *model, float *host_params, float *host_grads);
 gf_status gf_smp_model_forward_host(gf_smp_model *model, const double *targets, double *predict, double *loss);
 gf_status gf_smp_model_adam_step(gf_smp_model *model, double learning_rate, int nBatch);
+/* gf_smp_parameters_snapshot / _rollback and gf_smp_fit / gf_smp_fit_host for the composite handle, over the whole registration-order
+ * vector.  The composite classes train with Adam: optimiser = 1 is GF_ERR_UNSUPPORTED.  With device pointers the Adam moments are the
+ * handle's (those of gf_smp_model_adam_step). */
+gf_status gf_smp_model_parameters_snapshot(gf_smp_model *model, const float *params);
+gf_status gf_smp_model_parameters_rollback(gf_smp_model *model, float *params);
+gf_status gf_smp_model_fit(gf_smp_model *model, float *params, float *grads, const float *targets, const gf_smp_fit_config *cfg,
+                           gf_smp_fit_report *report, unsigned char *decisions);
+gf_status gf_smp_model_fit_host(gf_smp_model *model, const double *targets, const gf_smp_fit_config *cfg, gf_smp_fit_report *report,
+                                unsigned char *decisions);
 
 #ifdef __cplusplus
 }
