@@ -239,6 +239,40 @@ PROTOTYPES.update({
     "gf_smp_model_fit_host": (_i, [_vp, _dp, _fitc, _fitr, _u8p]),
 })
 
+
+
+class OptimConfig(C.Structure):
+    """gf_optim_config"""
+    _fields_ = [("kind", _i), ("nBatch", _i), ("learning_rate", C.c_double), ("gamma", C.c_double), ("beta1", C.c_double),
+                ("beta2", C.c_double), ("rho", C.c_double), ("epsilon", C.c_double)]
+
+
+OPTIMISERS = {"adam": 0, "momentum": 1, "sgd": 2, "adamax": 3, "adadelta": 4}   # gf_optim_config.kind = gf_smp_fit_config.optimiser
+_optc, _szp = C.POINTER(OptimConfig), C.POINTER(C.c_size_t)
+PROTOTYPES.update({
+    "gf_smp_config_param_blocks": (C.c_size_t, [_cfgp, _szp, C.c_size_t]),
+    "gf_smp_classifier_config_param_blocks": (C.c_size_t, [_cfgp, _i, _szp, C.c_size_t]),
+    "gf_smp_model_config_param_blocks": (C.c_size_t, [_vp, _szp, C.c_size_t]),
+    "gf_smp_optimiser_step": (_i, [_vp, _vp, _vp, _optc]),
+    "gf_smp_model_optimiser_step": (_i, [_vp, _vp, _vp, _optc]),
+    "gf_smp_regularise": (_i, [_vp, _vp, _vp, _i, C.c_double, _i, _dp]),
+    "gf_smp_model_regularise": (_i, [_vp, _vp, _vp, _i, C.c_double, _i, _dp]),
+    "gf_optimiser_step_f32": (_i, [_vp, _optc, _vp, _vp, C.c_size_t, _szp, _i, _vp, _vp, _vp, _dp]),
+    "gf_regularise_f32": (_i, [_vp, _vp, _vp, C.c_size_t, _i, C.c_double, _i, _dp]),
+})
+
+
+def param_blocks(call, *args):
+    """the offsets [count + 1] of one of the three *_config_param_blocks calls (the count first, then the table), or [] for a refusal"""
+    lib = load()
+    count = getattr(lib, call)(*args, None, 0)
+    if not count:
+        return []
+    offsets = (C.c_size_t * (count + 1))()
+    assert getattr(lib, call)(*args, offsets, count + 1) == count
+    return list(offsets)
+
+
 _lib = None
 
 

@@ -711,6 +711,7 @@ gf_status gf_smp_destroy(gf_smp *s) {
     for (float *p : {s->rs_inv, s->adam_m, s->adam_v, s->own_p, s->own_g, s->pad_p, s->pad_g, s->pad_feat, s->fit_cache})
         if (p) (void)hipFree(p);
     if (s->fit_sum) (void)hipFree(s->fit_sum);
+    gf::optim_free(&s->optim);
     delete s;
     return GF_OK;
 }

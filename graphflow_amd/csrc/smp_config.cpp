@@ -354,3 +354,136 @@ gf_status resolve_config(const gf_smp_config *cfg, const ConfigEntry &entry, Con
 #undef GF_REFUSE
 
 }  // namespace gfsmp
+
+namespace gf {
+
+bool model_plan(const gf_smp_model_config *cfg, ModelPlan *p, char *why, size_t nwhy) {
+    if (cfg->nTowers < 1 || cfg->nTowers > 2 || cfg->nLevels < 1 || cfg->nChanels < 1 || cfg->max_receptive_field < 1 || cfg->nKept < 0 ||
+        cfg->nKept > 18 || cfg->nFeatures[0] < 1 || (cfg->nTowers == 2 && cfg->nFeatures[1] < 1)) {   // (nFeatures: what gf_smp_create refuses of a tower)
+        snprintf(why, nwhy, "gf_smp_model_create: bad configuration");
+        return false;
+    }
+    const int nK = cfg->nContractions ? cfg->nContractions : 18;
+    if (nK != 18 && nK != 4) {
+        snprintf(why, nwhy, "gf_smp_model_create: nContractions = %d (expected 0 or 18: RisiContraction_18, 4: RisiContraction_4)", cfg->nContractions);
+        return false;
+    }
+    if (nK == 4 && cfg->nKept > 0) {
+        snprintf(why, nwhy, "gf_smp_model_create: nKept > 0 (RisiContraction_18_dropout) with nContractions = 4: no such model");
+        return false;
+    }
+    const int maxV[2] = {cfg->max_nVertices[0], cfg->max_nVertices[1] ? cfg->max_nVertices[1] : cfg->max_nVertices[0]};
+    if (cfg->first_order && (cfg->nContractions || cfg->nKept > 0 || maxV[0] < cfg->max_receptive_field || maxV[1] < cfg->max_receptive_field)) {
+        snprintf(why, nwhy, "gf_smp_model_create: first_order = 1 (SMP_theta_physics / _pairgraphs) needs nContractions = nKept = 0 and "
+                            "max_nVertices (%d, %d) >= max_receptive_field (%d)", maxV[0], maxV[1], cfg->max_receptive_field);
+        return false;
+    }
+    // CCN_1D (GraphFlow/CCN_1D.h:34-39): always two first-order towers, at least 16 channels, 0 < decay <= 1 (!(..): a NaN is refused too)
+    if (cfg->ccn_1d && (cfg->nTowers != 2 || cfg->first_order != 1 || cfg->nChanels < gfsmp::kCcnMinChanels ||
+                        !(cfg->nChanels_decay > 0.0 && cfg->nChanels_decay <= 1.0))) {
+        snprintf(why, nwhy, "gf_smp_model_create: ccn_1d = 1 (CCN_1D) needs nTowers = 2 (%d), first_order = 1 (%d), nChanels >= 16 (%d) and "
+                            "0 < nChanels_decay <= 1 (%g)", cfg->nTowers, cfg->first_order, cfg->nChanels, cfg->nChanels_decay);
+        return false;
+    }
+    p->nK = nK;
+    p->nTowers = cfg->nTowers;
+    p->maxV[0] = maxV[0];
+    p->maxV[1] = maxV[1];
+    p->decay = cfg->ccn_1d ? cfg->nChanels_decay : 0.0;
+    // the towers: what gf_smp_create is asked for, and what it will make of it (the width rule -- halving, or the decay -- and the blocks)
+    gfsmp::Config *tower = p->tower;
+    for (int t = 0; t < cfg->nTowers; ++t) {
+        gf_smp_config &tc = p->tower_cfg[t];
+        tc = gf_smp_config();   // (every field zero)
+        tc.nLevels = cfg->nLevels, tc.nChanels = cfg->nChanels, tc.nFeatures = cfg->nFeatures[t], tc.max_receptive_field = cfg->max_receptive_field;
+        tc.nContractions = cfg->first_order ? 0 : nK, tc.physics = 1;
+        tc.first_order = cfg->first_order ? 1 : 0, tc.max_nVertices = cfg->first_order ? maxV[t] : 0;
+        if (gfsmp::resolve_config(&p->tower_cfg[t], {gfsmp::ConfigEntry::Tower, 0, p->decay}, &tower[t], why, nwhy) != GF_OK) return false;
+    }
+    const int L = cfg->nLevels;
+    for (int l = 0; l <= L; ++l) {
+        p->lvlC.push_back(tower[0].level_channels(l));
+        p->fwidth += p->lvlC.back();
+    }
+    size_t off = 0;
+    // the H matrices come first (one per tower), then the levels, towers interleaved inside a level
+    size_t toff[2] = {0, 0};
+    for (int t = 0; t < cfg->nTowers; ++t) {
+        const size_t nH = tower[t].first_block().n;
+        p->segs[t].push_back({off, 0, nH});
+        off += nH;
+        toff[t] = nH;
+    }
+    for (int l = 1; l <= L; ++l)
+        for (int t = 0; t < cfg->nTowers; ++t) {
+            const size_t n = tower[t].level_blocks(l).total();   // (one contiguous segment in either layout)
+            p->segs[t].push_back({off, toff[t], n});
+            off += n;
+            toff[t] += n;
+        }
+    p->head_off = off;
+    // head widths: physics nTotal -> nTotal / 2 -> 1 (:229-238); pairgraphs nTotal -> max(nTotal / 2, 10) -> max(that / 2, 10) -> 1;
+    // CCN_1D nTotal -> max(int(ceil(nTotal * decay)), 16) -> max(int(ceil(that * decay)), 16) -> 1 (CCN_1D.h:352-353)
+    const int nTotal = cfg->nTowers * p->fwidth;
+    p->widths.push_back(nTotal);
+    if (p->decay > 0.0) {
+        for (int i = 0; i < 2; ++i) {
+            const int h = int(std::ceil(p->widths.back() * p->decay));
+            p->widths.push_back(h > gfsmp::kCcnMinChanels ? h : gfsmp::kCcnMinChanels);
+        }
+    } else if (cfg->nTowers == 1) {
+        p->widths.push_back(nTotal / 2);
+    } else {
+        const int h1 = nTotal / 2 > 10 ? nTotal / 2 : 10, h2 = h1 / 2 > 10 ? h1 / 2 : 10;
+        p->widths.push_back(h1);
+        p->widths.push_back(h2);
+    }
+    if (p->widths[1] < 1) {
+        snprintf(why, nwhy, "gf_smp_model_create: %d feature columns leave no hidden units (the reference uses nTotal / 2)", nTotal);
+        return false;
+    }
+    each_head_block(p->widths, [p](size_t n) { p->head_params += n; });   // (= gf_head_param_count)
+    p->n_params = off + p->head_params;
+    return true;
+}
+
+namespace {
+// The count / capacity protocol of the three *_config_param_blocks calls: each(f) calls f(n) for every block in order.  Two walks and no
+// allocation: a caller's configuration may have any number of blocks.
+template <class Each>
+size_t write_offsets(Each each, size_t *offsets, size_t capacity) {
+    size_t count = 0;
+    each([&count](size_t) { ++count; });
+    if (offsets && count && capacity > count) {
+        size_t at = 0, i = 0;
+        each([&](size_t n) {
+            offsets[i++] = at;
+            at += n;
+        });
+        offsets[count] = at;
+    }
+    return count;
+}
+size_t config_param_blocks(const gf_smp_config *cfg, const gfsmp::ConfigEntry &entry, size_t *offsets, size_t capacity) {
+    gfsmp::Config c;
+    char why[640];
+    if (gfsmp::resolve_config(cfg, entry, &c, why, sizeof why) != GF_OK) return 0;
+    return write_offsets([&c](auto f) { c.each_registered(f); }, offsets, capacity);
+}
+}  // namespace
+}  // namespace gf
+
+extern "C" {
+size_t gf_smp_config_param_blocks(const gf_smp_config *cfg, size_t *offsets, size_t capacity) {
+    return gf::config_param_blocks(cfg, gfsmp::kHandleEntry, offsets, capacity);
+}
+size_t gf_smp_classifier_config_param_blocks(const gf_smp_config *cfg, int nClass, size_t *offsets, size_t capacity) {
+    return gf::config_param_blocks(cfg, {gfsmp::ConfigEntry::Classifier, nClass, 0.0}, offsets, capacity);
+}
+size_t gf_smp_model_config_param_blocks(const gf_smp_model_config *cfg, size_t *offsets, size_t capacity) {
+    gf::ModelPlan plan;
+    char why[512];
+    if (!cfg || !gf::model_plan(cfg, &plan, why, sizeof why)) return 0;
+    return gf::write_offsets([&plan](auto f) { gf::each_registered(plan, f); }, offsets, capacity);
+}
+}  // extern "C"

@@ -66,4 +66,37 @@ constexpr ConfigEntry kHandleEntry = {ConfigEntry::Handle, 0, 0.0};
 // in why, the message gf_last_error gives.  Touches no device and allocates nothing.
 gf_status resolve_config(const gf_smp_config *cfg, const ConfigEntry &entry, Config *out, char *why, size_t nwhy);
 }  // namespace gfsmp
+
+namespace gf {
+struct ModelSeg { size_t model_off, tower_off, n; };   // a tower's contiguous run inside the model's parameter vector
+// What gf_smp_model_create derives from a configuration before it touches the device: level widths, head widths, the segments of the
+// towers inside the model vector.  false (and a message): a configuration it refuses.
+struct ModelPlan {
+    int nK = 18, maxV[2] = {0, 0}, fwidth = 0, nTowers = 0;
+    double decay = 0.0;                       // > 0: CCN_1D's width rule (gfsmp::Config::decay)
+    std::vector<int> lvlC, widths;
+    std::vector<ModelSeg> segs[2];
+    gf_smp_config tower_cfg[2];                // what gf_smp_create is asked for, tower by tower
+    gfsmp::Config tower[2];                    // ... and what it makes of it
+    size_t head_off = 0, head_params = 0, n_params = 0;
+};
+bool model_plan(const gf_smp_model_config *cfg, ModelPlan *p, char *why, size_t nwhy);
+// f(n) for every block of the head in registration order: one [widths[i]][widths[i - 1]] matrix per layer, then the vector of the last width
+template <class F>
+void each_head_block(const std::vector<int> &widths, F f) {
+    const int nLayers = (int)widths.size() - 1;
+    for (int i = 1; i <= nLayers; ++i) f((size_t)widths[i] * (size_t)widths[i - 1]);
+    f((size_t)widths[nLayers]);
+}
+// f(n) for every block a composite class registers with sgd->add: H of every tower; per level, tower by tower, the level's blocks; the head
+// (SMP_omega_pairgraphs.h:361-375, CCN_1D.h:381-403)
+template <class F>
+void each_registered(const ModelPlan &p, F f) {
+    const auto size = [&f](const gfsmp::Config::Block &b) { f(b.n); };
+    for (int t = 0; t < p.nTowers; ++t) p.tower[t].each_registered_first(f);
+    for (int l = 1; l <= p.tower[0].nLevels; ++l)
+        for (int t = 0; t < p.nTowers; ++t) p.tower[t].level_blocks(l).each_draw(size);
+    each_head_block(p.widths, f);
+}
+}  // namespace gf
 #endif

@@ -122,9 +122,9 @@ gf_status fit_adam_step_per_call(gf_ctx *ctx, float *params, const float *grads,
 
 gf_status fit_check_config(gf_ctx *ctx, const gf_smp_fit_config *cfg, gf_smp_fit_report *report, int nSamples, const char *who) {
     if (!cfg || !report) return fail(ctx, GF_ERR_INVALID, "%s: null configuration or report", who);
-    if (cfg->kind < 0 || cfg->kind > 1 || cfg->optimiser < 0 || cfg->optimiser > 1 || cfg->nIterations < 0)
-        return fail(ctx, GF_ERR_INVALID, "%s: kind %d (0: BatchLearn, 1: Learn), optimiser %d (0: Adam, 1: Momentum), nIterations %d", who, cfg->kind,
-                    cfg->optimiser, cfg->nIterations);
+    if (cfg->kind < 0 || cfg->kind > 1 || cfg->optimiser < kOptimAdam || cfg->optimiser > kOptimAdaDelta || cfg->nIterations < 0)
+        return fail(ctx, GF_ERR_INVALID, "%s: kind %d (0: BatchLearn, 1: Learn), optimiser %d (0: Adam, 1: Momentum, 2: SGD, 3: AdaMax, 4: AdaDelta), nIterations %d",
+                    who, cfg->kind, cfg->optimiser, cfg->nIterations);
     if (nSamples < 1) return fail(ctx, GF_ERR_INVALID, "%s: no prepared batch", who);
     if (cfg->kind == gf_fit::kLearn && nSamples != 1)
         return fail(ctx, GF_ERR_INVALID, "%s: kind 1 (Learn) trains on one sample, the prepared batch holds %d", who, nSamples);
@@ -267,6 +267,11 @@ gf_status gf_smp_fit(gf_smp *s, float *params, float *grads, const float *target
     const gf_smp_fit_config c = *cfg;
     d.step = [=](double lr, int nBatch, bool per_call) {
         if (c.optimiser == 1) return gf_smp_momentum_step(s, params, grads, lr, nBatch, c.gamma);   // (Learn(lr) is Learn(lr, 1) there)
+        if (c.optimiser >= gf::kOptimSGD) {   // SGD, AdaMax, AdaDelta at the classes' default constants; Learn(lr) is Learn(lr, 1) there too
+            const gf_optim_config oc = {c.optimiser, nBatch, lr, 0.0, 0.0, 0.0, 0.0, 0.0};
+            return gf_smp_optimiser_step(s, params, grads, &oc);
+        }
+        s->optim.kind = gf::kOptimAdam;
         if (per_call) return gf::fit_adam_step_per_call(ctx, params, grads, s->adam_m, s->adam_v, n_params, lr, &s->adam_n);
         return gf_smp_adam_step(s, params, grads, lr, nBatch);
     };

@@ -11,6 +11,7 @@
 
 #include "gf_internal.h"
 #include "smp_config.h"
+#include "smp_optimisers.h"
 #include "smp_prep.h"
 
 namespace gf {
@@ -399,6 +400,8 @@ struct gf_smp : gf_smp_batch {
     // handle-owned model (host-pointer mode of the driver): parameters and their gradient, [param_count] each
     float *own_p = nullptr, *own_g = nullptr;
     unsigned long long adam_n = 0;  // parameter elements processed so far (the reference's running beta powers)
+    // the kind of the last optimiser step, and what SGD / AdaMax / AdaDelta keep beside adam_m / adam_v (smp_optimisers.h)
+    gf::OptimState optim;
     // smp_fit.hip: the parameter cache of gf_smp_parameters_snapshot / _rollback [param_count] and the 8 bytes of the loop's loss sum;
     // taken on first use, freed by gf_smp_destroy
     float *fit_cache = nullptr;

@@ -21,9 +21,6 @@
 #include "smp_fit.h"
 #include "smp_internal.h"
 
-namespace gf {
-struct ModelSeg { size_t model_off, tower_off, n; };   // a tower's contiguous run inside the model's parameter vector
-}
 struct gf_smp_model {
     gf_ctx *ctx = nullptr;
     gf_smp_model_config cfg;
@@ -58,6 +55,9 @@ struct gf_smp_model {
     // the parameter cache of gf_smp_model_parameters_snapshot / _rollback and the 8 bytes of gf_smp_model_fit's loss sum (smp_fit.h)
     float *fit_cache = nullptr;
     double *fit_sum = nullptr;
+    // the kind of the last optimiser step and the state of SGD / AdaMax / AdaDelta (smp_optimisers.h); the blocks the class registers
+    gf::OptimState optim;
+    std::vector<size_t> block_sizes;
 };
 
 namespace gf {
@@ -107,102 +107,7 @@ void free_batch(gf_smp_model *m) {
     m->cap_mol = 0;
 }
 
-// What gf_smp_model_create derives from a configuration before it touches the device: level widths, head widths, the segments of the
-// towers inside the model vector.  false (and a message): a configuration it refuses.
-struct ModelPlan {
-    int nK = 18, maxV[2] = {0, 0}, fwidth = 0;
-    double decay = 0.0;                       // > 0: CCN_1D's width rule (gfsmp::Config::decay)
-    std::vector<int> lvlC, widths;
-    std::vector<ModelSeg> segs[2];
-    gf_smp_config tower_cfg[2];                // what gf_smp_create is asked for, tower by tower
-    size_t head_off = 0, head_params = 0, n_params = 0;
-};
-
-bool model_plan(const gf_smp_model_config *cfg, ModelPlan *p, char *why, size_t nwhy) {
-    if (cfg->nTowers < 1 || cfg->nTowers > 2 || cfg->nLevels < 1 || cfg->nChanels < 1 || cfg->max_receptive_field < 1 || cfg->nKept < 0 ||
-        cfg->nKept > 18 || cfg->nFeatures[0] < 1 || (cfg->nTowers == 2 && cfg->nFeatures[1] < 1)) {   // (nFeatures: what gf_smp_create refuses of a tower)
-        snprintf(why, nwhy, "gf_smp_model_create: bad configuration");
-        return false;
-    }
-    const int nK = cfg->nContractions ? cfg->nContractions : 18;
-    if (nK != 18 && nK != 4) {
-        snprintf(why, nwhy, "gf_smp_model_create: nContractions = %d (expected 0 or 18: RisiContraction_18, 4: RisiContraction_4)", cfg->nContractions);
-        return false;
-    }
-    if (nK == 4 && cfg->nKept > 0) {
-        snprintf(why, nwhy, "gf_smp_model_create: nKept > 0 (RisiContraction_18_dropout) with nContractions = 4: no such model");
-        return false;
-    }
-    const int maxV[2] = {cfg->max_nVertices[0], cfg->max_nVertices[1] ? cfg->max_nVertices[1] : cfg->max_nVertices[0]};
-    if (cfg->first_order && (cfg->nContractions || cfg->nKept > 0 || maxV[0] < cfg->max_receptive_field || maxV[1] < cfg->max_receptive_field)) {
-        snprintf(why, nwhy, "gf_smp_model_create: first_order = 1 (SMP_theta_physics / _pairgraphs) needs nContractions = nKept = 0 and "
-                            "max_nVertices (%d, %d) >= max_receptive_field (%d)", maxV[0], maxV[1], cfg->max_receptive_field);
-        return false;
-    }
-    // CCN_1D (GraphFlow/CCN_1D.h:34-39): always two first-order towers, at least 16 channels, 0 < decay <= 1 (!(..): a NaN is refused too)
-    if (cfg->ccn_1d && (cfg->nTowers != 2 || cfg->first_order != 1 || cfg->nChanels < gfsmp::kCcnMinChanels ||
-                        !(cfg->nChanels_decay > 0.0 && cfg->nChanels_decay <= 1.0))) {
-        snprintf(why, nwhy, "gf_smp_model_create: ccn_1d = 1 (CCN_1D) needs nTowers = 2 (%d), first_order = 1 (%d), nChanels >= 16 (%d) and "
-                            "0 < nChanels_decay <= 1 (%g)", cfg->nTowers, cfg->first_order, cfg->nChanels, cfg->nChanels_decay);
-        return false;
-    }
-    p->nK = nK;
-    p->maxV[0] = maxV[0];
-    p->maxV[1] = maxV[1];
-    p->decay = cfg->ccn_1d ? cfg->nChanels_decay : 0.0;
-    // the towers: what gf_smp_create is asked for, and what it will make of it (the width rule -- halving, or the decay -- and the blocks)
-    gfsmp::Config tower[2];
-    for (int t = 0; t < cfg->nTowers; ++t) {
-        p->tower_cfg[t] = {cfg->nLevels, cfg->nChanels, cfg->nFeatures[t], 0, cfg->max_receptive_field, 0, cfg->first_order ? 0 : nK, 0, 1,
-                           cfg->first_order ? 1 : 0, cfg->first_order ? maxV[t] : 0};
-        if (gfsmp::resolve_config(&p->tower_cfg[t], {gfsmp::ConfigEntry::Tower, 0, p->decay}, &tower[t], why, nwhy) != GF_OK) return false;
-    }
-    const int L = cfg->nLevels;
-    for (int l = 0; l <= L; ++l) {
-        p->lvlC.push_back(tower[0].level_channels(l));
-        p->fwidth += p->lvlC.back();
-    }
-    size_t off = 0;
-    // the H matrices come first (one per tower), then the levels, towers interleaved inside a level
-    size_t toff[2] = {0, 0};
-    for (int t = 0; t < cfg->nTowers; ++t) {
-        const size_t nH = tower[t].first_block().n;
-        p->segs[t].push_back({off, 0, nH});
-        off += nH;
-        toff[t] = nH;
-    }
-    for (int l = 1; l <= L; ++l)
-        for (int t = 0; t < cfg->nTowers; ++t) {
-            const size_t n = tower[t].level_blocks(l).total();   // (one contiguous segment in either layout)
-            p->segs[t].push_back({off, toff[t], n});
-            off += n;
-            toff[t] += n;
-        }
-    p->head_off = off;
-    // head widths: physics nTotal -> nTotal / 2 -> 1 (:229-238); pairgraphs nTotal -> max(nTotal / 2, 10) -> max(that / 2, 10) -> 1;
-    // CCN_1D nTotal -> max(int(ceil(nTotal * decay)), 16) -> max(int(ceil(that * decay)), 16) -> 1 (CCN_1D.h:352-353)
-    const int nTotal = cfg->nTowers * p->fwidth;
-    p->widths.push_back(nTotal);
-    if (p->decay > 0.0) {
-        for (int i = 0; i < 2; ++i) {
-            const int h = int(std::ceil(p->widths.back() * p->decay));
-            p->widths.push_back(h > gfsmp::kCcnMinChanels ? h : gfsmp::kCcnMinChanels);
-        }
-    } else if (cfg->nTowers == 1) {
-        p->widths.push_back(nTotal / 2);
-    } else {
-        const int h1 = nTotal / 2 > 10 ? nTotal / 2 : 10, h2 = h1 / 2 > 10 ? h1 / 2 : 10;
-        p->widths.push_back(h1);
-        p->widths.push_back(h2);
-    }
-    if (p->widths[1] < 1) {
-        snprintf(why, nwhy, "gf_smp_model_create: %d feature columns leave no hidden units (the reference uses nTotal / 2)", nTotal);
-        return false;
-    }
-    p->head_params = gf_head_param_count((int)p->widths.size() - 1, p->widths.data());
-    p->n_params = off + p->head_params;
-    return true;
-}
+// (what gf_smp_model_create derives from a configuration before it touches the device: gf::model_plan, smp_config.cpp -- host only)
 
 }  // namespace
 }  // namespace gf
@@ -233,6 +138,7 @@ gf_status gf_smp_model_create(gf_ctx *ctx, const gf_smp_model_config *cfg, gf_sm
     m->head_off = plan.head_off;
     m->head_params = plan.head_params;
     m->n_params = plan.n_params;
+    gf::each_registered(plan, [m](size_t n) { m->block_sizes.push_back(n); });
     for (int t = 0; t < m->nTowers; ++t) {
         m->segs[t] = plan.segs[t];
         // (nKept > 0, RisiContraction_18_dropout: towers of up to 32 channels run the fused levels with per-product slice factors since
@@ -283,6 +189,7 @@ gf_status gf_smp_model_destroy(gf_smp_model *m) {
     for (float *p : own)
         if (p) (void)hipFree(p);
     if (m->fit_sum) (void)hipFree(m->fit_sum);
+    gf::optim_free(&m->optim);
     delete m;
     return GF_OK;
 }
@@ -538,7 +445,56 @@ gf_status gf_smp_model_adam_step(gf_smp_model *m, double learning_rate, int nBat
     if (!m || !m->own_p) return fail(m ? m->ctx : nullptr, GF_ERR_INVALID, "gf_smp_model_adam_step: no handle-owned model");
     gf_status st = gf_adam_step_f32(m->ctx, m->own_p, m->own_g, m->adam_m, m->adam_v, m->n_params, learning_rate, nBatch, m->adam_n);
     if (st == GF_OK) m->adam_n += m->n_params;
+    if (st == GF_OK) m->optim.kind = gf::kOptimAdam;
     return st;
+}
+
+static gf_status model_moments(gf_smp_model *m) {   // the two fp32 state buffers, for callers that bring their own parameters
+    gf_ctx *ctx = m->ctx;
+    GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (m->adam_m) return GF_OK;
+    float **bufs[] = {&m->adam_m, &m->adam_v};
+    for (float **b : bufs) {
+        GF_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(b), m->n_params * sizeof(float)));
+        GF_HIP_TRY(ctx, hipMemsetAsync(*b, 0, m->n_params * sizeof(float), ctx->stream));
+    }
+    m->adam_n = 0;
+    return GF_OK;
+}
+
+// gf_smp_optimiser_step on the composite handle's flat vector: kind 0 is gf_smp_model_adam_step's launch, kind 1 Momentum's kernel, 2 .. 4
+// smp_optimisers.hip's over the blocks the class registers.  The composite handle has no reset: it keeps the kind of its first step.
+gf_status gf_smp_model_optimiser_step(gf_smp_model *m, float *params, const float *grads, const gf_optim_config *cfg) {
+    if (!m) return fail(nullptr, GF_ERR_INVALID, "null model");
+    gf_ctx *ctx = m->ctx;
+    gf_status st = gf::optim_check(ctx, &m->optim, cfg, "gf_smp_model_optimiser_step");
+    if (st != GF_OK) return st;
+    if (!params && !grads && m->own_p) {
+        params = m->own_p;
+        grads = m->own_g;
+    }
+    if (!params || !grads) return fail(ctx, GF_ERR_INVALID, "gf_smp_model_optimiser_step: null params / grads and no handle-owned model");
+    st = model_moments(m);
+    if (st != GF_OK) return st;
+    if (cfg->kind == gf::kOptimAdam) {
+        st = gf_adam_step_f32(ctx, params, grads, m->adam_m, m->adam_v, m->n_params, cfg->learning_rate, cfg->nBatch, m->adam_n);
+        if (st == GF_OK) m->adam_n += m->n_params;
+    } else if (cfg->kind == gf::kOptimMomentum) {
+        st = gf::momentum_step_on(ctx, params, grads, m->adam_m, m->n_params, cfg->learning_rate, cfg->nBatch, cfg->gamma);
+    } else {
+        return gf::optim_step(ctx, &m->optim, m->block_sizes, params, grads, m->n_params, m->adam_m, m->adam_v, cfg, "gf_smp_model_optimiser_step");
+    }
+    if (st == GF_OK) m->optim.kind = cfg->kind;
+    return st;
+}
+
+gf_status gf_smp_model_regularise(gf_smp_model *m, const float *params, float *grads, int norm, double lambda, int times, double *value_host) {
+    if (!m) return fail(nullptr, GF_ERR_INVALID, "null model");
+    if (!params && !grads && m->own_p) {
+        params = m->own_p;
+        grads = m->own_g;
+    }
+    return gf_regularise_f32(m->ctx, params, grads, m->n_params, norm, lambda, times, value_host);
 }
 
 // ---- the classes' iterative training calls (smp_fit.h) on the composite handle ----------------------------------------------
@@ -556,7 +512,8 @@ gf_status gf_smp_model_parameters_rollback(gf_smp_model *m, float *params) {
     return gf::fit_rollback(m->ctx, &m->fit_cache, params, m->n_params, "gf_smp_model_parameters_rollback");
 }
 
-// Every composite class of the reference trains with Adam (SMP_omega_physics.h:264): optimiser = 1 is refused.
+// Every composite class of the reference trains with Adam (SMP_omega_physics.h:264): optimiser = 1 is refused; 2 .. 4 (SGD, AdaMax,
+// AdaDelta at the classes' default constants) step through gf_smp_model_optimiser_step.
 gf_status gf_smp_model_fit(gf_smp_model *m, float *params, float *grads, const float *targets, const gf_smp_fit_config *cfg,
                            gf_smp_fit_report *report, unsigned char *decisions) {
     if (!m) return fail(nullptr, GF_ERR_INVALID, "null model");
@@ -568,7 +525,7 @@ gf_status gf_smp_model_fit(gf_smp_model *m, float *params, float *grads, const f
     if (!params || !grads || !targets) return fail(ctx, GF_ERR_INVALID, "gf_smp_model_fit: null params / grads (and no handle-owned model) or null targets");
     gf_status st = gf::fit_check_config(ctx, cfg, report, m->nMol, "gf_smp_model_fit");
     if (st != GF_OK) return st;
-    if (cfg->optimiser != 0) return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_model_fit: the composite models train with Adam (optimiser = 0)");
+    if (cfg->optimiser == gf::kOptimMomentum) return fail(ctx, GF_ERR_UNSUPPORTED, "gf_smp_model_fit: the composite models train with Adam (optimiser = 0)");
     GF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!m->adam_m) {
         float **bufs[] = {&m->adam_m, &m->adam_v};
@@ -589,7 +546,13 @@ gf_status gf_smp_model_fit(gf_smp_model *m, float *params, float *grads, const f
     d.sum = &m->fit_sum;
     d.forward = [=]() { return gf_smp_model_forward(m, params, targets, nullptr, m->own_loss); };
     d.backward = [=]() { return gf_smp_model_backward(m, params, grads, 0); };
+    const int optimiser = cfg->optimiser;
     d.step = [=](double lr, int nBatch, bool per_call) {
+        if (optimiser >= gf::kOptimSGD) {
+            const gf_optim_config oc = {optimiser, nBatch, lr, 0.0, 0.0, 0.0, 0.0, 0.0};
+            return gf_smp_model_optimiser_step(m, params, grads, &oc);
+        }
+        m->optim.kind = gf::kOptimAdam;
         if (per_call) return gf::fit_adam_step_per_call(ctx, params, grads, m->adam_m, m->adam_v, m->n_params, lr, &m->adam_n);
         const gf_status s2 = gf_adam_step_f32(ctx, params, grads, m->adam_m, m->adam_v, m->n_params, lr, nBatch, m->adam_n);
         if (s2 == GF_OK) m->adam_n += m->n_params;

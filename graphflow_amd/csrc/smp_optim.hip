@@ -65,6 +65,11 @@ gf_status optimiser_begin(gf_smp *s, float **params, const float **grads, int nB
 }
 }  // namespace
 
+gf_status momentum_step_on(gf_ctx *ctx, float *params, const float *grads, float *m, size_t n, double learning_rate, int nBatch, double gamma) {
+    GF_LAUNCH(ctx, "smp_momentum", momentum_step, dim3(grid_for(n)), dim3(256), 0, params, grads, m, n, learning_rate, 1.0 / (double)nBatch, gamma);
+    return GF_OK;
+}
+
 // the handle-owned parameter / gradient buffers (host-pointer mode), created on first use
 gf_status own_model(gf_smp *s) {
     if (s->own_p) return GF_OK;
@@ -151,6 +156,7 @@ gf_status gf_smp_adam_step(gf_smp *s, float *params, const float *grads, double 
     GF_LAUNCH(ctx, "smp_adam", gf::adam_step, dim3(gf::grid_for(n)), dim3(256), 0, params, grads, s->adam_m, s->adam_v, n,
               learning_rate, 1.0 / (double)nBatch, s->adam_n, 0.9, 0.999, 1e-8);
     s->adam_n += n;   // (touches the moment buffers only, not the batch's: the handle's next gf_smp_prepare need not wait for it)
+    s->optim.kind = gf::kOptimAdam;
     return GF_OK;
 }
 
@@ -163,7 +169,34 @@ gf_status gf_smp_momentum_step(gf_smp *s, float *params, const float *grads, dou
     const size_t n = gf::param_count(s->ucfg);
     GF_LAUNCH(ctx, "smp_momentum", gf::momentum_step, dim3(gf::grid_for(n)), dim3(256), 0, params, grads, s->adam_m, n,
               learning_rate, 1.0 / (double)nBatch, gamma);
+    s->optim.kind = gf::kOptimMomentum;
     return GF_OK;
+}
+
+// sgd->Learn(learning_rate, nBatch) for whichever of the reference's five optimisers `sgd` is (gf_optim_config.kind).  Kinds 0 and 1 are
+// the two calls above, launch for launch; 2 .. 4 are smp_optimisers.hip's, over the handle's block table.  A kind other than the one the
+// handle last stepped with is refused until gf_smp_adam_reset: the state buffers are shared.
+gf_status gf_smp_optimiser_step(gf_smp *s, float *params, const float *grads, const gf_optim_config *cfg) {
+    if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
+    gf_status st = gf::optim_check(s->ctx, &s->optim, cfg, "gf_smp_optimiser_step");
+    if (st != GF_OK) return st;
+    if (cfg->kind == gf::kOptimAdam) return gf_smp_adam_step(s, params, grads, cfg->learning_rate, cfg->nBatch);
+    if (cfg->kind == gf::kOptimMomentum) return gf_smp_momentum_step(s, params, grads, cfg->learning_rate, cfg->nBatch, cfg->gamma);
+    st = gf::optimiser_begin(s, &params, &grads, cfg->nBatch, "gf_smp_optimiser_step");
+    if (st != GF_OK) return st;
+    std::vector<size_t> blocks;
+    if (cfg->kind == gf::kOptimAdaMax && !s->optim.blocks) s->ucfg.each_registered([&blocks](size_t n) { blocks.push_back(n); });
+    return gf::optim_step(s->ctx, &s->optim, blocks, params, grads, gf::param_count(s->ucfg), s->adam_m, s->adam_v, cfg, "gf_smp_optimiser_step");
+}
+
+// L1Regularization / L2Regularization over every registered parameter: the value to the host, grads += times * the term of backward()
+gf_status gf_smp_regularise(gf_smp *s, const float *params, float *grads, int norm, double lambda, int times, double *value_host) {
+    if (!s) return fail(nullptr, GF_ERR_INVALID, "null smp handle");
+    if (!params && !grads && s->own_p) {
+        params = s->own_p;
+        grads = s->own_g;
+    }
+    return gf_regularise_f32(s->ctx, params, grads, gf::param_count(s->ucfg), norm, lambda, times, value_host);
 }
 
 // Adam::Learn(learning_rate, nBatch) (GraphFlow/Adam.h:106-133) on any flat parameter buffer with caller-owned moments:
@@ -186,7 +219,7 @@ gf_status gf_smp_adam_reset(gf_smp *s) {
         GF_HIP_TRY(s->ctx, hipMemsetAsync(s->adam_v, 0, n * sizeof(float), s->ctx->stream));
     }
     s->adam_n = 0;
-    return GF_OK;
+    return gf::optim_reset(s->ctx, &s->optim);   // no recorded kind, AdaMax's beta1_t and norms
 }
 
 // SMP_omega::weights_initialization (SMP_omega.h:334-338) = GraphFlow::uniform_init (GraphFlow.h:1297-1306) over the

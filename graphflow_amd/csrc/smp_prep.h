@@ -248,6 +248,27 @@ struct Config {
         const size_t n = physics || covariant ? 0 : (size_t)readout_rows() * top_channels();   // (CGCN_*: SumComponents, no W)
         return {n, n};
     }
+    // f(n) for every block the class registers with sgd->add, in registration order: the draw blocks above, except that the distance
+    // classes register W1^v_0 and W1^d_0 one by one (GCN_1D_Distance.h:168-169; uniform_init draws them with one divisor) and that an
+    // empty read-out is not a block.  `levels` = false: H alone (a tower of a composite model interleaves its levels with its partner's).
+    template <class F>
+    void each_registered_first(F f) const {
+        const size_t n = (size_t)nChanels * fdim();
+        if (distance_channel) {
+            f(n);
+            f(first_block().n - n);
+        } else {
+            f(first_block().n);
+        }
+    }
+    template <class F>
+    void each_registered(F f) const {
+        const auto size = [&f](const Block &b) { f(b.n); };
+        each_registered_first(f);
+        shared_blocks().each_draw(size);
+        for (int l = 1; l <= nLevels; ++l) level_blocks(l).each_draw(size);
+        if (readout_block().n) f(readout_block().n);
+    }
     int top_channels() const { return covariant ? max_nVertices : readout == 2 ? 0 : distance_channel || readout == 1 ? 2 * nChanels : matrix_form == 1 ? nDense : first_order >= 2 || steerable_2d ? level_channels(nLevels) : nChanels;  }   // width of the graph feature and of W's rows
     int readout_rows() const { return nClass > 1 ? nClass : 1; }   // rows of W: [1][C] is the regression's [C]
     bool square() const { return !physics || uniform; }   // K_l is [nContractions C][C] at every level

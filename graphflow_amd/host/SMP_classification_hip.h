@@ -53,7 +53,12 @@ public:
         std::pair<double, double> ret;
         ret.first = getLoss(nBatch, molecule, target);  // leaves the batch bound and forwarded
         must(gf_smp_backward(net, NULL, NULL, 0), "gf_smp_backward");
-        must(gf_smp_momentum_step(net, NULL, NULL, learning_rate, nBatch, momentum), "gf_smp_momentum_step");
+        if (choice.chosen) {
+            const gf_optim_config oc = choice.step_config(learning_rate, nBatch);
+            must(gf_smp_optimiser_step(net, NULL, NULL, &oc), "gf_smp_optimiser_step");
+        } else {
+            must(gf_smp_momentum_step(net, NULL, NULL, learning_rate, nBatch, momentum), "gf_smp_momentum_step");
+        }
         ret.second = forward_loss(nBatch, target);
         return ret;
     }
@@ -88,6 +93,12 @@ public:
 
     void save_model(std::string filename) { must(gf_smp_save_model(net, NULL, filename.c_str()), "gf_smp_save_model"); }
     void load_model(std::string filename) { must(gf_smp_load_model(net, NULL, filename.c_str()), "gf_smp_load_model"); }
+    // sgd = new SGD / Momentum / Adam / AdaMax / AdaDelta(...) in place of the class's Momentum (gfhost::OptimiserChoice); starts from zero state
+    void use_optimiser(const gf_optim_config &config) {
+        choice.optim = config;
+        choice.chosen = true;
+        must(gf_smp_adam_reset(net), "gf_smp_adam_reset");
+    }
 
     // flat view of sgd->params[i]->value in registration order (H, K_1, b_1, ..., W)
     std::vector<float> parameters() {
@@ -128,12 +139,14 @@ private:
         must(gf_smp_prepare(net, nBatch, &nV[0], &adj[0], &feature[0]), "gf_smp_prepare");
     }
     std::pair<double, double> fit(int kind, const double *target, int nIterations, double learning_rate, double epsilon) {
-        return gfhost::fit_host(gf_smp_fit_host, "gf_smp_fit_host", net, target, kind, 1, nIterations, learning_rate, epsilon, momentum, this);
+        return gfhost::fit_host(gf_smp_fit_host, "gf_smp_fit_host", net, target, kind, choice.chosen ? choice.optim.kind : 1, nIterations, learning_rate,
+                                epsilon, choice.chosen ? choice.optim.gamma : momentum, this);
     }
     void must(gf_status st, const char *what) {
         if (st != GF_OK) gfhost::die(gfhost::default_context(), what, st);
     }
     double momentum;
+    gfhost::OptimiserChoice choice;
     gf_smp *net;
     std::vector<int> nV, adj;
     std::vector<double> feature;

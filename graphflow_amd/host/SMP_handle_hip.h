@@ -98,6 +98,12 @@ public:
         return g;
     }
     void set_parameters(const std::vector<float> &p) { must(gf_smp_parameters_upload(net, &p[0]), "gf_smp_parameters_upload"); }
+    // sgd = new SGD / Momentum / Adam / AdaMax / AdaDelta(...) in place of the class's own (gfhost::OptimiserChoice); starts from zero state
+    void use_optimiser(const gf_optim_config &config) {
+        choice.optim = config;
+        choice.chosen = true;
+        must(gf_smp_adam_reset(net), "gf_smp_adam_reset");
+    }
 
     int nClass, max_nVertices, nFeatures;   // (last_fit / last_decisions of the last iterative call: gfhost::FitLog)
     double momentum;
@@ -142,17 +148,21 @@ protected:
         std::pair<double, double> ret;
         ret.first = forward_loss(nBatch, target);
         must(gf_smp_backward(net, NULL, NULL, 0), "gf_smp_backward");
-        if (use_momentum)
+        if (choice.chosen) {
+            const gf_optim_config oc = choice.step_config(learning_rate, nBatch);
+            must(gf_smp_optimiser_step(net, NULL, NULL, &oc), "gf_smp_optimiser_step");
+        } else if (use_momentum) {
             must(gf_smp_momentum_step(net, NULL, NULL, learning_rate, nBatch, momentum), "gf_smp_momentum_step");
-        else
+        } else {
             must(gf_smp_adam_step(net, NULL, NULL, learning_rate, nBatch), "gf_smp_adam_step");
+        }
         ret.second = forward_loss(nBatch, target);
         return ret;
     }
     // the two iterative calls on the bound batch (kind 0: BatchLearn, 1: Learn)
     std::pair<double, double> fit(int kind, const double *target, int nIterations, double learning_rate, double epsilon) {
-        return gfhost::fit_host(gf_smp_fit_host, "gf_smp_fit_host", net, target, kind, use_momentum ? 1 : 0, nIterations, learning_rate, epsilon,
-                                momentum, this);
+        return gfhost::fit_host(gf_smp_fit_host, "gf_smp_fit_host", net, target, kind, choice.chosen ? choice.optim.kind : use_momentum ? 1 : 0,
+                                nIterations, learning_rate, epsilon, choice.chosen ? choice.optim.gamma : momentum, this);
     }
     double predict_one() {
         double y = 0.0;
@@ -173,6 +183,7 @@ protected:
     bool use_momentum;
     gf_smp *net;
     gfhost::FlatBatch x, y;
+    gfhost::OptimiserChoice choice;
 
 private:
     SMP_handle_hip(const SMP_handle_hip &);

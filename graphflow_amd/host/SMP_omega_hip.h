@@ -68,6 +68,7 @@ protected:
     }
 
 private:
+    gfhost::OptimiserChoice choice;
     int wiring_contractions = 0, wiring_custom = 0;
     double momentum = 0.0;
     bool use_momentum = false;
@@ -82,6 +83,12 @@ private:
 
 public:
     void init_multi_threads(int) {}
+    // sgd = new SGD / Momentum / Adam / AdaMax / AdaDelta(...) in place of the class's own (gfhost::OptimiserChoice); starts from zero state
+    void use_optimiser(const gf_optim_config &config) {
+        choice.optim = config;
+        choice.chosen = true;
+        must(gf_smp_adam_reset(net), "gf_smp_adam_reset");
+    }
 
     template <class Graph>
     double getLoss(int nBatch, Graph **molecule, double *target) {
@@ -204,14 +211,18 @@ private:
     }
     void step(double learning_rate, int nBatch) {
         must(gf_smp_backward(net, NULL, NULL, 0), "gf_smp_backward");
-        if (use_momentum)
+        if (choice.chosen) {
+            const gf_optim_config oc = choice.step_config(learning_rate, nBatch);
+            must(gf_smp_optimiser_step(net, NULL, NULL, &oc), "gf_smp_optimiser_step");
+        } else if (use_momentum) {
             must(gf_smp_momentum_step(net, NULL, NULL, learning_rate, nBatch, momentum), "gf_smp_momentum_step");
-        else
+        } else {
             must(gf_smp_adam_step(net, NULL, NULL, learning_rate, nBatch), "gf_smp_adam_step");
+        }
     }
     std::pair<double, double> fit(int kind, const double *target, int nIterations, double learning_rate, double epsilon) {
-        return gfhost::fit_host(gf_smp_fit_host, "gf_smp_fit_host", net, target, kind, use_momentum ? 1 : 0, nIterations, learning_rate, epsilon,
-                                momentum, this);
+        return gfhost::fit_host(gf_smp_fit_host, "gf_smp_fit_host", net, target, kind, choice.chosen ? choice.optim.kind : use_momentum ? 1 : 0,
+                                nIterations, learning_rate, epsilon, choice.chosen ? choice.optim.gamma : momentum, this);
     }
     void must(gf_status st, const char *what) {
         if (st != GF_OK) gfhost::die(gfhost::default_context(), what, st);

@@ -59,6 +59,12 @@ public:
     void setMode(bool train) { must(gf_smp_model_set_mode(net, train ? 1 : 0), "gf_smp_model_set_mode"); }
     void setTrainMode() { setMode(true); }
     void setTestMode() { setMode(false); }
+    // sgd = new SGD / Momentum / Adam / AdaMax / AdaDelta(...) in place of the class's Adam (gfhost::OptimiserChoice).  Before the first
+    // step: the composite handle keeps the kind of its first step (optimiser 1, Momentum, has no iterative call here).
+    void use_optimiser(const gf_optim_config &config) {
+        choice.optim = config;
+        choice.chosen = true;
+    }
 
     void save_model(std::string filename) {
         std::vector<float> p = parameters();
@@ -123,7 +129,12 @@ protected:
             ret.first = loss_of_batch(nBatch, target);  // getLoss (its forward draws dropout masks too, as the reference's does)
         must(gf_smp_model_forward_host(net, target, NULL, NULL), "gf_smp_model_forward_host");
         must(gf_smp_model_backward(net, NULL, NULL, 0), "gf_smp_model_backward");
-        must(gf_smp_model_adam_step(net, learning_rate, nBatch), "gf_smp_model_adam_step");
+        if (choice.chosen) {
+            const gf_optim_config oc = choice.step_config(learning_rate, nBatch);
+            must(gf_smp_model_optimiser_step(net, NULL, NULL, &oc), "gf_smp_model_optimiser_step");
+        } else {
+            must(gf_smp_model_adam_step(net, learning_rate, nBatch), "gf_smp_model_adam_step");
+        }
         if (with_losses) ret.second = loss_of_batch(nBatch, target);
         return ret;
     }
@@ -133,7 +144,8 @@ protected:
     // class evaluates the loss with one set of slice masks and draws fresh ones for the forward its reverse sweep starts from; here the
     // reverse sweep starts from the forward that evaluated the loss (one draw per iteration where the class has two).
     std::pair<double, double> fit(int kind, const double *target, int nIterations, double learning_rate, double epsilon) {
-        return gfhost::fit_host(gf_smp_model_fit_host, "gf_smp_model_fit_host", net, target, kind, 0, nIterations, learning_rate, epsilon, 0.0, this);
+        return gfhost::fit_host(gf_smp_model_fit_host, "gf_smp_model_fit_host", net, target, kind, choice.chosen ? choice.optim.kind : 0, nIterations,
+                                learning_rate, epsilon, 0.0, this);
     }
     void must(gf_status st, const char *what) {
         if (st != GF_OK) gfhost::die(gfhost::default_context(), what, st);
@@ -143,6 +155,7 @@ protected:
         std::abort();
     }
     gf_smp_model *net;
+    gfhost::OptimiserChoice choice;
     int towers, maxV[2], nF[2];
     std::vector<int> nV[2], adj[2];
     std::vector<double> feature[2];

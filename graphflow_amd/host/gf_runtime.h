@@ -122,6 +122,21 @@ struct FitLog {
     std::vector<unsigned char> last_decisions;
     FitLog() { std::memset(&last_fit, 0, sizeof last_fit); }
 };
+// use_optimiser of the drop-in classes: what a reference user does by changing the type of the class's `sgd` member (SGD, Momentum, Adam,
+// AdaMax, AdaDelta: gf_optim_config.kind and the constants of its constructor).  BatchLearn(nBatch, ..., learning_rate) then steps through
+// gf_smp_optimiser_step with these constants; the iterative calls pass the kind on (gf_smp_fit_config.optimiser: the classes' DEFAULT
+// constants for kinds 2 to 4, `gamma` for Momentum).  Not chosen: the class's own optimiser, as before.
+struct OptimiserChoice {
+    bool chosen;
+    gf_optim_config optim;
+    OptimiserChoice() : chosen(false) { std::memset(&optim, 0, sizeof optim); }
+    gf_optim_config step_config(double learning_rate, int nBatch) const {   // of one sgd->Learn(learning_rate, nBatch)
+        gf_optim_config c = optim;
+        c.learning_rate = learning_rate;
+        c.nBatch = nBatch;
+        return c;
+    }
+};
 // The two iterative calls of every model class on the batch its handle holds: `call` is gf_smp_fit_host or gf_smp_model_fit_host.
 // kind 0: BatchLearn(nBatch, ..., nIterations, learning_rate, epsilon), 1: Learn(...); optimiser 0: Adam, 1: Momentum(gamma).
 template <class Handle>

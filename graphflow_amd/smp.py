@@ -133,19 +133,45 @@ class SMPOmega:
         return params
 
     def adam_reset(self):
+        """zero state for every optimiser of the handle, and no recorded kind"""
         self.ctx.check(self.lib.gf_smp_adam_reset(self.handle))
+
+    def optimiser_step(self, params, grads, kind, learning_rate, nBatch, gamma=0.9, beta1=0.0, beta2=0.0, rho=0.0, epsilon=0.0):
+        """sgd->Learn(learning_rate, nBatch) for kind "adam", "momentum", "sgd", "adamax" or "adadelta" (or gf_optim_config's number);
+        constants left at 0 are the classes' defaults.  A kind other than the handle's last one is refused until adam_reset()."""
+        self._flat(params, "params")
+        self._flat(grads, "grads")
+        cfg = _lib.OptimConfig(_lib.OPTIMISERS.get(kind, kind), int(nBatch), float(learning_rate), float(gamma), float(beta1), float(beta2),
+                               float(rho), float(epsilon))
+        self.ctx.check(self.lib.gf_smp_optimiser_step(self.handle, C.c_void_p(params.data_ptr()), C.c_void_p(grads.data_ptr()), C.byref(cfg)))
+        return params
+
+    def regularise(self, params, grads, norm, lam, times=1):
+        """L1Regularization (norm 1) / L2Regularization (norm 2): grads += times * the term of backward(); returns the value"""
+        self._flat(params, "params")
+        self._flat(grads, "grads")
+        value = C.c_double(0.0)
+        self.ctx.check(self.lib.gf_smp_regularise(self.handle, C.c_void_p(params.data_ptr()), C.c_void_p(grads.data_ptr()), int(norm), float(lam),
+                                                  int(times), C.byref(value)))
+        return value.value
+
+    def param_blocks(self):
+        """offsets [blocks + 1] of the blocks the class registers with sgd->add, into the flat parameter vector"""
+        if getattr(self, "nClass", 0):
+            return _lib.param_blocks("gf_smp_classifier_config_param_blocks", C.byref(self.cfg), self.nClass)
+        return _lib.param_blocks("gf_smp_config_param_blocks", C.byref(self.cfg))
 
     def fit(self, params, grads, targets, nIterations, learning_rate, epsilon=0.0, kind=0, optimiser="adam", gamma=0.9):
         """The classes' iterative training calls on the prepared batch (gf_smp_fit): kind 0 = BatchLearn(nBatch, molecule, target,
-        nIterations, learning_rate, epsilon), kind 1 = Learn(molecule, target, ...) on a batch of one sample.  optimiser "adam" or
-        "momentum" (with gamma).  targets: one float32 per sample on the device (None for the Gram auto-encoder).  Returns (report,
-        decisions): the dict of gf_smp_fit_report and one entry per iteration run -- 1 kept, 2 restored, 3 restored and left, 4 left on
-        error < epsilon."""
+        nIterations, learning_rate, epsilon), kind 1 = Learn(molecule, target, ...) on a batch of one sample.  optimiser "adam",
+        "momentum" (with gamma), "sgd", "adamax" or "adadelta" (the classes' default constants).  targets: one float32 per sample on the
+        device (None for the Gram auto-encoder).  Returns (report, decisions): the dict of gf_smp_fit_report and one entry per iteration
+        run -- 1 kept, 2 restored, 3 restored and left, 4 left on error < epsilon."""
         self._flat(params, "params")
         self._flat(grads, "grads")
-        if optimiser not in ("adam", "momentum"):
-            raise ValueError("fit: optimiser %r (\"adam\" or \"momentum\")" % (optimiser,))
-        cfg = _lib.FitConfig(int(kind), 1 if optimiser == "momentum" else 0, int(nIterations), float(learning_rate), float(epsilon), float(gamma))
+        if optimiser not in _lib.OPTIMISERS:
+            raise ValueError("fit: optimiser %r (one of %s)" % (optimiser, ", ".join(sorted(_lib.OPTIMISERS))))
+        cfg = _lib.FitConfig(int(kind), _lib.OPTIMISERS[optimiser], int(nIterations), float(learning_rate), float(epsilon), float(gamma))
         rep = _lib.FitReport()
         log = (C.c_ubyte * max(1, int(nIterations)))()
         t = C.c_void_p(targets.data_ptr()) if targets is not None else None
@@ -903,13 +929,37 @@ class SMPModel:
         self._adam[2] = n + self.n_params
         return params
 
-    def fit(self, params, grads, targets, nIterations, learning_rate, epsilon=0.0, kind=0):
-        """The classes' iterative training calls (gf_smp_model_fit; see SMPOmega.fit) with Adam, whose moments live in the HANDLE here --
-        not those of adam_step().  Returns (report, decisions)."""
+    def _flat(self, params, grads):
         for t, name in ((params, "params"), (grads, "grads")):
             if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == self.n_params):
                 raise TypeError("%s must be a contiguous float32 CUDA tensor of %d elements" % (name, self.n_params))
-        cfg = _lib.FitConfig(int(kind), 0, int(nIterations), float(learning_rate), float(epsilon), 0.0)
+
+    def optimiser_step(self, params, grads, kind, learning_rate, nBatch, gamma=0.9, beta1=0.0, beta2=0.0, rho=0.0, epsilon=0.0):
+        """SMPOmega.optimiser_step on the composite handle; the state lives in the HANDLE (kind "adam": not adam_step()'s moments), and
+        the handle keeps the kind of its first step"""
+        self._flat(params, grads)
+        cfg = _lib.OptimConfig(_lib.OPTIMISERS.get(kind, kind), int(nBatch), float(learning_rate), float(gamma), float(beta1), float(beta2),
+                               float(rho), float(epsilon))
+        self.ctx.check(self.lib.gf_smp_model_optimiser_step(self.handle, C.c_void_p(params.data_ptr()), C.c_void_p(grads.data_ptr()), C.byref(cfg)))
+        return params
+
+    def regularise(self, params, grads, norm, lam, times=1):
+        self._flat(params, grads)
+        value = C.c_double(0.0)
+        self.ctx.check(self.lib.gf_smp_model_regularise(self.handle, C.c_void_p(params.data_ptr()), C.c_void_p(grads.data_ptr()), int(norm),
+                                                        float(lam), int(times), C.byref(value)))
+        return value.value
+
+    def param_blocks(self):
+        return _lib.param_blocks("gf_smp_model_config_param_blocks", C.byref(self.cfg))
+
+    def fit(self, params, grads, targets, nIterations, learning_rate, epsilon=0.0, kind=0, optimiser="adam"):
+        """The classes' iterative training calls (gf_smp_model_fit; see SMPOmega.fit) with Adam -- or "sgd", "adamax", "adadelta" --, whose
+        state lives in the HANDLE here, not with adam_step().  Returns (report, decisions)."""
+        self._flat(params, grads)
+        if optimiser not in _lib.OPTIMISERS:
+            raise ValueError("fit: optimiser %r (one of %s)" % (optimiser, ", ".join(sorted(_lib.OPTIMISERS))))
+        cfg = _lib.FitConfig(int(kind), _lib.OPTIMISERS[optimiser], int(nIterations), float(learning_rate), float(epsilon), 0.0)
         rep = _lib.FitReport()
         log = (C.c_ubyte * max(1, int(nIterations)))()
         self.ctx.check(self.lib.gf_smp_model_fit(self.handle, C.c_void_p(params.data_ptr()), C.c_void_p(grads.data_ptr()),

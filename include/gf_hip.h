@@ -528,6 +528,14 @@ gf_status gf_smp_create(gf_ctx *ctx, const gf_smp_config *cfg, gf_smp **out);
 size_t    gf_smp_config_param_count(const gf_smp_config *cfg);
 /* ... of the handle gf_smp_create_classifier would build from (cfg, nClass); 0 on what it would refuse.  Host only. */
 size_t    gf_smp_classifier_config_param_count(const gf_smp_config *cfg, int nClass);
+/* The parameter-block table, host only: the blocks the model class registers with sgd->add (e.g. GraphFlow/SMP_omega.h:289-295: H; K_l, b_l
+ * per level; W), in that order, as offsets into the flat parameter vector.  Returns the number of blocks and writes count + 1 ascending
+ * offsets -- the last one is the parameter count -- when `capacity` >= count + 1; a smaller capacity (or NULL offsets) returns the count
+ * and writes nothing; a configuration the create call refuses returns 0.  The table follows sgd->add where that differs from the blocks
+ * weights_initialization draws: the distance classes register W1^v_0 and W1^d_0 one by one (GCN_1D_Distance.h:168-169).  AdaMax keeps
+ * one infinity norm per block of this table. */
+size_t    gf_smp_config_param_blocks(const gf_smp_config *cfg, size_t *offsets, size_t capacity);
+size_t    gf_smp_classifier_config_param_blocks(const gf_smp_config *cfg, int nClass, size_t *offsets, size_t capacity);
 gf_status gf_smp_destroy(gf_smp *smp);
 size_t    gf_smp_param_count(const gf_smp *smp);
 /* The `_classification` models: SMP_2D_ver6_classification (nContractions 10, custom_matmul 1) and SMP_2D_ver7_classification (50, 1) of
@@ -898,6 +906,37 @@ gf_status gf_smp_adam_reset(gf_smp *smp);   /* zeroes the moment buffers (Adam a
 /* Momentum::Learn(learning_rate, nBatch) (GraphFlow/Momentum.h:64-71), the optimiser of SMP_2D_ver6-8
  * (SMP_2D_ver6.h:204, :593): m = gamma m + learning_rate * grads / nBatch, params -= m. */
 gf_status gf_smp_momentum_step(gf_smp *smp, float *params, const float *grads, double learning_rate, int nBatch, double gamma);
+/* sgd->Learn(learning_rate, nBatch) for any of the reference's five optimisers over the same flat vector -- what a reference user gets by
+ * changing the type of the model's `sgd` member.  All arithmetic in double on fp32 storage, each expression in the reference's order
+ * (g = gradient / nBatch is a division); a state value the reference reads back after storing it is read back as stored (fp32).
+ *   kind 0  Adam       gf_smp_adam_step's launch, bit for bit
+ *   kind 1  Momentum   gf_smp_momentum_step's launch, bit for bit (gamma)
+ *   kind 2  SGD        SGD::Learn(lr, nBatch), SGD.h:44-50: p -= lr * g / nBatch.  No state.
+ *   kind 3  AdaMax     AdaMax::Learn(alpha, nBatch), AdaMax.h:97-122: beta1_t *= beta1 once per call (a host double in the handle); per
+ *                      registered block b (gf_smp_config_param_blocks): first_order = beta1 first_order + (1 - beta1) g, infinity_norm[b] =
+ *                      max(beta2 infinity_norm[b], max_j |g_j|), p -= alpha / (1 - beta1_t) * first_order / infinity_norm[b].
+ *                      A block whose gradient is all zero while its norm is still 0 divides 0 by 0 in the reference, and here: the
+ *                      block's parameters become NaN (and stay NaN); no other block is touched.  Per-size blocks of sizes a batch never
+ *                      shows hit it -- in the class as well.
+ *   kind 4  AdaDelta   AdaDelta::Learn(alpha, nBatch), AdaDelta.h:90-112: E[g^2], E[dx^2] per element; learning_rate is not read.
+ * nBatch = 1 is Learn(alpha) for kinds 2 to 4 (the overloads differ by a division by 1).  The two fp32 state buffers are the ones Adam and
+ * Momentum use, so the handle remembers the kind of its last step (the older step calls and gf_smp_fit record theirs and never refuse):
+ * a different kind here is GF_ERR_INVALID until gf_smp_adam_reset, which also clears AdaMax's norms and beta1_t.  NULL cfg, a kind
+ * outside 0 .. 4 and nBatch <= 0 are GF_ERR_INVALID. */
+typedef struct {
+    int kind;              /* 0 Adam, 1 Momentum, 2 SGD, 3 AdaMax, 4 AdaDelta: gf_smp_fit_config.optimiser's numbering */
+    int nBatch;
+    double learning_rate;
+    double gamma;          /* Momentum */
+    double beta1, beta2;   /* AdaMax; 0, 0 = 0.9, 0.999 (AdaMax.h:26-29) */
+    double rho, epsilon;   /* AdaDelta; 0, 0 = 0.95, 1e-6 (AdaDelta.h:26-28) */
+} gf_optim_config;
+gf_status gf_smp_optimiser_step(gf_smp *smp, float *params, const float *grads, const gf_optim_config *cfg);
+/* L1Regularization (L1Regularization.h:39-67; sign() is 0 for |p| < 1e-8) and L2Regularization (L2Regularization.h:39-58) over every
+ * registered parameter: *value_host = lambda * sum |p| (norm 1) or lambda * sum p^2 (norm 2), summed in double in a fixed two-stage shape
+ * (the same bits on every run), and grads[i] += times * (lambda sign(p_i) | 2 lambda p_i): `times` = how often the class's backward()
+ * would have run since the gradient was last zeroed, the batch size for a BatchLearn step.  Blocking.  The fit loops do not regularise. */
+gf_status gf_smp_regularise(gf_smp *smp, const float *params, float *grads, int norm, double lambda, int times, double *value_host);
 /* The classes' CacheParameters (GraphFlow/CacheParameters.h:45-59): a device-to-device copy of the flat parameter buffer into
  * (snapshot) or out of (rollback) a cache the handle owns, allocated by the first snapshot.  params NULL: the handle-owned model.
  * Values only -- Momentum's velocity, Adam's moments and its element counter stay as they are, as in the classes.  Rollback before any
@@ -926,7 +965,7 @@ gf_status gf_smp_gram_host(gf_smp *smp, double *out);
  * forward before the next reverse sweep (and before it returns), so the handle is left forwarded at the parameters it is left with. */
 typedef struct {
     int kind;        /* 0: the BatchLearn overload, 1: Learn */
-    int optimiser;   /* 0: Adam, 1: Momentum with `gamma` */
+    int optimiser;   /* 0: Adam, 1: Momentum with `gamma`, 2: SGD, 3: AdaMax, 4: AdaDelta (the classes' default constants) */
     int nIterations;
     double learning_rate, epsilon, gamma;
 } gf_smp_fit_config;
@@ -988,6 +1027,16 @@ gf_status gf_smp_dropout_masks(gf_smp *smp, const unsigned *masks, float scale);
  * element i uses the bias-correction powers beta^(elements_before + i + 1), as the reference's per-element advance gives. */
 gf_status gf_adam_step_f32(gf_ctx *ctx, float *params, const float *grads, float *m, float *v, size_t n, double learning_rate,
                            int nBatch, unsigned long long elements_before);
+/* gf_smp_optimiser_step's kinds 2 to 4 on any flat device buffer with caller-owned state (other kinds: GF_ERR_INVALID).  state0 / state1
+ * (device, n floats): AdaMax's first_order / unused, AdaDelta's E[g^2] / E[dx^2]; SGD reads neither.  AdaMax also takes its blocks --
+ * block_offsets_host: nBlocks + 1 strictly ascending offsets from 0 to n, on the HOST --, block_norms (device, nBlocks doubles:
+ * infinity_norm) and *beta1_t_inout (host; 1.0 before the first step), which the call advances. */
+gf_status gf_optimiser_step_f32(gf_ctx *ctx, const gf_optim_config *cfg, float *params, const float *grads, size_t n,
+                                const size_t *block_offsets_host, int nBlocks, float *state0, float *state1, double *block_norms,
+                                double *beta1_t_inout);
+/* gf_smp_regularise on any flat device buffers.  norm 1 | 2, times >= 0.  Blocking. */
+gf_status gf_regularise_f32(gf_ctx *ctx, const float *params, float *grads, size_t n, int norm, double lambda, int times,
+                            double *value_host);
 
 /* ---- the `_physics` / `_pairgraphs` models as one handle ------------------------------------------------------
  * nTowers 1: SMP_omega_physics (GraphFlow/SMP_omega_physics.h:29-606) -- SMP_beta_physics with max_receptive_field =
@@ -1032,6 +1081,9 @@ typedef struct {
 gf_status gf_smp_model_create(gf_ctx *ctx, const gf_smp_model_config *cfg, gf_smp_model **out);
 /* host only: the parameter count gf_smp_model_create gives the configuration, 0 for one it refuses */
 size_t    gf_smp_model_config_param_count(const gf_smp_model_config *cfg);
+/* gf_smp_config_param_blocks for a composite model: H of every tower; per level, tower by tower, the level's blocks; the head's W1, W2
+ * (, W3) (SMP_omega_pairgraphs.h:361-375, CCN_1D.h:381-403).  Host only. */
+size_t    gf_smp_model_config_param_blocks(const gf_smp_model_config *cfg, size_t *offsets, size_t capacity);
 gf_status gf_smp_model_destroy(gf_smp_model *model);
 size_t    gf_smp_model_param_count(const gf_smp_model *model);
 gf_status gf_smp_model_set_mode(gf_smp_model *model, int train);   /* SMP_sigma_pairgraphs::setMode (:139-149); default train */
@@ -1048,8 +1100,14 @@ gf_status gf_smp_model_parameters_upload(gf_smp_model *model, const float *host_
 gf_status gf_smp_model_parameters_download(gf_smp_model *model, float *host_params, float *host_grads);
 gf_status gf_smp_model_forward_host(gf_smp_model *model, const double *targets, double *predict, double *loss);
 gf_status gf_smp_model_adam_step(gf_smp_model *model, double learning_rate, int nBatch);
+/* gf_smp_optimiser_step / gf_smp_regularise on the composite handle's flat vector (NULL params / grads: the handle-owned model).  Kind 0
+ * leaves the bits of gf_smp_model_adam_step; kind 1 (Momentum) is available here although no composite class uses it.  The composite
+ * handle has no reset call: it keeps the kind of its first step. */
+gf_status gf_smp_model_optimiser_step(gf_smp_model *model, float *params, const float *grads, const gf_optim_config *cfg);
+gf_status gf_smp_model_regularise(gf_smp_model *model, const float *params, float *grads, int norm, double lambda, int times,
+                                  double *value_host);
 /* gf_smp_parameters_snapshot / _rollback and gf_smp_fit / gf_smp_fit_host for the composite handle, over the whole registration-order
- * vector.  The composite classes train with Adam: optimiser = 1 is GF_ERR_UNSUPPORTED.  With device pointers the Adam moments are the
+ * vector.  The composite classes train with Adam: optimiser = 1 is GF_ERR_UNSUPPORTED (2, 3 and 4 are accepted).  With device pointers the Adam moments are the
  * handle's (those of gf_smp_model_adam_step). */
 gf_status gf_smp_model_parameters_snapshot(gf_smp_model *model, const float *params);
 gf_status gf_smp_model_parameters_rollback(gf_smp_model *model, float *params);
